@@ -30,6 +30,9 @@ Two ways to get N ranks (one process per GPU, BASELINE.json configs
     processes (RANK/LOCAL_RANK/WORLD_SIZE/MASTER_* set, seeds 10..10+N-1) before anything touches a GPU,
     relays rank 0's JSON line and exits non-zero unless that line reports ``n_gpus == N``.
 A rank never re-executes itself; on failure it exits non-zero and the launcher stops the others.
+
+``--dump-outputs DIR`` writes what the headline's last timed step returned (a seeded sample of its magnitude frames) as
+``DIR/<name>.npy``; the inputs depend on the arguments only, so two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -216,6 +219,12 @@ class StubDevice:
     def host_us_per_call(self, n=8):
         return 10.0 * (1 + self.rank)
 
+    def finish_rotation(self):
+        pass
+
+    def output_sample(self, rows):
+        return {}
+
     def close(self):
         pass
 
@@ -254,6 +263,22 @@ class GpuWorkload:
         i = self.step_no % self.R
         self.step_no += 1
         self.ch.process_f32(self.xs[i], out=self.outs[i])
+
+    def finish_rotation(self):
+        """Untimed steps up to the end of the current round of buffer pairs, then a synchronisation: the next step uses
+        pair 0, so the pair a region of W + K steps ends on does not depend on how many steps a time-bounded loop made
+        before it (the next pair is the least recently used one either way)."""
+        while self.step_no % self.R:
+            self.step()
+        self.sync()
+
+    def output_sample(self, rows):
+        """{name: host array} of what the last step returned to its caller: the magnitudes of `rows` frames of its
+        output batch, drawn without replacement by a fixed seed (the whole batch is B x 64 KiB).  Call after sync()."""
+        i = (self.step_no - 1) % self.R
+        idx = np.sort(np.random.default_rng(0).choice(self.B, size=min(rows, self.B), replace=False))
+        sel = self.torch.as_tensor(idx, device=self.dev)
+        return {"magnitude": self.outs[i].index_select(0, sel).cpu().numpy()}
 
     def set_overlap(self, depth):
         """Launches of the handle kept in flight (include/specan.h, sa_set_overlap).  The rotating buffer pairs
@@ -580,9 +605,15 @@ def main():
     ap.add_argument("--no-configs", action="store_true",
                     help="skip the `configs` block (BASELINE.json configs[1] and configs[3] beside the headline; N = 1 only)")
     ap.add_argument("--extras", action="store_true", help="also time the bypass (config 2) and Q15 (config 4) paths")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one returned as DIR/<name>.npy (float32): the "
+                         "magnitudes of a fixed, seeded sample of its frames, 512 frames (32 MiB) over all ranks; "
+                         "the same arguments give the same inputs")
     a = ap.parse_args()
     if a.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if not 1 <= a.overlap <= 4:
         ap.error("--overlap must be 1..4")
 
@@ -659,7 +690,10 @@ def main():
         for _ in range(10):
             wl.step()
         wl.sync()
+    wl.finish_rotation()
     fps_total, elapsed = timed_region()                                  # the headline
+    # what the headline's last step computed, copied out before any later step reuses its buffers
+    dump = wl.output_sample(max(1, 512 // world)) if a.dump_outputs else {}
 
     # strictly stream-ordered mode: wall (same contract) and per-launch kernel time with HIP events on the launch
     # stream, same number of steps -- what rocprofv3 --kernel-trace shows for `--overlap 1`
@@ -695,6 +729,11 @@ def main():
             power["mj_per_step"] = round(power["socket_w"] * elapsed / a.steps * 1e3, 1)
 
     extras = wl.extras(a.steps, a.overlap > 1) if (a.extras and rank == 0 and not stub) else {}
+
+    if a.dump_outputs and dump:
+        os.makedirs(a.dump_outputs, exist_ok=True)
+        for name, arr in dump.items():
+            np.save(os.path.join(a.dump_outputs, f"{name}_rank{rank}.npy" if world > 1 else f"{name}.npy"), arr)
 
     if rank == 0:
         # HBM traffic per launch: FETCH_SIZE (doubled, gfx950) + WRITE_SIZE from the committed separate

@@ -680,3 +680,38 @@ def test_control_plane_refused_during_capture_changes_nothing(ch, torch_mod, ora
     ch.load_sos(other)                                               # ... and control-plane calls work again
     _, _, mag = oracle.chain_fp(x.cpu().numpy(), other)
     assert rel_maxnorm(ch.process_f32(x).cpu().numpy(), mag) <= TOL
+
+
+def test_bench_dump_outputs(tmp_path, torch_mod, oracle):
+    """bench.py --dump-outputs writes what the headline's last timed step returned (a seeded 512-frame sample of its
+    magnitudes, float32): the same arguments give the same file, and it is the oracle's chain of the inputs that step
+    read (regenerated here from the bench's own seeded set-up: pair (W + K - 1) mod R of B = 1024 frames)."""
+    import argparse
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    B, R, W, K = 1024, 4, 2, 5
+    dumps = []
+    for run in range(2):
+        d = tmp_path / f"run{run}"
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", str(K),
+                            "--warmup", str(W), "--batch", str(B), "--buffers", str(R), "--no-cpu-baseline",
+                            "--no-power", "--no-configs", "--dump-outputs", str(d)],
+                           cwd=root, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr
+        line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+        assert line["steps"] == K and line["ms_per_step"] > 0
+        assert sorted(os.listdir(d)) == ["magnitude.npy"]
+        dumps.append(np.load(d / "magnitude.npy"))
+    assert dumps[0].dtype == np.float32 and dumps[0].shape == (512, N) and dumps[0].nbytes <= 64 << 20
+    assert np.array_equal(dumps[0], dumps[1])
+    import bench
+    wl = bench.GpuWorkload(argparse.Namespace(batch=B, buffers=R), 0, 0, load_golden("g2_config1.npz")["sos"])
+    try:
+        idx = np.sort(np.random.default_rng(0).choice(B, size=512, replace=False))
+        x = wl.xs[(W + K - 1) % R][torch_mod.as_tensor(idx, device=wl.dev)].cpu().numpy()
+    finally:
+        wl.close()
+    _, _, ref = oracle.chain_fp(x, load_golden("g2_config1.npz")["sos"])
+    assert rel_maxnorm(dumps[0], ref) <= TOL
