@@ -17,7 +17,8 @@ import torch
 
 from . import abi
 from .abi import (SA_FILTER_CUSTOM, SA_FILTER_DEFAULT, SA_FILTER_NONE, SA_FILTER_WIDE, SA_N,
-                  SA_OUT_MAG_FULL, SA_OUT_MAG_HALF, SA_OUT_SPEC_HALF, SA_OUT_TIME, SpecanError)
+                  SA_OUT_MAG_FULL, SA_OUT_MAG_HALF, SA_OUT_SPEC_HALF, SA_OUT_TIME, SA_PRECISION_F32,
+                  SA_PRECISION_F64_STATE, SpecanError)
 
 # command bytes, same names as gui.py:28-37
 UART_REQUEST_CMD = 0xA5
@@ -38,6 +39,7 @@ FS_HZ = 1_000_000.0             # gui.py:45
 
 _OUT_KINDS = {"mag_full": SA_OUT_MAG_FULL, "mag_half": SA_OUT_MAG_HALF, "spec_half": SA_OUT_SPEC_HALF,
               "time": SA_OUT_TIME}
+_PRECISIONS = {"f32": SA_PRECISION_F32, "f64": SA_PRECISION_F64_STATE}
 
 
 class SpectrumChain:
@@ -270,6 +272,28 @@ class SpectrumChain:
         self._lib.sa_debug_iir_plan_f32(self._h, out.ctypes.data_as(C.POINTER(C.c_float)), n)
         return out
 
+    def set_precision(self, precision: str):
+        """'f32' (the default) or 'f64': window, inter-section signal and cascade of the float path in float64
+        (include/specan.h, sa_set_precision).  Applies to later :meth:`process_f32` calls in filter modes 0x00 and 0xA1."""
+        if precision not in _PRECISIONS:
+            raise SpecanError(abi.SA_EINVAL, f"precision must be one of {sorted(_PRECISIONS)}")
+        self._ctl(self._lib.sa_set_precision(self._h, _PRECISIONS[precision]))
+
+    @property
+    def precision(self) -> str:
+        v = C.c_int()
+        self._check(self._lib.sa_get_precision(self._h, C.byref(v)))
+        return {code: name for name, code in _PRECISIONS.items()}[v.value]
+
+    def iir_plan_f64(self) -> np.ndarray:
+        """The float64 plan the handle would launch in its current filter mode (sa_debug_iir_plan_f64)."""
+        n = self._lib.sa_debug_iir_plan_f64(self._h, None, 0)
+        if n < 0:
+            self._check(n)
+        out = np.zeros(n, np.float64)
+        self._lib.sa_debug_iir_plan_f64(self._h, out.ctypes.data_as(C.POINTER(C.c_double)), n)
+        return out
+
     # ------------------------------------------------------------------ data plane
     def process_f32(self, x: torch.Tensor, out: Optional[torch.Tensor] = None, out_kind: str = "mag_full",
                     scale: float = 1.0 / 2048.0):
@@ -344,6 +368,19 @@ def iir_plan_from_sos(sos) -> np.ndarray:
     out = np.zeros(n, np.float32)
     L.sa_iir_plan_from_sos(s.ctypes.data_as(C.POINTER(C.c_double)), s.shape[0],
                            out.ctypes.data_as(C.POINTER(C.c_float)), n)
+    return out
+
+
+def iir_plan_f64_from_sos(sos) -> np.ndarray:
+    """Host-only: the float64-state plan (no GPU needed); see include/specan.h sa_iir_plan_from_sos_f64."""
+    L = abi.lib()
+    s = np.ascontiguousarray(np.asarray(sos, np.float64).reshape(-1, 6))
+    n = L.sa_iir_plan_from_sos_f64(s.ctypes.data_as(C.POINTER(C.c_double)), s.shape[0], None, 0)
+    if n < 0:
+        raise SpecanError(n, "sa_iir_plan_from_sos_f64: bad SOS")
+    out = np.zeros(n, np.float64)
+    L.sa_iir_plan_from_sos_f64(s.ctypes.data_as(C.POINTER(C.c_double)), s.shape[0],
+                               out.ctypes.data_as(C.POINTER(C.c_double)), n)
     return out
 
 

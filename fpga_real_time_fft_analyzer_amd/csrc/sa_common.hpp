@@ -79,6 +79,26 @@ struct SaIirLaneTab {
     float win_t[SA_NPTS];
 };
 
+// Float64-state IIR plan (SA_PRECISION_F64_STATE, iir_f64.hip): the same predict / scan / recurse form as SaIirK, in
+// double and in the DF2T coordinates of scipy.signal.sosfilt (at 2^-53 the growth of the powers of A for poles next to
+// the real axis costs nothing that matters, so there is no pole-coordinate transform and no unit-numerator rewrite).
+// Built from the double SOS of the handle, padded with identity sections to 0, 2, 4 or 6 like SaIirK.  Lives in device
+// memory (7 KiB: too large for the kernel arguments); every matrix is row-major {m00, m01, m10, m11}.
+struct SaIirSecF64 {
+    double c[6];           // b0, b1, b2, a1, a2, 0
+    double m[16][2];       // predictor taps m[j] = A^(15-j) Bv of a half chunk (block Horner, as SaIirSecK::mnext)
+    double p16[4];         // A^16
+    double pc[4];          // A^32: one chunk
+    double plev[4][4];     // A^(64 * 2^k), k = 0..3: in-row scan levels (one thread = two chunks = 64 samples)
+    double prow[4][4];     // A^(1024 * 2^k): scan over the 16 row totals
+    double lane[16][4];    // A^(64 i): start-state injection for lane i of a 16-lane row
+};
+struct SaIirF64 {
+    double hdr[4];         // hdr[0] = padded section count (0, 2, 4, 6); the rest 0
+    SaIirSecF64 sec[SA_MAXSEC];
+};
+constexpr int kSaIirF64Doubles = (int)(sizeof(SaIirF64) / sizeof(double));
+
 // Integer-path parameters passed by value (kernarg => stream-ordered for free).
 struct SaQ15Params {
     int win_mode;          // SA_WIN_*
@@ -121,6 +141,13 @@ hipError_t sa_launch_chain_f32(const float *in, void *out, int batch, int out_ki
 // the same chain on int16 samples (chain_f32_i16.hip): x = float(sample) * in_scale, then exactly the float32 path
 hipError_t sa_launch_chain_f32_i16(const int16_t *in, float in_scale, void *out, int batch, int out_kind, const SaF32Tables &t,
                                    hipStream_t stream, SaLaunchEv ev);
+
+// Float64-state cascade (iir_f64.hip): window and cascade of the frame in double, y rounded once to float32 into
+// out [B,16384] (the workspace of the FFT launch, or the SA_OUT_TIME output itself).  `in` is float32 frames, or int16
+// samples when in_i16 (x = float(sample) * in_scale rounded to float32 first, as on the float32 path).
+//   plan: device SaIirF64 whose hdr[0] == nsec;  win_tr: device [32][256][2] doubles, win_tr[g][t] = w[64t + 2g], w[..+1]
+hipError_t sa_launch_iir_f64(const void *in, bool in_i16, float in_scale, float *out, int batch, int nsec,
+                             const SaIirF64 *plan, const double *win_tr, hipStream_t stream, SaLaunchEv ev);
 
 struct SaQ15Tables {
     const int16_t *rom;        // [16384] window ROM

@@ -216,6 +216,63 @@ void sos_from_q7(const int8_t *c12, double *sos /*[6][6]*/)
     }
 }
 
+
+inline void put_rm(double *dst, const Mat2 &m)      // row-major
+{
+    dst[0] = m.a; dst[1] = m.b; dst[2] = m.c; dst[3] = m.d;
+}
+
+// The float64-state plan (SaIirF64, iir_f64.hip) of an a0-normalised SOS: DF2T coordinates, no unit-numerator rewrite,
+// shorter cascades padded with identity sections (b0 = 1, rest 0: y = x exactly, every tap and power >= 2 is zero).
+void build_plan_f64(const double *sos_in, int nsec_in, SaIirF64 *p)
+{
+    std::memset(p, 0, sizeof(*p));
+    const int nsec = nsec_in == 0 ? 0 : (nsec_in <= 2 ? 2 : (nsec_in <= 4 ? 4 : 6));
+    p->hdr[0] = (double)nsec;
+    for (int s = 0; s < nsec; ++s) {
+        const double ident[6] = {1, 0, 0, 1, 0, 0};
+        const double *r = s < nsec_in ? sos_in + 6 * s : ident;
+        const double b0 = r[0], b1 = r[1], b2 = r[2], a1 = r[4], a2 = r[5];
+        SaIirSecF64 &k = p->sec[s];
+        k.c[0] = b0; k.c[1] = b1; k.c[2] = b2; k.c[3] = a1; k.c[4] = a2;
+        const Mat2 A = {-a1, 1.0, -a2, 0.0};
+        double v0 = b1 - a1 * b0, v1 = b2 - a2 * b0;          // Bv
+        for (int j = 15; j >= 0; --j) {                       // m[j] = A^(15-j) Bv
+            k.m[j][0] = v0;
+            k.m[j][1] = v1;
+            const double n0 = A.a * v0 + A.b * v1, n1 = A.c * v0 + A.d * v1;
+            v0 = n0; v1 = n1;
+        }
+        put_rm(k.p16, mpow(A, 16));
+        const Mat2 Pc = mpow(A, SA_CHUNK);
+        put_rm(k.pc, Pc);
+        const Mat2 P2 = mul(Pc, Pc);
+        Mat2 q = P2, qr = mpow(P2, 16);
+        for (int i = 0; i < 4; ++i) {
+            put_rm(k.plev[i], q);
+            put_rm(k.prow[i], qr);
+            q = mul(q, q);
+            qr = mul(qr, qr);
+        }
+        Mat2 pw = {1, 0, 0, 1};
+        for (int i = 0; i < 16; ++i) {
+            put_rm(k.lane[i], pw);
+            pw = mul(pw, P2);
+        }
+    }
+}
+
+// a0-normalised copy of a caller's SOS; false on a bad a0 (the checks of sa_load_sos_f64 / sa_iir_plan_from_sos)
+bool normalise_a0(const double *sos, int n_sections, double *norm /*[36]*/)
+{
+    for (int s = 0; s < n_sections; ++s) {
+        const double a0 = sos[6 * s + 3];
+        if (a0 == 0.0 || !std::isfinite(a0)) return false;
+        for (int i = 0; i < 6; ++i) norm[6 * s + i] = sos[6 * s + i] / a0;
+    }
+    return true;
+}
+
 }  // namespace
 
 hipError_t sa_set_dyn_lds_once(const void *kernel, int bytes)
@@ -268,6 +325,16 @@ struct sa_handle {
     int16_t *d_work[kMaxOverlap] = {nullptr, nullptr, nullptr, nullptr};
     int work_frames[kMaxOverlap] = {0, 0, 0, 0};
     std::vector<void *> retired;
+    int reserved_max = 0;                  // largest batch passed to sa_reserve so far
+    // ---- float64-state IIR (opt-in, sa_set_precision): everything below is allocated by the first
+    // sa_set_precision(F64_STATE) and kept up to date only while the handle is in that mode (re-synced on entry)
+    int precision = SA_PRECISION_F32;
+    std::vector<double> win64;             // the window in double, natural order: default Hann or the caller's table widened
+    SaIirF64 *d_p64_default = nullptr, *d_p64_custom = nullptr;
+    double *d_win64 = nullptr;             // win64 transposed for iir_f64.hip: [32][256] pairs, pair (g, t) = w[64t + 2g], w[..+1]
+    float4 *d_win_half = nullptr;          // constant 1/2 (the split step's factor) in the pass-A layout: the FFT launch's window
+    float *d_work64[kMaxOverlap] = {nullptr, nullptr, nullptr, nullptr};   // float32 y [B,16384] per launch slot
+    int work64_frames[kMaxOverlap] = {0, 0, 0, 0};
     // ---- stream-ordered control plane (no device-wide synchronisation anywhere after sa_create)
     // Table uploads run on the handle's own control stream: it first waits for everything the handle has
     // launched so far, copies from a pinned staging slot, and records `uploaded`; the next process call makes its
@@ -590,6 +657,21 @@ int ensure_work(sa_handle *h, int slot, int frames, bool captured, bool geometri
     return SA_OK;
 }
 
+// The float32 workspace of the float64-state mode (iir_f64.hip output, FFT launch input); same growth rules as ensure_work
+int ensure_work64(sa_handle *h, int slot, int frames, bool captured, bool geometric = true)
+{
+    if (frames <= h->work64_frames[slot]) return SA_OK;
+    if (captured) return fail(h, SA_ESTATE, "workspace growth inside a stream capture: call sa_reserve() first");
+    long want = frames, geo = (long)h->work64_frames[slot] + h->work64_frames[slot] / 2;
+    if (geometric && geo > want) want = geo;
+    void *p = nullptr;
+    SA_HIP(h, hipMalloc(&p, (size_t)want * SA_NPTS * sizeof(float)));
+    if (h->d_work64[slot]) h->retired.push_back(h->d_work64[slot]);
+    h->d_work64[slot] = (float *)p;
+    h->work64_frames[slot] = (int)want;
+    return SA_OK;
+}
+
 void default_window_f64(std::vector<double> &w)
 {
     w.resize(SA_NPTS);
@@ -635,6 +717,30 @@ void pass_a_window(const std::vector<float> &half, std::vector<float> &pa)
 
 int rebuild_plans(sa_handle *h);
 
+// Device tables of the float64-state mode from the handle's double state: both plans (from the double SOS, never from
+// the float32 plan) and, with `window`, the double window.  Nothing unless the handle is in that mode or `force`.
+int sync_f64(sa_handle *h, bool window, bool force = false)
+{
+    if (h->precision != SA_PRECISION_F64_STATE && !force) return SA_OK;
+    SaIirF64 p;
+    double sos[36];
+    sos_from_q7(kDefaultQ7, sos);
+    build_plan_f64(sos, 6, &p);
+    int rc = upload(h, h->d_p64_default, &p, sizeof p);
+    if (rc != SA_OK) return rc;
+    build_plan_f64(h->sos_custom, h->nsec_custom, &p);
+    rc = upload(h, h->d_p64_custom, &p, sizeof p);
+    if (rc != SA_OK || !window) return rc;
+    std::vector<double> tr(SA_NPTS);
+    for (int t = 0; t < 256; ++t)
+        for (int g = 0; g < 32; ++g)
+            for (int e = 0; e < 2; ++e) tr[(g * 256 + t) * 2 + e] = h->win64[64 * t + 2 * g + e];
+    const size_t half = sizeof(double) * SA_NPTS / 2;     // two uploads: a staging slot holds 64 KiB, the table is 128
+    rc = upload(h, h->d_win64, tr.data(), half);
+    if (rc != SA_OK) return rc;
+    return upload(h, h->d_win64 + SA_NPTS / 2, tr.data() + SA_NPTS / 2, half);
+}
+
 int upload_window_half(sa_handle *h, const std::vector<float> &half)
 {
     std::vector<float> tr, pa;
@@ -676,6 +782,7 @@ int set_window_f32_from(sa_handle *h, const float *w)
     std::vector<float> half(SA_NPTS);
     for (int i = 0; i < SA_NPTS; ++i) half[i] = 0.5f * w[i];
     h->win_is_cos = fit_cosine_window(w, h->win_cos);
+    h->win64.assign(w, w + SA_NPTS);                    // widened exactly
     return upload_window_half(h, half);
 }
 
@@ -722,7 +829,9 @@ int set_custom_plan(sa_handle *h, const double *sos_norm, int nsec)
     h->nsec_custom = nsec;
     const double *cw = h->win_is_cos ? h->win_cos : nullptr;
     build_plan(h->sos_custom, nsec, &h->plan_custom, &h->lt_custom, h->half_win.data(), cw);
-    return upload(h, h->d_lt_custom, &h->lt_custom, sizeof(SaIirLaneTab));
+    const int rc = upload(h, h->d_lt_custom, &h->lt_custom, sizeof(SaIirLaneTab));
+    if (rc != SA_OK) return rc;
+    return sync_f64(h, false);
 }
 
 int rebuild_plans(sa_handle *h)
@@ -734,7 +843,9 @@ int rebuild_plans(sa_handle *h)
     int rc = upload(h, h->d_lt_default, &h->lt_default, sizeof(SaIirLaneTab));
     if (rc != SA_OK) return rc;
     build_plan(h->sos_custom, h->nsec_custom, &h->plan_custom, &h->lt_custom, h->half_win.data(), cw);
-    return upload(h, h->d_lt_custom, &h->lt_custom, sizeof(SaIirLaneTab));
+    rc = upload(h, h->d_lt_custom, &h->lt_custom, sizeof(SaIirLaneTab));
+    if (rc != SA_OK) return rc;
+    return sync_f64(h, true);               // rebuild_plans runs on every window change
 }
 
 }  // namespace
@@ -796,6 +907,7 @@ int sa_create(int device, sa_handle **out)
         transpose_window(half, tr);
         pass_a_window(half, pa);
         h->half_win = half;
+        h->win64 = w;
         SA_HIPC(hipMemcpy(h->d_win_b, pa.data(), sizeof(float) * SA_NPTS, hipMemcpyHostToDevice));
         SA_HIPC(hipMemcpy(h->d_win_t, tr.data(), sizeof(float) * SA_NPTS, hipMemcpyHostToDevice));
         std::vector<float4> ta(6 * 256), tb(8 * 16);
@@ -915,6 +1027,11 @@ int sa_destroy(sa_handle *h)
     (void)hipFree(h->d_twq);
     (void)hipFree(h->d_twrec);
     for (int i = 0; i < sa_handle::kMaxOverlap; ++i) (void)hipFree(h->d_work[i]);
+    for (int i = 0; i < sa_handle::kMaxOverlap; ++i) (void)hipFree(h->d_work64[i]);
+    (void)hipFree(h->d_p64_default);
+    (void)hipFree(h->d_p64_custom);
+    (void)hipFree(h->d_win64);
+    (void)hipFree(h->d_win_half);
     for (void *p : h->retired) (void)hipFree(p);
     delete h;
     return SA_OK;
@@ -925,8 +1042,10 @@ int sa_reserve(sa_handle *h, int max_batch)
     if (!h) return SA_EINVAL;
     if (max_batch < 0) return fail(h, SA_ESHAPE, "sa_reserve: negative batch");
     SA_HIP(h, hipSetDevice(h->device));
+    if (max_batch > h->reserved_max) h->reserved_max = max_batch;
     for (int i = 0; i < h->overlap; ++i) {
-        const int rc = ensure_work(h, i, max_batch, false);
+        int rc = ensure_work(h, i, max_batch, false);
+        if (rc == SA_OK && h->precision == SA_PRECISION_F64_STATE) rc = ensure_work64(h, i, max_batch, false);
         if (rc != SA_OK) return rc;
     }
     return SA_OK;
@@ -957,7 +1076,12 @@ int sa_set_overlap(sa_handle *h, int depth)
         // every slot starts with the workspace the handle already has somewhere
         int most = 0;
         for (int j = 0; j < sa_handle::kMaxOverlap; ++j) most = h->work_frames[j] > most ? h->work_frames[j] : most;
-        const int rc = ensure_work(h, i, most, false, /*geometric=*/false);
+        int rc = ensure_work(h, i, most, false, /*geometric=*/false);
+        if (rc == SA_OK && h->precision == SA_PRECISION_F64_STATE) {
+            int most64 = 0;
+            for (int j = 0; j < sa_handle::kMaxOverlap; ++j) most64 = h->work64_frames[j] > most64 ? h->work64_frames[j] : most64;
+            rc = ensure_work64(h, i, most64, false, /*geometric=*/false);
+        }
         if (rc != SA_OK) return rc;
     }
     h->overlap = depth;
@@ -1209,6 +1333,7 @@ int sa_set_window_f32(sa_handle *h, const float *w)
     for (int i = 0; i < SA_NPTS; ++i) half[i] = (float)(0.5 * d[i]);
     h->win_is_cos = true;
     h->win_cos[0] = h->win_cos[1] = 0.5;                  // scripts/hann_coeff.py:3-4
+    h->win64 = d;
     return upload_window_half(h, half);
 }
 
@@ -1281,6 +1406,40 @@ int sa_process_q15(sa_handle *h, const int16_t *in, int16_t *out_iq, int batch, 
     return end_call(h, c);
 }
 
+// SA_PRECISION_F64_STATE with a cascade (DEFAULT, or CUSTOM with at least one section): the plan the first launch uses
+// and its padded section count; null when the call takes the float32 path (every other case, filter NONE included).
+static const SaIirF64 *f64_plan(const sa_handle *h, int *nsec)
+{
+    if (h->precision != SA_PRECISION_F64_STATE) return nullptr;
+    if (h->filter_mode == SA_FILTER_DEFAULT) {
+        *nsec = h->plan_default.nsec;
+        return h->d_p64_default;
+    }
+    if (h->filter_mode == SA_FILTER_CUSTOM && h->plan_custom.nsec > 0) {
+        *nsec = h->plan_custom.nsec;
+        return h->d_p64_custom;
+    }
+    return nullptr;
+}
+
+// The float64-state call: iir_f64.hip (window + cascade in double, y rounded once) into the slot's workspace, then the
+// bypassed float chain on y with the constant 1/2 window (exact).  SA_OUT_TIME is the first launch alone, into `out`.
+// Timed as one call: the start event rides on the first kernel, the stop event on the last.
+static int launch_f64(sa_handle *h, const void *in, bool i16, float scale, void *out, int batch, int out_kind,
+                      const CallCtx &c, const SaIirF64 *plan, int nsec)
+{
+    if (out_kind == SA_OUT_TIME) {
+        SA_HIP(h, sa_launch_iir_f64(in, i16, scale, (float *)out, batch, nsec, plan, h->d_win64, c.stream, {c.start, c.stop}));
+        return end_call(h, c);
+    }
+    { const int rc = ensure_work64(h, c.slot, batch, c.captured); if (rc != SA_OK) return rc; }
+    float *ws = h->d_work64[c.slot];
+    SA_HIP(h, sa_launch_iir_f64(in, i16, scale, ws, batch, nsec, plan, h->d_win64, c.stream, {c.start, nullptr}));
+    const SaF32Tables t = {h->d_win_half, h->d_win_t, h->d_twT, h->d_twB, h->d_twC, h->d_lt_custom, nullptr};
+    SA_HIP(h, sa_launch_chain_f32(ws, out, batch, out_kind, t, c.stream, {nullptr, c.stop}));
+    return end_call(h, c);
+}
+
 int sa_process_f32(sa_handle *h, const float *in, void *out, int batch, int out_kind, void *stream)
 {
     if (!h) return SA_EINVAL;
@@ -1293,6 +1452,8 @@ int sa_process_f32(sa_handle *h, const float *in, void *out, int batch, int out_
     SA_HIP(h, hipSetDevice(h->device));
     CallCtx c;
     { const int rc = begin_call(h, (hipStream_t)stream, &c); if (rc != SA_OK) return rc; }
+    int nsec64 = 0;
+    if (const SaIirF64 *p64 = f64_plan(h, &nsec64)) return launch_f64(h, in, false, 1.f, out, batch, out_kind, c, p64, nsec64);
     // The section coefficients and predictor taps travel by value in the kernel arguments (stream-ordered
     // by construction); the per-lane matrices and the window live in device memory (stream-ordered uploads).
     SaF32Tables t = {h->d_win_b, h->d_win_t, h->d_twT, h->d_twB, h->d_twC, h->d_lt_custom, nullptr};
@@ -1320,6 +1481,8 @@ int sa_process_f32_i16(sa_handle *h, const int16_t *in, float scale, void *out, 
     SA_HIP(h, hipSetDevice(h->device));
     CallCtx c;
     { const int rc = begin_call(h, (hipStream_t)stream, &c); if (rc != SA_OK) return rc; }
+    int nsec64 = 0;
+    if (const SaIirF64 *p64 = f64_plan(h, &nsec64)) return launch_f64(h, in, true, scale, out, batch, out_kind, c, p64, nsec64);
     SaF32Tables t = {h->d_win_b, h->d_win_t, h->d_twT, h->d_twB, h->d_twC, h->d_lt_custom, nullptr};
     if (h->filter_mode == SA_FILTER_DEFAULT) {
         t.lanetab = h->d_lt_default;
@@ -1363,6 +1526,66 @@ int sa_iir_plan_from_sos(const double *sos, int n_sections, float *out, int cap)
     std::vector<SaIirLaneTab> lt(1);
     build_plan(norm, n_sections, &p, &lt[0], nullptr);
     return export_plan(p, lt[0], out, cap);
+}
+
+int sa_set_precision(sa_handle *h, int precision)
+{
+    if (!h) return SA_EINVAL;
+    if (precision != SA_PRECISION_F32 && precision != SA_PRECISION_F64_STATE)
+        return fail(h, SA_EINVAL, "sa_set_precision: SA_PRECISION_F32 (0) or SA_PRECISION_F64_STATE (1)");
+    { const int rc = control_allowed(h); if (rc != SA_OK) return rc; }
+    if (precision == h->precision) return SA_OK;
+    if (precision == SA_PRECISION_F32) {        // the float64 tables and workspaces are kept (hipFree synchronises the device)
+        h->precision = precision;
+        return SA_OK;
+    }
+    SA_HIP(h, hipSetDevice(h->device));
+    if (!h->d_p64_default) SA_HIP(h, hipMalloc(&h->d_p64_default, sizeof(SaIirF64)));
+    if (!h->d_p64_custom) SA_HIP(h, hipMalloc(&h->d_p64_custom, sizeof(SaIirF64)));
+    if (!h->d_win64) SA_HIP(h, hipMalloc(&h->d_win64, sizeof(double) * SA_NPTS));
+    if (!h->d_win_half) SA_HIP(h, hipMalloc(&h->d_win_half, sizeof(float) * SA_NPTS));
+    // the FFT launch's window: 1/2 everywhere, laid out by the code that lays out the handle's own window table
+    std::vector<float> half(SA_NPTS, 0.5f), pa;
+    pass_a_window(half, pa);
+    int rc = upload(h, h->d_win_half, pa.data(), sizeof(float) * SA_NPTS);
+    if (rc == SA_OK) rc = sync_f64(h, true, /*force=*/true);      // tables were not kept up to date outside the mode
+    for (int i = 0; i < h->overlap && rc == SA_OK; ++i) rc = ensure_work64(h, i, h->reserved_max, false, /*geometric=*/false);
+    if (rc != SA_OK) return rc;
+    h->precision = precision;
+    return SA_OK;
+}
+
+int sa_get_precision(const sa_handle *h, int *precision)
+{
+    if (!h || !precision) return SA_EINVAL;
+    *precision = h->precision;
+    return SA_OK;
+}
+
+int sa_debug_iir_plan_f64(const sa_handle *h, double *out, int cap)
+{
+    if (!h || cap < 0) return SA_EINVAL;
+    SaIirF64 p;
+    if (h->filter_mode == SA_FILTER_DEFAULT) {
+        double sos[36];
+        sos_from_q7(kDefaultQ7, sos);
+        build_plan_f64(sos, 6, &p);
+    } else {
+        build_plan_f64(h->sos_custom, h->nsec_custom, &p);
+    }
+    if (out && cap > 0) std::memcpy(out, &p, sizeof(double) * (size_t)(cap < kSaIirF64Doubles ? cap : kSaIirF64Doubles));
+    return kSaIirF64Doubles;
+}
+
+int sa_iir_plan_from_sos_f64(const double *sos, int n_sections, double *out, int cap)
+{
+    if (!sos || n_sections < 0 || n_sections > SA_MAXSEC || cap < 0) return SA_EINVAL;
+    double norm[36];
+    if (!normalise_a0(sos, n_sections, norm)) return SA_EINVAL;
+    SaIirF64 p;
+    build_plan_f64(norm, n_sections, &p);
+    if (out && cap > 0) std::memcpy(out, &p, sizeof(double) * (size_t)(cap < kSaIirF64Doubles ? cap : kSaIirF64Doubles));
+    return kSaIirF64Doubles;
 }
 
 }  // extern "C"

@@ -92,6 +92,10 @@ extern "C" {
 #define SA_OUT_SPEC_HALF  2   /* float2 [B,8193]    X[k] = (re,im), k = 0..N/2 (numpy.fft.rfft layout) */
 #define SA_OUT_TIME       3   /* float  [B,16384]   FFT input: window (+ IIR) output time series */
 
+/* precision of the float path's window and cascade (sa_set_precision) */
+#define SA_PRECISION_F32       0   /* default: float32 arithmetic throughout, one fused kernel per call */
+#define SA_PRECISION_F64_STATE 1   /* window, inter-section signal and DF2T recursion in float64; FFT in float32 */
+
 typedef struct sa_handle sa_handle;
 
 /* ---- lifetime ------------------------------------------------------------------------- */
@@ -215,18 +219,15 @@ int sa_filter_q15(sa_handle *h, const int16_t *in, int16_t *out_time, int batch,
 
 /* float path: in [B,16384] float32 device -> out per out_kind (SA_OUT_*), device.
  * Accuracy against the float64 oracle |rfft(sosfilt(sos, x*window))| (scipy / numpy), in ONE norm throughout: the
- * max-norm error of the magnitude spectrum of a frame relative to that spectrum's peak.  Within 1e-5 wherever
- * float32 arithmetic itself allows it: every fixture, the headline 12th-order Butterworth (worst of 4096 frames
- * 1.9e-6), 4412 of 4500 random designs (tests/fuzz_parity.py, seeds 7 / 11 / 23 x 1500, round 4).  For filters whose
- * poles sit next to the unit circle, or whose output is stop-band leakage far below the input, float32 runs out: a
- * SEQUENTIAL float32 evaluation of sosfilt's own recurrence is above 1e-5 in this norm for 237 of the same 4500
- * designs, this path for 88.  Of those 88, 86 are within 4x the sequential figure (83 within 2x); the two others
- * measure 4.0x (8.2e-5) and 15.6x (2.4e-4: a 12th-order Butterworth band-pass with double zeros at z = 1 and poles of
- * radius 0.984 eight degrees away from them -- a float32 recursion restarted from EXACT chunk start states gives the same
- * 2.4e-4, so the cost is that of evaluating in chunks at all, not of the predictor; tools/accuracy_study.py).  The GPU
- * tests enforce max(1e-5, 4x sequential float32) on the first 160 designs of seed 7 and pin three of the outliers by
- * name with the bounds they meet (tests/test_gpu_f32.py::test_random_designs).  Callers that need 1e-5 on such
- * designs need float64, which this path does not offer. */
+ * max-norm error of the magnitude spectrum of a frame relative to that spectrum's peak.
+ * In the default precision (SA_PRECISION_F32) within 1e-5 wherever float32 arithmetic itself allows it: every fixture,
+ * the headline 12th-order Butterworth (worst of 4096 frames 1.9e-6), 4412 of 4500 random designs (tests/fuzz_parity.py,
+ * seeds 7 / 11 / 23 x 1500).  For filters whose poles sit next to the unit circle, or whose output is stop-band leakage
+ * far below the input, float32 runs out: a SEQUENTIAL float32 evaluation of sosfilt's own recurrence is above 1e-5 in
+ * this norm for 237 of the same 4500 designs, this path for 88 (worst 6.5e-4; two of them more than 4x the sequential
+ * figure, one 15.6x -- restarting the float32 recursion from EXACT chunk start states gives the same error, so no
+ * float64 predictor or scan alone helps; tools/accuracy_study.py).  tests/test_gpu_f32.py::test_random_designs pins
+ * that behaviour.  Callers that need 1e-5 on such designs select SA_PRECISION_F64_STATE (sa_set_precision below). */
 int sa_process_f32(sa_handle *h, const float *in, void *out, int batch, int out_kind, void *stream);
 
 /* The float path fed with the ADC's samples (build extension): in [B,16384] int16 device -- the board delivers
@@ -249,6 +250,36 @@ int sa_debug_iir_plan_f32(const sa_handle *h, float *out, int cap);
 /* Same plan computed on the host from an SOS (scipy row order, a0-normalised here), without a
  * handle or a GPU: pure host logic, used by the CPU tests to check the chunked-scan algebra. */
 int sa_iir_plan_from_sos(const double *sos, int n_sections, float *out, int cap);
+
+/* ---- float64-state IIR (opt-in; build extension) --------------------------------------------------------------------
+ * sa_set_precision(h, SA_PRECISION_F64_STATE): sa_process_f32 and sa_process_f32_i16 in filter modes DEFAULT and CUSTOM
+ * evaluate the window (x * w in double, w = the default Hann of scripts/hann_coeff.py:3-4 in double, or the table of
+ * sa_set_window_f32 widened exactly), the signal between sections and the DF2T recursion of scipy.signal.sosfilt in
+ * float64, and round only the cascade output y to float32.  The FFT of y is the float32 one (its own error on a float32
+ * y is ~1e-6).  Within 1e-5 of the oracle above on every design of tests/fuzz_parity.py (profiles/r5_fuzz_f64.txt).
+ *   - a call is TWO kernels: the float64 cascade into a float32 workspace [B,16384] of the handle, then the bypassed
+ *     float chain on it (SA_OUT_TIME: the first kernel alone, writing y to `out`).  Cost: about 2x the float32 call at
+ *     B = 4096 (profiles/r5_f64_cost.txt), and one write and one read of 64 KiB per frame more HBM traffic.
+ *   - the workspace is per launch slot, allocated only in this mode: sa_reserve() sizes it too while the handle is in
+ *     this mode, sa_set_precision() sizes it to the largest batch reserved so far, and a process call grows it on
+ *     demand (SA_ESTATE inside a stream capture, as for the Q15 workspace).  Overlap depths 1..4 work as in the default
+ *     precision, each slot with its own workspace.  Launch timing reports one time per call, from the start of the
+ *     first kernel to the end of the second.  Captured calls replay both kernels.
+ *   - filter NONE (and a CUSTOM cascade of zero sections) keeps the single bypassed launch of the default precision,
+ *     bit for bit; the Q15 path ignores the setting.
+ *   - control-plane call: stream-ordered (applies to later process calls only), refused while a capture is open
+ *     (SA_ESTATE), SA_EINVAL for any other value.  Leaving the mode keeps its device tables until sa_destroy(). */
+int sa_set_precision(sa_handle *h, int precision /* SA_PRECISION_* */);
+int sa_get_precision(const sa_handle *h, int *precision);
+
+/* The float64 plan (iir_f64.hip, struct SaIirF64): hdr[4] (hdr[0] = padded section count 0/2/4/6) then 6 sections of
+ * {c[6] = b0,b1,b2,a1,a2,0; m[16][2] predictor taps A^(15-j) Bv; A^16; A^32; A^(64 * 2^k) k < 4; A^(1024 * 2^k) k < 4;
+ * A^(64 i) i < 16}, every 2x2 matrix row-major, in the DF2T coordinates of sosfilt (A = [[-a1,1],[-a2,0]],
+ * Bv = [b1 - a1 b0, b2 - a2 b0]).  Write at most `cap` doubles, return the count needed (or a negative error).
+ * sa_debug_iir_plan_f64: the plan the handle would launch in its current filter mode (built from its double SOS);
+ * sa_iir_plan_from_sos_f64: the same from an SOS (scipy row order, a0-normalised here), no handle or GPU needed. */
+int sa_debug_iir_plan_f64(const sa_handle *h, double *out, int cap);
+int sa_iir_plan_from_sos_f64(const double *sos, int n_sections, double *out, int cap);
 
 #ifdef __cplusplus
 }

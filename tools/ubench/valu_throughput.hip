@@ -13,6 +13,7 @@ typedef float v2f __attribute__((ext_vector_type(2)));
 
 // KIND 0 v_fma_f32   1 v_pk_fma_f32   2 v_add_f32   3 v_pk_add_f32   4 v_mul_f32 (VOP2)   5 v_pk_mul_f32
 //      6 v_fma_f32 with an SGPR operand   7 v_pk_fma_f32 with an SGPR pair operand (op_sel_hi broadcast)
+//      22 v_fma_f64 (the recursion of iir_f64.hip: ILP = 1 is one dependent chain, 2 the kernel's two chunks)
 template <int KIND, int ILP>
 __global__ __launch_bounds__(1024) void k(float *out, unsigned long long *cyc, unsigned long long *rt, int n, float c0, float c1)
 {
@@ -20,6 +21,10 @@ __global__ __launch_bounds__(1024) void k(float *out, unsigned long long *cyc, u
 #pragma unroll
     for (int i = 0; i < ILP; ++i) a[i] = v2f{threadIdx.x * 1e-3f + i, 0.5f + i};
     const v2f b = {c0, c1};
+    double ad[ILP];
+#pragma unroll
+    for (int i = 0; i < ILP; ++i) ad[i] = threadIdx.x * 1e-3 + i;
+    const double bd = c0;
     const float bs = c0;
     const unsigned long long t0 = __builtin_amdgcn_s_memtime(), r0 = __builtin_amdgcn_s_memrealtime();
     for (int it = 0; it < n; ++it) {
@@ -49,13 +54,14 @@ __global__ __launch_bounds__(1024) void k(float *out, unsigned long long *cyc, u
                 if (KIND == 19) asm volatile("v_sqrt_f32 %0, %0" : "+v"(a[i].x));
                 if (KIND == 20) asm volatile("v_fma_f32 %0, %0, %1, %2" : "+v"(a[i].x) : "v"(b.x), "s"(bs));      // SGPR as addend
                 if (KIND == 21) asm volatile("v_fmac_f32 %0, %1, %2" : "+v"(a[i].x) : "v"(a[i].y), "v"(a[i].y));  // VOP2 same src
+                if (KIND == 22) asm volatile("v_fma_f64 %0, %0, %1, %1" : "+v"(ad[i]) : "v"(bd));
             }
         }
     }
     const unsigned long long t1 = __builtin_amdgcn_s_memtime(), r1 = __builtin_amdgcn_s_memrealtime();
     v2f r = {0, 0};
 #pragma unroll
-    for (int i = 0; i < ILP; ++i) r += a[i];
+    for (int i = 0; i < ILP; ++i) r += a[i] + v2f{(float)ad[i], 0.f};
     out[(size_t)blockIdx.x * blockDim.x + threadIdx.x] = r.x + r.y;
     if ((threadIdx.x & 63) == 0) {
         const size_t w = (size_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
@@ -97,13 +103,22 @@ void run(const char *name, int waves, float *out, unsigned long long *cyc, unsig
     hipEventDestroy(e1);
 }
 
-int main()
+int main(int argc, char **argv)
 {
     float *out;
     unsigned long long *cyc, *rt;
     hipMalloc(&out, (size_t)256 * 8 * 256 * 4);
     hipMalloc(&cyc, 8 * 256 * 8 * 4);
     hipMalloc(&rt, 8 * 256 * 8 * 4);
+    if (argc > 1 && argv[1][0] == 'd') {              // ./valu_throughput d: the v_fma_f64 rows only
+        for (int waves = 1; waves <= 8; waves *= 2) {
+            run<22, 1>("v_fma_f64 1 chain (dependent)", waves, out, cyc, rt);
+            run<22, 2>("v_fma_f64 2 chains", waves, out, cyc, rt);
+            run<22, 8>("v_fma_f64 8 chains (independent)", waves, out, cyc, rt);
+            run<0, 8>("v_fma_f32 v,v,v(dup)", waves, out, cyc, rt);
+        }
+        return 0;
+    }
     for (int waves = 2; waves <= 8; waves *= 2) {
         run<0, 8>("v_fma_f32 v,v,v(dup)", waves, out, cyc, rt);
         run<17, 8>("v_fma_f32 vvv distinct", waves, out, cyc, rt);
