@@ -23,11 +23,12 @@
 #define SA_IIR_SKIP_ROWSCAN 16
 // State coordinates.  Everything between the predictor taps and the start states (taps m, Pc, plev, prow,
 // the per-lane table) lives in the section's *pole coordinates* z' = T z: T A T^-1 is a scaled rotation for a
-// complex pole pair and diagonal for two distinct real poles, so its powers never exceed |pole|^k.  In the
+// complex pole pair and diagonal for two well-separated real poles, so its powers never exceed |pole|^k (two real
+// poles closer than that, a double pole included, use an orthonormal real Schur basis: A upper triangular).  In the
 // DF2T coordinates the powers of A = [[-a1,1],[-a2,0]] grow to ~1/angle for poles close to the real axis and
 // the float32 scan then loses up to 30x against a sequential evaluation (measured).
 // mback = T^-1 (row-major) takes the two start states back to DF2T right before the recursion.  It is the
-// identity for first-order, repeated-pole and padding sections.
+// identity for first-order and padding sections.
 #define SA_PRED_TAPS 16    // predictor taps per half chunk (block Horner, below)
 struct SaIirSecK {
     // Predictor of the NEXT section (zeros for the last one): its chunk end state from zero state,

@@ -53,12 +53,16 @@ inline void put(float *dst, const Mat2 &m)
 
 // Pole coordinates of one section (sa_common.hpp): M = T^-1 has the eigen-directions (1, a1 + lambda) as unit columns
 // -- real and imaginary part for a complex pair -- and A = T A0 M is what predictor and scan work with.
+// Two real poles whose eigen-directions lie closer than 0.1 rad (a double pole included) would make that basis
+// ill-conditioned (cond ~ 1/angle: the float32 scan lost 1e3-1e4x against a sequential sosfilt at a pole gap of 1e-5,
+// tests/test_plan_conditioning.py); they take the real Schur basis instead -- the first eigen-direction and its
+// orthogonal complement, M orthonormal, A upper triangular.
 void pole_coordinates(double a1, double a2, Mat2 *Mo, Mat2 *To, Mat2 *Ao)
 {
     const Mat2 A0 = {-a1, 1.0, -a2, 0.0};
     Mat2 M = {1, 0, 0, 1};
     const double disc = a1 * a1 - 4.0 * a2;
-    if (a2 != 0.0 && disc != 0.0) {
+    if (a2 != 0.0) {
         double c0[2], c1[2];
         if (disc < 0.0) {
             c0[0] = 1.0; c0[1] = 0.5 * a1;                 // Re (1, a1 + lambda), lambda = -a1/2 + i sqrt(-disc)/2
@@ -71,8 +75,11 @@ void pole_coordinates(double a1, double a2, Mat2 *Mo, Mat2 *To, Mat2 *Ao)
         const double n0 = std::hypot(c0[0], c0[1]), n1 = std::hypot(c1[0], c1[1]);
         const Mat2 cand = {c0[0] / n0, c1[0] / n1, c0[1] / n0, c1[1] / n1};
         const double det = cand.a * cand.d - cand.b * cand.c;
-        // unit columns: |det| = sine of the angle between them; below 1e-6 the pair is numerically defective
-        if (std::isfinite(det) && std::fabs(det) > 1e-6) M = cand;
+        // unit columns: |det| = sine of the angle between them
+        if (std::isfinite(det) && std::fabs(det) > (disc < 0.0 ? 1e-6 : 0.1))
+            M = cand;
+        else if (disc >= 0.0 && std::isfinite(cand.a) && std::isfinite(cand.c))
+            M = {cand.a, -cand.c, cand.c, cand.a};
     }
     const double detM = M.a * M.d - M.b * M.c;
     const Mat2 T = {M.d / detM, -M.b / detM, -M.c / detM, M.a / detM};

@@ -227,7 +227,11 @@ int sa_filter_q15(sa_handle *h, const int16_t *in, int16_t *out_time, int batch,
  * this norm for 237 of the same 4500 designs, this path for 88 (worst 6.5e-4; two of them more than 4x the sequential
  * figure, one 15.6x -- restarting the float32 recursion from EXACT chunk start states gives the same error, so no
  * float64 predictor or scan alone helps; tools/accuracy_study.py).  tests/test_gpu_f32.py::test_random_designs pins
- * that behaviour.  Callers that need 1e-5 on such designs select SA_PRECISION_F64_STATE (sa_set_precision below). */
+ * that behaviour.  Callers that need 1e-5 on such designs select SA_PRECISION_F64_STATE (sa_set_precision below).
+ * The path is linear: an input scaled by 2^k gives SA_OUT_SPEC_HALF and SA_OUT_TIME scaled by exactly 2^k, bit for bit, and
+ * magnitudes within 1 ulp, while every intermediate stays a normal float32 -- |X|^2 is formed in float32, so every
+ * nonzero bin needs roughly 1e-19 < |X| < 1.8e19, and no nonzero sample, state or product may fall below 1.2e-38
+ * (tests/test_gpu_f32_structured.py::test_power_of_two_scaling_is_exact). */
 int sa_process_f32(sa_handle *h, const float *in, void *out, int batch, int out_kind, void *stream);
 
 /* The float path fed with the ADC's samples (build extension): in [B,16384] int16 device -- the board delivers
