@@ -232,8 +232,9 @@ class SpectrumChain:
         call's input and output tensors belong to the library until then (the wrapper holds them: class docstring).
         1 = strictly stream-ordered."""
         self._check(self._lib.sa_set_overlap(self._h, int(depth)))
-        self._depth = int(depth)                 # a change of depth waited on the host for everything in flight
-        self._lent.clear()
+        if int(depth) != self._depth:            # a change of depth waited on the host for everything in flight;
+            self._depth = int(depth)             # the same depth returns at once, with the lent tensors still in use
+            self._lent.clear()
 
     @property
     def overlap(self) -> int:

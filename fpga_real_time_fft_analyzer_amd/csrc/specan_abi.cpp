@@ -1,12 +1,14 @@
 // specan_abi.cpp -- host side of the C ABI declared in include/specan.h.
 //
-// Owns: the opaque handle, device tables (window, twiddles, IIR plan), the Q15 workspace and the
+// Owns: the opaque handle, device tables (window, twiddles, IIR plans: built by iir_plan.cpp), the launch slots and the
 // command-byte state machine that mirrors new/rx_filter_coeff.vhd + new/command_control.vhd.
 // Never touches caller tensors except through the pointers given to the process calls, never
 // falls back to CPU compute.
 #include "../../include/specan.h"
+#include "iir_plan.hpp"
 #include "sa_common.hpp"
 
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -23,262 +25,6 @@ namespace {
 // last sa_create() failure of the calling thread (sa_last_error(NULL)); per thread, so that concurrent creates on
 // several host threads -- one per GPU, SURVEY 8(e) -- do not race on it
 thread_local std::string g_create_error;
-
-// imp/filter_pkg.vhd:54-68, wire order B0,B1,B2,A0,A1,A2 per set (ALPHA then BETA)
-const int8_t kDefaultQ7[12] = {-14, 0, 14, 107, 21, 127, -15, 0, 15, 107, -21, 127};
-
-struct Mat2 {
-    double a, b, c, d;
-};
-inline Mat2 mul(const Mat2 &x, const Mat2 &y)
-{
-    return {x.a * y.a + x.b * y.c, x.a * y.b + x.b * y.d, x.c * y.a + x.d * y.c, x.c * y.b + x.d * y.d};
-}
-
-inline Mat2 mpow(Mat2 m, int e)
-{
-    Mat2 r = {1, 0, 0, 1};
-    while (e > 0) {
-        if (e & 1) r = mul(r, m);
-        m = mul(m, m);
-        e >>= 1;
-    }
-    return r;
-}
-
-inline void put(float *dst, const Mat2 &m)
-{
-    dst[0] = (float)m.a; dst[1] = (float)m.b; dst[2] = (float)m.c; dst[3] = (float)m.d;
-}
-
-// Pole coordinates of one section (sa_common.hpp): M = T^-1 has the eigen-directions (1, a1 + lambda) as unit columns
-// -- real and imaginary part for a complex pair -- and A = T A0 M is what predictor and scan work with.
-// Two real poles whose eigen-directions lie closer than 0.1 rad (a double pole included) would make that basis
-// ill-conditioned (cond ~ 1/angle: the float32 scan lost 1e3-1e4x against a sequential sosfilt at a pole gap of 1e-5,
-// tests/test_plan_conditioning.py); they take the real Schur basis instead -- the first eigen-direction and its
-// orthogonal complement, M orthonormal, A upper triangular.
-void pole_coordinates(double a1, double a2, Mat2 *Mo, Mat2 *To, Mat2 *Ao)
-{
-    const Mat2 A0 = {-a1, 1.0, -a2, 0.0};
-    Mat2 M = {1, 0, 0, 1};
-    const double disc = a1 * a1 - 4.0 * a2;
-    if (a2 != 0.0) {
-        double c0[2], c1[2];
-        if (disc < 0.0) {
-            c0[0] = 1.0; c0[1] = 0.5 * a1;                 // Re (1, a1 + lambda), lambda = -a1/2 + i sqrt(-disc)/2
-            c1[0] = 0.0; c1[1] = 0.5 * std::sqrt(-disc);   // Im
-        } else {
-            const double sq = std::sqrt(disc);
-            c0[0] = 1.0; c0[1] = a1 + 0.5 * (-a1 + sq);
-            c1[0] = 1.0; c1[1] = a1 + 0.5 * (-a1 - sq);
-        }
-        const double n0 = std::hypot(c0[0], c0[1]), n1 = std::hypot(c1[0], c1[1]);
-        const Mat2 cand = {c0[0] / n0, c1[0] / n1, c0[1] / n0, c1[1] / n1};
-        const double det = cand.a * cand.d - cand.b * cand.c;
-        // unit columns: |det| = sine of the angle between them
-        if (std::isfinite(det) && std::fabs(det) > (disc < 0.0 ? 1e-6 : 0.1))
-            M = cand;
-        else if (disc >= 0.0 && std::isfinite(cand.a) && std::isfinite(cand.c))
-            M = {cand.a, -cand.c, cand.c, cand.a};
-    }
-    const double detM = M.a * M.d - M.b * M.c;
-    const Mat2 T = {M.d / detM, -M.b / detM, -M.c / detM, M.a / detM};
-    *Mo = M;
-    *To = T;
-    *Ao = mul(T, mul(A0, M));
-}
-
-// Padded section count, unit-numerator rewrite and folded gain shared by both plan layouts; returns the padded count.
-int normalise_cascade(const double *sos_in, int nsec_in, double *sos /*[36]*/, bool *unit_out, double *gain_out)
-{
-    const int nsec = nsec_in == 0 ? 0 : (nsec_in <= 2 ? 2 : (nsec_in <= 4 ? 4 : 6));
-    for (int s = 0; s < nsec; ++s)
-        for (int i = 0; i < 6; ++i)
-            sos[6 * s + i] = s < nsec_in ? sos_in[6 * s + i] : ((i == 0 || i == 3) ? 1.0 : 0.0);
-    bool unit = nsec > 0 && nsec == nsec_in;
-    double gain = 1.0;
-    for (int s = 0; s < nsec && unit; ++s) {
-        const double b0 = sos[6 * s], b2 = sos[6 * s + 2];
-        if (b0 == 0.0 || b2 != b0 || !std::isfinite(1.0 / b0)) unit = false;
-        gain *= b0;
-    }
-    if (unit && (!std::isfinite(gain) || std::fabs(gain) < 1e-30 || std::fabs(gain) > 1e30)) unit = false;
-    if (unit) {
-        for (int s = 0; s < nsec; ++s) {
-            const double b0 = sos[6 * s];
-            sos[6 * s + 1] /= b0;
-            sos[6 * s] = 1.0;
-            sos[6 * s + 2] = 1.0;
-        }
-    } else {
-        gain = 1.0;
-    }
-    *unit_out = unit;
-    *gain_out = gain;
-    return nsec;
-}
-
-inline void put_cm(float *dst, const Mat2 &m)      // column-major
-{
-    dst[0] = (float)m.a; dst[1] = (float)m.c; dst[2] = (float)m.b; dst[3] = (float)m.d;
-}
-
-
-// Build the predict/scan/recurse plan for an a0-normalised SOS (rows b0,b1,b2,1,a1,a2), double in.
-// The kernels are compiled for 2, 4 and 6 sections; shorter cascades are padded with identity
-// sections (b0 = 1, rest 0: y = x exactly, all scan matrices and predictor taps come out zero).
-//
-// Unit-numerator form: when no padding is needed and every section has b2 == b0 != 0 (all-pole-pair
-// zeros on the unit circle: Butterworth / Chebyshev / elliptic low-, high-pass and band-stop), the
-// sections are rewritten as b = [1, b1/b0, 1] and the product of the b0's is folded into this plan's
-// copy of the window: one multiply less per sample and section in the recursion.
-// half_win: 0.5 * window in natural order (size SA_NPTS).
-// cosw: {a0, a1} when the window is a0 - a1 cos(2 pi n / (N-1)) (then the IIR kernels evaluate it in place,
-// see SaIirLaneTab::wgen), null for any other window.
-void build_plan(const double *sos_in, int nsec_in, SaIirK *plan, SaIirLaneTab *lt, const float *half_win,
-                const double *cosw = nullptr)
-{
-    std::memset(plan, 0, sizeof(*plan));
-    std::memset(lt, 0, sizeof(*lt));
-    double sos[36];
-    bool unit;
-    double gain;
-    const int nsec = normalise_cascade(sos_in, nsec_in, sos, &unit, &gain);
-    plan->nsec = nsec;
-    plan->unit = unit ? 1 : 0;
-    plan->gain = (float)gain;
-    if (half_win)
-        for (int t = 0; t < 256; ++t)
-            for (int g = 0; g < 16; ++g)
-                for (int e = 0; e < 4; ++e)
-                    lt->win_t[(g * 256 + t) * 4 + e] = (float)((double)half_win[64 * t + 4 * g + e] * gain);
-    plan->wingen = 0;
-    if (half_win && cosw) {
-        const double theta = 2.0 * M_PI / (double)(SA_NPTS - 1), S = 0.5 * gain;
-        plan->wingen = 1;
-        lt->wg0 = (float)(S * cosw[0]);
-        for (int t = 0; t < SA_NTHREADS; ++t)
-            for (int h = 0; h < 2; ++h) {
-                const double a = theta * (double)(64 * t + 32 * h);
-                lt->wgen[t][2 * h] = (float)(-S * cosw[1] * std::cos(a));
-                lt->wgen[t][2 * h + 1] = (float)(S * cosw[1] * std::sin(a));
-            }
-        for (int j = 0; j < SA_CHUNK; ++j) {
-            lt->wcs[j][0] = (float)std::cos(theta * j);
-            lt->wcs[j][1] = (float)std::sin(theta * j);
-        }
-    }
-    for (int s = 0; s < nsec; ++s) {
-        const double *r = sos + 6 * s;
-        const double b0 = r[0], b1 = r[1], b2 = r[2], a1 = r[4], a2 = r[5];
-        SaIirSecK &sp = plan->sec[s];
-        sp.c[0] = (float)b0; sp.c[1] = (float)b1; sp.c[2] = (float)b2; sp.c[3] = (float)a1; sp.c[4] = (float)a2;
-        Mat2 M, T, A;
-        pole_coordinates(a1, a2, &M, &T, &A);
-        put_cm(sp.mback, M);
-        double v0 = T.a * (b1 - a1 * b0) + T.b * (b2 - a2 * b0);      // T Bv
-        double v1 = T.c * (b1 - a1 * b0) + T.d * (b2 - a2 * b0);
-        float (*mdst)[2] = s == 0 ? plan->m0 : plan->sec[s - 1].mnext;       // taps of section s ride with section s-1
-        for (int j = SA_PRED_TAPS - 1; j >= 0; --j) {     // m[j] = A^(15-j) Bv: the taps of a HALF chunk (block Horner)
-            mdst[j][0] = (float)v0;
-            mdst[j][1] = (float)v1;
-            const double n0 = A.a * v0 + A.b * v1, n1 = A.c * v0 + A.d * v1;
-            v0 = n0; v1 = n1;
-        }
-        put_cm(s == 0 ? plan->p16_0 : plan->sec[s - 1].p16next, mpow(A, SA_PRED_TAPS));
-        const Mat2 Pc = mpow(A, SA_CHUNK);                  // one chunk
-        const Mat2 P2 = mul(Pc, Pc);                        // one thread (two chunks)
-        const Mat2 Prow = mpow(P2, 16);                     // one 16-lane row
-        put_cm(sp.pc, Pc);
-        Mat2 q = P2, qr = Prow;
-        auto tiny = [](const Mat2 &m) {
-            const double mx = std::fmax(std::fmax(std::fabs(m.a), std::fabs(m.b)), std::fmax(std::fabs(m.c), std::fabs(m.d)));
-            return mx < 1e-10;
-        };
-        sp.flags = tiny(Prow) ? SA_IIR_SKIP_ROWSCAN : 0;
-        for (int i = 0; i < 4; ++i) {                       // powers 1,2,4,8
-            put_cm(sp.plev[i], q);
-            put_cm(sp.prow[i], qr);
-            if (tiny(q)) sp.flags |= 1 << i;
-            q = mul(q, q);
-            qr = mul(qr, qr);
-        }
-        Mat2 pw = {1, 0, 0, 1};
-        for (int i = 0; i < 16; ++i) {                      // lanetab[s][i] = P2^i
-            put_cm(lt->p[s][i], pw);
-            pw = mul(pw, P2);
-        }
-    }
-}
-
-// The RTL taps as real numbers: y = (B2 x + B1 x1 + B0 x2 - A0 y2 - A1 y1)/128
-// => scipy row [B2,B1,B0, 128, A1, A0] / 128; stages alternate set 0 / set 1 (filter_iir12_cust.vhd:68-240).
-void sos_from_q7(const int8_t *c12, double *sos /*[6][6]*/)
-{
-    for (int k = 0; k < 6; ++k) {
-        const int8_t *c = c12 + ((k & 1) ? 6 : 0);
-        double *r = sos + 6 * k;
-        r[0] = c[2] / 128.0; r[1] = c[1] / 128.0; r[2] = c[0] / 128.0;
-        r[3] = 1.0; r[4] = c[4] / 128.0; r[5] = c[3] / 128.0;
-    }
-}
-
-
-inline void put_rm(double *dst, const Mat2 &m)      // row-major
-{
-    dst[0] = m.a; dst[1] = m.b; dst[2] = m.c; dst[3] = m.d;
-}
-
-// The float64-state plan (SaIirF64, iir_f64.hip) of an a0-normalised SOS: DF2T coordinates, no unit-numerator rewrite,
-// shorter cascades padded with identity sections (b0 = 1, rest 0: y = x exactly, every tap and power >= 2 is zero).
-void build_plan_f64(const double *sos_in, int nsec_in, SaIirF64 *p)
-{
-    std::memset(p, 0, sizeof(*p));
-    const int nsec = nsec_in == 0 ? 0 : (nsec_in <= 2 ? 2 : (nsec_in <= 4 ? 4 : 6));
-    p->hdr[0] = (double)nsec;
-    for (int s = 0; s < nsec; ++s) {
-        const double ident[6] = {1, 0, 0, 1, 0, 0};
-        const double *r = s < nsec_in ? sos_in + 6 * s : ident;
-        const double b0 = r[0], b1 = r[1], b2 = r[2], a1 = r[4], a2 = r[5];
-        SaIirSecF64 &k = p->sec[s];
-        k.c[0] = b0; k.c[1] = b1; k.c[2] = b2; k.c[3] = a1; k.c[4] = a2;
-        const Mat2 A = {-a1, 1.0, -a2, 0.0};
-        double v0 = b1 - a1 * b0, v1 = b2 - a2 * b0;          // Bv
-        for (int j = 15; j >= 0; --j) {                       // m[j] = A^(15-j) Bv
-            k.m[j][0] = v0;
-            k.m[j][1] = v1;
-            const double n0 = A.a * v0 + A.b * v1, n1 = A.c * v0 + A.d * v1;
-            v0 = n0; v1 = n1;
-        }
-        put_rm(k.p16, mpow(A, 16));
-        const Mat2 Pc = mpow(A, SA_CHUNK);
-        put_rm(k.pc, Pc);
-        const Mat2 P2 = mul(Pc, Pc);
-        Mat2 q = P2, qr = mpow(P2, 16);
-        for (int i = 0; i < 4; ++i) {
-            put_rm(k.plev[i], q);
-            put_rm(k.prow[i], qr);
-            q = mul(q, q);
-            qr = mul(qr, qr);
-        }
-        Mat2 pw = {1, 0, 0, 1};
-        for (int i = 0; i < 16; ++i) {
-            put_rm(k.lane[i], pw);
-            pw = mul(pw, P2);
-        }
-    }
-}
-
-// a0-normalised copy of a caller's SOS; false on a bad a0 (the checks of sa_load_sos_f64 / sa_iir_plan_from_sos)
-bool normalise_a0(const double *sos, int n_sections, double *norm /*[36]*/)
-{
-    for (int s = 0; s < n_sections; ++s) {
-        const double a0 = sos[6 * s + 3];
-        if (a0 == 0.0 || !std::isfinite(a0)) return false;
-        for (int i = 0; i < 6; ++i) norm[6 * s + i] = sos[6 * s + i] / a0;
-    }
-    return true;
-}
 
 }  // namespace
 
@@ -309,39 +55,57 @@ struct sa_handle {
     int8_t rx_buf[12] = {0};
     // host tables
     std::vector<int16_t> rom;
-    SaIirK plan_default{}, plan_custom{};
-    SaIirLaneTab lt_default{}, lt_custom{};
+    // One float cascade: its a0-normalised SOS (kept to rebuild on window change), the float32 plan and its device lane
+    // table, and the device float64-state plan (allocated by the first sa_set_precision(F64_STATE)).
+    struct Plan {
+        double sos[36] = {0};
+        int nsec = 0;
+        SaIirK k{};
+        SaIirLaneTab lt{};
+        SaIirLaneTab *d_lt = nullptr;
+        SaIirF64 *d_p64 = nullptr;
+    };
+    Plan plan_default, plan_custom;        // the fixed ALPHA/BETA cascade; the loaded one
     std::vector<float> half_win;           // 0.5 * float window, natural order
     bool win_is_cos = true;                // the float window is a0 - a1 cos(2 pi n / (N-1)) (default: Hann)
     double win_cos[2] = {0.5, 0.5};
-    double sos_custom[36] = {0};          // a0-normalised custom cascade (kept to rebuild on window change)
-    int nsec_custom = 0;
     // device tables
     float4 *d_win_b = nullptr;
     float4 *d_win_t = nullptr;
     float4 *d_twT = nullptr, *d_twB = nullptr;
     float2 *d_twC = nullptr;
-    SaIirLaneTab *d_lt_default = nullptr, *d_lt_custom = nullptr;
     int16_t *d_rom = nullptr;
     uint2 *d_twq = nullptr;          // SA-FXFFT-1 twiddles, {(wr, wi), (-wi, wr)} packed int16 pairs
     uint4 *d_twrec = nullptr;        // the same words regrouped per butterfly for the per-lane stages (SaQ15Tables::twrec)
-    // Q15 IIR workspace, one per launch slot (slot 0 = ordered mode; overlap mode uses slots 0..depth-1).  A
-    // workspace that is outgrown is retired, not freed (hipFree synchronises the whole device; launches in flight
-    // may still use it): freed in sa_destroy.  Growth is geometric so that the retired total stays below the live one.
+    // A launch slot's workspace of `elem`-byte samples.  A workspace that is outgrown is retired, not freed (hipFree
+    // synchronises the whole device; launches in flight may still use it): freed in sa_destroy.  Growth is geometric
+    // so that the retired total stays below the live one.
+    struct Workspace {
+        void *ptr;
+        int frames;
+        size_t elem;
+    };
+    enum { kWorkQ15, kWorkF64, kWorkKinds };
+    // Launch slot i (slot 0 = ordered mode; overlap mode uses slots 0..depth-1): its workspaces -- the Q15 cascade's
+    // int16 output, and in float64-state mode the float32 y [B,16384] -- and, in overlap mode, its internal stream
+    struct Slot {
+        Workspace work[kWorkKinds] = {{nullptr, 0, sizeof(int16_t)}, {nullptr, 0, sizeof(float)}};
+        hipStream_t stream = nullptr;
+        hipEvent_t fork = nullptr, done = nullptr;
+        bool used = false;                 // `done` has been recorded
+        bool unjoined = false;             // ... and no caller stream waits for it yet
+        unsigned seen_gen = 0;             // uploads `stream` has waited for
+    };
     static constexpr int kMaxOverlap = 4;
-    int16_t *d_work[kMaxOverlap] = {nullptr, nullptr, nullptr, nullptr};
-    int work_frames[kMaxOverlap] = {0, 0, 0, 0};
+    Slot slot[kMaxOverlap];
     std::vector<void *> retired;
     int reserved_max = 0;                  // largest batch passed to sa_reserve so far
-    // ---- float64-state IIR (opt-in, sa_set_precision): everything below is allocated by the first
-    // sa_set_precision(F64_STATE) and kept up to date only while the handle is in that mode (re-synced on entry)
+    // ---- float64-state IIR (opt-in, sa_set_precision): everything below and the plans' d_p64 is allocated by the
+    // first sa_set_precision(F64_STATE) and kept up to date only while the handle is in that mode (re-synced on entry)
     int precision = SA_PRECISION_F32;
     std::vector<double> win64;             // the window in double, natural order: default Hann or the caller's table widened
-    SaIirF64 *d_p64_default = nullptr, *d_p64_custom = nullptr;
     double *d_win64 = nullptr;             // win64 transposed for iir_f64.hip: [32][256] pairs, pair (g, t) = w[64t + 2g], w[..+1]
     float4 *d_win_half = nullptr;          // constant 1/2 (the split step's factor) in the pass-A layout: the FFT launch's window
-    float *d_work64[kMaxOverlap] = {nullptr, nullptr, nullptr, nullptr};   // float32 y [B,16384] per launch slot
-    int work64_frames[kMaxOverlap] = {0, 0, 0, 0};
     // ---- stream-ordered control plane (no device-wide synchronisation anywhere after sa_create)
     // Table uploads run on the handle's own control stream: it first waits for everything the handle has
     // launched so far, copies from a pinned staging slot, and records `uploaded`; the next process call makes its
@@ -367,26 +131,23 @@ struct sa_handle {
     hipStream_t capture_stream = nullptr;
     // ---- launch timing (opt-in, sa_set_profiling): a ring of timing-enabled event pairs; ordered-mode call k binds
     // pair k mod n to the begin of its first and the end of its last kernel (hipExtLaunchKernel: the events ride on the
-    // dispatch packets, no marker packets), and `launched` aliases the pair's stop event meanwhile
+    // dispatch packets, no marker packets), and `launched` aliases the pair's stop event from then on
     std::vector<hipEvent_t> prof_start, prof_stop;
     hipEvent_t launched_own = nullptr;     // the handle's own (timing-disabled) completion event
     unsigned long long prof_calls = 0;
     // ---- overlapped launches (opt-in, sa_set_overlap): consecutive process calls alternate over `overlap` internal
-    // streams so that the tail of one launch runs under the head of the next; see include/specan.h
+    // streams (Slot::stream) so that the tail of one launch runs under the head of the next; see include/specan.h
     int overlap = 1;
-    hipStream_t ov_stream[kMaxOverlap] = {nullptr, nullptr, nullptr, nullptr};
     hipStream_t ov_fit_stream = nullptr;      // the caller stream the internal streams were last fitted to (compared, never used)
     bool ov_fit_valid = false;
-    hipEvent_t ov_fork[kMaxOverlap] = {nullptr, nullptr, nullptr, nullptr};
-    hipEvent_t ov_done[kMaxOverlap] = {nullptr, nullptr, nullptr, nullptr};
-    bool ov_used[kMaxOverlap] = {false, false, false, false};      // ov_done[i] has been recorded
-    bool ov_unjoined[kMaxOverlap] = {false, false, false, false};  // ... and no caller stream waits for it yet
-    unsigned ov_seen_gen[kMaxOverlap] = {0, 0, 0, 0};
     unsigned long long ov_calls = 0;
-    static constexpr int kStage = 4;       // pinned staging slots (a slot is reused after kStage uploads)
-    void *stage[kStage] = {nullptr, nullptr, nullptr, nullptr};
-    hipEvent_t stage_done[kStage] = {nullptr, nullptr, nullptr, nullptr};
-    bool stage_used[kStage] = {false, false, false, false};
+    struct Stage {                         // a pinned staging slot (reused after kStage uploads)
+        void *buf = nullptr;
+        hipEvent_t done = nullptr;
+        bool used = false;
+    };
+    static constexpr int kStage = 4;
+    Stage stage[kStage];
     int stage_next = 0;
     // transport / sequencing state of imp/sequ2.vhd as far as the command bytes define it
     uint8_t transport = SA_CMD_ETHERNET_MODE;     // ether_en <= '1' on reset (imp/sequ2.vhd:85-86)
@@ -403,6 +164,14 @@ int fail(sa_handle *h, int code, const char *what, hipError_t e = hipSuccess)
         std::snprintf(buf, sizeof buf, "%s", what);
     if (h) h->err = buf; else g_create_error = buf;
     return code;
+}
+
+// fail() of an entry point that shares its body with another: "fn: what"
+int fail_at(sa_handle *h, int code, const char *fn, const char *what)
+{
+    char buf[160];
+    std::snprintf(buf, sizeof buf, "%s: %s", fn, what);
+    return fail(h, code, buf);
 }
 
 #define SA_HIP(h, call)                                          \
@@ -509,24 +278,62 @@ int upload(sa_handle *h, void *dst, const void *src, size_t bytes)
 {
     if (bytes > kStageBytes) return fail(h, SA_EINVAL, "upload: table larger than the staging slot");
     SA_HIP(h, hipSetDevice(h->device));
-    const int slot = h->stage_next;
-    h->stage_next = (slot + 1) % sa_handle::kStage;
-    if (h->stage_used[slot]) SA_HIP(h, hipEventSynchronize(h->stage_done[slot]));   // that slot's old copy has run
-    std::memcpy(h->stage[slot], src, bytes);
+    sa_handle::Stage &st = h->stage[h->stage_next];
+    h->stage_next = (h->stage_next + 1) % sa_handle::kStage;
+    if (st.used) SA_HIP(h, hipEventSynchronize(st.done));       // that slot's old copy has run
+    std::memcpy(st.buf, src, bytes);
     if (h->launched_valid) SA_HIP(h, hipStreamWaitEvent(h->ctl, h->launched, 0));
-    for (int i = 0; i < sa_handle::kMaxOverlap; ++i)
-        if (h->ov_used[i]) SA_HIP(h, hipStreamWaitEvent(h->ctl, h->ov_done[i], 0));
-    SA_HIP(h, hipMemcpyAsync(dst, h->stage[slot], bytes, hipMemcpyHostToDevice, h->ctl));
-    SA_HIP(h, hipEventRecord(h->stage_done[slot], h->ctl));
-    h->stage_used[slot] = true;
+    for (const sa_handle::Slot &s : h->slot)
+        if (s.used) SA_HIP(h, hipStreamWaitEvent(h->ctl, s.done, 0));
+    SA_HIP(h, hipMemcpyAsync(dst, st.buf, bytes, hipMemcpyHostToDevice, h->ctl));
+    SA_HIP(h, hipEventRecord(st.done, h->ctl));
+    st.used = true;
     SA_HIP(h, hipEventRecord(h->uploaded, h->ctl));
     ++h->upload_gen;
     return SA_OK;
 }
 
-// One process call = begin_call, launches on c.stream with workspace slot c.slot, end_call.
+// Workspace `w` grown to `frames` without touching launches in flight (see sa_handle::Workspace).
+// `geometric`: grow by at least half (process calls with creeping batch sizes); exact sizing where the size is copied
+// from another slot -- sa_set_overlap gave every slot max(the others, 1.5 x its own), and two slots leap-frogged each
+// other by a factor 1.5 per mode change until hipMalloc failed (found by a 10-minute soak, seed 77).
+int ensure_work(sa_handle *h, sa_handle::Workspace &w, int frames, bool captured, bool geometric = true)
+{
+    if (frames <= w.frames) return SA_OK;
+    if (captured) return fail(h, SA_ESTATE, "workspace growth inside a stream capture: call sa_reserve() first");
+    long want = frames, geo = (long)w.frames + w.frames / 2;
+    if (geometric && geo > want) want = geo;
+    void *p = nullptr;
+    SA_HIP(h, hipMalloc(&p, (size_t)want * SA_NPTS * w.elem));
+    if (w.ptr) h->retired.push_back(w.ptr);
+    w.ptr = p;
+    w.frames = (int)want;
+    return SA_OK;
+}
+
+// The workspaces of slots 0..n-1 that the handle's precision launches with (`f64_only`: the float64-state one alone)
+// grown to `frames`; frames < 0: exactly to the largest of that kind any slot has (slots new to overlap mode start with
+// what the handle already has somewhere)
+int grow_slots(sa_handle *h, int n, int frames, bool geometric, bool f64_only = false)
+{
+    const int k0 = f64_only ? sa_handle::kWorkF64 : sa_handle::kWorkQ15;
+    const int k1 = f64_only || h->precision == SA_PRECISION_F64_STATE ? sa_handle::kWorkKinds : sa_handle::kWorkF64;
+    for (int k = k0; k < k1; ++k) {
+        int want = frames;
+        if (want < 0)
+            for (const sa_handle::Slot &s : h->slot) want = std::max(want, s.work[k].frames);
+        for (int i = 0; i < n; ++i) {
+            const int rc = ensure_work(h, h->slot[i].work[k], want, false, geometric);
+            if (rc != SA_OK) return rc;
+        }
+    }
+    return SA_OK;
+}
+
+// One process call = begin_call, the launches on c.stream with workspace slot c.slot, end_call (see begin_call).
 //   ordered mode: c.stream is the caller's stream; the call is ordered after pending table uploads and, if the
-//     caller switched streams, after the handle's earlier launches; end_call records `launched` on it.
+//     caller switched streams, after the handle's earlier launches; its last launch is bound to c.stop, which end_call
+//     makes the handle's `launched`.
 //   overlap mode (sa_set_overlap(h, d), d > 1): call k runs on internal stream k % d behind a fork event taken from
 //     the caller's stream BEFORE that stream is made to wait for call k-d+1 (the join): kernel k depends on
 //     what the caller enqueued before call k, not on kernels k-1 .. k-d+1, and may run beside them.
@@ -535,6 +342,7 @@ struct CallCtx {
     hipEvent_t start;         // bound to the call's first kernel while sa_set_profiling is on, else null
     hipEvent_t stop;          // bound to the call's last kernel by the launcher (null inside a stream capture)
     int slot;
+    int join;                 // overlap mode: the slot the caller's stream was made to wait for, else -1
     bool overlapped, captured;
 };
 
@@ -548,32 +356,38 @@ int fit_overlap_streams(sa_handle *h, hipStream_t user)
 {
     for (int i = 0; i < h->overlap; ++i) {
         hipError_t pe = hipSuccess;
-        const int r = streams_run_side_by_side(user, h->ov_stream[i], &pe);
+        sa_handle::Slot &s = h->slot[i];
+        const int r = streams_run_side_by_side(user, s.stream, &pe);
         if (r < 0) return fail(h, SA_EHIP, "overlap: stream probe", pe);
         if (r == 1) continue;
         hipStream_t avoid[sa_handle::kMaxOverlap + 1] = {user};
         int n = 1;
         for (int j = 0; j < h->overlap; ++j)
-            if (j != i) avoid[n++] = h->ov_stream[j];
+            if (j != i) avoid[n++] = h->slot[j].stream;
         hipStream_t repl = nullptr;
         const int rc = pick_stream(h, avoid, n, &repl);
         if (rc != SA_OK) return rc;
-        if (h->ov_used[i]) SA_HIP(h, hipEventSynchronize(h->ov_done[i]));      // the old stream's work is over
-        (void)hipStreamDestroy(h->ov_stream[i]);
-        h->ov_stream[i] = repl;
-        h->ov_seen_gen[i] = h->upload_gen - 1;                                   // the new stream has seen no upload
+        if (s.used) SA_HIP(h, hipEventSynchronize(s.done));                      // the old stream's work is over
+        (void)hipStreamDestroy(s.stream);
+        s.stream = repl;
+        s.seen_gen = h->upload_gen - 1;                                          // the new stream has seen no upload
     }
     h->ov_fit_stream = user;
     h->ov_fit_valid = true;
     return SA_OK;
 }
 
-int begin_call(sa_handle *h, hipStream_t user, CallCtx *c)
+// Steps 1 and 2 of a process call: (1) decide -- capture query (it also keeps the sticky capture record), stream, slot,
+// growth of the slot's workspace `work` to `frames` (work < 0: none); (2) enqueue the ordering waits.  The caller
+// launches (3) and commits with end_call (4) only when every launch succeeded: a call that fails leaves `launched`,
+// the profiling ring and the join state on the last launch that did happen.
+int begin_call(sa_handle *h, hipStream_t user, int work, int frames, CallCtx *c)
 {
     c->stream = user;
-    c->start = nullptr;
+    c->start = c->stop = nullptr;
     c->slot = 0;
-    c->overlapped = false;
+    c->join = -1;
+    c->overlapped = h->overlap > 1;
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     SA_HIP(h, hipStreamIsCapturing(user, &cs));
     c->captured = cs != hipStreamCaptureStatusNone;
@@ -584,31 +398,40 @@ int begin_call(sa_handle *h, hipStream_t user, CallCtx *c)
         h->capture_open = false;             // that stream's capture has ended
         h->capture_stream = nullptr;
     }
-    if (h->overlap > 1) {
+    if (c->overlapped) {
         if (c->captured)
             return fail(h, SA_ESTATE, "overlapped launches (sa_set_overlap > 1) cannot be captured into a graph");
         if (!h->ov_fit_valid || h->ov_fit_stream != user) {
             const int rc = fit_overlap_streams(h, user);
             if (rc != SA_OK) return rc;
         }
-        const int d = h->overlap, slot = (int)(h->ov_calls % (unsigned)d);
-        SA_HIP(h, hipEventRecord(h->ov_fork[slot], user));
+        c->slot = (int)(h->ov_calls % (unsigned)h->overlap);
+        c->stream = h->slot[c->slot].stream;
+        c->stop = h->slot[c->slot].done;
+    } else if (!c->captured) {               // a captured record would tie the event to the graph; replays are ordered by the caller (include/specan.h)
+        c->stop = h->launched;
+        if (!h->prof_stop.empty()) {         // timed call: the ring's next pair
+            const size_t i = (size_t)(h->prof_calls % h->prof_stop.size());
+            c->start = h->prof_start[i];
+            c->stop = h->prof_stop[i];
+        }
+    }
+    if (work >= 0) { const int rc = ensure_work(h, h->slot[c->slot].work[work], frames, c->captured); if (rc != SA_OK) return rc; }
+    if (c->overlapped) {
+        sa_handle::Slot &s = h->slot[c->slot];
+        SA_HIP(h, hipEventRecord(s.fork, user));
         // join: the call issued d-1 calls ago (the next user of the oldest slot is the call after this one)
-        const int join = (slot + 1) % d;
-        if (h->ov_unjoined[join]) {
-            SA_HIP(h, hipStreamWaitEvent(user, h->ov_done[join], 0));
-            h->ov_unjoined[join] = false;
+        const int join = (c->slot + 1) % h->overlap;
+        if (h->slot[join].unjoined) {
+            SA_HIP(h, hipStreamWaitEvent(user, h->slot[join].done, 0));
+            c->join = join;
         }
-        SA_HIP(h, hipStreamWaitEvent(h->ov_stream[slot], h->ov_fork[slot], 0));
+        SA_HIP(h, hipStreamWaitEvent(s.stream, s.fork, 0));
         // (ordered-mode launches made before the switch to overlap mode have completed: sa_set_overlap waited)
-        if (h->ov_seen_gen[slot] != h->upload_gen) {
-            SA_HIP(h, hipStreamWaitEvent(h->ov_stream[slot], h->uploaded, 0));
-            h->ov_seen_gen[slot] = h->upload_gen;
+        if (s.seen_gen != h->upload_gen) {
+            SA_HIP(h, hipStreamWaitEvent(s.stream, h->uploaded, 0));
+            s.seen_gen = h->upload_gen;
         }
-        c->stream = h->ov_stream[slot];
-        c->stop = h->ov_done[slot];
-        c->slot = slot;
-        c->overlapped = true;
         return SA_OK;
     }
     if (h->have_last_stream && h->last_stream != user) {
@@ -621,61 +444,22 @@ int begin_call(sa_handle *h, hipStream_t user, CallCtx *c)
     }
     h->last_stream = user;
     h->have_last_stream = true;
-    if (!c->captured && !h->prof_stop.empty()) {          // timed call: the ring's next pair; `launched` follows it
-        const size_t i = (size_t)(h->prof_calls % h->prof_stop.size());
-        c->start = h->prof_start[i];
-        h->launched = h->prof_stop[i];
-    }
-    // a captured record would tie the event to the graph; replays are ordered by the caller (include/specan.h)
-    c->stop = c->captured ? nullptr : h->launched;
     return SA_OK;
 }
 
+// Step 4: every launch of the call was enqueued
 int end_call(sa_handle *h, const CallCtx &c)
 {
     if (c.overlapped) {
-        h->ov_used[c.slot] = true;
-        h->ov_unjoined[c.slot] = true;
+        if (c.join >= 0) h->slot[c.join].unjoined = false;
+        h->slot[c.slot].used = true;
+        h->slot[c.slot].unjoined = true;
         ++h->ov_calls;
-        return SA_OK;
-    }
-    if (!c.captured) {
+    } else if (!c.captured) {
+        h->launched = c.stop;
         h->launched_valid = true;
         if (!h->prof_stop.empty()) ++h->prof_calls;
     }
-    return SA_OK;
-}
-
-// Workspace of a launch slot, grown without touching launches in flight (see sa_handle::retired).
-// `geometric`: grow by at least half (process calls with creeping batch sizes); exact sizing where the size is copied
-// from another slot -- sa_set_overlap gave every slot max(the others, 1.5 x its own), and two slots leap-frogged each
-// other by a factor 1.5 per mode change until hipMalloc failed (found by a 10-minute soak, seed 77).
-int ensure_work(sa_handle *h, int slot, int frames, bool captured, bool geometric = true)
-{
-    if (frames <= h->work_frames[slot]) return SA_OK;
-    if (captured) return fail(h, SA_ESTATE, "workspace growth inside a stream capture: call sa_reserve() first");
-    long want = frames, geo = (long)h->work_frames[slot] + h->work_frames[slot] / 2;
-    if (geometric && geo > want) want = geo;
-    void *p = nullptr;
-    SA_HIP(h, hipMalloc(&p, (size_t)want * SA_NPTS * sizeof(int16_t)));
-    if (h->d_work[slot]) h->retired.push_back(h->d_work[slot]);
-    h->d_work[slot] = (int16_t *)p;
-    h->work_frames[slot] = (int)want;
-    return SA_OK;
-}
-
-// The float32 workspace of the float64-state mode (iir_f64.hip output, FFT launch input); same growth rules as ensure_work
-int ensure_work64(sa_handle *h, int slot, int frames, bool captured, bool geometric = true)
-{
-    if (frames <= h->work64_frames[slot]) return SA_OK;
-    if (captured) return fail(h, SA_ESTATE, "workspace growth inside a stream capture: call sa_reserve() first");
-    long want = frames, geo = (long)h->work64_frames[slot] + h->work64_frames[slot] / 2;
-    if (geometric && geo > want) want = geo;
-    void *p = nullptr;
-    SA_HIP(h, hipMalloc(&p, (size_t)want * SA_NPTS * sizeof(float)));
-    if (h->d_work64[slot]) h->retired.push_back(h->d_work64[slot]);
-    h->d_work64[slot] = (float *)p;
-    h->work64_frames[slot] = (int)want;
     return SA_OK;
 }
 
@@ -699,14 +483,17 @@ void default_rom(std::vector<int16_t> &rom)
 
 // half = 0.5 * window (exact scaling, undone by the split step).  Two device copies, each arranged so
 // that the kernel's loads are coalesced 16-byte accesses in the layout it computes in:
-//   tr (IIR kernels, chunk layout):   tr[g][t] = half[64t + 4g .. +3]
+//   tr (IIR kernels, chunk layout):   tr[g][t] = w[64t + E g .. + E-1], E = 16 bytes / sizeof(T) (float: the half
+//                                     window, [16][256] quads; double: the window of iir_f64.hip, [32][256] pairs)
 //   pa (no-IIR kernel, pass-A layout): pa[p][t] = half[512(2p)+2t], [..+1], half[512(2p+1)+2t], [..+1]
-void transpose_window(const std::vector<float> &half, std::vector<float> &tr)
+template <class T>
+void transpose_window(const std::vector<T> &w, std::vector<T> &tr)
 {
+    constexpr int E = 16 / sizeof(T);
     tr.resize(SA_NPTS);
     for (int t = 0; t < 256; ++t)
-        for (int g = 0; g < 16; ++g)
-            for (int e = 0; e < 4; ++e) tr[(g * 256 + t) * 4 + e] = half[64 * t + 4 * g + e];
+        for (int g = 0; g < 64 / E; ++g)
+            for (int e = 0; e < E; ++e) tr[(g * 256 + t) * E + e] = w[64 * t + E * g + e];
 }
 
 void pass_a_window(const std::vector<float> &half, std::vector<float> &pa)
@@ -722,43 +509,15 @@ void pass_a_window(const std::vector<float> &half, std::vector<float> &pa)
         }
 }
 
-int rebuild_plans(sa_handle *h);
-
-// Device tables of the float64-state mode from the handle's double state: both plans (from the double SOS, never from
-// the float32 plan) and, with `window`, the double window.  Nothing unless the handle is in that mode or `force`.
-int sync_f64(sa_handle *h, bool window, bool force = false)
+// The default window, Hann (scripts/hann_coeff.py:3-4): in double, its float half, and the cosine form set to
+// (0.5, 0.5) exactly (not fitted: a fitted (a0, a1) would change the bits of the generated window)
+void default_window(sa_handle *h)
 {
-    if (h->precision != SA_PRECISION_F64_STATE && !force) return SA_OK;
-    SaIirF64 p;
-    double sos[36];
-    sos_from_q7(kDefaultQ7, sos);
-    build_plan_f64(sos, 6, &p);
-    int rc = upload(h, h->d_p64_default, &p, sizeof p);
-    if (rc != SA_OK) return rc;
-    build_plan_f64(h->sos_custom, h->nsec_custom, &p);
-    rc = upload(h, h->d_p64_custom, &p, sizeof p);
-    if (rc != SA_OK || !window) return rc;
-    std::vector<double> tr(SA_NPTS);
-    for (int t = 0; t < 256; ++t)
-        for (int g = 0; g < 32; ++g)
-            for (int e = 0; e < 2; ++e) tr[(g * 256 + t) * 2 + e] = h->win64[64 * t + 2 * g + e];
-    const size_t half = sizeof(double) * SA_NPTS / 2;     // two uploads: a staging slot holds 64 KiB, the table is 128
-    rc = upload(h, h->d_win64, tr.data(), half);
-    if (rc != SA_OK) return rc;
-    return upload(h, h->d_win64 + SA_NPTS / 2, tr.data() + SA_NPTS / 2, half);
-}
-
-int upload_window_half(sa_handle *h, const std::vector<float> &half)
-{
-    std::vector<float> tr, pa;
-    transpose_window(half, tr);
-    pass_a_window(half, pa);
-    h->half_win = half;
-    int rc = upload(h, h->d_win_b, pa.data(), sizeof(float) * SA_NPTS);
-    if (rc != SA_OK) return rc;
-    rc = upload(h, h->d_win_t, tr.data(), sizeof(float) * SA_NPTS);
-    if (rc != SA_OK) return rc;
-    return rebuild_plans(h);          // each plan carries its own (gain-scaled) copy of the window
+    default_window_f64(h->win64);
+    h->half_win.resize(SA_NPTS);
+    for (int i = 0; i < SA_NPTS; ++i) h->half_win[i] = (float)(0.5 * h->win64[i]);
+    h->win_is_cos = true;
+    h->win_cos[0] = h->win_cos[1] = 0.5;
 }
 
 // Is w[n] = a0 - a1 cos(2 pi n / (N-1)) to within float rounding?  Least-squares fit of (a0, a1) in double, then
@@ -784,75 +543,74 @@ bool fit_cosine_window(const float *w, double out[2])
     return true;
 }
 
-int set_window_f32_from(sa_handle *h, const float *w)
+// How a table reaches the device: upload() on the control plane; copy_at_create in sa_create
+using CopyFn = int (*)(sa_handle *h, void *dst, const void *src, size_t bytes);
+
+// sa_create's copies are blocking (it synchronises the device at the end) and no uploads: upload_gen stays 0
+int copy_at_create(sa_handle *, void *dst, const void *src, size_t bytes)
 {
-    std::vector<float> half(SA_NPTS);
-    for (int i = 0; i < SA_NPTS; ++i) half[i] = 0.5f * w[i];
-    h->win_is_cos = fit_cosine_window(w, h->win_cos);
-    h->win64.assign(w, w + SA_NPTS);                    // widened exactly
-    return upload_window_half(h, half);
+    const hipError_t e = hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice);
+    return e == hipSuccess ? SA_OK : fail(nullptr, SA_EHIP, "sa_create: hipMemcpy", e);
 }
 
-// flat float view for tests (layout documented in include/specan.h, sa_iir_plan_from_sos): header, the six
-// sections' constants, then the predictor taps m[6][16][2], their half-chunk matrices p16[6][4] and the per-lane
-// matrices p[6][16][4] (every matrix row-major here)
-int export_plan(const SaIirK &p, const SaIirLaneTab &lt, float *out, int cap)
+// Device tables of the float64-state mode from the handle's double state: both plans (from the double SOS, never from
+// the float32 plan) and, with `window`, the double window.  Nothing unless the handle is in that mode or `force`.
+int sync_f64(sa_handle *h, bool window, bool force = false)
 {
-    std::vector<float> v;
-    auto put_i = [&](int x) { float f; std::memcpy(&f, &x, 4); v.push_back(f); };
-    put_i(p.nsec); put_i(p.unit); v.push_back(p.gain); put_i(p.wingen);
-    for (int s = 0; s < SA_MAXSEC; ++s) {
-        const SaIirSecK &k = p.sec[s];
-        for (int i = 0; i < 5; ++i) v.push_back(k.c[i]);
-        put_i(k.flags); v.push_back(k.pad[0]); v.push_back(k.pad[1]);
-        auto rm = [&](const float *m) { v.push_back(m[0]); v.push_back(m[2]); v.push_back(m[1]); v.push_back(m[3]); };   // stored column-major
-        rm(k.pc);
-        rm(k.mback);
-        for (int i = 0; i < 4; ++i) rm(k.plev[i]);
-        for (int i = 0; i < 4; ++i) rm(k.prow[i]);
+    if (h->precision != SA_PRECISION_F64_STATE && !force) return SA_OK;
+    for (sa_handle::Plan *pl : {&h->plan_default, &h->plan_custom}) {
+        SaIirF64 p;
+        build_plan_f64(pl->sos, pl->nsec, &p);
+        const int rc = upload(h, pl->d_p64, &p, sizeof p);
+        if (rc != SA_OK) return rc;
     }
-    for (int s = 0; s < SA_MAXSEC; ++s) {
-        const float (*m)[2] = s == 0 ? p.m0 : p.sec[s - 1].mnext;
-        v.insert(v.end(), &m[0][0], &m[0][0] + 2 * SA_PRED_TAPS);
-    }
-    for (int s = 0; s < SA_MAXSEC; ++s) {
-        const float *m = s == 0 ? p.p16_0 : p.sec[s - 1].p16next;
-        v.push_back(m[0]); v.push_back(m[2]); v.push_back(m[1]); v.push_back(m[3]);
-    }
-    for (int sct = 0; sct < SA_MAXSEC; ++sct)
-        for (int i = 0; i < 16; ++i) {
-            const float *m = lt.p[sct][i];
-            v.push_back(m[0]); v.push_back(m[2]); v.push_back(m[1]); v.push_back(m[3]);
-        }
-    const int n = (int)v.size();
-    if (out && cap > 0) std::memcpy(out, v.data(), sizeof(float) * (size_t)(cap < n ? cap : n));
-    return n;
+    if (!window) return SA_OK;
+    std::vector<double> tr;
+    transpose_window(h->win64, tr);
+    const size_t half = sizeof(double) * SA_NPTS / 2;     // two uploads: a staging slot holds 64 KiB, the table is 128
+    const int rc = upload(h, h->d_win64, tr.data(), half);
+    if (rc != SA_OK) return rc;
+    return upload(h, h->d_win64 + SA_NPTS / 2, tr.data() + SA_NPTS / 2, half);
+}
+
+// The float32 plan `pl` from its SOS and the handle's window; its lane table to the device
+int write_plan(sa_handle *h, sa_handle::Plan &pl, CopyFn copy)
+{
+    build_plan(pl.sos, pl.nsec, &pl.k, &pl.lt, h->half_win.data(), h->win_is_cos ? h->win_cos : nullptr);
+    return copy(h, pl.d_lt, &pl.lt, sizeof pl.lt);
+}
+
+// The device tables that follow the float window h->half_win: its two layouts, then both plans (each carries its own
+// gain-scaled copy of the window) and the float64-state tables (none in sa_create: a new handle is in float32 precision)
+int write_window(sa_handle *h, CopyFn copy)
+{
+    std::vector<float> tr, pa;
+    transpose_window(h->half_win, tr);
+    pass_a_window(h->half_win, pa);
+    int rc = copy(h, h->d_win_b, pa.data(), sizeof(float) * SA_NPTS);
+    if (rc == SA_OK) rc = copy(h, h->d_win_t, tr.data(), sizeof(float) * SA_NPTS);
+    if (rc == SA_OK) rc = write_plan(h, h->plan_default, copy);
+    if (rc == SA_OK) rc = write_plan(h, h->plan_custom, copy);
+    if (rc == SA_OK) rc = sync_f64(h, true);
+    return rc;
 }
 
 int set_custom_plan(sa_handle *h, const double *sos_norm, int nsec)
 {
-    std::memset(h->sos_custom, 0, sizeof h->sos_custom);
-    std::memcpy(h->sos_custom, sos_norm, sizeof(double) * 6 * (size_t)nsec);
-    h->nsec_custom = nsec;
-    const double *cw = h->win_is_cos ? h->win_cos : nullptr;
-    build_plan(h->sos_custom, nsec, &h->plan_custom, &h->lt_custom, h->half_win.data(), cw);
-    const int rc = upload(h, h->d_lt_custom, &h->lt_custom, sizeof(SaIirLaneTab));
+    sa_handle::Plan &pl = h->plan_custom;
+    std::memset(pl.sos, 0, sizeof pl.sos);
+    std::memcpy(pl.sos, sos_norm, sizeof(double) * 6 * (size_t)nsec);
+    pl.nsec = nsec;
+    const int rc = write_plan(h, pl, upload);
     if (rc != SA_OK) return rc;
     return sync_f64(h, false);
 }
 
-int rebuild_plans(sa_handle *h)
+// The cascade of the filter mode: the fixed one for DEFAULT, the loaded one for every other mode (what the debug
+// exports show for NONE and WIDE; float launches in mode NONE run without a cascade)
+const sa_handle::Plan &active_plan(const sa_handle *h)
 {
-    double sos[36];
-    sos_from_q7(kDefaultQ7, sos);
-    const double *cw = h->win_is_cos ? h->win_cos : nullptr;
-    build_plan(sos, 6, &h->plan_default, &h->lt_default, h->half_win.data(), cw);
-    int rc = upload(h, h->d_lt_default, &h->lt_default, sizeof(SaIirLaneTab));
-    if (rc != SA_OK) return rc;
-    build_plan(h->sos_custom, h->nsec_custom, &h->plan_custom, &h->lt_custom, h->half_win.data(), cw);
-    rc = upload(h, h->d_lt_custom, &h->lt_custom, sizeof(SaIirLaneTab));
-    if (rc != SA_OK) return rc;
-    return sync_f64(h, true);               // rebuild_plans runs on every window change
+    return h->filter_mode == SA_FILTER_DEFAULT ? h->plan_default : h->plan_custom;
 }
 
 }  // namespace
@@ -889,34 +647,32 @@ int sa_create(int device, sa_handle **out)
     SA_HIPC(hipEventCreateWithFlags(&h->launched_own, hipEventDisableTiming));
     h->launched = h->launched_own;
     SA_HIPC(hipEventCreateWithFlags(&h->uploaded, hipEventDisableTiming));
-    for (int i = 0; i < sa_handle::kStage; ++i) {
-        SA_HIPC(hipHostMalloc(&h->stage[i], kStageBytes, hipHostMallocDefault));
-        SA_HIPC(hipEventCreateWithFlags(&h->stage_done[i], hipEventDisableTiming));
+    for (sa_handle::Stage &st : h->stage) {
+        SA_HIPC(hipHostMalloc(&st.buf, kStageBytes, hipHostMallocDefault));
+        SA_HIPC(hipEventCreateWithFlags(&st.done, hipEventDisableTiming));
     }
     SA_HIPC(hipMalloc(&h->d_win_b, sizeof(float) * SA_NPTS));
     SA_HIPC(hipMalloc(&h->d_win_t, sizeof(float) * SA_NPTS));
     SA_HIPC(hipMalloc(&h->d_twT, sizeof(float4) * 6 * 256));
     SA_HIPC(hipMalloc(&h->d_twB, sizeof(float4) * 8 * 16));
     SA_HIPC(hipMalloc(&h->d_twC, sizeof(float2) * 25));
-    SA_HIPC(hipMalloc(&h->d_lt_default, sizeof(SaIirLaneTab)));
-    SA_HIPC(hipMalloc(&h->d_lt_custom, sizeof(SaIirLaneTab)));
+    SA_HIPC(hipMalloc(&h->plan_default.d_lt, sizeof(SaIirLaneTab)));
+    SA_HIPC(hipMalloc(&h->plan_custom.d_lt, sizeof(SaIirLaneTab)));
     SA_HIPC(hipMalloc(&h->d_rom, sizeof(int16_t) * SA_NPTS));
     SA_HIPC(hipMalloc(&h->d_twq, sizeof(uint2) * SA_NPTS));
     SA_HIPC(hipMalloc(&h->d_twrec, sizeof(uint4) * 2 * kSaTwRecs));
 
-    // float tables
+    // float tables: the default window and the IIR plans (default = the fixed ALPHA/BETA cascade as real taps;
+    // custom = cleared coefficients), then the twiddles
+    sos_from_q7(kDefaultQ7, h->plan_default.sos);
+    sos_from_q7(h->c12_custom, h->plan_custom.sos);
+    h->plan_default.nsec = h->plan_custom.nsec = 6;
+    default_window(h);
+    if (write_window(h, copy_at_create) != SA_OK) {
+        sa_destroy(h);
+        return SA_EHIP;
+    }
     {
-        std::vector<double> w;
-        default_window_f64(w);
-        std::vector<float> half(SA_NPTS);
-        for (int i = 0; i < SA_NPTS; ++i) half[i] = (float)(0.5 * w[i]);
-        std::vector<float> tr, pa;
-        transpose_window(half, tr);
-        pass_a_window(half, pa);
-        h->half_win = half;
-        h->win64 = w;
-        SA_HIPC(hipMemcpy(h->d_win_b, pa.data(), sizeof(float) * SA_NPTS, hipMemcpyHostToDevice));
-        SA_HIPC(hipMemcpy(h->d_win_t, tr.data(), sizeof(float) * SA_NPTS, hipMemcpyHostToDevice));
         std::vector<float4> ta(6 * 256), tb(8 * 16);
         std::vector<float2> tc(25);
         auto w8192 = [](long e) {                          // exp(-2 pi i e / 8192), e reduced first (exact)
@@ -947,18 +703,6 @@ int sa_create(int device, sa_handle **out)
         SA_HIPC(hipMemcpy(h->d_twT, ta.data(), sizeof(float4) * ta.size(), hipMemcpyHostToDevice));
         SA_HIPC(hipMemcpy(h->d_twB, tb.data(), sizeof(float4) * tb.size(), hipMemcpyHostToDevice));
         SA_HIPC(hipMemcpy(h->d_twC, tc.data(), sizeof(float2) * tc.size(), hipMemcpyHostToDevice));
-    }
-    // IIR plans: default = the fixed ALPHA/BETA cascade as real taps; custom = cleared coefficients
-    {
-        double sos[36];
-        sos_from_q7(kDefaultQ7, sos);
-        build_plan(sos, 6, &h->plan_default, &h->lt_default, h->half_win.data(), h->win_cos);
-        SA_HIPC(hipMemcpy(h->d_lt_default, &h->lt_default, sizeof(SaIirLaneTab), hipMemcpyHostToDevice));
-        sos_from_q7(h->c12_custom, sos);
-        std::memcpy(h->sos_custom, sos, sizeof sos);
-        h->nsec_custom = 6;
-        build_plan(sos, 6, &h->plan_custom, &h->lt_custom, h->half_win.data(), h->win_cos);
-        SA_HIPC(hipMemcpy(h->d_lt_custom, &h->lt_custom, sizeof(SaIirLaneTab), hipMemcpyHostToDevice));
     }
     // integer tables
     {
@@ -1007,16 +751,17 @@ int sa_destroy(sa_handle *h)
     (void)hipSetDevice(h->device);
     // this handle's work only, through handle-owned objects (the caller's streams may be gone already)
     if (h->launched_valid) (void)hipEventSynchronize(h->launched);
-    for (int i = 0; i < sa_handle::kMaxOverlap; ++i) {
-        if (h->ov_stream[i]) (void)hipStreamSynchronize(h->ov_stream[i]);
-        if (h->ov_fork[i]) (void)hipEventDestroy(h->ov_fork[i]);
-        if (h->ov_done[i]) (void)hipEventDestroy(h->ov_done[i]);
-        if (h->ov_stream[i]) (void)hipStreamDestroy(h->ov_stream[i]);
+    for (sa_handle::Slot &s : h->slot) {
+        if (s.stream) (void)hipStreamSynchronize(s.stream);
+        if (s.fork) (void)hipEventDestroy(s.fork);
+        if (s.done) (void)hipEventDestroy(s.done);
+        if (s.stream) (void)hipStreamDestroy(s.stream);
+        for (const sa_handle::Workspace &w : s.work) (void)hipFree(w.ptr);
     }
     if (h->ctl) (void)hipStreamSynchronize(h->ctl);
-    for (int i = 0; i < sa_handle::kStage; ++i) {
-        if (h->stage[i]) (void)hipHostFree(h->stage[i]);
-        if (h->stage_done[i]) (void)hipEventDestroy(h->stage_done[i]);
+    for (sa_handle::Stage &st : h->stage) {
+        if (st.buf) (void)hipHostFree(st.buf);
+        if (st.done) (void)hipEventDestroy(st.done);
     }
     for (hipEvent_t e : h->prof_start) (void)hipEventDestroy(e);
     for (hipEvent_t e : h->prof_stop) (void)hipEventDestroy(e);
@@ -1028,15 +773,13 @@ int sa_destroy(sa_handle *h)
     (void)hipFree(h->d_twT);
     (void)hipFree(h->d_twB);
     (void)hipFree(h->d_twC);
-    (void)hipFree(h->d_lt_default);
-    (void)hipFree(h->d_lt_custom);
     (void)hipFree(h->d_rom);
     (void)hipFree(h->d_twq);
     (void)hipFree(h->d_twrec);
-    for (int i = 0; i < sa_handle::kMaxOverlap; ++i) (void)hipFree(h->d_work[i]);
-    for (int i = 0; i < sa_handle::kMaxOverlap; ++i) (void)hipFree(h->d_work64[i]);
-    (void)hipFree(h->d_p64_default);
-    (void)hipFree(h->d_p64_custom);
+    for (sa_handle::Plan *pl : {&h->plan_default, &h->plan_custom}) {
+        (void)hipFree(pl->d_lt);
+        (void)hipFree(pl->d_p64);
+    }
     (void)hipFree(h->d_win64);
     (void)hipFree(h->d_win_half);
     for (void *p : h->retired) (void)hipFree(p);
@@ -1050,12 +793,7 @@ int sa_reserve(sa_handle *h, int max_batch)
     if (max_batch < 0) return fail(h, SA_ESHAPE, "sa_reserve: negative batch");
     SA_HIP(h, hipSetDevice(h->device));
     if (max_batch > h->reserved_max) h->reserved_max = max_batch;
-    for (int i = 0; i < h->overlap; ++i) {
-        int rc = ensure_work(h, i, max_batch, false);
-        if (rc == SA_OK && h->precision == SA_PRECISION_F64_STATE) rc = ensure_work64(h, i, max_batch, false);
-        if (rc != SA_OK) return rc;
-    }
-    return SA_OK;
+    return grow_slots(h, h->overlap, max_batch, /*geometric=*/true);
 }
 
 int sa_set_overlap(sa_handle *h, int depth)
@@ -1069,28 +807,22 @@ int sa_set_overlap(sa_handle *h, int depth)
     SA_HIP(h, hipSetDevice(h->device));
     // leave the old mode with nothing of the handle's in flight (host wait on the handle's own work only)
     if (h->launched_valid) SA_HIP(h, hipEventSynchronize(h->launched));
-    for (int i = 0; i < sa_handle::kMaxOverlap; ++i) {
-        if (h->ov_used[i]) SA_HIP(h, hipEventSynchronize(h->ov_done[i]));
-        h->ov_unjoined[i] = false;
+    for (sa_handle::Slot &s : h->slot) {
+        if (s.used) SA_HIP(h, hipEventSynchronize(s.done));
+        s.unjoined = false;
     }
+    hipStream_t have[sa_handle::kMaxOverlap];
     for (int i = 0; i < depth; ++i) {
-        if (!h->ov_stream[i]) {
-            const int rc = pick_stream(h, h->ov_stream, i, &h->ov_stream[i]);     // beside the streams the handle already has
+        sa_handle::Slot &s = h->slot[i];
+        if (!s.stream) {
+            const int rc = pick_stream(h, have, i, &s.stream);     // beside the streams the handle already has
             if (rc != SA_OK) return rc;
         }
-        if (!h->ov_fork[i]) SA_HIP(h, hipEventCreateWithFlags(&h->ov_fork[i], hipEventDisableTiming));
-        if (!h->ov_done[i]) SA_HIP(h, hipEventCreateWithFlags(&h->ov_done[i], hipEventDisableTiming));
-        // every slot starts with the workspace the handle already has somewhere
-        int most = 0;
-        for (int j = 0; j < sa_handle::kMaxOverlap; ++j) most = h->work_frames[j] > most ? h->work_frames[j] : most;
-        int rc = ensure_work(h, i, most, false, /*geometric=*/false);
-        if (rc == SA_OK && h->precision == SA_PRECISION_F64_STATE) {
-            int most64 = 0;
-            for (int j = 0; j < sa_handle::kMaxOverlap; ++j) most64 = h->work64_frames[j] > most64 ? h->work64_frames[j] : most64;
-            rc = ensure_work64(h, i, most64, false, /*geometric=*/false);
-        }
-        if (rc != SA_OK) return rc;
+        have[i] = s.stream;
+        if (!s.fork) SA_HIP(h, hipEventCreateWithFlags(&s.fork, hipEventDisableTiming));
+        if (!s.done) SA_HIP(h, hipEventCreateWithFlags(&s.done, hipEventDisableTiming));
     }
+    { const int rc = grow_slots(h, depth, -1, /*geometric=*/false); if (rc != SA_OK) return rc; }
     h->overlap = depth;
     h->ov_calls = 0;
     h->ov_fit_valid = false;
@@ -1114,7 +846,7 @@ int sa_debug_overlap_streams(sa_handle *h, void *stream, int *side_by_side)
     for (int i = 0; i < h->overlap; ++i)
         for (int j = -1; j < i; ++j) {                       // j = -1: the caller's stream
             hipError_t pe = hipSuccess;
-            const int r = streams_run_side_by_side(j < 0 ? (hipStream_t)stream : h->ov_stream[j], h->ov_stream[i], &pe);
+            const int r = streams_run_side_by_side(j < 0 ? (hipStream_t)stream : h->slot[j].stream, h->slot[i].stream, &pe);
             if (r < 0) return fail(h, SA_EHIP, "sa_debug_overlap_streams", pe);
             if (r == 0) *side_by_side = 0;
         }
@@ -1173,10 +905,10 @@ int sa_flush(sa_handle *h, void *stream)
 {
     if (!h) return SA_EINVAL;
     SA_HIP(h, hipSetDevice(h->device));
-    for (int i = 0; i < sa_handle::kMaxOverlap; ++i)
-        if (h->ov_unjoined[i]) {
-            SA_HIP(h, hipStreamWaitEvent((hipStream_t)stream, h->ov_done[i], 0));
-            h->ov_unjoined[i] = false;
+    for (sa_handle::Slot &s : h->slot)
+        if (s.unjoined) {
+            SA_HIP(h, hipStreamWaitEvent((hipStream_t)stream, s.done, 0));
+            s.unjoined = false;
         }
     return SA_OK;
 }
@@ -1284,11 +1016,7 @@ int sa_load_sos_f64(sa_handle *h, const double *sos, int n_sections)
     if (n_sections < 0 || n_sections > SA_MAXSEC) return fail(h, SA_EINVAL, "sa_load_sos: 0..6 sections");
     { const int rc = control_allowed(h); if (rc != SA_OK) return rc; }
     double norm[36];
-    for (int s = 0; s < n_sections; ++s) {
-        const double a0 = sos[6 * s + 3];
-        if (a0 == 0.0 || !std::isfinite(a0)) return fail(h, SA_EINVAL, "sa_load_sos: a0 must be finite and non-zero");
-        for (int i = 0; i < 6; ++i) norm[6 * s + i] = sos[6 * s + i] / a0;
-    }
+    if (!normalise_a0(sos, n_sections, norm)) return fail(h, SA_EINVAL, "sa_load_sos: a0 must be finite and non-zero");
     return set_custom_plan(h, norm, n_sections);
 }
 
@@ -1333,15 +1061,15 @@ int sa_set_window_f32(sa_handle *h, const float *w)
 {
     if (!h) return SA_EINVAL;
     { const int rc = control_allowed(h); if (rc != SA_OK) return rc; }
-    if (w) return set_window_f32_from(h, w);
-    std::vector<double> d;
-    default_window_f64(d);
-    std::vector<float> half(SA_NPTS);
-    for (int i = 0; i < SA_NPTS; ++i) half[i] = (float)(0.5 * d[i]);
-    h->win_is_cos = true;
-    h->win_cos[0] = h->win_cos[1] = 0.5;                  // scripts/hann_coeff.py:3-4
-    h->win64 = d;
-    return upload_window_half(h, half);
+    if (w) {
+        h->half_win.resize(SA_NPTS);
+        for (int i = 0; i < SA_NPTS; ++i) h->half_win[i] = 0.5f * w[i];
+        h->win_is_cos = fit_cosine_window(w, h->win_cos);
+        h->win64.assign(w, w + SA_NPTS);                    // widened exactly
+    } else {
+        default_window(h);
+    }
+    return write_window(h, upload);
 }
 
 int sa_set_window_mode_q15(sa_handle *h, int mode)
@@ -1353,153 +1081,111 @@ int sa_set_window_mode_q15(sa_handle *h, int mode)
     return SA_OK;
 }
 
-static int q15_params(sa_handle *h, SaQ15Params *p)
+static SaQ15Params q15_params(const sa_handle *h)
 {
-    std::memset(p, 0, sizeof(*p));
-    p->win_mode = h->win_mode_q15;
-    p->filter = h->filter_mode;
-    p->nsec_wide = h->nsec_q14;
-    if (h->filter_mode == SA_FILTER_DEFAULT) std::memcpy(p->c12, kDefaultQ7, 12);
-    else std::memcpy(p->c12, h->c12_custom, 12);
-    std::memcpy(p->sos_q14, h->sos_q14, sizeof p->sos_q14);
-    if (h->filter_mode == SA_FILTER_WIDE && h->nsec_q14 == 0) p->filter = SA_FILTER_NONE;   // no sections = wire
-    return SA_OK;
+    SaQ15Params p;
+    std::memset(&p, 0, sizeof p);
+    p.win_mode = h->win_mode_q15;
+    p.filter = h->filter_mode;
+    p.nsec_wide = h->nsec_q14;
+    std::memcpy(p.c12, h->filter_mode == SA_FILTER_DEFAULT ? kDefaultQ7 : h->c12_custom, 12);
+    std::memcpy(p.sos_q14, h->sos_q14, sizeof p.sos_q14);
+    if (h->filter_mode == SA_FILTER_WIDE && h->nsec_q14 == 0) p.filter = SA_FILTER_NONE;   // no sections = wire
+    return p;
 }
 
-int sa_filter_q15(sa_handle *h, const int16_t *in, int16_t *out_time, int batch, void *stream)
+// sa_filter_q15 (`fft` false: window + integer cascade into `out`) and sa_process_q15; `fn` names the entry point
+static int process_q15(sa_handle *h, const char *fn, const int16_t *in, int16_t *out, int batch, void *stream, bool fft)
 {
     if (!h) return SA_EINVAL;
-    if (batch < 0) return fail(h, SA_ESHAPE, "sa_filter_q15: negative batch");
+    if (batch < 0) return fail_at(h, SA_ESHAPE, fn, "negative batch");
     if (batch == 0) return SA_OK;
-    if (!in || !out_time) return fail(h, SA_EINVAL, "sa_filter_q15: NULL tensor");
+    if (!in || !out) return fail_at(h, SA_EINVAL, fn, "NULL tensor");
     SA_HIP(h, hipSetDevice(h->device));
+    const SaQ15Params p = q15_params(h);
+    const bool staged = fft && p.filter != SA_FILTER_NONE;      // cascade into the slot's workspace, then the FFT
     CallCtx c;
-    { const int rc = begin_call(h, (hipStream_t)stream, &c); if (rc != SA_OK) return rc; }
-    SaQ15Params p;
-    q15_params(h, &p);
+    { const int rc = begin_call(h, (hipStream_t)stream, staged ? sa_handle::kWorkQ15 : -1, batch, &c); if (rc != SA_OK) return rc; }
     const SaQ15Tables t = {h->d_rom, h->d_twq, h->d_twrec};
-    SA_HIP(h, sa_launch_filter_q15(in, out_time, batch, p, t, c.stream, {c.start, c.stop}));
-    return end_call(h, c);
-}
-
-int sa_process_q15(sa_handle *h, const int16_t *in, int16_t *out_iq, int batch, void *stream)
-{
-    if (!h) return SA_EINVAL;
-    if (batch < 0) return fail(h, SA_ESHAPE, "sa_process_q15: negative batch");
-    if (batch == 0) return SA_OK;
-    if (!in || !out_iq) return fail(h, SA_EINVAL, "sa_process_q15: NULL tensor");
-    SA_HIP(h, hipSetDevice(h->device));
-    CallCtx c;
-    { const int rc = begin_call(h, (hipStream_t)stream, &c); if (rc != SA_OK) return rc; }
-    SaQ15Params p;
-    q15_params(h, &p);
-    const SaQ15Tables t = {h->d_rom, h->d_twq, h->d_twrec};
-    if (p.filter == SA_FILTER_NONE) {
-        SA_HIP(h, sa_launch_fft_q15(in, out_iq, batch, true, p, t, c.stream, {c.start, c.stop}));
+    if (!staged) {
+        SA_HIP(h, fft ? sa_launch_fft_q15(in, out, batch, true, p, t, c.stream, {c.start, c.stop})
+                      : sa_launch_filter_q15(in, out, batch, p, t, c.stream, {c.start, c.stop}));
         return end_call(h, c);
     }
-    { const int rc = ensure_work(h, c.slot, batch, c.captured); if (rc != SA_OK) return rc; }
     // The WIDE cascade does not gain from overlapped launches (tools/q15_overlap_modes.py, profiles/r4_q15_helper_waves.txt):
     // its step is made of packed dot products, the integer FFT's twiddle products are too, and side by side the two starve
     // each other -- 7.5-7.9 M frames/s at depth 2 when left free against 8.3 M stream-ordered.  At depth 2 its cascade
     // therefore waits for the previous call of the handle (8.0 M; at depth 3 it runs free: 7.9-8.2 M).
-    const bool wide = p.filter == SA_FILTER_WIDE;
-    if (c.overlapped && wide && h->overlap == 2) {
-        const int prev = (c.slot + h->overlap - 1) % h->overlap;
-        if (h->ov_used[prev]) SA_HIP(h, hipStreamWaitEvent(c.stream, h->ov_done[prev], 0));
+    if (c.overlapped && p.filter == SA_FILTER_WIDE && h->overlap == 2) {
+        const sa_handle::Slot &prev = h->slot[(c.slot + h->overlap - 1) % h->overlap];
+        if (prev.used) SA_HIP(h, hipStreamWaitEvent(c.stream, prev.done, 0));
     }
-    SA_HIP(h, sa_launch_filter_q15(in, h->d_work[c.slot], batch, p, t, c.stream, {c.start, nullptr}));
-    SA_HIP(h, sa_launch_fft_q15(h->d_work[c.slot], out_iq, batch, false, p, t, c.stream, {nullptr, c.stop}));
+    int16_t *ws = (int16_t *)h->slot[c.slot].work[sa_handle::kWorkQ15].ptr;
+    SA_HIP(h, sa_launch_filter_q15(in, ws, batch, p, t, c.stream, {c.start, nullptr}));
+    SA_HIP(h, sa_launch_fft_q15(ws, out, batch, false, p, t, c.stream, {nullptr, c.stop}));
     return end_call(h, c);
 }
 
-// SA_PRECISION_F64_STATE with a cascade (DEFAULT, or CUSTOM with at least one section): the plan the first launch uses
-// and its padded section count; null when the call takes the float32 path (every other case, filter NONE included).
-static const SaIirF64 *f64_plan(const sa_handle *h, int *nsec)
+int sa_filter_q15(sa_handle *h, const int16_t *in, int16_t *out_time, int batch, void *stream)
 {
-    if (h->precision != SA_PRECISION_F64_STATE) return nullptr;
-    if (h->filter_mode == SA_FILTER_DEFAULT) {
-        *nsec = h->plan_default.nsec;
-        return h->d_p64_default;
-    }
-    if (h->filter_mode == SA_FILTER_CUSTOM && h->plan_custom.nsec > 0) {
-        *nsec = h->plan_custom.nsec;
-        return h->d_p64_custom;
-    }
-    return nullptr;
+    return process_q15(h, "sa_filter_q15", in, out_time, batch, stream, false);
 }
 
-// The float64-state call: iir_f64.hip (window + cascade in double, y rounded once) into the slot's workspace, then the
-// bypassed float chain on y with the constant 1/2 window (exact).  SA_OUT_TIME is the first launch alone, into `out`.
-// Timed as one call: the start event rides on the first kernel, the stop event on the last.
-static int launch_f64(sa_handle *h, const void *in, bool i16, float scale, void *out, int batch, int out_kind,
-                      const CallCtx &c, const SaIirF64 *plan, int nsec)
+int sa_process_q15(sa_handle *h, const int16_t *in, int16_t *out_iq, int batch, void *stream)
 {
-    if (out_kind == SA_OUT_TIME) {
-        SA_HIP(h, sa_launch_iir_f64(in, i16, scale, (float *)out, batch, nsec, plan, h->d_win64, c.stream, {c.start, c.stop}));
+    return process_q15(h, "sa_process_q15", in, out_iq, batch, stream, true);
+}
+
+// sa_process_f32 (float frames) and sa_process_f32_i16 (int16 samples times `scale`); `fn` names the entry point.
+// The float32 path: one launch of the fused chain.  The section coefficients and predictor taps travel by value in the
+// kernel arguments (stream-ordered by construction); the per-lane matrices and the window live in device memory
+// (stream-ordered uploads).
+// The float64-state path (SA_PRECISION_F64_STATE with a cascade: DEFAULT, or CUSTOM with at least one section):
+// iir_f64.hip (window + cascade in double, y rounded once) into the slot's workspace, then the bypassed float chain on
+// y with the constant 1/2 window (exact).  SA_OUT_TIME is the first launch alone, into `out`.  Timed as one call: the
+// start event rides on the first kernel, the stop event on the last.
+static int process_float(sa_handle *h, const char *fn, const void *in, bool i16, float scale, void *out, int batch,
+                         int out_kind, void *stream)
+{
+    if (!h) return SA_EINVAL;
+    if (batch < 0) return fail_at(h, SA_ESHAPE, fn, "negative batch");
+    if (out_kind < SA_OUT_MAG_FULL || out_kind > SA_OUT_TIME) return fail_at(h, SA_EINVAL, fn, "bad out_kind");
+    if (!(scale == scale) || scale - scale != 0.f) return fail_at(h, SA_EINVAL, fn, "scale is not finite");
+    if (batch == 0) return SA_OK;
+    if (!in || !out) return fail_at(h, SA_EINVAL, fn, "NULL tensor");
+    if (h->filter_mode == SA_FILTER_WIDE)
+        return fail_at(h, SA_ESTATE, fn, "filter mode 0xA2 (Q2.14) belongs to the Q15 path; use 0xA1 with sa_load_sos_f32");
+    SA_HIP(h, hipSetDevice(h->device));
+    const sa_handle::Plan &pl = active_plan(h);
+    const bool cascade = h->filter_mode != SA_FILTER_NONE;
+    const bool f64 = h->precision == SA_PRECISION_F64_STATE && cascade && pl.k.nsec > 0;
+    const bool two = f64 && out_kind != SA_OUT_TIME;
+    CallCtx c;
+    { const int rc = begin_call(h, (hipStream_t)stream, two ? sa_handle::kWorkF64 : -1, batch, &c); if (rc != SA_OK) return rc; }
+    SaF32Tables t = {h->d_win_b, h->d_win_t, h->d_twT, h->d_twB, h->d_twC, pl.d_lt, cascade ? &pl.k : nullptr};
+    if (!f64) {
+        SA_HIP(h, i16 ? sa_launch_chain_f32_i16((const int16_t *)in, scale, out, batch, out_kind, t, c.stream, {c.start, c.stop})
+                      : sa_launch_chain_f32((const float *)in, out, batch, out_kind, t, c.stream, {c.start, c.stop}));
         return end_call(h, c);
     }
-    { const int rc = ensure_work64(h, c.slot, batch, c.captured); if (rc != SA_OK) return rc; }
-    float *ws = h->d_work64[c.slot];
-    SA_HIP(h, sa_launch_iir_f64(in, i16, scale, ws, batch, nsec, plan, h->d_win64, c.stream, {c.start, nullptr}));
-    const SaF32Tables t = {h->d_win_half, h->d_win_t, h->d_twT, h->d_twB, h->d_twC, h->d_lt_custom, nullptr};
-    SA_HIP(h, sa_launch_chain_f32(ws, out, batch, out_kind, t, c.stream, {nullptr, c.stop}));
+    float *y = two ? (float *)h->slot[c.slot].work[sa_handle::kWorkF64].ptr : (float *)out;
+    SA_HIP(h, sa_launch_iir_f64(in, i16, scale, y, batch, pl.k.nsec, pl.d_p64, h->d_win64, c.stream,
+                                {c.start, two ? nullptr : c.stop}));
+    if (two) {
+        t = {h->d_win_half, h->d_win_t, h->d_twT, h->d_twB, h->d_twC, h->plan_custom.d_lt, nullptr};
+        SA_HIP(h, sa_launch_chain_f32(y, out, batch, out_kind, t, c.stream, {nullptr, c.stop}));
+    }
     return end_call(h, c);
 }
 
 int sa_process_f32(sa_handle *h, const float *in, void *out, int batch, int out_kind, void *stream)
 {
-    if (!h) return SA_EINVAL;
-    if (batch < 0) return fail(h, SA_ESHAPE, "sa_process_f32: negative batch");
-    if (out_kind < SA_OUT_MAG_FULL || out_kind > SA_OUT_TIME) return fail(h, SA_EINVAL, "sa_process_f32: bad out_kind");
-    if (batch == 0) return SA_OK;
-    if (!in || !out) return fail(h, SA_EINVAL, "sa_process_f32: NULL tensor");
-    if (h->filter_mode == SA_FILTER_WIDE)
-        return fail(h, SA_ESTATE, "sa_process_f32: filter mode 0xA2 (Q2.14) belongs to the Q15 path; use 0xA1 with sa_load_sos_f32");
-    SA_HIP(h, hipSetDevice(h->device));
-    CallCtx c;
-    { const int rc = begin_call(h, (hipStream_t)stream, &c); if (rc != SA_OK) return rc; }
-    int nsec64 = 0;
-    if (const SaIirF64 *p64 = f64_plan(h, &nsec64)) return launch_f64(h, in, false, 1.f, out, batch, out_kind, c, p64, nsec64);
-    // The section coefficients and predictor taps travel by value in the kernel arguments (stream-ordered
-    // by construction); the per-lane matrices and the window live in device memory (stream-ordered uploads).
-    SaF32Tables t = {h->d_win_b, h->d_win_t, h->d_twT, h->d_twB, h->d_twC, h->d_lt_custom, nullptr};
-    if (h->filter_mode == SA_FILTER_DEFAULT) {
-        t.lanetab = h->d_lt_default;
-        t.iir = &h->plan_default;
-    } else if (h->filter_mode == SA_FILTER_CUSTOM) {
-        t.lanetab = h->d_lt_custom;
-        t.iir = &h->plan_custom;
-    }
-    SA_HIP(h, sa_launch_chain_f32(in, out, batch, out_kind, t, c.stream, {c.start, c.stop}));
-    return end_call(h, c);
+    return process_float(h, "sa_process_f32", in, false, 1.f, out, batch, out_kind, stream);
 }
 
 int sa_process_f32_i16(sa_handle *h, const int16_t *in, float scale, void *out, int batch, int out_kind, void *stream)
 {
-    if (!h) return SA_EINVAL;
-    if (batch < 0) return fail(h, SA_ESHAPE, "sa_process_f32_i16: negative batch");
-    if (out_kind < SA_OUT_MAG_FULL || out_kind > SA_OUT_TIME) return fail(h, SA_EINVAL, "sa_process_f32_i16: bad out_kind");
-    if (!(scale == scale) || scale - scale != 0.f) return fail(h, SA_EINVAL, "sa_process_f32_i16: scale is not finite");
-    if (batch == 0) return SA_OK;
-    if (!in || !out) return fail(h, SA_EINVAL, "sa_process_f32_i16: NULL tensor");
-    if (h->filter_mode == SA_FILTER_WIDE)
-        return fail(h, SA_ESTATE, "sa_process_f32_i16: filter mode 0xA2 (Q2.14) belongs to the Q15 path; use 0xA1 with sa_load_sos_f32");
-    SA_HIP(h, hipSetDevice(h->device));
-    CallCtx c;
-    { const int rc = begin_call(h, (hipStream_t)stream, &c); if (rc != SA_OK) return rc; }
-    int nsec64 = 0;
-    if (const SaIirF64 *p64 = f64_plan(h, &nsec64)) return launch_f64(h, in, true, scale, out, batch, out_kind, c, p64, nsec64);
-    SaF32Tables t = {h->d_win_b, h->d_win_t, h->d_twT, h->d_twB, h->d_twC, h->d_lt_custom, nullptr};
-    if (h->filter_mode == SA_FILTER_DEFAULT) {
-        t.lanetab = h->d_lt_default;
-        t.iir = &h->plan_default;
-    } else if (h->filter_mode == SA_FILTER_CUSTOM) {
-        t.lanetab = h->d_lt_custom;
-        t.iir = &h->plan_custom;
-    }
-    SA_HIP(h, sa_launch_chain_f32_i16(in, scale, out, batch, out_kind, t, c.stream, {c.start, c.stop}));
-    return end_call(h, c);
+    return process_float(h, "sa_process_f32_i16", in, true, scale, out, batch, out_kind, stream);
 }
 
 int sa_pack_frame(const int16_t *iq_host, uint8_t *frame_bytes)
@@ -1516,19 +1202,15 @@ int sa_pack_frame(const int16_t *iq_host, uint8_t *frame_bytes)
 int sa_debug_iir_plan_f32(const sa_handle *h, float *out, int cap)
 {
     if (!h) return SA_EINVAL;
-    const bool def = h->filter_mode == SA_FILTER_DEFAULT;
-    return export_plan(def ? h->plan_default : h->plan_custom, def ? h->lt_default : h->lt_custom, out, cap);
+    const sa_handle::Plan &pl = active_plan(h);
+    return export_plan(pl.k, pl.lt, out, cap);
 }
 
 int sa_iir_plan_from_sos(const double *sos, int n_sections, float *out, int cap)
 {
     if (!sos || n_sections < 0 || n_sections > SA_MAXSEC) return SA_EINVAL;
     double norm[36];
-    for (int s = 0; s < n_sections; ++s) {
-        const double a0 = sos[6 * s + 3];
-        if (a0 == 0.0 || !std::isfinite(a0)) return SA_EINVAL;
-        for (int i = 0; i < 6; ++i) norm[6 * s + i] = sos[6 * s + i] / a0;
-    }
+    if (!normalise_a0(sos, n_sections, norm)) return SA_EINVAL;
     SaIirK p;
     std::vector<SaIirLaneTab> lt(1);
     build_plan(norm, n_sections, &p, &lt[0], nullptr);
@@ -1547,8 +1229,8 @@ int sa_set_precision(sa_handle *h, int precision)
         return SA_OK;
     }
     SA_HIP(h, hipSetDevice(h->device));
-    if (!h->d_p64_default) SA_HIP(h, hipMalloc(&h->d_p64_default, sizeof(SaIirF64)));
-    if (!h->d_p64_custom) SA_HIP(h, hipMalloc(&h->d_p64_custom, sizeof(SaIirF64)));
+    for (sa_handle::Plan *pl : {&h->plan_default, &h->plan_custom})
+        if (!pl->d_p64) SA_HIP(h, hipMalloc(&pl->d_p64, sizeof(SaIirF64)));
     if (!h->d_win64) SA_HIP(h, hipMalloc(&h->d_win64, sizeof(double) * SA_NPTS));
     if (!h->d_win_half) SA_HIP(h, hipMalloc(&h->d_win_half, sizeof(float) * SA_NPTS));
     // the FFT launch's window: 1/2 everywhere, laid out by the code that lays out the handle's own window table
@@ -1556,7 +1238,7 @@ int sa_set_precision(sa_handle *h, int precision)
     pass_a_window(half, pa);
     int rc = upload(h, h->d_win_half, pa.data(), sizeof(float) * SA_NPTS);
     if (rc == SA_OK) rc = sync_f64(h, true, /*force=*/true);      // tables were not kept up to date outside the mode
-    for (int i = 0; i < h->overlap && rc == SA_OK; ++i) rc = ensure_work64(h, i, h->reserved_max, false, /*geometric=*/false);
+    if (rc == SA_OK) rc = grow_slots(h, h->overlap, h->reserved_max, /*geometric=*/false, /*f64_only=*/true);
     if (rc != SA_OK) return rc;
     h->precision = precision;
     return SA_OK;
@@ -1572,14 +1254,9 @@ int sa_get_precision(const sa_handle *h, int *precision)
 int sa_debug_iir_plan_f64(const sa_handle *h, double *out, int cap)
 {
     if (!h || cap < 0) return SA_EINVAL;
+    const sa_handle::Plan &pl = active_plan(h);
     SaIirF64 p;
-    if (h->filter_mode == SA_FILTER_DEFAULT) {
-        double sos[36];
-        sos_from_q7(kDefaultQ7, sos);
-        build_plan_f64(sos, 6, &p);
-    } else {
-        build_plan_f64(h->sos_custom, h->nsec_custom, &p);
-    }
+    build_plan_f64(pl.sos, pl.nsec, &p);
     if (out && cap > 0) std::memcpy(out, &p, sizeof(double) * (size_t)(cap < kSaIirF64Doubles ? cap : kSaIirF64Doubles));
     return kSaIirF64Doubles;
 }

@@ -377,6 +377,16 @@ def test_overlap_mode_keeps_lent_tensors_alive(ch, torch_mod):
         assert len(ch._lent) == 0
         for k, o in outs:
             assert torch.equal(o, ref[k]), (depth, k)
+        # the same depth again returns without a host wait: the calls in flight keep their tensors
+        outs = [(k, ch.process_f32(x.clone())) for k, x in enumerate(xs[:depth])]     # inputs are temporaries
+        lent = len(ch._lent)
+        ch.set_overlap(depth)
+        assert len(ch._lent) == lent == depth - 1
+        scribble = torch.full_like(xs[0], float("nan"))     # would land in an input block released too early
+        del scribble
+        ch.flush()
+        for k, o in outs:
+            assert torch.equal(o, ref[k]), (depth, k, "same-depth set_overlap")
     ch.set_overlap(1)
     assert len(ch._lent) == 0
 
