@@ -20,7 +20,7 @@ SA_N = 16384
 SA_FRAME_BYTES = 65536
 SA_FILTER_DEFAULT, SA_FILTER_CUSTOM, SA_FILTER_NONE, SA_FILTER_WIDE = 0x00, 0xA1, 0xB1, 0xA2
 SA_WIN_RTL_SIGNED, SA_WIN_HANN_U16 = 0, 1
-SA_OUT_MAG_FULL, SA_OUT_MAG_HALF, SA_OUT_SPEC_HALF, SA_OUT_TIME = 0, 1, 2, 3
+SA_OUT_MAG_FULL, SA_OUT_MAG_HALF, SA_OUT_SPEC_HALF, SA_OUT_TIME, SA_OUT_MARKER = 0, 1, 2, 3, 4
 SA_PRECISION_F32, SA_PRECISION_F64_STATE = 0, 1
 
 
@@ -104,6 +104,8 @@ def lib() -> C.CDLL:
     L.sa_get_precision.argtypes = [H, C.POINTER(C.c_int)]
     L.sa_debug_iir_plan_f64.argtypes = [H, C.POINTER(C.c_double), C.c_int]
     L.sa_iir_plan_from_sos_f64.argtypes = [C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_double), C.c_int]
+    L.sa_set_marker_range.argtypes = [H, C.c_int, C.c_int]
+    L.sa_get_marker_range.argtypes = [H, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     for name in ("sa_create", "sa_destroy", "sa_abi_version", "sa_reserve", "sa_set_overlap", "sa_get_overlap",
                  "sa_debug_overlap_streams", "sa_flush", "sa_set_profiling", "sa_profile_read", "sa_set_filter_mode",
                  "sa_get_filter_mode", "sa_load_coeffs_q7", "sa_get_coeffs_q7", "sa_feed_command_bytes",
@@ -112,7 +114,7 @@ def lib() -> C.CDLL:
                  "sa_set_window_f32", "sa_set_window_mode_q15", "sa_get_window_q15", "sa_process_q15",
                  "sa_filter_q15", "sa_process_f32", "sa_process_f32_i16", "sa_pack_frame", "sa_debug_iir_plan_f32",
                  "sa_iir_plan_from_sos", "sa_set_precision", "sa_get_precision", "sa_debug_iir_plan_f64",
-                 "sa_iir_plan_from_sos_f64"):
+                 "sa_iir_plan_from_sos_f64", "sa_set_marker_range", "sa_get_marker_range"):
         getattr(L, name).restype = C.c_int
     _lib = L
     return L

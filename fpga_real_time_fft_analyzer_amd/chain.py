@@ -17,7 +17,7 @@ import torch
 
 from . import abi
 from .abi import (SA_FILTER_CUSTOM, SA_FILTER_DEFAULT, SA_FILTER_NONE, SA_FILTER_WIDE, SA_N,
-                  SA_OUT_MAG_FULL, SA_OUT_MAG_HALF, SA_OUT_SPEC_HALF, SA_OUT_TIME, SA_PRECISION_F32,
+                  SA_OUT_MAG_FULL, SA_OUT_MAG_HALF, SA_OUT_MARKER, SA_OUT_SPEC_HALF, SA_OUT_TIME, SA_PRECISION_F32,
                   SA_PRECISION_F64_STATE, SpecanError)
 
 # command bytes, same names as gui.py:28-37
@@ -38,7 +38,7 @@ FFT_SIZE = 16384                # gui.py:44
 FS_HZ = 1_000_000.0             # gui.py:45
 
 _OUT_KINDS = {"mag_full": SA_OUT_MAG_FULL, "mag_half": SA_OUT_MAG_HALF, "spec_half": SA_OUT_SPEC_HALF,
-              "time": SA_OUT_TIME}
+              "time": SA_OUT_TIME, "marker": SA_OUT_MARKER}
 _PRECISIONS = {"f32": SA_PRECISION_F32, "f64": SA_PRECISION_F64_STATE}
 
 
@@ -295,11 +295,24 @@ class SpectrumChain:
         self._lib.sa_debug_iir_plan_f64(self._h, out.ctypes.data_as(C.POINTER(C.c_double)), n)
         return out
 
+    def set_marker_range(self, lo: int, hi: int):
+        """The full-spectrum bins [lo, hi) that ``out_kind='marker'`` covers (include/specan.h, sa_set_marker_range):
+        0 <= lo < hi <= 16384, [0, 16384) by default.  frames.bin_range_from_permille maps the gui's per-mille range.
+        Stream-ordered; the 0xFF reset leaves it alone."""
+        self._ctl(self._lib.sa_set_marker_range(self._h, int(lo), int(hi)))
+
+    @property
+    def marker_range(self) -> tuple:
+        lo, hi = C.c_int(), C.c_int()
+        self._check(self._lib.sa_get_marker_range(self._h, C.byref(lo), C.byref(hi)))
+        return lo.value, hi.value
+
     # ------------------------------------------------------------------ data plane
     def process_f32(self, x: torch.Tensor, out: Optional[torch.Tensor] = None, out_kind: str = "mag_full",
                     scale: float = 1.0 / 2048.0):
         """[B,16384] float32 -> per ``out_kind``: 'mag_full' [B,16384] f32, 'mag_half' [B,8193] f32,
-        'spec_half' [B,8193] complex64, 'time' [B,16384] f32.
+        'spec_half' [B,8193] complex64, 'time' [B,16384] f32, 'marker' [B,4] int32 (one sa_marker per frame:
+        peak_mag as float32 bits, peak_bin, band_power as float32 bits, 0; see :meth:`markers`).
 
         An int16 tensor (the ADC's samples, what the ingest front-end delivers) takes the same float path through
         sa_process_f32_i16: x = float(sample) * ``scale``, rounded once, no conversion pass; ``scale`` is ignored for
@@ -312,6 +325,8 @@ class SpectrumChain:
             shape, dt = (B, SA_N), torch.float32
         elif out_kind == "mag_half":
             shape, dt = (B, SA_N // 2 + 1), torch.float32
+        elif out_kind == "marker":
+            shape, dt = (B, 4), torch.int32
         else:
             shape, dt = (B, SA_N // 2 + 1), torch.complex64
         if out is None:
@@ -326,6 +341,14 @@ class SpectrumChain:
                                                  self._stream()))
         self._lend(x, out)
         return out
+
+    def markers(self, x: torch.Tensor, out: Optional[torch.Tensor] = None, scale: float = 1.0 / 2048.0):
+        """Peak search and band power over the marker range, per frame: ``(peak_mag float32 [B], peak_bin int32 [B],
+        band_power float32 [B])``, views of the [B,4] int32 record tensor (``out``, allocated when None) that
+        ``process_f32(x, out, 'marker', scale)`` fills.  peak_mag is the 'mag_full' value at peak_bin, bit for bit."""
+        rec = self.process_f32(x, out, out_kind="marker", scale=scale)
+        f = rec.view(torch.float32)
+        return f[:, 0], rec[:, 1], f[:, 2]
 
     def process_q15(self, x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """[B,16384] int16 -> [B,16384,2] int16 (re, im): B frames of 65536 bytes."""

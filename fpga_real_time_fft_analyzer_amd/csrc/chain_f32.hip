@@ -17,7 +17,8 @@
 //     each factor in registers (fft_regs.hpp), then the split step X[k] = Xe[k] + W_N^k Xo[k].
 //     Taps and scan matrices live in the section's pole coordinates (sa_common.hpp): float32 accuracy
 //     then matches a sequential evaluation also for poles next to the real axis.
-//   * all 16384 magnitudes are written (upper half mirrored) as aligned 16-byte nontemporal stores.
+//   * all 16384 magnitudes are written (upper half mirrored) as aligned 16-byte nontemporal stores, or, for
+//     SA_OUT_MARKER, reduced in place to one 16-byte record per frame (peak, its bin, band power).
 // The factor 1/2 of the split step is folded into the window table (exact in binary fp).
 #include "chain_f32_dev.hpp"
 
@@ -534,12 +535,14 @@ __device__ __forceinline__ int zpos_partner(int w) { return zrow_pos(w, (4 + (w 
 // requested at once into a 64 KiB LDS image instead of two half-frame rounds -- one HBM round trip and one barrier
 // fewer per frame, at two workgroups per CU instead of four, which costs nothing while the batch leaves the CUs
 // half empty anyway (B <= 512: at most two workgroups per CU either way).
+// mlo, mhi: the marker range [mlo, mhi) of full-spectrum bins; read by the SA_OUT_MARKER instantiations only.
 template <int NSEC, bool UNIT, int OUT, bool WINGEN, bool ONE_ROUND, typename PlanT>
 __device__ __forceinline__ void chain_frame(const sa_in_t *__restrict__ in, SA_IN_SCALE_PARAM void *__restrict__ out,
                                             const int f, unsigned char *smem,
                                             const float4 *__restrict__ winb, const float4 *__restrict__ twT,
                                             const float4 *__restrict__ twB, const float2 *__restrict__ twC,
-                                            const SaIirLaneTab *__restrict__ lanetab, const PlanT &ka)
+                                            const SaIirLaneTab *__restrict__ lanetab, const PlanT &ka,
+                                            const int mlo = 0, const int mhi = 0)
 {
     cf *ldc = reinterpret_cast<cf *>(smem);
     float2 *scr = reinterpret_cast<float2 *>(smem + kScrOff);
@@ -664,9 +667,11 @@ __device__ __forceinline__ void chain_frame(const sa_in_t *__restrict__ in, SA_I
     // The split-step anchors W_16384^(4 t), W_16384^(4 (t + 1)) ride along for the full-spectrum output (round 4: requested
     // right before the split step their L2 round trip was exposed once per frame -- 103.8 -> 97.0 us on the bypassed chain
     // at B = 4096, 11.5 -> 10.8 us at B = 256, -1 % with the cascade, gpurun_out/ab_an5.txt).  The half-spectrum variants
-    // keep the late request: four more registers through three FFT passes make them spill.
+    // keep the late request: four more registers through three FFT passes make them spill.  The marker, whose epilogue
+    // holds no staging registers either, takes the early one.
+    constexpr bool AN5_EARLY = OUT == SA_OUT_MAG_FULL || OUT == SA_OUT_MARKER;
     float4 an5_early = make_float4(0.f, 0.f, 0.f, 0.f);
-    if constexpr (OUT == SA_OUT_MAG_FULL) an5_early = twT[5 * 256 + t];
+    if constexpr (AN5_EARLY) an5_early = twT[5 * 256 + t];
     safft::fft_dit<32>(a);
     {
         const cf wb[8] = {{1.f, 0.f}, {an[0].x, an[0].y}, {an[0].z, an[0].w}, {an[1].x, an[1].y},
@@ -737,8 +742,9 @@ __device__ __forceinline__ void chain_frame(const sa_in_t *__restrict__ in, SA_I
     int ts = t;
     asm volatile("" : "+v"(ts));
     float4 an5 = an5_early;
-    if constexpr (OUT != SA_OUT_MAG_FULL) an5 = twT[5 * 256 + ts];
+    if constexpr (!AN5_EARLY) an5 = twT[5 * 256 + ts];
     const cf wP = {an5.x, an5.y}, wPn = {an5.z, an5.w};
+    MarkerAcc mk = {-1.f, SA_NPTS, 0.f};                   // SA_OUT_MARKER: this thread's part of the record
     // ---- natural-order image + split step, two rounds: round 0 = d in {0..3,12..15} (bins k < 2048
     //      and their partners), round 1 = d in {4..11}.  Z[2048] and Z[6144] sit on the seam and
     //      travel through two side slots.
@@ -797,7 +803,9 @@ __device__ __forceinline__ void chain_frame(const sa_in_t *__restrict__ in, SA_I
             cf R[5], I[5];
 #pragma unroll
             for (int e = 0; e < 5; ++e) split_eval(zk[e], zm[e], w[e], R[e], I[e]);
-            if constexpr (!HALF) {
+            if constexpr (OUT == SA_OUT_MARKER) {
+                marker_group(R, I, k0, __builtin_amdgcn_readfirstlane(k0), mlo, mhi, mk);     // lane 0: the wave's first group
+            } else if constexpr (!HALF) {
                 split_store<OUT>(R, I, out, f, k0);
             } else if constexpr (OUT == SA_OUT_SPEC_HALF) {
 #pragma unroll
@@ -854,6 +862,8 @@ __device__ __forceinline__ void chain_frame(const sa_in_t *__restrict__ in, SA_I
             }
         }
     }
+    // the scan scratch has been idle since the cascade; the barrier inside orders the half-wave parts before thread 0
+    if constexpr (OUT == SA_OUT_MARKER) marker_finish(mk, reinterpret_cast<float4 *>(scr), out, f, t);
     SA_STAMP(11);
 #ifdef SA_STAMPS
     __builtin_amdgcn_s_waitcnt(0);      // drain the stores so the last stamp sees them retire
@@ -883,6 +893,26 @@ __global__ __launch_bounds__(kThreads, 4) void chain_f32_kernel(const sa_in_t *_
     int f = blockIdx.x;
     if (f >= batch) return;
     chain_frame<NSEC, UNIT, OUT, WINGEN, ONE_ROUND>(in, SA_IN_SCALE_ARG out, f, smem, winb, twT, twB, twC, lanetab, ka);
+}
+
+// SA_OUT_MARKER: the same chain with the marker range [lo, hi) in its arguments (chain_f32_kernel keeps its own), packed
+// as lo | hi << 16 into one word: one scalar register held through the kernel, not two (the six-section variants run
+// out of scalar registers)
+template <int NSEC, bool UNIT, bool WINGEN, bool ONE_ROUND = false>
+__global__ __launch_bounds__(kThreads, 4) void chain_marker_kernel(const sa_in_t *__restrict__ in, SA_IN_SCALE_PARAM
+                                                                    void *__restrict__ out, int batch, int range,
+                                                                    const float4 *__restrict__ winb,
+                                                                    const float4 *__restrict__ twT,
+                                                                    const float4 *__restrict__ twB,
+                                                                    const float2 *__restrict__ twC,
+                                                                    const SaIirLaneTab *__restrict__ lanetab,
+                                                                    const SaIirK ka)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    int f = blockIdx.x;
+    if (f >= batch) return;
+    chain_frame<NSEC, UNIT, SA_OUT_MARKER, WINGEN, ONE_ROUND>(in, SA_IN_SCALE_ARG out, f, smem, winb, twT, twB, twC,
+                                                               lanetab, ka, range & 0xFFFF, range >> 16);
 }
 
 // Window (+ IIR) only: the FFT input time series (debug / parity output, not a hot path: two workgroups per CU are
@@ -979,6 +1009,14 @@ hipError_t launch_nsec(const sa_in_t *in, const float in_scale, void *out, int b
             case SA_OUT_MAG_FULL: SA_LAUNCH1(SA_OUT_MAG_FULL); break;
             case SA_OUT_MAG_HALF: SA_LAUNCH1(SA_OUT_MAG_HALF); break;
             case SA_OUT_SPEC_HALF: SA_LAUNCH1(SA_OUT_SPEC_HALF); break;
+            case SA_OUT_MARKER: {
+                auto kern = chain_marker_kernel<0, false, false, true>;
+                e = sa_set_dyn_lds_once(reinterpret_cast<const void *>(kern), kLdsOneRound);
+                if (e != hipSuccess) return e;
+                hipExtLaunchKernelGGL(kern, grid, block, kLdsOneRound, stream, ev.start, ev.stop, 0, in, out, batch,
+                                      tb.marker_lo | tb.marker_hi << 16, tb.win_b, tb.twT, tb.twB, tb.twC, tb.lanetab, ka);
+                break;
+            }
             default: return hipErrorInvalidValue;
         }
 #undef SA_LAUNCH1
@@ -998,6 +1036,14 @@ hipError_t launch_nsec(const sa_in_t *in, const float in_scale, void *out, int b
         case SA_OUT_MAG_FULL: SA_LAUNCH(SA_OUT_MAG_FULL); break;
         case SA_OUT_MAG_HALF: SA_LAUNCH(SA_OUT_MAG_HALF); break;
         case SA_OUT_SPEC_HALF: SA_LAUNCH(SA_OUT_SPEC_HALF); break;
+        case SA_OUT_MARKER: {
+            auto kern = ka.wingen ? chain_marker_kernel<NSEC, UNIT, (NSEC > 0)> : chain_marker_kernel<NSEC, UNIT, false>;
+            e = set_lds(kern);
+            if (e != hipSuccess) return e;
+            hipExtLaunchKernelGGL(kern, grid, block, kLdsBytes, stream, ev.start, ev.stop, 0, in, SA_IN_SCALE_ARG out, batch,
+                                  tb.marker_lo | tb.marker_hi << 16, tb.win_b, tb.twT, tb.twB, tb.twC, tb.lanetab, ka);
+            break;
+        }
         case SA_OUT_TIME: {
             auto kern = time_f32_kernel<NSEC, UNIT>;
             e = set_lds(kern);

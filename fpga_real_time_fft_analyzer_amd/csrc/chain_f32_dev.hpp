@@ -1,5 +1,5 @@
 // chain_f32_dev.hpp -- device helpers of the float-path kernels (chain_f32.hip): LDS-only barrier, DPP row shifts,
-// nontemporal stores, the split step of the packed real FFT and its output layouts.
+// nontemporal stores, the split step of the packed real FFT, its output layouts and the marker reduction.
 #pragma once
 #include "sa_common.hpp"
 #include "fft_regs.hpp"
@@ -144,6 +144,124 @@ __device__ __forceinline__ void split_store(const cf (&R)[5], const cf (&I)[5], 
 #pragma unroll
         for (int e = 1; e < 5; ++e) store_nt(o + SA_MC - k0 - e, R[e].y, -I[e].y);
         if (k0 == 0) store_nt(o + SA_MC, R[0].y, -I[0].y);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// SA_OUT_MARKER: peak search and band power over the full-spectrum bins [lo, hi) of a frame, with no spectrum stored.
+// A thread owns the positions split_store<SA_OUT_MAG_FULL> writes for its groups, and sees each with the value that
+// call stores there: every bin of the range is counted once, with no special case for bin 0, bin 8192 or the
+// duplicated e = 4 pairs.  Ties on the magnitude go to the lower bin, so the result is numpy.argmax on the MAG_FULL row.
+struct MarkerAcc {
+    float mag;      // largest |X[k]| seen (-1: none yet)
+    int bin;        // lowest k attaining it
+    float pow;      // sum of |X[k]|^2, in the thread's fixed visiting order
+};
+
+// One run of four consecutive bins s .. s+3 holding magnitudes m[0..3] and squares p[0..3], visited in ascending order:
+// a strict > keeps the lowest bin of the run on a tie, and the run's winner joins the thread's pair with the full rule.
+// MASK: the run may straddle [lo, hi) (a bin outside counts as magnitude -1, power 0).
+template <bool MASK>
+__device__ __forceinline__ void marker_run(MarkerAcc &a, const float (&m)[4], const float (&p)[4], int s, int lo, int hi)
+{
+    float best = -1.f, pw = 0.f;
+    int be = 0;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        float mm = m[e], pe = p[e];
+        if constexpr (MASK) {
+            const bool in = (unsigned)(s + e - lo) < (unsigned)(hi - lo);
+            mm = in ? mm : -1.f;
+            pe = in ? pe : 0.f;
+        }
+        pw += pe;
+        if (mm > best) {
+            best = mm;
+            be = e;
+        }
+    }
+    a.pow += pw;
+    if (best > a.mag || (best == a.mag && s + be < a.bin)) {
+        a.mag = best;
+        a.bin = s + be;
+    }
+}
+
+// The wave's 64 runs of one kind cover the bins [w, w + 256) (w wave-uniform): one scalar decision for all of them --
+// skip, take whole, or mask bin by bin where the range edge cuts through.
+__device__ __forceinline__ void marker_run_any(MarkerAcc &a, const float (&m)[4], const float (&p)[4], int s, int w, int lo,
+                                               int hi)
+{
+    if (w + 256 <= lo || w >= hi) return;
+    if (w >= lo && w + 256 <= hi)
+        marker_run<false>(a, m, p, s, lo, hi);
+    else
+        marker_run<true>(a, m, p, s, lo, hi);
+}
+
+// one group of bins k0..k0+4 (the ownership map of split_store): same squares, same square roots.
+// kw: the wave-uniform k0 of the wave's lane 0 (the wave's groups of this round are k0 = kw + 4 lane)
+__device__ __forceinline__ void marker_group(const cf (&R)[5], const cf (&I)[5], int k0, int kw, int lo, int hi, MarkerAcc &a)
+{
+    float mp[5], mq[5], pp[5], pq[5];
+#pragma unroll
+    for (int e = 0; e < 5; ++e) {
+        const cf m2 = safft::pk_fma(I[e], I[e], R[e] * R[e]);          // (|P|^2, |Q|^2)
+        pp[e] = m2.x;
+        pq[e] = m2.y;
+        mp[e] = fast_sqrt(m2.x);
+        mq[e] = fast_sqrt(m2.y);
+    }
+    const float m0[4] = {mp[0], mp[1], mp[2], mp[3]}, p0[4] = {pp[0], pp[1], pp[2], pp[3]};
+    const float m1[4] = {mp[4], mp[3], mp[2], mp[1]}, p1[4] = {pp[4], pp[3], pp[2], pp[1]};
+    const float m2[4] = {mq[0], mq[1], mq[2], mq[3]}, p2[4] = {pq[0], pq[1], pq[2], pq[3]};
+    const float m3[4] = {mq[4], mq[3], mq[2], mq[1]}, p3[4] = {pq[4], pq[3], pq[2], pq[1]};
+    marker_run_any(a, m0, p0, k0, kw, lo, hi);                                            // [k0 ..]        P0..3
+    marker_run_any(a, m1, p1, SA_NPTS - k0 - 4, SA_NPTS - kw - 256, lo, hi);              // [N-k0-4 ..]    P4..1
+    marker_run_any(a, m2, p2, SA_MC + k0, SA_MC + kw, lo, hi);                            // [8192+k0 ..]   Q0..3
+    marker_run_any(a, m3, p3, SA_MC - k0 - 4, SA_MC - kw - 256, lo, hi);                  // [8192-k0-4 ..] Q4..1
+}
+
+// a <- combine(a, b): the sum and the (larger magnitude, then lower bin) pair.  Symmetric in a and b, so both lanes of
+// a butterfly pair end with the same bits.
+__device__ __forceinline__ void marker_merge(MarkerAcc &a, const MarkerAcc &b)
+{
+    a.pow += b.pow;
+    if (b.mag > a.mag || (b.mag == a.mag && b.bin < a.bin)) {
+        a.mag = b.mag;
+        a.bin = b.bin;
+    }
+}
+
+template <int XOR>
+__device__ __forceinline__ MarkerAcc marker_swizzle(const MarkerAcc &a)
+{
+    constexpr int pat = (XOR << 10) | 0x1F;                  // ds_swizzle bitmask mode: lane ^ XOR inside 32 lanes
+    return {__builtin_bit_cast(float, __builtin_amdgcn_ds_swizzle(__builtin_bit_cast(int, a.mag), pat)),
+            __builtin_amdgcn_ds_swizzle(a.bin, pat),
+            __builtin_bit_cast(float, __builtin_amdgcn_ds_swizzle(__builtin_bit_cast(int, a.pow), pat))};
+}
+
+// The workgroup's record: a swizzle butterfly inside each half-wave, the eight half-wave results through `scr`
+// (8 x 16 bytes of LDS no other thread uses at this point), merged by thread 0 in a fixed order and stored as one
+// 16-byte sa_marker.  No atomics: the bits depend on the data alone.
+constexpr int kMarkerParts = SA_NTHREADS / 32;
+__device__ __forceinline__ void marker_finish(MarkerAcc a, float4 *scr, void *__restrict__ out, int f, int t)
+{
+    marker_merge(a, marker_swizzle<1>(a));
+    marker_merge(a, marker_swizzle<2>(a));
+    marker_merge(a, marker_swizzle<4>(a));
+    marker_merge(a, marker_swizzle<8>(a));
+    marker_merge(a, marker_swizzle<16>(a));
+    if ((t & 31) == 0) scr[t >> 5] = make_float4(a.mag, __builtin_bit_cast(float, a.bin), a.pow, 0.f);
+    lds_barrier();
+    if (t == 0) {
+#pragma unroll
+        for (int i = 1; i < kMarkerParts; ++i) {
+            const float4 v = scr[i];
+            marker_merge(a, MarkerAcc{v.x, __builtin_bit_cast(int, v.y), v.z});
+        }
+        store_nt(reinterpret_cast<float *>(out) + (size_t)f * 4, a.mag, __builtin_bit_cast(float, a.bin), a.pow, 0.f);
     }
 }
 

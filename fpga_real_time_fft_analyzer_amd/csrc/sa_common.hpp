@@ -128,6 +128,7 @@ struct SaF32Tables {
                                //            factor of the split-step twiddles
     const SaIirLaneTab *lanetab;   // device
     const SaIirK *iir;             // HOST pointer, copied into the kernel arguments (null = no IIR)
+    int marker_lo, marker_hi;      // SA_OUT_MARKER: the bin range [lo, hi), by value in the kernel arguments
 };
 
 // Events of a launch (either may be null), attached to the dispatch packet itself by hipExtLaunchKernel: no marker

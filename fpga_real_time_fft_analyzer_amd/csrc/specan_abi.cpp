@@ -106,6 +106,8 @@ struct sa_handle {
     std::vector<double> win64;             // the window in double, natural order: default Hann or the caller's table widened
     double *d_win64 = nullptr;             // win64 transposed for iir_f64.hip: [32][256] pairs, pair (g, t) = w[64t + 2g], w[..+1]
     float4 *d_win_half = nullptr;          // constant 1/2 (the split step's factor) in the pass-A layout: the FFT launch's window
+    // ---- SA_OUT_MARKER range (sa_set_marker_range): host state only, passed by value to every marker launch
+    int marker_lo = 0, marker_hi = SA_NPTS;
     // ---- stream-ordered control plane (no device-wide synchronisation anywhere after sa_create)
     // Table uploads run on the handle's own control stream: it first waits for everything the handle has
     // launched so far, copies from a pinned staging slot, and records `uploaded`; the next process call makes its
@@ -1149,10 +1151,12 @@ static int process_float(sa_handle *h, const char *fn, const void *in, bool i16,
 {
     if (!h) return SA_EINVAL;
     if (batch < 0) return fail_at(h, SA_ESHAPE, fn, "negative batch");
-    if (out_kind < SA_OUT_MAG_FULL || out_kind > SA_OUT_TIME) return fail_at(h, SA_EINVAL, fn, "bad out_kind");
+    if (out_kind < SA_OUT_MAG_FULL || out_kind > SA_OUT_MARKER) return fail_at(h, SA_EINVAL, fn, "bad out_kind");
     if (!(scale == scale) || scale - scale != 0.f) return fail_at(h, SA_EINVAL, fn, "scale is not finite");
     if (batch == 0) return SA_OK;
     if (!in || !out) return fail_at(h, SA_EINVAL, fn, "NULL tensor");
+    if (out_kind == SA_OUT_MARKER && ((uintptr_t)out & 15u) != 0)
+        return fail_at(h, SA_EINVAL, fn, "SA_OUT_MARKER output must be 16-byte aligned");
     if (h->filter_mode == SA_FILTER_WIDE)
         return fail_at(h, SA_ESTATE, fn, "filter mode 0xA2 (Q2.14) belongs to the Q15 path; use 0xA1 with sa_load_sos_f32");
     SA_HIP(h, hipSetDevice(h->device));
@@ -1162,7 +1166,8 @@ static int process_float(sa_handle *h, const char *fn, const void *in, bool i16,
     const bool two = f64 && out_kind != SA_OUT_TIME;
     CallCtx c;
     { const int rc = begin_call(h, (hipStream_t)stream, two ? sa_handle::kWorkF64 : -1, batch, &c); if (rc != SA_OK) return rc; }
-    SaF32Tables t = {h->d_win_b, h->d_win_t, h->d_twT, h->d_twB, h->d_twC, pl.d_lt, cascade ? &pl.k : nullptr};
+    SaF32Tables t = {h->d_win_b, h->d_win_t, h->d_twT, h->d_twB, h->d_twC, pl.d_lt, cascade ? &pl.k : nullptr,
+                     h->marker_lo, h->marker_hi};
     if (!f64) {
         SA_HIP(h, i16 ? sa_launch_chain_f32_i16((const int16_t *)in, scale, out, batch, out_kind, t, c.stream, {c.start, c.stop})
                       : sa_launch_chain_f32((const float *)in, out, batch, out_kind, t, c.stream, {c.start, c.stop}));
@@ -1172,7 +1177,7 @@ static int process_float(sa_handle *h, const char *fn, const void *in, bool i16,
     SA_HIP(h, sa_launch_iir_f64(in, i16, scale, y, batch, pl.k.nsec, pl.d_p64, h->d_win64, c.stream,
                                 {c.start, two ? nullptr : c.stop}));
     if (two) {
-        t = {h->d_win_half, h->d_win_t, h->d_twT, h->d_twB, h->d_twC, h->plan_custom.d_lt, nullptr};
+        t = {h->d_win_half, h->d_win_t, h->d_twT, h->d_twB, h->d_twC, h->plan_custom.d_lt, nullptr, h->marker_lo, h->marker_hi};
         SA_HIP(h, sa_launch_chain_f32(y, out, batch, out_kind, t, c.stream, {nullptr, c.stop}));
     }
     return end_call(h, c);
@@ -1248,6 +1253,24 @@ int sa_get_precision(const sa_handle *h, int *precision)
 {
     if (!h || !precision) return SA_EINVAL;
     *precision = h->precision;
+    return SA_OK;
+}
+
+int sa_set_marker_range(sa_handle *h, int lo, int hi)
+{
+    if (!h) return SA_EINVAL;
+    if (lo < 0 || lo >= hi || hi > SA_NPTS) return fail(h, SA_EINVAL, "sa_set_marker_range: need 0 <= lo < hi <= 16384");
+    { const int rc = control_allowed(h); if (rc != SA_OK) return rc; }
+    h->marker_lo = lo;
+    h->marker_hi = hi;
+    return SA_OK;
+}
+
+int sa_get_marker_range(const sa_handle *h, int *lo, int *hi)
+{
+    if (!h || !lo || !hi) return SA_EINVAL;
+    *lo = h->marker_lo;
+    *hi = h->marker_hi;
     return SA_OK;
 }
 

@@ -40,6 +40,18 @@ def frequency_axis_khz(n_bins: int = FFT_SIZE) -> np.ndarray:
     return np.arange(n_bins, dtype=np.float32) * (FS_HZ / FFT_SIZE) / 1e3
 
 
+def bin_range_from_permille(start: float, end: float, n_bins: int = FFT_SIZE) -> tuple[int, int]:
+    """The gui's frequency range (per mille of the N bins, gui.py:294-305) as the bin range [lo, hi) it slices.
+
+    Both ends are truncated toward zero, then lo is clamped to [0, N-1] and hi to [lo+1, N]: the slice is never empty.
+    (lo, hi) is what SpectrumChain.set_marker_range takes, and frequency_axis_khz()[peak_bin] the gui's peak_frequency."""
+    lo = int(float(start) * n_bins / 1000.0)
+    hi = int(float(end) * n_bins / 1000.0)
+    lo = min(max(lo, 0), n_bins - 1)
+    hi = max(min(hi, n_bins), lo + 1)
+    return lo, hi
+
+
 def frame_to_udp_payloads(frame_bytes: bytes) -> list[bytes]:
     """Cut a frame into the 64 datagram payloads the FPGA MAC sends: index byte 0..63 followed by
     1024 data bytes (consumed by MultiPacketAssembler.add, gui.py:318-339)."""

@@ -91,6 +91,27 @@ extern "C" {
 #define SA_OUT_MAG_HALF   1   /* float  [B,8193]    |X[k]|, k = 0..N/2 */
 #define SA_OUT_SPEC_HALF  2   /* float2 [B,8193]    X[k] = (re,im), k = 0..N/2 (numpy.fft.rfft layout) */
 #define SA_OUT_TIME       3   /* float  [B,16384]   FFT input: window (+ IIR) output time series */
+#define SA_OUT_MARKER     4   /* sa_marker [B]: per-frame peak search + band power over the marker range */
+
+/* SA_OUT_MARKER record: what scripts/fft_analyzer_gui.py computes for every frame it shows -- the magnitude spectrum
+ * cut to the user's range (get_frequency_range_data, gui.py:294-305), then np.max / np.argmax over that slice
+ * (emit_plot_data, gui.py:415-455) -- made on the device in the chain's epilogue: 16 bytes per frame instead of a
+ * 64 KiB spectrum that the host would copy back and search.
+ *   - bins: k indexes the full N = 16384-bin spectrum exactly as SA_OUT_MAG_FULL lays it out (gui.py numbers them so);
+ *     bins above 8192 hold the mirrored |X[N-k]|.  A range inside the upper half reports an upper-half bin.
+ *   - peak_mag is bit for bit the value SA_OUT_MAG_FULL writes at peak_bin, and peak_bin the LOWEST k in [lo, hi)
+ *     attaining it: numpy.argmax on the MAG_FULL row slice, plus lo.  (gui.py's own 'peak_bin' is that argmax, relative
+ *     to the slice.)  The mirror is a bit-identical tie, so a full-range peak on a tone at bin b reports b, not N-b.
+ *   - band_power is the sum over k in [lo, hi) of |X[k]|^2 as the kernel forms it (R^2 + I^2, before the square root),
+ *     summed in float32 in a fixed order: the record is bit-reproducible from run to run (no atomics).
+ *   - frames with a non-finite sample give unspecified records.
+ *   - `out` of SA_OUT_MARKER must be 16-byte aligned (SA_EINVAL otherwise). */
+typedef struct sa_marker {
+    float    peak_mag;    /* max |X[k]| over k in [lo, hi) */
+    int32_t  peak_bin;    /* lowest k in [lo, hi) attaining it */
+    float    band_power;  /* sum over k in [lo, hi) of |X[k]|^2 */
+    uint32_t reserved;    /* written as 0 */
+} sa_marker;              /* 16 bytes; one aligned store per frame */
 
 /* precision of the float path's window and cascade (sa_set_precision) */
 #define SA_PRECISION_F32       0   /* default: float32 arithmetic throughout, one fused kernel per call */
@@ -275,6 +296,20 @@ int sa_iir_plan_from_sos(const double *sos, int n_sections, float *out, int cap)
  *     (SA_ESTATE), SA_EINVAL for any other value.  Leaving the mode keeps its device tables until sa_destroy(). */
 int sa_set_precision(sa_handle *h, int precision /* SA_PRECISION_* */);
 int sa_get_precision(const sa_handle *h, int *precision);
+
+/* ---- marker range (SA_OUT_MARKER; build extension) ------------------------------------------------------------------
+ * The full-spectrum bins [lo, hi) the SA_OUT_MARKER records of sa_process_f32 / sa_process_f32_i16 cover: the gui's
+ * frequency range (web_config freq_range_start / freq_range_end in per mille of the N bins, gui.py:294-305) as bin
+ * indices.  [0, 16384) at sa_create(), the gui's default 0..1000 per mille.  0 <= lo < hi <= SA_N, else SA_EINVAL and
+ * nothing changed.  Not board state: the 0xFF reset of sa_feed_command_bytes leaves it alone.
+ *   - control-plane call with the rules of sa_set_precision: stream-ordered (applies to later process calls only),
+ *     refused while a capture is open (SA_ESTATE).  No upload: the range travels by value in the kernel arguments,
+ *     so a captured call keeps the range of its capture time.
+ *   - SA_OUT_MARKER works in filter modes NONE, DEFAULT and CUSTOM, in both precisions (in SA_PRECISION_F64_STATE the
+ *     float chain on the float64 cascade's output makes the records), at every overlap depth, with launch timing and
+ *     under hipGraph capture. */
+int sa_set_marker_range(sa_handle *h, int lo, int hi);
+int sa_get_marker_range(const sa_handle *h, int *lo, int *hi);
 
 /* The float64 plan (iir_f64.hip, struct SaIirF64): hdr[4] (hdr[0] = padded section count 0/2/4/6) then 6 sections of
  * {c[6] = b0,b1,b2,a1,a2,0; m[16][2] predictor taps A^(15-j) Bv; A^16; A^32; A^(64 * 2^k) k < 4; A^(1024 * 2^k) k < 4;
