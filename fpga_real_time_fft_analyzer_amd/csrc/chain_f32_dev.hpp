@@ -1,5 +1,6 @@
-// chain_f32_dev.hpp -- device helpers of the float-path kernels (chain_f32.hip): LDS-only barrier, DPP row shifts,
-// nontemporal stores, the split step of the packed real FFT, its output layouts and the marker reduction.
+// chain_f32_dev.hpp -- device helpers of the float-path kernels (chain_f32.hpp, iir_f64.hip): LDS-only barrier, DPP row
+// shifts, nontemporal stores, the row image that stages frames in and out of the IIR kernels, the split step of the
+// packed real FFT, its output layouts and the marker reduction.
 #pragma once
 #include "sa_common.hpp"
 #include "fft_regs.hpp"
@@ -72,6 +73,65 @@ __device__ __forceinline__ void store_nt(float2 *p, float a, float b)
     __builtin_nontemporal_store(f2nt{a, b}, reinterpret_cast<f2nt *>(p));
 }
 __device__ __forceinline__ void store_nt(float *p, float a) { __builtin_nontemporal_store(a, p); }
+
+// ---------------------------------------------------------------------------------------------
+// The row image that stages a frame in and out of the IIR kernels (float and float64 state).  Thread t owns the 64
+// samples [64t, 64t+64) and LDS row t (128 bytes: all 64 int16 samples, or one chunk of 32 float32 samples per round).
+// Wave w moves rows 64w .. 64w+63 as eight 1 KiB slabs, one wave instruction each; the 16-byte column c of row r sits
+// in slot c ^ row_swizzle(r), i.e. at 16-byte unit 8r + (c ^ row_swizzle(r)) of the image, so that a thread's
+// ds_read_b128 / ds_write_b128 of its own row are conflict-free at this pitch.  The rows are wave-private: a wave waits
+// for its own traffic only, no workgroup barrier.
+__device__ __forceinline__ int row_swizzle(int r) { return (r >> 1) & 7; }
+
+// Stage-in, one round: row r <- 128 bytes of the frame x by LDS-DMA (global_load_lds_dwordx4: no VGPRs, no ds_write).
+// The slab lands linearly in LDS, so the swizzle is applied to the per-lane SOURCE address.  Issued at raised priority
+// so that the requests leave ahead of the other workgroups' arithmetic.
+template <typename T>
+__device__ __forceinline__ void dma_rows_impl(const T *x, int h, unsigned char *smem, int lane, int wave)
+{
+    const int rl = lane >> 3;                                  // row inside the slab
+    __builtin_amdgcn_s_setprio(3);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const int n = wave * 8 + i;                            // slab: rows 8n .. 8n+7
+        const int r = 8 * n + rl;
+        const int lc = (lane & 7) ^ row_swizzle(r);
+        const T *src = x + r * 64 + h * 32 + lc * (16 / (int)sizeof(T));
+        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)src,
+                                         (__attribute__((address_space(3))) void *)(smem + n * 1024), 16, 0, SA_DMA_AUX);
+    }
+    __builtin_amdgcn_s_setprio(0);
+}
+// float32 frames: round h (0 or 1) brings chunk h, samples x[64r + 32h ..], of every row
+__device__ __forceinline__ void dma_rows(const float *x, int h, unsigned char *smem, int lane, int wave)
+{
+    dma_rows_impl(x, h, smem, lane, wave);
+}
+// int16 samples: one round brings all 64 samples of every row
+__device__ __forceinline__ void dma_rows(const int16_t *x, unsigned char *smem, int lane, int wave)
+{
+    dma_rows_impl(x, 0, smem, lane, wave);
+}
+
+// Stage-out, round h, the stage-in run backwards: row r (32 float32 samples) -> o[64r + 32h ..].
+// Every wave instruction picks up 1 KiB of LDS in linear order and stores it with 16 bytes per lane: stored straight
+// from the registers, every lane of a store instruction would land in another 256-byte block.
+// t: the thread index, passed by the kernels as an opaque copy (asm volatile).  Derived from the plain index, the row
+// addresses here equal the stage-in's, and the compiler keeps those live through the whole cascade to reuse them: up to
+// 40 more VGPRs in the time-series and float64-state kernels.
+__device__ __forceinline__ void store_rows(float *o, int h, const unsigned char *smem, int t)
+{
+    const float4 *lds4 = reinterpret_cast<const float4 *>(smem);
+    const int lane = t & 63, wave = t >> 6, rl = lane >> 3;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const int n = wave * 8 + i;
+        const int r = 8 * n + rl;
+        const int lc = (lane & 7) ^ row_swizzle(r);
+        const float4 v = lds4[n * 64 + lane];
+        store_nt(o + r * 64 + h * 32 + lc * 4, v.x, v.y, v.z, v.w);
+    }
+}
 
 // ---------------------------------------------------------------------------------------------
 // a * w with w wave-uniform (an SGPR pair): two packed ops, no copy of w into VGPRs

@@ -1,5 +1,9 @@
-// The float chain with int16 samples in (sa_process_f32_i16): chain_f32.hip compiled a second time with the int16
-// stage-in.  Everything behind the stage-in -- cascade, FFT, split step, outputs -- is the same source.
-#undef SA_STAMPS                 // the diagnostic stamps belong to the float32 translation unit
-#define SA_F32_INPUT_I16 1
-#include "chain_f32.hip"
+// chain_f32_i16.hip -- the float chain on int16 samples (sa_process_f32_i16): x = float(sample) * in_scale in the
+// stage-in, then exactly the float32 path (chain_f32.hpp).  A translation unit of its own, compiled beside chain_f32.hip.
+#include "chain_f32.hpp"
+
+hipError_t sa_launch_chain_f32_i16(const int16_t *in, float in_scale, void *out, int batch, int out_kind,
+                                   const SaF32Tables &tb, hipStream_t stream, SaLaunchEv ev)
+{
+    return launch_chain(out, batch, out_kind, tb, stream, ev, in, in_scale);
+}

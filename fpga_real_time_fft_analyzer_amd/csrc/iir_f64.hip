@@ -1,9 +1,9 @@
 // iir_f64.hip -- window and IIR cascade of the float path with float64 state (SA_PRECISION_F64_STATE):
 //     x * window  ->  up to 6 biquads (DF2T of scipy.signal.sosfilt)  ->  y rounded once to float32
-// The first of the two launches of a call in that mode; the second is the bypassed float chain (chain_f32.hip, NSEC = 0)
+// The first of the two launches of a call in that mode; the second is the bypassed float chain (chain_f32.hpp, NSEC = 0)
 // on y with a constant window of 1/2 (the split step's factor, exact), so the FFT half is the proven float32 kernel.
 //
-// Shape (the float32 cascade's, chain_f32.hip, in double):
+// Shape (the float32 cascade's, chain_f32.hpp, in double):
 //   * one 256-thread workgroup per frame; thread t owns samples [64t, 64t+64) as two independent chunks of 32 (chunk A,
 //     chunk B): the recursion then has two dependency chains per thread instead of one.
 //   * per section: chunk end states from zero state (predictor taps, block Horner over two half chunks), an affine scan
@@ -55,30 +55,21 @@ __device__ __forceinline__ void scan_level(d2 &z, const double (&p)[4])
 }
 
 // ---------------------------------------------------------------------------------------------
-// Stage-in: HBM -> LDS by LDS-DMA (global_load_lds_dwordx4, no VGPRs on the way), the 16-byte columns of row r stored at
-// c ^ ((r >> 1) & 7) by swizzling the per-lane SOURCE address (conflict-free ds_read_b128 at a 128-byte pitch), as
-// chain_f32.hip's stage_in_chunks does.  Row r is thread r's; wave w requests rows 64w .. 64w+63 only, so the image is
-// wave-private and needs no workgroup barrier.  The window is read as 16-byte pairs of a transposed double table.
+// Stage-in through the row image of the float32 cascade (chain_f32_dev.hpp): wave-private rows, no workgroup barrier.
+// The window is read as 16-byte pairs of a transposed double table.
 // float32 frames: two rounds, round h brings chunk h (32 samples = 128 bytes) of every thread.
 __device__ __forceinline__ void stage_in(const float *__restrict__ xin, float, const double2 *__restrict__ wt,
                                          unsigned char *smem, int t, double (&d)[2][32])
 {
     const float4 *lds4 = reinterpret_cast<const float4 *>(smem);
-    const int lane = t & 63, wave = t >> 6, rl = lane >> 3, sw = (t >> 1) & 7;
+    const int lane = t & 63, wave = t >> 6, sw = row_swizzle(t);
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
         if (h == 1) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // this wave's reads of round 0 are done
-        __builtin_amdgcn_s_setprio(3);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const int n = wave * 8 + i;                        // slab: rows 8n .. 8n+7
-            const int r = 8 * n + rl;
-            const int lc = (lane & 7) ^ ((r >> 1) & 7);
-            const float *src = xin + r * 64 + h * 32 + lc * 4;
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)src,
-                                             (__attribute__((address_space(3))) void *)(smem + n * 1024), 16, 0, SA_DMA_AUX);
-        }
-        __builtin_amdgcn_s_setprio(0);
+        // opaque copies per round: otherwise the row addresses of both rounds are computed and held from the start
+        int l = lane, w = wave;
+        asm volatile("" : "+v"(l), "+v"(w));
+        dma_rows(xin, h, smem, l, w);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -100,18 +91,8 @@ __device__ __forceinline__ void stage_in(const int16_t *__restrict__ xin, const 
                                          unsigned char *smem, int t, double (&d)[2][32])
 {
     const uint4 *lds4 = reinterpret_cast<const uint4 *>(smem);
-    const int lane = t & 63, wave = t >> 6, rl = lane >> 3, sw = (t >> 1) & 7;
-    __builtin_amdgcn_s_setprio(3);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const int n = wave * 8 + i;
-        const int r = 8 * n + rl;
-        const int lc = (lane & 7) ^ ((r >> 1) & 7);
-        const int16_t *src = xin + r * 64 + lc * 8;
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)src,
-                                         (__attribute__((address_space(3))) void *)(smem + n * 1024), 16, 0, SA_DMA_AUX);
-    }
-    __builtin_amdgcn_s_setprio(0);
+    const int lane = t & 63, wave = t >> 6, sw = row_swizzle(t);
+    dma_rows(xin, smem, lane, wave);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -207,12 +188,13 @@ __global__ __launch_bounds__(kThreads, 2) void iir_f64_kernel(const InT *__restr
         // the sections' scan slots are separate: no barrier between the last read of one and the first write of the next
         section(d, plan->sec[s], scr + 16 * s, lane, wave);
     }
-    // Stage-out, the float-input stage-in run backwards (time_f32_kernel of chain_f32.hip): round h writes chunk h, rounded
-    // once to float32, into the thread's 128-byte row (same swizzle), then every wave instruction stores 1 KiB of LDS in
-    // linear order, 16 bytes per lane.  Rows are wave-private here too; the barriers keep the rounds apart.
+    // Stage-out through the row image, as time_f32_kernel (chain_f32.hpp) does: round h writes chunk h, rounded once to
+    // float32, into the thread's row, then store_rows.  The barriers keep the rounds apart.
     float4 *lds4 = reinterpret_cast<float4 *>(smem);
     float *o = out + (size_t)f * SA_NPTS;
-    const int rl = lane >> 3, sw = (t >> 1) & 7;
+    const int sw = row_swizzle(t);
+    int ts = t;                              // opaque copy for store_rows
+    asm volatile("" : "+v"(ts));
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
         lds_barrier();
@@ -221,14 +203,7 @@ __global__ __launch_bounds__(kThreads, 2) void iir_f64_kernel(const InT *__restr
             lds4[t * 8 + (g ^ sw)] = make_float4((float)d[h][4 * g], (float)d[h][4 * g + 1], (float)d[h][4 * g + 2],
                                                  (float)d[h][4 * g + 3]);
         lds_barrier();
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const int n = wave * 8 + i;
-            const int r = 8 * n + rl;
-            const int lc = (lane & 7) ^ ((r >> 1) & 7);
-            const float4 v = lds4[n * 64 + lane];
-            store_nt(o + r * 64 + h * 32 + lc * 4, v.x, v.y, v.z, v.w);
-        }
+        store_rows(o, h, smem, ts);
     }
 }
 

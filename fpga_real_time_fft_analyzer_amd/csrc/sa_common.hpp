@@ -44,7 +44,7 @@ struct SaIirSecK {
     int flags;
     float pad[2];
     // every 2x2 matrix below and in SaIirLaneTab::p is stored COLUMN-major (m00, m10, m01, m11): a column is an aligned
-    // register pair and a matrix-vector product is two packed FMAs (chain_f32.hip, mv_s)
+    // register pair and a matrix-vector product is two packed FMAs (chain_f32.hpp, mv_s)
     float pc[4];           // Pc
     float mback[4];        // T^-1
     float plev[4][4];      // P2^(1,2,4,8)      in-row scan (DPP row_shr 1,2,4,8)
@@ -68,7 +68,7 @@ struct SaIirK {
 //   p[s][i]   = P2^i, i = lane index inside its 16-lane row (start-state injection per lane)
 //   win_t     = 0.5 * window * G, transposed for the chunk layout (win_t[g][t][e] = w[64t + 4g + e]);
 //               G = product of the sections' b0 when the plan is in unit-numerator form, else 1
-//   wgen, wcs, wg0 = the in-place window generator of the IIR kernels (chain_f32.hip, stage_in_direct):
+//   wgen, wcs, wg0 = the in-place window generator of the IIR kernels (chain_f32.hpp, stage_in_chunks):
 //               W[64t + 32h + j] = wg0 + wgen[t][2h] * wcs[j][0] + wgen[t][2h+1] * wcs[j][1], all including the
 //               factor 0.5 * G; valid when the plan's `wingen` flag is set
 struct SaIirLaneTab {
@@ -115,7 +115,7 @@ struct SaQ15Params {
 // operation: doing it on every launch costs host time and cannot be captured into a hipGraph.
 hipError_t sa_set_dyn_lds_once(const void *kernel, int bytes);
 
-// launchers (defined in chain_f32.hip / chain_q15.hip)
+// launchers (defined in chain_f32.hip, chain_f32_i16.hip and chain_q15.hip)
 struct SaF32Tables {
     const float4 *win_b;       // [16][256] 0.5 * window in the pass-A layout of the no-IIR kernel:
                                //   win_b[p][t] = w[512(2p)+2t], w[..+1], w[512(2p+1)+2t], w[..+1]
