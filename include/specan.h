@@ -44,6 +44,10 @@
  *     the replay stream) before a control-plane call.
  *   - frame length is fixed: SA_N = 16384 samples (gui.py:43-44, imp/dsp_system_top.vhd:440,
  *     ip/xfft_0/xfft_0.xci:12).
+ *   - frames are isolated: a frame's outputs depend only on that frame and the control state of
+ *     its call, not on the other frames of the batch or on anything run earlier on the GPU.  A NaN,
+ *     an Inf or a sample whose spectrum overflows float32 affects only its own frame's outputs
+ *     (whose values, and marker record, are then unspecified).
  */
 #ifndef SPECAN_H_
 #define SPECAN_H_
