@@ -1,0 +1,37 @@
+// q15_dev.hpp -- device helpers shared by the integer cascades (cascade_q15.hip) and the fixed-point FFT (fft_q15.hip):
+// the Q15 window of one sample and the packed int16 pair.
+#pragma once
+#include "sa_common.hpp"
+
+namespace {
+
+// new/hann8192.vhd:36-39: out = resize16(product(31..15) + product(14)).
+// product(31..15) + product(14) = floor((p + 2^14) / 2^15); resize16 of the 17-bit sum keeps its sign bit (16) and its
+// low 15 bits, which differs from plain truncation only for +32768 (x = c = -32768), mapped to 0.
+__device__ __forceinline__ int win_rtl(int x, int c)
+{
+    const int r = (x * c + 16384) >> 15;
+    return (int)(short)((r & 0x7FFF) | ((r >> 1) & 0x8000));
+}
+
+// SURVEY quirk Q2 alternative: ROM + 32768 as unsigned Q16 Hann, round half up.  |x (c + 32768) + 32768| < 2^31 for
+// 16-bit x and c (largest 32767 * 65535 + 32768): 32-bit arithmetic is exact.
+__device__ __forceinline__ int win_u16(int x, int c)
+{
+    return (int)(short)((x * (c + 32768) + 32768) >> 16);
+}
+
+__device__ __forceinline__ unsigned pack2(int lo, int hi) { return ((unsigned)lo & 0xFFFFu) | ((unsigned)hi << 16); }
+// (sat16(lo), sat16(hi)) as one packed dword: v_cvt_pk_i16_i32 saturates and packs in ONE instruction
+// (two v_med3_i32, an and and a shift-or otherwise -- a seventh of the kernel's vector instructions)
+__device__ __forceinline__ unsigned sat_pack2(int lo, int hi)
+{
+    typedef short s2 __attribute__((ext_vector_type(2)));
+    const s2 r = __builtin_amdgcn_cvt_pk_i16(lo, hi);
+    return __builtin_bit_cast(unsigned, r);
+}
+
+__device__ __forceinline__ int lo16(unsigned v) { return (int)(short)(v & 0xFFFFu); }
+__device__ __forceinline__ int hi16(unsigned v) { return (int)v >> 16; }
+
+}  // namespace

@@ -115,7 +115,7 @@ struct SaQ15Params {
 // operation: doing it on every launch costs host time and cannot be captured into a hipGraph.
 hipError_t sa_set_dyn_lds_once(const void *kernel, int bytes);
 
-// launchers (defined in chain_f32.hip, chain_f32_i16.hip and chain_q15.hip)
+// launchers (defined in chain_f32.hip, chain_f32_i16.hip, cascade_q15.hip and fft_q15.hip)
 struct SaF32Tables {
     const float4 *win_b;       // [16][256] 0.5 * window in the pass-A layout of the no-IIR kernel:
                                //   win_b[p][t] = w[512(2p)+2t], w[..+1], w[512(2p+1)+2t], w[..+1]

@@ -313,7 +313,7 @@ Q15_CASES = {
 
 
 def _launched_q15(ch, nsec_wide, fft):
-    """The kernels a Q15 call launches, from the handle's state as specan_abi.cpp (process_q15) and chain_q15.hip
+    """The kernels a Q15 call launches, from the handle's state as specan_abi.cpp (process_q15) and cascade_q15.hip
     (sa_launch_filter_q15: the short step when B1 = 0 in both coefficient sets; 0x00 runs the fixed taps, whose B1 is 0)."""
     mode = ch.filter_mode
     if mode == 0xB1:

@@ -316,7 +316,7 @@ def test_fft_regs_host(tmp_path):
 
 
 def test_wide_step_split_accumulators_are_exact():
-    """The wide Q2.14 step of the GPU kernel (chain_q15.hip, filter_w14_kernel) never forms the 34-bit sum of
+    """The wide Q2.14 step of the GPU kernel (cascade_q15.hip, filter_w14_kernel) never forms the 34-bit sum of
     or_iir_sos_q14: every tap -- and every NEGATED feedback tap, which reaches +32768 -- splits as c = 2^14 ch + cl with
     cl in [-8192, 8191], the two sums acc_l = 8192 + sum cl v and acc_h = sum ch v stay inside 32 bits at every partial sum,
     and (acc + 8192) >> 14 = acc_h + (acc_l >> 14) exactly.  Checked here on the host for random and extreme operands, so
@@ -342,7 +342,7 @@ def test_wide_step_split_accumulators_are_exact():
 
 
 def test_fft_q15_paired_stage_addressing():
-    """The index arithmetic of fft_q15_kernel (csrc/chain_q15.hip) restated in numpy on complex doubles: stage 0 from
+    """The index arithmetic of fft_q15_kernel (csrc/fft_q15.hip) restated in numpy on complex doubles: stage 0 from
     the input, the register passes (1,2), (3,4), (5,6) with their thread-to-butterfly maps, twiddle exponents, output
     positions and the two XOR swizzles.  With exact arithmetic the result must be the DFT in natural order, and every
     swizzled LDS access of a wave must touch 64 different banks."""
@@ -420,20 +420,24 @@ def test_fft_q15_paired_stage_addressing():
 
 
 def test_cascade_helper_wave_schedule():
-    """The hand-over between a cascade wave and its helper wave (csrc/chain_q15.hip: q15_helper_wave), interval by interval
+    """The hand-over between a cascade wave and its helper wave (csrc/cascade_q15.hip: q15_helper_wave), interval by interval
     between workgroup barriers: within an interval the two waves never touch the same half of either ring, a flush only
     reads samples the cascade wrote in an EARLIER interval, and the flushes cover every sample of the frame exactly once."""
     tile, ring, nt, n = 256, 512, 64, 16384
     slot = lambda m: (m + 8) % ring                          # sample m lives in ring slot (m + 8) mod kRing
     written_in = {}                                          # sample -> interval in which the cascade stored it
     flushed = []
-    for k in range(nt + 1):                                  # interval k: cascade tile k (k = nt: the drain group)
+    for k in range(nt + 1):                                  # interval k: cascade tile k (k = nt: the drain)
         if k < nt:
             cas_samples = range(k * tile - 8, (k + 1) * tile - 8)
             cas_in_half = k & 1                              # input ring half the cascade reads
         else:
-            cas_samples = range(nt * tile - 8, nt * tile)    # the drain's first group: the frame's last eight samples
-            cas_in_half = None
+            # the drain.  The wide cascade runs one more iteration of its tile loop = four groups: the first stores the
+            # frame's last eight samples, the other three store 24 "samples" beyond the frame into ring slots 8..31.
+            # (The Q7 cascade runs the first group only: a subset.)
+            cas_samples = range(nt * tile - 8, nt * tile + 24)
+            assert {slot(m) for m in cas_samples} == set(range(32))
+            cas_in_half = k & 1                              # and reads on in the input ring (a tile long consumed)
         cas_slots = {slot(m) for m in cas_samples}
         hlp_in_half = (k + 1) & 1 if k + 1 < nt else None    # input ring half the helper windows the next tile into
         if cas_in_half is not None and hlp_in_half is not None:

@@ -1,6 +1,6 @@
 // Micro-benchmark, round 4: wall-clock time per step of the integer cascades' inner blocks, one wave per SIMD on every
 // SIMD of the chip (256 workgroups x 4 waves), eight blocks per asm statement and named registers as in the product
-// loops (chain_q15.hip).  No LDS, no refill, no stores: the floor of the recursion itself.
+// loops (cascade_q15.hip; the step text comes from its q15_steps.hpp).  No LDS, no refill, no stores: the floor of the recursion itself.
 //   * the Q7 seven-instruction block as shipped in round 3 (order H I B A C E F: the neighbour's output is read by a DPP
 //     product two instructions after it was written and sits on the recurrence H -> C -> F -> H)
 //   * the same arithmetic retimed: every DPP product reads a neighbour output that is one or two blocks old, hi(p0) is
@@ -14,18 +14,8 @@
 #include <cstdio>
 
 // ---------------------------------------------------------------------------------------------- Q7, as shipped
-#define I_H(Y) "v_add_u32_sdwa " Y ", %[s2], %[t] dst_sel:WORD_0 dst_unused:UNUSED_SEXT src0_sel:DWORD src1_sel:DWORD\n\t"
-#define I_I "v_add_u32_sdwa %[s2], %[p2], %[p3] dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_1 src1_sel:WORD_1\n\t"
-#define I_B(H1) "v_mul_i32_i24_dpp %[p2], " H1 ", %[cB0] row_ror:1 row_mask:0xf bank_mask:0xf\n\t"
-#define I_C(Y) "v_mul_i32_i24_dpp %[p0], " Y ", %[cB2] row_ror:1 row_mask:0xf bank_mask:0xf\n\t"
-#define I_D(Y) "v_mul_i32_i24_dpp %[p1], " Y ", %[cB1] row_ror:1 row_mask:0xf bank_mask:0xf\n\t"
-#define I_A(Y) "v_mad_i32_i24 %[p4], " Y ", %[nA1], %[k]\n\t"
-#define I_E(Y) "v_mad_i32_i24 %[p3], " Y ", %[nA0], %[k]\n\t"
-#define I_F "v_add_u32_sdwa %[t], %[p0], %[p4] dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_1 src1_sel:WORD_1\n\t"
-#define I_G "v_add_u32_sdwa %[u], %[p1], %[p2] dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_1 src1_sel:WORD_1\n\t"
-#define I_I9 "v_add_u32_sdwa %[s2], %[u], %[p3] dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:WORD_1\n\t"
-#define OLD7(Y, H1) I_H(Y) I_I I_B(H1) I_A(Y) I_C(Y) I_E(Y) I_F
-#define OLD9(Y, H1) I_H(Y) I_G I_B(H1) I_C(Y) I_A(Y) I_I9 I_D(Y) I_F I_E(Y)
+// SA_Q7_BLOCK7 (H I B A C E F) and SA_Q7_BLOCK9 (H G B C A I D F E), eight to a group as SA_Q7_STEPS8 lays them out
+#include "../../fpga_real_time_fft_analyzer_amd/csrc/q15_steps.hpp"
 
 // ---------------------------------------------------------------------------------------------- Q7, retimed
 // y[n] = sext16(S + hi(p4)),  p4 = y[n-1] * -A1 + k,  S = hi(B2 x[n]) + hi(B0 x[n-2]) + hi(-A0 y[n-2] + k) (+ hi(B1 x[n-1]))
@@ -56,9 +46,8 @@
 #define NEW7S(Y, Y1, Y2) S_H(Y) S_I S_A(Y) S_E(Y) R_C(Y1) R_B(Y2) R_F
 // round-3 order with the short encodings: H I B A C E F, t = hi(p0) - hi(p4)
 #define O_F "v_sub_u32_sdwa %[t], %[p0], %[p4] dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_1 src1_sel:WORD_1\n\t"
-#define OLD7S(Y, H1) I_H(Y) S_I I_B(H1) S_A(Y) I_C(Y) S_E(Y) O_F
+#define OLD7S(Y, H1) SA_Q7I_H(Y) S_I SA_Q7I_B(H1) S_A(Y) SA_Q7I_C(Y) S_E(Y) O_F
 
-#define G8_OLD(BLK) BLK("v52", "v59") BLK("v53", "v52") BLK("v54", "v53") BLK("v55", "v54") BLK("v56", "v55") BLK("v57", "v56") BLK("v58", "v57") BLK("v59", "v58")
 #define G8_NEW(BLK)                                                                                                    \
     BLK("v52", "v59", "v58") BLK("v53", "v52", "v59") BLK("v54", "v53", "v52") BLK("v55", "v54", "v53")                \
     BLK("v56", "v55", "v54") BLK("v57", "v56", "v55") BLK("v58", "v57", "v56") BLK("v59", "v58", "v57")
@@ -82,8 +71,8 @@
         out[blockIdx.x * blockDim.x + threadIdx.x] = s2 + S + p0 + p1 + p2 + p3 + p4 + t + u + y;                      \
     }
 
-Q7_KERNEL(k_old7, G8_OLD(OLD7))
-Q7_KERNEL(k_old9, G8_OLD(OLD9))
+Q7_KERNEL(k_old7, SA_Q7_STEPS8(SA_Q7_BLOCK7))
+Q7_KERNEL(k_old9, SA_Q7_STEPS8(SA_Q7_BLOCK9))
 Q7_KERNEL(k_new7a, G8_NEW(NEW7A))
 Q7_KERNEL(k_new7b, G8_NEW(NEW7B))
 Q7_KERNEL(k_new7c, G8_NEW(NEW7C))
@@ -91,21 +80,10 @@ Q7_KERNEL(k_new7d, G8_NEW(NEW7D))
 Q7_KERNEL(k_new9a, G8_NEW(NEW9A))
 Q7_KERNEL(k_new9b, G8_NEW(NEW9B))
 Q7_KERNEL(k_new7s, G8_NEW(NEW7S))
-Q7_KERNEL(k_old7s, G8_OLD(OLD7S))
+Q7_KERNEL(k_old7s, SA_Q7_STEPS8(OLD7S))
 
 // ---------------------------------------------------------------------------------------------- wide Q2.14
-// serial form (filter_w14_kernel): PP = own pair of block e-1 (the neighbour's is read from the same register name)
-#define W_SER(PP, PC, XC, XP, WC, WP)                                                                                  \
-    "v_dot2_i32_i16 %[al], " PP ", %[cfbl], %[k]\n\t"                                                                  \
-    "v_dot2_i32_i16 %[ah], " PP ", %[cfbh], 0\n\t"                                                                     \
-    "v_mov_b32_dpp " XC ", " PP " row_ror:1 row_mask:0xf bank_mask:0xf\n\t"                                            \
-    "v_dot2_i32_i16 %[al], " XC ", %[c01l], %[al]\n\t"                                                                 \
-    "v_dot2_i32_i16 %[ah], " XC ", %[c01h], %[ah]\n\t"                                                                 \
-    "v_dot2_i32_i16 %[al], " XP ", %[c2l], %[al]\n\t"                                                                  \
-    "v_dot2_i32_i16 %[ah], " XP ", %[c2h], %[ah]\n\t"                                                                  \
-    "v_ashrrev_i32 %[al], 14, %[al]\n\t"                                                                               \
-    "v_add_u32 " WC ", %[ah], %[al]\n\t"                                                                               \
-    "v_cvt_pk_i16_i32 " PC ", " WP ", " WC "\n\t"
+// serial form as shipped (filter_w14_kernel): SA_W14_BLOCK without the refill select
 // retimed form: the feed-forward sums (fl, fh) of block e+1 are formed inside block e from neighbour pairs that are at
 // least a block old (P2 = the pair of block e-2), interleaved with the feedback chain of block e
 #define W_RET(PP, P2, PC, XC, XP, WC, WP)                                                                              \
@@ -136,11 +114,12 @@ Q7_KERNEL(k_old7s, G8_OLD(OLD7S))
     W_SHORT("v52", "v57", "%[x0]", "%[x1]", "%[w0]", "%[w1]") W_SHORT("v57", "v53", "%[x1]", "%[x0]", "%[w1]", "%[w0]") \
     W_SHORT("v53", "v58", "%[x0]", "%[x1]", "%[w0]", "%[w1]") W_SHORT("v58", "v54", "%[x1]", "%[x0]", "%[w1]", "%[w0]") \
     W_SHORT("v54", "v59", "%[x0]", "%[x1]", "%[w0]", "%[w1]") W_SHORT("v59", "v55", "%[x1]", "%[x0]", "%[w1]", "%[w0]")
+#define W_SHIPPED(PP, PC, XC, XP, WC, WP) SA_W14_BLOCK(PP, PC, XC, XP, WC, WP, "")
 #define WG_SER                                                                                                         \
-    W_SER("v55", "v56", "%[x0]", "%[x1]", "%[w0]", "%[w1]") W_SER("v56", "v52", "%[x1]", "%[x0]", "%[w1]", "%[w0]")    \
-    W_SER("v52", "v57", "%[x0]", "%[x1]", "%[w0]", "%[w1]") W_SER("v57", "v53", "%[x1]", "%[x0]", "%[w1]", "%[w0]")    \
-    W_SER("v53", "v58", "%[x0]", "%[x1]", "%[w0]", "%[w1]") W_SER("v58", "v54", "%[x1]", "%[x0]", "%[w1]", "%[w0]")    \
-    W_SER("v54", "v59", "%[x0]", "%[x1]", "%[w0]", "%[w1]") W_SER("v59", "v55", "%[x1]", "%[x0]", "%[w1]", "%[w0]")
+    W_SHIPPED("v55", "v56", "%[x0]", "%[x1]", "%[w0]", "%[w1]") W_SHIPPED("v56", "v52", "%[x1]", "%[x0]", "%[w1]", "%[w0]") \
+    W_SHIPPED("v52", "v57", "%[x0]", "%[x1]", "%[w0]", "%[w1]") W_SHIPPED("v57", "v53", "%[x1]", "%[x0]", "%[w1]", "%[w0]") \
+    W_SHIPPED("v53", "v58", "%[x0]", "%[x1]", "%[w0]", "%[w1]") W_SHIPPED("v58", "v54", "%[x1]", "%[x0]", "%[w1]", "%[w0]") \
+    W_SHIPPED("v54", "v59", "%[x0]", "%[x1]", "%[w0]", "%[w1]") W_SHIPPED("v59", "v55", "%[x1]", "%[x0]", "%[w1]", "%[w0]")
 #define WG_RET                                                                                                         \
     W_RET("v55", "v59", "v56", "%[x0]", "%[x1]", "%[w0]", "%[w1]") W_RET("v56", "v55", "v52", "%[x1]", "%[x0]", "%[w1]", "%[w0]") \
     W_RET("v52", "v56", "v57", "%[x0]", "%[x1]", "%[w0]", "%[w1]") W_RET("v57", "v52", "v53", "%[x1]", "%[x0]", "%[w1]", "%[w0]") \

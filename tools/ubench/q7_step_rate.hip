@@ -1,20 +1,16 @@
-// Micro-benchmark: wall-clock time per step of the Q15 cascade's inner loop (chain_q15.hip, SA_Q7_STEP) with one
-// wave per SIMD on every SIMD of the chip (256 workgroups x 4 waves), against variants of the same nine
-// instructions.  No LDS, no refill, no stores: what is left is the floor of the recursion itself.
+// Micro-benchmark: wall-clock time per step of the Q15 cascade's inner loop (cascade_q15.hip; the instructions and the
+// shipped block SA_Q7_BLOCK9 come from its q15_steps.hpp) with one wave per SIMD on every SIMD of the chip (256
+// workgroups x 4 waves), against variants of the same nine instructions.  No LDS, no refill, no stores: what is left is
+// the floor of the recursion itself.
 //   hipcc -O3 --offload-arch=gfx950 q7_step_rate.hip -o q7_step_rate && ./q7_step_rate
 #include <hip/hip_runtime.h>
 #include <cstdio>
+#include "../../fpga_real_time_fft_analyzer_amd/csrc/q15_steps.hpp"
 
+#define R(NAME) "%[" NAME "]"
+// the first order this step shipped in: A B C D E F G H I on the outputs of the two steps before
 #define STEP_A(Y, H1, H2)                                                                                              \
-    "v_mad_i32_i24 %[p4], %[" H1 "], %[nA1], %[k]\n\t"                                                                 \
-    "v_mul_i32_i24_dpp %[p2], %[" H2 "], %[cB0] row_ror:1 row_mask:0xf bank_mask:0xf\n\t"                              \
-    "v_mul_i32_i24_dpp %[p0], %[" H1 "], %[cB2] row_ror:1 row_mask:0xf bank_mask:0xf\n\t"                              \
-    "v_mul_i32_i24_dpp %[p1], %[" H1 "], %[cB1] row_ror:1 row_mask:0xf bank_mask:0xf\n\t"                              \
-    "v_mad_i32_i24 %[p3], %[" H1 "], %[nA0], %[k]\n\t"                                                                 \
-    "v_add_u32_sdwa %[t], %[p0], %[p4] dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_1 src1_sel:WORD_1\n\t"        \
-    "v_add_u32_sdwa %[u], %[p1], %[p2] dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_1 src1_sel:WORD_1\n\t"        \
-    "v_add_u32_sdwa %[" Y "], %[s2], %[t] dst_sel:WORD_0 dst_unused:UNUSED_SEXT src0_sel:DWORD src1_sel:DWORD\n\t"     \
-    "v_add_u32_sdwa %[s2], %[u], %[p3] dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:WORD_1"
+    SA_Q7I_A(R(H1)) SA_Q7I_B(R(H2)) SA_Q7I_C(R(H1)) SA_Q7I_D(R(H1)) SA_Q7I_E(R(H1)) SA_Q7I_F SA_Q7I_G SA_Q7I_H(R(Y)) SA_Q7I_I9
 
 // same data flow, no SDWA / DPP modifiers at all (NOT the same arithmetic: a probe of what the modifiers cost)
 #define STEP_PLAIN(Y, H1, H2)                                                                                          \
@@ -99,18 +95,10 @@ __global__ __launch_bounds__(256) void k(int *out, int ngroups, int c)
 
 
 // ---- the same nine instructions in other cyclic orders (block = H first: y[n] from the prepared s2 and t) ------------
-// instruction names: A p4 = y*nA1 + k | B p2 = x[n-2]*B0 | C p0 = x*B2 | D p1 = x*B1 | E p3 = y*nA0 + k | F t = hi p0 + hi p4
-//                    G u = hi p1 + hi p2 | H y = s2 + t (word, sign-extended) | I s2 = u + hi p3
-#define I_A(H1) "v_mad_i32_i24 %[p4], %[" H1 "], %[nA1], %[k]\n\t"
-#define I_B(H2) "v_mul_i32_i24_dpp %[p2], %[" H2 "], %[cB0] row_ror:1 row_mask:0xf bank_mask:0xf\n\t"
-#define I_C(H1) "v_mul_i32_i24_dpp %[p0], %[" H1 "], %[cB2] row_ror:1 row_mask:0xf bank_mask:0xf\n\t"
-#define I_D(H1) "v_mul_i32_i24_dpp %[p1], %[" H1 "], %[cB1] row_ror:1 row_mask:0xf bank_mask:0xf\n\t"
-#define I_E(H1) "v_mad_i32_i24 %[p3], %[" H1 "], %[nA0], %[k]\n\t"
-#define I_F "v_add_u32_sdwa %[t], %[p0], %[p4] dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_1 src1_sel:WORD_1\n\t"
-#define I_G "v_add_u32_sdwa %[u], %[p1], %[p2] dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_1 src1_sel:WORD_1\n\t"
-#define I_H(Y) "v_add_u32_sdwa %[" Y "], %[s2], %[t] dst_sel:WORD_0 dst_unused:UNUSED_SEXT src0_sel:DWORD src1_sel:DWORD\n\t"
+// instruction names (SA_Q7I_* of q15_steps.hpp): A p4 = y*nA1 + k | B p2 = x[n-2]*B0 | C p0 = x*B2 | D p1 = x*B1 |
+//                    E p3 = y*nA0 + k | F t = hi p0 + hi p4 | G u = hi p1 + hi p2 | H y = s2 + t (word, sign-extended) |
+//                    I9 s2 = u + hi p3
 #define I_HP(Y) "v_add_u32 %[" Y "], %[s2], %[t]\n\t"
-#define I_I "v_add_u32_sdwa %[s2], %[u], %[p3] dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:WORD_1\n\t"
 // ten-instruction form: y written by a plain add, sign-extended off the critical cycle (S), own-lane products take
 // the low word sign-extended through SDWA (no rounding constant: the feedback terms are subtracted)
 #define I_S(Y) "v_bfe_i32 %[ys], %[" Y "], 0, 16\n\t"
@@ -131,10 +119,12 @@ template <int KIND>
 __device__ __forceinline__ void rstep(int &y, int &s2, Carry &c, int h1, int cB2, int cB1, int cB0, int nA0, int nA1, int k127)
 {
     int y0, p0 = c.p0, p1 = c.p1, p2 = c.p2, p3 = c.p3, p4 = c.p4, t = c.t, u = c.u;
-    if (KIND == 5) asm volatile(I_H("y0") I_G I_B("y7") I_C("y0") I_A("y0") I_I I_D("y0") I_F I_E("y0") ROPERANDS);     // F->H 2
-    if (KIND == 6) asm volatile(I_H("y0") I_G I_B("y7") I_C("y0") I_A("y0") I_I I_F I_D("y0") I_E("y0") ROPERANDS);     // A->F 2
-    if (KIND == 7) asm volatile(I_HP("y0") I_G I_B("y7") I_C("y0") I_A("y0") I_I I_D("y0") I_F I_E("y0") ROPERANDS);    // 5 with a plain y
-    if (KIND == 8) asm volatile(I_H("y0") I_B("y7") I_G I_I I_C("y0") I_A("y0") I_D("y0") I_F I_E("y0") ROPERANDS);     // H->C 4, H->A 5, G->I 1
+#define Y0 R("y0")
+#define Y7 R("y7")
+    if (KIND == 5) asm volatile(SA_Q7_BLOCK9(Y0, Y7) ROPERANDS);                                                        // as shipped; F->H 2
+    if (KIND == 6) asm volatile(SA_Q7I_H(Y0) SA_Q7I_G SA_Q7I_B(Y7) SA_Q7I_C(Y0) SA_Q7I_A(Y0) SA_Q7I_I9 SA_Q7I_F SA_Q7I_D(Y0) SA_Q7I_E(Y0) ROPERANDS);   // A->F 2
+    if (KIND == 7) asm volatile(I_HP("y0") SA_Q7I_G SA_Q7I_B(Y7) SA_Q7I_C(Y0) SA_Q7I_A(Y0) SA_Q7I_I9 SA_Q7I_D(Y0) SA_Q7I_F SA_Q7I_E(Y0) ROPERANDS);   // 5 with a plain y
+    if (KIND == 8) asm volatile(SA_Q7I_H(Y0) SA_Q7I_B(Y7) SA_Q7I_G SA_Q7I_I9 SA_Q7I_C(Y0) SA_Q7I_A(Y0) SA_Q7I_D(Y0) SA_Q7I_F SA_Q7I_E(Y0) ROPERANDS);   // H->C 4, H->A 5, G->I 1
     y = y0; c.p0 = p0; c.p1 = p1; c.p2 = p2; c.p3 = p3; c.p4 = p4; c.t = t; c.u = u;
 }
 
@@ -142,7 +132,7 @@ __device__ __forceinline__ void rstep(int &y, int &s2, Carry &c, int h1, int cB2
 __device__ __forceinline__ void tstep(int &yw, int &ysn, int &s2, Carry &c, int ys1, int ys2, int cB2, int cB1, int cB0, int nA0, int nA1)
 {
     int p0 = c.p0, p1 = c.p1, p2 = c.p2, p3 = c.p3, p4 = c.p4, t = c.t, u = c.u, ys;
-    asm volatile(I_HP("y0") I_G "v_mul_i32_i24_dpp %[p0], %[x1], %[cB2] row_ror:1 row_mask:0xf bank_mask:0xf\n\t" I_A2("y0")
+    asm volatile(I_HP("y0") SA_Q7I_G "v_mul_i32_i24_dpp %[p0], %[x1], %[cB2] row_ror:1 row_mask:0xf bank_mask:0xf\n\t" I_A2("y0")
                  "v_mul_i32_i24_dpp %[p1], %[x1], %[cB1] row_ror:1 row_mask:0xf bank_mask:0xf\n\t" I_I2 I_F2
                  "v_mul_i32_i24_dpp %[p2], %[x2], %[cB0] row_ror:1 row_mask:0xf bank_mask:0xf\n\t" I_S("y0") I_E2("y0")
                  : [y0] "+v"(yw), [ys] "=&v"(ys), [s2] "+v"(s2), [p0] "+v"(p0), [p1] "+v"(p1), [p2] "+v"(p2), [p3] "+v"(p3), [p4] "+v"(p4),
@@ -173,7 +163,7 @@ __global__ __launch_bounds__(256) void kr(int *out, int ngroups, int cc)
 }
 
 // eight blocks of the order H G B C A I D F E in ONE asm statement (no compiler padding between blocks)
-#define BLK(Y, H1) I_H(Y) I_G I_B(H1) I_C(Y) I_A(Y) I_I I_D(Y) I_F I_E(Y)
+#define BLK(Y, H1) SA_Q7_BLOCK9(R(Y), R(H1))
 __global__ __launch_bounds__(256) void kmerged(int *out, int ngroups, int cc)
 {
     int y0 = threadIdx.x, y1 = y0 + 1, y2 = y0 + 2, y3 = y0 + 3, y4 = y0 + 4, y5 = y0 + 5, y6 = y0 + 6, y7 = y0 + 7;
