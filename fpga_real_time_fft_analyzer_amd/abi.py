@@ -21,6 +21,7 @@ SA_FRAME_BYTES = 65536
 SA_FILTER_DEFAULT, SA_FILTER_CUSTOM, SA_FILTER_NONE, SA_FILTER_WIDE = 0x00, 0xA1, 0xB1, 0xA2
 SA_WIN_RTL_SIGNED, SA_WIN_HANN_U16 = 0, 1
 SA_OUT_MAG_FULL, SA_OUT_MAG_HALF, SA_OUT_SPEC_HALF, SA_OUT_TIME, SA_OUT_MARKER = 0, 1, 2, 3, 4
+SA_Q15_OUT_IQ, SA_Q15_OUT_MAG, SA_Q15_OUT_MARKER = 0, 1, 2
 SA_PRECISION_F32, SA_PRECISION_F64_STATE = 0, 1
 
 
@@ -28,6 +29,11 @@ class CmdEvents(C.Structure):
     """sa_cmd_events of include/specan.h."""
     _fields_ = [("n_start", C.c_int), ("n_uart_request", C.c_int), ("n_reset", C.c_int), ("n_uploads", C.c_int),
                 ("control_changed", C.c_int), ("transport", C.c_uint8)]
+
+
+class MarkerQ15(C.Structure):
+    """sa_marker_q15 of include/specan.h: one SA_Q15_OUT_MARKER record, 16 bytes."""
+    _fields_ = [("peak_mag", C.c_float), ("peak_bin", C.c_int32), ("band_power", C.c_uint64)]
 
 
 class SpecanError(RuntimeError):
@@ -94,6 +100,7 @@ def lib() -> C.CDLL:
     L.sa_set_window_mode_q15.argtypes = [H, C.c_int]
     L.sa_get_window_q15.argtypes = [H, C.POINTER(C.c_int16)]
     L.sa_process_q15.argtypes = [H, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    L.sa_process_q15_out.argtypes = [H, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
     L.sa_filter_q15.argtypes = [H, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
     L.sa_process_f32.argtypes = [H, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
     L.sa_process_f32_i16.argtypes = [H, C.c_void_p, C.c_float, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
@@ -111,7 +118,7 @@ def lib() -> C.CDLL:
                  "sa_get_filter_mode", "sa_load_coeffs_q7", "sa_get_coeffs_q7", "sa_feed_command_bytes",
                  "sa_feed_command_bytes_ex", "sa_get_transport",
                  "sa_load_sos_f32", "sa_load_sos_f64", "sa_load_sos_q14", "sa_set_window_q15",
-                 "sa_set_window_f32", "sa_set_window_mode_q15", "sa_get_window_q15", "sa_process_q15",
+                 "sa_set_window_f32", "sa_set_window_mode_q15", "sa_get_window_q15", "sa_process_q15", "sa_process_q15_out",
                  "sa_filter_q15", "sa_process_f32", "sa_process_f32_i16", "sa_pack_frame", "sa_debug_iir_plan_f32",
                  "sa_iir_plan_from_sos", "sa_set_precision", "sa_get_precision", "sa_debug_iir_plan_f64",
                  "sa_iir_plan_from_sos_f64", "sa_set_marker_range", "sa_get_marker_range"):

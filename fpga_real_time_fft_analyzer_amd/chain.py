@@ -18,7 +18,7 @@ import torch
 from . import abi
 from .abi import (SA_FILTER_CUSTOM, SA_FILTER_DEFAULT, SA_FILTER_NONE, SA_FILTER_WIDE, SA_N,
                   SA_OUT_MAG_FULL, SA_OUT_MAG_HALF, SA_OUT_MARKER, SA_OUT_SPEC_HALF, SA_OUT_TIME, SA_PRECISION_F32,
-                  SA_PRECISION_F64_STATE, SpecanError)
+                  SA_PRECISION_F64_STATE, SA_Q15_OUT_IQ, SA_Q15_OUT_MAG, SA_Q15_OUT_MARKER, SpecanError)
 
 # command bytes, same names as gui.py:28-37
 UART_REQUEST_CMD = 0xA5
@@ -39,6 +39,7 @@ FS_HZ = 1_000_000.0             # gui.py:45
 
 _OUT_KINDS = {"mag_full": SA_OUT_MAG_FULL, "mag_half": SA_OUT_MAG_HALF, "spec_half": SA_OUT_SPEC_HALF,
               "time": SA_OUT_TIME, "marker": SA_OUT_MARKER}
+_Q15_OUT_KINDS = {"iq": SA_Q15_OUT_IQ, "mag": SA_Q15_OUT_MAG, "marker": SA_Q15_OUT_MARKER}
 _PRECISIONS = {"f32": SA_PRECISION_F32, "f64": SA_PRECISION_F64_STATE}
 
 
@@ -350,17 +351,35 @@ class SpectrumChain:
         f = rec.view(torch.float32)
         return f[:, 0], rec[:, 1], f[:, 2]
 
-    def process_q15(self, x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """[B,16384] int16 -> [B,16384,2] int16 (re, im): B frames of 65536 bytes."""
+    def process_q15(self, x: torch.Tensor, out: Optional[torch.Tensor] = None, out_kind: str = "iq") -> torch.Tensor:
+        """[B,16384] int16 -> per ``out_kind``: 'iq' (the default) [B,16384,2] int16 (re, im), B frames of 65536 bytes;
+        'mag' [B,16384] float32, frames.decode_mag_16iq_le of each of those frames bit for bit (gui.py:250-260);
+        'marker' [B,4] int32, one sa_marker_q15 per frame over the marker range (peak_mag as float32 bits, peak_bin,
+        band_power as the two halves of an int64; see :meth:`markers_q15`)."""
+        if out_kind not in _Q15_OUT_KINDS:
+            raise SpecanError(abi.SA_EINVAL, f"out_kind must be one of {sorted(_Q15_OUT_KINDS)}")
         B = self._check_in(x, torch.int16)
-        shape = (B, SA_N, 2)
+        shape, dt = {"iq": ((B, SA_N, 2), torch.int16), "mag": ((B, SA_N), torch.float32),
+                     "marker": ((B, 4), torch.int32)}[out_kind]
         if out is None:
-            out = torch.empty(shape, dtype=torch.int16, device=self.device)
-        elif tuple(out.shape) != shape or out.dtype != torch.int16 or out.device != self.device or not out.is_contiguous():
-            raise SpecanError(abi.SA_ESHAPE, f"out must be a contiguous int16 tensor of shape {shape}")
-        self._check(self._lib.sa_process_q15(self._h, x.data_ptr(), out.data_ptr(), B, self._stream()))
+            out = torch.empty(shape, dtype=dt, device=self.device)
+        elif tuple(out.shape) != shape or out.dtype != dt or out.device != self.device or not out.is_contiguous():
+            raise SpecanError(abi.SA_ESHAPE, f"out must be a contiguous {dt} tensor of shape {shape}")
+        if out_kind == "iq":
+            self._check(self._lib.sa_process_q15(self._h, x.data_ptr(), out.data_ptr(), B, self._stream()))
+        else:
+            self._check(self._lib.sa_process_q15_out(self._h, x.data_ptr(), out.data_ptr(), B, _Q15_OUT_KINDS[out_kind],
+                                                     self._stream()))
         self._lend(x, out)
         return out
+
+    def markers_q15(self, x: torch.Tensor, out: Optional[torch.Tensor] = None):
+        """Peak search and band power of the integer chain's frames over the marker range: ``(peak_mag float32 [B],
+        peak_bin int32 [B], band_power int64 [B])``, views of the [B,4] int32 record tensor (``out``, allocated when
+        None) that ``process_q15(x, out, 'marker')`` fills.  peak_mag is the 'mag' value at peak_bin, bit for bit, and
+        band_power the exact integer sum of re^2 + im^2 over the range."""
+        rec = self.process_q15(x, out, out_kind="marker")
+        return rec.view(torch.float32)[:, 0], rec[:, 1], rec.view(torch.int64)[:, 1]
 
     def filter_q15(self, x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Window (+ integer IIR) only: the FFT input stream, [B,16384] int16."""

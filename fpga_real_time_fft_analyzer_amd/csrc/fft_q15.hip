@@ -144,6 +144,148 @@ __device__ __forceinline__ void fx_butterfly_real(int a, int b, int c, int d, ui
     }
 }
 
+constexpr int kFftWide = 1024;                            // threads per frame (fft_q15_kernel below)
+
+// ---- SA_Q15_OUT_MAG / SA_Q15_OUT_MARKER: the host's decode of the wire frame, made in the epilogue -------------------
+// decode_mag_16iq_le (gui.py:250-260) is np.sqrt(re.astype(float32)**2 + im.astype(float32)**2): four float32 operations,
+// each rounded on its own.  The two squares and their sum must therefore not be contracted into an FMA (hipcc's default
+// is -ffp-contract=fast; squares are exact only up to |v| = 4096), and the root must be the correctly rounded one.
+__device__ __forceinline__ float fx_mag_sum(unsigned p)
+{
+#pragma clang fp contract(off)
+    const float r = (float)lo16(p), i = (float)hi16(p);
+    const float rr = r * r, ii = i * i;
+    return rr + ii;
+}
+
+// Correctly rounded square root of s = 0 or an integer-valued float in [1, 2^31]: v_sqrt_f32 is within 1 ulp, so the
+// result is y or one of its two neighbours, told apart by the signs of the exact residuals s - y_down y and s - y_up y
+// (one FMA each).  This is the compiler's own sequence for sqrtf without its input scaling for denormals and its class
+// test for 0 and infinity, neither of which can occur: for s = 0 the lower neighbour is a NaN whose comparison fails
+// and the upper one gives a residual of 0, so the result is +0.
+__device__ __forceinline__ float fx_sqrt_rn(float s)
+{
+    const float y = __builtin_amdgcn_sqrtf(s);
+    const float dn = __builtin_bit_cast(float, __builtin_bit_cast(int, y) - 1);
+    const float up = __builtin_bit_cast(float, __builtin_bit_cast(int, y) + 1);
+    const float rd = __builtin_fmaf(-dn, y, s), ru = __builtin_fmaf(-up, y, s);
+    float z = rd <= 0.f ? dn : y;
+    z = ru > 0.f ? up : z;
+    return z;
+}
+
+__device__ __forceinline__ float fx_mag(unsigned p) { return fx_sqrt_rn(fx_mag_sum(p)); }
+
+// SA_Q15_OUT_MARKER: a part of the record -- the largest magnitude seen (-1: none yet), the lowest bin attaining it, and
+// the exact integer power sum (at most 16384 x 2^31 = 2^45).
+struct FxMark {
+    float mag;
+    int bin;
+    unsigned long long pow;
+};
+
+// Per bin the thread forms only s = fl(fl(re re) + fl(im im)) (-1 outside [lo, hi)) and the integer power; the root is
+// deferred to fx_mark_thread.  re^2 + im^2 reaches 2^31 (re = im = -32768): the dot product's 32-bit result is read as
+// unsigned.  MASK: k may lie outside the range.
+template <bool MASK>
+__device__ __forceinline__ float fx_mark_sum(unsigned long long &pow, unsigned p, int k, int lo, int hi)
+{
+    float s = fx_mag_sum(p);
+    unsigned pw = (unsigned)fx_dot2(p, p);
+    if constexpr (MASK) {
+        const bool in = (unsigned)(k - lo) < (unsigned)(hi - lo);
+        s = in ? s : -1.f;
+        pw = in ? pw : 0u;
+    }
+    pow += pw;
+    return s;
+}
+
+// The wave's 64 bins of one m' are [kw, kw + 64) (kw wave-uniform): one scalar decision for all of them -- skip, take
+// whole, or test bin by bin where an edge of the range cuts through.
+__device__ __forceinline__ float fx_mark_sum_any(unsigned long long &pow, unsigned p, int k, int kw, int lo, int hi)
+{
+    if (kw + 64 <= lo || kw >= hi) return -1.f;
+    if (kw >= lo && kw + 64 <= hi) return fx_mark_sum<false>(pow, p, k, lo, hi);
+    return fx_mark_sum<true>(pow, p, k, lo, hi);
+}
+
+// The thread's part from its 16 sums s[m'] (bin t + 1024 m'), with ONE root instead of sixteen.  The correctly rounded
+// root is monotone, so the thread's largest magnitude is M = rt(S), S = max s, and its bins attaining M are those with
+// s > L, L = ((M + M_prev) / 2)^2 the square of the rounding boundary below M (s <= S keeps them below the upper one).
+// L is exact in double (a 25-bit number squared).  s = L cannot happen: the boundary is an odd multiple of half an ulp,
+// its square has some 49 significant bits and s has 24 -- so there is no tie case, and the test per bin is s >= T with
+// T the float next above L.  M = 0: every bin of the range attains it (T = 0; bins outside hold -1).  No bin of the
+// thread in the range (S = -1): magnitude -1, T = +inf.
+__device__ __forceinline__ FxMark fx_mark_thread(const float (&s)[16], int t, unsigned long long pow)
+{
+    float top = -1.f;
+#pragma unroll
+    for (int m = 0; m < 16; ++m) top = __builtin_fmaxf(top, s[m]);
+    const float mag = fx_sqrt_rn(__builtin_fmaxf(top, 0.f));
+    const float prev = __builtin_bit_cast(float, __builtin_bit_cast(int, mag) - 1);
+    const double mid = 0.5 * ((double)mag + (double)prev);
+    const double edge = mid * mid;
+    float thr = (float)edge;
+    thr = (double)thr > edge ? thr : __builtin_bit_cast(float, __builtin_bit_cast(int, thr) + 1);
+    thr = mag > 0.f ? thr : 0.f;
+    thr = top < 0.f ? __builtin_inff() : thr;
+    int bin = SA_NPTS;
+#pragma unroll
+    for (int m = 15; m >= 0; --m) bin = s[m] >= thr ? t + kFftWide * m : bin;      // descending: the lowest bin stays
+    return {top < 0.f ? -1.f : mag, bin, pow};
+}
+
+// a <- combine(a, b): the exact sum and the (larger magnitude, then lower bin) pair.  Symmetric and associative, integer
+// sum: the record's bits depend on the data alone, whatever the order of the merges.
+__device__ __forceinline__ void fx_mark_merge(FxMark &a, const FxMark &b)
+{
+    a.pow += b.pow;
+    if (b.mag > a.mag || (b.mag == a.mag && b.bin < a.bin)) {
+        a.mag = b.mag;
+        a.bin = b.bin;
+    }
+}
+
+template <int XOR>
+__device__ __forceinline__ FxMark fx_mark_swizzle(const FxMark &a)
+{
+    constexpr int pat = (XOR << 10) | 0x1F;                  // ds_swizzle bitmask mode: lane ^ XOR inside 32 lanes
+    const unsigned lo = (unsigned)__builtin_amdgcn_ds_swizzle((int)(unsigned)a.pow, pat);
+    const unsigned hi = (unsigned)__builtin_amdgcn_ds_swizzle((int)(unsigned)(a.pow >> 32), pat);
+    return {__builtin_bit_cast(float, __builtin_amdgcn_ds_swizzle(__builtin_bit_cast(int, a.mag), pat)),
+            __builtin_amdgcn_ds_swizzle(a.bin, pat), (unsigned long long)hi << 32 | lo};
+}
+
+// every lane of a half-wave ends with the half-wave's part
+__device__ __forceinline__ void fx_mark_reduce32(FxMark &a)
+{
+    fx_mark_merge(a, fx_mark_swizzle<1>(a));
+    fx_mark_merge(a, fx_mark_swizzle<2>(a));
+    fx_mark_merge(a, fx_mark_swizzle<4>(a));
+    fx_mark_merge(a, fx_mark_swizzle<8>(a));
+    fx_mark_merge(a, fx_mark_swizzle<16>(a));
+}
+
+// The frame's record from the threads' parts: a swizzle butterfly inside each half-wave, the 32 half-wave parts through
+// `scr` (512 bytes of LDS behind the frame image, so no barrier is needed to free the image first), a second butterfly
+// over them in wave 0, and one 16-byte vector store by thread 0.  No atomics.
+constexpr int kFxMarkParts = kFftWide / 32;
+__device__ __forceinline__ void fx_mark_finish(FxMark a, uint4 *scr, void *__restrict__ out, int f, int t, int wave)
+{
+    fx_mark_reduce32(a);
+    if ((t & 31) == 0)
+        scr[t >> 5] = make_uint4(__builtin_bit_cast(unsigned, a.mag), (unsigned)a.bin, (unsigned)a.pow, (unsigned)(a.pow >> 32));
+    __syncthreads();
+    if (wave != 0) return;
+    const uint4 v = scr[t & 31];
+    a = {__builtin_bit_cast(float, v.x), (int)v.y, (unsigned long long)v.w << 32 | v.z};
+    fx_mark_reduce32(a);
+    if (t == 0)
+        reinterpret_cast<uint4 *>(out)[f] =
+            make_uint4(__builtin_bit_cast(unsigned, a.mag), (unsigned)a.bin, (unsigned)a.pow, (unsigned)(a.pow >> 32));
+}
+
 // SA-FXFFT-1 with 1024 threads per frame: 16 positions per thread (t + 1024 m); the seven radix-4 stages run as four
 // register passes -- stage 0 from global memory, then (1,2), (3,4), (5,6) -- with one LDS exchange between passes.
 // (Round 1 and most of round 2 ran 256 threads x 64 positions, stages 4..6 in registers: 120 registers per thread, 2 waves
@@ -156,13 +298,17 @@ __device__ __forceinline__ void fx_butterfly_real(int a, int b, int c, int d, ui
 //   butterfly bf in [0,4096): j' = bf >> 2s, kappa = bf & (4^s - 1); inputs at bf + i*4096;
 //   output i' at (j' << (2s+2)) | (i' << 2s) | kappa; twiddle exponent i' * j' * 4^s.
 // 8 waves per SIMD (two frames per CU, 64 KiB of LDS each) need <= 64 registers: the second launch bound asks for that.
-constexpr int kFftWide = 1024;
+// OUT (SA_Q15_OUT_*): what the epilogue makes of the natural-order bins -- the wire frame itself, its magnitudes, or the
+// marker record over the bins [mrange & 0xFFFF, mrange >> 16) (read by the MARKER instantiations only; last in the
+// arguments, so the other kinds' argument loads are where they were).
+constexpr int kFftLds = SA_NPTS * 4;                      // the frame image; MARKER: + kFxMarkParts x 16 bytes behind it
 
-template <bool WINDOW>
+template <bool WINDOW, int OUT>
 __global__ __launch_bounds__(kFftWide, 8) void fft_q15_kernel(const int16_t *__restrict__ in,
-                                                               int16_t *__restrict__ out_iq, int batch,
+                                                               void *__restrict__ out, int batch,
                                                                SaQ15Params prm, const int16_t *__restrict__ rom,
-                                                               const uint2 *__restrict__ tw, const uint4 *__restrict__ twrec)
+                                                               const uint2 *__restrict__ tw, const uint4 *__restrict__ twrec,
+                                                               unsigned mrange)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_q[];
     unsigned *buf = reinterpret_cast<unsigned *>(smem_q);     // [16384] packed (re, im)
@@ -280,28 +426,57 @@ __global__ __launch_bounds__(kFftWide, 8) void fft_q15_kernel(const int16_t *__r
     }
     // stage 6 (4^s = 4096): no twiddles; outputs at m' = u + 4 i' = natural-order bin t + 1024 m'
     // frame layout: [16384] x (re, im) int16 = 65536 bytes (imp/sequ2.vhd:153); one dword per lane
-    unsigned *o32 = reinterpret_cast<unsigned *>(out_iq + (size_t)f * SA_NPTS * 2);
+    // SA_Q15_OUT_MAG: the same dwords at the same offsets of a float row, each the magnitude of its bin.
+    // SA_Q15_OUT_MARKER: no spectrum store; the thread keeps the 16 sums re^2 + im^2 of its bins and roots their largest.
+    unsigned *o32 = reinterpret_cast<unsigned *>(reinterpret_cast<int16_t *>(out) + (size_t)f * SA_NPTS * 2);
+    const int mlo = (int)(mrange & 0xFFFFu), mhi = (int)(mrange >> 16);
+    float ms[16];
+    unsigned long long mpow = 0ull;
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
         unsigned o[4];
         fx_butterfly(w[u], w[u + 4], w[u + 8], w[u + 12], make_uint2(0u, 0u), make_uint2(0u, 0u), make_uint2(0u, 0u), true, o, false,
                      false, false);
 #pragma unroll
-        for (int i = 0; i < 4; ++i) __builtin_nontemporal_store(o[i], o32 + t + kFftWide * (u + 4 * i));   // streaming: written once
+        for (int i = 0; i < 4; ++i) {
+            const int mp = u + 4 * i;
+            if constexpr (OUT == SA_Q15_OUT_IQ)
+                __builtin_nontemporal_store(o[i], o32 + t + kFftWide * mp);   // streaming: written once
+            else if constexpr (OUT == SA_Q15_OUT_MAG)
+                __builtin_nontemporal_store(fx_mag(o[i]), reinterpret_cast<float *>(o32) + t + kFftWide * mp);
+            else
+                ms[mp] = fx_mark_sum_any(mpow, o[i], t + kFftWide * mp, (wave << 6) + kFftWide * mp, mlo, mhi);
+        }
     }
+    if constexpr (OUT == SA_Q15_OUT_MARKER) {
+        fx_mark_finish(fx_mark_thread(ms, t, mpow), reinterpret_cast<uint4 *>(smem_q + kFftLds), out, f, t, wave);
+    }
+}
+
+template <int OUT>
+hipError_t launch_fft_q15(const int16_t *in_time, void *out, int batch, bool apply_window, const SaQ15Params &p,
+                          const SaQ15Tables &t, hipStream_t stream, SaLaunchEv ev)
+{
+    const dim3 grid(batch), block(kFftWide);
+    const int lds = kFftLds + (OUT == SA_Q15_OUT_MARKER ? kFxMarkParts * (int)sizeof(uint4) : 0);
+    auto k = apply_window ? fft_q15_kernel<true, OUT> : fft_q15_kernel<false, OUT>;
+    const hipError_t e = sa_set_dyn_lds_once(reinterpret_cast<const void *>(k), lds);
+    if (e != hipSuccess) return e;
+    hipExtLaunchKernelGGL(k, grid, block, lds, stream, ev.start, ev.stop, 0, in_time, out, batch, p, t.rom, t.tw, t.twrec,
+                          (unsigned)t.marker_lo | (unsigned)t.marker_hi << 16);
+    return hipGetLastError();
 }
 
 }  // namespace
 
-hipError_t sa_launch_fft_q15(const int16_t *in_time, int16_t *out_iq, int batch, bool apply_window,
+hipError_t sa_launch_fft_q15(const int16_t *in_time, void *out, int batch, int out_kind, bool apply_window,
                              const SaQ15Params &p, const SaQ15Tables &t, hipStream_t stream, SaLaunchEv ev)
 {
     if (batch <= 0) return hipSuccess;
-    const dim3 grid(batch), block(kFftWide);
-    const int lds = SA_NPTS * 4;
-    auto k = apply_window ? fft_q15_kernel<true> : fft_q15_kernel<false>;
-    const hipError_t e = sa_set_dyn_lds_once(reinterpret_cast<const void *>(k), lds);
-    if (e != hipSuccess) return e;
-    hipExtLaunchKernelGGL(k, grid, block, lds, stream, ev.start, ev.stop, 0, in_time, out_iq, batch, p, t.rom, t.tw, t.twrec);
-    return hipGetLastError();
+    switch (out_kind) {
+        case SA_Q15_OUT_IQ: return launch_fft_q15<SA_Q15_OUT_IQ>(in_time, out, batch, apply_window, p, t, stream, ev);
+        case SA_Q15_OUT_MAG: return launch_fft_q15<SA_Q15_OUT_MAG>(in_time, out, batch, apply_window, p, t, stream, ev);
+        case SA_Q15_OUT_MARKER: return launch_fft_q15<SA_Q15_OUT_MARKER>(in_time, out, batch, apply_window, p, t, stream, ev);
+        default: return hipErrorInvalidValue;
+    }
 }

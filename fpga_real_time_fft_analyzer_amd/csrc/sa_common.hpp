@@ -156,10 +156,12 @@ struct SaQ15Tables {
     const uint2 *tw;           // [16384] Q15 twiddles as packed int16 pairs: x = (wr, wi), y = (-wi, wr)
     const uint4 *twrec;        // [2 * kSaTwRecs] the per-lane twiddles of FFT stages 0..2 as 32-byte records {w1, w2, w3, pad}:
                                // records 0..4095: stage 0, exponent bf; 4096..5119: stage 1, exponent 4 j'; 5120..5375: stage 2, 16 j''
+    int marker_lo, marker_hi;  // SA_Q15_OUT_MARKER: the bin range [lo, hi), by value in the kernel arguments
 };
 constexpr int kSaTwRecs = 4096 + 1024 + 256;
 
 hipError_t sa_launch_filter_q15(const int16_t *in, int16_t *out_time, int batch, const SaQ15Params &p,
                                 const SaQ15Tables &t, hipStream_t stream, SaLaunchEv ev);
-hipError_t sa_launch_fft_q15(const int16_t *in_time, int16_t *out_iq, int batch, bool apply_window,
+// out per out_kind (SA_Q15_OUT_*): int16 [B,16384,2], float [B,16384] or sa_marker_q15 [B]
+hipError_t sa_launch_fft_q15(const int16_t *in_time, void *out, int batch, int out_kind, bool apply_window,
                              const SaQ15Params &p, const SaQ15Tables &t, hipStream_t stream, SaLaunchEv ev);

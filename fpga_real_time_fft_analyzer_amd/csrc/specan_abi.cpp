@@ -106,7 +106,7 @@ struct sa_handle {
     std::vector<double> win64;             // the window in double, natural order: default Hann or the caller's table widened
     double *d_win64 = nullptr;             // win64 transposed for iir_f64.hip: [32][256] pairs, pair (g, t) = w[64t + 2g], w[..+1]
     float4 *d_win_half = nullptr;          // constant 1/2 (the split step's factor) in the pass-A layout: the FFT launch's window
-    // ---- SA_OUT_MARKER range (sa_set_marker_range): host state only, passed by value to every marker launch
+    // ---- SA_OUT_MARKER / SA_Q15_OUT_MARKER range (sa_set_marker_range): host state only, passed by value to every marker launch
     int marker_lo = 0, marker_hi = SA_NPTS;
     // ---- stream-ordered control plane (no device-wide synchronisation anywhere after sa_create)
     // Table uploads run on the handle's own control stream: it first waits for everything the handle has
@@ -1096,22 +1096,27 @@ static SaQ15Params q15_params(const sa_handle *h)
     return p;
 }
 
-// sa_filter_q15 (`fft` false: window + integer cascade into `out`) and sa_process_q15; `fn` names the entry point
-static int process_q15(sa_handle *h, const char *fn, const int16_t *in, int16_t *out, int batch, void *stream, bool fft)
+// sa_filter_q15 (`fft` false: window + integer cascade into `out`, out_kind unused) and sa_process_q15 / sa_process_q15_out
+// (`out` per out_kind, SA_Q15_OUT_*: the FFT launch's epilogue makes it); `fn` names the entry point
+static int process_q15(sa_handle *h, const char *fn, const int16_t *in, void *out, int batch, int out_kind, void *stream,
+                       bool fft)
 {
     if (!h) return SA_EINVAL;
     if (batch < 0) return fail_at(h, SA_ESHAPE, fn, "negative batch");
+    if (out_kind < SA_Q15_OUT_IQ || out_kind > SA_Q15_OUT_MARKER) return fail_at(h, SA_EINVAL, fn, "bad out_kind");
     if (batch == 0) return SA_OK;
     if (!in || !out) return fail_at(h, SA_EINVAL, fn, "NULL tensor");
+    if (out_kind == SA_Q15_OUT_MARKER && ((uintptr_t)out & 15u) != 0)
+        return fail_at(h, SA_EINVAL, fn, "SA_Q15_OUT_MARKER output must be 16-byte aligned");
     SA_HIP(h, hipSetDevice(h->device));
     const SaQ15Params p = q15_params(h);
     const bool staged = fft && p.filter != SA_FILTER_NONE;      // cascade into the slot's workspace, then the FFT
     CallCtx c;
     { const int rc = begin_call(h, (hipStream_t)stream, staged ? sa_handle::kWorkQ15 : -1, batch, &c); if (rc != SA_OK) return rc; }
-    const SaQ15Tables t = {h->d_rom, h->d_twq, h->d_twrec};
+    const SaQ15Tables t = {h->d_rom, h->d_twq, h->d_twrec, h->marker_lo, h->marker_hi};
     if (!staged) {
-        SA_HIP(h, fft ? sa_launch_fft_q15(in, out, batch, true, p, t, c.stream, {c.start, c.stop})
-                      : sa_launch_filter_q15(in, out, batch, p, t, c.stream, {c.start, c.stop}));
+        SA_HIP(h, fft ? sa_launch_fft_q15(in, out, batch, out_kind, true, p, t, c.stream, {c.start, c.stop})
+                      : sa_launch_filter_q15(in, (int16_t *)out, batch, p, t, c.stream, {c.start, c.stop}));
         return end_call(h, c);
     }
     // The WIDE cascade does not gain from overlapped launches (tools/q15_overlap_modes.py, profiles/r4_q15_helper_waves.txt):
@@ -1124,18 +1129,23 @@ static int process_q15(sa_handle *h, const char *fn, const int16_t *in, int16_t 
     }
     int16_t *ws = (int16_t *)h->slot[c.slot].work[sa_handle::kWorkQ15].ptr;
     SA_HIP(h, sa_launch_filter_q15(in, ws, batch, p, t, c.stream, {c.start, nullptr}));
-    SA_HIP(h, sa_launch_fft_q15(ws, out, batch, false, p, t, c.stream, {nullptr, c.stop}));
+    SA_HIP(h, sa_launch_fft_q15(ws, out, batch, out_kind, false, p, t, c.stream, {nullptr, c.stop}));
     return end_call(h, c);
 }
 
 int sa_filter_q15(sa_handle *h, const int16_t *in, int16_t *out_time, int batch, void *stream)
 {
-    return process_q15(h, "sa_filter_q15", in, out_time, batch, stream, false);
+    return process_q15(h, "sa_filter_q15", in, out_time, batch, SA_Q15_OUT_IQ, stream, false);
 }
 
 int sa_process_q15(sa_handle *h, const int16_t *in, int16_t *out_iq, int batch, void *stream)
 {
-    return process_q15(h, "sa_process_q15", in, out_iq, batch, stream, true);
+    return process_q15(h, "sa_process_q15", in, out_iq, batch, SA_Q15_OUT_IQ, stream, true);
+}
+
+int sa_process_q15_out(sa_handle *h, const int16_t *in, void *out, int batch, int out_kind, void *stream)
+{
+    return process_q15(h, "sa_process_q15_out", in, out, batch, out_kind, stream, true);
 }
 
 // sa_process_f32 (float frames) and sa_process_f32_i16 (int16 samples times `scale`); `fn` names the entry point.

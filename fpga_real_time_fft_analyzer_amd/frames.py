@@ -29,6 +29,18 @@ def decode_mag_16iq_le(frame_bytes: bytes) -> np.ndarray:
     return np.sqrt(re.astype(np.float32) ** 2 + im.astype(np.float32) ** 2)
 
 
+def marker_of_frame(frame_bytes: bytes, lo: int = 0, hi: int = FFT_SIZE):
+    """What the gui shows of a frame cut to the bins [lo, hi) (gui.py:294-305, 415-455): ``(peak_mag float32, peak_bin
+    int, band_power int)`` -- np.max and lo + np.argmax of the decoded magnitudes, and the exact integer sum of
+    re^2 + im^2.  The host mirror of one sa_marker_q15 record (include/specan.h)."""
+    if not 0 <= lo < hi <= FFT_SIZE:
+        raise ValueError("need 0 <= lo < hi <= 16384")
+    mag = decode_mag_16iq_le(frame_bytes)[lo:hi]
+    re, im = _iq(frame_bytes)
+    power = (re[lo:hi].astype(np.int64) ** 2 + im[lo:hi].astype(np.int64) ** 2).sum()
+    return np.float32(mag.max()), lo + int(mag.argmax()), int(power)
+
+
 def decode_iq_components(frame_bytes: bytes):
     """Same result as gui.py:262-270: (re, im) as float32 arrays."""
     re, im = _iq(frame_bytes)

@@ -117,6 +117,35 @@ typedef struct sa_marker {
     uint32_t reserved;    /* written as 0 */
 } sa_marker;              /* 16 bytes; one aligned store per frame */
 
+/* output layouts for sa_process_q15_out(): three views of the integer chain's frame, each defined bit for bit */
+#define SA_Q15_OUT_IQ      0   /* int16 [B,16384,2]  the 65536-byte wire frame: what sa_process_q15 writes */
+#define SA_Q15_OUT_MAG     1   /* float [B,16384]    decode_mag_16iq_le of that frame (gui.py:250-260), bit for bit */
+#define SA_Q15_OUT_MARKER  2   /* sa_marker_q15 [B]  peak search + band power of that decode over the marker range */
+
+/* SA_Q15_OUT_MAG is DEFINED as the float32 evaluation gui.py:250-260 makes of the frame,
+ *     np.sqrt(re.astype(np.float32)**2 + im.astype(np.float32)**2):
+ * r = (float)re, i = (float)im, p = fl(r*r), q = fl(i*i), s = fl(p + q), mag = the correctly rounded sqrt(s); each of the
+ * four operations rounds to float32 on its own (no fused multiply-add: |re| or |im| above 4096 has an inexact square).
+ * All N bins, as gui.py:294-305 plots them.  re = im = -32768 is reachable: re^2 + im^2 goes up to 2^31.
+ *
+ * SA_Q15_OUT_MARKER record: what gui.py computes from that decode for every frame it shows -- the slice to the user's
+ * range (get_frequency_range_data, gui.py:294-305), then np.max / np.argmax (emit_plot_data, gui.py:415-455; the peak
+ * markers of gui.py:691-712) -- made in the FFT kernel's epilogue with no spectrum stored: 16 bytes per frame.
+ *   - peak_mag is bit for bit the SA_Q15_OUT_MAG value at peak_bin, and peak_bin the LOWEST k in [lo, hi) attaining it:
+ *     numpy.argmax on the MAG row slice, plus lo.  The comparison is on the float magnitudes, not on the integers
+ *     re^2 + im^2: two bins with different integer powers can round to one float, and the lower bin is reported.
+ *     Unlike the float chain, the mirror bin N-k is NOT always a bit-identical tie here (the per-stage truncation of
+ *     SA-FXFFT-1 breaks the symmetry), so a full-range record may name N-b for a tone at b -- as numpy does on the frame.
+ *   - band_power is the sum over k in [lo, hi) of re[k]^2 + im[k]^2 as an exact integer (at most 16384 x 2^31 = 2^45):
+ *     order-free, so the record is bit-reproducible with no rule about the summation order.  No atomics.
+ *   - an all-zero frame gives (+0.0f, lo, 0).
+ *   - `out` of SA_Q15_OUT_MARKER must be 16-byte aligned (SA_EINVAL otherwise). */
+typedef struct sa_marker_q15 {
+    float    peak_mag;    /* max over k in [lo, hi) of the SA_Q15_OUT_MAG value */
+    int32_t  peak_bin;    /* lowest k in [lo, hi) attaining it */
+    uint64_t band_power;  /* sum over k in [lo, hi) of re[k]^2 + im[k]^2, exact */
+} sa_marker_q15;          /* 16 bytes; one aligned store per frame */
+
 /* precision of the float path's window and cascade (sa_set_precision) */
 #define SA_PRECISION_F32       0   /* default: float32 arithmetic throughout, one fused kernel per call */
 #define SA_PRECISION_F64_STATE 1   /* window, inter-section signal and DF2T recursion in float64; FFT in float32 */
@@ -238,6 +267,15 @@ int sa_get_window_q15(const sa_handle *h, int16_t *w /* [16384] */);
  * stands where ip/xfft_0 stands; 1/N scaling, truncation. */
 int sa_process_q15(sa_handle *h, const int16_t *in, int16_t *out_iq, int batch, void *stream);
 
+/* The same chain with the host's first steps on the frame made in the FFT kernel's epilogue (build extension): `out` per
+ * out_kind (SA_Q15_OUT_*, above).  SA_Q15_OUT_IQ is sa_process_q15() itself; SA_Q15_OUT_MAG replaces decode_mag_16iq_le
+ * (gui.py:250-260) on the host, SA_Q15_OUT_MARKER the range slice and np.max / np.argmax on top (gui.py:294-305, 415-455,
+ * 691-712), 16 bytes per frame instead of 64 KiB.  Everything sa_process_q15() does holds for every kind: all four filter
+ * modes, both window modes, custom ROMs, every overlap depth, launch timing, hipGraph capture once sa_reserve() has
+ * sized the workspace.  SA_EINVAL for an unknown kind, a NULL tensor or a marker `out` that is not 16-byte aligned:
+ * nothing is launched and no call state changes. */
+int sa_process_q15_out(sa_handle *h, const int16_t *in, void *out, int batch, int out_kind, void *stream);
+
 /* Window (+ integer IIR) only: the FFT input stream, [B,16384] int16 (fft_in16 of
  * new/command_control.vhd:90-123). */
 int sa_filter_q15(sa_handle *h, const int16_t *in, int16_t *out_time, int batch, void *stream);
@@ -301,8 +339,9 @@ int sa_iir_plan_from_sos(const double *sos, int n_sections, float *out, int cap)
 int sa_set_precision(sa_handle *h, int precision /* SA_PRECISION_* */);
 int sa_get_precision(const sa_handle *h, int *precision);
 
-/* ---- marker range (SA_OUT_MARKER; build extension) ------------------------------------------------------------------
- * The full-spectrum bins [lo, hi) the SA_OUT_MARKER records of sa_process_f32 / sa_process_f32_i16 cover: the gui's
+/* ---- marker range (SA_OUT_MARKER, SA_Q15_OUT_MARKER; build extension) ------------------------------------------------
+ * The full-spectrum bins [lo, hi) the SA_OUT_MARKER records of sa_process_f32 / sa_process_f32_i16 and the
+ * SA_Q15_OUT_MARKER records of sa_process_q15_out cover -- one range per handle for both chains: the gui's
  * frequency range (web_config freq_range_start / freq_range_end in per mille of the N bins, gui.py:294-305) as bin
  * indices.  [0, 16384) at sa_create(), the gui's default 0..1000 per mille.  0 <= lo < hi <= SA_N, else SA_EINVAL and
  * nothing changed.  Not board state: the 0xFF reset of sa_feed_command_bytes leaves it alone.
@@ -311,7 +350,9 @@ int sa_get_precision(const sa_handle *h, int *precision);
  *     so a captured call keeps the range of its capture time.
  *   - SA_OUT_MARKER works in filter modes NONE, DEFAULT and CUSTOM, in both precisions (in SA_PRECISION_F64_STATE the
  *     float chain on the float64 cascade's output makes the records), at every overlap depth, with launch timing and
- *     under hipGraph capture. */
+ *     under hipGraph capture.
+ *   - SA_Q15_OUT_MARKER works in filter modes NONE, DEFAULT, CUSTOM and WIDE under the same rules: the range travels by
+ *     value in the FFT launch's arguments (gui.py:294-305 slices the decoded frame with the very same indices). */
 int sa_set_marker_range(sa_handle *h, int lo, int hi);
 int sa_get_marker_range(const sa_handle *h, int *lo, int *hi);
 
