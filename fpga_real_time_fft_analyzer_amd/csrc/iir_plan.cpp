@@ -300,3 +300,12 @@ int export_plan(const SaIirK &p, const SaIirLaneTab &lt, float *out, int cap)
     if (out && cap > 0) std::memcpy(out, v.data(), sizeof(float) * (size_t)(cap < n ? cap : n));
     return n;
 }
+
+// the float64-state plan of an a0-normalised SOS as flat doubles (sa_debug_iir_plan_f64, sa_iir_plan_from_sos_f64)
+int export_plan_f64(const double *sos_norm, int nsec, double *out, int cap)
+{
+    SaIirF64 p;
+    build_plan_f64(sos_norm, nsec, &p);
+    if (out && cap > 0) std::memcpy(out, &p, sizeof(double) * (size_t)(cap < kSaIirF64Doubles ? cap : kSaIirF64Doubles));
+    return kSaIirF64Doubles;
+}

@@ -13,5 +13,6 @@ void build_plan_f64(const double *sos_in, int nsec_in, SaIirF64 *p);
 void sos_from_q7(const int8_t *c12, double *sos /*[6][6]*/);
 bool normalise_a0(const double *sos, int n_sections, double *norm /*[36]*/);
 int export_plan(const SaIirK &p, const SaIirLaneTab &lt, float *out, int cap);
+int export_plan_f64(const double *sos_norm, int nsec, double *out, int cap);
 
 #pragma GCC visibility pop

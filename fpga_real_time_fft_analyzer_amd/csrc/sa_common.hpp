@@ -116,7 +116,7 @@ struct SaQ15Params {
 hipError_t sa_set_dyn_lds_once(const void *kernel, int bytes);
 
 // launchers (defined in chain_f32.hip, chain_f32_i16.hip, cascade_q15.hip and fft_q15.hip)
-struct SaF32Tables {
+struct SaF32Tables {               // the windows and twiddles are filled by sa_tables.hpp / sa_tables.cpp
     const float4 *win_b;       // [16][256] 0.5 * window in the pass-A layout of the no-IIR kernel:
                                //   win_b[p][t] = w[512(2p)+2t], w[..+1], w[512(2p+1)+2t], w[..+1]
     const float4 *win_t;       // [16][256] the same, transposed: win_t[g][t] = win_half[64t + 4g .. +3]
@@ -151,7 +151,7 @@ hipError_t sa_launch_chain_f32_i16(const int16_t *in, float in_scale, void *out,
 hipError_t sa_launch_iir_f64(const void *in, bool in_i16, float in_scale, float *out, int batch, int nsec,
                              const SaIirF64 *plan, const double *win_tr, hipStream_t stream, SaLaunchEv ev);
 
-struct SaQ15Tables {
+struct SaQ15Tables {                 // rom, tw and twrec are filled by sa_tables.hpp / sa_tables.cpp
     const int16_t *rom;        // [16384] window ROM
     const uint2 *tw;           // [16384] Q15 twiddles as packed int16 pairs: x = (wr, wi), y = (-wi, wr)
     const uint4 *twrec;        // [2 * kSaTwRecs] the per-lane twiddles of FFT stages 0..2 as 32-byte records {w1, w2, w3, pad}:
