@@ -18,6 +18,7 @@ CSRC = os.path.join(_PKG, "csrc")
 SA_OK, SA_EINVAL, SA_ESHAPE, SA_EHIP, SA_ESTATE, SA_ENOMEM = 0, -1, -2, -3, -4, -5
 SA_N = 16384
 SA_FRAME_BYTES = 65536
+SA_P12_FRAME_BYTES = 24576       # packed 12-bit samples: 3 bytes per 2 samples
 SA_FILTER_DEFAULT, SA_FILTER_CUSTOM, SA_FILTER_NONE, SA_FILTER_WIDE = 0x00, 0xA1, 0xB1, 0xA2
 SA_WIN_RTL_SIGNED, SA_WIN_HANN_U16 = 0, 1
 SA_OUT_MAG_FULL, SA_OUT_MAG_HALF, SA_OUT_SPEC_HALF, SA_OUT_TIME, SA_OUT_MARKER = 0, 1, 2, 3, 4
@@ -104,6 +105,9 @@ def lib() -> C.CDLL:
     L.sa_filter_q15.argtypes = [H, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
     L.sa_process_f32.argtypes = [H, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
     L.sa_process_f32_i16.argtypes = [H, C.c_void_p, C.c_float, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    L.sa_process_f32_p12.argtypes = [H, C.c_void_p, C.c_float, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    L.sa_pack_samples_p12.argtypes = [C.POINTER(C.c_int16), C.c_size_t, C.POINTER(C.c_uint8)]
+    L.sa_unpack_samples_p12.argtypes = [C.POINTER(C.c_uint8), C.c_size_t, C.POINTER(C.c_int16)]
     L.sa_pack_frame.argtypes = [C.POINTER(C.c_int16), C.POINTER(C.c_uint8)]
     L.sa_debug_iir_plan_f32.argtypes = [H, C.POINTER(C.c_float), C.c_int]
     L.sa_iir_plan_from_sos.argtypes = [C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_float), C.c_int]
@@ -119,7 +123,8 @@ def lib() -> C.CDLL:
                  "sa_feed_command_bytes_ex", "sa_get_transport",
                  "sa_load_sos_f32", "sa_load_sos_f64", "sa_load_sos_q14", "sa_set_window_q15",
                  "sa_set_window_f32", "sa_set_window_mode_q15", "sa_get_window_q15", "sa_process_q15", "sa_process_q15_out",
-                 "sa_filter_q15", "sa_process_f32", "sa_process_f32_i16", "sa_pack_frame", "sa_debug_iir_plan_f32",
+                 "sa_filter_q15", "sa_process_f32", "sa_process_f32_i16", "sa_process_f32_p12", "sa_pack_samples_p12",
+                 "sa_unpack_samples_p12", "sa_pack_frame", "sa_debug_iir_plan_f32",
                  "sa_iir_plan_from_sos", "sa_set_precision", "sa_get_precision", "sa_debug_iir_plan_f64",
                  "sa_iir_plan_from_sos_f64", "sa_set_marker_range", "sa_get_marker_range"):
         getattr(L, name).restype = C.c_int

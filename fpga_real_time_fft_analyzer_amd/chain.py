@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from . import abi
-from .abi import (SA_FILTER_CUSTOM, SA_FILTER_DEFAULT, SA_FILTER_NONE, SA_FILTER_WIDE, SA_N,
+from .abi import (SA_FILTER_CUSTOM, SA_FILTER_DEFAULT, SA_FILTER_NONE, SA_FILTER_WIDE, SA_N, SA_P12_FRAME_BYTES,
                   SA_OUT_MAG_FULL, SA_OUT_MAG_HALF, SA_OUT_MARKER, SA_OUT_SPEC_HALF, SA_OUT_TIME, SA_PRECISION_F32,
                   SA_PRECISION_F64_STATE, SA_Q15_OUT_IQ, SA_Q15_OUT_MAG, SA_Q15_OUT_MARKER, SpecanError)
 
@@ -118,8 +118,9 @@ class SpectrumChain:
             raise SpecanError(abi.SA_EINVAL, f"input must be a {dtype} tensor")
         if x.device != self.device:
             raise SpecanError(abi.SA_EINVAL, f"input must live on {self.device}")
-        if x.dim() != 2 or x.shape[1] != SA_N or not x.is_contiguous():
-            raise SpecanError(abi.SA_ESHAPE, "input must be a contiguous [B, 16384] tensor")
+        row = SA_P12_FRAME_BYTES if dtype == torch.uint8 else SA_N         # uint8: packed 12-bit samples
+        if x.dim() != 2 or x.shape[1] != row or not x.is_contiguous():
+            raise SpecanError(abi.SA_ESHAPE, f"input must be a contiguous [B, {row}] tensor")
         return x.shape[0]
 
     # ------------------------------------------------------------------ control plane
@@ -317,11 +318,17 @@ class SpectrumChain:
 
         An int16 tensor (the ADC's samples, what the ingest front-end delivers) takes the same float path through
         sa_process_f32_i16: x = float(sample) * ``scale``, rounded once, no conversion pass; ``scale`` is ignored for
-        float32 input."""
+        float32 input.
+
+        A uint8 tensor [B,24576] holds the same samples packed to 12 bits, two samples in three bytes (include/specan.h,
+        "p12"; ingest.pack12 is the host packer): it goes to sa_process_f32_p12, is unpacked in the stage-in and gives
+        the results of the int16 tensor of the same samples bit for bit, from three quarters of the input bytes.  Its
+        data pointer must be 16-byte aligned (any tensor torch allocates is, and so is every whole-frame slice of one)."""
         if out_kind not in _OUT_KINDS:
             raise SpecanError(abi.SA_EINVAL, f"out_kind must be one of {sorted(_OUT_KINDS)}")
         from_i16 = x.dtype == torch.int16
-        B = self._check_in(x, torch.int16 if from_i16 else torch.float32)
+        from_p12 = x.dtype == torch.uint8
+        B = self._check_in(x, torch.int16 if from_i16 else torch.uint8 if from_p12 else torch.float32)
         if out_kind in ("mag_full", "time"):
             shape, dt = (B, SA_N), torch.float32
         elif out_kind == "mag_half":
@@ -334,7 +341,10 @@ class SpectrumChain:
             out = torch.empty(shape, dtype=dt, device=self.device)
         elif tuple(out.shape) != shape or out.dtype != dt or out.device != self.device or not out.is_contiguous():
             raise SpecanError(abi.SA_ESHAPE, f"out must be a contiguous {dt} tensor of shape {shape}")
-        if from_i16:
+        if from_p12:
+            self._check(self._lib.sa_process_f32_p12(self._h, x.data_ptr(), float(scale), out.data_ptr(), B,
+                                                     _OUT_KINDS[out_kind], self._stream()))
+        elif from_i16:
             self._check(self._lib.sa_process_f32_i16(self._h, x.data_ptr(), float(scale), out.data_ptr(), B,
                                                      _OUT_KINDS[out_kind], self._stream()))
         else:
@@ -346,7 +356,8 @@ class SpectrumChain:
     def markers(self, x: torch.Tensor, out: Optional[torch.Tensor] = None, scale: float = 1.0 / 2048.0):
         """Peak search and band power over the marker range, per frame: ``(peak_mag float32 [B], peak_bin int32 [B],
         band_power float32 [B])``, views of the [B,4] int32 record tensor (``out``, allocated when None) that
-        ``process_f32(x, out, 'marker', scale)`` fills.  peak_mag is the 'mag_full' value at peak_bin, bit for bit."""
+        ``process_f32(x, out, 'marker', scale)`` fills.  peak_mag is the 'mag_full' value at peak_bin, bit for bit.
+        ``x`` is float32, int16 or packed uint8 as for :meth:`process_f32`."""
         rec = self.process_f32(x, out, out_kind="marker", scale=scale)
         f = rec.view(torch.float32)
         return f[:, 0], rec[:, 1], f[:, 2]

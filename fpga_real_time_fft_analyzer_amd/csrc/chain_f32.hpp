@@ -21,10 +21,11 @@
 //     SA_OUT_MARKER, reduced in place to one 16-byte record per frame (peak, its bin, band power).
 // The factor 1/2 of the split step is folded into the window table (exact in binary fp).
 //
-// The kernels are templates on the input type InT: float32 frames (chain_f32.hip: sa_process_f32) or int16 samples
+// The kernels are templates on the input type InT: float32 frames (chain_f32.hip: sa_process_f32), int16 samples
 // (chain_f32_i16.hip: sa_process_f32_i16 -- what the board's ADC path delivers, imp/dsp_system_top.vhd:435 -- converted
-// and scaled in the stage-in).  Everything behind the stage-in is the same code.  The two entry points live in two
-// translation units so that the two halves of the build compile side by side.
+// and scaled in the stage-in) or the same samples packed to 12 bits (chain_f32_p12.hip: sa_process_f32_p12, unpacked in
+// the stage-in).  Everything behind the stage-in is the same code.  The entry points live in one translation unit each
+// so that the parts of the build compile side by side.
 #pragma once
 #include <type_traits>
 #include "chain_f32_dev.hpp"
@@ -33,7 +34,7 @@ namespace {
 
 // The input of a kernel: `const InT *in`, and for int16 samples the scale right behind it, x = float(sample) * scale.
 // The float32 kernels take no scale (their argument layout has no slot for one): the kernels' parameter pack Scale... is
-// empty for float32 and one float for int16, and in_scale_of turns it into the scale.
+// empty for float32 and one float for int16 and packed samples, and in_scale_of turns it into the scale.
 __device__ __forceinline__ float in_scale_of() { return 1.f; }          // float32 frames: not scaled, never read
 __device__ __forceinline__ float in_scale_of(float s) { return s; }
 
@@ -144,6 +145,61 @@ __device__ __forceinline__ void stage_in_chunks(const int16_t *__restrict__ xin,
                 const int ia = (e & 1) ? (int)ua[e >> 1] >> 16 : (int)(short)(ua[e >> 1] & 0xFFFFu);
                 const int ib = (e & 1) ? (int)ub[e >> 1] >> 16 : (int)(short)(ub[e >> 1] & 0xFFFFu);
                 const v2f x = v2f{(float)ia, (float)ib} * sc;   // rounded once: the float32 sample
+                v2f w;
+                if constexpr (WINGEN) {
+                    const v2f cs = {lt->wcs[j][0], lt->wcs[j][1]};
+                    asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[0,0,0] op_sel_hi:[1,0,1]\n\t"
+                        "v_pk_fma_f32 %0, %4, %2, %0 op_sel:[0,1,0] op_sel_hi:[1,1,1]"
+                        : "=&v"(w) : "v"(Pw), "s"(cs), "v"(G0), "v"(Qw));
+                } else {
+                    w = v2f{fa[e4], fb[e4]};
+                }
+                d[j] = x * w;
+            }
+        }
+    }
+}
+
+// Packed 12-bit samples in (SaP12, chain_f32_dev.hpp): a thread's 64 samples are 96 bytes = six 16-byte units, one round
+// of the LDS-DMA brings the whole frame (24 KiB) and the thread reads its units with conflict-free ds_read_b128
+// (p12_row_swizzle).  Units 0..2 are chunk A, 3..5 chunk B; three dwords hold eight samples (p12_unpack8), so step g
+// takes dwords 3g .. 3g+2 of either chunk: samples 8g .. 8g+7, as the int16 form does.  x = float(sample) * scale is
+// rounded once: the results are those of the int16 form on the sign-extended samples, bit for bit.
+template <bool WINGEN>
+__device__ __forceinline__ void stage_in_chunks(const SaP12 *__restrict__ xin, const float in_scale,
+                                                const float4 *__restrict__ wint, const SaIirLaneTab *__restrict__ lt,
+                                                unsigned char *smem, int t, v2f (&d)[32])
+{
+    const int lane = t & 63, wave = t >> 6;
+    float4 pq = make_float4(0.f, 0.f, 0.f, 0.f);
+    float g0 = 0.f;
+    if constexpr (WINGEN) {
+        pq = *reinterpret_cast<const float4 *>(&lt->wgen[t][0]);
+        g0 = lt->wg0;
+    }
+    dma_rows(xin, smem, lane, wave);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __builtin_amdgcn_sched_barrier(0);
+    const v2f Pw = {pq.x, pq.z}, Qw = {pq.y, pq.w}, G0 = {g0, g0}, sc = {in_scale, in_scale};
+    unsigned ua[12], ub[12];                                   // the 12 dwords of chunk A and of chunk B
+    p12_read_row(smem, t, ua, ub);
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {                              // samples 8g .. 8g+7 of chunk A and of chunk B
+        int sa[8], sb[8];
+        p12_unpack8(ua[3 * g], ua[3 * g + 1], ua[3 * g + 2], sa);
+        p12_unpack8(ub[3 * g], ub[3 * g + 1], ub[3 * g + 2], sb);
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {                          // four samples of either chunk at a time
+            float4 wa = make_float4(0.f, 0.f, 0.f, 0.f), wb = wa;
+            if constexpr (!WINGEN) {                           // table window: win_t[g'][t] = window at 64 t + 4 g' .. + 3
+                wa = wint[(2 * g + u) * 256 + t];
+                wb = wint[(8 + 2 * g + u) * 256 + t];
+            }
+            const float fa[4] = {wa.x, wa.y, wa.z, wa.w}, fb[4] = {wb.x, wb.y, wb.z, wb.w};
+#pragma unroll
+            for (int e4 = 0; e4 < 4; ++e4) {
+                const int e = 4 * u + e4, j = 8 * g + e;
+                const v2f x = v2f{(float)sa[e], (float)sb[e]} * sc;   // rounded once: the float32 sample
                 v2f w;
                 if constexpr (WINGEN) {
                     const v2f cs = {lt->wcs[j][0], lt->wcs[j][1]};
@@ -517,7 +573,7 @@ __device__ __forceinline__ void chain_frame(const InT *__restrict__ in, const fl
     const int wave = t >> 6;
     const int lo = lane & 15;          // b in pass B, c in pass C
     const int kq = lane >> 4;
-    const InT *xin = in + (size_t)f * SA_NPTS;
+    const InT *xin = in + (size_t)f * kFrameElems<InT>;
     constexpr bool IIR = NSEC > 0;
     cf a[32];
 #ifdef SA_STAMPS
@@ -577,6 +633,35 @@ __device__ __forceinline__ void chain_frame(const InT *__restrict__ in, const fl
             const unsigned u0 = ldu[256 * (2 * pp) + t], u1 = ldu[256 * (2 * pp + 1) + t];
             const cf z0 = cf{(float)(int)(short)(u0 & 0xFFFFu), (float)((int)u0 >> 16)} * cf{in_scale, in_scale};
             const cf z1 = cf{(float)(int)(short)(u1 & 0xFFFFu), (float)((int)u1 >> 16)} * cf{in_scale, in_scale};
+            a[safft::brev(2 * pp, 5)] = {z0.x * w.x, z0.y * w.y};
+            a[safft::brev(2 * pp + 1, 5)] = {z1.x * w.z, z1.y * w.w};
+        }
+    } else if constexpr (std::is_same_v<InT, SaP12>) {
+        // No IIR, packed 12-bit samples: the whole frame (24 KiB) in one round of six requests per wave, natural order;
+        // z[m] = (x[2 m], x[2 m + 1]), m = 256 m1 + t, is the three bytes at byte 3 m = 768 m1 + 3 t: the two aligned
+        // dwords around them and a funnel shift by 8 * (3 t mod 4) bits (the same for every m1), then two sign-extending
+        // extracts.  The second dword of the frame's last point lies one dword behind the frame (inside the image's
+        // allocation); at that point's shift of 8 none of its bits reaches the 24 that are used.
+        static_assert(!ONE_ROUND, "the one-round form is float32 only");
+        __builtin_amdgcn_s_setprio(3);
+#pragma unroll
+        for (int i = 0; i < 6; ++i) {
+            const int n = wave * 6 + i;
+            const SaP12 *src = xin + n * 1024 + lane * 16;
+            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)src,
+                                             (__attribute__((address_space(3))) void *)(smem + n * 1024), 16, 0, SA_DMA_AUX);
+        }
+        __builtin_amdgcn_s_setprio(0);
+        __syncthreads();
+        const unsigned *ldu = reinterpret_cast<const unsigned *>(smem) + ((3 * t) >> 2);
+        const unsigned sh = 8u * ((3u * (unsigned)t) & 3u);
+#pragma unroll
+        for (int pp = 0; pp < 16; ++pp) {
+            const float4 w = winb[pp * 256 + t];
+            const unsigned u0 = __builtin_amdgcn_alignbit(ldu[192 * (2 * pp) + 1], ldu[192 * (2 * pp)], sh);
+            const unsigned u1 = __builtin_amdgcn_alignbit(ldu[192 * (2 * pp + 1) + 1], ldu[192 * (2 * pp + 1)], sh);
+            const cf z0 = cf{(float)p12_bfe(u0, 0), (float)p12_bfe(u0, 12)} * cf{in_scale, in_scale};
+            const cf z1 = cf{(float)p12_bfe(u1, 0), (float)p12_bfe(u1, 12)} * cf{in_scale, in_scale};
             a[safft::brev(2 * pp, 5)] = {z0.x * w.x, z0.y * w.y};
             a[safft::brev(2 * pp + 1, 5)] = {z1.x * w.z, z1.y * w.w};
         }
@@ -890,7 +975,7 @@ __global__ __launch_bounds__(kThreads, 2) void time_f32_kernel(const InT *__rest
     if (f >= batch) return;
     v2f d[32];
     const float4 *wint = NSEC > 0 ? reinterpret_cast<const float4 *>(lanetab->win_t) : wint_plain;
-    stage_in_chunks<false>(in + (size_t)f * SA_NPTS, in_scale_of(in_scale...), wint, lanetab, smem, t, d);
+    stage_in_chunks<false>(in + (size_t)f * kFrameElems<InT>, in_scale_of(in_scale...), wint, lanetab, smem, t, d);
     if constexpr (NSEC > 0) iir_cascade<NSEC, UNIT>(d, ka, lanetab, scr, t);
     // Stage-out through the row image (chain_f32_dev.hpp): round h writes the thread's chunk h into its row, then
     // store_rows.  Stored straight from the registers it measured 5x slower than the whole spectrum chain.
@@ -971,7 +1056,8 @@ hipError_t launch_nsec(void *out, int batch, int out_kind, const SaF32Tables &tb
     }
 }
 
-// The launcher behind sa_launch_chain_f32 (chain_f32.hip) and sa_launch_chain_f32_i16 (chain_f32_i16.hip).
+// The launcher behind sa_launch_chain_f32 (chain_f32.hip), sa_launch_chain_f32_i16 (chain_f32_i16.hip) and
+// sa_launch_chain_f32_p12 (chain_f32_p12.hip).
 // tb.iir->nsec is the PADDED section count (0, 2, 4 or 6; see build_plan in iir_plan.cpp).
 template <typename InT, typename... Scale>
 hipError_t launch_chain(void *out, int batch, int out_kind, const SaF32Tables &tb, hipStream_t stream, SaLaunchEv ev,

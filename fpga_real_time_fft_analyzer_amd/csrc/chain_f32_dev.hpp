@@ -113,6 +113,84 @@ __device__ __forceinline__ void dma_rows(const int16_t *x, unsigned char *smem, 
     dma_rows_impl(x, 0, smem, lane, wave);
 }
 
+// Packed 12-bit samples ("p12", include/specan.h: sample n in bits [12n, 12n+12) of the frame read as a little-endian
+// bit stream, 24576 bytes per frame).  A tag type over the bytes, so that no overload collides with a plain byte pointer.
+struct SaP12 {
+    uint8_t b;
+};
+// elements of InT from one frame to the next
+template <typename InT> constexpr int kFrameElems = SA_NPTS;
+template <> constexpr int kFrameElems<SaP12> = SA_P12_FRAME_BYTES;
+
+// The p12 row image.  A thread's 64 samples are 96 bytes: row r is the six 16-byte units 6r .. 6r+5 of the frame, and
+// wave w's 64 rows are exactly six 1 KiB slabs, so ONE round of 6 requests per wave brings the frame and the rows stay
+// wave-private.  At the natural place (unit u in slot u) a ds_read_b128 of column g by every thread is 2-way
+// conflicted: the 16-byte slot inside the 256-byte bank row is (6r + g) mod 16, which has the parity of g and repeats
+// with r + 8, and each of the instruction's four 16-lane groups ({0-3, 12-15, 20-27}, ...) holds every r mod 8 twice,
+// once with bit 3 of r clear and once with it set.  So the rows with bit 3 set swap the two units of each 32-byte pair:
+// unit u sits in slot u ^ ((r >> 3) & 1), r = u / 6 (6r is even, so a pair never leaves its row).  The rows with the bit
+// clear then cover the eight slots of g's parity and the others the eight of the opposite parity: 16 lanes, 16 slots,
+// conflict-free.  The swap is applied to the per-lane SOURCE address (the slab lands linearly in LDS); a request still
+// reads 1 KiB contiguous.
+__device__ __forceinline__ int p12_row_swizzle(int r) { return (r >> 3) & 1; }
+
+__device__ __forceinline__ void dma_rows(const SaP12 *x, unsigned char *smem, int lane, int wave)
+{
+    __builtin_amdgcn_s_setprio(3);
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+        const int n = wave * 6 + i;                            // slab: slots 64n .. 64n+63
+        const int s = 64 * n + lane;                           // the slot this lane fills, of row s / 6
+        const int u = s ^ p12_row_swizzle(s / 6);
+        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(x + 16 * u),
+                                         (__attribute__((address_space(3))) void *)(smem + n * 1024), 16, 0, SA_DMA_AUX);
+    }
+    __builtin_amdgcn_s_setprio(0);
+}
+
+// The six units of row t (chunk A: 12 dwords, chunk B: 12 dwords) as six ds_read_b128 and their wait, written out as one
+// statement: left to the compiler the reads of some instantiations come out as ds_read2_b64 / ds_read2_b32 pieces, which
+// bank differently (modulo 32 dwords) and are not conflict-free in this image.  Unit c sits in slot 6t + (c ^ swizzle):
+// the even units are read from one base address and the odd ones from another, both with immediate offsets.
+typedef unsigned u4v __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ void p12_read_row(const unsigned char *smem, int t, unsigned (&ua)[12], unsigned (&ub)[12])
+{
+    const unsigned sw = (unsigned)p12_row_swizzle(t);
+    const unsigned row = (unsigned)(size_t)(const __attribute__((address_space(3))) unsigned char *)(smem) + 96u * (unsigned)t;
+    const unsigned ae = row + 16u * sw, ao = row + 16u * (sw ^ 1u);          // units 0, 2, 4 and 1, 3, 5 at +0, +32, +64
+    u4v q[6];
+    asm volatile("ds_read_b128 %0, %6\n\t"
+                 "ds_read_b128 %1, %7\n\t"
+                 "ds_read_b128 %2, %6 offset:32\n\t"
+                 "ds_read_b128 %3, %7 offset:32\n\t"
+                 "ds_read_b128 %4, %6 offset:64\n\t"
+                 "ds_read_b128 %5, %7 offset:64\n\t"
+                 "s_waitcnt lgkmcnt(0)"
+                 : "=&v"(q[0]), "=&v"(q[1]), "=&v"(q[2]), "=&v"(q[3]), "=&v"(q[4]), "=&v"(q[5])
+                 : "v"(ae), "v"(ao)
+                 : "memory");
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        ua[4 * c] = q[c].x; ua[4 * c + 1] = q[c].y; ua[4 * c + 2] = q[c].z; ua[4 * c + 3] = q[c].w;
+        ub[4 * c] = q[3 + c].x; ub[4 * c + 1] = q[3 + c].y; ub[4 * c + 2] = q[3 + c].z; ub[4 * c + 3] = q[3 + c].w;
+    }
+}
+
+// Eight samples from three dwords (96 bits): sign-extending bit-field extracts; samples 2 and 5 straddle a dword and
+// come out of a funnel shift (v_alignbit_b32) first.
+__device__ __forceinline__ int p12_bfe(unsigned w, int pos) { return (int)(w << (20 - pos)) >> 20; }
+__device__ __forceinline__ void p12_unpack8(unsigned w0, unsigned w1, unsigned w2, int (&s)[8])
+{
+    s[0] = p12_bfe(w0, 0);
+    s[1] = p12_bfe(w0, 12);
+    s[2] = p12_bfe(__builtin_amdgcn_alignbit(w1, w0, 24), 0);
+    s[3] = p12_bfe(w1, 4);
+    s[4] = p12_bfe(w1, 16);
+    s[5] = p12_bfe(__builtin_amdgcn_alignbit(w2, w1, 28), 0);
+    s[6] = p12_bfe(w2, 8);
+    s[7] = (int)w2 >> 20;
+}
+
 // Stage-out, round h, the stage-in run backwards: row r (32 float32 samples) -> o[64r + 32h ..].
 // Every wave instruction picks up 1 KiB of LDS in linear order and stores it with 16 bytes per lane: stored straight
 // from the registers, every lane of a store instruction would land in another 256-byte block.

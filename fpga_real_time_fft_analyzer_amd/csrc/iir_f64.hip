@@ -112,6 +112,37 @@ __device__ __forceinline__ void stage_in(const int16_t *__restrict__ xin, const 
     }
 }
 
+// packed 12-bit samples (SaP12, chain_f32_dev.hpp): a thread's 64 samples are six 16-byte units of its 96-byte row, brought
+// in one round; three dwords hold eight samples (p12_unpack8).  The same single float32 rounding of x as the int16 form, so
+// this entry point and the int16 one on the sign-extended samples agree bit for bit.
+__device__ __forceinline__ void stage_in(const SaP12 *__restrict__ xin, const float in_scale, const double2 *__restrict__ wt,
+                                         unsigned char *smem, int t, double (&d)[2][32])
+{
+    const int lane = t & 63, wave = t >> 6;
+    dma_rows(xin, smem, lane, wave);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __builtin_amdgcn_sched_barrier(0);
+    unsigned uab[2][12];                                       // units 3h .. 3h+2 of the row: chunk h
+    p12_read_row(smem, t, uab[0], uab[1]);
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const unsigned(&u)[12] = uab[h];
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {                          // samples 8g .. 8g+7 of the chunk
+            int s[8];
+            p12_unpack8(u[3 * g], u[3 * g + 1], u[3 * g + 2], s);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const int j = 8 * g + e;
+                float x;
+                asm("v_mul_f32 %0, %1, %2" : "=v"(x) : "v"((float)s[e]), "v"(in_scale));     // one float32 rounding, never fused
+                const double2 w = wt[(16 * h + (j >> 1)) * 256 + t];
+                d[h][j] = (double)x * ((j & 1) ? w.y : w.x);
+            }
+        }
+    }
+}
+
 // Chunk end state from zero state: z = A^16 (sum_{j<16} m[j] v[j]) + sum_{j<16} m[j] v[16 + j]
 __device__ __forceinline__ d2 predict(const SaIirSecF64 &k, const double (&v)[32])
 {
@@ -181,7 +212,7 @@ __global__ __launch_bounds__(kThreads, 2) void iir_f64_kernel(const InT *__restr
     if (f >= batch) return;
     const int lane = t & 63, wave = t >> 6;
     double d[2][32];
-    stage_in(in + (size_t)f * SA_NPTS, in_scale, wt, smem, t, d);
+    stage_in(in + (size_t)f * kFrameElems<InT>, in_scale, wt, smem, t, d);
     double2 *scr = reinterpret_cast<double2 *>(smem + kScrOff);
 #pragma unroll
     for (int s = 0; s < NSEC; ++s) {
@@ -231,10 +262,14 @@ hipError_t launch_in(const InT *in, float in_scale, float *out, int batch, int n
 
 }  // namespace
 
-hipError_t sa_launch_iir_f64(const void *in, bool in_i16, float in_scale, float *out, int batch, int nsec,
+hipError_t sa_launch_iir_f64(const void *in, SaInKind in_kind, float in_scale, float *out, int batch, int nsec,
                              const SaIirF64 *plan, const double *win_tr, hipStream_t stream, SaLaunchEv ev)
 {
     if (batch <= 0) return hipSuccess;
-    if (in_i16) return launch_in(static_cast<const int16_t *>(in), in_scale, out, batch, nsec, plan, win_tr, stream, ev);
-    return launch_in(static_cast<const float *>(in), 1.f, out, batch, nsec, plan, win_tr, stream, ev);
+    switch (in_kind) {
+        case SaInKind::I16: return launch_in(static_cast<const int16_t *>(in), in_scale, out, batch, nsec, plan, win_tr, stream, ev);
+        case SaInKind::P12: return launch_in(static_cast<const SaP12 *>(in), in_scale, out, batch, nsec, plan, win_tr, stream, ev);
+        case SaInKind::F32: return launch_in(static_cast<const float *>(in), 1.f, out, batch, nsec, plan, win_tr, stream, ev);
+    }
+    return hipErrorInvalidValue;
 }

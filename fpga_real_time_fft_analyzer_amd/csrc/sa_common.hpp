@@ -115,7 +115,7 @@ struct SaQ15Params {
 // operation: doing it on every launch costs host time and cannot be captured into a hipGraph.
 hipError_t sa_set_dyn_lds_once(const void *kernel, int bytes);
 
-// launchers (defined in chain_f32.hip, chain_f32_i16.hip, cascade_q15.hip and fft_q15.hip)
+// launchers (defined in chain_f32.hip, chain_f32_i16.hip, chain_f32_p12.hip, iir_f64.hip, cascade_q15.hip and fft_q15.hip)
 struct SaF32Tables {               // the windows and twiddles are filled by sa_tables.hpp / sa_tables.cpp
     const float4 *win_b;       // [16][256] 0.5 * window in the pass-A layout of the no-IIR kernel:
                                //   win_b[p][t] = w[512(2p)+2t], w[..+1], w[512(2p+1)+2t], w[..+1]
@@ -144,11 +144,19 @@ hipError_t sa_launch_chain_f32(const float *in, void *out, int batch, int out_ki
 hipError_t sa_launch_chain_f32_i16(const int16_t *in, float in_scale, void *out, int batch, int out_kind, const SaF32Tables &t,
                                    hipStream_t stream, SaLaunchEv ev);
 
+// the same chain on packed 12-bit samples (chain_f32_p12.hip; include/specan.h, SA_P12_FRAME_BYTES per frame, 16-byte
+// aligned): unpacked in the stage-in, then as the int16 form on the sign-extended samples
+hipError_t sa_launch_chain_f32_p12(const uint8_t *in, float in_scale, void *out, int batch, int out_kind, const SaF32Tables &t,
+                                   hipStream_t stream, SaLaunchEv ev);
+
+// what a float-path call's `in` points to: float32 frames, int16 samples or packed 12-bit samples
+enum class SaInKind { F32, I16, P12 };
+
 // Float64-state cascade (iir_f64.hip): window and cascade of the frame in double, y rounded once to float32 into
-// out [B,16384] (the workspace of the FFT launch, or the SA_OUT_TIME output itself).  `in` is float32 frames, or int16
-// samples when in_i16 (x = float(sample) * in_scale rounded to float32 first, as on the float32 path).
+// out [B,16384] (the workspace of the FFT launch, or the SA_OUT_TIME output itself).  `in` is float32 frames, or int16 /
+// packed 12-bit samples per in_kind (x = float(sample) * in_scale rounded to float32 first, as on the float32 path).
 //   plan: device SaIirF64 whose hdr[0] == nsec;  win_tr: device [32][256][2] doubles, win_tr[g][t] = w[64t + 2g], w[..+1]
-hipError_t sa_launch_iir_f64(const void *in, bool in_i16, float in_scale, float *out, int batch, int nsec,
+hipError_t sa_launch_iir_f64(const void *in, SaInKind in_kind, float in_scale, float *out, int batch, int nsec,
                              const SaIirF64 *plan, const double *win_tr, hipStream_t stream, SaLaunchEv ev);
 
 struct SaQ15Tables {                 // rom, tw and twrec are filled by sa_tables.hpp / sa_tables.cpp

@@ -470,7 +470,8 @@ int sa_process_q15_out(sa_handle *h, const int16_t *in, void *out, int batch, in
     return process_q15(h, "sa_process_q15_out", in, out, batch, out_kind, stream, true);
 }
 
-// sa_process_f32 (float frames) and sa_process_f32_i16 (int16 samples times `scale`); `fn` names the entry point.
+// sa_process_f32 (float frames), sa_process_f32_i16 (int16 samples times `scale`) and sa_process_f32_p12 (the same
+// samples packed to 12 bits); `fn` names the entry point.
 // The float32 path: one launch of the fused chain.  The section coefficients and predictor taps travel by value in the
 // kernel arguments (stream-ordered by construction); the per-lane matrices and the window live in device memory
 // (stream-ordered uploads).
@@ -478,7 +479,7 @@ int sa_process_q15_out(sa_handle *h, const int16_t *in, void *out, int batch, in
 // iir_f64.hip (window + cascade in double, y rounded once) into the slot's workspace, then the bypassed float chain on
 // y with the constant 1/2 window (exact).  SA_OUT_TIME is the first launch alone, into `out`.  Timed as one call: the
 // start event rides on the first kernel, the stop event on the last.
-static int process_float(sa_handle *h, const char *fn, const void *in, bool i16, float scale, void *out, int batch,
+static int process_float(sa_handle *h, const char *fn, const void *in, SaInKind kind, float scale, void *out, int batch,
                          int out_kind, void *stream)
 {
     if (!h) return SA_EINVAL;
@@ -489,6 +490,8 @@ static int process_float(sa_handle *h, const char *fn, const void *in, bool i16,
     if (!in || !out) return fail_at(h, SA_EINVAL, fn, "NULL tensor");
     if (out_kind == SA_OUT_MARKER && ((uintptr_t)out & 15u) != 0)
         return fail_at(h, SA_EINVAL, fn, "SA_OUT_MARKER output must be 16-byte aligned");
+    if (kind == SaInKind::P12 && ((uintptr_t)in & 15u) != 0)       // the stage-in issues 16-byte requests
+        return fail_at(h, SA_EINVAL, fn, "packed input must be 16-byte aligned");
     if (h->filter_mode == SA_FILTER_WIDE)
         return fail_at(h, SA_ESTATE, fn, "filter mode 0xA2 (Q2.14) belongs to the Q15 path; use 0xA1 with sa_load_sos_f32");
     SA_HIP(h, hipSetDevice(h->device));
@@ -501,12 +504,14 @@ static int process_float(sa_handle *h, const char *fn, const void *in, bool i16,
     SaF32Tables t = {h->d_win_b, h->d_win_t, h->d_twT, h->d_twB, h->d_twC, pl.d_lt, cascade ? &pl.k : nullptr,
                      h->marker_lo, h->marker_hi};
     if (!f64) {
-        SA_HIP(h, i16 ? sa_launch_chain_f32_i16((const int16_t *)in, scale, out, batch, out_kind, t, c.stream, {c.start, c.stop})
-                      : sa_launch_chain_f32((const float *)in, out, batch, out_kind, t, c.stream, {c.start, c.stop}));
+        const SaLaunchEv ev = {c.start, c.stop};
+        SA_HIP(h, kind == SaInKind::I16   ? sa_launch_chain_f32_i16((const int16_t *)in, scale, out, batch, out_kind, t, c.stream, ev)
+                  : kind == SaInKind::P12 ? sa_launch_chain_f32_p12((const uint8_t *)in, scale, out, batch, out_kind, t, c.stream, ev)
+                                          : sa_launch_chain_f32((const float *)in, out, batch, out_kind, t, c.stream, ev));
         return end_call(h, c);
     }
     float *y = two ? (float *)h->slot[c.slot].work[sa_handle::kWorkF64].ptr : (float *)out;
-    SA_HIP(h, sa_launch_iir_f64(in, i16, scale, y, batch, pl.k.nsec, pl.d_p64, h->d_win64, c.stream,
+    SA_HIP(h, sa_launch_iir_f64(in, kind, scale, y, batch, pl.k.nsec, pl.d_p64, h->d_win64, c.stream,
                                 {c.start, two ? nullptr : c.stop}));
     if (two) {
         t = {h->d_win_half, h->d_win_t, h->d_twT, h->d_twB, h->d_twC, h->plan_custom.d_lt, nullptr, h->marker_lo, h->marker_hi};
@@ -517,12 +522,17 @@ static int process_float(sa_handle *h, const char *fn, const void *in, bool i16,
 
 int sa_process_f32(sa_handle *h, const float *in, void *out, int batch, int out_kind, void *stream)
 {
-    return process_float(h, "sa_process_f32", in, false, 1.f, out, batch, out_kind, stream);
+    return process_float(h, "sa_process_f32", in, SaInKind::F32, 1.f, out, batch, out_kind, stream);
 }
 
 int sa_process_f32_i16(sa_handle *h, const int16_t *in, float scale, void *out, int batch, int out_kind, void *stream)
 {
-    return process_float(h, "sa_process_f32_i16", in, true, scale, out, batch, out_kind, stream);
+    return process_float(h, "sa_process_f32_i16", in, SaInKind::I16, scale, out, batch, out_kind, stream);
+}
+
+int sa_process_f32_p12(sa_handle *h, const uint8_t *in, float scale, void *out, int batch, int out_kind, void *stream)
+{
+    return process_float(h, "sa_process_f32_p12", in, SaInKind::P12, scale, out, batch, out_kind, stream);
 }
 
 int sa_pack_frame(const int16_t *iq_host, uint8_t *frame_bytes)

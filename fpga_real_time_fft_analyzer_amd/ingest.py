@@ -17,6 +17,46 @@ import torch
 from . import frames
 
 N = frames.FFT_SIZE
+P12_FRAME_BYTES = 3 * N // 2       # SA_P12_FRAME_BYTES (include/specan.h): 24576
+
+
+def pack12(samples) -> np.ndarray:
+    """Pack 12-bit samples, two to three bytes, along the last axis (the "p12" format of include/specan.h): sample n
+    occupies bits [12n, 12n+12) of the row read as a little-endian bit stream.  ``samples``: integers in [-2048, 2047]
+    (``ValueError`` otherwise), last axis of even length n; returns uint8 with last axis 3n/2.
+
+    For tests, tools and files, not for the hot path: at 30 G samples/s no host packer keeps up.  The format pays when
+    the source (a digitiser, a capture file) delivers it."""
+    s = np.asarray(samples)
+    if s.dtype.kind not in "iu":
+        raise ValueError("samples must be integers")
+    if s.shape[-1] % 2:
+        raise ValueError("the last axis must hold an even number of samples")
+    if s.size and (s.min() < -2048 or s.max() > 2047):
+        raise ValueError("samples do not fit 12 bits")
+    u = s.astype(np.int32) & 0xFFF
+    u0, u1 = u[..., 0::2], u[..., 1::2]
+    out = np.empty(s.shape[:-1] + (s.shape[-1] // 2, 3), np.uint8)
+    out[..., 0] = u0 & 0xFF
+    out[..., 1] = (u0 >> 8) | ((u1 & 0xF) << 4)
+    out[..., 2] = u1 >> 4
+    return out.reshape(s.shape[:-1] + (3 * (s.shape[-1] // 2),))
+
+
+def unpack12(packed) -> np.ndarray:
+    """The inverse of :func:`pack12` along the last axis (a multiple of 3 bytes, ``ValueError`` otherwise): uint8 -> int16,
+    sign-extended.  Every bit pattern is valid.  For tests, tools and files, like :func:`pack12`."""
+    b = np.asarray(packed)
+    if b.dtype != np.uint8:
+        raise ValueError("packed samples must be uint8")
+    if b.shape[-1] % 3:
+        raise ValueError("the last axis must hold a multiple of 3 bytes")
+    t = b.reshape(b.shape[:-1] + (b.shape[-1] // 3, 3)).astype(np.int16)
+    out = np.empty(b.shape[:-1] + (b.shape[-1] // 3, 2), np.int16)
+    out[..., 0] = t[..., 0] | ((t[..., 1] & 0xF) << 8)
+    out[..., 1] = (t[..., 1] >> 4) | (t[..., 2] << 4)
+    out = (out ^ 0x800) - 0x800                              # sign extension of 12 bits
+    return out.reshape(b.shape[:-1] + (2 * (b.shape[-1] // 3),))
 
 
 class FrameCutter:
@@ -24,16 +64,40 @@ class FrameCutter:
 
     ``hop`` < 16384 gives overlapping frames (hop = 16384 reproduces the FPGA: back-to-back
     acquisitions, no overlap).  Samples are kept as delivered (the XADC delivers 12-bit values
-    sign-extended to int16, imp/dsp_system_top.vhd:435)."""
+    sign-extended to int16, imp/dsp_system_top.vhd:435).
 
-    def __init__(self, hop: int = N):
+    ``packed=True``: the stream is the packed 12-bit byte stream (:func:`pack12`), pushed in chunks of any length
+    (a chunk may end inside a pair of samples), and the frames come out packed, [k, 24576] uint8.  ``hop`` must then
+    be even, so that every frame starts on a whole byte."""
+
+    def __init__(self, hop: int = N, packed: bool = False):
         if not 0 < hop <= N:
             raise ValueError("hop must be in 1..16384")
+        if packed and hop % 2:
+            raise ValueError("hop must be even for a packed stream (frames start on whole bytes)")
         self.hop = hop
-        self._buf = np.empty(0, np.int16)
+        self.packed = bool(packed)
+        self._buf = np.empty(0, np.uint8 if packed else np.int16)
+
+    def _push_packed(self, data) -> np.ndarray:
+        b = np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.asarray(data)
+        if b.dtype != np.uint8:
+            raise ValueError("a packed stream is pushed as uint8 / bytes")
+        self._buf = np.concatenate([self._buf, b.reshape(-1)])
+        n, hop = self._buf.size, 3 * self.hop // 2           # in bytes
+        if n < P12_FRAME_BYTES:
+            return np.empty((0, P12_FRAME_BYTES), np.uint8)
+        k = (n - P12_FRAME_BYTES) // hop + 1
+        idx = np.arange(k)[:, None] * hop + np.arange(P12_FRAME_BYTES)[None, :]
+        out = self._buf[idx]
+        self._buf = self._buf[k * hop:]
+        return out
 
     def push(self, samples) -> np.ndarray:
-        """Append samples; return the frames that became complete, shape [k, 16384] (k may be 0)."""
+        """Append samples; return the frames that became complete, shape [k, 16384] (k may be 0).
+        Packed: append bytes of the packed stream; the frames are [k, 24576] uint8."""
+        if self.packed:
+            return self._push_packed(samples)
         s = np.asarray(samples)
         if s.dtype != np.int16:
             if np.any(s < -32768) or np.any(s > 32767):
@@ -51,27 +115,36 @@ class FrameCutter:
 
     @property
     def pending(self) -> int:
+        """Samples (packed: bytes) waiting for the rest of their frame."""
         return int(self._buf.size)
 
 
 class DeviceFeeder:
     """Double-buffered host -> device mover: ``feed(batch_iter)`` yields device tensors [B,16384] int16
-    while the next batch is already in flight on a side stream.
+    (``packed``: [B,24576] uint8) while the next batch is already in flight on a side stream.
 
     Two pinned staging buffers, two device buffers, and FOUR events created once (a "copied" and a
     "consumed" event per slot).  Measured (profiles/r2_ingest.txt): 1.42 M frames/s = 46.5 GB/s end to end
     against 55 GB/s for the bare pinned copy, i.e. PCIe-bound, with the copy of batch k+1 under the kernels of
     batch k.  The staging copy numpy -> pinned runs on torch's intra-op thread pool: on a host that exposes
     more cores than the job may use (a 16-CPU share of a 256-core box) the default pool stalls it for 50-100 ms
-    every dozen batches -- pass ``host_threads`` (or call torch.set_num_threads yourself)."""
+    every dozen batches -- pass ``host_threads`` (or call torch.set_num_threads yourself).
 
-    def __init__(self, device: torch.device | int = 0, max_batch: int = 256, host_threads: Optional[int] = None):
+    ``packed=True``: the batches are packed 12-bit frames, [B,24576] uint8 (what a packed :class:`FrameCutter` cuts), and
+    so are the staging and device buffers and the tensors handed out: three quarters of the bytes per frame on the link.
+    ``SpectrumChain.process_f32`` takes them as they are."""
+
+    def __init__(self, device: torch.device | int = 0, max_batch: int = 256, host_threads: Optional[int] = None,
+                 packed: bool = False):
         if host_threads is not None:
             torch.set_num_threads(int(host_threads))
         self.device = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
         self.max_batch = max_batch
-        self._pinned = [torch.empty((max_batch, N), dtype=torch.int16).pin_memory() for _ in range(2)]
-        self._dev = [torch.empty((max_batch, N), dtype=torch.int16, device=self.device) for _ in range(2)]
+        self.packed = bool(packed)
+        self._row, self._np_dtype = (P12_FRAME_BYTES, np.uint8) if packed else (N, np.int16)
+        dt = torch.uint8 if packed else torch.int16
+        self._pinned = [torch.empty((max_batch, self._row), dtype=dt).pin_memory() for _ in range(2)]
+        self._dev = [torch.empty((max_batch, self._row), dtype=dt, device=self.device) for _ in range(2)]
         self._copy_stream = torch.cuda.Stream(self.device)
         self._copied = [torch.cuda.Event() for _ in range(2)]      # slot's host->device copy has run
         self._consumed = [torch.cuda.Event() for _ in range(2)]    # slot's consumer work has been enqueued and run
@@ -81,7 +154,7 @@ class DeviceFeeder:
         cur = torch.cuda.current_stream(self.device)
         pend = None                                             # (slot, n_frames) handed out next
         for i, b in enumerate(batches):
-            b = np.ascontiguousarray(b, np.int16).reshape(-1, N)
+            b = np.ascontiguousarray(b, self._np_dtype).reshape(-1, self._row)
             n = b.shape[0]
             if n > self.max_batch:
                 raise ValueError("batch larger than max_batch")

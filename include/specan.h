@@ -304,6 +304,33 @@ int sa_process_f32(sa_handle *h, const float *in, void *out, int batch, int out_
  * without the conversion pass and with half the input bytes (32 KiB per frame, one fetch round instead of two). */
 int sa_process_f32_i16(sa_handle *h, const int16_t *in, float scale, void *out, int batch, int out_kind, void *stream);
 
+/* The float path fed with packed 12-bit samples ("p12", build extension; ABI version 4, added compatibly).  The ADC's
+ * samples are 12 bits wide -- imp/dsp_system_top.vhd:435 sign-extends adc_out(15 downto 4) -- so in int16 a quarter of
+ * every byte on the link is sign extension; digitisers and capture files commonly pack two samples into three bytes.
+ * The format:
+ *   - a frame is SA_P12_FRAME_BYTES = 24576 bytes, a batch a contiguous [B,24576] uint8 array;
+ *   - sample n of a frame (s_n in [-2048, 2047], u_n = s_n & 0xFFF) occupies bits [12n, 12n+12) of the frame read as a
+ *     little-endian bit stream; for each pair i
+ *         b[3i]   = u_{2i} & 0xFF
+ *         b[3i+1] = (u_{2i} >> 8) | ((u_{2i+1} & 0xF) << 4)
+ *         b[3i+2] = u_{2i+1} >> 4
+ *   - known answers: samples [0x123, 0x456] pack to bytes 23 61 45; samples [-1, -2048] to bytes FF 0F 80;
+ *   - every bit pattern is a valid frame.
+ * x = (float)s_n * scale is rounded once in the stage-in and then takes exactly the float32 path: the results are those
+ * of sa_process_f32_i16() on the sign-extended samples, bit for bit, for every output kind, filter mode and precision,
+ * with no unpack pass, no workspace and no extra launch (24 KiB of input per frame instead of 32).  Everything said of
+ * sa_process_f32_i16 holds, and one more argument check: `in` must be 16-byte aligned (SA_EINVAL otherwise, nothing is
+ * launched; the stage-in issues 16-byte requests, and the frame stride of 24576 keeps every frame aligned). */
+#define SA_P12_FRAME_BYTES 24576
+int sa_process_f32_p12(sa_handle *h, const uint8_t *in /* [B,24576] device */, float scale, void *out, int batch,
+                       int out_kind, void *stream);
+
+/* Host helpers of the p12 format: pure functions, no handle, no GPU.  n is the number of SAMPLES and must be even
+ * (SA_EINVAL otherwise); `packed` holds 3n/2 bytes.  Packing a sample outside [-2048, 2047] is SA_EINVAL and nothing
+ * is written.  Unpacking sign-extends to int16. */
+int sa_pack_samples_p12(const int16_t *samples, size_t n, uint8_t *packed /* 3n/2 bytes */);
+int sa_unpack_samples_p12(const uint8_t *packed, size_t n, int16_t *samples);
+
 /* Host helper: view of one frame as the byte stream sequ2 emits.  On little-endian hosts the
  * Q15 output already is that stream; this copies 65536 bytes and is provided for symmetry with
  * gui.py:250-260 (decode side). */
@@ -319,7 +346,7 @@ int sa_debug_iir_plan_f32(const sa_handle *h, float *out, int cap);
 int sa_iir_plan_from_sos(const double *sos, int n_sections, float *out, int cap);
 
 /* ---- float64-state IIR (opt-in; build extension) --------------------------------------------------------------------
- * sa_set_precision(h, SA_PRECISION_F64_STATE): sa_process_f32 and sa_process_f32_i16 in filter modes DEFAULT and CUSTOM
+ * sa_set_precision(h, SA_PRECISION_F64_STATE): sa_process_f32, _i16 and _p12 in filter modes DEFAULT and CUSTOM
  * evaluate the window (x * w in double, w = the default Hann of scripts/hann_coeff.py:3-4 in double, or the table of
  * sa_set_window_f32 widened exactly), the signal between sections and the DF2T recursion of scipy.signal.sosfilt in
  * float64, and round only the cascade output y to float32.  The FFT of y is the float32 one (its own error on a float32

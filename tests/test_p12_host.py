@@ -1,0 +1,155 @@
+"""CPU: the packed 12-bit sample format ("p12", include/specan.h) on the host: ingest.pack12 / unpack12 (numpy), the C
+helpers sa_pack_samples_p12 / sa_unpack_samples_p12 (csrc/sa_p12.cpp, no GPU), the packed FrameCutter, and the
+stand-alone program tests/cpp/test_sa_p12.cpp that runs the C helpers under the host sanitizers."""
+import ctypes as C
+import os
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+from conftest import N, ROOT
+
+from fpga_real_time_fft_analyzer_amd.ingest import FrameCutter, P12_FRAME_BYTES, pack12, unpack12
+
+SA_OK, SA_EINVAL = 0, -1
+
+
+def c_pack(lib, samples, n=None, out=None):
+    s = np.ascontiguousarray(samples, np.int16)
+    n = s.size if n is None else n
+    if out is None:
+        out = np.zeros(3 * n // 2, np.uint8)
+    rc = lib.sa_pack_samples_p12(s.ctypes.data_as(C.POINTER(C.c_int16)), n, out.ctypes.data_as(C.POINTER(C.c_uint8)))
+    return rc, out
+
+
+def c_unpack(lib, packed, n):
+    p = np.ascontiguousarray(packed, np.uint8)
+    out = np.zeros(n, np.int16)
+    rc = lib.sa_unpack_samples_p12(p.ctypes.data_as(C.POINTER(C.c_uint8)), n, out.ctypes.data_as(C.POINTER(C.c_int16)))
+    return rc, out
+
+
+def bitstream_samples(packed):
+    """The format's definition evaluated directly: sample n = bits [12n, 12n+12) of the little-endian bit stream."""
+    bits = np.unpackbits(np.ascontiguousarray(packed, np.uint8), axis=-1, bitorder="little")
+    f = bits.reshape(bits.shape[:-1] + (bits.shape[-1] // 12, 12)).astype(np.int32)
+    u = (f << np.arange(12)).sum(axis=-1)
+    return ((u ^ 0x800) - 0x800).astype(np.int16)
+
+
+def cases():
+    rng = np.random.default_rng(12)
+    n = np.arange(4096)
+    return {"random": rng.integers(-2048, 2048, 4096).astype(np.int16),
+            "extremes": np.where(n & 1, 2047, -2048).astype(np.int16),
+            "ramp": ((37 * n) % 4096 - 2048).astype(np.int16)}
+
+
+def test_known_answers(hip_lib_built):
+    for samples, want in (([0x123, 0x456], "236145"), ([-1, -2048], "ff0f80")):
+        assert pack12(np.array(samples)).tobytes().hex() == want
+        rc, out = c_pack(hip_lib_built, samples)
+        assert rc == SA_OK and out.tobytes().hex() == want
+
+
+@pytest.mark.parametrize("name", ["random", "extremes", "ramp"])
+def test_c_and_numpy_packers_agree_and_round_trip(hip_lib_built, name):
+    x = cases()[name]
+    p = pack12(x)
+    rc, pc = c_pack(hip_lib_built, x)
+    assert rc == SA_OK and p.dtype == np.uint8 and p.shape == (6144,) and np.array_equal(p, pc)
+    assert np.array_equal(bitstream_samples(p), x)
+    u = unpack12(p)
+    rc, uc = c_unpack(hip_lib_built, p, x.size)
+    assert rc == SA_OK and u.dtype == np.int16 and np.array_equal(u, x) and np.array_equal(uc, x)
+
+
+def test_last_axis_and_batches():
+    x = np.random.default_rng(3).integers(-2048, 2048, (3, 2, 64)).astype(np.int16)
+    p = pack12(x)
+    assert p.shape == (3, 2, 96)
+    for i in range(3):
+        for j in range(2):
+            assert np.array_equal(p[i, j], pack12(x[i, j]))
+    assert np.array_equal(unpack12(p), x)
+    assert P12_FRAME_BYTES == 24576 and pack12(np.zeros((2, N), np.int16)).shape == (2, P12_FRAME_BYTES)
+
+
+def test_every_three_byte_pattern_unpacks_as_the_bit_stream(hip_lib_built):
+    v = np.arange(1 << 24, dtype=np.uint32)
+    p = np.stack([v & 0xFF, (v >> 8) & 0xFF, v >> 16], axis=1).astype(np.uint8)          # [2^24, 3]
+    want = np.stack([(v & 0xFFF), (v >> 12)], axis=1).astype(np.int32)                   # the two 12-bit fields
+    want = ((want ^ 0x800) - 0x800).astype(np.int16)
+    assert np.array_equal(bitstream_samples(p[:4096]), want[:4096])                      # the shortcut above is the definition
+    assert np.array_equal(bitstream_samples(p[-4096:]), want[-4096:])
+    assert np.array_equal(unpack12(p), want)
+    rc, uc = c_unpack(hip_lib_built, p.reshape(-1), 2 << 24)
+    assert rc == SA_OK and np.array_equal(uc.reshape(-1, 2), want)
+    assert np.array_equal(pack12(want), p)                                               # and every pattern is a packing
+
+
+def test_errors(hip_lib_built):
+    with pytest.raises(ValueError):
+        pack12(np.zeros(7, np.int16))
+    for bad in (2048, -2049):
+        x = np.zeros(8, np.int16)
+        x[5] = bad
+        with pytest.raises(ValueError):
+            pack12(x)
+        sentinel = np.full(12, 0xEE, np.uint8)
+        rc, out = c_pack(hip_lib_built, x, out=sentinel)
+        assert rc == SA_EINVAL and (out == 0xEE).all()                                   # checked before anything is written
+    sentinel = np.full(12, 0xEE, np.uint8)
+    rc, out = c_pack(hip_lib_built, np.zeros(8, np.int16), n=7, out=sentinel)
+    assert rc == SA_EINVAL and (out == 0xEE).all()
+    rc, _ = c_unpack(hip_lib_built, np.zeros(12, np.uint8), 7)
+    assert rc == SA_EINVAL
+    with pytest.raises(ValueError):
+        unpack12(np.zeros(7, np.uint8))
+    with pytest.raises(ValueError):
+        unpack12(np.zeros(6, np.int16))
+    with pytest.raises(ValueError):
+        FrameCutter(3, packed=True)
+    FrameCutter(3)                                                                       # unpacked streams keep odd hops
+
+
+@pytest.mark.parametrize("hop", [16384, 8192, 2])
+def test_packed_frame_cutter(hop):
+    """Any chunking of the packed byte stream, chunks that split a pair included, gives pack12 of the frames that the
+    unpacked cutter cuts from the unpacked stream."""
+    rng = np.random.default_rng(hop)
+    n = 2 * N + 1000 if hop > 2 else N + 40                  # 2 / 3 / 21 frames and a remainder
+    s = rng.integers(-2048, 2048, n).astype(np.int16)
+    want = pack12(FrameCutter(hop).push(s))
+    assert want.shape[0] == {16384: 2, 8192: 3, 2: 21}[hop]
+    stream = pack12(s)
+    for chunk in (1, 2, 3, 7, 4099):
+        fc = FrameCutter(hop, packed=True)
+        got = [fc.push(stream[i:i + chunk]) for i in range(0, stream.size, chunk)]
+        assert all(g.dtype == np.uint8 and g.shape[1:] == (P12_FRAME_BYTES,) for g in got)
+        assert np.array_equal(np.concatenate(got), want), chunk
+        assert fc.pending == stream.size - want.shape[0] * (3 * hop // 2)
+    fc = FrameCutter(hop, packed=True)
+    assert np.array_equal(fc.push(stream.tobytes()), want)   # bytes are taken too
+
+
+def test_standalone_program_under_host_sanitizers(tmp_path):
+    """tests/cpp/test_sa_p12.cpp + csrc/sa_p12.cpp, host only, with -fsanitize=address,undefined when that links here
+    (a plain build otherwise: the program's own checks still run)."""
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    exe = str(tmp_path / "test_sa_p12")
+    srcs = [os.path.join(ROOT, "tests", "cpp", "test_sa_p12.cpp"),
+            os.path.join(ROOT, "fpga_real_time_fft_analyzer_amd", "csrc", "sa_p12.cpp")]
+    base = [hipcc, "-O1", "-g", "-std=c++17", "--offload-host-only", "-x", "hip", *srcs, "-o", exe]
+    r = subprocess.run(base + ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"],
+                       capture_output=True, text=True, timeout=300)
+    sanitized = r.returncode == 0
+    if not sanitized:
+        r = subprocess.run(base, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr
+    print("sanitizers:", "address,undefined" if sanitized else "did not link here: plain build")
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and r.stdout.startswith("ok "), r.stdout + r.stderr

@@ -8,7 +8,9 @@ memory).  With --events it also prints, per batch, the copy and kernel intervals
 their own streams, which shows the copy of batch k+1 running under the kernels of batch k.
 --float: the same int16 batches into the FLOAT chain (sa_process_f32_i16, mode 0xA1 with the headline cascade): no
 conversion pass on the device, the PCIe volume of the Q15 path.
-usage: ingest_bench.py [batch_frames] [n_batches] [mode] [--events] [--float]"""
+--packed (implies --float): the same samples packed to 12 bits (sa_process_f32_p12, 24576 bytes per frame instead of
+32768), packed once up front as the int16 batches are generated up front; the GB/s figures count the packed bytes.
+usage: ingest_bench.py [batch_frames] [n_batches] [mode] [--events] [--float] [--packed]"""
 import os
 import sys
 import time
@@ -19,7 +21,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from fpga_real_time_fft_analyzer_amd.chain import SpectrumChain  # noqa: E402
-from fpga_real_time_fft_analyzer_amd.ingest import DeviceFeeder  # noqa: E402
+from fpga_real_time_fft_analyzer_amd.ingest import DeviceFeeder, pack12  # noqa: E402
 
 # the box gives this job 16 CPUs of a 256-core host: torch's default intra-op pool (one thread per visible core)
 # stalls the staging copy for 50-100 ms every dozen batches
@@ -28,7 +30,10 @@ N = 16384
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 1024
 NB = int(sys.argv[2]) if len(sys.argv) > 2 else 32
 mode = int(sys.argv[3], 0) if len(sys.argv) > 3 and not sys.argv[3].startswith("--") else 0xB1
-FLOAT = "--float" in sys.argv
+PACKED = "--packed" in sys.argv
+FLOAT = "--float" in sys.argv or PACKED
+ROW, FRAME_BYTES = (3 * N // 2, 3 * N // 2) if PACKED else (N, 2 * N)      # elements and bytes of an input frame
+IN_DT = torch.uint8 if PACKED else torch.int16
 
 ch = SpectrumChain(0)
 if FLOAT:
@@ -37,14 +42,16 @@ ch.set_filter_mode(mode)
 ch.reserve(B)
 rng = np.random.default_rng(0)
 host = [rng.integers(-2048, 2048, size=(B, N), dtype=np.int16) for _ in range(4)]       # 4 distinct batches, reused
+if PACKED:
+    host = [pack12(b) for b in host]
 out = [torch.empty((B, N) if FLOAT else (B, N, 2), dtype=torch.float32 if FLOAT else torch.int16, device="cuda")
        for _ in range(2)]
-feeder = DeviceFeeder(0, max_batch=B)
+feeder = DeviceFeeder(0, max_batch=B, packed=PACKED)
 
 
 def process(xd, o):
     if FLOAT:
-        ch.process_f32(xd, out=o)          # int16 tensor in: sa_process_f32_i16
+        ch.process_f32(xd, out=o)          # int16 tensor in: sa_process_f32_i16; uint8: sa_process_f32_p12
     else:
         ch.process_q15(xd, out=o)
 
@@ -59,8 +66,8 @@ def run(batches):
 
 
 def pure_h2d():
-    pin = torch.empty((B, N), dtype=torch.int16).pin_memory()
-    dev = torch.empty((B, N), dtype=torch.int16, device="cuda")
+    pin = torch.empty((B, ROW), dtype=IN_DT).pin_memory()
+    dev = torch.empty((B, ROW), dtype=IN_DT, device="cuda")
     for _ in range(3):
         dev.copy_(pin, non_blocking=True)
     torch.cuda.synchronize()
@@ -68,7 +75,7 @@ def pure_h2d():
     for _ in range(20):
         dev.copy_(pin, non_blocking=True)
     torch.cuda.synchronize()
-    return 20 * B * N * 2 / (time.perf_counter() - t0)
+    return 20 * B * FRAME_BYTES / (time.perf_counter() - t0)
 
 
 def pure_kernels():
@@ -88,9 +95,9 @@ dt = run(host[i & 3] for i in range(NB))
 h2d = pure_h2d()
 kfps = pure_kernels()
 print(f"batch {B} frames x {NB} batches, filter mode 0x{mode:02X}")
-print(f"  pinned host -> device copy alone      : {h2d / 1e9:6.1f} GB/s = {h2d / (N * 2) / 1e6:5.2f} M frames/s   (PCIe Gen5 x16 spec 63 GB/s = 1.92 M frames/s)")
-print(f"  {'float chain from int16' if FLOAT else 'Q15 kernels'} alone, inputs resident: {kfps / 1e6:5.2f} M frames/s")
-print(f"  feeder end to end (numpy -> pinned -> device -> path): {NB * B / dt / 1e6:5.2f} M frames/s = {NB * B * N * 2 / dt / 1e9:5.1f} GB/s of samples")
+print(f"  pinned host -> device copy alone      : {h2d / 1e9:6.1f} GB/s = {h2d / FRAME_BYTES / 1e6:5.2f} M frames/s   (PCIe Gen5 x16 spec 63 GB/s = {63e9 / FRAME_BYTES / 1e6:4.2f} M frames/s)")
+print(f"  {('float chain from packed 12-bit' if PACKED else 'float chain from int16') if FLOAT else 'Q15 kernels'} alone, inputs resident: {kfps / 1e6:5.2f} M frames/s")
+print(f"  feeder end to end (numpy -> pinned -> device -> path): {NB * B / dt / 1e6:5.2f} M frames/s = {NB * B * FRAME_BYTES / dt / 1e9:5.1f} GB/s of samples ({FRAME_BYTES} bytes per frame)")
 # the host copy into the staging buffer is part of the feeder; how much of the time is it?
 t0 = time.perf_counter()
 for i in range(8):
