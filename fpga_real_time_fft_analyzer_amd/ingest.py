@@ -120,7 +120,7 @@ class FrameCutter:
 
 
 class DeviceFeeder:
-    """Double-buffered host -> device mover: ``feed(batch_iter)`` yields device tensors [B,16384] int16
+    """Buffered host -> device mover: ``feed(batch_iter)`` yields device tensors [B,16384] int16
     (``packed``: [B,24576] uint8) while the next batch is already in flight on a side stream.
 
     Two pinned staging buffers, two device buffers, and FOUR events created once (a "copied" and a
@@ -132,51 +132,105 @@ class DeviceFeeder:
 
     ``packed=True``: the batches are packed 12-bit frames, [B,24576] uint8 (what a packed :class:`FrameCutter` cuts), and
     so are the staging and device buffers and the tensors handed out: three quarters of the bytes per frame on the link.
-    ``SpectrumChain.process_f32`` takes them as they are."""
+    ``SpectrumChain.process_f32`` takes them as they are.
+
+    **The consumer's contract.**  The tensor handed out for batch k is a view of a slot's device buffer.  The consumer
+    enqueues its work on the stream that was current when ``feed`` started, between taking batch k and asking for
+    batch k+1, and the feeder rewrites a slot -- its pinned and its device buffer -- only after the consumer's work on
+    it is ordered on that stream and has run there (a host wait on the slot's "consumed" event).
+
+    ``consumer_depth`` (1..4) says how far the consumer's reads lag behind its calls.  1 (the default): the work on
+    batch k is on the current stream when the consumer asks for batch k+1 -- any stream-ordered consumer, a
+    ``SpectrumChain`` at overlap depth 1.  d > 1: the consumer is a chain with ``set_overlap(d)`` (or anything that
+    follows the overlap contract of include/specan.h): call k runs on a stream of the library's and the current stream
+    joins it only when call k+d-1 is made, so the slot of batch k counts as consumed from that call on, and the feeder
+    keeps d+1 slots (d batches lent to the consumer, one being filled) where depth 1 keeps two.  A feeder whose
+    ``consumer_depth`` is smaller than the chain's overlap depth rewrites buffers under running kernels.
+
+    **At the end of a feed** -- the iterator is exhausted, or the consumer stops early -- the last d-1 calls of an
+    overlapped consumer are not joined by anything: call ``SpectrumChain.flush()`` on the same current stream before
+    the results are read there AND before the next ``feed()`` of this feeder is started; the next ``feed()`` takes
+    everything enqueued on the current stream at its start as the end of the earlier consumers' work.  With
+    ``consumer_depth`` 1 nothing is to be done.
+
+    **Refused** (``ValueError``): a ``consumer_depth`` outside 1..4, a batch of more than ``max_batch`` frames.
+    ``RuntimeError``: going on with an iterator of an earlier ``feed()`` after a new ``feed()`` of the same feeder has
+    started -- one feed at a time; an abandoned iterator needs no closing."""
+
+    MAX_CONSUMER_DEPTH = 4              # sa_set_overlap's largest depth (include/specan.h)
 
     def __init__(self, device: torch.device | int = 0, max_batch: int = 256, host_threads: Optional[int] = None,
-                 packed: bool = False):
+                 packed: bool = False, consumer_depth: int = 1):
+        if not 1 <= int(consumer_depth) <= self.MAX_CONSUMER_DEPTH:
+            raise ValueError("consumer_depth must be in 1..4 (the overlap depths of SpectrumChain.set_overlap)")
         if host_threads is not None:
             torch.set_num_threads(int(host_threads))
         self.device = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
         self.max_batch = max_batch
         self.packed = bool(packed)
+        self.consumer_depth = int(consumer_depth)
         self._row, self._np_dtype = (P12_FRAME_BYTES, np.uint8) if packed else (N, np.int16)
         dt = torch.uint8 if packed else torch.int16
-        self._pinned = [torch.empty((max_batch, self._row), dtype=dt).pin_memory() for _ in range(2)]
-        self._dev = [torch.empty((max_batch, self._row), dtype=dt, device=self.device) for _ in range(2)]
+        ns = self._nslots = 2 if self.consumer_depth == 1 else self.consumer_depth + 1
+        self._pinned = [torch.empty((max_batch, self._row), dtype=dt).pin_memory() for _ in range(ns)]
+        self._dev = [torch.empty((max_batch, self._row), dtype=dt, device=self.device) for _ in range(ns)]
         self._copy_stream = torch.cuda.Stream(self.device)
-        self._copied = [torch.cuda.Event() for _ in range(2)]      # slot's host->device copy has run
-        self._consumed = [torch.cuda.Event() for _ in range(2)]    # slot's consumer work has been enqueued and run
-        self._used = [False, False]
+        self._copied = [torch.cuda.Event() for _ in range(ns)]      # slot's host->device copy has run
+        self._consumed = [torch.cuda.Event() for _ in range(ns)]    # slot's consumer work is ordered on the stream and has run
+        self._used = [False] * ns
+        self._copying = [False] * ns    # a copy into the slot was enqueued and the slot not handed out since (abandoned feed)
+        self._lent = []                 # slots handed out and not yet recorded as consumed, oldest first
+        self._feed = 0                  # serial number of the feed() that owns the feeder
+
+    def _retire(self, cur, keep: int):
+        """Record "consumed" on `cur` for all but the newest `keep` lent slots: the consumer's latest call joined the
+        one made consumer_depth-1 calls before it, and a new feed() starts behind the consumer's flush."""
+        while len(self._lent) > keep:
+            s = self._lent.pop(0)
+            self._consumed[s].record(cur)
+            self._used[s] = True
 
     def feed(self, batches: Iterable[np.ndarray]) -> Iterator[torch.Tensor]:
         cur = torch.cuda.current_stream(self.device)
+        self._feed += 1
+        me = self._feed
+        # what an earlier feed left lent (an overlapped consumer's last calls, a batch taken from an abandoned iterator):
+        # the consumer has flushed onto `cur` by now (class docstring)
+        self._retire(cur, 0)
         pend = None                                             # (slot, n_frames) handed out next
         for i, b in enumerate(batches):
             b = np.ascontiguousarray(b, self._np_dtype).reshape(-1, self._row)
             n = b.shape[0]
             if n > self.max_batch:
                 raise ValueError("batch larger than max_batch")
-            slot = i & 1
+            slot = i % self._nslots
             if self._used[slot]:
                 self._consumed[slot].synchronize()              # the slot's previous consumer is done with it
+            if self._copying[slot]:
+                self._copied[slot].synchronize()                # an abandoned feed's copy still reads the pinned buffer
             self._pinned[slot][:n].copy_(torch.from_numpy(b))
             with torch.cuda.stream(self._copy_stream):
                 self._dev[slot][:n].copy_(self._pinned[slot][:n], non_blocking=True)
                 self._copied[slot].record(self._copy_stream)
+            self._copying[slot] = True
             if pend is not None:
                 ps, pn = pend
+                self._copying[ps] = False
+                self._lent.append(ps)
                 yield self._dev[ps][:pn]                        # the consumer enqueues its work on `cur` here
-                self._consumed[ps].record(cur)
-                self._used[ps] = True
+                if me != self._feed:
+                    raise RuntimeError("DeviceFeeder: this iterator was superseded by a later feed()")
+                self._retire(cur, self.consumer_depth - 1)
             cur.wait_event(self._copied[slot])
             pend = (slot, n)
         if pend is not None:
             ps, pn = pend
+            self._copying[ps] = False
+            self._lent.append(ps)
             yield self._dev[ps][:pn]
-            self._consumed[ps].record(cur)
-            self._used[ps] = True
+            if me != self._feed:
+                raise RuntimeError("DeviceFeeder: this iterator was superseded by a later feed()")
+            self._retire(cur, self.consumer_depth - 1)
 
 
 def udp_emit(frame_bytes: bytes, addr: tuple[str, int], sock: Optional[socket.socket] = None,
