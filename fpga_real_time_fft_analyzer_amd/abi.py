@@ -103,6 +103,8 @@ def lib() -> C.CDLL:
     L.sa_process_q15.argtypes = [H, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
     L.sa_process_q15_out.argtypes = [H, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
     L.sa_filter_q15.argtypes = [H, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    L.sa_process_q15_p12.argtypes = [H, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    L.sa_filter_q15_p12.argtypes = [H, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
     L.sa_process_f32.argtypes = [H, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
     L.sa_process_f32_i16.argtypes = [H, C.c_void_p, C.c_float, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
     L.sa_process_f32_p12.argtypes = [H, C.c_void_p, C.c_float, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
@@ -123,7 +125,7 @@ def lib() -> C.CDLL:
                  "sa_feed_command_bytes_ex", "sa_get_transport",
                  "sa_load_sos_f32", "sa_load_sos_f64", "sa_load_sos_q14", "sa_set_window_q15",
                  "sa_set_window_f32", "sa_set_window_mode_q15", "sa_get_window_q15", "sa_process_q15", "sa_process_q15_out",
-                 "sa_filter_q15", "sa_process_f32", "sa_process_f32_i16", "sa_process_f32_p12", "sa_pack_samples_p12",
+                 "sa_filter_q15", "sa_process_q15_p12", "sa_filter_q15_p12", "sa_process_f32", "sa_process_f32_i16", "sa_process_f32_p12", "sa_pack_samples_p12",
                  "sa_unpack_samples_p12", "sa_pack_frame", "sa_debug_iir_plan_f32",
                  "sa_iir_plan_from_sos", "sa_set_precision", "sa_get_precision", "sa_debug_iir_plan_f64",
                  "sa_iir_plan_from_sos_f64", "sa_set_marker_range", "sa_get_marker_range"):

@@ -366,17 +366,26 @@ class SpectrumChain:
         """[B,16384] int16 -> per ``out_kind``: 'iq' (the default) [B,16384,2] int16 (re, im), B frames of 65536 bytes;
         'mag' [B,16384] float32, frames.decode_mag_16iq_le of each of those frames bit for bit (gui.py:250-260);
         'marker' [B,4] int32, one sa_marker_q15 per frame over the marker range (peak_mag as float32 bits, peak_bin,
-        band_power as the two halves of an int64; see :meth:`markers_q15`)."""
+        band_power as the two halves of an int64; see :meth:`markers_q15`).
+
+        A uint8 tensor [B,24576] holds the same samples packed to 12 bits (include/specan.h, "p12"; ingest.pack12 is the
+        host packer): it goes to sa_process_q15_p12, is unpacked inside the kernels that read the samples and gives the
+        results of the int16 tensor of the same samples bit for bit, from three quarters of the input bytes.  Its data
+        pointer must be 16-byte aligned (any tensor torch allocates is, and so is every whole-frame slice of one)."""
         if out_kind not in _Q15_OUT_KINDS:
             raise SpecanError(abi.SA_EINVAL, f"out_kind must be one of {sorted(_Q15_OUT_KINDS)}")
-        B = self._check_in(x, torch.int16)
+        from_p12 = isinstance(x, torch.Tensor) and x.dtype == torch.uint8
+        B = self._check_in(x, torch.uint8 if from_p12 else torch.int16)
         shape, dt = {"iq": ((B, SA_N, 2), torch.int16), "mag": ((B, SA_N), torch.float32),
                      "marker": ((B, 4), torch.int32)}[out_kind]
         if out is None:
             out = torch.empty(shape, dtype=dt, device=self.device)
         elif tuple(out.shape) != shape or out.dtype != dt or out.device != self.device or not out.is_contiguous():
             raise SpecanError(abi.SA_ESHAPE, f"out must be a contiguous {dt} tensor of shape {shape}")
-        if out_kind == "iq":
+        if from_p12:
+            self._check(self._lib.sa_process_q15_p12(self._h, x.data_ptr(), out.data_ptr(), B, _Q15_OUT_KINDS[out_kind],
+                                                     self._stream()))
+        elif out_kind == "iq":
             self._check(self._lib.sa_process_q15(self._h, x.data_ptr(), out.data_ptr(), B, self._stream()))
         else:
             self._check(self._lib.sa_process_q15_out(self._h, x.data_ptr(), out.data_ptr(), B, _Q15_OUT_KINDS[out_kind],
@@ -388,18 +397,22 @@ class SpectrumChain:
         """Peak search and band power of the integer chain's frames over the marker range: ``(peak_mag float32 [B],
         peak_bin int32 [B], band_power int64 [B])``, views of the [B,4] int32 record tensor (``out``, allocated when
         None) that ``process_q15(x, out, 'marker')`` fills.  peak_mag is the 'mag' value at peak_bin, bit for bit, and
-        band_power the exact integer sum of re^2 + im^2 over the range."""
+        band_power the exact integer sum of re^2 + im^2 over the range.  ``x`` is int16 or packed uint8 as for
+        :meth:`process_q15`."""
         rec = self.process_q15(x, out, out_kind="marker")
         return rec.view(torch.float32)[:, 0], rec[:, 1], rec.view(torch.int64)[:, 1]
 
     def filter_q15(self, x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """Window (+ integer IIR) only: the FFT input stream, [B,16384] int16."""
-        B = self._check_in(x, torch.int16)
+        """Window (+ integer IIR) only: the FFT input stream, [B,16384] int16.  ``x`` is [B,16384] int16 or the same
+        samples packed, [B,24576] uint8 (sa_filter_q15_p12), as for :meth:`process_q15`."""
+        from_p12 = isinstance(x, torch.Tensor) and x.dtype == torch.uint8
+        B = self._check_in(x, torch.uint8 if from_p12 else torch.int16)
         if out is None:
             out = torch.empty((B, SA_N), dtype=torch.int16, device=self.device)
         elif tuple(out.shape) != (B, SA_N) or out.dtype != torch.int16 or out.device != self.device or not out.is_contiguous():
             raise SpecanError(abi.SA_ESHAPE, "out must be a contiguous int16 [B,16384] tensor")
-        self._check(self._lib.sa_filter_q15(self._h, x.data_ptr(), out.data_ptr(), B, self._stream()))
+        fn = self._lib.sa_filter_q15_p12 if from_p12 else self._lib.sa_filter_q15
+        self._check(fn(self._h, x.data_ptr(), out.data_ptr(), B, self._stream()))
         self._lend(x, out)
         return out
 

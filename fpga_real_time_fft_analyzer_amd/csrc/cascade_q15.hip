@@ -9,6 +9,7 @@
 //   staging and flushing.  The text of the pinned loops is in q15_steps.hpp, the FFT that follows in fft_q15.hip.
 #include "q15_dev.hpp"
 #include "q15_steps.hpp"
+#include "p12_dev.hpp"
 #include "../../include/specan.h"
 
 #if defined(SA_STAMPS)
@@ -53,23 +54,55 @@ constexpr int kTileRows = 64 / kTileLanes;                  // rows a wave cover
 constexpr int kTilePasses = kFramesPerWave / kTileRows;     // passes over the wave's four frames
 static_assert(kTile % 32 == 0 && kTileLanes <= 64 && kTileRows * kTilePasses == kFramesPerWave, "tile geometry");
 
-// one tile of the wave's four frames (and the matching ROM words) on its way from HBM to the input ring: 16 B per lane and pass
+// The eight samples a lane moves, as they come from memory.  int16 samples (sa_process_q15, sa_filter_q15): 16 bytes, the
+// four int16-pair words win8 takes.  Packed 12-bit samples (the _p12 entry points; include/specan.h, 24576 bytes per frame,
+// 3/2 bytes per sample): samples n .. n+7, n a multiple of 8, are the 12 bytes at byte 3 n / 2 of the frame -- a multiple
+// of 12, so three aligned dwords in ONE request, and the last unit of a frame ends with the frame (12 x 2048 = 24576):
+// nothing outside [in, in + B * 24576) is read.
+struct Q15P12x8 {
+    unsigned w0, w1, w2;
+};
+__device__ __forceinline__ Q15P12x8 q15_load8_p12(const SaP12 *in, size_t byte)
+{
+    return *reinterpret_cast<const Q15P12x8 *>(in + byte);
+}
+// ... unpacked and repacked to the four int16-pair words
+__device__ __forceinline__ uint4 q15_pairs(Q15P12x8 x)
+{
+    int s[8];
+    p12_unpack8(x.w0, x.w1, x.w2, s);
+    return make_uint4(pack2(s[0], s[1]), pack2(s[2], s[3]), pack2(s[4], s[5]), pack2(s[6], s[7]));
+}
+template <typename InT> constexpr bool kIsP12 = false;
+template <> constexpr bool kIsP12<SaP12> = true;
+template <typename InT> struct Q15Raw8 { typedef uint4 type; };
+template <> struct Q15Raw8<SaP12> { typedef Q15P12x8 type; };
+
+// one tile of the wave's four frames (and the matching ROM words) on its way from HBM to the input ring: 16 B per lane and
+// pass (12 B of packed samples)
+template <typename InT>
 struct Q15TileRegs {
-    uint4 x[kTilePasses];
+    typename Q15Raw8<InT>::type x[kTilePasses];
     uint4 c[kTilePasses];
 };
 
 // issue the global loads of one tile (4 frames x 256 samples and the matching ROM words), 16 B per lane
-__device__ __forceinline__ void q15_load_tile(const int16_t *__restrict__ in, const int16_t *__restrict__ rom, int f0,
-                                              int batch, int n0, int lane, Q15TileRegs &r)
+template <typename InT>
+__device__ __forceinline__ void q15_load_tile(const InT *__restrict__ in, const int16_t *__restrict__ rom, int f0,
+                                              int batch, int n0, int lane, Q15TileRegs<InT> &r)
 {
 #pragma unroll
     for (int i = 0; i < kTilePasses; ++i) {
         const int row = kTileRows * i + lane / kTileLanes;
         const int col = (lane % kTileLanes) * 8;
         const int f = f0 + row;
-        r.x[i] = make_uint4(0, 0, 0, 0);
-        if (f < batch) r.x[i] = *reinterpret_cast<const uint4 *>(in + (size_t)f * SA_NPTS + n0 + col);
+        if constexpr (kIsP12<InT>) {
+            r.x[i] = {0u, 0u, 0u};
+            if (f < batch) r.x[i] = q15_load8_p12(in, (size_t)f * SA_P12_FRAME_BYTES + 3 * ((n0 + col) >> 1));
+        } else {
+            r.x[i] = make_uint4(0, 0, 0, 0);
+            if (f < batch) r.x[i] = *reinterpret_cast<const uint4 *>(in + (size_t)f * SA_NPTS + n0 + col);
+        }
         r.c[i] = *reinterpret_cast<const uint4 *>(rom + n0 + col);
     }
 }
@@ -94,19 +127,32 @@ __device__ __forceinline__ uint4 win8(uint4 x, uint4 c, int win_mode)
     return make_uint4(o[0], o[1], o[2], o[3]);
 }
 
+// Every kernel of this file is defined by a macro, once per input form: on int16 samples (window_q15_kernel,
+// filter_q7_kernel, filter_w14_kernel) and on packed 12-bit samples (the same names with _p12).  Two kernels of one text
+// rather than one more template parameter or a shared inlined body: the int16 kernels keep their symbols and, instruction
+// for instruction, the code they had before the packed form existed (an inlined body did not: DESIGN.md section 4.10).
+
 // Window only (filter mode 0xB1 through sa_filter_q15: the windowed time series, new/hann8192.vhd:36-39): element-wise,
-// 16 bytes (eight samples) of a frame per thread, the ROM words from the L2.
+// eight samples of a frame per thread (16 bytes, 12 of packed samples), the ROM words from the L2.
 constexpr int kWinThreads = 256;
-__global__ __launch_bounds__(kWinThreads) void window_q15_kernel(const int16_t *__restrict__ in, int16_t *__restrict__ out, int batch,
-                                                                  SaQ15Params prm, const int16_t *__restrict__ rom)
-{
-    const size_t chunk = (size_t)blockIdx.x * kWinThreads + threadIdx.x;       // 16-byte chunk of the batch
-    if (chunk >= (size_t)batch * (SA_NPTS / 8)) return;
-    const int col = (int)(chunk % (SA_NPTS / 8)) * 8;
-    const uint4 xv = *reinterpret_cast<const uint4 *>(in + chunk * 8);
-    const uint4 cv = *reinterpret_cast<const uint4 *>(rom + col);
-    *reinterpret_cast<uint4 *>(out + chunk * 8) = win8(xv, cv, prm.win_mode);
-}
+// samples n .. n + 7 of the batch (n a multiple of 8) as int16-pair words: a frame is 3/2 x 16384 bytes of packed samples, so
+// packed sample n of the batch begins at byte 3 n / 2 of the batch
+__device__ __forceinline__ uint4 win_load8(const int16_t *in, size_t n) { return *reinterpret_cast<const uint4 *>(in + n); }
+__device__ __forceinline__ uint4 win_load8(const SaP12 *in, size_t n) { return q15_pairs(q15_load8_p12(in, 3 * (n >> 1))); }
+#define SA_WINDOW_Q15_KERNEL(NAME, InT)                                                                                         \
+    __global__ __launch_bounds__(kWinThreads) void NAME(const InT *__restrict__ in, int16_t *__restrict__ out, int batch,       \
+                                                        SaQ15Params prm, const int16_t *__restrict__ rom)                       \
+    {                                                                                                                           \
+        const size_t chunk = (size_t)blockIdx.x * kWinThreads + threadIdx.x; /* 16-byte chunk of the batch */                   \
+        if (chunk >= (size_t)batch * (SA_NPTS / 8)) return;                                                                     \
+        const int col = (int)(chunk % (SA_NPTS / 8)) * 8;                                                                       \
+        const uint4 xv = win_load8(in, chunk * 8);                                                                              \
+        const uint4 cv = *reinterpret_cast<const uint4 *>(rom + col);                                                           \
+        *reinterpret_cast<uint4 *>(out + chunk * 8) = win8(xv, cv, prm.win_mode);                                               \
+    }
+SA_WINDOW_Q15_KERNEL(window_q15_kernel, int16_t)
+SA_WINDOW_Q15_KERNEL(window_q15_p12_kernel, SaP12)
+#undef SA_WINDOW_Q15_KERNEL
 
 // ------------------------------------------------------------------------------------------ the cascade frame
 // The cascade is organised around what bounds it: the recursion is serial in time, there is one wave per SIMD at
@@ -151,13 +197,15 @@ static_assert(kOutMask == 0x0100010001000100ull && kInMask == 0xFE01FE01FE01FE01
 static_assert(kLaneSec0 + SA_MAXSEC < kLaneOut && !row_is_in(kLaneOut) && kRowLanes * kFramesPerWave == 64, "row geometry");
 
 // window the loaded tile and put it into its half (col0 = 0 or kTile) of the wave's input ring: 16 bytes per lane
-__device__ __forceinline__ void q15_window_into_ring(const Q15TileRegs &r, int16_t (*dst)[kInPitch], int col0, int lane, int win_mode)
+template <typename InT>
+__device__ __forceinline__ void q15_window_into_ring(const Q15TileRegs<InT> &r, int16_t (*dst)[kInPitch], int col0, int lane, int win_mode)
 {
 #pragma unroll
     for (int i = 0; i < kTilePasses; ++i) {
         const int row = kTileRows * i + lane / kTileLanes;
         const int col = col0 + (lane % kTileLanes) * 8;
-        *reinterpret_cast<uint4 *>(&dst[row][col]) = win8(r.x[i], r.c[i], win_mode);
+        if constexpr (kIsP12<InT>) *reinterpret_cast<uint4 *>(&dst[row][col]) = win8(q15_pairs(r.x[i]), r.c[i], win_mode);
+        else *reinterpret_cast<uint4 *>(&dst[row][col]) = win8(r.x[i], r.c[i], win_mode);
     }
 }
 
@@ -204,13 +252,13 @@ __device__ __forceinline__ void wg_lds_sync()
 // samples of delay, so that a flush covers exactly one half of the output ring (samples [kTile j - 8, kTile (j+1) - 8) live in
 // slots [kTile j, kTile (j+1)) mod kRing) while the cascade writes the other half.  One workgroup barrier per tile (both sides
 // wait for their LDS traffic only); the cascade side runs nt tiles, the drain, and the same nt + 2 barriers.
-template <typename T>
-__device__ __forceinline__ void q15_helper_wave(const int16_t *__restrict__ in, int16_t *__restrict__ out, const int16_t *__restrict__ rom,
+template <typename T, typename InT>
+__device__ __forceinline__ void q15_helper_wave(const InT *__restrict__ in, int16_t *__restrict__ out, const int16_t *__restrict__ rom,
                                                 int16_t (*tin)[kInPitch], const T (*ring)[kRingPitch], int f0, int batch, int lane,
                                                 int win_mode, bool idle)
 {
     constexpr int nt = SA_NPTS / kTile;
-    Q15TileRegs pre;
+    Q15TileRegs<InT> pre;
     if (!idle) {
         q15_load_tile(in, rom, f0, batch, 0, lane, pre);
         q15_window_into_ring(pre, tin, 0, lane, win_mode);
@@ -237,8 +285,8 @@ __device__ __forceinline__ void q15_helper_wave(const int16_t *__restrict__ in, 
 // Sample m lives in ring slot (m + 8) mod kRing (lane 8 holds samples T0 - 8 .. T0 - 1 at the end of the group that
 // starts at step T0), so that the groups of one tile store to consecutive slots (the first group of the frame stores
 // eight zeros into slots nobody reads).
-template <typename T, typename Carry, typename LaneTaps, typename Tile, typename Drain>
-__device__ __forceinline__ void q15_cascade(const int16_t *__restrict__ in, int16_t *__restrict__ out, int batch, int win_mode,
+template <typename T, typename Carry, typename InT, typename LaneTaps, typename Tile, typename Drain>
+__device__ __forceinline__ void q15_cascade(const InT *__restrict__ in, int16_t *__restrict__ out, int batch, int win_mode,
                                             const int16_t *__restrict__ rom, LaneTaps lane_taps, Tile tile, Drain drain)
 {
     __shared__ __attribute__((aligned(16))) int16_t tin_all[kV2Waves][kFramesPerWave][kInPitch];
@@ -255,7 +303,7 @@ __device__ __forceinline__ void q15_cascade(const int16_t *__restrict__ in, int1
     constexpr int nt = SA_NPTS / kTile;
     const bool idle = f0 >= batch;      // a pair without frames still takes part in the workgroup's barriers
     if (helper) {
-        q15_helper_wave(in, out, rom, tin, ring, f0, batch, lane, win_mode, idle);
+        q15_helper_wave<T>(in, out, rom, tin, ring, f0, batch, lane, win_mode, idle);
         return;
     }
     SA_Q15_STAMP_BEGIN(blockIdx.x * kV2Waves + wave);
@@ -363,16 +411,20 @@ __device__ __forceinline__ void q7_drain(Q7Carry &c, const Q7Taps &t, unsigned x
     lds_store16_masked(ra + 16, vb, kOutMask);
 }
 
-template <bool NOB1>
-__global__ __launch_bounds__(64 * kWgWaves) void filter_q7_kernel(const int16_t *__restrict__ in, int16_t *__restrict__ out,
-                                                                   int batch, SaQ15Params prm, const int16_t *__restrict__ rom)
-{
-    q15_cascade<int, Q7Carry>(in, out, batch, prm.win_mode, rom, [&](int sec) -> Q7Taps {
-        if (sec < 0 || sec >= SA_MAXSEC) return {128 << 9, 0, 0, 0, 0};      // identity = (128 x) >> 7
-        const int8_t *c = &prm.c12[(sec & 1) ? 6 : 0];                        // stages 1,3,5 = set 0; 2,4,6 = set 1
-        return {c[2] << 9, c[1] << 9, c[0] << 9, -(c[3] << 9), -(c[4] << 9)};
-    }, [](Q7Carry &c, const Q7Taps &t, unsigned xa, unsigned ra) { q7_tile<NOB1>(c, t, xa, ra); }, q7_drain);
-}
+#define SA_FILTER_Q7_KERNEL(NAME, InT)                                                                                          \
+    template <bool NOB1>                                                                                                        \
+    __global__ __launch_bounds__(64 * kWgWaves) void NAME(const InT *__restrict__ in, int16_t *__restrict__ out, int batch,     \
+                                                          SaQ15Params prm, const int16_t *__restrict__ rom)                     \
+    {                                                                                                                           \
+        q15_cascade<int, Q7Carry>(in, out, batch, prm.win_mode, rom, [&](int sec) -> Q7Taps {                                   \
+            if (sec < 0 || sec >= SA_MAXSEC) return {128 << 9, 0, 0, 0, 0}; /* identity = (128 x) >> 7 */                       \
+            const int8_t *c = &prm.c12[(sec & 1) ? 6 : 0];                  /* stages 1,3,5 = set 0; 2,4,6 = set 1 */           \
+            return {c[2] << 9, c[1] << 9, c[0] << 9, -(c[3] << 9), -(c[4] << 9)};                                               \
+        }, [](Q7Carry &c, const Q7Taps &t, unsigned xa, unsigned ra) { q7_tile<NOB1>(c, t, xa, ra); }, q7_drain);               \
+    }
+SA_FILTER_Q7_KERNEL(filter_q7_kernel, int16_t)
+SA_FILTER_Q7_KERNEL(filter_q7_p12_kernel, SaP12)
+#undef SA_FILTER_Q7_KERNEL
 
 // ------------------------------------------------------------------------------------------ IIR, wide Q2.14 form
 // Mode 0xA2 (the build's own spec, oracle/specan_oracle.c:or_iir_sos_q14; the six sections scripts/fft_analyzer_gui.py:108-157
@@ -440,40 +492,58 @@ __device__ __forceinline__ void w14_tile(W14Carry &c, const W14Taps &t, unsigned
                  : SA_TILE_CLOBBERS);
 }
 
-__global__ __launch_bounds__(64 * kWgWaves) void filter_w14_kernel(const int16_t *__restrict__ in, int16_t *__restrict__ out,
-                                                                    int batch, SaQ15Params prm, const int16_t *__restrict__ rom)
-{
-    q15_cascade<int16_t, W14Carry>(in, out, batch, prm.win_mode, rom, [&](int sec) {
-        if (sec < 0 || sec >= prm.nsec_wide) return w14_taps(16384, 0, 0, 0, 0);   // identity: (16384 x + 8192) >> 14 = x exactly
-        const int16_t *c = &prm.sos_q14[sec * 6];           // scipy row order [b0, b1, b2, a0, a1, a2], a0 ignored (= 1.0)
-        return w14_taps(c[0], c[1], c[2], c[4], c[5]);
-    }, [](W14Carry &c, const W14Taps &t, unsigned xa, unsigned ra) { w14_tile(c, t, xa, ra, kTileIters); },
-    // one pass of four groups: the first delivers the frame's last eight samples, the other three filter whatever the
-    // input ring holds into slots that were flushed long ago
-    [](W14Carry &c, const W14Taps &t, unsigned xa, unsigned ra) { w14_tile(c, t, xa, ra, 1); });
-}
+// one pass of four groups as the drain: the first delivers the frame's last eight samples, the other three filter whatever
+// the input ring holds into slots that were flushed long ago
+#define SA_FILTER_W14_KERNEL(NAME, InT)                                                                                         \
+    __global__ __launch_bounds__(64 * kWgWaves) void NAME(const InT *__restrict__ in, int16_t *__restrict__ out, int batch,     \
+                                                          SaQ15Params prm, const int16_t *__restrict__ rom)                     \
+    {                                                                                                                           \
+        q15_cascade<int16_t, W14Carry>(in, out, batch, prm.win_mode, rom, [&](int sec) {                                        \
+            /* identity: (16384 x + 8192) >> 14 = x exactly */                                                                  \
+            if (sec < 0 || sec >= prm.nsec_wide) return w14_taps(16384, 0, 0, 0, 0);                                            \
+            /* scipy row order [b0, b1, b2, a0, a1, a2], a0 ignored (= 1.0) */                                                  \
+            const int16_t *c = &prm.sos_q14[sec * 6];                                                                           \
+            return w14_taps(c[0], c[1], c[2], c[4], c[5]);                                                                      \
+        }, [](W14Carry &c, const W14Taps &t, unsigned xa, unsigned ra) { w14_tile(c, t, xa, ra, kTileIters); },                 \
+        [](W14Carry &c, const W14Taps &t, unsigned xa, unsigned ra) { w14_tile(c, t, xa, ra, 1); });                            \
+    }
+SA_FILTER_W14_KERNEL(filter_w14_kernel, int16_t)
+SA_FILTER_W14_KERNEL(filter_w14_p12_kernel, SaP12)
+#undef SA_FILTER_W14_KERNEL
 
-}  // namespace
-
-hipError_t sa_launch_filter_q15(const int16_t *in, int16_t *out_time, int batch, const SaQ15Params &p,
-                                const SaQ15Tables &t, hipStream_t stream, SaLaunchEv ev)
+// every launch of one input form: window only, the wide cascade, the Q7 cascade with its seven- or nine-instruction step
+template <typename InT, typename K>
+void launch_filter(K window, K wide, K q7_short, K q7_long, const InT *in, int16_t *out_time, int batch, const SaQ15Params &p,
+                   const SaQ15Tables &t, hipStream_t stream, SaLaunchEv ev)
 {
-    if (batch <= 0) return hipSuccess;
     const int per_wg = kFramesPerWave * kV2Waves;
     const dim3 grid_wg((batch + per_wg - 1) / per_wg), block_wg(64 * kWgWaves);
     if (p.filter == SA_FILTER_NONE) {
         const size_t chunks = (size_t)batch * (SA_NPTS / 8);
-        hipExtLaunchKernelGGL(window_q15_kernel, dim3((unsigned)((chunks + kWinThreads - 1) / kWinThreads)), dim3(kWinThreads), 0, stream,
+        hipExtLaunchKernelGGL(window, dim3((unsigned)((chunks + kWinThreads - 1) / kWinThreads)), dim3(kWinThreads), 0, stream,
                               ev.start, ev.stop, 0, in, out_time, batch, p, t.rom);
     } else if (p.filter == SA_FILTER_WIDE) {
-        hipExtLaunchKernelGGL(filter_w14_kernel, grid_wg, block_wg, 0, stream, ev.start, ev.stop, 0, in, out_time, batch, p, t.rom);
+        hipExtLaunchKernelGGL(wide, grid_wg, block_wg, 0, stream, ev.start, ev.stop, 0, in, out_time, batch, p, t.rom);
     } else {
         // B1 = 0 in both coefficient sets (wire order b0,b1,b2,a0,a1,a2 per set): the seven-instruction step
         const bool nob1 = p.c12[1] == 0 && p.c12[7] == 0;
-        if (nob1)
-            hipExtLaunchKernelGGL(filter_q7_kernel<true>, grid_wg, block_wg, 0, stream, ev.start, ev.stop, 0, in, out_time, batch, p, t.rom);
-        else
-            hipExtLaunchKernelGGL(filter_q7_kernel<false>, grid_wg, block_wg, 0, stream, ev.start, ev.stop, 0, in, out_time, batch, p, t.rom);
+        hipExtLaunchKernelGGL(nob1 ? q7_short : q7_long, grid_wg, block_wg, 0, stream, ev.start, ev.stop, 0, in, out_time, batch, p,
+                              t.rom);
     }
+}
+
+}  // namespace
+
+hipError_t sa_launch_filter_q15(const void *in, SaInKind in_kind, int16_t *out_time, int batch, const SaQ15Params &p,
+                                const SaQ15Tables &t, hipStream_t stream, SaLaunchEv ev)
+{
+    if (in_kind != SaInKind::I16 && in_kind != SaInKind::P12) return hipErrorInvalidValue;
+    if (batch <= 0) return hipSuccess;
+    if (in_kind == SaInKind::P12)
+        launch_filter(window_q15_p12_kernel, filter_w14_p12_kernel, filter_q7_p12_kernel<true>, filter_q7_p12_kernel<false>,
+                      static_cast<const SaP12 *>(in), out_time, batch, p, t, stream, ev);
+    else
+        launch_filter(window_q15_kernel, filter_w14_kernel, filter_q7_kernel<true>, filter_q7_kernel<false>,
+                      static_cast<const int16_t *>(in), out_time, batch, p, t, stream, ev);
     return hipGetLastError();
 }

@@ -4,6 +4,7 @@
 #pragma once
 #include "sa_common.hpp"
 #include "fft_regs.hpp"
+#include "p12_dev.hpp"
 #include "../../include/specan.h"
 
 using safft::cf;
@@ -113,11 +114,7 @@ __device__ __forceinline__ void dma_rows(const int16_t *x, unsigned char *smem, 
     dma_rows_impl(x, 0, smem, lane, wave);
 }
 
-// Packed 12-bit samples ("p12", include/specan.h: sample n in bits [12n, 12n+12) of the frame read as a little-endian
-// bit stream, 24576 bytes per frame).  A tag type over the bytes, so that no overload collides with a plain byte pointer.
-struct SaP12 {
-    uint8_t b;
-};
+// Packed 12-bit samples: the tag type SaP12 over the bytes and the unpack of eight samples are in p12_dev.hpp.
 // elements of InT from one frame to the next
 template <typename InT> constexpr int kFrameElems = SA_NPTS;
 template <> constexpr int kFrameElems<SaP12> = SA_P12_FRAME_BYTES;
@@ -174,21 +171,6 @@ __device__ __forceinline__ void p12_read_row(const unsigned char *smem, int t, u
         ua[4 * c] = q[c].x; ua[4 * c + 1] = q[c].y; ua[4 * c + 2] = q[c].z; ua[4 * c + 3] = q[c].w;
         ub[4 * c] = q[3 + c].x; ub[4 * c + 1] = q[3 + c].y; ub[4 * c + 2] = q[3 + c].z; ub[4 * c + 3] = q[3 + c].w;
     }
-}
-
-// Eight samples from three dwords (96 bits): sign-extending bit-field extracts; samples 2 and 5 straddle a dword and
-// come out of a funnel shift (v_alignbit_b32) first.
-__device__ __forceinline__ int p12_bfe(unsigned w, int pos) { return (int)(w << (20 - pos)) >> 20; }
-__device__ __forceinline__ void p12_unpack8(unsigned w0, unsigned w1, unsigned w2, int (&s)[8])
-{
-    s[0] = p12_bfe(w0, 0);
-    s[1] = p12_bfe(w0, 12);
-    s[2] = p12_bfe(__builtin_amdgcn_alignbit(w1, w0, 24), 0);
-    s[3] = p12_bfe(w1, 4);
-    s[4] = p12_bfe(w1, 16);
-    s[5] = p12_bfe(__builtin_amdgcn_alignbit(w2, w1, 28), 0);
-    s[6] = p12_bfe(w2, 8);
-    s[7] = (int)w2 >> 20;
 }
 
 // Stage-out, round h, the stage-in run backwards: row r (32 float32 samples) -> o[64r + 32h ..].

@@ -1,8 +1,10 @@
 // fft_q15.hip -- SA-FXFFT-1 for gfx950 (MI355X): the fixed-point FFT that stands where ip/xfft_0 stands
 // (radix-4 DIF, >>2 per stage, Q15 twiddles, truncation).  One 1024-thread workgroup per frame, data in LDS as packed
 // (re,im) int16 pairs, Stockham (autosort) addressing so the result is in natural order, stages paired in registers; the
-// arithmetic per butterfly is exactly oracle/specan_oracle.c:or_fxfft16k.
+// arithmetic per butterfly is exactly oracle/specan_oracle.c:or_fxfft16k.  The kernel's text is fft_q15_kernel.inc, included
+// once for int16 samples and once for packed 12-bit samples (include/specan.h, "p12"; unpacked in stage 0).
 #include "q15_dev.hpp"
+#include "p12_dev.hpp"
 #include "../../include/specan.h"
 
 namespace {
@@ -303,163 +305,52 @@ __device__ __forceinline__ void fx_mark_finish(FxMark a, uint4 *scr, void *__res
 // arguments, so the other kinds' argument loads are where they were).
 constexpr int kFftLds = SA_NPTS * 4;                      // the frame image; MARKER: + kFxMarkParts x 16 bytes behind it
 
-template <bool WINDOW, int OUT>
-__global__ __launch_bounds__(kFftWide, 8) void fft_q15_kernel(const int16_t *__restrict__ in,
-                                                               void *__restrict__ out, int batch,
-                                                               SaQ15Params prm, const int16_t *__restrict__ rom,
-                                                               const uint2 *__restrict__ tw, const uint4 *__restrict__ twrec,
-                                                               unsigned mrange)
+// Stage 0's samples of thread t, x[m] = sample t + 1024 m of frame f.  int16 samples: 2-byte loads, 128 contiguous bytes
+// per wave instruction.
+__device__ __forceinline__ void fx_load16(const int16_t *in, int f, int t, int (&x)[16])
 {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_q[];
-    unsigned *buf = reinterpret_cast<unsigned *>(smem_q);     // [16384] packed (re, im)
-    const int t = threadIdx.x;
-    const int f = blockIdx.x;
-    if (f >= batch) return;
-    // ---- stage 0 straight from global memory: the thread's 16 positions t + 1024 m as 2-byte loads (128 contiguous
-    // bytes per wave instruction), optional window, imag = 0 (new/command_control.vhd:123).  No staging pass
-    // through LDS, no barrier in front of the first butterflies; outputs 4 bf + i' are one 16-byte LDS write.
-    // Exponents with wi = -32768 (see fx_butterfly): stages 0 and 1, u = 3 for output 1, u = 1 for output 3.
-    {
-        const int16_t *xf = in + (size_t)f * SA_NPTS + t;
-        int x[16];
+    const int16_t *xf = in + (size_t)f * SA_NPTS + t;
 #pragma unroll
-        for (int m = 0; m < 16; ++m) x[m] = xf[kFftWide * m];
-        if constexpr (WINDOW) {
-            int c[16];
+    for (int m = 0; m < 16; ++m) x[m] = xf[kFftWide * m];
+}
+// Packed 12-bit samples (include/specan.h; a frame is 6144 dwords, every frame 16-byte aligned): sample n sits at bit 12 n,
+// so sample t + 1024 m begins in dword (12 t >> 5) + 384 m at bit sh = 12 t & 31, the same for all 16 m.  It reaches into
+// the next dword only where sh > 20, i.e. sh = 24 or 28, t mod 8 = 2 or 5.  Two aligned dword loads (a wave instruction
+// covers 96 contiguous bytes), a funnel shift by sh and a sign-extending extract of the low 12 bits.  The second load
+// takes the next dword ONLY in the straddling lanes and the first dword again in all others (where the funnel shift's
+// upper input does not reach the 12 bits kept): the frame's last dword, 6143, is the first dword of t = 1022 (sh = 8) and
+// t = 1023 (sh = 20) at m = 15, neither of which straddles, so no index exceeds 6143 and no byte outside
+// [in, in + B * 24576) is read -- by the address map, not by slack behind the tensor.
+constexpr int kP12FrameDwords = SA_P12_FRAME_BYTES / 4;
+__device__ __forceinline__ void fx_load16(const SaP12 *in, int f, int t, int (&x)[16])
+{
+    const int bit = 12 * t, sh = bit & 31;
+    const unsigned *lo = reinterpret_cast<const unsigned *>(in) + (size_t)f * kP12FrameDwords + (bit >> 5);
+    const unsigned *hi = lo + (sh > 20 ? 1 : 0);
+    constexpr int step = 12 * kFftWide / 32;                  // dwords from sample n to sample n + 1024
 #pragma unroll
-            for (int m = 0; m < 16; ++m) c[m] = rom[t + kFftWide * m];
-#pragma unroll
-            for (int m = 0; m < 16; ++m)
-                x[m] = (prm.win_mode == SA_WIN_RTL_SIGNED) ? win_rtl(x[m], c[m]) : win_u16(x[m], c[m]);
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int bf = t + kFftWide * u;                   // j' = bf, kappa = 0, e1 = bf
-            unsigned o[4];
-            const SaTw3 w = fx_twrec(twrec, bf);
-            fx_butterfly_real(x[u], x[u + 4], x[u + 8], x[u + 12], w.w1, w.w2.x, w.w3, bf == 0, o, u == 3, u == 1);
-            *reinterpret_cast<uint4 *>(buf + 4 * bf) = make_uint4(o[0], o[1], o[2], o[3]);
-        }
-        __syncthreads();
-    }
-
-    // ---- stages 1..4 as two register passes of two stages each.  A thread that runs the stage-s butterflies
-    // bf = t + 1024 u (u = 0..3) holds, in output i' of butterfly u, input u of the stage-(s+1) butterfly
-    // ((j' mod 4^(5-s)) << (2s+2)) | (i' << 2s) | kappa -- its own four next butterflies, which all share ONE twiddle
-    // exponent (j'' = (t >> 2s) mod 4^(5-s) does not depend on i').  One LDS exchange per two stages instead of one per
-    // stage, a quarter of the twiddle loads in the second stage of a pass.
-    //   outputs of the pass: pos = (j'' << (2s+4)) | (i'' << (2s+2)) | (i' << 2s) | kappa
-    // Pass (1,2) writes with kappa = t & 3 in the bank bits: the words are stored at pos ^ ((j'' & 15) << 2), which spreads
-    // the 16 values of j'' in a wave over the banks (conflict-free), and pass (3,4) reads t + 1024 m through the same
-    // exchange of bits (there it permutes the lanes of a wave: conflict-free as well).
-    unsigned v[16];
-    const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
-    {
-#pragma unroll
-        for (int m = 0; m < 16; ++m) v[m] = buf[t + kFftWide * m];
-        __syncthreads();
-        unsigned x[16];                                        // x[4 i' + u]
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int e1 = ((t + kFftWide * u) >> 2) << 2;
-            unsigned o[4];
-            // exponents with wi = -32768 (see fx_butterfly): output 1 at u = 3, output 3 at u = 1, output 2 at u = 1 or 2
-            const SaTw3 w = fx_twrec(twrec, 4096 + (e1 >> 2));
-            fx_butterfly(v[u], v[u + 4], v[u + 8], v[u + 12], w.w1, w.w2, w.w3, e1 == 0, o, u == 3, u == 1 || u == 2, u == 1);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) x[4 * i + u] = o[i];
-        }
-        // stage 2: j'' = (t >> 2) & 255, exponent 16 j'' (never in 4082..4095; 3 e never in 4083..4110; 2 e = 4096 for
-        // j'' = 128, i.e. threads 512..515: wave 8 takes the two-multiply form for output 2)
-        const int j2 = (t >> 2) & 255, e2 = j2 << 4;
-        const SaTw3 w2 = fx_twrec(twrec, 5120 + j2);
-        const uint2 a1 = w2.w1, a2 = w2.w2, a3 = w2.w3;
-        const int ob = ((j2 << 6) | (t & 3)) ^ ((j2 & 15) << 2);
-#pragma unroll
-        for (int ip = 0; ip < 4; ++ip) {
-            unsigned o[4];
-            if (wave == 8) fx_butterfly(x[4 * ip], x[4 * ip + 1], x[4 * ip + 2], x[4 * ip + 3], a1, a2, a3, false, o, false, true, false);
-            else fx_butterfly(x[4 * ip], x[4 * ip + 1], x[4 * ip + 2], x[4 * ip + 3], a1, a2, a3, e2 == 0, o, false, false, false);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) buf[ob ^ ((4 * i + ip) << 2)] = o[i];
-        }
-        __syncthreads();
-    }
-    {
-        // pass (3,4): scalar twiddles in both stages (j' = wave + 16 u, then j'' = wave)
-#pragma unroll
-        for (int m = 0; m < 16; ++m) v[m] = buf[(t + kFftWide * m) ^ (wave << 2)];
-        __syncthreads();
-        unsigned x[16];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int e1 = (wave + 16 * u) << 6;
-            unsigned o[4];
-            fx_butterfly<true>(v[u], v[u + 4], v[u + 8], v[u + 12], tw[e1], tw[2 * e1], tw[3 * e1], e1 == 0, o, false, u == 2, false);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) x[4 * i + u] = o[i];
-        }
-        const int e2 = wave << 8;                              // 2 e = 4096 for wave 8
-        const uint2 a1 = tw[e2], a2 = tw[2 * e2], a3 = tw[3 * e2];
-        const int ob = (wave << 10) | (t & 63);
-#pragma unroll
-        for (int ip = 0; ip < 4; ++ip) {
-            unsigned o[4];
-            if (wave == 8) fx_butterfly<true>(x[4 * ip], x[4 * ip + 1], x[4 * ip + 2], x[4 * ip + 3], a1, a2, a3, false, o, false, true, false);
-            else fx_butterfly<true>(x[4 * ip], x[4 * ip + 1], x[4 * ip + 2], x[4 * ip + 3], a1, a2, a3, e2 == 0, o, false, false, false);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) buf[ob | ((4 * i + ip) << 6)] = o[i];
-        }
-        __syncthreads();
-    }
-#pragma unroll
-    for (int m = 0; m < 16; ++m) v[m] = buf[t + kFftWide * m];
-    unsigned w[16];
-    // stage 5 (4^s = 1024): j' = u, kappa = t; outputs land at m' = 4u + i'; exponents are compile-time
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-        unsigned o[4];
-        fx_butterfly<true>(v[u], v[u + 4], v[u + 8], v[u + 12], tw[u * 1024], tw[2 * u * 1024], tw[3 * u * 1024], u == 0, o, false,
-                           u == 2, false);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) w[4 * u + i] = o[i];
-    }
-    // stage 6 (4^s = 4096): no twiddles; outputs at m' = u + 4 i' = natural-order bin t + 1024 m'
-    // frame layout: [16384] x (re, im) int16 = 65536 bytes (imp/sequ2.vhd:153); one dword per lane
-    // SA_Q15_OUT_MAG: the same dwords at the same offsets of a float row, each the magnitude of its bin.
-    // SA_Q15_OUT_MARKER: no spectrum store; the thread keeps the 16 sums re^2 + im^2 of its bins and roots their largest.
-    unsigned *o32 = reinterpret_cast<unsigned *>(reinterpret_cast<int16_t *>(out) + (size_t)f * SA_NPTS * 2);
-    const int mlo = (int)(mrange & 0xFFFFu), mhi = (int)(mrange >> 16);
-    float ms[16];
-    unsigned long long mpow = 0ull;
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-        unsigned o[4];
-        fx_butterfly(w[u], w[u + 4], w[u + 8], w[u + 12], make_uint2(0u, 0u), make_uint2(0u, 0u), make_uint2(0u, 0u), true, o, false,
-                     false, false);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int mp = u + 4 * i;
-            if constexpr (OUT == SA_Q15_OUT_IQ)
-                __builtin_nontemporal_store(o[i], o32 + t + kFftWide * mp);   // streaming: written once
-            else if constexpr (OUT == SA_Q15_OUT_MAG)
-                __builtin_nontemporal_store(fx_mag(o[i]), reinterpret_cast<float *>(o32) + t + kFftWide * mp);
-            else
-                ms[mp] = fx_mark_sum_any(mpow, o[i], t + kFftWide * mp, (wave << 6) + kFftWide * mp, mlo, mhi);
-        }
-    }
-    if constexpr (OUT == SA_Q15_OUT_MARKER) {
-        fx_mark_finish(fx_mark_thread(ms, t, mpow), reinterpret_cast<uint4 *>(smem_q + kFftLds), out, f, t, wave);
-    }
+    for (int m = 0; m < 16; ++m)
+        x[m] = p12_bfe(__builtin_amdgcn_alignbit(hi[step * m], lo[step * m], (unsigned)sh), 0);
 }
 
-template <int OUT>
-hipError_t launch_fft_q15(const int16_t *in_time, void *out, int batch, bool apply_window, const SaQ15Params &p,
-                          const SaQ15Tables &t, hipStream_t stream, SaLaunchEv ev)
+#define SA_FX_KERNEL fft_q15_kernel
+#define SA_FX_IN int16_t
+#include "fft_q15_kernel.inc"
+#undef SA_FX_KERNEL
+#undef SA_FX_IN
+// packed samples arrive unwindowed from the caller only (filter mode 0xB1): WINDOW = true is all that is instantiated
+#define SA_FX_KERNEL fft_q15_p12_kernel
+#define SA_FX_IN SaP12
+#include "fft_q15_kernel.inc"
+#undef SA_FX_KERNEL
+#undef SA_FX_IN
+
+template <int OUT, typename K, typename InT>
+hipError_t launch_fft_q15(K k, const InT *in_time, void *out, int batch, const SaQ15Params &p, const SaQ15Tables &t,
+                          hipStream_t stream, SaLaunchEv ev)
 {
     const dim3 grid(batch), block(kFftWide);
     const int lds = kFftLds + (OUT == SA_Q15_OUT_MARKER ? kFxMarkParts * (int)sizeof(uint4) : 0);
-    auto k = apply_window ? fft_q15_kernel<true, OUT> : fft_q15_kernel<false, OUT>;
     const hipError_t e = sa_set_dyn_lds_once(reinterpret_cast<const void *>(k), lds);
     if (e != hipSuccess) return e;
     hipExtLaunchKernelGGL(k, grid, block, lds, stream, ev.start, ev.stop, 0, in_time, out, batch, p, t.rom, t.tw, t.twrec,
@@ -467,16 +358,27 @@ hipError_t launch_fft_q15(const int16_t *in_time, void *out, int batch, bool app
     return hipGetLastError();
 }
 
+template <int OUT>
+hipError_t launch_fft_q15(const void *in_time, SaInKind in_kind, void *out, int batch, bool apply_window, const SaQ15Params &p,
+                          const SaQ15Tables &t, hipStream_t stream, SaLaunchEv ev)
+{
+    if (in_kind == SaInKind::P12)
+        return launch_fft_q15<OUT>(fft_q15_p12_kernel<true, OUT>, static_cast<const SaP12 *>(in_time), out, batch, p, t, stream, ev);
+    return launch_fft_q15<OUT>(apply_window ? fft_q15_kernel<true, OUT> : fft_q15_kernel<false, OUT>,
+                               static_cast<const int16_t *>(in_time), out, batch, p, t, stream, ev);
+}
+
 }  // namespace
 
-hipError_t sa_launch_fft_q15(const int16_t *in_time, void *out, int batch, int out_kind, bool apply_window,
+hipError_t sa_launch_fft_q15(const void *in_time, SaInKind in_kind, void *out, int batch, int out_kind, bool apply_window,
                              const SaQ15Params &p, const SaQ15Tables &t, hipStream_t stream, SaLaunchEv ev)
 {
+    if (in_kind != SaInKind::I16 && !(in_kind == SaInKind::P12 && apply_window)) return hipErrorInvalidValue;
     if (batch <= 0) return hipSuccess;
     switch (out_kind) {
-        case SA_Q15_OUT_IQ: return launch_fft_q15<SA_Q15_OUT_IQ>(in_time, out, batch, apply_window, p, t, stream, ev);
-        case SA_Q15_OUT_MAG: return launch_fft_q15<SA_Q15_OUT_MAG>(in_time, out, batch, apply_window, p, t, stream, ev);
-        case SA_Q15_OUT_MARKER: return launch_fft_q15<SA_Q15_OUT_MARKER>(in_time, out, batch, apply_window, p, t, stream, ev);
+        case SA_Q15_OUT_IQ: return launch_fft_q15<SA_Q15_OUT_IQ>(in_time, in_kind, out, batch, apply_window, p, t, stream, ev);
+        case SA_Q15_OUT_MAG: return launch_fft_q15<SA_Q15_OUT_MAG>(in_time, in_kind, out, batch, apply_window, p, t, stream, ev);
+        case SA_Q15_OUT_MARKER: return launch_fft_q15<SA_Q15_OUT_MARKER>(in_time, in_kind, out, batch, apply_window, p, t, stream, ev);
         default: return hipErrorInvalidValue;
     }
 }

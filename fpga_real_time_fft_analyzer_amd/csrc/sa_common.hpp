@@ -149,7 +149,7 @@ hipError_t sa_launch_chain_f32_i16(const int16_t *in, float in_scale, void *out,
 hipError_t sa_launch_chain_f32_p12(const uint8_t *in, float in_scale, void *out, int batch, int out_kind, const SaF32Tables &t,
                                    hipStream_t stream, SaLaunchEv ev);
 
-// what a float-path call's `in` points to: float32 frames, int16 samples or packed 12-bit samples
+// what a process call's `in` points to: float32 frames (float path only), int16 samples or packed 12-bit samples
 enum class SaInKind { F32, I16, P12 };
 
 // Float64-state cascade (iir_f64.hip): window and cascade of the frame in double, y rounded once to float32 into
@@ -168,8 +168,11 @@ struct SaQ15Tables {                 // rom, tw and twrec are filled by sa_table
 };
 constexpr int kSaTwRecs = 4096 + 1024 + 256;
 
-hipError_t sa_launch_filter_q15(const int16_t *in, int16_t *out_time, int batch, const SaQ15Params &p,
+// `in` per in_kind: int16 samples [B,16384] (I16) or the same samples packed to 12 bits [B,24576] (P12: include/specan.h,
+// 16-byte aligned; unpacked where the kernels read them, every result that of the I16 form on the sign-extended samples).
+// The FFT takes P12 only with apply_window: a cascade's output, the only unwindowed input there is, is int16.
+hipError_t sa_launch_filter_q15(const void *in, SaInKind in_kind, int16_t *out_time, int batch, const SaQ15Params &p,
                                 const SaQ15Tables &t, hipStream_t stream, SaLaunchEv ev);
 // out per out_kind (SA_Q15_OUT_*): int16 [B,16384,2], float [B,16384] or sa_marker_q15 [B]
-hipError_t sa_launch_fft_q15(const int16_t *in_time, void *out, int batch, int out_kind, bool apply_window,
+hipError_t sa_launch_fft_q15(const void *in_time, SaInKind in_kind, void *out, int batch, int out_kind, bool apply_window,
                              const SaQ15Params &p, const SaQ15Tables &t, hipStream_t stream, SaLaunchEv ev);

@@ -419,9 +419,10 @@ static SaQ15Params q15_params(const sa_handle *h)
 }
 
 // sa_filter_q15 (`fft` false: window + integer cascade into `out`, out_kind unused) and sa_process_q15 / sa_process_q15_out
-// (`out` per out_kind, SA_Q15_OUT_*: the FFT launch's epilogue makes it); `fn` names the entry point
-static int process_q15(sa_handle *h, const char *fn, const int16_t *in, void *out, int batch, int out_kind, void *stream,
-                       bool fft)
+// (`out` per out_kind, SA_Q15_OUT_*: the FFT launch's epilogue makes it), on int16 samples or, the _p12 entry points, on
+// packed 12-bit samples (`kind`: I16 or P12); `fn` names the entry point
+static int process_q15(sa_handle *h, const char *fn, const void *in, SaInKind kind, void *out, int batch, int out_kind,
+                       void *stream, bool fft)
 {
     if (!h) return SA_EINVAL;
     if (batch < 0) return fail_at(h, SA_ESHAPE, fn, "negative batch");
@@ -430,6 +431,8 @@ static int process_q15(sa_handle *h, const char *fn, const int16_t *in, void *ou
     if (!in || !out) return fail_at(h, SA_EINVAL, fn, "NULL tensor");
     if (out_kind == SA_Q15_OUT_MARKER && ((uintptr_t)out & 15u) != 0)
         return fail_at(h, SA_EINVAL, fn, "SA_Q15_OUT_MARKER output must be 16-byte aligned");
+    if (kind == SaInKind::P12 && ((uintptr_t)in & 15u) != 0)       // the rule of sa_process_f32_p12; every frame is then aligned
+        return fail_at(h, SA_EINVAL, fn, "packed input must be 16-byte aligned");
     SA_HIP(h, hipSetDevice(h->device));
     const SaQ15Params p = q15_params(h);
     const bool staged = fft && p.filter != SA_FILTER_NONE;      // cascade into the slot's workspace, then the FFT
@@ -437,8 +440,8 @@ static int process_q15(sa_handle *h, const char *fn, const int16_t *in, void *ou
     { const int rc = begin_call(h, (hipStream_t)stream, staged ? sa_handle::kWorkQ15 : -1, batch, &c); if (rc != SA_OK) return rc; }
     const SaQ15Tables t = {h->d_rom, h->d_twq, h->d_twrec, h->marker_lo, h->marker_hi};
     if (!staged) {
-        SA_HIP(h, fft ? sa_launch_fft_q15(in, out, batch, out_kind, true, p, t, c.stream, {c.start, c.stop})
-                      : sa_launch_filter_q15(in, (int16_t *)out, batch, p, t, c.stream, {c.start, c.stop}));
+        SA_HIP(h, fft ? sa_launch_fft_q15(in, kind, out, batch, out_kind, true, p, t, c.stream, {c.start, c.stop})
+                      : sa_launch_filter_q15(in, kind, (int16_t *)out, batch, p, t, c.stream, {c.start, c.stop}));
         return end_call(h, c);
     }
     // The WIDE cascade does not gain from overlapped launches (tools/q15_overlap_modes.py, profiles/r4_q15_helper_waves.txt):
@@ -450,24 +453,35 @@ static int process_q15(sa_handle *h, const char *fn, const int16_t *in, void *ou
         if (prev.used) SA_HIP(h, hipStreamWaitEvent(c.stream, prev.done, 0));
     }
     int16_t *ws = (int16_t *)h->slot[c.slot].work[sa_handle::kWorkQ15].ptr;
-    SA_HIP(h, sa_launch_filter_q15(in, ws, batch, p, t, c.stream, {c.start, nullptr}));
-    SA_HIP(h, sa_launch_fft_q15(ws, out, batch, out_kind, false, p, t, c.stream, {nullptr, c.stop}));
+    // the packed form is read by the first launch alone: the workspace holds int16 samples whatever came in
+    SA_HIP(h, sa_launch_filter_q15(in, kind, ws, batch, p, t, c.stream, {c.start, nullptr}));
+    SA_HIP(h, sa_launch_fft_q15(ws, SaInKind::I16, out, batch, out_kind, false, p, t, c.stream, {nullptr, c.stop}));
     return end_call(h, c);
 }
 
 int sa_filter_q15(sa_handle *h, const int16_t *in, int16_t *out_time, int batch, void *stream)
 {
-    return process_q15(h, "sa_filter_q15", in, out_time, batch, SA_Q15_OUT_IQ, stream, false);
+    return process_q15(h, "sa_filter_q15", in, SaInKind::I16, out_time, batch, SA_Q15_OUT_IQ, stream, false);
 }
 
 int sa_process_q15(sa_handle *h, const int16_t *in, int16_t *out_iq, int batch, void *stream)
 {
-    return process_q15(h, "sa_process_q15", in, out_iq, batch, SA_Q15_OUT_IQ, stream, true);
+    return process_q15(h, "sa_process_q15", in, SaInKind::I16, out_iq, batch, SA_Q15_OUT_IQ, stream, true);
 }
 
 int sa_process_q15_out(sa_handle *h, const int16_t *in, void *out, int batch, int out_kind, void *stream)
 {
-    return process_q15(h, "sa_process_q15_out", in, out, batch, out_kind, stream, true);
+    return process_q15(h, "sa_process_q15_out", in, SaInKind::I16, out, batch, out_kind, stream, true);
+}
+
+int sa_process_q15_p12(sa_handle *h, const uint8_t *in, void *out, int batch, int out_kind, void *stream)
+{
+    return process_q15(h, "sa_process_q15_p12", in, SaInKind::P12, out, batch, out_kind, stream, true);
+}
+
+int sa_filter_q15_p12(sa_handle *h, const uint8_t *in, int16_t *out_time, int batch, void *stream)
+{
+    return process_q15(h, "sa_filter_q15_p12", in, SaInKind::P12, out_time, batch, SA_Q15_OUT_IQ, stream, false);
 }
 
 // sa_process_f32 (float frames), sa_process_f32_i16 (int16 samples times `scale`) and sa_process_f32_p12 (the same

@@ -4,7 +4,7 @@ Stands where the serial port / UDP socket of `UartReceiver` / `UdpReceiver` stan
 The host writes command bytes; the board answers with 65536-byte frames, raw on the UART or as 64
 datagram payloads of 1 index byte + 1024 data bytes on Ethernet (gui.py:48-50, imp/phy_rmii_if.vhd:173,322).
 Sample acquisition (XADC, imp/dsp_system_top.vhd:412-435) is replaced by a caller-supplied source of
-int16 frames.
+int16 frames, or of the same 12-bit samples packed two to three bytes.
 
 Sequencing follows imp/sequ2.vhd (command decode through the C ABI, which mirrors
 new/command_control.vhd and new/rx_filter_coeff.vhd):
@@ -35,9 +35,12 @@ import numpy as np
 import torch
 
 from . import frames
+from .abi import SA_P12_FRAME_BYTES
 from .chain import ETHERNET_MODE_CMD, UART_MODE_CMD, SpectrumChain
 
-SampleSource = Callable[[int], np.ndarray]     # n_frames -> [n_frames, 16384] int16 (12-bit values)
+# n_frames -> [n_frames, 16384] int16 (12-bit values), or the same samples packed to 12 bits: [n_frames, 24576] uint8
+# (include/specan.h, "p12"; what ingest.pack12 and a packed FrameCutter deliver)
+SampleSource = Callable[[int], np.ndarray]
 
 ETHERNET_FPS_LIMIT = 30.0                      # gui.py:53
 FPGA_SRC_PORT, HOST_DST_PORT = 5005, 6006      # imp/head_data.mif:27-38, gui.py:20-22
@@ -107,7 +110,11 @@ class VirtualFpga:
         if self._pending_generation != self.chain.control_generation:
             self._pending.clear()
         if not self._pending:
-            x = np.ascontiguousarray(self.source(self.batch), dtype=np.int16).reshape(-1, frames.FFT_SIZE)
+            x = np.asarray(self.source(self.batch))
+            if x.dtype == np.uint8:                            # packed frames go to the chain as they are
+                x = np.ascontiguousarray(x).reshape(-1, SA_P12_FRAME_BYTES)
+            else:
+                x = np.ascontiguousarray(x, dtype=np.int16).reshape(-1, frames.FFT_SIZE)
             iq = self.chain.process_q15(torch.from_numpy(x).to(self.chain.device))
             self._pending.extend(self.chain.frames_bytes(iq))
             self._pending_generation = self.chain.control_generation

@@ -325,6 +325,26 @@ int sa_process_f32_i16(sa_handle *h, const int16_t *in, float scale, void *out, 
 int sa_process_f32_p12(sa_handle *h, const uint8_t *in /* [B,24576] device */, float scale, void *out, int batch,
                        int out_kind, void *stream);
 
+/* The Q15 path fed with packed 12-bit samples (build extension; ABI version 4, added compatibly).  The integer chain is the
+ * FPGA-exact mode, and its real input is exactly that 12-bit stream: imp/dsp_system_top.vhd:435 sign-extends
+ * adc_out(15 downto 4) into the 16-bit sample the window takes (new/hann8192.vhd:36-39).  `in` is the p12 format defined
+ * above, [B,24576] uint8, 16-byte aligned (SA_EINVAL otherwise: the rule of sa_process_f32_p12).
+ *   sa_process_q15_p12: `out` per out_kind (SA_Q15_OUT_IQ, SA_Q15_OUT_MAG or SA_Q15_OUT_MARKER) -- the results of
+ *     sa_process_q15_out() (imp/sequ2.vhd:153 frames, gui.py:250-260 magnitudes, gui.py:294-305 / 691-712 markers) on
+ *     sa_unpack_samples_p12(in), bit for bit;
+ *   sa_filter_q15_p12: the FFT input stream (fft_in16 of new/command_control.vhd:90-123) -- the results of sa_filter_q15()
+ *     on the same samples, bit for bit.
+ * The samples are unpacked inside the kernels that read them (the window kernel, the cascades' staging waves, stage 0 of
+ * the FFT in filter mode 0xB1): no unpack pass, no workspace of their own, no extra launch, 24 KiB of input per frame
+ * instead of 32, and no byte outside [in, in + batch * 24576) is read.  Everything said of sa_process_q15_out() holds: all
+ * four filter modes (0xA2 with no sections included), both window modes, custom ROMs, every overlap depth (the ordering of
+ * the wide cascade at depth 2 included), launch timing, hipGraph capture once sa_reserve() has sized the workspace, and its
+ * argument checks, made before any call state changes: SA_EINVAL for an unknown kind, a NULL tensor, a marker `out` or an
+ * `in` that is not 16-byte aligned, SA_ESHAPE for a negative batch; nothing is launched then. */
+int sa_process_q15_p12(sa_handle *h, const uint8_t *in /* [B,24576] device */, void *out, int batch, int out_kind,
+                       void *stream);
+int sa_filter_q15_p12(sa_handle *h, const uint8_t *in /* [B,24576] device */, int16_t *out_time, int batch, void *stream);
+
 /* Host helpers of the p12 format: pure functions, no handle, no GPU.  n is the number of SAMPLES and must be even
  * (SA_EINVAL otherwise); `packed` holds 3n/2 bytes.  Packing a sample outside [-2048, 2047] is SA_EINVAL and nothing
  * is written.  Unpacking sign-extends to int16. */

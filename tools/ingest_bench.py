@@ -10,7 +10,9 @@ their own streams, which shows the copy of batch k+1 running under the kernels o
 conversion pass on the device, the PCIe volume of the Q15 path.
 --packed (implies --float): the same samples packed to 12 bits (sa_process_f32_p12, 24576 bytes per frame instead of
 32768), packed once up front as the int16 batches are generated up front; the GB/s figures count the packed bytes.
-usage: ingest_bench.py [batch_frames] [n_batches] [mode] [--events] [--float] [--packed]"""
+--packed-q15: the packed feeder into the INTEGER chain (sa_process_q15_p12; without --float / --packed, which keep their
+meaning and win when given as well): the bit-exact frames from 24576 input bytes per frame.
+usage: ingest_bench.py [batch_frames] [n_batches] [mode] [--events] [--float] [--packed] [--packed-q15]"""
 import os
 import sys
 import time
@@ -32,6 +34,7 @@ NB = int(sys.argv[2]) if len(sys.argv) > 2 else 32
 mode = int(sys.argv[3], 0) if len(sys.argv) > 3 and not sys.argv[3].startswith("--") else 0xB1
 PACKED = "--packed" in sys.argv
 FLOAT = "--float" in sys.argv or PACKED
+PACKED = PACKED or ("--packed-q15" in sys.argv and not FLOAT)              # from here on: the input form alone
 ROW, FRAME_BYTES = (3 * N // 2, 3 * N // 2) if PACKED else (N, 2 * N)      # elements and bytes of an input frame
 IN_DT = torch.uint8 if PACKED else torch.int16
 
@@ -53,7 +56,7 @@ def process(xd, o):
     if FLOAT:
         ch.process_f32(xd, out=o)          # int16 tensor in: sa_process_f32_i16; uint8: sa_process_f32_p12
     else:
-        ch.process_q15(xd, out=o)
+        ch.process_q15(xd, out=o)          # int16 tensor in: sa_process_q15; uint8: sa_process_q15_p12
 
 
 def run(batches):
@@ -96,7 +99,7 @@ h2d = pure_h2d()
 kfps = pure_kernels()
 print(f"batch {B} frames x {NB} batches, filter mode 0x{mode:02X}")
 print(f"  pinned host -> device copy alone      : {h2d / 1e9:6.1f} GB/s = {h2d / FRAME_BYTES / 1e6:5.2f} M frames/s   (PCIe Gen5 x16 spec 63 GB/s = {63e9 / FRAME_BYTES / 1e6:4.2f} M frames/s)")
-print(f"  {('float chain from packed 12-bit' if PACKED else 'float chain from int16') if FLOAT else 'Q15 kernels'} alone, inputs resident: {kfps / 1e6:5.2f} M frames/s")
+print(f"  {('float chain from packed 12-bit' if PACKED else 'float chain from int16') if FLOAT else 'Q15 kernels from packed 12-bit' if PACKED else 'Q15 kernels'} alone, inputs resident: {kfps / 1e6:5.2f} M frames/s")
 print(f"  feeder end to end (numpy -> pinned -> device -> path): {NB * B / dt / 1e6:5.2f} M frames/s = {NB * B * FRAME_BYTES / dt / 1e9:5.1f} GB/s of samples ({FRAME_BYTES} bytes per frame)")
 # the host copy into the staging buffer is part of the feeder; how much of the time is it?
 t0 = time.perf_counter()
