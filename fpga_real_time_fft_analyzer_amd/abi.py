@@ -1,8 +1,8 @@
 """ctypes binding of ``libspecan_hip.so`` (the C ABI declared in ``include/specan.h``).
 
 This is the only place the shared library is loaded.  There is no CPU fallback: if the
-library is missing the import of any compute entry point raises, and ``sa_create`` itself
-fails when no HIP device is usable.
+library is missing the import of any compute entry point raises, and creating a handle
+itself fails when no HIP device is usable.
 """
 from __future__ import annotations
 
@@ -52,6 +52,58 @@ def build(verbose: bool = False) -> str:
     return LIB_PATH
 
 
+H = C.c_void_p
+_P = C.POINTER
+_INT = C.c_int
+# the one list of entry points: name -> (restype, argtypes), name for name the declarations of include/specan.h
+# (tests/test_abi_symbols.py holds the key set against the header)
+SIGNATURES = {
+    "sa_create": (_INT, [_INT, _P(H)]),
+    "sa_destroy": (_INT, [H]),
+    "sa_abi_version": (_INT, []),
+    "sa_last_error": (C.c_char_p, [H]),
+    "sa_reserve": (_INT, [H, _INT]),
+    "sa_set_overlap": (_INT, [H, _INT]),
+    "sa_get_overlap": (_INT, [H, _P(_INT)]),
+    "sa_debug_overlap_streams": (_INT, [H, C.c_void_p, _P(_INT)]),
+    "sa_flush": (_INT, [H, C.c_void_p]),
+    "sa_set_profiling": (_INT, [H, _INT]),
+    "sa_profile_read": (_INT, [H, _P(C.c_float), _INT]),
+    "sa_set_filter_mode": (_INT, [H, C.c_uint8]),
+    "sa_get_filter_mode": (_INT, [H, _P(C.c_uint8)]),
+    "sa_load_coeffs_q7": (_INT, [H, _P(C.c_int8)]),
+    "sa_get_coeffs_q7": (_INT, [H, _P(C.c_int8)]),
+    "sa_feed_command_bytes": (_INT, [H, _P(C.c_uint8), C.c_size_t, _P(_INT)]),
+    "sa_feed_command_bytes_ex": (_INT, [H, _P(C.c_uint8), C.c_size_t, _P(CmdEvents)]),
+    "sa_get_transport": (_INT, [H, _P(C.c_uint8)]),
+    "sa_load_sos_f32": (_INT, [H, _P(C.c_float), _INT]),
+    "sa_load_sos_f64": (_INT, [H, _P(C.c_double), _INT]),
+    "sa_load_sos_q14": (_INT, [H, _P(C.c_int16), _INT]),
+    "sa_set_window_q15": (_INT, [H, _P(C.c_int16)]),
+    "sa_set_window_f32": (_INT, [H, _P(C.c_float)]),
+    "sa_set_window_mode_q15": (_INT, [H, _INT]),
+    "sa_get_window_q15": (_INT, [H, _P(C.c_int16)]),
+    "sa_process_q15": (_INT, [H, C.c_void_p, C.c_void_p, _INT, C.c_void_p]),
+    "sa_process_q15_out": (_INT, [H, C.c_void_p, C.c_void_p, _INT, _INT, C.c_void_p]),
+    "sa_filter_q15": (_INT, [H, C.c_void_p, C.c_void_p, _INT, C.c_void_p]),
+    "sa_process_q15_p12": (_INT, [H, C.c_void_p, C.c_void_p, _INT, _INT, C.c_void_p]),
+    "sa_filter_q15_p12": (_INT, [H, C.c_void_p, C.c_void_p, _INT, C.c_void_p]),
+    "sa_process_f32": (_INT, [H, C.c_void_p, C.c_void_p, _INT, _INT, C.c_void_p]),
+    "sa_process_f32_i16": (_INT, [H, C.c_void_p, C.c_float, C.c_void_p, _INT, _INT, C.c_void_p]),
+    "sa_process_f32_p12": (_INT, [H, C.c_void_p, C.c_float, C.c_void_p, _INT, _INT, C.c_void_p]),
+    "sa_pack_samples_p12": (_INT, [_P(C.c_int16), C.c_size_t, _P(C.c_uint8)]),
+    "sa_unpack_samples_p12": (_INT, [_P(C.c_uint8), C.c_size_t, _P(C.c_int16)]),
+    "sa_pack_frame": (_INT, [_P(C.c_int16), _P(C.c_uint8)]),
+    "sa_debug_iir_plan_f32": (_INT, [H, _P(C.c_float), _INT]),
+    "sa_iir_plan_from_sos": (_INT, [_P(C.c_double), _INT, _P(C.c_float), _INT]),
+    "sa_set_precision": (_INT, [H, _INT]),
+    "sa_get_precision": (_INT, [H, _P(_INT)]),
+    "sa_debug_iir_plan_f64": (_INT, [H, _P(C.c_double), _INT]),
+    "sa_iir_plan_from_sos_f64": (_INT, [_P(C.c_double), _INT, _P(C.c_double), _INT]),
+    "sa_set_marker_range": (_INT, [H, _INT, _INT]),
+    "sa_get_marker_range": (_INT, [H, _P(_INT), _P(_INT)]),
+}
+
 _lib = None
 
 
@@ -73,62 +125,8 @@ def lib() -> C.CDLL:
     except ImportError:
         pass
     L = C.CDLL(LIB_PATH)
-    H = C.c_void_p
-    L.sa_create.argtypes = [C.c_int, C.POINTER(H)]
-    L.sa_destroy.argtypes = [H]
-    L.sa_abi_version.argtypes = []
-    L.sa_last_error.argtypes = [H]
-    L.sa_last_error.restype = C.c_char_p
-    L.sa_reserve.argtypes = [H, C.c_int]
-    L.sa_set_overlap.argtypes = [H, C.c_int]
-    L.sa_get_overlap.argtypes = [H, C.POINTER(C.c_int)]
-    L.sa_debug_overlap_streams.argtypes = [H, C.c_void_p, C.POINTER(C.c_int)]
-    L.sa_flush.argtypes = [H, C.c_void_p]
-    L.sa_set_profiling.argtypes = [H, C.c_int]
-    L.sa_profile_read.argtypes = [H, C.POINTER(C.c_float), C.c_int]
-    L.sa_set_filter_mode.argtypes = [H, C.c_uint8]
-    L.sa_get_filter_mode.argtypes = [H, C.POINTER(C.c_uint8)]
-    L.sa_load_coeffs_q7.argtypes = [H, C.POINTER(C.c_int8)]
-    L.sa_get_coeffs_q7.argtypes = [H, C.POINTER(C.c_int8)]
-    L.sa_feed_command_bytes.argtypes = [H, C.POINTER(C.c_uint8), C.c_size_t, C.POINTER(C.c_int)]
-    L.sa_feed_command_bytes_ex.argtypes = [H, C.POINTER(C.c_uint8), C.c_size_t, C.POINTER(CmdEvents)]
-    L.sa_get_transport.argtypes = [H, C.POINTER(C.c_uint8)]
-    L.sa_load_sos_f32.argtypes = [H, C.POINTER(C.c_float), C.c_int]
-    L.sa_load_sos_f64.argtypes = [H, C.POINTER(C.c_double), C.c_int]
-    L.sa_load_sos_q14.argtypes = [H, C.POINTER(C.c_int16), C.c_int]
-    L.sa_set_window_q15.argtypes = [H, C.POINTER(C.c_int16)]
-    L.sa_set_window_f32.argtypes = [H, C.POINTER(C.c_float)]
-    L.sa_set_window_mode_q15.argtypes = [H, C.c_int]
-    L.sa_get_window_q15.argtypes = [H, C.POINTER(C.c_int16)]
-    L.sa_process_q15.argtypes = [H, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
-    L.sa_process_q15_out.argtypes = [H, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
-    L.sa_filter_q15.argtypes = [H, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
-    L.sa_process_q15_p12.argtypes = [H, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
-    L.sa_filter_q15_p12.argtypes = [H, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
-    L.sa_process_f32.argtypes = [H, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
-    L.sa_process_f32_i16.argtypes = [H, C.c_void_p, C.c_float, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
-    L.sa_process_f32_p12.argtypes = [H, C.c_void_p, C.c_float, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
-    L.sa_pack_samples_p12.argtypes = [C.POINTER(C.c_int16), C.c_size_t, C.POINTER(C.c_uint8)]
-    L.sa_unpack_samples_p12.argtypes = [C.POINTER(C.c_uint8), C.c_size_t, C.POINTER(C.c_int16)]
-    L.sa_pack_frame.argtypes = [C.POINTER(C.c_int16), C.POINTER(C.c_uint8)]
-    L.sa_debug_iir_plan_f32.argtypes = [H, C.POINTER(C.c_float), C.c_int]
-    L.sa_iir_plan_from_sos.argtypes = [C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_float), C.c_int]
-    L.sa_set_precision.argtypes = [H, C.c_int]
-    L.sa_get_precision.argtypes = [H, C.POINTER(C.c_int)]
-    L.sa_debug_iir_plan_f64.argtypes = [H, C.POINTER(C.c_double), C.c_int]
-    L.sa_iir_plan_from_sos_f64.argtypes = [C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_double), C.c_int]
-    L.sa_set_marker_range.argtypes = [H, C.c_int, C.c_int]
-    L.sa_get_marker_range.argtypes = [H, C.POINTER(C.c_int), C.POINTER(C.c_int)]
-    for name in ("sa_create", "sa_destroy", "sa_abi_version", "sa_reserve", "sa_set_overlap", "sa_get_overlap",
-                 "sa_debug_overlap_streams", "sa_flush", "sa_set_profiling", "sa_profile_read", "sa_set_filter_mode",
-                 "sa_get_filter_mode", "sa_load_coeffs_q7", "sa_get_coeffs_q7", "sa_feed_command_bytes",
-                 "sa_feed_command_bytes_ex", "sa_get_transport",
-                 "sa_load_sos_f32", "sa_load_sos_f64", "sa_load_sos_q14", "sa_set_window_q15",
-                 "sa_set_window_f32", "sa_set_window_mode_q15", "sa_get_window_q15", "sa_process_q15", "sa_process_q15_out",
-                 "sa_filter_q15", "sa_process_q15_p12", "sa_filter_q15_p12", "sa_process_f32", "sa_process_f32_i16", "sa_process_f32_p12", "sa_pack_samples_p12",
-                 "sa_unpack_samples_p12", "sa_pack_frame", "sa_debug_iir_plan_f32",
-                 "sa_iir_plan_from_sos", "sa_set_precision", "sa_get_precision", "sa_debug_iir_plan_f64",
-                 "sa_iir_plan_from_sos_f64", "sa_set_marker_range", "sa_get_marker_range"):
-        getattr(L, name).restype = C.c_int
+    for name, (restype, argtypes) in SIGNATURES.items():
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = restype, argtypes
     _lib = L
     return L

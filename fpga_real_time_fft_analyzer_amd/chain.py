@@ -10,7 +10,7 @@ from __future__ import annotations
 
 import collections
 import ctypes as C
-from typing import Optional, Sequence
+from typing import NamedTuple, Optional, Sequence
 
 import numpy as np
 import torch
@@ -37,10 +37,73 @@ SAMPLES_PER_FRAME = 16384       # gui.py:43
 FFT_SIZE = 16384                # gui.py:44
 FS_HZ = 1_000_000.0             # gui.py:45
 
-_OUT_KINDS = {"mag_full": SA_OUT_MAG_FULL, "mag_half": SA_OUT_MAG_HALF, "spec_half": SA_OUT_SPEC_HALF,
-              "time": SA_OUT_TIME, "marker": SA_OUT_MARKER}
-_Q15_OUT_KINDS = {"iq": SA_Q15_OUT_IQ, "mag": SA_Q15_OUT_MAG, "marker": SA_Q15_OUT_MARKER}
 _PRECISIONS = {"f32": SA_PRECISION_F32, "f64": SA_PRECISION_F64_STATE}
+
+
+# C entry point -> (takes scale, takes out_kind): the argument lists of include/specan.h
+_ARGS = {"sa_process_f32": (False, True), "sa_process_f32_i16": (True, True), "sa_process_f32_p12": (True, True),
+         "sa_process_q15": (False, False), "sa_process_q15_out": (False, True), "sa_process_q15_p12": (False, True),
+         "sa_filter_q15": (False, False), "sa_filter_q15_p12": (False, False)}
+
+
+class _Chain(NamedTuple):
+    """What a process call has to know about one chain.  A new input form is one row of ``inputs``, a new output kind one
+    row of ``outputs``."""
+    outputs: dict   # out_kind -> (C code, shape of one frame's output, torch dtype)
+    inputs: dict    # torch dtype of x -> _form(...); the first dtype stands in the message for an x that is no tensor of a
+                    # listed dtype
+
+    def output(self, out_kind) -> tuple:
+        if out_kind not in self.outputs:
+            raise SpecanError(abi.SA_EINVAL, f"out_kind must be one of {sorted(self.outputs)}")
+        return self.outputs[out_kind]
+
+
+def _form(row: int, outputs: dict, name: str, **other) -> tuple:
+    """One input form: (row length of x, {out_kind: (C entry point, takes scale, takes out_kind)}).  The entry point is
+    ``name``, or what ``other`` names for that out_kind."""
+    return row, {k: (other.get(k, name),) + _ARGS[other.get(k, name)] for k in outputs}
+
+
+_HALF = SA_N // 2 + 1
+_FLOAT_OUT = {"mag_full": (SA_OUT_MAG_FULL, (SA_N,), torch.float32),
+              "mag_half": (SA_OUT_MAG_HALF, (_HALF,), torch.float32),
+              "spec_half": (SA_OUT_SPEC_HALF, (_HALF,), torch.complex64),
+              "time": (SA_OUT_TIME, (SA_N,), torch.float32),
+              "marker": (SA_OUT_MARKER, (4,), torch.int32)}
+FLOAT_CHAIN = _Chain(_FLOAT_OUT, {torch.float32: _form(SA_N, _FLOAT_OUT, "sa_process_f32"),
+                                  torch.int16: _form(SA_N, _FLOAT_OUT, "sa_process_f32_i16"),
+                                  torch.uint8: _form(SA_P12_FRAME_BYTES, _FLOAT_OUT, "sa_process_f32_p12")})
+_Q15_OUT = {"iq": (SA_Q15_OUT_IQ, (SA_N, 2), torch.int16),
+            "mag": (SA_Q15_OUT_MAG, (SA_N,), torch.float32),
+            "marker": (SA_Q15_OUT_MARKER, (4,), torch.int32)}
+Q15_CHAIN = _Chain(_Q15_OUT, {torch.int16: _form(SA_N, _Q15_OUT, "sa_process_q15_out", iq="sa_process_q15"),
+                              torch.uint8: _form(SA_P12_FRAME_BYTES, _Q15_OUT, "sa_process_q15_p12")})
+# the Q15 chain without its FFT (filter_q15): one output, which has no name
+_WINDOW_OUT = {None: (SA_Q15_OUT_IQ, (SA_N,), torch.int16)}
+Q15_WINDOW_CHAIN = _Chain(_WINDOW_OUT, {torch.int16: _form(SA_N, _WINDOW_OUT, "sa_filter_q15"),
+                                        torch.uint8: _form(SA_P12_FRAME_BYTES, _WINDOW_OUT, "sa_filter_q15_p12")})
+
+
+def output_spec(chain: _Chain, out_kind: Optional[str], B: int) -> tuple:
+    """``(shape, dtype)`` of the output of a process call on ``B`` frames (no handle, no GPU)."""
+    _, frame, dtype = chain.output(out_kind)
+    return (B,) + frame, dtype
+
+
+def _sized_export(fn, head: tuple, dtype, what: str) -> np.ndarray:
+    """The exports that are called twice: ``fn(*head, NULL, 0)`` returns the number of elements (negative: an error code),
+    ``fn(*head, out, n)`` fills them."""
+    n = fn(*head, None, 0)
+    if n < 0:
+        raise SpecanError(n, what)
+    out = np.zeros(n, dtype)
+    fn(*head, out.ctypes.data_as(fn.argtypes[-2]), n)
+    return out
+
+
+def _command_buffer(data: bytes):
+    return (C.c_uint8 * len(data)).from_buffer_copy(bytes(data)) if len(data) else (C.c_uint8 * 1)()
 
 
 class SpectrumChain:
@@ -113,15 +176,33 @@ class SpectrumChain:
     def _stream(self) -> int:
         return torch.cuda.current_stream(self.device).cuda_stream
 
-    def _check_in(self, x: torch.Tensor, dtype: torch.dtype) -> int:
+    def _check_in(self, x: torch.Tensor, dtype: torch.dtype, row: int) -> int:
         if not isinstance(x, torch.Tensor) or x.dtype != dtype:
             raise SpecanError(abi.SA_EINVAL, f"input must be a {dtype} tensor")
         if x.device != self.device:
             raise SpecanError(abi.SA_EINVAL, f"input must live on {self.device}")
-        row = SA_P12_FRAME_BYTES if dtype == torch.uint8 else SA_N         # uint8: packed 12-bit samples
         if x.dim() != 2 or x.shape[1] != row or not x.is_contiguous():
             raise SpecanError(abi.SA_ESHAPE, f"input must be a contiguous [B, {row}] tensor")
         return x.shape[0]
+
+    def _process(self, chain: _Chain, x, out, out_kind, scale=None):
+        """Every process call: ``x`` by its dtype to the chain's entry point for it, into ``out`` (allocated when None)."""
+        code, frame, dt = chain.output(out_kind)
+        dtype = x.dtype if isinstance(x, torch.Tensor) and x.dtype in chain.inputs else next(iter(chain.inputs))
+        row, calls = chain.inputs[dtype]
+        B = self._check_in(x, dtype, row)
+        shape = (B,) + frame
+        if out is None:
+            out = torch.empty(shape, dtype=dt, device=self.device)
+        elif tuple(out.shape) != shape or out.dtype != dt or out.device != self.device or not out.is_contiguous():
+            raise SpecanError(abi.SA_ESHAPE, f"out must be a contiguous {dt} tensor of shape {shape}")
+        name, takes_scale, takes_kind = calls[out_kind]
+        args = (self._h, x.data_ptr()) + ((float(scale),) if takes_scale else ()) + (out.data_ptr(), B)
+        if takes_kind:
+            args += (code,)
+        self._check(getattr(self._lib, name)(*args, self._stream()))
+        self._lend(x, out)
+        return out
 
     # ------------------------------------------------------------------ control plane
     def set_filter_mode(self, cmd: int):
@@ -155,16 +236,14 @@ class SpectrumChain:
     def feed_command_bytes(self, data: bytes) -> int:
         """Push raw UART bytes through the RX state machine; returns the number of UART read requests
         (0xA5, imp/sequ2.vhd:216) seen outside coefficient uploads."""
-        buf = (C.c_uint8 * len(data)).from_buffer_copy(bytes(data)) if len(data) else (C.c_uint8 * 1)()
         n = C.c_int(0)
-        self._ctl(self._lib.sa_feed_command_bytes(self._h, buf, len(data), C.byref(n)))
+        self._ctl(self._lib.sa_feed_command_bytes(self._h, _command_buffer(data), len(data), C.byref(n)))
         return n.value
 
     def feed_command_bytes_ex(self, data: bytes) -> "abi.CmdEvents":
         """The same, reporting everything a transport shim needs (sa_cmd_events of include/specan.h)."""
-        buf = (C.c_uint8 * len(data)).from_buffer_copy(bytes(data)) if len(data) else (C.c_uint8 * 1)()
         ev = abi.CmdEvents()
-        self._check(self._lib.sa_feed_command_bytes_ex(self._h, buf, len(data), C.byref(ev)))
+        self._check(self._lib.sa_feed_command_bytes_ex(self._h, _command_buffer(data), len(data), C.byref(ev)))
         if ev.control_changed:
             self.control_generation += 1
         return ev
@@ -270,10 +349,7 @@ class SpectrumChain:
         return [float(buf[i]) for i in range(got)]
 
     def iir_plan(self) -> np.ndarray:
-        n = self._lib.sa_debug_iir_plan_f32(self._h, None, 0)
-        out = np.zeros(n, np.float32)
-        self._lib.sa_debug_iir_plan_f32(self._h, out.ctypes.data_as(C.POINTER(C.c_float)), n)
-        return out
+        return _sized_export(self._lib.sa_debug_iir_plan_f32, (self._h,), np.float32, "sa_debug_iir_plan_f32")
 
     def set_precision(self, precision: str):
         """'f32' (the default) or 'f64': window, inter-section signal and cascade of the float path in float64
@@ -290,12 +366,7 @@ class SpectrumChain:
 
     def iir_plan_f64(self) -> np.ndarray:
         """The float64 plan the handle would launch in its current filter mode (sa_debug_iir_plan_f64)."""
-        n = self._lib.sa_debug_iir_plan_f64(self._h, None, 0)
-        if n < 0:
-            self._check(n)
-        out = np.zeros(n, np.float64)
-        self._lib.sa_debug_iir_plan_f64(self._h, out.ctypes.data_as(C.POINTER(C.c_double)), n)
-        return out
+        return _sized_export(self._lib.sa_debug_iir_plan_f64, (self._h,), np.float64, "sa_debug_iir_plan_f64")
 
     def set_marker_range(self, lo: int, hi: int):
         """The full-spectrum bins [lo, hi) that ``out_kind='marker'`` covers (include/specan.h, sa_set_marker_range):
@@ -324,34 +395,7 @@ class SpectrumChain:
         "p12"; ingest.pack12 is the host packer): it goes to sa_process_f32_p12, is unpacked in the stage-in and gives
         the results of the int16 tensor of the same samples bit for bit, from three quarters of the input bytes.  Its
         data pointer must be 16-byte aligned (any tensor torch allocates is, and so is every whole-frame slice of one)."""
-        if out_kind not in _OUT_KINDS:
-            raise SpecanError(abi.SA_EINVAL, f"out_kind must be one of {sorted(_OUT_KINDS)}")
-        from_i16 = x.dtype == torch.int16
-        from_p12 = x.dtype == torch.uint8
-        B = self._check_in(x, torch.int16 if from_i16 else torch.uint8 if from_p12 else torch.float32)
-        if out_kind in ("mag_full", "time"):
-            shape, dt = (B, SA_N), torch.float32
-        elif out_kind == "mag_half":
-            shape, dt = (B, SA_N // 2 + 1), torch.float32
-        elif out_kind == "marker":
-            shape, dt = (B, 4), torch.int32
-        else:
-            shape, dt = (B, SA_N // 2 + 1), torch.complex64
-        if out is None:
-            out = torch.empty(shape, dtype=dt, device=self.device)
-        elif tuple(out.shape) != shape or out.dtype != dt or out.device != self.device or not out.is_contiguous():
-            raise SpecanError(abi.SA_ESHAPE, f"out must be a contiguous {dt} tensor of shape {shape}")
-        if from_p12:
-            self._check(self._lib.sa_process_f32_p12(self._h, x.data_ptr(), float(scale), out.data_ptr(), B,
-                                                     _OUT_KINDS[out_kind], self._stream()))
-        elif from_i16:
-            self._check(self._lib.sa_process_f32_i16(self._h, x.data_ptr(), float(scale), out.data_ptr(), B,
-                                                     _OUT_KINDS[out_kind], self._stream()))
-        else:
-            self._check(self._lib.sa_process_f32(self._h, x.data_ptr(), out.data_ptr(), B, _OUT_KINDS[out_kind],
-                                                 self._stream()))
-        self._lend(x, out)
-        return out
+        return self._process(FLOAT_CHAIN, x, out, out_kind, scale)
 
     def markers(self, x: torch.Tensor, out: Optional[torch.Tensor] = None, scale: float = 1.0 / 2048.0):
         """Peak search and band power over the marker range, per frame: ``(peak_mag float32 [B], peak_bin int32 [B],
@@ -372,26 +416,7 @@ class SpectrumChain:
         host packer): it goes to sa_process_q15_p12, is unpacked inside the kernels that read the samples and gives the
         results of the int16 tensor of the same samples bit for bit, from three quarters of the input bytes.  Its data
         pointer must be 16-byte aligned (any tensor torch allocates is, and so is every whole-frame slice of one)."""
-        if out_kind not in _Q15_OUT_KINDS:
-            raise SpecanError(abi.SA_EINVAL, f"out_kind must be one of {sorted(_Q15_OUT_KINDS)}")
-        from_p12 = isinstance(x, torch.Tensor) and x.dtype == torch.uint8
-        B = self._check_in(x, torch.uint8 if from_p12 else torch.int16)
-        shape, dt = {"iq": ((B, SA_N, 2), torch.int16), "mag": ((B, SA_N), torch.float32),
-                     "marker": ((B, 4), torch.int32)}[out_kind]
-        if out is None:
-            out = torch.empty(shape, dtype=dt, device=self.device)
-        elif tuple(out.shape) != shape or out.dtype != dt or out.device != self.device or not out.is_contiguous():
-            raise SpecanError(abi.SA_ESHAPE, f"out must be a contiguous {dt} tensor of shape {shape}")
-        if from_p12:
-            self._check(self._lib.sa_process_q15_p12(self._h, x.data_ptr(), out.data_ptr(), B, _Q15_OUT_KINDS[out_kind],
-                                                     self._stream()))
-        elif out_kind == "iq":
-            self._check(self._lib.sa_process_q15(self._h, x.data_ptr(), out.data_ptr(), B, self._stream()))
-        else:
-            self._check(self._lib.sa_process_q15_out(self._h, x.data_ptr(), out.data_ptr(), B, _Q15_OUT_KINDS[out_kind],
-                                                     self._stream()))
-        self._lend(x, out)
-        return out
+        return self._process(Q15_CHAIN, x, out, out_kind)
 
     def markers_q15(self, x: torch.Tensor, out: Optional[torch.Tensor] = None):
         """Peak search and band power of the integer chain's frames over the marker range: ``(peak_mag float32 [B],
@@ -405,16 +430,7 @@ class SpectrumChain:
     def filter_q15(self, x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Window (+ integer IIR) only: the FFT input stream, [B,16384] int16.  ``x`` is [B,16384] int16 or the same
         samples packed, [B,24576] uint8 (sa_filter_q15_p12), as for :meth:`process_q15`."""
-        from_p12 = isinstance(x, torch.Tensor) and x.dtype == torch.uint8
-        B = self._check_in(x, torch.uint8 if from_p12 else torch.int16)
-        if out is None:
-            out = torch.empty((B, SA_N), dtype=torch.int16, device=self.device)
-        elif tuple(out.shape) != (B, SA_N) or out.dtype != torch.int16 or out.device != self.device or not out.is_contiguous():
-            raise SpecanError(abi.SA_ESHAPE, "out must be a contiguous int16 [B,16384] tensor")
-        fn = self._lib.sa_filter_q15_p12 if from_p12 else self._lib.sa_filter_q15
-        self._check(fn(self._h, x.data_ptr(), out.data_ptr(), B, self._stream()))
-        self._lend(x, out)
-        return out
+        return self._process(Q15_WINDOW_CHAIN, x, out, None)
 
     def frames_bytes(self, iq: torch.Tensor) -> list[bytes]:
         """Device IQ tensor -> list of 65536-byte frames exactly as sequ2 emits them.  In overlap mode the current
@@ -427,28 +443,16 @@ class SpectrumChain:
 
 def iir_plan_from_sos(sos) -> np.ndarray:
     """Host-only: the float IIR plan (no GPU needed); see include/specan.h sa_iir_plan_from_sos."""
-    L = abi.lib()
     s = np.ascontiguousarray(np.asarray(sos, np.float64).reshape(-1, 6))
-    n = L.sa_iir_plan_from_sos(s.ctypes.data_as(C.POINTER(C.c_double)), s.shape[0], None, 0)
-    if n < 0:
-        raise SpecanError(n, "sa_iir_plan_from_sos: bad SOS")
-    out = np.zeros(n, np.float32)
-    L.sa_iir_plan_from_sos(s.ctypes.data_as(C.POINTER(C.c_double)), s.shape[0],
-                           out.ctypes.data_as(C.POINTER(C.c_float)), n)
-    return out
+    return _sized_export(abi.lib().sa_iir_plan_from_sos, (s.ctypes.data_as(C.POINTER(C.c_double)), s.shape[0]), np.float32,
+                         "sa_iir_plan_from_sos: bad SOS")
 
 
 def iir_plan_f64_from_sos(sos) -> np.ndarray:
     """Host-only: the float64-state plan (no GPU needed); see include/specan.h sa_iir_plan_from_sos_f64."""
-    L = abi.lib()
     s = np.ascontiguousarray(np.asarray(sos, np.float64).reshape(-1, 6))
-    n = L.sa_iir_plan_from_sos_f64(s.ctypes.data_as(C.POINTER(C.c_double)), s.shape[0], None, 0)
-    if n < 0:
-        raise SpecanError(n, "sa_iir_plan_from_sos_f64: bad SOS")
-    out = np.zeros(n, np.float64)
-    L.sa_iir_plan_from_sos_f64(s.ctypes.data_as(C.POINTER(C.c_double)), s.shape[0],
-                               out.ctypes.data_as(C.POINTER(C.c_double)), n)
-    return out
+    return _sized_export(abi.lib().sa_iir_plan_from_sos_f64, (s.ctypes.data_as(C.POINTER(C.c_double)), s.shape[0]), np.float64,
+                         "sa_iir_plan_from_sos_f64: bad SOS")
 
 
 def pack_frame(iq_host: np.ndarray) -> bytes:

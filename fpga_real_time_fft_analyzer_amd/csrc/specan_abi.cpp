@@ -418,21 +418,38 @@ static SaQ15Params q15_params(const sa_handle *h)
     return p;
 }
 
+// The argument checks of process_q15 and process_float, made before anything else; callers of the ABI see their order.
+// The output kinds of both chains run from 0 to `marker`, the marker records (`marker_name` in the message).
+// `scale_finite`: what process_float found of its scale, which is refused between the kind and the empty batch (process_q15
+// has no scale: true).  An empty batch returns SA_OK here, and the caller returns it at once.
+static int check_process_args(sa_handle *h, const char *fn, const void *in, SaInKind kind, const void *out, int batch,
+                              int out_kind, int marker, const char *marker_name, bool scale_finite)
+{
+    static_assert(SA_OUT_MAG_FULL == 0 && SA_Q15_OUT_IQ == 0, "the kinds of both chains are 0 .. marker");
+    if (!h) return SA_EINVAL;
+    if (batch < 0) return fail_at(h, SA_ESHAPE, fn, "negative batch");
+    if (out_kind < 0 || out_kind > marker) return fail_at(h, SA_EINVAL, fn, "bad out_kind");
+    if (!scale_finite) return fail_at(h, SA_EINVAL, fn, "scale is not finite");
+    if (batch == 0) return SA_OK;
+    if (!in || !out) return fail_at(h, SA_EINVAL, fn, "NULL tensor");
+    if (out_kind == marker && ((uintptr_t)out & 15u) != 0) {
+        char msg[64];
+        std::snprintf(msg, sizeof msg, "%s output must be 16-byte aligned", marker_name);
+        return fail_at(h, SA_EINVAL, fn, msg);
+    }
+    if (kind == SaInKind::P12 && ((uintptr_t)in & 15u) != 0)       // the stage-ins issue 16-byte requests; every frame is then aligned
+        return fail_at(h, SA_EINVAL, fn, "packed input must be 16-byte aligned");
+    return SA_OK;
+}
+
 // sa_filter_q15 (`fft` false: window + integer cascade into `out`, out_kind unused) and sa_process_q15 / sa_process_q15_out
 // (`out` per out_kind, SA_Q15_OUT_*: the FFT launch's epilogue makes it), on int16 samples or, the _p12 entry points, on
 // packed 12-bit samples (`kind`: I16 or P12); `fn` names the entry point
 static int process_q15(sa_handle *h, const char *fn, const void *in, SaInKind kind, void *out, int batch, int out_kind,
                        void *stream, bool fft)
 {
-    if (!h) return SA_EINVAL;
-    if (batch < 0) return fail_at(h, SA_ESHAPE, fn, "negative batch");
-    if (out_kind < SA_Q15_OUT_IQ || out_kind > SA_Q15_OUT_MARKER) return fail_at(h, SA_EINVAL, fn, "bad out_kind");
-    if (batch == 0) return SA_OK;
-    if (!in || !out) return fail_at(h, SA_EINVAL, fn, "NULL tensor");
-    if (out_kind == SA_Q15_OUT_MARKER && ((uintptr_t)out & 15u) != 0)
-        return fail_at(h, SA_EINVAL, fn, "SA_Q15_OUT_MARKER output must be 16-byte aligned");
-    if (kind == SaInKind::P12 && ((uintptr_t)in & 15u) != 0)       // the rule of sa_process_f32_p12; every frame is then aligned
-        return fail_at(h, SA_EINVAL, fn, "packed input must be 16-byte aligned");
+    { const int rc = check_process_args(h, fn, in, kind, out, batch, out_kind, SA_Q15_OUT_MARKER, "SA_Q15_OUT_MARKER", true);
+      if (rc != SA_OK || batch == 0) return rc; }
     SA_HIP(h, hipSetDevice(h->device));
     const SaQ15Params p = q15_params(h);
     const bool staged = fft && p.filter != SA_FILTER_NONE;      // cascade into the slot's workspace, then the FFT
@@ -496,16 +513,9 @@ int sa_filter_q15_p12(sa_handle *h, const uint8_t *in, int16_t *out_time, int ba
 static int process_float(sa_handle *h, const char *fn, const void *in, SaInKind kind, float scale, void *out, int batch,
                          int out_kind, void *stream)
 {
-    if (!h) return SA_EINVAL;
-    if (batch < 0) return fail_at(h, SA_ESHAPE, fn, "negative batch");
-    if (out_kind < SA_OUT_MAG_FULL || out_kind > SA_OUT_MARKER) return fail_at(h, SA_EINVAL, fn, "bad out_kind");
-    if (!(scale == scale) || scale - scale != 0.f) return fail_at(h, SA_EINVAL, fn, "scale is not finite");
-    if (batch == 0) return SA_OK;
-    if (!in || !out) return fail_at(h, SA_EINVAL, fn, "NULL tensor");
-    if (out_kind == SA_OUT_MARKER && ((uintptr_t)out & 15u) != 0)
-        return fail_at(h, SA_EINVAL, fn, "SA_OUT_MARKER output must be 16-byte aligned");
-    if (kind == SaInKind::P12 && ((uintptr_t)in & 15u) != 0)       // the stage-in issues 16-byte requests
-        return fail_at(h, SA_EINVAL, fn, "packed input must be 16-byte aligned");
+    const bool scale_finite = scale == scale && scale - scale == 0.f;
+    { const int rc = check_process_args(h, fn, in, kind, out, batch, out_kind, SA_OUT_MARKER, "SA_OUT_MARKER", scale_finite);
+      if (rc != SA_OK || batch == 0) return rc; }
     if (h->filter_mode == SA_FILTER_WIDE)
         return fail_at(h, SA_ESTATE, fn, "filter mode 0xA2 (Q2.14) belongs to the Q15 path; use 0xA1 with sa_load_sos_f32");
     SA_HIP(h, hipSetDevice(h->device));

@@ -79,16 +79,14 @@ class FrameCutter:
         self.packed = bool(packed)
         self._buf = np.empty(0, np.uint8 if packed else np.int16)
 
-    def _push_packed(self, data) -> np.ndarray:
-        b = np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.asarray(data)
-        if b.dtype != np.uint8:
-            raise ValueError("a packed stream is pushed as uint8 / bytes")
-        self._buf = np.concatenate([self._buf, b.reshape(-1)])
-        n, hop = self._buf.size, 3 * self.hop // 2           # in bytes
-        if n < P12_FRAME_BYTES:
-            return np.empty((0, P12_FRAME_BYTES), np.uint8)
-        k = (n - P12_FRAME_BYTES) // hop + 1
-        idx = np.arange(k)[:, None] * hop + np.arange(P12_FRAME_BYTES)[None, :]
+    def _cut(self, new: np.ndarray, row: int, hop: int) -> np.ndarray:
+        """Append `new` to the buffer and take out every complete frame: `row` elements of the buffer each, `hop` apart."""
+        self._buf = np.concatenate([self._buf, new.reshape(-1)])
+        n = self._buf.size
+        if n < row:
+            return np.empty((0, row), self._buf.dtype)
+        k = (n - row) // hop + 1
+        idx = np.arange(k)[:, None] * hop + np.arange(row)[None, :]
         out = self._buf[idx]
         self._buf = self._buf[k * hop:]
         return out
@@ -97,21 +95,17 @@ class FrameCutter:
         """Append samples; return the frames that became complete, shape [k, 16384] (k may be 0).
         Packed: append bytes of the packed stream; the frames are [k, 24576] uint8."""
         if self.packed:
-            return self._push_packed(samples)
+            b = (np.frombuffer(samples, np.uint8) if isinstance(samples, (bytes, bytearray, memoryview))
+                 else np.asarray(samples))
+            if b.dtype != np.uint8:
+                raise ValueError("a packed stream is pushed as uint8 / bytes")
+            return self._cut(b, P12_FRAME_BYTES, 3 * self.hop // 2)          # in bytes
         s = np.asarray(samples)
         if s.dtype != np.int16:
             if np.any(s < -32768) or np.any(s > 32767):
                 raise ValueError("samples do not fit int16")
             s = s.astype(np.int16)
-        self._buf = np.concatenate([self._buf, s.reshape(-1)])
-        n = self._buf.size
-        if n < N:
-            return np.empty((0, N), np.int16)
-        k = (n - N) // self.hop + 1
-        idx = np.arange(k)[:, None] * self.hop + np.arange(N)[None, :]
-        out = self._buf[idx]
-        self._buf = self._buf[k * self.hop:]
-        return out
+        return self._cut(s, N, self.hop)
 
     @property
     def pending(self) -> int:

@@ -26,6 +26,19 @@ def test_library_exports_every_declared_symbol(hip_lib_built):
     assert hip_lib_built.sa_abi_version() == 4
 
 
+def test_binding_table_names_exactly_the_declared_symbols():
+    from fpga_real_time_fft_analyzer_amd import abi
+    assert sorted(abi.SIGNATURES) == declared_symbols() and len(abi.SIGNATURES) == 44
+
+
+def test_every_declared_symbol_is_bound_with_its_signature(hip_lib_built):
+    from fpga_real_time_fft_analyzer_amd import abi
+    for name in declared_symbols():
+        fn, (restype, argtypes) = getattr(hip_lib_built, name), abi.SIGNATURES[name]
+        assert fn.argtypes is not None and list(fn.argtypes) == list(argtypes), name
+        assert fn.restype is restype is (ctypes.c_char_p if name == "sa_last_error" else ctypes.c_int), name
+
+
 def test_no_torch_or_oracle_linkage(hip_lib_built):
     """The product library links HIP only: no torch, no oracle."""
     from fpga_real_time_fft_analyzer_amd import abi

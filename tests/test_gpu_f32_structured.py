@@ -15,6 +15,7 @@ import pytest
 from scipy import signal
 
 from conftest import N
+from gpu_support import ch, table_window, to_device, torch_mod  # noqa: F401 (fixtures)
 from structured_cases import CASCADE_VARIANTS, H, bin_norm, cascades, f32_fft_figure, fft_bound, plan_header
 
 pytestmark = pytest.mark.gpu
@@ -24,31 +25,6 @@ IMPULSE_AT = [0, 1, 2, 3, 30, 31, 32, 33, 62, 63, 64, 65, 510, 511, 512, 513, 10
 COSINE_BINS = [0, 1, 2, 4095, 4096, 4097, 8191, 8192]
 CASCADE_IMPULSE_AT = [0, 15, 16, 31, 32, 63, 64, 1023, 1024, 8191, 8192, 16383]
 I16_AMP = 2048                        # impulse / cosine amplitude on the int16 entry: x = sample / 2048
-
-
-@pytest.fixture(scope="module")
-def torch_mod():
-    import torch
-    assert torch.cuda.is_available()
-    return torch
-
-
-@pytest.fixture()
-def ch(chain_cls):
-    c = chain_cls(0)
-    yield c
-    c.close()
-
-
-def _dev(torch_mod, a):
-    return torch_mod.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def _table_window():
-    """ones with a 1e-5 ripple at 3 cycles per frame: not a0 - a1 cos(2 pi n / (N-1)) (fit bound 1.5e-7), so the
-    kernels read the window table."""
-    n = np.arange(N)
-    return (1.0 + 1e-5 * np.cos(2 * np.pi * 3 * n / N)).astype(np.float32)
 
 
 def _fft_frames(i16, seed=0):
@@ -87,7 +63,7 @@ FFT_FORMS = {
 
 
 def _setup(ch, mode, nident, window, precision):
-    w = np.ones(N, np.float32) if window == "ones" else _table_window()
+    w = np.ones(N, np.float32) if window == "ones" else table_window()
     ch.set_window_f32(w)
     if nident:
         ch.load_sos(np.tile([1.0, 0, 0, 1.0, 0, 0], (nident, 1)))
@@ -121,7 +97,7 @@ def test_fft_bin_by_bin(ch, torch_mod, form):
     x64 = x.astype(np.float64) / (I16_AMP if i16 else 1.0)
     xw64 = x64 * w.astype(np.float64)
     ref = np.fft.rfft(xw64, axis=1)
-    xd = _dev(torch_mod, xin)
+    xd = to_device(torch_mod, xin)
     kw = {"scale": 1.0 / I16_AMP} if i16 else {}
     out = {k: ch.process_f32(xd, out_kind=k, **kw).cpu().numpy()[:B] for k in ("spec_half", "mag_half", "mag_full", "time")}
     assert np.array_equal(out["mag_full"][:, H:], out["mag_full"][:, 1:H - 1][:, ::-1])
@@ -168,7 +144,7 @@ def _run_cascade(ch, torch_mod, name, sos, precision):
     nsec, unit, wingen, _ = plan_header(ch.iir_plan())
     assert (nsec, unit, wingen) == (CASCADE_VARIANTS[name][0], CASCADE_VARIANTS[name][1], 1)
     pos, x = _cascade_frames(np.random.default_rng(sum(map(ord, name))))
-    xd = _dev(torch_mod, x)
+    xd = to_device(torch_mod, x)
     y = ch.process_f32(xd, out_kind="time").cpu().numpy().astype(np.float64)
     spec = ch.process_f32(xd, out_kind="spec_half").cpu().numpy()
     ref = signal.sosfilt(sos, x.astype(np.float64), axis=1)
@@ -235,12 +211,12 @@ def test_power_of_two_scaling_is_exact(ch, torch_mod, form):
     x = (0.5 * np.sin(2 * np.pi * 0.0123 * n) + 0.3 * rng.standard_normal((4, N))).astype(np.float32)
     xi = rng.integers(-2048, 2048, size=(3, N)).astype(np.int16)
     kinds = ("spec_half", "time", "mag_full")
-    base = {k: ch.process_f32(_dev(torch_mod, x), out_kind=k).cpu().numpy() for k in kinds}
-    base_i = {k: ch.process_f32(_dev(torch_mod, xi), out_kind=k, scale=1.0 / 2048).cpu().numpy() for k in kinds}
+    base = {k: ch.process_f32(to_device(torch_mod, x), out_kind=k).cpu().numpy() for k in kinds}
+    base_i = {k: ch.process_f32(to_device(torch_mod, xi), out_kind=k, scale=1.0 / 2048).cpu().numpy() for k in kinds}
     for k2 in (-30, -8, 8, 30):
         s = np.float32(2.0 ** k2)
-        got = {k: ch.process_f32(_dev(torch_mod, x * s), out_kind=k).cpu().numpy() for k in kinds}
-        got_i = {k: ch.process_f32(_dev(torch_mod, xi), out_kind=k, scale=2.0 ** k2 / 2048).cpu().numpy() for k in kinds}
+        got = {k: ch.process_f32(to_device(torch_mod, x * s), out_kind=k).cpu().numpy() for k in kinds}
+        got_i = {k: ch.process_f32(to_device(torch_mod, xi), out_kind=k, scale=2.0 ** k2 / 2048).cpu().numpy() for k in kinds}
         for g, b in ((got, base), (got_i, base_i)):
             assert np.array_equal(g["spec_half"], b["spec_half"] * s), (form, k2)
             assert np.array_equal(g["time"], b["time"] * s), (form, k2)

@@ -7,35 +7,11 @@ import numpy as np
 import pytest
 
 from conftest import N, load_golden, rel_maxnorm
+from gpu_support import ch, synth, to_device, torch_mod  # noqa: F401 (fixtures)
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-5
 KINDS = ("mag_full", "mag_half", "spec_half", "time")
-
-
-@pytest.fixture(scope="module")
-def torch_mod():
-    import torch
-    assert torch.cuda.is_available()
-    return torch
-
-
-@pytest.fixture()
-def ch(chain_cls):
-    c = chain_cls(0)
-    yield c
-    c.close()
-
-
-def _dev(torch_mod, a):
-    return torch_mod.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def synth(B, seed):
-    rng = np.random.default_rng(seed)
-    n = np.arange(N)
-    fb = rng.uniform(0.01, 0.45, size=B)
-    return (0.8 * np.sin(2 * np.pi * fb[:, None] * n[None, :]) + 0.05 * rng.standard_normal((B, N))).astype(np.float32)
 
 
 def rel_err(got, ref):
@@ -126,7 +102,7 @@ def test_table_window_through_the_iir(ch, torch_mod, oracle):
     ch.set_precision("f64")
     x = synth(6, seed=3)
     _, X, M = oracle.chain_fp(x, sos, hann=w.astype(np.float64))
-    d = _dev(torch_mod, x)
+    d = to_device(torch_mod, x)
     assert rel_maxnorm(ch.process_f32(d).cpu().numpy(), M) <= TOL
     assert rel_err(ch.process_f32(d, out_kind="spec_half").cpu().numpy(), X) <= TOL
     ch.set_window_f32(None)                                   # back to the default Hann, in double too
@@ -141,7 +117,7 @@ def test_int16_and_float32_entry_points_agree_bit_for_bit(ch, torch_mod):
     rng = np.random.default_rng(17)
     xi = rng.integers(-2048, 2048, size=(5, N)).astype(np.int16)
     xi[1] = rng.integers(-32768, 32768, size=N).astype(np.int16)
-    d_i = _dev(torch, xi)
+    d_i = to_device(torch, xi)
     d_f = (d_i.to(torch.float32) * np.float32(scale)).contiguous()
     ch.set_precision("f64")
     for sos in (signal.butter(12, 0.2, output="sos"), signal.ellip(4, 0.5, 40.0, [0.1, 0.3], btype="bandpass", output="sos")[:3]):
@@ -159,8 +135,8 @@ def test_default_precision_and_bypass_unchanged(chain_cls, torch_mod):
     from scipy import signal
     torch = torch_mod
     sos = signal.cheby2(8, 60, 0.3, output="sos")
-    x = _dev(torch, synth(8, seed=9))
-    xi = _dev(torch, np.random.default_rng(4).integers(-2048, 2048, size=(3, N)).astype(np.int16))
+    x = to_device(torch, synth(8, seed=9))
+    xi = to_device(torch, np.random.default_rng(4).integers(-2048, 2048, size=(3, N)).astype(np.int16))
     fresh, ch = chain_cls(0), chain_cls(0)
     try:
         for h in (fresh, ch):
@@ -192,7 +168,7 @@ def test_overlap_depths(ch, torch_mod, depth):
     ch.load_sos(g["sos"])
     ch.set_filter_mode(0xA1)
     ch.set_precision("f64")
-    xs = [_dev(torch, synth(64, seed=200 + i)) for i in range(5)]
+    xs = [to_device(torch, synth(64, seed=200 + i)) for i in range(5)]
     ref = [ch.process_f32(x).clone() for x in xs]
     ref_t = ch.process_f32(xs[0], out_kind="time").clone()
     torch.cuda.synchronize()
@@ -217,7 +193,7 @@ def test_graph_capture_and_replay(ch, torch_mod):
     ch.set_filter_mode(0xA1)
     ch.reserve(8)
     ch.set_precision("f64")
-    x = _dev(torch, synth(8, seed=31))
+    x = to_device(torch, synth(8, seed=31))
     ref = ch.process_f32(x).clone()
     out = torch.empty_like(ref)
     graph = torch.cuda.CUDAGraph()
@@ -230,7 +206,7 @@ def test_graph_capture_and_replay(ch, torch_mod):
     graph.replay()
     torch.cuda.synchronize()
     assert torch.equal(out, ref)
-    x2 = _dev(torch, synth(8, seed=32))
+    x2 = to_device(torch, synth(8, seed=32))
     ref2 = ch.process_f32(x2).clone()
     x.copy_(x2)                                            # new data, same graph
     graph.replay()

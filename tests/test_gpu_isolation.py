@@ -24,6 +24,7 @@ import numpy as np
 import pytest
 
 from conftest import N, ROOT, load_golden
+from gpu_support import ch, table_window, to_device, torch_mod  # noqa: F401 (fixtures)
 from structured_cases import cascades, plan_header
 
 HELPER_SRC = os.path.join(ROOT, "tests", "hip", "lds_fill.hip")
@@ -88,26 +89,8 @@ class Lds:
 
 
 @pytest.fixture(scope="module")
-def torch_mod():
-    import torch
-    assert torch.cuda.is_available()
-    return torch
-
-
-@pytest.fixture(scope="module")
 def lds(lds_helper_so, hip_lib_built, torch_mod):
     return Lds(lds_helper_so, torch_mod)
-
-
-@pytest.fixture()
-def ch(chain_cls):
-    c = chain_cls(0)
-    yield c
-    c.close()
-
-
-def _dev(torch_mod, a):
-    return torch_mod.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 @pytest.mark.gpu
@@ -148,11 +131,6 @@ def _frames_i16(B, seed, amp=2048):
     if B > 2:
         x[-1] = rng.integers(-32768, 32768, N)            # one full-scale frame
     return x.astype(np.int16)
-
-
-def _table_window():
-    """ones with a 1e-5 ripple: not a cosine window, so the float kernels read the window table (WINGEN off)."""
-    return (1.0 + 1e-5 * np.cos(2 * np.pi * 3 * np.arange(N) / N)).astype(np.float32)
 
 
 def _floats(kind, a):
@@ -236,7 +214,7 @@ FLOAT_GROUPS = {
 
 def _configure(ch, mode, casc, window, precision):
     ch.set_precision("f32")
-    ch.set_window_f32(None if window == "cos" else _table_window())
+    ch.set_window_f32(None if window == "cos" else table_window())
     if casc == "smoother_f32":
         ch.load_sos_f32(cascades()[casc])
     elif casc is not None:
@@ -257,7 +235,7 @@ def test_poisoned_lds_float_chain(ch, torch_mod, lds, group):
         _configure(ch, mode, casc, window, precision)
         for in_t, B in inputs:
             x = _frames_f32(B, B) if in_t == "float32" else _frames_i16(B, B)
-            xd = _dev(torch_mod, x)
+            xd = to_device(torch_mod, x)
             kw = {"scale": I16_SCALE} if in_t == "int16" else {}
             for kind, rng in KIND_RUNS:
                 if rng is not None:
@@ -345,7 +323,7 @@ def test_poisoned_lds_integer_chain(ch, torch_mod, oracle, lds, case):
         for B in (1, 7, 17):
             x = _frames_i16(B, 100 * B + win_mode, amp=8192)
             ref_iq, ref_t = oracle.chain_q15(x, None, win_mode, mode, c12, sos14 if nsec_wide else None, want_time=True)
-            xd = _dev(torch_mod, x)
+            xd = to_device(torch_mod, x)
             reached.add((_launched_q15(ch, nsec_wide, False), win_mode))
             reached.add((_launched_q15(ch, nsec_wide, True), win_mode))
             for word in Q15_POISON:
@@ -416,8 +394,8 @@ NEIGHBOUR_FORMS = {
 
 
 def _check_neighbours(ch, torch_mod, x, clean, kinds, tag, **kw):
-    xd = _dev(torch_mod, x)
-    cd = _dev(torch_mod, x[clean])
+    xd = to_device(torch_mod, x)
+    cd = to_device(torch_mod, x[clean])
     bad, spoilt = [], 0
     for kind in kinds:
         mixed = ch.process_f32(xd, out_kind=kind, **kw).cpu().numpy()
@@ -476,7 +454,7 @@ def test_nonfinite_neighbours_overlapped(ch, torch_mod):
     _configure(ch, 0x00, None, "cos", "f32")
     xb, clean_b = _mixed_f32(1024, 11, bad_of_3=2)
     xc = _frames_f32(1024, 12)
-    db, dc = _dev(torch_mod, xb), _dev(torch_mod, xc)
+    db, dc = to_device(torch_mod, xb), to_device(torch_mod, xc)
     ref_b = {k: ch.process_f32(db, out_kind=k).cpu().numpy()[clean_b] for k in KINDS}
     ref_c = {k: ch.process_f32(dc, out_kind=k).cpu().numpy() for k in KINDS}
     ch.set_overlap(2)

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 from conftest import N, load_golden
+from gpu_support import ch, table_window, to_device, torch_mod  # noqa: F401 (fixtures)
 from structured_cases import cascades
 
 pytestmark = pytest.mark.gpu
@@ -20,24 +21,6 @@ pytestmark = pytest.mark.gpu
 COSINE_BINS = [0, 1, 2, 4095, 4096, 4097, 8191, 8192]
 RANGES = [(0, N), (0, 8193), (100, 2000), (9000, 12000), (8000, 8400), (0, 1), (8192, 8193), (16383, 16384)]
 SA_EINVAL, SA_ESTATE = -1, -4
-
-
-@pytest.fixture(scope="module")
-def torch_mod():
-    import torch
-    assert torch.cuda.is_available()
-    return torch
-
-
-@pytest.fixture()
-def ch(chain_cls):
-    c = chain_cls(0)
-    yield c
-    c.close()
-
-
-def _dev(torch_mod, a):
-    return torch_mod.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 def _frames(B, seed, i16=False):
@@ -76,12 +59,6 @@ def _check_against_mag_full(mag, rec, lo, hi):
     return float((err / np.maximum(ref_p, 1e-300)).max())
 
 
-def _table_window():
-    """not a0 - a1 cos(2 pi n / (N-1)): the IIR kernels read the window table"""
-    n = np.arange(N)
-    return (1.0 + 1e-5 * np.cos(2 * np.pi * 3 * n / N)).astype(np.float32)
-
-
 G2 = load_golden("g2_config1.npz")["sos"]
 _CASC = cascades()
 # form -> (filter mode, sos or None, table window, int16 entry, batch, precision)
@@ -116,12 +93,12 @@ def test_marker_matches_mag_full_exactly(ch, torch_mod, form):
     First MI355X run: every peak and bin exact in all 44 forms; worst band_power error 3.5e-7 relative (bound 1e-5)."""
     mode, sos, table, i16, B, precision = FORMS[form]
     if table:
-        ch.set_window_f32(_table_window())
+        ch.set_window_f32(table_window())
     if sos is not None:
         ch.load_sos(sos)
     ch.set_filter_mode(mode)
     ch.set_precision(precision)
-    x = _dev(torch_mod, _frames(B, seed=list(FORMS).index(form), i16=i16))
+    x = to_device(torch_mod, _frames(B, seed=list(FORMS).index(form), i16=i16))
     mag = ch.process_f32(x).cpu().numpy()
     worst = 0.0
     for lo, hi in RANGES:
@@ -160,7 +137,7 @@ def test_marker_against_float64_oracle(ch, torch_mod, oracle):
         else:
             ch.load_sos(sos)
             ch.set_filter_mode(0xA1)
-        xd = _dev(torch_mod, x)
+        xd = to_device(torch_mod, x)
         P = ref.max(axis=1)
         S = (ref ** 2).sum(axis=1)
         nz = P > 0
@@ -189,7 +166,7 @@ def test_exact_bin_cosines_and_zero_frames(ch, torch_mod, i16):
     n = np.arange(N)
     x = np.stack([np.cos(2 * np.pi * ((b * n) % N) / N) for b in COSINE_BINS] + [np.zeros(N)] * 2)
     x = np.rint(x * 2047).astype(np.int16) if i16 else x.astype(np.float32)
-    xd = _dev(torch_mod, x)
+    xd = to_device(torch_mod, x)
     kw = {"scale": 1.0 / 2048} if i16 else {}
     nb = len(COSINE_BINS)
     upper = [i for i, b in enumerate(COSINE_BINS) if b not in (0, N // 2)]
@@ -221,7 +198,7 @@ def test_records_are_reproducible_across_calls_overlap_and_graphs(ch, torch_mod)
     torch = torch_mod
     _setup_g2(ch)
     ch.set_marker_range(100, 9000)
-    xs = [_dev(torch, _frames(600, seed=s)) for s in range(4)]
+    xs = [to_device(torch, _frames(600, seed=s)) for s in range(4)]
     ref = [ch.process_f32(x, out_kind="marker").clone() for x in xs]
     for _ in range(3):
         for x, r in zip(xs, ref):
@@ -263,7 +240,7 @@ def test_range_is_stream_ordered(ch, torch_mod):
     overlap depth 2."""
     torch = torch_mod
     _setup_g2(ch)
-    x = _dev(torch, _frames(64, seed=9))
+    x = to_device(torch, _frames(64, seed=9))
     mag = ch.process_f32(x).cpu().numpy()
     for depth in (1, 2):
         ch.set_overlap(depth)
@@ -290,7 +267,7 @@ def test_range_refusals_and_reset(ch, torch_mod):
             ch.set_marker_range(lo, hi)
         assert e.value.code == SA_EINVAL and ch.marker_range == (300, 700)
     _setup_g2(ch)
-    x = _dev(torch, _frames(4, seed=3))
+    x = to_device(torch, _frames(4, seed=3))
     out = torch.empty((4, 4), dtype=torch.int32, device="cuda")
     ch.process_f32(x, out=out, out_kind="marker")
     graph = torch.cuda.CUDAGraph()

@@ -31,6 +31,7 @@ import numpy as np
 import pytest
 
 from conftest import N, ROOT, load_golden
+from gpu_support import torch_mod  # noqa: F401 (fixtures)
 from structured_cases import cascades
 
 HELPER_SRC = os.path.join(ROOT, "tests", "hip", "stream_hold.hip")
@@ -60,13 +61,6 @@ def test_stream_hold_cross_compiles(hold_so):
     assert r.returncode == 0, r.stderr
     text = {ln.split()[-1] for ln in r.stdout.splitlines() if len(ln.split()) == 3 and ln.split()[1] == "T"}
     assert "stream_hold" in text, r.stdout
-
-
-@pytest.fixture(scope="module")
-def torch_mod():
-    import torch
-    assert torch.cuda.is_available()
-    return torch
 
 
 class Env:

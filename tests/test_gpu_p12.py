@@ -9,30 +9,13 @@ import numpy as np
 import pytest
 
 from conftest import N
+from gpu_support import ch, check_overlap_profiling_and_graph_capture, to_device, torch_mod  # noqa: F401 (fixtures)
 
 pytestmark = pytest.mark.gpu
 
 P12 = 24576
 KINDS = ("mag_full", "mag_half", "spec_half", "time", "marker")
 SCALES = (1.0 / 2048.0, 3.1e-4)
-
-
-@pytest.fixture(scope="module")
-def torch_mod():
-    import torch
-    assert torch.cuda.is_available()
-    return torch
-
-
-@pytest.fixture()
-def ch(chain_cls):
-    c = chain_cls(0)
-    yield c
-    c.close()
-
-
-def _dev(torch_mod, a):
-    return torch_mod.from_numpy(np.array(a)).cuda()            # a copy: the shared batch is read-only
 
 
 @functools.lru_cache(maxsize=None)
@@ -86,7 +69,7 @@ def same(torch, a, b):
 def test_packed_equals_int16_for_every_mode_and_kind(ch, torch_mod, window, scale):
     torch = torch_mod
     x, p = batch()
-    d_i, d_p = _dev(torch, x), _dev(torch, p)
+    d_i, d_p = to_device(torch, x), to_device(torch, p)
     if window == "blackman":
         ch.set_window_f32(np.blackman(N).astype(np.float32))       # a table window: no in-place generator
     for name, sos in cascades().items():
@@ -103,7 +86,7 @@ def test_packed_equals_int16_for_every_mode_and_kind(ch, torch_mod, window, scal
 def test_packed_equals_int16_with_float64_state(ch, torch_mod, scale):
     torch = torch_mod
     x, p = batch()
-    d_i, d_p = _dev(torch, x), _dev(torch, p)
+    d_i, d_p = to_device(torch, x), to_device(torch, p)
     ch.set_precision("f64")
     for window in (None, np.blackman(N).astype(np.float32)):
         if window is not None:
@@ -128,11 +111,11 @@ def test_sample_order_against_numpy(ch, torch_mod):
     ch.set_filter_mode(0xB1)
     one = np.zeros((1, N), np.int16)
     one[0, 5] = 1
-    c = ch.process_f32(_dev(torch, one), out_kind="time", scale=1.0).cpu().numpy()
+    c = ch.process_f32(to_device(torch, one), out_kind="time", scale=1.0).cpu().numpy()
     assert c[0, 5] != 0 and not np.delete(c[0], 5).any()
     c = np.float32(c[0, 5])
     for scale in SCALES:
-        got = ch.process_f32(_dev(torch, p), out_kind="time", scale=scale).cpu().numpy()
+        got = ch.process_f32(to_device(torch, p), out_kind="time", scale=scale).cpu().numpy()
         want = (unpack12(p).astype(np.float32) * np.float32(scale)) * c
         assert want.dtype == np.float32 and np.array_equal(got, want)
         assert np.array_equal(unpack12(p), x)
@@ -144,7 +127,7 @@ def test_frame_stride_and_isolation(ch, torch_mod, mode):
     give the rows of the batch call."""
     torch = torch_mod
     _, p = batch()
-    d_p = _dev(torch, p)
+    d_p = to_device(torch, p)
     select(ch, cascades()[mode])
     for kind in ("mag_full", "time", "marker"):
         ref = ch.process_f32(d_p, out_kind=kind).clone()
@@ -160,7 +143,7 @@ def test_frame_stride_and_isolation(ch, torch_mod, mode):
 def test_marker_range_that_cuts_the_spectrum(ch, torch_mod):
     torch = torch_mod
     x, p = batch()
-    d_i, d_p = _dev(torch, x), _dev(torch, p)
+    d_i, d_p = to_device(torch, x), to_device(torch, p)
     ch.set_marker_range(100, 5000)
     for name in ("none", "butter12"):
         select(ch, cascades()[name])
@@ -175,45 +158,18 @@ def test_overlap_profiling_and_graph_capture(ch, torch_mod):
     call, and capture into a graph after reserve; all outputs equal the plain stream-ordered call."""
     torch = torch_mod
     _, p = batch()
-    d_p = _dev(torch, p)
+    d_p = to_device(torch, p)
     select(ch, cascades()["butter12"])
     ch.reserve(8)
     ref = ch.process_f32(d_p).clone()
-    # overlap depth 2
-    ch.set_overlap(2)
-    outs = [torch.zeros_like(ref) for _ in range(3)]
-    for o in outs:
-        ch.process_f32(d_p, out=o)
-    ch.flush()
-    torch.cuda.synchronize()
-    ch.set_overlap(1)
-    for o in outs:
-        assert torch.equal(o, ref)
-    # launch timing: one time per call
-    ch.set_profiling(4)
-    out = torch.zeros_like(ref)
-    for _ in range(3):
-        ch.process_f32(d_p, out=out)
-    ms = ch.profile_read(4)
-    assert len(ms) == 3 and all(v > 0.0 for v in ms)
-    ch.set_profiling(0)
-    assert torch.equal(out, ref)
-    # graph capture and replay
-    graph = torch.cuda.CUDAGraph()
-    out.zero_()
-    with torch.cuda.graph(graph):
-        ch.process_f32(d_p, out=out)
-    out.zero_()
-    graph.replay()
-    torch.cuda.synchronize()
-    assert torch.equal(out, ref)
+    check_overlap_profiling_and_graph_capture(torch, ch, lambda out: ch.process_f32(d_p, out=out), ref)
 
 
 def test_argument_errors(ch, torch_mod):
     from fpga_real_time_fft_analyzer_amd.abi import SA_EINVAL, SA_ESHAPE, SA_ESTATE, SpecanError
     torch = torch_mod
     _, p = batch()
-    d_p = _dev(torch, p[:2])
+    d_p = to_device(torch, p[:2])
     ref = ch.process_f32(d_p).clone()
     flat = torch.zeros(8 + 2 * P12, dtype=torch.uint8, device="cuda")
     off = flat[8:].view(2, P12)                                    # contiguous, 8 bytes off a 16-byte boundary

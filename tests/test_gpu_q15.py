@@ -7,30 +7,13 @@ import pytest
 
 from udp_collect import FrameCollector
 from conftest import N, load_golden
+from gpu_support import ch, to_device, torch_mod  # noqa: F401 (fixtures)
 
 pytestmark = pytest.mark.gpu
 
 
 def sha(a):
     return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
-
-
-@pytest.fixture(scope="module")
-def torch_mod():
-    import torch
-    assert torch.cuda.is_available()
-    return torch
-
-
-@pytest.fixture()
-def ch(chain_cls):
-    c = chain_cls(0)
-    yield c
-    c.close()
-
-
-def _dev(torch_mod, a):
-    return torch_mod.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 def test_power_on_state(ch, oracle):
@@ -41,7 +24,7 @@ def test_power_on_state(ch, oracle):
 
 def test_golden_digests_all_modes(ch, torch_mod):
     g = load_golden("g4_q15_frames.npz")
-    x = _dev(torch_mod, g["x"])
+    x = to_device(torch_mod, g["x"])
     for name, cmd, c12 in (("bypass", 0xB1, None), ("default", 0x00, None), ("gui", 0xA1, g["c_gui"])):
         if c12 is not None:
             ch.load_coeffs_q7(c12)
@@ -72,7 +55,7 @@ def test_bit_exact_vs_integer_model(ch, torch_mod, oracle, B, cmd):
     ch.load_sos_q14(sos14)
     ch.set_filter_mode(cmd)
     ref_iq, ref_t = oracle.chain_q15(x, None, 0, cmd, c12, sos14, want_time=True)
-    xd = _dev(torch_mod, x)
+    xd = to_device(torch_mod, x)
     assert np.array_equal(ch.filter_q15(xd).cpu().numpy(), ref_t)
     assert np.array_equal(ch.process_q15(xd).cpu().numpy(), ref_iq)
 
@@ -87,7 +70,7 @@ def test_extreme_inputs(ch, torch_mod, oracle):
     for cmd in (0xB1, 0x00):
         ch.set_filter_mode(cmd)
         ref = oracle.chain_q15(x, None, 0, cmd, None, None)
-        assert np.array_equal(ch.process_q15(_dev(torch_mod, x)).cpu().numpy(), ref)
+        assert np.array_equal(ch.process_q15(to_device(torch_mod, x)).cpu().numpy(), ref)
     e = torch_mod.empty((0, N), dtype=torch_mod.int16, device="cuda")
     assert ch.process_q15(e).shape == (0, N, 2)
 
@@ -106,8 +89,8 @@ def test_random_coefficient_uploads(ch, torch_mod, oracle):
         x[1] = rng.integers(-2048, 2048, N)
         ch.load_coeffs_q7(c12)
         iq_ref, t_ref = oracle.chain_q15(x, None, 0, 0xA1, c12, None, want_time=True)
-        assert np.array_equal(ch.filter_q15(_dev(torch_mod, x)).cpu().numpy(), t_ref), (case, c12)
-        assert np.array_equal(ch.process_q15(_dev(torch_mod, x)).cpu().numpy(), iq_ref), (case, c12)
+        assert np.array_equal(ch.filter_q15(to_device(torch_mod, x)).cpu().numpy(), t_ref), (case, c12)
+        assert np.array_equal(ch.process_q15(to_device(torch_mod, x)).cpu().numpy(), iq_ref), (case, c12)
 
 
 def test_zero_tap_uploads_take_the_short_step_and_stay_exact(ch, torch_mod, oracle):
@@ -119,7 +102,7 @@ def test_zero_tap_uploads_take_the_short_step_and_stay_exact(ch, torch_mod, orac
     rng = np.random.default_rng(777)
     x = rng.integers(-32768, 32768, (3, N)).astype(np.int16)
     x[1] = rng.integers(-2048, 2048, N)
-    xd = _dev(torch_mod, x)
+    xd = to_device(torch_mod, x)
     ch.set_filter_mode(0xA1)
     for case in range(36):
         c12 = rng.integers(-128, 128, 12).astype(np.int8)            # wire order b0,b1,b2,a0,a1,a2 per set
@@ -159,7 +142,7 @@ def test_overlapped_launches_q15(ch, torch_mod, oracle):
     ch.set_overlap(2)
     s = torch.cuda.Stream()
     with torch.cuda.stream(s):
-        xd = [_dev(torch, x) for x in xs]
+        xd = [to_device(torch, x) for x in xs]
         outs = []
         for k, x in enumerate(xd):
             if k == 3:                                       # control plane between overlapped calls: custom coefficients
@@ -178,7 +161,7 @@ def test_overlapped_launches_q15(ch, torch_mod, oracle):
         assert np.array_equal(got[k], ref), k
     ch.set_filter_mode(0xA1)
     ch.set_overlap(1)
-    assert np.array_equal(ch.process_q15(_dev(torch, xs[3])).cpu().numpy(), got[3])
+    assert np.array_equal(ch.process_q15(to_device(torch, xs[3])).cpu().numpy(), got[3])
 
 
 def test_mode_changes_do_not_grow_the_workspace(chain_cls, torch_mod):
@@ -243,7 +226,7 @@ def test_random_wide_cascades(ch, torch_mod, oracle):
         ch.set_window_mode_q15(wm)
         ch.load_sos_q14(sos)
         ref = oracle.chain_q15(x, None, wm, 0xA2, None, sos)
-        assert np.array_equal(ch.process_q15(_dev(torch_mod, x)).cpu().numpy(), ref), (case, sos)
+        assert np.array_equal(ch.process_q15(to_device(torch_mod, x)).cpu().numpy(), ref), (case, sos)
     ch.set_window_mode_q15(0)
 
 
@@ -255,7 +238,7 @@ def test_custom_rom_and_window_modes(ch, torch_mod, oracle):
     for wm in (0, 1):
         ch.set_window_mode_q15(wm)
         ref = oracle.chain_q15(x, rom, wm, 0xB1, None, None)
-        assert np.array_equal(ch.process_q15(_dev(torch_mod, x)).cpu().numpy(), ref)
+        assert np.array_equal(ch.process_q15(to_device(torch_mod, x)).cpu().numpy(), ref)
     # the corners of the window arithmetic: x = c = -32768 (the 17-bit sum +32768 that resize16 maps to 0,
     # new/hann8192.vhd:36-39), full-scale products of either sign, in the FFT-side and the filter-side window
     xf = rng.integers(-32768, 32768, size=(3, N)).astype(np.int16)
@@ -270,7 +253,7 @@ def test_custom_rom_and_window_modes(ch, torch_mod, oracle):
         for cmd in (0xB1, 0x00):
             ch.set_filter_mode(cmd)
             ref = oracle.chain_q15(xf, rom, wm, cmd, None, None)
-            assert np.array_equal(ch.process_q15(_dev(torch_mod, xf)).cpu().numpy(), ref), (wm, cmd)
+            assert np.array_equal(ch.process_q15(to_device(torch_mod, xf)).cpu().numpy(), ref), (wm, cmd)
     # The same corner through the staging of the cascade kernels (the tests above reach it through the FFT-side window only):
     # a ROM whose -32768 entries sit in a few tiles, full-scale samples with -32768 at those very positions and at others,
     # all three cascade kernels, stream-ordered and with two launches in flight, time series and frames
@@ -291,16 +274,16 @@ def test_custom_rom_and_window_modes(ch, torch_mod, oracle):
         for cmd in (0x00, 0xA1, 0xA2):
             ch.set_filter_mode(cmd)
             ref_iq, ref_t = oracle.chain_q15(xg, rom2, 0, cmd, gui, sos14, want_time=True)
-            got = ch.process_q15(_dev(torch_mod, xg))
+            got = ch.process_q15(to_device(torch_mod, xg))
             ch.flush()
             assert np.array_equal(got.cpu().numpy(), ref_iq), (depth, cmd)
             if depth == 1:
-                assert np.array_equal(ch.filter_q15(_dev(torch_mod, xg)).cpu().numpy(), ref_t), cmd
+                assert np.array_equal(ch.filter_q15(to_device(torch_mod, xg)).cpu().numpy(), ref_t), cmd
     ch.set_overlap(1)
     ch.set_filter_mode(0xB1)
     ch.set_window_q15(None)
     ch.set_window_mode_q15(0)
-    assert np.array_equal(ch.process_q15(_dev(torch_mod, x)).cpu().numpy(), oracle.chain_q15(x))
+    assert np.array_equal(ch.process_q15(to_device(torch_mod, x)).cpu().numpy(), oracle.chain_q15(x))
 
 
 def test_command_byte_stream(ch, torch_mod, oracle):
@@ -334,7 +317,7 @@ def test_command_byte_stream(ch, torch_mod, oracle):
     ch.feed_command_bytes(wire + bytes([0xA1]))
     x = np.random.default_rng(5).integers(-2048, 2048, size=(2, N)).astype(np.int16)
     ref = oracle.chain_q15(x, None, 0, 0xA1, ch.coeffs_q7(), None)
-    assert np.array_equal(ch.process_q15(_dev(torch_mod, x)).cpu().numpy(), ref)
+    assert np.array_equal(ch.process_q15(to_device(torch_mod, x)).cpu().numpy(), ref)
 
 
 def test_frames_feed_the_reference_decoder_contract(ch, torch_mod):
@@ -342,7 +325,7 @@ def test_frames_feed_the_reference_decoder_contract(ch, torch_mod):
     g6 = load_golden("g6_frame.npz")
     g4 = load_golden("g4_q15_frames.npz")
     ch.set_filter_mode(0x00)
-    iq = ch.process_q15(_dev(torch_mod, g4["x"][2:3]))
+    iq = ch.process_q15(to_device(torch_mod, g4["x"][2:3]))
     fb = ch.frames_bytes(iq)
     assert len(fb) == 1 and fb[0] == g6["frame"].tobytes()
     assert np.array_equal(frames.decode_mag_16iq_le(fb[0]), g6["mag"])
@@ -353,7 +336,7 @@ def test_fxfft_close_to_float_fft_on_gpu(ch, torch_mod):
     x = rng.integers(-2048, 2048, size=(8, N)).astype(np.int16)
     rom = np.full(N, 32767, np.int16)                                  # ~unity window
     ch.set_window_q15(rom)
-    iq = ch.process_q15(_dev(torch_mod, x)).cpu().numpy().astype(np.float64)
+    iq = ch.process_q15(to_device(torch_mod, x)).cpu().numpy().astype(np.float64)
     ref = np.fft.fft(x.astype(np.float64), axis=-1) / N
     assert np.abs(iq[..., 0] + 1j * iq[..., 1] - ref).max() <= 7.0
 

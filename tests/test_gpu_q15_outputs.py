@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from conftest import N, load_golden
+from gpu_support import ch, to_device, torch_mod  # noqa: F401 (fixtures)
 
 pytestmark = pytest.mark.gpu
 
@@ -19,24 +20,6 @@ RANGES = [(0, N), (0, 8193), (100, 2000), (9000, 12000), (8000, 8400), (0, 1), (
 SA_EINVAL, SA_ESHAPE = -1, -2
 GUI_UPLOAD = np.array([0, 1, 0, 64, -67, 19, 64, 127, 64, 64, -85, 40], np.int8)      # gui.py:159-179, 1186-1192 defaults
 C12_SET = GUI_UPLOAD                      # the 12-byte set of test_gpu_q15.py::test_bit_exact_vs_integer_model is the same upload
-
-
-@pytest.fixture(scope="module")
-def torch_mod():
-    import torch
-    assert torch.cuda.is_available()
-    return torch
-
-
-@pytest.fixture()
-def ch(chain_cls):
-    c = chain_cls(0)
-    yield c
-    c.close()
-
-
-def _dev(torch_mod, a):
-    return torch_mod.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 def _decode(iq):
@@ -143,7 +126,7 @@ def test_mag_and_marker_equal_the_decoded_wire_frame(ch, torch_mod, oracle, form
     ch.set_filter_mode(cmd)
     x = _samples(rng, B, full)
     ref = oracle.chain_q15(x, rom, wm, cmd, c12, sos14)
-    xd = _dev(torch_mod, x)
+    xd = to_device(torch_mod, x)
     _check_all(ch, torch_mod, xd, ref, tag=form)
     if B >= 7:                                                   # the all-zero frame, spelled out
         assert not ref[1].any()
@@ -179,7 +162,7 @@ def test_extreme_frames(ch, torch_mod, oracle):
     bin 0 holds re = -32768 -- asserted on the oracle's frames, so the case cannot go missing: re^2 is 2^30 there,
     and a bin's integer power can reach 2^31, which fits uint32_t and not int32_t."""
     x = _extreme_frames()
-    xd = _dev(torch_mod, x)
+    xd = to_device(torch_mod, x)
     for cmd in (0xB1, 0x00):
         ch.set_filter_mode(cmd)
         _check_all(ch, torch_mod, xd, oracle.chain_q15(x, None, 0, cmd, None, None), tag=hex(cmd))
@@ -244,7 +227,7 @@ def test_rounding_cases_large_components(ch, torch_mod, oracle):
     assert n_re >= 10 and n_im >= 10, (n_re, n_im)
     ch.set_window_q15(rom)
     ch.set_filter_mode(0xB1)
-    _check_all(ch, torch_mod, _dev(torch_mod, x), ref, tag="tones")
+    _check_all(ch, torch_mod, to_device(torch_mod, x), ref, tag="tones")
 
 
 def test_tie_rule_mirror_bins(ch, torch_mod, oracle):
@@ -267,10 +250,10 @@ def test_tie_rule_mirror_bins(ch, torch_mod, oracle):
     ch.set_window_q15(rom)
     ch.set_filter_mode(0xB1)
     ch.set_marker_range(0, N)
-    pm, pb, bp = _records(ch.process_q15(_dev(torch_mod, x), out_kind="marker"))
+    pm, pb, bp = _records(ch.process_q15(to_device(torch_mod, x), out_kind="marker"))
     assert np.array_equal(pb[tie], bins[tie].astype(np.int32))
     assert np.array_equal(pb, pk.astype(np.int32))
-    _check_marker(ch.process_q15(_dev(torch_mod, x), out_kind="marker"), mag, ip, 0, N, "tones")
+    _check_marker(ch.process_q15(to_device(torch_mod, x), out_kind="marker"), mag, ip, 0, N, "tones")
 
 
 def _sine_tones():
@@ -304,7 +287,7 @@ def test_tie_rule_equal_floats_of_different_integer_powers(ch, torch_mod, oracle
     print(f"FIGURE tie rule: {int(kind.sum())} of {len(bins)} frames have equal floats of different integer powers at k and N - k")
     ch.set_window_q15(rom)
     ch.set_filter_mode(0xB1)
-    xd = _dev(torch_mod, x)
+    xd = to_device(torch_mod, x)
     ch.set_marker_range(0, N)
     rec = ch.process_q15(xd, out_kind="marker")
     pm, pb, bp = _records(rec)
@@ -351,7 +334,7 @@ def test_records_are_reproducible_across_calls_overlap_and_graphs(ch, torch_mod)
     positive time per call for the new kinds."""
     torch = torch_mod
     rng = np.random.default_rng(31)
-    xs = [_dev(torch, rng.integers(-2048, 2048, (600, N)).astype(np.int16)) for _ in range(4)]
+    xs = [to_device(torch, rng.integers(-2048, 2048, (600, N)).astype(np.int16)) for _ in range(4)]
     ch.reserve(600)
     for setup in (_setup_wide, lambda c: c.set_filter_mode(0x00)):
         setup(ch)
@@ -404,7 +387,7 @@ def test_range_is_stream_ordered(ch, torch_mod, oracle):
     x = rng.integers(-2048, 2048, (64, N)).astype(np.int16)
     ch.set_filter_mode(0x00)
     mag, ip = _decode(oracle.chain_q15(x, None, 0, 0x00, None, None))
-    xd = _dev(torch, x)
+    xd = to_device(torch, x)
     for depth in (1, 2):
         ch.set_overlap(depth)
         outs = []
@@ -433,7 +416,7 @@ def test_refusals_leave_the_handle_usable(ch, torch_mod, oracle):
     x = rng.integers(-2048, 2048, (4, N)).astype(np.int16)
     ref = oracle.chain_q15(x, None, 0, 0x00, None, None)
     mag, ip = _decode(ref)
-    xd = _dev(torch, x)
+    xd = to_device(torch, x)
     ch.set_filter_mode(0x00)
     ch.set_marker_range(300, 700)
     ch.set_profiling(64)
@@ -488,11 +471,11 @@ def test_frames_are_isolated(ch, torch_mod, oracle):
     keep = [i for i in range(9) if i != 4]
     for cmd in (0xB1, 0x00, 0xA2):
         ch.set_filter_mode(cmd)
-        alone_r = ch.process_q15(_dev(torch, x[keep]), out_kind="marker").cpu().numpy()
-        alone_m = ch.process_q15(_dev(torch, x[keep]), out_kind="mag").cpu().numpy()
+        alone_r = ch.process_q15(to_device(torch, x[keep]), out_kind="marker").cpu().numpy()
+        alone_m = ch.process_q15(to_device(torch, x[keep]), out_kind="mag").cpu().numpy()
         for e in range(4):
             y = x.copy()
             y[4] = ext[e]
-            yd = _dev(torch, y)
+            yd = to_device(torch, y)
             assert np.array_equal(ch.process_q15(yd, out_kind="marker").cpu().numpy()[keep], alone_r), (cmd, e)
             assert np.array_equal(_bits(ch.process_q15(yd, out_kind="mag").cpu().numpy()[keep]), _bits(alone_m)), (cmd, e)

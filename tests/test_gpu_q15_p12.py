@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from conftest import N
+from gpu_support import ch, check_overlap_profiling_and_graph_capture, to_device, torch_mod  # noqa: F401 (fixtures)
 
 pytestmark = pytest.mark.gpu
 
@@ -26,24 +27,6 @@ ZERO_B1_C12 = np.array([-14, 0, 14, 107, 21, 127, -15, 0, 15, 107, -21, 127], np
 # filter select, 12-byte upload or None, Q2.14 sections (how many of wide_sections()) or None
 MODES = {"0xB1": (0xB1, None, None), "0x00": (0x00, None, None), "0xA1-b1": (0xA1, GUI_C12, None),
          "0xA1-zero-b1": (0xA1, ZERO_B1_C12, None), "0xA2-six": (0xA2, None, 6), "0xA2-none": (0xA2, None, 0)}
-
-
-@pytest.fixture(scope="module")
-def torch_mod():
-    import torch
-    assert torch.cuda.is_available()
-    return torch
-
-
-@pytest.fixture()
-def ch(chain_cls):
-    c = chain_cls(0)
-    yield c
-    c.close()
-
-
-def _dev(torch_mod, a):
-    return torch_mod.from_numpy(np.array(a)).cuda()            # a copy: the shared batch is read-only
 
 
 @functools.lru_cache(maxsize=None)
@@ -107,7 +90,7 @@ def assert_packed_equals_int16(torch, ch, d_p, d_i, what):
 @pytest.mark.parametrize("mode", list(MODES))
 def test_packed_equals_int16_for_every_mode_and_kind(ch, torch_mod, mode, win_mode):
     x, p = batch()
-    d_i, d_p = _dev(torch_mod, x[:5]), _dev(torch_mod, p[:5])
+    d_i, d_p = to_device(torch_mod, x[:5]), to_device(torch_mod, p[:5])
     ch.set_window_mode_q15(win_mode)
     select(ch, mode)
     assert_packed_equals_int16(torch_mod, ch, d_p, d_i, (mode, win_mode))
@@ -115,7 +98,7 @@ def test_packed_equals_int16_for_every_mode_and_kind(ch, torch_mod, mode, win_mo
 
 def test_packed_equals_int16_with_a_custom_rom(ch, torch_mod):
     x, p = batch()
-    d_i, d_p = _dev(torch_mod, x[:5]), _dev(torch_mod, p[:5])
+    d_i, d_p = to_device(torch_mod, x[:5]), to_device(torch_mod, p[:5])
     ch.set_window_q15(np.random.default_rng(3).integers(-32768, 32768, N).astype(np.int16))
     for mode in ("0xB1", "0x00", "0xA2-six"):
         select(ch, mode)
@@ -127,7 +110,7 @@ def test_sample_order_against_the_integer_model(ch, torch_mod, oracle, mode):
     """An order check that does not go through the int16 kernels' loads: the integer model on unpack12 of the bytes."""
     from fpga_real_time_fft_analyzer_amd.ingest import unpack12
     x, p = batch()
-    d_p = _dev(torch_mod, p[:5])
+    d_p = to_device(torch_mod, p[:5])
     cmd, c12, sos = select(ch, mode)
     s = unpack12(p[:5])
     assert np.array_equal(s, x[:5])
@@ -142,7 +125,7 @@ def test_batch_geometry(ch, torch_mod, mode):
     slice of a larger tensor (its data pointer is offset by whole frames) equals the matching rows."""
     torch = torch_mod
     x, p = batch()
-    d_i, d_p = _dev(torch, x), _dev(torch, p)
+    d_i, d_p = to_device(torch, x), to_device(torch, p)
     select(ch, mode)
     for kind in ("iq", "marker", "filter"):
         ref = call(ch, kind, d_i).clone()
@@ -160,7 +143,7 @@ def test_batch_geometry(ch, torch_mod, mode):
 def test_marker_range_that_cuts_the_spectrum(ch, torch_mod):
     torch = torch_mod
     x, p = batch()
-    d_i, d_p = _dev(torch, x[:5]), _dev(torch, p[:5])
+    d_i, d_p = to_device(torch, x[:5]), to_device(torch, p[:5])
     ch.set_marker_range(100, 5000)
     for mode in ("0xB1", "0x00"):
         select(ch, mode)
@@ -177,46 +160,19 @@ def test_overlap_profiling_and_graph_capture(ch, torch_mod, mode):
     outputs equal the plain stream-ordered int16 call."""
     torch = torch_mod
     x, p = batch()
-    d_i, d_p = _dev(torch, x[:5]), _dev(torch, p[:5])
+    d_i, d_p = to_device(torch, x[:5]), to_device(torch, p[:5])
     select(ch, mode)
     ch.reserve(8)
     ref = ch.process_q15(d_i).clone()
     assert ref.any()
-    # overlap depth 2
-    ch.set_overlap(2)
-    outs = [torch.zeros_like(ref) for _ in range(3)]
-    for o in outs:
-        ch.process_q15(d_p, out=o)
-    ch.flush()
-    torch.cuda.synchronize()
-    ch.set_overlap(1)
-    for o in outs:
-        assert torch.equal(o, ref)
-    # launch timing: one time per call
-    ch.set_profiling(4)
-    out = torch.zeros_like(ref)
-    for _ in range(3):
-        ch.process_q15(d_p, out=out)
-    ms = ch.profile_read(4)
-    assert len(ms) == 3 and all(v > 0.0 for v in ms)
-    ch.set_profiling(0)
-    assert torch.equal(out, ref)
-    # graph capture and replay
-    graph = torch.cuda.CUDAGraph()
-    out.zero_()
-    with torch.cuda.graph(graph):
-        ch.process_q15(d_p, out=out)
-    out.zero_()
-    graph.replay()
-    torch.cuda.synchronize()
-    assert torch.equal(out, ref)
+    check_overlap_profiling_and_graph_capture(torch, ch, lambda out: ch.process_q15(d_p, out=out), ref)
 
 
 def test_argument_errors(ch, torch_mod):
     from fpga_real_time_fft_analyzer_amd.abi import SA_EINVAL, SA_ESHAPE, SA_OK, SA_Q15_OUT_IQ, SA_Q15_OUT_MARKER, SpecanError
     torch = torch_mod
     x, p = batch()
-    d_i, d_p = _dev(torch, x[:2]), _dev(torch, p[:2])
+    d_i, d_p = to_device(torch, x[:2]), to_device(torch, p[:2])
     ch.set_filter_mode(0x00)
     ref = ch.process_q15(d_i).clone()
     ref_t = ch.filter_q15(d_i).clone()

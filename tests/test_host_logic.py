@@ -1,4 +1,5 @@
 """CPU: host-side logic -- designer/quantiser mirror, frame helpers, IIR plan algebra."""
+import ctypes
 import os
 
 import numpy as np
@@ -259,6 +260,61 @@ def test_iir_plan_rejects_bad_sos(hip_lib_built):
     with pytest.raises(SpecanError):
         iir_plan_from_sos(np.array([[1, 0, 0, 0, 0, 0.0]]))     # a0 = 0
     assert int(iir_plan_from_sos(np.zeros((0, 6)))[:1].view(np.int32)[0]) == 0
+
+
+# ---- the tables of chain.py that every process call goes through (no handle, no GPU)
+def _chains():
+    from fpga_real_time_fft_analyzer_amd.chain import FLOAT_CHAIN, Q15_CHAIN, Q15_WINDOW_CHAIN
+    return {"float": FLOAT_CHAIN, "q15": Q15_CHAIN, "window": Q15_WINDOW_CHAIN}
+
+
+def test_output_spec_table():
+    import torch
+    from fpga_real_time_fft_analyzer_amd.abi import SA_EINVAL, SpecanError
+    from fpga_real_time_fft_analyzer_amd.chain import output_spec
+    chains = _chains()
+    want = {("float", "mag_full"): ((N,), torch.float32), ("float", "time"): ((N,), torch.float32),
+            ("float", "mag_half"): ((8193,), torch.float32), ("float", "spec_half"): ((8193,), torch.complex64),
+            ("float", "marker"): ((4,), torch.int32),
+            ("q15", "iq"): ((N, 2), torch.int16), ("q15", "mag"): ((N,), torch.float32),
+            ("q15", "marker"): ((4,), torch.int32),
+            ("window", None): ((N,), torch.int16)}
+    assert {(n, k) for n, c in chains.items() for k in c.outputs} == set(want)
+    for B in (0, 1, 5):
+        for (chain, kind), (frame, dtype) in want.items():
+            assert output_spec(chains[chain], kind, B) == ((B,) + frame, dtype), (kind, B)
+    for chain, kind in (("float", "iq"), ("float", None), ("q15", "mag_full"), ("q15", None),
+                        ("window", "iq"), ("float", "bogus")):
+        with pytest.raises(SpecanError) as e:
+            output_spec(chains[chain], kind, 1)
+        assert e.value.code == SA_EINVAL
+
+
+def test_entry_point_table():
+    import torch
+    from fpga_real_time_fft_analyzer_amd.abi import SA_P12_FRAME_BYTES, SIGNATURES
+    from fpga_real_time_fft_analyzer_amd.chain import _ARGS
+    chains = _chains()
+    f32, i16, p12 = torch.float32, torch.int16, torch.uint8
+    want = {("float", f32): "sa_process_f32", ("float", i16): "sa_process_f32_i16",
+            ("float", p12): "sa_process_f32_p12",
+            ("q15", i16): {"iq": "sa_process_q15", "mag": "sa_process_q15_out", "marker": "sa_process_q15_out"},
+            ("q15", p12): "sa_process_q15_p12",
+            ("window", i16): "sa_filter_q15", ("window", p12): "sa_filter_q15_p12"}
+    assert {(n, d) for n, c in chains.items() for d in c.inputs} == set(want)
+    assert [list(c.inputs)[0] for c in chains.values()] == [f32, i16, i16]
+    for (chain, dtype), name in want.items():
+        chain = chains[chain]
+        assert chain.inputs[dtype][0] == (SA_P12_FRAME_BYTES if dtype == p12 else N)
+        for kind in chain.outputs:
+            assert chain.inputs[dtype][1][kind][0] == (name[kind] if isinstance(name, dict) else name), (dtype, kind)
+    # the argument list each entry point is called with is the one the binding declares for it
+    for name, (takes_scale, takes_kind) in _ARGS.items():
+        argtypes = SIGNATURES[name][1]
+        assert (ctypes.c_float in argtypes) == takes_scale and argtypes.count(ctypes.c_int) == 1 + takes_kind, name
+        assert len(argtypes) == 5 + takes_scale + takes_kind
+    assert {call for c in chains.values() for _, calls in c.inputs.values() for call in calls.values()} == \
+        {(name,) + form for name, form in _ARGS.items()}
 
 
 # ---- N2 / N3 edges: framing front-end and UDP emitter (pure host logic)

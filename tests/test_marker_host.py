@@ -65,7 +65,7 @@ def test_library_exports_marker_range_calls(hip_lib_built):
 
 def test_chain_exposes_marker_kind():
     from fpga_real_time_fft_analyzer_amd import chain
-    assert chain._OUT_KINDS["marker"] == 4
+    assert chain.FLOAT_CHAIN.outputs["marker"][0] == 4
     assert callable(chain.SpectrumChain.set_marker_range) and callable(chain.SpectrumChain.markers)
 
 

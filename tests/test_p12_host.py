@@ -136,6 +136,23 @@ def test_packed_frame_cutter(hop):
     assert np.array_equal(fc.push(stream.tobytes()), want)   # bytes are taken too
 
 
+@pytest.mark.parametrize("hop", [16384, 4096])
+def test_int16_and_packed_cutters_cut_the_same_frames(hop):
+    """One stream of 3 x 16384 + 100 samples through both forms of the cutter, in chunks: 1000 samples, and 1001 bytes of
+    the packed stream (chunks end inside a sample pair).  The same frames after unpack12, the remainder left pending."""
+    s = np.random.default_rng(12).integers(-2048, 2048, 3 * N + 100).astype(np.int16)
+    k = (s.size - N) // hop + 1
+    want = np.stack([s[i * hop:i * hop + N] for i in range(k)])
+    fi = FrameCutter(hop)
+    got_i = np.concatenate([fi.push(s[i:i + 1000]) for i in range(0, s.size, 1000)])
+    assert got_i.dtype == np.int16 and np.array_equal(got_i, want) and fi.pending == s.size - k * hop
+    stream = pack12(s)
+    fp = FrameCutter(hop, packed=True)
+    got_p = np.concatenate([fp.push(stream[i:i + 1001]) for i in range(0, stream.size, 1001)])
+    assert got_p.dtype == np.uint8 and got_p.shape == (k, P12_FRAME_BYTES)
+    assert np.array_equal(unpack12(got_p), got_i) and fp.pending == stream.size - k * (3 * hop // 2)
+
+
 def test_standalone_program_under_host_sanitizers(tmp_path):
     """tests/cpp/test_sa_p12.cpp + csrc/sa_p12.cpp, host only, with -fsanitize=address,undefined when that links here
     (a plain build otherwise: the program's own checks still run)."""
