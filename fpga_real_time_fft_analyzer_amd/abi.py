@@ -23,7 +23,13 @@ SA_FILTER_DEFAULT, SA_FILTER_CUSTOM, SA_FILTER_NONE, SA_FILTER_WIDE = 0x00, 0xA1
 SA_WIN_RTL_SIGNED, SA_WIN_HANN_U16 = 0, 1
 SA_OUT_MAG_FULL, SA_OUT_MAG_HALF, SA_OUT_SPEC_HALF, SA_OUT_TIME, SA_OUT_MARKER = 0, 1, 2, 3, 4
 SA_Q15_OUT_IQ, SA_Q15_OUT_MAG, SA_Q15_OUT_MARKER = 0, 1, 2
+SA_Q15_TRACE_LOG2W_MIN, SA_Q15_TRACE_LOG2W_MAX = 1, 6
 SA_PRECISION_F32, SA_PRECISION_F64_STATE = 0, 1
+
+
+def SA_Q15_TRACE_KIND(log2w: int) -> int:
+    """The out_kind of the Q15 chain's display trace with buckets of 2**log2w bins (the macro of include/specan.h)."""
+    return 0x10 | log2w
 
 
 class CmdEvents(C.Structure):
@@ -35,6 +41,11 @@ class CmdEvents(C.Structure):
 class MarkerQ15(C.Structure):
     """sa_marker_q15 of include/specan.h: one SA_Q15_OUT_MARKER record, 16 bytes."""
     _fields_ = [("peak_mag", C.c_float), ("peak_bin", C.c_int32), ("band_power", C.c_uint64)]
+
+
+class TracePointQ15(C.Structure):
+    """sa_trace_point_q15 of include/specan.h: one record of SA_Q15_TRACE_KIND(k), 8 bytes."""
+    _fields_ = [("peak_mag", C.c_float), ("power", C.c_float)]
 
 
 class SpecanError(RuntimeError):

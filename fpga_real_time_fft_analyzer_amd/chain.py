@@ -79,6 +79,12 @@ _Q15_OUT = {"iq": (SA_Q15_OUT_IQ, (SA_N, 2), torch.int16),
             "marker": (SA_Q15_OUT_MARKER, (4,), torch.int32)}
 Q15_CHAIN = _Chain(_Q15_OUT, {torch.int16: _form(SA_N, _Q15_OUT, "sa_process_q15_out", iq="sa_process_q15"),
                               torch.uint8: _form(SA_P12_FRAME_BYTES, _Q15_OUT, "sa_process_q15_p12")})
+# the Q15 chain's display trace (traces_q15): one output per bucket width W = 2^k, named by W; a table of its own, so that
+# process_q15(out_kind=...) keeps the three kinds it has
+_TRACE_OUT = {1 << k: (abi.SA_Q15_TRACE_KIND(k), (SA_N >> k, 2), torch.float32)
+              for k in range(abi.SA_Q15_TRACE_LOG2W_MIN, abi.SA_Q15_TRACE_LOG2W_MAX + 1)}
+Q15_TRACE_CHAIN = _Chain(_TRACE_OUT, {torch.int16: _form(SA_N, _TRACE_OUT, "sa_process_q15_out"),
+                                      torch.uint8: _form(SA_P12_FRAME_BYTES, _TRACE_OUT, "sa_process_q15_p12")})
 # the Q15 chain without its FFT (filter_q15): one output, which has no name
 _WINDOW_OUT = {None: (SA_Q15_OUT_IQ, (SA_N,), torch.int16)}
 Q15_WINDOW_CHAIN = _Chain(_WINDOW_OUT, {torch.int16: _form(SA_N, _WINDOW_OUT, "sa_filter_q15"),
@@ -426,6 +432,17 @@ class SpectrumChain:
         :meth:`process_q15`."""
         rec = self.process_q15(x, out, out_kind="marker")
         return rec.view(torch.float32)[:, 0], rec[:, 1], rec.view(torch.int64)[:, 1]
+
+    def traces_q15(self, x: torch.Tensor, bucket: int = 16, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The display trace of the integer chain's frames: [B, 16384 // bucket, 2] float32, one sa_trace_point_q15 per
+        bucket of ``bucket`` consecutive bins of the full spectrum (include/specan.h, SA_Q15_TRACE_KIND).  ``[..., 0]`` is
+        the peak, the largest 'mag' value of the bucket bit for bit; ``[..., 1]`` the power, the exact integer sum of
+        re^2 + im^2 over the bucket rounded once to float32 (frames.trace_of_frame is the numpy mirror).  ``bucket`` is
+        2, 4, 8, 16, 32 or 64 -- anything else is SA_EINVAL before any device call; the marker range plays no part.
+        ``x`` is int16 or packed uint8 as for :meth:`process_q15`."""
+        if isinstance(bucket, bool) or not isinstance(bucket, (int, np.integer)) or int(bucket) not in _TRACE_OUT:
+            raise SpecanError(abi.SA_EINVAL, f"bucket must be one of {sorted(_TRACE_OUT)}")
+        return self._process(Q15_TRACE_CHAIN, x, out, int(bucket))
 
     def filter_q15(self, x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Window (+ integer IIR) only: the FFT input stream, [B,16384] int16.  ``x`` is [B,16384] int16 or the same

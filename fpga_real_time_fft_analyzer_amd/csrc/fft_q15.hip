@@ -288,6 +288,91 @@ __device__ __forceinline__ void fx_mark_finish(FxMark a, uint4 *scr, void *__res
             make_uint4(__builtin_bit_cast(unsigned, a.mag), (unsigned)a.bin, (unsigned)a.pow, (unsigned)(a.pow >> 32));
 }
 
+// ---- SA_Q15_TRACE_KIND(k): one record {peak_mag, power} per bucket of W = 2^k consecutive bins (k = 1..6) -------------
+// After stage 6 thread t holds bin t + 1024 m': a bucket is W adjacent lanes of one wave at one m', aligned to W, so the
+// reduction is a xor butterfly over the lane bits 0..k-1 and never leaves the wave.  No LDS image, no barrier.
+//   peak:  the float sums s = fl(fl(re re) + fl(im im)) are non-negative, so their order is the order of their bit
+//          patterns: an unsigned maximum, then ONE root per bucket (the correctly rounded root is monotone).
+//   power: the integer power re^2 + im^2 <= 2^31 goes as its two 16-bit halves; a bucket's sums of halves are at most
+//          64 x 65535 < 2^22 and 64 x 32768 = 2^21, exact in 32 bits whatever the frame holds.  Both sums are exact as
+//          floats (below 2^24), and so is hi 2^16; fma(hi, 2^16, lo) rounds the exact value hi 2^16 + lo ONCE, to
+//          nearest even: the float32 nearest to the exact integer sum.
+// The template value of the epilogue arm; the bucket width itself is a run-time word (the kernel's trailing argument).
+constexpr int kFxOutTrace = SA_Q15_TRACE_KIND(0);
+
+struct FxTrace {
+    unsigned s, lo, hi;                                      // bits of max s; sums of the low / high halves of the power
+};
+
+// a <- a (+) the part of the lane that DPP control CTRL names (a lane inside the same row of 16)
+template <int CTRL>
+__device__ __forceinline__ void fx_trace_dpp(FxTrace &a)
+{
+    const unsigned s = (unsigned)__builtin_amdgcn_update_dpp(0, (int)a.s, CTRL, 0xF, 0xF, true);
+    const unsigned lo = (unsigned)__builtin_amdgcn_update_dpp(0, (int)a.lo, CTRL, 0xF, 0xF, true);
+    const unsigned hi = (unsigned)__builtin_amdgcn_update_dpp(0, (int)a.hi, CTRL, 0xF, 0xF, true);
+    a.s = a.s > s ? a.s : s;
+    a.lo += lo;
+    a.hi += hi;
+}
+
+// One m' of a wave, K = log2 W.  The steps for lane bits 0..3 stay in the VALU: quad_perm [1,0,3,2] and [2,3,0,1] are
+// lane ^ 1 and lane ^ 2; after them the four lanes of a quad agree, so row_half_mirror (lane 7 - i of the eight) reads the
+// other quad's part, and after that the eight agree and row_mirror (lane 15 - i) reads the other eight's.  Bit 4 is one
+// ds_swizzle (lane ^ 16, as in fx_mark_swizzle).  Bit 5 (W = 64: lane 0 alone stores) takes the upper half-wave's part from
+// lane 32 through scalar registers.  All 64 lanes run every step; the first lane of each bucket stores its record.
+template <int K>
+__device__ __forceinline__ void fx_trace_point(unsigned p, int t, uint2 *__restrict__ row, int bin)
+{
+    const unsigned pw = (unsigned)fx_dot2(p, p);
+    FxTrace a = {__builtin_bit_cast(unsigned, fx_mag_sum(p)), pw & 0xFFFFu, pw >> 16};
+    fx_trace_dpp<0xB1>(a);
+    if constexpr (K >= 2) fx_trace_dpp<0x4E>(a);
+    if constexpr (K >= 3) fx_trace_dpp<0x141>(a);
+    if constexpr (K >= 4) fx_trace_dpp<0x140>(a);
+    if constexpr (K >= 5) {
+        constexpr int pat = (16 << 10) | 0x1F;
+        const unsigned s = (unsigned)__builtin_amdgcn_ds_swizzle((int)a.s, pat);
+        a.lo += (unsigned)__builtin_amdgcn_ds_swizzle((int)a.lo, pat);
+        a.hi += (unsigned)__builtin_amdgcn_ds_swizzle((int)a.hi, pat);
+        a.s = a.s > s ? a.s : s;
+    }
+    if constexpr (K >= 6) {
+        const unsigned s = (unsigned)__builtin_amdgcn_readlane((int)a.s, 32);
+        a.lo += (unsigned)__builtin_amdgcn_readlane((int)a.lo, 32);
+        a.hi += (unsigned)__builtin_amdgcn_readlane((int)a.hi, 32);
+        a.s = a.s > s ? a.s : s;
+    }
+    const float peak = fx_sqrt_rn(__builtin_bit_cast(float, a.s));
+    const float power = __builtin_fmaf((float)a.hi, 65536.f, (float)a.lo);
+    if ((t & ((1 << K) - 1)) == 0)
+        row[bin >> K] = make_uint2(__builtin_bit_cast(unsigned, peak), __builtin_bit_cast(unsigned, power));
+}
+
+// The thread's 16 bins q[m'] = bin t + 1024 m' into the frame's row of 16384 >> K records: one straight-line block per
+// width, so the sixteen reductions interleave and no step waits on the one before it.
+template <int K>
+__device__ __forceinline__ void fx_trace_rows(const unsigned (&q)[16], int t, void *__restrict__ out, int f)
+{
+    uint2 *row = reinterpret_cast<uint2 *>(out) + (size_t)f * (SA_NPTS >> K);
+#pragma unroll
+    for (int m = 0; m < 16; ++m) fx_trace_point<K>(q[m], t, row, t + kFftWide * m);
+}
+
+// k is wave-uniform (a kernel argument): one scalar branch per frame
+__device__ __forceinline__ void fx_trace_frame(const unsigned (&q)[16], int k, int t, void *__restrict__ out, int f)
+{
+    switch (k) {
+        case 1: fx_trace_rows<1>(q, t, out, f); break;
+        case 2: fx_trace_rows<2>(q, t, out, f); break;
+        case 3: fx_trace_rows<3>(q, t, out, f); break;
+        case 4: fx_trace_rows<4>(q, t, out, f); break;
+        case 5: fx_trace_rows<5>(q, t, out, f); break;
+        case 6: fx_trace_rows<6>(q, t, out, f); break;
+        default: break;                                      // the host admits 1..6 only
+    }
+}
+
 // SA-FXFFT-1 with 1024 threads per frame: 16 positions per thread (t + 1024 m); the seven radix-4 stages run as four
 // register passes -- stage 0 from global memory, then (1,2), (3,4), (5,6) -- with one LDS exchange between passes.
 // (Round 1 and most of round 2 ran 256 threads x 64 positions, stages 4..6 in registers: 120 registers per thread, 2 waves
@@ -302,7 +387,8 @@ __device__ __forceinline__ void fx_mark_finish(FxMark a, uint4 *scr, void *__res
 // 8 waves per SIMD (two frames per CU, 64 KiB of LDS each) need <= 64 registers: the second launch bound asks for that.
 // OUT (SA_Q15_OUT_*): what the epilogue makes of the natural-order bins -- the wire frame itself, its magnitudes, or the
 // marker record over the bins [mrange & 0xFFFF, mrange >> 16) (read by the MARKER instantiations only; last in the
-// arguments, so the other kinds' argument loads are where they were).
+// arguments, so the other kinds' argument loads are where they were) -- or, OUT = kFxOutTrace, the bucket records of
+// SA_Q15_TRACE_KIND(k), for which the same trailing word carries k.
 constexpr int kFftLds = SA_NPTS * 4;                      // the frame image; MARKER: + kFxMarkParts x 16 bytes behind it
 
 // Stage 0's samples of thread t, x[m] = sample t + 1024 m of frame f.  int16 samples: 2-byte loads, 128 contiguous bytes
@@ -345,27 +431,29 @@ __device__ __forceinline__ void fx_load16(const SaP12 *in, int f, int t, int (&x
 #undef SA_FX_KERNEL
 #undef SA_FX_IN
 
+// `log2w`: the k of SA_Q15_TRACE_KIND(k), which rides in the kernel's trailing word in place of the marker range
 template <int OUT, typename K, typename InT>
 hipError_t launch_fft_q15(K k, const InT *in_time, void *out, int batch, const SaQ15Params &p, const SaQ15Tables &t,
-                          hipStream_t stream, SaLaunchEv ev)
+                          int log2w, hipStream_t stream, SaLaunchEv ev)
 {
     const dim3 grid(batch), block(kFftWide);
     const int lds = kFftLds + (OUT == SA_Q15_OUT_MARKER ? kFxMarkParts * (int)sizeof(uint4) : 0);
     const hipError_t e = sa_set_dyn_lds_once(reinterpret_cast<const void *>(k), lds);
     if (e != hipSuccess) return e;
-    hipExtLaunchKernelGGL(k, grid, block, lds, stream, ev.start, ev.stop, 0, in_time, out, batch, p, t.rom, t.tw, t.twrec,
-                          (unsigned)t.marker_lo | (unsigned)t.marker_hi << 16);
+    const unsigned word = OUT == kFxOutTrace ? (unsigned)log2w : (unsigned)t.marker_lo | (unsigned)t.marker_hi << 16;
+    hipExtLaunchKernelGGL(k, grid, block, lds, stream, ev.start, ev.stop, 0, in_time, out, batch, p, t.rom, t.tw, t.twrec, word);
     return hipGetLastError();
 }
 
 template <int OUT>
 hipError_t launch_fft_q15(const void *in_time, SaInKind in_kind, void *out, int batch, bool apply_window, const SaQ15Params &p,
-                          const SaQ15Tables &t, hipStream_t stream, SaLaunchEv ev)
+                          const SaQ15Tables &t, int log2w, hipStream_t stream, SaLaunchEv ev)
 {
     if (in_kind == SaInKind::P12)
-        return launch_fft_q15<OUT>(fft_q15_p12_kernel<true, OUT>, static_cast<const SaP12 *>(in_time), out, batch, p, t, stream, ev);
+        return launch_fft_q15<OUT>(fft_q15_p12_kernel<true, OUT>, static_cast<const SaP12 *>(in_time), out, batch, p, t, log2w,
+                                   stream, ev);
     return launch_fft_q15<OUT>(apply_window ? fft_q15_kernel<true, OUT> : fft_q15_kernel<false, OUT>,
-                               static_cast<const int16_t *>(in_time), out, batch, p, t, stream, ev);
+                               static_cast<const int16_t *>(in_time), out, batch, p, t, log2w, stream, ev);
 }
 
 }  // namespace
@@ -375,10 +463,12 @@ hipError_t sa_launch_fft_q15(const void *in_time, SaInKind in_kind, void *out, i
 {
     if (in_kind != SaInKind::I16 && !(in_kind == SaInKind::P12 && apply_window)) return hipErrorInvalidValue;
     if (batch <= 0) return hipSuccess;
+    if (out_kind >= SA_Q15_TRACE_KIND(SA_Q15_TRACE_LOG2W_MIN) && out_kind <= SA_Q15_TRACE_KIND(SA_Q15_TRACE_LOG2W_MAX))
+        return launch_fft_q15<kFxOutTrace>(in_time, in_kind, out, batch, apply_window, p, t, out_kind - kFxOutTrace, stream, ev);
     switch (out_kind) {
-        case SA_Q15_OUT_IQ: return launch_fft_q15<SA_Q15_OUT_IQ>(in_time, in_kind, out, batch, apply_window, p, t, stream, ev);
-        case SA_Q15_OUT_MAG: return launch_fft_q15<SA_Q15_OUT_MAG>(in_time, in_kind, out, batch, apply_window, p, t, stream, ev);
-        case SA_Q15_OUT_MARKER: return launch_fft_q15<SA_Q15_OUT_MARKER>(in_time, in_kind, out, batch, apply_window, p, t, stream, ev);
+        case SA_Q15_OUT_IQ: return launch_fft_q15<SA_Q15_OUT_IQ>(in_time, in_kind, out, batch, apply_window, p, t, 0, stream, ev);
+        case SA_Q15_OUT_MAG: return launch_fft_q15<SA_Q15_OUT_MAG>(in_time, in_kind, out, batch, apply_window, p, t, 0, stream, ev);
+        case SA_Q15_OUT_MARKER: return launch_fft_q15<SA_Q15_OUT_MARKER>(in_time, in_kind, out, batch, apply_window, p, t, 0, stream, ev);
         default: return hipErrorInvalidValue;
     }
 }

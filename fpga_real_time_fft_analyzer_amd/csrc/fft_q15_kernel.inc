@@ -127,10 +127,14 @@ __global__ __launch_bounds__(kFftWide, 8) void SA_FX_KERNEL(const SA_FX_IN *__re
     // frame layout: [16384] x (re, im) int16 = 65536 bytes (imp/sequ2.vhd:153); one dword per lane
     // SA_Q15_OUT_MAG: the same dwords at the same offsets of a float row, each the magnitude of its bin.
     // SA_Q15_OUT_MARKER: no spectrum store; the thread keeps the 16 sums re^2 + im^2 of its bins and roots their largest.
+    // kFxOutTrace: no spectrum store either; the thread keeps its 16 bins, then per m' the wave reduces its 64 bins to
+    // 64 / W records (W = 1 << mrange) and the first lane of each bucket stores one: row [16384 / W] of the frame
+    // (fx_trace_frame).
     unsigned *o32 = reinterpret_cast<unsigned *>(reinterpret_cast<int16_t *>(out) + (size_t)f * SA_NPTS * 2);
     const int mlo = (int)(mrange & 0xFFFFu), mhi = (int)(mrange >> 16);
     float ms[16];
     unsigned long long mpow = 0ull;
+    unsigned tq[16];
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
         unsigned o[4];
@@ -143,11 +147,14 @@ __global__ __launch_bounds__(kFftWide, 8) void SA_FX_KERNEL(const SA_FX_IN *__re
                 __builtin_nontemporal_store(o[i], o32 + t + kFftWide * mp);   // streaming: written once
             else if constexpr (OUT == SA_Q15_OUT_MAG)
                 __builtin_nontemporal_store(fx_mag(o[i]), reinterpret_cast<float *>(o32) + t + kFftWide * mp);
-            else
+            else if constexpr (OUT == SA_Q15_OUT_MARKER)
                 ms[mp] = fx_mark_sum_any(mpow, o[i], t + kFftWide * mp, (wave << 6) + kFftWide * mp, mlo, mhi);
+            else
+                tq[mp] = o[i];
         }
     }
     if constexpr (OUT == SA_Q15_OUT_MARKER) {
         fx_mark_finish(fx_mark_thread(ms, t, mpow), reinterpret_cast<uint4 *>(smem_q + kFftLds), out, f, t, wave);
     }
+    if constexpr (OUT == kFxOutTrace) fx_trace_frame(tq, (int)mrange, t, out, f);
 }

@@ -173,6 +173,7 @@ constexpr int kSaTwRecs = 4096 + 1024 + 256;
 // The FFT takes P12 only with apply_window: a cascade's output, the only unwindowed input there is, is int16.
 hipError_t sa_launch_filter_q15(const void *in, SaInKind in_kind, int16_t *out_time, int batch, const SaQ15Params &p,
                                 const SaQ15Tables &t, hipStream_t stream, SaLaunchEv ev);
-// out per out_kind (SA_Q15_OUT_*): int16 [B,16384,2], float [B,16384] or sa_marker_q15 [B]
+// out per out_kind: SA_Q15_OUT_* -- int16 [B,16384,2], float [B,16384] or sa_marker_q15 [B] -- or SA_Q15_TRACE_KIND(k),
+// k = 1..6: sa_trace_point_q15 [B, 16384 >> k] (the width reaches the kernel in the word that carries the marker range)
 hipError_t sa_launch_fft_q15(const void *in_time, SaInKind in_kind, void *out, int batch, int out_kind, bool apply_window,
                              const SaQ15Params &p, const SaQ15Tables &t, hipStream_t stream, SaLaunchEv ev);

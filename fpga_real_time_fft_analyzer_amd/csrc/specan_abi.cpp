@@ -420,21 +420,24 @@ static SaQ15Params q15_params(const sa_handle *h)
 
 // The argument checks of process_q15 and process_float, made before anything else; callers of the ABI see their order.
 // The output kinds of both chains run from 0 to `marker`, the marker records (`marker_name` in the message).
+// `trace`: the entry point also takes the SA_Q15_TRACE_KIND(k) family (the Q15 FFT calls; never the float chain).
 // `scale_finite`: what process_float found of its scale, which is refused between the kind and the empty batch (process_q15
 // has no scale: true).  An empty batch returns SA_OK here, and the caller returns it at once.
 static int check_process_args(sa_handle *h, const char *fn, const void *in, SaInKind kind, const void *out, int batch,
-                              int out_kind, int marker, const char *marker_name, bool scale_finite)
+                              int out_kind, int marker, const char *marker_name, bool trace, bool scale_finite)
 {
     static_assert(SA_OUT_MAG_FULL == 0 && SA_Q15_OUT_IQ == 0, "the kinds of both chains are 0 .. marker");
     if (!h) return SA_EINVAL;
     if (batch < 0) return fail_at(h, SA_ESHAPE, fn, "negative batch");
-    if (out_kind < 0 || out_kind > marker) return fail_at(h, SA_EINVAL, fn, "bad out_kind");
+    const bool is_trace = trace && out_kind >= SA_Q15_TRACE_KIND(SA_Q15_TRACE_LOG2W_MIN) &&
+                          out_kind <= SA_Q15_TRACE_KIND(SA_Q15_TRACE_LOG2W_MAX);
+    if (!is_trace && (out_kind < 0 || out_kind > marker)) return fail_at(h, SA_EINVAL, fn, "bad out_kind");
     if (!scale_finite) return fail_at(h, SA_EINVAL, fn, "scale is not finite");
     if (batch == 0) return SA_OK;
     if (!in || !out) return fail_at(h, SA_EINVAL, fn, "NULL tensor");
-    if (out_kind == marker && ((uintptr_t)out & 15u) != 0) {
+    if ((out_kind == marker || is_trace) && ((uintptr_t)out & 15u) != 0) {
         char msg[64];
-        std::snprintf(msg, sizeof msg, "%s output must be 16-byte aligned", marker_name);
+        std::snprintf(msg, sizeof msg, "%s output must be 16-byte aligned", is_trace ? "SA_Q15_TRACE_KIND" : marker_name);
         return fail_at(h, SA_EINVAL, fn, msg);
     }
     if (kind == SaInKind::P12 && ((uintptr_t)in & 15u) != 0)       // the stage-ins issue 16-byte requests; every frame is then aligned
@@ -443,12 +446,12 @@ static int check_process_args(sa_handle *h, const char *fn, const void *in, SaIn
 }
 
 // sa_filter_q15 (`fft` false: window + integer cascade into `out`, out_kind unused) and sa_process_q15 / sa_process_q15_out
-// (`out` per out_kind, SA_Q15_OUT_*: the FFT launch's epilogue makes it), on int16 samples or, the _p12 entry points, on
-// packed 12-bit samples (`kind`: I16 or P12); `fn` names the entry point
+// (`out` per out_kind, SA_Q15_OUT_* or SA_Q15_TRACE_KIND(k): the FFT launch's epilogue makes it), on int16 samples or, the
+// _p12 entry points, on packed 12-bit samples (`kind`: I16 or P12); `fn` names the entry point
 static int process_q15(sa_handle *h, const char *fn, const void *in, SaInKind kind, void *out, int batch, int out_kind,
                        void *stream, bool fft)
 {
-    { const int rc = check_process_args(h, fn, in, kind, out, batch, out_kind, SA_Q15_OUT_MARKER, "SA_Q15_OUT_MARKER", true);
+    { const int rc = check_process_args(h, fn, in, kind, out, batch, out_kind, SA_Q15_OUT_MARKER, "SA_Q15_OUT_MARKER", fft, true);
       if (rc != SA_OK || batch == 0) return rc; }
     SA_HIP(h, hipSetDevice(h->device));
     const SaQ15Params p = q15_params(h);
@@ -514,7 +517,7 @@ static int process_float(sa_handle *h, const char *fn, const void *in, SaInKind 
                          int out_kind, void *stream)
 {
     const bool scale_finite = scale == scale && scale - scale == 0.f;
-    { const int rc = check_process_args(h, fn, in, kind, out, batch, out_kind, SA_OUT_MARKER, "SA_OUT_MARKER", scale_finite);
+    { const int rc = check_process_args(h, fn, in, kind, out, batch, out_kind, SA_OUT_MARKER, "SA_OUT_MARKER", false, scale_finite);
       if (rc != SA_OK || batch == 0) return rc; }
     if (h->filter_mode == SA_FILTER_WIDE)
         return fail_at(h, SA_ESTATE, fn, "filter mode 0xA2 (Q2.14) belongs to the Q15 path; use 0xA1 with sa_load_sos_f32");

@@ -41,6 +41,23 @@ def marker_of_frame(frame_bytes: bytes, lo: int = 0, hi: int = FFT_SIZE):
     return np.float32(mag.max()), lo + int(mag.argmax()), int(power)
 
 
+TRACE_BUCKETS = (2, 4, 8, 16, 32, 64)
+
+
+def trace_of_frame(frame_bytes: bytes, bucket: int):
+    """A frame reduced to P = 16384 // bucket display points, point j over the bins [j bucket, (j + 1) bucket): ``(peak
+    float32 [P], power float32 [P], exact int64 [P])`` -- the largest decoded magnitude of each bucket, the exact integer
+    sum of re^2 + im^2 over it rounded once to float32 (numpy's int64 -> float32 conversion rounds to nearest even), and
+    that sum itself.  The host mirror of one frame's sa_trace_point_q15 records (include/specan.h, SA_Q15_TRACE_KIND)."""
+    if isinstance(bucket, bool) or not isinstance(bucket, (int, np.integer)) or int(bucket) not in TRACE_BUCKETS:
+        raise ValueError(f"bucket must be one of {TRACE_BUCKETS}")
+    bucket = int(bucket)
+    peak = decode_mag_16iq_le(frame_bytes).reshape(-1, bucket).max(axis=1)
+    re, im = _iq(frame_bytes)
+    exact = (re.astype(np.int64) ** 2 + im.astype(np.int64) ** 2).reshape(-1, bucket).sum(axis=1)
+    return peak, exact.astype(np.float32), exact
+
+
 def decode_iq_components(frame_bytes: bytes):
     """Same result as gui.py:262-270: (re, im) as float32 arrays."""
     re, im = _iq(frame_bytes)

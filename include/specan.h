@@ -146,6 +146,31 @@ typedef struct sa_marker_q15 {
     uint64_t band_power;  /* sum over k in [lo, hi) of re[k]^2 + im[k]^2, exact */
 } sa_marker_q15;          /* 16 bytes; one aligned store per frame */
 
+/* A fourth family of output kinds of sa_process_q15_out() and sa_process_q15_p12(): the display trace (build extension; ABI
+ * version 4, added compatibly).  The bucket width travels inside the kind -- SA_Q15_TRACE_KIND(k) = 0x10 | k = 17..22 for
+ * W = 2^k = 2..64 bins -- so there is no control state to set and nothing a captured graph could freeze.  A display has
+ * about a thousand columns; gui.py:294-305, 415-455 ship all 16384 magnitudes of a frame to one.  An analyser's detector
+ * reduces the bins that fall into a column before they leave the instrument, and this kind is that detector, made in the
+ * FFT kernel's epilogue with no spectrum stored: P = 16384 / W records of 8 bytes per frame (8 KiB at W = 16) instead of
+ * 64 KiB.
+ *   - `out` is sa_trace_point_q15 [B, P]; point j covers the bins [jW, (j+1)W) of the full N-bin spectrum as
+ *     SA_Q15_OUT_MAG lays it out.  Always the whole spectrum: the handle's marker range has no part in it.
+ *   - peak_mag is the maximum of the SA_Q15_OUT_MAG values of the bucket, bit for bit (the positive-peak detector).  The
+ *     correctly rounded root is monotone, so this is the root of the bucket's largest s = fl(fl(r*r) + fl(i*i)).
+ *   - power is the float32 nearest (ties to even) to the EXACT integer sum over the bucket of re^2 + im^2 (at most
+ *     64 x 2^31 = 2^37): one rounding of an exact sum, not a float accumulation, so it is order-free and bit-reproducible
+ *     (the sample detector's power, or the RMS detector's after a division by W and a root on the host).
+ *   - an all-zero frame gives (+0.0f, +0.0f) in every point.
+ *   - `out` must be 16-byte aligned; SA_Q15_TRACE_KIND(0), SA_Q15_TRACE_KIND(7) and every other value outside the kinds
+ *     listed here are SA_EINVAL.  The float entry points refuse these values: they are kinds of the Q15 chain alone. */
+#define SA_Q15_TRACE_KIND(log2w) (0x10 | (log2w))
+#define SA_Q15_TRACE_LOG2W_MIN 1
+#define SA_Q15_TRACE_LOG2W_MAX 6
+typedef struct sa_trace_point_q15 {
+    float peak_mag;       /* max over the bucket of the SA_Q15_OUT_MAG value */
+    float power;          /* the exact sum over the bucket of re[k]^2 + im[k]^2, rounded once to float32 */
+} sa_trace_point_q15;     /* 8 bytes; one store per bucket */
+
 /* precision of the float path's window and cascade (sa_set_precision) */
 #define SA_PRECISION_F32       0   /* default: float32 arithmetic throughout, one fused kernel per call */
 #define SA_PRECISION_F64_STATE 1   /* window, inter-section signal and DF2T recursion in float64; FFT in float32 */
@@ -273,7 +298,8 @@ int sa_process_q15(sa_handle *h, const int16_t *in, int16_t *out_iq, int batch, 
  * 691-712), 16 bytes per frame instead of 64 KiB.  Everything sa_process_q15() does holds for every kind: all four filter
  * modes, both window modes, custom ROMs, every overlap depth, launch timing, hipGraph capture once sa_reserve() has
  * sized the workspace.  SA_EINVAL for an unknown kind, a NULL tensor or a marker `out` that is not 16-byte aligned:
- * nothing is launched and no call state changes. */
+ * nothing is launched and no call state changes.  out_kind may also be SA_Q15_TRACE_KIND(k), k = 1..6 (above): one
+ * sa_trace_point_q15 per bucket of 2^k bins, under the same rules, its `out` 16-byte aligned as well. */
 int sa_process_q15_out(sa_handle *h, const int16_t *in, void *out, int batch, int out_kind, void *stream);
 
 /* Window (+ integer IIR) only: the FFT input stream, [B,16384] int16 (fft_in16 of
@@ -329,7 +355,7 @@ int sa_process_f32_p12(sa_handle *h, const uint8_t *in /* [B,24576] device */, f
  * FPGA-exact mode, and its real input is exactly that 12-bit stream: imp/dsp_system_top.vhd:435 sign-extends
  * adc_out(15 downto 4) into the 16-bit sample the window takes (new/hann8192.vhd:36-39).  `in` is the p12 format defined
  * above, [B,24576] uint8, 16-byte aligned (SA_EINVAL otherwise: the rule of sa_process_f32_p12).
- *   sa_process_q15_p12: `out` per out_kind (SA_Q15_OUT_IQ, SA_Q15_OUT_MAG or SA_Q15_OUT_MARKER) -- the results of
+ *   sa_process_q15_p12: `out` per out_kind (SA_Q15_OUT_IQ, SA_Q15_OUT_MAG, SA_Q15_OUT_MARKER or SA_Q15_TRACE_KIND(k)) -- the results of
  *     sa_process_q15_out() (imp/sequ2.vhd:153 frames, gui.py:250-260 magnitudes, gui.py:294-305 / 691-712 markers) on
  *     sa_unpack_samples_p12(in), bit for bit;
  *   sa_filter_q15_p12: the FFT input stream (fft_in16 of new/command_control.vhd:90-123) -- the results of sa_filter_q15()
