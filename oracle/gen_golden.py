@@ -6,7 +6,9 @@ What comes from where:
     and the pure helpers of scripts/fft_analyzer_gui.py (design_iir_filter :108,
     quantize_coefficients :159, decode_mag_16iq_le :250, decode_iq_components :262,
     MultiPacketAssembler :308) with PyQt5 / flask_socketio stubbed in sys.modules
-    (both absent here -> ordinary ModuleNotFoundError; nothing was denied by the environment).
+    (both absent here -> ordinary ModuleNotFoundError; nothing was denied by the environment);
+    for G7 its socket handlers, receivers and start-up block as well, run against recording
+    stand-ins (oracle/gui_sessions.py, which lists the arrays of g7_gui_sessions.npz).
   * stock scipy.signal.sosfilt / numpy.fft (the float oracle BASELINE.json names).
   * this build's integer model (oracle/specan_oracle.c) for G4 -- the reference has no
     RTL simulator output; those vectors are pinned by the hand KATs of SURVEY.md 8(a) only.
@@ -21,7 +23,6 @@ import re
 import runpy
 import sys
 import tempfile
-import types
 
 import numpy as np
 
@@ -40,60 +41,10 @@ def sha(a: np.ndarray) -> str:
 
 
 def import_gui():
-    """Import scripts/fft_analyzer_gui.py with the two absent GUI packages stubbed."""
-    qt = types.ModuleType("PyQt5")
-    qtcore = types.ModuleType("PyQt5.QtCore")
-
-    class _QObject:  # minimal stand-ins: only class definitions touch them at import time
-        def __init__(self, *a, **k):
-            pass
-
-    def _sig(*a, **k):
-        return None
-
-    def _slot(*a, **k):
-        return lambda f: f
-
-    qtcore.QObject = _QObject
-    qtcore.pyqtSignal = _sig
-    qtcore.pyqtSlot = _slot
-    qtcore.QTimer = _QObject
-    qtcore.QByteArray = bytes
-    qtcore.QIODevice = _QObject
-    qtcore.QThread = _QObject
-    qtcore.QCoreApplication = _QObject
-    qtcore.QMetaObject = _QObject
-    qtcore.Qt = types.SimpleNamespace(QueuedConnection=0)
-    qtcore.Q_ARG = lambda *a, **k: None
-    qtnet = types.ModuleType("PyQt5.QtNetwork")
-    qtnet.QUdpSocket = _QObject
-    qtnet.QHostAddress = _QObject
-    qtw = types.ModuleType("PyQt5.QtWidgets")
-    qtw.QApplication = _QObject
-    qt.QtCore, qt.QtNetwork, qt.QtWidgets = qtcore, qtnet, qtw
-    sio = types.ModuleType("flask_socketio")
-
-    class _SocketIO:
-        def __init__(self, *a, **k):
-            pass
-
-        def on(self, *a, **k):
-            return lambda f: f
-
-        def emit(self, *a, **k):
-            pass
-
-        def run(self, *a, **k):
-            pass
-
-    sio.SocketIO = _SocketIO
-    sio.emit = lambda *a, **k: None
-    for name, mod in [("PyQt5", qt), ("PyQt5.QtCore", qtcore), ("PyQt5.QtNetwork", qtnet),
-                      ("PyQt5.QtWidgets", qtw), ("flask_socketio", sio)]:
-        sys.modules.setdefault(name, mod)
-    sys.path.insert(0, os.path.join(REF, "scripts"))
-    import fft_analyzer_gui as gui  # noqa
-    return gui
+    """Import scripts/fft_analyzer_gui.py over the stand-ins of oracle/gui_sessions.py for the packages that are absent
+    here (PyQt5, flask_socketio, serial)."""
+    from oracle import gui_sessions
+    return gui_sessions.import_gui()
 
 
 def run_hann_coeff() -> np.ndarray:
@@ -213,6 +164,9 @@ def main():
                         cmds=np.array([gui.UART_REQUEST_CMD, gui.FPGA_RESET_CMD, gui.ETHERNET_MODE_CMD,
                                        gui.UART_MODE_CMD, gui.START_COMMAND, gui.FILTER_UPDATE_CMD,
                                        gui.FILTER_DEFAULT_CMD, gui.FILTER_CUSTOM_CMD, gui.FILTER_NONE_CMD]))
+    # ---- G7: the GUI's own caller code, recorded (oracle/gui_sessions.py lists the arrays)
+    from oracle import gui_sessions
+    gui_sessions.write(os.path.join(OUT, "g7_gui_sessions.npz"))
     tot = sum(os.path.getsize(os.path.join(OUT, f)) for f in os.listdir(OUT))
     print(f"golden fixtures written to {OUT}: {tot / 1024:.0f} KiB")
 

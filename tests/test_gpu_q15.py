@@ -439,7 +439,9 @@ def test_virtual_fpga_uart_and_udp(chain_cls, torch_mod, oracle):
     """N1/N2: the board as gui.py sees it -- command bytes in, frames / datagrams out, sequenced like
     imp/sequ2.vhd: Ethernet after reset, 0x55 arms the UART and the first 0xA5 starts a CONTINUOUS byte stream
     (what gui.py:529-549 sends and :616-689 slices), frames computed ahead are dropped when the control state
-    changes, coefficient bytes are never commands."""
+    changes, coefficient bytes are never commands.  The UART session written here is a shortened one, put together by
+    hand; the sessions recorded from the GUI's own handlers (temporary ports, the three 0xFF of a mode switch, the reset
+    cool-down) are replayed in test_gpu_gui_sessions.py."""
     import socket
     import threading
     from fpga_real_time_fft_analyzer_amd import designer, frames
@@ -463,7 +465,7 @@ def test_virtual_fpga_uart_and_udp(chain_cls, torch_mod, oracle):
     ser.reset_output_buffer()
     q = designer.two_sections_for_fpga(designer.quantize_coefficients(designer.design_iir_filter("lowpass", 4, 10.0, 20.0, 100.0)))
     c12 = np.array(q, np.int8).reshape(12)
-    # UART session exactly as the GUI runs it: mode byte, upload, select custom, 0x55, (100 ms), 0xA5
+    # a shortened UART session: mode byte, upload, select custom, 0x55, (100 ms), 0xA5
     ser.write(bytes([0xFE]))
     ser.write(designer.coefficient_upload_bytes(q) + bytes([0xA1]))
     ser.write(bytes([0x55]))
