@@ -32,6 +32,15 @@ def SA_Q15_TRACE_KIND(log2w: int) -> int:
     return 0x10 | log2w
 
 
+SA_Q15_HOP_FIELD_MAX = 2048
+
+
+def SA_Q15_HOP_KIND(kind: int, hop: int) -> int:
+    """The out_kind word of sa_process_q15_out / sa_process_q15_p12 for frames cut from one sample stream ``hop`` samples
+    apart (the macro of include/specan.h): the kind in bits 0..7, hop / 8 in bits 8..19.  hop = 0 is the kind itself."""
+    return kind | (hop // 8) << 8
+
+
 class CmdEvents(C.Structure):
     """sa_cmd_events of include/specan.h."""
     _fields_ = [("n_start", C.c_int), ("n_uart_request", C.c_int), ("n_reset", C.c_int), ("n_uploads", C.c_int),

@@ -52,6 +52,9 @@ class _Chain(NamedTuple):
     outputs: dict   # out_kind -> (C code, shape of one frame's output, torch dtype)
     inputs: dict    # torch dtype of x -> _form(...); the first dtype stands in the message for an x that is no tensor of a
                     # listed dtype
+    streams: dict = {}  # the same for a call with ``hop``: x is ONE 1-D stream, frame b its `row` elements from element
+                        # b * row * hop / 16384 on, and the C code goes out as SA_Q15_HOP_KIND(code, hop).  Empty: the chain
+                        # takes frames only.
 
     def output(self, out_kind) -> tuple:
         if out_kind not in self.outputs:
@@ -77,14 +80,22 @@ FLOAT_CHAIN = _Chain(_FLOAT_OUT, {torch.float32: _form(SA_N, _FLOAT_OUT, "sa_pro
 _Q15_OUT = {"iq": (SA_Q15_OUT_IQ, (SA_N, 2), torch.int16),
             "mag": (SA_Q15_OUT_MAG, (SA_N,), torch.float32),
             "marker": (SA_Q15_OUT_MARKER, (4,), torch.int32)}
+def _q15_streams(outputs: dict) -> dict:
+    """The stream forms of the Q15 chain: the two entry points whose out_kind word carries the hop."""
+    return {torch.int16: _form(SA_N, outputs, "sa_process_q15_out"),
+            torch.uint8: _form(SA_P12_FRAME_BYTES, outputs, "sa_process_q15_p12")}
+
+
 Q15_CHAIN = _Chain(_Q15_OUT, {torch.int16: _form(SA_N, _Q15_OUT, "sa_process_q15_out", iq="sa_process_q15"),
-                              torch.uint8: _form(SA_P12_FRAME_BYTES, _Q15_OUT, "sa_process_q15_p12")})
+                              torch.uint8: _form(SA_P12_FRAME_BYTES, _Q15_OUT, "sa_process_q15_p12")},
+                   _q15_streams(_Q15_OUT))
 # the Q15 chain's display trace (traces_q15): one output per bucket width W = 2^k, named by W; a table of its own, so that
 # process_q15(out_kind=...) keeps the three kinds it has
 _TRACE_OUT = {1 << k: (abi.SA_Q15_TRACE_KIND(k), (SA_N >> k, 2), torch.float32)
               for k in range(abi.SA_Q15_TRACE_LOG2W_MIN, abi.SA_Q15_TRACE_LOG2W_MAX + 1)}
 Q15_TRACE_CHAIN = _Chain(_TRACE_OUT, {torch.int16: _form(SA_N, _TRACE_OUT, "sa_process_q15_out"),
-                                      torch.uint8: _form(SA_P12_FRAME_BYTES, _TRACE_OUT, "sa_process_q15_p12")})
+                                      torch.uint8: _form(SA_P12_FRAME_BYTES, _TRACE_OUT, "sa_process_q15_p12")},
+                         _q15_streams(_TRACE_OUT))
 # the Q15 chain without its FFT (filter_q15): one output, which has no name
 _WINDOW_OUT = {None: (SA_Q15_OUT_IQ, (SA_N,), torch.int16)}
 Q15_WINDOW_CHAIN = _Chain(_WINDOW_OUT, {torch.int16: _form(SA_N, _WINDOW_OUT, "sa_filter_q15"),
@@ -182,21 +193,35 @@ class SpectrumChain:
     def _stream(self) -> int:
         return torch.cuda.current_stream(self.device).cuda_stream
 
-    def _check_in(self, x: torch.Tensor, dtype: torch.dtype, row: int) -> int:
+    def _check_in(self, x: torch.Tensor, dtype: torch.dtype, row: int, hop: Optional[int] = None) -> int:
+        """The number of frames in ``x``: its rows, or with ``hop`` the frames of `row` elements that the 1-D stream holds
+        row * hop / 16384 elements apart."""
         if not isinstance(x, torch.Tensor) or x.dtype != dtype:
             raise SpecanError(abi.SA_EINVAL, f"input must be a {dtype} tensor")
         if x.device != self.device:
             raise SpecanError(abi.SA_EINVAL, f"input must live on {self.device}")
+        if hop is not None:
+            step = row * hop // SA_N
+            if x.dim() != 1 or not x.is_contiguous() or x.shape[0] < row or (x.shape[0] - row) % step:
+                raise SpecanError(abi.SA_ESHAPE, f"with hop={hop} the input must be a contiguous 1-D stream of "
+                                                 f"{row} + k * {step} elements")
+            return (x.shape[0] - row) // step + 1
         if x.dim() != 2 or x.shape[1] != row or not x.is_contiguous():
             raise SpecanError(abi.SA_ESHAPE, f"input must be a contiguous [B, {row}] tensor")
         return x.shape[0]
 
-    def _process(self, chain: _Chain, x, out, out_kind, scale=None):
-        """Every process call: ``x`` by its dtype to the chain's entry point for it, into ``out`` (allocated when None)."""
+    def _process(self, chain: _Chain, x, out, out_kind, scale=None, hop=None):
+        """Every process call: ``x`` by its dtype to the chain's entry point for it, into ``out`` (allocated when None).
+        ``hop``: ``x`` is one sample stream and the frames are cut from it on the device (the chain's ``streams``)."""
         code, frame, dt = chain.output(out_kind)
-        dtype = x.dtype if isinstance(x, torch.Tensor) and x.dtype in chain.inputs else next(iter(chain.inputs))
-        row, calls = chain.inputs[dtype]
-        B = self._check_in(x, dtype, row)
+        forms = chain.inputs
+        if hop is not None:
+            if isinstance(hop, bool) or not isinstance(hop, (int, np.integer)) or not 8 <= hop <= SA_N or hop % 8:
+                raise SpecanError(abi.SA_EINVAL, "hop must be an int, a multiple of 8 in 8..16384")
+            hop, forms, code = int(hop), chain.streams, abi.SA_Q15_HOP_KIND(code, int(hop))
+        dtype = x.dtype if isinstance(x, torch.Tensor) and x.dtype in forms else next(iter(forms))
+        row, calls = forms[dtype]
+        B = self._check_in(x, dtype, row, hop)
         shape = (B,) + frame
         if out is None:
             out = torch.empty(shape, dtype=dt, device=self.device)
@@ -412,7 +437,8 @@ class SpectrumChain:
         f = rec.view(torch.float32)
         return f[:, 0], rec[:, 1], f[:, 2]
 
-    def process_q15(self, x: torch.Tensor, out: Optional[torch.Tensor] = None, out_kind: str = "iq") -> torch.Tensor:
+    def process_q15(self, x: torch.Tensor, out: Optional[torch.Tensor] = None, out_kind: str = "iq",
+                    hop: Optional[int] = None) -> torch.Tensor:
         """[B,16384] int16 -> per ``out_kind``: 'iq' (the default) [B,16384,2] int16 (re, im), B frames of 65536 bytes;
         'mag' [B,16384] float32, frames.decode_mag_16iq_le of each of those frames bit for bit (gui.py:250-260);
         'marker' [B,4] int32, one sa_marker_q15 per frame over the marker range (peak_mag as float32 bits, peak_bin,
@@ -421,28 +447,35 @@ class SpectrumChain:
         A uint8 tensor [B,24576] holds the same samples packed to 12 bits (include/specan.h, "p12"; ingest.pack12 is the
         host packer): it goes to sa_process_q15_p12, is unpacked inside the kernels that read the samples and gives the
         results of the int16 tensor of the same samples bit for bit, from three quarters of the input bytes.  Its data
-        pointer must be 16-byte aligned (any tensor torch allocates is, and so is every whole-frame slice of one)."""
-        return self._process(Q15_CHAIN, x, out, out_kind)
+        pointer must be 16-byte aligned (any tensor torch allocates is, and so is every whole-frame slice of one).
 
-    def markers_q15(self, x: torch.Tensor, out: Optional[torch.Tensor] = None):
+        ``hop`` (a multiple of 8 in 8..16384; include/specan.h, SA_Q15_HOP_KIND): overlapping frames cut on the device.
+        ``x`` is then ONE 1-D stream -- (B-1) * hop + 16384 int16 samples, or 3/2 as many packed bytes -- frame b is its
+        samples [b * hop, b * hop + 16384), and the result is that of the plain call on those B frames copied out
+        (``ingest.FrameCutter(hop)``), bit for bit, with every sample sent to the device once (``ingest.StreamCutter`` cuts
+        such streams).  The data pointer must be 16-byte aligned for both dtypes.  ``hop=None`` is the call on frames."""
+        return self._process(Q15_CHAIN, x, out, out_kind, hop=hop)
+
+    def markers_q15(self, x: torch.Tensor, out: Optional[torch.Tensor] = None, hop: Optional[int] = None):
         """Peak search and band power of the integer chain's frames over the marker range: ``(peak_mag float32 [B],
         peak_bin int32 [B], band_power int64 [B])``, views of the [B,4] int32 record tensor (``out``, allocated when
         None) that ``process_q15(x, out, 'marker')`` fills.  peak_mag is the 'mag' value at peak_bin, bit for bit, and
         band_power the exact integer sum of re^2 + im^2 over the range.  ``x`` is int16 or packed uint8 as for
-        :meth:`process_q15`."""
-        rec = self.process_q15(x, out, out_kind="marker")
+        :meth:`process_q15`, and with ``hop`` a 1-D stream as there."""
+        rec = self.process_q15(x, out, out_kind="marker", hop=hop)
         return rec.view(torch.float32)[:, 0], rec[:, 1], rec.view(torch.int64)[:, 1]
 
-    def traces_q15(self, x: torch.Tensor, bucket: int = 16, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    def traces_q15(self, x: torch.Tensor, bucket: int = 16, out: Optional[torch.Tensor] = None,
+                   hop: Optional[int] = None) -> torch.Tensor:
         """The display trace of the integer chain's frames: [B, 16384 // bucket, 2] float32, one sa_trace_point_q15 per
         bucket of ``bucket`` consecutive bins of the full spectrum (include/specan.h, SA_Q15_TRACE_KIND).  ``[..., 0]`` is
         the peak, the largest 'mag' value of the bucket bit for bit; ``[..., 1]`` the power, the exact integer sum of
         re^2 + im^2 over the bucket rounded once to float32 (frames.trace_of_frame is the numpy mirror).  ``bucket`` is
         2, 4, 8, 16, 32 or 64 -- anything else is SA_EINVAL before any device call; the marker range plays no part.
-        ``x`` is int16 or packed uint8 as for :meth:`process_q15`."""
+        ``x`` is int16 or packed uint8 as for :meth:`process_q15`, and with ``hop`` a 1-D stream as there."""
         if isinstance(bucket, bool) or not isinstance(bucket, (int, np.integer)) or int(bucket) not in _TRACE_OUT:
             raise SpecanError(abi.SA_EINVAL, f"bucket must be one of {sorted(_TRACE_OUT)}")
-        return self._process(Q15_TRACE_CHAIN, x, out, int(bucket))
+        return self._process(Q15_TRACE_CHAIN, x, out, int(bucket), hop=hop)
 
     def filter_q15(self, x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Window (+ integer IIR) only: the FFT input stream, [B,16384] int16.  ``x`` is [B,16384] int16 or the same

@@ -86,9 +86,13 @@ struct Q15TileRegs {
     uint4 c[kTilePasses];
 };
 
-// issue the global loads of one tile (4 frames x 256 samples and the matching ROM words), 16 B per lane
-template <typename InT>
-__device__ __forceinline__ void q15_load_tile(const InT *__restrict__ in, const int16_t *__restrict__ rom, int f0,
+// issue the global loads of one tile (4 frames x 256 samples and the matching ROM words), 16 B per lane.  HOP (the _hop
+// kernels): `in` is one stream and frame f begins at sample f hop of it, packed at byte 3 f hop / 2 -- hop is a multiple of 8:
+// a 16-byte boundary of int16 samples, a dword boundary of packed ones.  Otherwise the frames lie back to back and `hop` is
+// not read (a template parameter, not a stride argument: with a stride that the inliner folds to the constant, the int16
+// kernels came out with other registers and one instruction more than they had).
+template <bool HOP, typename InT>
+__device__ __forceinline__ void q15_load_tile(const InT *__restrict__ in, int hop, const int16_t *__restrict__ rom, int f0,
                                               int batch, int n0, int lane, Q15TileRegs<InT> &r)
 {
 #pragma unroll
@@ -98,10 +102,18 @@ __device__ __forceinline__ void q15_load_tile(const InT *__restrict__ in, const 
         const int f = f0 + row;
         if constexpr (kIsP12<InT>) {
             r.x[i] = {0u, 0u, 0u};
-            if (f < batch) r.x[i] = q15_load8_p12(in, (size_t)f * SA_P12_FRAME_BYTES + 3 * ((n0 + col) >> 1));
+            if constexpr (HOP) {
+                if (f < batch) r.x[i] = q15_load8_p12(in, (size_t)f * (size_t)(3 * hop / 2) + 3 * ((n0 + col) >> 1));
+            } else {
+                if (f < batch) r.x[i] = q15_load8_p12(in, (size_t)f * SA_P12_FRAME_BYTES + 3 * ((n0 + col) >> 1));
+            }
         } else {
             r.x[i] = make_uint4(0, 0, 0, 0);
-            if (f < batch) r.x[i] = *reinterpret_cast<const uint4 *>(in + (size_t)f * SA_NPTS + n0 + col);
+            if constexpr (HOP) {
+                if (f < batch) r.x[i] = *reinterpret_cast<const uint4 *>(in + (size_t)f * (size_t)hop + n0 + col);
+            } else {
+                if (f < batch) r.x[i] = *reinterpret_cast<const uint4 *>(in + (size_t)f * SA_NPTS + n0 + col);
+            }
         }
         r.c[i] = *reinterpret_cast<const uint4 *>(rom + n0 + col);
     }
@@ -131,6 +143,10 @@ __device__ __forceinline__ uint4 win8(uint4 x, uint4 c, int win_mode)
 // filter_q7_kernel, filter_w14_kernel) and on packed 12-bit samples (the same names with _p12).  Two kernels of one text
 // rather than one more template parameter or a shared inlined body: the int16 kernels keep their symbols and, instruction
 // for instruction, the code they had before the packed form existed (an inlined body did not: DESIGN.md section 4.10).
+// The cascades exist a third and fourth time, on frames cut from ONE sample stream at a hop (the names with _hop: SA_Q15_HOP_KIND
+// of include/specan.h): the same text with one more kernel argument, the hop in samples, and the
+// frame base of q15_load_tile taken from it -- HOP, HOP_ARG and HOP_VAL of the macros: false, empty and 0 in the frame forms.
+#define SA_Q15_HOP_ARG , int hop
 
 // Window only (filter mode 0xB1 through sa_filter_q15: the windowed time series, new/hann8192.vhd:36-39): element-wise,
 // eight samples of a frame per thread (16 bytes, 12 of packed samples), the ROM words from the L2.
@@ -252,23 +268,23 @@ __device__ __forceinline__ void wg_lds_sync()
 // samples of delay, so that a flush covers exactly one half of the output ring (samples [kTile j - 8, kTile (j+1) - 8) live in
 // slots [kTile j, kTile (j+1)) mod kRing) while the cascade writes the other half.  One workgroup barrier per tile (both sides
 // wait for their LDS traffic only); the cascade side runs nt tiles, the drain, and the same nt + 2 barriers.
-template <typename T, typename InT>
-__device__ __forceinline__ void q15_helper_wave(const InT *__restrict__ in, int16_t *__restrict__ out, const int16_t *__restrict__ rom,
+template <typename T, bool HOP, typename InT>
+__device__ __forceinline__ void q15_helper_wave(const InT *__restrict__ in, int hop, int16_t *__restrict__ out, const int16_t *__restrict__ rom,
                                                 int16_t (*tin)[kInPitch], const T (*ring)[kRingPitch], int f0, int batch, int lane,
                                                 int win_mode, bool idle)
 {
     constexpr int nt = SA_NPTS / kTile;
     Q15TileRegs<InT> pre;
     if (!idle) {
-        q15_load_tile(in, rom, f0, batch, 0, lane, pre);
+        q15_load_tile<HOP>(in, hop, rom, f0, batch, 0, lane, pre);
         q15_window_into_ring(pre, tin, 0, lane, win_mode);
-        q15_load_tile(in, rom, f0, batch, kTile, lane, pre);
+        q15_load_tile<HOP>(in, hop, rom, f0, batch, kTile, lane, pre);
     }
     wg_lds_sync();
     for (int k = 0; k <= nt; ++k) {                        // k = nt: the cascade runs its drain
         if (!idle) {
             if (k + 1 < nt) q15_window_into_ring(pre, tin, ((k + 1) & 1) * kTile, lane, win_mode);
-            if (k + 2 < nt) q15_load_tile(in, rom, f0, batch, (k + 2) * kTile, lane, pre);
+            if (k + 2 < nt) q15_load_tile<HOP>(in, hop, rom, f0, batch, (k + 2) * kTile, lane, pre);
             if (k >= 1) flush_tile(out, ring, (k - 1) * kTile, f0, batch, (k - 1) * kTile - 8, lane, kTile);
         }
         wg_lds_sync();
@@ -285,8 +301,8 @@ __device__ __forceinline__ void q15_helper_wave(const InT *__restrict__ in, int1
 // Sample m lives in ring slot (m + 8) mod kRing (lane 8 holds samples T0 - 8 .. T0 - 1 at the end of the group that
 // starts at step T0), so that the groups of one tile store to consecutive slots (the first group of the frame stores
 // eight zeros into slots nobody reads).
-template <typename T, typename Carry, typename InT, typename LaneTaps, typename Tile, typename Drain>
-__device__ __forceinline__ void q15_cascade(const InT *__restrict__ in, int16_t *__restrict__ out, int batch, int win_mode,
+template <typename T, typename Carry, bool HOP, typename InT, typename LaneTaps, typename Tile, typename Drain>
+__device__ __forceinline__ void q15_cascade(const InT *__restrict__ in, int hop, int16_t *__restrict__ out, int batch, int win_mode,
                                             const int16_t *__restrict__ rom, LaneTaps lane_taps, Tile tile, Drain drain)
 {
     __shared__ __attribute__((aligned(16))) int16_t tin_all[kV2Waves][kFramesPerWave][kInPitch];
@@ -303,7 +319,7 @@ __device__ __forceinline__ void q15_cascade(const InT *__restrict__ in, int16_t 
     constexpr int nt = SA_NPTS / kTile;
     const bool idle = f0 >= batch;      // a pair without frames still takes part in the workgroup's barriers
     if (helper) {
-        q15_helper_wave<T>(in, out, rom, tin, ring, f0, batch, lane, win_mode, idle);
+        q15_helper_wave<T, HOP>(in, hop, out, rom, tin, ring, f0, batch, lane, win_mode, idle);
         return;
     }
     SA_Q15_STAMP_BEGIN(blockIdx.x * kV2Waves + wave);
@@ -411,19 +427,21 @@ __device__ __forceinline__ void q7_drain(Q7Carry &c, const Q7Taps &t, unsigned x
     lds_store16_masked(ra + 16, vb, kOutMask);
 }
 
-#define SA_FILTER_Q7_KERNEL(NAME, InT)                                                                                          \
+#define SA_FILTER_Q7_KERNEL(NAME, InT, HOP, HOP_ARG, HOP_VAL)                                                                   \
     template <bool NOB1>                                                                                                        \
     __global__ __launch_bounds__(64 * kWgWaves) void NAME(const InT *__restrict__ in, int16_t *__restrict__ out, int batch,     \
-                                                          SaQ15Params prm, const int16_t *__restrict__ rom)                     \
+                                                          SaQ15Params prm, const int16_t *__restrict__ rom HOP_ARG)             \
     {                                                                                                                           \
-        q15_cascade<int, Q7Carry>(in, out, batch, prm.win_mode, rom, [&](int sec) -> Q7Taps {                                   \
+        q15_cascade<int, Q7Carry, HOP>(in, HOP_VAL, out, batch, prm.win_mode, rom, [&](int sec) -> Q7Taps {                     \
             if (sec < 0 || sec >= SA_MAXSEC) return {128 << 9, 0, 0, 0, 0}; /* identity = (128 x) >> 7 */                       \
             const int8_t *c = &prm.c12[(sec & 1) ? 6 : 0];                  /* stages 1,3,5 = set 0; 2,4,6 = set 1 */           \
             return {c[2] << 9, c[1] << 9, c[0] << 9, -(c[3] << 9), -(c[4] << 9)};                                               \
         }, [](Q7Carry &c, const Q7Taps &t, unsigned xa, unsigned ra) { q7_tile<NOB1>(c, t, xa, ra); }, q7_drain);               \
     }
-SA_FILTER_Q7_KERNEL(filter_q7_kernel, int16_t)
-SA_FILTER_Q7_KERNEL(filter_q7_p12_kernel, SaP12)
+SA_FILTER_Q7_KERNEL(filter_q7_kernel, int16_t, false, , 0)
+SA_FILTER_Q7_KERNEL(filter_q7_p12_kernel, SaP12, false, , 0)
+SA_FILTER_Q7_KERNEL(filter_q7_hop_kernel, int16_t, true, SA_Q15_HOP_ARG, hop)
+SA_FILTER_Q7_KERNEL(filter_q7_hop_p12_kernel, SaP12, true, SA_Q15_HOP_ARG, hop)
 #undef SA_FILTER_Q7_KERNEL
 
 // ------------------------------------------------------------------------------------------ IIR, wide Q2.14 form
@@ -494,11 +512,11 @@ __device__ __forceinline__ void w14_tile(W14Carry &c, const W14Taps &t, unsigned
 
 // one pass of four groups as the drain: the first delivers the frame's last eight samples, the other three filter whatever
 // the input ring holds into slots that were flushed long ago
-#define SA_FILTER_W14_KERNEL(NAME, InT)                                                                                         \
+#define SA_FILTER_W14_KERNEL(NAME, InT, HOP, HOP_ARG, HOP_VAL)                                                                  \
     __global__ __launch_bounds__(64 * kWgWaves) void NAME(const InT *__restrict__ in, int16_t *__restrict__ out, int batch,     \
-                                                          SaQ15Params prm, const int16_t *__restrict__ rom)                     \
+                                                          SaQ15Params prm, const int16_t *__restrict__ rom HOP_ARG)             \
     {                                                                                                                           \
-        q15_cascade<int16_t, W14Carry>(in, out, batch, prm.win_mode, rom, [&](int sec) {                                        \
+        q15_cascade<int16_t, W14Carry, HOP>(in, HOP_VAL, out, batch, prm.win_mode, rom, [&](int sec) {                          \
             /* identity: (16384 x + 8192) >> 14 = x exactly */                                                                  \
             if (sec < 0 || sec >= prm.nsec_wide) return w14_taps(16384, 0, 0, 0, 0);                                            \
             /* scipy row order [b0, b1, b2, a0, a1, a2], a0 ignored (= 1.0) */                                                  \
@@ -507,28 +525,42 @@ __device__ __forceinline__ void w14_tile(W14Carry &c, const W14Taps &t, unsigned
         }, [](W14Carry &c, const W14Taps &t, unsigned xa, unsigned ra) { w14_tile(c, t, xa, ra, kTileIters); },                 \
         [](W14Carry &c, const W14Taps &t, unsigned xa, unsigned ra) { w14_tile(c, t, xa, ra, 1); });                            \
     }
-SA_FILTER_W14_KERNEL(filter_w14_kernel, int16_t)
-SA_FILTER_W14_KERNEL(filter_w14_p12_kernel, SaP12)
+SA_FILTER_W14_KERNEL(filter_w14_kernel, int16_t, false, , 0)
+SA_FILTER_W14_KERNEL(filter_w14_p12_kernel, SaP12, false, , 0)
+SA_FILTER_W14_KERNEL(filter_w14_hop_kernel, int16_t, true, SA_Q15_HOP_ARG, hop)
+SA_FILTER_W14_KERNEL(filter_w14_hop_p12_kernel, SaP12, true, SA_Q15_HOP_ARG, hop)
 #undef SA_FILTER_W14_KERNEL
+#undef SA_Q15_HOP_ARG
 
-// every launch of one input form: window only, the wide cascade, the Q7 cascade with its seven- or nine-instruction step
-template <typename InT, typename K>
-void launch_filter(K window, K wide, K q7_short, K q7_long, const InT *in, int16_t *out_time, int batch, const SaQ15Params &p,
-                   const SaQ15Tables &t, hipStream_t stream, SaLaunchEv ev)
+// the cascade launch of one input form: the wide cascade, or the Q7 cascade with its seven- or nine-instruction step.
+// `hop`: nothing for the frame kernels, the hop in samples for the _hop kernels (their trailing argument).
+template <typename InT, typename K, typename... Hop>
+void launch_cascade(K wide, K q7_short, K q7_long, const InT *in, int16_t *out_time, int batch, const SaQ15Params &p,
+                    const SaQ15Tables &t, hipStream_t stream, SaLaunchEv ev, Hop... hop)
 {
     const int per_wg = kFramesPerWave * kV2Waves;
     const dim3 grid_wg((batch + per_wg - 1) / per_wg), block_wg(64 * kWgWaves);
-    if (p.filter == SA_FILTER_NONE) {
-        const size_t chunks = (size_t)batch * (SA_NPTS / 8);
-        hipExtLaunchKernelGGL(window, dim3((unsigned)((chunks + kWinThreads - 1) / kWinThreads)), dim3(kWinThreads), 0, stream,
-                              ev.start, ev.stop, 0, in, out_time, batch, p, t.rom);
-    } else if (p.filter == SA_FILTER_WIDE) {
-        hipExtLaunchKernelGGL(wide, grid_wg, block_wg, 0, stream, ev.start, ev.stop, 0, in, out_time, batch, p, t.rom);
+    if (p.filter == SA_FILTER_WIDE) {
+        hipExtLaunchKernelGGL(wide, grid_wg, block_wg, 0, stream, ev.start, ev.stop, 0, in, out_time, batch, p, t.rom, hop...);
     } else {
         // B1 = 0 in both coefficient sets (wire order b0,b1,b2,a0,a1,a2 per set): the seven-instruction step
         const bool nob1 = p.c12[1] == 0 && p.c12[7] == 0;
         hipExtLaunchKernelGGL(nob1 ? q7_short : q7_long, grid_wg, block_wg, 0, stream, ev.start, ev.stop, 0, in, out_time, batch, p,
-                              t.rom);
+                              t.rom, hop...);
+    }
+}
+
+// every launch of one input form on frames: window only, or its cascade
+template <typename InT, typename K>
+void launch_filter(K window, K wide, K q7_short, K q7_long, const InT *in, int16_t *out_time, int batch, const SaQ15Params &p,
+                   const SaQ15Tables &t, hipStream_t stream, SaLaunchEv ev)
+{
+    if (p.filter == SA_FILTER_NONE) {
+        const size_t chunks = (size_t)batch * (SA_NPTS / 8);
+        hipExtLaunchKernelGGL(window, dim3((unsigned)((chunks + kWinThreads - 1) / kWinThreads)), dim3(kWinThreads), 0, stream,
+                              ev.start, ev.stop, 0, in, out_time, batch, p, t.rom);
+    } else {
+        launch_cascade(wide, q7_short, q7_long, in, out_time, batch, p, t, stream, ev);
     }
 }
 
@@ -545,5 +577,22 @@ hipError_t sa_launch_filter_q15(const void *in, SaInKind in_kind, int16_t *out_t
     else
         launch_filter(window_q15_kernel, filter_w14_kernel, filter_q7_kernel<true>, filter_q7_kernel<false>,
                       static_cast<const int16_t *>(in), out_time, batch, p, t, stream, ev);
+    return hipGetLastError();
+}
+
+// A stream is read by a cascade only: window-only output of a stream is not offered (sa_filter_q15 has no kind word), and in
+// filter mode 0xB1 the FFT's stage 0 reads the stream itself.
+hipError_t sa_launch_filter_q15_hop(const void *in, SaInKind in_kind, int hop, int16_t *out_time, int batch, const SaQ15Params &p,
+                                    const SaQ15Tables &t, hipStream_t stream, SaLaunchEv ev)
+{
+    if (in_kind != SaInKind::I16 && in_kind != SaInKind::P12) return hipErrorInvalidValue;
+    if (hop <= 0 || hop > SA_NPTS || hop % 8 != 0 || p.filter == SA_FILTER_NONE) return hipErrorInvalidValue;
+    if (batch <= 0) return hipSuccess;
+    if (in_kind == SaInKind::P12)
+        launch_cascade(filter_w14_hop_p12_kernel, filter_q7_hop_p12_kernel<true>, filter_q7_hop_p12_kernel<false>,
+                       static_cast<const SaP12 *>(in), out_time, batch, p, t, stream, ev, hop);
+    else
+        launch_cascade(filter_w14_hop_kernel, filter_q7_hop_kernel<true>, filter_q7_hop_kernel<false>,
+                       static_cast<const int16_t *>(in), out_time, batch, p, t, stream, ev, hop);
     return hipGetLastError();
 }

@@ -392,10 +392,11 @@ __device__ __forceinline__ void fx_trace_frame(const unsigned (&q)[16], int k, i
 constexpr int kFftLds = SA_NPTS * 4;                      // the frame image; MARKER: + kFxMarkParts x 16 bytes behind it
 
 // Stage 0's samples of thread t, x[m] = sample t + 1024 m of frame f.  int16 samples: 2-byte loads, 128 contiguous bytes
-// per wave instruction.
-__device__ __forceinline__ void fx_load16(const int16_t *in, int f, int t, int (&x)[16])
+// per wave instruction.  Frame f begins `stride` samples after frame f - 1: SA_NPTS, a constant, where the frames lie back
+// to back, the hop where they are cut from one stream (the _hop kernels; SA_FX_STRIDE of fft_q15_kernel.inc).
+__device__ __forceinline__ void fx_load16(const int16_t *in, int f, size_t stride, int t, int (&x)[16])
 {
-    const int16_t *xf = in + (size_t)f * SA_NPTS + t;
+    const int16_t *xf = in + (size_t)f * stride + t;
 #pragma unroll
     for (int m = 0; m < 16; ++m) x[m] = xf[kFftWide * m];
 }
@@ -406,12 +407,14 @@ __device__ __forceinline__ void fx_load16(const int16_t *in, int f, int t, int (
 // takes the next dword ONLY in the straddling lanes and the first dword again in all others (where the funnel shift's
 // upper input does not reach the 12 bits kept): the frame's last dword, 6143, is the first dword of t = 1022 (sh = 8) and
 // t = 1023 (sh = 20) at m = 15, neither of which straddles, so no index exceeds 6143 and no byte outside
-// [in, in + B * 24576) is read -- by the address map, not by slack behind the tensor.
+// [in, in + B * 24576) is read -- by the address map, not by slack behind the tensor.  `stride` is in dwords: 6144 for
+// frames back to back; 3 hop / 8 for frames cut from one stream (hop a multiple of 8: every frame begins on a dword, and
+// dwords are all this map reads).  The argument above is per frame, so the last frame of a stream ends with the stream.
 constexpr int kP12FrameDwords = SA_P12_FRAME_BYTES / 4;
-__device__ __forceinline__ void fx_load16(const SaP12 *in, int f, int t, int (&x)[16])
+__device__ __forceinline__ void fx_load16(const SaP12 *in, int f, size_t stride, int t, int (&x)[16])
 {
     const int bit = 12 * t, sh = bit & 31;
-    const unsigned *lo = reinterpret_cast<const unsigned *>(in) + (size_t)f * kP12FrameDwords + (bit >> 5);
+    const unsigned *lo = reinterpret_cast<const unsigned *>(in) + (size_t)f * stride + (bit >> 5);
     const unsigned *hi = lo + (sh > 20 ? 1 : 0);
     constexpr int step = 12 * kFftWide / 32;                  // dwords from sample n to sample n + 1024
 #pragma unroll
@@ -421,34 +424,68 @@ __device__ __forceinline__ void fx_load16(const SaP12 *in, int f, int t, int (&x
 
 #define SA_FX_KERNEL fft_q15_kernel
 #define SA_FX_IN int16_t
+#define SA_FX_HOP_ARG
+#define SA_FX_STRIDE (size_t)SA_NPTS
 #include "fft_q15_kernel.inc"
 #undef SA_FX_KERNEL
 #undef SA_FX_IN
+#undef SA_FX_STRIDE
 // packed samples arrive unwindowed from the caller only (filter mode 0xB1): WINDOW = true is all that is instantiated
 #define SA_FX_KERNEL fft_q15_p12_kernel
 #define SA_FX_IN SaP12
+#define SA_FX_STRIDE (size_t)kP12FrameDwords
 #include "fft_q15_kernel.inc"
 #undef SA_FX_KERNEL
 #undef SA_FX_IN
+#undef SA_FX_STRIDE
+#undef SA_FX_HOP_ARG
+// Frames cut from one sample stream at a hop (SA_Q15_HOP_KIND of include/specan.h): the same text
+// twice more, with the hop in samples as one more kernel argument behind `mrange`.  A stream comes from the caller only,
+// unwindowed (mode 0xB1; the cascades' workspace is frames): WINDOW = true is all that is instantiated.
+#define SA_FX_HOP_ARG , int hop
+#define SA_FX_KERNEL fft_q15_hop_kernel
+#define SA_FX_IN int16_t
+#define SA_FX_STRIDE (size_t)hop
+#include "fft_q15_kernel.inc"
+#undef SA_FX_KERNEL
+#undef SA_FX_IN
+#undef SA_FX_STRIDE
+#define SA_FX_KERNEL fft_q15_hop_p12_kernel
+#define SA_FX_IN SaP12
+#define SA_FX_STRIDE (size_t)(3 * hop / 8)
+#include "fft_q15_kernel.inc"
+#undef SA_FX_KERNEL
+#undef SA_FX_IN
+#undef SA_FX_STRIDE
+#undef SA_FX_HOP_ARG
 
-// `log2w`: the k of SA_Q15_TRACE_KIND(k), which rides in the kernel's trailing word in place of the marker range
-template <int OUT, typename K, typename InT>
+// `log2w`: the k of SA_Q15_TRACE_KIND(k), which rides in the kernel's trailing word in place of the marker range;
+// `hop`: nothing for the frame kernels, the hop in samples for the _hop kernels (their trailing argument)
+template <int OUT, typename K, typename InT, typename... Hop>
 hipError_t launch_fft_q15(K k, const InT *in_time, void *out, int batch, const SaQ15Params &p, const SaQ15Tables &t,
-                          int log2w, hipStream_t stream, SaLaunchEv ev)
+                          int log2w, hipStream_t stream, SaLaunchEv ev, Hop... hop)
 {
     const dim3 grid(batch), block(kFftWide);
     const int lds = kFftLds + (OUT == SA_Q15_OUT_MARKER ? kFxMarkParts * (int)sizeof(uint4) : 0);
     const hipError_t e = sa_set_dyn_lds_once(reinterpret_cast<const void *>(k), lds);
     if (e != hipSuccess) return e;
     const unsigned word = OUT == kFxOutTrace ? (unsigned)log2w : (unsigned)t.marker_lo | (unsigned)t.marker_hi << 16;
-    hipExtLaunchKernelGGL(k, grid, block, lds, stream, ev.start, ev.stop, 0, in_time, out, batch, p, t.rom, t.tw, t.twrec, word);
+    hipExtLaunchKernelGGL(k, grid, block, lds, stream, ev.start, ev.stop, 0, in_time, out, batch, p, t.rom, t.tw, t.twrec, word,
+                          hop...);
     return hipGetLastError();
 }
 
+// hop = 0: frames back to back; otherwise `in_time` is one stream and frame f begins at sample f hop (windowed always)
 template <int OUT>
-hipError_t launch_fft_q15(const void *in_time, SaInKind in_kind, void *out, int batch, bool apply_window, const SaQ15Params &p,
-                          const SaQ15Tables &t, int log2w, hipStream_t stream, SaLaunchEv ev)
+hipError_t launch_fft_q15(const void *in_time, SaInKind in_kind, int hop, void *out, int batch, bool apply_window,
+                          const SaQ15Params &p, const SaQ15Tables &t, int log2w, hipStream_t stream, SaLaunchEv ev)
 {
+    if (hop != 0 && in_kind == SaInKind::P12)
+        return launch_fft_q15<OUT>(fft_q15_hop_p12_kernel<true, OUT>, static_cast<const SaP12 *>(in_time), out, batch, p, t, log2w,
+                                   stream, ev, hop);
+    if (hop != 0)
+        return launch_fft_q15<OUT>(fft_q15_hop_kernel<true, OUT>, static_cast<const int16_t *>(in_time), out, batch, p, t, log2w,
+                                   stream, ev, hop);
     if (in_kind == SaInKind::P12)
         return launch_fft_q15<OUT>(fft_q15_p12_kernel<true, OUT>, static_cast<const SaP12 *>(in_time), out, batch, p, t, log2w,
                                    stream, ev);
@@ -456,19 +493,34 @@ hipError_t launch_fft_q15(const void *in_time, SaInKind in_kind, void *out, int 
                                static_cast<const int16_t *>(in_time), out, batch, p, t, log2w, stream, ev);
 }
 
+// both launches: `hop` = 0 for frames
+hipError_t launch_fft_q15_kind(const void *in_time, SaInKind in_kind, int hop, void *out, int batch, int out_kind, bool apply_window,
+                               const SaQ15Params &p, const SaQ15Tables &t, hipStream_t stream, SaLaunchEv ev)
+{
+    if (in_kind != SaInKind::I16 && !(in_kind == SaInKind::P12 && apply_window)) return hipErrorInvalidValue;
+    if (batch <= 0) return hipSuccess;
+    if (out_kind >= SA_Q15_TRACE_KIND(SA_Q15_TRACE_LOG2W_MIN) && out_kind <= SA_Q15_TRACE_KIND(SA_Q15_TRACE_LOG2W_MAX))
+        return launch_fft_q15<kFxOutTrace>(in_time, in_kind, hop, out, batch, apply_window, p, t, out_kind - kFxOutTrace, stream, ev);
+    switch (out_kind) {
+        case SA_Q15_OUT_IQ: return launch_fft_q15<SA_Q15_OUT_IQ>(in_time, in_kind, hop, out, batch, apply_window, p, t, 0, stream, ev);
+        case SA_Q15_OUT_MAG: return launch_fft_q15<SA_Q15_OUT_MAG>(in_time, in_kind, hop, out, batch, apply_window, p, t, 0, stream, ev);
+        case SA_Q15_OUT_MARKER:
+            return launch_fft_q15<SA_Q15_OUT_MARKER>(in_time, in_kind, hop, out, batch, apply_window, p, t, 0, stream, ev);
+        default: return hipErrorInvalidValue;
+    }
+}
+
 }  // namespace
 
 hipError_t sa_launch_fft_q15(const void *in_time, SaInKind in_kind, void *out, int batch, int out_kind, bool apply_window,
                              const SaQ15Params &p, const SaQ15Tables &t, hipStream_t stream, SaLaunchEv ev)
 {
-    if (in_kind != SaInKind::I16 && !(in_kind == SaInKind::P12 && apply_window)) return hipErrorInvalidValue;
-    if (batch <= 0) return hipSuccess;
-    if (out_kind >= SA_Q15_TRACE_KIND(SA_Q15_TRACE_LOG2W_MIN) && out_kind <= SA_Q15_TRACE_KIND(SA_Q15_TRACE_LOG2W_MAX))
-        return launch_fft_q15<kFxOutTrace>(in_time, in_kind, out, batch, apply_window, p, t, out_kind - kFxOutTrace, stream, ev);
-    switch (out_kind) {
-        case SA_Q15_OUT_IQ: return launch_fft_q15<SA_Q15_OUT_IQ>(in_time, in_kind, out, batch, apply_window, p, t, 0, stream, ev);
-        case SA_Q15_OUT_MAG: return launch_fft_q15<SA_Q15_OUT_MAG>(in_time, in_kind, out, batch, apply_window, p, t, 0, stream, ev);
-        case SA_Q15_OUT_MARKER: return launch_fft_q15<SA_Q15_OUT_MARKER>(in_time, in_kind, out, batch, apply_window, p, t, 0, stream, ev);
-        default: return hipErrorInvalidValue;
-    }
+    return launch_fft_q15_kind(in_time, in_kind, 0, out, batch, out_kind, apply_window, p, t, stream, ev);
+}
+
+hipError_t sa_launch_fft_q15_hop(const void *in, SaInKind in_kind, int hop, void *out, int batch, int out_kind, const SaQ15Params &p,
+                                 const SaQ15Tables &t, hipStream_t stream, SaLaunchEv ev)
+{
+    if (hop <= 0 || hop > SA_NPTS || hop % 8 != 0) return hipErrorInvalidValue;
+    return launch_fft_q15_kind(in, in_kind, hop, out, batch, out_kind, true, p, t, stream, ev);
 }

@@ -1,14 +1,16 @@
 // fft_q15_kernel.inc -- the text of the integer FFT's kernel, included by fft_q15.hip once per input form with
 //   SA_FX_KERNEL  the kernel's name        SA_FX_IN  the element type of `in`
-// defined: fft_q15_kernel on int16 samples and fft_q15_p12_kernel on packed 12-bit samples (p12_dev.hpp).  The forms
-// differ in fx_load16 alone.  Text inclusion rather than a shared inlined body or one more template parameter: the
+//   SA_FX_HOP_ARG  nothing, or `, int hop`: one more kernel argument        SA_FX_STRIDE  the frame stride fx_load16 takes
+// defined: fft_q15_kernel on int16 samples and fft_q15_p12_kernel on packed 12-bit samples (p12_dev.hpp), frames back to
+// back (a constant stride), and fft_q15_hop_kernel / fft_q15_hop_p12_kernel on frames cut from one stream (the stride from
+// `hop`).  The forms differ in fx_load16 and its stride alone.  Text inclusion rather than a shared inlined body or one more template parameter: the
 // int16 kernels keep their symbols and, instruction for instruction, the code they had before the packed form existed.
 template <bool WINDOW, int OUT>
 __global__ __launch_bounds__(kFftWide, 8) void SA_FX_KERNEL(const SA_FX_IN *__restrict__ in,
                                                              void *__restrict__ out, int batch,
                                                              SaQ15Params prm, const int16_t *__restrict__ rom,
                                                              const uint2 *__restrict__ tw, const uint4 *__restrict__ twrec,
-                                                             unsigned mrange)
+                                                             unsigned mrange SA_FX_HOP_ARG)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_q[];
     unsigned *buf = reinterpret_cast<unsigned *>(smem_q);     // [16384] packed (re, im)
@@ -22,7 +24,7 @@ __global__ __launch_bounds__(kFftWide, 8) void SA_FX_KERNEL(const SA_FX_IN *__re
     // Exponents with wi = -32768 (see fx_butterfly): stages 0 and 1, u = 3 for output 1, u = 1 for output 3.
     {
         int x[16];
-        fx_load16(in, f, t, x);
+        fx_load16(in, f, SA_FX_STRIDE, t, x);
         if constexpr (WINDOW) {
             int c[16];
 #pragma unroll

@@ -177,3 +177,12 @@ hipError_t sa_launch_filter_q15(const void *in, SaInKind in_kind, int16_t *out_t
 // k = 1..6: sa_trace_point_q15 [B, 16384 >> k] (the width reaches the kernel in the word that carries the marker range)
 hipError_t sa_launch_fft_q15(const void *in_time, SaInKind in_kind, void *out, int batch, int out_kind, bool apply_window,
                              const SaQ15Params &p, const SaQ15Tables &t, hipStream_t stream, SaLaunchEv ev);
+// The same two launches on frames cut from ONE sample stream (SA_Q15_HOP_KIND of include/specan.h): frame f is the 16384
+// samples from sample f * hop on, hop a multiple of 8 in 8..16384; `in` holds (batch - 1) * hop + 16384 samples, int16 or
+// packed (3/2 bytes per sample), 16-byte aligned.  The cascade writes frames, [B,16384] int16, as ever; the FFT reads a stream
+// only in filter mode 0xB1 and always windows it.
+hipError_t sa_launch_filter_q15_hop(const void *in, SaInKind in_kind, int hop, int16_t *out_time, int batch, const SaQ15Params &p,
+                                    const SaQ15Tables &t, hipStream_t stream, SaLaunchEv ev);
+hipError_t sa_launch_fft_q15_hop(const void *in, SaInKind in_kind, int hop, void *out, int batch, int out_kind, const SaQ15Params &p,
+                                 const SaQ15Tables &t, hipStream_t stream, SaLaunchEv ev);
+

@@ -423,12 +423,23 @@ static SaQ15Params q15_params(const sa_handle *h)
 // `trace`: the entry point also takes the SA_Q15_TRACE_KIND(k) family (the Q15 FFT calls; never the float chain).
 // `scale_finite`: what process_float found of its scale, which is refused between the kind and the empty batch (process_q15
 // has no scale: true).  An empty batch returns SA_OK here, and the caller returns it at once.
+// `hop`: null, or where the entry point's word is a SA_Q15_HOP_KIND: the word is taken apart before anything else, *hop is
+// its hop in samples (0: frames) and the kind checked below is its low byte.  An entry point without one (every float one)
+// sees a word with a hop field as the unknown kind it is there.
 static int check_process_args(sa_handle *h, const char *fn, const void *in, SaInKind kind, const void *out, int batch,
-                              int out_kind, int marker, const char *marker_name, bool trace, bool scale_finite)
+                              int out_kind, int marker, const char *marker_name, bool trace, bool scale_finite, int *hop = nullptr)
 {
     static_assert(SA_OUT_MAG_FULL == 0 && SA_Q15_OUT_IQ == 0, "the kinds of both chains are 0 .. marker");
+    int field = 0;
+    bool bad_word = false;
+    if (hop && out_kind >= 0) {                                    // a negative word is the bad kind it always was
+        field = (out_kind >> 8) & 0xFFF;
+        bad_word = (out_kind >> 20) != 0 || field > SA_Q15_HOP_FIELD_MAX;
+        out_kind &= 0xFF;
+    }
     if (!h) return SA_EINVAL;
     if (batch < 0) return fail_at(h, SA_ESHAPE, fn, "negative batch");
+    if (bad_word) return fail_at(h, SA_EINVAL, fn, "bad out_kind: hop field above 2048 or bits 20..30 set");
     const bool is_trace = trace && out_kind >= SA_Q15_TRACE_KIND(SA_Q15_TRACE_LOG2W_MIN) &&
                           out_kind <= SA_Q15_TRACE_KIND(SA_Q15_TRACE_LOG2W_MAX);
     if (!is_trace && (out_kind < 0 || out_kind > marker)) return fail_at(h, SA_EINVAL, fn, "bad out_kind");
@@ -442,17 +453,25 @@ static int check_process_args(sa_handle *h, const char *fn, const void *in, SaIn
     }
     if (kind == SaInKind::P12 && ((uintptr_t)in & 15u) != 0)       // the stage-ins issue 16-byte requests; every frame is then aligned
         return fail_at(h, SA_EINVAL, fn, "packed input must be 16-byte aligned");
+    if (field != 0 && ((uintptr_t)in & 15u) != 0)                  // int16: every frame is then aligned for the 16-byte tile loads
+        return fail_at(h, SA_EINVAL, fn, "a sample stream (SA_Q15_HOP_KIND) must be 16-byte aligned");
+    if (hop) *hop = 8 * field;
     return SA_OK;
 }
 
 // sa_filter_q15 (`fft` false: window + integer cascade into `out`, out_kind unused) and sa_process_q15 / sa_process_q15_out
 // (`out` per out_kind, SA_Q15_OUT_* or SA_Q15_TRACE_KIND(k): the FFT launch's epilogue makes it), on int16 samples or, the
-// _p12 entry points, on packed 12-bit samples (`kind`: I16 or P12); `fn` names the entry point
+// _p12 entry points, on packed 12-bit samples (`kind`: I16 or P12); `fn` names the entry point.  `hop_word`: out_kind is a
+// SA_Q15_HOP_KIND (sa_process_q15_out, sa_process_q15_p12); with a hop, `in` is one stream and whichever launch reads the
+// samples -- the cascade, or the FFT in mode 0xB1 -- is its _hop sibling.  Everything else is the frame call.
 static int process_q15(sa_handle *h, const char *fn, const void *in, SaInKind kind, void *out, int batch, int out_kind,
-                       void *stream, bool fft)
+                       void *stream, bool fft, bool hop_word = false)
 {
-    { const int rc = check_process_args(h, fn, in, kind, out, batch, out_kind, SA_Q15_OUT_MARKER, "SA_Q15_OUT_MARKER", fft, true);
+    int hop = 0;
+    { const int rc = check_process_args(h, fn, in, kind, out, batch, out_kind, SA_Q15_OUT_MARKER, "SA_Q15_OUT_MARKER", fft, true,
+                                        hop_word ? &hop : nullptr);
       if (rc != SA_OK || batch == 0) return rc; }
+    if (hop_word) out_kind &= 0xFF;
     SA_HIP(h, hipSetDevice(h->device));
     const SaQ15Params p = q15_params(h);
     const bool staged = fft && p.filter != SA_FILTER_NONE;      // cascade into the slot's workspace, then the FFT
@@ -460,8 +479,9 @@ static int process_q15(sa_handle *h, const char *fn, const void *in, SaInKind ki
     { const int rc = begin_call(h, (hipStream_t)stream, staged ? sa_handle::kWorkQ15 : -1, batch, &c); if (rc != SA_OK) return rc; }
     const SaQ15Tables t = {h->d_rom, h->d_twq, h->d_twrec, h->marker_lo, h->marker_hi};
     if (!staged) {
-        SA_HIP(h, fft ? sa_launch_fft_q15(in, kind, out, batch, out_kind, true, p, t, c.stream, {c.start, c.stop})
-                      : sa_launch_filter_q15(in, kind, (int16_t *)out, batch, p, t, c.stream, {c.start, c.stop}));
+        SA_HIP(h, hop   ? sa_launch_fft_q15_hop(in, kind, hop, out, batch, out_kind, p, t, c.stream, {c.start, c.stop})
+                  : fft ? sa_launch_fft_q15(in, kind, out, batch, out_kind, true, p, t, c.stream, {c.start, c.stop})
+                        : sa_launch_filter_q15(in, kind, (int16_t *)out, batch, p, t, c.stream, {c.start, c.stop}));
         return end_call(h, c);
     }
     // The WIDE cascade does not gain from overlapped launches (tools/q15_overlap_modes.py, profiles/r4_q15_helper_waves.txt):
@@ -474,7 +494,8 @@ static int process_q15(sa_handle *h, const char *fn, const void *in, SaInKind ki
     }
     int16_t *ws = (int16_t *)h->slot[c.slot].work[sa_handle::kWorkQ15].ptr;
     // the packed form is read by the first launch alone: the workspace holds int16 samples whatever came in
-    SA_HIP(h, sa_launch_filter_q15(in, kind, ws, batch, p, t, c.stream, {c.start, nullptr}));
+    SA_HIP(h, hop ? sa_launch_filter_q15_hop(in, kind, hop, ws, batch, p, t, c.stream, {c.start, nullptr})
+                  : sa_launch_filter_q15(in, kind, ws, batch, p, t, c.stream, {c.start, nullptr}));
     SA_HIP(h, sa_launch_fft_q15(ws, SaInKind::I16, out, batch, out_kind, false, p, t, c.stream, {nullptr, c.stop}));
     return end_call(h, c);
 }
@@ -491,12 +512,12 @@ int sa_process_q15(sa_handle *h, const int16_t *in, int16_t *out_iq, int batch, 
 
 int sa_process_q15_out(sa_handle *h, const int16_t *in, void *out, int batch, int out_kind, void *stream)
 {
-    return process_q15(h, "sa_process_q15_out", in, SaInKind::I16, out, batch, out_kind, stream, true);
+    return process_q15(h, "sa_process_q15_out", in, SaInKind::I16, out, batch, out_kind, stream, true, true);
 }
 
 int sa_process_q15_p12(sa_handle *h, const uint8_t *in, void *out, int batch, int out_kind, void *stream)
 {
-    return process_q15(h, "sa_process_q15_p12", in, SaInKind::P12, out, batch, out_kind, stream, true);
+    return process_q15(h, "sa_process_q15_p12", in, SaInKind::P12, out, batch, out_kind, stream, true, true);
 }
 
 int sa_filter_q15_p12(sa_handle *h, const uint8_t *in, int16_t *out_time, int batch, void *stream)

@@ -113,6 +113,69 @@ class FrameCutter:
         return int(self._buf.size)
 
 
+class StreamCutter:
+    """Cut a sample stream into 1-D blocks for the device-side framing of ``SpectrumChain.process_q15(x, hop=...)``: every
+    block holds exactly ``frames`` frames' worth of the stream, (frames - 1) * hop + 16384 samples, and consecutive blocks
+    start frames * hop samples apart -- so each block repeats the last 16384 - hop samples of the one before it (carried
+    here, on the host), and every other sample crosses the link once instead of 16384 / hop times.  The frames of the
+    blocks, in order, are the frames :class:`FrameCutter` ``(hop)`` cuts from the same stream, once each.
+
+    ``hop``: a multiple of 8 in 8..16384, what the device call takes (``ValueError`` otherwise).  ``packed=True``: the
+    stream is the packed 12-bit byte stream (:func:`pack12`), pushed in chunks of any length (a chunk may end inside a
+    pair of samples), and the blocks are uint8, 3/2 bytes per sample."""
+
+    def __init__(self, hop: int, frames: int, packed: bool = False):
+        if isinstance(hop, bool) or not isinstance(hop, (int, np.integer)) or not 8 <= hop <= N or hop % 8:
+            raise ValueError("hop must be a multiple of 8 in 8..16384")
+        if isinstance(frames, bool) or not isinstance(frames, (int, np.integer)) or frames < 1:
+            raise ValueError("frames must be a positive integer")
+        self.hop, self.frames, self.packed = int(hop), int(frames), bool(packed)
+        self._row, self._dtype = (P12_FRAME_BYTES, np.uint8) if packed else (N, np.int16)
+        self._step = self._row * self.hop // N                      # elements of the buffer per hop
+        self._buf = np.empty(0, self._dtype)
+
+    @property
+    def block_size(self) -> int:
+        """Elements (samples; packed: bytes) of a full block."""
+        return (self.frames - 1) * self._step + self._row
+
+    def push(self, samples) -> list:
+        """Append samples (packed: bytes of the packed stream); return the blocks that became complete, a list of 1-D
+        arrays of ``block_size`` elements (possibly empty)."""
+        if self.packed:
+            s = (np.frombuffer(samples, np.uint8) if isinstance(samples, (bytes, bytearray, memoryview))
+                 else np.asarray(samples))
+            if s.dtype != np.uint8:
+                raise ValueError("a packed stream is pushed as uint8 / bytes")
+        else:
+            s = np.asarray(samples)
+            if s.dtype != np.int16:
+                if np.any(s < -32768) or np.any(s > 32767):
+                    raise ValueError("samples do not fit int16")
+                s = s.astype(np.int16)
+        self._buf = np.concatenate([self._buf, s.reshape(-1)])
+        size, advance = self.block_size, self.frames * self._step
+        k = 0 if self._buf.size < size else (self._buf.size - size) // advance + 1
+        out = [self._buf[i * advance:i * advance + size].copy() for i in range(k)]
+        self._buf = self._buf[k * advance:]
+        return out
+
+    def flush(self):
+        """A last block of the complete frames that remain (fewer than ``frames``), or None.  What is left after it is
+        less than a frame beyond the last hop; pushing may go on."""
+        if self._buf.size < self._row:
+            return None
+        k = (self._buf.size - self._row) // self._step + 1
+        out = self._buf[:(k - 1) * self._step + self._row].copy()
+        self._buf = self._buf[k * self._step:]
+        return out
+
+    @property
+    def pending(self) -> int:
+        """Samples (packed: bytes) held for the next block."""
+        return int(self._buf.size)
+
+
 class DeviceFeeder:
     """Buffered host -> device mover: ``feed(batch_iter)`` yields device tensors [B,16384] int16
     (``packed``: [B,24576] uint8) while the next batch is already in flight on a side stream.
@@ -127,6 +190,10 @@ class DeviceFeeder:
     ``packed=True``: the batches are packed 12-bit frames, [B,24576] uint8 (what a packed :class:`FrameCutter` cuts), and
     so are the staging and device buffers and the tensors handed out: three quarters of the bytes per frame on the link.
     ``SpectrumChain.process_f32`` takes them as they are.
+
+    ``stream=True``: the batches are 1-D blocks of a sample stream (what :class:`StreamCutter` cuts; packed or not), of at
+    most ``max_batch`` x 16384 samples.  They are staged, copied and handed out 1-D, for
+    ``SpectrumChain.process_q15(x, hop=...)``, which cuts the overlapping frames on the device.
 
     **The consumer's contract.**  The tensor handed out for batch k is a view of a slot's device buffer.  The consumer
     enqueues its work on the stream that was current when ``feed`` started, between taking batch k and asking for
@@ -147,14 +214,15 @@ class DeviceFeeder:
     everything enqueued on the current stream at its start as the end of the earlier consumers' work.  With
     ``consumer_depth`` 1 nothing is to be done.
 
-    **Refused** (``ValueError``): a ``consumer_depth`` outside 1..4, a batch of more than ``max_batch`` frames.
+    **Refused** (``ValueError``): a ``consumer_depth`` outside 1..4, a batch of more than ``max_batch`` frames (``stream``:
+    a block of more than ``max_batch`` frames' elements).
     ``RuntimeError``: going on with an iterator of an earlier ``feed()`` after a new ``feed()`` of the same feeder has
     started -- one feed at a time; an abandoned iterator needs no closing."""
 
     MAX_CONSUMER_DEPTH = 4              # sa_set_overlap's largest depth (include/specan.h)
 
     def __init__(self, device: torch.device | int = 0, max_batch: int = 256, host_threads: Optional[int] = None,
-                 packed: bool = False, consumer_depth: int = 1):
+                 packed: bool = False, consumer_depth: int = 1, stream: bool = False):
         if not 1 <= int(consumer_depth) <= self.MAX_CONSUMER_DEPTH:
             raise ValueError("consumer_depth must be in 1..4 (the overlap depths of SpectrumChain.set_overlap)")
         if host_threads is not None:
@@ -163,11 +231,14 @@ class DeviceFeeder:
         self.max_batch = max_batch
         self.packed = bool(packed)
         self.consumer_depth = int(consumer_depth)
+        self.stream = bool(stream)
         self._row, self._np_dtype = (P12_FRAME_BYTES, np.uint8) if packed else (N, np.int16)
         dt = torch.uint8 if packed else torch.int16
         ns = self._nslots = 2 if self.consumer_depth == 1 else self.consumer_depth + 1
-        self._pinned = [torch.empty((max_batch, self._row), dtype=dt).pin_memory() for _ in range(ns)]
-        self._dev = [torch.empty((max_batch, self._row), dtype=dt, device=self.device) for _ in range(ns)]
+        # a slot holds max_batch rows: frames, or in stream mode the same room as one row of elements
+        self._shape = (max_batch * self._row,) if self.stream else (max_batch, self._row)
+        self._pinned = [torch.empty(self._shape, dtype=dt).pin_memory() for _ in range(ns)]
+        self._dev = [torch.empty(self._shape, dtype=dt, device=self.device) for _ in range(ns)]
         self._copy_stream = torch.cuda.Stream(self.device)
         self._copied = [torch.cuda.Event() for _ in range(ns)]      # slot's host->device copy has run
         self._consumed = [torch.cuda.Event() for _ in range(ns)]    # slot's consumer work is ordered on the stream and has run
@@ -193,9 +264,9 @@ class DeviceFeeder:
         self._retire(cur, 0)
         pend = None                                             # (slot, n_frames) handed out next
         for i, b in enumerate(batches):
-            b = np.ascontiguousarray(b, self._np_dtype).reshape(-1, self._row)
-            n = b.shape[0]
-            if n > self.max_batch:
+            b = np.ascontiguousarray(b, self._np_dtype).reshape((-1,) + self._shape[1:])
+            n = b.shape[0]                                      # frames; stream mode: elements
+            if n > self._shape[0]:
                 raise ValueError("batch larger than max_batch")
             slot = i % self._nslots
             if self._used[slot]:

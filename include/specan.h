@@ -371,6 +371,43 @@ int sa_process_q15_p12(sa_handle *h, const uint8_t *in /* [B,24576] device */, v
                        void *stream);
 int sa_filter_q15_p12(sa_handle *h, const uint8_t *in /* [B,24576] device */, int16_t *out_time, int batch, void *stream);
 
+/* Overlapping frames cut on the device from ONE sample stream (build extension; ABI version 4, added compatibly).  A
+ * windowed analyser that must not lose signal between frames runs at hop = N/2 or N/4; cut on the host
+ * (ingest.FrameCutter), every sample then crosses the link N/hop times.  Frames are independent (history is reset per
+ * frame, the window is applied per frame), so frame b of a stream is simply the 16384 samples from sample b * hop on, and
+ * the kernels that read samples address it there.  The hop travels inside the out_kind word of sa_process_q15_out() and
+ * sa_process_q15_p12(), as the trace width does: no control state, nothing a captured graph could freeze.
+ *     SA_Q15_HOP_KIND(kind, hop) = kind | (hop / 8) << 8
+ *   bits 0..7    the kind as above: SA_Q15_OUT_IQ, _MAG, _MARKER or SA_Q15_TRACE_KIND(k) = 17..22
+ *   bits 8..19   the hop field h = hop / 8
+ *   bits 20..30  must be zero
+ *   - h = 0 is every call described so far: `in` is [B,16384] (packed: [B,24576]), frames back to back.  Every out_kind that
+ *     existed keeps its value, its meaning and its kernels.
+ *   - h = 1..SA_Q15_HOP_FIELD_MAX (2048): hop = 8 h samples, a multiple of 8 in 8..16384.  `in` is ONE stream of
+ *     (batch - 1) * hop + 16384 samples -- int16, or packed 12-bit at 3/2 bytes per sample (the p12 bit stream above, not
+ *     cut into frames) -- and frame b is its samples [b hop, b hop + 16384).  `out` is what it is for frames: [B, ...]
+ *     per kind, bit for bit the result of the plain call on the B frames copied out of the stream.  h = 2048 (hop = N)
+ *     gives the bits of the plain call on the same memory.
+ *   - `in` must be 16-byte aligned for both input forms when h > 0 (SA_EINVAL otherwise).  int16: every frame is then 16-byte
+ *     aligned (16 h bytes apart), which the cascades' 16-byte tile loads need.  Packed: frame b begins at byte 12 h b -- on
+ *     a dword, which is all the packed loads need, and deliberately NOT on 16 bytes.  No byte outside the stream is read:
+ *     the last frame ends with it.
+ *   - refused with SA_EINVAL before any call state changes, nothing launched: h above 2048, any of bits 20..30 set, a low
+ *     byte that is not a kind of the entry point, a misaligned `in`.  The float entry points refuse every word with h > 0,
+ *     as they refuse any unknown kind; sa_process_q15, sa_filter_q15 and sa_filter_q15_p12 have no kind word and take
+ *     frames only.
+ *   - everything said of sa_process_q15_out() holds: all four filter modes, both window modes, custom ROMs, every overlap
+ *     depth, launch timing, hipGraph capture once sa_reserve() has sized the workspace (which is sized by B as ever: with
+ *     a cascade, the cascade reads the stream and writes B frames into it; in mode 0xB1 the FFT's first stage reads the
+ *     stream).
+ *   - known answers: SA_Q15_HOP_KIND(SA_Q15_OUT_IQ, 8192) = 0x40000; SA_Q15_HOP_KIND(SA_Q15_OUT_MARKER, 4096) = 0x20002;
+ *     SA_Q15_HOP_KIND(SA_Q15_TRACE_KIND(4), 8) = 0x114; SA_Q15_HOP_KIND(SA_Q15_OUT_MAG, 16384) = 0x80001.  A batch of
+ *     B = 5 at hop 4096 is a stream of SA_Q15_HOP_STREAM_SAMPLES(5, 4096) = 32768 samples: 65536 bytes of int16 or 49152
+ *     packed, against 163840 and 122880 for the five frames. */
+#define SA_Q15_HOP_KIND(kind, hop) ((kind) | ((hop) / 8) << 8)
+#define SA_Q15_HOP_FIELD_MAX 2048
+#define SA_Q15_HOP_STREAM_SAMPLES(batch, hop) (((size_t)(batch) - 1) * (size_t)(hop) + SA_N)
+
 /* Host helpers of the p12 format: pure functions, no handle, no GPU.  n is the number of SAMPLES and must be even
  * (SA_EINVAL otherwise); `packed` holds 3n/2 bytes.  Packing a sample outside [-2048, 2047] is SA_EINVAL and nothing
  * is written.  Unpacking sign-extends to int16. */

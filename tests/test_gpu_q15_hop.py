@@ -1,0 +1,314 @@
+"""GPU: overlapping frames cut on the device from one sample stream (include/specan.h, SA_Q15_HOP_KIND; the `hop` argument of
+SpectrumChain.process_q15, markers_q15 and traces_q15).
+
+The criterion throughout is torch.equal against the existing frame call on the frames that ingest.FrameCutter(hop) (packed:
+FrameCutter(hop, packed=True)) cuts from the same stream on the host: the hop call addresses frame b at sample b * hop and
+is otherwise that call, so there are no tolerances.  Once per filter mode the integer model (oracle.chain_q15) is asked about
+the cut frames directly."""
+import functools
+
+import numpy as np
+import pytest
+
+from conftest import N
+from gpu_support import ch, check_overlap_profiling_and_graph_capture, to_device, torch_mod  # noqa: F401 (fixtures)
+
+pytestmark = pytest.mark.gpu
+
+P12 = 24576
+SA_EINVAL, SA_ESHAPE = -1, -2
+KINDS = ("iq", "mag", "marker", 16, 64)                    # a number: the display trace with buckets of that many bins
+BATCHES = (1, 5, 17, 37)       # no multiple of a wave's 4 frames or a workgroup's 16: the f < batch guards, a second and third workgroup
+HOPS = (8,                     # packed frames 12 bytes apart: every alignment mod 16
+        4104,                  # = 8 * 513, an odd field: packed frames alternate between 8-byte aligned and not
+        8192, 16376,
+        16384)                 # the plain call on the reshaped tensor
+GUI_UPLOAD = np.array([0, 1, 0, 64, -67, 19, 64, 127, 64, 64, -85, 40], np.int8)      # gui.py:159-179, 1186-1192 defaults
+# mode -> (filter byte, 12-byte upload, Q2.14 sections, window mode, custom ROM)
+MODES = {
+    "b1_rtl": (0xB1, None, None, 0, False),
+    "b1_hann_u16": (0xB1, None, None, 1, False),
+    "b1_rom": (0xB1, None, None, 0, True),
+    "default": (0x00, None, None, 0, False),
+    "gui_upload": (0xA1, GUI_UPLOAD, None, 0, False),
+    "wide6": (0xA2, None, 6, 0, False),
+    "wide0": (0xA2, None, 0, 0, False),
+}
+
+
+@functools.lru_cache(maxsize=None)
+def samples(full_scale=False):
+    """One stream for every test, read-only: random 12-bit samples (so that it serves int16 and packed alike), or full-scale
+    int16 ones; as long as the largest batch at the largest hop."""
+    lo, hi = (-32768, 32768) if full_scale else (-2048, 2048)
+    s = np.random.default_rng(1212 + full_scale).integers(lo, hi, max(BATCHES) * N).astype(np.int16)
+    s.setflags(write=False)
+    return s
+
+
+@functools.lru_cache(maxsize=None)
+def wide_sections():
+    """Six Q2.14 sections that let the test frames through (the recipe of tests/test_gpu_q15_p12.py)."""
+    from scipy import signal
+    sos = np.concatenate([signal.butter(2, wc, output="sos") for wc in (0.35, 0.45, 0.55, 0.65, 0.75, 0.85)])
+    q = np.rint(sos * 16384.0)
+    assert q.shape == (6, 6) and np.abs(q).max() <= 32767
+    return q.astype(np.int16)
+
+
+def configure(ch, mode):
+    """Put the handle into `mode`; returns oracle.chain_q15's arguments after x."""
+    cmd, c12, nsec, wm, custom_rom = MODES[mode]
+    rom = np.random.default_rng(5).integers(-32768, 32768, N).astype(np.int16) if custom_rom else None
+    if rom is not None:
+        ch.set_window_q15(rom)
+    ch.set_window_mode_q15(wm)
+    if c12 is not None:
+        ch.load_coeffs_q7(c12)
+    sos = None if nsec is None else wide_sections()[:nsec]
+    if sos is not None:
+        ch.load_sos_q14(sos)
+    ch.set_filter_mode(cmd)
+    return rom, wm, cmd, c12, sos
+
+
+def call(ch, kind, x, hop=None, out=None):
+    if isinstance(kind, int):
+        return ch.traces_q15(x, bucket=kind, out=out, hop=hop)
+    return ch.process_q15(x, out=out, out_kind=kind, hop=hop)
+
+
+def cut(stream, hop, packed=False):
+    """The host's framing of a whole stream: FrameCutter(hop), with nothing left over beyond a rest short of a hop."""
+    from fpga_real_time_fft_analyzer_amd.ingest import FrameCutter
+    c = FrameCutter(hop, packed=packed)
+    frames = c.push(stream)
+    assert c.pending == stream.size - frames.shape[0] * (3 * hop // 2 if packed else hop)
+    return frames
+
+
+def stream_and_frames(torch, s, hop, B):
+    """The first B frames' worth of `s` at `hop`, on the device: {form: (1-D stream, frames cut on the host)}"""
+    from fpga_real_time_fft_analyzer_amd.ingest import pack12
+    st = s[:(B - 1) * hop + N]
+    fr = cut(st, hop)
+    assert fr.shape == (B, N)
+    if hop == N:
+        assert np.array_equal(fr, st.reshape(B, N))
+    forms = {"int16": (to_device(torch, st), to_device(torch, fr))}
+    if s.min() >= -2048 and s.max() <= 2047:
+        p = pack12(st)
+        pf = cut(p, hop, packed=True)
+        assert p.size == 3 * st.size // 2 and pf.shape == (B, P12) and np.array_equal(pf, pack12(fr))
+        forms["packed"] = (to_device(torch, p), to_device(torch, pf))
+    return forms
+
+
+@pytest.mark.parametrize("mode", list(MODES))
+def test_hop_call_equals_the_frame_call_on_host_cut_frames(ch, torch_mod, oracle, mode):
+    """Every kind, both input forms, B = 1, 5, 17, 37 and hop = 8, 4104, 8192, 16376, 16384 in one filter mode; and once,
+    at B = 5 and hop = 4104, the integer model on the cut frames."""
+    torch = torch_mod
+    args = configure(ch, mode)
+    s = samples()
+    for hop in HOPS:
+        for B in BATCHES:
+            forms = stream_and_frames(torch, s, hop, B)
+            for form, (d_stream, d_frames) in forms.items():
+                assert d_stream.dim() == 1 and d_stream.data_ptr() % 16 == 0
+                for kind in KINDS:
+                    got, ref = call(ch, kind, d_stream, hop), call(ch, kind, d_frames)
+                    assert got.shape == ref.shape and got.dtype == ref.dtype and got.shape[0] == B
+                    assert torch.equal(got, ref), (mode, hop, B, form, kind)
+                    assert ref.any(), (mode, hop, B, form, kind)
+            if (hop, B) == (4104, 5):
+                model = oracle.chain_q15(cut(s[:(B - 1) * hop + N], hop), *args)
+                for form, (d_stream, _) in forms.items():
+                    assert np.array_equal(ch.process_q15(d_stream, hop=hop).cpu().numpy(), model) and model.any(), (mode, form)
+
+
+@pytest.mark.parametrize("mode", ["b1_hann_u16", "gui_upload"])
+def test_full_scale_samples(ch, torch_mod, mode):
+    """int16 samples over the whole 16-bit range, which no packed stream can hold: the int16 form alone."""
+    torch = torch_mod
+    configure(ch, mode)
+    for hop, B in ((4104, 5), (8, 17)):
+        (d_stream, d_frames), = stream_and_frames(torch, samples(True), hop, B).values()
+        for kind in KINDS:
+            ref = call(ch, kind, d_frames)
+            assert torch.equal(call(ch, kind, d_stream, hop), ref) and ref.any(), (mode, hop, B, kind)
+
+
+@pytest.mark.parametrize("form", ["int16", "packed"])
+@pytest.mark.parametrize("mode", ["b1_rtl", "default", "wide6"])
+def test_poisoned_neighbours_and_canaries(ch, torch_mod, mode, form):
+    """The stream is a slice of a larger tensor whose elements before and after it are full-scale poison (the offset a
+    multiple of 16 bytes and of nothing larger), `out` a slice of a canary-filled tensor: the results are those of the stream
+    alone, and nothing outside [B, ...] is written.  A frame base off by a frame, or in bytes where samples are meant,
+    reads poison."""
+    torch = torch_mod
+    configure(ch, mode)
+    hop, B = 4104, 5
+    d_stream, _ = stream_and_frames(torch, samples(), hop, B)[form]
+    n = d_stream.numel()
+    lead = 16 // d_stream.element_size() * 3                                   # 48 bytes: 16-byte aligned, not 64
+    poison = 0x7FFF if form == "int16" else 0x7F                               # packed: the samples -129 and 2039
+    big = torch.full((lead + n + 2 * N,), poison, dtype=d_stream.dtype, device="cuda")
+    big[lead:lead + n] = d_stream
+    inner = big[lead:lead + n]
+    assert inner.is_contiguous() and inner.data_ptr() % 16 == 0 and inner.data_ptr() % 64 != 0
+    canary = 0x5A
+    for kind in ("iq", "marker", 16):
+        ref = call(ch, kind, d_stream, hop).clone()
+        nbytes, pad = ref.numel() * ref.element_size(), 4096
+        raw = torch.full((nbytes + 2 * pad,), canary, dtype=torch.uint8, device="cuda")
+        out = raw[pad:pad + nbytes].view(ref.dtype).view(ref.shape)
+        assert out.data_ptr() % 16 == 0
+        got = call(ch, kind, inner, hop, out=out)
+        torch.cuda.synchronize()
+        assert got.data_ptr() == out.data_ptr() and torch.equal(out, ref) and ref.any(), (mode, form, kind)
+        assert (raw[:pad] == canary).all().item() and (raw[pad + nbytes:] == canary).all().item(), (mode, form, kind)
+    assert (big[:lead] == poison).all().item() and (big[lead + n:] == poison).all().item()
+
+
+@pytest.mark.parametrize("form", ["int16", "packed"])
+def test_two_overlapping_blocks_equal_one_call_on_the_whole_stream(ch, torch_mod, form):
+    """Two calls on streams that overlap by N - hop samples, as StreamCutter cuts them: together they are one call on the
+    whole stream, and the frame call on all ten host-cut frames."""
+    from fpga_real_time_fft_analyzer_amd.ingest import StreamCutter, pack12
+    torch = torch_mod
+    configure(ch, "default")
+    hop, per_block = 4096, 5
+    st = samples()[:(2 * per_block - 1) * hop + N]
+    packed = form == "packed"
+    host = pack12(st) if packed else st
+    blocks = StreamCutter(hop, per_block, packed).push(host)
+    assert len(blocks) == 2
+    ov = (N - hop) * (3 if packed else 2) // 2
+    assert np.array_equal(blocks[0][-ov:], blocks[1][:ov])
+    for kind in ("iq", "marker"):
+        whole = call(ch, kind, to_device(torch, host), hop)
+        parts = torch.cat([call(ch, kind, to_device(torch, b), hop) for b in blocks])
+        frames = call(ch, kind, to_device(torch, cut(host, hop, packed)))
+        assert whole.shape[0] == 2 * per_block and torch.equal(parts, whole) and torch.equal(whole, frames) and frames.any()
+
+
+@pytest.mark.parametrize("form", ["int16", "packed"])
+@pytest.mark.parametrize("mode", ["b1_rtl", "default", "wide6"])
+def test_overlap_profiling_and_graph_capture(ch, torch_mod, mode, form):
+    """The launch contracts of the frame call, unstaged (0xB1: the FFT's first stage reads the stream) and staged (0x00,
+    0xA2: the cascade does): overlap depth 2 with flush (in 0xA2 the wide cascade's ordering behind the previous call), one
+    device time per timed call, capture into a graph after reserve; all outputs equal the stream-ordered frame call."""
+    torch = torch_mod
+    configure(ch, mode)
+    hop, B = 8192, 7
+    d_stream, d_frames = stream_and_frames(torch, samples(), hop, B)[form]
+    ch.reserve(8)
+    for kind in ("iq", "marker"):
+        ref = call(ch, kind, d_frames).clone()
+        assert ref.any()
+        check_overlap_profiling_and_graph_capture(torch, ch, lambda out: call(ch, kind, d_stream, hop, out=out), ref)
+
+
+def test_refusals_leave_the_handle_usable(ch, torch_mod):
+    """Through both C entry points: hop field 2049, bit 20 set, a field with low byte 3, 16 or 23, and an `in` 2 bytes (int16)
+    or 1 byte (packed) off a 16-byte boundary with a field set are SA_EINVAL; so is a field on sa_process_f32 and
+    sa_process_f32_i16.  The profiling ring shows no launch for any of them, and a good hop call afterwards is correct."""
+    from fpga_real_time_fft_analyzer_amd import abi
+    torch = torch_mod
+    configure(ch, "default")
+    hop, B = 4096, 5
+    forms = stream_and_frames(torch, samples(), hop, B)
+    L, h, stream = abi.lib(), ch._h, torch.cuda.current_stream().cuda_stream
+    good = abi.SA_Q15_HOP_KIND(abi.SA_Q15_OUT_IQ, hop)
+    out = torch.zeros((B, N, 2), dtype=torch.int16, device="cuda")
+    ref = ch.process_q15(forms["int16"][1]).clone()
+    ch.set_profiling(64)
+    entries = ((L.sa_process_q15_out, forms["int16"][0], 2), (L.sa_process_q15_p12, forms["packed"][0], 1))
+    for fn, d, _ in entries:
+        assert fn(h, d.data_ptr(), out.data_ptr(), B, good, stream) == 0
+        assert torch.equal(out, ref)
+    timed = len(ch.profile_read(64))
+    assert timed == 2
+    out.zero_()
+    for fn, d, off in entries:
+        assert fn(h, d.data_ptr(), out.data_ptr(), B, abi.SA_Q15_OUT_IQ | 2049 << 8, stream) == SA_EINVAL
+        assert fn(h, d.data_ptr(), out.data_ptr(), B, good | 1 << 20, stream) == SA_EINVAL
+        assert fn(h, d.data_ptr(), out.data_ptr(), B, good | 1 << 30, stream) == SA_EINVAL
+        for low in (3, 16, 23):
+            assert fn(h, d.data_ptr(), out.data_ptr(), B, abi.SA_Q15_HOP_KIND(low, hop), stream) == SA_EINVAL, low
+        # one frame fewer, so that the shifted stream still lies inside the tensor
+        assert (d.data_ptr() + off) % 16 == off
+        assert fn(h, d.data_ptr() + off, out.data_ptr(), B - 1, good, stream) == SA_EINVAL
+    xf = torch.zeros((B, N), dtype=torch.float32, device="cuda")
+    xi = torch.zeros((B, N), dtype=torch.int16, device="cuda")
+    of = torch.zeros((B, N), dtype=torch.float32, device="cuda")
+    word = abi.SA_Q15_HOP_KIND(abi.SA_OUT_MAG_FULL, hop)
+    assert L.sa_process_f32(h, xf.data_ptr(), of.data_ptr(), B, word, stream) == SA_EINVAL
+    assert L.sa_process_f32_i16(h, xi.data_ptr(), 1.0, of.data_ptr(), B, word, stream) == SA_EINVAL
+    assert len(ch.profile_read(64)) == timed                   # no refused call was timed: no call state committed
+    ch.set_profiling(0)
+    torch.cuda.synchronize()
+    assert not out.any() and not of.any()                      # nothing was launched
+    for fn, d, _ in entries:
+        out.zero_()
+        assert fn(h, d.data_ptr(), out.data_ptr(), B, good, stream) == 0
+        assert torch.equal(out, ref)
+    # field 2048 is the largest: hop = N, the plain call
+    whole = to_device(torch, samples()[:2 * N])
+    assert L.sa_process_q15_out(h, whole.data_ptr(), out.data_ptr(), 2, abi.SA_Q15_OUT_IQ | 2048 << 8, stream) == 0
+    assert torch.equal(out[:2], ch.process_q15(whole.view(2, N)))
+
+
+def test_wrapper_refusals(ch, torch_mod):
+    from fpga_real_time_fft_analyzer_amd.abi import SpecanError
+    torch = torch_mod
+    configure(ch, "default")
+    hop, B = 4096, 5
+    d_stream, d_frames = stream_and_frames(torch, samples(), hop, B)["int16"]
+    ref = ch.process_q15(d_frames).clone()
+
+    def refused(code, fn, *a, **kw):
+        with pytest.raises(SpecanError) as e:
+            fn(*a, **kw)
+        assert e.value.code == code, (a, kw)
+
+    for bad in (0, 4, 12, 16392, 8.0, True):
+        refused(SA_EINVAL, ch.process_q15, d_stream, hop=bad)
+        refused(SA_EINVAL, ch.markers_q15, d_stream, hop=bad)
+        refused(SA_EINVAL, ch.traces_q15, d_stream, hop=bad)
+    refused(SA_ESHAPE, ch.process_q15, d_frames, hop=hop)                       # 2-D with a hop
+    refused(SA_ESHAPE, ch.process_q15, d_stream)                                # 1-D without one
+    refused(SA_ESHAPE, ch.process_q15, d_stream[:-8].clone(), hop=hop)          # (n - N) % hop != 0
+    refused(SA_ESHAPE, ch.process_q15, d_stream[:N - 8].clone(), hop=hop)       # too short for one frame
+    refused(SA_EINVAL, ch.process_q15, d_stream.to(torch.float32), hop=hop)     # wrong dtype
+    refused(SA_ESHAPE, ch.process_q15, d_stream, out=torch.empty((B + 1, N, 2), dtype=torch.int16, device="cuda"), hop=hop)
+    assert torch.equal(ch.process_q15(d_stream, hop=hop), ref)
+    pm, pb, bp = ch.markers_q15(d_stream, hop=hop)
+    qm, qb, bq = ch.markers_q15(d_frames)
+    assert torch.equal(pm, qm) and torch.equal(pb, qb) and torch.equal(bp, bq) and pm.shape == (B,)
+
+
+@pytest.mark.parametrize("form", ["int16", "packed"])
+def test_stream_feeder(ch, torch_mod, form):
+    """DeviceFeeder(max_batch=8, stream=True) on three blocks of 5 frames at hop 4096 from StreamCutter: the markers are
+    those of one frame call on all 15 host-cut frames.  A block of more than max_batch frames' elements is refused."""
+    from fpga_real_time_fft_analyzer_amd.ingest import DeviceFeeder, StreamCutter, pack12
+    torch = torch_mod
+    configure(ch, "default")
+    hop, per_block = 4096, 5
+    packed = form == "packed"
+    st = samples()[:(3 * per_block - 1) * hop + N]
+    host = pack12(st) if packed else st
+    blocks = StreamCutter(hop, per_block, packed).push(host)
+    assert len(blocks) == 3 and all(b.ndim == 1 for b in blocks)
+    feeder = DeviceFeeder(0, max_batch=8, packed=packed, stream=True)
+    got = []
+    for xd in feeder.feed(blocks):
+        assert xd.dim() == 1 and xd.numel() == blocks[0].size and xd.data_ptr() % 16 == 0
+        got.append(ch.process_q15(xd, out_kind="marker", hop=hop).clone())
+    torch.cuda.synchronize()
+    ref = ch.process_q15(to_device(torch, cut(host, hop, packed)), out_kind="marker")
+    assert ref.shape == (15, 4) and torch.equal(torch.cat(got), ref) and ref.any()
+    with pytest.raises(ValueError):
+        next(iter(feeder.feed([np.zeros(8 * (P12 if packed else N) + 2, host.dtype)])))

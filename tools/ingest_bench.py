@@ -12,7 +12,12 @@ conversion pass on the device, the PCIe volume of the Q15 path.
 32768), packed once up front as the int16 batches are generated up front; the GB/s figures count the packed bytes.
 --packed-q15: the packed feeder into the INTEGER chain (sa_process_q15_p12; without --float / --packed, which keep their
 meaning and win when given as well): the bit-exact frames from 24576 input bytes per frame.
-usage: ingest_bench.py [batch_frames] [n_batches] [mode] [--events] [--float] [--packed] [--packed-q15]"""
+--hop H (the integer chain; with --packed-q15 on packed samples): overlapping frames at hop H, a multiple of 8.  The sample
+stream through StreamCutter(H, batch_frames) + the stream feeder into process_q15(x, hop=H) -- every sample crosses the link
+once -- against the same stream cut on the host by FrameCutter(H) + the frame feeder into the frame call, 16384 / H times
+the bytes; both cut up front, 'marker' records out, the two alternating in one process over --rounds R (default 5) runs of
+n_batches batches each.  Choose n_batches so that a run lasts some tenths of a second.  The bound on the ratio is 16384 / H.
+usage: ingest_bench.py [batch_frames] [n_batches] [mode] [--events] [--float] [--packed] [--packed-q15] [--hop H [--rounds R]]"""
 import os
 import sys
 import time
@@ -23,7 +28,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from fpga_real_time_fft_analyzer_amd.chain import SpectrumChain  # noqa: E402
-from fpga_real_time_fft_analyzer_amd.ingest import DeviceFeeder, pack12  # noqa: E402
+from fpga_real_time_fft_analyzer_amd.ingest import DeviceFeeder, FrameCutter, StreamCutter, pack12  # noqa: E402
 
 # the box gives this job 16 CPUs of a 256-core host: torch's default intra-op pool (one thread per visible core)
 # stalls the staging copy for 50-100 ms every dozen batches
@@ -37,6 +42,80 @@ FLOAT = "--float" in sys.argv or PACKED
 PACKED = PACKED or ("--packed-q15" in sys.argv and not FLOAT)              # from here on: the input form alone
 ROW, FRAME_BYTES = (3 * N // 2, 3 * N // 2) if PACKED else (N, 2 * N)      # elements and bytes of an input frame
 IN_DT = torch.uint8 if PACKED else torch.int16
+
+
+
+def opt(name, default):
+    return int(sys.argv[sys.argv.index(name) + 1]) if name in sys.argv else default
+
+
+def hop_mode(hop, rounds):
+    """--hop: the stream form against host-cut frames, alternating"""
+    ch = SpectrumChain(0)
+    ch.set_filter_mode(mode)
+    ch.reserve(B)
+    s = np.random.default_rng(0).integers(-2048, 2048, size=(4 * B - 1) * hop + N, dtype=np.int16)
+    s = pack12(s) if PACKED else s
+    blocks = StreamCutter(hop, B, PACKED).push(s)                      # 4 distinct blocks of B frames, reused
+    frames = FrameCutter(hop, PACKED).push(s)
+    assert len(blocks) == 4 and frames.shape == (4 * B, ROW)
+    batches = [frames[i * B:(i + 1) * B] for i in range(4)]
+    elem = s.itemsize
+    forms = {"frames": (DeviceFeeder(0, max_batch=B, packed=PACKED), batches, None, B * ROW * elem),
+             "stream": (DeviceFeeder(0, max_batch=B, packed=PACKED, stream=True), blocks, hop, blocks[0].size * elem)}
+    out = [torch.empty((B, 4), dtype=torch.int32, device="cuda") for _ in range(2)]
+
+    def run(form, nb):
+        feeder, data, h, _ = forms[form]
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for i, xd in enumerate(feeder.feed(data[j & 3] for j in range(nb))):
+            ch.process_q15(xd, out=out[i & 1], out_kind="marker", hop=h)
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0
+
+    rec = {}
+    for form in forms:                                                  # warm-up, and the two forms agree
+        run(form, 4)
+        rec[form] = out[1].clone()
+    assert torch.equal(rec["frames"], rec["stream"]), "the stream form and the host-cut frames disagree"
+    rate = {form: [] for form in forms}
+    for _ in range(rounds):
+        for form in forms:
+            rate[form].append(NB * B / run(form, NB))
+    h2d = pure_h2d()
+    print(f"hop {hop} ({'packed 12-bit' if PACKED else 'int16'} samples), batch {B} frames x {NB} batches per run, {rounds} "
+          f"alternating runs, filter mode 0x{mode:02X}, marker records out; a frames run lasts {NB * B / np.median(rate['frames']):.2f} s")
+    print(f"  pinned host -> device copy alone: {h2d / 1e9:6.1f} GB/s")
+    for form, (_, _, _, nbytes) in forms.items():
+        r = np.array(rate[form])
+        print(f"  {form:6s}: {nbytes / B:8.0f} bytes per frame on the link; M frames/s per run "
+              f"{' '.join(f'{v / 1e6:.3f}' for v in r)}; median {np.median(r) / 1e6:.3f} (max/min {r.max() / r.min():.3f}) = "
+              f"{np.median(r) * nbytes / B / 1e9:5.1f} GB/s")
+    ratio = np.array(rate["stream"]) / np.array(rate["frames"])
+    print(f"  stream / frames per round: {' '.join(f'{v:.3f}' for v in ratio)}; median {np.median(ratio):.3f}; "
+          f"the bound is 16384 / hop = {N / hop:.2f} (bytes: {forms['frames'][3] / forms['stream'][3]:.3f})")
+    ch.close()
+
+
+def pure_h2d():
+    pin = torch.empty((B, ROW), dtype=IN_DT).pin_memory()
+    dev = torch.empty((B, ROW), dtype=IN_DT, device="cuda")
+    for _ in range(3):
+        dev.copy_(pin, non_blocking=True)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(20):
+        dev.copy_(pin, non_blocking=True)
+    torch.cuda.synchronize()
+    return 20 * B * FRAME_BYTES / (time.perf_counter() - t0)
+
+
+if "--hop" in sys.argv:
+    if FLOAT:
+        sys.exit("--hop is a mode of the integer chain (with --packed-q15 for packed samples)")
+    hop_mode(opt("--hop", N), opt("--rounds", 5))
+    sys.exit(0)
 
 ch = SpectrumChain(0)
 if FLOAT:
@@ -66,19 +145,6 @@ def run(batches):
         process(xd, out[i & 1])
     torch.cuda.synchronize()
     return time.perf_counter() - t0
-
-
-def pure_h2d():
-    pin = torch.empty((B, ROW), dtype=IN_DT).pin_memory()
-    dev = torch.empty((B, ROW), dtype=IN_DT, device="cuda")
-    for _ in range(3):
-        dev.copy_(pin, non_blocking=True)
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(20):
-        dev.copy_(pin, non_blocking=True)
-    torch.cuda.synchronize()
-    return 20 * B * FRAME_BYTES / (time.perf_counter() - t0)
 
 
 def pure_kernels():
