@@ -25,6 +25,9 @@ SA_OUT_MAG_FULL, SA_OUT_MAG_HALF, SA_OUT_SPEC_HALF, SA_OUT_TIME, SA_OUT_MARKER =
 SA_Q15_OUT_IQ, SA_Q15_OUT_MAG, SA_Q15_OUT_MARKER = 0, 1, 2
 SA_Q15_TRACE_LOG2W_MIN, SA_Q15_TRACE_LOG2W_MAX = 1, 6
 SA_PRECISION_F32, SA_PRECISION_F64_STATE = 0, 1
+# the entry points as sa_debug_check_pointers numbers them (SA_ENTRY_* of include/specan.h)
+SA_ENTRIES = ("sa_process_f32", "sa_process_f32_i16", "sa_process_f32_p12", "sa_process_q15", "sa_process_q15_out",
+              "sa_process_q15_p12", "sa_filter_q15", "sa_filter_q15_p12")
 
 
 def SA_Q15_TRACE_KIND(log2w: int) -> int:
@@ -113,6 +116,7 @@ SIGNATURES = {
     "sa_process_f32_p12": (_INT, [H, C.c_void_p, C.c_float, C.c_void_p, _INT, _INT, C.c_void_p]),
     "sa_pack_samples_p12": (_INT, [_P(C.c_int16), C.c_size_t, _P(C.c_uint8)]),
     "sa_unpack_samples_p12": (_INT, [_P(C.c_uint8), C.c_size_t, _P(C.c_int16)]),
+    "sa_debug_check_pointers": (_INT, [_INT, _INT, C.c_uint64, C.c_uint64, _INT]),
     "sa_pack_frame": (_INT, [_P(C.c_int16), _P(C.c_uint8)]),
     "sa_debug_iir_plan_f32": (_INT, [H, _P(C.c_float), _INT]),
     "sa_iir_plan_from_sos": (_INT, [_P(C.c_double), _INT, _P(C.c_float), _INT]),

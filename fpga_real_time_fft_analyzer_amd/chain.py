@@ -425,7 +425,13 @@ class SpectrumChain:
         A uint8 tensor [B,24576] holds the same samples packed to 12 bits, two samples in three bytes (include/specan.h,
         "p12"; ingest.pack12 is the host packer): it goes to sa_process_f32_p12, is unpacked in the stage-in and gives
         the results of the int16 tensor of the same samples bit for bit, from three quarters of the input bytes.  Its
-        data pointer must be 16-byte aligned (any tensor torch allocates is, and so is every whole-frame slice of one)."""
+        data pointer must be 16-byte aligned (any tensor torch allocates is, and so is every whole-frame slice of one).
+
+        Pointer contract (include/specan.h; checked by the C entry point, SA_EINVAL): the data pointer of ``x`` is 16-byte
+        aligned, and so is that of ``out`` except for 'mag_half' (4 bytes) and 'spec_half' (8 bytes), which are aligned to
+        their element: every row slice ``big[a:a+B]`` of such a tensor is a valid ``out``.  The bytes read through ``x``
+        and the bytes written through ``out`` are disjoint: no call works in place (``out=x``); buffers that merely touch
+        are fine.  A contiguous view that starts one element into a buffer is not aligned."""
         return self._process(FLOAT_CHAIN, x, out, out_kind, scale)
 
     def markers(self, x: torch.Tensor, out: Optional[torch.Tensor] = None, scale: float = 1.0 / 2048.0):
@@ -453,7 +459,11 @@ class SpectrumChain:
         ``x`` is then ONE 1-D stream -- (B-1) * hop + 16384 int16 samples, or 3/2 as many packed bytes -- frame b is its
         samples [b * hop, b * hop + 16384), and the result is that of the plain call on those B frames copied out
         (``ingest.FrameCutter(hop)``), bit for bit, with every sample sent to the device once (``ingest.StreamCutter`` cuts
-        such streams).  The data pointer must be 16-byte aligned for both dtypes.  ``hop=None`` is the call on frames."""
+        such streams).  The data pointer must be 16-byte aligned for both dtypes.  ``hop=None`` is the call on frames.
+
+        Pointer contract (include/specan.h; checked by the C entry point, SA_EINVAL): the data pointers of ``x`` and of
+        ``out`` are 16-byte aligned for every ``out_kind``, and the bytes read through ``x`` -- with ``hop`` the stream, not
+        B whole frames -- and the bytes written through ``out`` are disjoint; buffers that merely touch are fine."""
         return self._process(Q15_CHAIN, x, out, out_kind, hop=hop)
 
     def markers_q15(self, x: torch.Tensor, out: Optional[torch.Tensor] = None, hop: Optional[int] = None):
@@ -479,7 +489,11 @@ class SpectrumChain:
 
     def filter_q15(self, x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Window (+ integer IIR) only: the FFT input stream, [B,16384] int16.  ``x`` is [B,16384] int16 or the same
-        samples packed, [B,24576] uint8 (sa_filter_q15_p12), as for :meth:`process_q15`."""
+        samples packed, [B,24576] uint8 (sa_filter_q15_p12), as for :meth:`process_q15`.
+
+        Pointer contract (include/specan.h; checked by the C entry point, SA_EINVAL): the data pointers of ``x`` and of
+        ``out`` are 16-byte aligned, and the bytes read through ``x`` and written through ``out`` are disjoint: the call
+        does not work in place (``out=x``), although the sizes would match; buffers that merely touch are fine."""
         return self._process(Q15_WINDOW_CHAIN, x, out, None)
 
     def frames_bytes(self, iq: torch.Tensor) -> list[bytes]:

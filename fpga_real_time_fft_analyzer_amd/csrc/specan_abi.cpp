@@ -8,6 +8,7 @@
 // falls back to CPU compute.
 #include "iir_plan.hpp"
 #include "sa_handle.hpp"
+#include "sa_pointers.hpp"
 #include "sa_tables.hpp"
 
 #include <array>
@@ -426,9 +427,15 @@ static SaQ15Params q15_params(const sa_handle *h)
 // `hop`: null, or where the entry point's word is a SA_Q15_HOP_KIND: the word is taken apart before anything else, *hop is
 // its hop in samples (0: frames) and the kind checked below is its low byte.  An entry point without one (every float one)
 // sees a word with a hop field as the unknown kind it is there.
+// Last, the pointer contract of include/specan.h: `chain` names the family of outputs, sa_pointers.cpp holds the rule.  The
+// alignment rules that were there before it (marker and trace `out`, packed `in`, a stream `in`) are instances of it and
+// keep their messages; all of this before any call state exists.
 static int check_process_args(sa_handle *h, const char *fn, const void *in, SaInKind kind, const void *out, int batch,
-                              int out_kind, int marker, const char *marker_name, bool trace, bool scale_finite, int *hop = nullptr)
+                              int out_kind, SaChain chain, int marker, const char *marker_name, bool trace, bool scale_finite,
+                              int *hop = nullptr)
 {
+    static_assert((int)SaInKind::F32 == kSaInF32 && (int)SaInKind::I16 == kSaInI16 && (int)SaInKind::P12 == kSaInP12,
+                  "sa_pointers.hpp numbers the input forms as SaInKind does");
     static_assert(SA_OUT_MAG_FULL == 0 && SA_Q15_OUT_IQ == 0, "the kinds of both chains are 0 .. marker");
     int field = 0;
     bool bad_word = false;
@@ -446,15 +453,28 @@ static int check_process_args(sa_handle *h, const char *fn, const void *in, SaIn
     if (!scale_finite) return fail_at(h, SA_EINVAL, fn, "scale is not finite");
     if (batch == 0) return SA_OK;
     if (!in || !out) return fail_at(h, SA_EINVAL, fn, "NULL tensor");
-    if ((out_kind == marker || is_trace) && ((uintptr_t)out & 15u) != 0) {
-        char msg[64];
+    SaCallSpan span;
+    if (!sa_call_span(chain, (int)kind, out_kind, 8 * field, batch, &span)) return fail_at(h, SA_EINVAL, fn, "bad out_kind");
+    const unsigned faults = sa_pointer_faults(span, (uint64_t)(uintptr_t)in, (uint64_t)(uintptr_t)out);
+    char msg[96];
+    if ((out_kind == marker || is_trace) && (faults & kSaPtrOutAlign)) {
         std::snprintf(msg, sizeof msg, "%s output must be 16-byte aligned", is_trace ? "SA_Q15_TRACE_KIND" : marker_name);
         return fail_at(h, SA_EINVAL, fn, msg);
     }
-    if (kind == SaInKind::P12 && ((uintptr_t)in & 15u) != 0)       // the stage-ins issue 16-byte requests; every frame is then aligned
-        return fail_at(h, SA_EINVAL, fn, "packed input must be 16-byte aligned");
-    if (field != 0 && ((uintptr_t)in & 15u) != 0)                  // int16: every frame is then aligned for the 16-byte tile loads
-        return fail_at(h, SA_EINVAL, fn, "a sample stream (SA_Q15_HOP_KIND) must be 16-byte aligned");
+    if (faults & kSaPtrInAlign)       // the stage-ins and tile loads issue 16-byte requests; every frame is then aligned (int16
+        return fail_at(h, SA_EINVAL, fn,     // streams: 16 h bytes apart; packed streams need a dword per frame and have it)
+                       kind == SaInKind::P12 ? "packed input must be 16-byte aligned"
+                       : field != 0          ? "a sample stream (SA_Q15_HOP_KIND) must be 16-byte aligned"
+                                             : "`in` must be 16-byte aligned");
+    if (faults & kSaPtrOutAlign) {
+        std::snprintf(msg, sizeof msg, "`out` must be %u-byte aligned", span.out_align);
+        return fail_at(h, SA_EINVAL, fn, msg);
+    }
+    if (faults & kSaPtrOverlap) {
+        std::snprintf(msg, sizeof msg, "`in` (%llu bytes read) and `out` (%llu bytes written) overlap",
+                      (unsigned long long)span.in_bytes, (unsigned long long)span.out_bytes);
+        return fail_at(h, SA_EINVAL, fn, msg);
+    }
     if (hop) *hop = 8 * field;
     return SA_OK;
 }
@@ -468,8 +488,8 @@ static int process_q15(sa_handle *h, const char *fn, const void *in, SaInKind ki
                        void *stream, bool fft, bool hop_word = false)
 {
     int hop = 0;
-    { const int rc = check_process_args(h, fn, in, kind, out, batch, out_kind, SA_Q15_OUT_MARKER, "SA_Q15_OUT_MARKER", fft, true,
-                                        hop_word ? &hop : nullptr);
+    { const int rc = check_process_args(h, fn, in, kind, out, batch, out_kind, fft ? SaChain::Q15 : SaChain::Q15Filter,
+                                        SA_Q15_OUT_MARKER, "SA_Q15_OUT_MARKER", fft, true, hop_word ? &hop : nullptr);
       if (rc != SA_OK || batch == 0) return rc; }
     if (hop_word) out_kind &= 0xFF;
     SA_HIP(h, hipSetDevice(h->device));
@@ -538,7 +558,8 @@ static int process_float(sa_handle *h, const char *fn, const void *in, SaInKind 
                          int out_kind, void *stream)
 {
     const bool scale_finite = scale == scale && scale - scale == 0.f;
-    { const int rc = check_process_args(h, fn, in, kind, out, batch, out_kind, SA_OUT_MARKER, "SA_OUT_MARKER", false, scale_finite);
+    { const int rc = check_process_args(h, fn, in, kind, out, batch, out_kind, SaChain::Float, SA_OUT_MARKER, "SA_OUT_MARKER", false,
+                                        scale_finite);
       if (rc != SA_OK || batch == 0) return rc; }
     if (h->filter_mode == SA_FILTER_WIDE)
         return fail_at(h, SA_ESTATE, fn, "filter mode 0xA2 (Q2.14) belongs to the Q15 path; use 0xA1 with sa_load_sos_f32");

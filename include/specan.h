@@ -17,6 +17,28 @@
  *     sa_create() fails with SA_EHIP.
  *   - the library never allocates, frees or retains caller tensors.  It owns the opaque handle,
  *     its device-side tables and (for the Q15 IIR modes) a workspace sized by sa_reserve().
+ *   - pointer contract of every process and filter call (sa_process_f32, _f32_i16, _f32_p12, sa_process_q15, _q15_out,
+ *     _q15_p12, sa_filter_q15, _q15_p12): the kernels move 16 bytes per lane through the two pointers and declare both
+ *     `__restrict__`, so
+ *       alignment   `in` is 16-byte aligned: float32, int16, packed and hop streams alike (the rules stated below for
+ *                   packed input and for sample streams are instances of this one).  `out` is 16-byte aligned for
+ *                   SA_OUT_MAG_FULL, SA_OUT_TIME, SA_OUT_MARKER, SA_Q15_OUT_IQ, SA_Q15_OUT_MAG, SA_Q15_OUT_MARKER, every
+ *                   SA_Q15_TRACE_KIND and the output of sa_filter_q15*.  For the two half layouts `out` is aligned to its
+ *                   element: 4 bytes for SA_OUT_MAG_HALF, 8 bytes for SA_OUT_SPEC_HALF -- their rows are 32 772 and 65 544
+ *                   bytes long, so every row slice out[a : a + B] of such a tensor stays valid.  Anything else is SA_EINVAL;
+ *                   the message names the entry point and which pointer is at fault.
+ *       no overlap  the bytes the call reads, [in, in + in_bytes), and the bytes it writes, [out, out + out_bytes), must be
+ *                   disjoint; otherwise the call returns SA_EINVAL, `out == in` included (no call works in place).
+ *                   in_bytes is B * 65536 for float32, B * 32768 for int16 and B * 24576 for packed input; with a hop H it
+ *                   is ((B - 1) * H + 16384) * 2 for int16 and three quarters of that for packed.  out_bytes follows the
+ *                   tables of output kinds below (B rows of 65536, 32772, 65544, 65536, 16 bytes for SA_OUT_*; 65536,
+ *                   65536, 16 for SA_Q15_OUT_*; 131072 >> k for SA_Q15_TRACE_KIND(k); 32768 for sa_filter_q15*).  Buffers
+ *                   that merely touch (out == in + in_bytes, or the reverse) are accepted.
+ *       a refusal   launches nothing and changes no call state: launch slot, overlap counter, profiling ring, the stream
+ *                   the handle remembers and workspace growth all stay as they were, and the next call on the handle
+ *                   behaves as if the refused one had not been made.
+ *       order       these checks come after the NULL-tensor check; an empty batch returns SA_OK before any pointer is
+ *                   looked at.  sa_debug_check_pointers() below is the same rule without a handle.
  *   - a handle is not thread-safe; use one handle per (GPU, stream) -- different handles may be
  *     used from different host threads at the same time (one thread per GPU).
  *     Process calls are asynchronous on the given stream; mode / coefficient / window changes are
@@ -297,8 +319,9 @@ int sa_process_q15(sa_handle *h, const int16_t *in, int16_t *out_iq, int batch, 
  * (gui.py:250-260) on the host, SA_Q15_OUT_MARKER the range slice and np.max / np.argmax on top (gui.py:294-305, 415-455,
  * 691-712), 16 bytes per frame instead of 64 KiB.  Everything sa_process_q15() does holds for every kind: all four filter
  * modes, both window modes, custom ROMs, every overlap depth, launch timing, hipGraph capture once sa_reserve() has
- * sized the workspace.  SA_EINVAL for an unknown kind, a NULL tensor or a marker `out` that is not 16-byte aligned:
- * nothing is launched and no call state changes.  out_kind may also be SA_Q15_TRACE_KIND(k), k = 1..6 (above): one
+ * sized the workspace.  SA_EINVAL for an unknown kind, a NULL tensor or a marker `out` that is not 16-byte aligned (an
+ * instance of the pointer contract at the top of this file, which holds for every kind): nothing is launched and no call
+ * state changes.  out_kind may also be SA_Q15_TRACE_KIND(k), k = 1..6 (above): one
  * sa_trace_point_q15 per bucket of 2^k bins, under the same rules, its `out` 16-byte aligned as well. */
 int sa_process_q15_out(sa_handle *h, const int16_t *in, void *out, int batch, int out_kind, void *stream);
 
@@ -388,7 +411,8 @@ int sa_filter_q15_p12(sa_handle *h, const uint8_t *in /* [B,24576] device */, in
  *     cut into frames) -- and frame b is its samples [b hop, b hop + 16384).  `out` is what it is for frames: [B, ...]
  *     per kind, bit for bit the result of the plain call on the B frames copied out of the stream.  h = 2048 (hop = N)
  *     gives the bits of the plain call on the same memory.
- *   - `in` must be 16-byte aligned for both input forms when h > 0 (SA_EINVAL otherwise).  int16: every frame is then 16-byte
+ *   - `in` must be 16-byte aligned for both input forms (SA_EINVAL otherwise; the pointer contract at the top of this file,
+ *     whose message names the sample stream when h > 0).  int16: every frame is then 16-byte
  *     aligned (16 h bytes apart), which the cascades' 16-byte tile loads need.  Packed: frame b begins at byte 12 h b -- on
  *     a dword, which is all the packed loads need, and deliberately NOT on 16 bytes.  No byte outside the stream is read:
  *     the last frame ends with it.
@@ -413,6 +437,23 @@ int sa_filter_q15_p12(sa_handle *h, const uint8_t *in /* [B,24576] device */, in
  * is written.  Unpacking sign-extends to int16. */
 int sa_pack_samples_p12(const int16_t *samples, size_t n, uint8_t *packed /* 3n/2 bytes */);
 int sa_unpack_samples_p12(const uint8_t *packed, size_t n, int16_t *samples);
+
+/* Introspection for tests: the pointer contract of the process and filter calls (top of this file) as a pure function -- no
+ * handle, no GPU, the addresses are compared as integers and never dereferenced.  `entry` names the entry point
+ * (SA_ENTRY_*), `kind_word` is its out_kind argument, a SA_Q15_HOP_KIND word where the entry point takes one (ignored by the
+ * entry points that have no out_kind).  SA_OK where the call would pass its pointer checks; SA_EINVAL for a misaligned
+ * `in` or `out`, overlapping byte ranges, a zero address, an unknown entry or a kind word the entry point refuses; SA_ESHAPE
+ * for a negative batch; batch == 0 is SA_OK for any addresses.  The entry points themselves ask the same code. */
+#define SA_ENTRY_PROCESS_F32      0
+#define SA_ENTRY_PROCESS_F32_I16  1
+#define SA_ENTRY_PROCESS_F32_P12  2
+#define SA_ENTRY_PROCESS_Q15      3
+#define SA_ENTRY_PROCESS_Q15_OUT  4
+#define SA_ENTRY_PROCESS_Q15_P12  5
+#define SA_ENTRY_FILTER_Q15       6
+#define SA_ENTRY_FILTER_Q15_P12   7
+#define SA_ENTRY_COUNT            8
+int sa_debug_check_pointers(int entry, int kind_word, uint64_t in_addr, uint64_t out_addr, int batch);
 
 /* Host helper: view of one frame as the byte stream sequ2 emits.  On little-endian hosts the
  * Q15 output already is that stream; this copies 65536 bytes and is provided for symmetry with

@@ -28,7 +28,8 @@ def test_library_exports_every_declared_symbol(hip_lib_built):
 
 def test_binding_table_names_exactly_the_declared_symbols():
     from fpga_real_time_fft_analyzer_amd import abi
-    assert sorted(abi.SIGNATURES) == declared_symbols() and len(abi.SIGNATURES) == 44
+    assert sorted(abi.SIGNATURES) == declared_symbols() and len(abi.SIGNATURES) == 45
+    assert "sa_debug_check_pointers" in abi.SIGNATURES
 
 
 def test_every_declared_symbol_is_bound_with_its_signature(hip_lib_built):

@@ -212,7 +212,7 @@ def test_overlap_profiling_and_graph_capture(ch, torch_mod, mode, form):
 
 def test_refusals_leave_the_handle_usable(ch, torch_mod):
     """Through both C entry points: hop field 2049, bit 20 set, a field with low byte 3, 16 or 23, and an `in` 2 bytes (int16)
-    or 1 byte (packed) off a 16-byte boundary with a field set are SA_EINVAL; so is a field on sa_process_f32 and
+    or 1 byte (packed) off a 16-byte boundary, with a field set or without one, are SA_EINVAL; so is a field on sa_process_f32 and
     sa_process_f32_i16.  The profiling ring shows no launch for any of them, and a good hop call afterwards is correct."""
     from fpga_real_time_fft_analyzer_amd import abi
     torch = torch_mod
@@ -240,6 +240,8 @@ def test_refusals_leave_the_handle_usable(ch, torch_mod):
         # one frame fewer, so that the shifted stream still lies inside the tensor
         assert (d.data_ptr() + off) % 16 == off
         assert fn(h, d.data_ptr() + off, out.data_ptr(), B - 1, good, stream) == SA_EINVAL
+        # the same pointer without a field: one frame inside the stream, refused by the pointer contract of every process call
+        assert fn(h, d.data_ptr() + off, out.data_ptr(), 1, abi.SA_Q15_OUT_IQ, stream) == SA_EINVAL
     xf = torch.zeros((B, N), dtype=torch.float32, device="cuda")
     xi = torch.zeros((B, N), dtype=torch.int16, device="cuda")
     of = torch.zeros((B, N), dtype=torch.float32, device="cuda")
