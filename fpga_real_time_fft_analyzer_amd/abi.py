@@ -35,6 +35,15 @@ def SA_Q15_TRACE_KIND(log2w: int) -> int:
     return 0x10 | log2w
 
 
+SA_Q15_TRACE_LOG2A_MIN, SA_Q15_TRACE_LOG2A_MAX = 1, 7
+
+
+def SA_Q15_TRACE_AVG_KIND(log2w: int, log2a: int) -> int:
+    """The out_kind of the Q15 chain's trace over buckets of 2**log2w bins and groups of 2**log2a consecutive frames (the macro
+    of include/specan.h): max hold and summed power, one record per bucket and group."""
+    return 0x80 | log2a << 3 | log2w
+
+
 SA_Q15_HOP_FIELD_MAX = 2048
 
 

@@ -49,7 +49,8 @@ _ARGS = {"sa_process_f32": (False, True), "sa_process_f32_i16": (True, True), "s
 class _Chain(NamedTuple):
     """What a process call has to know about one chain.  A new input form is one row of ``inputs``, a new output kind one
     row of ``outputs``."""
-    outputs: dict   # out_kind -> (C code, shape of one frame's output, torch dtype)
+    outputs: dict   # out_kind -> (C code, shape of one row of the output, torch dtype[, frames per row]): a row is one frame's
+                    # output, or, where the fourth entry names an A > 1, that of A consecutive frames (B a multiple of A)
     inputs: dict    # torch dtype of x -> _form(...); the first dtype stands in the message for an x that is no tensor of a
                     # listed dtype
     streams: dict = {}  # the same for a call with ``hop``: x is ONE 1-D stream, frame b its `row` elements from element
@@ -57,9 +58,17 @@ class _Chain(NamedTuple):
                         # takes frames only.
 
     def output(self, out_kind) -> tuple:
+        """(C code, shape of one row, torch dtype, frames per row) of ``out_kind``."""
         if out_kind not in self.outputs:
             raise SpecanError(abi.SA_EINVAL, f"out_kind must be one of {sorted(self.outputs)}")
-        return self.outputs[out_kind]
+        return (self.outputs[out_kind] + (1,))[:4]
+
+    def rows(self, out_kind, B: int) -> int:
+        """The rows of the output of a call on ``B`` frames: SA_ESHAPE where B is no multiple of the frames per row."""
+        per_row = self.output(out_kind)[3]
+        if B % per_row:
+            raise SpecanError(abi.SA_ESHAPE, f"the batch ({B} frames) must be a multiple of {per_row}")
+        return B // per_row
 
 
 def _form(row: int, outputs: dict, name: str, **other) -> tuple:
@@ -96,6 +105,14 @@ _TRACE_OUT = {1 << k: (abi.SA_Q15_TRACE_KIND(k), (SA_N >> k, 2), torch.float32)
 Q15_TRACE_CHAIN = _Chain(_TRACE_OUT, {torch.int16: _form(SA_N, _TRACE_OUT, "sa_process_q15_out"),
                                       torch.uint8: _form(SA_P12_FRAME_BYTES, _TRACE_OUT, "sa_process_q15_p12")},
                          _q15_streams(_TRACE_OUT))
+# the trace over groups of A = 2^a consecutive frames (traces_q15(group=A)): one output per (W, A), one row per group
+_TRACE_AVG_OUT = {(1 << k, 1 << a): (abi.SA_Q15_TRACE_AVG_KIND(k, a), (SA_N >> k, 2), torch.float32, 1 << a)
+                  for k in range(abi.SA_Q15_TRACE_LOG2W_MIN, abi.SA_Q15_TRACE_LOG2W_MAX + 1)
+                  for a in range(abi.SA_Q15_TRACE_LOG2A_MIN, abi.SA_Q15_TRACE_LOG2A_MAX + 1)}
+TRACE_GROUPS = tuple(1 << a for a in range(abi.SA_Q15_TRACE_LOG2A_MIN, abi.SA_Q15_TRACE_LOG2A_MAX + 1))
+Q15_TRACE_AVG_CHAIN = _Chain(_TRACE_AVG_OUT, {torch.int16: _form(SA_N, _TRACE_AVG_OUT, "sa_process_q15_out"),
+                                              torch.uint8: _form(SA_P12_FRAME_BYTES, _TRACE_AVG_OUT, "sa_process_q15_p12")},
+                             _q15_streams(_TRACE_AVG_OUT))
 # the Q15 chain without its FFT (filter_q15): one output, which has no name
 _WINDOW_OUT = {None: (SA_Q15_OUT_IQ, (SA_N,), torch.int16)}
 Q15_WINDOW_CHAIN = _Chain(_WINDOW_OUT, {torch.int16: _form(SA_N, _WINDOW_OUT, "sa_filter_q15"),
@@ -104,8 +121,8 @@ Q15_WINDOW_CHAIN = _Chain(_WINDOW_OUT, {torch.int16: _form(SA_N, _WINDOW_OUT, "s
 
 def output_spec(chain: _Chain, out_kind: Optional[str], B: int) -> tuple:
     """``(shape, dtype)`` of the output of a process call on ``B`` frames (no handle, no GPU)."""
-    _, frame, dtype = chain.output(out_kind)
-    return (B,) + frame, dtype
+    _, frame, dtype, _ = chain.output(out_kind)
+    return (chain.rows(out_kind, B),) + frame, dtype
 
 
 def _sized_export(fn, head: tuple, dtype, what: str) -> np.ndarray:
@@ -213,7 +230,7 @@ class SpectrumChain:
     def _process(self, chain: _Chain, x, out, out_kind, scale=None, hop=None):
         """Every process call: ``x`` by its dtype to the chain's entry point for it, into ``out`` (allocated when None).
         ``hop``: ``x`` is one sample stream and the frames are cut from it on the device (the chain's ``streams``)."""
-        code, frame, dt = chain.output(out_kind)
+        code, frame, dt, _ = chain.output(out_kind)
         forms = chain.inputs
         if hop is not None:
             if isinstance(hop, bool) or not isinstance(hop, (int, np.integer)) or not 8 <= hop <= SA_N or hop % 8:
@@ -222,7 +239,7 @@ class SpectrumChain:
         dtype = x.dtype if isinstance(x, torch.Tensor) and x.dtype in forms else next(iter(forms))
         row, calls = forms[dtype]
         B = self._check_in(x, dtype, row, hop)
-        shape = (B,) + frame
+        shape = (chain.rows(out_kind, B),) + frame
         if out is None:
             out = torch.empty(shape, dtype=dt, device=self.device)
         elif tuple(out.shape) != shape or out.dtype != dt or out.device != self.device or not out.is_contiguous():
@@ -476,16 +493,30 @@ class SpectrumChain:
         return rec.view(torch.float32)[:, 0], rec[:, 1], rec.view(torch.int64)[:, 1]
 
     def traces_q15(self, x: torch.Tensor, bucket: int = 16, out: Optional[torch.Tensor] = None,
-                   hop: Optional[int] = None) -> torch.Tensor:
+                   hop: Optional[int] = None, group: Optional[int] = None) -> torch.Tensor:
         """The display trace of the integer chain's frames: [B, 16384 // bucket, 2] float32, one sa_trace_point_q15 per
         bucket of ``bucket`` consecutive bins of the full spectrum (include/specan.h, SA_Q15_TRACE_KIND).  ``[..., 0]`` is
         the peak, the largest 'mag' value of the bucket bit for bit; ``[..., 1]`` the power, the exact integer sum of
         re^2 + im^2 over the bucket rounded once to float32 (frames.trace_of_frame is the numpy mirror).  ``bucket`` is
         2, 4, 8, 16, 32 or 64 -- anything else is SA_EINVAL before any device call; the marker range plays no part.
-        ``x`` is int16 or packed uint8 as for :meth:`process_q15`, and with ``hop`` a 1-D stream as there."""
+        ``x`` is int16 or packed uint8 as for :meth:`process_q15`, and with ``hop`` a 1-D stream as there.
+
+        ``group=A`` (2, 4, ..., 128; include/specan.h, SA_Q15_TRACE_AVG_KIND) reduces groups of A consecutive frames as well:
+        [B // A, 16384 // bucket, 2] float32, record (g, j) over the bucket j of the frames gA .. gA + A - 1 -- with ``hop``
+        the frames of the stream.  ``[..., 0]`` is the largest of the A frames' peaks, bit for bit (max hold); ``[..., 1]``
+        the exact integer sum of re^2 + im^2 over bucket x A frames (at most 2^44), rounded once to float32.  It is the
+        SUM: the mean is ``power / A``, exactly.  frames.trace_of_frames is the numpy mirror.  Any other ``group`` (a
+        bool or a float included) is SA_EINVAL, a B that is no multiple of A SA_ESHAPE, both before any device call.
+        The call keeps B * (16384 // bucket) * 16 bytes of workspace in the handle, grown by the call itself and never by
+        :meth:`reserve`: before capturing such a call into a graph, make one of the same bucket and batch outside it
+        (SA_ESTATE otherwise).  ``group=None`` is the call on single frames."""
         if isinstance(bucket, bool) or not isinstance(bucket, (int, np.integer)) or int(bucket) not in _TRACE_OUT:
             raise SpecanError(abi.SA_EINVAL, f"bucket must be one of {sorted(_TRACE_OUT)}")
-        return self._process(Q15_TRACE_CHAIN, x, out, int(bucket), hop=hop)
+        if group is None:
+            return self._process(Q15_TRACE_CHAIN, x, out, int(bucket), hop=hop)
+        if isinstance(group, bool) or not isinstance(group, (int, np.integer)) or int(group) not in TRACE_GROUPS:
+            raise SpecanError(abi.SA_EINVAL, f"group must be one of {TRACE_GROUPS}")
+        return self._process(Q15_TRACE_AVG_CHAIN, x, out, (int(bucket), int(group)), hop=hop)
 
     def filter_q15(self, x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Window (+ integer IIR) only: the FFT input stream, [B,16384] int16.  ``x`` is [B,16384] int16 or the same

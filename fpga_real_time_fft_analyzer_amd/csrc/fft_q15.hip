@@ -160,22 +160,7 @@ __device__ __forceinline__ float fx_mag_sum(unsigned p)
     return rr + ii;
 }
 
-// Correctly rounded square root of s = 0 or an integer-valued float in [1, 2^31]: v_sqrt_f32 is within 1 ulp, so the
-// result is y or one of its two neighbours, told apart by the signs of the exact residuals s - y_down y and s - y_up y
-// (one FMA each).  This is the compiler's own sequence for sqrtf without its input scaling for denormals and its class
-// test for 0 and infinity, neither of which can occur: for s = 0 the lower neighbour is a NaN whose comparison fails
-// and the upper one gives a residual of 0, so the result is +0.
-__device__ __forceinline__ float fx_sqrt_rn(float s)
-{
-    const float y = __builtin_amdgcn_sqrtf(s);
-    const float dn = __builtin_bit_cast(float, __builtin_bit_cast(int, y) - 1);
-    const float up = __builtin_bit_cast(float, __builtin_bit_cast(int, y) + 1);
-    const float rd = __builtin_fmaf(-dn, y, s), ru = __builtin_fmaf(-up, y, s);
-    float z = rd <= 0.f ? dn : y;
-    z = ru > 0.f ? up : z;
-    return z;
-}
-
+// fx_sqrt_rn, the correctly rounded root: q15_dev.hpp (shared with trace_fold_q15.hip)
 __device__ __forceinline__ float fx_mag(unsigned p) { return fx_sqrt_rn(fx_mag_sum(p)); }
 
 // SA_Q15_OUT_MARKER: a part of the record -- the largest magnitude seen (-1: none yet), the lowest bin attaining it, and
@@ -299,10 +284,29 @@ __device__ __forceinline__ void fx_mark_finish(FxMark a, uint4 *scr, void *__res
 //          nearest even: the float32 nearest to the exact integer sum.
 // The template value of the epilogue arm; the bucket width itself is a run-time word (the kernel's trailing argument).
 constexpr int kFxOutTrace = SA_Q15_TRACE_KIND(0);
+// SA_Q15_TRACE_AVG_KIND(k, a): the same reduction, stopped before the root and the two conversions -- the first lane of each
+// bucket stores the bucket's FxTrace as one 16-byte partial record {s, hi, lo, 0} (hi 65536 + lo is the exact bucket power)
+// into a [B, 16384 >> k] workspace, and trace_fold_q15.hip folds A = 2^a frames of such records into one trace point.
+// The arm knows nothing of a: k alone rides in the trailing word.
+constexpr int kFxOutTraceRaw = SA_Q15_TRACE_AVG_KIND(0, 0);
 
 struct FxTrace {
     unsigned s, lo, hi;                                      // bits of max s; sums of the low / high halves of the power
 };
+
+// The store of a partial record: plain, so that the fold launch right behind finds the records in the cache hierarchy
+// (-DSA_FX_RAW_NT: the nontemporal form, for the A/B of tools/q15_trace_avg_cost.py)
+#ifdef SA_FX_RAW_NT
+#define SA_FX_RAW_STORE(v, ptr) fx_store_nt4((v), (ptr))
+__device__ __forceinline__ void fx_store_nt4(uint4 v, uint4 *p)
+{
+    typedef unsigned u4 __attribute__((ext_vector_type(4)));
+    u4 w = {v.x, v.y, v.z, v.w};
+    __builtin_nontemporal_store(w, reinterpret_cast<u4 *>(p));
+}
+#else
+#define SA_FX_RAW_STORE(v, ptr) (*(ptr) = (v))
+#endif
 
 // a <- a (+) the part of the lane that DPP control CTRL names (a lane inside the same row of 16)
 template <int CTRL>
@@ -321,8 +325,9 @@ __device__ __forceinline__ void fx_trace_dpp(FxTrace &a)
 // other quad's part, and after that the eight agree and row_mirror (lane 15 - i) reads the other eight's.  Bit 4 is one
 // ds_swizzle (lane ^ 16, as in fx_mark_swizzle).  Bit 5 (W = 64: lane 0 alone stores) takes the upper half-wave's part from
 // lane 32 through scalar registers.  All 64 lanes run every step; the first lane of each bucket stores its record.
-template <int K>
-__device__ __forceinline__ void fx_trace_point(unsigned p, int t, uint2 *__restrict__ row, int bin)
+// RAW (kFxOutTraceRaw): `row` is the frame's row of partial records, no root and no conversion.
+template <int K, bool RAW = false>
+__device__ __forceinline__ void fx_trace_point(unsigned p, int t, void *__restrict__ row, int bin)
 {
     const unsigned pw = (unsigned)fx_dot2(p, p);
     FxTrace a = {__builtin_bit_cast(unsigned, fx_mag_sum(p)), pw & 0xFFFFu, pw >> 16};
@@ -343,32 +348,37 @@ __device__ __forceinline__ void fx_trace_point(unsigned p, int t, uint2 *__restr
         a.hi += (unsigned)__builtin_amdgcn_readlane((int)a.hi, 32);
         a.s = a.s > s ? a.s : s;
     }
+    if constexpr (RAW) {
+        if ((t & ((1 << K) - 1)) == 0) SA_FX_RAW_STORE(make_uint4(a.s, a.hi, a.lo, 0u), reinterpret_cast<uint4 *>(row) + (bin >> K));
+        return;
+    }
     const float peak = fx_sqrt_rn(__builtin_bit_cast(float, a.s));
     const float power = __builtin_fmaf((float)a.hi, 65536.f, (float)a.lo);
     if ((t & ((1 << K) - 1)) == 0)
-        row[bin >> K] = make_uint2(__builtin_bit_cast(unsigned, peak), __builtin_bit_cast(unsigned, power));
+        reinterpret_cast<uint2 *>(row)[bin >> K] = make_uint2(__builtin_bit_cast(unsigned, peak), __builtin_bit_cast(unsigned, power));
 }
 
 // The thread's 16 bins q[m'] = bin t + 1024 m' into the frame's row of 16384 >> K records: one straight-line block per
 // width, so the sixteen reductions interleave and no step waits on the one before it.
-template <int K>
+template <int K, bool RAW>
 __device__ __forceinline__ void fx_trace_rows(const unsigned (&q)[16], int t, void *__restrict__ out, int f)
 {
-    uint2 *row = reinterpret_cast<uint2 *>(out) + (size_t)f * (SA_NPTS >> K);
+    void *row = reinterpret_cast<unsigned char *>(out) + (size_t)f * (SA_NPTS >> K) * (RAW ? sizeof(uint4) : sizeof(uint2));
 #pragma unroll
-    for (int m = 0; m < 16; ++m) fx_trace_point<K>(q[m], t, row, t + kFftWide * m);
+    for (int m = 0; m < 16; ++m) fx_trace_point<K, RAW>(q[m], t, row, t + kFftWide * m);
 }
 
 // k is wave-uniform (a kernel argument): one scalar branch per frame
+template <bool RAW>
 __device__ __forceinline__ void fx_trace_frame(const unsigned (&q)[16], int k, int t, void *__restrict__ out, int f)
 {
     switch (k) {
-        case 1: fx_trace_rows<1>(q, t, out, f); break;
-        case 2: fx_trace_rows<2>(q, t, out, f); break;
-        case 3: fx_trace_rows<3>(q, t, out, f); break;
-        case 4: fx_trace_rows<4>(q, t, out, f); break;
-        case 5: fx_trace_rows<5>(q, t, out, f); break;
-        case 6: fx_trace_rows<6>(q, t, out, f); break;
+        case 1: fx_trace_rows<1, RAW>(q, t, out, f); break;
+        case 2: fx_trace_rows<2, RAW>(q, t, out, f); break;
+        case 3: fx_trace_rows<3, RAW>(q, t, out, f); break;
+        case 4: fx_trace_rows<4, RAW>(q, t, out, f); break;
+        case 5: fx_trace_rows<5, RAW>(q, t, out, f); break;
+        case 6: fx_trace_rows<6, RAW>(q, t, out, f); break;
         default: break;                                      // the host admits 1..6 only
     }
 }
@@ -469,7 +479,7 @@ hipError_t launch_fft_q15(K k, const InT *in_time, void *out, int batch, const S
     const int lds = kFftLds + (OUT == SA_Q15_OUT_MARKER ? kFxMarkParts * (int)sizeof(uint4) : 0);
     const hipError_t e = sa_set_dyn_lds_once(reinterpret_cast<const void *>(k), lds);
     if (e != hipSuccess) return e;
-    const unsigned word = OUT == kFxOutTrace ? (unsigned)log2w : (unsigned)t.marker_lo | (unsigned)t.marker_hi << 16;
+    const unsigned word = OUT == kFxOutTrace || OUT == kFxOutTraceRaw ? (unsigned)log2w : (unsigned)t.marker_lo | (unsigned)t.marker_hi << 16;
     hipExtLaunchKernelGGL(k, grid, block, lds, stream, ev.start, ev.stop, 0, in_time, out, batch, p, t.rom, t.tw, t.twrec, word,
                           hop...);
     return hipGetLastError();
@@ -501,6 +511,9 @@ hipError_t launch_fft_q15_kind(const void *in_time, SaInKind in_kind, int hop, v
     if (batch <= 0) return hipSuccess;
     if (out_kind >= SA_Q15_TRACE_KIND(SA_Q15_TRACE_LOG2W_MIN) && out_kind <= SA_Q15_TRACE_KIND(SA_Q15_TRACE_LOG2W_MAX))
         return launch_fft_q15<kFxOutTrace>(in_time, in_kind, hop, out, batch, apply_window, p, t, out_kind - kFxOutTrace, stream, ev);
+    // the grouped kind: `out` is the workspace of partial records [B, 16384 >> k]; the group size is the fold launch's alone
+    if (SA_Q15_IS_TRACE_AVG_KIND(out_kind))
+        return launch_fft_q15<kFxOutTraceRaw>(in_time, in_kind, hop, out, batch, apply_window, p, t, SA_Q15_TRACE_AVG_LOG2W(out_kind), stream, ev);
     switch (out_kind) {
         case SA_Q15_OUT_IQ: return launch_fft_q15<SA_Q15_OUT_IQ>(in_time, in_kind, hop, out, batch, apply_window, p, t, 0, stream, ev);
         case SA_Q15_OUT_MAG: return launch_fft_q15<SA_Q15_OUT_MAG>(in_time, in_kind, hop, out, batch, apply_window, p, t, 0, stream, ev);

@@ -131,7 +131,8 @@ __global__ __launch_bounds__(kFftWide, 8) void SA_FX_KERNEL(const SA_FX_IN *__re
     // SA_Q15_OUT_MARKER: no spectrum store; the thread keeps the 16 sums re^2 + im^2 of its bins and roots their largest.
     // kFxOutTrace: no spectrum store either; the thread keeps its 16 bins, then per m' the wave reduces its 64 bins to
     // 64 / W records (W = 1 << mrange) and the first lane of each bucket stores one: row [16384 / W] of the frame
-    // (fx_trace_frame).
+    // (fx_trace_frame).  kFxOutTraceRaw: the same reduction, the bucket's partial record {s, hi, lo, 0} stored instead
+    // (row [16384 / W] of 16-byte records in the workspace `out`).
     unsigned *o32 = reinterpret_cast<unsigned *>(reinterpret_cast<int16_t *>(out) + (size_t)f * SA_NPTS * 2);
     const int mlo = (int)(mrange & 0xFFFFu), mhi = (int)(mrange >> 16);
     float ms[16];
@@ -158,5 +159,6 @@ __global__ __launch_bounds__(kFftWide, 8) void SA_FX_KERNEL(const SA_FX_IN *__re
     if constexpr (OUT == SA_Q15_OUT_MARKER) {
         fx_mark_finish(fx_mark_thread(ms, t, mpow), reinterpret_cast<uint4 *>(smem_q + kFftLds), out, f, t, wave);
     }
-    if constexpr (OUT == kFxOutTrace) fx_trace_frame(tq, (int)mrange, t, out, f);
+    if constexpr (OUT == kFxOutTrace) fx_trace_frame<false>(tq, (int)mrange, t, out, f);
+    if constexpr (OUT == kFxOutTraceRaw) fx_trace_frame<true>(tq, (int)mrange, t, out, f);
 }

@@ -1,5 +1,6 @@
 // q15_dev.hpp -- device helpers shared by the integer cascades (cascade_q15.hip) and the fixed-point FFT (fft_q15.hip):
-// the Q15 window of one sample and the packed int16 pair.
+// the Q15 window of one sample and the packed int16 pair -- and, shared by the FFT's epilogues and the trace fold
+// (trace_fold_q15.hip), the correctly rounded square root.
 #pragma once
 #include "sa_common.hpp"
 
@@ -33,5 +34,21 @@ __device__ __forceinline__ unsigned sat_pack2(int lo, int hi)
 
 __device__ __forceinline__ int lo16(unsigned v) { return (int)(short)(v & 0xFFFFu); }
 __device__ __forceinline__ int hi16(unsigned v) { return (int)v >> 16; }
+
+// Correctly rounded square root of s = 0 or an integer-valued float in [1, 2^31]: v_sqrt_f32 is within 1 ulp, so the
+// result is y or one of its two neighbours, told apart by the signs of the exact residuals s - y_down y and s - y_up y
+// (one FMA each).  This is the compiler's own sequence for sqrtf without its input scaling for denormals and its class
+// test for 0 and infinity, neither of which can occur: for s = 0 the lower neighbour is a NaN whose comparison fails
+// and the upper one gives a residual of 0, so the result is +0.
+__device__ __forceinline__ float fx_sqrt_rn(float s)
+{
+    const float y = __builtin_amdgcn_sqrtf(s);
+    const float dn = __builtin_bit_cast(float, __builtin_bit_cast(int, y) - 1);
+    const float up = __builtin_bit_cast(float, __builtin_bit_cast(int, y) + 1);
+    const float rd = __builtin_fmaf(-dn, y, s), ru = __builtin_fmaf(-up, y, s);
+    float z = rd <= 0.f ? dn : y;
+    z = ru > 0.f ? up : z;
+    return z;
+}
 
 }  // namespace

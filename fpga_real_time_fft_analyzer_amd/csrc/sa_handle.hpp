@@ -51,11 +51,13 @@ struct sa_handle {
         int frames;
         size_t elem;
     };
-    enum { kWorkQ15, kWorkF64, kWorkKinds };
+    enum { kWorkQ15, kWorkF64, kWorkTraceRaw, kWorkKinds };
     // Launch slot i (slot 0 = ordered mode; overlap mode uses slots 0..depth-1): its workspaces -- the Q15 cascade's
-    // int16 output, and in float64-state mode the float32 y [B,16384] -- and, in overlap mode, its internal stream
+    // int16 output, in float64-state mode the float32 y [B,16384], and the partial records of SA_Q15_TRACE_AVG_KIND (bytes,
+    // counted in units of 16384: grown by the calls of that kind alone, never by sa_reserve or a change of mode) -- and, in
+    // overlap mode, its internal stream
     struct Slot {
-        Workspace work[kWorkKinds] = {{nullptr, 0, sizeof(int16_t)}, {nullptr, 0, sizeof(float)}};
+        Workspace work[kWorkKinds] = {{nullptr, 0, sizeof(int16_t)}, {nullptr, 0, sizeof(float)}, {nullptr, 0, 1}};
         hipStream_t stream = nullptr;
         hipEvent_t fork = nullptr, done = nullptr;
         bool used = false;                 // `done` has been recorded
@@ -175,7 +177,7 @@ inline int fail_at(sa_handle *h, int code, const char *fn, const char *what)
 int control_allowed(sa_handle *h);
 int upload(sa_handle *h, void *dst, const void *src, size_t bytes);
 int grow_slots(sa_handle *h, int n, int frames, bool geometric, bool f64_only = false);
-int begin_call(sa_handle *h, hipStream_t user, int work, int frames, CallCtx *c);
+int begin_call(sa_handle *h, hipStream_t user, int work, int frames, CallCtx *c, int work2 = -1, int frames2 = 0);
 int end_call(sa_handle *h, const CallCtx &c);
 
 #pragma GCC visibility pop

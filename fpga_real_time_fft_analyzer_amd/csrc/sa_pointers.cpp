@@ -20,7 +20,7 @@ bool in_frame_bytes(int in_form, uint64_t *bytes)
     }
 }
 
-// bytes of one frame of output and the alignment of `out`, by chain and kind: the table of kinds of include/specan.h
+// bytes of one row of output (one frame's, or one group's of sa_frames_per_row frames) and the alignment of `out`, by chain and kind: the table of kinds of include/specan.h
 bool out_frame_bytes(SaChain chain, int out_kind, uint64_t *bytes, unsigned *align)
 {
     *align = 16;
@@ -39,6 +39,10 @@ bool out_frame_bytes(SaChain chain, int out_kind, uint64_t *bytes, unsigned *ali
         *bytes = (kN >> (out_kind & 0xF)) * sizeof(sa_trace_point_q15);
         return true;
     }
+    if (SA_Q15_IS_TRACE_AVG_KIND(out_kind)) {                                         // one row per A frames (sa_frames_per_row)
+        *bytes = (kN >> SA_Q15_TRACE_AVG_LOG2W(out_kind)) * sizeof(sa_trace_point_q15);
+        return true;
+    }
     switch (out_kind) {
         case SA_Q15_OUT_IQ:
         case SA_Q15_OUT_MAG: *bytes = kN * 4; return true;                            // int16 [B,16384,2], float [B,16384]
@@ -49,6 +53,11 @@ bool out_frame_bytes(SaChain chain, int out_kind, uint64_t *bytes, unsigned *ali
 
 }  // namespace
 
+int sa_frames_per_row(SaChain chain, int out_kind)
+{
+    return chain == SaChain::Q15 && SA_Q15_IS_TRACE_AVG_KIND(out_kind) ? 1 << SA_Q15_TRACE_AVG_LOG2A(out_kind) : 1;
+}
+
 bool sa_call_span(SaChain chain, int in_form, int out_kind, int hop, int batch, SaCallSpan *s)
 {
     uint64_t in_frame = 0, out_frame = 0;
@@ -58,7 +67,7 @@ bool sa_call_span(SaChain chain, int in_form, int out_kind, int hop, int batch, 
     if (hop != 0 && (chain != SaChain::Q15 || hop < 8 || hop > SA_N || hop % 8 != 0)) return false;
     const uint64_t B = (uint64_t)batch;
     s->in_align = 16;
-    s->out_bytes = B * out_frame;
+    s->out_bytes = B / (uint64_t)sa_frames_per_row(chain, out_kind) * out_frame;
     if (hop == 0) {
         s->in_bytes = B * in_frame;
     } else {                                   // one stream: the last frame ends with it
@@ -118,6 +127,7 @@ extern "C" int sa_debug_check_pointers(int entry, int kind_word, uint64_t in_add
     SaCallSpan s;
     if (!sa_call_span(e.chain, e.in_form, kind, hop, batch == 0 ? 1 : batch, &s)) return SA_EINVAL;    // a kind is checked
     if (batch == 0) return SA_OK;                                                                    // before the pointers
+    if (batch % sa_frames_per_row(e.chain, kind)) return SA_ESHAPE;                                  // and so is the group
     if (in_addr == 0 || out_addr == 0) return SA_EINVAL;
     return sa_pointer_faults(s, in_addr, out_addr) ? SA_EINVAL : SA_OK;
 }

@@ -10,7 +10,7 @@
 #pragma GCC visibility push(hidden)
 
 // which family of outputs the entry point has: the float chain (SA_OUT_*), the integer chain with its FFT (SA_Q15_OUT_*,
-// SA_Q15_TRACE_KIND) or the integer chain without it (sa_filter_q15*: one output, no kind)
+// SA_Q15_TRACE_KIND, SA_Q15_TRACE_AVG_KIND) or the integer chain without it (sa_filter_q15*: one output, no kind)
 enum class SaChain { Float, Q15, Q15Filter };
 
 // what `in` points to; the values of SaInKind (sa_common.hpp), which this unit does not include: it pulls in the HIP runtime
@@ -25,6 +25,11 @@ struct SaCallSpan {
 // the hop in samples (8..16384) of a stream, which holds (batch - 1) * hop + 16384 samples.  False for an input form, a
 // kind or a hop the chain does not have.
 bool sa_call_span(SaChain chain, int in_form, int out_kind, int hop, int batch, SaCallSpan *s);
+
+// The number of frames one row of `out` stands for: A = 2^a for SA_Q15_TRACE_AVG_KIND(k, a) of the Q15 chain, 1 for every
+// other kind there is (and for one there is not: sa_call_span is what refuses a kind).  A call's batch must be a multiple
+// of it (SA_ESHAPE), and sa_call_span counts batch / A rows of output.
+int sa_frames_per_row(SaChain chain, int out_kind);
 
 // What is wrong with the pair of addresses, as a set: every fault is reported, the caller chooses which one to name
 enum : unsigned { kSaPtrInAlign = 1u, kSaPtrOutAlign = 2u, kSaPtrOverlap = 4u };

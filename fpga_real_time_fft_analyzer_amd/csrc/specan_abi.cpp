@@ -422,6 +422,8 @@ static SaQ15Params q15_params(const sa_handle *h)
 // The argument checks of process_q15 and process_float, made before anything else; callers of the ABI see their order.
 // The output kinds of both chains run from 0 to `marker`, the marker records (`marker_name` in the message).
 // `trace`: the entry point also takes the SA_Q15_TRACE_KIND(k) family (the Q15 FFT calls; never the float chain).
+// `grouped`: it also takes SA_Q15_TRACE_AVG_KIND(k, a) -- the two entry points with a kind word alone; a batch that is no
+// multiple of A = 2^a is SA_ESHAPE, after the kind and before the pointers.
 // `scale_finite`: what process_float found of its scale, which is refused between the kind and the empty batch (process_q15
 // has no scale: true).  An empty batch returns SA_OK here, and the caller returns it at once.
 // `hop`: null, or where the entry point's word is a SA_Q15_HOP_KIND: the word is taken apart before anything else, *hop is
@@ -432,7 +434,7 @@ static SaQ15Params q15_params(const sa_handle *h)
 // keep their messages; all of this before any call state exists.
 static int check_process_args(sa_handle *h, const char *fn, const void *in, SaInKind kind, const void *out, int batch,
                               int out_kind, SaChain chain, int marker, const char *marker_name, bool trace, bool scale_finite,
-                              int *hop = nullptr)
+                              int *hop = nullptr, bool grouped = false)
 {
     static_assert((int)SaInKind::F32 == kSaInF32 && (int)SaInKind::I16 == kSaInI16 && (int)SaInKind::P12 == kSaInP12,
                   "sa_pointers.hpp numbers the input forms as SaInKind does");
@@ -449,16 +451,20 @@ static int check_process_args(sa_handle *h, const char *fn, const void *in, SaIn
     if (bad_word) return fail_at(h, SA_EINVAL, fn, "bad out_kind: hop field above 2048 or bits 20..30 set");
     const bool is_trace = trace && out_kind >= SA_Q15_TRACE_KIND(SA_Q15_TRACE_LOG2W_MIN) &&
                           out_kind <= SA_Q15_TRACE_KIND(SA_Q15_TRACE_LOG2W_MAX);
-    if (!is_trace && (out_kind < 0 || out_kind > marker)) return fail_at(h, SA_EINVAL, fn, "bad out_kind");
+    const bool is_avg = grouped && out_kind >= 0 && SA_Q15_IS_TRACE_AVG_KIND(out_kind);
+    if (!is_trace && !is_avg && (out_kind < 0 || out_kind > marker)) return fail_at(h, SA_EINVAL, fn, "bad out_kind");
     if (!scale_finite) return fail_at(h, SA_EINVAL, fn, "scale is not finite");
     if (batch == 0) return SA_OK;
+    if (is_avg && batch % sa_frames_per_row(chain, out_kind))
+        return fail_at(h, SA_ESHAPE, fn, "SA_Q15_TRACE_AVG_KIND: batch must be a multiple of the group size A");
     if (!in || !out) return fail_at(h, SA_EINVAL, fn, "NULL tensor");
     SaCallSpan span;
     if (!sa_call_span(chain, (int)kind, out_kind, 8 * field, batch, &span)) return fail_at(h, SA_EINVAL, fn, "bad out_kind");
     const unsigned faults = sa_pointer_faults(span, (uint64_t)(uintptr_t)in, (uint64_t)(uintptr_t)out);
     char msg[96];
-    if ((out_kind == marker || is_trace) && (faults & kSaPtrOutAlign)) {
-        std::snprintf(msg, sizeof msg, "%s output must be 16-byte aligned", is_trace ? "SA_Q15_TRACE_KIND" : marker_name);
+    if ((out_kind == marker || is_trace || is_avg) && (faults & kSaPtrOutAlign)) {
+        std::snprintf(msg, sizeof msg, "%s output must be 16-byte aligned",
+                      is_avg ? "SA_Q15_TRACE_AVG_KIND" : is_trace ? "SA_Q15_TRACE_KIND" : marker_name);
         return fail_at(h, SA_EINVAL, fn, msg);
     }
     if (faults & kSaPtrInAlign)       // the stage-ins and tile loads issue 16-byte requests; every frame is then aligned (int16
@@ -480,7 +486,8 @@ static int check_process_args(sa_handle *h, const char *fn, const void *in, SaIn
 }
 
 // sa_filter_q15 (`fft` false: window + integer cascade into `out`, out_kind unused) and sa_process_q15 / sa_process_q15_out
-// (`out` per out_kind, SA_Q15_OUT_* or SA_Q15_TRACE_KIND(k): the FFT launch's epilogue makes it), on int16 samples or, the
+// (`out` per out_kind, SA_Q15_OUT_* or SA_Q15_TRACE_KIND(k): the FFT launch's epilogue makes it; SA_Q15_TRACE_AVG_KIND(k, a):
+// the epilogue's partial records and a fold launch behind it), on int16 samples or, the
 // _p12 entry points, on packed 12-bit samples (`kind`: I16 or P12); `fn` names the entry point.  `hop_word`: out_kind is a
 // SA_Q15_HOP_KIND (sa_process_q15_out, sa_process_q15_p12); with a hop, `in` is one stream and whichever launch reads the
 // samples -- the cascade, or the FFT in mode 0xB1 -- is its _hop sibling.  Everything else is the frame call.
@@ -489,19 +496,33 @@ static int process_q15(sa_handle *h, const char *fn, const void *in, SaInKind ki
 {
     int hop = 0;
     { const int rc = check_process_args(h, fn, in, kind, out, batch, out_kind, fft ? SaChain::Q15 : SaChain::Q15Filter,
-                                        SA_Q15_OUT_MARKER, "SA_Q15_OUT_MARKER", fft, true, hop_word ? &hop : nullptr);
+                                        SA_Q15_OUT_MARKER, "SA_Q15_OUT_MARKER", fft, true, hop_word ? &hop : nullptr, hop_word);
       if (rc != SA_OK || batch == 0) return rc; }
     if (hop_word) out_kind &= 0xFF;
     SA_HIP(h, hipSetDevice(h->device));
     const SaQ15Params p = q15_params(h);
     const bool staged = fft && p.filter != SA_FILTER_NONE;      // cascade into the slot's workspace, then the FFT
+    // SA_Q15_TRACE_AVG_KIND(k, a): the FFT launch writes partial records [B, 16384 >> k] into a workspace of its own and one
+    // more launch folds them into `out`.  B (16384 >> k) records of kSaTraceRawBytes are ceil(16 B / W) "frames" of the
+    // workspace's one-byte elements.  Grown here, on demand, with the cascade's workspace and before the first launch;
+    // never by sa_reserve, which does not know W.
+    const bool folded = hop_word && SA_Q15_IS_TRACE_AVG_KIND(out_kind);
+    const int log2w = SA_Q15_TRACE_AVG_LOG2W(out_kind), log2a = SA_Q15_TRACE_AVG_LOG2A(out_kind);
+    const long long raw_frames = folded ? ((long long)batch * kSaTraceRawBytes + (1 << log2w) - 1) >> log2w : 0;
+    if (raw_frames > 0x7FFFFFFF) return fail_at(h, SA_ESHAPE, fn, "SA_Q15_TRACE_AVG_KIND: batch too large for the workspace");
     CallCtx c;
-    { const int rc = begin_call(h, (hipStream_t)stream, staged ? sa_handle::kWorkQ15 : -1, batch, &c); if (rc != SA_OK) return rc; }
+    { const int rc = begin_call(h, (hipStream_t)stream, staged ? sa_handle::kWorkQ15 : -1, batch, &c,
+                                folded ? sa_handle::kWorkTraceRaw : -1, (int)raw_frames);
+      if (rc != SA_OK) return rc; }
     const SaQ15Tables t = {h->d_rom, h->d_twq, h->d_twrec, h->marker_lo, h->marker_hi};
+    // what the FFT launch writes, and the event its completion is bound to: the fold launch, where there is one, is the call's last
+    void *fft_out = folded ? h->slot[c.slot].work[sa_handle::kWorkTraceRaw].ptr : out;
+    hipEvent_t fft_stop = folded ? nullptr : c.stop;
     if (!staged) {
-        SA_HIP(h, hop   ? sa_launch_fft_q15_hop(in, kind, hop, out, batch, out_kind, p, t, c.stream, {c.start, c.stop})
-                  : fft ? sa_launch_fft_q15(in, kind, out, batch, out_kind, true, p, t, c.stream, {c.start, c.stop})
+        SA_HIP(h, hop   ? sa_launch_fft_q15_hop(in, kind, hop, fft_out, batch, out_kind, p, t, c.stream, {c.start, fft_stop})
+                  : fft ? sa_launch_fft_q15(in, kind, fft_out, batch, out_kind, true, p, t, c.stream, {c.start, fft_stop})
                         : sa_launch_filter_q15(in, kind, (int16_t *)out, batch, p, t, c.stream, {c.start, c.stop}));
+        if (folded) SA_HIP(h, sa_launch_trace_fold_q15(fft_out, out, batch, log2w, log2a, c.stream, {nullptr, c.stop}));
         return end_call(h, c);
     }
     // The WIDE cascade does not gain from overlapped launches (tools/q15_overlap_modes.py, profiles/r4_q15_helper_waves.txt):
@@ -516,7 +537,8 @@ static int process_q15(sa_handle *h, const char *fn, const void *in, SaInKind ki
     // the packed form is read by the first launch alone: the workspace holds int16 samples whatever came in
     SA_HIP(h, hop ? sa_launch_filter_q15_hop(in, kind, hop, ws, batch, p, t, c.stream, {c.start, nullptr})
                   : sa_launch_filter_q15(in, kind, ws, batch, p, t, c.stream, {c.start, nullptr}));
-    SA_HIP(h, sa_launch_fft_q15(ws, SaInKind::I16, out, batch, out_kind, false, p, t, c.stream, {nullptr, c.stop}));
+    SA_HIP(h, sa_launch_fft_q15(ws, SaInKind::I16, fft_out, batch, out_kind, false, p, t, c.stream, {nullptr, fft_stop}));
+    if (folded) SA_HIP(h, sa_launch_trace_fold_q15(fft_out, out, batch, log2w, log2a, c.stream, {nullptr, c.stop}));
     return end_call(h, c);
 }
 

@@ -58,6 +58,23 @@ def trace_of_frame(frame_bytes: bytes, bucket: int):
     return peak, exact.astype(np.float32), exact
 
 
+TRACE_GROUPS = (2, 4, 8, 16, 32, 64, 128)
+
+
+def trace_of_frames(frames_bytes, bucket: int):
+    """A group of A = 2, 4, ..., 128 consecutive frames reduced to P = 16384 // bucket display points, point j over the bins
+    [j bucket, (j + 1) bucket) of all A frames: ``(peak float32 [P], power float32 [P], exact int64 [P])`` -- the largest of
+    the frames' trace_of_frame peaks (max hold), the exact integer sum of re^2 + im^2 over bucket x A bins (at most 2^44)
+    rounded once to float32, and that sum itself.  The power is the sum, not the mean: the mean is power / A, exactly.  The
+    host mirror of one group's sa_trace_point_q15 records (include/specan.h, SA_Q15_TRACE_AVG_KIND)."""
+    frames_bytes = list(frames_bytes)
+    if len(frames_bytes) not in TRACE_GROUPS:
+        raise ValueError(f"a group is one of {TRACE_GROUPS} frames")
+    parts = [trace_of_frame(f, bucket) for f in frames_bytes]
+    exact = np.sum([e for _, _, e in parts], axis=0, dtype=np.int64)
+    return np.max([p for p, _, _ in parts], axis=0), exact.astype(np.float32), exact
+
+
 def decode_iq_components(frame_bytes: bytes):
     """Same result as gui.py:262-270: (re, im) as float32 arrays."""
     re, im = _iq(frame_bytes)

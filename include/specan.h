@@ -23,7 +23,7 @@
  *       alignment   `in` is 16-byte aligned: float32, int16, packed and hop streams alike (the rules stated below for
  *                   packed input and for sample streams are instances of this one).  `out` is 16-byte aligned for
  *                   SA_OUT_MAG_FULL, SA_OUT_TIME, SA_OUT_MARKER, SA_Q15_OUT_IQ, SA_Q15_OUT_MAG, SA_Q15_OUT_MARKER, every
- *                   SA_Q15_TRACE_KIND and the output of sa_filter_q15*.  For the two half layouts `out` is aligned to its
+ *                   SA_Q15_TRACE_KIND, every SA_Q15_TRACE_AVG_KIND and the output of sa_filter_q15*.  For the two half layouts `out` is aligned to its
  *                   element: 4 bytes for SA_OUT_MAG_HALF, 8 bytes for SA_OUT_SPEC_HALF -- their rows are 32 772 and 65 544
  *                   bytes long, so every row slice out[a : a + B] of such a tensor stays valid.  Anything else is SA_EINVAL;
  *                   the message names the entry point and which pointer is at fault.
@@ -32,7 +32,8 @@
  *                   in_bytes is B * 65536 for float32, B * 32768 for int16 and B * 24576 for packed input; with a hop H it
  *                   is ((B - 1) * H + 16384) * 2 for int16 and three quarters of that for packed.  out_bytes follows the
  *                   tables of output kinds below (B rows of 65536, 32772, 65544, 65536, 16 bytes for SA_OUT_*; 65536,
- *                   65536, 16 for SA_Q15_OUT_*; 131072 >> k for SA_Q15_TRACE_KIND(k); 32768 for sa_filter_q15*).  Buffers
+ *                   65536, 16 for SA_Q15_OUT_*; 131072 >> k for SA_Q15_TRACE_KIND(k); 32768 for sa_filter_q15*;
+ *                   B / A rows of 131072 >> k for SA_Q15_TRACE_AVG_KIND(k, a), A = 2^a).  Buffers
  *                   that merely touch (out == in + in_bytes, or the reverse) are accepted.
  *       a refusal   launches nothing and changes no call state: launch slot, overlap counter, profiling ring, the stream
  *                   the handle remembers and workspace growth all stay as they were, and the next call on the handle
@@ -192,6 +193,48 @@ typedef struct sa_trace_point_q15 {
     float peak_mag;       /* max over the bucket of the SA_Q15_OUT_MAG value */
     float power;          /* the exact sum over the bucket of re[k]^2 + im[k]^2, rounded once to float32 */
 } sa_trace_point_q15;     /* 8 bytes; one store per bucket */
+
+/* A fifth family of output kinds of sa_process_q15_out() and sa_process_q15_p12(): the display trace reduced over groups of
+ * A = 2^a consecutive frames as well as over buckets of W = 2^k bins -- max hold and summed power across sweeps, made before
+ * the data leaves the device (build extension; ABI version 4, added compatibly: no new function).
+ *     SA_Q15_TRACE_AVG_KIND(log2w, log2a) = 0x80 | (log2a) << 3 | (log2w)
+ *         log2w = 1..6  (W = 2..64 bins, as SA_Q15_TRACE_KIND)
+ *         log2a = 1..7  (A = 2..128 frames)
+ * Values run from 0x89 to 0xBE.  The kind sits in the low byte of the kind word, so it combines with SA_Q15_HOP_KIND as the
+ * trace kinds do.  One record covers W bins x A frames: 512 bytes per input frame at W = 16, A = 16, against 8 KiB.
+ *   - `batch` must be a multiple of A, SA_ESHAPE otherwise: checked after the kind and before the pointers, with nothing
+ *     launched and no call state.  batch == 0 is SA_OK.
+ *   - `out` is sa_trace_point_q15 [B / A, P], P = 16384 / W, 16-byte aligned; the call writes (B / A) * P * 8 bytes, and the
+ *     pointer contract is decided on that count.
+ *   - record (g, j) covers the bins [jW, (j+1)W) of the frames gA .. gA + A - 1; with a hop these are the frames of the
+ *     stream as SA_Q15_HOP_KIND numbers them.
+ *   - peak_mag is the maximum over the A frames of the SA_Q15_TRACE_KIND(log2w) peak of the same bucket, bit for bit: the
+ *     max-hold detector.  The correctly rounded root is monotone, so it is the root of the largest s of the W x A bins.
+ *   - power is the float32 nearest (ties to even) to the EXACT integer sum of re^2 + im^2 over the W x A bins (at most
+ *     128 x 64 x 2^31 = 2^44): one rounding of an exact sum.  It is the SUM, not the mean: A is a power of two, so the mean
+ *     is power / A exactly (short of underflow, which an integer sum cannot reach).
+ *   - a group of all-zero frames gives (+0.0f, +0.0f) in every point; the marker range plays no part.
+ *   - SA_EINVAL: log2a = 0 (0x81..0x86), log2w = 0 or 7, any word with bit 6 set, and any of these words on a float
+ *     entry point.  Every value refused before stays refused.
+ *   - everything said of sa_process_q15_out holds: all four filter modes, both window modes, custom ROMs, int16 and packed
+ *     input, hop streams, every overlap depth, and launch timing (one device time per call, from the call's first launch to
+ *     its last: the FFT launch leaves one 16-byte partial record per bucket and frame in a workspace of the handle, and a
+ *     second launch folds each group of A of them).
+ *   - capture into a graph has one difference: that workspace, B * P * 16 bytes per launch slot, is grown on demand only
+ *     (sa_reserve(max_batch) does not know W and allocates nothing for a kind the handle may never use).  A captured call
+ *     whose workspace is too small is SA_ESTATE with nothing launched: make one call of that kind and size outside the
+ *     capture first.  Once grown, the call captures and replays like any other.
+ * Known answers: SA_Q15_TRACE_AVG_KIND(1,1) = 0x89; (4,3) = 0x9C; (6,7) = 0xBE;
+ * SA_Q15_HOP_KIND(SA_Q15_TRACE_AVG_KIND(4,3), 4096) = 0x2009C. */
+#define SA_Q15_TRACE_AVG_KIND(log2w, log2a) (0x80 | (log2a) << 3 | (log2w))
+#define SA_Q15_TRACE_LOG2A_MIN 1
+#define SA_Q15_TRACE_LOG2A_MAX 7
+#define SA_Q15_TRACE_AVG_LOG2W(kind) ((kind) & 7)
+#define SA_Q15_TRACE_AVG_LOG2A(kind) ((kind) >> 3 & 7)
+/* non-zero iff `kind`, the low byte of a kind word, is a SA_Q15_TRACE_AVG_KIND with both fields in their ranges */
+#define SA_Q15_IS_TRACE_AVG_KIND(kind)                                                                       \
+    (((kind) & ~0x3F) == 0x80 && SA_Q15_TRACE_AVG_LOG2W(kind) >= SA_Q15_TRACE_LOG2W_MIN &&                    \
+     SA_Q15_TRACE_AVG_LOG2W(kind) <= SA_Q15_TRACE_LOG2W_MAX && SA_Q15_TRACE_AVG_LOG2A(kind) >= SA_Q15_TRACE_LOG2A_MIN)
 
 /* precision of the float path's window and cascade (sa_set_precision) */
 #define SA_PRECISION_F32       0   /* default: float32 arithmetic throughout, one fused kernel per call */
@@ -401,7 +444,8 @@ int sa_filter_q15_p12(sa_handle *h, const uint8_t *in /* [B,24576] device */, in
  * the kernels that read samples address it there.  The hop travels inside the out_kind word of sa_process_q15_out() and
  * sa_process_q15_p12(), as the trace width does: no control state, nothing a captured graph could freeze.
  *     SA_Q15_HOP_KIND(kind, hop) = kind | (hop / 8) << 8
- *   bits 0..7    the kind as above: SA_Q15_OUT_IQ, _MAG, _MARKER or SA_Q15_TRACE_KIND(k) = 17..22
+ *   bits 0..7    the kind as above: SA_Q15_OUT_IQ, _MAG, _MARKER, SA_Q15_TRACE_KIND(k) = 17..22 or
+ *                SA_Q15_TRACE_AVG_KIND(k, a) = 0x89..0xBE
  *   bits 8..19   the hop field h = hop / 8
  *   bits 20..30  must be zero
  *   - h = 0 is every call described so far: `in` is [B,16384] (packed: [B,24576]), frames back to back.  Every out_kind that
@@ -443,7 +487,8 @@ int sa_unpack_samples_p12(const uint8_t *packed, size_t n, int16_t *samples);
  * (SA_ENTRY_*), `kind_word` is its out_kind argument, a SA_Q15_HOP_KIND word where the entry point takes one (ignored by the
  * entry points that have no out_kind).  SA_OK where the call would pass its pointer checks; SA_EINVAL for a misaligned
  * `in` or `out`, overlapping byte ranges, a zero address, an unknown entry or a kind word the entry point refuses; SA_ESHAPE
- * for a negative batch; batch == 0 is SA_OK for any addresses.  The entry points themselves ask the same code. */
+ * for a negative batch and for a batch that is no multiple of the A of a SA_Q15_TRACE_AVG_KIND (after the kind, before the
+ * addresses); batch == 0 is SA_OK for any addresses.  The entry points themselves ask the same code. */
 #define SA_ENTRY_PROCESS_F32      0
 #define SA_ENTRY_PROCESS_F32_I16  1
 #define SA_ENTRY_PROCESS_F32_P12  2

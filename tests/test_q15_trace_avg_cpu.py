@@ -1,0 +1,241 @@
+"""CPU: the grouped trace kinds of the integer chain (include/specan.h, SA_Q15_TRACE_AVG_KIND(k, a): one {peak_mag, power}
+record per bucket of W = 2^k bins and group of A = 2^a consecutive frames) as far as no GPU is needed: the header's known
+answers, the pointer contract through sa_debug_check_pointers with made-up addresses (after tests/test_pointer_contract_cpu.py:
+every expected answer is worked out here from the words of the header), the wrapper's tables, the numpy mirror
+frames.trace_of_frames against a direct evaluation, and the stand-alone program that runs the kind's one rounding
+(csrc/q15_round.hpp) under the host sanitizers."""
+import os
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+from conftest import N, ROOT
+
+SA_OK, SA_EINVAL, SA_ESHAPE = 0, -1, -2
+KA = ((1, 1), (4, 3), (6, 7))
+HOPS = (0, 8, 4104, 16384)
+ENTRIES = {4: "i16", 5: "p12"}                       # sa_process_q15_out, sa_process_q15_p12
+IN_FRAME = {"i16": 32768, "p12": 24576}
+SAMPLE_BYTES = {"i16": (2, 1), "p12": (3, 2)}
+BASE = (1 << 47) - (1 << 36)
+FAR = BASE + (1 << 40)
+BAD_WORDS = (0x80, 0x81, 0x86, 0x88, 0x8F, 0xC9)
+
+
+def kind(k, a):
+    return 0x80 | a << 3 | k
+
+
+def word(k, a, hop):
+    return kind(k, a) | (hop // 8) << 8
+
+
+def in_bytes(form, hop, B):
+    if hop == 0:
+        return B * IN_FRAME[form]
+    num, den = SAMPLE_BYTES[form]
+    return ((B - 1) * hop + N) * num // den
+
+
+def out_bytes(k, a, B):
+    return (B >> a) * (N >> k) * 8
+
+
+@pytest.fixture(scope="module")
+def check(hip_lib_built):
+    return hip_lib_built.sa_debug_check_pointers
+
+
+def test_known_answers_of_the_header():
+    from fpga_real_time_fft_analyzer_amd import abi
+    assert abi.SA_Q15_TRACE_AVG_KIND(1, 1) == 0x89
+    assert abi.SA_Q15_TRACE_AVG_KIND(4, 3) == 0x9C
+    assert abi.SA_Q15_TRACE_AVG_KIND(6, 7) == 0xBE
+    assert abi.SA_Q15_HOP_KIND(abi.SA_Q15_TRACE_AVG_KIND(4, 3), 4096) == 0x2009C
+    assert (abi.SA_Q15_TRACE_LOG2A_MIN, abi.SA_Q15_TRACE_LOG2A_MAX) == (1, 7)
+    kinds = {abi.SA_Q15_TRACE_AVG_KIND(k, a) for k in range(1, 7) for a in range(1, 8)}
+    assert len(kinds) == 42 and min(kinds) == 0x89 and max(kinds) == 0xBE
+    assert not kinds & ({0, 1, 2} | {abi.SA_Q15_TRACE_KIND(k) for k in range(8)})
+    txt = open(os.path.join(ROOT, "include", "specan.h")).read()
+    assert "#define SA_Q15_TRACE_AVG_KIND(log2w, log2a) (0x80 | (log2a) << 3 | (log2w))" in txt
+    assert len(abi.SIGNATURES) == 45                                         # no new exported function
+
+
+def test_the_wrappers_tables():
+    import torch
+    from fpga_real_time_fft_analyzer_amd import abi, chain, frames
+    c = chain.Q15_TRACE_AVG_CHAIN
+    assert sorted(c.outputs) == [(1 << k, 1 << a) for k in range(1, 7) for a in range(1, 8)]
+    assert chain.TRACE_GROUPS == frames.TRACE_GROUPS == (2, 4, 8, 16, 32, 64, 128)
+    for (W, A), spec in c.outputs.items():
+        k, a = W.bit_length() - 1, A.bit_length() - 1
+        assert spec == (abi.SA_Q15_TRACE_AVG_KIND(k, a), (N // W, 2), torch.float32, A)
+        assert c.output((W, A)) == spec
+        for rows in (0, 1, 3):
+            assert chain.output_spec(c, (W, A), rows * A) == ((rows, N // W, 2), torch.float32)
+        for B in (1, A + 1, 3 * A - 1):
+            with pytest.raises(abi.SpecanError) as e:
+                chain.output_spec(c, (W, A), B)
+            assert e.value.code == SA_ESHAPE
+    for dtype, (row, calls) in c.inputs.items():
+        want = "sa_process_q15_out" if dtype == torch.int16 else "sa_process_q15_p12"
+        assert {call[0] for call in calls.values()} == {want} and c.streams[dtype][1] == calls
+    # every other table keeps one frame per row
+    for other in (chain.FLOAT_CHAIN, chain.Q15_CHAIN, chain.Q15_TRACE_CHAIN, chain.Q15_WINDOW_CHAIN):
+        for name in other.outputs:
+            assert other.output(name)[3] == 1 and other.rows(name, 7) == 7
+    for bad in ((16, 1), (16, 256), (1, 4), (128, 4), (16, 3), 16, None):
+        with pytest.raises(abi.SpecanError) as e:
+            chain.output_spec(c, bad, 8)
+        assert e.value.code == SA_EINVAL
+
+
+def test_pointer_contract_far_apart_and_alignment(check):
+    """SA_OK with the tensors far apart; every `in` offset is refused; `out` is refused exactly where it is off 16 bytes."""
+    for e in ENTRIES:
+        for k, a in KA:
+            A = 1 << a
+            for hop in HOPS:
+                w = word(k, a, hop)
+                for B in (A, 3 * A):
+                    tag = (e, hex(w), B)
+                    assert check(e, w, BASE, FAR, B) == SA_OK, tag
+                    assert check(e, w, FAR, BASE, B) == SA_OK, tag
+                    for off in (1, 2, 4, 8, 12, 16, 32):
+                        assert check(e, w, BASE + off, FAR, B) == (SA_OK if off % 16 == 0 else SA_EINVAL), tag + (off,)
+                        assert check(e, w, BASE, FAR + off, B) == (SA_OK if off % 16 == 0 else SA_EINVAL), tag + (off,)
+                    assert check(e, w, 0, FAR, B) == SA_EINVAL and check(e, w, BASE, 0, B) == SA_EINVAL, tag
+
+
+def test_overlap_is_decided_on_the_bytes_of_the_groups(check):
+    """`out` right behind what `in` reads is accepted and one byte (or one aligned step) less refused; `in` right behind the
+    (B / A) P 8 bytes that are written is accepted -- an address that B rows of P records would cover for every A > 1 --
+    and one aligned step, or one byte, further in is refused."""
+    for e, form in ENTRIES.items():
+        for k, a in KA:
+            A = 1 << a
+            for hop in HOPS:
+                w = word(k, a, hop)
+                for B in (A, 2 * A, 5 * A):
+                    tag = (e, hex(w), B)
+                    n_in, n_out = in_bytes(form, hop, B), out_bytes(k, a, B)
+                    assert n_out == (B // A) * (N >> k) * 8 and n_out % 16 == 0 and n_out * A == B * (N >> k) * 8
+                    behind = -(-(BASE + n_in) // 16) * 16
+                    assert check(e, w, BASE, behind, B) == SA_OK, tag
+                    assert check(e, w, BASE, behind - 16, B) == SA_EINVAL, tag
+                    if behind == BASE + n_in:
+                        assert check(e, w, BASE, behind - 1, B) == SA_EINVAL, tag
+                    else:
+                        assert form == "p12" and hop not in (0, 16384)
+                    # `out` below `in`: it ends where `in` begins, counted in groups
+                    front = BASE - n_out
+                    assert check(e, w, BASE, front, B) == SA_OK, tag
+                    assert check(e, w, BASE, front + 16, B) == SA_EINVAL, tag
+                    assert check(e, w, BASE, front + 1, B) == SA_EINVAL, tag
+                    assert check(e, w, BASE, BASE, B) == SA_EINVAL, tag
+                    # the plain trace kind of the same width writes A times as much: the same `out` is refused there
+                    assert check(e, (0x10 | k) | (hop // 8) << 8, BASE, front, B) == SA_EINVAL, tag
+
+
+def test_batches_and_refused_words(check):
+    for e in ENTRIES:
+        for k, a in KA:
+            A = 1 << a
+            for hop in HOPS:
+                w = word(k, a, hop)
+                for B in (A + 1, 1, A - 1, 2 * A + 1):
+                    if B % A:
+                        assert check(e, w, BASE, FAR, B) == SA_ESHAPE, (e, hex(w), B)
+                        assert check(e, w, 0, 0, B) == SA_ESHAPE, (e, hex(w), B)      # the batch before the pointers
+                assert check(e, w, BASE, FAR, -1) == SA_ESHAPE
+                for a_in, a_out in ((BASE, FAR), (0, 0), (BASE + 1, BASE + 3)):
+                    assert check(e, w, a_in, a_out, 0) == SA_OK, (e, hex(w))
+        for bad in BAD_WORDS:
+            for hop in HOPS:
+                for B in (0, 1, 128, 129):                                           # the kind before the empty batch
+                    assert check(e, bad | (hop // 8) << 8, BASE, FAR, B) == SA_EINVAL, (e, hex(bad), hop, B)
+        # every word of the low byte: the 42 kinds, the kinds there were, and nothing else
+        ok = {w for w in range(256) if check(e, w, BASE, FAR, 128) == SA_OK}
+        assert ok == {0, 1, 2} | {0x10 | k for k in range(1, 7)} | {kind(k, a) for k in range(1, 7) for a in range(1, 8)}
+        for bad in (3, 16, 23, 99, -1, 1 << 20, 1 << 30, 0x9C | 1 << 20, 0x9C | 2049 << 8):
+            assert check(e, bad, BASE, FAR, 128) == SA_EINVAL, (e, bad)
+        assert check(e, 0x9C | 2048 << 8, BASE, FAR, 8) == SA_OK
+    for e in (0, 1, 2):                                                              # the float entry points
+        for B in (0, 8):
+            assert check(e, 0x9C, BASE, FAR, B) == SA_EINVAL, (e, B)
+    for e in (3, 6, 7):                                                              # no kind word: ignored, as ever
+        assert check(e, 0x9C, BASE, FAR, 3) == SA_OK
+
+
+def test_trace_of_frames_against_a_direct_evaluation():
+    """Random full-scale int16 IQ frames whose first 64 bins hold (-32768, -32768), 2^31 each: point 0 is (A - 1) W 2^31,
+    past 2^32 in every case (one frame of each group is all zero)."""
+    from fpga_real_time_fft_analyzer_amd import frames
+    rng = np.random.default_rng(2024)
+    for A, W in ((2, 4), (4, 2), (8, 16), (8, 64), (128, 64)):
+        iq = rng.integers(-32768, 32768, size=(A, N, 2)).astype("<i2")
+        iq[:, :64] = -32768                                                          # 2^31 per bin
+        iq[A // 2] = 0                                                               # an all-zero frame inside the group
+        peak, power, exact = frames.trace_of_frames([f.tobytes() for f in iq], W)
+        re, im = iq[..., 0].astype(np.int64), iq[..., 1].astype(np.int64)
+        want = (re * re + im * im).reshape(A, N // W, W).sum(axis=(0, 2))
+        mag = np.sqrt(iq[..., 0].astype(np.float32) ** 2 + iq[..., 1].astype(np.float32) ** 2)
+        assert exact.dtype == np.int64 and np.array_equal(exact, want)
+        assert want[0] == (A - 1) * W << 31 and want[0] > 1 << 32
+        assert power.dtype == np.float32 and np.array_equal(power.view(np.uint32), want.astype(np.float32).view(np.uint32))
+        assert peak.dtype == np.float32
+        assert np.array_equal(peak.view(np.uint32), mag.reshape(A, N // W, W).max(axis=(0, 2)).view(np.uint32))
+        # built on trace_of_frame: the maximum of the frames' peaks and the sum of their exact sums
+        one = [frames.trace_of_frame(f.tobytes(), W) for f in iq]
+        assert np.array_equal(peak, np.max([p for p, _, _ in one], axis=0))
+        assert np.array_equal(exact, np.sum([x for _, _, x in one], axis=0))
+        if A >= 8:                                                                   # the float32 rounding is a real one
+            assert (power.astype(np.float64) != want).any()
+    z = frames.trace_of_frames([bytes(65536)] * 4, 16)
+    assert not z[0].view(np.uint32).any() and not z[1].view(np.uint32).any() and not z[2].any()
+    for bad in ([bytes(65536)], [bytes(65536)] * 3, [bytes(65536)] * 256):
+        with pytest.raises(ValueError):
+            frames.trace_of_frames(bad, 16)
+    with pytest.raises(ValueError):
+        frames.trace_of_frames([bytes(65536)] * 2, 3)
+
+
+def test_numpy_rounds_int64_to_float32_to_nearest_even():
+    """The Python-side reference of the power: ties at every shift up to 2^44 against an integer model."""
+    rng = np.random.default_rng(5)
+    m = rng.integers(1 << 23, 1 << 24, size=20000)
+    sh = rng.integers(1, 21, size=20000)
+    ties = (m << sh) + (1 << (sh - 1))
+    v = np.concatenate([ties, ties - 1, ties + 1, rng.integers(0, 1 << 44, size=40000), [0, 1, 1 << 24, (1 << 24) + 1, 1 << 44]])
+    got = v.astype(np.int64).astype(np.float32)
+    for x, g in zip(v.tolist(), got.tolist()):
+        n = x.bit_length()
+        if n <= 24:
+            want = x
+        else:
+            s = n - 24
+            q, r = x >> s, x & ((1 << s) - 1)
+            q += r > (1 << (s - 1)) or (r == (1 << (s - 1)) and q & 1)
+            want = q << s
+        assert int(g) == want, x
+
+
+def test_standalone_rounding_program_under_host_sanitizers(tmp_path):
+    """tests/cpp/test_q15_round.cpp on csrc/q15_round.hpp, host only, with -fsanitize=address,undefined when that links here
+    (a plain build otherwise: the program's own checks still run)."""
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    exe = str(tmp_path / "test_q15_round")
+    srcs = [os.path.join(ROOT, "tests", "cpp", "test_q15_round.cpp")]
+    base = [hipcc, "-O1", "-g", "-std=c++17", "--offload-host-only", "-x", "hip", *srcs, "-o", exe]
+    r = subprocess.run(base + ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"],
+                       capture_output=True, text=True, timeout=300)
+    sanitized = r.returncode == 0
+    if not sanitized:
+        r = subprocess.run(base, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr
+    print("sanitizers:", "address,undefined" if sanitized else "did not link here: plain build")
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and r.stdout.startswith("ok "), r.stdout + r.stderr
+    assert int(r.stdout.split()[1]) > 1 << 25

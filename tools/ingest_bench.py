@@ -17,7 +17,11 @@ stream through StreamCutter(H, batch_frames) + the stream feeder into process_q1
 once -- against the same stream cut on the host by FrameCutter(H) + the frame feeder into the frame call, 16384 / H times
 the bytes; both cut up front, 'marker' records out, the two alternating in one process over --rounds R (default 5) runs of
 n_batches batches each.  Choose n_batches so that a run lasts some tenths of a second.  The bound on the ratio is 16384 / H.
-usage: ingest_bench.py [batch_frames] [n_batches] [mode] [--events] [--float] [--packed] [--packed-q15] [--hop H [--rounds R]]"""
+--hop H --trace W --group A: the stream form alone, with the copy of the result back to pinned host memory behind every call
+on the call's stream: the plain trace at bucket W (traces_q15(x, bucket=W, hop=H): 131072 / W bytes per frame back) against
+the grouped one (group=A: a factor A fewer), alternating as above.
+usage: ingest_bench.py [batch_frames] [n_batches] [mode] [--events] [--float] [--packed] [--packed-q15]
+                       [--hop H [--rounds R] [--trace W --group A]]"""
 import os
 import sys
 import time
@@ -98,6 +102,50 @@ def hop_mode(hop, rounds):
     ch.close()
 
 
+def hop_trace_mode(hop, rounds, W, A):
+    """--hop H --trace W --group A: plain against grouped trace from the stream, results copied back"""
+    ch = SpectrumChain(0)
+    ch.set_filter_mode(mode)
+    ch.reserve(B)
+    s = np.random.default_rng(0).integers(-2048, 2048, size=(4 * B - 1) * hop + N, dtype=np.int16)
+    s = pack12(s) if PACKED else s
+    blocks = StreamCutter(hop, B, PACKED).push(s)                      # 4 distinct blocks of B frames, reused
+    feeder = DeviceFeeder(0, max_batch=B, packed=PACKED, stream=True)
+    forms = {"plain": None, "grouped": A}
+    out = {f: [torch.empty((B // (g or 1), N // W, 2), dtype=torch.float32, device="cuda") for _ in range(2)] for f, g in forms.items()}
+    host = {f: [torch.empty(o.shape, dtype=torch.float32).pin_memory() for o in out[f]] for f in forms}
+
+    def run(form, nb):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for i, xd in enumerate(feeder.feed(blocks[j & 3] for j in range(nb))):
+            ch.traces_q15(xd, bucket=W, out=out[form][i & 1], hop=hop, group=forms[form])
+            host[form][i & 1].copy_(out[form][i & 1], non_blocking=True)
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0
+
+    for form in forms:                                                  # warm-up (grows the grouped kind's workspace)
+        run(form, 4)
+    # the last block fed was blocks[3] into buffer 1 in both forms: the grouped records are the plain ones, reduced
+    assert torch.equal(host["grouped"][1][..., 0], host["plain"][1][..., 0].reshape(B // A, A, N // W).amax(1))
+    rate = {form: [] for form in forms}
+    for _ in range(rounds):
+        for form in forms:
+            rate[form].append(NB * B / run(form, NB))
+    print(f"hop {hop} ({'packed 12-bit' if PACKED else 'int16'} samples), batch {B} frames x {NB} batches per run, {rounds} "
+          f"alternating runs, filter mode 0x{mode:02X}, trace W = {W} from the stream, result copied to pinned host memory; "
+          f"a plain run lasts {NB * B / np.median(rate['plain']):.2f} s")
+    for form, g in forms.items():
+        r = np.array(rate[form])
+        back = (N // W) * 8 / (g or 1)
+        print(f"  {form:7s}{'' if g is None else f' A = {g}'}: {back:6.0f} bytes per frame back; M frames/s per run "
+              f"{' '.join(f'{v / 1e6:.3f}' for v in r)}; median {np.median(r) / 1e6:.3f} (max/min {r.max() / r.min():.3f}) = "
+              f"{np.median(r) * back / 1e9:5.1f} GB/s back, {np.median(r) * blocks[0].size * s.itemsize / B / 1e9:5.1f} GB/s in")
+    ratio = np.array(rate["grouped"]) / np.array(rate["plain"])
+    print(f"  grouped / plain per round: {' '.join(f'{v:.3f}' for v in ratio)}; median {np.median(ratio):.3f}")
+    ch.close()
+
+
 def pure_h2d():
     pin = torch.empty((B, ROW), dtype=IN_DT).pin_memory()
     dev = torch.empty((B, ROW), dtype=IN_DT, device="cuda")
@@ -114,6 +162,9 @@ def pure_h2d():
 if "--hop" in sys.argv:
     if FLOAT:
         sys.exit("--hop is a mode of the integer chain (with --packed-q15 for packed samples)")
+    if "--trace" in sys.argv:
+        hop_trace_mode(opt("--hop", N), opt("--rounds", 5), opt("--trace", 16), opt("--group", 16))
+        sys.exit(0)
     hop_mode(opt("--hop", N), opt("--rounds", 5))
     sys.exit(0)
 
