@@ -1,4 +1,4 @@
-"""ctypes binding of ``libspecan_hip.so`` (the C ABI declared in ``include/specan.h``).
+"""ctypes binding of ``libspecan_hip.so`` (the C ABI declared in ``include/specan.h`` and ``include/specan_ext.h``).
 
 This is the only place the shared library is loaded.  There is no CPU fallback: if the
 library is missing the import of any compute entry point raises, and creating a handle
@@ -137,6 +137,19 @@ SIGNATURES = {
     "sa_get_marker_range": (_INT, [H, _P(_INT), _P(_INT)]),
 }
 
+# the entry points of include/specan_ext.h, data-plane calls added after the version-4 surface of include/specan.h closed:
+# a table of their own, bound by lib() like the one above and held name for name against that header
+# (tests/test_q15_spectra_cpu.py); no name is in both
+SA_EXT_VERSION = 1
+SA_EXT_ENTRIES = ("sa_spectra_q15", "sa_spectra_q15_p12", "sa_fold_iq_q15")     # as sa_ext_check_pointers numbers them
+EXT_SIGNATURES = {
+    "sa_ext_version": (_INT, []),
+    "sa_spectra_q15": (_INT, [H, C.c_void_p, C.c_void_p, _INT, _INT, _INT, C.c_void_p]),
+    "sa_spectra_q15_p12": (_INT, [H, C.c_void_p, C.c_void_p, _INT, _INT, _INT, C.c_void_p]),
+    "sa_fold_iq_q15": (_INT, [H, C.c_void_p, C.c_void_p, _INT, _INT, C.c_void_p]),
+    "sa_ext_check_pointers": (_INT, [_INT, _INT, _INT, C.c_uint64, C.c_uint64, _INT]),
+}
+
 _lib = None
 
 
@@ -158,7 +171,7 @@ def lib() -> C.CDLL:
     except ImportError:
         pass
     L = C.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in SIGNATURES.items():
+    for name, (restype, argtypes) in {**SIGNATURES, **EXT_SIGNATURES}.items():
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, argtypes
     _lib = L

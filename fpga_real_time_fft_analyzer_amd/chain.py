@@ -518,6 +518,71 @@ class SpectrumChain:
             raise SpecanError(abi.SA_EINVAL, f"group must be one of {TRACE_GROUPS}")
         return self._process(Q15_TRACE_AVG_CHAIN, x, out, (int(bucket), int(group)), hop=hop)
 
+    # The calls of include/specan_ext.h have argument lists of their own (log2a and hop as plain ints, no kind word), so they
+    # have a small call path of their own beside _process: the input forms below, _check_in's checks, _lend's lending.
+    _SPECTRA_IN = {torch.int16: (SA_N, "sa_spectra_q15"), torch.uint8: (SA_P12_FRAME_BYTES, "sa_spectra_q15_p12")}
+
+    @staticmethod
+    def _log2_group(group) -> int:
+        if isinstance(group, bool) or not isinstance(group, (int, np.integer)) or int(group) not in TRACE_GROUPS:
+            raise SpecanError(abi.SA_EINVAL, f"group must be one of {TRACE_GROUPS}")
+        return int(group).bit_length() - 1
+
+    def _spectra_out(self, out, B: int, group: int) -> torch.Tensor:
+        if B % group:
+            raise SpecanError(abi.SA_ESHAPE, f"the batch ({B} frames) must be a multiple of {group}")
+        shape = (B // group, SA_N, 2)
+        if out is None:
+            return torch.empty(shape, dtype=torch.float32, device=self.device)
+        if tuple(out.shape) != shape or out.dtype != torch.float32 or out.device != self.device or not out.is_contiguous():
+            raise SpecanError(abi.SA_ESHAPE, f"out must be a contiguous {torch.float32} tensor of shape {shape}")
+        return out
+
+    def spectra_q15(self, x: torch.Tensor, group: int, out: Optional[torch.Tensor] = None,
+                    hop: Optional[int] = None) -> torch.Tensor:
+        """Max hold and summed power of the integer chain's frames over groups of ``group`` consecutive frames, at the full
+        resolution of 16384 bins: [B // group, 16384, 2] float32, one sa_trace_point_q15 per bin and group
+        (include/specan_ext.h, sa_spectra_q15).  ``[..., 0]`` is the largest 'mag' value of the bin over the group's frames,
+        bit for bit; ``[..., 1]`` the exact integer sum of re^2 + im^2 over them (at most 2^38) rounded once to float32.  It
+        is the SUM: the mean is ``power / group``, exactly -- a Welch estimate where the frames overlap (``hop``).
+        frames.spectrum_of_frames is the numpy mirror of one row; the marker range plays no part.
+
+        ``group`` is 2, 4, ..., 128; anything else (a bool or a float included) is SA_EINVAL, a B that is no multiple of it
+        SA_ESHAPE, both before any device call.  ``x`` is int16 or packed uint8 as for :meth:`process_q15`, and with ``hop``
+        a 1-D stream as there.  The call is :meth:`process_q15` ``(out_kind='iq')`` into a workspace of the handle, 64 KiB
+        per frame, and one more launch that folds it; the workspace is grown by the call itself and never by
+        :meth:`reserve`: before capturing such a call into a graph, make one of the same batch outside it (SA_ESTATE
+        otherwise).  The pointer contract is that of :meth:`process_q15`, on (B // group) * 131072 bytes written."""
+        a = self._log2_group(group)
+        if hop is not None and (isinstance(hop, bool) or not isinstance(hop, (int, np.integer)) or not 8 <= hop <= SA_N or hop % 8):
+            raise SpecanError(abi.SA_EINVAL, "hop must be an int, a multiple of 8 in 8..16384")
+        forms = self._SPECTRA_IN
+        dtype = x.dtype if isinstance(x, torch.Tensor) and x.dtype in forms else next(iter(forms))
+        row, name = forms[dtype]
+        B = self._check_in(x, dtype, row, None if hop is None else int(hop))
+        out = self._spectra_out(out, B, 1 << a)
+        self._check(getattr(self._lib, name)(self._h, x.data_ptr(), out.data_ptr(), B, a, 0 if hop is None else int(hop),
+                                             self._stream()))
+        self._lend(x, out)
+        return out
+
+    def fold_iq_q15(self, iq: torch.Tensor, group: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The fold of :meth:`spectra_q15` alone, on frames the caller already has: ``iq`` is an int16 [B,16384,2] device
+        tensor, the result of ``process_q15(out_kind='iq')`` (include/specan_ext.h, sa_fold_iq_q15); the result is
+        [B // group, 16384, 2] float32 as there.  One launch, no workspace: it captures into a graph at any time."""
+        a = self._log2_group(group)
+        if not isinstance(iq, torch.Tensor) or iq.dtype != torch.int16:
+            raise SpecanError(abi.SA_EINVAL, f"input must be a {torch.int16} tensor")
+        if iq.device != self.device:
+            raise SpecanError(abi.SA_EINVAL, f"input must live on {self.device}")
+        if iq.dim() != 3 or tuple(iq.shape[1:]) != (SA_N, 2) or not iq.is_contiguous():
+            raise SpecanError(abi.SA_ESHAPE, f"input must be a contiguous [B, {SA_N}, 2] tensor")
+        B = iq.shape[0]
+        out = self._spectra_out(out, B, 1 << a)
+        self._check(self._lib.sa_fold_iq_q15(self._h, iq.data_ptr(), out.data_ptr(), B, a, self._stream()))
+        self._lend(iq, out)
+        return out
+
     def filter_q15(self, x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Window (+ integer IIR) only: the FFT input stream, [B,16384] int16.  ``x`` is [B,16384] int16 or the same
         samples packed, [B,24576] uint8 (sa_filter_q15_p12), as for :meth:`process_q15`.

@@ -29,14 +29,7 @@ namespace {
         : "=&v"(P0), "=&v"(P1), "=&v"(P2), "=&v"(P3)                                                                   \
         : "v"(LO0), "v"(LO1), "v"(LO2), "v"(LO3), "v"(HI0), "v"(HI1), "v"(HI2), "v"(HI3), "s"(2))
 
-// lo(a) lo(b) + hi(a) hi(b), exact in 32 bits.  Written out: the builtin is selected as the accumulating two-operand
-// form v_dot2c_i32_i16, which costs a v_mov of zero into the accumulator per product.
-__device__ __forceinline__ int fx_dot2(unsigned a, unsigned b)
-{
-    int r;
-    asm("v_dot2_i32_i16 %0, %1, %2, 0" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
+// fx_dot2, lo(a) lo(b) + hi(a) hi(b) exact in 32 bits: q15_dev.hpp (shared with spectra_fold_q15.hip)
 // the same with a wave-uniform second operand taken straight from its scalar register (no v_mov per product)
 __device__ __forceinline__ int fx_dot2_s(unsigned a, unsigned b)
 {
@@ -149,18 +142,8 @@ __device__ __forceinline__ void fx_butterfly_real(int a, int b, int c, int d, ui
 constexpr int kFftWide = 1024;                            // threads per frame (fft_q15_kernel below)
 
 // ---- SA_Q15_OUT_MAG / SA_Q15_OUT_MARKER: the host's decode of the wire frame, made in the epilogue -------------------
-// decode_mag_16iq_le (gui.py:250-260) is np.sqrt(re.astype(float32)**2 + im.astype(float32)**2): four float32 operations,
-// each rounded on its own.  The two squares and their sum must therefore not be contracted into an FMA (hipcc's default
-// is -ffp-contract=fast; squares are exact only up to |v| = 4096), and the root must be the correctly rounded one.
-__device__ __forceinline__ float fx_mag_sum(unsigned p)
-{
-#pragma clang fp contract(off)
-    const float r = (float)lo16(p), i = (float)hi16(p);
-    const float rr = r * r, ii = i * i;
-    return rr + ii;
-}
-
-// fx_sqrt_rn, the correctly rounded root: q15_dev.hpp (shared with trace_fold_q15.hip)
+// fx_mag_sum, the three uncontracted float operations under the root, and fx_sqrt_rn, the correctly rounded root: q15_dev.hpp
+// (shared with trace_fold_q15.hip and spectra_fold_q15.hip)
 __device__ __forceinline__ float fx_mag(unsigned p) { return fx_sqrt_rn(fx_mag_sum(p)); }
 
 // SA_Q15_OUT_MARKER: a part of the record -- the largest magnitude seen (-1: none yet), the lowest bin attaining it, and

@@ -1,6 +1,7 @@
 // q15_dev.hpp -- device helpers shared by the integer cascades (cascade_q15.hip) and the fixed-point FFT (fft_q15.hip):
-// the Q15 window of one sample and the packed int16 pair -- and, shared by the FFT's epilogues and the trace fold
-// (trace_fold_q15.hip), the correctly rounded square root.
+// the Q15 window of one sample and the packed int16 pair -- and, shared by the FFT's epilogues and the fold kernels
+// (trace_fold_q15.hip, spectra_fold_q15.hip), the packed dot product, the float sum under the magnitude's root and the
+// correctly rounded square root.
 #pragma once
 #include "sa_common.hpp"
 
@@ -34,6 +35,27 @@ __device__ __forceinline__ unsigned sat_pack2(int lo, int hi)
 
 __device__ __forceinline__ int lo16(unsigned v) { return (int)(short)(v & 0xFFFFu); }
 __device__ __forceinline__ int hi16(unsigned v) { return (int)v >> 16; }
+
+// lo(a) lo(b) + hi(a) hi(b), exact in 32 bits.  Written out: the builtin is selected as the accumulating two-operand
+// form v_dot2c_i32_i16, which costs a v_mov of zero into the accumulator per product.
+__device__ __forceinline__ int fx_dot2(unsigned a, unsigned b)
+{
+    int r;
+    asm("v_dot2_i32_i16 %0, %1, %2, 0" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+
+// decode_mag_16iq_le (gui.py:250-260) is np.sqrt(re.astype(float32)**2 + im.astype(float32)**2): four float32 operations,
+// each rounded on its own.  The two squares and their sum must therefore not be contracted into an FMA (hipcc's default
+// is -ffp-contract=fast; squares are exact only up to |v| = 4096), and the root must be the correctly rounded one
+// (fx_sqrt_rn below).  This is the sum under the root, s = fl(fl(re re) + fl(im im)), of one packed (re, im) word.
+__device__ __forceinline__ float fx_mag_sum(unsigned p)
+{
+#pragma clang fp contract(off)
+    const float r = (float)lo16(p), i = (float)hi16(p);
+    const float rr = r * r, ii = i * i;
+    return rr + ii;
+}
 
 // Correctly rounded square root of s = 0 or an integer-valued float in [1, 2^31]: v_sqrt_f32 is within 1 ulp, so the
 // result is y or one of its two neighbours, told apart by the signs of the exact residuals s - y_down y and s - y_up y

@@ -184,6 +184,9 @@ constexpr int kSaTraceRawBytes = 16;
 // trace_fold_q15.hip: batch a multiple of 2^log2a; reads batch * (16384 >> log2w) records, writes (batch >> log2a) rows
 hipError_t sa_launch_trace_fold_q15(const void *partial, void *out, int batch, int log2w, int log2a, hipStream_t stream,
                                     SaLaunchEv ev);
+// spectra_fold_q15.hip (include/specan_ext.h): iq = int16 [batch,16384,2], batch a multiple of 2^log2a; writes
+// sa_trace_point_q15 [batch >> log2a, 16384], each row the fold of 2^log2a consecutive frames bin by bin
+hipError_t sa_launch_spectra_fold_q15(const void *iq, void *out, int batch, int log2a, hipStream_t stream, SaLaunchEv ev);
 // The same two launches on frames cut from ONE sample stream (SA_Q15_HOP_KIND of include/specan.h): frame f is the 16384
 // samples from sample f * hop on, hop a multiple of 8 in 8..16384; `in` holds (batch - 1) * hop + 16384 samples, int16 or
 // packed (3/2 bytes per sample), 16-byte aligned.  The cascade writes frames, [B,16384] int16, as ever; the FFT reads a stream

@@ -51,13 +51,15 @@ struct sa_handle {
         int frames;
         size_t elem;
     };
-    enum { kWorkQ15, kWorkF64, kWorkTraceRaw, kWorkKinds };
+    enum { kWorkQ15, kWorkF64, kWorkTraceRaw, kWorkSpectra, kWorkKinds };
     // Launch slot i (slot 0 = ordered mode; overlap mode uses slots 0..depth-1): its workspaces -- the Q15 cascade's
     // int16 output, in float64-state mode the float32 y [B,16384], and the partial records of SA_Q15_TRACE_AVG_KIND (bytes,
-    // counted in units of 16384: grown by the calls of that kind alone, never by sa_reserve or a change of mode) -- and, in
-    // overlap mode, its internal stream
+    // counted in units of 16384: grown by the calls of that kind alone, never by sa_reserve or a change of mode), and the
+    // int16 (re, im) frames of sa_spectra_q15 (include/specan_ext.h; 64 KiB per frame, grown by those calls alone too) -- and,
+    // in overlap mode, its internal stream
     struct Slot {
-        Workspace work[kWorkKinds] = {{nullptr, 0, sizeof(int16_t)}, {nullptr, 0, sizeof(float)}, {nullptr, 0, 1}};
+        Workspace work[kWorkKinds] = {{nullptr, 0, sizeof(int16_t)}, {nullptr, 0, sizeof(float)}, {nullptr, 0, 1},
+                                      {nullptr, 0, 2 * sizeof(int16_t)}};
         hipStream_t stream = nullptr;
         hipEvent_t fork = nullptr, done = nullptr;
         bool used = false;                 // `done` has been recorded

@@ -3,7 +3,7 @@
 // compared as integers, never dereferenced.
 #include "sa_pointers.hpp"
 
-#include "../../include/specan.h"
+#include "../../include/specan_ext.h"
 
 namespace {
 
@@ -130,4 +130,48 @@ extern "C" int sa_debug_check_pointers(int entry, int kind_word, uint64_t in_add
     if (batch % sa_frames_per_row(e.chain, kind)) return SA_ESHAPE;                                  // and so is the group
     if (in_addr == 0 || out_addr == 0) return SA_EINVAL;
     return sa_pointer_faults(s, in_addr, out_addr) ? SA_EINVAL : SA_OK;
+}
+
+// ---- include/specan_ext.h ---------------------------------------------------------------------------------------------
+
+int sa_ext_check(int entry, int log2a, int hop, uint64_t in, uint64_t out, int batch, SaExtWhy *why, SaCallSpan *span)
+{
+    static_assert(SA_EXT_ENTRY_SPECTRA_Q15 == 0 && SA_EXT_ENTRY_SPECTRA_Q15_P12 == 1 && SA_EXT_ENTRY_FOLD_IQ_Q15 == 2 &&
+                      SA_EXT_ENTRY_COUNT == 3, "the entries told apart below");
+    *why = kSaExtEntry;
+    if (entry < 0 || entry >= SA_EXT_ENTRY_COUNT) return SA_EINVAL;
+    const bool fold = entry == SA_EXT_ENTRY_FOLD_IQ_Q15;
+    *why = kSaExtBatch;
+    if (batch < 0) return SA_ESHAPE;
+    *why = kSaExtLog2a;
+    if (log2a < SA_Q15_TRACE_LOG2A_MIN || log2a > SA_Q15_TRACE_LOG2A_MAX) return SA_EINVAL;
+    *why = kSaExtHop;
+    if (hop != 0 && (fold || hop < 8 || hop > SA_N || hop % 8 != 0)) return SA_EINVAL;
+    *why = kSaExtNone;
+    if (batch == 0) return SA_OK;
+    *why = kSaExtGroup;
+    if (batch & ((1 << log2a) - 1)) return SA_ESHAPE;
+    *why = kSaExtNull;
+    const uint64_t B = (uint64_t)batch;
+    if (fold) {
+        span->in_bytes = B * kN * 4;                                // int16 [B,16384,2]
+        span->in_align = 16;
+    } else if (!sa_call_span(SaChain::Q15, entry == SA_EXT_ENTRY_SPECTRA_Q15_P12 ? kSaInP12 : kSaInI16, SA_Q15_OUT_IQ, hop, batch,
+                             span)) {
+        *why = kSaExtHop;                                           // unreachable: the hop was checked above
+        return SA_EINVAL;
+    }
+    span->out_bytes = (B >> log2a) * kN * sizeof(sa_trace_point_q15);
+    span->out_align = 16;
+    if (in == 0 || out == 0) return SA_EINVAL;
+    const unsigned faults = sa_pointer_faults(*span, in, out);
+    *why = faults & kSaPtrInAlign ? kSaExtInAlign : faults & kSaPtrOutAlign ? kSaExtOutAlign : faults ? kSaExtOverlap : kSaExtNone;
+    return faults ? SA_EINVAL : SA_OK;
+}
+
+extern "C" int sa_ext_check_pointers(int entry, int log2a, int hop, uint64_t in_addr, uint64_t out_addr, int batch)
+{
+    SaExtWhy why;
+    SaCallSpan s;
+    return sa_ext_check(entry, log2a, hop, in_addr, out_addr, batch, &why, &s);
 }

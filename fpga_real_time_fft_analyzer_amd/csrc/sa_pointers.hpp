@@ -3,7 +3,8 @@
 // ranges are disjoint.  Pure integer arithmetic on addresses that are never dereferenced: no handle, no stream and no HIP
 // runtime call, so tests/test_pointer_contract_cpu.py (through sa_debug_check_pointers) and tests/cpp/test_sa_pointers.cpp
 // run the whole matrix without a GPU.  check_process_args (specan_abi.cpp) asks the same two functions before any call
-// state exists.
+// state exists.  The calls of include/specan_ext.h have their argument and pointer checks here too (sa_ext_check, with
+// sa_ext_check_pointers as its export and tests/cpp/test_sa_ext_pointers.cpp as its stand-alone test).
 #pragma once
 #include <stdint.h>
 
@@ -34,5 +35,14 @@ int sa_frames_per_row(SaChain chain, int out_kind);
 // What is wrong with the pair of addresses, as a set: every fault is reported, the caller chooses which one to name
 enum : unsigned { kSaPtrInAlign = 1u, kSaPtrOutAlign = 2u, kSaPtrOverlap = 4u };
 unsigned sa_pointer_faults(const SaCallSpan &s, uint64_t in, uint64_t out);
+
+// ---- the calls of include/specan_ext.h (sa_spectra_q15, sa_spectra_q15_p12, sa_fold_iq_q15; `entry` = SA_EXT_ENTRY_*): every
+// refusal the header lists, in its order, as one function.  Returns SA_OK, SA_EINVAL or SA_ESHAPE; `why` says which rule
+// refused (the entry points choose their message by it; kSaExtNone with SA_OK) and, from kSaExtNull on, `span` holds the byte
+// counts of the call: what the Q15 chain reads for that input form and hop (the fold: batch * 65536) and
+// (batch >> log2a) * 131072 written.  batch == 0 that passes the argument checks is SA_OK with the addresses unread.
+enum SaExtWhy { kSaExtNone, kSaExtEntry, kSaExtBatch, kSaExtLog2a, kSaExtHop, kSaExtGroup, kSaExtNull, kSaExtInAlign, kSaExtOutAlign,
+                kSaExtOverlap };
+int sa_ext_check(int entry, int log2a, int hop, uint64_t in, uint64_t out, int batch, SaExtWhy *why, SaCallSpan *span);
 
 #pragma GCC visibility pop

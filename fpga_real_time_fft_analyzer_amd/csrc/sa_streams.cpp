@@ -81,14 +81,14 @@ int pick_stream(sa_handle *h, const hipStream_t *avoid, int navoid, hipStream_t 
 // `geometric`: grow by at least half (process calls with creeping batch sizes); exact sizing where the size is copied
 // from another slot -- sa_set_overlap gave every slot max(the others, 1.5 x its own), and two slots leap-frogged each
 // other by a factor 1.5 per mode change until hipMalloc failed (found by a 10-minute soak, seed 77).
-// `on_demand`: a workspace sa_reserve does not size (kWorkTraceRaw); the refusal inside a capture names the other remedy.
-int ensure_work(sa_handle *h, sa_handle::Workspace &w, int frames, bool captured, bool geometric = true, bool on_demand = false)
+// `on_demand`: null, or for a workspace sa_reserve does not size (kWorkTraceRaw, kWorkSpectra) the refusal inside a capture,
+// which names the other remedy.
+int ensure_work(sa_handle *h, sa_handle::Workspace &w, int frames, bool captured, bool geometric = true,
+                const char *on_demand = nullptr)
 {
     if (frames <= w.frames) return SA_OK;
     if (captured)
-        return fail(h, SA_ESTATE, on_demand ? "workspace growth inside a stream capture: make one SA_Q15_TRACE_AVG_KIND call of this "
-                                              "bucket width and batch outside the capture first (sa_reserve does not size it)"
-                                            : "workspace growth inside a stream capture: call sa_reserve() first");
+        return fail(h, SA_ESTATE, on_demand ? on_demand : "workspace growth inside a stream capture: call sa_reserve() first");
     long want = frames, geo = (long)w.frames + w.frames / 2;
     if (geometric && geo > want) want = geo;
     void *p = nullptr;
@@ -187,7 +187,7 @@ int grow_slots(sa_handle *h, int n, int frames, bool geometric, bool f64_only)
 {
     const int k0 = f64_only ? sa_handle::kWorkF64 : sa_handle::kWorkQ15;
     const int k1 = f64_only || h->precision == SA_PRECISION_F64_STATE ? sa_handle::kWorkF64 + 1 : sa_handle::kWorkF64;
-    static_assert(sa_handle::kWorkQ15 == 0 && sa_handle::kWorkF64 == 1, "the two kinds sized here; kWorkTraceRaw grows on demand");
+    static_assert(sa_handle::kWorkQ15 == 0 && sa_handle::kWorkF64 == 1, "the two kinds sized here; kWorkTraceRaw and kWorkSpectra grow on demand");
     for (int k = k0; k < k1; ++k) {
         int want = frames;
         if (want < 0)
@@ -241,7 +241,13 @@ int begin_call(sa_handle *h, hipStream_t user, int work, int frames, CallCtx *c,
     }
     if (work >= 0) { const int rc = ensure_work(h, h->slot[c->slot].work[work], frames, c->captured); if (rc != SA_OK) return rc; }
     if (work2 >= 0) {
-        const int rc = ensure_work(h, h->slot[c->slot].work[work2], frames2, c->captured, true, work2 == sa_handle::kWorkTraceRaw);
+        const char *remedy =
+            work2 == sa_handle::kWorkTraceRaw  ? "workspace growth inside a stream capture: make one SA_Q15_TRACE_AVG_KIND call of this "
+                                                 "bucket width and batch outside the capture first (sa_reserve does not size it)"
+            : work2 == sa_handle::kWorkSpectra ? "workspace growth inside a stream capture: make one sa_spectra_q15 call of this batch "
+                                                 "outside the capture first (sa_reserve does not size it)"
+                                               : nullptr;
+        const int rc = ensure_work(h, h->slot[c->slot].work[work2], frames2, c->captured, true, remedy);
         if (rc != SA_OK) return rc;
     }
     if (c->overlapped) {

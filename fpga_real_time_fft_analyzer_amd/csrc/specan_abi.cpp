@@ -11,6 +11,8 @@
 #include "sa_pointers.hpp"
 #include "sa_tables.hpp"
 
+#include "../../include/specan_ext.h"
+
 #include <array>
 #include <cstring>
 #include <memory>
@@ -485,44 +487,54 @@ static int check_process_args(sa_handle *h, const char *fn, const void *in, SaIn
     return SA_OK;
 }
 
-// sa_filter_q15 (`fft` false: window + integer cascade into `out`, out_kind unused) and sa_process_q15 / sa_process_q15_out
-// (`out` per out_kind, SA_Q15_OUT_* or SA_Q15_TRACE_KIND(k): the FFT launch's epilogue makes it; SA_Q15_TRACE_AVG_KIND(k, a):
-// the epilogue's partial records and a fold launch behind it), on int16 samples or, the
-// _p12 entry points, on packed 12-bit samples (`kind`: I16 or P12); `fn` names the entry point.  `hop_word`: out_kind is a
-// SA_Q15_HOP_KIND (sa_process_q15_out, sa_process_q15_p12); with a hop, `in` is one stream and whichever launch reads the
-// samples -- the cascade, or the FFT in mode 0xB1 -- is its _hop sibling.  Everything else is the frame call.
-static int process_q15(sa_handle *h, const char *fn, const void *in, SaInKind kind, void *out, int batch, int out_kind,
-                       void *stream, bool fft, bool hop_word = false)
+// What a Q15 call launches behind its FFT: nothing, the fold of SA_Q15_TRACE_AVG_KIND(k, a)'s partial records
+// (trace_fold_q15.hip), or the bin-by-bin fold of sa_spectra_q15's IQ frames (spectra_fold_q15.hip, include/specan_ext.h).
+// With a fold the FFT launch writes into a workspace of the slot and the fold writes `out`.
+struct Q15Fold {
+    enum What { None, Trace, Spectra } what;
+    int log2w, log2a;
+};
+
+// The launches of a Q15 call whose arguments have passed their checks (batch > 0): sa_filter_q15 (`fft` false: window +
+// integer cascade into `out`, out_kind unused), sa_process_q15 / sa_process_q15_out (`out` per out_kind, SA_Q15_OUT_* or
+// SA_Q15_TRACE_KIND(k): the FFT launch's epilogue makes it; SA_Q15_TRACE_AVG_KIND(k, a): the epilogue's partial records and a
+// fold launch behind it) and sa_spectra_q15 (out_kind SA_Q15_OUT_IQ into a workspace and its fold behind it), on int16 samples
+// or on packed 12-bit samples (`kind`: I16 or P12); `fn` names the entry point.  With a hop, `in` is one stream and whichever
+// launch reads the samples -- the cascade, or the FFT in mode 0xB1 -- is its _hop sibling.  Everything else is the frame call.
+static int launch_q15(sa_handle *h, const char *fn, const void *in, SaInKind kind, void *out, int batch, int out_kind,
+                      void *stream, bool fft, int hop, Q15Fold fold)
 {
-    int hop = 0;
-    { const int rc = check_process_args(h, fn, in, kind, out, batch, out_kind, fft ? SaChain::Q15 : SaChain::Q15Filter,
-                                        SA_Q15_OUT_MARKER, "SA_Q15_OUT_MARKER", fft, true, hop_word ? &hop : nullptr, hop_word);
-      if (rc != SA_OK || batch == 0) return rc; }
-    if (hop_word) out_kind &= 0xFF;
     SA_HIP(h, hipSetDevice(h->device));
     const SaQ15Params p = q15_params(h);
     const bool staged = fft && p.filter != SA_FILTER_NONE;      // cascade into the slot's workspace, then the FFT
     // SA_Q15_TRACE_AVG_KIND(k, a): the FFT launch writes partial records [B, 16384 >> k] into a workspace of its own and one
     // more launch folds them into `out`.  B (16384 >> k) records of kSaTraceRawBytes are ceil(16 B / W) "frames" of the
-    // workspace's one-byte elements.  Grown here, on demand, with the cascade's workspace and before the first launch;
-    // never by sa_reserve, which does not know W.
-    const bool folded = hop_word && SA_Q15_IS_TRACE_AVG_KIND(out_kind);
-    const int log2w = SA_Q15_TRACE_AVG_LOG2W(out_kind), log2a = SA_Q15_TRACE_AVG_LOG2A(out_kind);
-    const long long raw_frames = folded ? ((long long)batch * kSaTraceRawBytes + (1 << log2w) - 1) >> log2w : 0;
-    if (raw_frames > 0x7FFFFFFF) return fail_at(h, SA_ESHAPE, fn, "SA_Q15_TRACE_AVG_KIND: batch too large for the workspace");
+    // workspace's one-byte elements.  sa_spectra_q15: the FFT launch writes B IQ frames into a workspace of 4-byte elements.
+    // Grown here, on demand, with the cascade's workspace and before the first launch; never by sa_reserve, which does not
+    // know W and sizes nothing for a call the handle may never make.
+    const bool folded = fold.what != Q15Fold::None;
+    const int work2 = fold.what == Q15Fold::Trace ? sa_handle::kWorkTraceRaw : folded ? sa_handle::kWorkSpectra : -1;
+    const long long frames2 = fold.what == Q15Fold::Trace ? ((long long)batch * kSaTraceRawBytes + (1 << fold.log2w) - 1) >> fold.log2w
+                              : folded                    ? batch
+                                                          : 0;
+    if (frames2 > 0x7FFFFFFF) return fail_at(h, SA_ESHAPE, fn, "SA_Q15_TRACE_AVG_KIND: batch too large for the workspace");
     CallCtx c;
-    { const int rc = begin_call(h, (hipStream_t)stream, staged ? sa_handle::kWorkQ15 : -1, batch, &c,
-                                folded ? sa_handle::kWorkTraceRaw : -1, (int)raw_frames);
+    { const int rc = begin_call(h, (hipStream_t)stream, staged ? sa_handle::kWorkQ15 : -1, batch, &c, work2, (int)frames2);
       if (rc != SA_OK) return rc; }
     const SaQ15Tables t = {h->d_rom, h->d_twq, h->d_twrec, h->marker_lo, h->marker_hi};
     // what the FFT launch writes, and the event its completion is bound to: the fold launch, where there is one, is the call's last
-    void *fft_out = folded ? h->slot[c.slot].work[sa_handle::kWorkTraceRaw].ptr : out;
+    void *fft_out = folded ? h->slot[c.slot].work[work2].ptr : out;
     hipEvent_t fft_stop = folded ? nullptr : c.stop;
+    const auto launch_fold = [&]() {
+        return fold.what == Q15Fold::Trace
+                   ? sa_launch_trace_fold_q15(fft_out, out, batch, fold.log2w, fold.log2a, c.stream, {nullptr, c.stop})
+                   : sa_launch_spectra_fold_q15(fft_out, out, batch, fold.log2a, c.stream, {nullptr, c.stop});
+    };
     if (!staged) {
         SA_HIP(h, hop   ? sa_launch_fft_q15_hop(in, kind, hop, fft_out, batch, out_kind, p, t, c.stream, {c.start, fft_stop})
                   : fft ? sa_launch_fft_q15(in, kind, fft_out, batch, out_kind, true, p, t, c.stream, {c.start, fft_stop})
                         : sa_launch_filter_q15(in, kind, (int16_t *)out, batch, p, t, c.stream, {c.start, c.stop}));
-        if (folded) SA_HIP(h, sa_launch_trace_fold_q15(fft_out, out, batch, log2w, log2a, c.stream, {nullptr, c.stop}));
+        if (folded) SA_HIP(h, launch_fold());
         return end_call(h, c);
     }
     // The WIDE cascade does not gain from overlapped launches (tools/q15_overlap_modes.py, profiles/r4_q15_helper_waves.txt):
@@ -538,8 +550,83 @@ static int process_q15(sa_handle *h, const char *fn, const void *in, SaInKind ki
     SA_HIP(h, hop ? sa_launch_filter_q15_hop(in, kind, hop, ws, batch, p, t, c.stream, {c.start, nullptr})
                   : sa_launch_filter_q15(in, kind, ws, batch, p, t, c.stream, {c.start, nullptr}));
     SA_HIP(h, sa_launch_fft_q15(ws, SaInKind::I16, fft_out, batch, out_kind, false, p, t, c.stream, {nullptr, fft_stop}));
-    if (folded) SA_HIP(h, sa_launch_trace_fold_q15(fft_out, out, batch, log2w, log2a, c.stream, {nullptr, c.stop}));
+    if (folded) SA_HIP(h, launch_fold());
     return end_call(h, c);
+}
+
+// sa_filter_q15 (`fft` false), sa_process_q15 / sa_process_q15_out and their _p12 siblings: the argument checks, then
+// launch_q15.  `hop_word`: out_kind is a SA_Q15_HOP_KIND (sa_process_q15_out, sa_process_q15_p12).
+static int process_q15(sa_handle *h, const char *fn, const void *in, SaInKind kind, void *out, int batch, int out_kind,
+                       void *stream, bool fft, bool hop_word = false)
+{
+    int hop = 0;
+    { const int rc = check_process_args(h, fn, in, kind, out, batch, out_kind, fft ? SaChain::Q15 : SaChain::Q15Filter,
+                                        SA_Q15_OUT_MARKER, "SA_Q15_OUT_MARKER", fft, true, hop_word ? &hop : nullptr, hop_word);
+      if (rc != SA_OK || batch == 0) return rc; }
+    if (hop_word) out_kind &= 0xFF;
+    const bool avg = hop_word && SA_Q15_IS_TRACE_AVG_KIND(out_kind);
+    const Q15Fold fold = {avg ? Q15Fold::Trace : Q15Fold::None, SA_Q15_TRACE_AVG_LOG2W(out_kind), SA_Q15_TRACE_AVG_LOG2A(out_kind)};
+    return launch_q15(h, fn, in, kind, out, batch, out_kind, stream, fft, hop, fold);
+}
+
+// The calls of include/specan_ext.h.  Every refusal comes from sa_ext_check (sa_pointers.cpp) before any call state exists.
+static int ext_q15(sa_handle *h, const char *fn, int entry, const void *in, void *out, int batch, int log2a, int hop, void *stream)
+{
+    if (!h) return SA_EINVAL;
+    SaExtWhy why;
+    SaCallSpan span;
+    const int rc = sa_ext_check(entry, log2a, hop, (uint64_t)(uintptr_t)in, (uint64_t)(uintptr_t)out, batch, &why, &span);
+    if (rc != SA_OK) {
+        char msg[112];
+        const char *what = msg;
+        switch (why) {
+            case kSaExtBatch: what = "negative batch"; break;
+            case kSaExtLog2a: what = "log2a must be 1..7 (groups of A = 2..128 frames)"; break;
+            case kSaExtHop:
+                what = entry == SA_EXT_ENTRY_FOLD_IQ_Q15 ? "the fold takes frames: no hop" : "hop must be 0 or a multiple of 8 in 8..16384";
+                break;
+            case kSaExtGroup: what = "batch must be a multiple of the group size A"; break;
+            case kSaExtNull: what = "NULL tensor"; break;
+            case kSaExtInAlign:
+                what = entry == SA_EXT_ENTRY_SPECTRA_Q15_P12 ? "packed input must be 16-byte aligned"
+                       : hop != 0                            ? "a sample stream must be 16-byte aligned"
+                                                             : "`in` must be 16-byte aligned";
+                break;
+            case kSaExtOutAlign: what = "`out` must be 16-byte aligned"; break;
+            case kSaExtOverlap:
+                std::snprintf(msg, sizeof msg, "`in` (%llu bytes read) and `out` (%llu bytes written) overlap",
+                              (unsigned long long)span.in_bytes, (unsigned long long)span.out_bytes);
+                break;
+            default: what = "bad argument"; break;
+        }
+        return fail_at(h, rc, fn, what);
+    }
+    if (batch == 0) return SA_OK;
+    if (entry != SA_EXT_ENTRY_FOLD_IQ_Q15)
+        return launch_q15(h, fn, in, entry == SA_EXT_ENTRY_SPECTRA_Q15_P12 ? SaInKind::P12 : SaInKind::I16, out, batch, SA_Q15_OUT_IQ,
+                          stream, true, hop, {Q15Fold::Spectra, 0, log2a});
+    SA_HIP(h, hipSetDevice(h->device));                          // the fold alone: one launch, no workspace
+    CallCtx c;
+    { const int rc2 = begin_call(h, (hipStream_t)stream, -1, batch, &c); if (rc2 != SA_OK) return rc2; }
+    SA_HIP(h, sa_launch_spectra_fold_q15(in, out, batch, log2a, c.stream, {c.start, c.stop}));
+    return end_call(h, c);
+}
+
+int sa_ext_version(void) { return SA_EXT_VERSION; }
+
+int sa_spectra_q15(sa_handle *h, const int16_t *in, sa_trace_point_q15 *out, int batch, int log2a, int hop, void *stream)
+{
+    return ext_q15(h, "sa_spectra_q15", SA_EXT_ENTRY_SPECTRA_Q15, in, out, batch, log2a, hop, stream);
+}
+
+int sa_spectra_q15_p12(sa_handle *h, const uint8_t *in, sa_trace_point_q15 *out, int batch, int log2a, int hop, void *stream)
+{
+    return ext_q15(h, "sa_spectra_q15_p12", SA_EXT_ENTRY_SPECTRA_Q15_P12, in, out, batch, log2a, hop, stream);
+}
+
+int sa_fold_iq_q15(sa_handle *h, const int16_t *iq, sa_trace_point_q15 *out, int batch, int log2a, void *stream)
+{
+    return ext_q15(h, "sa_fold_iq_q15", SA_EXT_ENTRY_FOLD_IQ_Q15, iq, out, batch, log2a, 0, stream);
 }
 
 int sa_filter_q15(sa_handle *h, const int16_t *in, int16_t *out_time, int batch, void *stream)

@@ -75,6 +75,23 @@ def trace_of_frames(frames_bytes, bucket: int):
     return np.max([p for p, _, _ in parts], axis=0), exact.astype(np.float32), exact
 
 
+def spectrum_of_frames(frames_bytes):
+    """A group of A = 2, 4, ..., 128 consecutive frames reduced bin by bin, at the full resolution of 16384 bins: ``(peak
+    float32 [16384], power float32 [16384], exact int64 [16384])`` -- the largest of the frames' decoded magnitudes of each bin
+    (max hold), the exact integer sum of re^2 + im^2 over the A frames (at most 2^38) rounded once to float32, and that sum
+    itself.  The power is the sum, not the mean: the mean is power / A, exactly.  The host mirror of one row of
+    sa_spectra_q15 / sa_fold_iq_q15 (include/specan_ext.h); trace_of_frames is the same over buckets of 2..64 bins."""
+    frames_bytes = list(frames_bytes)
+    if len(frames_bytes) not in TRACE_GROUPS:
+        raise ValueError(f"a group is one of {TRACE_GROUPS} frames")
+    peak = np.max([decode_mag_16iq_le(f) for f in frames_bytes], axis=0)
+    exact = np.zeros(FFT_SIZE, np.int64)
+    for f in frames_bytes:
+        re, im = _iq(f)
+        exact += re.astype(np.int64) ** 2 + im.astype(np.int64) ** 2
+    return peak, exact.astype(np.float32), exact
+
+
 def decode_iq_components(frame_bytes: bytes):
     """Same result as gui.py:262-270: (re, im) as float32 arrays."""
     re, im = _iq(frame_bytes)

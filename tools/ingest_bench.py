@@ -20,8 +20,10 @@ n_batches batches each.  Choose n_batches so that a run lasts some tenths of a s
 --hop H --trace W --group A: the stream form alone, with the copy of the result back to pinned host memory behind every call
 on the call's stream: the plain trace at bucket W (traces_q15(x, bucket=W, hop=H): 131072 / W bytes per frame back) against
 the grouped one (group=A: a factor A fewer), alternating as above.
+--hop H --spectra A: the same with the full-resolution spectra over groups of A frames (spectra_q15(x, A, hop=H): 131072 / A
+bytes per frame back) against the grouped trace at bucket W = --trace (default 16) and the same A, a factor 16384 / W fewer.
 usage: ingest_bench.py [batch_frames] [n_batches] [mode] [--events] [--float] [--packed] [--packed-q15]
-                       [--hop H [--rounds R] [--trace W --group A]]"""
+                       [--hop H [--rounds R] [--trace W --group A | --spectra A [--trace W]]]"""
 import os
 import sys
 import time
@@ -146,6 +148,53 @@ def hop_trace_mode(hop, rounds, W, A):
     ch.close()
 
 
+def hop_spectra_mode(hop, rounds, A, W):
+    """--hop H --spectra A: grouped trace at bucket W against full-resolution spectra from the stream, results copied back"""
+    ch = SpectrumChain(0)
+    ch.set_filter_mode(mode)
+    ch.reserve(B)
+    s = np.random.default_rng(0).integers(-2048, 2048, size=(4 * B - 1) * hop + N, dtype=np.int16)
+    s = pack12(s) if PACKED else s
+    blocks = StreamCutter(hop, B, PACKED).push(s)                      # 4 distinct blocks of B frames, reused
+    feeder = DeviceFeeder(0, max_batch=B, packed=PACKED, stream=True)
+    forms = {"trace": N // W, "spectra": N}                             # records per row
+    out = {f: [torch.empty((B // A, p, 2), dtype=torch.float32, device="cuda") for _ in range(2)] for f, p in forms.items()}
+    host = {f: [torch.empty(o.shape, dtype=torch.float32).pin_memory() for o in out[f]] for f in forms}
+
+    def run(form, nb):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for i, xd in enumerate(feeder.feed(blocks[j & 3] for j in range(nb))):
+            if form == "trace":
+                ch.traces_q15(xd, bucket=W, out=out[form][i & 1], hop=hop, group=A)
+            else:
+                ch.spectra_q15(xd, A, out=out[form][i & 1], hop=hop)
+            host[form][i & 1].copy_(out[form][i & 1], non_blocking=True)
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0
+
+    for form in forms:                                                  # warm-up (grows both workspaces)
+        run(form, 4)
+    # the last block fed was blocks[3] into buffer 1 in both forms: the trace's peaks are the spectra's, topped per bucket
+    assert torch.equal(host["trace"][1][..., 0], host["spectra"][1][..., 0].reshape(B // A, N // W, W).amax(2))
+    rate = {form: [] for form in forms}
+    for _ in range(rounds):
+        for form in forms:
+            rate[form].append(NB * B / run(form, NB))
+    print(f"hop {hop} ({'packed 12-bit' if PACKED else 'int16'} samples), batch {B} frames x {NB} batches per run, {rounds} "
+          f"alternating runs, filter mode 0x{mode:02X}, groups of A = {A} frames from the stream, result copied to pinned host "
+          f"memory; a trace run lasts {NB * B / np.median(rate['trace']):.2f} s")
+    for form, p in forms.items():
+        r = np.array(rate[form])
+        back = p * 8 / A
+        print(f"  {form:7s} {'W = ' + str(W) if form == 'trace' else 'all bins'}: {back:6.0f} bytes per frame back; M frames/s per run "
+              f"{' '.join(f'{v / 1e6:.3f}' for v in r)}; median {np.median(r) / 1e6:.3f} (max/min {r.max() / r.min():.3f}) = "
+              f"{np.median(r) * back / 1e9:5.1f} GB/s back, {np.median(r) * blocks[0].size * s.itemsize / B / 1e9:5.1f} GB/s in")
+    ratio = np.array(rate["spectra"]) / np.array(rate["trace"])
+    print(f"  spectra / trace per round: {' '.join(f'{v:.3f}' for v in ratio)}; median {np.median(ratio):.3f}")
+    ch.close()
+
+
 def pure_h2d():
     pin = torch.empty((B, ROW), dtype=IN_DT).pin_memory()
     dev = torch.empty((B, ROW), dtype=IN_DT, device="cuda")
@@ -162,6 +211,9 @@ def pure_h2d():
 if "--hop" in sys.argv:
     if FLOAT:
         sys.exit("--hop is a mode of the integer chain (with --packed-q15 for packed samples)")
+    if "--spectra" in sys.argv:
+        hop_spectra_mode(opt("--hop", N), opt("--rounds", 5), opt("--spectra", 16), opt("--trace", 16))
+        sys.exit(0)
     if "--trace" in sys.argv:
         hop_trace_mode(opt("--hop", N), opt("--rounds", 5), opt("--trace", 16), opt("--group", 16))
         sys.exit(0)
