@@ -40,10 +40,13 @@ FS_HZ = 1_000_000.0             # gui.py:45
 _PRECISIONS = {"f32": SA_PRECISION_F32, "f64": SA_PRECISION_F64_STATE}
 
 
-# C entry point -> (takes scale, takes out_kind): the argument lists of include/specan.h
+# C entry point -> (takes scale, takes out_kind): the argument lists of include/specan.h, `..., batch[, kind], stream`
 _ARGS = {"sa_process_f32": (False, True), "sa_process_f32_i16": (True, True), "sa_process_f32_p12": (True, True),
          "sa_process_q15": (False, False), "sa_process_q15_out": (False, True), "sa_process_q15_p12": (False, True),
          "sa_filter_q15": (False, False), "sa_filter_q15_p12": (False, False)}
+# C entry point -> the ints behind batch: the argument lists of include/specan_ext.h, `..., batch, log2a[, hop], stream` (no
+# scale, no out_kind)
+_EXT_ARGS = {"sa_spectra_q15": ("log2a", "hop"), "sa_spectra_q15_p12": ("log2a", "hop"), "sa_fold_iq_q15": ("log2a",)}
 
 
 class _Chain(NamedTuple):
@@ -54,8 +57,8 @@ class _Chain(NamedTuple):
     inputs: dict    # torch dtype of x -> _form(...); the first dtype stands in the message for an x that is no tensor of a
                     # listed dtype
     streams: dict = {}  # the same for a call with ``hop``: x is ONE 1-D stream, frame b its `row` elements from element
-                        # b * row * hop / 16384 on, and the C code goes out as SA_Q15_HOP_KIND(code, hop).  Empty: the chain
-                        # takes frames only.
+                        # b * row * hop / 16384 on, and the hop goes out inside the kind word, SA_Q15_HOP_KIND(code, hop), or
+                        # as the entry point's own argument (_EXT_ARGS).  Empty: the chain takes frames only.
 
     def output(self, out_kind) -> tuple:
         """(C code, shape of one row, torch dtype, frames per row) of ``out_kind``."""
@@ -71,10 +74,10 @@ class _Chain(NamedTuple):
         return B // per_row
 
 
-def _form(row: int, outputs: dict, name: str, **other) -> tuple:
-    """One input form: (row length of x, {out_kind: (C entry point, takes scale, takes out_kind)}).  The entry point is
-    ``name``, or what ``other`` names for that out_kind."""
-    return row, {k: (other.get(k, name),) + _ARGS[other.get(k, name)] for k in outputs}
+def _form(row, outputs: dict, name: str, **other) -> tuple:
+    """One input form: (row of x -- its length, or its shape as a tuple --, {out_kind: (C entry point, takes scale, takes
+    out_kind)}).  The entry point is ``name``, or what ``other`` names for that out_kind; one of _EXT_ARGS takes neither."""
+    return row, {k: (other.get(k, name),) + _ARGS.get(other.get(k, name), (False, False)) for k in outputs}
 
 
 _HALF = SA_N // 2 + 1
@@ -117,6 +120,13 @@ Q15_TRACE_AVG_CHAIN = _Chain(_TRACE_AVG_OUT, {torch.int16: _form(SA_N, _TRACE_AV
 _WINDOW_OUT = {None: (SA_Q15_OUT_IQ, (SA_N,), torch.int16)}
 Q15_WINDOW_CHAIN = _Chain(_WINDOW_OUT, {torch.int16: _form(SA_N, _WINDOW_OUT, "sa_filter_q15"),
                                         torch.uint8: _form(SA_P12_FRAME_BYTES, _WINDOW_OUT, "sa_filter_q15_p12")})
+# the calls of include/specan_ext.h: one record per bin and group of A frames (spectra_q15), one output per A, named by A;
+# and the fold alone (fold_iq_q15), whose input rows are the IQ frames themselves
+_SPECTRA_OUT = {A: (SA_Q15_OUT_IQ, (SA_N, 2), torch.float32, A) for A in TRACE_GROUPS}
+_SPECTRA_IN = {torch.int16: _form(SA_N, _SPECTRA_OUT, "sa_spectra_q15"),
+               torch.uint8: _form(SA_P12_FRAME_BYTES, _SPECTRA_OUT, "sa_spectra_q15_p12")}
+Q15_SPECTRA_CHAIN = _Chain(_SPECTRA_OUT, _SPECTRA_IN, _SPECTRA_IN)
+Q15_FOLD_CHAIN = _Chain(_SPECTRA_OUT, {torch.int16: _form((SA_N, 2), _SPECTRA_OUT, "sa_fold_iq_q15")})
 
 
 def output_spec(chain: _Chain, out_kind: Optional[str], B: int) -> tuple:
@@ -210,9 +220,9 @@ class SpectrumChain:
     def _stream(self) -> int:
         return torch.cuda.current_stream(self.device).cuda_stream
 
-    def _check_in(self, x: torch.Tensor, dtype: torch.dtype, row: int, hop: Optional[int] = None) -> int:
-        """The number of frames in ``x``: its rows, or with ``hop`` the frames of `row` elements that the 1-D stream holds
-        row * hop / 16384 elements apart."""
+    def _check_in(self, x: torch.Tensor, dtype: torch.dtype, row, hop: Optional[int] = None) -> int:
+        """The number of frames in ``x``: its rows (of length ``row``, or of that shape where it is a tuple), or with ``hop``
+        the frames of `row` elements that the 1-D stream holds row * hop / 16384 elements apart."""
         if not isinstance(x, torch.Tensor) or x.dtype != dtype:
             raise SpecanError(abi.SA_EINVAL, f"input must be a {dtype} tensor")
         if x.device != self.device:
@@ -223,19 +233,20 @@ class SpectrumChain:
                 raise SpecanError(abi.SA_ESHAPE, f"with hop={hop} the input must be a contiguous 1-D stream of "
                                                  f"{row} + k * {step} elements")
             return (x.shape[0] - row) // step + 1
-        if x.dim() != 2 or x.shape[1] != row or not x.is_contiguous():
-            raise SpecanError(abi.SA_ESHAPE, f"input must be a contiguous [B, {row}] tensor")
+        shape = row if isinstance(row, tuple) else (row,)
+        if x.dim() != 1 + len(shape) or tuple(x.shape[1:]) != shape or not x.is_contiguous():
+            raise SpecanError(abi.SA_ESHAPE, f"input must be a contiguous [B, {', '.join(map(str, shape))}] tensor")
         return x.shape[0]
 
     def _process(self, chain: _Chain, x, out, out_kind, scale=None, hop=None):
         """Every process call: ``x`` by its dtype to the chain's entry point for it, into ``out`` (allocated when None).
         ``hop``: ``x`` is one sample stream and the frames are cut from it on the device (the chain's ``streams``)."""
-        code, frame, dt, _ = chain.output(out_kind)
+        code, frame, dt, per_row = chain.output(out_kind)
         forms = chain.inputs
         if hop is not None:
             if isinstance(hop, bool) or not isinstance(hop, (int, np.integer)) or not 8 <= hop <= SA_N or hop % 8:
                 raise SpecanError(abi.SA_EINVAL, "hop must be an int, a multiple of 8 in 8..16384")
-            hop, forms, code = int(hop), chain.streams, abi.SA_Q15_HOP_KIND(code, int(hop))
+            hop, forms = int(hop), chain.streams
         dtype = x.dtype if isinstance(x, torch.Tensor) and x.dtype in forms else next(iter(forms))
         row, calls = forms[dtype]
         B = self._check_in(x, dtype, row, hop)
@@ -245,9 +256,11 @@ class SpectrumChain:
         elif tuple(out.shape) != shape or out.dtype != dt or out.device != self.device or not out.is_contiguous():
             raise SpecanError(abi.SA_ESHAPE, f"out must be a contiguous {dt} tensor of shape {shape}")
         name, takes_scale, takes_kind = calls[out_kind]
-        args = (self._h, x.data_ptr()) + ((float(scale),) if takes_scale else ()) + (out.data_ptr(), B)
-        if takes_kind:
-            args += (code,)
+        if takes_kind:                     # the kind word, which carries the hop
+            tail = (abi.SA_Q15_HOP_KIND(code, hop or 0),)
+        else:                              # nothing, or the ints of _EXT_ARGS
+            tail = tuple({"log2a": per_row.bit_length() - 1, "hop": hop or 0}[k] for k in _EXT_ARGS.get(name, ()))
+        args = (self._h, x.data_ptr()) + ((float(scale),) if takes_scale else ()) + (out.data_ptr(), B) + tail
         self._check(getattr(self._lib, name)(*args, self._stream()))
         self._lend(x, out)
         return out
@@ -514,29 +527,15 @@ class SpectrumChain:
             raise SpecanError(abi.SA_EINVAL, f"bucket must be one of {sorted(_TRACE_OUT)}")
         if group is None:
             return self._process(Q15_TRACE_CHAIN, x, out, int(bucket), hop=hop)
-        if isinstance(group, bool) or not isinstance(group, (int, np.integer)) or int(group) not in TRACE_GROUPS:
-            raise SpecanError(abi.SA_EINVAL, f"group must be one of {TRACE_GROUPS}")
+        self._log2_group(group)
         return self._process(Q15_TRACE_AVG_CHAIN, x, out, (int(bucket), int(group)), hop=hop)
-
-    # The calls of include/specan_ext.h have argument lists of their own (log2a and hop as plain ints, no kind word), so they
-    # have a small call path of their own beside _process: the input forms below, _check_in's checks, _lend's lending.
-    _SPECTRA_IN = {torch.int16: (SA_N, "sa_spectra_q15"), torch.uint8: (SA_P12_FRAME_BYTES, "sa_spectra_q15_p12")}
 
     @staticmethod
     def _log2_group(group) -> int:
+        """The one validation of a ``group`` argument: a of A = 2^a, or SA_EINVAL."""
         if isinstance(group, bool) or not isinstance(group, (int, np.integer)) or int(group) not in TRACE_GROUPS:
             raise SpecanError(abi.SA_EINVAL, f"group must be one of {TRACE_GROUPS}")
         return int(group).bit_length() - 1
-
-    def _spectra_out(self, out, B: int, group: int) -> torch.Tensor:
-        if B % group:
-            raise SpecanError(abi.SA_ESHAPE, f"the batch ({B} frames) must be a multiple of {group}")
-        shape = (B // group, SA_N, 2)
-        if out is None:
-            return torch.empty(shape, dtype=torch.float32, device=self.device)
-        if tuple(out.shape) != shape or out.dtype != torch.float32 or out.device != self.device or not out.is_contiguous():
-            raise SpecanError(abi.SA_ESHAPE, f"out must be a contiguous {torch.float32} tensor of shape {shape}")
-        return out
 
     def spectra_q15(self, x: torch.Tensor, group: int, out: Optional[torch.Tensor] = None,
                     hop: Optional[int] = None) -> torch.Tensor:
@@ -553,35 +552,15 @@ class SpectrumChain:
         per frame, and one more launch that folds it; the workspace is grown by the call itself and never by
         :meth:`reserve`: before capturing such a call into a graph, make one of the same batch outside it (SA_ESTATE
         otherwise).  The pointer contract is that of :meth:`process_q15`, on (B // group) * 131072 bytes written."""
-        a = self._log2_group(group)
-        if hop is not None and (isinstance(hop, bool) or not isinstance(hop, (int, np.integer)) or not 8 <= hop <= SA_N or hop % 8):
-            raise SpecanError(abi.SA_EINVAL, "hop must be an int, a multiple of 8 in 8..16384")
-        forms = self._SPECTRA_IN
-        dtype = x.dtype if isinstance(x, torch.Tensor) and x.dtype in forms else next(iter(forms))
-        row, name = forms[dtype]
-        B = self._check_in(x, dtype, row, None if hop is None else int(hop))
-        out = self._spectra_out(out, B, 1 << a)
-        self._check(getattr(self._lib, name)(self._h, x.data_ptr(), out.data_ptr(), B, a, 0 if hop is None else int(hop),
-                                             self._stream()))
-        self._lend(x, out)
-        return out
+        self._log2_group(group)
+        return self._process(Q15_SPECTRA_CHAIN, x, out, int(group), hop=hop)
 
     def fold_iq_q15(self, iq: torch.Tensor, group: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """The fold of :meth:`spectra_q15` alone, on frames the caller already has: ``iq`` is an int16 [B,16384,2] device
         tensor, the result of ``process_q15(out_kind='iq')`` (include/specan_ext.h, sa_fold_iq_q15); the result is
         [B // group, 16384, 2] float32 as there.  One launch, no workspace: it captures into a graph at any time."""
-        a = self._log2_group(group)
-        if not isinstance(iq, torch.Tensor) or iq.dtype != torch.int16:
-            raise SpecanError(abi.SA_EINVAL, f"input must be a {torch.int16} tensor")
-        if iq.device != self.device:
-            raise SpecanError(abi.SA_EINVAL, f"input must live on {self.device}")
-        if iq.dim() != 3 or tuple(iq.shape[1:]) != (SA_N, 2) or not iq.is_contiguous():
-            raise SpecanError(abi.SA_ESHAPE, f"input must be a contiguous [B, {SA_N}, 2] tensor")
-        B = iq.shape[0]
-        out = self._spectra_out(out, B, 1 << a)
-        self._check(self._lib.sa_fold_iq_q15(self._h, iq.data_ptr(), out.data_ptr(), B, a, self._stream()))
-        self._lend(iq, out)
-        return out
+        self._log2_group(group)
+        return self._process(Q15_FOLD_CHAIN, iq, out, int(group))
 
     def filter_q15(self, x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Window (+ integer IIR) only: the FFT input stream, [B,16384] int16.  ``x`` is [B,16384] int16 or the same

@@ -421,103 +421,51 @@ static SaQ15Params q15_params(const sa_handle *h)
     return p;
 }
 
-// The argument checks of process_q15 and process_float, made before anything else; callers of the ABI see their order.
-// The output kinds of both chains run from 0 to `marker`, the marker records (`marker_name` in the message).
-// `trace`: the entry point also takes the SA_Q15_TRACE_KIND(k) family (the Q15 FFT calls; never the float chain).
-// `grouped`: it also takes SA_Q15_TRACE_AVG_KIND(k, a) -- the two entry points with a kind word alone; a batch that is no
-// multiple of A = 2^a is SA_ESHAPE, after the kind and before the pointers.
-// `scale_finite`: what process_float found of its scale, which is refused between the kind and the empty batch (process_q15
-// has no scale: true).  An empty batch returns SA_OK here, and the caller returns it at once.
-// `hop`: null, or where the entry point's word is a SA_Q15_HOP_KIND: the word is taken apart before anything else, *hop is
-// its hop in samples (0: frames) and the kind checked below is its low byte.  An entry point without one (every float one)
-// sees a word with a hop field as the unknown kind it is there.
-// Last, the pointer contract of include/specan.h: `chain` names the family of outputs, sa_pointers.cpp holds the rule.  The
-// alignment rules that were there before it (marker and trace `out`, packed `in`, a stream `in`) are instances of it and
-// keep their messages; all of this before any call state exists.
-static int check_process_args(sa_handle *h, const char *fn, const void *in, SaInKind kind, const void *out, int batch,
-                              int out_kind, SaChain chain, int marker, const char *marker_name, bool trace, bool scale_finite,
-                              int *hop = nullptr, bool grouped = false)
+// The argument check of every data-plane call is made before anything else and before any call state exists.  The rules,
+// their order and their words are sa_pointers.cpp's (sa_check_call, sa_refusal_text), for the entry points of
+// include/specan.h and of include/specan_ext.h alike; callers of the ABI see that order.  A NULL handle is SA_EINVAL without
+// a message, before the check; an empty batch that passes is SA_OK, and the caller returns it at once.  refused(): a
+// refusal of the check leaves "<entry point>: <words>" in sa_last_error.
+static int refused(sa_handle *h, int entry, const SaChecked &r)
 {
     static_assert((int)SaInKind::F32 == kSaInF32 && (int)SaInKind::I16 == kSaInI16 && (int)SaInKind::P12 == kSaInP12,
                   "sa_pointers.hpp numbers the input forms as SaInKind does");
     static_assert(SA_OUT_MAG_FULL == 0 && SA_Q15_OUT_IQ == 0, "the kinds of both chains are 0 .. marker");
-    int field = 0;
-    bool bad_word = false;
-    if (hop && out_kind >= 0) {                                    // a negative word is the bad kind it always was
-        field = (out_kind >> 8) & 0xFFF;
-        bad_word = (out_kind >> 20) != 0 || field > SA_Q15_HOP_FIELD_MAX;
-        out_kind &= 0xFF;
-    }
-    if (!h) return SA_EINVAL;
-    if (batch < 0) return fail_at(h, SA_ESHAPE, fn, "negative batch");
-    if (bad_word) return fail_at(h, SA_EINVAL, fn, "bad out_kind: hop field above 2048 or bits 20..30 set");
-    const bool is_trace = trace && out_kind >= SA_Q15_TRACE_KIND(SA_Q15_TRACE_LOG2W_MIN) &&
-                          out_kind <= SA_Q15_TRACE_KIND(SA_Q15_TRACE_LOG2W_MAX);
-    const bool is_avg = grouped && out_kind >= 0 && SA_Q15_IS_TRACE_AVG_KIND(out_kind);
-    if (!is_trace && !is_avg && (out_kind < 0 || out_kind > marker)) return fail_at(h, SA_EINVAL, fn, "bad out_kind");
-    if (!scale_finite) return fail_at(h, SA_EINVAL, fn, "scale is not finite");
-    if (batch == 0) return SA_OK;
-    if (is_avg && batch % sa_frames_per_row(chain, out_kind))
-        return fail_at(h, SA_ESHAPE, fn, "SA_Q15_TRACE_AVG_KIND: batch must be a multiple of the group size A");
-    if (!in || !out) return fail_at(h, SA_EINVAL, fn, "NULL tensor");
-    SaCallSpan span;
-    if (!sa_call_span(chain, (int)kind, out_kind, 8 * field, batch, &span)) return fail_at(h, SA_EINVAL, fn, "bad out_kind");
-    const unsigned faults = sa_pointer_faults(span, (uint64_t)(uintptr_t)in, (uint64_t)(uintptr_t)out);
-    char msg[96];
-    if ((out_kind == marker || is_trace || is_avg) && (faults & kSaPtrOutAlign)) {
-        std::snprintf(msg, sizeof msg, "%s output must be 16-byte aligned",
-                      is_avg ? "SA_Q15_TRACE_AVG_KIND" : is_trace ? "SA_Q15_TRACE_KIND" : marker_name);
-        return fail_at(h, SA_EINVAL, fn, msg);
-    }
-    if (faults & kSaPtrInAlign)       // the stage-ins and tile loads issue 16-byte requests; every frame is then aligned (int16
-        return fail_at(h, SA_EINVAL, fn,     // streams: 16 h bytes apart; packed streams need a dword per frame and have it)
-                       kind == SaInKind::P12 ? "packed input must be 16-byte aligned"
-                       : field != 0          ? "a sample stream (SA_Q15_HOP_KIND) must be 16-byte aligned"
-                                             : "`in` must be 16-byte aligned");
-    if (faults & kSaPtrOutAlign) {
-        std::snprintf(msg, sizeof msg, "`out` must be %u-byte aligned", span.out_align);
-        return fail_at(h, SA_EINVAL, fn, msg);
-    }
-    if (faults & kSaPtrOverlap) {
-        std::snprintf(msg, sizeof msg, "`in` (%llu bytes read) and `out` (%llu bytes written) overlap",
-                      (unsigned long long)span.in_bytes, (unsigned long long)span.out_bytes);
-        return fail_at(h, SA_EINVAL, fn, msg);
-    }
-    if (hop) *hop = 8 * field;
-    return SA_OK;
+    static_assert(kSaTraceRawBytes == kSaTraceRawRecord, "sa_pointers.hpp sizes the partial records as the kernels do");
+    char msg[112];
+    sa_refusal_text(entry, r, msg, sizeof msg);
+    return fail_at(h, r.code, sa_entry(entry).name, msg);
 }
 
-// What a Q15 call launches behind its FFT: nothing, the fold of SA_Q15_TRACE_AVG_KIND(k, a)'s partial records
-// (trace_fold_q15.hip), or the bin-by-bin fold of sa_spectra_q15's IQ frames (spectra_fold_q15.hip, include/specan_ext.h).
-// With a fold the FFT launch writes into a workspace of the slot and the fold writes `out`.
-struct Q15Fold {
-    enum What { None, Trace, Spectra } what;
-    int log2w, log2a;
-};
-
-// The launches of a Q15 call whose arguments have passed their checks (batch > 0): sa_filter_q15 (`fft` false: window +
-// integer cascade into `out`, out_kind unused), sa_process_q15 / sa_process_q15_out (`out` per out_kind, SA_Q15_OUT_* or
-// SA_Q15_TRACE_KIND(k): the FFT launch's epilogue makes it; SA_Q15_TRACE_AVG_KIND(k, a): the epilogue's partial records and a
-// fold launch behind it) and sa_spectra_q15 (out_kind SA_Q15_OUT_IQ into a workspace and its fold behind it), on int16 samples
-// or on packed 12-bit samples (`kind`: I16 or P12); `fn` names the entry point.  With a hop, `in` is one stream and whichever
-// launch reads the samples -- the cascade, or the FFT in mode 0xB1 -- is its _hop sibling.  Everything else is the frame call.
-static int launch_q15(sa_handle *h, const char *fn, const void *in, SaInKind kind, void *out, int batch, int out_kind,
-                      void *stream, bool fft, int hop, Q15Fold fold)
+// The launches of a Q15 call of entry point `e` whose arguments have passed their check (batch > 0), as `r` decoded them:
+// sa_filter_q15* (window + integer cascade into `out`, r.kind unused), sa_process_q15* (`out` per r.kind, SA_Q15_OUT_* or
+// SA_Q15_TRACE_KIND(k): the FFT launch's epilogue makes it; SA_Q15_TRACE_AVG_KIND(k, a), r.fold Trace: the epilogue's partial
+// records and a fold launch behind it -- trace_fold_q15.hip), sa_spectra_q15* (r.fold Spectra: r.kind SA_Q15_OUT_IQ into a
+// workspace and its bin-by-bin fold behind it -- spectra_fold_q15.hip, include/specan_ext.h) and sa_fold_iq_q15 (that fold
+// with nothing in front of it: `in` holds the IQ frames), on int16 samples or on packed 12-bit samples.  With a fold behind
+// an FFT, the FFT launch writes into a workspace of the slot and the fold writes `out`.  With a hop, `in` is one stream and
+// whichever launch reads the samples -- the cascade, or the FFT in mode 0xB1 -- is its _hop sibling.  Everything else is the
+// frame call.
+static int launch_q15(sa_handle *h, const SaEntry &e, const void *in, void *out, int batch, void *stream,
+                      const SaChecked &r)
 {
+    const SaInKind kind = e.in_form == kSaInP12 ? SaInKind::P12 : SaInKind::I16;
+    const bool bare = e.in_form == kSaInIQ;                         // the fold alone: nothing in front of it, no workspace
+    const bool fft = e.chain == SaChain::Q15 && !bare;
+    const int out_kind = r.kind, hop = r.hop;
     SA_HIP(h, hipSetDevice(h->device));
     const SaQ15Params p = q15_params(h);
     const bool staged = fft && p.filter != SA_FILTER_NONE;      // cascade into the slot's workspace, then the FFT
     // SA_Q15_TRACE_AVG_KIND(k, a): the FFT launch writes partial records [B, 16384 >> k] into a workspace of its own and one
     // more launch folds them into `out`.  B (16384 >> k) records of kSaTraceRawBytes are ceil(16 B / W) "frames" of the
-    // workspace's one-byte elements.  sa_spectra_q15: the FFT launch writes B IQ frames into a workspace of 4-byte elements.
-    // Grown here, on demand, with the cascade's workspace and before the first launch; never by sa_reserve, which does not
-    // know W and sizes nothing for a call the handle may never make.
-    const bool folded = fold.what != Q15Fold::None;
-    const int work2 = fold.what == Q15Fold::Trace ? sa_handle::kWorkTraceRaw : folded ? sa_handle::kWorkSpectra : -1;
-    const long long frames2 = fold.what == Q15Fold::Trace ? ((long long)batch * kSaTraceRawBytes + (1 << fold.log2w) - 1) >> fold.log2w
-                              : folded                    ? batch
-                                                          : 0;
-    if (frames2 > 0x7FFFFFFF) return fail_at(h, SA_ESHAPE, fn, "SA_Q15_TRACE_AVG_KIND: batch too large for the workspace");
+    // workspace's one-byte elements (an int: sa_check_call refuses a batch past it).  sa_spectra_q15: the FFT launch writes B
+    // IQ frames into a workspace of 4-byte elements.  Grown here, on demand, with the cascade's workspace and before the first
+    // launch; never by sa_reserve, which does not know W and sizes nothing for a call the handle may never make.
+    const bool folded = fft && r.fold != SaFold::None;
+    const int work2 = !folded ? -1 : r.fold == SaFold::Trace ? sa_handle::kWorkTraceRaw : sa_handle::kWorkSpectra;
+    const long long frames2 = !folded                  ? 0
+                              : r.fold == SaFold::Trace ? ((long long)batch * kSaTraceRawBytes + (1 << r.log2w) - 1) >> r.log2w
+                                                        : batch;
     CallCtx c;
     { const int rc = begin_call(h, (hipStream_t)stream, staged ? sa_handle::kWorkQ15 : -1, batch, &c, work2, (int)frames2);
       if (rc != SA_OK) return rc; }
@@ -525,16 +473,19 @@ static int launch_q15(sa_handle *h, const char *fn, const void *in, SaInKind kin
     // what the FFT launch writes, and the event its completion is bound to: the fold launch, where there is one, is the call's last
     void *fft_out = folded ? h->slot[c.slot].work[work2].ptr : out;
     hipEvent_t fft_stop = folded ? nullptr : c.stop;
-    const auto launch_fold = [&]() {
-        return fold.what == Q15Fold::Trace
-                   ? sa_launch_trace_fold_q15(fft_out, out, batch, fold.log2w, fold.log2a, c.stream, {nullptr, c.stop})
-                   : sa_launch_spectra_fold_q15(fft_out, out, batch, fold.log2a, c.stream, {nullptr, c.stop});
+    const auto launch_fold = [&](const void *from, hipEvent_t start) {
+        return r.fold == SaFold::Trace ? sa_launch_trace_fold_q15(from, out, batch, r.log2w, r.log2a, c.stream, {start, c.stop})
+                                       : sa_launch_spectra_fold_q15(from, out, batch, r.log2a, c.stream, {start, c.stop});
     };
+    if (bare) {
+        SA_HIP(h, launch_fold(in, c.start));
+        return end_call(h, c);
+    }
     if (!staged) {
         SA_HIP(h, hop   ? sa_launch_fft_q15_hop(in, kind, hop, fft_out, batch, out_kind, p, t, c.stream, {c.start, fft_stop})
                   : fft ? sa_launch_fft_q15(in, kind, fft_out, batch, out_kind, true, p, t, c.stream, {c.start, fft_stop})
                         : sa_launch_filter_q15(in, kind, (int16_t *)out, batch, p, t, c.stream, {c.start, c.stop}));
-        if (folded) SA_HIP(h, launch_fold());
+        if (folded) SA_HIP(h, launch_fold(fft_out, nullptr));
         return end_call(h, c);
     }
     // The WIDE cascade does not gain from overlapped launches (tools/q15_overlap_modes.py, profiles/r4_q15_helper_waves.txt):
@@ -550,112 +501,68 @@ static int launch_q15(sa_handle *h, const char *fn, const void *in, SaInKind kin
     SA_HIP(h, hop ? sa_launch_filter_q15_hop(in, kind, hop, ws, batch, p, t, c.stream, {c.start, nullptr})
                   : sa_launch_filter_q15(in, kind, ws, batch, p, t, c.stream, {c.start, nullptr}));
     SA_HIP(h, sa_launch_fft_q15(ws, SaInKind::I16, fft_out, batch, out_kind, false, p, t, c.stream, {nullptr, fft_stop}));
-    if (folded) SA_HIP(h, launch_fold());
+    if (folded) SA_HIP(h, launch_fold(fft_out, nullptr));
     return end_call(h, c);
 }
 
-// sa_filter_q15 (`fft` false), sa_process_q15 / sa_process_q15_out and their _p12 siblings: the argument checks, then
-// launch_q15.  `hop_word`: out_kind is a SA_Q15_HOP_KIND (sa_process_q15_out, sa_process_q15_p12).
-static int process_q15(sa_handle *h, const char *fn, const void *in, SaInKind kind, void *out, int batch, int out_kind,
-                       void *stream, bool fft, bool hop_word = false)
+// Every Q15 call, of include/specan.h (`kind_word`: its out_kind where it has one) and of include/specan_ext.h (`log2a`,
+// `hop`): the argument check, then launch_q15 on what the check decoded.  One instance per entry point, so that each of
+// them is the check and, for a call that launches, a jump to the shared launch_q15.
+extern "C++" template <int kEntry>
+static int call_q15(sa_handle *h, const void *in, void *out, int batch, int kind_word, int log2a, int hop, void *stream)
 {
-    int hop = 0;
-    { const int rc = check_process_args(h, fn, in, kind, out, batch, out_kind, fft ? SaChain::Q15 : SaChain::Q15Filter,
-                                        SA_Q15_OUT_MARKER, "SA_Q15_OUT_MARKER", fft, true, hop_word ? &hop : nullptr, hop_word);
-      if (rc != SA_OK || batch == 0) return rc; }
-    if (hop_word) out_kind &= 0xFF;
-    const bool avg = hop_word && SA_Q15_IS_TRACE_AVG_KIND(out_kind);
-    const Q15Fold fold = {avg ? Q15Fold::Trace : Q15Fold::None, SA_Q15_TRACE_AVG_LOG2W(out_kind), SA_Q15_TRACE_AVG_LOG2A(out_kind)};
-    return launch_q15(h, fn, in, kind, out, batch, out_kind, stream, fft, hop, fold);
-}
-
-// The calls of include/specan_ext.h.  Every refusal comes from sa_ext_check (sa_pointers.cpp) before any call state exists.
-static int ext_q15(sa_handle *h, const char *fn, int entry, const void *in, void *out, int batch, int log2a, int hop, void *stream)
-{
+    SaChecked r;
+    const SaCall call = {kEntry, kind_word, log2a, hop, batch, (uint64_t)(uintptr_t)in, (uint64_t)(uintptr_t)out, true};
     if (!h) return SA_EINVAL;
-    SaExtWhy why;
-    SaCallSpan span;
-    const int rc = sa_ext_check(entry, log2a, hop, (uint64_t)(uintptr_t)in, (uint64_t)(uintptr_t)out, batch, &why, &span);
-    if (rc != SA_OK) {
-        char msg[112];
-        const char *what = msg;
-        switch (why) {
-            case kSaExtBatch: what = "negative batch"; break;
-            case kSaExtLog2a: what = "log2a must be 1..7 (groups of A = 2..128 frames)"; break;
-            case kSaExtHop:
-                what = entry == SA_EXT_ENTRY_FOLD_IQ_Q15 ? "the fold takes frames: no hop" : "hop must be 0 or a multiple of 8 in 8..16384";
-                break;
-            case kSaExtGroup: what = "batch must be a multiple of the group size A"; break;
-            case kSaExtNull: what = "NULL tensor"; break;
-            case kSaExtInAlign:
-                what = entry == SA_EXT_ENTRY_SPECTRA_Q15_P12 ? "packed input must be 16-byte aligned"
-                       : hop != 0                            ? "a sample stream must be 16-byte aligned"
-                                                             : "`in` must be 16-byte aligned";
-                break;
-            case kSaExtOutAlign: what = "`out` must be 16-byte aligned"; break;
-            case kSaExtOverlap:
-                std::snprintf(msg, sizeof msg, "`in` (%llu bytes read) and `out` (%llu bytes written) overlap",
-                              (unsigned long long)span.in_bytes, (unsigned long long)span.out_bytes);
-                break;
-            default: what = "bad argument"; break;
-        }
-        return fail_at(h, rc, fn, what);
-    }
+    if (sa_check_call(call, &r) != SA_OK) return refused(h, call.entry, r);
     if (batch == 0) return SA_OK;
-    if (entry != SA_EXT_ENTRY_FOLD_IQ_Q15)
-        return launch_q15(h, fn, in, entry == SA_EXT_ENTRY_SPECTRA_Q15_P12 ? SaInKind::P12 : SaInKind::I16, out, batch, SA_Q15_OUT_IQ,
-                          stream, true, hop, {Q15Fold::Spectra, 0, log2a});
-    SA_HIP(h, hipSetDevice(h->device));                          // the fold alone: one launch, no workspace
-    CallCtx c;
-    { const int rc2 = begin_call(h, (hipStream_t)stream, -1, batch, &c); if (rc2 != SA_OK) return rc2; }
-    SA_HIP(h, sa_launch_spectra_fold_q15(in, out, batch, log2a, c.stream, {c.start, c.stop}));
-    return end_call(h, c);
+    return launch_q15(h, sa_entry(kEntry), in, out, batch, stream, r);
 }
 
 int sa_ext_version(void) { return SA_EXT_VERSION; }
 
 int sa_spectra_q15(sa_handle *h, const int16_t *in, sa_trace_point_q15 *out, int batch, int log2a, int hop, void *stream)
 {
-    return ext_q15(h, "sa_spectra_q15", SA_EXT_ENTRY_SPECTRA_Q15, in, out, batch, log2a, hop, stream);
+    return call_q15<kSaEntryExt + SA_EXT_ENTRY_SPECTRA_Q15>(h, in, out, batch, 0, log2a, hop, stream);
 }
 
 int sa_spectra_q15_p12(sa_handle *h, const uint8_t *in, sa_trace_point_q15 *out, int batch, int log2a, int hop, void *stream)
 {
-    return ext_q15(h, "sa_spectra_q15_p12", SA_EXT_ENTRY_SPECTRA_Q15_P12, in, out, batch, log2a, hop, stream);
+    return call_q15<kSaEntryExt + SA_EXT_ENTRY_SPECTRA_Q15_P12>(h, in, out, batch, 0, log2a, hop, stream);
 }
 
 int sa_fold_iq_q15(sa_handle *h, const int16_t *iq, sa_trace_point_q15 *out, int batch, int log2a, void *stream)
 {
-    return ext_q15(h, "sa_fold_iq_q15", SA_EXT_ENTRY_FOLD_IQ_Q15, iq, out, batch, log2a, 0, stream);
+    return call_q15<kSaEntryExt + SA_EXT_ENTRY_FOLD_IQ_Q15>(h, iq, out, batch, 0, log2a, 0, stream);
 }
 
 int sa_filter_q15(sa_handle *h, const int16_t *in, int16_t *out_time, int batch, void *stream)
 {
-    return process_q15(h, "sa_filter_q15", in, SaInKind::I16, out_time, batch, SA_Q15_OUT_IQ, stream, false);
+    return call_q15<SA_ENTRY_FILTER_Q15>(h, in, out_time, batch, 0, 0, 0, stream);
 }
 
 int sa_process_q15(sa_handle *h, const int16_t *in, int16_t *out_iq, int batch, void *stream)
 {
-    return process_q15(h, "sa_process_q15", in, SaInKind::I16, out_iq, batch, SA_Q15_OUT_IQ, stream, true);
+    return call_q15<SA_ENTRY_PROCESS_Q15>(h, in, out_iq, batch, 0, 0, 0, stream);
 }
 
 int sa_process_q15_out(sa_handle *h, const int16_t *in, void *out, int batch, int out_kind, void *stream)
 {
-    return process_q15(h, "sa_process_q15_out", in, SaInKind::I16, out, batch, out_kind, stream, true, true);
+    return call_q15<SA_ENTRY_PROCESS_Q15_OUT>(h, in, out, batch, out_kind, 0, 0, stream);
 }
 
 int sa_process_q15_p12(sa_handle *h, const uint8_t *in, void *out, int batch, int out_kind, void *stream)
 {
-    return process_q15(h, "sa_process_q15_p12", in, SaInKind::P12, out, batch, out_kind, stream, true, true);
+    return call_q15<SA_ENTRY_PROCESS_Q15_P12>(h, in, out, batch, out_kind, 0, 0, stream);
 }
 
 int sa_filter_q15_p12(sa_handle *h, const uint8_t *in, int16_t *out_time, int batch, void *stream)
 {
-    return process_q15(h, "sa_filter_q15_p12", in, SaInKind::P12, out_time, batch, SA_Q15_OUT_IQ, stream, false);
+    return call_q15<SA_ENTRY_FILTER_Q15_P12>(h, in, out_time, batch, 0, 0, 0, stream);
 }
 
 // sa_process_f32 (float frames), sa_process_f32_i16 (int16 samples times `scale`) and sa_process_f32_p12 (the same
-// samples packed to 12 bits); `fn` names the entry point.
+// samples packed to 12 bits), by `entry`.
 // The float32 path: one launch of the fused chain.  The section coefficients and predictor taps travel by value in the
 // kernel arguments (stream-ordered by construction); the per-lane matrices and the window live in device memory
 // (stream-ordered uploads).
@@ -663,13 +570,16 @@ int sa_filter_q15_p12(sa_handle *h, const uint8_t *in, int16_t *out_time, int ba
 // iir_f64.hip (window + cascade in double, y rounded once) into the slot's workspace, then the bypassed float chain on
 // y with the constant 1/2 window (exact).  SA_OUT_TIME is the first launch alone, into `out`.  Timed as one call: the
 // start event rides on the first kernel, the stop event on the last.
-static int process_float(sa_handle *h, const char *fn, const void *in, SaInKind kind, float scale, void *out, int batch,
-                         int out_kind, void *stream)
+static int process_float(sa_handle *h, int entry, const void *in, float scale, void *out, int batch, int out_kind, void *stream)
 {
     const bool scale_finite = scale == scale && scale - scale == 0.f;
-    { const int rc = check_process_args(h, fn, in, kind, out, batch, out_kind, SaChain::Float, SA_OUT_MARKER, "SA_OUT_MARKER", false,
-                                        scale_finite);
-      if (rc != SA_OK || batch == 0) return rc; }
+    SaChecked r;
+    const SaCall call = {entry, out_kind, 0, 0, batch, (uint64_t)(uintptr_t)in, (uint64_t)(uintptr_t)out, scale_finite};
+    if (!h) return SA_EINVAL;
+    if (sa_check_call(call, &r) != SA_OK) return refused(h, call.entry, r);
+    if (batch == 0) return SA_OK;
+    const char *fn = sa_entry(entry).name;
+    const SaInKind kind = (SaInKind)sa_entry(entry).in_form;
     if (h->filter_mode == SA_FILTER_WIDE)
         return fail_at(h, SA_ESTATE, fn, "filter mode 0xA2 (Q2.14) belongs to the Q15 path; use 0xA1 with sa_load_sos_f32");
     SA_HIP(h, hipSetDevice(h->device));
@@ -700,17 +610,17 @@ static int process_float(sa_handle *h, const char *fn, const void *in, SaInKind 
 
 int sa_process_f32(sa_handle *h, const float *in, void *out, int batch, int out_kind, void *stream)
 {
-    return process_float(h, "sa_process_f32", in, SaInKind::F32, 1.f, out, batch, out_kind, stream);
+    return process_float(h, SA_ENTRY_PROCESS_F32, in, 1.f, out, batch, out_kind, stream);
 }
 
 int sa_process_f32_i16(sa_handle *h, const int16_t *in, float scale, void *out, int batch, int out_kind, void *stream)
 {
-    return process_float(h, "sa_process_f32_i16", in, SaInKind::I16, scale, out, batch, out_kind, stream);
+    return process_float(h, SA_ENTRY_PROCESS_F32_I16, in, scale, out, batch, out_kind, stream);
 }
 
 int sa_process_f32_p12(sa_handle *h, const uint8_t *in, float scale, void *out, int batch, int out_kind, void *stream)
 {
-    return process_float(h, "sa_process_f32_p12", in, SaInKind::P12, scale, out, batch, out_kind, stream);
+    return process_float(h, SA_ENTRY_PROCESS_F32_P12, in, scale, out, batch, out_kind, stream);
 }
 
 int sa_pack_frame(const int16_t *iq_host, uint8_t *frame_bytes)

@@ -1,5 +1,6 @@
 """GPU: the pointer contract of the process and filter calls (include/specan.h, "pointer contract") at the eight entry
-points themselves and through SpectrumChain.
+points themselves and through SpectrumChain, and every refusal of the one argument check (csrc/sa_pointers.cpp) at the eleven
+data-plane entry points of include/specan.h and include/specan_ext.h.
 
 tests/test_pointer_contract_cpu.py pins the rule (alignment, byte counts, the interval test) without a GPU.  Here: a refused
 call launches nothing and leaves no trace on the handle; buffers that touch and row slices of the half layouts, which the
@@ -253,3 +254,126 @@ def test_wrapper_surfaces_the_refusals(ch, torch_mod):
     assert torch.equal(xf, keep_f) and torch.equal(xi, keep_i)
     assert torch.equal(ch.process_f32(xf), ref_f) and torch.equal(ch.process_q15(xi), ref_q)
     assert torch.equal(ch.filter_q15(xi), ref_t)
+
+
+# ---- every entry point is wired to the one argument check (sa_check_call, csrc/sa_pointers.cpp)
+SA_ESHAPE = -2
+AVG, TRACE = 0x80 | 2 << 3 | 4, 0x10 | 4                    # SA_Q15_TRACE_AVG_KIND(4, 2): A = 4; SA_Q15_TRACE_KIND(4)
+HOPW = (4096 // 8) << 8                                     # the hop field of SA_Q15_HOP_KIND(kind, 4096)
+# entry point -> (input form, (bytes read, bytes written) of the plain call on 4 frames -- the ext calls: groups of A = 4)
+WIRED = {
+    "sa_process_f32": ("f32", (262144, 262144)), "sa_process_f32_i16": ("i16", (131072, 262144)),
+    "sa_process_f32_p12": ("p12", (98304, 262144)), "sa_process_q15": ("i16", (131072, 262144)),
+    "sa_process_q15_out": ("i16", (131072, 262144)), "sa_process_q15_p12": ("p12", (98304, 262144)),
+    "sa_filter_q15": ("i16", (131072, 131072)), "sa_filter_q15_p12": ("p12", (98304, 131072)),
+    "sa_spectra_q15": ("i16", (131072, 131072)), "sa_spectra_q15_p12": ("p12", (98304, 131072)),
+    "sa_fold_iq_q15": ("iq", (262144, 131072)),
+}
+
+
+def wired_refusals(name, IN, OUT):
+    """(words of sa_last_error behind the entry point's name, code, arguments that differ from the good call) for each rule
+    that `name` can reach through its C argument list with addresses inside one allocation: all but the workspace rule, whose
+    batch no allocation holds (tests/cpp/test_sa_call_check.cpp has it).  The words are written out here."""
+    form, (n_in, n_out) = WIRED[name]
+    in_words = "packed input must be 16-byte aligned" if form == "p12" else "`in` must be 16-byte aligned"
+    off = {"f32": 4, "i16": 2, "p12": 1, "iq": 4}[form]
+    r = [("negative batch", SA_ESHAPE, dict(batch=-1)),
+         ("NULL tensor", SA_EINVAL, dict(a_in=0)),
+         ("NULL tensor", SA_EINVAL, dict(a_out=0)),
+         (in_words, SA_EINVAL, dict(a_in=IN + off)),
+         ("`out` must be 16-byte aligned", SA_EINVAL, dict(a_out=OUT + 8)),
+         (f"`in` ({n_in} bytes read) and `out` ({n_out} bytes written) overlap", SA_EINVAL, dict(a_out=IN))]
+    if name.startswith("sa_process_f32"):
+        r += [("bad out_kind", SA_EINVAL, dict(word=5)),
+              ("bad out_kind", SA_EINVAL, dict(word=5, batch=0)),
+              ("`out` must be 4-byte aligned", SA_EINVAL, dict(word=1, a_out=OUT + 2)),
+              ("`out` must be 8-byte aligned", SA_EINVAL, dict(word=2, a_out=OUT + 4)),
+              ("SA_OUT_MARKER output must be 16-byte aligned", SA_EINVAL, dict(word=4, a_out=OUT + 8)),
+              ("SA_OUT_MARKER output must be 16-byte aligned", SA_EINVAL, dict(word=4, a_in=IN + off, a_out=OUT + 8)),
+              (in_words, SA_EINVAL, dict(word=0, a_in=IN + off, a_out=OUT + 8))]
+        if name != "sa_process_f32":
+            r += [("scale is not finite", None, dict(scale=float("nan"))),           # the export has no scale: the code below
+                  ("scale is not finite", None, dict(scale=float("inf"), batch=0)),
+                  ("bad out_kind", SA_EINVAL, dict(word=5, scale=float("nan")))]
+    if name in ("sa_process_q15_out", "sa_process_q15_p12"):
+        stream = "packed input must be 16-byte aligned" if form == "p12" else "a sample stream (SA_Q15_HOP_KIND) must be 16-byte aligned"
+        r += [("bad out_kind: hop field above 2048 or bits 20..30 set", SA_EINVAL, dict(word=0 | 2049 << 8)),
+              ("bad out_kind: hop field above 2048 or bits 20..30 set", SA_EINVAL, dict(word=3 | 1 << 20, batch=0)),
+              ("bad out_kind", SA_EINVAL, dict(word=3)),
+              ("bad out_kind", SA_EINVAL, dict(word=0x88, batch=0)),
+              ("SA_Q15_TRACE_AVG_KIND: batch must be a multiple of the group size A", SA_ESHAPE, dict(word=AVG, batch=5)),
+              ("SA_Q15_TRACE_AVG_KIND: batch must be a multiple of the group size A", SA_ESHAPE, dict(word=AVG | HOPW, batch=5, a_in=0)),
+              (stream, SA_EINVAL, dict(word=0 | HOPW, a_in=IN + off)),
+              ("SA_Q15_OUT_MARKER output must be 16-byte aligned", SA_EINVAL, dict(word=2, a_out=OUT + 8)),
+              ("SA_Q15_TRACE_KIND output must be 16-byte aligned", SA_EINVAL, dict(word=TRACE, a_out=OUT + 8)),
+              ("SA_Q15_TRACE_AVG_KIND output must be 16-byte aligned", SA_EINVAL, dict(word=AVG | HOPW, a_out=OUT + 8)),
+              ("SA_Q15_OUT_MARKER output must be 16-byte aligned", SA_EINVAL, dict(word=2, a_in=IN + off, a_out=OUT + 8)),
+              (in_words, SA_EINVAL, dict(word=1, a_in=IN + off, a_out=OUT + 8))]
+    if name.startswith("sa_spectra") or name == "sa_fold_iq_q15":
+        r += [("log2a must be 1..7 (groups of A = 2..128 frames)", SA_EINVAL, dict(log2a=0)),
+              ("log2a must be 1..7 (groups of A = 2..128 frames)", SA_EINVAL, dict(log2a=8, batch=0)),
+              ("negative batch", SA_ESHAPE, dict(log2a=0, batch=-1)),
+              ("batch must be a multiple of the group size A", SA_ESHAPE, dict(batch=5)),
+              ("batch must be a multiple of the group size A", SA_ESHAPE, dict(batch=5, a_in=0, a_out=0))]
+    if name.startswith("sa_spectra"):                       # the C argument list of the fold has no hop to refuse
+        stream = "packed input must be 16-byte aligned" if form == "p12" else "a sample stream must be 16-byte aligned"
+        r += [("hop must be 0 or a multiple of 8 in 8..16384", SA_EINVAL, dict(hop=4)),
+              ("hop must be 0 or a multiple of 8 in 8..16384", SA_EINVAL, dict(hop=16392, batch=0)),
+              (stream, SA_EINVAL, dict(hop=4096, a_in=IN + off))]
+    return r
+
+
+def test_every_entry_point_runs_the_one_check(ch, torch_mod):
+    """For each of the eleven C entry points and each rule it can reach: the code is the one the handle-free export gives for
+    the same arguments, sa_last_error is the entry point's name and the rule's words, nothing is written and nothing timed.
+    Every address lies inside one canary-filled allocation that holds both ranges of any of these calls; a misaligned or
+    overlapping pair only ever goes to a call that must refuse it.  Before that, the one accepted call whose host path is
+    new: the fold alone gives the bits of spectra_q15 on the same frames."""
+    from fpga_real_time_fft_analyzer_amd import abi
+    torch = torch_mod
+    L = ch._lib
+    stream = torch.cuda.current_stream().cuda_stream
+    ch.set_filter_mode(0x00)
+    x = to_device(torch, host_inputs()["i16"][:4])
+    want = ch.spectra_q15(x, 2)
+    got = ch.fold_iq_q15(ch.process_q15(x, out_kind="iq"), 2)
+    torch.cuda.synchronize()
+    assert got.shape == (2, N, 2) and torch.equal(got.view(torch.int32), want.view(torch.int32)) and want.any().item()
+
+    half = 1 << 20
+    raw = torch.full((PAD + 2 * half,), CANARY, dtype=torch.uint8, device="cuda")
+    IN = raw.data_ptr() + PAD
+    OUT = IN + half
+    assert IN % 16 == 0 and 5 * 65544 + 16 < half - PAD
+    ch.set_profiling(8)
+    timed = len(ch.profile_read(8))
+    assert list(WIRED) == list(abi.SA_ENTRIES) + list(abi.SA_EXT_ENTRIES)
+    for entry, name in enumerate(WIRED):
+        ext = entry >= 8
+        fn = getattr(L, name)
+        for words, code, change in wired_refusals(name, IN, OUT):
+            a = dict(a_in=IN, a_out=OUT, batch=4, word=0, log2a=2, hop=0, scale=1.0 / 2048.0)
+            a.update(change)
+            tag = (name, words, change)
+            if ext:
+                exported = L.sa_ext_check_pointers(entry - 8, a["log2a"], a["hop"], a["a_in"], a["a_out"], a["batch"])
+                tail = (a["log2a"],) + ((a["hop"],) if name != "sa_fold_iq_q15" else ())
+            else:
+                exported = L.sa_debug_check_pointers(entry, a["word"], a["a_in"], a["a_out"], a["batch"])
+                tail = (a["word"],) if ENTRIES[name][2] else ()
+            if code is None:                                # a scale that is not finite: the export has no scale to refuse
+                assert exported == SA_OK, tag
+                exported = SA_EINVAL
+            else:
+                assert exported == code, tag                # what this file expects of the export, written out
+            head = (a["a_in"],) + ((a["scale"],) if not ext and ENTRIES[name][1] else ()) + (a["a_out"], a["batch"])
+            rc = fn(ch._h, *head, *tail, stream)
+            assert rc == exported, tag + (rc,)
+            assert L.sa_last_error(ch._h).decode() == name + ": " + words, tag
+            assert fn(None, *head, *tail, stream) == SA_EINVAL, tag                       # no handle: no message either
+    torch.cuda.synchronize()
+    assert (raw == CANARY).all().item()                     # nothing was launched
+    assert len(ch.profile_read(8)) == timed                 # no refused call was timed
+    ch.set_profiling(0)
+    assert torch.equal(ch.spectra_q15(x, 2), want)          # the handle goes on

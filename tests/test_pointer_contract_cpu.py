@@ -6,8 +6,9 @@ What a call must answer is written here, from the words of the contract, and nev
   - [in, in + in_bytes) and [out, out + out_bytes) are disjoint; touching is fine;
   - in_bytes = B * 65536 (float32), B * 32768 (int16), B * 24576 (packed); with a hop H ((B - 1) H + 16384) * 2, packed three
     quarters of that; out_bytes = B rows of the kind.
-The same rule decides inside every entry point (check_process_args calls the same functions); tests/test_gpu_pointer_contract.py
-holds the entry points to it on the device, and tests/cpp/test_sa_pointers.cpp runs the unit under the host sanitizers."""
+The export returns the code of sa_check_call (csrc/sa_pointers.cpp), the one check every entry point runs before anything
+else; tests/test_gpu_pointer_contract.py holds the entry points to it on the device, and tests/cpp/test_sa_pointers.cpp and
+tests/cpp/test_sa_call_check.cpp run the unit under the host sanitizers."""
 import os
 import shutil
 import subprocess
@@ -219,9 +220,21 @@ def test_empty_batch_and_bad_arguments(check):
 def test_standalone_program_under_host_sanitizers(tmp_path):
     """tests/cpp/test_sa_pointers.cpp + csrc/sa_pointers.cpp, host only, with -fsanitize=address,undefined when that links
     here (a plain build otherwise: the program's own checks still run)."""
+    run_standalone(tmp_path, "test_sa_pointers")
+
+
+def test_standalone_call_check_under_host_sanitizers(tmp_path):
+    """tests/cpp/test_sa_call_check.cpp + csrc/sa_pointers.cpp, built and run the same way: for each of the eleven entry
+    points every rule it can reach -- code, rule and the words of sa_last_error -- the order of the rules, what the check
+    decodes from an accepted call, and both exports against the check."""
+    assert run_standalone(tmp_path, "test_sa_call_check") > 600
+
+
+def run_standalone(tmp_path, name):
+    """Builds tests/cpp/<name>.cpp with csrc/sa_pointers.cpp and runs it; returns the number of checks it reports."""
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    exe = str(tmp_path / "test_sa_pointers")
-    srcs = [os.path.join(ROOT, "tests", "cpp", "test_sa_pointers.cpp"),
+    exe = str(tmp_path / name)
+    srcs = [os.path.join(ROOT, "tests", "cpp", name + ".cpp"),
             os.path.join(ROOT, "fpga_real_time_fft_analyzer_amd", "csrc", "sa_pointers.cpp")]
     base = [hipcc, "-O1", "-g", "-std=c++17", "--offload-host-only", "-x", "hip", *srcs, "-o", exe]
     r = subprocess.run(base + ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"],
@@ -233,3 +246,4 @@ def test_standalone_program_under_host_sanitizers(tmp_path):
     print("sanitizers:", "address,undefined" if sanitized else "did not link here: plain build")
     r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0 and r.stdout.startswith("ok "), r.stdout + r.stderr
+    return int(r.stdout.split()[1])
