@@ -8,9 +8,19 @@ cancels it arithmetically passes them all: 0 * x = 0 for finite garbage.  Here t
   - tests/hip/lds_fill.hip (built by the fixture below, loaded with ctypes; not part of the library) writes one 32-bit
     word to all 160 KiB of LDS of every CU, and probes, without writing, what a later dispatch finds there.
   - (a) float chain, (b) integer chain: lds_fill(P) then the call on the same stream.  The float chain must give the
-    bits it gives after lds_fill(0), all finite; the integer chain the bits of the integer model (oracle.chain_q15).
-    Victim batches are small enough that each of their workgroups is the first on its LDS slot.  Each test pins the set
-    of kernel variants it launched, read from the handle's state (exported plan, precision, batch, input type).
+    bits it gives after lds_fill(0), all finite; the integer chain the bits of the integer model (oracle.chain_q15) and of
+    the numpy mirrors of its output kinds (q15_mirrors.py).  Victim batches are small enough that each of their workgroups
+    is the first on its LDS slot.  Each test pins the set of kernel variants it launched, read from the handle's state
+    (exported plan, precision, coefficient bytes, batch, input type, hop); kernel_inventory.py turns a variant into the
+    names of the kernel instantiations it launches, and test_kernel_inventory_is_classified (CPU) holds the union of the
+    pinned sets to the symbol table of the built library: a kernel form added to the library fails the CPU suite until a
+    case here poisons it.
+  - What the poison reaches in a call of more than one launch.  lds_fill precedes the FIRST kernel only.  A second
+    kernel (fft_q15_kernel<false, OUT> behind a cascade, the bypassed float chain behind iir_f64_kernel, a fold) meets the
+    poison on every CU the first kernel's few workgroups did not occupy -- at B = 17 the cascade has 2 workgroups and the
+    FFT 17, so 15 FFT workgroups at least start on untouched, fully poisoned LDS -- and on the others it meets poison in
+    the part of its 64 KiB that the cascade's 33-50 KiB did not overwrite, and the cascade's residue (finite samples) in
+    the rest.  Nothing here steers the dispatcher: which workgroup lands where is the hardware's choice.
   - (c) non-finite neighbours: every third frame of a batch holds a NaN, an Inf or overflows |X|^2; the other frames
     must be bit-identical to the same frames run as a clean-only batch, and finite.  Nothing is asserted about the bad
     frames except the shape of their rows.
@@ -25,6 +35,8 @@ import pytest
 
 from conftest import N, ROOT, load_golden
 from gpu_support import ch, table_window, to_device, torch_mod  # noqa: F401 (fixtures)
+from kernel_inventory import (NO_LDS_UNITS, TABLE, float_kernels, inventory, lds_of, lds_remarks, q15_kernels, unit_text)
+from q15_mirrors import bits, decode, marker_expect, spectra_expect, trace_expect
 from structured_cases import cascades, plan_header
 
 HELPER_SRC = os.path.join(ROOT, "tests", "hip", "lds_fill.hip")
@@ -123,12 +135,12 @@ def _frames_f32(B, seed):
     return x.astype(np.float32)
 
 
-def _frames_i16(B, seed, amp=2048):
+def _frames_i16(B, seed, amp=2048, full_scale_last=True):
     rng = np.random.default_rng(seed)
     x = rng.integers(-amp, amp, (B, N))
     x[:2] = 0
     x[0, 0] = amp - 1
-    if B > 2:
+    if B > 2 and full_scale_last:
         x[-1] = rng.integers(-32768, 32768, N)            # one full-scale frame
     return x.astype(np.int16)
 
@@ -159,6 +171,14 @@ def _bits_equal(a, b):
     return a.shape == b.shape and a.dtype == b.dtype and np.ascontiguousarray(a).tobytes() == np.ascontiguousarray(b).tobytes()
 
 
+def _rows_differing(a, b):
+    """The rows in which two outputs of one shape and dtype differ in any byte; the shapes and dtypes where those differ."""
+    if a.shape != b.shape or a.dtype != b.dtype:
+        return (a.shape, a.dtype, b.shape, b.dtype)
+    rows = lambda x: np.ascontiguousarray(x).view(np.uint8).reshape(x.shape[0], -1)     # noqa: E731
+    return np.flatnonzero((rows(a) != rows(b)).any(axis=1)).tolist()
+
+
 def _after_fill(torch_mod, lds, word, call):
     """lds_fill(word), then `call` on the same stream, with nothing else in flight; the result on the host."""
     torch_mod.cuda.synchronize()
@@ -179,36 +199,57 @@ def _launched_f32(ch, x, kind):
     if ch.precision == "f64" and nsec > 0:
         return (in_t, nsec, 0, 0, kind != "time" and x.shape[0] <= 512, kind, "f64")
     one_round = nsec == 0 and in_t == "float32" and kind != "time" and x.shape[0] <= 512
-    return (in_t, nsec, unit, wingen if nsec else 0, one_round, kind, "f32")
+    return (in_t, nsec, unit, wingen if nsec and kind != "time" else 0, one_round, kind, "f32")      # time_f32_kernel has no WINGEN
 
 
 def _variants(in_ts, nsec_unit, wingens, one_rounds, precision):
-    """The tuples of _launched_f32 for every out kind; 'time' has no one-round form."""
-    return {(t, ns, u, w, o and k != "time", k, precision)
+    """The tuples of _launched_f32 for every out kind; 'time' has no one-round form and no window generator.  Each
+    tuple stands for the kernel instantiations kernel_inventory.float_kernels names, one to one."""
+    return {(t, ns, u, w if k != "time" else 0, o and k != "time", k, precision)
             for t in in_ts for ns, u in nsec_unit for w in wingens for o in one_rounds for k in KINDS}
 
 
-CASCADE_NSEC_UNIT = {(6, 1), (6, 0), (2, 1), (2, 0), (4, 0)}
+CASCADE_NSEC_UNIT = {(6, 1), (6, 0), (2, 1), (2, 0), (4, 0), (4, 1)}
+INPUTS = ("float32", "int16", "uint8")        # uint8: the int16 samples packed to 12 bits, [B, 24576] (ingest.pack12)
+
+
+def local_cascades():
+    """Cascades of this module alone (structured_cases.cascades() and its EXPECTED tables stay as they are): an 8th-order
+    Butterworth low-pass plans to four sections, none padded, in the unit-numerator form -- the (4, 1) kernels, which no
+    cascade of structured_cases reaches.  The test asserts the plan's header where it loads it."""
+    from scipy import signal
+    return {"butter8_unit4": signal.butter(8, 0.1, output="sos")}
+
+
+LOCAL_PLANS = {"butter8_unit4": (4, 1)}
+
+
+def _cascade_names():
+    return list(cascades()) + list(local_cascades())
+
+
+def _cascade_group(in_t):
+    return ([(f"{n}_{w}", 0xA1, n, w, "f32") for n in _cascade_names() for w in ("cos", "table")], [(in_t, 24)],
+            _variants((in_t,), CASCADE_NSEC_UNIT, (0, 1), (False,), "f32"))
+
+
 F64_CASCADES = ("long_memory", "butter5_padded", "butter12", "rtl_default")     # padded nsec 2, 4, 6, 6
 
 # group -> (configurations: (label, filter mode, cascade name or None, window, precision), inputs: (dtype, B), variants)
 FLOAT_GROUPS = {
     "bypass": ([("bypass", 0xB1, None, "cos", "f32")],
-               [("float32", 200), ("float32", 520), ("int16", 200), ("int16", 520)],
+               [(t, B) for t in INPUTS for B in (200, 520)],
                _variants(("float32",), {(0, 0)}, (0,), (True, False), "f32")
-               | _variants(("int16",), {(0, 0)}, (0,), (False,), "f32")),
+               | _variants(("int16", "uint8"), {(0, 0)}, (0,), (False,), "f32")),
     "defaults": ([("default_" + w, 0x00, None, w, "f32") for w in ("cos", "table")],
-                 [("float32", 24), ("int16", 24)],
-                 _variants(("float32", "int16"), {(6, 0)}, (0, 1), (False,), "f32")),
-    "cascades_float32": ([(f"{n}_{w}", 0xA1, n, w, "f32") for n in cascades() for w in ("cos", "table")],
-                         [("float32", 24)],
-                         _variants(("float32",), CASCADE_NSEC_UNIT, (0, 1), (False,), "f32")),
-    "cascades_int16": ([(f"{n}_{w}", 0xA1, n, w, "f32") for n in cascades() for w in ("cos", "table")],
-                       [("int16", 24)],
-                       _variants(("int16",), CASCADE_NSEC_UNIT, (0, 1), (False,), "f32")),
+                 [(t, 24) for t in INPUTS],
+                 _variants(INPUTS, {(6, 0)}, (0, 1), (False,), "f32")),
+    "cascades_float32": _cascade_group("float32"),
+    "cascades_int16": _cascade_group("int16"),
+    "cascades_uint8": _cascade_group("uint8"),
     "f64": ([(n + "_f64", 0xA1, n, "cos", "f64") for n in F64_CASCADES] + [("default_f64", 0x00, None, "cos", "f64")],
-            [("float32", 24), ("int16", 24)],
-            _variants(("float32", "int16"), {(2, 0), (4, 0), (6, 0)}, (0,), (True,), "f64")),
+            [(t, 24) for t in INPUTS],
+            _variants(INPUTS, {(2, 0), (4, 0), (6, 0)}, (0,), (True,), "f64")),
 }
 
 
@@ -217,10 +258,27 @@ def _configure(ch, mode, casc, window, precision):
     ch.set_window_f32(None if window == "cos" else table_window())
     if casc == "smoother_f32":
         ch.load_sos_f32(cascades()[casc])
+    elif casc in LOCAL_PLANS:
+        ch.load_sos(local_cascades()[casc])
+        got = plan_header(ch.iir_plan())[:2]
+        assert got == LOCAL_PLANS[casc], f"{casc} plans to (nsec, unit) = {got}, not {LOCAL_PLANS[casc]}: its kernels go unreached"
     elif casc is not None:
         ch.load_sos(cascades()[casc])
     ch.set_filter_mode(mode)
     ch.set_precision(precision)
+
+
+def _float_input(torch_mod, in_t, B):
+    """(x on the device, keyword arguments, the int16 tensor of the same samples for a packed x or None).  Packed frames
+    hold 12-bit samples: _frames_i16 at amp 2048 without its full-scale last frame."""
+    from fpga_real_time_fft_analyzer_amd.ingest import pack12
+    if in_t == "float32":
+        return to_device(torch_mod, _frames_f32(B, B)), {}, None
+    if in_t == "int16":
+        return to_device(torch_mod, _frames_i16(B, B)), {"scale": I16_SCALE}, None
+    x = _frames_i16(B, B, amp=2048, full_scale_last=False)
+    assert x.min() >= -2048 and x.max() <= 2047
+    return to_device(torch_mod, pack12(x)), {"scale": I16_SCALE}, to_device(torch_mod, x)
 
 
 @pytest.mark.gpu
@@ -228,15 +286,15 @@ def _configure(ch, mode, casc, window, precision):
 def test_poisoned_lds_float_chain(ch, torch_mod, lds, group):
     """(a) lds_fill(P) then process_f32, for P = NaN / +Inf words, against the same call after lds_fill(0): bit for bit,
     and every output finite.  Every out kind (the marker over the full range and over [9000, 12001)); the group's
-    configurations and batches reach exactly the variant set the group pins (see FLOAT_GROUPS)."""
+    configurations and batches reach exactly the variant set the group pins (see FLOAT_GROUPS).  A packed input (uint8)
+    must also give, after each poison word, the bits of the int16 call on the same samples after lds_fill(0): the
+    contract of tests/test_gpu_p12.py, held where a stale word could break it."""
     configs, inputs, want = FLOAT_GROUPS[group]
     reached, bad, worst, n_calls = set(), [], 0.0, 0
     for label, mode, casc, window, precision in configs:
         _configure(ch, mode, casc, window, precision)
         for in_t, B in inputs:
-            x = _frames_f32(B, B) if in_t == "float32" else _frames_i16(B, B)
-            xd = to_device(torch_mod, x)
-            kw = {"scale": I16_SCALE} if in_t == "int16" else {}
+            xd, kw, twin = _float_input(torch_mod, in_t, B)
             for kind, rng in KIND_RUNS:
                 if rng is not None:
                     ch.set_marker_range(*rng)
@@ -245,6 +303,7 @@ def test_poisoned_lds_float_chain(ch, torch_mod, lds, group):
                 ref = _after_fill(torch_mod, lds, 0, call)
                 if not _all_finite(kind, ref):
                     bad.append((label, in_t, B, kind, rng, "after fill 0", "non-finite"))
+                same = None if twin is None else _after_fill(torch_mod, lds, 0, lambda: ch.process_f32(twin, out_kind=kind, **kw))
                 for word in FLOAT_POISON:
                     got = _after_fill(torch_mod, lds, word, call)
                     n_calls += 1
@@ -254,6 +313,10 @@ def test_poisoned_lds_float_chain(ch, torch_mod, lds, group):
                         rows = int(np.count_nonzero((got != ref).reshape(B, -1).any(axis=1)))
                         bad.append((label, in_t, B, kind, rng, f"0x{word:08X}", f"{rows} rows differ, worst |d| {d:.3g}",
                                     "finite" if _all_finite(kind, got) else "NON-FINITE"))
+                    if same is not None and not _bits_equal(got, same):
+                        rows = int(np.count_nonzero((got != same).reshape(B, -1).any(axis=1)))
+                        bad.append((label, in_t, B, kind, rng, f"0x{word:08X}", f"{rows} rows differ from the int16 call on "
+                                    f"the same samples, worst |d| {_worst_delta(kind, got, same):.3g}"))
     ch.set_marker_range(0, N)
     print(f"FIGURE poisoned float {group}: {n_calls} poisoned calls, {len(reached)} variants, worst |d| {worst:.3g}")
     assert not bad, "\n".join(map(str, bad[:10]))
@@ -261,82 +324,272 @@ def test_poisoned_lds_float_chain(ch, torch_mod, lds, group):
 
 
 def test_float_poison_groups_cover_every_form():
-    """CPU: the union of the variant sets pinned by test_poisoned_lds_float_chain covers both input types, padded
-    section counts 0/2/4/6, both numerator forms, both window forms, the one- and two-round bypass, every out kind and
-    both precisions, and the float64-state path at nsec 2, 4 and 6 on both inputs."""
+    """CPU: the union of the variant sets pinned by test_poisoned_lds_float_chain covers the three input types, padded
+    section counts 0/2/4/6 in both numerator forms -- (4, 1) included -- on every input type, both window forms, the one-
+    and two-round bypass, every out kind and both precisions, and the float64-state path at nsec 2, 4 and 6 on every
+    input."""
     allv = set().union(*(g[2] for g in FLOAT_GROUPS.values()))
-    assert {v[0] for v in allv} == {"float32", "int16"}
+    assert {v[0] for v in allv} == {"float32", "int16", "uint8"}
     assert {v[1] for v in allv} == {0, 2, 4, 6}
     assert {v[2] for v in allv if v[6] == "f32" and v[1]} == {0, 1}
+    assert ({(v[0], v[1], v[2]) for v in allv if v[6] == "f32" and v[1]}
+            == {(t, n, u) for t in INPUTS for n in (2, 4, 6) for u in (0, 1)})
     assert {v[3] for v in allv if v[6] == "f32" and v[1]} == {0, 1}
     assert {v[4] for v in allv if v[0] == "float32" and v[1] == 0} == {True, False}
+    assert {v[4] for v in allv if v[0] != "float32" and v[6] == "f32"} == {False}       # the one-round form is float32 only
     assert {v[5] for v in allv} == set(KINDS)
-    assert {(v[0], v[1]) for v in allv if v[6] == "f64"} == {(t, n) for t in ("float32", "int16") for n in (2, 4, 6)}
+    assert {(v[0], v[1]) for v in allv if v[6] == "f64"} == {(t, n) for t in INPUTS for n in (2, 4, 6)}
 
 
 # ------------------------------------------------------------------------------------- (b) integer chain, poisoned
 C12_B1 = np.array([0, 1, 0, 64, -67, 19, 64, 127, 64, 64, -85, 40], np.int8)          # B1 != 0: the long step
 C12_NOB1 = np.array([32, 0, -32, 64, -67, 19, 64, 0, 64, 64, -85, 40], np.int8)       # B1 = 0 in both sets
 
-# label -> (filter mode, Q7 upload, Q2.14 sections, kernels of filter_q15, kernels of process_q15)
+# label -> (filter mode, Q7 upload, Q2.14 sections, the cascade kernel: stem and template arguments, None = no cascade)
 Q15_CASES = {
-    "bypass": (0xB1, None, 0, ("window_q15",), ("fft_q15<true>",)),
-    "default": (0x00, None, 0, ("filter_q7<true>",), ("filter_q7<true>", "fft_q15<false>")),
-    "custom_nob1": (0xA1, C12_NOB1, 0, ("filter_q7<true>",), ("filter_q7<true>", "fft_q15<false>")),
-    "custom_b1": (0xA1, C12_B1, 0, ("filter_q7<false>",), ("filter_q7<false>", "fft_q15<false>")),
-    "wide1": (0xA2, None, 1, ("filter_w14/1",), ("filter_w14/1", "fft_q15<false>")),
-    "wide3": (0xA2, None, 3, ("filter_w14/3",), ("filter_w14/3", "fft_q15<false>")),
-    "wide6": (0xA2, None, 6, ("filter_w14/6",), ("filter_w14/6", "fft_q15<false>")),
+    "bypass": (0xB1, None, 0, None),
+    "default": (0x00, None, 0, ("filter_q7", "<true>")),
+    "custom_nob1": (0xA1, C12_NOB1, 0, ("filter_q7", "<true>")),
+    "custom_b1": (0xA1, C12_B1, 0, ("filter_q7", "<false>")),
+    "wide1": (0xA2, None, 1, ("filter_w14", "")),
+    "wide3": (0xA2, None, 3, ("filter_w14", "")),
+    "wide6": (0xA2, None, 6, ("filter_w14", "")),
 }
+Q15_HOP = 4104                  # 8 * 513: the packed frames of a stream alternate between 8-byte aligned and not
+Q15_FORMS = ("i16", "p12", "i16_hop", "p12_hop")       # int16 frames, packed frames, an int16 stream at a hop, a packed one
+# (call, argument): the plain kinds -- the marker over the full range and over a range that cuts a wave's 64 bins, the trace
+# at both ends of its DPP / swizzle / readlane ladder -- and the grouped ones (the partial-record arm and trace_fold; the IQ
+# arm into the workspace and spectra_fold)
+Q15_PLAIN = (("iq", None), ("mag", None), ("marker", (0, N)), ("marker", (9000, 12001)), ("trace", 2), ("trace", 64))
+Q15_GROUPED = (("trace_avg", (16, 2)), ("spectra", 2))
+Q15_FILTER = ("filter", None)                          # filter_q15: the two frame forms only, the wrapper offers no hop
+Q15_BATCHES, Q15_GROUPED_BATCHES, Q15_MAX = (1, 7, 17), (2, 6, 18), 18
 
 
-def _launched_q15(ch, nsec_wide, fft):
-    """The kernels a Q15 call launches, from the handle's state as specan_abi.cpp (process_q15) and cascade_q15.hip
-    (sa_launch_filter_q15: the short step when B1 = 0 in both coefficient sets; 0x00 runs the fixed taps, whose B1 is 0)."""
+def _q15_plan(bypass):
+    """[(window mode, input form, batch, poison words, calls)] of one case.  Pruned by coverage: every call of every input
+    form runs under all three poison words at the largest ragged batch (17, and 18 for the grouped kinds) and under one
+    word each at the smaller batches; both window modes run all of that in the bypass case only, where the FFT applies
+    the window -- a cascade case runs in window mode 1 what this test ran before it grew: filter_q15 and process_q15 on
+    int16 frames, every batch, every word."""
+    plan = []
+    for win_mode in (0, 1):
+        for form in Q15_FORMS:
+            frames = "hop" not in form
+            if win_mode == 1 and not bypass:
+                if form == "i16":
+                    plan += [(1, form, B, Q15_POISON, (Q15_FILTER, ("iq", None))) for B in Q15_BATCHES]
+                continue
+            plain = Q15_PLAIN + ((Q15_FILTER,) if frames else ())
+            for batches, calls in ((Q15_BATCHES, plain), (Q15_GROUPED_BATCHES, Q15_GROUPED)):
+                plan += [(win_mode, form, B, Q15_POISON if B == batches[-1] else Q15_POISON[i:i + 1], calls)
+                         for i, B in enumerate(batches)]
+    return plan
+
+
+def _q15_want(case):
+    """The (kernels launched, window mode) pairs of a case: from Q15_CASES alone, no handle."""
+    cascade = Q15_CASES[case][3]
+    return {(q15_kernels(cascade, form, call), w) for w, form, _, _, calls in _q15_plan(cascade is None) for call, _ in calls}
+
+
+def _launched_q15(ch, nsec_wide, xd, hop, call):
+    """The kernels a Q15 call launches, from the handle's state and the call's input, as specan_abi.cpp (launch_q15) and
+    cascade_q15.hip decide it (launch_cascade: the short step when B1 = 0 in both coefficient sets; 0x00 runs the fixed
+    taps, whose B1 is 0; 0xA2 without sections is the wire)."""
     mode = ch.filter_mode
-    if mode == 0xB1:
-        return ("fft_q15<true>",) if fft else ("window_q15",)
-    if mode == 0xA2:
-        filt = f"filter_w14/{nsec_wide}"
+    form = ("p12" if str(xd.dtype) == "torch.uint8" else "i16") + ("_hop" if hop else "")
+    if mode == 0xB1 or (mode == 0xA2 and nsec_wide == 0):
+        cascade = None
+    elif mode == 0xA2:
+        cascade = ("filter_w14", "")
     else:
         c = ch.coeffs_q7()
-        filt = f"filter_q7<{'true' if mode == 0x00 or (c[1] == 0 and c[7] == 0) else 'false'}>"
-    return (filt, "fft_q15<false>") if fft else (filt,)
+        cascade = ("filter_q7", "<true>" if mode == 0x00 or (c[1] == 0 and c[7] == 0) else "<false>")
+    return q15_kernels(cascade, form, call)
+
+
+def _q15_samples(seed, amp, full_scale_last):
+    """One stream of (Q15_MAX - 1) * hop + N samples whose frames at the hop begin with _frames_i16's impulse frame and
+    zero frame (frame 1 overlaps nothing else) and, for int16 samples, end with a full-scale frame: (stream, frames)."""
+    from fpga_real_time_fft_analyzer_amd.ingest import FrameCutter
+    rng = np.random.default_rng(seed)
+    n = (Q15_MAX - 1) * Q15_HOP + N
+    s = rng.integers(-amp, amp, n)
+    s[:Q15_HOP + N] = 0
+    s[0] = amp - 1
+    if full_scale_last:
+        s[(Q15_MAX - 1) * Q15_HOP:] = rng.integers(-32768, 32768, N)
+    s = s.astype(np.int16)
+    frames = FrameCutter(Q15_HOP).push(s)
+    assert frames.shape == (Q15_MAX, N) and not frames[1].any() and frames[0, 0] == amp - 1 and not frames[0, 1:].any()
+    return s, frames
+
+
+def _q15_rows(B):
+    """The frames of a batch of B out of the Q15_MAX frames of _frames_i16: the first B - 1 and the full-scale last one."""
+    return list(range(B)) if B <= 2 else list(range(B - 1)) + [Q15_MAX - 1]
+
+
+def _q15_expect(call, arg, iq, t, mag, ip):
+    """The output of a call as a numpy array of the call's dtype and shape, from the oracle's frames `iq` (their decode
+    `mag`, `ip`) and time series `t`: the mirrors of q15_mirrors.py, every one exact."""
+    B = iq.shape[0]
+    if call == "filter":
+        return t
+    if call == "iq":
+        return iq
+    if call == "mag":
+        return mag
+    if call == "marker":
+        pm, pb, bp = marker_expect(mag, ip, *arg)
+        rec = np.zeros((B, 4), np.int32)
+        rec[:, 0], rec[:, 1] = bits(pm).view(np.int32), pb
+        rec.view(np.int64)[:, 1] = bp
+        return rec
+    if call == "trace":
+        peak, power, _ = trace_expect(mag, ip, arg)
+    elif call == "trace_avg":
+        peak, power, _ = trace_expect(mag, ip, *arg)
+    else:
+        peak, power, _ = spectra_expect(mag, ip, arg)
+    return np.stack([peak, power], axis=-1).astype(np.float32)
+
+
+def _q15_call(ch, call, arg, xd, hop):
+    if call == "filter":
+        return ch.filter_q15(xd)
+    if call == "trace":
+        return ch.traces_q15(xd, bucket=arg, hop=hop)
+    if call == "trace_avg":
+        return ch.traces_q15(xd, bucket=arg[0], group=arg[1], hop=hop)
+    if call == "spectra":
+        return ch.spectra_q15(xd, arg, hop=hop)
+    return ch.process_q15(xd, out_kind=call, hop=hop)
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("case", list(Q15_CASES))
 def test_poisoned_lds_integer_chain(ch, torch_mod, oracle, lds, case):
-    """(b) lds_fill(P) then filter_q15 / process_q15, for P = NaN / +Inf / (-32768, -32768) words: bit for bit the
-    integer model, in both window modes, at ragged batches 1, 7 and 17 (the last workgroup of the cascade kernels has
-    idle frame pairs, which still take part in the barriers)."""
-    mode, c12, nsec_wide, want_filt, want_fft = Q15_CASES[case]
+    """(b) lds_fill(P) then a call of the integer chain, for P = NaN / +Inf / (-32768, -32768) words: bit for bit the
+    integer model (oracle.chain_q15: IQ and the time series) and the numpy mirrors of the other kinds on the model's
+    frames.  Calls: process_q15 as 'iq', 'mag' and 'marker' (two ranges), traces_q15 at buckets 2 and 64, the grouped
+    traces_q15(16, group=2) and spectra_q15(2) with their fold launches, and filter_q15; input forms: int16 frames, packed
+    frames, an int16 stream and a packed stream at hop 4104 (the host cuts the reference's frames, ingest.FrameCutter).
+    Ragged batches 1, 7 and 17, and 2, 6 and 18 for the grouped kinds: the smallest that leave idle frame pairs in a
+    cascade workgroup's last wave (which still take part in its barriers, and whose staging registers q15_load_tile
+    leaves to its `f < batch` guards), start a second cascade workgroup, and keep every workgroup first on its LDS slot.
+    The int16 forms keep _frames_i16's impulse frame, zero frame and full-scale last frame; packed forms hold 12-bit
+    samples.  _q15_plan says which batch runs under which words and window modes."""
+    from fpga_real_time_fft_analyzer_amd.ingest import pack12
+    mode, c12, nsec_wide, cascade = Q15_CASES[case]
     sos14 = load_golden("g4_q15_frames.npz")["sos_q14"][:max(1, nsec_wide)]
     if c12 is not None:
         ch.load_coeffs_q7(c12)
     if nsec_wide:
         ch.load_sos_q14(sos14)
     ch.set_filter_mode(mode)
+    plan = _q15_plan(mode == 0xB1)
+    # samples: int16 frames as _frames_i16 makes them, and one int16 and one 12-bit stream whose frames at the hop are the
+    # frames of the two packed forms and of the stream forms
+    x16 = _frames_i16(Q15_MAX, 100 + mode, amp=8192)
+    s16, f16 = _q15_samples(200 + mode, 8192, True)
+    s12, f12 = _q15_samples(300 + mode, 2048, False)
+    frames_of = {"i16": x16, "p12": f12, "i16_hop": f16, "p12_hop": f12}
+    refs, expect, dev = {}, {}, {}
+
+    def reference(form, win_mode, B):
+        """(iq, time series, mag, integer power) of the batch: the oracle once per sample set and window mode"""
+        src = "p12" if form == "p12_hop" else form
+        if (src, win_mode) not in refs:
+            iq, t = oracle.chain_q15(frames_of[src], None, win_mode, mode, c12, sos14 if nsec_wide else None, want_time=True)
+            refs[src, win_mode] = (iq, t) + decode(iq)
+        rows = _q15_rows(B) if src == "i16" else list(range(B))
+        return tuple(a[rows] for a in refs[src, win_mode])
+
+    def device_input(form, B):
+        if (form, B) not in dev:
+            n = (B - 1) * Q15_HOP + N
+            x = {"i16": lambda: x16[_q15_rows(B)], "p12": lambda: pack12(f12[:B]), "i16_hop": lambda: s16[:n],
+                 "p12_hop": lambda: pack12(s12[:n])}[form]()
+            dev[form, B] = to_device(torch_mod, x)
+        return dev[form, B]
+
     reached, bad, n_calls = set(), [], 0
-    for win_mode in (0, 1):
+    for win_mode, form, B, words, calls in plan:
         ch.set_window_mode_q15(win_mode)
-        for B in (1, 7, 17):
-            x = _frames_i16(B, 100 * B + win_mode, amp=8192)
-            ref_iq, ref_t = oracle.chain_q15(x, None, win_mode, mode, c12, sos14 if nsec_wide else None, want_time=True)
-            xd = to_device(torch_mod, x)
-            reached.add((_launched_q15(ch, nsec_wide, False), win_mode))
-            reached.add((_launched_q15(ch, nsec_wide, True), win_mode))
-            for word in Q15_POISON:
-                t = _after_fill(torch_mod, lds, word, lambda: ch.filter_q15(xd))
-                iq = _after_fill(torch_mod, lds, word, lambda: ch.process_q15(xd))
-                n_calls += 2
-                for what, got, ref in (("filter_q15", t, ref_t), ("process_q15", iq, ref_iq)):
-                    if not np.array_equal(got, ref):
-                        rows = np.flatnonzero((got != ref).reshape(B, -1).any(axis=1)).tolist()
-                        bad.append((case, win_mode, B, f"0x{word:08X}", what, "rows", rows))
-    print(f"FIGURE poisoned q15 {case}: {n_calls} poisoned calls bit-exact: {sorted(reached)}")
+        xd, hop = device_input(form, B), (Q15_HOP if "hop" in form else None)
+        for call, arg in calls:
+            if call == "marker":
+                ch.set_marker_range(*arg)
+            key = ("p12" if form == "p12_hop" else form, win_mode, B, call, arg)
+            if key not in expect:
+                expect[key] = _q15_expect(call, arg, *reference(form, win_mode, B))
+            want = expect[key]
+            reached.add((_launched_q15(ch, nsec_wide, xd, hop, call), win_mode))
+            for word in words:
+                got = _after_fill(torch_mod, lds, word, lambda: _q15_call(ch, call, arg, xd, hop))
+                n_calls += 1
+                if not _bits_equal(got, want):
+                    bad.append((case, win_mode, form, B, f"0x{word:08X}", call, arg, "rows", _rows_differing(got, want)))
+    ch.set_marker_range(0, N)
+    kernels = sorted({k for ks, _ in reached for k in ks})
+    print(f"FIGURE poisoned q15 {case}: {n_calls} poisoned calls, {len(bad)} not bit-exact; {len(reached)} (launches, window mode) "
+          f"pairs of {len(kernels)} kernels: {kernels}")
     assert not bad, "\n".join(map(str, bad[:10]))
-    assert reached == {(k, w) for k in (want_filt, want_fft) for w in (0, 1)}
+    want = _q15_want(case)
+    assert reached == want, (sorted(want - reached), sorted(reached - want))
+
+
+# ------------------------------------------------------------------------------------------- the kernel inventory (CPU)
+def _poisoned_kernels():
+    """{"float:<group>" / "q15:<case>": the kernel instantiations its pinned variant set launches}"""
+    out = {f"float:{g}": {k for v in want for k in float_kernels(v)} for g, (_, _, want) in FLOAT_GROUPS.items()}
+    out.update({f"q15:{c}": {k for ks, _ in _q15_want(c) for k in ks} for c in Q15_CASES})
+    return out
+
+
+def test_kernel_inventory_is_classified(hip_lib_built):
+    """CPU: every kernel instantiation of the built library -- the `__device_stub__` symbols of its symbol table -- has
+    one row in kernel_inventory.TABLE, and the table has no row without a kernel; every "float:" / "q15:" row names a case
+    of the two poisoning tests whose pinned variant set launches that kernel; the "exempt" rows are exactly the kernels
+    proven here to use no LDS (static: the compiler's resource remark; dynamic: no `extern __shared__` in the unit or
+    the headers it includes); together the pinned sets launch every kernel that is neither exempt nor unreachable."""
+    from concurrent.futures import ThreadPoolExecutor
+    from fpga_real_time_fft_analyzer_amd import abi
+    built = inventory(abi.LIB_PATH)
+    assert len(built) > 200, built
+    unclassified, vanished = sorted(built - set(TABLE)), sorted(set(TABLE) - built)
+    assert not unclassified and not vanished, (
+        "kernels of the library without a row in tests/kernel_inventory.py TABLE:\n  " + "\n  ".join(unclassified or ["-"])
+        + "\nrows of TABLE whose kernel the library no longer has:\n  " + "\n  ".join(vanished or ["-"]))
+    classes = {k: v.split(":", 1)[0] for k, v in TABLE.items()}
+    assert set(classes.values()) <= {"float", "q15", "exempt", "unreachable"}, set(classes.values())
+    assert all(v.split(":", 1)[1].strip() for v in TABLE.values()), "a row without its case or its reason"
+    # poisoned by: the named case pins a variant that launches the kernel
+    poisoned = _poisoned_kernels()
+    wrong = sorted((k, v) for k, v in TABLE.items() if classes[k] in ("float", "q15") and k not in poisoned.get(v, ()))
+    assert not wrong, wrong
+    # exempt = proven to use no LDS
+    with ThreadPoolExecutor(len(NO_LDS_UNITS)) as pool:
+        remarks = dict(zip(NO_LDS_UNITS, pool.map(lds_remarks, NO_LDS_UNITS)))
+    proven = set()
+    for unit, kernels in NO_LDS_UNITS.items():
+        assert "extern __shared__" not in unit_text(unit), unit
+        for k in kernels:
+            sizes = lds_of(remarks[unit], k)
+            assert sizes == [0], (unit, k, sizes, sorted(remarks[unit]))
+            proven.add(k)
+    assert "extern __shared__" in unit_text("fft_q15.hip")          # the search sees through includes: the FFT's is in its .inc
+    assert {k for k, c in classes.items() if c == "exempt"} == proven
+    # every other kernel is launched by a pinned variant, and no pinned variant launches a kernel the library lacks
+    launched = set().union(*poisoned.values())
+    assert launched <= built, sorted(launched - built)
+    rest = {k for k, c in classes.items() if c in ("float", "q15")}
+    assert launched - proven == rest, (sorted(rest - launched), sorted(launched - proven - rest))
+    assert not launched & {k for k, c in classes.items() if c == "unreachable"}
+    print(f"FIGURE kernel inventory: {len(built)} instantiations; {len(rest)} poisoned, {len(proven)} without LDS, "
+          f"{len(built) - len(rest) - len(proven)} unreachable")
 
 
 # --------------------------------------------------------------------------------- (c) non-finite neighbour frames
@@ -380,6 +633,21 @@ def _mixed_i16(B, seed):
     for k, i in enumerate(bad_idx):
         x[i] = (32767, np.rint(32767 * np.cos(2 * np.pi * 4096 * n / N)), rng.integers(-32768, 32768, N))[k % 3]
     return x, np.array([i for i in range(B) if i % 3 != 2])
+
+
+P12_BIG_SCALE = 2.0 ** 44      # 2047 * 2^44 is within 0.05 % of 32767 * 2^40: the same |X|^2 overflows; clean frames reach ~4e31
+
+
+def _mixed_p12(B, seed):
+    """_mixed_i16 in 12 bits: every third frame 12-bit full scale (a constant 2047, a tone at bin 4096, random), the clean
+    frames |sample| <= 8: (packed batch [B, 24576] uint8, indices of the clean frames)."""
+    from fpga_real_time_fft_analyzer_amd.ingest import pack12
+    rng = np.random.default_rng(seed)
+    x = rng.integers(-8, 9, (B, N)).astype(np.int16)
+    n = np.arange(N)
+    for k, i in enumerate(range(2, B, 3)):
+        x[i] = (2047, np.rint(2047 * np.cos(2 * np.pi * 4096 * n / N)), rng.integers(-2048, 2048, N))[k % 3]
+    return pack12(x), np.array([i for i in range(B) if i % 3 != 2])
 
 
 # label -> (filter mode, cascade name, precision).  Precision does not apply in mode 0xB1 (include/specan.h): the
@@ -435,15 +703,16 @@ def test_nonfinite_neighbour_frames(ch, torch_mod, form):
 @pytest.mark.parametrize("form", list(NEIGHBOUR_FORMS))
 def test_nonfinite_neighbour_frames_int16(ch, torch_mod, form):
     """(c) the int16 entry at scale 2^40, where a full-scale frame overflows |X|^2 in float32: the clean frames
-    (|sample| <= 8) equal the clean-only batch bit for bit and are finite, for every out kind."""
+    (|sample| <= 8) equal the clean-only batch bit for bit and are finite, for every out kind.  The same through the
+    packed entry, 12-bit full scale at scale 2^44."""
     mode, casc, precision = NEIGHBOUR_FORMS[form]
     _configure(ch, mode, casc, "cos", precision)
-    x, clean = _mixed_i16(1024, 7)
-    bad, spoilt = _check_neighbours(ch, torch_mod, x, clean, KINDS, (form, "int16"), scale=I16_BIG_SCALE)
-    print(f"FIGURE neighbours int16 {form}: clean frames bit-identical; {spoilt} bad rows with non-finite outputs "
-          f"(not asserted)")
-    assert spoilt > 0, "no full-scale frame overflowed: the scale no longer tests overflow"
-    assert not bad, "\n".join(map(str, bad))
+    for what, (x, clean), scale in (("int16", _mixed_i16(1024, 7), I16_BIG_SCALE), ("packed", _mixed_p12(1024, 8), P12_BIG_SCALE)):
+        bad, spoilt = _check_neighbours(ch, torch_mod, x, clean, KINDS, (form, what), scale=scale)
+        print(f"FIGURE neighbours {what} {form}: clean frames bit-identical; {spoilt} bad rows with non-finite outputs "
+              f"(not asserted)")
+        assert spoilt > 0, f"{what}: no full-scale frame overflowed: the scale no longer tests overflow"
+        assert not bad, "\n".join(map(str, bad))
 
 
 @pytest.mark.gpu

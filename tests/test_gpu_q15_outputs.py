@@ -11,6 +11,7 @@ import pytest
 
 from conftest import N, load_golden
 from gpu_support import ch, to_device, torch_mod  # noqa: F401 (fixtures)
+from q15_mirrors import bits as _bits, decode as _decode, marker_expect as _expect, marker_records as _records
 
 pytestmark = pytest.mark.gpu
 
@@ -20,29 +21,6 @@ RANGES = [(0, N), (0, 8193), (100, 2000), (9000, 12000), (8000, 8400), (0, 1), (
 SA_EINVAL, SA_ESHAPE = -1, -2
 GUI_UPLOAD = np.array([0, 1, 0, 64, -67, 19, 64, 127, 64, 64, -85, 40], np.int8)      # gui.py:159-179, 1186-1192 defaults
 C12_SET = GUI_UPLOAD                      # the 12-byte set of test_gpu_q15.py::test_bit_exact_vs_integer_model is the same upload
-
-
-def _decode(iq):
-    """[B,N,2] int16 frames -> (mag float32 [B,N] through frames.decode_mag_16iq_le, integer power int64 [B,N])"""
-    from fpga_real_time_fft_analyzer_amd import frames
-    iq = np.ascontiguousarray(iq).astype("<i2", copy=False)
-    mag = np.stack([frames.decode_mag_16iq_le(iq[f].tobytes()) for f in range(iq.shape[0])])
-    return mag, iq[..., 0].astype(np.int64) ** 2 + iq[..., 1].astype(np.int64) ** 2
-
-
-def _expect(mag, ip, lo, hi):
-    sl = mag[:, lo:hi]
-    return sl.max(axis=1), (lo + sl.argmax(axis=1)).astype(np.int32), ip[:, lo:hi].sum(axis=1)
-
-
-def _records(rec):
-    """[B,4] int32 record tensor -> (peak_mag f32, peak_bin i32, band_power i64) numpy arrays"""
-    r = np.ascontiguousarray(rec.cpu().numpy())
-    return r[:, 0].copy().view(np.float32), r[:, 1].copy(), r.view(np.int64)[:, 1].copy()
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
 def _check_marker(rec, mag, ip, lo, hi, tag=""):

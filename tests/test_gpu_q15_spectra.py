@@ -12,20 +12,13 @@ import pytest
 
 from conftest import N
 from gpu_support import ch, check_overlap_profiling_and_graph_capture, to_device, torch_mod  # noqa: F401 (fixtures)
-from test_gpu_q15_trace_avg import FORMS, _bits, _configure, _decode, _iq, wide_sections
+from q15_mirrors import bits as _bits, decode as _decode, spectra_expect as _expect, wide_sections
+from test_gpu_q15_trace_avg import FORMS, _configure, _iq
 
 pytestmark = pytest.mark.gpu
 
 SA_EINVAL, SA_ESHAPE, SA_ESTATE = -1, -2, -4
 SHAPES = ((2, 2), (2, 6), (4, 8), (8, 24))                   # (A, B): every B is a prefix of one 24-frame batch
-
-
-def _expect(mag, ip, A):
-    """(peak float32 [B/A,N], power float32 [B/A,N], exact int64 [B/A,N]) of decoded frames"""
-    B = mag.shape[0]
-    assert B % A == 0
-    exact = ip.reshape(B // A, A, N).sum(axis=1)
-    return mag.reshape(B // A, A, N).max(axis=1), exact.astype(np.float32), exact
 
 
 def _check(rec, mag, ip, A, tag=""):

@@ -5,38 +5,18 @@ Every comparison is exact, on float bits: the records are bit-defined.  The expe
 frames oracle.chain_q15(...): the peak is the bucket maximum of frames.decode_mag_16iq_le, the power the int64 sum of
 re^2 + im^2 over the bucket converted once to float32 (nearest even; tests/test_q15_trace_cpu.py pins that conversion).
 """
-import functools
-
 import numpy as np
 import pytest
 
 from conftest import N
 from gpu_support import ch, check_overlap_profiling_and_graph_capture, to_device, torch_mod  # noqa: F401 (fixtures)
+from q15_mirrors import bits as _bits, decode as _decode, trace_expect as _expect, wide_sections
 
 pytestmark = pytest.mark.gpu
 
 WIDTHS = (2, 4, 8, 16, 32, 64)
 SA_EINVAL = -1
 GUI_UPLOAD = np.array([0, 1, 0, 64, -67, 19, 64, 127, 64, 64, -85, 40], np.int8)      # gui.py:159-179, 1186-1192 defaults
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-def _decode(iq):
-    """[B,N,2] int16 frames -> (mag float32 [B,N] through frames.decode_mag_16iq_le, integer power int64 [B,N])"""
-    from fpga_real_time_fft_analyzer_amd import frames
-    iq = np.ascontiguousarray(iq).astype("<i2", copy=False)
-    mag = np.stack([frames.decode_mag_16iq_le(iq[f].tobytes()) for f in range(iq.shape[0])])
-    return mag, iq[..., 0].astype(np.int64) ** 2 + iq[..., 1].astype(np.int64) ** 2
-
-
-def _expect(mag, ip, W):
-    """(peak float32 [B,P], power float32 [B,P], exact int64 [B,P]) of decoded frames"""
-    B = mag.shape[0]
-    exact = ip.reshape(B, N // W, W).sum(axis=2)
-    return mag.reshape(B, N // W, W).max(axis=2), exact.astype(np.float32), exact
 
 
 def _check(rec, mag, ip, W, tag=""):
@@ -49,17 +29,6 @@ def _check(rec, mag, ip, W, tag=""):
     assert bad[0].size == 0, (tag, W, "peak", bad[0][:5], bad[1][:5], r[..., 0][bad][:5], peak[bad][:5])
     bad = np.nonzero(_bits(r[..., 1]) != _bits(power))
     assert bad[0].size == 0, (tag, W, "power", bad[0][:5], bad[1][:5], r[..., 1][bad][:5], power[bad][:5])
-
-
-@functools.lru_cache(maxsize=None)
-def wide_sections():
-    """Six Q2.14 sections that let the test frames through (the recipe of tests/test_gpu_q15_p12.py): second-order
-    Butterworth low-passes of unity DC gain, cut-offs 0.35 .. 0.85 of Nyquist."""
-    from scipy import signal
-    sos = np.concatenate([signal.butter(2, wc, output="sos") for wc in (0.35, 0.45, 0.55, 0.65, 0.75, 0.85)])
-    q = np.rint(sos * 16384.0)
-    assert q.shape == (6, 6) and np.abs(q).max() <= 32767
-    return q.astype(np.int16)
 
 
 # form -> (filter byte, 12-byte upload, Q2.14 sections, window mode, custom ROM)
