@@ -1,6 +1,7 @@
-"""ctypes binding of ``libspecan_hip.so`` (the C ABI declared in ``include/specan.h`` and ``include/specan_ext.h``).
+"""ctypes binding of ``libspecan_hip.so`` (the C ABI declared in ``include/specan.h`` and ``include/specan_ext.h``) and of
+``libspecan_fold.so`` (``include/specan_fold.h``).
 
-This is the only place the shared library is loaded.  There is no CPU fallback: if the
+This is the only place the shared libraries are loaded.  There is no CPU fallback: if the
 library is missing the import of any compute entry point raises, and creating a handle
 itself fails when no HIP device is usable.
 """
@@ -12,6 +13,7 @@ import subprocess
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_PKG, "libspecan_hip.so")
+FOLD_LIB_PATH = os.path.join(_PKG, "libspecan_fold.so")      # include/specan_fold.h: built by the same make
 CSRC = os.path.join(_PKG, "csrc")
 
 # error codes / constants (include/specan.h)
@@ -76,7 +78,8 @@ class SpecanError(RuntimeError):
 
 
 def build(verbose: bool = False) -> str:
-    """Compile the HIP extension in-tree for gfx950 (hipcc cross-compiles without a GPU)."""
+    """Compile the HIP extension in-tree for gfx950 (hipcc cross-compiles without a GPU): both libraries, LIB_PATH and
+    FOLD_LIB_PATH, are the Makefile's first target."""
     cmd = ["make", "-j4", "-C", CSRC]
     if not verbose:
         cmd.insert(1, "-s")
@@ -150,17 +153,27 @@ EXT_SIGNATURES = {
     "sa_ext_check_pointers": (_INT, [_INT, _INT, _INT, C.c_uint64, C.c_uint64, _INT]),
 }
 
+# the entry points of include/specan_fold.h: libspecan_fold.so, a second product library without a handle (the fold of float
+# magnitudes over groups of frames and buckets of bins), bound by fold_lib() and held name for name against that header
+# (tests/test_f32_fold_cpu.py); no name is in the two tables above
+SA_FOLD_VERSION = 1
+SA_FOLD_LOG2A_MAX, SA_FOLD_LOG2W_MAX = 7, 6
+FOLD_SIGNATURES = {
+    "sa_fold_version": (_INT, []),
+    "sa_fold_mag_f32": (_INT, [C.c_void_p, C.c_void_p, _INT, _INT, _INT, C.c_void_p]),
+    "sa_fold_check": (_INT, [_INT, _INT, C.c_uint64, C.c_uint64, _INT]),
+    "sa_fold_last_error": (C.c_char_p, []),
+}
+
 _lib = None
+_fold_lib = None
 
 
-def lib() -> C.CDLL:
-    """Load the shared library; raise loudly when it has not been built."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(LIB_PATH):
+def _load(path: str, tables: tuple) -> C.CDLL:
+    """Map one of the package's shared libraries and bind the names of ``tables``; raise loudly when it has not been built."""
+    if not os.path.exists(path):
         raise ImportError(
-            f"{LIB_PATH} not found: the HIP extension is not built (run __graft_entry__.build() or "
+            f"{path} not found: the HIP extension is not built (run __graft_entry__.build() or "
             f"`make -C {CSRC}`).  This package has no CPU fallback.")
     # torch first: its wheel bundles a HIP runtime under the same SONAME (libamdhip64.so.7) but another file
     # name, so if this library is mapped first the process ends up with two runtimes and the second one to
@@ -170,9 +183,25 @@ def lib() -> C.CDLL:
         import torch  # noqa: F401
     except ImportError:
         pass
-    L = C.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in {**SIGNATURES, **EXT_SIGNATURES}.items():
-        fn = getattr(L, name)
-        fn.restype, fn.argtypes = restype, argtypes
-    _lib = L
+    L = C.CDLL(path)
+    for table in tables:
+        for name, (restype, argtypes) in table.items():
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = restype, argtypes
     return L
+
+
+def lib() -> C.CDLL:
+    """Load the shared library; raise loudly when it has not been built."""
+    global _lib
+    if _lib is None:
+        _lib = _load(LIB_PATH, (SIGNATURES, EXT_SIGNATURES))
+    return _lib
+
+
+def fold_lib() -> C.CDLL:
+    """Load libspecan_fold.so (include/specan_fold.h), after torch as lib() does; raise loudly when it has not been built."""
+    global _fold_lib
+    if _fold_lib is None:
+        _fold_lib = _load(FOLD_LIB_PATH, (FOLD_SIGNATURES,))
+    return _fold_lib

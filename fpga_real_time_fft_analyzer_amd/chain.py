@@ -15,7 +15,7 @@ from typing import NamedTuple, Optional, Sequence
 import numpy as np
 import torch
 
-from . import abi
+from . import abi, frames
 from .abi import (SA_FILTER_CUSTOM, SA_FILTER_DEFAULT, SA_FILTER_NONE, SA_FILTER_WIDE, SA_N, SA_P12_FRAME_BYTES,
                   SA_OUT_MAG_FULL, SA_OUT_MAG_HALF, SA_OUT_MARKER, SA_OUT_SPEC_HALF, SA_OUT_TIME, SA_PRECISION_F32,
                   SA_PRECISION_F64_STATE, SA_Q15_OUT_IQ, SA_Q15_OUT_MAG, SA_Q15_OUT_MARKER, SpecanError)
@@ -127,6 +127,9 @@ _SPECTRA_IN = {torch.int16: _form(SA_N, _SPECTRA_OUT, "sa_spectra_q15"),
                torch.uint8: _form(SA_P12_FRAME_BYTES, _SPECTRA_OUT, "sa_spectra_q15_p12")}
 Q15_SPECTRA_CHAIN = _Chain(_SPECTRA_OUT, _SPECTRA_IN, _SPECTRA_IN)
 Q15_FOLD_CHAIN = _Chain(_SPECTRA_OUT, {torch.int16: _form((SA_N, 2), _SPECTRA_OUT, "sa_fold_iq_q15")})
+# the fold of float magnitudes (include/specan_fold.h; fold_mag_f32, spectra_f32): a call of libspecan_fold.so, which takes
+# no handle and is no row of the tables above -- the float chain's own call writes the magnitudes it reads
+FOLD_GROUPS, FOLD_BUCKETS = frames.FOLD_GROUPS, frames.FOLD_BUCKETS         # 1 .. 128 and 1 .. 64: the mirror's, defined once
 
 
 def output_spec(chain: _Chain, out_kind: Optional[str], B: int) -> tuple:
@@ -181,6 +184,7 @@ class SpectrumChain:
         self.control_generation = 0        # bumped by every call that changes what the path computes (virtual_fpga.py)
         self._depth = 1                    # launches in flight (sa_set_overlap)
         self._lent = collections.deque()   # (input, output) of the overlapped calls the caller's stream has not joined
+        self._fold_work = None             # float32 [B,16384] of the largest spectra_f32 call made without `work`
 
     # ------------------------------------------------------------------ plumbing
     def _check(self, rc: int):
@@ -197,6 +201,7 @@ class SpectrumChain:
             self._lib.sa_destroy(self._h)        # waits on the host for the handle's own work
             self._h = None
             self._lent.clear()
+            self._fold_work = None
 
     def _lend(self, x: torch.Tensor, out: torch.Tensor):
         """Overlap mode: the call just made owns (x, out) until depth-1 further calls have been made."""
@@ -561,6 +566,92 @@ class SpectrumChain:
         [B // group, 16384, 2] float32 as there.  One launch, no workspace: it captures into a graph at any time."""
         self._log2_group(group)
         return self._process(Q15_FOLD_CHAIN, iq, out, int(group))
+
+    @staticmethod
+    def _log2_fold(group, bucket) -> tuple:
+        """The one validation of the ``group`` and ``bucket`` of the float fold: (a, k) of A = 2^a and W = 2^k, or SA_EINVAL."""
+        for name, v, allowed in (("group", group, FOLD_GROUPS), ("bucket", bucket, FOLD_BUCKETS)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or int(v) not in allowed:
+                raise SpecanError(abi.SA_EINVAL, f"{name} must be one of {allowed}")
+        if int(group) == 1 and int(bucket) == 1:
+            raise SpecanError(abi.SA_EINVAL, "group = bucket = 1 folds nothing")
+        return int(group).bit_length() - 1, int(bucket).bit_length() - 1
+
+    def _fold_out(self, B: int, group: int, bucket: int, out: Optional[torch.Tensor]) -> torch.Tensor:
+        """``out`` of the float fold of ``B`` frames, allocated when None: SA_ESHAPE where B is no multiple of the group or
+        ``out`` is not the contiguous float32 [B // group, 16384 // bucket, 2] tensor on the handle's device."""
+        if B % group:
+            raise SpecanError(abi.SA_ESHAPE, f"the batch ({B} frames) must be a multiple of {group}")
+        shape = (B // group, SA_N // bucket, 2)
+        if out is None:
+            return torch.empty(shape, dtype=torch.float32, device=self.device)
+        if (not isinstance(out, torch.Tensor) or tuple(out.shape) != shape or out.dtype != torch.float32
+                or out.device != self.device or not out.is_contiguous()):
+            raise SpecanError(abi.SA_ESHAPE, f"out must be a contiguous torch.float32 tensor of shape {shape}")
+        return out
+
+    def fold_mag_f32(self, mag: torch.Tensor, group: int = 1, bucket: int = 1,
+                     out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Max hold and summed power of float32 magnitudes over groups of ``group`` consecutive frames and buckets of
+        ``bucket`` adjacent bins (include/specan_fold.h, sa_fold_mag_f32): ``mag`` is a float32 [B,16384] device tensor, what
+        ``process_f32(out_kind='mag_full')`` or ``process_q15(out_kind='mag')`` wrote; the result is float32
+        [B // group, 16384 // bucket, 2], one sa_fold_point per bucket and group.  ``[..., 0]`` is the peak: the input whose
+        bits with the sign cleared are largest as an integer -- the float maximum of the chain's non-negative values, bit for
+        bit; a NaN shows, -0.0 reads as +0.0, no denormal is flushed.  ``[..., 1]`` is the power: the float64 sum of the exact
+        squares, per bin over the frames in ascending order and then across the bucket's bins by a balanced pair tree,
+        rounded once to float32.  It is the SUM: the mean is ``power / (group * bucket)``, exactly.  frames.fold_of_mags is
+        the numpy mirror, bit for bit.
+
+        ``group`` is 1, 2, ..., 128 and ``bucket`` 1, 2, ..., 64, not both 1; anything else (a bool or a float included) is
+        SA_EINVAL, a B that is no multiple of ``group`` SA_ESHAPE, both before any device call.  One launch on the current
+        stream of the handle's device, no handle state, no workspace: it captures into a graph at any time.  Where ``mag`` is
+        the result of a call made in overlap mode, call :meth:`flush` first.  Pointer contract (checked by the C entry
+        point, SA_EINVAL): both data pointers are 16-byte aligned and the B * 65536 bytes read and the
+        (B // group) * (16384 // bucket) * 8 bytes written are disjoint; buffers that merely touch are fine."""
+        a, k = self._log2_fold(group, bucket)
+        B = self._check_in(mag, torch.float32, SA_N)
+        out = self._fold_out(B, int(group), int(bucket), out)
+        L = abi.fold_lib()
+        with torch.cuda.device(self.device):         # the C call launches on the calling thread's current device
+            rc = L.sa_fold_mag_f32(mag.data_ptr(), out.data_ptr(), B, a, k, self._stream())
+        if rc != abi.SA_OK:
+            raise SpecanError(rc, L.sa_fold_last_error().decode())
+        return out
+
+    def spectra_f32(self, x: torch.Tensor, group: int, bucket: int = 1, out: Optional[torch.Tensor] = None,
+                    scale: float = 1.0 / 2048.0, work: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Max hold and summed power of the float chain's spectra over groups of ``group`` consecutive frames and buckets of
+        ``bucket`` adjacent bins: float32 [B // group, 16384 // bucket, 2], the records of :meth:`fold_mag_f32` of
+        ``process_f32(x, out_kind='mag_full', scale=scale)``, bit for bit -- the input of a Welch estimate (``[..., 1] /
+        group``) or a max-hold display, from (2 / (group * bucket)) of the full spectrum's bytes.  ``x`` is float32, int16 or
+        packed uint8 exactly as for :meth:`process_f32`; every filter mode and both precisions apply, because the call is
+        that call, unchanged, into a float32 [B,16384] workspace, followed by one fold launch on the current stream.
+
+        The workspace is ``work`` (float32, contiguous, [B,16384] or more rows, on the handle's device; 16-byte aligned),
+        or, when None, a tensor cached on this object and regrown when B grows: allocate it by one call of the largest batch
+        before capturing the call into a graph, and give calls made on different streams a ``work`` each.  In overlap mode
+        (:meth:`set_overlap` with depth > 1) the call joins every outstanding call of the handle on the device, as
+        :meth:`flush` does and with no host wait, between its two launches: the result is valid on the current stream when
+        the call returns, and ``x`` and the workspace are free again then -- the call lends nothing.  ``group``, ``bucket``,
+        ``out`` and a B that is no multiple of ``group`` are refused as by :meth:`fold_mag_f32`, before anything is
+        launched."""
+        self._log2_fold(group, bucket)
+        forms = FLOAT_CHAIN.inputs
+        dtype = x.dtype if isinstance(x, torch.Tensor) and x.dtype in forms else next(iter(forms))
+        B = self._check_in(x, dtype, forms[dtype][0])
+        out = self._fold_out(B, int(group), int(bucket), out)
+        if work is None:
+            if self._fold_work is None or self._fold_work.shape[0] < B:
+                self._fold_work = None               # released before the larger one is taken
+                self._fold_work = torch.empty((B, SA_N), dtype=torch.float32, device=self.device)
+            work = self._fold_work
+        elif (not isinstance(work, torch.Tensor) or work.dtype != torch.float32 or work.device != self.device or work.dim() != 2
+              or work.shape[1] != SA_N or work.shape[0] < B or not work.is_contiguous()):
+            raise SpecanError(abi.SA_ESHAPE, f"work must be a contiguous torch.float32 tensor of shape [{B} or more, {SA_N}]")
+        mag = self.process_f32(x, out=work[:B], out_kind="mag_full", scale=scale)
+        if self._depth > 1:
+            self.flush()                             # the fold reads what an internal stream of the library writes
+        return self.fold_mag_f32(mag, group, bucket, out)
 
     def filter_q15(self, x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Window (+ integer IIR) only: the FFT input stream, [B,16384] int16.  ``x`` is [B,16384] int16 or the same

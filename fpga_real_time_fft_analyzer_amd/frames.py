@@ -92,6 +92,47 @@ def spectrum_of_frames(frames_bytes):
     return peak, exact.astype(np.float32), exact
 
 
+# A = 2^a, a = 0 .. SA_FOLD_LOG2A_MAX, and W = 2^k, k = 0 .. SA_FOLD_LOG2W_MAX (include/specan_fold.h): the one definition
+FOLD_GROUPS = (1, 2, 4, 8, 16, 32, 64, 128)
+FOLD_BUCKETS = (1, 2, 4, 8, 16, 32, 64)
+
+
+def fold_of_mags(mag, group: int, bucket: int):
+    """Float32 magnitudes [B, n] (n = 16384 for the chain's 'mag_full' frames; any multiple of ``bucket`` here) reduced over
+    groups of ``group`` = 1, 2, ..., 128 consecutive frames and buckets of ``bucket`` = 1, 2, ..., 64 adjacent bins, not both
+    1: ``(peak float32 [B // group, n // bucket], power float32 [same], s64 float64 [same])``.  The numpy mirror of
+    sa_fold_mag_f32 (include/specan_fold.h), step for step:
+
+    - peak: the input whose bits with the sign cleared are largest as a uint32, as those bits -- the float maximum of
+      non-negative finite data; +inf above every finite value, a NaN above +inf, -0.0 as +0.0, denormals kept;
+    - s64: the float64 sum of the exact squares ``float64(m) * float64(m)``, per bin over the frames of the group one after
+      the other, ascending, from +0.0 (the explicit loop), then across the bucket's bins by a balanced tree of adjacent
+      pairs, ``t[i] = t[2i] + t[2i+1]`` (the explicit halving); power is s64 rounded once to float32 (numpy's cast rounds to
+      nearest even, overflows to inf and keeps denormals).  It is the sum: the mean is ``power / (group * bucket)``, exactly."""
+    for name, v, allowed in (("group", group, FOLD_GROUPS), ("bucket", bucket, FOLD_BUCKETS)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or int(v) not in allowed:
+            raise ValueError(f"{name} must be one of {allowed}")
+    group, bucket = int(group), int(bucket)
+    if group == 1 and bucket == 1:
+        raise ValueError("group = bucket = 1 folds nothing")
+    mag = np.ascontiguousarray(mag)
+    if mag.dtype != np.float32 or mag.ndim != 2 or mag.shape[0] % group or mag.shape[1] % bucket:
+        raise ValueError("mag must be float32 [B, n] with B a multiple of group and n a multiple of bucket")
+    B, n = mag.shape
+    G, P = B // group, n // bucket
+    u = mag.view(np.uint32) & np.uint32(0x7FFFFFFF)
+    peak = np.ascontiguousarray(u.reshape(G, group, P, bucket).max(axis=(1, 3))).view(np.float32)
+    m = mag.astype(np.float64).reshape(G, group, n)
+    with np.errstate(over="ignore", invalid="ignore"):
+        t = np.zeros((G, n), np.float64)
+        for i in range(group):                        # frames ascending, one after the other
+            t = t + m[:, i] * m[:, i]
+        while t.shape[1] > P:                         # adjacent pairs on the bin index, log2(bucket) levels
+            t = t[:, 0::2] + t[:, 1::2]
+        power = t.astype(np.float32)
+    return peak, power, t
+
+
 def decode_iq_components(frame_bytes: bytes):
     """Same result as gui.py:262-270: (re, im) as float32 arrays."""
     re, im = _iq(frame_bytes)
