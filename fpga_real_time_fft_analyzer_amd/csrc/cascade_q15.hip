@@ -86,9 +86,9 @@ struct Q15TileRegs {
     uint4 c[kTilePasses];
 };
 
-// issue the global loads of one tile (4 frames x 256 samples and the matching ROM words), 16 B per lane.  HOP (the _hop
-// kernels): `in` is one stream and frame f begins at sample f hop of it, packed at byte 3 f hop / 2 -- hop is a multiple of 8:
-// a 16-byte boundary of int16 samples, a dword boundary of packed ones.  Otherwise the frames lie back to back and `hop` is
+// issue the global loads of one tile (4 frames x 256 samples and the matching ROM words), 16 B per lane.  HOP (the kernels
+// with a hop argument): `in` is one stream and frame f begins at sample f hop of it, packed at byte 3 f hop / 2 -- hop is a
+// multiple of 8: a 16-byte boundary of int16 samples, a dword boundary of packed ones.  Otherwise the frames lie back to back and `hop` is
 // not read (a template parameter, not a stride argument: with a stride that the inliner folds to the constant, the int16
 // kernels came out with other registers and one instruction more than they had).
 template <bool HOP, typename InT>
@@ -139,14 +139,15 @@ __device__ __forceinline__ uint4 win8(uint4 x, uint4 c, int win_mode)
     return make_uint4(o[0], o[1], o[2], o[3]);
 }
 
-// Every kernel of this file is defined by a macro, once per input form: on int16 samples (window_q15_kernel,
-// filter_q7_kernel, filter_w14_kernel) and on packed 12-bit samples (the same names with _p12).  Two kernels of one text
-// rather than one more template parameter or a shared inlined body: the int16 kernels keep their symbols and, instruction
-// for instruction, the code they had before the packed form existed (an inlined body did not: DESIGN.md section 4.10).
-// The cascades exist a third and fourth time, on frames cut from ONE sample stream at a hop (the names with _hop: SA_Q15_HOP_KIND
-// of include/specan.h): the same text with one more kernel argument, the hop in samples, and the
-// frame base of q15_load_tile taken from it -- HOP, HOP_ARG and HOP_VAL of the macros: false, empty and 0 in the frame forms.
-#define SA_Q15_HOP_ARG , int hop
+// Every kernel of this file is a template on its input form: InT is int16_t or SaP12 (packed 12-bit samples), and the
+// cascades take a trailing pack Hop -- empty on frames back to back, `int` on frames cut from ONE sample stream at a hop
+// (SA_Q15_HOP_KIND of include/specan.h): one more kernel argument, the hop in samples, from which
+// q15_load_tile takes the frame base.  One kernel per form, not a shared inlined body behind several kernels: that did
+// not leave the int16 kernels the code they had before the packed form existed; these instantiations do, instruction
+// for instruction.
+// q15_cascade's HOP and `hop` of a kernel's pack: false and 0 (never read) for the empty pack
+__device__ __forceinline__ int hop_or_zero() { return 0; }
+__device__ __forceinline__ int hop_or_zero(int hop) { return hop; }
 
 // Window only (filter mode 0xB1 through sa_filter_q15: the windowed time series, new/hann8192.vhd:36-39): element-wise,
 // eight samples of a frame per thread (16 bytes, 12 of packed samples), the ROM words from the L2.
@@ -155,20 +156,17 @@ constexpr int kWinThreads = 256;
 // packed sample n of the batch begins at byte 3 n / 2 of the batch
 __device__ __forceinline__ uint4 win_load8(const int16_t *in, size_t n) { return *reinterpret_cast<const uint4 *>(in + n); }
 __device__ __forceinline__ uint4 win_load8(const SaP12 *in, size_t n) { return q15_pairs(q15_load8_p12(in, 3 * (n >> 1))); }
-#define SA_WINDOW_Q15_KERNEL(NAME, InT)                                                                                         \
-    __global__ __launch_bounds__(kWinThreads) void NAME(const InT *__restrict__ in, int16_t *__restrict__ out, int batch,       \
-                                                        SaQ15Params prm, const int16_t *__restrict__ rom)                       \
-    {                                                                                                                           \
-        const size_t chunk = (size_t)blockIdx.x * kWinThreads + threadIdx.x; /* 16-byte chunk of the batch */                   \
-        if (chunk >= (size_t)batch * (SA_NPTS / 8)) return;                                                                     \
-        const int col = (int)(chunk % (SA_NPTS / 8)) * 8;                                                                       \
-        const uint4 xv = win_load8(in, chunk * 8);                                                                              \
-        const uint4 cv = *reinterpret_cast<const uint4 *>(rom + col);                                                           \
-        *reinterpret_cast<uint4 *>(out + chunk * 8) = win8(xv, cv, prm.win_mode);                                               \
-    }
-SA_WINDOW_Q15_KERNEL(window_q15_kernel, int16_t)
-SA_WINDOW_Q15_KERNEL(window_q15_p12_kernel, SaP12)
-#undef SA_WINDOW_Q15_KERNEL
+template <typename InT>
+__global__ __launch_bounds__(kWinThreads) void window_q15_kernel(const InT *__restrict__ in, int16_t *__restrict__ out, int batch,
+                                                                 SaQ15Params prm, const int16_t *__restrict__ rom)
+{
+    const size_t chunk = (size_t)blockIdx.x * kWinThreads + threadIdx.x;      // 16-byte chunk of the batch
+    if (chunk >= (size_t)batch * (SA_NPTS / 8)) return;
+    const int col = (int)(chunk % (SA_NPTS / 8)) * 8;
+    const uint4 xv = win_load8(in, chunk * 8);
+    const uint4 cv = *reinterpret_cast<const uint4 *>(rom + col);
+    *reinterpret_cast<uint4 *>(out + chunk * 8) = win8(xv, cv, prm.win_mode);
+}
 
 // ------------------------------------------------------------------------------------------ the cascade frame
 // The cascade is organised around what bounds it: the recursion is serial in time, there is one wave per SIMD at
@@ -427,22 +425,16 @@ __device__ __forceinline__ void q7_drain(Q7Carry &c, const Q7Taps &t, unsigned x
     lds_store16_masked(ra + 16, vb, kOutMask);
 }
 
-#define SA_FILTER_Q7_KERNEL(NAME, InT, HOP, HOP_ARG, HOP_VAL)                                                                   \
-    template <bool NOB1>                                                                                                        \
-    __global__ __launch_bounds__(64 * kWgWaves) void NAME(const InT *__restrict__ in, int16_t *__restrict__ out, int batch,     \
-                                                          SaQ15Params prm, const int16_t *__restrict__ rom HOP_ARG)             \
-    {                                                                                                                           \
-        q15_cascade<int, Q7Carry, HOP>(in, HOP_VAL, out, batch, prm.win_mode, rom, [&](int sec) -> Q7Taps {                     \
-            if (sec < 0 || sec >= SA_MAXSEC) return {128 << 9, 0, 0, 0, 0}; /* identity = (128 x) >> 7 */                       \
-            const int8_t *c = &prm.c12[(sec & 1) ? 6 : 0];                  /* stages 1,3,5 = set 0; 2,4,6 = set 1 */           \
-            return {c[2] << 9, c[1] << 9, c[0] << 9, -(c[3] << 9), -(c[4] << 9)};                                               \
-        }, [](Q7Carry &c, const Q7Taps &t, unsigned xa, unsigned ra) { q7_tile<NOB1>(c, t, xa, ra); }, q7_drain);               \
-    }
-SA_FILTER_Q7_KERNEL(filter_q7_kernel, int16_t, false, , 0)
-SA_FILTER_Q7_KERNEL(filter_q7_p12_kernel, SaP12, false, , 0)
-SA_FILTER_Q7_KERNEL(filter_q7_hop_kernel, int16_t, true, SA_Q15_HOP_ARG, hop)
-SA_FILTER_Q7_KERNEL(filter_q7_hop_p12_kernel, SaP12, true, SA_Q15_HOP_ARG, hop)
-#undef SA_FILTER_Q7_KERNEL
+template <typename InT, bool NOB1, typename... Hop>
+__global__ __launch_bounds__(64 * kWgWaves) void filter_q7_kernel(const InT *__restrict__ in, int16_t *__restrict__ out, int batch,
+                                                                  SaQ15Params prm, const int16_t *__restrict__ rom, Hop... hop)
+{
+    q15_cascade<int, Q7Carry, sizeof...(Hop) != 0>(in, hop_or_zero(hop...), out, batch, prm.win_mode, rom, [&](int sec) -> Q7Taps {
+        if (sec < 0 || sec >= SA_MAXSEC) return {128 << 9, 0, 0, 0, 0};     // identity = (128 x) >> 7
+        const int8_t *c = &prm.c12[(sec & 1) ? 6 : 0];                      // stages 1,3,5 = set 0; 2,4,6 = set 1
+        return {c[2] << 9, c[1] << 9, c[0] << 9, -(c[3] << 9), -(c[4] << 9)};
+    }, [](Q7Carry &c, const Q7Taps &t, unsigned xa, unsigned ra) { q7_tile<NOB1>(c, t, xa, ra); }, q7_drain);
+}
 
 // ------------------------------------------------------------------------------------------ IIR, wide Q2.14 form
 // Mode 0xA2 (the build's own spec, oracle/specan_oracle.c:or_iir_sos_q14; the six sections scripts/fft_analyzer_gui.py:108-157
@@ -512,87 +504,66 @@ __device__ __forceinline__ void w14_tile(W14Carry &c, const W14Taps &t, unsigned
 
 // one pass of four groups as the drain: the first delivers the frame's last eight samples, the other three filter whatever
 // the input ring holds into slots that were flushed long ago
-#define SA_FILTER_W14_KERNEL(NAME, InT, HOP, HOP_ARG, HOP_VAL)                                                                  \
-    __global__ __launch_bounds__(64 * kWgWaves) void NAME(const InT *__restrict__ in, int16_t *__restrict__ out, int batch,     \
-                                                          SaQ15Params prm, const int16_t *__restrict__ rom HOP_ARG)             \
-    {                                                                                                                           \
-        q15_cascade<int16_t, W14Carry, HOP>(in, HOP_VAL, out, batch, prm.win_mode, rom, [&](int sec) {                          \
-            /* identity: (16384 x + 8192) >> 14 = x exactly */                                                                  \
-            if (sec < 0 || sec >= prm.nsec_wide) return w14_taps(16384, 0, 0, 0, 0);                                            \
-            /* scipy row order [b0, b1, b2, a0, a1, a2], a0 ignored (= 1.0) */                                                  \
-            const int16_t *c = &prm.sos_q14[sec * 6];                                                                           \
-            return w14_taps(c[0], c[1], c[2], c[4], c[5]);                                                                      \
-        }, [](W14Carry &c, const W14Taps &t, unsigned xa, unsigned ra) { w14_tile(c, t, xa, ra, kTileIters); },                 \
-        [](W14Carry &c, const W14Taps &t, unsigned xa, unsigned ra) { w14_tile(c, t, xa, ra, 1); });                            \
-    }
-SA_FILTER_W14_KERNEL(filter_w14_kernel, int16_t, false, , 0)
-SA_FILTER_W14_KERNEL(filter_w14_p12_kernel, SaP12, false, , 0)
-SA_FILTER_W14_KERNEL(filter_w14_hop_kernel, int16_t, true, SA_Q15_HOP_ARG, hop)
-SA_FILTER_W14_KERNEL(filter_w14_hop_p12_kernel, SaP12, true, SA_Q15_HOP_ARG, hop)
-#undef SA_FILTER_W14_KERNEL
-#undef SA_Q15_HOP_ARG
+template <typename InT, typename... Hop>
+__global__ __launch_bounds__(64 * kWgWaves) void filter_w14_kernel(const InT *__restrict__ in, int16_t *__restrict__ out, int batch,
+                                                                   SaQ15Params prm, const int16_t *__restrict__ rom, Hop... hop)
+{
+    q15_cascade<int16_t, W14Carry, sizeof...(Hop) != 0>(in, hop_or_zero(hop...), out, batch, prm.win_mode, rom, [&](int sec) {
+        // identity: (16384 x + 8192) >> 14 = x exactly
+        if (sec < 0 || sec >= prm.nsec_wide) return w14_taps(16384, 0, 0, 0, 0);
+        // scipy row order [b0, b1, b2, a0, a1, a2], a0 ignored (= 1.0)
+        const int16_t *c = &prm.sos_q14[sec * 6];
+        return w14_taps(c[0], c[1], c[2], c[4], c[5]);
+    }, [](W14Carry &c, const W14Taps &t, unsigned xa, unsigned ra) { w14_tile(c, t, xa, ra, kTileIters); },
+    [](W14Carry &c, const W14Taps &t, unsigned xa, unsigned ra) { w14_tile(c, t, xa, ra, 1); });
+}
 
 // the cascade launch of one input form: the wide cascade, or the Q7 cascade with its seven- or nine-instruction step.
-// `hop`: nothing for the frame kernels, the hop in samples for the _hop kernels (their trailing argument).
-template <typename InT, typename K, typename... Hop>
-void launch_cascade(K wide, K q7_short, K q7_long, const InT *in, int16_t *out_time, int batch, const SaQ15Params &p,
-                    const SaQ15Tables &t, hipStream_t stream, SaLaunchEv ev, Hop... hop)
+// `hop`: nothing for frames back to back, the hop in samples for frames cut from one stream (the kernels' trailing argument).
+template <typename InT, typename... Hop>
+void launch_cascade(const InT *in, int16_t *out_time, int batch, const SaQ15Params &p, const SaQ15Tables &t, hipStream_t stream,
+                    SaLaunchEv ev, Hop... hop)
 {
     const int per_wg = kFramesPerWave * kV2Waves;
     const dim3 grid_wg((batch + per_wg - 1) / per_wg), block_wg(64 * kWgWaves);
     if (p.filter == SA_FILTER_WIDE) {
-        hipExtLaunchKernelGGL(wide, grid_wg, block_wg, 0, stream, ev.start, ev.stop, 0, in, out_time, batch, p, t.rom, hop...);
+        hipExtLaunchKernelGGL((filter_w14_kernel<InT, Hop...>), grid_wg, block_wg, 0, stream, ev.start, ev.stop, 0, in, out_time, batch,
+                              p, t.rom, hop...);
     } else {
         // B1 = 0 in both coefficient sets (wire order b0,b1,b2,a0,a1,a2 per set): the seven-instruction step
         const bool nob1 = p.c12[1] == 0 && p.c12[7] == 0;
-        hipExtLaunchKernelGGL(nob1 ? q7_short : q7_long, grid_wg, block_wg, 0, stream, ev.start, ev.stop, 0, in, out_time, batch, p,
-                              t.rom, hop...);
+        hipExtLaunchKernelGGL(nob1 ? filter_q7_kernel<InT, true, Hop...> : filter_q7_kernel<InT, false, Hop...>, grid_wg, block_wg, 0,
+                              stream, ev.start, ev.stop, 0, in, out_time, batch, p, t.rom, hop...);
     }
 }
 
-// every launch of one input form on frames: window only, or its cascade
-template <typename InT, typename K>
-void launch_filter(K window, K wide, K q7_short, K q7_long, const InT *in, int16_t *out_time, int batch, const SaQ15Params &p,
-                   const SaQ15Tables &t, hipStream_t stream, SaLaunchEv ev)
+// every launch of one input form: window only (frames alone), or its cascade on frames (hop = 0) or on one stream
+template <typename InT>
+void launch_filter(const InT *in, int hop, int16_t *out_time, int batch, const SaQ15Params &p, const SaQ15Tables &t,
+                   hipStream_t stream, SaLaunchEv ev)
 {
     if (p.filter == SA_FILTER_NONE) {
         const size_t chunks = (size_t)batch * (SA_NPTS / 8);
-        hipExtLaunchKernelGGL(window, dim3((unsigned)((chunks + kWinThreads - 1) / kWinThreads)), dim3(kWinThreads), 0, stream,
-                              ev.start, ev.stop, 0, in, out_time, batch, p, t.rom);
+        hipExtLaunchKernelGGL(window_q15_kernel<InT>, dim3((unsigned)((chunks + kWinThreads - 1) / kWinThreads)), dim3(kWinThreads), 0,
+                              stream, ev.start, ev.stop, 0, in, out_time, batch, p, t.rom);
+    } else if (hop != 0) {
+        launch_cascade(in, out_time, batch, p, t, stream, ev, hop);
     } else {
-        launch_cascade(wide, q7_short, q7_long, in, out_time, batch, p, t, stream, ev);
+        launch_cascade(in, out_time, batch, p, t, stream, ev);
     }
 }
 
 }  // namespace
 
-hipError_t sa_launch_filter_q15(const void *in, SaInKind in_kind, int16_t *out_time, int batch, const SaQ15Params &p,
+// A stream is read by a cascade only: window-only output of a stream is not offered (sa_filter_q15 has no kind word), and in
+// filter mode 0xB1 the FFT's stage 0 reads the stream itself.
+hipError_t sa_launch_filter_q15(const void *in, SaInKind in_kind, int hop, int16_t *out_time, int batch, const SaQ15Params &p,
                                 const SaQ15Tables &t, hipStream_t stream, SaLaunchEv ev)
 {
     if (in_kind != SaInKind::I16 && in_kind != SaInKind::P12) return hipErrorInvalidValue;
+    if (hop != 0 && (hop < 0 || hop > SA_NPTS || hop % 8 != 0 || p.filter == SA_FILTER_NONE)) return hipErrorInvalidValue;
     if (batch <= 0) return hipSuccess;
-    if (in_kind == SaInKind::P12)
-        launch_filter(window_q15_p12_kernel, filter_w14_p12_kernel, filter_q7_p12_kernel<true>, filter_q7_p12_kernel<false>,
-                      static_cast<const SaP12 *>(in), out_time, batch, p, t, stream, ev);
-    else
-        launch_filter(window_q15_kernel, filter_w14_kernel, filter_q7_kernel<true>, filter_q7_kernel<false>,
-                      static_cast<const int16_t *>(in), out_time, batch, p, t, stream, ev);
-    return hipGetLastError();
-}
-
-// A stream is read by a cascade only: window-only output of a stream is not offered (sa_filter_q15 has no kind word), and in
-// filter mode 0xB1 the FFT's stage 0 reads the stream itself.
-hipError_t sa_launch_filter_q15_hop(const void *in, SaInKind in_kind, int hop, int16_t *out_time, int batch, const SaQ15Params &p,
-                                    const SaQ15Tables &t, hipStream_t stream, SaLaunchEv ev)
-{
-    if (in_kind != SaInKind::I16 && in_kind != SaInKind::P12) return hipErrorInvalidValue;
-    if (hop <= 0 || hop > SA_NPTS || hop % 8 != 0 || p.filter == SA_FILTER_NONE) return hipErrorInvalidValue;
-    if (batch <= 0) return hipSuccess;
-    if (in_kind == SaInKind::P12)
-        launch_cascade(filter_w14_hop_p12_kernel, filter_q7_hop_p12_kernel<true>, filter_q7_hop_p12_kernel<false>,
-                       static_cast<const SaP12 *>(in), out_time, batch, p, t, stream, ev, hop);
-    else
-        launch_cascade(filter_w14_hop_kernel, filter_q7_hop_kernel<true>, filter_q7_hop_kernel<false>,
-                       static_cast<const int16_t *>(in), out_time, batch, p, t, stream, ev, hop);
+    if (in_kind == SaInKind::P12) launch_filter(static_cast<const SaP12 *>(in), hop, out_time, batch, p, t, stream, ev);
+    else launch_filter(static_cast<const int16_t *>(in), hop, out_time, batch, p, t, stream, ev);
     return hipGetLastError();
 }

@@ -1,8 +1,8 @@
 // fft_q15.hip -- SA-FXFFT-1 for gfx950 (MI355X): the fixed-point FFT that stands where ip/xfft_0 stands
 // (radix-4 DIF, >>2 per stage, Q15 twiddles, truncation).  One 1024-thread workgroup per frame, data in LDS as packed
 // (re,im) int16 pairs, Stockham (autosort) addressing so the result is in natural order, stages paired in registers; the
-// arithmetic per butterfly is exactly oracle/specan_oracle.c:or_fxfft16k.  The kernel's text is fft_q15_kernel.inc, included
-// once for int16 samples and once for packed 12-bit samples (include/specan.h, "p12"; unpacked in stage 0).
+// arithmetic per butterfly is exactly oracle/specan_oracle.c:or_fxfft16k.  One kernel template, fft_q15_kernel, instantiated
+// for int16 samples and for packed 12-bit samples (include/specan.h, "p12"; unpacked in stage 0), in frames or in one stream.
 #include "q15_dev.hpp"
 #include "p12_dev.hpp"
 #include "../../include/specan.h"
@@ -385,14 +385,16 @@ __device__ __forceinline__ void fx_trace_frame(const unsigned (&q)[16], int k, i
 constexpr int kFftLds = SA_NPTS * 4;                      // the frame image; MARKER: + kFxMarkParts x 16 bytes behind it
 
 // Stage 0's samples of thread t, x[m] = sample t + 1024 m of frame f.  int16 samples: 2-byte loads, 128 contiguous bytes
-// per wave instruction.  Frame f begins `stride` samples after frame f - 1: SA_NPTS, a constant, where the frames lie back
-// to back, the hop where they are cut from one stream (the _hop kernels; SA_FX_STRIDE of fft_q15_kernel.inc).
+// per wave instruction.  Frame f begins `stride` samples after frame f - 1 (fx_stride): SA_NPTS, a constant, where the
+// frames lie back to back, the hop where they are cut from one stream (the kernel's trailing `int hop`).
 __device__ __forceinline__ void fx_load16(const int16_t *in, int f, size_t stride, int t, int (&x)[16])
 {
     const int16_t *xf = in + (size_t)f * stride + t;
 #pragma unroll
     for (int m = 0; m < 16; ++m) x[m] = xf[kFftWide * m];
 }
+__device__ __forceinline__ size_t fx_stride(const int16_t *) { return (size_t)SA_NPTS; }
+__device__ __forceinline__ size_t fx_stride(const int16_t *, int hop) { return (size_t)hop; }
 // Packed 12-bit samples (include/specan.h; a frame is 6144 dwords, every frame 16-byte aligned): sample n sits at bit 12 n,
 // so sample t + 1024 m begins in dword (12 t >> 5) + 384 m at bit sh = 12 t & 31, the same for all 16 m.  It reaches into
 // the next dword only where sh > 20, i.e. sh = 24 or 28, t mod 8 = 2 or 5.  Two aligned dword loads (a wave instruction
@@ -414,50 +416,180 @@ __device__ __forceinline__ void fx_load16(const SaP12 *in, int f, size_t stride,
     for (int m = 0; m < 16; ++m)
         x[m] = p12_bfe(__builtin_amdgcn_alignbit(hi[step * m], lo[step * m], (unsigned)sh), 0);
 }
+__device__ __forceinline__ size_t fx_stride(const SaP12 *) { return (size_t)kP12FrameDwords; }
+__device__ __forceinline__ size_t fx_stride(const SaP12 *, int hop) { return (size_t)(3 * hop / 8); }
 
-#define SA_FX_KERNEL fft_q15_kernel
-#define SA_FX_IN int16_t
-#define SA_FX_HOP_ARG
-#define SA_FX_STRIDE (size_t)SA_NPTS
-#include "fft_q15_kernel.inc"
-#undef SA_FX_KERNEL
-#undef SA_FX_IN
-#undef SA_FX_STRIDE
-// packed samples arrive unwindowed from the caller only (filter mode 0xB1): WINDOW = true is all that is instantiated
-#define SA_FX_KERNEL fft_q15_p12_kernel
-#define SA_FX_IN SaP12
-#define SA_FX_STRIDE (size_t)kP12FrameDwords
-#include "fft_q15_kernel.inc"
-#undef SA_FX_KERNEL
-#undef SA_FX_IN
-#undef SA_FX_STRIDE
-#undef SA_FX_HOP_ARG
-// Frames cut from one sample stream at a hop (SA_Q15_HOP_KIND of include/specan.h): the same text
-// twice more, with the hop in samples as one more kernel argument behind `mrange`.  A stream comes from the caller only,
-// unwindowed (mode 0xB1; the cascades' workspace is frames): WINDOW = true is all that is instantiated.
-#define SA_FX_HOP_ARG , int hop
-#define SA_FX_KERNEL fft_q15_hop_kernel
-#define SA_FX_IN int16_t
-#define SA_FX_STRIDE (size_t)hop
-#include "fft_q15_kernel.inc"
-#undef SA_FX_KERNEL
-#undef SA_FX_IN
-#undef SA_FX_STRIDE
-#define SA_FX_KERNEL fft_q15_hop_p12_kernel
-#define SA_FX_IN SaP12
-#define SA_FX_STRIDE (size_t)(3 * hop / 8)
-#include "fft_q15_kernel.inc"
-#undef SA_FX_KERNEL
-#undef SA_FX_IN
-#undef SA_FX_STRIDE
-#undef SA_FX_HOP_ARG
+// The integer FFT's kernel, one template for every input form: InT is int16_t or SaP12 (packed 12-bit samples, p12_dev.hpp),
+// and Hop is empty for frames back to back -- no further kernel argument, a constant stride -- or `int` for frames cut from
+// one stream: the hop in samples, one more kernel argument behind `mrange`.  The forms share every line below and differ in
+// fx_load16 and its stride (fx_stride) alone.  A template on the input form, not a shared inlined body: the body inlined into
+// one kernel per form changed the int16 kernels' instruction streams, the template leaves every instantiation the code
+// it had as a kernel of its own name.  Instantiated: WINDOW = false for <int16_t, ...> without a
+// hop alone (the FFT behind a cascade); packed samples and streams come from the caller only, unwindowed (filter mode 0xB1).
+template <typename InT, bool WINDOW, int OUT, typename... Hop>
+__global__ __launch_bounds__(kFftWide, 8) void fft_q15_kernel(const InT *__restrict__ in, void *__restrict__ out, int batch,
+                                                               SaQ15Params prm, const int16_t *__restrict__ rom,
+                                                               const uint2 *__restrict__ tw, const uint4 *__restrict__ twrec,
+                                                               unsigned mrange, Hop... hop)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_q[];
+    unsigned *buf = reinterpret_cast<unsigned *>(smem_q);     // [16384] packed (re, im)
+    const int t = threadIdx.x;
+    const int f = blockIdx.x;
+    if (f >= batch) return;
+    // ---- stage 0 straight from global memory: the thread's 16 positions t + 1024 m (fx_load16: 2-byte loads of int16
+    // samples, or dword loads and an unpack of packed ones), optional window, imag = 0 (new/command_control.vhd:123).
+    // No staging pass through LDS, no barrier in front of the first butterflies; outputs 4 bf + i' are one 16-byte LDS
+    // write.
+    // Exponents with wi = -32768 (see fx_butterfly): stages 0 and 1, u = 3 for output 1, u = 1 for output 3.
+    {
+        int x[16];
+        fx_load16(in, f, fx_stride(in, hop...), t, x);
+        if constexpr (WINDOW) {
+            int c[16];
+#pragma unroll
+            for (int m = 0; m < 16; ++m) c[m] = rom[t + kFftWide * m];
+#pragma unroll
+            for (int m = 0; m < 16; ++m)
+                x[m] = (prm.win_mode == SA_WIN_RTL_SIGNED) ? win_rtl(x[m], c[m]) : win_u16(x[m], c[m]);
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int bf = t + kFftWide * u;                   // j' = bf, kappa = 0, e1 = bf
+            unsigned o[4];
+            const SaTw3 w = fx_twrec(twrec, bf);
+            fx_butterfly_real(x[u], x[u + 4], x[u + 8], x[u + 12], w.w1, w.w2.x, w.w3, bf == 0, o, u == 3, u == 1);
+            *reinterpret_cast<uint4 *>(buf + 4 * bf) = make_uint4(o[0], o[1], o[2], o[3]);
+        }
+        __syncthreads();
+    }
+
+    // ---- stages 1..4 as two register passes of two stages each.  A thread that runs the stage-s butterflies
+    // bf = t + 1024 u (u = 0..3) holds, in output i' of butterfly u, input u of the stage-(s+1) butterfly
+    // ((j' mod 4^(5-s)) << (2s+2)) | (i' << 2s) | kappa -- its own four next butterflies, which all share ONE twiddle
+    // exponent (j'' = (t >> 2s) mod 4^(5-s) does not depend on i').  One LDS exchange per two stages instead of one per
+    // stage, a quarter of the twiddle loads in the second stage of a pass.
+    //   outputs of the pass: pos = (j'' << (2s+4)) | (i'' << (2s+2)) | (i' << 2s) | kappa
+    // Pass (1,2) writes with kappa = t & 3 in the bank bits: the words are stored at pos ^ ((j'' & 15) << 2), which spreads
+    // the 16 values of j'' in a wave over the banks (conflict-free), and pass (3,4) reads t + 1024 m through the same
+    // exchange of bits (there it permutes the lanes of a wave: conflict-free as well).
+    unsigned v[16];
+    const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
+    {
+#pragma unroll
+        for (int m = 0; m < 16; ++m) v[m] = buf[t + kFftWide * m];
+        __syncthreads();
+        unsigned x[16];                                        // x[4 i' + u]
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int e1 = ((t + kFftWide * u) >> 2) << 2;
+            unsigned o[4];
+            // exponents with wi = -32768 (see fx_butterfly): output 1 at u = 3, output 3 at u = 1, output 2 at u = 1 or 2
+            const SaTw3 w = fx_twrec(twrec, 4096 + (e1 >> 2));
+            fx_butterfly(v[u], v[u + 4], v[u + 8], v[u + 12], w.w1, w.w2, w.w3, e1 == 0, o, u == 3, u == 1 || u == 2, u == 1);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) x[4 * i + u] = o[i];
+        }
+        // stage 2: j'' = (t >> 2) & 255, exponent 16 j'' (never in 4082..4095; 3 e never in 4083..4110; 2 e = 4096 for
+        // j'' = 128, i.e. threads 512..515: wave 8 takes the two-multiply form for output 2)
+        const int j2 = (t >> 2) & 255, e2 = j2 << 4;
+        const SaTw3 w2 = fx_twrec(twrec, 5120 + j2);
+        const uint2 a1 = w2.w1, a2 = w2.w2, a3 = w2.w3;
+        const int ob = ((j2 << 6) | (t & 3)) ^ ((j2 & 15) << 2);
+#pragma unroll
+        for (int ip = 0; ip < 4; ++ip) {
+            unsigned o[4];
+            if (wave == 8) fx_butterfly(x[4 * ip], x[4 * ip + 1], x[4 * ip + 2], x[4 * ip + 3], a1, a2, a3, false, o, false, true, false);
+            else fx_butterfly(x[4 * ip], x[4 * ip + 1], x[4 * ip + 2], x[4 * ip + 3], a1, a2, a3, e2 == 0, o, false, false, false);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) buf[ob ^ ((4 * i + ip) << 2)] = o[i];
+        }
+        __syncthreads();
+    }
+    {
+        // pass (3,4): scalar twiddles in both stages (j' = wave + 16 u, then j'' = wave)
+#pragma unroll
+        for (int m = 0; m < 16; ++m) v[m] = buf[(t + kFftWide * m) ^ (wave << 2)];
+        __syncthreads();
+        unsigned x[16];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int e1 = (wave + 16 * u) << 6;
+            unsigned o[4];
+            fx_butterfly<true>(v[u], v[u + 4], v[u + 8], v[u + 12], tw[e1], tw[2 * e1], tw[3 * e1], e1 == 0, o, false, u == 2, false);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) x[4 * i + u] = o[i];
+        }
+        const int e2 = wave << 8;                              // 2 e = 4096 for wave 8
+        const uint2 a1 = tw[e2], a2 = tw[2 * e2], a3 = tw[3 * e2];
+        const int ob = (wave << 10) | (t & 63);
+#pragma unroll
+        for (int ip = 0; ip < 4; ++ip) {
+            unsigned o[4];
+            if (wave == 8) fx_butterfly<true>(x[4 * ip], x[4 * ip + 1], x[4 * ip + 2], x[4 * ip + 3], a1, a2, a3, false, o, false, true, false);
+            else fx_butterfly<true>(x[4 * ip], x[4 * ip + 1], x[4 * ip + 2], x[4 * ip + 3], a1, a2, a3, e2 == 0, o, false, false, false);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) buf[ob | ((4 * i + ip) << 6)] = o[i];
+        }
+        __syncthreads();
+    }
+#pragma unroll
+    for (int m = 0; m < 16; ++m) v[m] = buf[t + kFftWide * m];
+    unsigned w[16];
+    // stage 5 (4^s = 1024): j' = u, kappa = t; outputs land at m' = 4u + i'; exponents are compile-time
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        unsigned o[4];
+        fx_butterfly<true>(v[u], v[u + 4], v[u + 8], v[u + 12], tw[u * 1024], tw[2 * u * 1024], tw[3 * u * 1024], u == 0, o, false,
+                           u == 2, false);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) w[4 * u + i] = o[i];
+    }
+    // stage 6 (4^s = 4096): no twiddles; outputs at m' = u + 4 i' = natural-order bin t + 1024 m'
+    // frame layout: [16384] x (re, im) int16 = 65536 bytes (imp/sequ2.vhd:153); one dword per lane
+    // SA_Q15_OUT_MAG: the same dwords at the same offsets of a float row, each the magnitude of its bin.
+    // SA_Q15_OUT_MARKER: no spectrum store; the thread keeps the 16 sums re^2 + im^2 of its bins and roots their largest.
+    // kFxOutTrace: no spectrum store either; the thread keeps its 16 bins, then per m' the wave reduces its 64 bins to
+    // 64 / W records (W = 1 << mrange) and the first lane of each bucket stores one: row [16384 / W] of the frame
+    // (fx_trace_frame).  kFxOutTraceRaw: the same reduction, the bucket's partial record {s, hi, lo, 0} stored instead
+    // (row [16384 / W] of 16-byte records in the workspace `out`).
+    unsigned *o32 = reinterpret_cast<unsigned *>(reinterpret_cast<int16_t *>(out) + (size_t)f * SA_NPTS * 2);
+    const int mlo = (int)(mrange & 0xFFFFu), mhi = (int)(mrange >> 16);
+    float ms[16];
+    unsigned long long mpow = 0ull;
+    unsigned tq[16];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        unsigned o[4];
+        fx_butterfly(w[u], w[u + 4], w[u + 8], w[u + 12], make_uint2(0u, 0u), make_uint2(0u, 0u), make_uint2(0u, 0u), true, o, false,
+                     false, false);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int mp = u + 4 * i;
+            if constexpr (OUT == SA_Q15_OUT_IQ)
+                __builtin_nontemporal_store(o[i], o32 + t + kFftWide * mp);   // streaming: written once
+            else if constexpr (OUT == SA_Q15_OUT_MAG)
+                __builtin_nontemporal_store(fx_mag(o[i]), reinterpret_cast<float *>(o32) + t + kFftWide * mp);
+            else if constexpr (OUT == SA_Q15_OUT_MARKER)
+                ms[mp] = fx_mark_sum_any(mpow, o[i], t + kFftWide * mp, (wave << 6) + kFftWide * mp, mlo, mhi);
+            else
+                tq[mp] = o[i];
+        }
+    }
+    if constexpr (OUT == SA_Q15_OUT_MARKER) {
+        fx_mark_finish(fx_mark_thread(ms, t, mpow), reinterpret_cast<uint4 *>(smem_q + kFftLds), out, f, t, wave);
+    }
+    if constexpr (OUT == kFxOutTrace) fx_trace_frame<false>(tq, (int)mrange, t, out, f);
+    if constexpr (OUT == kFxOutTraceRaw) fx_trace_frame<true>(tq, (int)mrange, t, out, f);
+}
 
 // `log2w`: the k of SA_Q15_TRACE_KIND(k), which rides in the kernel's trailing word in place of the marker range;
-// `hop`: nothing for the frame kernels, the hop in samples for the _hop kernels (their trailing argument)
-template <int OUT, typename K, typename InT, typename... Hop>
-hipError_t launch_fft_q15(K k, const InT *in_time, void *out, int batch, const SaQ15Params &p, const SaQ15Tables &t,
-                          int log2w, hipStream_t stream, SaLaunchEv ev, Hop... hop)
+// `hop`: nothing for frames back to back, the hop in samples for frames cut from one stream (the kernel's trailing argument)
+template <int OUT, bool WINDOW, typename InT, typename... Hop>
+hipError_t launch_fft_q15(const InT *in_time, void *out, int batch, const SaQ15Params &p, const SaQ15Tables &t, int log2w,
+                          hipStream_t stream, SaLaunchEv ev, Hop... hop)
 {
+    const auto k = fft_q15_kernel<InT, WINDOW, OUT, Hop...>;
     const dim3 grid(batch), block(kFftWide);
     const int lds = kFftLds + (OUT == SA_Q15_OUT_MARKER ? kFxMarkParts * (int)sizeof(uint4) : 0);
     const hipError_t e = sa_set_dyn_lds_once(reinterpret_cast<const void *>(k), lds);
@@ -468,29 +600,30 @@ hipError_t launch_fft_q15(K k, const InT *in_time, void *out, int batch, const S
     return hipGetLastError();
 }
 
-// hop = 0: frames back to back; otherwise `in_time` is one stream and frame f begins at sample f hop (windowed always)
+// hop = 0: frames back to back; otherwise `in_time` is one stream and frame f begins at sample f hop.  The caller has
+// refused unwindowed input in any form but int16 frames.
 template <int OUT>
 hipError_t launch_fft_q15(const void *in_time, SaInKind in_kind, int hop, void *out, int batch, bool apply_window,
                           const SaQ15Params &p, const SaQ15Tables &t, int log2w, hipStream_t stream, SaLaunchEv ev)
 {
-    if (hop != 0 && in_kind == SaInKind::P12)
-        return launch_fft_q15<OUT>(fft_q15_hop_p12_kernel<true, OUT>, static_cast<const SaP12 *>(in_time), out, batch, p, t, log2w,
-                                   stream, ev, hop);
-    if (hop != 0)
-        return launch_fft_q15<OUT>(fft_q15_hop_kernel<true, OUT>, static_cast<const int16_t *>(in_time), out, batch, p, t, log2w,
-                                   stream, ev, hop);
-    if (in_kind == SaInKind::P12)
-        return launch_fft_q15<OUT>(fft_q15_p12_kernel<true, OUT>, static_cast<const SaP12 *>(in_time), out, batch, p, t, log2w,
-                                   stream, ev);
-    return launch_fft_q15<OUT>(apply_window ? fft_q15_kernel<true, OUT> : fft_q15_kernel<false, OUT>,
-                               static_cast<const int16_t *>(in_time), out, batch, p, t, log2w, stream, ev);
+    const int16_t *i16 = static_cast<const int16_t *>(in_time);
+    const SaP12 *p12 = static_cast<const SaP12 *>(in_time);
+    if (hop != 0 && in_kind == SaInKind::P12) return launch_fft_q15<OUT, true>(p12, out, batch, p, t, log2w, stream, ev, hop);
+    if (hop != 0) return launch_fft_q15<OUT, true>(i16, out, batch, p, t, log2w, stream, ev, hop);
+    if (in_kind == SaInKind::P12) return launch_fft_q15<OUT, true>(p12, out, batch, p, t, log2w, stream, ev);
+    return apply_window ? launch_fft_q15<OUT, true>(i16, out, batch, p, t, log2w, stream, ev)
+                        : launch_fft_q15<OUT, false>(i16, out, batch, p, t, log2w, stream, ev);
 }
 
-// both launches: `hop` = 0 for frames
-hipError_t launch_fft_q15_kind(const void *in_time, SaInKind in_kind, int hop, void *out, int batch, int out_kind, bool apply_window,
-                               const SaQ15Params &p, const SaQ15Tables &t, hipStream_t stream, SaLaunchEv ev)
+}  // namespace
+
+hipError_t sa_launch_fft_q15(const void *in_time, SaInKind in_kind, int hop, void *out, int batch, int out_kind, bool apply_window,
+                             const SaQ15Params &p, const SaQ15Tables &t, hipStream_t stream, SaLaunchEv ev)
 {
-    if (in_kind != SaInKind::I16 && !(in_kind == SaInKind::P12 && apply_window)) return hipErrorInvalidValue;
+    if (hop != 0 && (hop < 0 || hop > SA_NPTS || hop % 8 != 0)) return hipErrorInvalidValue;
+    if (in_kind != SaInKind::I16 && in_kind != SaInKind::P12) return hipErrorInvalidValue;
+    // unwindowed input is a cascade's output alone: int16 frames
+    if (!apply_window && (in_kind != SaInKind::I16 || hop != 0)) return hipErrorInvalidValue;
     if (batch <= 0) return hipSuccess;
     if (out_kind >= SA_Q15_TRACE_KIND(SA_Q15_TRACE_LOG2W_MIN) && out_kind <= SA_Q15_TRACE_KIND(SA_Q15_TRACE_LOG2W_MAX))
         return launch_fft_q15<kFxOutTrace>(in_time, in_kind, hop, out, batch, apply_window, p, t, out_kind - kFxOutTrace, stream, ev);
@@ -504,19 +637,4 @@ hipError_t launch_fft_q15_kind(const void *in_time, SaInKind in_kind, int hop, v
             return launch_fft_q15<SA_Q15_OUT_MARKER>(in_time, in_kind, hop, out, batch, apply_window, p, t, 0, stream, ev);
         default: return hipErrorInvalidValue;
     }
-}
-
-}  // namespace
-
-hipError_t sa_launch_fft_q15(const void *in_time, SaInKind in_kind, void *out, int batch, int out_kind, bool apply_window,
-                             const SaQ15Params &p, const SaQ15Tables &t, hipStream_t stream, SaLaunchEv ev)
-{
-    return launch_fft_q15_kind(in_time, in_kind, 0, out, batch, out_kind, apply_window, p, t, stream, ev);
-}
-
-hipError_t sa_launch_fft_q15_hop(const void *in, SaInKind in_kind, int hop, void *out, int batch, int out_kind, const SaQ15Params &p,
-                                 const SaQ15Tables &t, hipStream_t stream, SaLaunchEv ev)
-{
-    if (hop <= 0 || hop > SA_NPTS || hop % 8 != 0) return hipErrorInvalidValue;
-    return launch_fft_q15_kind(in, in_kind, hop, out, batch, out_kind, true, p, t, stream, ev);
 }

@@ -171,14 +171,18 @@ constexpr int kSaTwRecs = 4096 + 1024 + 256;
 // `in` per in_kind: int16 samples [B,16384] (I16) or the same samples packed to 12 bits [B,24576] (P12: include/specan.h,
 // 16-byte aligned; unpacked where the kernels read them, every result that of the I16 form on the sign-extended samples).
 // The FFT takes P12 only with apply_window: a cascade's output, the only unwindowed input there is, is int16.
-hipError_t sa_launch_filter_q15(const void *in, SaInKind in_kind, int16_t *out_time, int batch, const SaQ15Params &p,
+// `hop` = 0: frames.  Otherwise `in` is ONE sample stream (SA_Q15_HOP_KIND of include/specan.h): frame f is the 16384
+// samples from sample f * hop on, hop a multiple of 8 in 8..16384; `in` holds (batch - 1) * hop + 16384 samples, int16 or
+// packed (3/2 bytes per sample), 16-byte aligned.  The cascade writes frames, [B,16384] int16, as ever, and reads a stream
+// only as a cascade (not in filter mode NONE); the FFT reads a stream only in filter mode 0xB1 and always windows it.
+hipError_t sa_launch_filter_q15(const void *in, SaInKind in_kind, int hop, int16_t *out_time, int batch, const SaQ15Params &p,
                                 const SaQ15Tables &t, hipStream_t stream, SaLaunchEv ev);
 // out per out_kind: SA_Q15_OUT_* -- int16 [B,16384,2], float [B,16384] or sa_marker_q15 [B] -- or SA_Q15_TRACE_KIND(k),
 // k = 1..6: sa_trace_point_q15 [B, 16384 >> k] (the width reaches the kernel in the word that carries the marker range)
 // -- or SA_Q15_TRACE_AVG_KIND(k, a): `out` is then a workspace of 16-byte partial records [B, 16384 >> k] (kSaTraceRawBytes
 // each: {bits of the bucket's largest float sum, sum of the high halves of its powers, sum of the low halves, 0}), which
 // sa_launch_trace_fold_q15 folds, A = 2^a frames at a time, into sa_trace_point_q15 [B / A, 16384 >> k]
-hipError_t sa_launch_fft_q15(const void *in_time, SaInKind in_kind, void *out, int batch, int out_kind, bool apply_window,
+hipError_t sa_launch_fft_q15(const void *in_time, SaInKind in_kind, int hop, void *out, int batch, int out_kind, bool apply_window,
                              const SaQ15Params &p, const SaQ15Tables &t, hipStream_t stream, SaLaunchEv ev);
 constexpr int kSaTraceRawBytes = 16;
 // trace_fold_q15.hip: batch a multiple of 2^log2a; reads batch * (16384 >> log2w) records, writes (batch >> log2a) rows
@@ -187,12 +191,4 @@ hipError_t sa_launch_trace_fold_q15(const void *partial, void *out, int batch, i
 // spectra_fold_q15.hip (include/specan_ext.h): iq = int16 [batch,16384,2], batch a multiple of 2^log2a; writes
 // sa_trace_point_q15 [batch >> log2a, 16384], each row the fold of 2^log2a consecutive frames bin by bin
 hipError_t sa_launch_spectra_fold_q15(const void *iq, void *out, int batch, int log2a, hipStream_t stream, SaLaunchEv ev);
-// The same two launches on frames cut from ONE sample stream (SA_Q15_HOP_KIND of include/specan.h): frame f is the 16384
-// samples from sample f * hop on, hop a multiple of 8 in 8..16384; `in` holds (batch - 1) * hop + 16384 samples, int16 or
-// packed (3/2 bytes per sample), 16-byte aligned.  The cascade writes frames, [B,16384] int16, as ever; the FFT reads a stream
-// only in filter mode 0xB1 and always windows it.
-hipError_t sa_launch_filter_q15_hop(const void *in, SaInKind in_kind, int hop, int16_t *out_time, int batch, const SaQ15Params &p,
-                                    const SaQ15Tables &t, hipStream_t stream, SaLaunchEv ev);
-hipError_t sa_launch_fft_q15_hop(const void *in, SaInKind in_kind, int hop, void *out, int batch, int out_kind, const SaQ15Params &p,
-                                 const SaQ15Tables &t, hipStream_t stream, SaLaunchEv ev);
 

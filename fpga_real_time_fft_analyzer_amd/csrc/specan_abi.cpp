@@ -444,7 +444,7 @@ static int refused(sa_handle *h, int entry, const SaChecked &r)
 // workspace and its bin-by-bin fold behind it -- spectra_fold_q15.hip, include/specan_ext.h) and sa_fold_iq_q15 (that fold
 // with nothing in front of it: `in` holds the IQ frames), on int16 samples or on packed 12-bit samples.  With a fold behind
 // an FFT, the FFT launch writes into a workspace of the slot and the fold writes `out`.  With a hop, `in` is one stream and
-// whichever launch reads the samples -- the cascade, or the FFT in mode 0xB1 -- is its _hop sibling.  Everything else is the
+// whichever launch reads the samples -- the cascade, or the FFT in mode 0xB1 -- is handed the hop.  Everything else is the
 // frame call.
 static int launch_q15(sa_handle *h, const SaEntry &e, const void *in, void *out, int batch, void *stream,
                       const SaChecked &r)
@@ -482,9 +482,8 @@ static int launch_q15(sa_handle *h, const SaEntry &e, const void *in, void *out,
         return end_call(h, c);
     }
     if (!staged) {
-        SA_HIP(h, hop   ? sa_launch_fft_q15_hop(in, kind, hop, fft_out, batch, out_kind, p, t, c.stream, {c.start, fft_stop})
-                  : fft ? sa_launch_fft_q15(in, kind, fft_out, batch, out_kind, true, p, t, c.stream, {c.start, fft_stop})
-                        : sa_launch_filter_q15(in, kind, (int16_t *)out, batch, p, t, c.stream, {c.start, c.stop}));
+        SA_HIP(h, fft ? sa_launch_fft_q15(in, kind, hop, fft_out, batch, out_kind, true, p, t, c.stream, {c.start, fft_stop})
+                      : sa_launch_filter_q15(in, kind, hop, (int16_t *)out, batch, p, t, c.stream, {c.start, c.stop}));
         if (folded) SA_HIP(h, launch_fold(fft_out, nullptr));
         return end_call(h, c);
     }
@@ -498,9 +497,8 @@ static int launch_q15(sa_handle *h, const SaEntry &e, const void *in, void *out,
     }
     int16_t *ws = (int16_t *)h->slot[c.slot].work[sa_handle::kWorkQ15].ptr;
     // the packed form is read by the first launch alone: the workspace holds int16 samples whatever came in
-    SA_HIP(h, hop ? sa_launch_filter_q15_hop(in, kind, hop, ws, batch, p, t, c.stream, {c.start, nullptr})
-                  : sa_launch_filter_q15(in, kind, ws, batch, p, t, c.stream, {c.start, nullptr}));
-    SA_HIP(h, sa_launch_fft_q15(ws, SaInKind::I16, fft_out, batch, out_kind, false, p, t, c.stream, {nullptr, fft_stop}));
+    SA_HIP(h, sa_launch_filter_q15(in, kind, hop, ws, batch, p, t, c.stream, {c.start, nullptr}));
+    SA_HIP(h, sa_launch_fft_q15(ws, SaInKind::I16, 0, fft_out, batch, out_kind, false, p, t, c.stream, {nullptr, fft_stop}));
     if (folded) SA_HIP(h, launch_fold(fft_out, nullptr));
     return end_call(h, c);
 }

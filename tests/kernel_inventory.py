@@ -4,7 +4,8 @@ says of every instantiation how the suite knows it does not read LDS words it di
 
 hipcc emits one host function `__device_stub__<kernel>` per kernel instantiation of a unit; `nm -C` lists them demangled.
 The key used here is the kernel's name with its template arguments and without its argument list, the anonymous namespace
-dropped: "fft_q15_kernel<false, 128>", "chain_f32_kernel<SaP12, 4, true, 0, false, false, float>", "filter_w14_hop_kernel".
+dropped: "fft_q15_kernel<short, false, 128>", "chain_f32_kernel<SaP12, 4, true, 0, false, false, float>",
+"filter_w14_kernel<short, int>".
 
 TABLE classifies every key as exactly one of
   "float:<group>"       poisoned by test_poisoned_lds_float_chain[<group>]: the group's variant set holds a tuple whose
@@ -27,9 +28,9 @@ CSRC = os.path.join(ROOT, "fpga_real_time_fft_analyzer_amd", "csrc")
 STUB = "__device_stub__"
 
 
-def normalise(demangled):
-    """A demangled stub symbol -> the key: kernel name plus template arguments, the argument list dropped."""
-    s = demangled.replace("(anonymous namespace)::", "").split(STUB, 1)[1]
+def key_of(function):
+    """A demangled function, from its name on -> the key: name plus template arguments, the argument list dropped."""
+    s = function.replace("(anonymous namespace)::", "")
     name = re.match(r"\w+", s).group(0)
     rest = s[len(name):]
     if not rest.startswith("<"):
@@ -39,7 +40,12 @@ def normalise(demangled):
         depth += (c == "<") - (c == ">")
         if depth == 0:
             return name + rest[:i + 1]
-    raise ValueError(demangled)
+    raise ValueError(function)
+
+
+def normalise(demangled):
+    """A demangled stub symbol -> the key of its kernel."""
+    return key_of(demangled.replace("(anonymous namespace)::", "").split(STUB, 1)[1])
 
 
 def inventory(lib_path):
@@ -83,24 +89,35 @@ def float_kernels(variant):
     return (_chain_kernel(in_t, nsec, unit, wingen, one_round, kind),)
 
 
-Q15_FORM_SUFFIX = {"i16": "", "p12": "_p12", "i16_hop": "_hop", "p12_hop": "_hop_p12"}
-# call -> (OUT of fft_q15*_kernel, the fold launch behind it)
+# input form -> the template arguments that name it: (InT,) in front, and behind the kernel's own arguments the `int` of the
+# forms cut from one stream
+Q15_FORM_SUFFIX = {"i16": (("short",), ()), "p12": (("SaP12",), ()), "i16_hop": (("short",), ("int",)),
+                   "p12_hop": (("SaP12",), ("int",))}
+# call -> (OUT of fft_q15_kernel, the fold launch behind it)
 Q15_CALL = {"iq": (0, None), "mag": (1, None), "marker": (2, None), "trace": (16, None),
             "trace_avg": (128, "trace_fold_q15_kernel"), "spectra": (0, "spectra_fold_q15_kernel")}
 
 
+def _tmpl(name, *args):
+    return f"{name}<{', '.join(str(a) for a in args)}>"
+
+
 def q15_kernels(cascade, form, call):
     """The keys of the launches of one Q15 call, in order (specan_abi.cpp, launch_q15).  `cascade`: None in filter mode
-    0xB1, else the cascade kernel's stem and template arguments -- ("filter_q7", "<true>"), ("filter_q7", "<false>") or
-    ("filter_w14", ""); `form`: a key of Q15_FORM_SUFFIX; `call`: "filter" (filter_q15) or a key of Q15_CALL.  The input
-    form names the kernel that reads the samples; an FFT behind a cascade reads int16 frames from the workspace."""
-    sfx = Q15_FORM_SUFFIX[form]
-    first = None if cascade is None else f"{cascade[0]}{sfx}_kernel{cascade[1]}"
+    0xB1, else the cascade kernel's stem and its own template arguments, those between InT and the hop --
+    ("filter_q7", ("true",)), ("filter_q7", ("false",)) or ("filter_w14", ()); `form`: a key of Q15_FORM_SUFFIX; `call`:
+    "filter" (filter_q15) or a key of Q15_CALL.  The input form names the kernel that reads the samples; an FFT behind a
+    cascade reads int16 frames from the workspace."""
+    in_t, hop = Q15_FORM_SUFFIX[form]
+    first = None if cascade is None else _tmpl(f"{cascade[0]}_kernel", *in_t, *cascade[1], *hop)
     if call == "filter":
         assert "hop" not in form, "filter_q15 takes frames only"
-        return (f"window_q15{sfx}_kernel",) if first is None else (first,)
+        return (_tmpl("window_q15_kernel", *in_t),) if first is None else (first,)
     out, fold = Q15_CALL[call]
-    k = (f"fft_q15{sfx}_kernel<true, {out}>",) if first is None else (first, f"fft_q15_kernel<false, {out}>")
+    if first is None:
+        k = (_tmpl("fft_q15_kernel", *in_t, "true", out, *hop),)
+    else:
+        k = (first, _tmpl("fft_q15_kernel", "short", "false", out))
     return k + ((fold,) if fold else ())
 
 
@@ -110,7 +127,7 @@ def q15_kernels(cascade, form, call):
 # "LDS Size [bytes/block]: 0" -- and, because dynamic LDS shows as 0 in that remark (the FFT kernels prove it), the unit
 # and the headers it includes to no `extern __shared__` declaration (unit_text).
 NO_LDS_UNITS = {
-    "cascade_q15.hip": ("window_q15_kernel", "window_q15_p12_kernel"),
+    "cascade_q15.hip": ("window_q15_kernel<short>", "window_q15_kernel<SaP12>"),
     "trace_fold_q15.hip": ("trace_fold_q15_kernel",),
     "spectra_fold_q15.hip": ("spectra_fold_q15_kernel",),
     "sa_streams.cpp": ("sa_spin_kernel",),
@@ -135,9 +152,22 @@ def lds_remarks(unit):
     return out
 
 
+def demangled_keys(mangled):
+    """{mangled kernel name: its key} through c++filt, as inventory() has them from `nm -C`."""
+    filt = shutil.which("c++filt") or shutil.which("llvm-cxxfilt") or "/opt/rocm/llvm/bin/llvm-cxxfilt"
+    names = list(mangled)
+    r = subprocess.run([filt], input="\n".join(names), capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and len(r.stdout.splitlines()) == len(names), r.stderr
+    return {m: key_of(re.sub(r"^void ", "", d)) for m, d in zip(names, r.stdout.splitlines())}
+
+
 def lds_of(remarks, kernel):
-    """The LDS sizes of the instantiations of `kernel` among a unit's remarks: an Itanium-mangled name holds the source
-    name behind its length."""
+    """The LDS sizes of the instantiations of `kernel` among a unit's remarks.  A plain name: every instantiation of it (an
+    Itanium-mangled name holds the source name behind its length).  A key with template arguments: that instantiation
+    alone, found by demangling the remarks' names to keys."""
+    if "<" in kernel:
+        keys = demangled_keys(remarks)
+        return [v for k, v in remarks.items() if keys[k] == kernel]
     return [v for k, v in remarks.items() if f"{len(kernel)}{kernel}E" in k or f"{len(kernel)}{kernel}I" in k]
 
 
@@ -319,43 +349,43 @@ TABLE = {
     "chain_marker_kernel<short, 6, false, true, false, float>": "float:defaults",
     "chain_marker_kernel<short, 6, true, false, false, float>": "float:cascades_int16",
     "chain_marker_kernel<short, 6, true, true, false, float>": "float:cascades_int16",
-    "fft_q15_hop_kernel<true, 0>": "q15:bypass",
-    "fft_q15_hop_kernel<true, 128>": "q15:bypass",
-    "fft_q15_hop_kernel<true, 16>": "q15:bypass",
-    "fft_q15_hop_kernel<true, 1>": "q15:bypass",
-    "fft_q15_hop_kernel<true, 2>": "q15:bypass",
-    "fft_q15_hop_p12_kernel<true, 0>": "q15:bypass",
-    "fft_q15_hop_p12_kernel<true, 128>": "q15:bypass",
-    "fft_q15_hop_p12_kernel<true, 16>": "q15:bypass",
-    "fft_q15_hop_p12_kernel<true, 1>": "q15:bypass",
-    "fft_q15_hop_p12_kernel<true, 2>": "q15:bypass",
-    "fft_q15_kernel<false, 0>": "q15:default",
-    "fft_q15_kernel<false, 128>": "q15:default",
-    "fft_q15_kernel<false, 16>": "q15:default",
-    "fft_q15_kernel<false, 1>": "q15:default",
-    "fft_q15_kernel<false, 2>": "q15:default",
-    "fft_q15_kernel<true, 0>": "q15:bypass",
-    "fft_q15_kernel<true, 128>": "q15:bypass",
-    "fft_q15_kernel<true, 16>": "q15:bypass",
-    "fft_q15_kernel<true, 1>": "q15:bypass",
-    "fft_q15_kernel<true, 2>": "q15:bypass",
-    "fft_q15_p12_kernel<true, 0>": "q15:bypass",
-    "fft_q15_p12_kernel<true, 128>": "q15:bypass",
-    "fft_q15_p12_kernel<true, 16>": "q15:bypass",
-    "fft_q15_p12_kernel<true, 1>": "q15:bypass",
-    "fft_q15_p12_kernel<true, 2>": "q15:bypass",
-    "filter_q7_hop_kernel<false>": "q15:custom_b1",
-    "filter_q7_hop_kernel<true>": "q15:default",
-    "filter_q7_hop_p12_kernel<false>": "q15:custom_b1",
-    "filter_q7_hop_p12_kernel<true>": "q15:default",
-    "filter_q7_kernel<false>": "q15:custom_b1",
-    "filter_q7_kernel<true>": "q15:default",
-    "filter_q7_p12_kernel<false>": "q15:custom_b1",
-    "filter_q7_p12_kernel<true>": "q15:default",
-    "filter_w14_hop_kernel": "q15:wide6",
-    "filter_w14_hop_p12_kernel": "q15:wide6",
-    "filter_w14_kernel": "q15:wide6",
-    "filter_w14_p12_kernel": "q15:wide6",
+    "fft_q15_kernel<short, true, 0, int>": "q15:bypass",
+    "fft_q15_kernel<short, true, 128, int>": "q15:bypass",
+    "fft_q15_kernel<short, true, 16, int>": "q15:bypass",
+    "fft_q15_kernel<short, true, 1, int>": "q15:bypass",
+    "fft_q15_kernel<short, true, 2, int>": "q15:bypass",
+    "fft_q15_kernel<SaP12, true, 0, int>": "q15:bypass",
+    "fft_q15_kernel<SaP12, true, 128, int>": "q15:bypass",
+    "fft_q15_kernel<SaP12, true, 16, int>": "q15:bypass",
+    "fft_q15_kernel<SaP12, true, 1, int>": "q15:bypass",
+    "fft_q15_kernel<SaP12, true, 2, int>": "q15:bypass",
+    "fft_q15_kernel<short, false, 0>": "q15:default",
+    "fft_q15_kernel<short, false, 128>": "q15:default",
+    "fft_q15_kernel<short, false, 16>": "q15:default",
+    "fft_q15_kernel<short, false, 1>": "q15:default",
+    "fft_q15_kernel<short, false, 2>": "q15:default",
+    "fft_q15_kernel<short, true, 0>": "q15:bypass",
+    "fft_q15_kernel<short, true, 128>": "q15:bypass",
+    "fft_q15_kernel<short, true, 16>": "q15:bypass",
+    "fft_q15_kernel<short, true, 1>": "q15:bypass",
+    "fft_q15_kernel<short, true, 2>": "q15:bypass",
+    "fft_q15_kernel<SaP12, true, 0>": "q15:bypass",
+    "fft_q15_kernel<SaP12, true, 128>": "q15:bypass",
+    "fft_q15_kernel<SaP12, true, 16>": "q15:bypass",
+    "fft_q15_kernel<SaP12, true, 1>": "q15:bypass",
+    "fft_q15_kernel<SaP12, true, 2>": "q15:bypass",
+    "filter_q7_kernel<short, false, int>": "q15:custom_b1",
+    "filter_q7_kernel<short, true, int>": "q15:default",
+    "filter_q7_kernel<SaP12, false, int>": "q15:custom_b1",
+    "filter_q7_kernel<SaP12, true, int>": "q15:default",
+    "filter_q7_kernel<short, false>": "q15:custom_b1",
+    "filter_q7_kernel<short, true>": "q15:default",
+    "filter_q7_kernel<SaP12, false>": "q15:custom_b1",
+    "filter_q7_kernel<SaP12, true>": "q15:default",
+    "filter_w14_kernel<short, int>": "q15:wide6",
+    "filter_w14_kernel<SaP12, int>": "q15:wide6",
+    "filter_w14_kernel<short>": "q15:wide6",
+    "filter_w14_kernel<SaP12>": "q15:wide6",
     "iir_f64_kernel<0, SaP12>": UNREACHABLE_F64,
     "iir_f64_kernel<0, float>": UNREACHABLE_F64,
     "iir_f64_kernel<0, short>": UNREACHABLE_F64,
@@ -392,6 +422,6 @@ TABLE = {
     "time_f32_kernel<short, 6, false, float>": "float:defaults",
     "time_f32_kernel<short, 6, true, float>": "float:cascades_int16",
     "trace_fold_q15_kernel": "exempt: no LDS (trace_fold_q15.hip: one record per thread, registers only)",
-    "window_q15_kernel": "exempt: no LDS (cascade_q15.hip: element-wise, eight samples per thread)",
-    "window_q15_p12_kernel": "exempt: no LDS (cascade_q15.hip: element-wise, eight samples per thread)",
+    "window_q15_kernel<short>": "exempt: no LDS (cascade_q15.hip: element-wise, eight samples per thread)",
+    "window_q15_kernel<SaP12>": "exempt: no LDS (cascade_q15.hip: element-wise, eight samples per thread)",
 }

@@ -16,7 +16,7 @@ cancels it arithmetically passes them all: 0 * x = 0 for finite garbage.  Here t
     pinned sets to the symbol table of the built library: a kernel form added to the library fails the CPU suite until a
     case here poisons it.
   - What the poison reaches in a call of more than one launch.  lds_fill precedes the FIRST kernel only.  A second
-    kernel (fft_q15_kernel<false, OUT> behind a cascade, the bypassed float chain behind iir_f64_kernel, a fold) meets the
+    kernel (fft_q15_kernel<short, false, OUT> behind a cascade, the bypassed float chain behind iir_f64_kernel, a fold) meets the
     poison on every CU the first kernel's few workgroups did not occupy -- at B = 17 the cascade has 2 workgroups and the
     FFT 17, so 15 FFT workgroups at least start on untouched, fully poisoned LDS -- and on the others it meets poison in
     the part of its 64 KiB that the cascade's 33-50 KiB did not overwrite, and the cascade's residue (finite samples) in
@@ -345,15 +345,15 @@ def test_float_poison_groups_cover_every_form():
 C12_B1 = np.array([0, 1, 0, 64, -67, 19, 64, 127, 64, 64, -85, 40], np.int8)          # B1 != 0: the long step
 C12_NOB1 = np.array([32, 0, -32, 64, -67, 19, 64, 0, 64, 64, -85, 40], np.int8)       # B1 = 0 in both sets
 
-# label -> (filter mode, Q7 upload, Q2.14 sections, the cascade kernel: stem and template arguments, None = no cascade)
+# label -> (filter mode, Q7 upload, Q2.14 sections, the cascade kernel: stem and its own template arguments, None = no cascade)
 Q15_CASES = {
     "bypass": (0xB1, None, 0, None),
-    "default": (0x00, None, 0, ("filter_q7", "<true>")),
-    "custom_nob1": (0xA1, C12_NOB1, 0, ("filter_q7", "<true>")),
-    "custom_b1": (0xA1, C12_B1, 0, ("filter_q7", "<false>")),
-    "wide1": (0xA2, None, 1, ("filter_w14", "")),
-    "wide3": (0xA2, None, 3, ("filter_w14", "")),
-    "wide6": (0xA2, None, 6, ("filter_w14", "")),
+    "default": (0x00, None, 0, ("filter_q7", ("true",))),
+    "custom_nob1": (0xA1, C12_NOB1, 0, ("filter_q7", ("true",))),
+    "custom_b1": (0xA1, C12_B1, 0, ("filter_q7", ("false",))),
+    "wide1": (0xA2, None, 1, ("filter_w14", ())),
+    "wide3": (0xA2, None, 3, ("filter_w14", ())),
+    "wide6": (0xA2, None, 6, ("filter_w14", ())),
 }
 Q15_HOP = 4104                  # 8 * 513: the packed frames of a stream alternate between 8-byte aligned and not
 Q15_FORMS = ("i16", "p12", "i16_hop", "p12_hop")       # int16 frames, packed frames, an int16 stream at a hop, a packed one
@@ -402,10 +402,10 @@ def _launched_q15(ch, nsec_wide, xd, hop, call):
     if mode == 0xB1 or (mode == 0xA2 and nsec_wide == 0):
         cascade = None
     elif mode == 0xA2:
-        cascade = ("filter_w14", "")
+        cascade = ("filter_w14", ())
     else:
         c = ch.coeffs_q7()
-        cascade = ("filter_q7", "<true>" if mode == 0x00 or (c[1] == 0 and c[7] == 0) else "<false>")
+        cascade = ("filter_q7", ("true" if mode == 0x00 or (c[1] == 0 and c[7] == 0) else "false",))
     return q15_kernels(cascade, form, call)
 
 
@@ -580,7 +580,8 @@ def test_kernel_inventory_is_classified(hip_lib_built):
             sizes = lds_of(remarks[unit], k)
             assert sizes == [0], (unit, k, sizes, sorted(remarks[unit]))
             proven.add(k)
-    assert "extern __shared__" in unit_text("fft_q15.hip")          # the search sees through includes: the FFT's is in its .inc
+    assert "extern __shared__" in unit_text("fft_q15.hip")          # the search finds the FFT's dynamic LDS ...
+    assert "extern __shared__" in unit_text("chain_f32.hip")        # ... and through includes: the float chain's is in chain_f32.hpp
     assert {k for k, c in classes.items() if c == "exempt"} == proven
     # every other kernel is launched by a pinned variant, and no pinned variant launches a kernel the library lacks
     launched = set().union(*poisoned.values())

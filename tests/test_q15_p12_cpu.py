@@ -79,7 +79,7 @@ def test_fft_stage0_address_map():
 
 
 def test_tile_unit_address_map():
-    """q15_load_tile / window_q15_p12_kernel: samples 8 u .. 8 u + 7 are the 12 bytes at byte 3 (8 u) / 2 = 12 u, three
+    """q15_load_tile / window_q15_kernel<SaP12>: samples 8 u .. 8 u + 7 are the 12 bytes at byte 3 (8 u) / 2 = 12 u, three
     aligned dwords that end with the frame at the latest; p12_unpack8 takes them apart."""
     from fpga_real_time_fft_analyzer_amd.ingest import unpack12
     u = np.arange(N // 8)
