@@ -1,5 +1,5 @@
 """ctypes binding of ``libspecan_hip.so`` (the C ABI declared in ``include/specan.h`` and ``include/specan_ext.h``) and of
-``libspecan_fold.so`` (``include/specan_fold.h``).
+``libspecan_fold.so`` (``include/specan_fold.h``) and ``libspecan_peaks.so`` (``include/specan_peaks.h``).
 
 This is the only place the shared libraries are loaded.  There is no CPU fallback: if the
 library is missing the import of any compute entry point raises, and creating a handle
@@ -14,6 +14,7 @@ import subprocess
 _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_PKG, "libspecan_hip.so")
 FOLD_LIB_PATH = os.path.join(_PKG, "libspecan_fold.so")      # include/specan_fold.h: built by the same make
+PEAKS_LIB_PATH = os.path.join(_PKG, "libspecan_peaks.so")    # include/specan_peaks.h: built by the same make
 CSRC = os.path.join(_PKG, "csrc")
 
 # error codes / constants (include/specan.h)
@@ -78,8 +79,8 @@ class SpecanError(RuntimeError):
 
 
 def build(verbose: bool = False) -> str:
-    """Compile the HIP extension in-tree for gfx950 (hipcc cross-compiles without a GPU): both libraries, LIB_PATH and
-    FOLD_LIB_PATH, are the Makefile's first target."""
+    """Compile the HIP extension in-tree for gfx950 (hipcc cross-compiles without a GPU): the three libraries, LIB_PATH,
+    FOLD_LIB_PATH and PEAKS_LIB_PATH, are the Makefile's first target."""
     cmd = ["make", "-j4", "-C", CSRC]
     if not verbose:
         cmd.insert(1, "-s")
@@ -165,8 +166,22 @@ FOLD_SIGNATURES = {
     "sa_fold_last_error": (C.c_char_p, []),
 }
 
+# the entry points of include/specan_peaks.h: libspecan_peaks.so, the third product library, again without a handle (the K
+# strongest local maxima of each row of 16384 points), bound by peaks_lib() and held name for name against that header
+# (tests/test_f32_peaks_cpu.py); no name is in the three tables above
+SA_PEAKS_VERSION = 1
+SA_PEAKS_K_MAX = 32
+SA_PEAKS_IN_MAG, SA_PEAKS_IN_POINT_PEAK, SA_PEAKS_IN_POINT_POWER = 0, 1, 2
+PEAKS_SIGNATURES = {
+    "sa_peaks_version": (_INT, []),
+    "sa_peaks_f32": (_INT, [C.c_void_p, _INT, C.c_void_p, C.c_void_p, _INT, _INT, C.c_float, _INT, _INT, _INT, C.c_void_p]),
+    "sa_peaks_check": (_INT, [_INT, C.c_uint64, C.c_uint64, C.c_uint64, _INT, _INT, C.c_uint32, _INT, _INT, _INT]),
+    "sa_peaks_last_error": (C.c_char_p, []),
+}
+
 _lib = None
 _fold_lib = None
+_peaks_lib = None
 
 
 def _load(path: str, tables: tuple) -> C.CDLL:
@@ -205,3 +220,11 @@ def fold_lib() -> C.CDLL:
     if _fold_lib is None:
         _fold_lib = _load(FOLD_LIB_PATH, (FOLD_SIGNATURES,))
     return _fold_lib
+
+
+def peaks_lib() -> C.CDLL:
+    """Load libspecan_peaks.so (include/specan_peaks.h), after torch as lib() does; raise loudly when it has not been built."""
+    global _peaks_lib
+    if _peaks_lib is None:
+        _peaks_lib = _load(PEAKS_LIB_PATH, (PEAKS_SIGNATURES,))
+    return _peaks_lib

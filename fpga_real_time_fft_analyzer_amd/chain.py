@@ -130,6 +130,8 @@ Q15_FOLD_CHAIN = _Chain(_SPECTRA_OUT, {torch.int16: _form((SA_N, 2), _SPECTRA_OU
 # the fold of float magnitudes (include/specan_fold.h; fold_mag_f32, spectra_f32): a call of libspecan_fold.so, which takes
 # no handle and is no row of the tables above -- the float chain's own call writes the magnitudes it reads
 FOLD_GROUPS, FOLD_BUCKETS = frames.FOLD_GROUPS, frames.FOLD_BUCKETS         # 1 .. 128 and 1 .. 64: the mirror's, defined once
+# find_peaks(field=...) -> the `field` of include/specan_peaks.h: plain magnitudes, or one float of (peak, power) records
+_PEAK_FIELDS = {None: abi.SA_PEAKS_IN_MAG, "peak": abi.SA_PEAKS_IN_POINT_PEAK, "power": abi.SA_PEAKS_IN_POINT_POWER}
 
 
 def output_spec(chain: _Chain, out_kind: Optional[str], B: int) -> tuple:
@@ -640,6 +642,12 @@ class SpectrumChain:
         dtype = x.dtype if isinstance(x, torch.Tensor) and x.dtype in forms else next(iter(forms))
         B = self._check_in(x, dtype, forms[dtype][0])
         out = self._fold_out(B, int(group), int(bucket), out)
+        mag = self._mag_full_in_work(x, B, scale, work)
+        return self.fold_mag_f32(mag, group, bucket, out)
+
+    def _mag_full_in_work(self, x: torch.Tensor, B: int, scale: float, work: Optional[torch.Tensor]) -> torch.Tensor:
+        """``process_f32(x, 'mag_full')`` of B frames into ``work`` or, when None, the cached workspace (regrown when B grows),
+        joined with the current stream where overlap is on: what :meth:`spectra_f32` and :meth:`peak_table_f32` reduce."""
         if work is None:
             if self._fold_work is None or self._fold_work.shape[0] < B:
                 self._fold_work = None               # released before the larger one is taken
@@ -650,8 +658,110 @@ class SpectrumChain:
             raise SpecanError(abi.SA_ESHAPE, f"work must be a contiguous torch.float32 tensor of shape [{B} or more, {SA_N}]")
         mag = self.process_f32(x, out=work[:B], out_kind="mag_full", scale=scale)
         if self._depth > 1:
-            self.flush()                             # the fold reads what an internal stream of the library writes
-        return self.fold_mag_f32(mag, group, bucket, out)
+            self.flush()                             # the reduction reads what an internal stream of the library writes
+        return mag
+
+    @staticmethod
+    def _peaks_args(k, threshold, lo, hi, min_sep, field) -> int:
+        """The one validation of the arguments of the peak table: the ``field`` code of include/specan_peaks.h, or SA_EINVAL."""
+        for name, v in (("k", k), ("lo", lo), ("hi", hi), ("min_sep", min_sep)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise SpecanError(abi.SA_EINVAL, f"{name} must be an int")
+        if not 1 <= int(k) <= abi.SA_PEAKS_K_MAX:
+            raise SpecanError(abi.SA_EINVAL, f"k must be 1..{abi.SA_PEAKS_K_MAX}")
+        if isinstance(threshold, bool) or not isinstance(threshold, (int, float, np.integer, np.floating)):
+            raise SpecanError(abi.SA_EINVAL, "threshold must be a number")
+        if int(np.array([threshold], np.float32).view(np.uint32)[0]) > 0x7F800000:
+            raise SpecanError(abi.SA_EINVAL, "threshold must be +0.0 .. +inf: no NaN, no sign bit")
+        if not 0 <= int(lo) < int(hi) <= SA_N:
+            raise SpecanError(abi.SA_EINVAL, f"the range must be 0 <= lo < hi <= {SA_N}")
+        if not 1 <= int(min_sep) <= SA_N:
+            raise SpecanError(abi.SA_EINVAL, f"min_sep must be 1..{SA_N}")
+        if not (field is None or isinstance(field, str)) or field not in _PEAK_FIELDS:
+            raise SpecanError(abi.SA_EINVAL, "field must be None, 'peak' or 'power'")
+        return _PEAK_FIELDS[field]
+
+    def _peaks_out(self, R: int, k: int, out: Optional[torch.Tensor]) -> torch.Tensor:
+        """``out`` of the peak table of ``R`` rows, allocated when None: SA_ESHAPE where it is not the contiguous int32 [R, k, 2]
+        tensor on the handle's device."""
+        shape = (R, k, 2)
+        if out is None:
+            return torch.empty(shape, dtype=torch.int32, device=self.device)
+        if (not isinstance(out, torch.Tensor) or tuple(out.shape) != shape or out.dtype != torch.int32
+                or out.device != self.device or not out.is_contiguous()):
+            raise SpecanError(abi.SA_ESHAPE, f"out must be a contiguous torch.int32 tensor of shape {shape}")
+        return out
+
+    def find_peaks(self, t: torch.Tensor, k: int = 8, threshold: float = 0.0, lo: int = 0, hi: int = SA_N, min_sep: int = 1,
+                   field: Optional[str] = None, out: Optional[torch.Tensor] = None) -> tuple:
+        """The peak table of each row of ``t`` (include/specan_peaks.h, sa_peaks_f32): the ``k`` strongest local maxima with
+        their bins.  ``t`` is a float32 [R,16384] device tensor -- what ``process_f32(out_kind='mag_full')`` or
+        ``process_q15(out_kind='mag')`` wrote -- or, with ``field='peak'`` or ``field='power'``, float32 [R,16384,2], the
+        records of :meth:`fold_mag_f32` at bucket 1, :meth:`spectra_f32` or :meth:`spectra_q15`, of which that float is the
+        point.  Returns ``(mag float32 [R,k], bin int32 [R,k], count int32 [R])``: mag and bin are views of the [R,k,2] int32
+        record tensor (``out``, allocated when None; one sa_peak per slot), count is allocated by the call.
+
+        A point's key is its bits with the sign cleared, as an integer: the float order of the chains' non-negative values; a
+        NaN shows above +inf, -0.0 reads as +0.0, no denormal is flushed.  Bin i is a candidate when ``lo <= i < hi``, its key
+        is not 0 and not below that of ``threshold``, above that of bin i-1 and not below that of bin i+1 (the row's
+        neighbours, in the range or not; bins 0 and 16383 lack one, which then agrees): a plateau gives its lowest bin.  The
+        candidates are walked by larger key, then lower bin, and one is accepted when it lies ``min_sep`` or more bins from
+        every one accepted before; the first ``k`` accepted are the records, in that order, the unused slots (+0.0, -1).
+        ``count`` is the number of candidates before suppression and truncation.  frames.peaks_of_rows is the numpy mirror,
+        bit for bit.  With k = 1, threshold 0 and the full range the record is (peak_mag, peak_bin) of :meth:`markers` /
+        :meth:`markers_q15` on the same frames, wherever that peak is not zero.
+
+        ``k`` is 1..32, ``threshold`` not negative and no NaN, ``0 <= lo < hi <= 16384``, ``min_sep`` 1..16384; k, lo, hi and
+        min_sep take ints only (a bool or a float is SA_EINVAL); a wrong dtype is SA_EINVAL and a wrong shape SA_ESHAPE, all
+        before any device call.  One launch on the current stream of the handle's device, no handle state, no workspace: it
+        captures into a graph at any time (count then lives in the graph's pool, like an ``out`` the call allocates).  Where
+        ``t`` is the result of a call made in overlap mode, call :meth:`flush` first.  Pointer contract
+        (checked by the C entry point, SA_EINVAL): ``t`` is 16-byte aligned, and the bytes read and the R * k * 8 and R * 4
+        bytes written are disjoint; buffers that merely touch are fine."""
+        code = self._peaks_args(k, threshold, lo, hi, min_sep, field)
+        R = self._check_in(t, torch.float32, (SA_N, 2) if code else SA_N)
+        out = self._peaks_out(R, int(k), out)
+        count = torch.empty((R,), dtype=torch.int32, device=self.device)
+        L = abi.peaks_lib()
+        with torch.cuda.device(self.device):         # the C call launches on the calling thread's current device
+            rc = L.sa_peaks_f32(t.data_ptr(), code, out.data_ptr(), count.data_ptr(), R, int(k), float(threshold), int(lo),
+                                int(hi), int(min_sep), self._stream())
+        if rc != abi.SA_OK:
+            raise SpecanError(rc, L.sa_peaks_last_error().decode())
+        return out.view(torch.float32)[..., 0], out[..., 1], count
+
+    def peak_table_f32(self, x: torch.Tensor, k: int = 8, threshold: float = 0.0, lo: int = 0, hi: int = SA_N,
+                       min_sep: int = 1, group: Optional[int] = None, scale: float = 1.0 / 2048.0,
+                       work: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> tuple:
+        """The peak table of the float chain's spectra, without the spectra leaving the device: ``(mag float32 [R,k], bin
+        int32 [R,k], count int32 [R])`` as :meth:`find_peaks` returns them.  ``x`` is float32, int16 or packed uint8 exactly
+        as for :meth:`process_f32`; every filter mode and both precisions apply.
+
+        Without ``group`` (R = B) the call is ``process_f32(x, out_kind='mag_full', scale=scale)`` into the workspace of
+        :meth:`spectra_f32` followed by :meth:`find_peaks`: the peaks of every frame's magnitudes.  With ``group=A`` (2, 4,
+        ..., 128; R = B // A) it is ``spectra_f32(x, group=A, scale=scale, work=work)`` followed by ``find_peaks(...,
+        field='power')``: the peaks of the summed power of every A consecutive frames, the Welch estimate times A (mag is that
+        sum).
+
+        The workspace is ``work`` or the cached tensor, as for :meth:`spectra_f32`, and in overlap mode the call joins every
+        outstanding call of the handle on the device (as :meth:`flush` does) before the find: the result is valid on the
+        current stream when the call returns, and the call lends nothing.  The arguments of the find and ``out`` are refused
+        as by :meth:`find_peaks`, ``group`` and a B that is no multiple of it as by :meth:`spectra_f32`, all before anything
+        is launched, and so is a wrong ``work``."""
+        self._peaks_args(k, threshold, lo, hi, min_sep, None)
+        if group is not None:
+            self._log2_fold(group, 1)
+        forms = FLOAT_CHAIN.inputs
+        dtype = x.dtype if isinstance(x, torch.Tensor) and x.dtype in forms else next(iter(forms))
+        B = self._check_in(x, dtype, forms[dtype][0])
+        if group is not None:
+            if B % int(group):
+                raise SpecanError(abi.SA_ESHAPE, f"the batch ({B} frames) must be a multiple of {int(group)}")
+            out = self._peaks_out(B // int(group), int(k), out)      # refused here, before the chain is launched
+            rec = self.spectra_f32(x, group, 1, scale=scale, work=work)
+            return self.find_peaks(rec, k, threshold, lo, hi, min_sep, field="power", out=out)
+        out = self._peaks_out(B, int(k), out)
+        return self.find_peaks(self._mag_full_in_work(x, B, scale, work), k, threshold, lo, hi, min_sep, out=out)
 
     def filter_q15(self, x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Window (+ integer IIR) only: the FFT input stream, [B,16384] int16.  ``x`` is [B,16384] int16 or the same

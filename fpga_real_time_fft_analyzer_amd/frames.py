@@ -133,6 +133,57 @@ def fold_of_mags(mag, group: int, bucket: int):
     return peak, power, t
 
 
+PEAKS_K_MAX = 32
+
+
+def peaks_of_rows(points, k: int = 8, threshold: float = 0.0, lo: int = 0, hi: int = FFT_SIZE, min_sep: int = 1):
+    """The peak table of float32 ``points`` [R,16384]: ``(mag float32 [R,k], bin int32 [R,k], count int32 [R])``.  The numpy
+    mirror of sa_peaks_f32 (include/specan_peaks.h), step for step:
+
+    - key: the float's bits with the sign cleared, as a uint32 -- +inf above every finite value, a NaN above +inf, -0.0 as
+      +0.0, denormals kept;
+    - candidate: ``lo <= i < hi``, ``u[i] > 0``, ``u[i] >= key(threshold)``, ``u[i] > u[i-1]`` and ``u[i] >= u[i+1]``, the
+      neighbours those of the row whether or not they lie in the range, a missing neighbour (i = 0, i = 16383) satisfying its
+      condition; count is their number;
+    - selection: the candidates sorted by larger key, then lower bin (the sort), walked in that order (the explicit loop): one
+      is accepted when it lies ``min_sep`` or more bins from every one accepted before it, until ``k`` are; a candidate that
+      was not accepted suppresses nothing;
+    - the records in acceptance order, mag the point with its sign cleared; the unused slots are (+0.0, -1).
+
+    ``k`` is 1..32, ``threshold`` no NaN and not negative (-0.0 included), ``0 <= lo < hi <= 16384``, ``min_sep`` 1..16384, the
+    integers ints (no bool, no float): ValueError otherwise."""
+    for name, v in (("k", k), ("lo", lo), ("hi", hi), ("min_sep", min_sep)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f"{name} must be an int")
+    k, lo, hi, min_sep = int(k), int(lo), int(hi), int(min_sep)
+    tkey = int(np.array([threshold], np.float32).view(np.uint32)[0])
+    if not 1 <= k <= PEAKS_K_MAX or tkey > 0x7F800000 or not 0 <= lo < hi <= FFT_SIZE or not 1 <= min_sep <= FFT_SIZE:
+        raise ValueError("k must be 1..32, threshold +0.0..+inf, 0 <= lo < hi <= 16384 and min_sep 1..16384")
+    points = np.ascontiguousarray(points)
+    if points.dtype != np.float32 or points.ndim != 2 or points.shape[1] != FFT_SIZE:
+        raise ValueError("points must be float32 [R, 16384]")
+    R = points.shape[0]
+    u = (points.view(np.uint32) & np.uint32(0x7FFFFFFF)).astype(np.int64)
+    left = np.concatenate([np.full((R, 1), -1, np.int64), u[:, :-1]], axis=1)      # below every key: the missing neighbours
+    right = np.concatenate([u[:, 1:], np.full((R, 1), -1, np.int64)], axis=1)
+    i = np.arange(FFT_SIZE)
+    cand = (i >= lo) & (i < hi) & (u > 0) & (u >= tkey) & (u > left) & (u >= right)
+    mag = np.zeros((R, k), np.uint32)
+    bins = np.full((R, k), -1, np.int32)
+    for r in range(R):
+        c = np.nonzero(cand[r])[0]
+        order = c[np.lexsort((c, -u[r, c]))]          # larger key first, then lower bin
+        taken = []
+        for p in order:
+            if all(abs(int(p) - q) >= min_sep for q in taken):
+                taken.append(int(p))
+                if len(taken) == k:
+                    break
+        mag[r, :len(taken)] = u[r, taken]
+        bins[r, :len(taken)] = taken
+    return mag.view(np.float32), bins, cand.sum(axis=1).astype(np.int32)
+
+
 def decode_iq_components(frame_bytes: bytes):
     """Same result as gui.py:262-270: (re, im) as float32 arrays."""
     re, im = _iq(frame_bytes)

@@ -1,0 +1,478 @@
+"""CPU: the peak table (include/specan_peaks.h: sa_peaks_f32 of libspecan_peaks.so; SpectrumChain.find_peaks and
+peak_table_f32) as far as no GPU is needed: the numpy mirror frames.peaks_of_rows against probes whose expected records are
+worked out by hand below, never from the code under test; the header against the built library and the binding table
+abi.PEAKS_SIGNATURES; the kernels the three libraries hold; the refusals through sa_peaks_check with made-up addresses
+(every expected answer follows from the words of the header); the same arithmetic in a stand-alone program under the host
+sanitizers; and the compiler's resource remarks."""
+import ctypes
+import itertools
+import os
+import re
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+from conftest import N, ROOT
+from kernel_inventory import HIPCC_FLAGS, TABLE, inventory, unit_text
+
+SA_OK, SA_EINVAL, SA_ESHAPE = 0, -1, -2
+BASE = (1 << 47) - (1 << 36)
+FAR = BASE + (1 << 40)
+FAR2 = BASE + (1 << 41)
+INCLUDE = os.path.join(ROOT, "include")
+HEADER = os.path.join(INCLUDE, "specan_peaks.h")
+CSRC = os.path.join(ROOT, "fpga_real_time_fft_analyzer_amd", "csrc")
+NAMES = ["sa_peaks_check", "sa_peaks_f32", "sa_peaks_last_error", "sa_peaks_version"]
+NAN_KEY = 0x7FC00000
+
+
+def bits(x):
+    return np.ascontiguousarray(x, np.float32).view(np.uint32)
+
+
+def key(v):
+    """the key of one value: its float32 bits with the sign cleared"""
+    return int(bits(np.float32(v)).ravel()[0]) & 0x7FFFFFFF
+
+
+def row_of(pairs):
+    """one otherwise zero row with the (bin, value) pairs planted"""
+    r = np.zeros((1, N), np.float32)
+    for b, v in pairs:
+        r[0, b] = v
+    return r
+
+
+def table(points, *args, **kw):
+    """the mirror's records of a one-row input as [(key, bin), ...] without the unused slots, and the count"""
+    from fpga_real_time_fft_analyzer_amd import frames
+    mag, bins, count = frames.peaks_of_rows(points, *args, **kw)
+    assert mag.dtype == np.float32 and bins.dtype == np.int32 and count.dtype == np.int32
+    assert mag.shape == bins.shape and count.shape == (points.shape[0],)
+    k = mag.shape[1]
+    used = int((bins[0] >= 0).sum())
+    assert (bins[0, used:] == -1).all() and not bits(mag)[0, used:].any()        # the rest: (+0.0, -1)
+    assert used <= k
+    return [(int(bits(mag)[0, i]), int(bins[0, i])) for i in range(used)], int(count[0])
+
+
+# ------------------------------------------------------------------------------------------------------------- the mirror
+def test_plateaus():
+    """The five conditions look one bin to each side and no further.  A plateau gives its lowest bin, the only one above its
+    left neighbour.  That holds whatever follows the plateau: where it ends in a rise, its lowest bin still passes
+    u[i] > u[i-1] and u[i] >= u[i+1] and is a candidate by the header's definition, beside the bin the rise leads to; what
+    the rise rules out is every other bin of the plateau, the one next to the rise included -- from the plateau's second bin
+    on there is no candidate."""
+    # 5 5 5 at bins 100..102: only bin 100 is above its left neighbour; 101 and 102 are not
+    assert table(row_of([(100, 5), (101, 5), (102, 5)]), 4) == ([(key(5), 100)], 1)
+    # a plateau followed by a rise, 5 5 7: bin 100 (0 < 5 >= 5) and bin 102 (5 < 7 >= 0); bin 101 is not above bin 100
+    assert table(row_of([(100, 5), (101, 5), (102, 7)]), 4) == ([(key(7), 102), (key(5), 100)], 2)
+    # the same from the plateau's second bin on: no candidate there (bin 101 is not above bin 100, and is below bin 102)
+    assert table(row_of([(100, 5), (101, 5), (102, 7)]), 4, lo=101, hi=102) == ([], 0)
+    assert table(row_of([(200, 3), (201, 3), (202, 3), (203, 9)]), 4, lo=201, hi=203) == ([], 0)
+    # a rise, a plateau, a rise: 2 3 3 4 -- bin 301 (2 < 3 >= 3) and bin 303
+    assert table(row_of([(300, 2), (301, 3), (302, 3), (303, 4)]), 4) == ([(key(4), 303), (key(3), 301)], 2)
+    # a plateau that ends in a fall is one peak: 2 6 6 6 1
+    assert table(row_of([(400, 2), (401, 6), (402, 6), (403, 6), (404, 1)]), 4) == ([(key(6), 401)], 1)
+
+
+def test_bins_0_and_16383():
+    # the missing neighbour satisfies its condition: a lone value at either end is a peak
+    assert table(row_of([(0, 2)]), 2) == ([(key(2), 0)], 1)
+    assert table(row_of([(N - 1, 2)]), 2) == ([(key(2), N - 1)], 1)
+    # bin 0 with an equal bin 1: u[0] >= u[1] holds, bin 1 is not above bin 0
+    assert table(row_of([(0, 2), (1, 2)]), 2) == ([(key(2), 0)], 1)
+    # bin 16383 with an equal bin 16382: the lower bin of the plateau
+    assert table(row_of([(N - 2, 2), (N - 1, 2)]), 2) == ([(key(2), N - 2)], 1)
+    # rising into the end / falling from the start
+    assert table(row_of([(N - 2, 2), (N - 1, 3)]), 2) == ([(key(3), N - 1)], 1)
+    assert table(row_of([(0, 2), (1, 3)]), 2) == ([(key(3), 1)], 1)
+    # both ends and the order between them: larger key first
+    assert table(row_of([(0, 2), (N - 1, 3)]), 2) == ([(key(3), N - 1), (key(2), 0)], 2)
+
+
+def test_adjacent_bins_are_never_both_candidates():
+    # 4 6 at 50, 51: 50 is below 51.  6 4 at 60, 61: 61 is below 60.  7 7 at 70, 71: only 70
+    assert table(row_of([(50, 4), (51, 6), (60, 6), (61, 4), (70, 7), (71, 7)]), 8) == \
+        ([(key(7), 70), (key(6), 51), (key(6), 60)], 3)
+    rng = np.random.default_rng(1700)
+    from fpga_real_time_fft_analyzer_amd import frames
+    pts = rng.integers(0, 4, size=(2, N)).astype(np.float32)      # many ties and zeros
+    u = bits(pts).astype(np.int64)
+    for r in range(2):
+        c = [i for i in range(N) if u[r, i] > 0 and (i == 0 or u[r, i] > u[r, i - 1]) and (i == N - 1 or u[r, i] >= u[r, i + 1])]
+        assert not set(c) & {i + 1 for i in c}
+        _, _, count = frames.peaks_of_rows(pts[r:r + 1], 1)
+        assert count[0] == len(c)
+
+
+def test_equal_keys_lower_bin_first_also_through_the_kth_slot():
+    pairs = [(900, 3), (300, 3), (600, 3), (100, 1), (1200, 8)]
+    assert table(row_of(pairs), 8) == ([(key(8), 1200), (key(3), 300), (key(3), 600), (key(3), 900), (key(1), 100)], 5)
+    assert table(row_of(pairs), 3) == ([(key(8), 1200), (key(3), 300), (key(3), 600)], 5)     # K cuts the tie: the lower bins
+    assert table(row_of(pairs), 2) == ([(key(8), 1200), (key(3), 300)], 5)
+    assert table(row_of(pairs), 1) == ([(key(8), 1200)], 5)
+
+
+def test_threshold_equal_to_a_key_and_one_ulp_above():
+    v = np.float32(2.5)
+    up = np.nextafter(v, np.float32(np.inf), dtype=np.float32)
+    assert bits(up)[()] == bits(v)[()] + 1
+    pts = row_of([(40, v), (80, 9)])
+    assert table(pts, 4, threshold=float(v)) == ([(key(9), 80), (key(v), 40)], 2)      # u >= key(threshold): kept
+    assert table(pts, 4, threshold=float(up)) == ([(key(9), 80)], 1)
+    assert table(pts, 4, threshold=10.0) == ([], 0)                                    # above the row's maximum
+    assert table(pts, 4, threshold=float("inf")) == ([], 0)
+
+
+def test_the_range_and_its_outside():
+    # a larger neighbour outside [lo, hi): bin 500 is not a peak although it is the largest inside
+    assert table(row_of([(499, 7), (500, 5)]), 4, lo=500, hi=600) == ([], 0)
+    assert table(row_of([(500, 5), (501, 7)]), 4, lo=400, hi=501) == ([], 0)
+    # an equal right neighbour outside is fine, an equal left one is not
+    assert table(row_of([(500, 5), (501, 5)]), 4, lo=400, hi=501) == ([(key(5), 500)], 1)
+    assert table(row_of([(499, 5), (500, 5)]), 4, lo=500, hi=600) == ([], 0)
+    # a candidate outside the range suppresses nothing: 9 at 98 is out, 5 at 100 is in and found with min_sep 50
+    assert table(row_of([(98, 9), (100, 5)]), 4, lo=100, hi=200, min_sep=50) == ([(key(5), 100)], 1)
+    # lo and hi are inclusive and exclusive
+    pts = row_of([(100, 5), (200, 6), (300, 7)])
+    assert table(pts, 4, lo=100, hi=300) == ([(key(6), 200), (key(5), 100)], 2)
+    assert table(pts, 4, lo=101, hi=301) == ([(key(7), 300), (key(6), 200)], 2)
+
+
+def test_greedy_order_of_the_suppression():
+    pts = row_of([(100, 10), (103, 9), (106, 8)])
+    # 100 is accepted; 103 is 3 < 4 from it: rejected, and suppresses nothing; 106 is 6 from 100: accepted
+    assert table(pts, 8, min_sep=4) == ([(key(10), 100), (key(8), 106)], 3)
+    assert table(pts, 8, min_sep=3) == ([(key(10), 100), (key(9), 103), (key(8), 106)], 3)   # |p - q| >= min_sep: kept
+    assert table(pts, 8, min_sep=1) == ([(key(10), 100), (key(9), 103), (key(8), 106)], 3)
+    assert table(pts, 8, min_sep=7) == ([(key(10), 100)], 3)
+    assert table(pts, 8, min_sep=N) == ([(key(10), 100)], 3)
+    # equal keys 6 apart with min_sep 7: the lower bin is taken and suppresses the other
+    assert table(row_of([(100, 4), (106, 4), (113, 4)]), 8, min_sep=7) == ([(key(4), 100), (key(4), 113)], 3)
+    # bins 0 and 16383 are N - 1 apart: one of them at min_sep N, both at N - 1
+    ends = row_of([(0, 3), (N - 1, 3)])
+    assert table(ends, 8, min_sep=N) == ([(key(3), 0)], 2)
+    assert table(ends, 8, min_sep=N - 1) == ([(key(3), 0), (key(3), N - 1)], 2)
+
+
+def test_nan_inf_finite_and_the_sign():
+    pts = row_of([(10, 3e38), (20, np.inf), (30, np.nan), (40, -np.inf), (50, -7.0)])
+    got, count = table(pts, 8)
+    assert count == 5
+    assert got == [(NAN_KEY, 30), (0x7F800000, 20), (0x7F800000, 40), (key(3e38), 10), (key(7.0), 50)]
+    # a negative NaN: the sign is cleared, the payload kept
+    pts = np.zeros((1, N), np.float32)
+    pts.view(np.uint32)[0, 77] = 0xFFC00123
+    assert table(pts, 2) == ([(0x7FC00123, 77)], 1)
+    # -0.0 counts as +0.0: never a peak, and as a neighbour it is zero
+    pts = row_of([(5, -0.0), (6, -0.0)])
+    assert bits(pts)[0, 5] == 0x80000000
+    assert table(pts, 2) == ([], 0)
+    # a denormal is a peak, ranked by its bits; 2^-149 (bits 1) is above zero
+    pts = row_of([(60, 2.0 ** -149), (70, 2.0 ** -140), (80, -(2.0 ** -130))])
+    assert bits(pts)[0, 60] == 1 and bits(pts)[0, 70] == 0x200
+    assert table(pts, 4) == ([(1 << 19, 80), (0x200, 70), (1, 60)], 3)
+    assert table(pts, 4, threshold=2.0 ** -140) == ([(1 << 19, 80), (0x200, 70)], 2)
+    # a negative input next to a smaller positive one: compared by magnitude
+    assert table(row_of([(90, -3.0), (91, 2.0)]), 4) == ([(key(3.0), 90)], 1)
+
+
+def test_all_zero_row():
+    from fpga_real_time_fft_analyzer_amd import frames
+    mag, bins, count = frames.peaks_of_rows(np.zeros((2, N), np.float32), 5)
+    assert count.tolist() == [0, 0] and (bins == -1).all() and not bits(mag).any()
+    assert mag.shape == (2, 5) and bins.shape == (2, 5)
+    mag, bins, count = frames.peaks_of_rows(np.zeros((0, N), np.float32), 5)
+    assert mag.shape == (0, 5) and bins.shape == (0, 5) and count.shape == (0,)
+
+
+def test_k1_full_range_is_the_argmax_of_the_keys():
+    from fpga_real_time_fft_analyzer_amd import frames
+    rng = np.random.default_rng(1701)
+    pts = np.exp(rng.uniform(-60.0, 60.0, size=(6, N))).astype(np.float32)
+    pts[1] = rng.integers(0, 16, N)                                # many ties at the maximum
+    pts[2] *= rng.choice([-1.0, 1.0], N).astype(np.float32)
+    pts[3, 5000:5003] = 3e38                                       # a plateau at the top
+    pts[4, 0] = pts[4, N - 1] = 3e38
+    pts[5, N - 1] = 3e38
+    mag, bins, count = frames.peaks_of_rows(pts, 1)
+    u = bits(pts) & 0x7FFFFFFF
+    assert bins[:, 0].tolist() == u.argmax(axis=1).tolist()        # numpy's argmax is the lowest index of the maximum
+    assert np.array_equal(bits(mag)[:, 0], u.max(axis=1))
+    assert bins[3, 0] == 5000 and bins[4, 0] == 0 and bins[5, 0] == N - 1
+
+
+def test_rows_are_independent_and_arguments_are_checked():
+    from fpga_real_time_fft_analyzer_amd import frames
+    rng = np.random.default_rng(1702)
+    pts = np.exp(rng.uniform(-60.0, 60.0, size=(3, N))).astype(np.float32)
+    whole = frames.peaks_of_rows(pts, 7, 1e-3, 100, 9000, 5)
+    for r in range(3):
+        one = frames.peaks_of_rows(pts[r:r + 1], 7, 1e-3, 100, 9000, 5)
+        for w, o in zip(whole, one):
+            assert np.array_equal(np.ascontiguousarray(w[r:r + 1]).view(np.uint32), o.view(np.uint32))
+    bad = [dict(k=0), dict(k=33), dict(k=True), dict(k=2.0), dict(threshold=-1.0), dict(threshold=-0.0),
+           dict(threshold=float("nan")), dict(lo=-1), dict(lo=5, hi=5), dict(hi=N + 1), dict(lo=1.0), dict(hi=True),
+           dict(min_sep=0), dict(min_sep=N + 1), dict(min_sep=2.0), dict(min_sep=False)]
+    for kw in bad:
+        with pytest.raises(ValueError):
+            frames.peaks_of_rows(pts, **kw)
+    for wrong in (pts.astype(np.float64), pts[:, :N // 2], pts[0]):
+        with pytest.raises(ValueError):
+            frames.peaks_of_rows(wrong)
+    assert frames.peaks_of_rows(pts, np.int64(3), np.float32(0.5), np.int32(0), np.int64(N), np.int16(2))[0].shape == (3, 3)
+
+
+# ------------------------------------------------------------------------------------------------------------ the surface
+def declared(path):
+    txt = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
+    return sorted(set(re.findall(r"\b(sa_[a-z0-9_]+)\s*\(", txt)))
+
+
+@pytest.fixture(scope="module")
+def peaks_lib():
+    """libspecan_peaks.so, built on demand by the package's one build step (hipcc cross-compiles without a GPU)."""
+    from fpga_real_time_fft_analyzer_amd import abi
+    if not os.path.exists(abi.PEAKS_LIB_PATH):
+        abi.build()
+    return abi.peaks_lib()
+
+
+@pytest.fixture(scope="module")
+def check(peaks_lib):
+    def call(field=0, a_in=BASE, a_out=FAR, a_count=FAR2, rows=3, k=8, thr=0, lo=0, hi=N, min_sep=1):
+        return peaks_lib.sa_peaks_check(field, a_in, a_out, a_count, rows, k, thr, lo, hi, min_sep)
+    return call
+
+
+def test_header_library_and_binding_table(peaks_lib):
+    """Name for name: declared in specan_peaks.h = exported by libspecan_peaks.so = bound in abi.PEAKS_SIGNATURES; nothing is
+    in the other tables or headers, which are what they were."""
+    from fpga_real_time_fft_analyzer_amd import abi
+    assert declared(HEADER) == NAMES
+    nm = shutil.which("nm") or "/opt/rocm/llvm/bin/llvm-nm"
+    r = subprocess.run([nm, "-D", "--defined-only", abi.PEAKS_LIB_PATH], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr
+    exported = sorted(ln.split()[-1] for ln in r.stdout.splitlines() if " T " in ln and "sa_" in ln.split()[-1])
+    assert exported == NAMES, exported
+    assert sorted(abi.PEAKS_SIGNATURES) == NAMES
+    assert not set(NAMES) & (set(abi.SIGNATURES) | set(abi.EXT_SIGNATURES) | set(abi.FOLD_SIGNATURES))
+    for other in ("specan.h", "specan_ext.h", "specan_fold.h"):
+        assert not set(NAMES) & set(declared(os.path.join(INCLUDE, other))), other
+    for name in NAMES:
+        fn, (restype, argtypes) = getattr(peaks_lib, name), abi.PEAKS_SIGNATURES[name]
+        assert fn.argtypes is not None and list(fn.argtypes) == list(argtypes), name
+        assert fn.restype is restype is (ctypes.c_char_p if name == "sa_peaks_last_error" else ctypes.c_int), name
+    assert peaks_lib.sa_peaks_version() == abi.SA_PEAKS_VERSION == 1 and abi.SA_PEAKS_K_MAX == 32
+    text = open(HEADER).read()
+    assert "#define SA_PEAKS_VERSION 1" in text and "#define SA_PEAKS_K_MAX 32" in text
+    assert peaks_lib.sa_peaks_last_error() == b""
+    assert len(abi.SIGNATURES) == 45 and len(abi.EXT_SIGNATURES) == 5 and len(abi.FOLD_SIGNATURES) == 4
+    assert os.path.basename(abi.PEAKS_LIB_PATH) == "libspecan_peaks.so"
+    assert os.path.dirname(abi.PEAKS_LIB_PATH) == os.path.dirname(abi.LIB_PATH)
+
+
+def test_header_compiles_as_c99_pedantic(tmp_path):
+    src = tmp_path / "use_peaks.c"
+    src.write_text('#include "specan_peaks.h"\n'
+                   "int use(const void *p, sa_peak *o, int32_t *c) { return sa_peaks_f32(p, SA_PEAKS_IN_POINT_POWER, o, c, 8, 8, 0.5f,"
+                   " 0, SA_N, 1, 0) + sa_peaks_check(SA_PEAKS_IN_MAG, 16, 32, 64, 0, 1, 0u, 0, 1, 1) + sa_peaks_version()"
+                   " - SA_PEAKS_VERSION + (int)sizeof(sa_peak) - 8 + (sa_peaks_last_error()[0] != 0) + SA_PEAKS_K_MAX - 32"
+                   " + SA_PEAKS_IN_POINT_PEAK - 1 + (o->bin < 0) + (o->mag > 0.0f); }\n")
+    gcc = shutil.which("gcc") or shutil.which("cc")
+    r = subprocess.run([gcc, "-std=c99", "-Wall", "-Werror", "-pedantic", "-fsyntax-only", "-I", INCLUDE, str(src)],
+                       capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr
+
+
+def test_library_links_hip_alone_and_reads_no_environment(peaks_lib):
+    from fpga_real_time_fft_analyzer_amd import abi
+    r = subprocess.run(["ldd", abi.PEAKS_LIB_PATH], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr
+    for other in ("torch", "oracle", "specan_hip", "specan_fold"):
+        assert other not in r.stdout, r.stdout
+    assert "amdhip64" in r.stdout
+    nm = shutil.which("nm") or "/opt/rocm/llvm/bin/llvm-nm"
+    undefined = subprocess.run([nm, "-D", "--undefined-only", abi.PEAKS_LIB_PATH], capture_output=True, text=True, timeout=120).stdout
+    assert "getenv" not in undefined
+    text = unit_text("peaks_f32.hip") + unit_text("sa_peaks_check.cpp")
+    assert "sa_peaks_f32" in text and "sa_peaks_check_call" in text
+    assert "getenv" not in text and "environ" not in text.replace("environment", "")
+    kernel = open(os.path.join(CSRC, "peaks_f32.hip")).read()
+    assert "atomic" not in kernel.replace("No atomics", "") and "s_setreg" not in kernel and "denorm" not in kernel
+    # the units include nothing of the chains or of the fold
+    assert not re.search(r'#\s*include\s+"(?!sa_peaks\.hpp|\.\./\.\./include/specan_peaks\.h|specan\.h)', text), text[:200]
+
+
+def test_kernel_inventories(peaks_lib):
+    """libspecan_peaks.so holds the three instantiations, one per input layout, and nothing else; the other two libraries hold
+    what they held."""
+    from fpga_real_time_fft_analyzer_amd import abi
+    assert inventory(abi.PEAKS_LIB_PATH) == {f"peaks_f32_kernel<{f}>" for f in range(3)}
+    for path in (abi.LIB_PATH, abi.FOLD_LIB_PATH):
+        if not os.path.exists(path):
+            abi.build()
+    assert inventory(abi.LIB_PATH) == set(TABLE)
+    assert inventory(abi.FOLD_LIB_PATH) == {f"fold_mag_f32_kernel<{k}>" for k in range(7)}
+
+
+def test_resource_remarks_show_no_scratch_and_no_spill():
+    """The compiler's figures for the three kernels, as `make resource-peaks-f32` prints them: no scratch, no SGPR or VGPR
+    spill, the 80 bytes of LDS of the four wave slots (two buffers) and the four counts, static -- no dynamic LDS."""
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    r = subprocess.run([hipcc, *HIPCC_FLAGS, "peaks_f32.hip", "-o", os.devnull, "-Rpass-analysis=kernel-resource-usage"], cwd=CSRC,
+                       capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    err = r.stderr
+    assert len(re.findall(r"Function Name: \S*peaks_f32_kernel", err)) == 3
+    for what, want in (("ScratchSize \\[bytes/lane\\]", 0), ("SGPRs Spill", 0), ("VGPRs Spill", 0), ("LDS Size \\[bytes/block\\]", 80)):
+        got = [int(v) for v in re.findall(what + r": (\d+)", err)]
+        assert got == [want] * 3, (what, got)
+    print("FIGURE VGPRs", re.findall(r" VGPRs: (\d+)", err), "occupancy", re.findall(r"Occupancy \[waves/SIMD\]: (\d+)", err))
+    assert "extern __shared__" not in unit_text("peaks_f32.hip")
+    make = open(os.path.join(CSRC, "Makefile")).read()
+    assert "resource-peaks-f32:" in make and re.search(r"^all:.*\$\(PEAKS_OUT\)", make, re.M)
+
+
+# -------------------------------------------------------------------------------------------------------------- the check
+def in_bytes(field, rows):
+    return rows * 65536 * (2 if field else 1)
+
+
+def test_known_answers_of_the_header(check):
+    for field, rows, k, n_in, n_out, n_count in ((1, 8, 8, 1048576, 512, 32), (0, 3, 32, 196608, 768, 12), (2, 1, 1, 131072, 8, 4)):
+        tag = (field, rows, k)
+        assert (in_bytes(field, rows), rows * k * 8, rows * 4) == (n_in, n_out, n_count), tag
+        # in | out | count packed back to back: every pair merely touches
+        assert check(field, BASE, BASE + n_in, BASE + n_in + n_out, rows, k) == SA_OK, tag
+        assert check(field, BASE, BASE + n_in - 8, FAR2, rows, k) == SA_EINVAL, tag                   # out reaches into in
+        assert check(field, BASE, BASE + n_in, BASE + n_in + n_out - 4, rows, k) == SA_EINVAL, tag    # count reaches into out
+        assert check(field, BASE, FAR, BASE + n_in - 4, rows, k) == SA_EINVAL, tag                    # count reaches into in
+        # count | out | in
+        assert check(field, BASE, BASE - n_out, BASE - n_out - n_count, rows, k) == SA_OK, tag
+
+
+def test_every_pair_of_ranges_touching_and_overlapping(check):
+    """Every ordered pair (a, b) of the three ranges, b right behind a and b right in front of a, the third far away: touching
+    is fine; moved into a by 1 byte (which also breaks b's alignment), by b's own alignment (the smallest overlap an aligned b
+    can have) and by 16 bytes it is refused.  X is 16-byte aligned and every size is a multiple of its range's alignment, so
+    a = [X - size, X) and b = [X - size, X) are aligned."""
+    X = BASE + (1 << 30)
+    for field, rows, k in itertools.product((0, 1, 2), (1, 4, 5), (1, 7, 32)):
+        size = {"in": in_bytes(field, rows), "out": rows * k * 8, "count": rows * 4}
+        align = {"in": 16, "out": 8, "count": 4}
+        far = {"in": BASE, "out": FAR, "count": FAR2}
+        args = dict(field=field, rows=rows, k=k)
+
+        def at(**where):
+            put = dict(far, **where)
+            return check(a_in=put["in"], a_out=put["out"], a_count=put["count"], **args)
+
+        for a, b in itertools.permutations(("in", "out", "count"), 2):
+            tag = (field, rows, k, a, b)
+            assert size[a] % align[a] == 0 and size[b] % align[b] == 0
+            assert at(**{a: X - size[a], b: X}) == SA_OK, tag                      # b right behind a
+            assert at(**{a: X, b: X - size[b]}) == SA_OK, tag                      # b right in front of a
+            for by in (1, align[b], 16):
+                # moved by `by`, b still meets a unless it has passed it altogether (the 4 + 8 bytes of one row at k = 1)
+                want = SA_EINVAL if by % align[b] or by < size[a] + size[b] else SA_OK
+                assert want == SA_EINVAL or (rows, k, by) == (1, 1, 16), tag
+                assert at(**{a: X - size[a], b: X - by}) == want, tag + (by,)
+                assert at(**{a: X, b: X - size[b] + by}) == want, tag + (by,)
+        # alignment alone
+        for off in (1, 2, 4, 8, 12, 16, 32):
+            assert check(field, BASE + off, FAR, FAR2, rows, k) == (SA_OK if off % 16 == 0 else SA_EINVAL), off
+            assert check(field, BASE, FAR + off, FAR2, rows, k) == (SA_OK if off % 8 == 0 else SA_EINVAL), off
+            assert check(field, BASE, FAR, FAR2 + off, rows, k) == (SA_OK if off % 4 == 0 else SA_EINVAL), off
+        for null in ("a_in", "a_out", "a_count"):
+            assert check(field=field, rows=rows, k=k, **{null: 0}) == SA_EINVAL, null
+        assert check(field, BASE, BASE, FAR2, rows, k) == SA_EINVAL and check(field, BASE, FAR, FAR, rows, k) == SA_EINVAL
+
+
+def test_refusals_in_their_order(check, peaks_lib):
+    """1 negative rows, 2 the scalar arguments (also at rows 0), 3 the empty call, 4 the pointers: each refusal is shown to win
+    over every later one by making the later ones wrong too."""
+    inf, nan = 0x7F800000, 0x7FC00000
+    bad = [dict(field=-1), dict(field=3), dict(k=0), dict(k=33), dict(k=-1), dict(thr=nan), dict(thr=inf + 1), dict(thr=0x80000000),
+           dict(thr=0xBF800000), dict(thr=0xFFFFFFFF), dict(lo=-1), dict(lo=5, hi=5), dict(lo=6, hi=5), dict(hi=N + 1),
+           dict(lo=N, hi=N + 1), dict(min_sep=0), dict(min_sep=-3), dict(min_sep=N + 1)]
+    wrong_ptrs = [dict(), dict(a_in=0, a_out=0, a_count=0), dict(a_in=BASE + 1, a_out=BASE + 3, a_count=BASE + 2),
+                  dict(a_in=BASE, a_out=BASE, a_count=BASE)]
+    # 1: before bad arguments and bad pointers
+    for kw in [dict()] + bad:
+        for p in wrong_ptrs:
+            assert check(rows=-1, **kw, **p) == SA_ESHAPE, (kw, p)
+            assert check(rows=-(1 << 31), **kw, **p) == SA_ESHAPE, (kw, p)
+    # 2: before the empty call and the pointers
+    for rows in (0, 1, 5, (1 << 31) - 1):
+        for kw in bad:
+            for p in wrong_ptrs:
+                assert check(rows=rows, **kw, **p) == SA_EINVAL, (rows, kw, p)
+    # 3: the empty call is SA_OK whatever the pointers are
+    for p in wrong_ptrs:
+        for field in (0, 1, 2):
+            assert check(field=field, rows=0, **p) == SA_OK, p
+    # 4: the pointers, last
+    for p in wrong_ptrs[1:]:
+        assert check(rows=1, **p) == SA_EINVAL, p
+    assert check(rows=1) == SA_OK
+    # the edges of every scalar that are good
+    for kw in (dict(k=1), dict(k=32), dict(thr=inf), dict(thr=1), dict(lo=0, hi=1), dict(lo=N - 1, hi=N), dict(min_sep=N),
+               dict(field=2), dict(rows=(1 << 31) - 1, a_in=1 << 20, a_out=1 << 62, a_count=1 << 61)):
+        assert check(**kw) == SA_OK, kw
+    assert peaks_lib.sa_peaks_last_error() == b""                  # the check alone leaves the thread's text alone
+
+
+def test_standalone_program_under_host_sanitizers(tmp_path):
+    """tests/cpp/test_sa_peaks_check.cpp + csrc/sa_peaks_check.cpp, host only, with -fsanitize=address,undefined when that
+    links here (a plain build otherwise: the program's own checks still run): the same arithmetic at rows up to 2^31 - 1 and
+    addresses near 2^47 and 2^64.  Nothing is loaded into this process."""
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    exe = str(tmp_path / "test_sa_peaks_check")
+    srcs = [os.path.join(ROOT, "tests", "cpp", "test_sa_peaks_check.cpp"), os.path.join(CSRC, "sa_peaks_check.cpp")]
+    base = [hipcc, "-O1", "-g", "-std=c++17", "--offload-host-only", "-x", "hip", *srcs, "-o", exe]
+    r = subprocess.run(base + ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"],
+                       capture_output=True, text=True, timeout=300)
+    sanitized = r.returncode == 0
+    if not sanitized:
+        r = subprocess.run(base, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr
+    print("sanitizers:", "address,undefined" if sanitized else "did not link here: plain build")
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and r.stdout.startswith("ok "), r.stdout + r.stderr
+    assert int(r.stdout.split()[1]) > 100000
+
+
+# ----------------------------------------------------------------------------------------------------------- the wrappers
+def test_the_wrappers_surface():
+    """The Python entry points exist; a bad k, threshold, range, min_sep or field is SA_EINVAL before anything of the object
+    or of a library is touched (the object here has neither)."""
+    from fpga_real_time_fft_analyzer_amd import chain
+    cls = chain.SpectrumChain
+    assert callable(cls.find_peaks) and callable(cls.peak_table_f32)
+    bare = object.__new__(cls)
+    bad = [dict(k=0), dict(k=33), dict(k=True), dict(k=8.0), dict(k=None), dict(threshold=-1.0), dict(threshold=-0.0),
+           dict(threshold=float("nan")), dict(threshold="1"), dict(threshold=None), dict(lo=-1), dict(lo=7, hi=7), dict(hi=N + 1),
+           dict(lo=0.0), dict(hi=True), dict(min_sep=0), dict(min_sep=N + 1), dict(min_sep=1.0), dict(min_sep=False)]
+    for kw in bad:
+        for call in (lambda: bare.find_peaks(None, **kw), lambda: bare.peak_table_f32(None, **kw)):
+            with pytest.raises(chain.SpecanError) as e:
+                call()
+            assert e.value.code == SA_EINVAL, kw
+    for field in ("mag", 0, 1, ["peak"]):
+        with pytest.raises(chain.SpecanError) as e:
+            bare.find_peaks(None, field=field)
+        assert e.value.code == SA_EINVAL, field
+    for group in (0, 1, 3, 256, 2.0, True, "4"):                  # the input is no tensor either, the same code: the words say
+        with pytest.raises(chain.SpecanError) as e:               # which of the two checks spoke
+            bare.peak_table_f32(None, group=group)
+        assert e.value.code == SA_EINVAL, group
+        assert ("group" in str(e.value) or "folds nothing" in str(e.value)) and "tensor" not in str(e.value), (group, str(e.value))
+    with pytest.raises(chain.SpecanError) as e:                   # and with a good group the input's check does speak
+        bare.peak_table_f32(None, group=4)
+    assert e.value.code == SA_EINVAL and "tensor" in str(e.value)
+    assert cls._peaks_args(np.int64(1), np.float32(0.0), np.int32(0), N, np.int16(1), None) == 0
+    assert cls._peaks_args(32, float("inf"), N - 1, N, N, "peak") == 1 and cls._peaks_args(8, 1, 0, 1, 1, "power") == 2
