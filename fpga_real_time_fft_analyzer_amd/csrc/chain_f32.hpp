@@ -105,89 +105,36 @@ __device__ __forceinline__ float mul_to(float a, float b)
 // by the window, which the host stored transposed (wint[g][t] = window[64t + 4g .. +3]) so that its loads are coalesced
 // in this layout.  Thread t ends with d[j] = (x[64t + j], x[64t + 32 + j]) * window.
 //
-// int16 samples in: a thread's 64 samples are 128 bytes, so ONE round of the LDS-DMA brings the whole frame (32 KiB).
-// Column g of a row holds samples 8g .. 8g+7: g < 4 is chunk A, g >= 4 chunk B.  x = float(sample) * scale is rounded once
-// and then takes the window exactly as a float32 input sample does, so the results are those of sa_process_f32 on the
-// converted frame, bit for bit.
-template <bool WINGEN>
-__device__ __forceinline__ void stage_in_chunks(const int16_t *__restrict__ xin, const float in_scale,
+// Integer samples in (InT = int16_t or SaP12): ONE round of the LDS-DMA brings the whole frame (int16: 128 bytes per thread,
+// 32 KiB; packed 12-bit: 96 bytes per thread, 24 KiB), and the forms differ only in the reader that gets samples 8g .. 8g+7
+// of chunk A and of chunk B out of the row (chain_f32_dev.hpp: row_open, row_step).  x = float(sample) * scale is rounded
+// once and then takes the window exactly as a float32 input sample does, so the results are those of sa_process_f32 on the
+// converted frame, bit for bit, and the packed form's are those of the int16 form on the sign-extended samples.
+template <bool WINGEN, typename InT>
+__device__ __forceinline__ void stage_in_chunks(const InT *__restrict__ xin, const float in_scale,
                                                 const float4 *__restrict__ wint, const SaIirLaneTab *__restrict__ lt,
                                                 unsigned char *smem, int t, v2f (&d)[32])
 {
-    const uint4 *lds4 = reinterpret_cast<const uint4 *>(smem);
     const int lane = t & 63, wave = t >> 6;
-    float4 pq = make_float4(0.f, 0.f, 0.f, 0.f);
+    float4 pq = make_float4(0.f, 0.f, 0.f, 0.f);               // the window generator: see the float32 form below
     float g0 = 0.f;
     if constexpr (WINGEN) {
         pq = *reinterpret_cast<const float4 *>(&lt->wgen[t][0]);
         g0 = lt->wg0;
     }
-    dma_rows(xin, smem, lane, wave);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-    const int sw = row_swizzle(t);
-    const v2f Pw = {pq.x, pq.z}, Qw = {pq.y, pq.w}, G0 = {g0, g0}, sc = {in_scale, in_scale};
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {                              // samples 8g .. 8g+7 of chunk A and of chunk B
-        const uint4 qa = lds4[t * 8 + (g ^ sw)], qb = lds4[t * 8 + ((g + 4) ^ sw)];
-        const unsigned ua[4] = {qa.x, qa.y, qa.z, qa.w}, ub[4] = {qb.x, qb.y, qb.z, qb.w};
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {                          // four samples of either chunk at a time
-            float4 wa = make_float4(0.f, 0.f, 0.f, 0.f), wb = wa;
-            if constexpr (!WINGEN) {                           // table window: win_t[g'][t] = window at 64 t + 4 g' .. + 3
-                wa = wint[(2 * g + u) * 256 + t];
-                wb = wint[(8 + 2 * g + u) * 256 + t];
-            }
-            const float fa[4] = {wa.x, wa.y, wa.z, wa.w}, fb[4] = {wb.x, wb.y, wb.z, wb.w};
-#pragma unroll
-            for (int e4 = 0; e4 < 4; ++e4) {
-                const int e = 4 * u + e4, j = 8 * g + e;
-                const int ia = (e & 1) ? (int)ua[e >> 1] >> 16 : (int)(short)(ua[e >> 1] & 0xFFFFu);
-                const int ib = (e & 1) ? (int)ub[e >> 1] >> 16 : (int)(short)(ub[e >> 1] & 0xFFFFu);
-                const v2f x = v2f{(float)ia, (float)ib} * sc;   // rounded once: the float32 sample
-                v2f w;
-                if constexpr (WINGEN) {
-                    const v2f cs = {lt->wcs[j][0], lt->wcs[j][1]};
-                    asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[0,0,0] op_sel_hi:[1,0,1]\n\t"
-                        "v_pk_fma_f32 %0, %4, %2, %0 op_sel:[0,1,0] op_sel_hi:[1,1,1]"
-                        : "=&v"(w) : "v"(Pw), "s"(cs), "v"(G0), "v"(Qw));
-                } else {
-                    w = v2f{fa[e4], fb[e4]};
-                }
-                d[j] = x * w;
-            }
-        }
-    }
-}
-
-// Packed 12-bit samples in (SaP12, chain_f32_dev.hpp): a thread's 64 samples are 96 bytes = six 16-byte units, one round
-// of the LDS-DMA brings the whole frame (24 KiB) and the thread reads its units with conflict-free ds_read_b128
-// (p12_row_swizzle).  Units 0..2 are chunk A, 3..5 chunk B; three dwords hold eight samples (p12_unpack8), so step g
-// takes dwords 3g .. 3g+2 of either chunk: samples 8g .. 8g+7, as the int16 form does.  x = float(sample) * scale is
-// rounded once: the results are those of the int16 form on the sign-extended samples, bit for bit.
-template <bool WINGEN>
-__device__ __forceinline__ void stage_in_chunks(const SaP12 *__restrict__ xin, const float in_scale,
-                                                const float4 *__restrict__ wint, const SaIirLaneTab *__restrict__ lt,
-                                                unsigned char *smem, int t, v2f (&d)[32])
-{
-    const int lane = t & 63, wave = t >> 6;
-    float4 pq = make_float4(0.f, 0.f, 0.f, 0.f);
-    float g0 = 0.f;
-    if constexpr (WINGEN) {
-        pq = *reinterpret_cast<const float4 *>(&lt->wgen[t][0]);
-        g0 = lt->wg0;
-    }
+    // the rows are wave-private: the wave waits for its own DMA, and nothing of the window arithmetic is scheduled
+    // above the wait (float32 form below)
     dma_rows(xin, smem, lane, wave);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_sched_barrier(0);
     const v2f Pw = {pq.x, pq.z}, Qw = {pq.y, pq.w}, G0 = {g0, g0}, sc = {in_scale, in_scale};
-    unsigned ua[12], ub[12];                                   // the 12 dwords of chunk A and of chunk B
-    p12_read_row(smem, t, ua, ub);
+    unsigned row[2][12];                                       // packed form: the 12 dwords of chunk A and of chunk B
+    row_open(xin, smem, t, row);
 #pragma unroll
     for (int g = 0; g < 4; ++g) {                              // samples 8g .. 8g+7 of chunk A and of chunk B
         int sa[8], sb[8];
-        p12_unpack8(ua[3 * g], ua[3 * g + 1], ua[3 * g + 2], sa);
-        p12_unpack8(ub[3 * g], ub[3 * g + 1], ub[3 * g + 2], sb);
+        row_step(xin, smem, t, row, 0, g, sa);
+        row_step(xin, smem, t, row, 1, g, sb);
 #pragma unroll
         for (int u = 0; u < 2; ++u) {                          // four samples of either chunk at a time
             float4 wa = make_float4(0.f, 0.f, 0.f, 0.f), wb = wa;
@@ -612,56 +559,29 @@ __device__ __forceinline__ void chain_frame(const InT *__restrict__ in, const fl
 #pragma unroll
             for (int m = 0; m < 16; ++m) a[safft::brev(16 * h + m, 5)] = ldc[264 * m + 33 * (t >> 5) + (t & 31)];
         }
-    } else if constexpr (std::is_same_v<InT, int16_t>) {
-        // No IIR, int16 samples: as float32 frames do (below), but the whole frame (32 KiB) comes in one round;
-        // z[256 m1 + t] = (x[2 i], x[2 i + 1]) is one dword
+    } else if constexpr (!std::is_same_v<InT, float>) {
+        // No IIR, integer samples (int16 or packed 12-bit): as float32 frames do (below), but the whole frame (32 KiB or
+        // 24 KiB) comes in one round of 1 KiB requests, natural order, and the form's reader (chain_f32_dev.hpp:
+        // image_dword, point_of) gives z[256 m1 + t] = (x[2 i], x[2 i + 1])
         static_assert(!ONE_ROUND, "the one-round form is float32 only");
+        constexpr int kUnit = 16 / (int)sizeof(InT);                            // elements of InT per 16-byte lane request
+        constexpr int kSlabs = kFrameElems<InT> / (64 * kUnit) / (kThreads / 64);   // per wave: 8 (int16) or 6 (packed)
+        static_assert(kSlabs * (kThreads / 64) * 1024 == kFrameElems<InT> * (int)sizeof(InT), "the requests cover the frame exactly");
         __builtin_amdgcn_s_setprio(3);
 #pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const int n = wave * 8 + i;
-            const int16_t *src = xin + n * 512 + lane * 8;
+        for (int i = 0; i < kSlabs; ++i) {
+            const int n = wave * kSlabs + i;
+            const InT *src = xin + n * (64 * kUnit) + lane * kUnit;
             __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)src,
                                              (__attribute__((address_space(3))) void *)(smem + n * 1024), 16, 0, SA_DMA_AUX);
         }
         __builtin_amdgcn_s_setprio(0);
         __syncthreads();
-        const unsigned *ldu = reinterpret_cast<const unsigned *>(smem);
 #pragma unroll
         for (int pp = 0; pp < 16; ++pp) {
             const float4 w = winb[pp * 256 + t];
-            const unsigned u0 = ldu[256 * (2 * pp) + t], u1 = ldu[256 * (2 * pp + 1) + t];
-            const cf z0 = cf{(float)(int)(short)(u0 & 0xFFFFu), (float)((int)u0 >> 16)} * cf{in_scale, in_scale};
-            const cf z1 = cf{(float)(int)(short)(u1 & 0xFFFFu), (float)((int)u1 >> 16)} * cf{in_scale, in_scale};
-            a[safft::brev(2 * pp, 5)] = {z0.x * w.x, z0.y * w.y};
-            a[safft::brev(2 * pp + 1, 5)] = {z1.x * w.z, z1.y * w.w};
-        }
-    } else if constexpr (std::is_same_v<InT, SaP12>) {
-        // No IIR, packed 12-bit samples: the whole frame (24 KiB) in one round of six requests per wave, natural order;
-        // z[m] = (x[2 m], x[2 m + 1]), m = 256 m1 + t, is the three bytes at byte 3 m = 768 m1 + 3 t: the two aligned
-        // dwords around them and a funnel shift by 8 * (3 t mod 4) bits (the same for every m1), then two sign-extending
-        // extracts.  The second dword of the frame's last point lies one dword behind the frame (inside the image's
-        // allocation); at that point's shift of 8 none of its bits reaches the 24 that are used.
-        static_assert(!ONE_ROUND, "the one-round form is float32 only");
-        __builtin_amdgcn_s_setprio(3);
-#pragma unroll
-        for (int i = 0; i < 6; ++i) {
-            const int n = wave * 6 + i;
-            const SaP12 *src = xin + n * 1024 + lane * 16;
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)src,
-                                             (__attribute__((address_space(3))) void *)(smem + n * 1024), 16, 0, SA_DMA_AUX);
-        }
-        __builtin_amdgcn_s_setprio(0);
-        __syncthreads();
-        const unsigned *ldu = reinterpret_cast<const unsigned *>(smem) + ((3 * t) >> 2);
-        const unsigned sh = 8u * ((3u * (unsigned)t) & 3u);
-#pragma unroll
-        for (int pp = 0; pp < 16; ++pp) {
-            const float4 w = winb[pp * 256 + t];
-            const unsigned u0 = __builtin_amdgcn_alignbit(ldu[192 * (2 * pp) + 1], ldu[192 * (2 * pp)], sh);
-            const unsigned u1 = __builtin_amdgcn_alignbit(ldu[192 * (2 * pp + 1) + 1], ldu[192 * (2 * pp + 1)], sh);
-            const cf z0 = cf{(float)p12_bfe(u0, 0), (float)p12_bfe(u0, 12)} * cf{in_scale, in_scale};
-            const cf z1 = cf{(float)p12_bfe(u1, 0), (float)p12_bfe(u1, 12)} * cf{in_scale, in_scale};
+            const unsigned u0 = image_dword(xin, smem, t, 2 * pp), u1 = image_dword(xin, smem, t, 2 * pp + 1);
+            const cf z0 = point_of(xin, u0) * cf{in_scale, in_scale}, z1 = point_of(xin, u1) * cf{in_scale, in_scale};
             a[safft::brev(2 * pp, 5)] = {z0.x * w.x, z0.y * w.y};
             a[safft::brev(2 * pp + 1, 5)] = {z1.x * w.z, z1.y * w.w};
         }

@@ -173,6 +173,61 @@ __device__ __forceinline__ void p12_read_row(const unsigned char *smem, int t, u
     }
 }
 
+// The readers of the integer sample forms.  Behind dma_rows the two forms differ only in how a thread gets samples out of
+// its row, so the stage-ins (chain_f32.hpp: stage_in_chunks, iir_f64.hip: stage_in) are written once on two overloads
+// that the pointer type selects:
+//   row_open: what is read once per row, in front of the steps
+//   row_step: samples 8g .. 8g+7 of chunk h (0: chunk A, 1: chunk B) as ints, g = 0 .. 3
+// Free functions of (smem, t) on purpose: with t and the swizzle held in a reader object the address arithmetic of the
+// int16 kernels comes out differently.
+//
+// int16: nothing to open; column c of a row holds samples 8c .. 8c+7, c < 4 is chunk A and c >= 4 chunk B, so a step is the
+// ds_read_b128 of column g + 4h and the half-word extracts.
+__device__ __forceinline__ void row_open(const int16_t *, const unsigned char *, int, unsigned (&)[2][12]) {}
+__device__ __forceinline__ void row_step(const int16_t *, const unsigned char *smem, int t, unsigned (&)[2][12], int h, int g,
+                                         int (&s)[8])
+{
+    const uint4 q = reinterpret_cast<const uint4 *>(smem)[t * 8 + ((g + 4 * h) ^ row_swizzle(t))];
+    const unsigned u[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+    for (int e = 0; e < 8; ++e) s[e] = (e & 1) ? (int)u[e >> 1] >> 16 : (int)(short)(u[e >> 1] & 0xFFFFu);
+}
+// packed 12-bit: the whole row is read at the start (p12_read_row: units 0..2 are chunk A, 3..5 chunk B); three dwords
+// hold eight samples, so step g unpacks dwords 3g .. 3g+2 of the chunk.
+__device__ __forceinline__ void row_open(const SaP12 *, const unsigned char *smem, int t, unsigned (&u)[2][12])
+{
+    p12_read_row(smem, t, u[0], u[1]);
+}
+__device__ __forceinline__ void row_step(const SaP12 *, const unsigned char *, int, unsigned (&u)[2][12], int h, int g,
+                                         int (&s)[8])
+{
+    p12_unpack8(u[h][3 * g], u[h][3 * g + 1], u[h][3 * g + 2], s);
+}
+
+// The readers of the bypassed chain's natural-order image of integer samples (chain_f32.hpp, chain_frame with NSEC = 0):
+//   image_dword: the complex point z[m] = (x[2 m], x[2 m + 1]), m = 256 m1 + t, as the form packs it into a dword
+//   point_of   : that dword as a pair of floats
+// int16: the point is one dword of the image, two half-words
+__device__ __forceinline__ unsigned image_dword(const int16_t *, const unsigned char *smem, int t, int m1)
+{
+    return reinterpret_cast<const unsigned *>(smem)[256 * m1 + t];
+}
+__device__ __forceinline__ cf point_of(const int16_t *, unsigned u)
+{
+    return cf{(float)(int)(short)(u & 0xFFFFu), (float)((int)u >> 16)};
+}
+// packed 12-bit: the point is the three bytes at byte 3 m = 768 m1 + 3 t: the two aligned dwords around them and a funnel
+// shift by 8 * (3 t mod 4) bits (the same for every m1), then two sign-extending extracts.  The second dword of the
+// frame's last point lies one dword behind the frame (inside the image's allocation); at that point's shift of 8 none of
+// its bits reaches the 24 that are used.
+__device__ __forceinline__ unsigned image_dword(const SaP12 *, const unsigned char *smem, int t, int m1)
+{
+    const unsigned *ldu = reinterpret_cast<const unsigned *>(smem) + ((3 * t) >> 2);
+    const unsigned sh = 8u * ((3u * (unsigned)t) & 3u);
+    return __builtin_amdgcn_alignbit(ldu[192 * m1 + 1], ldu[192 * m1], sh);
+}
+__device__ __forceinline__ cf point_of(const SaP12 *, unsigned u) { return cf{(float)p12_bfe(u, 0), (float)p12_bfe(u, 12)}; }
+
 // Stage-out, round h, the stage-in run backwards: row r (32 float32 samples) -> o[64r + 32h ..].
 // Every wave instruction picks up 1 KiB of LDS in linear order and stores it with 16 bytes per lane: stored straight
 // from the registers, every lane of a store instruction would land in another 256-byte block.

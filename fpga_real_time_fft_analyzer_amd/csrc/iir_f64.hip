@@ -84,56 +84,31 @@ __device__ __forceinline__ void stage_in(const float *__restrict__ xin, float, c
     }
 }
 
-// int16 samples: a thread's 64 samples are 128 bytes, so one round brings the whole frame; column g of a row holds
-// samples 8g .. 8g+7 (g < 4: chunk A).  x = float(sample) * scale is rounded to float32 exactly as on the float32 path,
-// so this entry point and the float32 one on the converted frames agree bit for bit.
-__device__ __forceinline__ void stage_in(const int16_t *__restrict__ xin, const float in_scale, const double2 *__restrict__ wt,
-                                         unsigned char *smem, int t, double (&d)[2][32])
-{
-    const uint4 *lds4 = reinterpret_cast<const uint4 *>(smem);
-    const int lane = t & 63, wave = t >> 6, sw = row_swizzle(t);
-    dma_rows(xin, smem, lane, wave);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int g = 0; g < 8; ++g) {                              // samples 8g .. 8g+7 of the thread (chunk g >> 2)
-        const uint4 q = lds4[t * 8 + (g ^ sw)];
-        const unsigned u[4] = {q.x, q.y, q.z, q.w};
-        const int h = g >> 2;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const int j = 8 * (g & 3) + e;                     // index inside the chunk
-            const int s = (e & 1) ? (int)u[e >> 1] >> 16 : (int)(short)(u[e >> 1] & 0xFFFFu);
-            float x;
-            asm("v_mul_f32 %0, %1, %2" : "=v"(x) : "v"((float)s), "v"(in_scale));     // one float32 rounding, never fused
-            const double2 w = wt[(16 * h + (j >> 1)) * 256 + t];
-            d[h][j] = (double)x * ((j & 1) ? w.y : w.x);
-        }
-    }
-}
-
-// packed 12-bit samples (SaP12, chain_f32_dev.hpp): a thread's 64 samples are six 16-byte units of its 96-byte row, brought
-// in one round; three dwords hold eight samples (p12_unpack8).  The same single float32 rounding of x as the int16 form, so
-// this entry point and the int16 one on the sign-extended samples agree bit for bit.
-__device__ __forceinline__ void stage_in(const SaP12 *__restrict__ xin, const float in_scale, const double2 *__restrict__ wt,
+// Integer samples (InT = int16_t or SaP12): one round brings the whole frame, and the reader of the form (chain_f32_dev.hpp:
+// row_open, row_step) gives samples 8g .. 8g+7 of either chunk.  x = float(sample) * scale is rounded to float32 exactly as
+// on the float32 path -- one v_mul_f32, written out so that it is never fused into the double multiply behind it -- so the
+// int16 entry point and the float32 one on the converted frames agree bit for bit, and the packed one with the int16 one
+// on the sign-extended samples.
+template <typename InT>
+__device__ __forceinline__ void stage_in(const InT *__restrict__ xin, const float in_scale, const double2 *__restrict__ wt,
                                          unsigned char *smem, int t, double (&d)[2][32])
 {
     const int lane = t & 63, wave = t >> 6;
     dma_rows(xin, smem, lane, wave);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_sched_barrier(0);
-    unsigned uab[2][12];                                       // units 3h .. 3h+2 of the row: chunk h
-    p12_read_row(smem, t, uab[0], uab[1]);
+    unsigned row[2][12];                                       // packed form: the 12 dwords of either chunk
+    row_open(xin, smem, t, row);
+    // chunk by chunk: with both chunks of a step converted together the int16 kernels take up to 20 more VGPRs
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
-        const unsigned(&u)[12] = uab[h];
 #pragma unroll
-        for (int g = 0; g < 4; ++g) {                          // samples 8g .. 8g+7 of the chunk
+        for (int g = 0; g < 4; ++g) {                          // samples 8g .. 8g+7 of chunk h
             int s[8];
-            p12_unpack8(u[3 * g], u[3 * g + 1], u[3 * g + 2], s);
+            row_step(xin, smem, t, row, h, g, s);
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
-                const int j = 8 * g + e;
+                const int j = 8 * g + e;                       // index inside the chunk
                 float x;
                 asm("v_mul_f32 %0, %1, %2" : "=v"(x) : "v"((float)s[e]), "v"(in_scale));     // one float32 rounding, never fused
                 const double2 w = wt[(16 * h + (j >> 1)) * 256 + t];

@@ -91,7 +91,7 @@ def test_packed_equals_int16_with_float64_state(ch, torch_mod, scale):
     for window in (None, np.blackman(N).astype(np.float32)):
         if window is not None:
             ch.set_window_f32(window)
-        for name in ("butter12", "cheby7", "default"):
+        for name in ("butter12", "cheby7", "butter3", "default"):
             select(ch, cascades()[name])
             for kind in ("mag_full", "time"):
                 a = ch.process_f32(d_p, out_kind=kind, scale=scale)
