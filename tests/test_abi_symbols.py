@@ -1,15 +1,13 @@
 """CPU: the C-ABI library loads and exports every symbol include/specan.h declares (no compute)."""
 import ctypes
 import os
-import re
 
 from conftest import ROOT
+from native import declared, needed, undefined
 
 
 def declared_symbols():
-    txt = open(os.path.join(ROOT, "include", "specan.h")).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return sorted(set(re.findall(r"\b(sa_[a-z0-9_]+)\s*\(", txt)))
+    return declared(os.path.join(ROOT, "include", "specan.h"))
 
 
 def test_header_declares_the_boundary():
@@ -43,8 +41,7 @@ def test_every_declared_symbol_is_bound_with_its_signature(hip_lib_built):
 def test_no_torch_or_oracle_linkage(hip_lib_built):
     """The product library links HIP only: no torch, no oracle."""
     from fpga_real_time_fft_analyzer_amd import abi
-    import subprocess
-    out = subprocess.run(["ldd", abi.LIB_PATH], capture_output=True, text=True).stdout
+    out = needed(abi.LIB_PATH)
     assert "torch" not in out and "specan_oracle" not in out
     assert "amdhip64" in out
 
@@ -67,9 +64,7 @@ def test_no_environment_switches_in_the_product():
         if fn.endswith((".cpp", ".hip", ".hpp", ".h")):
             assert "getenv" not in open(os.path.join(csrc, fn)).read(), fn
     from fpga_real_time_fft_analyzer_amd import abi
-    import subprocess
-    syms = subprocess.run(["nm", "-D", "--undefined-only", abi.LIB_PATH], capture_output=True, text=True).stdout
-    assert "getenv" not in syms
+    assert "getenv" not in undefined(abi.LIB_PATH)
 
 
 def test_create_without_gpu_fails_loudly(hip_lib_built):

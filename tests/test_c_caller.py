@@ -7,7 +7,6 @@ GPU box: its frames equal the golden digests of G4 (integer model) bit for bit."
 import ctypes
 import hashlib
 import os
-import shutil
 import subprocess
 import threading
 
@@ -15,22 +14,15 @@ import numpy as np
 import pytest
 
 from conftest import N, ROOT, load_golden
+from native import link_c_caller
 
 PKG = os.path.join(ROOT, "fpga_real_time_fft_analyzer_amd")
 
 
 @pytest.fixture(scope="module")
 def caller(tmp_path_factory, hip_lib_built):
-    gcc = shutil.which("gcc")
-    assert gcc, "gcc is part of the image"
     exe = str(tmp_path_factory.mktemp("c_caller") / "abi_caller")
-    cmd = [gcc, "-O2", "-Wall", "-Werror", "-std=c11", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include",
-           "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "c", "abi_caller.c"),
-           "-L" + PKG, "-lspecan_hip", "-L/opt/rocm/lib", "-lamdhip64",
-           "-Wl,-rpath," + PKG, "-Wl,-rpath,/opt/rocm/lib", "-o", exe]
-    r = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr
-    return exe
+    return link_c_caller(os.path.join(ROOT, "tests", "c", "abi_caller.c"), exe, PKG)
 
 
 def test_c_caller_builds_and_fails_loudly_without_gpu(caller):

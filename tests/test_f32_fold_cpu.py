@@ -6,29 +6,20 @@ arithmetic in a stand-alone program under the host sanitizers, and the numpy mir
 whose expected bits are derived by hand below, never from the code under test."""
 import ctypes
 import os
-import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import N, ROOT
+from conftest import N
 from kernel_inventory import TABLE, inventory, lds_of, lds_remarks, unit_text
+from native import INCLUDE, compiles_as_c, declared, exported, needed, standalone_checks, undefined
 
 SA_OK, SA_EINVAL, SA_ESHAPE = 0, -1, -2
 BASE = (1 << 47) - (1 << 36)
 FAR = BASE + (1 << 40)
-INCLUDE = os.path.join(ROOT, "include")
 HEADER = os.path.join(INCLUDE, "specan_fold.h")
-CSRC = os.path.join(ROOT, "fpga_real_time_fft_analyzer_amd", "csrc")
 NAMES = ["sa_fold_check", "sa_fold_last_error", "sa_fold_mag_f32", "sa_fold_version"]
 PAIRS = [(a, k) for a in range(8) for k in range(7) if (a, k) != (0, 0)]
-
-
-def declared(path):
-    txt = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(sa_[a-z0-9_]+)\s*\(", txt)))
 
 
 def in_bytes(B):
@@ -54,7 +45,7 @@ def f32(*v):
 
 @pytest.fixture(scope="module")
 def fold_lib():
-    """libspecan_fold.so, built on demand by the package's one build step (hipcc cross-compiles without a GPU)."""
+    """libspecan_fold.so, built on demand by the package's one build step (it cross-compiles without a GPU)."""
     from fpga_real_time_fft_analyzer_amd import abi
     if not os.path.exists(abi.FOLD_LIB_PATH):
         abi.build()
@@ -72,11 +63,7 @@ def test_header_library_and_binding_table(fold_lib):
     c_int result except the error text; nothing is in the other two tables or headers, which are what they were."""
     from fpga_real_time_fft_analyzer_amd import abi
     assert declared(HEADER) == NAMES
-    nm = shutil.which("nm") or "/opt/rocm/llvm/bin/llvm-nm"
-    r = subprocess.run([nm, "-D", "--defined-only", abi.FOLD_LIB_PATH], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, r.stderr
-    exported = sorted(ln.split()[-1] for ln in r.stdout.splitlines() if " T " in ln and "sa_" in ln.split()[-1])
-    assert exported == NAMES, exported
+    assert [n for n in exported(abi.FOLD_LIB_PATH) if "sa_" in n] == NAMES
     assert sorted(abi.FOLD_SIGNATURES) == NAMES
     assert not set(NAMES) & (set(abi.SIGNATURES) | set(abi.EXT_SIGNATURES))
     assert not set(NAMES) & set(declared(os.path.join(INCLUDE, "specan.h")) + declared(os.path.join(INCLUDE, "specan_ext.h")))
@@ -92,25 +79,17 @@ def test_header_library_and_binding_table(fold_lib):
 
 
 def test_header_compiles_as_c(tmp_path):
-    src = tmp_path / "use_fold.c"
-    src.write_text('#include "specan_fold.h"\n'
+    compiles_as_c(tmp_path, '#include "specan_fold.h"\n'
                    "int use(const float *m, sa_fold_point *o) { return sa_fold_mag_f32(m, o, 8, 2, 4, 0) + sa_fold_check(2, 4, 16, 32, 0)"
                    " + sa_fold_version() - SA_FOLD_VERSION + (int)sizeof(sa_fold_point) - 8 + (sa_fold_last_error()[0] != 0)"
                    " + SA_N - 16384 + SA_FOLD_LOG2A_MAX - 7 + SA_FOLD_LOG2W_MAX - 6; }\n")
-    gcc = shutil.which("gcc") or shutil.which("cc")
-    r = subprocess.run([gcc, "-std=c99", "-Wall", "-Werror", "-pedantic", "-fsyntax-only", "-I", INCLUDE, str(src)],
-                       capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, r.stderr
 
 
 def test_library_links_hip_alone_and_reads_no_environment(fold_lib):
     from fpga_real_time_fft_analyzer_amd import abi
-    r = subprocess.run(["ldd", abi.FOLD_LIB_PATH], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, r.stderr
-    assert "amdhip64" in r.stdout and "torch" not in r.stdout and "oracle" not in r.stdout and "specan_hip" not in r.stdout, r.stdout
-    nm = shutil.which("nm") or "/opt/rocm/llvm/bin/llvm-nm"
-    undefined = subprocess.run([nm, "-D", "--undefined-only", abi.FOLD_LIB_PATH], capture_output=True, text=True, timeout=120).stdout
-    assert "getenv" not in undefined
+    libs = needed(abi.FOLD_LIB_PATH)
+    assert "amdhip64" in libs and "torch" not in libs and "oracle" not in libs and "specan_hip" not in libs, libs
+    assert "getenv" not in undefined(abi.FOLD_LIB_PATH)
     text = unit_text("fold_mag_f32.hip") + unit_text("sa_fold_check.cpp")
     assert "sa_fold_mag_f32" in text and "sa_fold_check_call" in text
     assert "getenv" not in text and "environ" not in text.replace("environment", "")
@@ -204,23 +183,10 @@ def test_refusals_in_their_order(check):
 
 
 def test_standalone_program_under_host_sanitizers(tmp_path):
-    """tests/cpp/test_sa_fold_check.cpp + csrc/sa_fold_check.cpp, host only, with -fsanitize=address,undefined when that links
-    here (a plain build otherwise: the program's own checks still run): the same arithmetic at B = 70 000, B = 2^31 - 128 and
-    addresses near 2^47 and 2^64."""
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    exe = str(tmp_path / "test_sa_fold_check")
-    srcs = [os.path.join(ROOT, "tests", "cpp", "test_sa_fold_check.cpp"), os.path.join(CSRC, "sa_fold_check.cpp")]
-    base = [hipcc, "-O1", "-g", "-std=c++17", "--offload-host-only", "-x", "hip", *srcs, "-o", exe]
-    r = subprocess.run(base + ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"],
-                       capture_output=True, text=True, timeout=300)
-    sanitized = r.returncode == 0
-    if not sanitized:
-        r = subprocess.run(base, capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr
-    print("sanitizers:", "address,undefined" if sanitized else "did not link here: plain build")
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0 and r.stdout.startswith("ok "), r.stdout + r.stderr
-    assert int(r.stdout.split()[1]) > 50000
+    """tests/cpp/test_sa_fold_check.cpp + csrc/sa_fold_check.cpp, host only, under the address and undefined-behaviour
+    sanitizers when they link here (a plain build otherwise: the program's own checks still run): the same arithmetic at
+    B = 70 000, B = 2^31 - 128 and addresses near 2^47 and 2^64."""
+    assert standalone_checks(tmp_path, "test_sa_fold_check", ["sa_fold_check.cpp"]) > 50000
 
 
 # ------------------------------------------------------------------------------------------------------------- the mirror

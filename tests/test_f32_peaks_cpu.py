@@ -8,22 +8,19 @@ import ctypes
 import itertools
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import N, ROOT
-from kernel_inventory import HIPCC_FLAGS, TABLE, inventory, unit_text
+from conftest import N
+from kernel_inventory import TABLE, inventory, unit_text
+from native import CSRC, INCLUDE, compiles_as_c, declared, exported, needed, remarks, standalone_checks, undefined
 
 SA_OK, SA_EINVAL, SA_ESHAPE = 0, -1, -2
 BASE = (1 << 47) - (1 << 36)
 FAR = BASE + (1 << 40)
 FAR2 = BASE + (1 << 41)
-INCLUDE = os.path.join(ROOT, "include")
 HEADER = os.path.join(INCLUDE, "specan_peaks.h")
-CSRC = os.path.join(ROOT, "fpga_real_time_fft_analyzer_amd", "csrc")
 NAMES = ["sa_peaks_check", "sa_peaks_f32", "sa_peaks_last_error", "sa_peaks_version"]
 NAN_KEY = 0x7FC00000
 
@@ -227,14 +224,9 @@ def test_rows_are_independent_and_arguments_are_checked():
 
 
 # ------------------------------------------------------------------------------------------------------------ the surface
-def declared(path):
-    txt = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(sa_[a-z0-9_]+)\s*\(", txt)))
-
-
 @pytest.fixture(scope="module")
 def peaks_lib():
-    """libspecan_peaks.so, built on demand by the package's one build step (hipcc cross-compiles without a GPU)."""
+    """libspecan_peaks.so, built on demand by the package's one build step (it cross-compiles without a GPU)."""
     from fpga_real_time_fft_analyzer_amd import abi
     if not os.path.exists(abi.PEAKS_LIB_PATH):
         abi.build()
@@ -253,11 +245,7 @@ def test_header_library_and_binding_table(peaks_lib):
     in the other tables or headers, which are what they were."""
     from fpga_real_time_fft_analyzer_amd import abi
     assert declared(HEADER) == NAMES
-    nm = shutil.which("nm") or "/opt/rocm/llvm/bin/llvm-nm"
-    r = subprocess.run([nm, "-D", "--defined-only", abi.PEAKS_LIB_PATH], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, r.stderr
-    exported = sorted(ln.split()[-1] for ln in r.stdout.splitlines() if " T " in ln and "sa_" in ln.split()[-1])
-    assert exported == NAMES, exported
+    assert [n for n in exported(abi.PEAKS_LIB_PATH) if "sa_" in n] == NAMES
     assert sorted(abi.PEAKS_SIGNATURES) == NAMES
     assert not set(NAMES) & (set(abi.SIGNATURES) | set(abi.EXT_SIGNATURES) | set(abi.FOLD_SIGNATURES))
     for other in ("specan.h", "specan_ext.h", "specan_fold.h"):
@@ -276,28 +264,20 @@ def test_header_library_and_binding_table(peaks_lib):
 
 
 def test_header_compiles_as_c99_pedantic(tmp_path):
-    src = tmp_path / "use_peaks.c"
-    src.write_text('#include "specan_peaks.h"\n'
+    compiles_as_c(tmp_path, '#include "specan_peaks.h"\n'
                    "int use(const void *p, sa_peak *o, int32_t *c) { return sa_peaks_f32(p, SA_PEAKS_IN_POINT_POWER, o, c, 8, 8, 0.5f,"
                    " 0, SA_N, 1, 0) + sa_peaks_check(SA_PEAKS_IN_MAG, 16, 32, 64, 0, 1, 0u, 0, 1, 1) + sa_peaks_version()"
                    " - SA_PEAKS_VERSION + (int)sizeof(sa_peak) - 8 + (sa_peaks_last_error()[0] != 0) + SA_PEAKS_K_MAX - 32"
                    " + SA_PEAKS_IN_POINT_PEAK - 1 + (o->bin < 0) + (o->mag > 0.0f); }\n")
-    gcc = shutil.which("gcc") or shutil.which("cc")
-    r = subprocess.run([gcc, "-std=c99", "-Wall", "-Werror", "-pedantic", "-fsyntax-only", "-I", INCLUDE, str(src)],
-                       capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, r.stderr
 
 
 def test_library_links_hip_alone_and_reads_no_environment(peaks_lib):
     from fpga_real_time_fft_analyzer_amd import abi
-    r = subprocess.run(["ldd", abi.PEAKS_LIB_PATH], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, r.stderr
+    libs = needed(abi.PEAKS_LIB_PATH)
     for other in ("torch", "oracle", "specan_hip", "specan_fold"):
-        assert other not in r.stdout, r.stdout
-    assert "amdhip64" in r.stdout
-    nm = shutil.which("nm") or "/opt/rocm/llvm/bin/llvm-nm"
-    undefined = subprocess.run([nm, "-D", "--undefined-only", abi.PEAKS_LIB_PATH], capture_output=True, text=True, timeout=120).stdout
-    assert "getenv" not in undefined
+        assert other not in libs, libs
+    assert "amdhip64" in libs
+    assert "getenv" not in undefined(abi.PEAKS_LIB_PATH)
     text = unit_text("peaks_f32.hip") + unit_text("sa_peaks_check.cpp")
     assert "sa_peaks_f32" in text and "sa_peaks_check_call" in text
     assert "getenv" not in text and "environ" not in text.replace("environment", "")
@@ -322,11 +302,7 @@ def test_kernel_inventories(peaks_lib):
 def test_resource_remarks_show_no_scratch_and_no_spill():
     """The compiler's figures for the three kernels, as `make resource-peaks-f32` prints them: no scratch, no SGPR or VGPR
     spill, the 80 bytes of LDS of the four wave slots (two buffers) and the four counts, static -- no dynamic LDS."""
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    r = subprocess.run([hipcc, *HIPCC_FLAGS, "peaks_f32.hip", "-o", os.devnull, "-Rpass-analysis=kernel-resource-usage"], cwd=CSRC,
-                       capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-2000:]
-    err = r.stderr
+    err = remarks("peaks_f32.hip")
     assert len(re.findall(r"Function Name: \S*peaks_f32_kernel", err)) == 3
     for what, want in (("ScratchSize \\[bytes/lane\\]", 0), ("SGPRs Spill", 0), ("VGPRs Spill", 0), ("LDS Size \\[bytes/block\\]", 80)):
         got = [int(v) for v in re.findall(what + r": (\d+)", err)]
@@ -427,23 +403,10 @@ def test_refusals_in_their_order(check, peaks_lib):
 
 
 def test_standalone_program_under_host_sanitizers(tmp_path):
-    """tests/cpp/test_sa_peaks_check.cpp + csrc/sa_peaks_check.cpp, host only, with -fsanitize=address,undefined when that
-    links here (a plain build otherwise: the program's own checks still run): the same arithmetic at rows up to 2^31 - 1 and
-    addresses near 2^47 and 2^64.  Nothing is loaded into this process."""
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    exe = str(tmp_path / "test_sa_peaks_check")
-    srcs = [os.path.join(ROOT, "tests", "cpp", "test_sa_peaks_check.cpp"), os.path.join(CSRC, "sa_peaks_check.cpp")]
-    base = [hipcc, "-O1", "-g", "-std=c++17", "--offload-host-only", "-x", "hip", *srcs, "-o", exe]
-    r = subprocess.run(base + ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"],
-                       capture_output=True, text=True, timeout=300)
-    sanitized = r.returncode == 0
-    if not sanitized:
-        r = subprocess.run(base, capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr
-    print("sanitizers:", "address,undefined" if sanitized else "did not link here: plain build")
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0 and r.stdout.startswith("ok "), r.stdout + r.stderr
-    assert int(r.stdout.split()[1]) > 100000
+    """tests/cpp/test_sa_peaks_check.cpp + csrc/sa_peaks_check.cpp, host only, under the address and undefined-behaviour
+    sanitizers when they link here (a plain build otherwise: the program's own checks still run): the same arithmetic at rows
+    up to 2^31 - 1 and addresses near 2^47 and 2^64.  Nothing is loaded into this process."""
+    assert standalone_checks(tmp_path, "test_sa_peaks_check", ["sa_peaks_check.cpp"]) > 100000
 
 
 # ----------------------------------------------------------------------------------------------------------- the wrappers

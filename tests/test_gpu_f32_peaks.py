@@ -10,16 +10,12 @@ bins of magnitudes (field 0) or two bins of records (fields 1, 2), so a lane bou
 wave boundary (64 lanes; the neighbour there comes from a load, not from the adjacent lane) at every multiple of 256 / 128
 bins, and a thread's next unit starts 1024 / 512 bins further on; bins 0 and 16383 have a neighbour that does not exist.
 EDGES holds the first and last bin on both sides of each kind of boundary for both unit sizes."""
-import ctypes
-import os
-import shutil
-import subprocess
-
 import numpy as np
 import pytest
 
-from conftest import N, ROOT, load_golden
+from conftest import N, load_golden
 from gpu_support import ch, to_device, torch_mod  # noqa: F401 (fixtures)
+from native import Lds, gpu_helper
 
 pytestmark = pytest.mark.gpu
 
@@ -27,7 +23,6 @@ SA_OK, SA_EINVAL, SA_ESHAPE = 0, -1, -2
 FIELDS = (None, "peak", "power")
 EDGES = (0, 1, 2, 3, 4, 5, 127, 128, 129, 255, 256, 257, 511, 512, 1023, 1024, 4095, 4096, 8191, 8192, 8193, 15359, 15360,
          16127, 16128, 16255, 16256, 16382, 16383)
-HELPER_SRC = os.path.join(ROOT, "tests", "hip", "lds_fill.hip")
 
 
 def _bits(a):
@@ -313,20 +308,7 @@ def test_exactly_the_output_bytes_are_written_and_a_refused_call_writes_nothing(
 def lds_fill(tmp_path_factory, torch_mod):
     """tests/hip/lds_fill.hip, built and bound as tests/test_gpu_isolation.py does: lds_fill(word) writes `word` to all of
     the LDS of every CU, on the current stream."""
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    so = str(tmp_path_factory.mktemp("lds_fill_peaks") / "liblds_fill.so")
-    r = subprocess.run([hipcc, "--offload-arch=gfx950", "-O2", "-fPIC", "-shared", HELPER_SRC, "-o", so],
-                       capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr
-    L = ctypes.CDLL(so)                        # torch is imported: the helper binds to the HIP runtime torch mapped
-    L.lds_fill.argtypes = [ctypes.c_uint32, ctypes.c_int, ctypes.c_void_p]
-    L.lds_fill.restype = ctypes.c_int
-    grid = 8 * torch_mod.cuda.get_device_properties(0).multi_processor_count
-
-    def fill(word):
-        rc = L.lds_fill(word, grid, torch_mod.cuda.current_stream().cuda_stream)
-        assert rc == 0, f"lds_fill: hipError {rc}"
-    return fill
+    return Lds(gpu_helper(tmp_path_factory.mktemp("lds_fill_peaks"), "lds_fill"), torch_mod).fill
 
 
 def test_poisoned_lds(ch, torch_mod, wide, lds_fill):

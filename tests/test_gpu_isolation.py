@@ -25,21 +25,16 @@ cancels it arithmetically passes them all: 0 * x = 0 for finite garbage.  Here t
     must be bit-identical to the same frames run as a clean-only batch, and finite.  Nothing is asserted about the bad
     frames except the shape of their rows.
 """
-import ctypes
-import os
-import shutil
-import subprocess
-
 import numpy as np
 import pytest
 
-from conftest import N, ROOT, load_golden
+from conftest import N, load_golden
 from gpu_support import ch, table_window, to_device, torch_mod  # noqa: F401 (fixtures)
 from kernel_inventory import (NO_LDS_UNITS, TABLE, float_kernels, inventory, lds_of, lds_remarks, q15_kernels, unit_text)
+from native import Lds, exported, gpu_helper
 from q15_mirrors import bits, decode, marker_expect, spectra_expect, trace_expect
 from structured_cases import cascades, plan_header
 
-HELPER_SRC = os.path.join(ROOT, "tests", "hip", "lds_fill.hip")
 NAN_WORD = 0xFFFFFFFF          # NaN as float and as double; -1 as an int16 pair
 INF_WORD = 0x7F800000          # +Inf as float
 I16_MIN_WORD = 0x80008000      # -32768 as an int16 pair
@@ -55,49 +50,12 @@ I16_SCALE = 1.0 / 2048
 # ------------------------------------------------------------------------------------------------------ LDS helper
 @pytest.fixture(scope="module")
 def lds_helper_so(tmp_path_factory):
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    so = str(tmp_path_factory.mktemp("lds_fill") / "liblds_fill.so")
-    r = subprocess.run([hipcc, "--offload-arch=gfx950", "-O2", "-fPIC", "-shared", HELPER_SRC, "-o", so],
-                       capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr
-    return so
+    return gpu_helper(tmp_path_factory.mktemp("lds_fill"), "lds_fill")
 
 
 def test_lds_helper_cross_compiles(lds_helper_so):
     """CPU: the helper builds for gfx950 and exports its two C entry points."""
-    nm = shutil.which("nm") or "/opt/rocm/llvm/bin/llvm-nm"
-    r = subprocess.run([nm, "-D", "--defined-only", lds_helper_so], capture_output=True, text=True, timeout=60)
-    assert r.returncode == 0, r.stderr
-    text = {ln.split()[-1] for ln in r.stdout.splitlines() if len(ln.split()) == 3 and ln.split()[1] == "T"}
-    assert {"lds_fill", "lds_probe"} <= text, r.stdout
-
-
-class Lds:
-    """lds_fill / lds_probe on the current torch stream, over a grid of 8 workgroups per CU."""
-
-    def __init__(self, so, torch):
-        self.torch = torch
-        L = ctypes.CDLL(so)                    # torch is imported: the helper binds to the HIP runtime torch mapped
-        L.lds_fill.argtypes = [ctypes.c_uint32, ctypes.c_int, ctypes.c_void_p]
-        L.lds_probe.argtypes = [ctypes.c_uint32, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
-        L.lds_fill.restype = L.lds_probe.restype = ctypes.c_int
-        self.L = L
-        self.grid = 8 * torch.cuda.get_device_properties(0).multi_processor_count
-        self.counts = torch.empty(self.grid * 4, dtype=torch.int32, device="cuda")
-
-    def _stream(self):
-        return self.torch.cuda.current_stream().cuda_stream
-
-    def fill(self, word):
-        rc = self.L.lds_fill(word, self.grid, self._stream())
-        assert rc == 0, f"lds_fill: hipError {rc}"
-
-    def probe(self, word):
-        """Words differing from `word`, one count per probe wave (-1 stays where a wave stored nothing)."""
-        self.counts.fill_(-1)
-        rc = self.L.lds_probe(word, self.grid, self.counts.data_ptr(), self._stream())
-        assert rc == 0, f"lds_probe: hipError {rc}"
-        return self.counts.cpu().numpy().view(np.uint32)
+    assert {"lds_fill", "lds_probe"} <= set(exported(lds_helper_so))
 
 
 @pytest.fixture(scope="module")

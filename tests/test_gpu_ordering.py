@@ -22,19 +22,16 @@ made) and one copy stream per cached feeder.  Every hold is one wave and at most
 to a few seconds (the last test prints and bounds the sum)."""
 import ctypes
 import itertools
-import os
-import shutil
-import subprocess
 import time
 
 import numpy as np
 import pytest
 
-from conftest import N, ROOT, load_golden
+from conftest import N, load_golden
 from gpu_support import torch_mod  # noqa: F401 (fixtures)
+from native import exported, gpu_helper
 from structured_cases import cascades
 
-HELPER_SRC = os.path.join(ROOT, "tests", "hip", "stream_hold.hip")
 HOLD_MS = 40               # H of every held scenario; the enqueues it has to outlast took 0.04 .. 0.74 ms (FIGURE lines)
 PROBE_MS = 20              # the hold of pick_held_stream
 FREE_WITHIN_S = 5e-3       # ... within which work on a free stream must complete
@@ -46,21 +43,12 @@ SIZES = (8, 8, 5, 8, 1, 8, 8, 3)          # frames per batch of the feeder tests
 # --------------------------------------------------------------------------------------------------- the hold helper
 @pytest.fixture(scope="module")
 def hold_so(tmp_path_factory):
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    so = str(tmp_path_factory.mktemp("stream_hold") / "libstream_hold.so")
-    r = subprocess.run([hipcc, "--offload-arch=gfx950", "-O2", "-fPIC", "-shared", HELPER_SRC, "-o", so],
-                       capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr
-    return so
+    return gpu_helper(tmp_path_factory.mktemp("stream_hold"), "stream_hold")
 
 
 def test_stream_hold_cross_compiles(hold_so):
     """CPU: the helper builds for gfx950 and exports its one C entry point."""
-    nm = shutil.which("nm") or "/opt/rocm/llvm/bin/llvm-nm"
-    r = subprocess.run([nm, "-D", "--defined-only", hold_so], capture_output=True, text=True, timeout=60)
-    assert r.returncode == 0, r.stderr
-    text = {ln.split()[-1] for ln in r.stdout.splitlines() if len(ln.split()) == 3 and ln.split()[1] == "T"}
-    assert "stream_hold" in text, r.stdout
+    assert "stream_hold" in exported(hold_so)
 
 
 class Env:

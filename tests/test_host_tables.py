@@ -3,13 +3,12 @@ tests/cpp/test_sa_tables.cpp.  sa_create() needs a GPU, these functions do not: 
 their per-butterfly records, the float window, the three window layouts, the three float twiddle tables and the
 cosine-window fit are checked here against the oracle, the golden ROM and numpy."""
 import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import N, ROOT, load_golden
+from conftest import N, load_golden
+from native import standalone
 
 TW_RECS = 4096 + 1024 + 256            # kSaTwRecs (csrc/sa_common.hpp)
 
@@ -17,20 +16,12 @@ TW_RECS = 4096 + 1024 + 256            # kSaTwRecs (csrc/sa_common.hpp)
 @pytest.fixture(scope="module")
 def tables(tmp_path_factory):
     """{file name: array} of everything the program wrote, plus "stdout"."""
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     d = tmp_path_factory.mktemp("sa_tables")
-    exe = str(d / "test_sa_tables")
-    srcs = [os.path.join(ROOT, "tests", "cpp", "test_sa_tables.cpp"),
-            os.path.join(ROOT, "fpga_real_time_fft_analyzer_amd", "csrc", "sa_tables.cpp")]
-    r = subprocess.run([hipcc, "-O2", "-std=c++17", "--offload-host-only", "-x", "hip", *srcs, "-o", exe],
-                       capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr
-    r = subprocess.run([exe, str(d)], capture_output=True, text=True, timeout=60)
-    assert r.returncode == 0, r.stdout + r.stderr
+    stdout = standalone(d, "test_sa_tables", ["sa_tables.cpp"], sanitize=False, args=[str(d)])
     kinds = {"f64": np.float64, "f32": np.float32, "i16": np.int16, "u32": np.uint32}
     t = {fn: np.fromfile(str(d / fn), dtype=np.dtype(kinds[fn.rsplit(".", 1)[1]]).newbyteorder("<"))
          for fn in os.listdir(str(d)) if fn.rsplit(".", 1)[-1] in kinds}
-    t["stdout"] = r.stdout
+    t["stdout"] = stdout
     return t
 
 

@@ -2,10 +2,10 @@
 import ctypes
 import os
 import re
-import subprocess
 
 import pytest
 
+import native
 from conftest import ROOT
 
 N = 16384
@@ -29,23 +29,15 @@ def test_header_declares_marker_output():
 
 def test_marker_record_layout_in_c(tmp_path):
     """sizeof(sa_marker) == 16 with the fields at 0, 4, 8, 12 for a C compiler that includes the header."""
-    src = tmp_path / "m.c"
-    src.write_text('#include <stddef.h>\n#include "specan.h"\n'
-                   "_Static_assert(sizeof(sa_marker) == 16, \"size\");\n"
-                   "_Static_assert(offsetof(sa_marker, peak_bin) == 4, \"bin\");\n"
-                   "_Static_assert(offsetof(sa_marker, band_power) == 8, \"power\");\n"
-                   "_Static_assert(offsetof(sa_marker, reserved) == 12, \"reserved\");\n"
-                   "int main(void) { return SA_OUT_MARKER == 4 ? 0 : 1; }\n")
-    cc = next((c for c in ("cc", "gcc", "clang", "/opt/rocm/llvm/bin/clang") if _which(c)), None)
-    if cc is None:
+    if native.CC is None:
         pytest.skip("no C compiler")
-    subprocess.check_call([cc, "-std=c11", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(tmp_path / "m")])
-    assert subprocess.call([str(tmp_path / "m")]) == 0
-
-
-def _which(c):
-    from shutil import which
-    return which(c) is not None
+    text = ('#include <stddef.h>\n#include "specan.h"\n'
+            "_Static_assert(sizeof(sa_marker) == 16, \"size\");\n"
+            "_Static_assert(offsetof(sa_marker, peak_bin) == 4, \"bin\");\n"
+            "_Static_assert(offsetof(sa_marker, band_power) == 8, \"power\");\n"
+            "_Static_assert(offsetof(sa_marker, reserved) == 12, \"reserved\");\n"
+            "int main(void) { return SA_OUT_MARKER == 4 ? 0 : 1; }\n")
+    assert native.c_program_exit_code(tmp_path, text) == 0
 
 
 def test_python_constants():

@@ -2,14 +2,11 @@
 helpers sa_pack_samples_p12 / sa_unpack_samples_p12 (csrc/sa_p12.cpp, no GPU), the packed FrameCutter, and the
 stand-alone program tests/cpp/test_sa_p12.cpp that runs the C helpers under the host sanitizers."""
 import ctypes as C
-import os
-import shutil
-import subprocess
-
 import numpy as np
 import pytest
 
-from conftest import N, ROOT
+from conftest import N
+from native import standalone_checks
 
 from fpga_real_time_fft_analyzer_amd.ingest import FrameCutter, P12_FRAME_BYTES, pack12, unpack12
 
@@ -154,19 +151,6 @@ def test_int16_and_packed_cutters_cut_the_same_frames(hop):
 
 
 def test_standalone_program_under_host_sanitizers(tmp_path):
-    """tests/cpp/test_sa_p12.cpp + csrc/sa_p12.cpp, host only, with -fsanitize=address,undefined when that links here
-    (a plain build otherwise: the program's own checks still run)."""
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    exe = str(tmp_path / "test_sa_p12")
-    srcs = [os.path.join(ROOT, "tests", "cpp", "test_sa_p12.cpp"),
-            os.path.join(ROOT, "fpga_real_time_fft_analyzer_amd", "csrc", "sa_p12.cpp")]
-    base = [hipcc, "-O1", "-g", "-std=c++17", "--offload-host-only", "-x", "hip", *srcs, "-o", exe]
-    r = subprocess.run(base + ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"],
-                       capture_output=True, text=True, timeout=300)
-    sanitized = r.returncode == 0
-    if not sanitized:
-        r = subprocess.run(base, capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr
-    print("sanitizers:", "address,undefined" if sanitized else "did not link here: plain build")
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0 and r.stdout.startswith("ok "), r.stdout + r.stderr
+    """tests/cpp/test_sa_p12.cpp + csrc/sa_p12.cpp, host only, under the address and undefined-behaviour sanitizers when
+    they link here (a plain build otherwise: the program's own checks still run)."""
+    standalone_checks(tmp_path, "test_sa_p12", ["sa_p12.cpp"])

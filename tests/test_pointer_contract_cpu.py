@@ -9,13 +9,9 @@ What a call must answer is written here, from the words of the contract, and nev
 The export returns the code of sa_check_call (csrc/sa_pointers.cpp), the one check every entry point runs before anything
 else; tests/test_gpu_pointer_contract.py holds the entry points to it on the device, and tests/cpp/test_sa_pointers.cpp and
 tests/cpp/test_sa_call_check.cpp run the unit under the host sanitizers."""
-import os
-import shutil
-import subprocess
-
 import pytest
 
-from conftest import ROOT
+from native import standalone_checks
 
 SA_OK, SA_EINVAL, SA_ESHAPE = 0, -1, -2
 N = 16384
@@ -218,32 +214,14 @@ def test_empty_batch_and_bad_arguments(check):
 
 
 def test_standalone_program_under_host_sanitizers(tmp_path):
-    """tests/cpp/test_sa_pointers.cpp + csrc/sa_pointers.cpp, host only, with -fsanitize=address,undefined when that links
-    here (a plain build otherwise: the program's own checks still run)."""
-    run_standalone(tmp_path, "test_sa_pointers")
+    """tests/cpp/test_sa_pointers.cpp + csrc/sa_pointers.cpp, host only, under the address and undefined-behaviour sanitizers
+    when they link here (a plain build otherwise: the program's own checks still run)."""
+    standalone_checks(tmp_path, "test_sa_pointers", ["sa_pointers.cpp"])
 
 
 def test_standalone_call_check_under_host_sanitizers(tmp_path):
     """tests/cpp/test_sa_call_check.cpp + csrc/sa_pointers.cpp, built and run the same way: for each of the eleven entry
     points every rule it can reach -- code, rule and the words of sa_last_error -- the order of the rules, what the check
     decodes from an accepted call, and both exports against the check."""
-    assert run_standalone(tmp_path, "test_sa_call_check") > 600
+    assert standalone_checks(tmp_path, "test_sa_call_check", ["sa_pointers.cpp"]) > 600
 
-
-def run_standalone(tmp_path, name):
-    """Builds tests/cpp/<name>.cpp with csrc/sa_pointers.cpp and runs it; returns the number of checks it reports."""
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    exe = str(tmp_path / name)
-    srcs = [os.path.join(ROOT, "tests", "cpp", name + ".cpp"),
-            os.path.join(ROOT, "fpga_real_time_fft_analyzer_amd", "csrc", "sa_pointers.cpp")]
-    base = [hipcc, "-O1", "-g", "-std=c++17", "--offload-host-only", "-x", "hip", *srcs, "-o", exe]
-    r = subprocess.run(base + ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"],
-                       capture_output=True, text=True, timeout=300)
-    sanitized = r.returncode == 0
-    if not sanitized:
-        r = subprocess.run(base, capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr
-    print("sanitizers:", "address,undefined" if sanitized else "did not link here: plain build")
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0 and r.stdout.startswith("ok "), r.stdout + r.stderr
-    return int(r.stdout.split()[1])

@@ -5,13 +5,12 @@ every expected answer is worked out here from the words of the header), the wrap
 frames.trace_of_frames against a direct evaluation, and the stand-alone program that runs the kind's one rounding
 (csrc/q15_round.hpp) under the host sanitizers."""
 import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 from conftest import N, ROOT
+from native import standalone_checks
 
 SA_OK, SA_EINVAL, SA_ESHAPE = 0, -1, -2
 KA = ((1, 1), (4, 3), (6, 7))
@@ -223,19 +222,6 @@ def test_numpy_rounds_int64_to_float32_to_nearest_even():
 
 
 def test_standalone_rounding_program_under_host_sanitizers(tmp_path):
-    """tests/cpp/test_q15_round.cpp on csrc/q15_round.hpp, host only, with -fsanitize=address,undefined when that links here
-    (a plain build otherwise: the program's own checks still run)."""
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    exe = str(tmp_path / "test_q15_round")
-    srcs = [os.path.join(ROOT, "tests", "cpp", "test_q15_round.cpp")]
-    base = [hipcc, "-O1", "-g", "-std=c++17", "--offload-host-only", "-x", "hip", *srcs, "-o", exe]
-    r = subprocess.run(base + ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"],
-                       capture_output=True, text=True, timeout=300)
-    sanitized = r.returncode == 0
-    if not sanitized:
-        r = subprocess.run(base, capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr
-    print("sanitizers:", "address,undefined" if sanitized else "did not link here: plain build")
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0 and r.stdout.startswith("ok "), r.stdout + r.stderr
-    assert int(r.stdout.split()[1]) > 1 << 25
+    """tests/cpp/test_q15_round.cpp on csrc/q15_round.hpp, host only, under the address and undefined-behaviour sanitizers
+    when they link here (a plain build otherwise: the program's own checks still run)."""
+    assert standalone_checks(tmp_path, "test_q15_round") > 1 << 25
