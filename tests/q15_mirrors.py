@@ -3,8 +3,6 @@ what the FFT epilogues and the two fold kernels compute, applied to [B,N,2] int1
 own IQ output where a test has held that to the oracle first.  Every one of them is exact: magnitudes through
 frames.decode_mag_16iq_le (the committed mirror of gui.py:250-260), powers as int64 sums rounded ONCE to float32 (nearest
 even; tests/test_q15_trace_cpu.py and tests/test_q15_trace_avg_cpu.py pin that conversion)."""
-import functools
-
 import numpy as np
 
 from conftest import N
@@ -52,14 +50,3 @@ def spectra_expect(mag, ip, A):
     assert B % A == 0
     exact = ip.reshape(B // A, A, N).sum(axis=1)
     return mag.reshape(B // A, A, N).max(axis=1), exact.astype(np.float32), exact
-
-
-@functools.lru_cache(maxsize=None)
-def wide_sections():
-    """Six Q2.14 sections that let the test frames through (the recipe of tests/test_gpu_q15_p12.py): second-order
-    Butterworth low-passes of unity DC gain, cut-offs 0.35 .. 0.85 of Nyquist."""
-    from scipy import signal
-    sos = np.concatenate([signal.butter(2, wc, output="sos") for wc in (0.35, 0.45, 0.55, 0.65, 0.75, 0.85)])
-    q = np.rint(sos * 16384.0)
-    assert q.shape == (6, 6) and np.abs(q).max() <= 32767
-    return q.astype(np.int16)

@@ -28,10 +28,11 @@ cancels it arithmetically passes them all: 0 * x = 0 for finite garbage.  Here t
 import numpy as np
 import pytest
 
-from conftest import N, load_golden
+from conftest import N
 from gpu_support import ch, table_window, to_device, torch_mod  # noqa: F401 (fixtures)
 from kernel_inventory import (NO_LDS_UNITS, TABLE, float_kernels, inventory, lds_of, lds_remarks, q15_kernels, unit_text)
 from native import Lds, exported, gpu_helper
+from q15_cases import call as q15_call, configure as configure_q15
 from q15_mirrors import bits, decode, marker_expect, spectra_expect, trace_expect
 from structured_cases import cascades, plan_header
 
@@ -300,18 +301,16 @@ def test_float_poison_groups_cover_every_form():
 
 
 # ------------------------------------------------------------------------------------- (b) integer chain, poisoned
-C12_B1 = np.array([0, 1, 0, 64, -67, 19, 64, 127, 64, 64, -85, 40], np.int8)          # B1 != 0: the long step
-C12_NOB1 = np.array([32, 0, -32, 64, -67, 19, 64, 0, 64, 64, -85, 40], np.int8)       # B1 = 0 in both sets
-
-# label -> (filter mode, Q7 upload, Q2.14 sections, the cascade kernel: stem and its own template arguments, None = no cascade)
+# setup of q15_cases.SETUPS -> the cascade kernel it launches: stem and its own template arguments, None = no cascade
+# (custom_nob1: B1 = 0 in both sets, the short step; custom_b1: the GUI upload, B1 != 0, the long step)
 Q15_CASES = {
-    "bypass": (0xB1, None, 0, None),
-    "default": (0x00, None, 0, ("filter_q7", ("true",))),
-    "custom_nob1": (0xA1, C12_NOB1, 0, ("filter_q7", ("true",))),
-    "custom_b1": (0xA1, C12_B1, 0, ("filter_q7", ("false",))),
-    "wide1": (0xA2, None, 1, ("filter_w14", ())),
-    "wide3": (0xA2, None, 3, ("filter_w14", ())),
-    "wide6": (0xA2, None, 6, ("filter_w14", ())),
+    "bypass": None,
+    "default": ("filter_q7", ("true",)),
+    "custom_nob1": ("filter_q7", ("true",)),
+    "custom_b1": ("filter_q7", ("false",)),
+    "wide1": ("filter_w14", ()),
+    "wide3": ("filter_w14", ()),
+    "wide6": ("filter_w14", ()),
 }
 Q15_HOP = 4104                  # 8 * 513: the packed frames of a stream alternate between 8-byte aligned and not
 Q15_FORMS = ("i16", "p12", "i16_hop", "p12_hop")       # int16 frames, packed frames, an int16 stream at a hop, a packed one
@@ -347,7 +346,7 @@ def _q15_plan(bypass):
 
 def _q15_want(case):
     """The (kernels launched, window mode) pairs of a case: from Q15_CASES alone, no handle."""
-    cascade = Q15_CASES[case][3]
+    cascade = Q15_CASES[case]
     return {(q15_kernels(cascade, form, call), w) for w, form, _, _, calls in _q15_plan(cascade is None) for call, _ in calls}
 
 
@@ -415,15 +414,13 @@ def _q15_expect(call, arg, iq, t, mag, ip):
 
 
 def _q15_call(ch, call, arg, xd, hop):
-    if call == "filter":
-        return ch.filter_q15(xd)
     if call == "trace":
-        return ch.traces_q15(xd, bucket=arg, hop=hop)
+        return q15_call(ch, arg, xd, hop)
     if call == "trace_avg":
         return ch.traces_q15(xd, bucket=arg[0], group=arg[1], hop=hop)
     if call == "spectra":
         return ch.spectra_q15(xd, arg, hop=hop)
-    return ch.process_q15(xd, out_kind=call, hop=hop)
+    return q15_call(ch, call, xd, hop)                         # "filter" and the out kinds of process_q15
 
 
 @pytest.mark.gpu
@@ -438,15 +435,12 @@ def test_poisoned_lds_integer_chain(ch, torch_mod, oracle, lds, case):
     cascade workgroup's last wave (which still take part in its barriers, and whose staging registers q15_load_tile
     leaves to its `f < batch` guards), start a second cascade workgroup, and keep every workgroup first on its LDS slot.
     The int16 forms keep _frames_i16's impulse frame, zero frame and full-scale last frame; packed forms hold 12-bit
-    samples.  _q15_plan says which batch runs under which words and window modes."""
+    samples.  _q15_plan says which batch runs under which words and window modes.  The wide cases run the first 1, 3 and 6
+    of wide_sections(): the model's time series of every random frame is not zero (asserted), so poison in
+    filter_w14_kernel's LDS rings has something to spoil."""
     from fpga_real_time_fft_analyzer_amd.ingest import pack12
-    mode, c12, nsec_wide, cascade = Q15_CASES[case]
-    sos14 = load_golden("g4_q15_frames.npz")["sos_q14"][:max(1, nsec_wide)]
-    if c12 is not None:
-        ch.load_coeffs_q7(c12)
-    if nsec_wide:
-        ch.load_sos_q14(sos14)
-    ch.set_filter_mode(mode)
+    _, _, mode, c12, sos14 = configure_q15(ch, case)
+    nsec_wide = 0 if sos14 is None else len(sos14)
     plan = _q15_plan(mode == 0xB1)
     # samples: int16 frames as _frames_i16 makes them, and one int16 and one 12-bit stream whose frames at the hop are the
     # frames of the two packed forms and of the stream forms
@@ -460,7 +454,9 @@ def test_poisoned_lds_integer_chain(ch, torch_mod, oracle, lds, case):
         """(iq, time series, mag, integer power) of the batch: the oracle once per sample set and window mode"""
         src = "p12" if form == "p12_hop" else form
         if (src, win_mode) not in refs:
-            iq, t = oracle.chain_q15(frames_of[src], None, win_mode, mode, c12, sos14 if nsec_wide else None, want_time=True)
+            iq, t = oracle.chain_q15(frames_of[src], None, win_mode, mode, c12, sos14, want_time=True)
+            # behind the impulse frame (which the window may null) and the zero frame, every frame carries signal
+            assert t[2:].any(axis=1).all() and iq[2:].reshape(Q15_MAX - 2, -1).any(axis=1).all(), (case, src, win_mode)
             refs[src, win_mode] = (iq, t) + decode(iq)
         rows = _q15_rows(B) if src == "i16" else list(range(B))
         return tuple(a[rows] for a in refs[src, win_mode])

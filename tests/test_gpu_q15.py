@@ -8,6 +8,7 @@ import pytest
 from udp_collect import FrameCollector
 from conftest import N, load_golden
 from gpu_support import ch, to_device, torch_mod  # noqa: F401 (fixtures)
+from q15_cases import GUI_UPLOAD, ZERO_B1_C12, configure, extreme_frames, sample_range, wide_sections
 
 pytestmark = pytest.mark.gpu
 
@@ -34,7 +35,8 @@ def test_golden_digests_all_modes(ch, torch_mod):
         assert np.array_equal(t[2], g[f"time_{name}_f2"])
         assert [sha(t[i]) for i in range(4)] == list(g[f"time_{name}_sha"])
         assert [sha(iq[i]) for i in range(4)] == list(g[f"iq_{name}_sha"])
-    # wide Q2.14 mode with the unsigned-Hann window
+    # wide Q2.14 mode with the unsigned-Hann window: the recorded digests of G4's own sections, which pass nothing (digests
+    # of zero frames, tests/test_q15_cases_cpu.py); the wide cascade on signal is every other 0xA2 test's business
     ch.load_sos_q14(g["sos_q14"])
     ch.set_window_mode_q15(1)
     ch.set_filter_mode(0xA2)
@@ -49,24 +51,20 @@ def test_bit_exact_vs_integer_model(ch, torch_mod, oracle, B, cmd):
     rng = np.random.default_rng(B * 7 + cmd)
     x = rng.integers(-2048, 2048, size=(B, N)).astype(np.int16)
     x[-1] = rng.integers(-32768, 32768, size=N)                      # one full-scale frame
-    c12 = np.array([0, 1, 0, 64, -67, 19, 64, 127, 64, 64, -85, 40], np.int8)
-    sos14 = load_golden("g4_q15_frames.npz")["sos_q14"][:1 + B % 6]      # ragged batches (last wave, last workgroup partly
+    c12 = GUI_UPLOAD
+    sos14 = wide_sections()[:1 + B % 6]                                  # ragged batches (last wave, last workgroup partly
     ch.load_coeffs_q7(c12)                                               # filled) for the wide cascade too, 1..6 sections
     ch.load_sos_q14(sos14)
     ch.set_filter_mode(cmd)
     ref_iq, ref_t = oracle.chain_q15(x, None, 0, cmd, c12, sos14, want_time=True)
+    assert ref_t.any(axis=1).all() and ref_iq.reshape(B, -1).any(axis=1).all()      # every frame carries signal
     xd = to_device(torch_mod, x)
     assert np.array_equal(ch.filter_q15(xd).cpu().numpy(), ref_t)
     assert np.array_equal(ch.process_q15(xd).cpu().numpy(), ref_iq)
 
 
 def test_extreme_inputs(ch, torch_mod, oracle):
-    x = np.zeros((4, N), np.int16)
-    x[0] = 32767
-    x[1] = -32768
-    x[2, ::2] = 32767
-    x[2, 1::2] = -32768
-    x[3, 0] = -32768
+    x = extreme_frames()
     for cmd in (0xB1, 0x00):
         ch.set_filter_mode(cmd)
         ref = oracle.chain_q15(x, None, 0, cmd, None, None)
@@ -119,8 +117,7 @@ def test_zero_tap_uploads_take_the_short_step_and_stay_exact(ch, torch_mod, orac
         iq_ref, t_ref = oracle.chain_q15(x, None, 0, 0xA1, c12, None, want_time=True)
         assert np.array_equal(ch.filter_q15(xd).cpu().numpy(), t_ref), (case, c12)
         assert np.array_equal(ch.process_q15(xd).cpu().numpy(), iq_ref), (case, c12)
-    default = np.array([-14, 0, 14, 107, 21, 127, -15, 0, 15, 107, -21, 127], np.int8)      # imp/filter_pkg.vhd:54-68
-    ch.load_coeffs_q7(default)
+    ch.load_coeffs_q7(ZERO_B1_C12)                                   # imp/filter_pkg.vhd:54-68
     up = ch.process_q15(xd).cpu().numpy()
     ch.set_filter_mode(0x00)
     assert np.array_equal(ch.process_q15(xd).cpu().numpy(), up)
@@ -136,8 +133,7 @@ def test_overlapped_launches_q15(ch, torch_mod, oracle):
     rng = np.random.default_rng(99)
     sizes = [3, 17, 5, 64, 33, 2]
     xs = [rng.integers(-2048, 2048, (b, N)).astype(np.int16) for b in sizes]
-    gui = np.array([0, 1, 0, 64, -67, 19, 64, 127, 64, 64, -85, 40], np.int8)
-    wide = load_golden("g4_q15_frames.npz")["sos_q14"]
+    gui, wide = GUI_UPLOAD, wide_sections()
     ch.set_filter_mode(0x00)
     ch.set_overlap(2)
     s = torch.cuda.Stream()
@@ -158,6 +154,7 @@ def test_overlapped_launches_q15(ch, torch_mod, oracle):
     for k, x in enumerate(xs):
         cmd = 0x00 if k < 3 else (0xA1 if k < 5 else 0xA2)
         ref = oracle.chain_q15(x, None, 0, cmd, gui if cmd == 0xA1 else None, wide if cmd == 0xA2 else None)
+        assert ref.reshape(sizes[k], -1).any(axis=1).all(), k
         assert np.array_equal(got[k], ref), k
     ch.set_filter_mode(0xA1)
     ch.set_overlap(1)
@@ -265,8 +262,7 @@ def test_custom_rom_and_window_modes(ch, torch_mod, oracle):
     xg[:, 777::1001] = -32768
     ch.set_window_q15(rom2)
     ch.set_window_mode_q15(0)
-    gui = np.array([0, 1, 0, 64, -67, 19, 64, 127, 64, 64, -85, 40], np.int8)
-    sos14 = load_golden("g4_q15_frames.npz")["sos_q14"]
+    gui, sos14 = GUI_UPLOAD, wide_sections()
     ch.load_coeffs_q7(gui)
     ch.load_sos_q14(sos14)
     for depth in (1, 2):
@@ -274,6 +270,7 @@ def test_custom_rom_and_window_modes(ch, torch_mod, oracle):
         for cmd in (0x00, 0xA1, 0xA2):
             ch.set_filter_mode(cmd)
             ref_iq, ref_t = oracle.chain_q15(xg, rom2, 0, cmd, gui, sos14, want_time=True)
+            assert ref_t.any(axis=1).all() and ref_iq.reshape(5, -1).any(axis=1).all(), cmd
             got = ch.process_q15(to_device(torch_mod, xg))
             ch.flush()
             assert np.array_equal(got.cpu().numpy(), ref_iq), (depth, cmd)
@@ -341,9 +338,6 @@ def test_fxfft_close_to_float_fft_on_gpu(ch, torch_mod):
     assert np.abs(iq[..., 0] + 1j * iq[..., 1] - ref).max() <= 7.0
 
 
-GUI_UPLOAD = np.array([0, 1, 0, 64, -67, 19, 64, 127, 64, 64, -85, 40], np.int8)      # gui.py:159-179, 1186-1192 defaults
-
-
 @pytest.mark.parametrize("full_scale", [False, True], ids=["12bit", "fullscale"])
 @pytest.mark.parametrize("coeffs", ["default", "gui", "wide"])
 def test_config4_whole_batch(ch, torch_mod, oracle, full_scale, coeffs):
@@ -351,33 +345,23 @@ def test_config4_whole_batch(ch, torch_mod, oracle, full_scale, coeffs):
     second run uniform over the full int16 range, coefficient set (a) the fixed ALPHA/BETA cascade
     (imp/filter_pkg.vhd:54-68, mode 0x00) and (b) the GUI's default upload (gui.py:1186-1192, mode 0xA1);
     the window + cascade output AND the IQ frame of EVERY one of the 4096 frames equal the SA integer model
-    (oracle/specan_oracle.c; parity unpinned vs the RTL / xfft_0).  Third set: mode 0xA2, all six
-    sections of the 12th-order Butterworth of fixture G2 (gui.py:108-157 designs them, :1186-1192 keeps two) in Q2.14
-    (fixture G4's `sos_q14`), unsigned-Hann window -- every frame against or_iir_sos_q14."""
+    (oracle/specan_oracle.c; parity unpinned vs the RTL / xfft_0).  Third set: mode 0xA2, the six
+    Q2.14 sections of q15_cases.wide_sections() (fixture G4's `sos_q14`, the quantised 12th-order Butterworth of fixture
+    G2, carries its gain in a numerator that rounds to zero: all its frames are zero), unsigned-Hann window -- every frame
+    against or_iir_sos_q14, and every frame of the reference carries signal."""
     torch = torch_mod
     gen = torch.Generator(device="cuda").manual_seed(2 + int(full_scale))
     B = 4096
-    lo, hi = (-32768, 32768) if full_scale else (-2048, 2048)
-    x = torch.randint(lo, hi, (B, N), generator=gen, device="cuda", dtype=torch.int32).to(torch.int16)
+    x = torch.randint(*sample_range(full_scale), (B, N), generator=gen, device="cuda", dtype=torch.int32).to(torch.int16)
     ch.reserve(B)
-    sos, wm = None, 0
-    if coeffs == "gui":
-        ch.load_coeffs_q7(GUI_UPLOAD)
-        cmd, c12 = 0xA1, GUI_UPLOAD
-    elif coeffs == "wide":
-        sos, wm = load_golden("g4_q15_frames.npz")["sos_q14"], 1
-        assert sos.shape == (6, 6)
-        ch.load_sos_q14(sos)
-        ch.set_window_mode_q15(wm)
-        cmd, c12 = 0xA2, None
-    else:
-        cmd, c12 = 0x00, None
-    ch.set_filter_mode(cmd)
+    args = configure(ch, {"default": "default", "gui": "gui_upload", "wide": "wide6_hann_u16"}[coeffs])
+    assert coeffs != "wide" or args[4].shape == (6, 6)
     iq = ch.process_q15(x).cpu().numpy()
     tm = ch.filter_q15(x).cpu().numpy()
     xh = x.cpu().numpy()
     for a in range(0, B, 512):                                         # the oracle in slices: bounded host memory
-        ref_iq, ref_t = oracle.chain_q15(xh[a:a + 512], None, wm, cmd, c12, sos, want_time=True)
+        ref_iq, ref_t = oracle.chain_q15(xh[a:a + 512], *args, want_time=True)
+        assert ref_t.any(axis=1).all() and ref_iq.reshape(ref_iq.shape[0], -1).any(axis=1).all(), a
         bad_t = np.nonzero((tm[a:a + 512] != ref_t).any(axis=1))[0]
         bad = np.nonzero((iq[a:a + 512] != ref_iq).reshape(ref_iq.shape[0], -1).any(axis=1))[0]
         assert bad_t.size == 0, f"time series differs in frames {a + bad_t[:8]}"
@@ -389,17 +373,20 @@ def test_config4_whole_batch(ch, torch_mod, oracle, full_scale, coeffs):
 
 
 def test_batch_beyond_two_gib(ch, torch_mod):
-    """36 000 frames: the IQ output is 2.36 GB (offsets pass 2^31), the filter workspace 1.18 GB."""
+    """36 000 frames: the IQ output is 2.36 GB (offsets pass 2^31), the filter workspace 1.18 GB.  In every mode (0xA2: all of
+    wide_sections()) the frames compared are not zero."""
     torch = torch_mod
     gen = torch.Generator(device="cuda").manual_seed(4)
     B = 36000
     x = torch.randint(-2048, 2048, (B, N), generator=gen, device="cuda", dtype=torch.int32).to(torch.int16)
     idx = torch.tensor([0, 1, 16383, 16384, 32767, 32768, B - 1], device="cuda")
-    ch.load_sos_q14(load_golden("g4_q15_frames.npz")["sos_q14"])
+    ch.load_sos_q14(wide_sections())
     for cmd in (0x00, 0xB1, 0xA2):
         ch.set_filter_mode(cmd)
         iq = ch.process_q15(x)
-        assert torch.equal(iq[idx], ch.process_q15(x[idx].contiguous()))
+        few = ch.process_q15(x[idx].contiguous())
+        assert (few != 0).reshape(len(idx), -1).any(dim=1).all().item(), cmd
+        assert torch.equal(iq[idx], few)
         del iq
 
 

@@ -12,70 +12,27 @@ import pytest
 
 from conftest import N
 from gpu_support import ch, check_overlap_profiling_and_graph_capture, to_device, torch_mod  # noqa: F401 (fixtures)
+from fpga_real_time_fft_analyzer_amd.abi import SA_EINVAL, SA_ESHAPE, SA_P12_FRAME_BYTES as P12
+from q15_cases import call, configure, uniform
 
 pytestmark = pytest.mark.gpu
 
-P12 = 24576
-SA_EINVAL, SA_ESHAPE = -1, -2
 KINDS = ("iq", "mag", "marker", 16, 64)                    # a number: the display trace with buckets of that many bins
 BATCHES = (1, 5, 17, 37)       # no multiple of a wave's 4 frames or a workgroup's 16: the f < batch guards, a second and third workgroup
 HOPS = (8,                     # packed frames 12 bytes apart: every alignment mod 16
         4104,                  # = 8 * 513, an odd field: packed frames alternate between 8-byte aligned and not
         8192, 16376,
         16384)                 # the plain call on the reshaped tensor
-GUI_UPLOAD = np.array([0, 1, 0, 64, -67, 19, 64, 127, 64, 64, -85, 40], np.int8)      # gui.py:159-179, 1186-1192 defaults
-# mode -> (filter byte, 12-byte upload, Q2.14 sections, window mode, custom ROM)
-MODES = {
-    "b1_rtl": (0xB1, None, None, 0, False),
-    "b1_hann_u16": (0xB1, None, None, 1, False),
-    "b1_rom": (0xB1, None, None, 0, True),
-    "default": (0x00, None, None, 0, False),
-    "gui_upload": (0xA1, GUI_UPLOAD, None, 0, False),
-    "wide6": (0xA2, None, 6, 0, False),
-    "wide0": (0xA2, None, 0, 0, False),
-}
+MODES = ("b1_rtl", "b1_hann_u16", "b1_rom", "default", "gui_upload", "wide6", "wide0")       # of q15_cases.SETUPS
 
 
 @functools.lru_cache(maxsize=None)
 def samples(full_scale=False):
     """One stream for every test, read-only: random 12-bit samples (so that it serves int16 and packed alike), or full-scale
     int16 ones; as long as the largest batch at the largest hop."""
-    lo, hi = (-32768, 32768) if full_scale else (-2048, 2048)
-    s = np.random.default_rng(1212 + full_scale).integers(lo, hi, max(BATCHES) * N).astype(np.int16)
+    s = uniform(np.random.default_rng(1212 + full_scale), max(BATCHES) * N, full_scale)
     s.setflags(write=False)
     return s
-
-
-@functools.lru_cache(maxsize=None)
-def wide_sections():
-    """Six Q2.14 sections that let the test frames through (the recipe of tests/test_gpu_q15_p12.py)."""
-    from scipy import signal
-    sos = np.concatenate([signal.butter(2, wc, output="sos") for wc in (0.35, 0.45, 0.55, 0.65, 0.75, 0.85)])
-    q = np.rint(sos * 16384.0)
-    assert q.shape == (6, 6) and np.abs(q).max() <= 32767
-    return q.astype(np.int16)
-
-
-def configure(ch, mode):
-    """Put the handle into `mode`; returns oracle.chain_q15's arguments after x."""
-    cmd, c12, nsec, wm, custom_rom = MODES[mode]
-    rom = np.random.default_rng(5).integers(-32768, 32768, N).astype(np.int16) if custom_rom else None
-    if rom is not None:
-        ch.set_window_q15(rom)
-    ch.set_window_mode_q15(wm)
-    if c12 is not None:
-        ch.load_coeffs_q7(c12)
-    sos = None if nsec is None else wide_sections()[:nsec]
-    if sos is not None:
-        ch.load_sos_q14(sos)
-    ch.set_filter_mode(cmd)
-    return rom, wm, cmd, c12, sos
-
-
-def call(ch, kind, x, hop=None, out=None):
-    if isinstance(kind, int):
-        return ch.traces_q15(x, bucket=kind, out=out, hop=hop)
-    return ch.process_q15(x, out=out, out_kind=kind, hop=hop)
 
 
 def cut(stream, hop, packed=False):
@@ -104,12 +61,12 @@ def stream_and_frames(torch, s, hop, B):
     return forms
 
 
-@pytest.mark.parametrize("mode", list(MODES))
+@pytest.mark.parametrize("mode", MODES)
 def test_hop_call_equals_the_frame_call_on_host_cut_frames(ch, torch_mod, oracle, mode):
     """Every kind, both input forms, B = 1, 5, 17, 37 and hop = 8, 4104, 8192, 16376, 16384 in one filter mode; and once,
     at B = 5 and hop = 4104, the integer model on the cut frames."""
     torch = torch_mod
-    args = configure(ch, mode)
+    args = configure(ch, mode, np.random.default_rng(5))
     s = samples()
     for hop in HOPS:
         for B in BATCHES:

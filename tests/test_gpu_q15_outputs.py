@@ -9,8 +9,10 @@ oracle.chain_q15(...) and (b) the handle's own process_q15 IQ output, asserted e
 import numpy as np
 import pytest
 
-from conftest import N, load_golden
+from conftest import N
 from gpu_support import ch, to_device, torch_mod  # noqa: F401 (fixtures)
+from fpga_real_time_fft_analyzer_amd.abi import SA_EINVAL, SA_ESHAPE
+from q15_cases import configure, extreme_frames, uniform, wide_sections
 from q15_mirrors import bits as _bits, decode as _decode, marker_expect as _expect, marker_records as _records
 
 pytestmark = pytest.mark.gpu
@@ -18,9 +20,6 @@ pytestmark = pytest.mark.gpu
 # RANGES of tests/test_gpu_marker.py, plus the two the Q15 contract adds
 RANGES = [(0, N), (0, 8193), (100, 2000), (9000, 12000), (8000, 8400), (0, 1), (8192, 8193), (16383, 16384),
           (8193, N), (5, 6)]
-SA_EINVAL, SA_ESHAPE = -1, -2
-GUI_UPLOAD = np.array([0, 1, 0, 64, -67, 19, 64, 127, 64, 64, -85, 40], np.int8)      # gui.py:159-179, 1186-1192 defaults
-C12_SET = GUI_UPLOAD                      # the 12-byte set of test_gpu_q15.py::test_bit_exact_vs_integer_model is the same upload
 
 
 def _check_marker(rec, mag, ip, lo, hi, tag=""):
@@ -53,57 +52,47 @@ def _check_all(ch, torch_mod, xd, ref_iq, ranges=RANGES, tag=""):
 
 def _samples(rng, B, full_scale):
     """12-bit or full-scale random samples; from B = 7 on: frame 1 all zero, the last frame of the other scale"""
-    lo, hi = (-32768, 32768) if full_scale else (-2048, 2048)
-    x = rng.integers(lo, hi, size=(B, N)).astype(np.int16)
+    x = uniform(rng, (B, N), full_scale)
     if B >= 7:
         x[1] = 0
-        x[-1] = rng.integers(-2048, 2048, N) if full_scale else rng.integers(-32768, 32768, N)
+        x[-1] = uniform(rng, N, not full_scale)
     return x
 
 
-# form -> (filter byte, coefficient set, wide sections, window mode, custom ROM, batch, full-scale samples)
+# form -> (setup of q15_cases.SETUPS, batch, full-scale samples)
 FORMS = {
-    "none_b1": (0xB1, None, 0, 0, False, 1, False),
-    "none_b7_hann_u16": (0xB1, None, 0, 1, False, 7, True),
-    "none_b520_rom": (0xB1, None, 0, 0, True, 520, True),
-    "none_b65": (0xB1, None, 0, 0, False, 65, False),
-    "default_b33": (0x00, None, 0, 0, False, 33, False),
-    "default_b65_rom_hann_u16": (0x00, None, 0, 1, True, 65, True),
-    "default_b520": (0x00, None, 0, 0, False, 520, False),
-    "gui_b7": (0xA1, "gui", 0, 0, False, 7, False),
-    "gui_b33_rom": (0xA1, "gui", 0, 0, True, 33, True),
-    "set12_b65_hann_u16": (0xA1, "set12", 0, 1, False, 65, True),
-    "wide1_b1": (0xA2, None, 1, 0, False, 1, True),
-    "wide2_b7_hann_u16": (0xA2, None, 2, 1, False, 7, False),
-    "wide3_b33_rom": (0xA2, None, 3, 0, True, 33, True),
-    "wide4_b65": (0xA2, None, 4, 0, False, 65, False),
-    "wide5_b7_rom_hann_u16": (0xA2, None, 5, 1, True, 7, True),
-    "wide6_b520_hann_u16": (0xA2, None, 6, 1, False, 520, False),
+    "none_b1": ("b1_rtl", 1, False),
+    "none_b7_hann_u16": ("b1_hann_u16", 7, True),
+    "none_b520_rom": ("b1_rom_rtl", 520, True),
+    "none_b65": ("b1_rtl", 65, False),
+    "default_b33": ("default", 33, False),
+    "default_b65_rom_hann_u16": ("default_rom_hann_u16", 65, True),
+    "default_b520": ("default", 520, False),
+    "gui_b7": ("gui_upload", 7, False),
+    "gui_b33_rom": ("gui_upload_rom", 33, True),
+    "set12_b65_hann_u16": ("gui_upload_hann_u16", 65, True),
+    "wide1_b1": ("wide1", 1, True),
+    "wide2_b7_hann_u16": ("wide2_hann_u16", 7, False),
+    "wide3_b33_rom": ("wide3_rom", 33, True),
+    "wide4_b65": ("wide4", 65, False),
+    "wide5_b7_rom_hann_u16": ("wide5_rom_hann_u16", 7, True),
+    "wide6_b520_hann_u16": ("wide6_hann_u16", 520, False),
 }
 
 
 @pytest.mark.parametrize("form", list(FORMS))
 def test_mag_and_marker_equal_the_decoded_wire_frame(ch, torch_mod, oracle, form):
     """MAG == decode_mag_16iq_le(frame) and MARKER == (max, lo + argmax, int64 power sum) of it, bit for bit, on the
-    oracle's frames: filter modes 0xB1, 0x00, 0xA1 (the GUI upload of fixture G4 and the 12-byte set of
-    test_bit_exact_vs_integer_model), 0xA2 with 1..6 sections; window modes 0 and 1; default and custom ROM; batches 1, 7,
-    33, 65 and 520; 12-bit and full-scale samples; every range of RANGES.  All-zero frames give (+0.0, lo, 0)."""
-    cmd, cset, nsec, wm, custom_rom, B, full = FORMS[form]
+    oracle's frames: filter modes 0xB1, 0x00, 0xA1 (the GUI upload, which is fixture G4's `c_gui` and the 12-byte set of
+    test_bit_exact_vs_integer_model), 0xA2 with the first 1..6 of wide_sections(); window modes 0 and 1; default and custom
+    ROM; batches 1, 7, 33, 65 and 520; 12-bit and full-scale samples; every range of RANGES.  All-zero frames give
+    (+0.0, lo, 0); the frames that are not all zero in are not all zero out."""
+    setup, B, full = FORMS[form]
     rng = np.random.default_rng(1000 + list(FORMS).index(form))
-    g4 = load_golden("g4_q15_frames.npz")
-    c12 = {"gui": np.asarray(g4["c_gui"], np.int8), "set12": C12_SET, None: None}[cset]
-    sos14 = g4["sos_q14"][:nsec] if nsec else None
-    rom = rng.integers(-32768, 32768, size=N).astype(np.int16) if custom_rom else None
-    if rom is not None:
-        ch.set_window_q15(rom)
-    ch.set_window_mode_q15(wm)
-    if c12 is not None:
-        ch.load_coeffs_q7(c12)
-    if sos14 is not None:
-        ch.load_sos_q14(sos14)
-    ch.set_filter_mode(cmd)
+    args = configure(ch, setup, rng)
     x = _samples(rng, B, full)
-    ref = oracle.chain_q15(x, rom, wm, cmd, c12, sos14)
+    ref = oracle.chain_q15(x, *args)
+    assert all(ref[f].any() for f in range(B) if x[f].any()), form
     xd = to_device(torch_mod, x)
     _check_all(ch, torch_mod, xd, ref, tag=form)
     if B >= 7:                                                   # the all-zero frame, spelled out
@@ -121,17 +110,6 @@ def test_mag_and_marker_equal_the_decoded_wire_frame(ch, torch_mod, oracle, form
     assert np.array_equal(bp.cpu().numpy(), bp2)
 
 
-def _extreme_frames():
-    """the frames of tests/test_gpu_q15.py::test_extreme_inputs"""
-    x = np.zeros((4, N), np.int16)
-    x[0] = 32767
-    x[1] = -32768
-    x[2, ::2] = 32767
-    x[2, 1::2] = -32768
-    x[3, 0] = -32768
-    return x
-
-
 def test_extreme_frames(ch, torch_mod, oracle):
     """The frames of test_extreme_inputs (constant +/- full scale, alternating full scale, one full-scale impulse) in
     modes 0xB1 and 0x00 under the default ROM, then in mode 0xB1 under constant ROMs of either sign in both window
@@ -139,7 +117,7 @@ def test_extreme_frames(ch, torch_mod, oracle):
     section in mode 0xA2 (b0 = 32767 in Q2.14, a gain of 2: the constant frames leave the cascade as -32768 / 32767), where
     bin 0 holds re = -32768 -- asserted on the oracle's frames, so the case cannot go missing: re^2 is 2^30 there,
     and a bin's integer power can reach 2^31, which fits uint32_t and not int32_t."""
-    x = _extreme_frames()
+    x = extreme_frames()
     xd = to_device(torch_mod, x)
     for cmd in (0xB1, 0x00):
         ch.set_filter_mode(cmd)
@@ -300,25 +278,21 @@ def test_config4_whole_batch_outputs(ch, torch_mod, oracle):
             _check_marker(rec[a:a + 512], mag, ip, lo, hi, f"frames {a}..")
 
 
-def _setup_wide(ch):
-    ch.load_sos_q14(load_golden("g4_q15_frames.npz")["sos_q14"])
-    ch.set_filter_mode(0xA2)
-
-
 def test_records_are_reproducible_across_calls_overlap_and_graphs(ch, torch_mod):
     """Bit-identical records and magnitudes: repeated calls, overlap depths 2 and 3 (after flush) against the ordered
-    mode, in mode 0xA2 (the depth-2 ordering rule of the wide cascade) and 0x00, and a torch.cuda.graph replay after
-    reserve() against the eager call; a captured call keeps the range of capture time.  Launch timing reports one
-    positive time per call for the new kinds."""
+    mode, in mode 0xA2 (all of wide_sections(): the depth-2 ordering rule of the wide cascade, on frames that are not
+    zero) and 0x00, and a torch.cuda.graph replay after reserve() against the eager call; a captured call keeps the range
+    of capture time.  Launch timing reports one positive time per call for the new kinds."""
     torch = torch_mod
     rng = np.random.default_rng(31)
     xs = [to_device(torch, rng.integers(-2048, 2048, (600, N)).astype(np.int16)) for _ in range(4)]
     ch.reserve(600)
-    for setup in (_setup_wide, lambda c: c.set_filter_mode(0x00)):
-        setup(ch)
+    for setup in ("wide6", "default"):
+        configure(ch, setup)
         ch.set_marker_range(100, 9000)
         ref = [ch.process_q15(x, out_kind="marker").clone() for x in xs]
         refm = ch.process_q15(xs[0], out_kind="mag").clone()
+        assert (refm != 0).any(dim=1).all().item(), setup                # every frame carries signal
         for _ in range(3):
             for x, r in zip(xs, ref):
                 assert torch.equal(ch.process_q15(x, out_kind="marker"), r)
@@ -439,18 +413,20 @@ def test_refusals_leave_the_handle_usable(ch, torch_mod, oracle):
 
 def test_frames_are_isolated(ch, torch_mod, oracle):
     """One frame of extreme samples between ordinary frames does not change the ordinary frames' records or magnitudes:
-    they equal those of the same frames processed alone, in modes 0xB1, 0x00 and 0xA2."""
+    they equal those of the same frames processed alone, in modes 0xB1, 0x00 and 0xA2 (all of wide_sections()), and in
+    each of them every ordinary frame's magnitudes are not all zero."""
     torch = torch_mod
     rng = np.random.default_rng(44)
     x = rng.integers(-2048, 2048, (9, N)).astype(np.int16)
-    ext = _extreme_frames()
-    ch.load_sos_q14(load_golden("g4_q15_frames.npz")["sos_q14"])
+    ext = extreme_frames()
+    ch.load_sos_q14(wide_sections())
     ch.set_marker_range(50, 16000)
     keep = [i for i in range(9) if i != 4]
     for cmd in (0xB1, 0x00, 0xA2):
         ch.set_filter_mode(cmd)
         alone_r = ch.process_q15(to_device(torch, x[keep]), out_kind="marker").cpu().numpy()
         alone_m = ch.process_q15(to_device(torch, x[keep]), out_kind="mag").cpu().numpy()
+        assert alone_m.any(axis=1).all(), cmd
         for e in range(4):
             y = x.copy()
             y[4] = ext[e]

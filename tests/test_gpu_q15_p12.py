@@ -11,10 +11,11 @@ import pytest
 
 from conftest import N
 from gpu_support import ch, check_overlap_profiling_and_graph_capture, to_device, torch_mod  # noqa: F401 (fixtures)
+from fpga_real_time_fft_analyzer_amd.abi import SA_P12_FRAME_BYTES as P12
+from q15_cases import call, configure
 
 pytestmark = pytest.mark.gpu
 
-P12 = 24576
 KINDS = ("iq", "mag", "marker")
 SEAMS = (2, 5, 1026,            # the straddling lanes of FFT stage 0
          7, 8,                  # a lane's 8-sample unit
@@ -22,11 +23,7 @@ SEAMS = (2, 5, 1026,            # the straddling lanes of FFT stage 0
          511, 512,              # the ring wrap
          1023, 1024,            # the stage-0 stride
          8191, 8192, 16376, 16382, 16383)
-GUI_C12 = np.array([0, 1, 0, 64, -67, 19, 64, 127, 64, 64, -85, 40], np.int8)                   # B1 != 0: nine-instruction step
-ZERO_B1_C12 = np.array([-14, 0, 14, 107, 21, 127, -15, 0, 15, 107, -21, 127], np.int8)          # imp/filter_pkg.vhd:54-68
-# filter select, 12-byte upload or None, Q2.14 sections (how many of wide_sections()) or None
-MODES = {"0xB1": (0xB1, None, None), "0x00": (0x00, None, None), "0xA1-b1": (0xA1, GUI_C12, None),
-         "0xA1-zero-b1": (0xA1, ZERO_B1_C12, None), "0xA2-six": (0xA2, None, 6), "0xA2-none": (0xA2, None, 0)}
+MODES = ("0xB1", "0x00", "0xA1-b1", "0xA1-zero-b1", "0xA2-six", "0xA2-none")           # of q15_cases.SETUPS
 
 
 @functools.lru_cache(maxsize=None)
@@ -52,33 +49,6 @@ def batch():
     return x, p
 
 
-@functools.lru_cache(maxsize=None)
-def wide_sections():
-    """Six Q2.14 sections that let the 12-bit test frames through: second-order Butterworth low-passes of unity DC gain,
-    cut-offs 0.35 .. 0.85 of Nyquist.  (The golden file's cascade carries its whole gain in the first section, whose
-    numerator rounds to zero in Q2.14: every output is zero, and a comparison of zeros shows nothing.)"""
-    from scipy import signal
-    sos = np.concatenate([signal.butter(2, wc, output="sos") for wc in (0.35, 0.45, 0.55, 0.65, 0.75, 0.85)])
-    q = np.rint(sos * 16384.0)
-    assert q.shape == (6, 6) and np.abs(q).max() <= 32767 and (q[:, 0] > 0).all()
-    return q.astype(np.int16)
-
-
-def select(ch, mode):
-    cmd, c12, nsec = MODES[mode]
-    if c12 is not None:
-        ch.load_coeffs_q7(c12)
-    sos = None if nsec is None else wide_sections()[:nsec]
-    if sos is not None:
-        ch.load_sos_q14(sos)
-    ch.set_filter_mode(cmd)
-    return cmd, c12, sos
-
-
-def call(ch, kind, x, out=None):
-    return ch.filter_q15(x, out) if kind == "filter" else ch.process_q15(x, out, out_kind=kind)
-
-
 def assert_packed_equals_int16(torch, ch, d_p, d_i, what):
     for kind in KINDS + ("filter",):
         a, b = call(ch, kind, d_p), call(ch, kind, d_i)
@@ -87,12 +57,12 @@ def assert_packed_equals_int16(torch, ch, d_p, d_i, what):
 
 
 @pytest.mark.parametrize("win_mode", [0, 1])
-@pytest.mark.parametrize("mode", list(MODES))
+@pytest.mark.parametrize("mode", MODES)
 def test_packed_equals_int16_for_every_mode_and_kind(ch, torch_mod, mode, win_mode):
     x, p = batch()
     d_i, d_p = to_device(torch_mod, x[:5]), to_device(torch_mod, p[:5])
+    configure(ch, mode)
     ch.set_window_mode_q15(win_mode)
-    select(ch, mode)
     assert_packed_equals_int16(torch_mod, ch, d_p, d_i, (mode, win_mode))
 
 
@@ -101,7 +71,7 @@ def test_packed_equals_int16_with_a_custom_rom(ch, torch_mod):
     d_i, d_p = to_device(torch_mod, x[:5]), to_device(torch_mod, p[:5])
     ch.set_window_q15(np.random.default_rng(3).integers(-32768, 32768, N).astype(np.int16))
     for mode in ("0xB1", "0x00", "0xA2-six"):
-        select(ch, mode)
+        configure(ch, mode)
         assert_packed_equals_int16(torch_mod, ch, d_p, d_i, mode)
 
 
@@ -111,7 +81,7 @@ def test_sample_order_against_the_integer_model(ch, torch_mod, oracle, mode):
     from fpga_real_time_fft_analyzer_amd.ingest import unpack12
     x, p = batch()
     d_p = to_device(torch_mod, p[:5])
-    cmd, c12, sos = select(ch, mode)
+    _, _, cmd, c12, sos = configure(ch, mode)
     s = unpack12(p[:5])
     assert np.array_equal(s, x[:5])
     ref_iq, ref_t = oracle.chain_q15(s, None, 0, cmd, c12, sos, want_time=True)
@@ -126,7 +96,7 @@ def test_batch_geometry(ch, torch_mod, mode):
     torch = torch_mod
     x, p = batch()
     d_i, d_p = to_device(torch, x), to_device(torch, p)
-    select(ch, mode)
+    configure(ch, mode)
     for kind in ("iq", "marker", "filter"):
         ref = call(ch, kind, d_i).clone()
         for B in (1, 5, 17):
@@ -146,7 +116,7 @@ def test_marker_range_that_cuts_the_spectrum(ch, torch_mod):
     d_i, d_p = to_device(torch, x[:5]), to_device(torch, p[:5])
     ch.set_marker_range(100, 5000)
     for mode in ("0xB1", "0x00"):
-        select(ch, mode)
+        configure(ch, mode)
         rec_p, rec_i = ch.process_q15(d_p, out_kind="marker"), ch.process_q15(d_i, out_kind="marker")
         assert torch.equal(rec_p, rec_i) and rec_i.any(), mode
         _, peak_bin, _ = ch.markers_q15(d_p)
@@ -161,7 +131,7 @@ def test_overlap_profiling_and_graph_capture(ch, torch_mod, mode):
     torch = torch_mod
     x, p = batch()
     d_i, d_p = to_device(torch, x[:5]), to_device(torch, p[:5])
-    select(ch, mode)
+    configure(ch, mode)
     ch.reserve(8)
     ref = ch.process_q15(d_i).clone()
     assert ref.any()

@@ -10,68 +10,33 @@ import pytest
 
 from conftest import N
 from gpu_support import ch, check_overlap_profiling_and_graph_capture, to_device, torch_mod  # noqa: F401 (fixtures)
-from q15_mirrors import bits as _bits, decode as _decode, trace_expect as _expect, wide_sections
+from q15_cases import SETUP_OF_MODE, configure, extreme_frames, records_equal, uniform
+from q15_mirrors import bits as _bits, decode as _decode, trace_expect as _expect
 
 pytestmark = pytest.mark.gpu
 
 WIDTHS = (2, 4, 8, 16, 32, 64)
-SA_EINVAL = -1
-GUI_UPLOAD = np.array([0, 1, 0, 64, -67, 19, 64, 127, 64, 64, -85, 40], np.int8)      # gui.py:159-179, 1186-1192 defaults
+FORMS = ("b1_rtl", "b1_hann_u16", "b1_rom_rtl", "b1_rom_hann_u16", "default", "gui_upload", "wide2", "wide6_hann_u16")      # of SETUPS
 
 
 def _check(rec, mag, ip, W, tag=""):
     """a [B,P,2] float32 record tensor against numpy on the decoded frames, by bits"""
-    B = mag.shape[0]
-    assert tuple(rec.shape) == (B, N // W, 2) and str(rec.dtype) == "torch.float32", (tag, W, rec.shape, rec.dtype)
-    r = rec.cpu().numpy()
     peak, power, _ = _expect(mag, ip, W)
-    bad = np.nonzero(_bits(r[..., 0]) != _bits(peak))
-    assert bad[0].size == 0, (tag, W, "peak", bad[0][:5], bad[1][:5], r[..., 0][bad][:5], peak[bad][:5])
-    bad = np.nonzero(_bits(r[..., 1]) != _bits(power))
-    assert bad[0].size == 0, (tag, W, "power", bad[0][:5], bad[1][:5], r[..., 1][bad][:5], power[bad][:5])
+    records_equal(rec, peak, power, (mag.shape[0], N // W, 2), (tag, W))
 
 
-# form -> (filter byte, 12-byte upload, Q2.14 sections, window mode, custom ROM)
-FORMS = {
-    "b1_rtl": (0xB1, None, 0, 0, False),
-    "b1_hann_u16": (0xB1, None, 0, 1, False),
-    "b1_rom_rtl": (0xB1, None, 0, 0, True),
-    "b1_rom_hann_u16": (0xB1, None, 0, 1, True),
-    "default": (0x00, None, 0, 0, False),
-    "gui_upload": (0xA1, GUI_UPLOAD, 0, 0, False),
-    "wide2": (0xA2, None, 2, 0, False),
-    "wide6_hann_u16": (0xA2, None, 6, 1, False),
-}
-
-
-def _configure(ch, rng, form):
-    cmd, c12, nsec, wm, custom_rom = FORMS[form]
-    rom = rng.integers(-32768, 32768, size=N).astype(np.int16) if custom_rom else None
-    if rom is not None:
-        ch.set_window_q15(rom)
-    ch.set_window_mode_q15(wm)
-    if c12 is not None:
-        ch.load_coeffs_q7(c12)
-    sos14 = wide_sections()[:nsec] if nsec else None
-    if sos14 is not None:
-        ch.load_sos_q14(sos14)
-    ch.set_filter_mode(cmd)
-    return rom, wm, cmd, c12, sos14                          # oracle.chain_q15's arguments after x
-
-
-@pytest.mark.parametrize("form", list(FORMS))
+@pytest.mark.parametrize("form", FORMS)
 def test_records_equal_numpy_on_the_oracles_frames(ch, torch_mod, oracle, form):
     """All six widths in filter modes 0xB1 (both window modes, default and custom ROM), 0x00, 0xA1 with the GUI upload and
     0xA2 with 2 and 6 sections; B = 1, 7 and 33; 12-bit and full-scale samples; int16 input and, for the 12-bit samples,
     the packed form of the same samples.  From B = 7 on, frame 1 is all zero: its records have all bits zero."""
     from fpga_real_time_fft_analyzer_amd import frames
     from fpga_real_time_fft_analyzer_amd.ingest import pack12
-    rng = np.random.default_rng(1100 + list(FORMS).index(form))
-    args = _configure(ch, rng, form)
+    rng = np.random.default_rng(1100 + FORMS.index(form))
+    args = configure(ch, form, rng)
     for B in (1, 7, 33):
         for full in (False, True):
-            lo, hi = (-32768, 32768) if full else (-2048, 2048)
-            x = rng.integers(lo, hi, size=(B, N)).astype(np.int16)
+            x = uniform(rng, (B, N), full)
             if B >= 7:
                 x[1] = 0
             ref = oracle.chain_q15(x, *args)
@@ -178,25 +143,14 @@ def test_rounding_is_exercised(ch, torch_mod, oracle):
         _check(ch.traces_q15(xd, bucket=W), mag, ip, W, "two tones")
 
 
-def _extreme_frames():
-    """the frames of tests/test_gpu_q15.py::test_extreme_inputs, and an all-zero frame"""
-    x = np.zeros((5, N), np.int16)
-    x[0] = 32767
-    x[1] = -32768
-    x[2, ::2] = 32767
-    x[2, 1::2] = -32768
-    x[3, 0] = -32768
-    return x
-
-
 def test_extreme_frames(ch, torch_mod, oracle):
     """Constant +32767, constant -32768, alternating extremes, a lone -32768 impulse and all zero: in modes 0xB1 and 0x00
     under the default ROM, and through a saturating section in mode 0xA2 under a constant ROM (b0 = 32767 in Q2.14: the
     constant frames leave the cascade at the rails), where the oracle's frames hold a component of -32768 -- asserted, so
     the 2^30 square cannot go missing.  The zero frame's records have all bits zero."""
-    x = _extreme_frames()
+    x = extreme_frames(zero_frame=True)
     xd = to_device(torch_mod, x)
-    sat = np.array([[32767, 0, 0, 16384, 0, 0]], np.int16)
+    sat =np.array([[32767, 0, 0, 16384, 0, 0]], np.int16)
     ch.load_sos_q14(sat)
     reached = 0
     for cmd, rom_v in ((0xB1, None), (0x00, None), (0xA2, -32768), (0xA2, 32767)):
@@ -250,12 +204,9 @@ def test_overlap_profiling_and_graph_capture(ch, torch_mod, oracle, mode):
     cmd = int(mode[:4], 16)
     rng = np.random.default_rng(66)
     x = rng.integers(-2048, 2048, size=(9, N)).astype(np.int16)
-    sos = wide_sections() if cmd == 0xA2 else None
-    if sos is not None:
-        ch.load_sos_q14(sos)
-    ch.set_filter_mode(cmd)
+    args = configure(ch, SETUP_OF_MODE[cmd])
     ch.reserve(9)
-    mag, ip = _decode(oracle.chain_q15(x, None, 0, cmd, None, sos))
+    mag, ip = _decode(oracle.chain_q15(x, *args))
     xd = to_device(torch, pack12(x) if mode.endswith("p12") else x)
     for W in (16, 64):
         ref = ch.traces_q15(xd, bucket=W).clone()
@@ -270,7 +221,7 @@ def test_refusals_leave_the_handle_usable(ch, torch_mod, oracle):
     SA_EINVAL; the profiling ring shows no launch for them; a good call afterwards is correct.  sa_process_f32 refuses
     kind 17.  The wrapper refuses a wrong `out`."""
     from fpga_real_time_fft_analyzer_amd import abi
-    from fpga_real_time_fft_analyzer_amd.abi import SpecanError
+    from fpga_real_time_fft_analyzer_amd.abi import SA_EINVAL, SA_ESHAPE, SpecanError
     from fpga_real_time_fft_analyzer_amd.ingest import pack12
     torch = torch_mod
     rng = np.random.default_rng(13)
@@ -308,7 +259,7 @@ def test_refusals_leave_the_handle_usable(ch, torch_mod, oracle):
                     torch.empty((4, N // 8, 2), dtype=torch.float32, device="cuda")):
         with pytest.raises(SpecanError) as e:
             ch.traces_q15(xd, bucket=W, out=bad_out)
-        assert e.value.code == -2
+        assert e.value.code == SA_ESHAPE
     _check(ch.traces_q15(xd, bucket=W), mag, ip, W, "after wrapper refusals")
     e = torch.empty((0, N), dtype=torch.int16, device="cuda")
     assert ch.traces_q15(e, bucket=64).shape == (0, N // 64, 2)

@@ -12,62 +12,25 @@ import pytest
 
 from conftest import N
 from gpu_support import ch, check_overlap_profiling_and_graph_capture, to_device, torch_mod  # noqa: F401 (fixtures)
-from q15_mirrors import bits as _bits, decode as _decode, trace_expect as _expect, wide_sections
+from fpga_real_time_fft_analyzer_amd.abi import SA_EINVAL, SA_ESHAPE, SA_ESTATE
+from q15_cases import SETUP_OF_MODE, SETUPS, configure, handle_iq as _iq, records_equal, uniform
+from q15_mirrors import bits as _bits, decode as _decode, trace_expect as _expect
 
 pytestmark = pytest.mark.gpu
 
 WIDTHS = (2, 4, 8, 16, 32, 64)
-SA_EINVAL, SA_ESHAPE, SA_ESTATE = -1, -2, -4
-GUI_UPLOAD = np.array([0, 1, 0, 64, -67, 19, 64, 127, 64, 64, -85, 40], np.int8)      # gui.py:159-179, 1186-1192 defaults
 BAD_WORDS = (0x80, 0x81, 0x86, 0x88, 0x8F, 0xC9)
-
-
-def _iq(ch, xd):
-    """the reference frames: the handle's own IQ call on the same input, on the host"""
-    return ch.process_q15(xd, out_kind="iq").cpu().numpy()
+FORMS = ("b1_rtl", "b1_rom_hann_u16", "default", "gui_upload", "wide6")       # of q15_cases.SETUPS
+SHAPES = ((2, 2), (2, 6), (4, 8), (8, 24))                   # (A, B): every B is a prefix of one 24-frame batch
 
 
 def _check(rec, mag, ip, W, A, tag=""):
     """a [B/A,P,2] float32 record tensor against numpy on the decoded frames, by bits"""
-    B = mag.shape[0]
-    assert tuple(rec.shape) == (B // A, N // W, 2) and str(rec.dtype) == "torch.float32", (tag, W, A, rec.shape, rec.dtype)
-    r = rec.cpu().numpy()
     peak, power, _ = _expect(mag, ip, W, A)
-    bad = np.nonzero(_bits(r[..., 0]) != _bits(peak))
-    assert bad[0].size == 0, (tag, W, A, "peak", bad[0][:5], bad[1][:5], r[..., 0][bad][:5], peak[bad][:5])
-    bad = np.nonzero(_bits(r[..., 1]) != _bits(power))
-    assert bad[0].size == 0, (tag, W, A, "power", bad[0][:5], bad[1][:5], r[..., 1][bad][:5], power[bad][:5])
+    records_equal(rec, peak, power, (mag.shape[0] // A, N // W, 2), (tag, W, A))
 
 
-# form -> (filter byte, 12-byte upload, Q2.14 sections, window mode, custom ROM)
-FORMS = {
-    "b1_rtl": (0xB1, None, 0, 0, False),
-    "b1_rom_hann_u16": (0xB1, None, 0, 1, True),
-    "default": (0x00, None, 0, 0, False),
-    "gui_upload": (0xA1, GUI_UPLOAD, 0, 0, False),
-    "wide6": (0xA2, None, 6, 0, False),
-}
-
-
-def _configure(ch, rng, form):
-    cmd, c12, nsec, wm, custom_rom = FORMS[form]
-    rom = rng.integers(-32768, 32768, size=N).astype(np.int16) if custom_rom else None
-    if rom is not None:
-        ch.set_window_q15(rom)
-    ch.set_window_mode_q15(wm)
-    if c12 is not None:
-        ch.load_coeffs_q7(c12)
-    sos14 = wide_sections()[:nsec] if nsec else None
-    if sos14 is not None:
-        ch.load_sos_q14(sos14)
-    ch.set_filter_mode(cmd)
-    return rom, wm, cmd, c12, sos14                          # oracle.chain_q15's arguments after x
-
-
-SHAPES = ((2, 2), (2, 6), (4, 8), (8, 24))                   # (A, B): every B is a prefix of one 24-frame batch
-
-
-@pytest.mark.parametrize("form", list(FORMS))
+@pytest.mark.parametrize("form", FORMS)
 def test_records_equal_numpy(ch, torch_mod, oracle, form):
     """Modes 0xB1 (RTL window; a custom ROM in the 16-bit Hann mode), 0x00, 0xA1 with the GUI upload and 0xA2 with six
     sections; (A, B) = (2,2), (2,6), (4,8), (8,24) at all six widths -- the first B frames of one 24-frame batch whose frames 2
@@ -76,11 +39,10 @@ def test_records_equal_numpy(ch, torch_mod, oracle, form):
     and 64.  The handle's IQ frames, the reference, are the oracle's for the 24-frame batches."""
     from fpga_real_time_fft_analyzer_amd.ingest import pack12
     torch = torch_mod
-    rng = np.random.default_rng(1300 + list(FORMS).index(form))
-    args = _configure(ch, rng, form)
+    rng = np.random.default_rng(1300 + FORMS.index(form))
+    args = configure(ch, form, rng)
     for full in (False, True):
-        lo, hi = (-32768, 32768) if full else (-2048, 2048)
-        x = rng.integers(lo, hi, size=(24, N)).astype(np.int16)
+        x = uniform(rng, (24, N), full)
         x[2:4] = 0
         xd = to_device(torch, x)
         pd = None if full else to_device(torch, pack12(x))
@@ -98,11 +60,10 @@ def test_records_equal_numpy(ch, torch_mod, oracle, form):
                 if (A, B) == (2, 6):
                     assert not rec[1].view(torch.int32).any().item(), tag
                     assert rec[0].view(torch.int32).any().item() and rec[2].view(torch.int32).any().item(), tag
-    if FORMS[form][0] != 0xB1 or FORMS[form][4]:
+    if SETUPS[form].cmd != 0xB1 or SETUPS[form].custom_rom:
         return
     for full in (False, True):
-        lo, hi = (-32768, 32768) if full else (-2048, 2048)
-        x = rng.integers(lo, hi, size=(256, N)).astype(np.int16)
+        x = uniform(rng, (256, N), full)
         xd = to_device(torch, x)
         pd = None if full else to_device(torch, pack12(x))
         mag, ip = _decode(_iq(ch, xd))
@@ -230,9 +191,7 @@ def test_overlap_profiling_and_graph_capture(ch, torch_mod, cmd):
     torch = torch_mod
     rng = np.random.default_rng(67)
     x = rng.integers(-2048, 2048, size=(8, N)).astype(np.int16)
-    if cmd == 0xA2:
-        ch.load_sos_q14(wide_sections())
-    ch.set_filter_mode(cmd)
+    configure(ch, SETUP_OF_MODE[cmd])
     xd = to_device(torch, x)
     mag, ip = _decode(_iq(ch, xd))
     for W, A in ((16, 4), (64, 2)):
