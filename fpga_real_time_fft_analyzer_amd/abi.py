@@ -1,5 +1,6 @@
 """ctypes binding of ``libspecan_hip.so`` (the C ABI declared in ``include/specan.h`` and ``include/specan_ext.h``) and of
-``libspecan_fold.so`` (``include/specan_fold.h``) and ``libspecan_peaks.so`` (``include/specan_peaks.h``).
+``libspecan_fold.so`` (``include/specan_fold.h``), ``libspecan_peaks.so`` (``include/specan_peaks.h``) and
+``libspecan_rank.so`` (``include/specan_rank.h``).
 
 This is the only place the shared libraries are loaded.  There is no CPU fallback: if the
 library is missing the import of any compute entry point raises, and creating a handle
@@ -15,6 +16,7 @@ _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_PKG, "libspecan_hip.so")
 FOLD_LIB_PATH = os.path.join(_PKG, "libspecan_fold.so")      # include/specan_fold.h: built by the same make
 PEAKS_LIB_PATH = os.path.join(_PKG, "libspecan_peaks.so")    # include/specan_peaks.h: built by the same make
+RANK_LIB_PATH = os.path.join(_PKG, "libspecan_rank.so")      # include/specan_rank.h: built by the same make
 CSRC = os.path.join(_PKG, "csrc")
 
 # error codes / constants (include/specan.h)
@@ -79,8 +81,8 @@ class SpecanError(RuntimeError):
 
 
 def build(verbose: bool = False) -> str:
-    """Compile the HIP extension in-tree for gfx950 (hipcc cross-compiles without a GPU): the three libraries, LIB_PATH,
-    FOLD_LIB_PATH and PEAKS_LIB_PATH, are the Makefile's first target."""
+    """Compile the HIP extension in-tree for gfx950 (hipcc cross-compiles without a GPU): the four libraries, LIB_PATH,
+    FOLD_LIB_PATH, PEAKS_LIB_PATH and RANK_LIB_PATH, are the Makefile's first target."""
     cmd = ["make", "-j4", "-C", CSRC]
     if not verbose:
         cmd.insert(1, "-s")
@@ -179,9 +181,23 @@ PEAKS_SIGNATURES = {
     "sa_peaks_last_error": (C.c_char_p, []),
 }
 
+# the entry points of include/specan_rank.h: libspecan_rank.so, the fourth product library, again without a handle (the keys
+# at given ranks of the sorted bins of each row of 16384 points), bound by rank_lib() and held name for name against that
+# header (tests/test_f32_rank_cpu.py); no name is in the four tables above
+SA_RANK_VERSION = 1
+SA_RANK_Q_MAX = 8
+SA_RANK_IN_MAG, SA_RANK_IN_POINT_PEAK, SA_RANK_IN_POINT_POWER = 0, 1, 2
+RANK_SIGNATURES = {
+    "sa_rank_version": (_INT, []),
+    "sa_rank_f32": (_INT, [C.c_void_p, _INT, C.c_void_p, _INT, _INT, _P(C.c_int32), _INT, _INT, C.c_void_p]),
+    "sa_rank_check": (_INT, [_INT, C.c_uint64, C.c_uint64, _INT, _INT, _P(C.c_int32), _INT, _INT]),
+    "sa_rank_last_error": (C.c_char_p, []),
+}
+
 _lib = None
 _fold_lib = None
 _peaks_lib = None
+_rank_lib = None
 
 
 def _load(path: str, tables: tuple) -> C.CDLL:
@@ -228,3 +244,11 @@ def peaks_lib() -> C.CDLL:
     if _peaks_lib is None:
         _peaks_lib = _load(PEAKS_LIB_PATH, (PEAKS_SIGNATURES,))
     return _peaks_lib
+
+
+def rank_lib() -> C.CDLL:
+    """Load libspecan_rank.so (include/specan_rank.h), after torch as lib() does; raise loudly when it has not been built."""
+    global _rank_lib
+    if _rank_lib is None:
+        _rank_lib = _load(RANK_LIB_PATH, (RANK_SIGNATURES,))
+    return _rank_lib

@@ -132,6 +132,8 @@ Q15_FOLD_CHAIN = _Chain(_SPECTRA_OUT, {torch.int16: _form((SA_N, 2), _SPECTRA_OU
 FOLD_GROUPS, FOLD_BUCKETS = frames.FOLD_GROUPS, frames.FOLD_BUCKETS         # 1 .. 128 and 1 .. 64: the mirror's, defined once
 # find_peaks(field=...) -> the `field` of include/specan_peaks.h: plain magnitudes, or one float of (peak, power) records
 _PEAK_FIELDS = {None: abi.SA_PEAKS_IN_MAG, "peak": abi.SA_PEAKS_IN_POINT_PEAK, "power": abi.SA_PEAKS_IN_POINT_POWER}
+# order_stats(field=...) -> the `field` of include/specan_rank.h: the same three layouts
+_RANK_FIELDS = {None: abi.SA_RANK_IN_MAG, "peak": abi.SA_RANK_IN_POINT_PEAK, "power": abi.SA_RANK_IN_POINT_POWER}
 
 
 def output_spec(chain: _Chain, out_kind: Optional[str], B: int) -> tuple:
@@ -762,6 +764,114 @@ class SpectrumChain:
             return self.find_peaks(rec, k, threshold, lo, hi, min_sep, field="power", out=out)
         out = self._peaks_out(B, int(k), out)
         return self.find_peaks(self._mag_full_in_work(x, B, scale, work), k, threshold, lo, hi, min_sep, out=out)
+
+    @staticmethod
+    def _rank_args(ranks, lo, hi, field) -> tuple:
+        """The one validation of the arguments of the order statistics: ``(field code of include/specan_rank.h, the ranks as a
+        tuple of ints)``, or SA_EINVAL."""
+        for name, v in (("lo", lo), ("hi", hi)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise SpecanError(abi.SA_EINVAL, f"{name} must be an int")
+        if not 0 <= int(lo) < int(hi) <= SA_N:
+            raise SpecanError(abi.SA_EINVAL, f"the range must be 0 <= lo < hi <= {SA_N}")
+        if isinstance(ranks, (str, bytes)) or not hasattr(ranks, "__len__") or not 1 <= len(ranks) <= abi.SA_RANK_Q_MAX:
+            raise SpecanError(abi.SA_EINVAL, f"ranks must be a sequence of 1..{abi.SA_RANK_Q_MAX} ints")
+        m = int(hi) - int(lo)
+        for v in ranks:
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) < m:
+                raise SpecanError(abi.SA_EINVAL, f"a rank must be an int in 0..{m - 1}")
+        if not (field is None or isinstance(field, str)) or field not in _RANK_FIELDS:
+            raise SpecanError(abi.SA_EINVAL, "field must be None, 'peak' or 'power'")
+        return _RANK_FIELDS[field], tuple(int(v) for v in ranks)
+
+    @staticmethod
+    def _quantile_ranks(q, lo, hi) -> tuple:
+        """``q``, a number in 0..1 or a sequence of 1..8 of them, as the ranks of those lower quantiles among the hi - lo bins
+        (frames.rank_of_quantile), or SA_EINVAL; ``lo`` and ``hi`` have been checked."""
+        qs = q if hasattr(q, "__len__") and not isinstance(q, (str, bytes)) else (q,)
+        if not 1 <= len(qs) <= abi.SA_RANK_Q_MAX:
+            raise SpecanError(abi.SA_EINVAL, f"q must be a number or a sequence of 1..{abi.SA_RANK_Q_MAX} numbers")
+        try:
+            return tuple(frames.rank_of_quantile(v, int(hi) - int(lo)) for v in qs)
+        except ValueError as e:
+            raise SpecanError(abi.SA_EINVAL, str(e)) from None
+
+    def _rank_out(self, R: int, q: int, out: Optional[torch.Tensor]) -> torch.Tensor:
+        """``out`` of the order statistics of ``R`` rows, allocated when None: SA_ESHAPE where it is not the contiguous float32
+        [R, q] tensor on the handle's device."""
+        shape = (R, q)
+        if out is None:
+            return torch.empty(shape, dtype=torch.float32, device=self.device)
+        if (not isinstance(out, torch.Tensor) or tuple(out.shape) != shape or out.dtype != torch.float32
+                or out.device != self.device or not out.is_contiguous()):
+            raise SpecanError(abi.SA_ESHAPE, f"out must be a contiguous torch.float32 tensor of shape {shape}")
+        return out
+
+    def order_stats(self, t: torch.Tensor, ranks: Sequence[int], lo: int = 0, hi: int = SA_N, field: Optional[str] = None,
+                    out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Order statistics of each row of ``t`` (include/specan_rank.h, sa_rank_f32): float32 [R, q], ``[r, j]`` the value at
+        rank ``ranks[j]`` of the ascending sort of the bins ``[lo, hi)`` of row r.  Rank 0 is the minimum of the range, rank
+        ``hi - lo - 1`` its maximum; frames.rank_of_quantile gives the rank of a quantile.  ``t`` is a float32 [R,16384]
+        device tensor -- what ``process_f32(out_kind='mag_full')`` or ``process_q15(out_kind='mag')`` wrote -- or, with
+        ``field='peak'`` or ``field='power'``, float32 [R,16384,2], the records of :meth:`fold_mag_f32` at bucket 1,
+        :meth:`spectra_f32` or :meth:`spectra_q15`, of which that float is the point.
+
+        A point's key is its bits with the sign cleared, as an integer: the float order of the chains' non-negative values; a
+        NaN ranks above +inf, -0.0 reads as +0.0, no denormal is flushed; the result is those bits.  frames.ranks_of_rows is
+        the numpy mirror, bit for bit.  The maximum over a range is peak_mag of :meth:`markers` / :meth:`markers_q15` with that
+        marker range on the same frames.  The cost is linear in the number of ranks.
+
+        ``ranks`` is a sequence of 1..8 ints, each ``0 <= rank < hi - lo``, in any order, repeats allowed;
+        ``0 <= lo < hi <= 16384``; ints only (a bool or a float is SA_EINVAL); a wrong dtype is SA_EINVAL and a wrong shape
+        SA_ESHAPE, all before any device call.  One launch on the current stream of the handle's device -- the ranks travel
+        in the launch's arguments -- no handle state, no workspace: it captures into a graph at any time.  Where ``t`` is the
+        result of a call made in overlap mode, call :meth:`flush` first.  Pointer contract (checked by the C entry point,
+        SA_EINVAL): ``t`` is 16-byte aligned, and the bytes read and the R * q * 4 bytes written are disjoint; buffers that
+        merely touch are fine."""
+        code, ranks = self._rank_args(ranks, lo, hi, field)
+        R = self._check_in(t, torch.float32, (SA_N, 2) if code else SA_N)
+        out = self._rank_out(R, len(ranks), out)
+        L = abi.rank_lib()
+        with torch.cuda.device(self.device):         # the C call launches on the calling thread's current device
+            rc = L.sa_rank_f32(t.data_ptr(), code, out.data_ptr(), R, len(ranks), (C.c_int32 * len(ranks))(*ranks), int(lo),
+                               int(hi), self._stream())
+        if rc != abi.SA_OK:
+            raise SpecanError(rc, L.sa_rank_last_error().decode())
+        return out
+
+    def noise_floor_f32(self, x: torch.Tensor, q=0.5, lo: int = 0, hi: int = SA_N, group: Optional[int] = None,
+                        scale: float = 1.0 / 2048.0, work: Optional[torch.Tensor] = None,
+                        out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The noise floor of the float chain's spectra, without the spectra leaving the device: float32 [R, len(q)], the lower
+        quantiles ``q`` (a number in 0..1, which gives [R, 1], or a sequence of 1..8 of them; 0.5 is the lower median) of the
+        bins ``[lo, hi)`` of every row, each the order statistic of rank ``frames.rank_of_quantile(q, hi - lo)``.  ``x`` is
+        float32, int16 or packed uint8 exactly as for :meth:`process_f32`; every filter mode and both precisions apply.
+
+        Without ``group`` (R = B) the call is ``process_f32(x, out_kind='mag_full', scale=scale)`` into the workspace of
+        :meth:`spectra_f32` followed by :meth:`order_stats`: the floor of every frame's magnitudes.  With ``group=A`` (2, 4,
+        ..., 128; R = B // A) it is ``spectra_f32(x, group=A, scale=scale, work=work)`` followed by ``order_stats(...,
+        field='power')``: the floor of the summed power of every A consecutive frames, the Welch estimate times A.
+
+        The workspace is ``work`` or the cached tensor, as for :meth:`spectra_f32`, and in overlap mode the call joins every
+        outstanding call of the handle on the device (as :meth:`flush` does) before the selection: the result is valid on
+        the current stream when the call returns, and the call lends nothing.  ``q``, the range and ``out`` are refused as by
+        :meth:`order_stats`, ``group`` and a B that is no multiple of it as by :meth:`spectra_f32`, all before anything is
+        launched, and so is a wrong ``work``."""
+        self._rank_args((0,), lo, hi, None)
+        ranks = self._quantile_ranks(q, lo, hi)
+        if group is not None:
+            self._log2_fold(group, 1)
+        forms = FLOAT_CHAIN.inputs
+        dtype = x.dtype if isinstance(x, torch.Tensor) and x.dtype in forms else next(iter(forms))
+        B = self._check_in(x, dtype, forms[dtype][0])
+        if group is not None:
+            if B % int(group):
+                raise SpecanError(abi.SA_ESHAPE, f"the batch ({B} frames) must be a multiple of {int(group)}")
+            out = self._rank_out(B // int(group), len(ranks), out)   # refused here, before the chain is launched
+            rec = self.spectra_f32(x, group, 1, scale=scale, work=work)
+            return self.order_stats(rec, ranks, lo, hi, field="power", out=out)
+        out = self._rank_out(B, len(ranks), out)
+        return self.order_stats(self._mag_full_in_work(x, B, scale, work), ranks, lo, hi, out=out)
 
     def filter_q15(self, x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Window (+ integer IIR) only: the FFT input stream, [B,16384] int16.  ``x`` is [B,16384] int16 or the same

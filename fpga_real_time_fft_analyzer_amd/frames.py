@@ -6,6 +6,8 @@ scripts/fft_analyzer_gui.py:250-270).  UDP transport = 64 datagrams per frame, p
 """
 from __future__ import annotations
 
+import math
+
 import numpy as np
 
 FRAME_SIZE_BYTES = 65536
@@ -182,6 +184,60 @@ def peaks_of_rows(points, k: int = 8, threshold: float = 0.0, lo: int = 0, hi: i
         mag[r, :len(taken)] = u[r, taken]
         bins[r, :len(taken)] = taken
     return mag.view(np.float32), bins, cand.sum(axis=1).astype(np.int32)
+
+
+RANK_Q_MAX = 8
+RANK_FIELDS = {None: None, "peak": 0, "power": 1}      # field -> the float of a (peak, power) record that is the point
+
+
+def ranks_of_rows(points, ranks, lo: int = 0, hi: int = FFT_SIZE, field=None):
+    """The order statistics of float32 ``points`` [R,16384] -- or, with ``field`` 'peak' or 'power', of that float of the
+    records [R,16384,2] -- over the bins [lo, hi): float32 [R, q], one value per row and entry of ``ranks``.  The numpy mirror
+    of sa_rank_f32 (include/specan_rank.h):
+
+    - key: the float's bits with the sign cleared, as a uint32 -- +inf above every finite value, a NaN above +inf, -0.0 as
+      +0.0, denormals kept;
+    - ``s = np.sort`` of the m = hi - lo keys of the slice, ascending; the result is ``s[ranks[j]]`` as float bits: rank 0 is
+      the minimum of the range, rank m - 1 its maximum.
+
+    ``ranks`` is a sequence of 1..8 ints, each ``0 <= rank < hi - lo``, in any order, repeats allowed;
+    ``0 <= lo < hi <= 16384``; the integers are ints (no bool, no float): ValueError otherwise, and on a wrong dtype or
+    shape."""
+    for name, v in (("lo", lo), ("hi", hi)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f"{name} must be an int")
+    lo, hi = int(lo), int(hi)
+    if not 0 <= lo < hi <= FFT_SIZE:
+        raise ValueError("the range must be 0 <= lo < hi <= 16384")
+    if isinstance(ranks, (str, bytes)) or not hasattr(ranks, "__len__") or not 1 <= len(ranks) <= RANK_Q_MAX:
+        raise ValueError(f"ranks must be a sequence of 1..{RANK_Q_MAX} ints")
+    for v in ranks:
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) < hi - lo:
+            raise ValueError(f"a rank must be an int in 0..{hi - lo - 1}")
+    if not (field is None or isinstance(field, str)) or field not in RANK_FIELDS:
+        raise ValueError("field must be None, 'peak' or 'power'")
+    points = np.ascontiguousarray(points)
+    shape = (FFT_SIZE,) if field is None else (FFT_SIZE, 2)
+    if points.dtype != np.float32 or points.ndim != 1 + len(shape) or points.shape[1:] != shape:
+        raise ValueError(f"points must be float32 [R, {', '.join(map(str, shape))}]")
+    if field is not None:
+        points = np.ascontiguousarray(points[..., RANK_FIELDS[field]])
+    u = points.view(np.uint32)[:, lo:hi] & np.uint32(0x7FFFFFFF)
+    s = np.sort(u, axis=1)
+    return np.ascontiguousarray(s[:, [int(v) for v in ranks]]).view(np.float32)
+
+
+def rank_of_quantile(q: float, m: int) -> int:
+    """The rank of the "lower" quantile ``q`` (0 <= q <= 1) among ``m`` >= 1 sorted values: ``math.floor(q * (m - 1))``,
+    the product taken in Python's double arithmetic.  0.0 is the minimum (rank 0), 1.0 the maximum (rank m - 1), 0.5 the
+    lower median.  The double product decides, not the decimal one: 0.29 * 100 is 28.999999999999996 in doubles, so
+    ``rank_of_quantile(0.29, 101)`` is 28.  ValueError on a q that is no number in [0, 1] (a NaN included) or an m that is no
+    int >= 1."""
+    if isinstance(m, bool) or not isinstance(m, (int, np.integer)) or int(m) < 1:
+        raise ValueError("m must be an int >= 1")
+    if isinstance(q, bool) or not isinstance(q, (int, float, np.integer, np.floating)) or not 0.0 <= float(q) <= 1.0:
+        raise ValueError("q must be a number in 0..1")
+    return math.floor(float(q) * (int(m) - 1))
 
 
 def decode_iq_components(frame_bytes: bytes):

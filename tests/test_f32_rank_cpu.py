@@ -1,0 +1,406 @@
+"""CPU: the order statistics (include/specan_rank.h: sa_rank_f32 of libspecan_rank.so; SpectrumChain.order_stats and
+noise_floor_f32) as far as no GPU is needed: the numpy mirror frames.ranks_of_rows against probes whose expected bits are
+worked out by hand below, never from the code under test; frames.rank_of_quantile by hand; the header against the built
+library and the binding table abi.RANK_SIGNATURES; the kernels the four libraries hold; the refusals through sa_rank_check
+with made-up addresses (every expected answer follows from the words of the header); the same arithmetic in a stand-alone
+program under the host sanitizers; and the compiler's resource remarks."""
+import ctypes
+import itertools
+import os
+import re
+
+import numpy as np
+import pytest
+
+from conftest import N
+from kernel_inventory import TABLE, inventory, unit_text
+from native import CSRC, INCLUDE, compiles_as_c, declared, exported, needed, remarks, standalone_checks, undefined
+
+SA_OK, SA_EINVAL, SA_ESHAPE = 0, -1, -2
+BASE = (1 << 47) - (1 << 36)
+FAR = BASE + (1 << 40)
+HEADER = os.path.join(INCLUDE, "specan_rank.h")
+NAMES = ["sa_rank_check", "sa_rank_f32", "sa_rank_last_error", "sa_rank_version"]
+ONE, ONE_UP = 0x3F800000, 0x3F800001                   # 1.0f and the next float above it
+# the planted specials (bin, value) and the six largest keys of the otherwise zero row they stand in, ascending: the two
+# zeros (-0.0 is one of them), the denormal 2^-149 = 1e-45f (bits 1), 2.0, |-3.0|, +inf, the NaN
+SPECIALS = ((11, np.nan), (222, np.inf), (3333, -3.0), (4444, 2.0), (5555, 1e-45), (6666, -0.0))
+SPECIALS_TOP6 = [0x0, 0x1, 0x40000000, 0x40400000, 0x7F800000, 0x7FC00000]
+
+
+def bits(x):
+    return np.ascontiguousarray(x, np.float32).view(np.uint32)
+
+
+def key(v):
+    """the key of one value: its float32 bits with the sign cleared"""
+    return int(bits(np.float32(v)).ravel()[0]) & 0x7FFFFFFF
+
+
+def planted(pairs, fill=0.0, rows=1):
+    """rows equal rows of `fill` with the (bin, value) pairs planted"""
+    r = np.full((rows, N), fill, np.float32)
+    for b, v in pairs:
+        r[:, b] = v
+    return r
+
+
+def stats(points, ranks, **kw):
+    """the mirror's result for row 0 as a list of keys"""
+    from fpga_real_time_fft_analyzer_amd import frames
+    got = frames.ranks_of_rows(points, ranks, **kw)
+    assert got.dtype == np.float32 and got.shape == (points.shape[0], len(ranks)) and got.flags["C_CONTIGUOUS"]
+    return [int(v) for v in bits(got)[0]]
+
+
+# ------------------------------------------------------------------------------------------------------------- the mirror
+def test_last_bit_probe():
+    """16383 bins of 1.0 and one of nextafter(1, 2): the maximum alone is the larger float, one bit above the rest."""
+    up = np.nextafter(np.float32(1), np.float32(2), dtype=np.float32)
+    assert key(up) == ONE_UP and key(1) == ONE
+    for at in (0, 7777, N - 1):
+        assert stats(planted([(at, up)], fill=1.0), [N - 1, N - 2, 0]) == [ONE_UP, ONE, ONE]
+
+
+def test_specials_probe():
+    """NaN above +inf above every finite value, -3.0 as 3.0, the denormal kept above zero, -0.0 as zero: 16378 zeros (one of
+    them the -0.0), then bits 1, 2.0, 3.0, +inf, NaN.  The answers lie on both sides of bit 30 (0x40000000 is 2.0) and differ
+    in bit 0 alone (0x0 and 0x1)."""
+    pts = planted(SPECIALS)
+    assert bits(pts)[0, 5555] == 1 and bits(pts)[0, 6666] == 0x80000000 and bits(pts)[0, 3333] == 0xC0400000
+    assert stats(pts, list(range(N - 6, N))) == SPECIALS_TOP6
+    assert stats(pts, [0, N - 7, N - 6]) == [0, 0, 0]             # the -0.0 and the zeros below the denormal
+    # a negative NaN: the sign cleared, the payload kept
+    pts = np.zeros((1, N), np.float32)
+    pts.view(np.uint32)[0, 77] = 0xFFC00123
+    assert stats(pts, [N - 1, N - 2]) == [0x7FC00123, 0]
+
+
+def test_narrow_ranges():
+    from fpga_real_time_fft_analyzer_amd import frames
+    pts = planted([(500, 5.0), (501, 5.0), (502, -7.0)])
+    five, seven = key(5), key(7)
+    assert stats(pts, [0], lo=500, hi=501) == [five]              # width 1: the bin itself
+    assert stats(pts, [0], lo=502, hi=503) == [seven]
+    assert stats(pts, [0], lo=499, hi=500) == [0]
+    assert stats(pts, [0, 1], lo=500, hi=502) == [five, five]     # width 2, equal keys
+    assert stats(pts, [1, 0], lo=501, hi=503) == [seven, five]
+    assert stats(pts, [0, 1], lo=499, hi=501) == [0, five]
+    assert stats(planted([(0, 2.0)]), [0], lo=0, hi=1) == [0x40000000]
+    assert stats(planted([(N - 1, 2.0)]), [0], lo=N - 1, hi=N) == [0x40000000]
+    with pytest.raises(ValueError):
+        frames.ranks_of_rows(pts, [1], lo=500, hi=501)            # rank 1 of one bin
+
+
+def test_repeated_and_unsorted_ranks():
+    """The row 0, 1, ..., 16383 (every integer up to 2^24 is a float): the key at rank r is the float r."""
+    ramp = np.arange(N, dtype=np.float32)[None, :]
+    ranks = [9000, 3, 9000, N - 1, 0, 3, 12345, 9000]
+    want = [key(r) for r in ranks]
+    assert stats(ramp, ranks) == want
+    assert stats(ramp[:, ::-1], ranks) == want                    # descending: the same sorted keys
+    assert stats(ramp, [10, 0, 10], lo=100, hi=200) == [key(v) for v in (110, 100, 110)]
+
+
+def test_bins_outside_the_range_do_not_exist():
+    rng = np.random.default_rng(1800)
+    pts = np.exp(rng.uniform(-60.0, 60.0, size=(2, N))).astype(np.float32)
+    lo, hi = 1000, 3000
+    ranks = [0, 1, 999, 1998, 1999]
+    before = stats(pts, ranks, lo=lo, hi=hi)
+    for v in (3e38, np.inf, np.nan, 0.0):
+        loud = pts.copy()
+        loud[:, lo - 1] = loud[:, hi] = v
+        assert stats(loud, ranks, lo=lo, hi=hi) == before, v
+    loud = pts.copy()
+    loud[:, lo] = 3e38                                            # inside: the maximum moves
+    assert stats(loud, ranks, lo=lo, hi=hi)[-1] == key(3e38) != before[-1]
+
+
+def test_any_permutation_of_a_row_gives_the_same_output():
+    from fpga_real_time_fft_analyzer_amd import frames
+    rng = np.random.default_rng(1801)
+    pts = np.exp(rng.uniform(-60.0, 60.0, size=(3, N))).astype(np.float32)
+    pts[1] = rng.integers(0, 4, N)                                # massive ties
+    pts[2, ::5] *= -1.0
+    ranks = [0, 1, N // 2, N - 2, N - 1, 4095]
+    want = bits(frames.ranks_of_rows(pts, ranks))
+    for seed in (1, 2):
+        perm = np.random.default_rng(seed).permutation(N)
+        assert np.array_equal(bits(frames.ranks_of_rows(pts[:, perm], ranks)), want)
+    assert np.array_equal(bits(frames.ranks_of_rows(pts[:, ::-1], ranks)), want)
+    # the tied row by counting: n0 zeros, then n1 ones, ...
+    n = [(pts[1] == v).sum() for v in range(4)]
+    edges = np.cumsum(n)
+    for v in range(4):
+        if n[v]:
+            first, last = int(edges[v] - n[v]), int(edges[v] - 1)
+            assert bits(frames.ranks_of_rows(pts[1:2], [first, last]))[0].tolist() == [key(v)] * 2
+
+
+def test_records_and_rows_and_arguments():
+    from fpga_real_time_fft_analyzer_amd import frames
+    rng = np.random.default_rng(1802)
+    pts = np.exp(rng.uniform(-60.0, 60.0, size=(3, N))).astype(np.float32)
+    ranks = [5, 8000, 15899]
+    whole = frames.ranks_of_rows(pts, ranks, 100, 16000)
+    for r in range(3):
+        assert np.array_equal(bits(whole[r:r + 1]), bits(frames.ranks_of_rows(pts[r:r + 1], ranks, 100, 16000)))
+        assert np.array_equal(bits(whole[r]), np.sort(bits(pts[r, 100:16000]))[ranks])       # positive data: keys are the bits
+    ranks = [5, 8000, N - 1]
+    whole = frames.ranks_of_rows(pts, ranks)
+    for r in range(3):
+        assert np.array_equal(bits(whole[r:r + 1]), bits(frames.ranks_of_rows(pts[r:r + 1], ranks)))
+    # records: the named float is the point, the other one is never looked at
+    for field, at in (("peak", 0), ("power", 1)):
+        rec = np.full((3, N, 2), np.nan, np.float32)
+        rec[..., at] = pts
+        assert np.array_equal(bits(frames.ranks_of_rows(rec, ranks, field=field)), bits(whole)), field
+    assert frames.ranks_of_rows(np.zeros((0, N), np.float32), [0, 1]).shape == (0, 2)
+    bad = [dict(ranks=[]), dict(ranks=list(range(9))), dict(ranks=[N]), dict(ranks=[-1]), dict(ranks=[True]), dict(ranks=[1.0]),
+           dict(ranks=3), dict(ranks="12"), dict(ranks=[N - 1], lo=100, hi=16000), dict(ranks=[100], lo=0, hi=100), dict(lo=-1),
+           dict(lo=5, hi=5), dict(hi=N + 1), dict(lo=1.0), dict(hi=True), dict(field="mag"), dict(field=0), dict(field=["peak"])]
+    for kw in bad:
+        with pytest.raises(ValueError):
+            frames.ranks_of_rows(pts, **dict(dict(ranks=[0]), **kw))
+    for wrong in (pts.astype(np.float64), pts[:, :N // 2], pts[0], np.zeros((2, N, 2), np.float32)):
+        with pytest.raises(ValueError):
+            frames.ranks_of_rows(wrong, [0])
+    with pytest.raises(ValueError):
+        frames.ranks_of_rows(pts, [0], field="peak")              # records are [R, 16384, 2]
+    got = frames.ranks_of_rows(pts, (np.int64(3), np.int16(7)), np.int32(0), np.int64(N))
+    assert got.shape == (3, 2)
+    assert np.array_equal(bits(frames.ranks_of_rows(pts, np.array([3, 7]))), bits(got))
+
+
+def test_rank_of_quantile_by_hand():
+    """floor(q (m - 1)): 0.5 * 16383 = 8191.5 -> 8191; 0.5 * 16382 = 8191; 0.25 * 16383 = 4095.75 -> 4095; 0.9 * 99 = 89.1 ->
+    89; and 0.29 * 100, 29 in decimals, is 28.999999999999996 in doubles -> 28."""
+    from fpga_real_time_fft_analyzer_amd import frames
+    for q, m, want in ((0.5, 16384, 8191), (0.5, 16383, 8191), (1.0, 16384, 16383), (0.0, 1, 0), (0.25, 16384, 4095),
+                       (0.9, 100, 89), (0.29, 101, 28), (0.0, 16384, 0), (1.0, 1, 0), (1, 7, 6), (0, 7, 0)):
+        got = frames.rank_of_quantile(q, m)
+        assert got == want and type(got) is int, (q, m, got)
+    assert frames.rank_of_quantile(np.float32(0.5), np.int64(3)) == 1
+    for q, m in ((-0.1, 5), (1.0000001, 5), (float("nan"), 5), ("0.5", 5), (None, 5), (True, 5), (0.5, 0), (0.5, -1), (0.5, 2.0),
+                 (0.5, True)):
+        with pytest.raises(ValueError):
+            frames.rank_of_quantile(q, m)
+
+
+# ------------------------------------------------------------------------------------------------------------ the surface
+@pytest.fixture(scope="module")
+def rank_lib():
+    """libspecan_rank.so, built on demand by the package's one build step (it cross-compiles without a GPU)."""
+    from fpga_real_time_fft_analyzer_amd import abi
+    if not os.path.exists(abi.RANK_LIB_PATH):
+        abi.build()
+    return abi.rank_lib()
+
+
+def _ranks(values):
+    return None if values is None else (ctypes.c_int32 * len(values))(*values)
+
+
+@pytest.fixture(scope="module")
+def check(rank_lib):
+    def call(field=0, a_in=BASE, a_out=FAR, rows=3, q=None, ranks=(0,), lo=0, hi=N):
+        return rank_lib.sa_rank_check(field, a_in, a_out, rows, (len(ranks) if ranks is not None else 1) if q is None else q,
+                                      _ranks(ranks), lo, hi)
+    return call
+
+
+def test_header_library_and_binding_table(rank_lib):
+    """Name for name: declared in specan_rank.h = exported by libspecan_rank.so = bound in abi.RANK_SIGNATURES; nothing is in
+    the other tables or headers, which are what they were."""
+    from fpga_real_time_fft_analyzer_amd import abi
+    assert declared(HEADER) == NAMES
+    assert [n for n in exported(abi.RANK_LIB_PATH) if "sa_" in n] == NAMES
+    assert sorted(abi.RANK_SIGNATURES) == NAMES
+    others = (abi.SIGNATURES, abi.EXT_SIGNATURES, abi.FOLD_SIGNATURES, abi.PEAKS_SIGNATURES)
+    assert not set(NAMES) & set().union(*others)
+    assert [len(t) for t in others] == [45, 5, 4, 4]
+    for other in ("specan.h", "specan_ext.h", "specan_fold.h", "specan_peaks.h"):
+        assert not set(NAMES) & set(declared(os.path.join(INCLUDE, other))), other
+    for name in NAMES:
+        fn, (restype, argtypes) = getattr(rank_lib, name), abi.RANK_SIGNATURES[name]
+        assert fn.argtypes is not None and list(fn.argtypes) == list(argtypes), name
+        assert fn.restype is restype is (ctypes.c_char_p if name == "sa_rank_last_error" else ctypes.c_int), name
+    assert rank_lib.sa_rank_version() == abi.SA_RANK_VERSION == 1 and abi.SA_RANK_Q_MAX == 8
+    text = open(HEADER).read()
+    assert "#define SA_RANK_VERSION 1" in text and "#define SA_RANK_Q_MAX 8" in text
+    assert '#include "specan.h"' in text and "#include \"specan_peaks.h\"" not in text
+    assert (abi.SA_RANK_IN_MAG, abi.SA_RANK_IN_POINT_PEAK, abi.SA_RANK_IN_POINT_POWER) == (0, 1, 2) == \
+        (abi.SA_PEAKS_IN_MAG, abi.SA_PEAKS_IN_POINT_PEAK, abi.SA_PEAKS_IN_POINT_POWER)
+    assert rank_lib.sa_rank_last_error() == b""
+    assert os.path.basename(abi.RANK_LIB_PATH) == "libspecan_rank.so"
+    assert os.path.dirname(abi.RANK_LIB_PATH) == os.path.dirname(abi.LIB_PATH)
+
+
+def test_header_compiles_as_c99_pedantic(tmp_path):
+    compiles_as_c(tmp_path, '#include "specan_rank.h"\n'
+                   "int use(const void *p, float *o, const int32_t *r) { return sa_rank_f32(p, SA_RANK_IN_POINT_POWER, o, 8, 2, r,"
+                   " 0, SA_N, 0) + sa_rank_check(SA_RANK_IN_MAG, 16, 32, 0, 1, r, 0, 1) + sa_rank_version() - SA_RANK_VERSION"
+                   " + (sa_rank_last_error()[0] != 0) + SA_RANK_Q_MAX - 8 + SA_RANK_IN_POINT_PEAK - 1 + (o[0] > 0.0f); }\n")
+
+
+def test_library_links_hip_alone_and_reads_no_environment(rank_lib):
+    from fpga_real_time_fft_analyzer_amd import abi
+    libs = needed(abi.RANK_LIB_PATH)
+    for other in ("torch", "oracle", "specan_hip", "specan_fold", "specan_peaks"):
+        assert other not in libs, libs
+    assert "amdhip64" in libs
+    assert "getenv" not in undefined(abi.RANK_LIB_PATH)
+    text = unit_text("rank_f32.hip") + unit_text("sa_rank_check.cpp")
+    assert "sa_rank_f32" in text and "sa_rank_check_call" in text
+    assert "getenv" not in text and "environ" not in text.replace("environment", "")
+    kernel = open(os.path.join(CSRC, "rank_f32.hip")).read()
+    assert "atomic" not in kernel and "s_setreg" not in kernel and "denorm" not in kernel
+    # the units include nothing of the chains, of the fold or of the peak table
+    assert not re.search(r'#\s*include\s+"(?!sa_rank\.hpp|\.\./\.\./include/specan_rank\.h|specan\.h)', text), text[:200]
+
+
+def test_kernel_inventories(rank_lib):
+    """libspecan_rank.so holds the three instantiations, one per input layout, and nothing else; the other three libraries
+    hold what they held."""
+    from fpga_real_time_fft_analyzer_amd import abi
+    assert inventory(abi.RANK_LIB_PATH) == {f"rank_f32_kernel<{f}>" for f in range(3)}
+    for path in (abi.LIB_PATH, abi.FOLD_LIB_PATH, abi.PEAKS_LIB_PATH):
+        if not os.path.exists(path):
+            abi.build()
+    assert inventory(abi.LIB_PATH) == set(TABLE)
+    assert inventory(abi.FOLD_LIB_PATH) == {f"fold_mag_f32_kernel<{k}>" for k in range(7)}
+    assert inventory(abi.PEAKS_LIB_PATH) == {f"peaks_f32_kernel<{f}>" for f in range(3)}
+
+
+def test_resource_remarks_show_no_scratch_and_no_spill():
+    """The compiler's figures for the three kernels, as `make resource-rank-f32` prints them: no scratch, no SGPR or VGPR
+    spill, the 256 bytes of LDS of the count words (two buffers of eight ranks by four waves), static -- no dynamic LDS."""
+    err = remarks("rank_f32.hip")
+    assert len(re.findall(r"Function Name: \S*rank_f32_kernel", err)) == 3
+    for what, want in (("ScratchSize \\[bytes/lane\\]", 0), ("SGPRs Spill", 0), ("VGPRs Spill", 0), ("LDS Size \\[bytes/block\\]", 256)):
+        got = [int(v) for v in re.findall(what + r": (\d+)", err)]
+        assert got == [want] * 3, (what, got)
+    print("FIGURE VGPRs", re.findall(r" VGPRs: (\d+)", err), "occupancy", re.findall(r"Occupancy \[waves/SIMD\]: (\d+)", err))
+    assert "extern __shared__" not in unit_text("rank_f32.hip")
+    make = open(os.path.join(CSRC, "Makefile")).read()
+    assert "resource-rank-f32:" in make and re.search(r"^all:.*\$\(RANK_OUT\)", make, re.M)
+    assert re.search(r"^UNITS = .*\$\(RANK_SRCS\)", make, re.M) and re.search(r"^clean:\n\trm .*\$\(RANK_OUT\)", make, re.M)
+
+
+# -------------------------------------------------------------------------------------------------------------- the check
+def in_bytes(field, rows):
+    return rows * 65536 * (2 if field else 1)
+
+
+def test_known_answers_of_the_header(check):
+    for field, rows, q, n_in, n_out in ((0, 3, 8, 196608, 96), (2, 1, 1, 131072, 4), (1, 8, 2, 1048576, 64)):
+        tag, ranks = (field, rows, q), (0,) * q
+        assert (in_bytes(field, rows), rows * q * 4) == (n_in, n_out), tag
+        assert check(field, BASE, BASE + n_in, rows, ranks=ranks) == SA_OK, tag                 # out right behind in
+        assert check(field, BASE, BASE - n_out, rows, ranks=ranks) == SA_OK, tag                # out right in front of in
+        assert check(field, BASE, BASE + n_in - 4, rows, ranks=ranks) == SA_EINVAL, tag         # out reaches into in
+        assert check(field, BASE, BASE - n_out + 4, rows, ranks=ranks) == SA_EINVAL, tag        # in reaches into out
+        assert check(field, BASE, BASE, rows, ranks=ranks) == SA_EINVAL, tag
+
+
+def test_touching_and_overlapping_ranges(check):
+    """out right behind in and right in front of it: touching is fine; moved into it by 1 byte (which also breaks the
+    alignment), by 4 (the smallest overlap an aligned out can have) and by 16 it is refused (in is 65536 bytes or more: out
+    cannot pass it in 16)."""
+    X = BASE + (1 << 30)
+    for field, rows, q in itertools.product((0, 1, 2), (1, 4, 5), (1, 3, 8)):
+        n_in, n_out, ranks = in_bytes(field, rows), rows * q * 4, (0,) * q
+        tag = (field, rows, q)
+        assert check(field, X, X + n_in, rows, ranks=ranks) == SA_OK, tag
+        assert check(field, X, X - n_out, rows, ranks=ranks) == SA_OK, tag
+        for by in (1, 4, 16):
+            assert check(field, X, X + n_in - by, rows, ranks=ranks) == SA_EINVAL, tag + (by,)
+            assert check(field, X, X - n_out + by, rows, ranks=ranks) == SA_EINVAL, tag + (by,)
+        assert check(field, X, X - n_out - 16, rows, ranks=ranks) == SA_OK, tag
+        assert check(field, X, X + n_in + 16, rows, ranks=ranks) == SA_OK, tag
+        assert check(field, X, X + n_in // 2, rows, ranks=ranks) == SA_EINVAL, tag               # out inside in
+        for off in (1, 2, 4, 8, 12, 16, 32):
+            assert check(field, BASE + off, FAR, rows, ranks=ranks) == (SA_OK if off % 16 == 0 else SA_EINVAL), off
+            assert check(field, BASE, FAR + off, rows, ranks=ranks) == (SA_OK if off % 4 == 0 else SA_EINVAL), off
+        for null in ("a_in", "a_out"):
+            assert check(field=field, rows=rows, ranks=ranks, **{null: 0}) == SA_EINVAL, null
+
+
+def test_refusals_in_their_order(check, rank_lib):
+    """1 negative rows, 2 the scalar arguments and the ranks (also at rows 0), 3 the empty call, 4 the pointers: each refusal
+    is shown to win over every later one by making the later ones wrong too."""
+    bad = [dict(field=-1), dict(field=3), dict(q=0), dict(q=9), dict(q=-1), dict(lo=-1), dict(lo=5, hi=5), dict(lo=6, hi=5),
+           dict(hi=N + 1), dict(lo=N, hi=N + 1), dict(ranks=None), dict(ranks=(N,)), dict(ranks=(-1,)), dict(ranks=(0, 0, N)),
+           dict(ranks=(0,) * 7 + (-1,)), dict(ranks=(100,), lo=50, hi=150), dict(ranks=(1,), lo=7, hi=8),
+           dict(ranks=(2 ** 31 - 1,)), dict(ranks=(-2 ** 31,))]
+    wrong_ptrs = [dict(), dict(a_in=0, a_out=0), dict(a_in=BASE + 1, a_out=BASE + 3), dict(a_in=BASE, a_out=BASE)]
+    # 1: before bad arguments and bad pointers
+    for kw in [dict()] + bad:
+        for p in wrong_ptrs:
+            assert check(rows=-1, **kw, **p) == SA_ESHAPE, (kw, p)
+            assert check(rows=-(1 << 31), **kw, **p) == SA_ESHAPE, (kw, p)
+    # 2: before the empty call and the pointers
+    for rows in (0, 1, 5, (1 << 31) - 1):
+        for kw in bad:
+            for p in wrong_ptrs:
+                assert check(rows=rows, **kw, **p) == SA_EINVAL, (rows, kw, p)
+    # 3: the empty call is SA_OK whatever the pointers are
+    for p in wrong_ptrs:
+        for field in (0, 1, 2):
+            assert check(field=field, rows=0, **p) == SA_OK, p
+    # 4: the pointers, last
+    for p in wrong_ptrs[1:]:
+        assert check(rows=1, **p) == SA_EINVAL, p
+    assert check(rows=1) == SA_OK
+    # within 2: q and the range are judged before the ranks are read -- a null array with a bad q is the bad q's refusal, and
+    # the same code; what shows it is that the call returns at all with q = 9 and an array of one entry (the stand-alone
+    # program holds every array at exactly q entries under the address sanitizer)
+    assert check(q=9, ranks=(0,)) == SA_EINVAL and check(q=8, ranks=None, lo=9, hi=9) == SA_EINVAL
+    # the edges of every scalar that are good
+    for kw in (dict(ranks=(0,)), dict(ranks=(N - 1,) * 8), dict(lo=0, hi=1), dict(lo=N - 1, hi=N), dict(ranks=(99,), lo=50, hi=150),
+               dict(field=2), dict(ranks=(5, 0, 5, N - 1)), dict(rows=(1 << 31) - 1, a_in=1 << 20, a_out=1 << 62)):
+        assert check(**kw) == SA_OK, kw
+    assert rank_lib.sa_rank_last_error() == b""                   # the check alone leaves the thread's text alone
+
+
+def test_standalone_program_under_host_sanitizers(tmp_path):
+    """tests/cpp/test_sa_rank_check.cpp + csrc/sa_rank_check.cpp, host only, under the address and undefined-behaviour
+    sanitizers when they link here (a plain build otherwise: the program's own checks still run): the same arithmetic at rows
+    up to 2^31 - 1 and addresses near 2^47 and 2^64, every array of ranks exactly q long.  Nothing is loaded into this
+    process."""
+    assert standalone_checks(tmp_path, "test_sa_rank_check", ["sa_rank_check.cpp"]) > 100000
+
+
+# ----------------------------------------------------------------------------------------------------------- the wrappers
+def test_the_wrappers_surface():
+    """The Python entry points exist; a bad rank set, quantile, range, field or group is SA_EINVAL before anything of the
+    object or of a library is touched (the object here has neither)."""
+    from fpga_real_time_fft_analyzer_amd import chain
+    cls = chain.SpectrumChain
+    assert callable(cls.order_stats) and callable(cls.noise_floor_f32)
+    bare = object.__new__(cls)
+    bad = [dict(ranks=[]), dict(ranks=list(range(9))), dict(ranks=[N]), dict(ranks=[-1]), dict(ranks=[True]), dict(ranks=[2.0]),
+           dict(ranks=5), dict(ranks=None), dict(ranks="1"), dict(ranks=[100], lo=0, hi=100), dict(lo=-1), dict(lo=7, hi=7),
+           dict(hi=N + 1), dict(lo=0.0), dict(hi=True), dict(field="mag"), dict(field=0), dict(field=["peak"])]
+    for kw in bad:
+        with pytest.raises(chain.SpecanError) as e:
+            bare.order_stats(None, **dict(dict(ranks=[0]), **kw))
+        assert e.value.code == SA_EINVAL, kw
+    for kw in (dict(q=-0.1), dict(q=1.5), dict(q=float("nan")), dict(q="0.5"), dict(q=None), dict(q=True), dict(q=[]),
+               dict(q=[0.1] * 9), dict(q=[0.5, 2.0]), dict(lo=-1), dict(lo=7, hi=7), dict(hi=N + 1), dict(lo=0.0), dict(hi=True)):
+        with pytest.raises(chain.SpecanError) as e:
+            bare.noise_floor_f32(None, **kw)
+        assert e.value.code == SA_EINVAL and "tensor" not in str(e.value), (kw, str(e.value))
+    for group in (0, 1, 3, 256, 2.0, True, "4"):
+        with pytest.raises(chain.SpecanError) as e:
+            bare.noise_floor_f32(None, group=group)
+        assert e.value.code == SA_EINVAL, group
+        assert ("group" in str(e.value) or "folds nothing" in str(e.value)) and "tensor" not in str(e.value), (group, str(e.value))
+    with pytest.raises(chain.SpecanError) as e:                   # with good arguments the input's check does speak
+        bare.noise_floor_f32(None, q=[0.1, 0.5], group=4)
+    assert e.value.code == SA_EINVAL and "tensor" in str(e.value)
+    assert cls._rank_args([np.int64(1), 0], np.int32(0), N, None) == (0, (1, 0))
+    assert cls._rank_args((N - 1,), 0, N, "peak") == (1, (N - 1,)) and cls._rank_args(np.array([0]), 5, 6, "power") == (2, (0,))
+    assert cls._quantile_ranks(0.5, 0, N) == (8191,) and cls._quantile_ranks([0.0, 0.25, 1.0], 0, N) == (0, 4095, 16383)
+    assert cls._quantile_ranks((0.29,), 100, 201) == (28,)
