@@ -1,6 +1,6 @@
 """ctypes binding of ``libspecan_hip.so`` (the C ABI declared in ``include/specan.h`` and ``include/specan_ext.h``) and of
-``libspecan_fold.so`` (``include/specan_fold.h``), ``libspecan_peaks.so`` (``include/specan_peaks.h``) and
-``libspecan_rank.so`` (``include/specan_rank.h``).
+``libspecan_fold.so`` (``include/specan_fold.h``), ``libspecan_peaks.so`` (``include/specan_peaks.h``),
+``libspecan_rank.so`` (``include/specan_rank.h``) and ``libspecan_hist.so`` (``include/specan_hist.h``).
 
 This is the only place the shared libraries are loaded.  There is no CPU fallback: if the
 library is missing the import of any compute entry point raises, and creating a handle
@@ -17,6 +17,7 @@ LIB_PATH = os.path.join(_PKG, "libspecan_hip.so")
 FOLD_LIB_PATH = os.path.join(_PKG, "libspecan_fold.so")      # include/specan_fold.h: built by the same make
 PEAKS_LIB_PATH = os.path.join(_PKG, "libspecan_peaks.so")    # include/specan_peaks.h: built by the same make
 RANK_LIB_PATH = os.path.join(_PKG, "libspecan_rank.so")      # include/specan_rank.h: built by the same make
+HIST_LIB_PATH = os.path.join(_PKG, "libspecan_hist.so")      # include/specan_hist.h: built by the same make
 CSRC = os.path.join(_PKG, "csrc")
 
 # error codes / constants (include/specan.h)
@@ -81,8 +82,8 @@ class SpecanError(RuntimeError):
 
 
 def build(verbose: bool = False) -> str:
-    """Compile the HIP extension in-tree for gfx950 (hipcc cross-compiles without a GPU): the four libraries, LIB_PATH,
-    FOLD_LIB_PATH, PEAKS_LIB_PATH and RANK_LIB_PATH, are the Makefile's first target."""
+    """Compile the HIP extension in-tree for gfx950 (hipcc cross-compiles without a GPU): the five libraries, LIB_PATH,
+    FOLD_LIB_PATH, PEAKS_LIB_PATH, RANK_LIB_PATH and HIST_LIB_PATH, are the Makefile's first target."""
     cmd = ["make", "-j4", "-C", CSRC]
     if not verbose:
         cmd.insert(1, "-s")
@@ -194,10 +195,23 @@ RANK_SIGNATURES = {
     "sa_rank_last_error": (C.c_char_p, []),
 }
 
+# the entry points of include/specan_hist.h: libspecan_hist.so, the fifth product library, again without a handle (the count
+# per group of rows, column of bins and amplitude level), bound by hist_lib() and held name for name against that header
+# (tests/test_f32_hist_cpu.py); no name is in the five tables above
+SA_HIST_VERSION = 1
+SA_HIST_LEVELS_MAX = 64
+HIST_SIGNATURES = {
+    "sa_hist_version": (_INT, []),
+    "sa_hist_f32": (_INT, [C.c_void_p, C.c_void_p, _INT, _INT, _INT, _INT, _P(C.c_float), _INT, _INT, C.c_void_p]),
+    "sa_hist_check": (_INT, [C.c_uint64, C.c_uint64, _INT, _INT, _INT, _INT, _P(C.c_float), _INT, _INT]),
+    "sa_hist_last_error": (C.c_char_p, []),
+}
+
 _lib = None
 _fold_lib = None
 _peaks_lib = None
 _rank_lib = None
+_hist_lib = None
 
 
 def _load(path: str, tables: tuple) -> C.CDLL:
@@ -252,3 +266,11 @@ def rank_lib() -> C.CDLL:
     if _rank_lib is None:
         _rank_lib = _load(RANK_LIB_PATH, (RANK_SIGNATURES,))
     return _rank_lib
+
+
+def hist_lib() -> C.CDLL:
+    """Load libspecan_hist.so (include/specan_hist.h), after torch as lib() does; raise loudly when it has not been built."""
+    global _hist_lib
+    if _hist_lib is None:
+        _hist_lib = _load(HIST_LIB_PATH, (HIST_SIGNATURES,))
+    return _hist_lib

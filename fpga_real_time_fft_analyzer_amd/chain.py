@@ -873,6 +873,96 @@ class SpectrumChain:
         out = self._rank_out(B, len(ranks), out)
         return self.order_stats(self._mag_full_in_work(x, B, scale, work), ranks, lo, hi, out=out)
 
+    @staticmethod
+    def _hist_args(edges, group, bucket, lo, hi) -> tuple:
+        """The one validation of the arguments of the level histogram: ``(log2 of the bucket, the edges as a tuple of float32
+        values)``, or SA_EINVAL.  ``group`` may be None (all rows)."""
+        for name, v in (("bucket", bucket), ("lo", lo), ("hi", hi)) + ((("group", group),) if group is not None else ()):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise SpecanError(abi.SA_EINVAL, f"{name} must be an int")
+        if group is not None and not 1 <= int(group) <= frames.HIST_GROUP_MAX:
+            raise SpecanError(abi.SA_EINVAL, f"group must be 1..{frames.HIST_GROUP_MAX}")
+        if int(bucket) not in frames.HIST_BUCKETS:
+            raise SpecanError(abi.SA_EINVAL, f"bucket must be one of {frames.HIST_BUCKETS}")
+        try:
+            keys = frames._hist_edge_keys(edges)
+        except ValueError as e:
+            raise SpecanError(abi.SA_EINVAL, str(e)) from None
+        if not 0 <= int(lo) < int(hi) <= SA_N or int(lo) % int(bucket) or int(hi) % int(bucket):
+            raise SpecanError(abi.SA_EINVAL, f"the range must be 0 <= lo < hi <= {SA_N}, both multiples of the bucket")
+        return int(bucket).bit_length() - 1, tuple(float(v) for v in keys.view(np.float32))
+
+    def _hist_out(self, R: int, group, bucket: int, lo: int, hi: int, L: int, out: Optional[torch.Tensor]) -> tuple:
+        """``(group, out)`` of the level histogram of ``R`` rows, ``group`` None meaning all of them and ``out`` allocated when
+        None: SA_ESHAPE where R is no multiple of the group or ``out`` is not the contiguous uint32 [G, C, L] tensor on the
+        handle's device."""
+        A = max(R, 1) if group is None else int(group)
+        if A > frames.HIST_GROUP_MAX:
+            raise SpecanError(abi.SA_EINVAL, f"group must be 1..{frames.HIST_GROUP_MAX}")
+        if R % A:
+            raise SpecanError(abi.SA_ESHAPE, f"the rows ({R}) must be a multiple of {A}")
+        shape = (R // A, (int(hi) - int(lo)) // int(bucket), L)
+        if out is None:
+            return A, torch.empty(shape, dtype=torch.uint32, device=self.device)
+        if (not isinstance(out, torch.Tensor) or tuple(out.shape) != shape or out.dtype != torch.uint32
+                or out.device != self.device or not out.is_contiguous()):
+            raise SpecanError(abi.SA_ESHAPE, f"out must be a contiguous torch.uint32 tensor of shape {shape}")
+        return A, out
+
+    def level_hist(self, t: torch.Tensor, edges: Sequence[float], group: Optional[int] = None, bucket: int = 1, lo: int = 0,
+                   hi: int = SA_N, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The level histogram of the rows of ``t`` (include/specan_hist.h, sa_hist_f32), the data of a persistence display:
+        uint32 [G, C, L], ``[g, c, l]`` the number of points of group g (``group`` consecutive rows; None: all rows, G = 1)
+        and column c (the bins ``[lo + c bucket, lo + (c + 1) bucket)``) whose level is l.  ``t`` is a float32 [R,16384]
+        device tensor: what ``process_f32(out_kind='mag_full')`` or ``process_q15(out_kind='mag')`` wrote.
+
+        A point's key is its bits with the sign cleared, as an integer: the float order of the chains' non-negative values; a
+        NaN is above +inf, -0.0 reads as +0.0, no denormal is flushed.  Its level is the number of ``edges`` whose key is not
+        above its own, 0..L-1 with L = len(edges) + 1: a value equal to an edge is in the level above it.  The L counters of
+        a cell column sum to ``group * bucket``; the counts add across calls, so a longer persistence is a sum (or a decayed
+        sum) of these small images on the host.  frames.hist_of_rows is the numpy mirror, bit for bit; frames.level_edges_db
+        makes edges evenly spaced in dB.
+
+        ``edges`` is a sequence of 1..63 numbers, each +0.0 .. +inf as a float32 and none below the one before; ``group`` is
+        1..2^24 and divides R; ``bucket`` is 1, 2, 4, ..., 64; ``0 <= lo < hi <= 16384``, both multiples of ``bucket``; ints
+        only (a bool or a float is SA_EINVAL); a wrong dtype is SA_EINVAL and a wrong shape SA_ESHAPE, all before any
+        device call.  One launch on the current stream of the handle's device (two, the first zeroing ``out``, where there
+        are fewer than 256 pairs of a group and a 256-bin tile and ``group`` is 64 or more) -- the edges travel in the
+        launch's arguments, every counter is written (``out`` needs no zeroing) -- no handle state, no workspace: it captures
+        into a graph at any time.  Where ``t`` is the result of a call made in overlap mode, call :meth:`flush` first.  Pointer
+        contract (checked by the C entry point, SA_EINVAL): ``t`` is 16-byte aligned, and the bytes read and the G * C * L * 4
+        bytes written are disjoint; buffers that merely touch are fine."""
+        log2w, edges = self._hist_args(edges, group, bucket, lo, hi)
+        R = self._check_in(t, torch.float32, SA_N)
+        A, out = self._hist_out(R, group, int(bucket), lo, hi, len(edges) + 1, out)
+        L = abi.hist_lib()
+        with torch.cuda.device(self.device):         # the C call launches on the calling thread's current device
+            rc = L.sa_hist_f32(t.data_ptr(), out.data_ptr(), R, A, log2w, len(edges) + 1, (C.c_float * len(edges))(*edges),
+                               int(lo), int(hi), self._stream())
+        if rc != abi.SA_OK:
+            raise SpecanError(rc, L.sa_hist_last_error().decode())
+        return out
+
+    def persistence_f32(self, x: torch.Tensor, edges: Sequence[float], group: Optional[int] = None, bucket: int = 16,
+                        lo: int = 0, hi: int = SA_N, scale: float = 1.0 / 2048.0, work: Optional[torch.Tensor] = None,
+                        out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The level histogram of the float chain's spectra, without the spectra leaving the device: uint32 [G, C, L] as
+        :meth:`level_hist` returns it.  ``x`` is float32, int16 or packed uint8 exactly as for :meth:`process_f32`; every
+        filter mode and both precisions apply.  The call is ``process_f32(x, out_kind='mag_full', scale=scale)`` into the
+        workspace of :meth:`spectra_f32` followed by :meth:`level_hist`.
+
+        The workspace is ``work`` or the cached tensor, as for :meth:`spectra_f32`, and in overlap mode the call joins every
+        outstanding call of the handle on the device (as :meth:`flush` does) before the count: the result is valid on the
+        current stream when the call returns, and the call lends nothing.  The edges, ``group`` (None: the whole batch),
+        ``bucket``, the range and ``out`` are refused as by :meth:`level_hist`, all before anything is launched, and so is
+        a wrong ``work``."""
+        log2w, keys = self._hist_args(edges, group, bucket, lo, hi)
+        forms = FLOAT_CHAIN.inputs
+        dtype = x.dtype if isinstance(x, torch.Tensor) and x.dtype in forms else next(iter(forms))
+        B = self._check_in(x, dtype, forms[dtype][0])
+        A, out = self._hist_out(B, group, int(bucket), lo, hi, len(keys) + 1, out)     # refused here, before the chain is launched
+        return self.level_hist(self._mag_full_in_work(x, B, scale, work), edges, A, bucket, lo, hi, out=out)
+
     def filter_q15(self, x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Window (+ integer IIR) only: the FFT input stream, [B,16384] int16.  ``x`` is [B,16384] int16 or the same
         samples packed, [B,24576] uint8 (sa_filter_q15_p12), as for :meth:`process_q15`.

@@ -240,6 +240,87 @@ def rank_of_quantile(q: float, m: int) -> int:
     return math.floor(float(q) * (int(m) - 1))
 
 
+HIST_LEVELS_MAX = 64
+HIST_BUCKETS = (1, 2, 4, 8, 16, 32, 64)
+HIST_GROUP_MAX = 1 << 24
+
+
+def _hist_edge_keys(edges) -> np.ndarray:
+    """``edges`` as the uint32 keys of 1..63 float32 values, or ValueError: numbers only, each with the sign bit clear and
+    no NaN (bits <= 0x7F800000), the keys non-decreasing."""
+    if isinstance(edges, (str, bytes)) or not hasattr(edges, "__len__") or not 1 <= len(edges) <= HIST_LEVELS_MAX - 1:
+        raise ValueError(f"edges must be a sequence of 1..{HIST_LEVELS_MAX - 1} numbers")
+    for v in edges:
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+            raise ValueError("an edge must be a number")
+    with np.errstate(over="ignore"):
+        keys = np.array([float(v) for v in edges], np.float64).astype(np.float32).view(np.uint32)
+    if (keys > 0x7F800000).any():
+        raise ValueError("an edge must be +0.0 .. +inf: no NaN, no sign bit")
+    if (keys[1:] < keys[:-1]).any():
+        raise ValueError("the edges must not decrease")
+    return keys
+
+
+def hist_of_rows(points, edges, group: int = 1, bucket: int = 1, lo: int = 0, hi: int = FFT_SIZE):
+    """The level histogram of float32 ``points`` [R,16384]: uint32 [G, C, L], C-contiguous, ``[g, c, l]`` the number of points
+    (row, bin) of group g (the rows [g group, (g + 1) group)) and column c (the bins [lo + c bucket, lo + (c + 1) bucket))
+    whose level is l.  The numpy mirror of sa_hist_f32 (include/specan_hist.h):
+
+    - key: the float's bits with the sign cleared, as a uint32 -- +inf above every finite value, a NaN above +inf, -0.0 as
+      +0.0, denormals kept;
+    - level: ``np.searchsorted(edge_keys, keys, side="right")``, the number of edges whose key is not above the point's: a
+      value equal to an edge is in the level above it, a NaN in level L - 1, L = len(edges) + 1.
+
+    ``edges`` is a sequence of 1..63 numbers, each +0.0 .. +inf as a float32 and none below the one before; ``group`` is
+    1..2^24 and divides R; ``bucket`` is 1, 2, ..., 64; ``0 <= lo < hi <= 16384``, both multiples of ``bucket``; the integers
+    are ints (no bool, no float): ValueError otherwise, and on a wrong dtype or shape."""
+    for name, v in (("group", group), ("bucket", bucket), ("lo", lo), ("hi", hi)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f"{name} must be an int")
+    group, bucket, lo, hi = int(group), int(bucket), int(lo), int(hi)
+    if not 1 <= group <= HIST_GROUP_MAX:
+        raise ValueError(f"group must be 1..{HIST_GROUP_MAX}")
+    if bucket not in HIST_BUCKETS:
+        raise ValueError(f"bucket must be one of {HIST_BUCKETS}")
+    edge_keys = _hist_edge_keys(edges)
+    if not 0 <= lo < hi <= FFT_SIZE or lo % bucket or hi % bucket:
+        raise ValueError("the range must be 0 <= lo < hi <= 16384, both multiples of the bucket")
+    points = np.ascontiguousarray(points)
+    if points.dtype != np.float32 or points.ndim != 2 or points.shape[1] != FFT_SIZE:
+        raise ValueError("points must be float32 [R, 16384]")
+    R = points.shape[0]
+    if R % group:
+        raise ValueError(f"the rows ({R}) must be a multiple of group ({group})")
+    G, cols, L = R // group, (hi - lo) // bucket, len(edge_keys) + 1
+    keys = points.view(np.uint32)[:, lo:hi] & np.uint32(0x7FFFFFFF)
+    level = np.searchsorted(edge_keys, keys, side="right").reshape(G, group, cols, bucket)
+    cell = (np.arange(G).reshape(G, 1, 1, 1) * cols + np.arange(cols).reshape(1, 1, cols, 1)) * L + level
+    return np.bincount(cell.ravel(), minlength=G * cols * L).astype(np.uint32).reshape(G, cols, L)
+
+
+def level_edges_db(top: float, span_db: float, levels: int) -> np.ndarray:
+    """``levels - 1`` float32 edges evenly spaced in dB for :func:`hist_of_rows` / sa_hist_f32: the last one is
+    ``float32(top)``, the first ``float32(top * 10 ** (-span_db / 20))``, edge j ``top * 10 ** (-span_db / 20 * (1 - j / (levels -
+    2)))`` computed in float64 and rounded once.  With ``levels`` = 2 the single edge is ``top``.  A host convenience: the
+    edges are an input of the histogram, not part of its definition.  ValueError unless ``top`` is a finite number above 0,
+    ``span_db`` a finite number not below 0 and ``levels`` an int in 2..64."""
+    if isinstance(levels, bool) or not isinstance(levels, (int, np.integer)) or not 2 <= int(levels) <= HIST_LEVELS_MAX:
+        raise ValueError(f"levels must be an int in 2..{HIST_LEVELS_MAX}")
+    for name, v in (("top", top), ("span_db", span_db)):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not math.isfinite(float(v)):
+            raise ValueError(f"{name} must be a finite number")
+    if not float(top) > 0.0 or float(span_db) < 0.0:
+        raise ValueError("top must be above 0 and span_db not below 0")
+    n, top, span_db = int(levels) - 1, float(top), float(span_db)
+    if n == 1:
+        return np.array([top], np.float32)
+    # edge j lies span_db (1 - j / (n - 1)) dB below top: span_db, ..., 0; Python's doubles, each product rounded once
+    edges = np.array([top * 10.0 ** (-(span_db * (1.0 - j / (n - 1))) / 20.0) for j in range(n)], np.float64).astype(np.float32)
+    edges[-1] = np.float32(top)
+    return edges
+
+
 def decode_iq_components(frame_bytes: bytes):
     """Same result as gui.py:262-270: (re, im) as float32 arrays."""
     re, im = _iq(frame_bytes)
