@@ -34,7 +34,9 @@ __device__ __forceinline__ void fold_quad(const uint4 &r, unsigned (&s)[4], unsi
     fold_bin(r.w, s[3], pw[3]);
 }
 
-// `quads` = (B / A) 4096 threads' worth of output; groupsize = A, a power of two from 2 on.  Every offset is a size_t: B 65536 bytes pass 2^32 at B = 65536.
+// `quads` = (B / A) 4096 threads' worth of output; groupsize = A, a power of two from 2 on.  Every offset is a size_t: frame
+// 65536 of `iq` starts at byte 2^32, so a batch of 65537 frames reads beyond it, and row 32768 of `out` (131072 bytes a row)
+// does, so B / A = 32769 rows write beyond it; tests/test_gpu_offsets.py goes there.
 __global__ __launch_bounds__(kFoldThreads) void spectra_fold_q15_kernel(const uint4 *__restrict__ iq, uint4 *__restrict__ out,
                                                                        size_t quads, int groupsize)
 {

@@ -16,8 +16,9 @@ namespace {
 constexpr int kFoldThreads = 256;
 static_assert(SA_NPTS == 1 << 14, "log2p = 14 - k");
 
-// `points` = (B / A) P output points; log2p = 14 - k.  Every offset is a size_t: B P 16 bytes pass 2^32 from B = 32768
-// at W = 2 on.
+// `points` = (B / A) P output points; log2p = 14 - k.  Every offset is a size_t: at W = 2 a frame's records are 131072
+// bytes and those of frame 32768 start at byte 2^32, so a batch of 32769 frames reads beyond it (at W = 2^k: of
+// 2^(14 + k) + 1); tests/test_gpu_offsets.py goes there.
 __global__ __launch_bounds__(kFoldThreads) void trace_fold_q15_kernel(const uint4 *__restrict__ part, uint2 *__restrict__ out,
                                                                      size_t points, int log2p, int groupsize)
 {
