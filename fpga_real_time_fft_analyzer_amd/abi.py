@@ -1,6 +1,7 @@
 """ctypes binding of ``libspecan_hip.so`` (the C ABI declared in ``include/specan.h`` and ``include/specan_ext.h``) and of
 ``libspecan_fold.so`` (``include/specan_fold.h``), ``libspecan_peaks.so`` (``include/specan_peaks.h``),
-``libspecan_rank.so`` (``include/specan_rank.h``) and ``libspecan_hist.so`` (``include/specan_hist.h``).
+``libspecan_rank.so`` (``include/specan_rank.h``), ``libspecan_hist.so`` (``include/specan_hist.h``) and
+``libspecan_bands.so`` (``include/specan_bands.h``).
 
 This is the only place the shared libraries are loaded.  There is no CPU fallback: if the
 library is missing the import of any compute entry point raises, and creating a handle
@@ -18,6 +19,7 @@ FOLD_LIB_PATH = os.path.join(_PKG, "libspecan_fold.so")      # include/specan_fo
 PEAKS_LIB_PATH = os.path.join(_PKG, "libspecan_peaks.so")    # include/specan_peaks.h: built by the same make
 RANK_LIB_PATH = os.path.join(_PKG, "libspecan_rank.so")      # include/specan_rank.h: built by the same make
 HIST_LIB_PATH = os.path.join(_PKG, "libspecan_hist.so")      # include/specan_hist.h: built by the same make
+BANDS_LIB_PATH = os.path.join(_PKG, "libspecan_bands.so")    # include/specan_bands.h: built by the same make
 CSRC = os.path.join(_PKG, "csrc")
 
 # error codes / constants (include/specan.h)
@@ -82,8 +84,8 @@ class SpecanError(RuntimeError):
 
 
 def build(verbose: bool = False) -> str:
-    """Compile the HIP extension in-tree for gfx950 (hipcc cross-compiles without a GPU): the five libraries, LIB_PATH,
-    FOLD_LIB_PATH, PEAKS_LIB_PATH, RANK_LIB_PATH and HIST_LIB_PATH, are the Makefile's first target."""
+    """Compile the HIP extension in-tree for gfx950 (hipcc cross-compiles without a GPU): the six libraries, LIB_PATH,
+    FOLD_LIB_PATH, PEAKS_LIB_PATH, RANK_LIB_PATH, HIST_LIB_PATH and BANDS_LIB_PATH, are the Makefile's first target."""
     cmd = ["make", "-j4", "-C", CSRC]
     if not verbose:
         cmd.insert(1, "-s")
@@ -207,11 +209,32 @@ HIST_SIGNATURES = {
     "sa_hist_last_error": (C.c_char_p, []),
 }
 
+
+class Band(C.Structure):
+    """sa_band of include/specan_bands.h: the bins [lo, hi) of one band, 8 bytes."""
+    _fields_ = [("lo", C.c_int32), ("hi", C.c_int32)]
+
+
+# the entry points of include/specan_bands.h: libspecan_bands.so, the sixth product library, again without a handle (the
+# float64 power of bands of bins of each row of 16384 points and the bins at which its cumulative power crosses given
+# fractions), bound by bands_lib() and held name for name against that header (tests/test_f32_bands_cpu.py); no name is in the
+# tables above
+SA_BANDS_VERSION = 1
+SA_BANDS_MAX, SA_BANDS_Q_MAX = 16, 4
+SA_BANDS_IN_MAG, SA_BANDS_IN_POINT_PEAK, SA_BANDS_IN_POINT_POWER = 0, 1, 2
+BANDS_SIGNATURES = {
+    "sa_bands_version": (_INT, []),
+    "sa_bands_f32": (_INT, [C.c_void_p, _INT, C.c_void_p, C.c_void_p, _INT, _INT, _P(Band), _INT, _P(C.c_double), C.c_void_p]),
+    "sa_bands_check": (_INT, [_INT, C.c_uint64, C.c_uint64, C.c_uint64, _INT, _INT, _P(Band), _INT, _P(C.c_double)]),
+    "sa_bands_last_error": (C.c_char_p, []),
+}
+
 _lib = None
 _fold_lib = None
 _peaks_lib = None
 _rank_lib = None
 _hist_lib = None
+_bands_lib = None
 
 
 def _load(path: str, tables: tuple) -> C.CDLL:
@@ -274,3 +297,11 @@ def hist_lib() -> C.CDLL:
     if _hist_lib is None:
         _hist_lib = _load(HIST_LIB_PATH, (HIST_SIGNATURES,))
     return _hist_lib
+
+
+def bands_lib() -> C.CDLL:
+    """Load libspecan_bands.so (include/specan_bands.h), after torch as lib() does; raise loudly when it has not been built."""
+    global _bands_lib
+    if _bands_lib is None:
+        _bands_lib = _load(BANDS_LIB_PATH, (BANDS_SIGNATURES,))
+    return _bands_lib

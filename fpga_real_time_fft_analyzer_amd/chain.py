@@ -134,6 +134,8 @@ FOLD_GROUPS, FOLD_BUCKETS = frames.FOLD_GROUPS, frames.FOLD_BUCKETS         # 1 
 _PEAK_FIELDS = {None: abi.SA_PEAKS_IN_MAG, "peak": abi.SA_PEAKS_IN_POINT_PEAK, "power": abi.SA_PEAKS_IN_POINT_POWER}
 # order_stats(field=...) -> the `field` of include/specan_rank.h: the same three layouts
 _RANK_FIELDS = {None: abi.SA_RANK_IN_MAG, "peak": abi.SA_RANK_IN_POINT_PEAK, "power": abi.SA_RANK_IN_POINT_POWER}
+# band_power(field=...) -> the `field` of include/specan_bands.h: the same three layouts
+_BANDS_FIELDS = {None: abi.SA_BANDS_IN_MAG, "peak": abi.SA_BANDS_IN_POINT_PEAK, "power": abi.SA_BANDS_IN_POINT_POWER}
 
 
 def output_spec(chain: _Chain, out_kind: Optional[str], B: int) -> tuple:
@@ -962,6 +964,103 @@ class SpectrumChain:
         B = self._check_in(x, dtype, forms[dtype][0])
         A, out = self._hist_out(B, group, int(bucket), lo, hi, len(keys) + 1, out)     # refused here, before the chain is launched
         return self.level_hist(self._mag_full_in_work(x, B, scale, work), edges, A, bucket, lo, hi, out=out)
+
+    @staticmethod
+    def _bands_args(bands, fracs, field) -> tuple:
+        """The one validation of the arguments of the band power: ``(field code of include/specan_bands.h, the bands as a
+        tuple of (lo, hi) int pairs, the fractions as a tuple of floats)``, or SA_EINVAL."""
+        try:
+            bands, fracs = frames._bands_args(bands, fracs, field)
+        except ValueError as e:
+            raise SpecanError(abi.SA_EINVAL, str(e)) from None
+        return _BANDS_FIELDS[field], bands, fracs
+
+    def _bands_out(self, R: int, nb: int, nq: int, power: Optional[torch.Tensor], cross: Optional[torch.Tensor]) -> tuple:
+        """``(power, cross)`` of the band power of ``R`` rows, each allocated when None: SA_ESHAPE where ``power`` is not the
+        contiguous float64 [R, nb] tensor or ``cross`` not the contiguous int32 [R, nb, nq] tensor on the handle's device.
+        Without fractions ``cross`` is handed back as it came and never looked at."""
+        for name, t, shape, dtype in (("power", power, (R, nb), torch.float64), ("cross", cross, (R, nb, nq), torch.int32)):
+            if t is None or (name == "cross" and nq == 0):
+                continue
+            if (not isinstance(t, torch.Tensor) or tuple(t.shape) != shape or t.dtype != dtype or t.device != self.device
+                    or not t.is_contiguous()):
+                raise SpecanError(abi.SA_ESHAPE, f"{name} must be a contiguous {dtype} tensor of shape {shape}")
+        if power is None:
+            power = torch.empty((R, nb), dtype=torch.float64, device=self.device)
+        if cross is None and nq:
+            cross = torch.empty((R, nb, nq), dtype=torch.int32, device=self.device)
+        return power, cross
+
+    def band_power(self, t: torch.Tensor, bands: Sequence, fracs: Sequence[float] = (), field: Optional[str] = None,
+                   power: Optional[torch.Tensor] = None, cross: Optional[torch.Tensor] = None) -> tuple:
+        """Band power and occupied bandwidth of each row of ``t`` (include/specan_bands.h, sa_bands_f32): ``(power float64
+        [R, nb], cross int32 [R, nb, nq])``, or ``(power, None)`` without fractions.  ``power[r, j]`` is the sum of the power
+        of the bins ``[lo_j, hi_j)`` of row r in float64; ``cross[r, j, q]`` the bin of that band at which its cumulative
+        power reaches ``fracs[q]`` of it, or -1 where the band holds a NaN.  ``t`` is a float32 [R,16384] device tensor --
+        what ``process_f32(out_kind='mag_full')`` or ``process_q15(out_kind='mag')`` wrote, squared bin by bin -- or, with
+        ``field='peak'`` (squared) or ``field='power'`` (taken as it is: a power sum already), float32 [R,16384,2], the
+        records of :meth:`fold_mag_f32` at bucket 1, :meth:`spectra_f32` or :meth:`spectra_q15`.  Of ``spectra_f32(group=A)``
+        the power is the sum over A frames: the Welch mean is ``power / A`` on the host.
+
+        A point's value is the float with its sign cleared, widened to float64 (denormals kept); a band's sum is the balanced
+        tree of adjacent pairs over the row with +0.0 outside the band -- the tree of :meth:`fold_mag_f32` across a bucket,
+        continued -- and a crossing a 14-step descent of that tree; frames.bands_of_rows is the numpy mirror, bit for bit.
+        Channel power and ACPR are a main band and its neighbours (frames.channel_bands); occupied bandwidth at 99 % is
+        ``fracs=(0.005, 0.995)``; the power median of a band is 0.5.
+
+        ``bands`` is a sequence of 1..16 (lo, hi) pairs of ints, ``0 <= lo < hi <= 16384``, in any order, overlapping or
+        repeated; ``fracs`` a sequence of 0..4 numbers in [0, 1 - 2^-32]; a bool or a float where an int belongs is
+        SA_EINVAL; a wrong dtype is SA_EINVAL and a wrong shape SA_ESHAPE, all before any device call.  One launch on the
+        current stream of the handle's device -- the bands and fractions travel in the launch's arguments -- no atomics, no
+        handle state, no workspace: it captures into a graph at any time.  Where ``t`` is the result of a call made in
+        overlap mode, call :meth:`flush` first.  Pointer contract (checked by the C entry point, SA_EINVAL): ``t`` is 16-byte
+        aligned, and the bytes read, the R * nb * 8 bytes of ``power`` and the R * nb * nq * 4 bytes of ``cross`` are
+        pairwise disjoint; buffers that merely touch are fine."""
+        code, bands, fracs = self._bands_args(bands, fracs, field)
+        R = self._check_in(t, torch.float32, (SA_N, 2) if code else SA_N)
+        nb, nq = len(bands), len(fracs)
+        power, cross = self._bands_out(R, nb, nq, power, cross)
+        L = abi.bands_lib()
+        c_bands = (abi.Band * nb)(*(abi.Band(lo, hi) for lo, hi in bands))
+        c_fracs = (C.c_double * nq)(*fracs) if nq else None
+        with torch.cuda.device(self.device):         # the C call launches on the calling thread's current device
+            rc = L.sa_bands_f32(t.data_ptr(), code, power.data_ptr(), cross.data_ptr() if nq else None, R, nb, c_bands, nq,
+                                c_fracs, self._stream())
+        if rc != abi.SA_OK:
+            raise SpecanError(rc, L.sa_bands_last_error().decode())
+        return power, cross if nq else None
+
+    def channel_power_f32(self, x: torch.Tensor, bands: Sequence, fracs: Sequence[float] = (), group: Optional[int] = None,
+                          scale: float = 1.0 / 2048.0, work: Optional[torch.Tensor] = None,
+                          power: Optional[torch.Tensor] = None, cross: Optional[torch.Tensor] = None) -> tuple:
+        """Band power and occupied bandwidth of the float chain's spectra, without the spectra leaving the device: ``(power
+        float64 [R, nb], cross int32 [R, nb, nq] or None)`` as :meth:`band_power` returns them.  ``x`` is float32, int16 or
+        packed uint8 exactly as for :meth:`process_f32`; every filter mode and both precisions apply.
+
+        Without ``group`` (R = B) the call is ``process_f32(x, out_kind='mag_full', scale=scale)`` into the workspace of
+        :meth:`spectra_f32` followed by :meth:`band_power`: the band powers of every frame.  With ``group=A`` (2, 4, ...,
+        128; R = B // A) it is ``spectra_f32(x, group=A, scale=scale, work=work)`` followed by ``band_power(...,
+        field='power')``: the band powers of the summed power of every A consecutive frames, the Welch estimate times A.
+
+        The workspace is ``work`` or the cached tensor, as for :meth:`spectra_f32`, and in overlap mode the call joins every
+        outstanding call of the handle on the device (as :meth:`flush` does) before the sums: the result is valid on the
+        current stream when the call returns, and the call lends nothing.  The bands, the fractions, ``power`` and ``cross``
+        are refused as by :meth:`band_power`, ``group`` and a B that is no multiple of it as by :meth:`spectra_f32`, all
+        before anything is launched, and so is a wrong ``work``."""
+        _, bands, fracs = self._bands_args(bands, fracs, None)
+        if group is not None:
+            self._log2_fold(group, 1)
+        forms = FLOAT_CHAIN.inputs
+        dtype = x.dtype if isinstance(x, torch.Tensor) and x.dtype in forms else next(iter(forms))
+        B = self._check_in(x, dtype, forms[dtype][0])
+        if group is not None:
+            if B % int(group):
+                raise SpecanError(abi.SA_ESHAPE, f"the batch ({B} frames) must be a multiple of {int(group)}")
+            power, cross = self._bands_out(B // int(group), len(bands), len(fracs), power, cross)      # refused here, before the chain
+            rec = self.spectra_f32(x, group, 1, scale=scale, work=work)
+            return self.band_power(rec, bands, fracs, field="power", power=power, cross=cross)
+        power, cross = self._bands_out(B, len(bands), len(fracs), power, cross)
+        return self.band_power(self._mag_full_in_work(x, B, scale, work), bands, fracs, power=power, cross=cross)
 
     def filter_q15(self, x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Window (+ integer IIR) only: the FFT input stream, [B,16384] int16.  ``x`` is [B,16384] int16 or the same

@@ -321,6 +321,124 @@ def level_edges_db(top: float, span_db: float, levels: int) -> np.ndarray:
     return edges
 
 
+BANDS_MAX = 16
+BANDS_Q_MAX = 4
+BANDS_FRAC_MAX = 1.0 - 2.0 ** -32
+
+
+def _bands_args(bands, fracs, field) -> tuple:
+    """``(bands as a tuple of (lo, hi) int pairs, fracs as a tuple of floats)`` of the band power, or ValueError: 1..16 bands,
+    each a pair of ints (no bool, no float) with ``0 <= lo < hi <= 16384``; 0..4 fractions, numbers in [0, 1 - 2^-32] (no NaN);
+    ``field`` None, 'peak' or 'power'."""
+    if isinstance(bands, (str, bytes)) or not hasattr(bands, "__len__") or not 1 <= len(bands) <= BANDS_MAX:
+        raise ValueError(f"bands must be a sequence of 1..{BANDS_MAX} (lo, hi) pairs")
+    pairs = []
+    for b in bands:
+        if isinstance(b, (str, bytes)) or not hasattr(b, "__len__") or len(b) != 2:
+            raise ValueError("a band must be a (lo, hi) pair")
+        for v in b:
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise ValueError("lo and hi of a band must be ints")
+        lo, hi = int(b[0]), int(b[1])
+        if not 0 <= lo < hi <= FFT_SIZE:
+            raise ValueError("a band must be 0 <= lo < hi <= 16384")
+        pairs.append((lo, hi))
+    if isinstance(fracs, (str, bytes)) or not hasattr(fracs, "__len__") or len(fracs) > BANDS_Q_MAX:
+        raise ValueError(f"fracs must be a sequence of 0..{BANDS_Q_MAX} numbers")
+    for v in fracs:
+        if (isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating))
+                or not 0.0 <= float(v) <= BANDS_FRAC_MAX):
+            raise ValueError("a fraction must be a number in 0 .. 1 - 2^-32")
+    if not (field is None or isinstance(field, str)) or field not in RANK_FIELDS:
+        raise ValueError("field must be None, 'peak' or 'power'")
+    return tuple(pairs), tuple(float(v) for v in fracs)
+
+
+def bands_of_rows(points, bands, fracs=(), field=None):
+    """The band power of float32 ``points`` [R,16384] -- or, with ``field`` 'peak' or 'power', of that float of the records
+    [R,16384,2]: ``(power float64 [R, nb], cross int32 [R, nb, nq])``, both C-contiguous.  The numpy mirror of sa_bands_f32
+    (include/specan_bands.h), step for step:
+
+    - value: ``a`` is the point with its sign bit cleared, widened to float64 (exact, denormals kept); ``v = a * a`` for the
+      magnitudes and for 'peak', ``v = a`` for 'power', which already is a power sum;
+    - band (lo, hi): ``w = v`` inside [lo, hi) and +0.0 outside;
+    - tree: ``T[0] = w``, ``T[l + 1] = T[l][0::2] + T[l][1::2]`` (the explicit halving, 14 levels); ``power = T[14][0]``,
+      not rounded;
+    - crossing of the fraction f: ``t = f * power``; from the root with ``E = 0.0`` and ``k = 0``, for l = 13 .. 0 (the
+      explicit loop): ``L = T[l][2k]``; where ``E + L >= t`` go left, ``k = 2k``, else ``E = E + L`` and ``k = 2k + 1``; at
+      the leaf the result is ``min(max(k, lo), hi - 1)`` where ``E + w[k] >= t`` and -1 otherwise.  A NaN in the band gives -1,
+      an all-zero band and a fraction of 0 give lo.
+
+    ``bands`` is a sequence of 1..16 (lo, hi) pairs of ints, ``0 <= lo < hi <= 16384``, in any order, overlapping or repeated;
+    ``fracs`` a sequence of 0..4 numbers in [0, 1 - 2^-32], in any order; the integers are ints (no bool, no float):
+    ValueError otherwise, and on a wrong dtype or shape."""
+    bands, fracs = _bands_args(bands, fracs, field)
+    points = np.ascontiguousarray(points)
+    shape = (FFT_SIZE,) if field is None else (FFT_SIZE, 2)
+    if points.dtype != np.float32 or points.ndim != 1 + len(shape) or points.shape[1:] != shape:
+        raise ValueError(f"points must be float32 [R, {', '.join(map(str, shape))}]")
+    if field is not None:
+        points = np.ascontiguousarray(points[..., RANK_FIELDS[field]])
+    R = points.shape[0]
+    a = (points.view(np.uint32) & np.uint32(0x7FFFFFFF)).view(np.float32).astype(np.float64)
+    power = np.zeros((R, len(bands)), np.float64)
+    cross = np.zeros((R, len(bands), len(fracs)), np.int32)
+    rows = np.arange(R)
+    with np.errstate(over="ignore", invalid="ignore"):
+        v = a if field == "power" else a * a
+        for j, (lo, hi) in enumerate(bands):
+            w = np.zeros_like(v)
+            w[:, lo:hi] = v[:, lo:hi]
+            T = [w]
+            while T[-1].shape[1] > 1:                 # adjacent pairs on the bin index, 14 levels
+                T.append(T[-1][:, 0::2] + T[-1][:, 1::2])
+            S = T[-1][:, 0]
+            power[:, j] = S
+            for q, f in enumerate(fracs):
+                t = f * S
+                E = np.zeros(R, np.float64)
+                k = np.zeros(R, np.int64)
+                for l in range(len(T) - 2, -1, -1):   # 13 .. 0
+                    EL = E + T[l][rows, 2 * k]
+                    left = EL >= t
+                    E = np.where(left, E, EL)
+                    k = np.where(left, 2 * k, 2 * k + 1)
+                reached = E + w[rows, k] >= t
+                cross[:, j, q] = np.where(reached, np.clip(k, lo, hi - 1), -1)
+    return power, cross
+
+
+def channel_bands(center: int, width: int, spacing: int, adjacent: int = 1) -> list:
+    """The bands of a channel-power measurement for :func:`bands_of_rows` / sa_bands_f32: the main channel, ``width`` bins
+    starting at ``center - width // 2``, then ``adjacent`` channels of the same width on either side, ``spacing`` bins from
+    centre to centre, as ``(lo, hi)`` tuples clipped to 0..16384 -- ``[main, lower 1, upper 1, lower 2, upper 2, ...]``.  An
+    adjacent channel that lies wholly outside the spectrum is left out.  A host convenience: the bands are an input of the
+    call, not part of its definition.  ValueError unless all four are ints (no bool, no float), ``width`` and ``spacing`` are
+    1 or more, ``adjacent`` is 0 or more, at most 16 bands result and the main band, clipped, is not empty."""
+    for name, v in (("center", center), ("width", width), ("spacing", spacing), ("adjacent", adjacent)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f"{name} must be an int")
+    center, width, spacing, adjacent = int(center), int(width), int(spacing), int(adjacent)
+    if width < 1 or spacing < 1 or adjacent < 0:
+        raise ValueError("width and spacing must be 1 or more and adjacent 0 or more")
+
+    def clipped(c):
+        lo = c - width // 2
+        return max(lo, 0), min(lo + width, FFT_SIZE)
+
+    main = clipped(center)
+    if main[0] >= main[1]:
+        raise ValueError("the main band is empty")
+    out = [main]
+    for i in range(1, adjacent + 1):
+        for b in (clipped(center - i * spacing), clipped(center + i * spacing)):
+            if b[0] < b[1]:
+                out.append(b)
+    if len(out) > BANDS_MAX:
+        raise ValueError(f"more than {BANDS_MAX} bands")
+    return out
+
+
 def decode_iq_components(frame_bytes: bytes):
     """Same result as gui.py:262-270: (re, im) as float32 arrays."""
     re, im = _iq(frame_bytes)

@@ -1,0 +1,414 @@
+"""GPU: the band power (include/specan_bands.h: sa_bands_f32 of libspecan_bands.so), through SpectrumChain.band_power,
+SpectrumChain.channel_power_f32 and the C entry point.
+
+Every comparison is exact -- float64 bits of the power, NaNs by position, and the int32 crossings -- against the numpy mirror
+frames.bands_of_rows, whose probes tests/test_f32_bands_cpu.py works out by hand and whose order it pins: the noise rows, the
+wide-range rows and the aimed fractions of that file are the data here, so a kernel that sums in another order or finds a
+crossing by a running sum fails.
+
+The kernel's ownership (csrc/bands_f32.hip): in round r thread t holds the four bins 1024 r + 4 t .. + 3; the 256 bins of a
+wave in one round are a tile, node 4 r + wave of tree level 8; a band's first and last tile are summed under its mask, the
+tiles between them once for all bands.  The bands below start and end on both sides of every power of two (quad, lane
+group, tile, wave-round and half-row boundaries) and inside a quad."""
+import ctypes
+
+import numpy as np
+import pytest
+
+import offset_cases as oc
+from conftest import N, load_golden
+from gpu_support import ch, to_device, torch_mod  # noqa: F401 (fixtures)
+from native import Lds, gpu_helper
+from test_f32_bands_cpu import AIMED_BAND, FRAC_MAX, ORDER_BANDS, aimed_fractions, noise_rows, same_bits, wide_rows
+from test_gpu_f32_peaks import _inputs, _tones
+
+pytestmark = pytest.mark.gpu
+
+SA_OK, SA_EINVAL, SA_ESHAPE = 0, -1, -2
+FIELDS = (None, "peak", "power")
+OBW = (0.005, 0.995)
+SIXTEEN = [(137 * j, min(137 * j + 1 + 997 * j, N)) for j in range(16)]       # widths from 1 bin to 14 thousand, overlapping
+
+
+def _records(pts, field):
+    """``pts`` float32 [R, N] in the layout of ``field``: itself, or records whose other float is a NaN"""
+    if field is None:
+        return pts
+    rec = np.full(pts.shape + (2,), np.nan, np.float32)
+    rec[..., 0 if field == "peak" else 1] = pts
+    return rec
+
+
+def _run(ch, torch, x, bands, fracs=(), **kw):
+    """band_power on the device tensor -> (power float64 [R, nb], cross int32 [R, nb, nq] or None) on the host"""
+    power, cross = ch.band_power(x, bands, fracs, **kw)
+    assert power.dtype == torch.float64 and tuple(power.shape) == (x.shape[0], len(bands)) and power.is_contiguous()
+    if len(fracs) == 0:
+        assert cross is None
+        return power.cpu().numpy(), None
+    assert cross.dtype == torch.int32 and tuple(cross.shape) == (x.shape[0], len(bands), len(fracs)) and cross.is_contiguous()
+    return power.cpu().numpy(), cross.cpu().numpy()
+
+
+def _same(got, pts, bands, fracs, field, tag):
+    """the device's result against the mirror's on the same points: bit for bit"""
+    from fpga_real_time_fft_analyzer_amd import frames
+    want_p, want_c = frames.bands_of_rows(_records(pts, field), bands, fracs, field=field)
+    assert same_bits(got[0], want_p), (tag, "power", np.argwhere(got[0].view(np.uint64) != want_p.view(np.uint64))[:5].tolist())
+    if len(fracs):
+        assert np.array_equal(got[1], want_c), (tag, "cross", np.argwhere(got[1] != want_c)[:5].tolist(),
+                                                got[1][got[1] != want_c][:5], want_c[got[1] != want_c][:5])
+    return want_p, want_c
+
+
+def _check(ch, torch, x, pts, bands, fracs, field, tag):
+    return _same(_run(ch, torch, x, bands, fracs, field=field), pts, bands, fracs, field, tag)
+
+
+@pytest.mark.parametrize("field", FIELDS)
+def test_band_edges_equal_the_mirror(ch, torch_mod, field):
+    """rows = 5, nq = 2: for every k in 0..14 the bands (2^k - 1, 2^k + 1), (0, 2^k) and (2^k, 16384); bands inside and across
+    a quad, a tile and a wave; 64 random bands, overlapping and repeated ones among them."""
+    pts = wide_rows()[:5]
+    x = to_device(torch_mod, _records(pts, field))
+    for name, bands in (("across", [(2 ** k - 1, 2 ** k + 1) for k in range(15)]), ("below", [(0, 2 ** k) for k in range(15)]),
+                        ("above", [(2 ** k, N) for k in range(14)] + [(N - 1, N)])):
+        assert name != "across" or bands[14] == (N - 1, N + 1)
+        if name == "across":
+            bands[14] = (N - 1, N)                                    # 2^14 + 1 is beyond the row: the last bin alone
+        _check(ch, torch_mod, x, pts, bands, OBW, field, (field, name))
+    inside = [(0, N), (0, 1), (N - 1, N), (5, 7), (3, 5), (255, 257), (256, 512)]
+    _check(ch, torch_mod, x, pts, inside, OBW, field, (field, "inside"))
+    rng = np.random.default_rng(2210)
+    los = rng.integers(0, N, size=64)
+    his = np.minimum(los + 1 + (rng.integers(0, N, size=64) >> rng.integers(0, 14, size=64)), N)
+    rand = [(int(a), int(b)) for a, b in zip(los, his)]
+    rand[5], rand[21], rand[40] = rand[4], rand[4], (rand[39][0], rand[39][1])       # repeated bands
+    for i in range(0, 64, 16):
+        _check(ch, torch_mod, x, pts, rand[i:i + 16], OBW, field, (field, "random", i))
+
+
+def test_the_order_of_the_tree_and_of_the_descent(ch, torch_mod):
+    """The 64 noise rows and the wide-range rows of the CPU file, one call each, and the aimed fractions as 64 calls of one
+    row: the inputs on which a sequential sum differs from the tree in every row and band, and a running-sum crossing from
+    the descent in most rows."""
+    fracs = (0.005, 0.5, 0.995, 0.25)
+    for name, pts in (("noise", noise_rows()), ("wide", wide_rows())):
+        for field in (None, "power"):
+            _check(ch, torch_mod, to_device(torch_mod, _records(pts, field)), pts, ORDER_BANDS, fracs, field, (name, field))
+    pts = noise_rows()
+    x = to_device(torch_mod, pts)
+    aimed, bins = aimed_fractions()
+    near = 0
+    for r in range(64):
+        _, c = _check(ch, torch_mod, x[r:r + 1], pts[r:r + 1], [AIMED_BAND], (float(aimed[r]),), None, ("aimed", r))
+        near += abs(int(c[0, 0, 0]) - int(bins[r])) <= 1
+    assert near == 64
+
+
+def test_counts_of_bands_and_fractions(ch, torch_mod):
+    """nb = 1 and 16; nq = 0 returns no crossings and leaves a sentinel-filled `cross` untouched; nq = 4, unsorted fractions
+    with 0 and the largest allowed among them."""
+    torch = torch_mod
+    pts = wide_rows()[:3]
+    x = to_device(torch, pts)
+    sixteen = SIXTEEN
+    assert all(0 <= lo < hi <= N for lo, hi in sixteen)
+    for bands in ([(100, 16000)], sixteen):
+        for fracs in ((), (0.5,), (FRAC_MAX, 0.0, 0.995, 0.005)):
+            _check(ch, torch, x, pts, bands, fracs, None, (len(bands), fracs))
+    cross = torch.full((3, 16, 4), -77, dtype=torch.int32, device="cuda")
+    power, none = ch.band_power(x, sixteen, (), cross=cross)
+    assert none is None and (cross == -77).all().item()
+    _same((power.cpu().numpy(), None), pts, sixteen, (), None, "nq 0 with a cross tensor")
+    mine_p = torch.zeros((3, 16), dtype=torch.float64, device="cuda")
+    mine_c = torch.zeros((3, 16, 2), dtype=torch.int32, device="cuda")
+    p, c = ch.band_power(x, sixteen, OBW, power=mine_p, cross=mine_c)
+    assert p.data_ptr() == mine_p.data_ptr() and c.data_ptr() == mine_c.data_ptr()
+    _same((mine_p.cpu().numpy(), mine_c.cpu().numpy()), pts, sixteen, OBW, None, "power=, cross=")
+    assert ch.band_power(torch.empty((0, N), dtype=torch.float32, device="cuda"), [(0, 5)], (0.5,))[1].shape == (0, 1, 1)
+
+
+@pytest.mark.parametrize("field", FIELDS)
+def test_specials_in_wide_rows_and_rows_between_nan_rows(ch, torch_mod, field):
+    """R = 7: NaN rows around and between the data rows, an all-inf row; -0.0, float32 denormals, +inf and a NaN inside and
+    outside the bands of the data rows; the data rows equal their calls of one row and of three."""
+    wide = wide_rows()
+    nan_row, inf_row = np.full((1, N), np.nan, np.float32), np.full((1, N), np.inf, np.float32)
+    pts = np.concatenate([nan_row, wide[:1], nan_row, wide[1:2], inf_row, wide[2:3], nan_row])
+    pts[1, 4000] = np.nan                                             # inside (3000, 9000), outside the others
+    pts[1, 12000] = -np.inf
+    pts[3, 100:400] = 1e-45                                           # denormals: a band of them alone, and among others
+    pts[3, 5000] = -0.0
+    pts[5, 1::2] *= -1.0
+    pts[5, 700:900] = 0.0                                             # an all-zero band
+    bands = [(0, N), (3000, 9000), (9000, 16384), (100, 400), (90, 410), (700, 900), (650, 950), (11999, 12001), (4001, 12000)]
+    fracs = (0.0, 0.5, 0.995)
+    x = to_device(torch_mod, _records(pts, field))
+    want_p, want_c = _check(ch, torch_mod, x, pts, bands, fracs, field, field)
+    assert np.isnan(want_p[[0, 2, 6]]).all() and (want_c[[0, 2, 6]] == -1).all() and np.isinf(want_p[4]).all()
+    assert np.isnan(want_p[1, 1]) and np.isinf(want_p[1, 2]) and np.isfinite(want_p[1, 8]) and (want_c[1, 1] == -1).all()
+    assert want_p[3, 3] == 300 * (2.0 ** -149 if field == "power" else 2.0 ** -298) and want_c[3, 3].tolist() == [100, 249, 398]
+    assert want_p[5, 5] == 0.0 and want_c[5, 5].tolist() == [700] * 3
+    for r in (1, 3, 5):
+        one = _run(ch, torch_mod, x[r:r + 1], bands, fracs, field=field)
+        assert same_bits(one[0], want_p[r:r + 1]) and np.array_equal(one[1], want_c[r:r + 1]), (field, r)
+    three = _run(ch, torch_mod, x[2:5], bands, fracs, field=field)
+    assert same_bits(three[0], want_p[2:5]) and np.array_equal(three[1], want_c[2:5]), field
+
+
+def _c_bands(values):
+    from fpga_real_time_fft_analyzer_amd import abi
+    return (abi.Band * len(values))(*(abi.Band(lo, hi) for lo, hi in values))
+
+
+def _c_fracs(values):
+    return (ctypes.c_double * len(values))(*values) if len(values) else None
+
+
+def test_exactly_the_output_bytes_are_written_and_a_refused_call_writes_nothing(ch, torch_mod):
+    from fpga_real_time_fft_analyzer_amd import abi
+    from fpga_real_time_fft_analyzer_amd.abi import SpecanError
+    torch = torch_mod
+    L = abi.bands_lib()
+    stream = torch.cuda.current_stream().cuda_stream
+    pts = wide_rows()[:3]
+    R, guard = 3, 4096
+    x = to_device(torch, pts)
+    for bands, fracs in (([(0, N)], ()), ([(5, 9), (100, 16000), (256, 512)], OBW), ([(j, N - j) for j in range(16)], (0.1, 0.2, 0.3, 0.4))):
+        nb, nq = len(bands), len(fracs)
+        n_p, n_c = R * nb * 8, R * nb * nq * 4
+        power = torch.full((guard + n_p + guard,), 0xFF, dtype=torch.uint8, device="cuda")
+        cross = torch.full((guard + n_c + guard,), 0xFF, dtype=torch.uint8, device="cuda")
+        rc = L.sa_bands_f32(x.data_ptr(), 0, power.data_ptr() + guard, cross.data_ptr() + guard, R, nb, _c_bands(bands), nq,
+                            _c_fracs(fracs), stream)
+        assert rc == SA_OK and L.sa_bands_last_error() == b""
+        torch.cuda.synchronize()
+        for t, n in ((power, n_p), (cross, n_c)):
+            assert (t[:guard] == 0xFF).all().item() and (t[guard + n:] == 0xFF).all().item()
+        got_p = power[guard:guard + n_p].cpu().numpy().view(np.float64).reshape(R, nb)
+        got_c = cross[guard:guard + n_c].cpu().numpy().view(np.int32).reshape(R, nb, nq)
+        assert not np.isnan(got_p).any()                            # every double was written: 0xFF bytes are a NaN
+        assert nq == 0 or (got_c >= 0).all()                        # every bin was written: 0xFF bytes are -1
+        _same((got_p, got_c), pts, bands, fracs, None, ("C call", nb, nq))
+    # refused calls: the code of sa_bands_check for the same arguments, its text, and nothing written
+    bands, fracs = [(0, N), (5, 9)], (0.5,)
+    power = torch.full((R * 2 * 8 + guard,), 0xFF, dtype=torch.uint8, device="cuda")
+    cross = torch.full((R * 2 * 4 + guard,), 0xFF, dtype=torch.uint8, device="cuda")
+    flat = torch.zeros((R * N + 64,), dtype=torch.float32, device="cuda")
+    before = flat.clone()
+    p_in, p_pw, p_cr = flat.data_ptr(), power.data_ptr(), cross.data_ptr()
+    for tag, args, code, words in (
+            ("in 4 bytes off", (p_in + 4, 0, p_pw, p_cr, R, bands, fracs), SA_EINVAL, "`in` must be 16-byte aligned"),
+            ("power 4 bytes off", (p_in, 0, p_pw + 4, p_cr, R, bands, fracs), SA_EINVAL, "`power` must be 8-byte aligned"),
+            ("cross 2 bytes off", (p_in, 0, p_pw, p_cr + 2, R, bands, fracs), SA_EINVAL, "`cross` must be 4-byte aligned"),
+            ("power inside in", (p_in, 0, p_in + R * N * 4 - 8, p_cr, R, bands, fracs), SA_EINVAL, "`in` and `power` overlap"),
+            ("records read twice as much", (p_in, 2, p_in + R * N * 4, p_cr, R, bands, fracs), SA_EINVAL, "`in` and `power` overlap"),
+            ("cross inside in", (p_in, 0, p_pw, p_in + 64, R, bands, fracs), SA_EINVAL, "`in` and `cross` overlap"),
+            ("cross inside power", (p_in, 0, p_pw, p_pw + 8, R, bands, fracs), SA_EINVAL, "`power` and `cross` overlap"),
+            ("NULL power", (p_in, 0, 0, p_cr, R, bands, fracs), SA_EINVAL, "NULL"),
+            ("NULL cross", (p_in, 0, p_pw, 0, R, bands, fracs), SA_EINVAL, "NULL `cross`"),
+            ("field 3", (p_in, 3, p_pw, p_cr, R, bands, fracs), SA_EINVAL, "field"),
+            ("lo = hi", (p_in, 0, p_pw, p_cr, R, [(0, N), (9, 9)], fracs), SA_EINVAL, "bands[1] = [9, 9)"),
+            ("hi beyond the row", (p_in, 0, p_pw, p_cr, R, [(0, N + 1), (5, 9)], fracs), SA_EINVAL, "bands[0] = [0, 16385)"),
+            ("a fraction of 1", (p_in, 0, p_pw, p_cr, R, bands, (1.0,)), SA_EINVAL, "fracs[0] = 1"),
+            ("a NaN fraction", (p_in, 0, p_pw, p_cr, R, bands, (float("nan"),)), SA_EINVAL, "fracs[0]"),
+            ("negative rows", (p_in, 0, p_pw, p_cr, -1, bands, fracs), SA_ESHAPE, "negative")):
+        a_in, field, a_pw, a_cr, rows, bd, fr = args
+        assert L.sa_bands_check(field, a_in, a_pw, a_cr, rows, len(bd), _c_bands(bd), len(fr), _c_fracs(fr)) == code, tag
+        assert L.sa_bands_f32(a_in, field, a_pw, a_cr, rows, len(bd), _c_bands(bd), len(fr), _c_fracs(fr), stream) == code, tag
+        assert words in L.sa_bands_last_error().decode(), (tag, L.sa_bands_last_error())
+    for nb, nq, words in ((0, 1, "nb must"), (17, 1, "nb must"), (2, 5, "nq must"), (2, -1, "nq must")):
+        assert L.sa_bands_f32(p_in, 0, p_pw, p_cr, R, nb, _c_bands(bands), nq, _c_fracs(fracs), stream) == SA_EINVAL
+        assert words in L.sa_bands_last_error().decode()
+    assert L.sa_bands_f32(p_in, 0, p_pw, p_cr, R, 2, None, 1, _c_fracs(fracs), stream) == SA_EINVAL and b"NULL bands" in L.sa_bands_last_error()
+    assert L.sa_bands_f32(p_in, 0, p_pw, p_cr, R, 2, _c_bands(bands), 1, None, stream) == SA_EINVAL and b"NULL fracs" in L.sa_bands_last_error()
+    torch.cuda.synchronize()
+    assert (power == 0xFF).all().item() and (cross == 0xFF).all().item() and torch.equal(flat, before)
+    assert L.sa_bands_f32(0, 0, 0, 0, 0, 2, _c_bands(bands), 1, _c_fracs(fracs), stream) == SA_OK and L.sa_bands_last_error() == b""
+    # the three buffers touching: `power` right behind `in`, `cross` right behind `power`
+    n_in, n_p, n_c = R * N * 4, R * 2 * 8, R * 2 * 4
+    packed = torch.zeros((n_in + n_p + n_c,), dtype=torch.uint8, device="cuda")
+    packed[:n_in] = x.view(torch.uint8).view(-1)
+    base = packed.data_ptr()
+    assert L.sa_bands_f32(base, 0, base + n_in, base + n_in + n_p, R, 2, _c_bands(bands), 1, _c_fracs(fracs), stream) == SA_OK
+    torch.cuda.synchronize()
+    host = packed[n_in:].cpu().numpy()
+    _same((host[:n_p].view(np.float64).reshape(R, 2), host[n_p:].view(np.int32).reshape(R, 2, 1)), pts, bands, fracs, None, "touching")
+    # through the wrapper: shapes and dtypes before any device call
+    for code, args, kw in ((SA_ESHAPE, (x[:, :N // 2], bands), {}), (SA_EINVAL, (x.double(), bands), {}),
+                           (SA_ESHAPE, (x, bands), dict(field="peak")),
+                           (SA_ESHAPE, (x, bands), dict(power=torch.empty((R, 3), dtype=torch.float64, device="cuda"))),
+                           (SA_ESHAPE, (x, bands), dict(power=torch.empty((R, 2), dtype=torch.float32, device="cuda"))),
+                           (SA_ESHAPE, (x, bands), dict(power=torch.empty((R, 2), dtype=torch.float64))),
+                           (SA_ESHAPE, (x, bands, fracs), dict(cross=torch.empty((R, 2), dtype=torch.int32, device="cuda"))),
+                           (SA_ESHAPE, (x, bands, fracs), dict(cross=torch.empty((R, 2, 1), dtype=torch.int64, device="cuda"))),
+                           (SA_EINVAL, (x.cpu(), bands), {})):
+        with pytest.raises(SpecanError) as e:
+            ch.band_power(*args, **kw)
+        assert e.value.code == code, (args[0].shape, kw)
+
+
+@pytest.fixture(scope="module")
+def lds_fill(tmp_path_factory, torch_mod):
+    """tests/hip/lds_fill.hip, built and bound as tests/test_gpu_f32_rank.py does: lds_fill(word) writes `word` to all of
+    the LDS of every CU, on the current stream."""
+    return Lds(gpu_helper(tmp_path_factory.mktemp("lds_fill_bands"), "lds_fill"), torch_mod).fill
+
+
+def test_poisoned_lds(ch, torch_mod, lds_fill):
+    """lds_fill(P) with P = 0xFFFFFFFF (a NaN as either half of a double, -1 as a tile) and 0x7FF00000, then the call on the
+    same stream: the bits of the mirror.  One tile, two tiles and many, with and without crossings."""
+    pts = wide_rows()[:3]
+    sets = ([(300, 400)], [(255, 257), (0, N)], SIXTEEN)
+    for field in FIELDS:
+        x = to_device(torch_mod, _records(pts, field))
+        for word in (0xFFFFFFFF, 0x7FF00000):
+            for bands in sets:
+                for fracs in ((), (0.5, 0.0, 0.995)):
+                    lds_fill(word)
+                    _check(ch, torch_mod, x, pts, bands, fracs, field, (field, hex(word), len(bands), fracs))
+
+
+def test_capture_and_replay(ch, torch_mod):
+    """band_power captures without a warm-up -- it is one launch with its bands and fractions in the launch's arguments -- and
+    a replay after the input has changed gives the eager result of the new input; the host arrays are gone by then.  At
+    depth 1, after one warm-up call of the same batch (it allocates the cached workspace), channel_power_f32 captures too."""
+    torch = torch_mod
+    wide = wide_rows()[:3]
+    bands, fracs = [(100, 16000), (5, 9), (4096, 8192)], OBW
+    x = to_device(torch, wide)
+    power = torch.zeros((3, 3), dtype=torch.float64, device="cuda")
+    cross = torch.zeros((3, 3, 2), dtype=torch.int32, device="cuda")
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        ch.band_power(x, list(bands), tuple(fracs), power=power, cross=cross)
+    for pts in (wide[::-1] * np.float32(3.0), wide):
+        pts = np.ascontiguousarray(pts)
+        x.copy_(to_device(torch, pts))
+        power.zero_()
+        cross.zero_()
+        graph.replay()
+        torch.cuda.synchronize()
+        _same((power.cpu().numpy(), cross.cpu().numpy()), pts, bands, fracs, None, "replay")
+    # the composed call
+    ch.set_filter_mode(0xB1)
+    assert ch.overlap == 1
+    xs = [to_device(torch, _tones(4, 2250 + i, bins=(1000 + 700 * i, 3100, 6000 + 90 * i), amps=(900.0 / (1 + i), 450.0, 220.0)))
+          for i in range(2)]
+    cb = [(900, 1300), (1600, 2000), (0, N)]
+    eager = [tuple(t.cpu().numpy() for t in ch.channel_power_f32(xi, cb, OBW)) for xi in xs]
+    assert not np.array_equal(eager[0][0], eager[1][0])
+    xin = xs[0].clone()
+    p2 = torch.zeros((4, 3), dtype=torch.float64, device="cuda")
+    c2 = torch.zeros((4, 3, 2), dtype=torch.int32, device="cuda")
+    graph2 = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph2):
+        ch.channel_power_f32(xin, cb, OBW, power=p2, cross=c2)
+    for i in (1, 0):
+        xin.copy_(xs[i])
+        p2.zero_()
+        c2.zero_()
+        graph2.replay()
+        torch.cuda.synchronize()
+        assert same_bits(p2.cpu().numpy(), eager[i][0]) and np.array_equal(c2.cpu().numpy(), eager[i][1]), i
+    assert "libspecan_bands.so" in open("/proc/self/maps").read()
+
+
+def test_a_bucket_of_the_fold_is_a_band(ch, torch_mod):
+    """The band [64 c, 64 c + 64) of band_power, rounded to float32, is the power of fold_mag_f32(bucket=64) on the same
+    magnitudes, bit for bit: the tree of the fold, continued."""
+    torch = torch_mod
+    for pts in (noise_rows()[:4], wide_rows()[:4]):
+        x = to_device(torch, pts)
+        fold = ch.fold_mag_f32(x, 1, 64)[..., 1]
+        for c0 in (0, 96, 240):
+            power, _ = ch.band_power(x, [(64 * c, 64 * c + 64) for c in range(c0, c0 + 16)])
+            assert torch.equal(power.to(torch.float32).view(torch.int32), fold[:, c0:c0 + 16].contiguous().view(torch.int32)), c0
+
+
+@pytest.mark.parametrize("mode", [0xB1, 0xA1])
+def test_channel_power_f32(ch, torch_mod, mode):
+    """The composed call equals band_power on process_f32's magnitudes, and with group = 4 band_power on spectra_f32's
+    records, field 'power' -- float32, int16 and packed input; a caller's work, power and cross; refusals before any launch."""
+    from fpga_real_time_fft_analyzer_amd import frames
+    from fpga_real_time_fft_analyzer_amd.abi import SpecanError
+    torch = torch_mod
+    if mode == 0xA1:
+        ch.load_sos(load_golden("g2_config1.npz")["sos"])
+    ch.set_filter_mode(mode)
+    B = 4
+    bands = frames.channel_bands(1200, 300, 400, 2) + [(0, N)]
+    assert bands[:3] == [(1050, 1350), (650, 950), (1450, 1750)] and len(bands) == 6
+    for form, x in _inputs(torch, _tones(B, 2240 + mode)).items():
+        mag = ch.process_f32(x, out_kind="mag_full")
+        want = ch.band_power(mag, bands, OBW)
+        got = ch.channel_power_f32(x, bands, OBW)
+        assert tuple(got[0].shape) == (B, 6) and tuple(got[1].shape) == (B, 6, 2)
+        assert same_bits(got[0].cpu().numpy(), want[0].cpu().numpy()) and torch.equal(got[1], want[1]), form
+        _same((got[0].cpu().numpy(), got[1].cpu().numpy()), mag.cpu().numpy(), bands, OBW, None, form)
+        assert (got[1] >= 0).all().item() and (got[1][..., 0] <= got[1][..., 1]).all().item()
+        rec = ch.spectra_f32(x, 4)
+        want4 = ch.band_power(rec, bands, OBW, field="power")
+        got4 = ch.channel_power_f32(x, bands, OBW, group=4)
+        assert tuple(got4[0].shape) == (1, 6) and tuple(got4[1].shape) == (1, 6, 2)
+        assert same_bits(got4[0].cpu().numpy(), want4[0].cpu().numpy()) and torch.equal(got4[1], want4[1]), form
+        _same((got4[0].cpu().numpy(), got4[1].cpu().numpy()), rec.cpu().numpy()[..., 1], bands, OBW, "power", (form, "group"))
+        none = ch.channel_power_f32(x, bands)
+        assert none[1] is None and same_bits(none[0].cpu().numpy(), want[0].cpu().numpy())
+    x = _inputs(torch, _tones(B, 2240 + mode))["int16"]
+    mag = ch.process_f32(x, out_kind="mag_full")
+    want = ch.band_power(mag, bands, OBW)
+    work = torch.full((B + 1, N), 3.0, dtype=torch.float32, device="cuda")
+    power = torch.zeros((B, 6), dtype=torch.float64, device="cuda")
+    cross = torch.zeros((B, 6, 2), dtype=torch.int32, device="cuda")
+    res = ch.channel_power_f32(x, bands, OBW, work=work, power=power, cross=cross)
+    assert res[0].data_ptr() == power.data_ptr() and res[1].data_ptr() == cross.data_ptr()
+    assert torch.equal(power.view(torch.int64), want[0].view(torch.int64)) and torch.equal(cross, want[1])
+    assert torch.equal(work[:B], mag) and (work[B] == 3.0).all().item()
+    for code, args, kw in ((SA_ESHAPE, (x[:3], bands), dict(group=4)), (SA_EINVAL, (x, bands), dict(group=3)),
+                           (SA_EINVAL, (x, bands, (1.0,)), {}), (SA_EINVAL, (x, [(5, 5)]), {}),
+                           (SA_ESHAPE, (x, bands), dict(work=torch.empty((B - 1, N), dtype=torch.float32, device="cuda"))),
+                           (SA_ESHAPE, (x, bands), dict(power=torch.zeros((B, 5), dtype=torch.float64, device="cuda"))),
+                           (SA_ESHAPE, (x, bands, OBW), dict(group=4, cross=torch.zeros((B, 6, 2), dtype=torch.int32, device="cuda")))):
+        work.fill_(3.0)
+        with pytest.raises(SpecanError) as e:
+            ch.channel_power_f32(*args, **dict(dict(work=work), **kw))
+        torch.cuda.synchronize()
+        assert e.value.code == code and (work == 3.0).all().item(), kw
+
+
+@pytest.mark.parametrize("form,rows", [("mag", 65539), ("rec", 32771)])
+def test_every_row_past_4_gib(ch, torch_mod, form, rows):
+    """The input tiled from one period of 1027 rows until its last rows start beyond byte 2^32 (the batches the rules of
+    offset_cases give such rows), nb = 2, nq = 1, into outputs of 0xFF bytes: ALL rows equal the call on one period."""
+    from fpga_real_time_fft_analyzer_amd import frames
+    torch = torch_mod
+    P = oc.period(1)
+    row = (N,) if form == "mag" else (N, 2)
+    assert rows == oc.batch({"in": int(np.prod(row)) * 4}, 1) and (rows - 1) * int(np.prod(row)) * 4 >= 1 << 32
+    field = None if form == "mag" else "power"
+    gen = torch.Generator(device="cuda")
+    gen.manual_seed(2260)
+    per = 0.001 + 0.78 * torch.rand((P,) + row, device="cuda", generator=gen)
+    x = torch.empty((rows,) + row, dtype=torch.float32, device="cuda")
+    for s in range(0, rows, P):
+        n = min(P, rows - s)
+        x[s:s + n] = per[:n]
+    assert x[rows - 1:].data_ptr() - x.data_ptr() >= 1 << 32
+    bands, fracs = [(100, 16000), (8191, 8450)], (0.5,)
+    ref_p, ref_c = ch.band_power(x[:P], bands, fracs, field=field)
+    refs = [oc.as_rows(torch, ref_p, P).clone(), oc.as_rows(torch, ref_c, P).clone()]
+    assert oc.vacuous(torch, refs[0], ref_p) is None
+    assert bool((ref_c >= 0).all()) and torch.unique(ref_c[:, 0, 0]).numel() > 8
+    want_p, want_c = frames.bands_of_rows(per[:3].cpu().numpy(), bands, fracs, field=field)
+    assert same_bits(ref_p[:3].cpu().numpy(), want_p) and np.array_equal(ref_c[:3].cpu().numpy(), want_c)
+    power = torch.full((rows * 2 * 8,), 0xFF, dtype=torch.uint8, device="cuda").view(torch.float64).view(rows, 2)
+    cross = torch.full((rows * 2 * 4,), 0xFF, dtype=torch.uint8, device="cuda").view(torch.int32).view(rows, 2, 1)
+    got = ch.band_power(x, bands, fracs, field=field, power=power, cross=cross)
+    for t, want in zip(got, refs):
+        bad = oc.tiled_mismatch(torch, oc.as_rows(torch, t, rows), want)
+        assert bad is None, (form, tuple(t.shape), bad)
+    torch.cuda.synchronize()
+    del x, power, cross, got
+    torch.cuda.empty_cache()
