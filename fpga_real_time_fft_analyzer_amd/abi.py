@@ -1,7 +1,7 @@
 """ctypes binding of ``libspecan_hip.so`` (the C ABI declared in ``include/specan.h`` and ``include/specan_ext.h``) and of
 ``libspecan_fold.so`` (``include/specan_fold.h``), ``libspecan_peaks.so`` (``include/specan_peaks.h``),
-``libspecan_rank.so`` (``include/specan_rank.h``), ``libspecan_hist.so`` (``include/specan_hist.h``) and
-``libspecan_bands.so`` (``include/specan_bands.h``).
+``libspecan_rank.so`` (``include/specan_rank.h``), ``libspecan_hist.so`` (``include/specan_hist.h``),
+``libspecan_bands.so`` (``include/specan_bands.h``) and ``libspecan_mask.so`` (``include/specan_mask.h``).
 
 This is the only place the shared libraries are loaded.  There is no CPU fallback: if the
 library is missing the import of any compute entry point raises, and creating a handle
@@ -20,6 +20,7 @@ PEAKS_LIB_PATH = os.path.join(_PKG, "libspecan_peaks.so")    # include/specan_pe
 RANK_LIB_PATH = os.path.join(_PKG, "libspecan_rank.so")      # include/specan_rank.h: built by the same make
 HIST_LIB_PATH = os.path.join(_PKG, "libspecan_hist.so")      # include/specan_hist.h: built by the same make
 BANDS_LIB_PATH = os.path.join(_PKG, "libspecan_bands.so")    # include/specan_bands.h: built by the same make
+MASK_LIB_PATH = os.path.join(_PKG, "libspecan_mask.so")      # include/specan_mask.h: built by the same make
 CSRC = os.path.join(_PKG, "csrc")
 
 # error codes / constants (include/specan.h)
@@ -84,8 +85,9 @@ class SpecanError(RuntimeError):
 
 
 def build(verbose: bool = False) -> str:
-    """Compile the HIP extension in-tree for gfx950 (hipcc cross-compiles without a GPU): the six libraries, LIB_PATH,
-    FOLD_LIB_PATH, PEAKS_LIB_PATH, RANK_LIB_PATH, HIST_LIB_PATH and BANDS_LIB_PATH, are the Makefile's first target."""
+    """Compile the HIP extension in-tree for gfx950 (hipcc cross-compiles without a GPU): the seven libraries, LIB_PATH,
+    FOLD_LIB_PATH, PEAKS_LIB_PATH, RANK_LIB_PATH, HIST_LIB_PATH, BANDS_LIB_PATH and MASK_LIB_PATH, are the Makefile's first
+    target."""
     cmd = ["make", "-j4", "-C", CSRC]
     if not verbose:
         cmd.insert(1, "-s")
@@ -229,12 +231,34 @@ BANDS_SIGNATURES = {
     "sa_bands_last_error": (C.c_char_p, []),
 }
 
+
+
+class MaskRow(C.Structure):
+    """sa_mask_row of include/specan_mask.h: the record of one row, 40 bytes."""
+    _fields_ = [("over", C.c_int32), ("under", C.c_int32), ("first", C.c_int32), ("last", C.c_int32), ("up_bin", C.c_int32),
+                ("lo_bin", C.c_int32), ("up_val", C.c_float), ("up_lim", C.c_float), ("lo_val", C.c_float), ("lo_lim", C.c_float)]
+
+
+# the entry points of include/specan_mask.h: libspecan_mask.so, the seventh product library, again without a handle (each row
+# of 16384 points against an upper and a lower limit line: the bins outside counted, the worst bin of either limit, and the
+# rows that failed), bound by mask_lib() and held name for name against that header (tests/test_f32_mask_cpu.py); no name is
+# in the tables above
+SA_MASK_VERSION = 1
+SA_MASK_IN_MAG, SA_MASK_IN_POINT_PEAK, SA_MASK_IN_POINT_POWER = 0, 1, 2
+MASK_SIGNATURES = {
+    "sa_mask_version": (_INT, []),
+    "sa_mask_f32": (_INT, [C.c_void_p, _INT, C.c_void_p, C.c_void_p, _INT, _INT, C.c_void_p, C.c_void_p, _INT, C.c_void_p]),
+    "sa_mask_check": (_INT, [C.c_uint64, _INT, C.c_uint64, C.c_uint64, _INT, _INT, C.c_uint64, C.c_uint64, _INT]),
+    "sa_mask_last_error": (C.c_char_p, []),
+}
+
 _lib = None
 _fold_lib = None
 _peaks_lib = None
 _rank_lib = None
 _hist_lib = None
 _bands_lib = None
+_mask_lib = None
 
 
 def _load(path: str, tables: tuple) -> C.CDLL:
@@ -305,3 +329,11 @@ def bands_lib() -> C.CDLL:
     if _bands_lib is None:
         _bands_lib = _load(BANDS_LIB_PATH, (BANDS_SIGNATURES,))
     return _bands_lib
+
+
+def mask_lib() -> C.CDLL:
+    """Load libspecan_mask.so (include/specan_mask.h), after torch as lib() does; raise loudly when it has not been built."""
+    global _mask_lib
+    if _mask_lib is None:
+        _mask_lib = _load(MASK_LIB_PATH, (MASK_SIGNATURES,))
+    return _mask_lib

@@ -136,6 +136,8 @@ _PEAK_FIELDS = {None: abi.SA_PEAKS_IN_MAG, "peak": abi.SA_PEAKS_IN_POINT_PEAK, "
 _RANK_FIELDS = {None: abi.SA_RANK_IN_MAG, "peak": abi.SA_RANK_IN_POINT_PEAK, "power": abi.SA_RANK_IN_POINT_POWER}
 # band_power(field=...) -> the `field` of include/specan_bands.h: the same three layouts
 _BANDS_FIELDS = {None: abi.SA_BANDS_IN_MAG, "peak": abi.SA_BANDS_IN_POINT_PEAK, "power": abi.SA_BANDS_IN_POINT_POWER}
+# mask_test(field=...) -> the `field` of include/specan_mask.h: the same three layouts
+_MASK_FIELDS = {None: abi.SA_MASK_IN_MAG, "peak": abi.SA_MASK_IN_POINT_PEAK, "power": abi.SA_MASK_IN_POINT_POWER}
 
 
 def output_spec(chain: _Chain, out_kind: Optional[str], B: int) -> tuple:
@@ -1061,6 +1063,123 @@ class SpectrumChain:
             return self.band_power(rec, bands, fracs, field="power", power=power, cross=cross)
         power, cross = self._bands_out(B, len(bands), len(fracs), power, cross)
         return self.band_power(self._mag_full_in_work(x, B, scale, work), bands, fracs, power=power, cross=cross)
+
+    @staticmethod
+    def _mask_args(upper, lower, lo, hi, field) -> int:
+        """The one validation of the scalar arguments of the mask test: the ``field`` code of include/specan_mask.h, or
+        SA_EINVAL.  The limits are only counted here; :meth:`_mask_limits` looks at them."""
+        for name, v in (("lo", lo), ("hi", hi)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise SpecanError(abi.SA_EINVAL, f"{name} must be an int")
+        if not 0 <= int(lo) < int(hi) <= SA_N:
+            raise SpecanError(abi.SA_EINVAL, f"the range must be 0 <= lo < hi <= {SA_N}")
+        if not (field is None or isinstance(field, str)) or field not in _MASK_FIELDS:
+            raise SpecanError(abi.SA_EINVAL, "field must be None, 'peak' or 'power'")
+        if upper is None and lower is None:
+            raise SpecanError(abi.SA_EINVAL, "upper and lower are both None: no limit at all")
+        return _MASK_FIELDS[field]
+
+    def _mask_limits(self, upper, lower) -> None:
+        """SA_ESHAPE where a limit is neither None nor a contiguous float32 [16384] tensor on the handle's device."""
+        for name, v in (("upper", upper), ("lower", lower)):
+            if v is not None and (not isinstance(v, torch.Tensor) or v.dtype != torch.float32 or tuple(v.shape) != (SA_N,)
+                                  or v.device != self.device or not v.is_contiguous()):
+                raise SpecanError(abi.SA_ESHAPE, f"{name} must be None or a contiguous torch.float32 tensor of shape ({SA_N},)")
+
+    def _mask_out(self, R: int, out: Optional[torch.Tensor], summary) -> tuple:
+        """``(out, summary)`` of the mask test of ``R`` rows: ``out`` allocated when None, ``summary`` allocated when True and
+        None when False or None: SA_ESHAPE where ``out`` is not the contiguous int32 [R, 10] tensor or a given ``summary`` not
+        the contiguous int32 [4] tensor on the handle's device."""
+        for name, t, shape in (("out", out, (R, 10)), ("summary", summary, (4,))):
+            if t is None or isinstance(t, bool):
+                continue
+            if (not isinstance(t, torch.Tensor) or tuple(t.shape) != shape or t.dtype != torch.int32 or t.device != self.device
+                    or not t.is_contiguous()):
+                raise SpecanError(abi.SA_ESHAPE, f"{name} must be a contiguous torch.int32 tensor of shape {shape}")
+        if out is None:
+            out = torch.empty((R, 10), dtype=torch.int32, device=self.device)
+        if summary is True:
+            summary = torch.empty((4,), dtype=torch.int32, device=self.device)
+        return out, (None if summary is False else summary)
+
+    def mask_test(self, t: torch.Tensor, upper: Optional[torch.Tensor], lower: Optional[torch.Tensor] = None, lo: int = 0,
+                  hi: int = SA_N, field: Optional[str] = None, out: Optional[torch.Tensor] = None, summary=False) -> tuple:
+        """The spectral mask test of each row of ``t`` (include/specan_mask.h, sa_mask_f32): ``(ints int32 [R, 6], floats
+        float32 [R, 4], summary int32 [4] or None)``.  ``ints[r]`` is (over, under, first, last, up_bin, lo_bin) and
+        ``floats[r]`` (up_val, up_lim, lo_val, lo_lim) of row r, both views of the [R, 10] int32 record tensor (``out``,
+        allocated when None; one sa_mask_row per row, frames.MASK_ROW on the host).  ``t`` is a float32 [R,16384] device
+        tensor -- what ``process_f32(out_kind='mag_full')`` or ``process_q15(out_kind='mag')`` wrote -- or, with
+        ``field='peak'`` or ``field='power'``, float32 [R,16384,2], the records of :meth:`fold_mag_f32` at bucket 1,
+        :meth:`spectra_f32` or :meth:`spectra_q15`, of which that float is the point.  Nothing is squared: the limits are in
+        the unit of the points, powers for ``field='power'``.
+
+        ``upper`` and ``lower`` are float32 [16384] device tensors shared by all rows, or None (not both; the same tensor may
+        be both); bin i has that limit where the value is finite and above 0 and ``lo <= i < hi`` -- 0, a negative value,
+        an infinity or a NaN leaves a gap.  ``over`` counts the limited bins where the point, its sign cleared, is above the
+        upper limit or a NaN, ``under`` those below the lower limit or a NaN; ``first`` and ``last`` are the lowest and
+        highest such bin or -1.  ``up_bin`` is the bin whose point / limit is largest and ``lo_bin`` the one where it is
+        smallest, by the exact ratio of the two float32 values, equal ratios to the lowest bin; the floats are the point and
+        the limit there (frames.mask_margin_db turns them into dB), -1 and +0.0 without a limited bin.  ``summary=True`` (or
+        an int32 [4] tensor to write into) adds the trigger: the rows with over > 0, the rows with under > 0, the first row
+        with either or -1 and the last.  frames.mask_of_rows is the numpy mirror, bit for bit.
+
+        ``lo`` and ``hi`` take ints only (a bool or a float is SA_EINVAL); a wrong dtype of ``t`` is SA_EINVAL and a wrong
+        shape SA_ESHAPE, all before any device call.  One launch on the current stream of the handle's device, and one more
+        of a single workgroup for the summary -- no atomics, nothing zeroed, no handle state, no workspace: it captures into a
+        graph at any time and every replay gives the summary of its own input.  Where ``t`` is the result of a call made in
+        overlap mode, call :meth:`flush` first.  Pointer contract (checked by the C entry point, SA_EINVAL): ``t`` and the
+        limits are 16-byte aligned, and the bytes read, the R * 40 bytes of the records and the 16 of the summary are
+        pairwise disjoint; buffers that merely touch are fine."""
+        code = self._mask_args(upper, lower, lo, hi, field)
+        R = self._check_in(t, torch.float32, (SA_N, 2) if code else SA_N)
+        self._mask_limits(upper, lower)
+        out, summary = self._mask_out(R, out, summary)
+        L = abi.mask_lib()
+        with torch.cuda.device(self.device):         # the C call launches on the calling thread's current device
+            rc = L.sa_mask_f32(t.data_ptr(), code, None if upper is None else upper.data_ptr(),
+                               None if lower is None else lower.data_ptr(), int(lo), int(hi), out.data_ptr(),
+                               None if summary is None else summary.data_ptr(), R, self._stream())
+        if rc != abi.SA_OK:
+            raise SpecanError(rc, L.sa_mask_last_error().decode())
+        return out[:, :6], out.view(torch.float32)[:, 6:], summary
+
+    def mask_trigger_f32(self, x: torch.Tensor, upper: Optional[torch.Tensor], lower: Optional[torch.Tensor] = None, lo: int = 0,
+                         hi: int = SA_N, group: Optional[int] = None, scale: float = 1.0 / 2048.0,
+                         work: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+                         summary: Optional[torch.Tensor] = None) -> tuple:
+        """The frequency-mask trigger on the float chain's spectra, without the spectra leaving the device: ``(ints int32
+        [R, 6], floats float32 [R, 4], summary int32 [4])`` as :meth:`mask_test` returns them with the summary -- which rows
+        left the mask, the first and last of them, and every row's worst bins.  ``x`` is float32, int16 or packed uint8
+        exactly as for :meth:`process_f32`; every filter mode and both precisions apply.
+
+        Without ``group`` (R = B) the call is ``process_f32(x, out_kind='mag_full', scale=scale)`` into the workspace of
+        :meth:`spectra_f32` followed by :meth:`mask_test`: every frame's magnitudes against limits in amplitude.  With
+        ``group=A`` (2, 4, ..., 128; R = B // A) it is ``spectra_f32(x, group=A, scale=scale, work=work)`` followed by
+        ``mask_test(..., field='power')``: the summed power of every A consecutive frames, the Welch estimate times A,
+        against limits in that unit.
+
+        The workspace is ``work`` or the cached tensor, as for :meth:`spectra_f32`, and in overlap mode the call joins every
+        outstanding call of the handle on the device (as :meth:`flush` does) before the test: the result is valid on the
+        current stream when the call returns, and the call lends nothing.  The limits, the range, ``out`` and ``summary``
+        (a tensor to write into, allocated when None) are refused as by :meth:`mask_test`, ``group`` and a B that is no
+        multiple of it as by :meth:`spectra_f32`, all before anything is launched, and so is a wrong ``work``."""
+        self._mask_args(upper, lower, lo, hi, None)
+        if group is not None:
+            self._log2_fold(group, 1)
+        forms = FLOAT_CHAIN.inputs
+        dtype = x.dtype if isinstance(x, torch.Tensor) and x.dtype in forms else next(iter(forms))
+        B = self._check_in(x, dtype, forms[dtype][0])
+        self._mask_limits(upper, lower)
+        if isinstance(summary, bool):
+            raise SpecanError(abi.SA_ESHAPE, "summary must be None or a contiguous torch.int32 tensor of shape (4,)")
+        if group is not None:
+            if B % int(group):
+                raise SpecanError(abi.SA_ESHAPE, f"the batch ({B} frames) must be a multiple of {int(group)}")
+            out, summary = self._mask_out(B // int(group), out, True if summary is None else summary)      # before the chain
+            rec = self.spectra_f32(x, group, 1, scale=scale, work=work)
+            return self.mask_test(rec, upper, lower, lo, hi, field="power", out=out, summary=summary)
+        out, summary = self._mask_out(B, out, True if summary is None else summary)
+        return self.mask_test(self._mag_full_in_work(x, B, scale, work), upper, lower, lo, hi, out=out, summary=summary)
 
     def filter_q15(self, x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Window (+ integer IIR) only: the FFT input stream, [B,16384] int16.  ``x`` is [B,16384] int16 or the same

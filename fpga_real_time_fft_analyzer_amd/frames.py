@@ -439,6 +439,200 @@ def channel_bands(center: int, width: int, spacing: int, adjacent: int = 1) -> l
     return out
 
 
+# sa_mask_row of include/specan_mask.h, 40 bytes
+MASK_ROW = np.dtype([("over", "<i4"), ("under", "<i4"), ("first", "<i4"), ("last", "<i4"), ("up_bin", "<i4"), ("lo_bin", "<i4"),
+                     ("up_val", "<f4"), ("up_lim", "<f4"), ("lo_val", "<f4"), ("lo_lim", "<f4")])
+_MASK_UNITS = {"amplitude": 20.0, "power": 10.0}       # dB = 20 log10 of a ratio of amplitudes, 10 log10 of one of powers
+
+
+def _mask_args(upper, lower, lo, hi, field) -> tuple:
+    """``(upper, lower, lo, hi)`` of the mask test, each limit None or a C-contiguous float32 [16384] array, or ValueError:
+    not both limits None, ``0 <= lo < hi <= 16384`` as ints (no bool, no float), ``field`` None, 'peak' or 'power'."""
+    for name, v in (("lo", lo), ("hi", hi)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f"{name} must be an int")
+    lo, hi = int(lo), int(hi)
+    if not 0 <= lo < hi <= FFT_SIZE:
+        raise ValueError("the range must be 0 <= lo < hi <= 16384")
+    if not (field is None or isinstance(field, str)) or field not in RANK_FIELDS:
+        raise ValueError("field must be None, 'peak' or 'power'")
+    if upper is None and lower is None:
+        raise ValueError("upper and lower are both None: no limit at all")
+    limits = []
+    for name, v in (("upper", upper), ("lower", lower)):
+        if v is not None:
+            if not isinstance(v, np.ndarray) or v.dtype != np.float32 or v.shape != (FFT_SIZE,):
+                raise ValueError(f"{name} must be None or a float32 [16384] array")
+            v = np.ascontiguousarray(v)
+        limits.append(v)
+    return limits[0], limits[1], lo, hi
+
+
+def _mask_worst(key, lim, has, up: bool) -> np.ndarray:
+    """The bin, or -1, of each row of ``key`` float64 [R, m] that has a limit (``has`` bool [m], ``lim`` float64 [m]) and comes
+    first in the order of include/specan_mask.h: the larger (``up``) or smaller key / lim, equal ratios to the lowest bin.  A
+    knock-out over adjacent pairs; ``k_i l_j > k_j l_i`` is exact in float64 for values that were float32, and the order is
+    total, so the pairing does not matter."""
+    R, m = key.shape
+    size = 1 << max(m - 1, 0).bit_length()
+    k = np.zeros((R, size), np.float64)
+    l = np.ones((R, size), np.float64)
+    b = np.full((R, size), -1, np.int64)
+    k[:, :m] = np.where(has, key, 0.0)
+    l[:, :m] = np.where(has, lim, 1.0)
+    b[:, :m] = np.where(has, np.arange(m), -1)
+    while size > 1:
+        kx, ky, lx, ly, bx, by = k[:, 0::2], k[:, 1::2], l[:, 0::2], l[:, 1::2], b[:, 0::2], b[:, 1::2]
+        cx, cy = kx * ly, ky * lx                     # keys in [0, +inf], limits finite and above 0: no NaN
+        first = ((cx > cy) if up else (cx < cy)) | ((cx == cy) & (bx < by))
+        take_x = (by < 0) | ((bx >= 0) & first)
+        k, l, b = np.where(take_x, kx, ky), np.where(take_x, lx, ly), np.where(take_x, bx, by)
+        size //= 2
+    return b[:, 0]
+
+
+def mask_of_rows(points, upper, lower=None, lo: int = 0, hi: int = FFT_SIZE, field=None):
+    """The mask test of float32 ``points`` [R,16384] -- or, with ``field`` 'peak' or 'power', of that float of the records
+    [R,16384,2] -- against the limit lines ``upper`` and ``lower``, float32 [16384] or None (not both), over the bins [lo, hi):
+    ``(records, summary)``, a structured array [R] of dtype MASK_ROW (sa_mask_row) and int32 [4].  The numpy mirror of
+    sa_mask_f32 (include/specan_mask.h), exact:
+
+    - ``a`` is the point with its sign bit cleared; nothing is squared.  Bin i has an upper (lower) limit where ``upper[i]``
+      (``lower[i]``) is finite and above 0 and ``lo <= i < hi``; any other value leaves a gap;
+    - ``over`` counts the bins with an upper limit where ``a > upper`` or a is a NaN, ``under`` those with a lower limit where
+      ``a < lower`` or a is a NaN (on the bits as integers: the float32 order of non-negative values); ``first`` and ``last``
+      are the lowest and highest bin counted in either, or -1;
+    - ``up_bin`` maximises ``a / upper`` as the exact ratio -- cross products in float64, a NaN point standing as +inf, equal
+      ratios to the lowest bin -- with ``up_val`` the bits of the point there and ``up_lim`` the limit; ``lo_bin`` minimises
+      ``a / lower``, a NaN standing as 0.  Without such a bin the bin is -1 and both floats +0.0;
+    - ``summary``: rows with over > 0, rows with under > 0, the first row with either or -1, the last or -1.
+
+    ``0 <= lo < hi <= 16384`` as ints (no bool, no float): ValueError otherwise, and on a wrong dtype or shape."""
+    upper, lower, lo, hi = _mask_args(upper, lower, lo, hi, field)
+    points = np.ascontiguousarray(points)
+    shape = (FFT_SIZE,) if field is None else (FFT_SIZE, 2)
+    if points.dtype != np.float32 or points.ndim != 1 + len(shape) or points.shape[1:] != shape:
+        raise ValueError(f"points must be float32 [R, {', '.join(map(str, shape))}]")
+    if field is not None:
+        points = np.ascontiguousarray(points[..., RANK_FIELDS[field]])
+    R = points.shape[0]
+    a = points.view(np.uint32) & np.uint32(0x7FFFFFFF)
+    nan = a > 0x7F800000
+    i = np.arange(FFT_SIZE)
+    inside = (i >= lo) & (i < hi)
+    rec = np.zeros(R, MASK_ROW)
+    outside = np.zeros((R, FFT_SIZE), bool)
+    rows = np.arange(R)
+    for up, limit, count, names in ((True, upper, "over", ("up_bin", "up_val", "up_lim")),
+                                    (False, lower, "under", ("lo_bin", "lo_val", "lo_lim"))):
+        rec[names[0]] = -1
+        if limit is None:
+            continue
+        bits = limit.view(np.uint32)
+        has = inside & (bits >= 1) & (bits <= 0x7F7FFFFF)             # finite and above 0, denormals included
+        out = has & ((a > bits) if up else ((a < bits) | nan))         # as integers: a NaN lies above every limit
+        rec[count] = out.sum(axis=1)
+        outside |= out
+        key = np.where(nan, np.uint32(0x7F800000 if up else 0), a).view(np.float32).astype(np.float64)
+        worst = _mask_worst(key[:, lo:hi], limit[lo:hi].astype(np.float64), has[lo:hi], up)
+        found = worst >= 0
+        at = np.where(found, worst + lo, 0)
+        rec[names[0]] = np.where(found, at, -1)
+        rec[names[1]] = np.where(found, a[rows, at], np.uint32(0)).astype(np.uint32).view(np.float32)
+        rec[names[2]] = np.where(found, limit[at], np.float32(0.0))
+    any_out = outside.any(axis=1)
+    rec["first"] = np.where(any_out, outside.argmax(axis=1), -1)
+    rec["last"] = np.where(any_out, FFT_SIZE - 1 - outside[:, ::-1].argmax(axis=1), -1)
+    failed = np.nonzero((rec["over"] > 0) | (rec["under"] > 0))[0]
+    summary = np.array([(rec["over"] > 0).sum(), (rec["under"] > 0).sum(), failed[0] if failed.size else -1,
+                        failed[-1] if failed.size else -1], np.int32)
+    return rec, summary
+
+
+def limit_line(points, unit: str = "amplitude") -> np.ndarray:
+    """A limit line for :func:`mask_of_rows` / sa_mask_f32 from breakpoints: float32 [16384].  ``points`` is a sequence of one
+    or more ``(bin, dB)`` pairs, the bins ints in 0..16383 and strictly ascending, the levels finite numbers; consecutive
+    breakpoints are joined by a straight line in dB, ``d0 + (d1 - d0) * (i - b0) / (b1 - b0)`` in Python's doubles, and bin i
+    gets ``10 ** (dB / 20)`` (``unit='amplitude'``) or ``10 ** (dB / 10)`` (``unit='power'``), computed in float64 and rounded
+    once.  Outside the first and last breakpoint the line is +inf: no limit there.  A host convenience: the limits are an
+    input of the test, not part of its definition.  ValueError otherwise."""
+    if not isinstance(unit, str) or unit not in _MASK_UNITS:
+        raise ValueError("unit must be 'amplitude' or 'power'")
+    if isinstance(points, (str, bytes)) or not hasattr(points, "__len__") or len(points) < 1:
+        raise ValueError("points must be a sequence of one or more (bin, dB) pairs")
+    pairs = []
+    for p in points:
+        if isinstance(p, (str, bytes)) or not hasattr(p, "__len__") or len(p) != 2:
+            raise ValueError("a breakpoint must be a (bin, dB) pair")
+        b, d = p
+        if isinstance(b, bool) or not isinstance(b, (int, np.integer)) or not 0 <= int(b) < FFT_SIZE:
+            raise ValueError("a breakpoint's bin must be an int in 0..16383")
+        if isinstance(d, bool) or not isinstance(d, (int, float, np.integer, np.floating)) or not math.isfinite(float(d)):
+            raise ValueError("a breakpoint's level must be a finite number of dB")
+        if pairs and int(b) <= pairs[-1][0]:
+            raise ValueError("the breakpoints' bins must ascend strictly")
+        pairs.append((int(b), float(d)))
+    div = _MASK_UNITS[unit]
+    db = np.full(FFT_SIZE, np.inf, np.float64)
+    for (b0, d0), (b1, d1) in zip(pairs, pairs[1:]):
+        for i in range(b0, b1):
+            db[i] = d0 + (d1 - d0) * (i - b0) / (b1 - b0)
+    db[pairs[-1][0]] = pairs[-1][1]
+    with np.errstate(over="ignore"):
+        return np.array([10.0 ** (d / div) if math.isfinite(d) else math.inf for d in db], np.float64).astype(np.float32)
+
+
+def mask_from_trace(trace, margin_db: float, widen: int, unit: str = "amplitude") -> np.ndarray:
+    """The usual "auto mask" from a known-good spectrum, an upper limit for :func:`mask_of_rows` / sa_mask_f32: float32
+    [16384], bin i the largest of ``|trace|`` over the bins ``i - widen .. i + widen`` (those of the row) times ``10 **
+    (margin_db / 20)`` (``unit='amplitude'``) or ``10 ** (margin_db / 10)`` (``unit='power'``), the product taken in float64
+    and rounded once.  With ``widen`` 0 and a margin of 0 it is ``|trace|``; with a margin of 0 or more the trace passes its
+    own mask (the rounding of a product by a factor of 1 or more never goes below the float32 it started from).  Where the
+    window's largest value is 0 or a NaN the result is no limit.  ValueError unless ``trace`` is float32 [16384],
+    ``margin_db`` a finite number and ``widen`` an int in 0..16384."""
+    if not isinstance(unit, str) or unit not in _MASK_UNITS:
+        raise ValueError("unit must be 'amplitude' or 'power'")
+    if isinstance(widen, bool) or not isinstance(widen, (int, np.integer)) or not 0 <= int(widen) <= FFT_SIZE:
+        raise ValueError("widen must be an int in 0..16384")
+    if (isinstance(margin_db, bool) or not isinstance(margin_db, (int, float, np.integer, np.floating))
+            or not math.isfinite(float(margin_db))):
+        raise ValueError("margin_db must be a finite number")
+    if not isinstance(trace, np.ndarray) or trace.dtype != np.float32 or trace.shape != (FFT_SIZE,):
+        raise ValueError("trace must be a float32 [16384] array")
+    w = int(widen)
+    a = (np.ascontiguousarray(trace).view(np.uint32) & np.uint32(0x7FFFFFFF)).view(np.float32)
+    L = 2 * w + 1
+    m = np.concatenate([np.zeros(w, np.float32), a, np.zeros(w, np.float32)])
+    span = 1
+    while 2 * span <= L:                              # m[i] = max of the padded row over [i, i + span)
+        m = np.maximum(m[:-span], m[span:])
+        span *= 2
+    widened = np.maximum(m[:FFT_SIZE], m[L - span:L - span + FFT_SIZE])
+    with np.errstate(over="ignore"):
+        return (widened.astype(np.float64) * 10.0 ** (float(margin_db) / _MASK_UNITS[unit])).astype(np.float32)
+
+
+def mask_margin_db(records, unit: str = "amplitude") -> tuple:
+    """``(upper, lower)`` float64 [R]: the margins in dB of the worst bins of mask records (the MASK_ROW array of
+    :func:`mask_of_rows`, or the device's records viewed with that dtype): ``20 log10(up_val / up_lim)`` and ``20 log10(lo_val /
+    lo_lim)``, 10 log10 with ``unit='power'``.  A row is over its upper limit where the first is above 0, under its lower
+    limit where the second is below 0.  A NaN point stands as in the test, +inf above and -inf below; a row without a
+    limited bin gives a NaN."""
+    if not isinstance(unit, str) or unit not in _MASK_UNITS:
+        raise ValueError("unit must be 'amplitude' or 'power'")
+    records = np.asarray(records)
+    if records.dtype != MASK_ROW:
+        raise ValueError("records must have the dtype MASK_ROW")
+    out = []
+    with np.errstate(divide="ignore", invalid="ignore"):
+        for up, b, v, l in ((True, "up_bin", "up_val", "up_lim"), (False, "lo_bin", "lo_val", "lo_lim")):
+            val = records[v].astype(np.float64)
+            val = np.where(np.isnan(val), np.inf if up else 0.0, val)
+            db = _MASK_UNITS[unit] * np.log10(val / records[l].astype(np.float64))
+            out.append(np.where(records[b] >= 0, db, np.nan))
+    return out[0], out[1]
+
+
 def decode_iq_components(frame_bytes: bytes):
     """Same result as gui.py:262-270: (re, im) as float32 arrays."""
     re, im = _iq(frame_bytes)

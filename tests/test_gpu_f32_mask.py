@@ -1,0 +1,431 @@
+"""GPU: the spectral mask test (include/specan_mask.h: sa_mask_f32 of libspecan_mask.so), through SpectrumChain.mask_test,
+SpectrumChain.mask_trigger_f32 and the C entry point.
+
+Every comparison is exact -- the integers of the records and the summary, the floats bit for bit, NaNs by position -- against
+the numpy mirror frames.mask_of_rows, which tests/test_f32_mask_cpu.py holds against a restatement of the header in
+fractions; the edge rows, the aimed rows and the ties of that file are the data here, so a kernel that divides in float32,
+breaks a tie towards another bin or counts a bin outside the range fails.
+
+The kernel's ownership (csrc/mask_f32.hip): in round r thread t holds the four bins 1024 r + 4 t .. + 3, a wave 256 adjacent
+bins of a round; only the rounds that hold a bin of the range are read.  The ranges below start and end on and beside every
+one of these boundaries."""
+import numpy as np
+import pytest
+
+import offset_cases as oc
+from conftest import N, load_golden
+from gpu_support import ch, check_overlap_profiling_and_graph_capture, to_device, torch_mod  # noqa: F401 (fixtures)
+from native import Lds, gpu_helper
+from test_f32_mask_cpu import (FIELDS, GAPS, aimed_narrow, aimed_wide, edge_case, edge_ranges, planted, records_of,
+                               same_records)
+from test_gpu_f32_peaks import _inputs, _tones
+
+pytestmark = pytest.mark.gpu
+
+SA_OK, SA_EINVAL, SA_ESHAPE = 0, -1, -2
+
+
+def _host(ints, floats):
+    """the two views mask_test returns -> a frames.MASK_ROW array on the host"""
+    from fpga_real_time_fft_analyzer_amd import frames
+    assert ints.shape[1:] == (6,) and floats.shape[1:] == (4,) and ints.data_ptr() + 24 == floats.data_ptr()
+    rec = np.zeros(ints.shape[0], frames.MASK_ROW)
+    i, f = ints.cpu().numpy(), floats.cpu().numpy()
+    for k, name in enumerate(frames.MASK_ROW.names):
+        rec[name] = i[:, k] if k < 6 else f[:, k - 6]
+    return rec
+
+
+def _run(ch, torch, x, upper, lower, lo=0, hi=N, field=None, summary=True, **kw):
+    ints, floats, s = ch.mask_test(x, upper, lower, lo, hi, field=field, summary=summary, **kw)
+    assert ints.dtype == torch.int32 and floats.dtype == torch.float32 and ints.shape[0] == x.shape[0]
+    assert (s is None) == (summary is False)
+    return _host(ints, floats), None if s is None else s.cpu().numpy()
+
+
+def _same(got, pts, upper, lower, lo, hi, field, tag):
+    """the device's records and summary against the mirror's on the same points: bit for bit"""
+    from fpga_real_time_fft_analyzer_amd import frames
+    want, want_s = frames.mask_of_rows(records_of(pts, field), upper, lower, lo, hi, field=field)
+    if not same_records(got[0], want):
+        bad = [(n, r, got[0][n][r], want[n][r]) for n in want.dtype.names for r in range(len(want))
+               if got[0][n][r] != want[n][r] and not (np.isnan(got[0][n][r]) and np.isnan(want[n][r]))]
+        raise AssertionError((tag, bad[:6]))
+    if got[1] is not None:
+        assert got[1].tolist() == want_s.tolist(), (tag, got[1], want_s)
+    return want, want_s
+
+
+def _dev(torch, a):
+    return None if a is None else to_device(torch, a)
+
+
+def _check(ch, torch, x, pts, upper, lower, lo, hi, field, tag, d_limits=None):
+    du, dl = d_limits if d_limits is not None else (_dev(torch, upper), _dev(torch, lower))
+    return _same(_run(ch, torch, x, du, dl, lo, hi, field), pts, upper, lower, lo, hi, field, tag)
+
+
+@pytest.mark.parametrize("field", FIELDS)
+def test_ranges_on_and_beside_every_boundary(ch, torch_mod, field):
+    """rows = 5, both limits: every lo < hi of 0, 1, 3, 4, 5, 255, 256, 257, 1023, 1024, 1025, 16383, 16384 and hi = lo + 1 at
+    each; the violations and worst bins planted on both sides of every boundary decide the record, those just outside the range
+    must not count.  One limit alone over the ranges of one bin and those that end at the row's end; rows = 1 and 3."""
+    pts, upper, lower = edge_case()
+    x = to_device(torch_mod, records_of(pts, field))
+    du, dl = to_device(torch_mod, upper), to_device(torch_mod, lower)
+    P = planted()
+    for lo, hi in edge_ranges():
+        want, _ = _check(ch, torch_mod, x, pts, upper, lower, lo, hi, field, (field, lo, hi), (du, dl))
+        inside = [b for b in P if lo <= b < hi]
+        assert want["up_bin"][:3].tolist() == [inside[-1], inside[0], inside[0]] and want["lo_bin"][3:].tolist() == [inside[-1], inside[0]]
+    some = [(lo, hi) for lo, hi in edge_ranges() if hi == lo + 1 or hi == N or lo == 0]
+    for lo, hi in some:
+        _check(ch, torch_mod, x, pts, upper, None, lo, hi, field, (field, "upper", lo, hi), (du, None))
+        _check(ch, torch_mod, x, pts, None, lower, lo, hi, field, (field, "lower", lo, hi), (None, dl))
+    for rows in (1, 3):
+        for lo, hi in ((0, N), (255, 1025), (4, 5)):
+            for lims in ((upper, lower), (upper, None), (None, lower)):
+                _check(ch, torch_mod, x[5 - rows:], pts[5 - rows:], lims[0], lims[1], lo, hi, field, (field, rows, lo, hi))
+
+
+def test_near_equal_ratios_and_exact_ties(ch, torch_mod):
+    """The 200 aimed rows of the CPU file, where a float32 quotient names another bin in more than a third, in one call; the
+    aimed rows over the whole row, and the rows in which every ratio is equal across all waves and rounds: the lowest bin of
+    the range wins, wherever the range starts."""
+    pts, upper, lo, hi = aimed_narrow()
+    for field in (None, "power"):
+        x = to_device(torch_mod, records_of(pts, field))
+        _check(ch, torch_mod, x, pts, upper, None, lo, hi, field, ("narrow upper", field))
+        _check(ch, torch_mod, x, pts, None, upper, lo, hi, field, ("narrow lower", field))
+        _check(ch, torch_mod, x, pts, upper, upper, lo - 3, hi + 5, field, ("narrow both", field))
+    wide, limit = aimed_wide()
+    x = to_device(torch_mod, wide)
+    d = to_device(torch_mod, limit)
+    for lo, hi in ((0, N), (1, N), (255, 16000), (1024, 1025), (1023, 9000), (257, 258), (4097, N)):
+        want, _ = _check(ch, torch_mod, x, wide, limit, limit, lo, hi, None, ("wide", lo, hi), (d, d))      # one tensor as both limits
+        assert want["up_bin"][4:].tolist() == [lo, lo] == want["lo_bin"][4:].tolist()
+        assert want["over"][4] == hi - lo == want["under"][5] and want["under"][4] == 0 == want["over"][5]
+    # equal ratios in two bins only, in different waves and rounds, either order of the larger point
+    two = np.full((4, N), 1.0, np.float32)
+    lim = np.full(N, 8.0, np.float32)
+    for r, (b0, b1) in enumerate(((100, 9000), (300, 1400), (1023, 1024), (5, 16383))):
+        lim[b0], lim[b1] = 2.0, 32.0
+        two[r, b0], two[r, b1] = 16.0, 256.0                      # both 8 times the limit
+    want, _ = _check(ch, torch_mod, to_device(torch_mod, two), two, lim, None, 0, N, None, "two bins")
+    assert want["up_bin"].tolist() == [100, 300, 1023, 5]
+
+
+@pytest.mark.parametrize("field", FIELDS)
+def test_specials_in_wide_rows_and_rows_between_nan_rows(ch, torch_mod, field):
+    """R = 7: NaN rows around and between the data rows, an all-inf row and an all-zero one; -0.0, float32 denormals, +-inf and
+    NaNs inside and outside the range of the data rows, denormal and huge limits, every kind of gap; the data rows equal their
+    calls of one row and of three."""
+    base, upper, lower = edge_case()
+    upper, lower = upper.copy(), lower.copy()
+    nan_row = np.full((1, N), np.nan, np.float32)
+    pts = np.concatenate([nan_row, base[:1], nan_row, base[3:4], np.full((1, N), np.inf, np.float32), np.zeros((1, N), np.float32), nan_row])
+    pts[1, 4000], pts[1, 4001], pts[1, 12000], pts[1, 299] = np.nan, -np.nan, -np.inf, np.nan
+    pts[3, 100:400] = 1e-45
+    pts[3, 5000], pts[3, 5001], pts[3, 5002] = -0.0, np.inf, 1e-39
+    upper[100:110], lower[110:120] = 1e-45, 1e-45                 # a denormal limit is a limit
+    upper[5002], lower[5002] = 3.4e38, 1e-40
+    upper[4001], lower[4001] = np.nan, 1.0
+    upper[4000], lower[4000] = 50.0, 0.05
+    lo, hi = 300, 15000
+    x = to_device(torch_mod, records_of(pts, field))
+    want, want_s = _check(ch, torch_mod, x, pts, upper, lower, lo, hi, field, field)
+    assert np.isnan(want["up_val"][[0, 2, 6]]).all() and np.isnan(want["lo_val"][[0, 2, 6]]).all()
+    assert (want["over"][[0, 2, 6]] > 10000).all() and (want["under"][[0, 2, 6]] > 10000).all() and (want["first"][[0, 2, 6]] == lo).all()
+    assert np.isnan(want["up_val"][1]) and want["up_bin"][1] == 4000 and want["lo_bin"][1] == 4000 and want["first"][1] >= lo
+    assert np.isinf(want["up_val"][4]) and want["under"][4] == 0 and want["under"][5] > 0 and want["lo_val"][5] == 0 and want["over"][5] == 0
+    assert want_s[2] == 0 and want_s[3] == 6
+    du, dl = to_device(torch_mod, upper), to_device(torch_mod, lower)
+    for r in (1, 3, 5):
+        one = _run(ch, torch_mod, x[r:r + 1], du, dl, lo, hi, field)
+        assert same_records(one[0], want[r:r + 1]), (field, r)
+    three = _run(ch, torch_mod, x[2:5], du, dl, lo, hi, field)
+    assert same_records(three[0], want[2:5]), field
+
+
+def test_no_limited_bin_and_the_summary(ch, torch_mod):
+    """A range in which every limit is a gap gives -1 and +0.0, whatever the points; the summary with no failing row, only row
+    0, only the last row, upper and lower failures in different rows; summary=False writes nothing."""
+    torch = torch_mod
+    pts = np.full((6, N), 5.0, np.float32)
+    upper = np.full(N, 10.0, np.float32)
+    lower = np.full(N, 1.0, np.float32)
+    upper[2000:2600] = np.tile(np.array(GAPS, np.float32), 100)
+    x = to_device(torch, pts)
+    want, want_s = _check(ch, torch, x, pts, upper, None, 2000, 2600, None, "no limited bin")
+    assert want["up_bin"].tolist() == [-1] * 6 and want_s.tolist() == [0, 0, -1, -1]
+    for name in ("up_val", "up_lim", "lo_val", "lo_lim"):
+        assert (want[name].view(np.uint32) == 0).all()
+    want, want_s = _check(ch, torch, x, pts, upper, lower, 0, N, None, "all pass")
+    assert want_s.tolist() == [0, 0, -1, -1] and (want["up_bin"] == 0).all() and (want["first"] == -1).all()
+    for tag, cells, expect in (("row 0", [(0, 700, 11.0)], [1, 0, 0, 0]), ("last row", [(5, 16383, 0.5)], [0, 1, 5, 5]),
+                               ("upper and lower in different rows", [(1, 3, 99.0), (4, 9000, 0.25), (2, 1023, np.nan)], [2, 2, 1, 4]),
+                               ("every row", [(r, 3000 * r, 20.0) for r in range(6)], [6, 0, 0, 5])):
+        p = pts.copy()
+        for r, b, v in cells:
+            p[r, b] = v
+        _, s = _check(ch, torch, to_device(torch, p), p, upper, lower, 0, N, None, tag)
+        assert s.tolist() == expect, (tag, s)
+    # a summary tensor of the caller's is written; summary=False leaves every byte alone
+    mine = torch.full((4,), -77, dtype=torch.int32, device="cuda")
+    du, dl = to_device(torch, upper), to_device(torch, lower)
+    assert ch.mask_test(x, du, dl, summary=mine)[2].data_ptr() == mine.data_ptr() and mine.tolist() == [0, 0, -1, -1]
+    out = torch.zeros((6, 10), dtype=torch.int32, device="cuda")
+    ints, floats, none = ch.mask_test(x, du, dl, out=out)
+    assert none is None and ints.data_ptr() == out.data_ptr()
+    assert ch.mask_test(torch.empty((0, N), dtype=torch.float32, device="cuda"), du, summary=True)[0].shape == (0, 6)
+
+
+def test_exactly_the_output_bytes_are_written_and_a_refused_call_writes_nothing(ch, torch_mod):
+    from fpga_real_time_fft_analyzer_amd import abi, frames
+    from fpga_real_time_fft_analyzer_amd.abi import SpecanError
+    torch = torch_mod
+    L = abi.mask_lib()
+    stream = torch.cuda.current_stream().cuda_stream
+    pts, upper, lower = edge_case()
+    R, guard = 5, 4096
+    x = to_device(torch, pts)
+    du, dl = to_device(torch, upper), to_device(torch, lower)
+    n_r = R * 40
+    for p_up, p_lo, with_summary in ((du.data_ptr(), dl.data_ptr(), True), (du.data_ptr(), None, False), (None, dl.data_ptr(), True)):
+        rows_out = torch.full((guard + n_r + guard,), 0xA5, dtype=torch.uint8, device="cuda")
+        summary = torch.full((guard + 16 + guard,), 0xA5, dtype=torch.uint8, device="cuda")
+        rc = L.sa_mask_f32(x.data_ptr(), 0, p_up, p_lo, 3, 16000, rows_out.data_ptr() + guard,
+                           summary.data_ptr() + guard if with_summary else None, R, stream)
+        assert rc == SA_OK and L.sa_mask_last_error() == b""
+        torch.cuda.synchronize()
+        for t, n in ((rows_out, n_r), (summary, 16 if with_summary else 0)):
+            assert (t[:guard] == 0xA5).all().item() and (t[guard + n:] == 0xA5).all().item()
+        got = rows_out[guard:guard + n_r].cpu().numpy().view(frames.MASK_ROW)
+        assert (got.view(np.uint32) != 0xA5A5A5A5).all()          # every word was written: no record holds the fill
+        got_s = summary[guard:guard + 16].cpu().numpy().view(np.int32) if with_summary else None
+        _same((got, got_s), pts, upper if p_up else None, lower if p_lo else None, 3, 16000, None, ("C call", bool(p_up), bool(p_lo)))
+    # refused calls: the code of sa_mask_check for the same arguments, its text, and nothing written
+    rows_out = torch.full((n_r + guard,), 0xA5, dtype=torch.uint8, device="cuda")
+    summary = torch.full((64,), 0xA5, dtype=torch.uint8, device="cuda")
+    flat = torch.zeros((R * N + 64,), dtype=torch.float32, device="cuda")
+    before = flat.clone()
+    p_in, p_up, p_lo, p_ro, p_su = flat.data_ptr(), du.data_ptr(), dl.data_ptr(), rows_out.data_ptr(), summary.data_ptr()
+    for tag, (a_in, field, a_up, a_lo, lo, hi, a_ro, a_su, rows), code, words in (
+            ("in 4 bytes off", (p_in + 4, 0, p_up, p_lo, 0, N, p_ro, p_su, R), SA_EINVAL, "`in` must be 16-byte aligned"),
+            ("upper 4 bytes off", (p_in, 0, p_up + 4, p_lo, 0, N, p_ro, p_su, R), SA_EINVAL, "`upper` must be 16-byte aligned"),
+            ("lower 8 bytes off", (p_in, 0, p_up, p_lo + 8, 0, N, p_ro, p_su, R), SA_EINVAL, "`lower` must be 16-byte aligned"),
+            ("rows_out 4 bytes off", (p_in, 0, p_up, p_lo, 0, N, p_ro + 4, p_su, R), SA_EINVAL, "`rows_out` must be 8-byte aligned"),
+            ("summary 2 bytes off", (p_in, 0, p_up, p_lo, 0, N, p_ro, p_su + 2, R), SA_EINVAL, "`summary` must be 4-byte aligned"),
+            ("rows_out inside in", (p_in, 0, p_up, p_lo, 0, N, p_in + R * N * 4 - 8, p_su, R), SA_EINVAL, "`in` and `rows_out` overlap"),
+            ("records read twice as much", (p_in, 2, p_up, p_lo, 0, N, p_in + R * N * 4, p_su, R), SA_EINVAL, "`in` and `rows_out` overlap"),
+            ("summary inside rows_out", (p_in, 0, p_up, p_lo, 0, N, p_ro, p_ro + 8, R), SA_EINVAL, "`rows_out` and `summary` overlap"),
+            ("summary inside upper", (p_in, 0, p_up, p_lo, 0, N, p_ro, p_up + 64, R), SA_EINVAL, "`upper` and `summary` overlap"),
+            ("rows_out inside lower", (p_in, 0, p_up, p_lo, 0, N, p_lo + 65536 - 8, p_su, R), SA_EINVAL, "`lower` and `rows_out` overlap"),
+            ("the limits meet", (p_in, 0, p_up, p_up + 16, 0, N, p_ro, p_su, R), SA_EINVAL, "`upper` and `lower` overlap"),
+            ("upper is the input", (p_in, 0, p_in, p_lo, 0, N, p_ro, p_su, R), SA_EINVAL, "`in` and `upper` overlap"),
+            ("NULL rows_out", (p_in, 0, p_up, p_lo, 0, N, 0, p_su, R), SA_EINVAL, "NULL"),
+            ("NULL in", (0, 0, p_up, p_lo, 0, N, p_ro, p_su, R), SA_EINVAL, "NULL"),
+            ("no limit", (p_in, 0, 0, 0, 0, N, p_ro, p_su, R), SA_EINVAL, "no limit"),
+            ("field 3", (p_in, 3, p_up, p_lo, 0, N, p_ro, p_su, R), SA_EINVAL, "field"),
+            ("lo = hi", (p_in, 0, p_up, p_lo, 9, 9, p_ro, p_su, R), SA_EINVAL, "[9, 9)"),
+            ("hi beyond the row", (p_in, 0, p_up, p_lo, 0, N + 1, p_ro, p_su, R), SA_EINVAL, "[0, 16385)"),
+            ("negative rows", (p_in, 0, p_up, p_lo, 0, N, p_ro, p_su, -1), SA_ESHAPE, "negative")):
+        assert L.sa_mask_check(a_in, field, a_up, a_lo, lo, hi, a_ro, a_su, rows) == code, tag
+        assert L.sa_mask_f32(a_in or None, field, a_up or None, a_lo or None, lo, hi, a_ro or None, a_su or None, rows, stream) == code, tag
+        assert words in L.sa_mask_last_error().decode(), (tag, L.sa_mask_last_error())
+    torch.cuda.synchronize()
+    assert (rows_out == 0xA5).all().item() and (summary == 0xA5).all().item() and torch.equal(flat, before)
+    for d, h in ((du, upper), (dl, lower)):
+        assert np.array_equal(d.cpu().numpy().view(np.uint32), h.view(np.uint32))
+    assert L.sa_mask_f32(None, 0, p_up, None, 0, N, None, None, 0, stream) == SA_OK and L.sa_mask_last_error() == b""
+    # the five buffers touching, one behind the other
+    n_in = R * N * 4
+    packed = torch.zeros((n_in + 65536 + 65536 + n_r + 16,), dtype=torch.uint8, device="cuda")
+    packed[:n_in] = x.view(torch.uint8).view(-1)
+    packed[n_in:n_in + 65536] = du.view(torch.uint8)
+    packed[n_in + 65536:n_in + 131072] = dl.view(torch.uint8)
+    base = packed.data_ptr()
+    assert L.sa_mask_f32(base, 0, base + n_in, base + n_in + 65536, 0, N, base + n_in + 131072, base + n_in + 131072 + n_r, R, stream) == SA_OK
+    torch.cuda.synchronize()
+    host = packed[n_in + 131072:].cpu().numpy()
+    _same((host[:n_r].view(frames.MASK_ROW), host[n_r:].view(np.int32)), pts, upper, lower, 0, N, None, "touching")
+    # through the wrapper: shapes and dtypes before any device call
+    for code, args, kw in ((SA_ESHAPE, (x[:, :N // 2], du), {}), (SA_EINVAL, (x.double(), du), {}), (SA_ESHAPE, (x, du), dict(field="peak")),
+                           (SA_ESHAPE, (x, du[:N - 4]), {}), (SA_ESHAPE, (x, du.double()), {}), (SA_ESHAPE, (x, du.cpu()), {}),
+                           (SA_ESHAPE, (x, du, dl[::2]), {}), (SA_ESHAPE, (x, upper), {}),
+                           (SA_ESHAPE, (x, du), dict(out=torch.empty((R, 9), dtype=torch.int32, device="cuda"))),
+                           (SA_ESHAPE, (x, du), dict(out=torch.empty((R, 10), dtype=torch.float32, device="cuda"))),
+                           (SA_ESHAPE, (x, du), dict(out=torch.empty((R, 10), dtype=torch.int32))),
+                           (SA_ESHAPE, (x, du), dict(summary=torch.empty((3,), dtype=torch.int32, device="cuda"))),
+                           (SA_ESHAPE, (x, du), dict(summary=torch.empty((4,), dtype=torch.int64, device="cuda"))),
+                           (SA_EINVAL, (x.cpu(), du), {}), (SA_EINVAL, (x, None), {}), (SA_EINVAL, (x, du, None, 5, 5), {})):
+        with pytest.raises(SpecanError) as e:
+            ch.mask_test(*args, **kw)
+        assert e.value.code == code, (args[0].shape, kw)
+
+
+@pytest.fixture(scope="module")
+def lds_fill(tmp_path_factory, torch_mod):
+    """tests/hip/lds_fill.hip, built and bound as tests/test_gpu_f32_rank.py does: lds_fill(word) writes `word` to all of
+    the LDS of every CU, on the current stream."""
+    return Lds(gpu_helper(tmp_path_factory.mktemp("lds_fill_mask"), "lds_fill"), torch_mod).fill
+
+
+def test_poisoned_lds(ch, torch_mod, lds_fill):
+    """lds_fill(P) with P = 0xFFFFFFFF (a NaN as a float, -1 as a bin or a count) and 0x7F800000 (+inf, a large count), then
+    the call on the same stream: the bits of the mirror, for every layout and set of limits, with the summary."""
+    pts, upper, lower = edge_case()
+    du, dl = to_device(torch_mod, upper), to_device(torch_mod, lower)
+    for field in FIELDS:
+        x = to_device(torch_mod, records_of(pts, field))
+        for word in (0xFFFFFFFF, 0x7F800000):
+            for lims, d in (((upper, lower), (du, dl)), ((upper, None), (du, None)), ((None, lower), (None, dl))):
+                for lo, hi in ((0, N), (1000, 1100)):
+                    lds_fill(word)
+                    _check(ch, torch_mod, x, pts, lims[0], lims[1], lo, hi, field, (field, hex(word), lo, hi), d)
+
+
+def test_capture_and_replay(ch, torch_mod):
+    """mask_test with the summary captures without a warm-up -- two launches, nothing zeroed -- and a replay after the input
+    has changed gives the records and the summary of the new input: one passing input and two that fail in different rows.
+    Then the composed call, in overlap mode, under launch timing and captured."""
+    torch = torch_mod
+    pts, upper, lower = edge_case()
+    clean = np.clip(np.abs(pts), 0.2, 5.0).astype(np.float32)
+    lim_u, lim_l = np.full(N, 8.0, np.float32), np.full(N, 0.125, np.float32)
+    fail_a, fail_b = clean.copy(), clean.copy()
+    fail_a[1, 300], fail_a[3, 16000] = 9.0, 0.01
+    fail_b[0, 5], fail_b[4, 1023] = np.nan, 77.0
+    du, dl = to_device(torch, lim_u), to_device(torch, lim_l)
+    x = to_device(torch, fail_a)
+    out = torch.zeros((5, 10), dtype=torch.int32, device="cuda")
+    summary = torch.zeros((4,), dtype=torch.int32, device="cuda")
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        ch.mask_test(x, du, dl, 1, N - 1, out=out, summary=summary)
+    seen = []
+    for p in (clean, fail_a, fail_b, clean):
+        x.copy_(to_device(torch, p))
+        out.fill_(-5)
+        graph.replay()                                           # the summary is left as the replay before wrote it
+        torch.cuda.synchronize()
+        _, s = _same((_host(out[:, :6], out.view(torch.float32)[:, 6:]), summary.cpu().numpy()), p, lim_u, lim_l, 1, N - 1, None, "replay")
+        seen.append(s.tolist())
+    assert seen == [[0, 0, -1, -1], [1, 1, 1, 3], [2, 1, 0, 4], [0, 0, -1, -1]], seen
+    # the composed call
+    ch.set_filter_mode(0xB1)
+    ch.reserve(8)
+    xin = to_device(torch, _tones(4, 2330))
+    mag = ch.process_f32(xin, out_kind="mag_full")
+    from fpga_real_time_fft_analyzer_amd import frames
+    mu = to_device(torch, frames.mask_from_trace(mag[0].cpu().numpy(), 0.5, 2))
+    ref = torch.zeros((4, 10), dtype=torch.int32, device="cuda")
+    ints, _, s = ch.mask_trigger_f32(xin, mu, None, 100, 16000, out=ref)
+    assert ints[0, 0].item() == 0 and 0 < s[0].item() < 4          # frame 0 passes its own mask, another frame does not
+    ref = ref.clone()
+    check_overlap_profiling_and_graph_capture(torch, ch, lambda o: ch.mask_trigger_f32(xin, mu, None, 100, 16000, out=o), ref)
+    assert "libspecan_mask.so" in open("/proc/self/maps").read()
+
+
+@pytest.mark.parametrize("mode", [0xB1, 0xA1])
+def test_mask_trigger_f32(ch, torch_mod, mode):
+    """The composed call equals mask_test on process_f32's magnitudes, and with group = 4 mask_test on spectra_f32's records,
+    field 'power' -- float32, int16 and packed input -- and the mirror on the same values; a caller's work, out and summary;
+    refusals before any launch."""
+    from fpga_real_time_fft_analyzer_amd import frames
+    from fpga_real_time_fft_analyzer_amd.abi import SpecanError
+    torch = torch_mod
+    if mode == 0xA1:
+        ch.load_sos(load_golden("g2_config1.npz")["sos"])
+    ch.set_filter_mode(mode)
+    B, lo, hi = 4, 50, 16300
+    for form, x in _inputs(torch, _tones(B, 2340 + mode)).items():
+        mag = ch.process_f32(x, out_kind="mag_full")
+        h_mag = mag.cpu().numpy()
+        upper = frames.mask_from_trace(h_mag[1], 0.25, 1)           # frame 1 passes; the noise of the others does not
+        lower = frames.mask_from_trace(h_mag[1], -40.0, 0)
+        lower[::3] = 0.0
+        du, dl = to_device(torch, upper), to_device(torch, lower)
+        got = ch.mask_trigger_f32(x, du, dl, lo, hi)
+        want, want_s = _same((_host(got[0], got[1]), got[2].cpu().numpy()), h_mag, upper, lower, lo, hi, None, form)
+        assert want["over"][1] == 0 and 0 < want_s[0] < B, (form, want_s)
+        direct = ch.mask_test(mag, du, dl, lo, hi, summary=True)
+        assert torch.equal(got[0], direct[0]) and torch.equal(got[1].view(torch.int32), direct[1].view(torch.int32)) and torch.equal(got[2], direct[2])
+        rec = ch.spectra_f32(x, 4)
+        h_pow = rec.cpu().numpy()[..., 1]
+        up4 = frames.mask_from_trace(np.ascontiguousarray(h_pow[0]), 1.0, 3, "power")
+        up4[6000:6100] = np.float32(0.5) * h_pow[0, 6000:6100]      # and a stretch that fails
+        d4 = to_device(torch, up4)
+        got4 = ch.mask_trigger_f32(x, d4, None, lo, hi, group=4)
+        assert tuple(got4[0].shape) == (1, 6) and tuple(got4[1].shape) == (1, 4)
+        want4, s4 = _same((_host(got4[0], got4[1]), got4[2].cpu().numpy()), h_pow, up4, None, lo, hi, "power", (form, "group"))
+        assert s4.tolist() == [1, 0, 0, 0] and 6000 <= want4["first"][0] and want4["last"][0] < 6100
+    x = _inputs(torch, _tones(B, 2340 + mode))["int16"]
+    mag = ch.process_f32(x, out_kind="mag_full")
+    du = to_device(torch, frames.mask_from_trace(mag[1].cpu().numpy(), 0.25, 1))
+    want = ch.mask_test(mag, du, None, lo, hi, summary=True)
+    work = torch.full((B + 1, N), 3.0, dtype=torch.float32, device="cuda")
+    out = torch.zeros((B, 10), dtype=torch.int32, device="cuda")
+    summary = torch.zeros((4,), dtype=torch.int32, device="cuda")
+    res = ch.mask_trigger_f32(x, du, None, lo, hi, work=work, out=out, summary=summary)
+    assert res[0].data_ptr() == out.data_ptr() and res[2].data_ptr() == summary.data_ptr()
+    assert torch.equal(out[:, :6], want[0]) and torch.equal(summary, want[2])
+    assert torch.equal(work[:B], mag) and (work[B] == 3.0).all().item()
+    for code, args, kw in ((SA_ESHAPE, (x[:3], du), dict(group=4)), (SA_EINVAL, (x, du), dict(group=3)), (SA_EINVAL, (x, None), {}),
+                           (SA_EINVAL, (x, du, None, 7, 7), {}), (SA_ESHAPE, (x, du[:100]), {}),
+                           (SA_ESHAPE, (x, du), dict(work=torch.empty((B - 1, N), dtype=torch.float32, device="cuda"))),
+                           (SA_ESHAPE, (x, du), dict(out=torch.zeros((B, 6), dtype=torch.int32, device="cuda"))),
+                           (SA_ESHAPE, (x, du), dict(summary=True)),
+                           (SA_ESHAPE, (x, du), dict(group=4, out=torch.zeros((B, 10), dtype=torch.int32, device="cuda")))):
+        work.fill_(3.0)
+        with pytest.raises(SpecanError) as e:
+            ch.mask_trigger_f32(*args, **dict(dict(work=work), **kw))
+        torch.cuda.synchronize()
+        assert e.value.code == code and (work == 3.0).all().item(), kw
+
+
+@pytest.mark.parametrize("form,rows", [("mag", 65539), ("rec", 32771)])
+def test_every_row_past_4_gib(ch, torch_mod, form, rows):
+    """The input tiled from one period of 1027 rows until its last rows start beyond byte 2^32 (the batches the rules of
+    offset_cases give such rows), both limits and the summary, into outputs of 0xFF bytes: ALL rows equal the call on one
+    period, and the summary counts every one of them."""
+    from fpga_real_time_fft_analyzer_amd import frames
+    torch = torch_mod
+    P = oc.period(1)
+    row = (N,) if form == "mag" else (N, 2)
+    assert rows == oc.batch({"in": int(np.prod(row)) * 4}, 1) and (rows - 1) * int(np.prod(row)) * 4 >= 1 << 32
+    field = None if form == "mag" else "power"
+    gen = torch.Generator(device="cuda")
+    gen.manual_seed(2360)
+    per = 0.001 + 0.78 * torch.rand((P,) + row, device="cuda", generator=gen)
+    x = torch.empty((rows,) + row, dtype=torch.float32, device="cuda")
+    for s in range(0, rows, P):
+        n = min(P, rows - s)
+        x[s:s + n] = per[:n]
+    assert x[rows - 1:].data_ptr() - x.data_ptr() >= 1 << 32
+    rng = np.random.default_rng(2361)
+    upper = rng.uniform(0.7808, 0.7812, N).astype(np.float32)       # the top 0.03 % of the points lie above it: some rows fail
+    lower = rng.uniform(0.0005, 0.0012, N).astype(np.float32)
+    du, dl = to_device(torch, upper), to_device(torch, lower)
+    lo, hi = 100, 16001
+    ref_i, ref_f, ref_s = ch.mask_test(x[:P], du, dl, lo, hi, field=field, summary=True)
+    ref = oc.as_rows(torch, torch.cat([ref_i, ref_f.view(torch.int32)], dim=1).contiguous(), P).clone()
+    assert oc.vacuous(torch, ref, ref_f) is None
+    failing = ((ref_i[:, 0] > 0) | (ref_i[:, 1] > 0))
+    assert 0 < int(failing.sum()) < P and torch.unique(ref_i[:, 4]).numel() > 8
+    h = per[:3].cpu().numpy()
+    want, _ = frames.mask_of_rows(h, upper, lower, lo, hi, field=field)
+    assert same_records(_host(ref_i[:3], ref_f[:3]), want)
+    out = torch.full((rows * 40,), 0xFF, dtype=torch.uint8, device="cuda").view(torch.int32).view(rows, 10)
+    summary = torch.full((4,), -9, dtype=torch.int32, device="cuda")
+    ch.mask_test(x, du, dl, lo, hi, field=field, out=out, summary=summary)
+    bad = oc.tiled_mismatch(torch, oc.as_rows(torch, out, rows), ref)
+    assert bad is None, (form, bad)
+    whole, tail = divmod(rows, P)
+    fails = torch.nonzero(failing).flatten()
+    n_over, n_under = (ref_i[:, 0] > 0), (ref_i[:, 1] > 0)
+    assert summary.tolist() == [whole * int(n_over.sum()) + int(n_over[:tail].sum()), whole * int(n_under.sum()) + int(n_under[:tail].sum()),
+                                int(fails[0]), max(int(f) + P * (whole if int(f) < tail else whole - 1) for f in fails.tolist())]
+    torch.cuda.synchronize()
+    del x, out
+    torch.cuda.empty_cache()
