@@ -1,7 +1,8 @@
 """ctypes binding of ``libspecan_hip.so`` (the C ABI declared in ``include/specan.h`` and ``include/specan_ext.h``) and of
 ``libspecan_fold.so`` (``include/specan_fold.h``), ``libspecan_peaks.so`` (``include/specan_peaks.h``),
 ``libspecan_rank.so`` (``include/specan_rank.h``), ``libspecan_hist.so`` (``include/specan_hist.h``),
-``libspecan_bands.so`` (``include/specan_bands.h``) and ``libspecan_mask.so`` (``include/specan_mask.h``).
+``libspecan_bands.so`` (``include/specan_bands.h``), ``libspecan_mask.so`` (``include/specan_mask.h``) and
+``libspecan_harm.so`` (``include/specan_harm.h``).
 
 This is the only place the shared libraries are loaded.  There is no CPU fallback: if the
 library is missing the import of any compute entry point raises, and creating a handle
@@ -21,6 +22,7 @@ RANK_LIB_PATH = os.path.join(_PKG, "libspecan_rank.so")      # include/specan_ra
 HIST_LIB_PATH = os.path.join(_PKG, "libspecan_hist.so")      # include/specan_hist.h: built by the same make
 BANDS_LIB_PATH = os.path.join(_PKG, "libspecan_bands.so")    # include/specan_bands.h: built by the same make
 MASK_LIB_PATH = os.path.join(_PKG, "libspecan_mask.so")      # include/specan_mask.h: built by the same make
+HARM_LIB_PATH = os.path.join(_PKG, "libspecan_harm.so")      # include/specan_harm.h: built by the same make
 CSRC = os.path.join(_PKG, "csrc")
 
 # error codes / constants (include/specan.h)
@@ -85,9 +87,9 @@ class SpecanError(RuntimeError):
 
 
 def build(verbose: bool = False) -> str:
-    """Compile the HIP extension in-tree for gfx950 (hipcc cross-compiles without a GPU): the seven libraries, LIB_PATH,
-    FOLD_LIB_PATH, PEAKS_LIB_PATH, RANK_LIB_PATH, HIST_LIB_PATH, BANDS_LIB_PATH and MASK_LIB_PATH, are the Makefile's first
-    target."""
+    """Compile the HIP extension in-tree for gfx950 (hipcc cross-compiles without a GPU): the eight libraries, LIB_PATH,
+    FOLD_LIB_PATH, PEAKS_LIB_PATH, RANK_LIB_PATH, HIST_LIB_PATH, BANDS_LIB_PATH, MASK_LIB_PATH and HARM_LIB_PATH, are the
+    Makefile's first target."""
     cmd = ["make", "-j4", "-C", CSRC]
     if not verbose:
         cmd.insert(1, "-s")
@@ -252,6 +254,34 @@ MASK_SIGNATURES = {
     "sa_mask_last_error": (C.c_char_p, []),
 }
 
+
+
+class HarmCfg(C.Structure):
+    """sa_harm_cfg of include/specan_harm.h: the parameters of a call, 28 bytes, a host struct."""
+    _fields_ = [("dc", C.c_int32), ("top", C.c_int32), ("lo", C.c_int32), ("hi", C.c_int32), ("fund", C.c_int32),
+                ("span", C.c_int32), ("order", C.c_int32)]
+
+
+class HarmRow(C.Structure):
+    """sa_harm_row of include/specan_harm.h: the record of one row, 168 bytes."""
+    _fields_ = [("power", C.c_double * 10), ("dist", C.c_double), ("nad", C.c_double), ("noise", C.c_double),
+                ("bin", C.c_int32 * 10), ("fund", C.c_float), ("spur", C.c_float), ("nonharm", C.c_float),
+                ("spur_bin", C.c_int32), ("nonharm_bin", C.c_int32), ("n_noise", C.c_int32)]
+
+
+# the entry points of include/specan_harm.h: libspecan_harm.so, the eighth product library, again without a handle (per row
+# of 16384 points the fundamental, the bands of its aliased harmonics, the worst spur and the power of the rest), bound by
+# harm_lib() and held name for name against that header (tests/test_f32_harm_cpu.py); no name is in the tables above
+SA_HARM_VERSION = 1
+SA_HARM_MAX, SA_HARM_SPAN_MAX, SA_HARM_TOP_MAX = 10, 64, 8193
+SA_HARM_IN_MAG, SA_HARM_IN_POINT_PEAK, SA_HARM_IN_POINT_POWER = 0, 1, 2
+HARM_SIGNATURES = {
+    "sa_harm_version": (_INT, []),
+    "sa_harm_f32": (_INT, [C.c_void_p, _INT, C.c_void_p, _INT, C.POINTER(HarmCfg), C.c_void_p]),
+    "sa_harm_check": (_INT, [_INT, C.c_uint64, C.c_uint64, _INT, C.POINTER(HarmCfg)]),
+    "sa_harm_last_error": (C.c_char_p, []),
+}
+
 _lib = None
 _fold_lib = None
 _peaks_lib = None
@@ -259,6 +289,7 @@ _rank_lib = None
 _hist_lib = None
 _bands_lib = None
 _mask_lib = None
+_harm_lib = None
 
 
 def _load(path: str, tables: tuple) -> C.CDLL:
@@ -337,3 +368,11 @@ def mask_lib() -> C.CDLL:
     if _mask_lib is None:
         _mask_lib = _load(MASK_LIB_PATH, (MASK_SIGNATURES,))
     return _mask_lib
+
+
+def harm_lib() -> C.CDLL:
+    """Load libspecan_harm.so (include/specan_harm.h), after torch as lib() does; raise loudly when it has not been built."""
+    global _harm_lib
+    if _harm_lib is None:
+        _harm_lib = _load(HARM_LIB_PATH, (HARM_SIGNATURES,))
+    return _harm_lib

@@ -138,6 +138,9 @@ _RANK_FIELDS = {None: abi.SA_RANK_IN_MAG, "peak": abi.SA_RANK_IN_POINT_PEAK, "po
 _BANDS_FIELDS = {None: abi.SA_BANDS_IN_MAG, "peak": abi.SA_BANDS_IN_POINT_PEAK, "power": abi.SA_BANDS_IN_POINT_POWER}
 # mask_test(field=...) -> the `field` of include/specan_mask.h: the same three layouts
 _MASK_FIELDS = {None: abi.SA_MASK_IN_MAG, "peak": abi.SA_MASK_IN_POINT_PEAK, "power": abi.SA_MASK_IN_POINT_POWER}
+# harmonics(field=...) -> the `field` of include/specan_harm.h: the same three layouts
+_HARM_FIELDS = {None: abi.SA_HARM_IN_MAG, "peak": abi.SA_HARM_IN_POINT_PEAK, "power": abi.SA_HARM_IN_POINT_POWER}
+_HARM_WORDS = C.sizeof(abi.HarmRow) // 4                                      # an sa_harm_row as int32 words: 42
 
 
 def output_spec(chain: _Chain, out_kind: Optional[str], B: int) -> tuple:
@@ -1180,6 +1183,99 @@ class SpectrumChain:
             return self.mask_test(rec, upper, lower, lo, hi, field="power", out=out, summary=summary)
         out, summary = self._mask_out(B, out, True if summary is None else summary)
         return self.mask_test(self._mag_full_in_work(x, B, scale, work), upper, lower, lo, hi, out=out, summary=summary)
+
+    @staticmethod
+    def _harm_args(order, span, lo, hi, fund, dc, top, field) -> tuple:
+        """The one validation of the arguments of the harmonic analysis: ``(field code of include/specan_harm.h, the
+        sa_harm_cfg with the defaults filled in)``, or SA_EINVAL."""
+        try:
+            cfg = frames._harm_args(order, span, lo, hi, fund, dc, top, field)
+        except ValueError as e:
+            raise SpecanError(abi.SA_EINVAL, str(e)) from None
+        return _HARM_FIELDS[field], abi.HarmCfg(*cfg)
+
+    def _harm_out(self, R: int, out: Optional[torch.Tensor]) -> torch.Tensor:
+        """The record tensor of the harmonic analysis of ``R`` rows, allocated when None: SA_ESHAPE where ``out`` is not the
+        contiguous int32 [R, 42] tensor on the handle's device."""
+        if out is None:
+            return torch.empty((R, _HARM_WORDS), dtype=torch.int32, device=self.device)
+        if (not isinstance(out, torch.Tensor) or tuple(out.shape) != (R, _HARM_WORDS) or out.dtype != torch.int32
+                or out.device != self.device or not out.is_contiguous()):
+            raise SpecanError(abi.SA_ESHAPE, f"out must be a contiguous torch.int32 tensor of shape ({R}, {_HARM_WORDS})")
+        return out
+
+    def harmonics(self, t: torch.Tensor, order: int = 5, span: int = 3, lo: Optional[int] = None, hi: Optional[int] = None,
+                  fund: Optional[int] = None, dc: Optional[int] = None, top: int = frames.HARM_TOP_MAX,
+                  field: Optional[str] = None, out: Optional[torch.Tensor] = None) -> tuple:
+        """The harmonic analysis of each row of ``t`` (include/specan_harm.h, sa_harm_f32): ``(sums float64 [R, 13], bins
+        int32 [R, 10], levels float32 [R, 3], marks int32 [R, 3])``, all views of the [R, 42] int32 record tensor (``out``,
+        allocated when None; one sa_harm_row of 168 bytes per row: ``out.cpu().numpy().view(frames.HARM_ROW)[:, 0]`` is what
+        frames.harm_metrics turns into SFDR, THD, SINAD, SNR and ENOB).  ``sums[r]`` is (power[0..9], dist, nad, noise),
+        ``bins[r]`` the fundamental's bin and the bins harmonics 2..order alias to (-1 in the unused slots), ``levels[r]``
+        (fund, spur, nonharm) and ``marks[r]`` (spur_bin, nonharm_bin, n_noise).  ``t`` is a float32 [R,16384] device tensor
+        -- what ``process_f32(out_kind='mag_full')`` or ``process_q15(out_kind='mag')`` wrote, squared bin by bin in the sums
+        -- or, with ``field='peak'`` (squared) or ``field='power'`` (taken as it is), float32 [R,16384,2], the records of
+        :meth:`fold_mag_f32` at bucket 1, :meth:`spectra_f32` or :meth:`spectra_q15`.
+
+        The analysed bins are ``[dc, top)`` (``dc`` defaults to ``span + 1``, ``top`` to 8193: a real input's spectrum).  The
+        fundamental is bin ``fund`` where given (coherent sampling), else the largest point of ``[lo, hi)`` (default: all
+        analysed bins), equal points to the lowest bin.  Harmonic h = 2..``order`` aliases to ``(h * k1) mod 16384`` folded
+        about 8192; a tone's band reaches ``span`` bins to either side, clipped to the analysed bins.  ``power[0]`` is the
+        float64 power of the fundamental's band F, ``power[h - 1]`` that of harmonic h's band less F, ``dist`` that of their
+        union, ``nad`` that of all analysed bins less F and ``noise`` that less the harmonics too, each the balanced pair tree
+        of :meth:`band_power`; ``spur`` is the largest point outside F and ``nonharm`` the largest that is in no harmonic's
+        band either.  frames.harm_of_rows is the numpy mirror, bit for bit.
+
+        The integers take ints only (a bool or a float is SA_EINVAL), ``order`` 1..10, ``span`` 0..64, ``0 <= dc < top <=
+        8193``, ``dc <= lo < hi <= top``; a wrong dtype of ``t`` is SA_EINVAL and a wrong shape SA_ESHAPE, all before any
+        device call.  One launch on the current stream of the handle's device -- the parameters travel in the launch's
+        arguments -- no atomics, nothing zeroed, no handle state, no workspace: it captures into a graph at any time.  Where
+        ``t`` is the result of a call made in overlap mode, call :meth:`flush` first.  Pointer contract (checked by the C
+        entry point, SA_EINVAL): ``t`` is 16-byte aligned, and the bytes of ``t`` and the R * 168 bytes of the records are
+        disjoint; buffers that merely touch are fine."""
+        code, cfg = self._harm_args(order, span, lo, hi, fund, dc, top, field)
+        R = self._check_in(t, torch.float32, (SA_N, 2) if code else SA_N)
+        out = self._harm_out(R, out)
+        L = abi.harm_lib()
+        with torch.cuda.device(self.device):         # the C call launches on the calling thread's current device
+            rc = L.sa_harm_f32(t.data_ptr(), code, out.data_ptr(), R, C.byref(cfg), self._stream())
+        if rc != abi.SA_OK:
+            raise SpecanError(rc, L.sa_harm_last_error().decode())
+        return out.view(torch.float64)[:, :13], out[:, 26:36], out.view(torch.float32)[:, 36:39], out[:, 39:]
+
+    def harmonics_f32(self, x: torch.Tensor, order: int = 5, span: int = 3, lo: Optional[int] = None, hi: Optional[int] = None,
+                      fund: Optional[int] = None, dc: Optional[int] = None, top: int = frames.HARM_TOP_MAX,
+                      group: Optional[int] = None, scale: float = 1.0 / 2048.0, work: Optional[torch.Tensor] = None,
+                      out: Optional[torch.Tensor] = None) -> tuple:
+        """The harmonic analysis of the float chain's spectra, without the spectra leaving the device: ``(sums, bins, levels,
+        marks)`` as :meth:`harmonics` returns them.  ``x`` is float32, int16 or packed uint8 exactly as for
+        :meth:`process_f32`; every filter mode and both precisions apply.
+
+        Without ``group`` (R = B) the call is ``process_f32(x, out_kind='mag_full', scale=scale)`` into the workspace of
+        :meth:`spectra_f32` followed by :meth:`harmonics`: the figures of every frame.  With ``group=A`` (2, 4, ..., 128;
+        R = B // A) it is ``spectra_f32(x, group=A, scale=scale, work=work)`` followed by ``harmonics(..., field='power')``:
+        the figures of the summed power of every A consecutive frames, where averaging has lowered the noise's variance
+        (frames.harm_metrics with ``unit='power'``).
+
+        The workspace is ``work`` or the cached tensor, as for :meth:`spectra_f32`, and in overlap mode the call joins every
+        outstanding call of the handle on the device (as :meth:`flush` does) before the analysis: the result is valid on the
+        current stream when the call returns, and the call lends nothing.  The parameters and ``out`` are refused as by
+        :meth:`harmonics`, ``group`` and a B that is no multiple of it as by :meth:`spectra_f32`, all before anything is
+        launched, and so is a wrong ``work``."""
+        self._harm_args(order, span, lo, hi, fund, dc, top, None)
+        if group is not None:
+            self._log2_fold(group, 1)
+        forms = FLOAT_CHAIN.inputs
+        dtype = x.dtype if isinstance(x, torch.Tensor) and x.dtype in forms else next(iter(forms))
+        B = self._check_in(x, dtype, forms[dtype][0])
+        if group is not None:
+            if B % int(group):
+                raise SpecanError(abi.SA_ESHAPE, f"the batch ({B} frames) must be a multiple of {int(group)}")
+            out = self._harm_out(B // int(group), out)             # refused here, before the chain is launched
+            rec = self.spectra_f32(x, group, 1, scale=scale, work=work)
+            return self.harmonics(rec, order, span, lo, hi, fund, dc, top, field="power", out=out)
+        out = self._harm_out(B, out)
+        return self.harmonics(self._mag_full_in_work(x, B, scale, work), order, span, lo, hi, fund, dc, top, out=out)
 
     def filter_q15(self, x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Window (+ integer IIR) only: the FFT input stream, [B,16384] int16.  ``x`` is [B,16384] int16 or the same

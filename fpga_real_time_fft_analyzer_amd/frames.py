@@ -633,6 +633,163 @@ def mask_margin_db(records, unit: str = "amplitude") -> tuple:
     return out[0], out[1]
 
 
+HARM_MAX = 10
+HARM_SPAN_MAX = 64
+HARM_TOP_MAX = FFT_SIZE // 2 + 1
+# sa_harm_row of include/specan_harm.h: the record of one row, 168 bytes without a gap
+HARM_ROW = np.dtype([("power", "<f8", (HARM_MAX,)), ("dist", "<f8"), ("nad", "<f8"), ("noise", "<f8"), ("bin", "<i4", (HARM_MAX,)),
+                     ("fund", "<f4"), ("spur", "<f4"), ("nonharm", "<f4"), ("spur_bin", "<i4"), ("nonharm_bin", "<i4"),
+                     ("n_noise", "<i4")])
+
+
+def _harm_args(order, span, lo, hi, fund, dc, top, field) -> tuple:
+    """``(dc, top, lo, hi, fund, span, order)`` of the harmonic analysis as ints, the defaults filled in (``dc = span + 1``,
+    ``lo = dc``, ``hi = top``, ``fund = -1`` for a search), or ValueError: every one an int (no bool, no float),
+    ``0 <= dc < top <= 8193``, ``dc <= lo < hi <= top``, ``fund`` None, -1 or in [dc, top), ``span`` 0..64, ``order`` 1..10;
+    ``field`` None, 'peak' or 'power'."""
+    for name, v, optional in (("order", order, False), ("span", span, False), ("lo", lo, True), ("hi", hi, True),
+                              ("fund", fund, True), ("dc", dc, True), ("top", top, False)):
+        if v is None and optional:
+            continue
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f"{name} must be an int")
+    order, span, top = int(order), int(span), int(top)
+    if not 0 <= span <= HARM_SPAN_MAX:
+        raise ValueError(f"span must be 0..{HARM_SPAN_MAX}")
+    if not 1 <= order <= HARM_MAX:
+        raise ValueError(f"order must be 1..{HARM_MAX}")
+    dc = span + 1 if dc is None else int(dc)
+    if not 0 <= dc < top <= HARM_TOP_MAX:
+        raise ValueError(f"the analysed bins must be 0 <= dc < top <= {HARM_TOP_MAX}")
+    lo = dc if lo is None else int(lo)
+    hi = top if hi is None else int(hi)
+    if not dc <= lo < hi <= top:
+        raise ValueError("the search range must be dc <= lo < hi <= top")
+    fund = -1 if fund is None else int(fund)
+    if fund != -1 and not dc <= fund < top:
+        raise ValueError("fund must be None, -1 or a bin in [dc, top)")
+    if not (field is None or isinstance(field, str)) or field not in RANK_FIELDS:
+        raise ValueError("field must be None, 'peak' or 'power'")
+    return dc, top, lo, hi, fund, span, order
+
+
+def harm_alias_bins(k1, order: int) -> np.ndarray:
+    """int64 [..., order]: the bins harmonics 1..``order`` of the fundamental bins ``k1`` alias to in a real spectrum of 16384
+    points: ``m = (h * k1) mod 16384``, folded about 8192."""
+    m = (np.asarray(k1, np.int64)[..., None] * np.arange(1, int(order) + 1)) % FFT_SIZE
+    return np.where(m <= FFT_SIZE // 2, m, FFT_SIZE - m)
+
+
+def _tree_sum(w: np.ndarray) -> np.ndarray:
+    """The balanced tree of adjacent pairs over the last axis (a power of two long), by explicit halving."""
+    while w.shape[-1] > 1:
+        w = w[..., 0::2] + w[..., 1::2]
+    return w[..., 0]
+
+
+def harm_of_rows(points, order: int = 5, span: int = 3, lo=None, hi=None, fund=None, dc=None, top: int = HARM_TOP_MAX, field=None):
+    """The harmonic analysis of float32 ``points`` [R,16384] -- or, with ``field`` 'peak' or 'power', of that float of the
+    records [R,16384,2]: a HARM_ROW array [R].  The numpy mirror of sa_harm_f32 (include/specan_harm.h), step for step:
+
+    - key: the point's bits with the sign cleared, compared as integers (a NaN above +inf, -0.0 as +0.0, denormals kept);
+      value: that float widened to float64, ``v = a * a`` for the magnitudes and for 'peak', ``v = a`` for 'power';
+    - fundamental ``k1``: ``fund`` where given, else ``np.argmax`` of the int64 keys of [lo, hi) -- the first of equal maxima;
+    - harmonic h = 2..order aliases to ``m = (h * k1) mod 16384``, ``k = m if m <= 8192 else 16384 - m``;
+    - the band of a tone at bin k is ``[max(k - span, dc), min(k + span + 1, top))``, possibly empty; ``F`` is that of k1,
+      ``B_h`` that of k_h less F, ``U`` the union of the B_h, ``A = [dc, top)``;
+    - a sum over a set: ``w = v`` inside it and +0.0 outside, ``T[0] = w``, ``T[l + 1] = T[l][0::2] + T[l][1::2]`` (the
+      explicit halving, 14 levels), not rounded.  ``power[0]`` is the sum over F and ``power[h - 1]`` over B_h (+0.0 in the
+      unused slots), ``dist`` over U, ``nad`` over A - F, ``noise`` over A - F - U: five kinds of tree, each summed on its own;
+    - ``fund`` is the point at k1 (sign cleared); ``spur, spur_bin`` the largest key of A - F and its bin, ``nonharm,
+      nonharm_bin`` that of A - F - U, first of equal maxima, (+0.0, -1) for an empty set; ``n_noise`` the bins of A - F - U;
+      ``bin`` is k1, k_2 .. k_order, -1 in the unused slots.
+
+    Defaults: ``dc = span + 1``, ``lo = dc``, ``hi = top``.  The integers are ints (no bool, no float), within the ranges of
+    the header: ValueError otherwise, and on a wrong dtype or shape."""
+    dc, top, lo, hi, fund, span, order = _harm_args(order, span, lo, hi, fund, dc, top, field)
+    points = np.ascontiguousarray(points)
+    shape = (FFT_SIZE,) if field is None else (FFT_SIZE, 2)
+    if points.dtype != np.float32 or points.ndim != 1 + len(shape) or points.shape[1:] != shape:
+        raise ValueError(f"points must be float32 [R, {', '.join(map(str, shape))}]")
+    if field is not None:
+        points = np.ascontiguousarray(points[..., RANK_FIELDS[field]])
+    R = points.shape[0]
+    bits = points.view(np.uint32) & np.uint32(0x7FFFFFFF)
+    keys = bits.astype(np.int64)
+    a = bits.view(np.float32).astype(np.float64)
+    rec = np.zeros(R, HARM_ROW)
+    rec["bin"] = -1
+    rows = np.arange(R)
+    idx = np.arange(FFT_SIZE)
+    k1 = np.full(R, fund, np.int64) if fund >= 0 else lo + np.argmax(keys[:, lo:hi], axis=1)
+    k = harm_alias_bins(k1, order)                                 # [R, order]; k[:, 0] is k1
+    rec["bin"][:, :order] = k
+    rec["fund"] = bits[rows, k1].view(np.float32)
+    b_lo, b_hi = np.maximum(k - span, dc), np.minimum(k + span + 1, top)
+    band = (idx >= b_lo[..., None]) & (idx < b_hi[..., None])      # [R, order, 16384]
+    F = band[:, 0]
+    A = np.broadcast_to((idx >= dc) & (idx < top), F.shape)
+    U = band[:, 1:].any(axis=1) & ~F
+    rest = A & ~F
+    noise = rest & ~U
+
+    def largest(member):
+        masked = np.where(member, keys, -1)
+        at = np.argmax(masked, axis=1)
+        some = masked[rows, at] >= 0
+        return np.where(some, bits[rows, at], 0).astype(np.uint32).view(np.float32), np.where(some, at, -1)
+
+    with np.errstate(over="ignore", invalid="ignore"):
+        v = a if field == "power" else a * a
+        rec["power"][:, 0] = _tree_sum(np.where(F, v, 0.0))
+        for h in range(1, order):
+            rec["power"][:, h] = _tree_sum(np.where(band[:, h] & ~F, v, 0.0))
+        rec["dist"] = _tree_sum(np.where(U, v, 0.0))
+        rec["nad"] = _tree_sum(np.where(rest, v, 0.0))
+        rec["noise"] = _tree_sum(np.where(noise, v, 0.0))
+    rec["spur"], rec["spur_bin"] = largest(rest)
+    rec["nonharm"], rec["nonharm_bin"] = largest(noise)
+    rec["n_noise"] = noise.sum(axis=1)
+    return rec
+
+
+def harm_metrics(records, unit: str = "amplitude") -> dict:
+    """The dynamic figures of harmonic records (the HARM_ROW array of :func:`harm_of_rows`, or the device's records viewed with
+    that dtype), float64 host arithmetic, as a dict of arrays [R] (``hd_dbc`` [R, 10]):
+
+    - ``sfdr_dbc``: ``20 log10(fund / spur)``, ``10 log10`` with ``unit='power'`` (the points of ``field='power'``);
+      ``sfdr_nonharm_dbc`` the same against ``nonharm``;
+    - ``thd_dbc``: ``10 log10(dist / power[0])``; ``hd_dbc[:, h - 1]``: ``10 log10(power[h - 1] / power[0])`` of harmonic h,
+      0 in column 0, NaN in the unused slots;
+    - ``sinad_db``: ``10 log10(power[0] / nad)``; ``snr_db``: ``10 log10(power[0] / noise)``; ``enob``: ``(sinad_db - 1.76) /
+      6.02``.
+
+    The sums are powers whatever the unit of the points.  A ratio with a zero numerator is -inf and with a zero denominator
+    +inf; 0 / 0 and a NaN give a NaN."""
+    if not isinstance(unit, str) or unit not in _MASK_UNITS:
+        raise ValueError("unit must be 'amplitude' or 'power'")
+    records = np.asarray(records)
+    if records.dtype != HARM_ROW:
+        raise ValueError("records must have the dtype HARM_ROW")
+    p1 = records["power"][..., 0]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        def db(num, den, scale=10.0):
+            return scale * np.log10(np.asarray(num, np.float64) / np.asarray(den, np.float64))
+
+        hd = db(records["power"], p1[..., None])
+        hd = np.where(records["bin"] >= 0, hd, np.nan)
+        sinad = db(p1, records["nad"])
+        return {
+            "sfdr_dbc": db(records["fund"], records["spur"], _MASK_UNITS[unit]),
+            "sfdr_nonharm_dbc": db(records["fund"], records["nonharm"], _MASK_UNITS[unit]),
+            "thd_dbc": db(records["dist"], p1),
+            "hd_dbc": hd,
+            "sinad_db": sinad,
+            "snr_db": db(p1, records["noise"]),
+            "enob": (sinad - 1.76) / 6.02,
+        }
+
+
 def decode_iq_components(frame_bytes: bytes):
     """Same result as gui.py:262-270: (re, im) as float32 arrays."""
     re, im = _iq(frame_bytes)
