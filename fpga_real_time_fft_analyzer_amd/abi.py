@@ -1,8 +1,6 @@
-"""ctypes binding of ``libspecan_hip.so`` (the C ABI declared in ``include/specan.h`` and ``include/specan_ext.h``) and of
-``libspecan_fold.so`` (``include/specan_fold.h``), ``libspecan_peaks.so`` (``include/specan_peaks.h``),
-``libspecan_rank.so`` (``include/specan_rank.h``), ``libspecan_hist.so`` (``include/specan_hist.h``),
-``libspecan_bands.so`` (``include/specan_bands.h``), ``libspecan_mask.so`` (``include/specan_mask.h``) and
-``libspecan_harm.so`` (``include/specan_harm.h``).
+"""ctypes binding of ``libspecan_hip.so`` (the C ABI declared in ``include/specan.h`` and ``include/specan_ext.h``) and of the
+handle-less libraries of the table ``LIBRARIES``: for every short name ``x`` there, ``libspecan_x.so`` declared in
+``include/specan_x.h``, its path ``X_LIB_PATH``, its entry points ``X_SIGNATURES`` and its loader ``x_lib()``.
 
 This is the only place the shared libraries are loaded.  There is no CPU fallback: if the
 library is missing the import of any compute entry point raises, and creating a handle
@@ -16,13 +14,6 @@ import subprocess
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_PKG, "libspecan_hip.so")
-FOLD_LIB_PATH = os.path.join(_PKG, "libspecan_fold.so")      # include/specan_fold.h: built by the same make
-PEAKS_LIB_PATH = os.path.join(_PKG, "libspecan_peaks.so")    # include/specan_peaks.h: built by the same make
-RANK_LIB_PATH = os.path.join(_PKG, "libspecan_rank.so")      # include/specan_rank.h: built by the same make
-HIST_LIB_PATH = os.path.join(_PKG, "libspecan_hist.so")      # include/specan_hist.h: built by the same make
-BANDS_LIB_PATH = os.path.join(_PKG, "libspecan_bands.so")    # include/specan_bands.h: built by the same make
-MASK_LIB_PATH = os.path.join(_PKG, "libspecan_mask.so")      # include/specan_mask.h: built by the same make
-HARM_LIB_PATH = os.path.join(_PKG, "libspecan_harm.so")      # include/specan_harm.h: built by the same make
 CSRC = os.path.join(_PKG, "csrc")
 
 # error codes / constants (include/specan.h)
@@ -87,9 +78,8 @@ class SpecanError(RuntimeError):
 
 
 def build(verbose: bool = False) -> str:
-    """Compile the HIP extension in-tree for gfx950 (hipcc cross-compiles without a GPU): the eight libraries, LIB_PATH,
-    FOLD_LIB_PATH, PEAKS_LIB_PATH, RANK_LIB_PATH, HIST_LIB_PATH, BANDS_LIB_PATH, MASK_LIB_PATH and HARM_LIB_PATH, are the
-    Makefile's first target."""
+    """Compile the HIP extension in-tree for gfx950 (hipcc cross-compiles without a GPU): LIB_PATH and the library of every
+    row of LIBRARIES are the Makefile's first target."""
     cmd = ["make", "-j4", "-C", CSRC]
     if not verbose:
         cmd.insert(1, "-s")
@@ -282,14 +272,15 @@ HARM_SIGNATURES = {
     "sa_harm_last_error": (C.c_char_p, []),
 }
 
-_lib = None
-_fold_lib = None
-_peaks_lib = None
-_rank_lib = None
-_hist_lib = None
-_bands_lib = None
-_mask_lib = None
-_harm_lib = None
+# the handle-less libraries: short name x -> (file name beside LIB_PATH, entry points); include/specan_x.h declares them and
+# the same make builds them.  A new library is a row here and its name in the two lines that spell the public names out.
+LIBRARIES = {x: (f"libspecan_{x}.so", table) for x, table in (
+    ("fold", FOLD_SIGNATURES), ("peaks", PEAKS_SIGNATURES), ("rank", RANK_SIGNATURES), ("hist", HIST_SIGNATURES),
+    ("bands", BANDS_SIGNATURES), ("mask", MASK_SIGNATURES), ("harm", HARM_SIGNATURES))}
+(FOLD_LIB_PATH, PEAKS_LIB_PATH, RANK_LIB_PATH, HIST_LIB_PATH, BANDS_LIB_PATH, MASK_LIB_PATH,
+ HARM_LIB_PATH) = (os.path.join(_PKG, name) for name, _ in LIBRARIES.values())
+
+_loaded = {}                     # path -> the library, mapped and bound: each is loaded once
 
 
 def _load(path: str, tables: tuple) -> C.CDLL:
@@ -314,65 +305,30 @@ def _load(path: str, tables: tuple) -> C.CDLL:
     return L
 
 
+def _loaded_once(path: str, tables: tuple) -> C.CDLL:
+    """The one cached loader: _load on the first call for ``path``, the same library afterwards."""
+    if path not in _loaded:
+        _loaded[path] = _load(path, tables)
+    return _loaded[path]
+
+
 def lib() -> C.CDLL:
     """Load the shared library; raise loudly when it has not been built."""
-    global _lib
-    if _lib is None:
-        _lib = _load(LIB_PATH, (SIGNATURES, EXT_SIGNATURES))
-    return _lib
+    return _loaded_once(LIB_PATH, (SIGNATURES, EXT_SIGNATURES))
 
 
-def fold_lib() -> C.CDLL:
-    """Load libspecan_fold.so (include/specan_fold.h), after torch as lib() does; raise loudly when it has not been built."""
-    global _fold_lib
-    if _fold_lib is None:
-        _fold_lib = _load(FOLD_LIB_PATH, (FOLD_SIGNATURES,))
-    return _fold_lib
+def _loader(x: str):
+    """``x_lib`` for a row of LIBRARIES: the public function that takes no argument and returns that library, loaded once."""
+    name, table = LIBRARIES[x]
+    path = os.path.join(_PKG, name)
+
+    def load() -> C.CDLL:
+        return _loaded_once(path, (table,))
+    load.__name__ = load.__qualname__ = f"{x}_lib"
+    load.__doc__ = f"Load {name} (include/specan_{x}.h), after torch as lib() does; raise loudly when it has not been built."
+    return load
 
 
-def peaks_lib() -> C.CDLL:
-    """Load libspecan_peaks.so (include/specan_peaks.h), after torch as lib() does; raise loudly when it has not been built."""
-    global _peaks_lib
-    if _peaks_lib is None:
-        _peaks_lib = _load(PEAKS_LIB_PATH, (PEAKS_SIGNATURES,))
-    return _peaks_lib
+fold_lib, peaks_lib, rank_lib, hist_lib, bands_lib, mask_lib, harm_lib = map(_loader, LIBRARIES)
 
 
-def rank_lib() -> C.CDLL:
-    """Load libspecan_rank.so (include/specan_rank.h), after torch as lib() does; raise loudly when it has not been built."""
-    global _rank_lib
-    if _rank_lib is None:
-        _rank_lib = _load(RANK_LIB_PATH, (RANK_SIGNATURES,))
-    return _rank_lib
-
-
-def hist_lib() -> C.CDLL:
-    """Load libspecan_hist.so (include/specan_hist.h), after torch as lib() does; raise loudly when it has not been built."""
-    global _hist_lib
-    if _hist_lib is None:
-        _hist_lib = _load(HIST_LIB_PATH, (HIST_SIGNATURES,))
-    return _hist_lib
-
-
-def bands_lib() -> C.CDLL:
-    """Load libspecan_bands.so (include/specan_bands.h), after torch as lib() does; raise loudly when it has not been built."""
-    global _bands_lib
-    if _bands_lib is None:
-        _bands_lib = _load(BANDS_LIB_PATH, (BANDS_SIGNATURES,))
-    return _bands_lib
-
-
-def mask_lib() -> C.CDLL:
-    """Load libspecan_mask.so (include/specan_mask.h), after torch as lib() does; raise loudly when it has not been built."""
-    global _mask_lib
-    if _mask_lib is None:
-        _mask_lib = _load(MASK_LIB_PATH, (MASK_SIGNATURES,))
-    return _mask_lib
-
-
-def harm_lib() -> C.CDLL:
-    """Load libspecan_harm.so (include/specan_harm.h), after torch as lib() does; raise loudly when it has not been built."""
-    global _harm_lib
-    if _harm_lib is None:
-        _harm_lib = _load(HARM_LIB_PATH, (HARM_SIGNATURES,))
-    return _harm_lib

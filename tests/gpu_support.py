@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 
 from conftest import N
+from native import Lds, gpu_helper
 
 
 @pytest.fixture(scope="module")
@@ -11,6 +12,13 @@ def torch_mod():
     import torch
     assert torch.cuda.is_available()
     return torch
+
+
+@pytest.fixture(scope="module")
+def lds_fill(tmp_path_factory, torch_mod):
+    """tests/hip/lds_fill.hip, built and bound once per module that asks for it: lds_fill(word) writes `word` to all of the
+    LDS of every CU, on the current stream."""
+    return Lds(gpu_helper(tmp_path_factory.mktemp("lds_fill"), "lds_fill"), torch_mod).fill
 
 
 @pytest.fixture()

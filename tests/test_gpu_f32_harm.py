@@ -15,8 +15,7 @@ import pytest
 
 import offset_cases as oc
 from conftest import N, load_golden
-from gpu_support import ch, to_device, torch_mod  # noqa: F401 (fixtures)
-from native import Lds, gpu_helper
+from gpu_support import ch, lds_fill, to_device, torch_mod  # noqa: F401 (fixtures)
 from test_f32_bands_cpu import noise_rows, same_bits, wide_rows
 from test_f32_harm_cpu import FIELDS, GOOD, HALF, plant, planted, records_of, same_records
 from test_gpu_f32_peaks import _inputs, _tones
@@ -260,13 +259,6 @@ def test_exactly_the_record_bytes_are_written_and_a_refused_call_writes_nothing(
             ch.harmonics(*args, **kw)
         assert e.value.code == code, (args[0].shape, kw)
     assert tuple(ch.harmonics(torch.empty((0, N), dtype=torch.float32, device="cuda"))[0].shape) == (0, 13)
-
-
-@pytest.fixture(scope="module")
-def lds_fill(tmp_path_factory, torch_mod):
-    """tests/hip/lds_fill.hip, built and bound as tests/test_gpu_f32_rank.py does: lds_fill(word) writes `word` to all of
-    the LDS of every CU, on the current stream."""
-    return Lds(gpu_helper(tmp_path_factory.mktemp("lds_fill_harm"), "lds_fill"), torch_mod).fill
 
 
 def test_poisoned_lds(ch, torch_mod, lds_fill):

@@ -18,8 +18,7 @@ import numpy as np
 import pytest
 
 from conftest import N, load_golden
-from gpu_support import ch, to_device, torch_mod  # noqa: F401 (fixtures)
-from native import Lds, gpu_helper
+from gpu_support import ch, lds_fill, to_device, torch_mod  # noqa: F401 (fixtures)
 from test_gpu_f32_peaks import _inputs, _tones
 
 pytestmark = pytest.mark.gpu
@@ -255,13 +254,6 @@ def test_exactly_the_output_bytes_are_written_and_a_refused_call_writes_nothing(
     mine = torch.empty((2, N // 16, 5), dtype=torch.uint32, device="cuda")
     got = ch.level_hist(x, edges, group=1, bucket=16, out=mine)
     assert got.data_ptr() == mine.data_ptr() and torch.equal(_host(mine), _want(torch, pts, edges, group=1, bucket=16))
-
-
-@pytest.fixture(scope="module")
-def lds_fill(tmp_path_factory, torch_mod):
-    """tests/hip/lds_fill.hip, built and bound as tests/test_gpu_f32_rank.py does: lds_fill(word) writes `word` to all of
-    the LDS of every CU, on the current stream."""
-    return Lds(gpu_helper(tmp_path_factory.mktemp("lds_fill_hist"), "lds_fill"), torch_mod).fill
 
 
 def test_poisoned_lds(ch, torch_mod, lds_fill):

@@ -14,8 +14,7 @@ import pytest
 
 import offset_cases as oc
 from conftest import N, load_golden
-from gpu_support import ch, check_overlap_profiling_and_graph_capture, to_device, torch_mod  # noqa: F401 (fixtures)
-from native import Lds, gpu_helper
+from gpu_support import ch, check_overlap_profiling_and_graph_capture, lds_fill, to_device, torch_mod  # noqa: F401 (fixtures)
 from test_f32_mask_cpu import (FIELDS, GAPS, aimed_narrow, aimed_wide, edge_case, edge_ranges, planted, records_of,
                                same_records)
 from test_gpu_f32_peaks import _inputs, _tones
@@ -262,13 +261,6 @@ def test_exactly_the_output_bytes_are_written_and_a_refused_call_writes_nothing(
         with pytest.raises(SpecanError) as e:
             ch.mask_test(*args, **kw)
         assert e.value.code == code, (args[0].shape, kw)
-
-
-@pytest.fixture(scope="module")
-def lds_fill(tmp_path_factory, torch_mod):
-    """tests/hip/lds_fill.hip, built and bound as tests/test_gpu_f32_rank.py does: lds_fill(word) writes `word` to all of
-    the LDS of every CU, on the current stream."""
-    return Lds(gpu_helper(tmp_path_factory.mktemp("lds_fill_mask"), "lds_fill"), torch_mod).fill
 
 
 def test_poisoned_lds(ch, torch_mod, lds_fill):

@@ -14,8 +14,7 @@ import numpy as np
 import pytest
 
 from conftest import N, load_golden
-from gpu_support import ch, to_device, torch_mod  # noqa: F401 (fixtures)
-from native import Lds, gpu_helper
+from gpu_support import ch, lds_fill, to_device, torch_mod  # noqa: F401 (fixtures)
 
 pytestmark = pytest.mark.gpu
 
@@ -302,13 +301,6 @@ def test_exactly_the_output_bytes_are_written_and_a_refused_call_writes_nothing(
     assert mag.data_ptr() == mine.data_ptr() and bins.data_ptr() == mine.data_ptr() + 4
     want = frames.peaks_of_rows(wide, K)
     assert np.array_equal(mine.cpu().numpy()[..., 1], want[1]) and np.array_equal(_bits(mag.contiguous().cpu().numpy()), _bits(want[0]))
-
-
-@pytest.fixture(scope="module")
-def lds_fill(tmp_path_factory, torch_mod):
-    """tests/hip/lds_fill.hip, built and bound as tests/test_gpu_isolation.py does: lds_fill(word) writes `word` to all of
-    the LDS of every CU, on the current stream."""
-    return Lds(gpu_helper(tmp_path_factory.mktemp("lds_fill_peaks"), "lds_fill"), torch_mod).fill
 
 
 def test_poisoned_lds(ch, torch_mod, wide, lds_fill):

@@ -16,8 +16,7 @@ import numpy as np
 import pytest
 
 from conftest import N, load_golden
-from gpu_support import ch, to_device, torch_mod  # noqa: F401 (fixtures)
-from native import Lds, gpu_helper
+from gpu_support import ch, lds_fill, to_device, torch_mod  # noqa: F401 (fixtures)
 from test_f32_rank_cpu import ONE, ONE_UP, SPECIALS, SPECIALS_TOP6
 from test_gpu_f32_peaks import EDGES, _inputs, _tones
 
@@ -260,13 +259,6 @@ def test_exactly_the_output_bytes_are_written_and_a_refused_call_writes_nothing(
     got = ch.order_stats(x, ranks, out=mine)
     assert got.data_ptr() == mine.data_ptr()
     _same(_bits(mine.cpu().numpy()), wide, ranks, "out=")
-
-
-@pytest.fixture(scope="module")
-def lds_fill(tmp_path_factory, torch_mod):
-    """tests/hip/lds_fill.hip, built and bound as tests/test_gpu_f32_peaks.py does: lds_fill(word) writes `word` to all of
-    the LDS of every CU, on the current stream."""
-    return Lds(gpu_helper(tmp_path_factory.mktemp("lds_fill_rank"), "lds_fill"), torch_mod).fill
 
 
 def test_poisoned_lds(ch, torch_mod, wide, lds_fill):
