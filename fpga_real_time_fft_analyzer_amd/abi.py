@@ -272,13 +272,36 @@ HARM_SIGNATURES = {
     "sa_harm_last_error": (C.c_char_p, []),
 }
 
+
+class Signal(C.Structure):
+    """sa_signal of include/specan_signals.h: one record of the signal list, 24 bytes."""
+    _fields_ = [("start", C.c_int32), ("stop", C.c_int32), ("peak", C.c_float), ("peak_bin", C.c_int32), ("power", C.c_double)]
+
+
+# the entry points of include/specan_signals.h: libspecan_signals.so, the ninth product library, again without a handle (per
+# row of 16384 points the runs of bins above the row's threshold with their bounds, peak and power, and the row's counts),
+# bound by signals_lib() and held name for name against that header (tests/test_f32_signals_cpu.py); no name is in the tables
+# above
+SA_SIGNALS_VERSION = 1
+SA_SIGNALS_K_MAX = 32
+SA_SIGNALS_IN_MAG, SA_SIGNALS_IN_POINT_PEAK, SA_SIGNALS_IN_POINT_POWER = 0, 1, 2
+SIGNALS_SIGNATURES = {
+    "sa_signals_version": (_INT, []),
+    "sa_signals_f32": (_INT, [C.c_void_p, _INT, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, _INT, _INT, _INT, _INT, _INT, _INT,
+                              C.c_void_p]),
+    "sa_signals_check": (_INT, [_INT, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint64, _INT, _INT, _INT, _INT, _INT,
+                                _INT]),
+    "sa_signals_last_error": (C.c_char_p, []),
+}
+
 # the handle-less libraries: short name x -> (file name beside LIB_PATH, entry points); include/specan_x.h declares them and
 # the same make builds them.  A new library is a row here and its name in the two lines that spell the public names out.
 LIBRARIES = {x: (f"libspecan_{x}.so", table) for x, table in (
     ("fold", FOLD_SIGNATURES), ("peaks", PEAKS_SIGNATURES), ("rank", RANK_SIGNATURES), ("hist", HIST_SIGNATURES),
-    ("bands", BANDS_SIGNATURES), ("mask", MASK_SIGNATURES), ("harm", HARM_SIGNATURES))}
-(FOLD_LIB_PATH, PEAKS_LIB_PATH, RANK_LIB_PATH, HIST_LIB_PATH, BANDS_LIB_PATH, MASK_LIB_PATH,
- HARM_LIB_PATH) = (os.path.join(_PKG, name) for name, _ in LIBRARIES.values())
+    ("bands", BANDS_SIGNATURES), ("mask", MASK_SIGNATURES), ("harm", HARM_SIGNATURES),
+    ("signals", SIGNALS_SIGNATURES))}
+(FOLD_LIB_PATH, PEAKS_LIB_PATH, RANK_LIB_PATH, HIST_LIB_PATH, BANDS_LIB_PATH, MASK_LIB_PATH, HARM_LIB_PATH,
+ SIGNALS_LIB_PATH) = (os.path.join(_PKG, name) for name, _ in LIBRARIES.values())
 
 _loaded = {}                     # path -> the library, mapped and bound: each is loaded once
 
@@ -329,6 +352,6 @@ def _loader(x: str):
     return load
 
 
-fold_lib, peaks_lib, rank_lib, hist_lib, bands_lib, mask_lib, harm_lib = map(_loader, LIBRARIES)
+fold_lib, peaks_lib, rank_lib, hist_lib, bands_lib, mask_lib, harm_lib, signals_lib = map(_loader, LIBRARIES)
 
 

@@ -790,6 +790,107 @@ def harm_metrics(records, unit: str = "amplitude") -> dict:
         }
 
 
+SIGNALS_K_MAX = 32
+SIGNALS_GAP_MAX = FFT_SIZE - 1
+# sa_signal of include/specan_signals.h: one record of the signal list, 24 bytes without a gap
+SIGNAL = np.dtype([("start", "<i4"), ("stop", "<i4"), ("peak", "<f4"), ("peak_bin", "<i4"), ("power", "<f8")])
+
+
+def _signals_args(k, lo, hi, gap, min_width, field) -> tuple:
+    """``(k, lo, hi, gap, min_width)`` of the signal list as ints, or ValueError: every one an int (no bool, no float), ``k``
+    1..32, ``0 <= lo < hi <= 16384``, ``gap`` 0..16383, ``min_width`` 1..16384; ``field`` None, 'peak' or 'power'."""
+    for name, v in (("k", k), ("lo", lo), ("hi", hi), ("gap", gap), ("min_width", min_width)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f"{name} must be an int")
+    k, lo, hi, gap, min_width = int(k), int(lo), int(hi), int(gap), int(min_width)
+    if not 1 <= k <= SIGNALS_K_MAX:
+        raise ValueError(f"k must be 1..{SIGNALS_K_MAX}")
+    if not 0 <= lo < hi <= FFT_SIZE:
+        raise ValueError(f"the range must be 0 <= lo < hi <= {FFT_SIZE}")
+    if not 0 <= gap <= SIGNALS_GAP_MAX:
+        raise ValueError(f"gap must be 0..{SIGNALS_GAP_MAX}")
+    if not 1 <= min_width <= FFT_SIZE:
+        raise ValueError(f"min_width must be 1..{FFT_SIZE}")
+    if not (field is None or isinstance(field, str)) or field not in RANK_FIELDS:
+        raise ValueError("field must be None, 'peak' or 'power'")
+    return k, lo, hi, gap, min_width
+
+
+def _threshold_key(threshold) -> int:
+    """The key of a threshold common to all rows, or ValueError: a number that is +0.0 .. +inf as a float32."""
+    if isinstance(threshold, bool) or not isinstance(threshold, (int, float, np.integer, np.floating)):
+        raise ValueError("threshold must be a number")
+    key = int(np.array([threshold], np.float32).view(np.uint32)[0])
+    if key > 0x7F800000:
+        raise ValueError("threshold must be +0.0 .. +inf: no NaN, no sign bit")
+    return key
+
+
+def signals_of_rows(points, k: int = 16, threshold=0.0, lo: int = 0, hi: int = FFT_SIZE, gap: int = 0, min_width: int = 1,
+                    field=None):
+    """The signal list of float32 ``points`` [R,16384] -- or, with ``field`` 'peak' or 'power', of that float of the records
+    [R,16384,2]: ``(records SIGNAL [R, k], stats int32 [R, 3])``.  The numpy mirror of sa_signals_f32
+    (include/specan_signals.h), step for step:
+
+    - key: the point's bits with the sign cleared, compared as integers (a NaN above +inf, -0.0 as +0.0, denormals kept);
+    - threshold: a number, +0.0 .. +inf, whose key is that of every row, or a float32 array [R] keyed like the points: a
+      negative value counts by its magnitude, a NaN passes only NaN points;
+    - on: ``lo <= i < hi``, ``u[i] > 0`` and ``u[i] >= T_r``;
+    - closing: ``p[i]`` is the last on bin at or below i (a running maximum) and ``n[i]`` the first at or above it (a running
+      minimum from the right); an off bin with both is bridged where ``n[i] - p[i] - 1 <= gap``;
+    - segments: the runs of ``on | bridged`` (the differences of the mask), kept where ``stop - start >= min_width``; the
+      records are the first ``k`` kept, ``peak`` the largest key of [start, stop) as a float with ``peak_bin`` the first such
+      bin, ``power`` the balanced tree of adjacent pairs of :func:`bands_of_rows` over the band [start, stop); the unused slots
+      are (-1, -1, +0.0, -1, +0.0);
+    - stats: (kept segments before the truncation to k, on bins, the bins of all kept segments).
+
+    ``k`` is 1..32, ``0 <= lo < hi <= 16384``, ``gap`` 0..16383, ``min_width`` 1..16384, the integers ints (no bool, no
+    float): ValueError otherwise, and on a wrong dtype or shape."""
+    k, lo, hi, gap, min_width = _signals_args(k, lo, hi, gap, min_width, field)
+    points = np.ascontiguousarray(points)
+    shape = (FFT_SIZE,) if field is None else (FFT_SIZE, 2)
+    if points.dtype != np.float32 or points.ndim != 1 + len(shape) or points.shape[1:] != shape:
+        raise ValueError(f"points must be float32 [R, {', '.join(map(str, shape))}]")
+    if field is not None:
+        points = np.ascontiguousarray(points[..., RANK_FIELDS[field]])
+    R = points.shape[0]
+    if isinstance(threshold, np.ndarray):
+        if threshold.dtype != np.float32 or threshold.shape != (R,):
+            raise ValueError(f"a threshold per row must be float32 [{R}]")
+        T = (np.ascontiguousarray(threshold).view(np.uint32) & np.uint32(0x7FFFFFFF)).astype(np.int64)
+    else:
+        T = np.full(R, _threshold_key(threshold), np.int64)
+    bits = points.view(np.uint32) & np.uint32(0x7FFFFFFF)
+    keys = bits.astype(np.int64)
+    a = bits.view(np.float32).astype(np.float64)
+    idx = np.arange(FFT_SIZE)
+    on = (idx >= lo) & (idx < hi) & (keys > 0) & (keys >= T[:, None])
+    prev = np.maximum.accumulate(np.where(on, idx, -1), axis=1)
+    nxt = np.minimum.accumulate(np.where(on, idx, 2 * FFT_SIZE)[:, ::-1], axis=1)[:, ::-1]
+    closed = on | ((prev >= 0) & (nxt < 2 * FFT_SIZE) & (nxt - prev - 1 <= gap))
+    edges = np.diff(closed.astype(np.int8), axis=1, prepend=0, append=0)              # [R, 16385]: +1 at a start, -1 at a stop
+    rec = np.zeros((R, k), SIGNAL)
+    rec["start"] = rec["stop"] = rec["peak_bin"] = -1
+    stats = np.zeros((R, 3), np.int32)
+    stats[:, 1] = on.sum(axis=1)
+    with np.errstate(over="ignore", invalid="ignore"):
+        v = a if field == "power" else a * a
+        for r in range(R):
+            start, stop = np.nonzero(edges[r] == 1)[0], np.nonzero(edges[r] == -1)[0]
+            keep = stop - start >= min_width
+            start, stop = start[keep], stop[keep]
+            stats[r, 0], stats[r, 2] = len(start), (stop - start).sum()
+            m = min(len(start), k)
+            if m == 0:
+                continue
+            inside = (idx >= start[:m, None]) & (idx < stop[:m, None])                # [m, 16384]
+            at = np.argmax(np.where(inside, keys[r], -1), axis=1)
+            rec["start"][r, :m], rec["stop"][r, :m] = start[:m], stop[:m]
+            rec["peak"][r, :m], rec["peak_bin"][r, :m] = bits[r, at].view(np.float32), at
+            rec["power"][r, :m] = _tree_sum(np.where(inside, v[r], 0.0))
+    return rec, stats
+
+
 def decode_iq_components(frame_bytes: bytes):
     """Same result as gui.py:262-270: (re, im) as float32 arrays."""
     re, im = _iq(frame_bytes)

@@ -1,6 +1,6 @@
 """The reductions of ``SpectrumChain``: the calls of the handle-less libraries of abi.LIBRARIES -- the fold of float
-magnitudes, the peak table, the order statistics, the level histogram, the band power, the mask test and the harmonic
-analysis -- on tensors the caller has (``fold_mag_f32``, ``find_peaks``, ...) and composed with the float chain, the
+magnitudes, the peak table, the order statistics, the level histogram, the band power, the mask test, the harmonic
+analysis and the signal list -- on tensors the caller has (``fold_mag_f32``, ``find_peaks``, ...) and composed with the float chain, the
 spectra never leaving the device (``spectra_f32``, ``peak_table_f32``, ...).
 
 ``Reductions`` is a mixin of ``SpectrumChain`` (chain.py, which this module does not import): it reaches the handle through
@@ -20,10 +20,11 @@ from . import abi, frames
 from .abi import SA_N, SpecanError
 
 FOLD_GROUPS, FOLD_BUCKETS = frames.FOLD_GROUPS, frames.FOLD_BUCKETS
-# field=... -> the `field` of include/specan_{peaks,rank,bands,mask,harm}.h: plain magnitudes, or one float of (peak, power)
-# records; the five headers number the three layouts alike (SA_X_IN_MAG, SA_X_IN_POINT_PEAK, SA_X_IN_POINT_POWER)
+# field=... -> the `field` of include/specan_{peaks,rank,bands,mask,harm,signals}.h: plain magnitudes, or one float of (peak,
+# power) records; the six headers number the three layouts alike (SA_X_IN_MAG, SA_X_IN_POINT_PEAK, SA_X_IN_POINT_POWER)
 FIELDS = {None: 0, "peak": 1, "power": 2}
 HARM_WORDS = C.sizeof(abi.HarmRow) // 4                                       # an sa_harm_row as int32 words: 42
+SIGNAL_WORDS = C.sizeof(abi.Signal) // 4                                      # an sa_signal as int32 words: 6
 
 
 def _ints(*pairs) -> None:
@@ -642,3 +643,114 @@ class Reductions:
         return self._of_spectra(x, group, scale, work, lambda R: self._harm_out(R, out),
                                 lambda t, field, out: self.harmonics(t, order, span, lo, hi, fund, dc, top, field, out))
 
+
+    @staticmethod
+    def _signals_args(k, threshold, lo, hi, gap, min_width, field) -> int:
+        """The one validation of the arguments of the signal list: the ``field`` code of include/specan_signals.h, or
+        SA_EINVAL.  Of a threshold per row only the dtype is looked at here; :meth:`_signals_out` looks at the rest."""
+        try:
+            frames._signals_args(k, lo, hi, gap, min_width, field)
+            if not isinstance(threshold, torch.Tensor):
+                frames._threshold_key(threshold)
+        except ValueError as e:
+            raise SpecanError(abi.SA_EINVAL, str(e)) from None
+        if isinstance(threshold, torch.Tensor) and threshold.dtype != torch.float32:
+            raise SpecanError(abi.SA_EINVAL, "a threshold per row must be a torch.float32 tensor")
+        return FIELDS[field]
+
+    @staticmethod
+    def _as_float32(v) -> float:
+        """The number ``v`` rounded to float32, as a Python float; what is too large is inf."""
+        with np.errstate(over="ignore"):
+            return float(np.float32(v))
+
+    def _signals_out(self, R: int, k: int, threshold, out: Optional[torch.Tensor], stats: Optional[torch.Tensor]) -> tuple:
+        """``(out, stats)`` of the signal list of ``R`` rows, each allocated when None: SA_ESHAPE where a threshold per row is
+        not the contiguous float32 [R] tensor, ``out`` not the contiguous int32 [R, k, 6] tensor or ``stats`` not the contiguous
+        int32 [R, 3] tensor on the handle's device."""
+        if isinstance(threshold, torch.Tensor) and (tuple(threshold.shape) != (R,) or threshold.device != self.device
+                                                    or not threshold.is_contiguous()):
+            raise SpecanError(abi.SA_ESHAPE, f"a threshold per row must be a contiguous torch.float32 tensor of shape ({R},)")
+        return tuple(self._outs(("out", out, (R, k, SIGNAL_WORDS), torch.int32), ("stats", stats, (R, 3), torch.int32)))
+
+    def find_signals(self, t: torch.Tensor, k: int = 16, threshold=0.0, lo: int = 0, hi: int = SA_N, gap: int = 0,
+                     min_width: int = 1, field: Optional[str] = None, out: Optional[torch.Tensor] = None,
+                     stats: Optional[torch.Tensor] = None) -> tuple:
+        """The signal list of each row of ``t`` (include/specan_signals.h, sa_signals_f32): the runs of bins that stand above
+        a threshold.  Returns ``(bounds int32 [R,k,2], peak float32 [R,k], peak_bin int32 [R,k], power float64 [R,k], stats
+        int32 [R,3])``: the first four are views of the [R,k,6] int32 record tensor (``out``, allocated when None; one
+        sa_signal of 24 bytes per slot, frames.SIGNAL on the host), ``stats`` is allocated when None.  ``t`` is a float32
+        [R,16384] device tensor -- what ``process_f32(out_kind='mag_full')`` or ``process_q15(out_kind='mag')`` wrote, squared
+        bin by bin in the power -- or, with ``field='peak'`` (squared) or ``field='power'`` (taken as it is), float32
+        [R,16384,2], the records of :meth:`fold_mag_f32` at bucket 1, :meth:`spectra_f32` or :meth:`spectra_q15`.
+
+        A point's key is its bits with the sign cleared, as an integer; bin i is on when ``lo <= i < hi``, its key is not 0
+        and not below the threshold's.  ``threshold`` is a number (+0.0 .. +inf) for all rows or a contiguous float32 [R]
+        tensor on the handle's device, one per row and keyed like a point -- the noise floor of :meth:`order_stats` times a
+        factor, say, made on the device.  Off runs of at most ``gap`` bins between two on bins are bridged; the runs
+        ``[start, stop)`` of on or bridged bins that are ``min_width`` or more wide are the segments, and the first ``k`` in
+        ascending order the records: ``bounds`` (start, stop), the largest point with its bin (equal ones to the lowest), and
+        the float64 power of the band ``[start, stop)`` by the balanced pair tree of :meth:`band_power`; the unused slots are
+        (-1, -1, +0.0, -1, +0.0).  ``stats[r]`` is (segments kept before the truncation to k, on bins, bins of all kept
+        segments).  frames.signals_of_rows is the numpy mirror, bit for bit.
+
+        ``k`` is 1..32, ``0 <= lo < hi <= 16384``, ``gap`` 0..16383, ``min_width`` 1..16384, ints only (a bool or a float is
+        SA_EINVAL); a wrong dtype is SA_EINVAL and a wrong shape SA_ESHAPE, all before any device call.  One launch on the
+        current stream of the handle's device -- the parameters travel in the launch's arguments -- no atomics, nothing
+        zeroed, no handle state, no workspace: it captures into a graph at any time.  Where ``t`` is the result of a call made
+        in overlap mode, call :meth:`flush` first.  Pointer contract (checked by the C entry point, SA_EINVAL): ``t`` is
+        16-byte aligned, and the R * k * 24 bytes of the records and the R * 12 of ``stats`` meet neither each other nor the
+        bytes read; buffers that merely touch are fine."""
+        code = self._signals_args(k, threshold, lo, hi, gap, min_width, field)
+        R = self._check_in(t, torch.float32, (SA_N, 2) if code else SA_N)
+        out, stats = self._signals_out(R, int(k), threshold, out, stats)
+        per_row = isinstance(threshold, torch.Tensor)
+        self._call(abi.signals_lib(), "sa_signals_f32", t.data_ptr(), code, threshold.data_ptr() if per_row else None,
+                   0.0 if per_row else float(threshold), out.data_ptr(), stats.data_ptr(), R, int(k), int(lo), int(hi), int(gap),
+                   int(min_width))
+        return out[..., :2], out.view(torch.float32)[..., 2], out[..., 3], out.view(torch.float64)[..., 2], stats
+
+    def signals_f32(self, x: torch.Tensor, k: int = 16, threshold=None, factor=None, q=0.5, lo: int = 0, hi: int = SA_N,
+                    gap: int = 0, min_width: int = 1, group: Optional[int] = None, scale: float = 1.0 / 2048.0,
+                    work: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+                    stats: Optional[torch.Tensor] = None) -> tuple:
+        """The signal list of the float chain's spectra, without the spectra leaving the device: ``(bounds, peak, peak_bin,
+        power, stats, thr)``, the five values of :meth:`find_signals` and the threshold per row, float32 [R], or None where the
+        threshold is absolute.  ``x`` is float32, int16 or packed uint8 exactly as for :meth:`process_f32`; every filter mode
+        and both precisions apply.
+
+        Exactly one of ``threshold`` and ``factor`` is given.  ``threshold`` is absolute, as for :meth:`find_signals`.
+        ``factor``, a finite number above 0, makes the threshold ride on the noise: it is ``order_stats(t,
+        [frames.rank_of_quantile(q, hi - lo)], lo, hi, field)[:, 0] * float32(factor)`` -- the lower quantile ``q`` of the
+        bins ``[lo, hi)`` of each row (0.5: the median) times the factor, one float32 multiply on the current stream -- of the
+        very rows the signals are then found in.
+
+        Without ``group`` (R = B) the rows are ``process_f32(x, out_kind='mag_full', scale=scale)`` in the workspace of
+        :meth:`spectra_f32`: the signals of every frame.  With ``group=A`` (2, 4, ..., 128; R = B // A) they are
+        ``spectra_f32(x, group=A, scale=scale, work=work)`` with ``field='power'``: the signals of the summed power of every A
+        consecutive frames, the Welch estimate times A, the threshold in that unit.
+
+        The workspace is ``work`` or the cached tensor, as for :meth:`spectra_f32`, and in overlap mode the call joins every
+        outstanding call of the handle on the device (as :meth:`flush` does) before the search: the result is valid on the
+        current stream when the call returns, and the call lends nothing.  The parameters, ``out`` and ``stats`` are refused
+        as by :meth:`find_signals`, ``q`` as by :meth:`noise_floor_f32` (one number), ``group`` and a B that is no multiple
+        of it as by :meth:`spectra_f32`, all before anything is launched, and so is a wrong ``work``."""
+        self._signals_args(k, 0.0 if threshold is None else threshold, lo, hi, gap, min_width, None)
+        if (threshold is None) == (factor is None):
+            raise SpecanError(abi.SA_EINVAL, "exactly one of threshold and factor must be given")
+        if factor is not None:
+            if isinstance(factor, bool) or not isinstance(factor, (int, float, np.integer, np.floating)) \
+                    or not 0.0 < self._as_float32(factor) < float("inf"):
+                raise SpecanError(abi.SA_EINVAL, "factor must be a finite number above 0 as a float32")
+            try:
+                rank = frames.rank_of_quantile(q, int(hi) - int(lo))
+            except ValueError as e:
+                raise SpecanError(abi.SA_EINVAL, str(e)) from None
+
+        def reduce(t, field, outs):
+            thr = threshold
+            if factor is not None:
+                thr = self.order_stats(t, (rank,), lo, hi, field)[:, 0] * self._as_float32(factor)
+            return (*self.find_signals(t, k, thr, lo, hi, gap, min_width, field, *outs), thr if factor is not None else None)
+
+        return self._of_spectra(x, group, scale, work, lambda R: self._signals_out(R, int(k), threshold, out, stats), reduce)

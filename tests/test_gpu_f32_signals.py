@@ -1,0 +1,460 @@
+"""GPU: the signal list (include/specan_signals.h: sa_signals_f32 of libspecan_signals.so), through SpectrumChain.find_signals,
+SpectrumChain.signals_f32 and the C entry point.
+
+Every comparison is exact -- the float64 bits of the power (a NaN by position), the words of everything else -- against the
+numpy mirror frames.signals_of_rows, which tests/test_f32_signals_cpu.py holds against the header bin by bin.
+
+The kernel's ownership (csrc/signals_f32.hip): in round r thread t holds the four bins 1024 r + 4 t .. + 3, one 16-byte unit of
+magnitudes or two of records; the 256 bins of a wave in one round are a tile, node 4 r + wave of tree level 8; the on-mask is
+256 words of 64 bins, word t thread t's from the first barrier on.  The rows of the CPU file put the ends of segments and of
+gaps on both sides of every one of these boundaries."""
+import numpy as np
+import pytest
+
+import offset_cases as oc
+from conftest import N, load_golden
+from gpu_support import ch, lds_fill, to_device, torch_mod  # noqa: F401 (fixtures)
+from test_f32_bands_cpu import noise_rows, same_bits, wide_rows
+from test_f32_signals_cpu import BOUNDS, FIELDS, GAPS, edge_rows, gap_rows, many_rows, records_of, same_result, special_rows
+from test_gpu_f32_peaks import _inputs, _tones
+
+pytestmark = pytest.mark.gpu
+
+SA_OK, SA_EINVAL, SA_ESHAPE = 0, -1, -2
+WORDS = 6
+POISON = 0x7FC00001
+
+
+def _host(out, stats):
+    """the [R, k, 6] int32 record tensor as a SIGNAL array [R, k] on the host, with the counts"""
+    from fpga_real_time_fft_analyzer_amd import frames
+    return out.cpu().numpy().view(frames.SIGNAL)[..., 0], stats.cpu().numpy()
+
+
+def _run(ch, torch, x, k=16, threshold=0.0, **kw):
+    """find_signals on the device tensor -> (records, stats) on the host, the five views checked against them"""
+    R = x.shape[0]
+    out = torch.full((R, k, WORDS), POISON, dtype=torch.int32, device="cuda")
+    stats = torch.full((R, 3), POISON, dtype=torch.int32, device="cuda")
+    thr = to_device(torch, threshold) if isinstance(threshold, np.ndarray) else threshold
+    bounds, peak, peak_bin, power, st = ch.find_signals(x, k, thr, out=out, stats=stats, **kw)
+    rec, counts = _host(out, stats)
+    assert bounds.dtype == torch.int32 and tuple(bounds.shape) == (R, k, 2) and bounds.data_ptr() == out.data_ptr()
+    assert peak.dtype == torch.float32 and tuple(peak.shape) == (R, k) and peak_bin.dtype == torch.int32 and tuple(peak_bin.shape) == (R, k)
+    assert power.dtype == torch.float64 and tuple(power.shape) == (R, k) and st.data_ptr() == stats.data_ptr()
+    assert np.array_equal(bounds.cpu().numpy(), np.stack([rec["start"], rec["stop"]], -1))
+    assert np.array_equal(peak.cpu().numpy().view(np.int32), rec["peak"].view(np.int32)) and np.array_equal(peak_bin.cpu().numpy(), rec["peak_bin"])
+    assert same_bits(power.cpu().numpy(), rec["power"])
+    return rec, counts
+
+
+def _check(ch, torch, x, pts, field, tag, **kw):
+    """the device's records and counts against the mirror's on the same points: bit for bit"""
+    from fpga_real_time_fft_analyzer_amd import frames
+    want = frames.signals_of_rows(records_of(pts, field), field=field, **kw)
+    bad = same_result(_run(ch, torch, x, field=field, **kw), want)
+    assert bad is None, (tag, bad)
+    return want
+
+
+EDGE_CALLS = (dict(k=32, threshold=0.5), dict(k=4, threshold=0.5, lo=100, hi=16000), dict(k=32, threshold=0.5, lo=1025, hi=8191),
+              dict(k=7, threshold=0.5, min_width=3), dict(k=32, threshold=0.5, lo=99, hi=16001, gap=5, min_width=2),
+              dict(k=32, threshold=0.0), dict(k=1, threshold=1.5))
+
+
+@pytest.mark.parametrize("field", FIELDS)
+def test_edges_equal_the_mirror(ch, torch_mod, field):
+    """8 rows: segments that end at, start at, straddle and lie next to every boundary of BOUNDS -- unit, lane, word, tile
+    and wave, round -- bins 0 and 16383, lo and hi - 1 with an on bin just outside the range, ranges that cut segments."""
+    pts = edge_rows()
+    x = to_device(torch_mod, records_of(pts, field))
+    for kw in EDGE_CALLS:
+        rec, stats = _check(ch, torch_mod, x, pts, field, (field, kw), **kw)
+        assert (stats[:, 0] >= 1).any(), kw
+    rec, stats = _check(ch, torch_mod, x, pts, field, "all", k=32, threshold=0.5)
+    assert stats[:5, 0].tolist() == [len(BOUNDS)] * 5 and rec["start"][1, :len(BOUNDS)].tolist() == list(BOUNDS)
+    rec, stats = _check(ch, torch_mod, x, pts, field, "range", k=4, threshold=0.5, lo=100, hi=16000)
+    assert stats[6].tolist() == [3, 3, 3] and rec["start"][6, :3].tolist() == [100, 5000, 15999]
+
+
+def test_gaps_equal_the_mirror(ch, torch_mod):
+    """6 rows, one per gap g: pairs of on bins g and g + 1 bins apart across word and tile borders, the bridged bins zeros;
+    with gap = g the first are one segment and the others two; a gap that reaches to lo or hi is not bridged."""
+    pts = gap_rows()
+    for field in FIELDS:
+        x = to_device(torch_mod, records_of(pts, field))
+        for r, g in enumerate(GAPS):
+            for kw in (dict(), dict(lo=12001, hi=14001), dict(lo=12000, hi=14002), dict(min_width=g + 2), dict(min_width=g + 3)):
+                rec, stats = _check(ch, torch_mod, x, pts, field, (field, g, kw), k=32, threshold=0.5, gap=g, **kw)
+                if not kw:
+                    assert stats[r].tolist() == [8, 12, 4 * (g + 2) + 4]         # bridged: the gaps of g; not: those of g + 1
+                    assert (rec["start"][r, 0], rec["stop"][r, 0]) == (767 - g // 2, 767 - g // 2 + g + 2)
+                if kw.get("lo") == 12001:
+                    assert stats[r].tolist() == [2, 2, 2]
+                if kw.get("min_width") == g + 3:
+                    assert stats[r, 0] == 0 and stats[r, 1] == 12
+        _check(ch, torch_mod, x, pts, field, (field, "all"), k=32, threshold=0.5, gap=N - 1)
+        _check(ch, torch_mod, x, pts, field, (field, "none"), k=32, threshold=0.5, gap=0)
+
+
+def test_many_segments_equal_the_mirror(ch, torch_mod):
+    """7 rows: the alternating row (8192 segments) at k = 1 and k = 32, widths cycling through 1, 2, 3 with min_width 2 and 3
+    -- kept ranks cross thread and wave borders, dropped segments lie between kept ones -- one segment over the whole row, an
+    all-zero row, and a NaN row between clean rows that equal their own calls."""
+    pts = many_rows()
+    for field in FIELDS:
+        x = to_device(torch_mod, records_of(pts, field))
+        for k in (1, 32):
+            rec, stats = _check(ch, torch_mod, x, pts, field, (field, k), k=k, threshold=0.5)
+            assert stats[0].tolist() == [8192] * 3 and stats[2].tolist() == [1, N, N] and stats[3].tolist() == [0, 0, 0]
+            assert (stats[[0, 1, 5, 6], 0] > k).all() and np.isnan(rec["power"][4, 0])
+            for r in (3, 5):                                      # the rows next to the NaN row equal their own calls
+                one = _run(ch, torch_mod, x[r:r + 1], field=field, k=k, threshold=0.5)
+                assert same_result(one, (rec[r:r + 1], stats[r:r + 1])) is None, (field, k, r)
+        for min_width in (2, 3):
+            rec, stats = _check(ch, torch_mod, x, pts, field, (field, "min_width", min_width), k=32, threshold=0.5, min_width=min_width)
+            assert stats[0, 0] == 0 and 32 < stats[1, 0] < 4096 and np.diff(rec["start"][1]).max() >= 6
+            for k in (1, 5):
+                _check(ch, torch_mod, x, pts, field, (field, "min_width", min_width, k), k=k, threshold=0.5, min_width=min_width)
+        rec, stats = _check(ch, torch_mod, x, pts, field, (field, "gap 1"), k=32, threshold=0.5, gap=1)
+        assert stats[0].tolist() == [1, 8192, N - 1] and stats[1, 0] == 1
+        _check(ch, torch_mod, x, pts, field, (field, "late"), k=32, threshold=0.5, lo=16000, min_width=2)
+
+
+def test_specials_and_thresholds_per_row(ch, torch_mod):
+    """-0.0, negative points, denormals and +inf; a thr per row holding 0, +inf, a NaN and a negative value; and thr made on
+    the device from the noise floor: order_stats(...)[:, 0] * 6 equals the mirror with that array."""
+    from fpga_real_time_fft_analyzer_amd import frames
+    torch = torch_mod
+    pts = special_rows()
+    thr = np.array([0.0, np.inf, np.nan, -1.5, 0.0, -np.inf], np.float32)
+    for field in FIELDS:
+        x = to_device(torch, records_of(pts, field))
+        for kw in (dict(threshold=0.5), dict(threshold=0.0), dict(threshold=1e-44), dict(threshold=float("inf")),
+                   dict(threshold=thr), dict(threshold=thr, gap=1), dict(threshold=thr[::-1].copy(), gap=3, min_width=2)):
+            rec, stats = _check(ch, torch, x, pts, field, (field, str(kw)), k=32, **kw)
+        rec, stats = _check(ch, torch, x, pts, field, (field, "0.5"), k=32, threshold=0.5)
+        assert rec["peak_bin"][3, 0] == 705 and np.isnan(rec["peak"][3, 0]) and np.isinf(rec["power"][2, 0]) and stats[1].tolist() == [0, 0, 0]
+    x = to_device(torch, pts[[2, 3, 3, 4]])
+    rec, stats = _check(ch, torch, x, pts[[2, 3, 3, 4]], None, "inf, nan", k=32, threshold=np.array([np.inf, np.inf, np.nan, -2.5], np.float32))
+    assert stats[:3].tolist() == [[2, 3, 3], [2, 2, 2], [2, 2, 2]] and stats[3, 0] > 10 and rec["start"][2, :2].tolist() == [705, 9000]
+    # the noise-riding threshold, made on the device
+    noise = noise_rows()[:8].copy()
+    for r in range(8):
+        noise[r, 1000 + 900 * r:1000 + 900 * r + 1 + 40 * r] = 9.0 + r
+    for field in (None, "power"):
+        x = to_device(torch, records_of(noise, field))
+        for lo, hi in ((0, N), (500, 9000)):
+            floor = ch.order_stats(x, [frames.rank_of_quantile(0.5, hi - lo)], lo, hi, field=field)
+            t = floor[:, 0] * 6
+            assert t.dtype == torch.float32 and t.is_contiguous()
+            host = frames.ranks_of_rows(records_of(noise, field), [frames.rank_of_quantile(0.5, hi - lo)], lo, hi, field=field)[:, 0] * np.float32(6)
+            assert np.array_equal(t.cpu().numpy().view(np.int32), host.view(np.int32))
+            want = frames.signals_of_rows(records_of(noise, field), k=8, threshold=host, lo=lo, hi=hi, gap=2, field=field)
+            out = ch.find_signals(x, 8, t, lo, hi, gap=2, field=field)
+            assert np.array_equal(out[0].cpu().numpy(), np.stack([want[0]["start"], want[0]["stop"]], -1)), (field, lo)
+            assert same_bits(out[3].cpu().numpy(), want[0]["power"]) and np.array_equal(out[4].cpu().numpy(), want[1])
+            assert (want[1][:, 0] >= 1).all() and (want[1][:, 0] < 8).all()
+
+
+def test_the_order_of_the_tree(ch, torch_mod):
+    """noise_rows / wide_rows carrying segments of the widths 1, 5, 64, 257 and 5000: the bits of `power` equal
+    band_power(x[r:r+1], [(start, stop)]) on the device and the mirror, and differ from a sequential sum in at least half the
+    rows."""
+    torch = torch_mod
+    widths = (1, 5, 64, 257, 5000)
+    starts = (100, 1022, 2000, 3900, 6000)
+    for name, base, level in (("noise", noise_rows()[:12], 8.0), ("wide", wide_rows(), 4e9)):
+        pts = base.copy()
+        rng = np.random.default_rng(2510)
+        for a, w in zip(starts, widths):                          # 1..2 times the level over the noise, over 6 decades in the wide rows
+            above = 1.0 + rng.random((len(pts), w)) if name == "noise" else 10.0 ** rng.uniform(0.0, 6.0, (len(pts), w))
+            pts[:, a:a + w] = (level * above).astype(np.float32)
+        for field in (None, "power"):
+            x = to_device(torch, records_of(pts, field))
+            rec, stats = _check(ch, torch, x, pts, field, (name, field), k=8, threshold=float(level))
+            assert stats[:, 0].tolist() == [5] * len(pts) and (rec["stop"][:, :5] - rec["start"][:, :5] == widths).all()
+            differ = 0
+            for r in range(len(pts)):
+                bands = [(int(rec["start"][r, j]), int(rec["stop"][r, j])) for j in range(5)]
+                power, _ = ch.band_power(x[r:r + 1], bands, field=field)
+                assert same_bits(power.cpu().numpy()[0], rec["power"][r, :5]), (name, field, r)
+                v = pts[r].astype(np.float64) if field == "power" else pts[r].astype(np.float64) ** 2
+                seq = np.cumsum(v[6000:11000])[-1]                # the same values added one after the other
+                assert np.isclose(seq, rec["power"][r, 4], rtol=1e-9)
+                differ += seq != rec["power"][r, 4]
+            if field is None:                                     # sums of the 24-bit values themselves are exact in any order
+                assert differ >= len(pts) // 2, (name, field, differ)
+
+
+def test_exactly_the_record_bytes_are_written_and_a_refused_call_writes_nothing(ch, torch_mod):
+    from fpga_real_time_fft_analyzer_amd import abi, frames
+    from fpga_real_time_fft_analyzer_amd.abi import SpecanError
+    torch = torch_mod
+    L = abi.signals_lib()
+    stream = torch.cuda.current_stream().cuda_stream
+    pts = edge_rows()[:5]
+    R, guard = 5, 4096
+    x = to_device(torch, pts)
+    thr = to_device(torch, np.array([0.5, 1.2, 0.5, 0.0, 9.0], np.float32))
+    for k, per_row, kw in ((8, False, dict()), (1, True, dict()), (32, True, dict(gap=5, min_width=2)), (3, False, dict(lo=100, hi=9000))):
+        a = dict(dict(lo=0, hi=N, gap=0, min_width=1), **kw)
+        for fill in (0xFF, 0x00):
+            buf = torch.full((guard + R * k * 24 + guard,), fill, dtype=torch.uint8, device="cuda")
+            sbuf = torch.full((guard + R * 12 + guard,), fill, dtype=torch.uint8, device="cuda")
+            assert L.sa_signals_f32(x.data_ptr(), 0, thr.data_ptr() if per_row else None, 0.5, buf.data_ptr() + guard,
+                                    sbuf.data_ptr() + guard, R, k, a["lo"], a["hi"], a["gap"], a["min_width"], stream) == SA_OK
+            assert L.sa_signals_last_error() == b""
+            torch.cuda.synchronize()
+            assert (buf[:guard] == fill).all().item() and (buf[guard + R * k * 24:] == fill).all().item()
+            assert (sbuf[:guard] == fill).all().item() and (sbuf[guard + R * 12:] == fill).all().item()
+            got = (buf[guard:guard + R * k * 24].cpu().numpy().view(frames.SIGNAL).reshape(R, k),
+                   sbuf[guard:guard + R * 12].cpu().numpy().view(np.int32).reshape(R, 3))
+            want = frames.signals_of_rows(pts, k=k, threshold=thr.cpu().numpy() if per_row else 0.5, **a)
+            assert same_result(got, want) is None, (k, per_row, kw, fill, same_result(got, want))
+            assert (want[1][:, 0] >= 1).any()
+    # refused calls: the code of sa_signals_check for the same arguments, its text, and nothing written
+    k = 8
+    buf = torch.full((R * k * 24 + guard,), 0xFF, dtype=torch.uint8, device="cuda")
+    sbuf = torch.full((R * 12 + guard,), 0xFF, dtype=torch.uint8, device="cuda")
+    flat = torch.zeros((R * N + 64,), dtype=torch.float32, device="cuda")
+    before = flat.clone()
+    p_in, p_out, p_st, p_thr = flat.data_ptr(), buf.data_ptr(), sbuf.data_ptr(), thr.data_ptr()
+    good = dict(field=0, thr=0, bits=0x3F000000, rows=R, k=k, lo=0, hi=N, gap=0, min_width=1)
+    good.update({"in": p_in, "out": p_out, "stats": p_st})
+    for tag, kw, code, words in (
+            ("in 4 bytes off", {"in": p_in + 4}, SA_EINVAL, "`in` must be 16-byte aligned"),
+            ("out 4 bytes off", dict(out=p_out + 4), SA_EINVAL, "`out` must be 8-byte aligned"),
+            ("stats 2 bytes off", dict(stats=p_st + 2), SA_EINVAL, "`stats` must be 4-byte aligned"),
+            ("thr 2 bytes off", dict(thr=p_thr + 2), SA_EINVAL, "`thr` must be 4-byte aligned"),
+            ("out inside in", dict(out=p_in + R * N * 4 - 8), SA_EINVAL, "`out` (960 bytes) and `in`"),
+            ("records read twice as much", dict(field=2, out=p_in + R * N * 4), SA_EINVAL, "overlap"),
+            ("stats inside out", dict(stats=p_out + 956), SA_EINVAL, "`out` (960 bytes) and `stats` (60 bytes) overlap"),
+            ("stats inside in", dict(stats=p_in + 64), SA_EINVAL, "`stats` (60 bytes) and `in`"),
+            ("thr inside out", dict(thr=p_out + 16), SA_EINVAL, "`out` (960 bytes) and `thr` (20 bytes) overlap"),
+            ("thr on stats", dict(thr=p_st + 56), SA_EINVAL, "`stats` (60 bytes) and `thr` (20 bytes) overlap"),
+            ("NULL out", dict(out=0), SA_EINVAL, "NULL"), ("NULL in", {"in": 0}, SA_EINVAL, "NULL"), ("NULL stats", dict(stats=0), SA_EINVAL, "NULL"),
+            ("field 3", dict(field=3), SA_EINVAL, "field"), ("k", dict(k=33), SA_EINVAL, "k must"),
+            ("a NaN threshold", dict(bits=0x7FC00000), SA_EINVAL, "threshold"), ("a negative threshold", dict(bits=0xBF000000), SA_EINVAL, "threshold"),
+            ("range", dict(lo=5, hi=5), SA_EINVAL, "range"), ("gap", dict(gap=N), SA_EINVAL, "gap"), ("min_width", dict(min_width=0), SA_EINVAL, "min_width"),
+            ("negative rows", dict(rows=-1), SA_ESHAPE, "negative")):
+        a = dict(good, **kw)
+        assert L.sa_signals_check(a["field"], a["in"], a["thr"], a["bits"], a["out"], a["stats"], a["rows"], a["k"], a["lo"], a["hi"],
+                                  a["gap"], a["min_width"]) == code, tag
+        threshold = float(np.array([a["bits"]], np.uint32).view(np.float32)[0])
+        assert L.sa_signals_f32(a["in"], a["field"], a["thr"] or None, threshold, a["out"], a["stats"], a["rows"], a["k"], a["lo"], a["hi"],
+                                a["gap"], a["min_width"], stream) == code, tag
+        assert words in L.sa_signals_last_error().decode(), (tag, L.sa_signals_last_error())
+    torch.cuda.synchronize()
+    assert (buf == 0xFF).all().item() and (sbuf == 0xFF).all().item() and torch.equal(flat, before)
+    assert L.sa_signals_f32(0, 0, None, 0.5, 0, 0, 0, 8, 0, N, 0, 1, stream) == SA_OK and L.sa_signals_last_error() == b""
+    # the buffers touching: in | thr | out | stats in a row; and thr inside in, both only read
+    n_in, n_thr, n_out = R * N * 4, 24, R * k * 24                   # thr is 20 bytes; the records start 8-byte aligned
+    packed = torch.zeros((n_in + n_thr + n_out + R * 12,), dtype=torch.uint8, device="cuda")
+    packed[:n_in] = x.view(torch.uint8).view(-1)
+    packed[n_in:n_in + 20] = thr.view(torch.uint8)
+    base = packed.data_ptr()
+    assert L.sa_signals_f32(base, 0, base + n_in + 8, 0.0, base + n_in + n_thr, base + n_in + n_thr + n_out, R, k, 0, N, 0, 1, stream) == SA_EINVAL
+    assert L.sa_signals_f32(base, 0, base + n_in, 0.0, base + n_in + n_thr, base + n_in + n_thr + n_out, R, k, 0, N, 0, 1, stream) == SA_OK
+    torch.cuda.synchronize()
+    got = (packed[n_in + n_thr:n_in + n_thr + n_out].cpu().numpy().view(frames.SIGNAL).reshape(R, k),
+           packed[n_in + n_thr + n_out:].cpu().numpy().view(np.int32).reshape(R, 3))
+    assert same_result(got, frames.signals_of_rows(pts, k=k, threshold=thr.cpu().numpy())) is None
+    assert torch.equal(packed[:n_in], x.view(torch.uint8).view(-1))
+    inside = x.clone()
+    inside[4, N - 8:N - 3] = thr                                      # the thresholds are the row's own last points
+    o = torch.zeros((R, k, WORDS), dtype=torch.int32, device="cuda")
+    s = torch.zeros((R, 3), dtype=torch.int32, device="cuda")
+    assert L.sa_signals_f32(inside.data_ptr(), 0, inside[4, N - 8:].data_ptr(), 0.0, o.data_ptr(), s.data_ptr(), R, k, 0, N, 0, 1, stream) == SA_OK
+    torch.cuda.synchronize()
+    assert same_result(_host(o, s), frames.signals_of_rows(inside.cpu().numpy(), k=k, threshold=thr.cpu().numpy())) is None
+    # through the wrapper: shapes and dtypes before any device call
+    for code, args, kw in ((SA_ESHAPE, (x[:, :N // 2],), {}), (SA_EINVAL, (x.double(),), {}), (SA_ESHAPE, (x,), dict(field="peak")),
+                           (SA_ESHAPE, (x,), dict(k=8, out=torch.empty((R, 8, 5), dtype=torch.int32, device="cuda"))),
+                           (SA_ESHAPE, (x,), dict(k=8, out=torch.empty((R, 8, 6), dtype=torch.float32, device="cuda"))),
+                           (SA_ESHAPE, (x,), dict(k=8, out=torch.empty((R, 8, 6), dtype=torch.int32))),
+                           (SA_ESHAPE, (x,), dict(stats=torch.empty((R, 4), dtype=torch.int32, device="cuda"))),
+                           (SA_ESHAPE, (x,), dict(threshold=thr[:4])), (SA_ESHAPE, (x,), dict(threshold=thr.cpu())),
+                           (SA_EINVAL, (x,), dict(threshold=thr.double())), (SA_EINVAL, (x,), dict(k=33)), (SA_EINVAL, (x.cpu(),), {})):
+        with pytest.raises(SpecanError) as e:
+            ch.find_signals(*args, **kw)
+        assert e.value.code == code, (args[0].shape, kw)
+    empty = ch.find_signals(torch.empty((0, N), dtype=torch.float32, device="cuda"), k=4)
+    assert tuple(empty[0].shape) == (0, 4, 2) and tuple(empty[4].shape) == (0, 3)
+
+
+def test_poisoned_lds(ch, torch_mod, lds_fill):
+    """lds_fill(P) with P = 0xFFFFFFFF (every bit of the masks on, a NaN as either half of a double, the largest key, -1 as a
+    count), 0x7FF00000 and 0, then the call on the same stream: the bits of the mirror, on the rows of the edges, the gaps and
+    the many segments."""
+    cases = [(edge_rows(), kw) for kw in EDGE_CALLS[:5]]
+    cases += [(gap_rows(), dict(k=32, threshold=0.5, gap=g)) for g in GAPS]
+    cases += [(many_rows(), kw) for kw in (dict(k=1, threshold=0.5), dict(k=32, threshold=0.5), dict(k=32, threshold=0.5, min_width=2),
+                                           dict(k=5, threshold=0.5, min_width=3), dict(k=32, threshold=0.5, gap=1))]
+    for field in FIELDS:
+        xs = {id(p): to_device(torch_mod, records_of(p, field)) for p in (edge_rows(), gap_rows(), many_rows())}
+        for n, (pts, kw) in enumerate(cases):
+            for word in (0xFFFFFFFF, 0x7FF00000, 0):
+                if field is not None and (n + (word & 1)) % 2:     # the record layouts take every other case
+                    continue
+                lds_fill(word)
+                _check(ch, torch_mod, xs[id(pts)], pts, field, (field, hex(word), kw), **kw)
+
+
+def test_capture_and_replay(ch, torch_mod):
+    """find_signals captures without a warm-up -- it is one launch with its parameters in the launch's arguments -- and a
+    replay after the input and the thresholds have changed gives the eager result of the new ones.  At depth 1, after one
+    warm-up call of the same batch (it allocates the cached workspace), signals_f32 captures with a factor too."""
+    from fpga_real_time_fft_analyzer_amd import frames
+    torch = torch_mod
+    first = edge_rows()[:5]
+    x = to_device(torch, first)
+    thr = to_device(torch, np.full(5, 0.5, np.float32))
+    out = torch.zeros((5, 8, WORDS), dtype=torch.int32, device="cuda")
+    stats = torch.zeros((5, 3), dtype=torch.int32, device="cuda")
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        ch.find_signals(x, 8, thr, gap=1, min_width=2, out=out, stats=stats)
+    for pts, t in ((np.ascontiguousarray(first[::-1]) * np.float32(3.0), np.array([1.5, 0.2, 4.0, 1.5, 1.5], np.float32)),
+                   (first, np.full(5, 0.5, np.float32))):
+        x.copy_(to_device(torch, pts))
+        thr.copy_(to_device(torch, t))
+        out.zero_()
+        stats.zero_()
+        graph.replay()
+        torch.cuda.synchronize()
+        want = frames.signals_of_rows(pts, k=8, threshold=t, gap=1, min_width=2)
+        assert same_result(_host(out, stats), want) is None and (want[1][:, 0] >= 1).any()
+    # the composed call
+    ch.set_filter_mode(0xB1)
+    assert ch.overlap == 1
+    xs = [to_device(torch, _tones(4, 2550 + i, bins=(1000 + 700 * i, 2000 + 1400 * i, 6000 + 90 * i), amps=(900.0 / (1 + i), 450.0, 220.0)))
+          for i in range(2)]
+    eager = []
+    for xi in xs:
+        o = torch.zeros((4, 8, WORDS), dtype=torch.int32, device="cuda")
+        s = torch.zeros((4, 3), dtype=torch.int32, device="cuda")
+        ch.signals_f32(xi, 8, factor=6.0, gap=2, out=o, stats=s)
+        assert (s[:, 0] >= 3).all().item()
+        eager.append((o, s))
+    assert not torch.equal(eager[0][0], eager[1][0])
+    xin = xs[0].clone()
+    o2 = torch.zeros((4, 8, WORDS), dtype=torch.int32, device="cuda")
+    s2 = torch.zeros((4, 3), dtype=torch.int32, device="cuda")
+    graph2 = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph2):
+        ch.signals_f32(xin, 8, factor=6.0, gap=2, out=o2, stats=s2)
+    for i in (1, 0):
+        xin.copy_(xs[i])
+        o2.zero_()
+        s2.zero_()
+        graph2.replay()
+        torch.cuda.synchronize()
+        assert torch.equal(o2, eager[i][0]) and torch.equal(s2, eager[i][1]), i
+    assert "libspecan_signals.so" in open("/proc/self/maps").read()
+
+
+@pytest.mark.parametrize("mode", [0xB1, 0xA1])
+def test_signals_f32(ch, torch_mod, mode):
+    """The composed call at B = 4 equals find_signals on process_f32's magnitudes, and with group = 2 find_signals on
+    spectra_f32's records, field 'power' -- float32, int16 and packed input, an absolute threshold and a factor; a caller's
+    work, out and stats; refusals before any launch."""
+    from fpga_real_time_fft_analyzer_amd import frames
+    from fpga_real_time_fft_analyzer_amd.abi import SpecanError
+    torch = torch_mod
+    if mode == 0xA1:
+        ch.load_sos(load_golden("g2_config1.npz")["sos"])
+    ch.set_filter_mode(mode)
+    B, k = 4, 8
+    tones = _tones(B, 2540 + mode, bins=(1200, 2400, 3600), amps=(900.0, 450.0, 220.0))
+    new = lambda R: (torch.zeros((R, k, WORDS), dtype=torch.int32, device="cuda"), torch.zeros((R, 3), dtype=torch.int32, device="cuda"))  # noqa: E731
+    for form, x in _inputs(torch, tones).items():
+        mag = ch.process_f32(x, out_kind="mag_full")
+        rec2 = ch.spectra_f32(x, 2)
+        for t, field, group in ((mag, None, None), (rec2, "power", 2)):
+            R = t.shape[0]
+            rank = frames.rank_of_quantile(0.25, 9000 - 100)
+            floor = ch.order_stats(t, [rank], 100, 9000, field=field)[:, 0]
+            thr = floor * float(np.float32(7.5))
+            level = float(thr.max().item())
+            for kw, threshold in ((dict(factor=7.5, q=0.25), thr), (dict(threshold=level), level), (dict(threshold=thr), thr)):
+                want = new(R)
+                ch.find_signals(t, k, threshold, 100, 9000, gap=2, min_width=1, field=field, out=want[0], stats=want[1])
+                got = new(R)
+                views = ch.signals_f32(x, k, lo=100, hi=9000, gap=2, group=group, out=got[0], stats=got[1], **kw)
+                assert torch.equal(got[0], want[0]) and torch.equal(got[1], want[1]) and views[0].data_ptr() == got[0].data_ptr(), (form, group, kw)
+                assert len(views) == 6 and ((views[5] is None) if "factor" not in kw else torch.equal(views[5], thr)), (form, group, kw)
+                host_thr = threshold.cpu().numpy() if isinstance(threshold, torch.Tensor) else threshold
+                mirror = frames.signals_of_rows(t.cpu().numpy(), k=k, threshold=host_thr, lo=100, hi=9000, gap=2, field=field)
+                assert same_result(_host(*got), mirror) is None, (form, group, kw)
+                assert mode != 0xB1 or (mirror[1][:, 0] >= 1).all()
+                # the three tones are there, each a segment of its own (7.5 times a floor of powers is 2.7 times in amplitude:
+                # there the noise gives the first k segments)
+                if mode == 0xB1 and "factor" in kw and group is None:
+                    peaks = [set(row[row >= 0].tolist()) for row in mirror[0]["peak_bin"]]
+                    assert all({1200, 2400, 3600} <= p for p in peaks), (form, group, peaks)
+        none = ch.signals_f32(x, k, factor=7.5, q=0.25, lo=100, hi=9000, gap=2)
+        assert tuple(none[0].shape) == (B, k, 2) and tuple(none[4].shape) == (B, 3) and tuple(none[5].shape) == (B,)
+    x = _inputs(torch, tones)["int16"]
+    mag = ch.process_f32(x, out_kind="mag_full")
+    want = new(B)
+    ch.find_signals(mag, k, 3.0, out=want[0], stats=want[1])
+    work = torch.full((B + 1, N), 3.0, dtype=torch.float32, device="cuda")
+    got = new(B)
+    ch.signals_f32(x, k, threshold=3.0, work=work, out=got[0], stats=got[1])
+    assert torch.equal(got[0], want[0]) and torch.equal(got[1], want[1]) and torch.equal(work[:B], mag) and (work[B] == 3.0).all().item()
+    for code, args, kw in ((SA_ESHAPE, (x[:3],), dict(factor=6.0, group=2)), (SA_EINVAL, (x,), dict(factor=6.0, group=3)),
+                           (SA_EINVAL, (x,), dict()), (SA_EINVAL, (x,), dict(threshold=1.0, factor=6.0)), (SA_EINVAL, (x,), dict(factor=0.0)),
+                           (SA_EINVAL, (x,), dict(factor=6.0, q=2.0)), (SA_EINVAL, (x,), dict(factor=6.0, k=0)),
+                           (SA_EINVAL, (x,), dict(factor=6.0, gap=N)), (SA_EINVAL, (x,), dict(threshold=-1.0)),
+                           (SA_ESHAPE, (x,), dict(threshold=torch.zeros(B + 1, device="cuda"))),
+                           (SA_ESHAPE, (x,), dict(factor=6.0, work=torch.empty((B - 1, N), dtype=torch.float32, device="cuda"))),
+                           (SA_ESHAPE, (x,), dict(factor=6.0, out=torch.zeros((B, k, 5), dtype=torch.int32, device="cuda"))),
+                           (SA_ESHAPE, (x,), dict(factor=6.0, stats=torch.zeros((B, 2), dtype=torch.int32, device="cuda"))),
+                           (SA_ESHAPE, (x,), dict(factor=6.0, group=2, out=torch.zeros((B, k, WORDS), dtype=torch.int32, device="cuda")))):
+        work.fill_(3.0)
+        with pytest.raises(SpecanError) as e:
+            ch.signals_f32(*args, **dict(dict(k=k, work=work), **kw))
+        torch.cuda.synchronize()
+        assert e.value.code == code and (work == 3.0).all().item(), kw
+
+
+def test_the_last_row_past_4_gib(ch, torch_mod):
+    """Magnitudes tiled from one period of 1027 rows until the last rows start beyond byte 2^32 (the batch the rules of
+    offset_cases give such rows), a threshold per row tiled alike, into records of 0xFF bytes: ALL rows equal the call on one
+    period."""
+    from fpga_real_time_fft_analyzer_amd import frames
+    torch = torch_mod
+    P, rows, k = oc.period(1), 65539, 4
+    assert rows == oc.batch({"in": N * 4}, 1) and (rows - 1) * N * 4 >= 1 << 32
+    gen = torch.Generator(device="cuda")
+    gen.manual_seed(2560)
+    per = 0.001 + 0.78 * torch.rand((P, N), device="cuda", generator=gen)
+    r = torch.arange(P, device="cuda")
+    for j in range(3):                                             # three segments of the row's own place and width
+        per[r, 100 + 7 * r + 3000 * j] = 5.0
+        per[r, 100 + 7 * r + 3000 * j + 1 + r % 3] = 6.0
+    tper = 2.0 + (r % 5).to(torch.float32) * 0.25
+    x = torch.empty((rows, N), dtype=torch.float32, device="cuda")
+    thr = torch.empty((rows,), dtype=torch.float32, device="cuda")
+    for s in range(0, rows, P):
+        n = min(P, rows - s)
+        x[s:s + n] = per[:n]
+        thr[s:s + n] = tper[:n]
+    assert x[rows - 1:].data_ptr() - x.data_ptr() >= 1 << 32
+    ref = torch.zeros((P, k * WORDS + 3), dtype=torch.int32, device="cuda")
+    o, s = torch.zeros((P, k, WORDS), dtype=torch.int32, device="cuda"), torch.zeros((P, 3), dtype=torch.int32, device="cuda")
+    ch.find_signals(x[:P], k, thr[:P], gap=3, out=o, stats=s)
+    ref[:, :k * WORDS], ref[:, k * WORDS:] = o.view(P, -1), s
+    assert oc.vacuous(torch, ref, None) is None
+    assert s[:, 0].tolist() == [3] * P and o[:, 0, 0].tolist() == [100 + 7 * i for i in range(P)]
+    want = frames.signals_of_rows(per[:3].cpu().numpy(), k=k, threshold=tper[:3].cpu().numpy(), gap=3)
+    assert same_result(_host(o[:3], s[:3]), want) is None
+    out = torch.full((rows * k * WORDS * 4,), 0xFF, dtype=torch.uint8, device="cuda").view(torch.int32).view(rows, k, WORDS)
+    stats = torch.full((rows * 12,), 0xFF, dtype=torch.uint8, device="cuda").view(torch.int32).view(rows, 3)
+    ch.find_signals(x, k, thr, gap=3, out=out, stats=stats)
+    bad = oc.tiled_mismatch(torch, out.view(rows, -1), o.view(P, -1)) or oc.tiled_mismatch(torch, stats, s)
+    assert bad is None, bad
+    torch.cuda.synchronize()
+    del x, out
+    torch.cuda.empty_cache()
