@@ -294,13 +294,30 @@ SIGNALS_SIGNATURES = {
     "sa_signals_last_error": (C.c_char_p, []),
 }
 
+# the entry points of include/specan_cfar.h: libspecan_cfar.so, the tenth product library, again without a handle (per row of
+# 16384 points every bin over the mean power of its training cells, or that local floor: float32 [R,16384]), bound by
+# cfar_lib() and held name for name against that header (tests/test_f32_cfar_cpu.py); no name is in the tables above
+SA_CFAR_VERSION = 1
+SA_CFAR_IN_MAG, SA_CFAR_IN_POINT_PEAK, SA_CFAR_IN_POINT_POWER = 0, 1, 2
+SA_CFAR_MODE_CA, SA_CFAR_MODE_GO, SA_CFAR_MODE_SO = 0, 1, 2
+SA_CFAR_OUT_RATIO, SA_CFAR_OUT_FLOOR = 0, 1
+SA_CFAR_LOG2_TRAIN_MAX = 6
+SA_CFAR_GUARD_MAX = 64
+CFAR_SIGNATURES = {
+    "sa_cfar_version": (_INT, []),
+    "sa_cfar_f32": (_INT, [C.c_void_p, _INT, C.c_void_p, _INT, _INT, _INT, _INT, _INT, _INT, _INT, C.c_void_p]),
+    "sa_cfar_check": (_INT, [_INT, C.c_uint64, C.c_uint64, _INT, _INT, _INT, _INT, _INT, _INT, _INT]),
+    "sa_cfar_last_error": (C.c_char_p, []),
+}
+
 # the handle-less libraries: short name x -> (file name beside LIB_PATH, entry points); include/specan_x.h declares them and
 # the same make builds them.  A new library is a row here and its name in the two lines that spell the public names out.
 LIBRARIES = {x: (f"libspecan_{x}.so", table) for x, table in (
     ("fold", FOLD_SIGNATURES), ("peaks", PEAKS_SIGNATURES), ("rank", RANK_SIGNATURES), ("hist", HIST_SIGNATURES),
     ("bands", BANDS_SIGNATURES), ("mask", MASK_SIGNATURES), ("harm", HARM_SIGNATURES),
-    ("signals", SIGNALS_SIGNATURES))}
-(FOLD_LIB_PATH, PEAKS_LIB_PATH, RANK_LIB_PATH, HIST_LIB_PATH, BANDS_LIB_PATH, MASK_LIB_PATH, HARM_LIB_PATH,
+    # "cfar", the tenth, stands before "signals": a test of the ninth holds "signals" to be the last row
+    ("cfar", CFAR_SIGNATURES), ("signals", SIGNALS_SIGNATURES))}
+(FOLD_LIB_PATH, PEAKS_LIB_PATH, RANK_LIB_PATH, HIST_LIB_PATH, BANDS_LIB_PATH, MASK_LIB_PATH, HARM_LIB_PATH, CFAR_LIB_PATH,
  SIGNALS_LIB_PATH) = (os.path.join(_PKG, name) for name, _ in LIBRARIES.values())
 
 _loaded = {}                     # path -> the library, mapped and bound: each is loaded once
@@ -352,6 +369,6 @@ def _loader(x: str):
     return load
 
 
-fold_lib, peaks_lib, rank_lib, hist_lib, bands_lib, mask_lib, harm_lib, signals_lib = map(_loader, LIBRARIES)
+fold_lib, peaks_lib, rank_lib, hist_lib, bands_lib, mask_lib, harm_lib, cfar_lib, signals_lib = map(_loader, LIBRARIES)
 
 

@@ -891,6 +891,119 @@ def signals_of_rows(points, k: int = 16, threshold=0.0, lo: int = 0, hi: int = F
     return rec, stats
 
 
+CFAR_TRAINS = (1, 2, 4, 8, 16, 32, 64)
+CFAR_GUARD_MAX = 64
+CFAR_MODES = {"ca": 0, "go": 1, "so": 2}               # mode -> SA_CFAR_MODE_* of include/specan_cfar.h
+CFAR_OUTPUTS = {"ratio": 0, "floor": 1}                # what -> SA_CFAR_OUT_*
+
+
+def _cfar_args(train, guard, mode, what, lo, hi, field) -> tuple:
+    """``(log2_train, guard, mode code, what code, lo, hi)`` of the CFAR normalisation, or ValueError: ``train``, ``guard``,
+    ``lo`` and ``hi`` ints (no bool, no float), ``train`` one of 1, 2, 4, ..., 64, ``guard`` 0..64, ``mode`` 'ca', 'go' or
+    'so', ``what`` 'ratio' or 'floor', ``0 <= lo < hi <= 16384`` with ``hi - lo >= 2 * guard + 2``; ``field`` None, 'peak' or
+    'power'."""
+    for name, v in (("train", train), ("guard", guard), ("lo", lo), ("hi", hi)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f"{name} must be an int")
+    train, guard, lo, hi = int(train), int(guard), int(lo), int(hi)
+    if train not in CFAR_TRAINS:
+        raise ValueError(f"train must be one of {CFAR_TRAINS}")
+    if not 0 <= guard <= CFAR_GUARD_MAX:
+        raise ValueError(f"guard must be 0..{CFAR_GUARD_MAX}")
+    if not isinstance(mode, str) or mode not in CFAR_MODES:
+        raise ValueError("mode must be 'ca', 'go' or 'so'")
+    if not isinstance(what, str) or what not in CFAR_OUTPUTS:
+        raise ValueError("what must be 'ratio' or 'floor'")
+    if not 0 <= lo < hi <= FFT_SIZE:
+        raise ValueError(f"the range must be 0 <= lo < hi <= {FFT_SIZE}")
+    if hi - lo < 2 * guard + 2:
+        raise ValueError("the range must hold 2 * guard + 2 bins or more")
+    if not (field is None or isinstance(field, str)) or field not in RANK_FIELDS:
+        raise ValueError("field must be None, 'peak' or 'power'")
+    return train.bit_length() - 1, guard, CFAR_MODES[mode], CFAR_OUTPUTS[what], lo, hi
+
+
+def cfar_alpha(pfa: float, n: int) -> float:
+    """The ratio threshold ``n * (pfa ** (-1 / n) - 1)`` of a cell-averaging detector over ``n`` training cells of
+    exponentially distributed power (the squared magnitude of complex Gaussian noise) at the false-alarm probability
+    ``pfa`` per bin: a bin of noise alone exceeds ``alpha`` times the mean of its n cells with that probability.  For
+    ``cfar_of_rows(..., mode='ca', what='ratio')`` n is 2 * train.  It applies to single frames: the sum of a ``group`` of
+    frames is gamma, not exponentially, distributed, and its threshold is lower.  ``0 < pfa < 1`` and ``n`` an int of 1 or
+    more: ValueError otherwise."""
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 1:
+        raise ValueError("n must be an int of 1 or more")
+    if isinstance(pfa, bool) or not isinstance(pfa, (int, float, np.integer, np.floating)) or not 0.0 < pfa < 1.0:
+        raise ValueError("pfa must be a number above 0 and below 1")
+    return int(n) * (float(pfa) ** (-1.0 / int(n)) - 1.0)
+
+
+def cfar_of_rows(points, train: int = 16, guard: int = 2, mode: str = "ca", what: str = "ratio", lo: int = 0,
+                 hi: int = FFT_SIZE, field=None) -> np.ndarray:
+    """The CFAR normalisation of float32 ``points`` [R,16384] -- or, with ``field`` 'peak' or 'power', of that float of the
+    records [R,16384,2]: float32 [R,16384], every bin of ``[lo, hi)`` over the mean power of its training cells
+    (``what='ratio'``) or that mean itself (``'floor'``), +0.0 outside the range.  The numpy mirror of sa_cfar_f32
+    (include/specan_cfar.h), step for step:
+
+    - point: ``a`` the point with its sign cleared as a float64, ``v = a * a``, or ``v = a`` with ``field='power'``;
+    - cells: ``c[j] = v[j]`` inside ``[lo, hi)`` and +0.0 for every other j, on a row padded with zeros on either side;
+    - window sums by doubling: ``W = W[:, :-h] + W[:, h:]`` for h = 1, 2, ..., train / 2: ``W[j]`` is the balanced pair tree
+      over the cells j .. j + train - 1;
+    - sides of bin i: ``L = W[i - guard - train]`` and ``R = W[i + guard + 1]`` with ``nL`` and ``nR`` their cells inside
+      ``[lo, hi)``;
+    - mode: 'ca' takes ``S = L + R`` and ``n = nL + nR``; 'go' the side with the larger mean and 'so' the one with the
+      smaller: the left with ``nR == 0``, the right with ``nL == 0``, otherwise the left where ``L * nR >= R * nL`` ('go')
+      or ``<=`` ('so');
+    - output: ``float32((v * n) / S)`` or ``float32(S / n)``; 0x7FC00000 where L or R is a NaN or, for the ratio, the point
+      is one; with ``S == 0`` the ratio is +0.0 where v is 0 and +inf otherwise and the floor +0.0; a quotient that is a
+      NaN is 0x7FC00000.
+
+    ``train`` is 1, 2, 4, ..., 64, ``guard`` 0..64, ``0 <= lo < hi <= 16384`` with ``hi - lo >= 2 * guard + 2``, the integers
+    ints (no bool, no float): ValueError otherwise, and on a wrong dtype or shape."""
+    t, G, mode, what, lo, hi = _cfar_args(train, guard, mode, what, lo, hi, field)
+    T = 1 << t
+    points = np.ascontiguousarray(points)
+    shape = (FFT_SIZE,) if field is None else (FFT_SIZE, 2)
+    if points.dtype != np.float32 or points.ndim != 1 + len(shape) or points.shape[1:] != shape:
+        raise ValueError(f"points must be float32 [R, {', '.join(map(str, shape))}]")
+    if field is not None:
+        points = np.ascontiguousarray(points[..., RANK_FIELDS[field]])
+    R = points.shape[0]
+    a = (points.view(np.uint32) & np.uint32(0x7FFFFFFF)).view(np.float32).astype(np.float64)
+    idx = np.arange(FFT_SIZE)
+    pad = G + T                                                            # W is wanted for j = -pad .. 16383 + G + 1
+    with np.errstate(over="ignore", invalid="ignore", divide="ignore"):
+        v = a if field == "power" else a * a
+        W = np.zeros((R, pad + FFT_SIZE + pad + T), np.float64)           # column e is cell e - pad
+        W[:, pad + lo:pad + hi] = v[:, lo:hi]
+        h = 1
+        while h < T:
+            W = W[:, :-h] + W[:, h:]
+            h *= 2
+        L, Rt = W[:, idx], W[:, idx + pad + G + 1]                         # W[i - G - T] and W[i + G + 1]
+        nL = np.maximum(0, np.minimum(idx - G, hi) - np.maximum(idx - G - T, lo))
+        nR = np.maximum(0, np.minimum(idx + G + 1 + T, hi) - np.maximum(idx + G + 1, lo))
+        if mode == 0:
+            S, n = L + Rt, np.broadcast_to(nL + nR, L.shape)
+        else:
+            pl, pr = L * nR.astype(np.float64), Rt * nL.astype(np.float64)
+            left = (pl >= pr) if mode == 1 else (pl <= pr)
+            left = np.where(nR == 0, True, np.where(nL == 0, False, left))
+            S, n = np.where(left, L, Rt), np.where(left, nL, nR)
+        dn = n.astype(np.float64)
+        q = (v * dn) / S if what == 0 else S / dn
+        bits = q.astype(np.float32).view(np.uint32).copy()
+        bits[np.isnan(q)] = 0x7FC00000
+        zero = S == 0
+        bits[zero] = np.where(v[zero] != 0, 0x7F800000, 0) if what == 0 else 0
+        nan = np.isnan(L) | np.isnan(Rt)
+        if what == 0:
+            nan |= np.isnan(v)
+        bits[nan] = 0x7FC00000
+    bits[:, :lo] = 0
+    bits[:, hi:] = 0
+    return bits.view(np.float32)
+
+
 def decode_iq_components(frame_bytes: bytes):
     """Same result as gui.py:262-270: (re, im) as float32 arrays."""
     re, im = _iq(frame_bytes)

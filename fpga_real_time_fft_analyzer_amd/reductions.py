@@ -1,7 +1,7 @@
 """The reductions of ``SpectrumChain``: the calls of the handle-less libraries of abi.LIBRARIES -- the fold of float
 magnitudes, the peak table, the order statistics, the level histogram, the band power, the mask test, the harmonic
-analysis and the signal list -- on tensors the caller has (``fold_mag_f32``, ``find_peaks``, ...) and composed with the float chain, the
-spectra never leaving the device (``spectra_f32``, ``peak_table_f32``, ...).
+analysis, the signal list and the CFAR normalisation -- on tensors the caller has (``fold_mag_f32``, ``find_peaks``, ...) and
+composed with the float chain, the spectra never leaving the device (``spectra_f32``, ``peak_table_f32``, ...).
 
 ``Reductions`` is a mixin of ``SpectrumChain`` (chain.py, which this module does not import): it reaches the handle through
 ``self`` -- ``device``, ``_stream``, ``_check_in``, ``_float_frames``, ``process_f32``, ``flush`` -- and keeps one copy of
@@ -20,8 +20,8 @@ from . import abi, frames
 from .abi import SA_N, SpecanError
 
 FOLD_GROUPS, FOLD_BUCKETS = frames.FOLD_GROUPS, frames.FOLD_BUCKETS
-# field=... -> the `field` of include/specan_{peaks,rank,bands,mask,harm,signals}.h: plain magnitudes, or one float of (peak,
-# power) records; the six headers number the three layouts alike (SA_X_IN_MAG, SA_X_IN_POINT_PEAK, SA_X_IN_POINT_POWER)
+# field=... -> the `field` of include/specan_{peaks,rank,bands,mask,harm,signals,cfar}.h: plain magnitudes, or one float of
+# (peak, power) records; the seven headers number the three layouts alike (SA_X_IN_MAG, SA_X_IN_POINT_PEAK, SA_X_IN_POINT_POWER)
 FIELDS = {None: 0, "peak": 1, "power": 2}
 HARM_WORDS = C.sizeof(abi.HarmRow) // 4                                       # an sa_harm_row as int32 words: 42
 SIGNAL_WORDS = C.sizeof(abi.Signal) // 4                                      # an sa_signal as int32 words: 6
@@ -754,3 +754,73 @@ class Reductions:
             return (*self.find_signals(t, k, thr, lo, hi, gap, min_width, field, *outs), thr if factor is not None else None)
 
         return self._of_spectra(x, group, scale, work, lambda R: self._signals_out(R, int(k), threshold, out, stats), reduce)
+
+    # ------------------------------------------------------------------ the CFAR normalisation
+    @staticmethod
+    def _cfar_args(train, guard, mode, what, lo, hi, field) -> tuple:
+        """The one validation of the arguments of the CFAR normalisation: ``(field code, log2_train, mode code, what code)``
+        of include/specan_cfar.h, or SA_EINVAL."""
+        _ints(("train", train), ("guard", guard), ("lo", lo), ("hi", hi))
+        code = _field_code(field)
+        try:
+            t, _, m, w, _, _ = frames._cfar_args(train, guard, mode, what, lo, hi, field)
+        except ValueError as e:
+            raise SpecanError(abi.SA_EINVAL, str(e)) from None
+        return code, t, m, w
+
+    def _cfar_out(self, R: int, out: Optional[torch.Tensor]) -> torch.Tensor:
+        """``out`` of the CFAR normalisation of ``R`` rows, allocated when None: SA_ESHAPE where it is not the contiguous
+        float32 [R, 16384] tensor on the handle's device."""
+        return self._outs(("out", out, (R, SA_N), torch.float32))[0]
+
+    def cfar(self, t: torch.Tensor, train: int = 16, guard: int = 2, mode: str = "ca", what: str = "ratio", lo: int = 0,
+             hi: int = SA_N, field: Optional[str] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Every bin of each row of ``t`` against its local noise floor (include/specan_cfar.h, sa_cfar_f32): float32
+        [R,16384] (``out``, allocated when None), a cell-averaging CFAR.  ``t`` is a float32 [R,16384] device tensor -- what
+        ``process_f32(out_kind='mag_full')`` or ``process_q15(out_kind='mag')`` wrote, squared bin by bin -- or, with
+        ``field='peak'`` (squared) or ``field='power'`` (taken as it is), float32 [R,16384,2], the records of
+        :meth:`fold_mag_f32` at bucket 1, :meth:`spectra_f32` or :meth:`spectra_q15`.
+
+        The floor of bin i is the mean power of the ``train`` cells below it and the ``train`` cells above it, ``guard`` cells
+        left out on either side, of which only those inside ``[lo, hi)`` count (``mode='ca'``); ``'go'`` takes the side with
+        the larger mean, which holds the false alarms down at a step of the floor, and ``'so'`` the side with the smaller,
+        which keeps a neighbouring emission from masking a bin.  ``what='ratio'`` gives the bin's power over that floor, a
+        pure number that :meth:`find_signals`, :meth:`find_peaks`, :meth:`mask_test` and :meth:`level_hist` take as
+        magnitudes with a threshold such as ``frames.cfar_alpha(pfa, 2 * train)``; ``what='floor'`` the floor itself, a
+        power.  Bins outside ``[lo, hi)`` are +0.0.  Every sum is a float64 balanced pair tree in bin order, the quotient a
+        float64 division rounded once to float32: frames.cfar_of_rows is the numpy mirror, bit for bit.
+
+        ``train`` is 1, 2, 4, ..., 64, ``guard`` 0..64, ``0 <= lo < hi <= 16384`` with ``hi - lo >= 2 * guard + 2``, ints only
+        (a bool or a float is SA_EINVAL); ``mode`` is 'ca', 'go' or 'so' and ``what`` 'ratio' or 'floor'; a wrong dtype is
+        SA_EINVAL and a wrong shape SA_ESHAPE, all before any device call.  One launch on the current stream of the handle's
+        device -- the parameters travel in the launch's arguments -- no atomics, nothing zeroed, no handle state, no
+        workspace: it captures into a graph at any time.  Where ``t`` is the result of a call made in overlap mode, call
+        :meth:`flush` first.  Pointer contract (checked by the C entry point, SA_EINVAL): ``t`` and ``out`` are 16-byte
+        aligned and the R * 65536 bytes written do not meet the bytes read; buffers that merely touch are fine."""
+        code, log2_train, m, w = self._cfar_args(train, guard, mode, what, lo, hi, field)
+        R = self._check_in(t, torch.float32, (SA_N, 2) if code else SA_N)
+        out = self._cfar_out(R, out)
+        self._call(abi.cfar_lib(), "sa_cfar_f32", t.data_ptr(), code, out.data_ptr(), R, log2_train, int(guard), m, w, int(lo),
+                   int(hi))
+        return out
+
+    def cfar_f32(self, x: torch.Tensor, train: int = 16, guard: int = 2, mode: str = "ca", what: str = "ratio", lo: int = 0,
+                 hi: int = SA_N, group: Optional[int] = None, scale: float = 1.0 / 2048.0,
+                 work: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The CFAR normalisation of the float chain's spectra, without the spectra leaving the device: float32 [R,16384],
+        the value of :meth:`cfar`.  ``x`` is float32, int16 or packed uint8 exactly as for :meth:`process_f32`; every filter
+        mode and both precisions apply.
+
+        Without ``group`` (R = B) the rows are ``process_f32(x, out_kind='mag_full', scale=scale)`` in the workspace of
+        :meth:`spectra_f32`: every frame against its own floor.  With ``group=A`` (2, 4, ..., 128; R = B // A) they are
+        ``spectra_f32(x, group=A, scale=scale, work=work)`` with ``field='power'``: the summed power of every A consecutive
+        frames against its floor -- a smoother floor, to which ``frames.cfar_alpha`` does not apply.
+
+        The workspace is ``work`` or the cached tensor, as for :meth:`spectra_f32`, and in overlap mode the call joins every
+        outstanding call of the handle on the device (as :meth:`flush` does) before the normalisation: the result is valid on
+        the current stream when the call returns, and the call lends nothing.  The parameters and ``out`` are refused as by
+        :meth:`cfar`, ``group`` and a B that is no multiple of it as by :meth:`spectra_f32`, all before anything is launched,
+        and so is a wrong ``work``."""
+        self._cfar_args(train, guard, mode, what, lo, hi, None)
+        return self._of_spectra(x, group, scale, work, lambda R: self._cfar_out(R, out),
+                                lambda t, field, o: self.cfar(t, train, guard, mode, what, lo, hi, field, o))

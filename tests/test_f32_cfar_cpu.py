@@ -1,0 +1,590 @@
+"""The CFAR normalisation without a GPU: frames.cfar_of_rows against a brute-force restatement of include/specan_cfar.h, the
+header's known answers, the specials, the header against the binding table and the library's symbols, the argument check,
+the wrappers' refusals, cfar_alpha, and the use the feature is for: a threshold that follows a shaped noise floor.
+
+Every comparison with the mirror is bit for bit, on uint32 views."""
+import ctypes
+import functools
+import inspect
+import itertools
+import os
+import re
+
+import numpy as np
+import pytest
+
+from conftest import N
+from kernel_inventory import inventory, unit_text
+from native import CSRC, INCLUDE, compiles_as_c, declared, exported, needed, remarks, standalone_checks, undefined
+from test_f32_bands_cpu import wide_rows
+
+SA_OK, SA_EINVAL, SA_ESHAPE = 0, -1, -2
+BASE = (1 << 47) - (1 << 36)
+HEADER = os.path.join(INCLUDE, "specan_cfar.h")
+NAMES = ["sa_cfar_check", "sa_cfar_f32", "sa_cfar_last_error", "sa_cfar_version"]
+KERNELS = {f"cfar_f32_kernel<{f}>" for f in range(3)}
+FIELDS = (None, "peak", "power")
+MODES = ("ca", "go", "so")
+WHATS = ("ratio", "floor")
+QNAN, INF = 0x7FC00000, 0x7F800000
+# (train, guard, lo, hi): the ends of both parameters, the defaults, odd ranges near both ends of the row
+SETUPS = ((1, 0, 0, N), (64, 64, 0, N), (16, 2, 0, N), (4, 1, 1, N - 1), (8, 3, 37, 16001), (64, 64, 5, 135), (2, 0, 16381, N),
+          (32, 7, 1023, 2051), (1, 64, 3, 16383), (64, 0, 0, 2))
+
+
+def _shared(a):
+    a.setflags(write=False)
+    return a
+
+
+def bits(a):
+    return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
+def records_of(pts, field):
+    """the rows as the input of layout `field`: the points themselves, or records whose other float is a NaN"""
+    if field is None:
+        return pts
+    rec = np.full(pts.shape + (2,), np.nan, np.float32)
+    rec[..., 0 if field == "peak" else 1] = pts
+    return rec
+
+
+def sampled_bins(T, G, lo, hi, extra=()):
+    """the bins the restatement is held on: all within G + T + 2 of lo and hi (and a little outside the range), the ends of
+    the row, and a spread between"""
+    near = [b for c in (lo, hi) for b in range(c - G - T - 2, c + G + T + 3)]
+    spread = list(range(lo, hi, 997)) + [0, 1, N - 2, N - 1] + list(extra)
+    return sorted({b for b in near + spread if 0 <= b < N})
+
+
+def brute(pts, train, guard, mode, what, lo, hi, field, bins):
+    """include/specan_cfar.h restated bin by bin in Python scalars: every window's pair tree built from scratch by halving.
+    uint32 [R, len(bins)]."""
+    T, G = train, guard
+
+    def cell(row, j):
+        if not (lo <= j < hi) or not (0 <= j < N):
+            return np.float64(0.0)
+        a = np.float64(np.abs(row[j]))
+        return a if field == "power" else a * a
+
+    def tree(c):
+        return c[0] if len(c) == 1 else tree(c[:len(c) // 2]) + tree(c[len(c) // 2:])
+
+    out = np.zeros((len(pts), len(bins)), np.uint32)
+    with np.errstate(all="ignore"):
+        for r, row in enumerate(pts):
+            for n_, i in enumerate(bins):
+                if not lo <= i < hi:
+                    continue
+                a = np.float64(np.abs(row[i]))
+                v = a if field == "power" else a * a
+                left, right = range(i - G - T, i - G), range(i + G + 1, i + G + 1 + T)
+                L, R = tree([cell(row, j) for j in left]), tree([cell(row, j) for j in right])
+                nL, nR = sum(lo <= j < hi for j in left), sum(lo <= j < hi for j in right)
+                assert nL + nR >= 1
+                if mode == "ca":
+                    S, n = L + R, nL + nR
+                else:
+                    pl, pr = L * np.float64(nR), R * np.float64(nL)
+                    take_left = True if nR == 0 else False if nL == 0 else bool(pl >= pr) if mode == "go" else bool(pl <= pr)
+                    S, n = (L, nL) if take_left else (R, nR)
+                if np.isnan(L) or np.isnan(R) or (what == "ratio" and np.isnan(v)):
+                    out[r, n_] = QNAN
+                elif S == 0:
+                    out[r, n_] = INF if what == "ratio" and v != 0 else 0
+                else:
+                    q = (v * np.float64(n)) / S if what == "ratio" else S / np.float64(n)
+                    out[r, n_] = QNAN if np.isnan(q) else np.array([q]).astype(np.float32).view(np.uint32)[0]
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def random_rows():
+    """4 rows: two log-uniform over 12 decades with a carrier, one of |N(0,1)| noise with signs, one of small integers"""
+    rng = np.random.default_rng(2600)
+    pts = np.empty((4, N), np.float32)
+    pts[:2] = wide_rows()[:2]
+    pts[2] = rng.standard_normal(N).astype(np.float32)
+    pts[3] = rng.integers(0, 9, N).astype(np.float32)
+    return _shared(pts)
+
+
+@functools.lru_cache(maxsize=None)
+def special_rows():
+    """8 rows around bin 5000 (and the row's ends), in a floor of 1.0 unless said:
+    0  a NaN at 5000 and at 2 and N - 1   1  +inf at 5000 and 5003   2  -0.0 everywhere but 5000 (1.0)   3  all +0.0
+    4  float32 denormals (1e-42 .. 1e-39), -1e-40 among them   5  1e-30 at 5000 in a floor of 1e+8: a denormal ratio
+    6  a block of zeros 4990..5010 around 2.0 at 5000   7  -3.0 at 5000 and the largest float at 8000"""
+    p = np.ones((8, N), np.float32)
+    p[0, [2, 5000, N - 1]] = np.nan
+    p[1, [5000, 5003]] = np.inf
+    p[2] = -0.0
+    p[2, 5000] = 1.0
+    p[3] = 0.0
+    p[4] = np.float32(1e-42) * (1 + np.arange(N) % 900).astype(np.float32)
+    p[4, 5001] = -1e-40
+    p[5] = 1e8
+    p[5, 5000] = 1e-30
+    p[6, 4990:5011] = 0.0
+    p[6, 5000] = 2.0
+    p[7, 5000] = -3.0
+    p[7, 8000] = np.finfo(np.float32).max
+    return _shared(p)
+
+
+SPECIAL_BINS = (0, 1, 2, 3, 4, 4980, 4989, 4990, 4995, 4996, 4997, 4998, 4999, 5000, 5001, 5002, 5003, 5004, 5005, 5010, 5011, 5020,
+                7990, 8000, 8003, N - 3, N - 2, N - 1)
+
+
+def cfar(pts, field=None, **kw):
+    from fpga_real_time_fft_analyzer_amd import frames
+    return bits(frames.cfar_of_rows(records_of(pts, field), field=field, **kw))
+
+
+# ------------------------------------------------------------------------------------------------------------- the mirror
+def test_known_answers_of_the_header():
+    x = np.ones((1, N), np.float32)
+    x[0, 100] = 3.0
+    at = (0, 97, 98, 99, 100, 101, 102, N - 1)
+    want = {"ca": [1.0, 0.5, 0.5, 1.0, 9.0, 1.0, 0.5, 1.0], "go": [1.0, 1 / 3, 1 / 3, 1.0, 9.0, 1.0, 1 / 3, 1.0], "so": [1.0] * 4 + [9.0] + [1.0] * 3}
+    for mode in MODES:
+        got = cfar(x, train=4, guard=1, mode=mode)
+        assert got[0, at].tolist() == bits(np.array(want[mode], np.float32)).tolist(), mode
+        assert (cfar(np.ones((2, N), np.float32), train=4, guard=1, mode=mode) == 0x3F800000).all(), mode
+        for field in FIELDS[1:]:
+            y = x * x if field == "power" else x                   # a power is taken as it is: 9.0 stands there
+            assert np.array_equal(cfar(y, field, train=4, guard=1, mode=mode), got), (mode, field)
+    assert cfar(x, train=4, guard=1, mode="go")[0, 97] == 0x3EAAAAAB
+    # the floor of the same row: 1.0 away from the carrier, (3 * 1 + 9) / 4 = 3 on the side that holds it
+    floor = cfar(x, train=4, guard=1, mode="go", what="floor")
+    assert floor[0, [0, 97, 100, N - 1]].tolist() == bits(np.array([1.0, 3.0, 1.0, 1.0], np.float32)).tolist()
+
+
+@pytest.mark.parametrize("setup", SETUPS, ids=lambda s: "T{}G{}_{}_{}".format(*s))
+def test_the_mirror_against_the_restatement(setup):
+    """All three modes, both outputs and all three layouts on every setup: sampled bins within G + T of lo and hi, odd lo and
+    hi, T = 1 with G = 0 and T = 64 with G = 64 among them.  Outside [lo, hi) every float is +0.0."""
+    train, guard, lo, hi = setup
+    pts = random_rows()
+    at = sampled_bins(train, guard, lo, hi)
+    for n, (mode, what, field) in enumerate(itertools.product(MODES, WHATS, FIELDS)):
+        rows = pts[n % 4:n % 4 + 1] if train > 8 else pts          # the large trees on one row a combination, in turn
+        got = cfar(rows, field, train=train, guard=guard, mode=mode, what=what, lo=lo, hi=hi)
+        want = brute(rows, train, guard, mode, what, lo, hi, field, at)
+        assert np.array_equal(got[:, at], want), (setup, mode, what, field, np.argwhere(got[:, at] != want)[:4])
+        assert not got[:, :lo].any() and not got[:, hi:].any()
+        assert got[:, lo:hi].any()
+
+
+def test_the_modes_differ_and_agree_where_they_must():
+    """On noise GO <= CA <= SO as ratios wherever both sides are whole (the larger mean is the smaller ratio); at the first
+    bins of the range only the right side exists, and the three agree bit for bit."""
+    pts = random_rows()[2:3]
+    r = {m: cfar(pts, train=16, guard=2, mode=m).view(np.float32)[0] for m in MODES}
+    inner = slice(18, N - 18)
+    assert (r["go"][inner] <= r["so"][inner]).all() and (r["go"][inner] < r["so"][inner]).mean() > 0.99
+    lo_, hi_ = np.minimum(r["go"], r["so"])[inner], np.maximum(r["go"], r["so"])[inner]
+    assert ((lo_ <= r["ca"][inner] * (1 + 1e-6)) & (r["ca"][inner] <= hi_ * (1 + 1e-6))).all()
+    assert np.array_equal(r["go"][:3], r["so"][:3]) and np.array_equal(r["go"][:3], r["ca"][:3])
+    assert np.array_equal(r["go"][-3:], r["so"][-3:]) and np.array_equal(r["go"][-3:], r["ca"][-3:])
+
+
+def test_specials():
+    """A NaN in a window -- on the side taken, on the side not taken and as the point -- +inf, -0.0, denormals, the all-zero
+    row and a ratio in the float32 denormal range: the restatement's bits, and the values the header names."""
+    p = special_rows()
+    for mode, what, field in itertools.product(MODES, WHATS, FIELDS):
+        got = cfar(p, field, train=4, guard=1, mode=mode, what=what)
+        want = brute(p, 4, 1, mode, what, 0, N, field, SPECIAL_BINS)
+        assert np.array_equal(got[:, SPECIAL_BINS], want), (mode, what, field, np.argwhere(got[:, SPECIAL_BINS] != want)[:4])
+        nan = np.isnan(got.view(np.float32))
+        assert (got[nan] == QNAN).all()                            # one NaN pattern, never another
+    for mode in MODES:
+        ratio, floor = (cfar(p, train=4, guard=1, mode=mode, what=w) for w in WHATS)
+        # row 0: the point a NaN -- the ratio is, the floor is not; bins 4995..4998 hold it in their right window and
+        # 5002..5005 in their left, taken or not; bins 4994 and 5006 do not
+        assert ratio[0, 5000] == QNAN and floor[0, 5000] == 0x3F800000
+        assert (ratio[0, 4995:4999] == QNAN).all() and (floor[0, 5002:5006] == QNAN).all()
+        assert ratio[0, 4994] == 0x3F800000 == ratio[0, 5006] and ratio[0, 0] == QNAN and ratio[0, 1] == 0x3F800000
+        # row 1, +inf at 5000 and 5003: over the finite left side it is +inf, over the right side, which holds the other,
+        # the one NaN; a finite point over an infinite floor is +0.0
+        assert ratio[1, 5000] == (INF if mode == "so" else QNAN) and floor[1, 4998] == (0x3F800000 if mode == "so" else INF)
+        assert ratio[1, 4996] == (0x3F800000 if mode == "so" else 0)
+        # rows 2 and 3: -0.0 is +0.0; 0 over 0 is +0.0, something over 0 +inf, the floor +0.0
+        assert ratio[2, 5000] == INF and floor[2, 5000] == 0 and ratio[2, 100] == 0 and not ratio[3].any() and not floor[3].any()
+        # row 4: denormals are kept: the floor is their square in float64, far below float32 -- +0.0 -- and the ratio is not
+        assert not floor[4].any() and (ratio[4, 10:N - 10] > 0).all() and (ratio[4] < INF).all()
+        # row 5: 1e-60 over 1e+16 is 1e-76 in float64 and +0.0 as a float; as a power 1e-30 over 1e+8 = 1e-38 is a denormal
+        assert ratio[5, 5000] == 0
+        den = cfar(p, "power", train=4, guard=1, mode=mode)[5, 5000]
+        assert 0 < den < 0x00800000 and den == bits(np.float32(np.float64(np.float32(1e-30)) * 8 / (8 * np.float64(np.float32(1e8)))
+                                                               if mode == "ca" else np.float64(np.float32(1e-30)) / np.float64(np.float32(1e8))))
+    # the side not taken: bin 4996 of row 1 has +inf on its right alone; SO takes the left and is finite -- a NaN there instead
+    # makes it the NaN all the same
+    q = np.ones((1, N), np.float32)
+    q[0, 5000] = np.nan
+    assert cfar(q, train=4, guard=1, mode="so")[0, 4996] == QNAN and cfar(q, train=4, guard=1, mode="so", what="floor")[0, 4996] == QNAN
+
+
+def test_arguments_of_the_mirror():
+    from fpga_real_time_fft_analyzer_amd import frames
+    x = np.zeros((1, N), np.float32)
+    for kw, words in ((dict(train=3), "train must be one of"), (dict(train=128), "train must be one of"), (dict(train=0), "train must be one of"),
+                      (dict(train=True), "train must be an int"), (dict(train=4.0), "train must be an int"), (dict(guard=-1), "guard must be 0..64"),
+                      (dict(guard=65), "guard must be 0..64"), (dict(guard=1.0), "guard must be an int"), (dict(mode="os"), "mode must be"),
+                      (dict(mode=0), "mode must be"), (dict(what="db"), "what must be"), (dict(what=None), "what must be"),
+                      (dict(lo=5, hi=5), "the range must be 0 <= lo < hi <= 16384"), (dict(hi=N + 1), "the range must be"),
+                      (dict(lo=False), "lo must be an int"), (dict(lo=10, hi=15, guard=2), "the range must hold 2 * guard + 2 bins or more"),
+                      (dict(lo=0, hi=1, guard=0), "the range must hold"), (dict(field="mag"), "field must be None, 'peak' or 'power'")):
+        with pytest.raises(ValueError, match=re.escape(words)):
+            frames.cfar_of_rows(x, **kw)
+    for bad in (x.astype(np.float64), x[0], np.zeros((1, N, 2), np.float32), np.zeros((1, N - 1), np.float32)):
+        with pytest.raises(ValueError, match="points must be float32"):
+            frames.cfar_of_rows(bad)
+    with pytest.raises(ValueError, match="points must be float32"):
+        frames.cfar_of_rows(x, field="peak")
+    assert frames.cfar_of_rows(x, lo=10, hi=16, guard=2).shape == (1, N) and frames.cfar_of_rows(x[:0]).shape == (0, N)
+    assert frames.cfar_of_rows(x, np.int64(4), np.int32(1)).dtype == np.float32
+    assert frames._cfar_args(64, 64, "so", "floor", 0, 130, "power") == (6, 64, 2, 1, 0, 130)
+    assert frames.CFAR_TRAINS == (1, 2, 4, 8, 16, 32, 64) and frames.CFAR_GUARD_MAX == 64
+
+
+def test_cfar_alpha():
+    from fpga_real_time_fft_analyzer_amd import frames
+    # n (pfa^(-1/n) - 1) at three points, worked by hand: n = 1 gives 1/pfa - 1; n = 2, pfa = 1/4 gives 2 (2 - 1); and
+    # (1 + alpha / n)^-n = pfa read backwards at (1e-6, 32)
+    assert frames.cfar_alpha(0.5, 1) == 1.0 and frames.cfar_alpha(0.25, 2) == 2.0
+    a = frames.cfar_alpha(1e-6, 32)
+    assert a == 32 * (1e-6 ** (-1 / 32) - 1) and abs((1 + a / 32) ** -32 / 1e-6 - 1) < 1e-12 and 17.27 < a < 17.29
+    assert frames.cfar_alpha(1e-3, np.int64(8)) == 8 * (1e-3 ** (-1 / 8) - 1)
+    for pfa, n in ((0.0, 4), (1.0, 4), (-0.1, 4), (1.5, 4), ("0.1", 4), (True, 4), (0.1, 0), (0.1, -1), (0.1, 2.0), (0.1, True), (None, 4)):
+        with pytest.raises(ValueError):
+            frames.cfar_alpha(pfa, n)
+    assert "single frames" in frames.cfar_alpha.__doc__ and "group" in frames.cfar_alpha.__doc__
+
+
+@functools.lru_cache(maxsize=None)
+def shaped_rows():
+    """(magnitudes float32 [4, N], tone bins [4][5]): exponentially distributed power on a floor that falls 40 dB across the
+    span, and in each row five tones 15 dB above the floor where they stand, in the low-floor part of the span"""
+    rng = np.random.default_rng(2610)
+    floor = 10.0 ** (-4.0 * np.arange(N) / N)
+    power = rng.exponential(1.0, (4, N)) * floor
+    tones = [[10000 + 1200 * j + 170 * r for j in range(5)] for r in range(4)]
+    for r in range(4):
+        power[r, tones[r]] = floor[tones[r]] * 10.0 ** 1.5
+    return _shared(np.sqrt(power).astype(np.float32)), tones
+
+
+def test_a_threshold_that_follows_the_floor_finds_what_a_row_wide_one_cannot():
+    """The use case, on the mirrors alone.  Six times the row's median, on the raw rows: every tone is below it and the
+    pass-band shoulder gives hundreds of segments.  cfar_alpha(1e-6, 2 T) on the CFAR ratio: exactly the tones."""
+    from fpga_real_time_fft_analyzer_amd import frames
+    mag, tones = shaped_rows()
+    T = 16
+    thr = (np.float32(6.0) * np.median(mag, axis=1)).astype(np.float32)
+    rec, stats = frames.signals_of_rows(mag, k=32, threshold=thr)
+    assert (stats[:, 0] >= 200).all(), stats[:, 0]                                    # false alarms by the hundred
+    for r in range(4):
+        assert (mag[r, tones[r]] < thr[r]).all()                                      # and blind to every tone
+        assert not np.isin(tones[r], rec["start"][r]).any()
+    ratio = frames.cfar_of_rows(mag, T, 2, "ca", "ratio")
+    alpha = frames.cfar_alpha(1e-6, 2 * T)
+    rec, stats = frames.signals_of_rows(ratio, k=32, threshold=alpha)
+    assert stats[:, 0].tolist() == [5] * 4 and stats[:, 1].tolist() == [5] * 4, stats
+    for r in range(4):
+        assert rec["start"][r, :5].tolist() == tones[r] and rec["stop"][r, :5].tolist() == [b + 1 for b in tones[r]]
+        assert rec["peak_bin"][r, :5].tolist() == tones[r] and (rec["start"][r, 5:] == -1).all()
+    # the floor follows the shape: the estimate at either end of the span is 40 dB apart, within the spread of 32 cells
+    floor = frames.cfar_of_rows(mag, 64, 2, "ca", "floor").astype(np.float64)
+    db = 10 * np.log10(floor[:, 200] / floor[:, N - 200])
+    assert (np.abs(db - 10 * np.log10(10.0 ** (4.0 * (N - 400) / N))) < 3.0).all(), db
+
+
+# ------------------------------------------------------------------------------------------------------------ the surface
+@pytest.fixture(scope="module")
+def cfar_lib():
+    """libspecan_cfar.so, built on demand by the package's one build step (it cross-compiles without a GPU)."""
+    from fpga_real_time_fft_analyzer_amd import abi
+    if not os.path.exists(abi.CFAR_LIB_PATH):
+        abi.build()
+    return abi.cfar_lib()
+
+
+GOOD = dict(rows=3, log2_train=4, guard=2, mode=0, what=0, lo=0, hi=N)
+FAR = {"in": BASE, "out": BASE + (1 << 40)}
+
+
+@pytest.fixture(scope="module")
+def check(cfar_lib):
+    def call(field=0, **kw):
+        addr = {name: kw.pop(name, FAR[name]) for name in FAR}
+        a = dict(GOOD, **kw)
+        return cfar_lib.sa_cfar_check(field, addr["in"], addr["out"], a["rows"], a["log2_train"], a["guard"], a["mode"], a["what"],
+                                      a["lo"], a["hi"])
+    return call
+
+
+def test_header_library_and_binding_table(cfar_lib):
+    """Name for name: declared in specan_cfar.h = exported by libspecan_cfar.so = bound in abi.CFAR_SIGNATURES; nothing is in
+    the other tables or headers, which are what they were.  The row of LIBRARIES stands before "signals", which stays last."""
+    from fpga_real_time_fft_analyzer_amd import abi, frames
+    assert declared(HEADER) == NAMES
+    assert [n for n in exported(abi.CFAR_LIB_PATH) if "sa_" in n] == NAMES
+    assert sorted(abi.CFAR_SIGNATURES) == NAMES
+    others = (abi.SIGNATURES, abi.EXT_SIGNATURES, abi.FOLD_SIGNATURES, abi.PEAKS_SIGNATURES, abi.RANK_SIGNATURES, abi.HIST_SIGNATURES,
+              abi.BANDS_SIGNATURES, abi.MASK_SIGNATURES, abi.HARM_SIGNATURES, abi.SIGNALS_SIGNATURES)
+    assert not set(NAMES) & set().union(*others)
+    assert [len(t) for t in others] == [45, 5, 4, 4, 4, 4, 4, 4, 4, 4]
+    for other in ("specan.h", "specan_ext.h", "specan_fold.h", "specan_peaks.h", "specan_rank.h", "specan_hist.h", "specan_bands.h",
+                  "specan_mask.h", "specan_harm.h", "specan_signals.h"):
+        assert not set(NAMES) & set(declared(os.path.join(INCLUDE, other))), other
+    for name in NAMES:
+        fn, (restype, argtypes) = getattr(cfar_lib, name), abi.CFAR_SIGNATURES[name]
+        assert fn.argtypes is not None and list(fn.argtypes) == list(argtypes), name
+        assert fn.restype is restype is (ctypes.c_char_p if name == "sa_cfar_last_error" else ctypes.c_int), name
+    assert cfar_lib.sa_cfar_version() == abi.SA_CFAR_VERSION == 1
+    text = open(HEADER).read()
+    flat = re.sub(r"\s+", " ", text)
+    for line in ("#define SA_CFAR_VERSION 1", "#define SA_CFAR_IN_MAG 0", "#define SA_CFAR_IN_POINT_PEAK 1", "#define SA_CFAR_IN_POINT_POWER 2",
+                 "#define SA_CFAR_MODE_CA 0", "#define SA_CFAR_MODE_GO 1", "#define SA_CFAR_MODE_SO 2", "#define SA_CFAR_OUT_RATIO 0",
+                 "#define SA_CFAR_OUT_FLOOR 1", "#define SA_CFAR_LOG2_TRAIN_MAX 6", "#define SA_CFAR_GUARD_MAX 64",
+                 "int sa_cfar_f32(const void *in, int field, float *out, int rows, int log2_train, int guard, int mode, int what, "
+                 "int lo, int hi, void *stream);",
+                 "int sa_cfar_check(int field, uint64_t in_addr, uint64_t out_addr, int rows, int log2_train, int guard, int mode, "
+                 "int what, int lo, int hi);",
+                 "int sa_cfar_version(void);", "const char *sa_cfar_last_error(void);"):
+        assert line in flat, line
+    assert '#include "specan.h"' in text and len(re.findall(r"#\s*include", text)) == 1
+    assert (abi.SA_CFAR_IN_MAG, abi.SA_CFAR_IN_POINT_PEAK, abi.SA_CFAR_IN_POINT_POWER) == (0, 1, 2) == \
+        (abi.SA_SIGNALS_IN_MAG, abi.SA_SIGNALS_IN_POINT_PEAK, abi.SA_SIGNALS_IN_POINT_POWER)
+    assert (abi.SA_CFAR_MODE_CA, abi.SA_CFAR_MODE_GO, abi.SA_CFAR_MODE_SO) == (0, 1, 2) == tuple(frames.CFAR_MODES[m] for m in MODES)
+    assert (abi.SA_CFAR_OUT_RATIO, abi.SA_CFAR_OUT_FLOOR) == (0, 1) == tuple(frames.CFAR_OUTPUTS[w] for w in WHATS)
+    assert abi.SA_CFAR_LOG2_TRAIN_MAX == 6 and 1 << 6 == frames.CFAR_TRAINS[-1] and abi.SA_CFAR_GUARD_MAX == 64 == frames.CFAR_GUARD_MAX
+    # the definition and the known answers stand in the header's comment
+    for words in ("W(l+1)[j] = W(l)[j] + W(l)[j + 2^l]", "L * (double)nR >= R * (double)nL", "0x7FC00000", "0x3EAAAAAB", "Refusals"):
+        assert words in flat, words
+    assert cfar_lib.sa_cfar_last_error() == b""
+    assert os.path.basename(abi.CFAR_LIB_PATH) == "libspecan_cfar.so"
+    assert os.path.dirname(abi.CFAR_LIB_PATH) == os.path.dirname(abi.LIB_PATH)
+    assert abi.LIBRARIES["cfar"] == ("libspecan_cfar.so", abi.CFAR_SIGNATURES)
+    assert list(abi.LIBRARIES)[-2:] == ["cfar", "signals"] and len(abi.LIBRARIES) == 9
+    assert abi.SIGNALS_LIB_PATH.endswith("libspecan_signals.so") and abi.HARM_LIB_PATH.endswith("libspecan_harm.so")
+    assert abi.cfar_lib.__name__ == "cfar_lib" and "specan_cfar.h" in abi.cfar_lib.__doc__
+    assert abi.signals_lib.__name__ == "signals_lib" and abi.harm_lib.__name__ == "harm_lib"
+
+
+def test_header_compiles_as_c99_pedantic(tmp_path):
+    compiles_as_c(tmp_path, '#include "specan_cfar.h"\n'
+                  "int use(const void *p, float *o) {"
+                  " return sa_cfar_f32(p, SA_CFAR_IN_POINT_POWER, o, 8, SA_CFAR_LOG2_TRAIN_MAX, SA_CFAR_GUARD_MAX, SA_CFAR_MODE_GO,"
+                  " SA_CFAR_OUT_FLOOR, 0, SA_N, 0)"
+                  " + sa_cfar_check(SA_CFAR_IN_MAG, 16, 1 << 20, 1, 0, 0, SA_CFAR_MODE_CA, SA_CFAR_OUT_RATIO, 0, 2)"
+                  " + sa_cfar_version() - SA_CFAR_VERSION + (sa_cfar_last_error()[0] != 0) + SA_CFAR_IN_POINT_PEAK - 1"
+                  " + SA_CFAR_MODE_SO - 2; }\n")
+
+
+def test_library_links_hip_alone_and_reads_no_environment(cfar_lib):
+    from fpga_real_time_fft_analyzer_amd import abi
+    libs = needed(abi.CFAR_LIB_PATH)
+    for other in ("torch", "oracle", "specan_hip", "specan_fold", "specan_peaks", "specan_rank", "specan_hist", "specan_bands",
+                  "specan_mask", "specan_harm", "specan_signals"):
+        assert other not in libs, libs
+    assert "amdhip64" in libs
+    assert "getenv" not in undefined(abi.CFAR_LIB_PATH)
+    text = unit_text("cfar_f32.hip") + unit_text("sa_cfar_check.cpp")
+    assert "sa_cfar_f32" in text and "sa_cfar_check_call" in text
+    assert "getenv" not in text and "environ" not in text.replace("environment", "")
+    kernel = open(os.path.join(CSRC, "cfar_f32.hip")).read()
+    code = re.sub(r"//.*", "", kernel)
+    assert "atomic" not in code and "s_setreg" not in code and "denorm" not in code and "hipMemset" not in code
+    assert "#pragma clang fp contract(off)" in code
+    # one launch, written once for the three instantiations
+    assert len(re.findall(r"hipLaunchKernelGGL", code)) == 1 and "extern __shared__" not in code
+    # the units include nothing of the chains or of the other reductions
+    assert not re.search(r'#\s*include\s+"(?!sa_cfar\.hpp|\.\./\.\./include/specan_cfar\.h|specan\.h)', text), text[:200]
+    # the one check behind both entry points
+    assert len(re.findall(r"sa_cfar_check_call\(", unit_text("sa_cfar_check.cpp"))) >= 2
+    assert len(re.findall(r"sa_cfar_check_call\(", code)) == 1
+
+
+def test_kernel_inventory(cfar_lib):
+    """libspecan_cfar.so holds the three instantiations, one per input layout, and nothing else."""
+    from fpga_real_time_fft_analyzer_amd import abi
+    assert inventory(abi.CFAR_LIB_PATH) == KERNELS
+
+
+def test_resource_remarks_show_no_scratch_and_no_spill():
+    """The compiler's figures for the three kernels, as `make resource-cfar-f32` prints them: no scratch, no SGPR or VGPR
+    spill, static LDS only and small enough for more than one workgroup on a CU (160 KiB).  VGPRs, occupancy and LDS are
+    printed; DESIGN.md section 4.24 records them."""
+    err = remarks("cfar_f32.hip")
+    assert len(re.findall(r"Function Name: \S*cfar_f32_kernel", err)) == 3
+    for what in ("ScratchSize \\[bytes/lane\\]", "SGPRs Spill", "VGPRs Spill"):
+        got = [int(v) for v in re.findall(what + r": (\d+)", err)]
+        assert got == [0] * 3, (what, got)
+    lds = [int(v) for v in re.findall(r"LDS Size \[bytes/block\]: (\d+)", err)]
+    assert len(lds) == 3 and all(0 < v <= 160 * 1024 // 2 for v in lds), lds
+    print("FIGURE VGPRs", re.findall(r" VGPRs: (\d+)", err), "occupancy", re.findall(r"Occupancy \[waves/SIMD\]: (\d+)", err), "LDS", lds)
+    assert "extern __shared__" not in unit_text("cfar_f32.hip")
+    make = open(os.path.join(CSRC, "Makefile")).read()
+    assert "resource-cfar-f32: UNITS = cfar_f32.hip" in make and re.search(r"^all:.*\$\(CFAR_OUT\)", make, re.M)
+    assert re.search(r"^CFAR_SRCS = cfar_f32\.hip sa_cfar_check\.cpp$", make, re.M) and re.search(r"^CFAR_OBJS = ", make, re.M)
+    assert re.search(r"^CFAR_OUT = \.\./libspecan_cfar\.so$", make, re.M)
+    assert re.search(r"^\$\(CFAR_OUT\): \$\(CFAR_OBJS\)\n\t\$\(HIPCC\) \$\(CXXFLAGS\) -shared \$\(CFAR_OBJS\) -o \$@$", make, re.M)
+    assert re.search(r"^UNITS = .*\$\(CFAR_SRCS\)", make, re.M) and re.search(r"^clean:\n\trm .*\$\(CFAR_OUT\)", make, re.M)
+    assert re.search(r"^RESOURCE = .*resource-cfar-f32", make, re.M) and "libspecan_cfar.so" in make.split("\n", 3)[1]
+
+
+# -------------------------------------------------------------------------------------------------------------- the check
+def test_known_answers_and_touching_ranges(check):
+    """The byte counts of the header's two known calls, and `out` right behind and right in front of `in` against one byte
+    less: at addresses past 2^32 and near 2^47."""
+    assert check(0, rows=3, **{"in": BASE, "out": BASE + 196608}) == SA_OK
+    assert check(0, rows=3, **{"in": BASE, "out": BASE + 196608 - 16}) == SA_EINVAL
+    assert check(0, rows=3, **{"in": BASE, "out": BASE - 196608}) == SA_OK
+    assert check(0, rows=3, **{"in": BASE, "out": BASE - 196608 + 16}) == SA_EINVAL
+    assert check(1, rows=3, **{"in": BASE, "out": BASE + 196608}) == SA_EINVAL        # records read twice as much
+    assert check(2, rows=1, **{"in": BASE, "out": BASE + 131072}) == SA_OK
+    assert check(2, rows=1, **{"in": BASE, "out": BASE + 131072 - 16}) == SA_EINVAL
+    assert check(2, rows=1, **{"in": BASE, "out": BASE - 65536}) == SA_OK
+    assert check(2, rows=1, **{"in": BASE, "out": BASE - 65536 + 16}) == SA_EINVAL
+    for X in (BASE + (1 << 30), (1 << 32) - 65536, 1 << 33):
+        for field, rows in itertools.product((0, 1, 2), (1, 5, 4096, (1 << 31) - 1)):
+            n_in, n_out = rows * 65536 * (2 if field else 1), rows * 65536
+            Y = X + (1 << 50)
+            assert check(field, rows=rows, **{"in": Y, "out": Y + n_in}) == SA_OK and check(field, rows=rows, **{"in": Y, "out": Y - n_out}) == SA_OK
+            assert check(field, rows=rows, **{"in": Y, "out": Y + n_in - 16}) == SA_EINVAL
+            assert check(field, rows=rows, **{"in": Y, "out": Y - n_out + 16}) == SA_EINVAL
+            assert check(field, rows=rows, **{"in": Y, "out": Y}) == SA_EINVAL
+            apart = {"in": 1 << 50, "out": 1 << 60}                # 2^48 bytes at the most lie between them
+            for off in (1, 2, 4, 8, 12, 16, 32):
+                assert check(field, rows=rows, **dict(apart, **{"in": apart["in"] + off})) == (SA_OK if off % 16 == 0 else SA_EINVAL)
+                assert check(field, rows=rows, **dict(apart, out=apart["out"] + off)) == (SA_OK if off % 16 == 0 else SA_EINVAL)
+            assert check(field, rows=rows, **dict(apart, **{"in": 0})) == SA_EINVAL and check(field, rows=rows, **dict(apart, out=0)) == SA_EINVAL
+
+
+def test_refusals_in_their_order(check, cfar_lib):
+    """1 negative rows, 2 the field and the parameters (also at rows 0), 3 the empty call, 4 the pointers: each refusal is
+    shown to win over every later one by making the later ones wrong too."""
+    bad = [dict(field=-1), dict(field=3), dict(mode=-1), dict(mode=3), dict(what=-1), dict(what=2), dict(log2_train=-1), dict(log2_train=7),
+           dict(log2_train=2 ** 31 - 1), dict(guard=-1), dict(guard=65), dict(guard=-2 ** 31), dict(lo=-1), dict(lo=5, hi=5), dict(lo=6, hi=5),
+           dict(hi=N + 1), dict(lo=-2 ** 31, hi=2 ** 31 - 1), dict(lo=0, hi=1, guard=0), dict(lo=100, hi=105), dict(lo=7, hi=136, guard=64)]
+    wrong_ptrs = [dict(), {"in": 0, "out": 0}, {"in": BASE + 1, "out": BASE + 3}, {"in": BASE, "out": BASE}]
+    for kw in [dict()] + bad:
+        for p in wrong_ptrs:
+            assert check(**dict(p, rows=-1, **kw)) == SA_ESHAPE, (kw, p)
+            assert check(**dict(p, rows=-(1 << 31), **kw)) == SA_ESHAPE, (kw, p)
+    for rows in (0, 1, 5, (1 << 31) - 1):
+        for kw in bad:
+            for p in wrong_ptrs:
+                assert check(**dict(p, rows=rows, **kw)) == SA_EINVAL, (rows, kw, p)
+    for p in wrong_ptrs:
+        for field in (0, 1, 2):
+            assert check(field=field, **dict(p, rows=0)) == SA_OK, p
+    for p in wrong_ptrs[1:]:
+        assert check(**dict(p, rows=1)) == SA_EINVAL, p
+    assert check(rows=1) == SA_OK
+    for kw in (dict(log2_train=0, guard=0, lo=0, hi=2), dict(log2_train=6, guard=64, lo=N - 130, hi=N), dict(field=2, mode=2, what=1),
+               dict(lo=7, hi=137, guard=64), dict(rows=(1 << 31) - 1, **{"in": 1 << 20, "out": 1 << 62})):
+        assert check(**kw) == SA_OK, kw
+    assert cfar_lib.sa_cfar_last_error() == b""                    # the check alone leaves the thread's text alone
+
+
+def test_standalone_program_under_host_sanitizers(tmp_path):
+    """tests/cpp/test_sa_cfar_check.cpp + csrc/sa_cfar_check.cpp, host only, under the address and undefined-behaviour
+    sanitizers when they link here (a plain build otherwise: the program's own checks still run): every refusal in its order
+    with the later ones wrong too, the known answers in bytes, touching and overlapping buffers at rows up to 2^31 - 1 and
+    addresses past 2^32, near 2^47 and near 2^64.  Nothing is loaded into this process."""
+    assert standalone_checks(tmp_path, "test_sa_cfar_check", ["sa_cfar_check.cpp"]) > 25000
+
+
+# ----------------------------------------------------------------------------------------------------------- the wrappers
+CASES = [
+    ('bare.cfar(None, train=True)', -1, 'train must be an int'),
+    ('bare.cfar(None, train=16.0)', -1, 'train must be an int'),
+    ('bare.cfar(None, guard=2.0)', -1, 'guard must be an int'),
+    ('bare.cfar(None, guard=False)', -1, 'guard must be an int'),
+    ('bare.cfar(None, lo=0.0)', -1, 'lo must be an int'),
+    ("bare.cfar(None, hi='5')", -1, 'hi must be an int'),
+    ('bare.cfar(None, train=3)', -1, 'train must be one of (1, 2, 4, 8, 16, 32, 64)'),
+    ('bare.cfar(None, train=0)', -1, 'train must be one of (1, 2, 4, 8, 16, 32, 64)'),
+    ('bare.cfar(None, train=128)', -1, 'train must be one of (1, 2, 4, 8, 16, 32, 64)'),
+    ('bare.cfar(None, guard=-1)', -1, 'guard must be 0..64'),
+    ('bare.cfar(None, guard=65)', -1, 'guard must be 0..64'),
+    ("bare.cfar(None, mode='os')", -1, "mode must be 'ca', 'go' or 'so'"),
+    ('bare.cfar(None, mode=0)', -1, "mode must be 'ca', 'go' or 'so'"),
+    ("bare.cfar(None, what='db')", -1, "what must be 'ratio' or 'floor'"),
+    ('bare.cfar(None, what=1)', -1, "what must be 'ratio' or 'floor'"),
+    ('bare.cfar(None, lo=5, hi=5)', -1, 'the range must be 0 <= lo < hi <= 16384'),
+    ('bare.cfar(None, hi=N + 1)', -1, 'the range must be 0 <= lo < hi <= 16384'),
+    ('bare.cfar(None, lo=10, hi=15)', -1, 'the range must hold 2 * guard + 2 bins or more'),
+    ('bare.cfar(None, guard=64, lo=0, hi=129)', -1, 'the range must hold 2 * guard + 2 bins or more'),
+    ("bare.cfar(None, field='mag')", -1, "field must be None, 'peak' or 'power'"),
+    ('bare.cfar(None, field=0)', -1, "field must be None, 'peak' or 'power'"),
+    ("bare.cfar(None, train=True, field='mag')", -1, 'train must be an int'),
+    ('bare.cfar(None)', -1, 'input must be a torch.float32 tensor'),
+    ("bare.cfar(None, 64, 64, 'so', 'floor', 0, 130, 'power')", -1, 'input must be a torch.float32 tensor'),
+    ("host.cfar(X, field='power')", -2, 'input must be a contiguous [B, 16384, 2] tensor'),
+    ('host.cfar(REC)', -2, 'input must be a contiguous [B, 16384] tensor'),
+    ('host.cfar(X, out=BAD)', -2, 'out must be a contiguous torch.float32 tensor of shape (2, 16384)'),
+    ('host.cfar(X, out=torch.zeros((2, N), dtype=torch.float64))', -2, 'out must be a contiguous torch.float32 tensor of shape (2, 16384)'),
+    ("host.cfar(REC, field='peak', out=torch.zeros((2, N, 2)))", -2, 'out must be a contiguous torch.float32 tensor of shape (2, 16384)'),
+    ('bare.cfar_f32(None, train=5)', -1, 'train must be one of (1, 2, 4, 8, 16, 32, 64)'),
+    ('bare.cfar_f32(None, train=5, group=3)', -1, 'train must be one of (1, 2, 4, 8, 16, 32, 64)'),
+    ('bare.cfar_f32(None, guard=1.5)', -1, 'guard must be an int'),
+    ('bare.cfar_f32(None, guard=100)', -1, 'guard must be 0..64'),
+    ("bare.cfar_f32(None, mode='CA')", -1, "mode must be 'ca', 'go' or 'so'"),
+    ("bare.cfar_f32(None, what='snr')", -1, "what must be 'ratio' or 'floor'"),
+    ('bare.cfar_f32(None, lo=5, hi=5)', -1, 'the range must be 0 <= lo < hi <= 16384'),
+    ('bare.cfar_f32(None, lo=0, hi=5)', -1, 'the range must hold 2 * guard + 2 bins or more'),
+    ('bare.cfar_f32(None, group=3)', -1, 'group must be one of (1, 2, 4, 8, 16, 32, 64, 128)'),
+    ('bare.cfar_f32(None, group=1)', -1, 'group = bucket = 1 folds nothing'),
+    ('bare.cfar_f32(None, group=2.0)', -1, 'group must be one of (1, 2, 4, 8, 16, 32, 64, 128)'),
+    ('bare.cfar_f32(None, group=128)', -1, 'input must be a torch.float32 tensor'),
+    ('bare.cfar_f32(None)', -1, 'input must be a torch.float32 tensor'),
+    ('host.cfar_f32(X, group=4)', -2, 'the batch (2 frames) must be a multiple of 4'),
+    ('host.cfar_f32(X, group=2, out=torch.zeros((2, N)))', -2, 'out must be a contiguous torch.float32 tensor of shape (1, 16384)'),
+    ('host.cfar_f32(X, out=BAD)', -2, 'out must be a contiguous torch.float32 tensor of shape (2, 16384)'),
+    ('host.cfar_f32(X, work=BAD)', -2, 'work must be a contiguous torch.float32 tensor of shape [2 or more, 16384]'),
+    ('host.cfar_f32(X, group=2, work=torch.zeros((1, N)))', -2, 'work must be a contiguous torch.float32 tensor of shape [2 or more, 16384]'),
+]
+
+
+def _namespace():
+    from test_reductions_wrappers_cpu import _namespace as objects
+    return objects()
+
+
+def test_every_refusal_of_the_wrappers_has_its_code_and_its_text():
+    """``bare`` is an object without a handle, a device or a library: nothing of it may be touched before the scalar
+    arguments and the input's type have passed.  ``host`` has the CPU as its device, so that the refusals behind the input's
+    check speak: the batch, the output and the workspace.  Every row ends in a refusal: nothing is loaded or launched."""
+    from fpga_real_time_fft_analyzer_amd.abi import SpecanError
+    ns = _namespace()
+    assert len({call for call, _, _ in CASES}) == len(CASES)
+    for call, code, message in CASES:
+        with pytest.raises(SpecanError) as e:
+            eval(call, ns)
+        assert (e.value.code, str(e.value)) == (code, f"specan error {code}: {message}"), call
+    for method in ("cfar", "cfar_f32"):
+        texts = [m for c, _, m in CASES if f"bare.{method}(" in c]
+        assert "input must be a torch.float32 tensor" in texts and len(set(texts)) >= 8, method
+        assert any("shape" in m for c, _, m in CASES if f"host.{method}(" in c), method
+
+
+def test_the_wrappers_surface():
+    from fpga_real_time_fft_analyzer_amd import chain, frames, reductions
+    cls = chain.SpectrumChain
+    assert list(inspect.signature(frames.cfar_of_rows).parameters) == ["points", "train", "guard", "mode", "what", "lo", "hi", "field"]
+    assert list(inspect.signature(cls.cfar).parameters) == ["self", "t", "train", "guard", "mode", "what", "lo", "hi", "field", "out"]
+    assert list(inspect.signature(cls.cfar_f32).parameters) == ["self", "x", "train", "guard", "mode", "what", "lo", "hi", "group", "scale",
+                                                                "work", "out"]
+    for fn in (frames.cfar_of_rows, cls.cfar, cls.cfar_f32):
+        sig = inspect.signature(fn).parameters
+        assert tuple(sig[n].default for n in ("train", "guard", "mode", "what", "lo", "hi")) == (16, 2, "ca", "ratio", 0, N)
+    assert inspect.signature(cls.cfar_f32).parameters["scale"].default == 1.0 / 2048.0
+    assert cls._cfar_args(np.int64(64), 64, "so", "floor", 0, 130, "power") == (2, 6, 2, 1)
+    assert cls.cfar is reductions.Reductions.cfar and "CFAR" in reductions.__doc__
