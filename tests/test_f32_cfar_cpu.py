@@ -1,6 +1,7 @@
 """The CFAR normalisation without a GPU: frames.cfar_of_rows against a brute-force restatement of include/specan_cfar.h, the
 header's known answers, the specials, the header against the binding table and the library's symbols, the argument check,
-the wrappers' refusals, cfar_alpha, and the use the feature is for: a threshold that follows a shaped noise floor.
+cfar_alpha, and the use the feature is for: a threshold that follows a shaped noise floor.  What it links and its resource
+remarks: tests/test_reduction_libraries_cpu.py; the refusals of the two wrappers: tests/test_reductions_wrappers_cpu.py.
 
 Every comparison with the mirror is bit for bit, on uint32 views."""
 import ctypes
@@ -14,40 +15,20 @@ import numpy as np
 import pytest
 
 from conftest import N
-from kernel_inventory import inventory, unit_text
-from native import CSRC, INCLUDE, compiles_as_c, declared, exported, needed, remarks, standalone_checks, undefined
+from kernel_inventory import inventory
+from native import INCLUDE, compiles_as_c, declared, exported, standalone_checks
+from reduction_libraries import BASE, FIELDS, SA_EINVAL, SA_ESHAPE, SA_OK, _shared, bits, built, records_of
 from test_f32_bands_cpu import wide_rows
 
-SA_OK, SA_EINVAL, SA_ESHAPE = 0, -1, -2
-BASE = (1 << 47) - (1 << 36)
 HEADER = os.path.join(INCLUDE, "specan_cfar.h")
 NAMES = ["sa_cfar_check", "sa_cfar_f32", "sa_cfar_last_error", "sa_cfar_version"]
 KERNELS = {f"cfar_f32_kernel<{f}>" for f in range(3)}
-FIELDS = (None, "peak", "power")
 MODES = ("ca", "go", "so")
 WHATS = ("ratio", "floor")
 QNAN, INF = 0x7FC00000, 0x7F800000
 # (train, guard, lo, hi): the ends of both parameters, the defaults, odd ranges near both ends of the row
 SETUPS = ((1, 0, 0, N), (64, 64, 0, N), (16, 2, 0, N), (4, 1, 1, N - 1), (8, 3, 37, 16001), (64, 64, 5, 135), (2, 0, 16381, N),
           (32, 7, 1023, 2051), (1, 64, 3, 16383), (64, 0, 0, 2))
-
-
-def _shared(a):
-    a.setflags(write=False)
-    return a
-
-
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-def records_of(pts, field):
-    """the rows as the input of layout `field`: the points themselves, or records whose other float is a NaN"""
-    if field is None:
-        return pts
-    rec = np.full(pts.shape + (2,), np.nan, np.float32)
-    rec[..., 0 if field == "peak" else 1] = pts
-    return rec
 
 
 def sampled_bins(T, G, lo, hi, extra=()):
@@ -306,11 +287,7 @@ def test_a_threshold_that_follows_the_floor_finds_what_a_row_wide_one_cannot():
 # ------------------------------------------------------------------------------------------------------------ the surface
 @pytest.fixture(scope="module")
 def cfar_lib():
-    """libspecan_cfar.so, built on demand by the package's one build step (it cross-compiles without a GPU)."""
-    from fpga_real_time_fft_analyzer_amd import abi
-    if not os.path.exists(abi.CFAR_LIB_PATH):
-        abi.build()
-    return abi.cfar_lib()
+    return built("cfar")
 
 
 GOOD = dict(rows=3, log2_train=4, guard=2, mode=0, what=0, lo=0, hi=N)
@@ -386,56 +363,10 @@ def test_header_compiles_as_c99_pedantic(tmp_path):
                   " + SA_CFAR_MODE_SO - 2; }\n")
 
 
-def test_library_links_hip_alone_and_reads_no_environment(cfar_lib):
-    from fpga_real_time_fft_analyzer_amd import abi
-    libs = needed(abi.CFAR_LIB_PATH)
-    for other in ("torch", "oracle", "specan_hip", "specan_fold", "specan_peaks", "specan_rank", "specan_hist", "specan_bands",
-                  "specan_mask", "specan_harm", "specan_signals"):
-        assert other not in libs, libs
-    assert "amdhip64" in libs
-    assert "getenv" not in undefined(abi.CFAR_LIB_PATH)
-    text = unit_text("cfar_f32.hip") + unit_text("sa_cfar_check.cpp")
-    assert "sa_cfar_f32" in text and "sa_cfar_check_call" in text
-    assert "getenv" not in text and "environ" not in text.replace("environment", "")
-    kernel = open(os.path.join(CSRC, "cfar_f32.hip")).read()
-    code = re.sub(r"//.*", "", kernel)
-    assert "atomic" not in code and "s_setreg" not in code and "denorm" not in code and "hipMemset" not in code
-    assert "#pragma clang fp contract(off)" in code
-    # one launch, written once for the three instantiations
-    assert len(re.findall(r"hipLaunchKernelGGL", code)) == 1 and "extern __shared__" not in code
-    # the units include nothing of the chains or of the other reductions
-    assert not re.search(r'#\s*include\s+"(?!sa_cfar\.hpp|\.\./\.\./include/specan_cfar\.h|specan\.h)', text), text[:200]
-    # the one check behind both entry points
-    assert len(re.findall(r"sa_cfar_check_call\(", unit_text("sa_cfar_check.cpp"))) >= 2
-    assert len(re.findall(r"sa_cfar_check_call\(", code)) == 1
-
-
 def test_kernel_inventory(cfar_lib):
     """libspecan_cfar.so holds the three instantiations, one per input layout, and nothing else."""
     from fpga_real_time_fft_analyzer_amd import abi
     assert inventory(abi.CFAR_LIB_PATH) == KERNELS
-
-
-def test_resource_remarks_show_no_scratch_and_no_spill():
-    """The compiler's figures for the three kernels, as `make resource-cfar-f32` prints them: no scratch, no SGPR or VGPR
-    spill, static LDS only and small enough for more than one workgroup on a CU (160 KiB).  VGPRs, occupancy and LDS are
-    printed; DESIGN.md section 4.24 records them."""
-    err = remarks("cfar_f32.hip")
-    assert len(re.findall(r"Function Name: \S*cfar_f32_kernel", err)) == 3
-    for what in ("ScratchSize \\[bytes/lane\\]", "SGPRs Spill", "VGPRs Spill"):
-        got = [int(v) for v in re.findall(what + r": (\d+)", err)]
-        assert got == [0] * 3, (what, got)
-    lds = [int(v) for v in re.findall(r"LDS Size \[bytes/block\]: (\d+)", err)]
-    assert len(lds) == 3 and all(0 < v <= 160 * 1024 // 2 for v in lds), lds
-    print("FIGURE VGPRs", re.findall(r" VGPRs: (\d+)", err), "occupancy", re.findall(r"Occupancy \[waves/SIMD\]: (\d+)", err), "LDS", lds)
-    assert "extern __shared__" not in unit_text("cfar_f32.hip")
-    make = open(os.path.join(CSRC, "Makefile")).read()
-    assert "resource-cfar-f32: UNITS = cfar_f32.hip" in make and re.search(r"^all:.*\$\(CFAR_OUT\)", make, re.M)
-    assert re.search(r"^CFAR_SRCS = cfar_f32\.hip sa_cfar_check\.cpp$", make, re.M) and re.search(r"^CFAR_OBJS = ", make, re.M)
-    assert re.search(r"^CFAR_OUT = \.\./libspecan_cfar\.so$", make, re.M)
-    assert re.search(r"^\$\(CFAR_OUT\): \$\(CFAR_OBJS\)\n\t\$\(HIPCC\) \$\(CXXFLAGS\) -shared \$\(CFAR_OBJS\) -o \$@$", make, re.M)
-    assert re.search(r"^UNITS = .*\$\(CFAR_SRCS\)", make, re.M) and re.search(r"^clean:\n\trm .*\$\(CFAR_OUT\)", make, re.M)
-    assert re.search(r"^RESOURCE = .*resource-cfar-f32", make, re.M) and "libspecan_cfar.so" in make.split("\n", 3)[1]
 
 
 # -------------------------------------------------------------------------------------------------------------- the check
@@ -502,79 +433,6 @@ def test_standalone_program_under_host_sanitizers(tmp_path):
 
 
 # ----------------------------------------------------------------------------------------------------------- the wrappers
-CASES = [
-    ('bare.cfar(None, train=True)', -1, 'train must be an int'),
-    ('bare.cfar(None, train=16.0)', -1, 'train must be an int'),
-    ('bare.cfar(None, guard=2.0)', -1, 'guard must be an int'),
-    ('bare.cfar(None, guard=False)', -1, 'guard must be an int'),
-    ('bare.cfar(None, lo=0.0)', -1, 'lo must be an int'),
-    ("bare.cfar(None, hi='5')", -1, 'hi must be an int'),
-    ('bare.cfar(None, train=3)', -1, 'train must be one of (1, 2, 4, 8, 16, 32, 64)'),
-    ('bare.cfar(None, train=0)', -1, 'train must be one of (1, 2, 4, 8, 16, 32, 64)'),
-    ('bare.cfar(None, train=128)', -1, 'train must be one of (1, 2, 4, 8, 16, 32, 64)'),
-    ('bare.cfar(None, guard=-1)', -1, 'guard must be 0..64'),
-    ('bare.cfar(None, guard=65)', -1, 'guard must be 0..64'),
-    ("bare.cfar(None, mode='os')", -1, "mode must be 'ca', 'go' or 'so'"),
-    ('bare.cfar(None, mode=0)', -1, "mode must be 'ca', 'go' or 'so'"),
-    ("bare.cfar(None, what='db')", -1, "what must be 'ratio' or 'floor'"),
-    ('bare.cfar(None, what=1)', -1, "what must be 'ratio' or 'floor'"),
-    ('bare.cfar(None, lo=5, hi=5)', -1, 'the range must be 0 <= lo < hi <= 16384'),
-    ('bare.cfar(None, hi=N + 1)', -1, 'the range must be 0 <= lo < hi <= 16384'),
-    ('bare.cfar(None, lo=10, hi=15)', -1, 'the range must hold 2 * guard + 2 bins or more'),
-    ('bare.cfar(None, guard=64, lo=0, hi=129)', -1, 'the range must hold 2 * guard + 2 bins or more'),
-    ("bare.cfar(None, field='mag')", -1, "field must be None, 'peak' or 'power'"),
-    ('bare.cfar(None, field=0)', -1, "field must be None, 'peak' or 'power'"),
-    ("bare.cfar(None, train=True, field='mag')", -1, 'train must be an int'),
-    ('bare.cfar(None)', -1, 'input must be a torch.float32 tensor'),
-    ("bare.cfar(None, 64, 64, 'so', 'floor', 0, 130, 'power')", -1, 'input must be a torch.float32 tensor'),
-    ("host.cfar(X, field='power')", -2, 'input must be a contiguous [B, 16384, 2] tensor'),
-    ('host.cfar(REC)', -2, 'input must be a contiguous [B, 16384] tensor'),
-    ('host.cfar(X, out=BAD)', -2, 'out must be a contiguous torch.float32 tensor of shape (2, 16384)'),
-    ('host.cfar(X, out=torch.zeros((2, N), dtype=torch.float64))', -2, 'out must be a contiguous torch.float32 tensor of shape (2, 16384)'),
-    ("host.cfar(REC, field='peak', out=torch.zeros((2, N, 2)))", -2, 'out must be a contiguous torch.float32 tensor of shape (2, 16384)'),
-    ('bare.cfar_f32(None, train=5)', -1, 'train must be one of (1, 2, 4, 8, 16, 32, 64)'),
-    ('bare.cfar_f32(None, train=5, group=3)', -1, 'train must be one of (1, 2, 4, 8, 16, 32, 64)'),
-    ('bare.cfar_f32(None, guard=1.5)', -1, 'guard must be an int'),
-    ('bare.cfar_f32(None, guard=100)', -1, 'guard must be 0..64'),
-    ("bare.cfar_f32(None, mode='CA')", -1, "mode must be 'ca', 'go' or 'so'"),
-    ("bare.cfar_f32(None, what='snr')", -1, "what must be 'ratio' or 'floor'"),
-    ('bare.cfar_f32(None, lo=5, hi=5)', -1, 'the range must be 0 <= lo < hi <= 16384'),
-    ('bare.cfar_f32(None, lo=0, hi=5)', -1, 'the range must hold 2 * guard + 2 bins or more'),
-    ('bare.cfar_f32(None, group=3)', -1, 'group must be one of (1, 2, 4, 8, 16, 32, 64, 128)'),
-    ('bare.cfar_f32(None, group=1)', -1, 'group = bucket = 1 folds nothing'),
-    ('bare.cfar_f32(None, group=2.0)', -1, 'group must be one of (1, 2, 4, 8, 16, 32, 64, 128)'),
-    ('bare.cfar_f32(None, group=128)', -1, 'input must be a torch.float32 tensor'),
-    ('bare.cfar_f32(None)', -1, 'input must be a torch.float32 tensor'),
-    ('host.cfar_f32(X, group=4)', -2, 'the batch (2 frames) must be a multiple of 4'),
-    ('host.cfar_f32(X, group=2, out=torch.zeros((2, N)))', -2, 'out must be a contiguous torch.float32 tensor of shape (1, 16384)'),
-    ('host.cfar_f32(X, out=BAD)', -2, 'out must be a contiguous torch.float32 tensor of shape (2, 16384)'),
-    ('host.cfar_f32(X, work=BAD)', -2, 'work must be a contiguous torch.float32 tensor of shape [2 or more, 16384]'),
-    ('host.cfar_f32(X, group=2, work=torch.zeros((1, N)))', -2, 'work must be a contiguous torch.float32 tensor of shape [2 or more, 16384]'),
-]
-
-
-def _namespace():
-    from test_reductions_wrappers_cpu import _namespace as objects
-    return objects()
-
-
-def test_every_refusal_of_the_wrappers_has_its_code_and_its_text():
-    """``bare`` is an object without a handle, a device or a library: nothing of it may be touched before the scalar
-    arguments and the input's type have passed.  ``host`` has the CPU as its device, so that the refusals behind the input's
-    check speak: the batch, the output and the workspace.  Every row ends in a refusal: nothing is loaded or launched."""
-    from fpga_real_time_fft_analyzer_amd.abi import SpecanError
-    ns = _namespace()
-    assert len({call for call, _, _ in CASES}) == len(CASES)
-    for call, code, message in CASES:
-        with pytest.raises(SpecanError) as e:
-            eval(call, ns)
-        assert (e.value.code, str(e.value)) == (code, f"specan error {code}: {message}"), call
-    for method in ("cfar", "cfar_f32"):
-        texts = [m for c, _, m in CASES if f"bare.{method}(" in c]
-        assert "input must be a torch.float32 tensor" in texts and len(set(texts)) >= 8, method
-        assert any("shape" in m for c, _, m in CASES if f"host.{method}(" in c), method
-
-
 def test_the_wrappers_surface():
     from fpga_real_time_fft_analyzer_amd import chain, frames, reductions
     cls = chain.SpectrumChain

@@ -1,7 +1,7 @@
 """CPU: the harmonic analysis (include/specan_harm.h: sa_harm_f32 of libspecan_harm.so) without a GPU -- the numpy mirror
 frames.harm_of_rows on planted spectra, by hand on the alias table, against frames.bands_of_rows and on edge rows;
 frames.harm_metrics; the header against the library's exports and the binding table; the argument check as a pure function
-and as a stand-alone program under the host sanitizers; the compiler's resource remarks of the kernel.
+and as a stand-alone program under the host sanitizers.  What it links and its resource remarks: tests/test_reduction_libraries_cpu.py.
 
 The rows made here are the data of tests/test_gpu_f32_harm.py too, which holds the device against the mirror bit for bit."""
 import ctypes
@@ -14,34 +14,18 @@ import numpy as np
 import pytest
 
 from conftest import N
-from kernel_inventory import inventory, unit_text
-from native import CSRC, INCLUDE, compiles_as_c, declared, exported, needed, remarks, standalone_checks, undefined
+from kernel_inventory import inventory
+from native import INCLUDE, compiles_as_c, declared, exported, standalone_checks
+from reduction_libraries import BASE, FIELDS, SA_EINVAL, SA_ESHAPE, SA_OK, _shared, bits, built, records_of
 from test_f32_bands_cpu import noise_rows, same_bits
 
-SA_OK, SA_EINVAL, SA_ESHAPE = 0, -1, -2
-BASE = (1 << 47) - (1 << 36)
 HEADER = os.path.join(INCLUDE, "specan_harm.h")
 NAMES = ["sa_harm_check", "sa_harm_f32", "sa_harm_last_error", "sa_harm_version"]
 KERNELS = {f"harm_f32_kernel<{f}>" for f in range(3)}
-FIELDS = (None, "peak", "power")
 HALF = N // 2
 PLANTED_AMPS = (1e-3, 3e-4, 1e-4, 5e-5)                          # harmonics 2..5 against a fundamental of 1
 SUMS = ("dist", "nad", "noise")
 WORDS = ("bin", "fund", "spur", "nonharm", "spur_bin", "nonharm_bin", "n_noise")
-
-
-def _shared(a):
-    a.setflags(write=False)                                       # computed once, shared by the tests of both files
-    return a
-
-
-def records_of(pts, field):
-    """``pts`` float32 [R, N] in the layout of ``field``: itself, or records whose other float is a NaN"""
-    if field is None:
-        return pts
-    rec = np.full(pts.shape + (2,), np.nan, np.float32)
-    rec[..., 0 if field == "peak" else 1] = pts
-    return rec
 
 
 def harm(pts, field=None, **kw):
@@ -323,11 +307,7 @@ def test_arguments_of_the_mirror():
 # ------------------------------------------------------------------------------------------------------------ the surface
 @pytest.fixture(scope="module")
 def harm_lib():
-    """libspecan_harm.so, built on demand by the package's one build step (it cross-compiles without a GPU)."""
-    from fpga_real_time_fft_analyzer_amd import abi
-    if not os.path.exists(abi.HARM_LIB_PATH):
-        abi.build()
-    return abi.harm_lib()
+    return built("harm")
 
 
 GOOD = dict(dc=4, top=8193, lo=4, hi=8193, fund=-1, span=3, order=5)
@@ -400,54 +380,10 @@ def test_header_compiles_as_c99_pedantic(tmp_path):
                   " + (int)sizeof(sa_harm_row); }\n")
 
 
-def test_library_links_hip_alone_and_reads_no_environment(harm_lib):
-    from fpga_real_time_fft_analyzer_amd import abi
-    libs = needed(abi.HARM_LIB_PATH)
-    for other in ("torch", "oracle", "specan_hip", "specan_fold", "specan_peaks", "specan_rank", "specan_hist", "specan_bands",
-                  "specan_mask"):
-        assert other not in libs, libs
-    assert "amdhip64" in libs
-    assert "getenv" not in undefined(abi.HARM_LIB_PATH)
-    text = unit_text("harm_f32.hip") + unit_text("sa_harm_check.cpp")
-    assert "sa_harm_f32" in text and "sa_harm_check_call" in text
-    assert "getenv" not in text and "environ" not in text.replace("environment", "")
-    kernel = open(os.path.join(CSRC, "harm_f32.hip")).read()
-    code = re.sub(r"//.*", "", kernel)
-    assert "atomic" not in code and "s_setreg" not in code and "denorm" not in code and "hipMemset" not in code
-    assert "#pragma clang fp contract(off)" in code
-    # one launch, written once for the three instantiations
-    assert len(re.findall(r"hipLaunchKernelGGL", code)) == 1 and "extern __shared__" not in code
-    # the units include nothing of the chains or of the other reductions
-    assert not re.search(r'#\s*include\s+"(?!sa_harm\.hpp|\.\./\.\./include/specan_harm\.h|specan\.h)', text), text[:200]
-    # the one check behind both entry points
-    assert len(re.findall(r"sa_harm_check_call\(", unit_text("sa_harm_check.cpp"))) >= 2
-    assert len(re.findall(r"sa_harm_check_call\(", code)) == 1
-
-
 def test_kernel_inventory(harm_lib):
     """libspecan_harm.so holds the three instantiations, one per input layout, and nothing else."""
     from fpga_real_time_fft_analyzer_amd import abi
     assert inventory(abi.HARM_LIB_PATH) == KERNELS
-
-
-def test_resource_remarks_show_no_scratch_and_no_spill():
-    """The compiler's figures for the three kernels, as `make resource-harm-f32` prints them: no scratch, no SGPR or VGPR
-    spill, static LDS only (below 2 KiB).  VGPRs, occupancy and LDS are printed; DESIGN.md section 4.22 records them."""
-    err = remarks("harm_f32.hip")
-    assert len(re.findall(r"Function Name: \S*harm_f32_kernel", err)) == 3
-    for what in ("ScratchSize \\[bytes/lane\\]", "SGPRs Spill", "VGPRs Spill"):
-        got = [int(v) for v in re.findall(what + r": (\d+)", err)]
-        assert got == [0] * 3, (what, got)
-    lds = [int(v) for v in re.findall(r"LDS Size \[bytes/block\]: (\d+)", err)]
-    assert len(lds) == 3 and all(0 < v <= 2048 for v in lds), lds
-    print("FIGURE VGPRs", re.findall(r" VGPRs: (\d+)", err), "occupancy", re.findall(r"Occupancy \[waves/SIMD\]: (\d+)", err), "LDS", lds)
-    assert "extern __shared__" not in unit_text("harm_f32.hip")
-    make = open(os.path.join(CSRC, "Makefile")).read()
-    assert "resource-harm-f32:" in make and re.search(r"^all:.*\$\(HARM_OUT\)", make, re.M)
-    assert re.search(r"^HARM_SRCS = harm_f32\.hip sa_harm_check\.cpp$", make, re.M) and re.search(r"^HARM_OBJS = ", make, re.M)
-    assert re.search(r"^HARM_OUT = \.\./libspecan_harm\.so$", make, re.M)
-    assert re.search(r"^UNITS = .*\$\(HARM_SRCS\)", make, re.M) and re.search(r"^clean:\n\trm .*\$\(HARM_OUT\)", make, re.M)
-    assert re.search(r"^RESOURCE = .*resource-harm-f32", make, re.M)
 
 
 # -------------------------------------------------------------------------------------------------------------- the check

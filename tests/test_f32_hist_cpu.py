@@ -3,7 +3,7 @@ persistence_f32) as far as no GPU is needed: the numpy mirror frames.hist_of_row
 worked out by hand below, never from the code under test; frames.level_edges_db by hand; the header against the built library
 and the binding table abi.HIST_SIGNATURES; the kernels the five libraries hold; the refusals through sa_hist_check with
 made-up addresses (every expected answer follows from the words of the header); the same arithmetic in a stand-alone program
-under the host sanitizers; and the compiler's resource remarks."""
+under the host sanitizers.  What it links and its resource remarks: tests/test_reduction_libraries_cpu.py."""
 import ctypes
 import itertools
 import os
@@ -13,24 +13,15 @@ import numpy as np
 import pytest
 
 from conftest import N
-from kernel_inventory import TABLE, inventory, unit_text
-from native import CSRC, INCLUDE, compiles_as_c, declared, exported, needed, remarks, standalone_checks, undefined
+from kernel_inventory import TABLE, inventory
+from native import INCLUDE, compiles_as_c, declared, exported, standalone_checks
+from reduction_libraries import BASE, SA_EINVAL, SA_ESHAPE, SA_OK, built, planted
 
-SA_OK, SA_EINVAL, SA_ESHAPE = 0, -1, -2
-BASE = (1 << 47) - (1 << 36)
 FAR = BASE + (1 << 40)
 HEADER = os.path.join(INCLUDE, "specan_hist.h")
 NAMES = ["sa_hist_check", "sa_hist_f32", "sa_hist_last_error", "sa_hist_version"]
 KERNELS = {f"hist_f32_kernel<{s}>" for s in range(1, 7)} | {"hist_zero_kernel"}
 ONE_DOWN, ONE, ONE_UP = 0x3F7FFFFF, 0x3F800000, 0x3F800001    # 1.0f and its two neighbours
-
-
-def planted(pairs, fill=0.0, rows=1):
-    """rows equal rows of `fill` with the (bin, value) pairs planted"""
-    r = np.full((rows, N), fill, np.float32)
-    for b, v in pairs:
-        r[:, b] = v
-    return r
 
 
 def hist(points, edges, **kw):
@@ -194,11 +185,7 @@ def test_level_edges_db_by_hand():
 # ------------------------------------------------------------------------------------------------------------ the surface
 @pytest.fixture(scope="module")
 def hist_lib():
-    """libspecan_hist.so, built on demand by the package's one build step (it cross-compiles without a GPU)."""
-    from fpga_real_time_fft_analyzer_amd import abi
-    if not os.path.exists(abi.HIST_LIB_PATH):
-        abi.build()
-    return abi.hist_lib()
+    return built("hist")
 
 
 def _edges(values):
@@ -245,23 +232,6 @@ def test_header_compiles_as_c99_pedantic(tmp_path):
                    " + (sa_hist_last_error()[0] != 0) + SA_HIST_LEVELS_MAX - 64 + (o[0] > 0u); }\n")
 
 
-def test_library_links_hip_alone_and_reads_no_environment(hist_lib):
-    from fpga_real_time_fft_analyzer_amd import abi
-    libs = needed(abi.HIST_LIB_PATH)
-    for other in ("torch", "oracle", "specan_hip", "specan_fold", "specan_peaks", "specan_rank"):
-        assert other not in libs, libs
-    assert "amdhip64" in libs
-    assert "getenv" not in undefined(abi.HIST_LIB_PATH)
-    text = unit_text("hist_f32.hip") + unit_text("sa_hist_check.cpp")
-    assert "sa_hist_f32" in text and "sa_hist_check_call" in text
-    assert "getenv" not in text and "environ" not in text.replace("environment", "")
-    kernel = open(os.path.join(CSRC, "hist_f32.hip")).read()
-    assert "atomicAdd(" not in kernel and kernel.count("__hip_atomic_fetch_add(") == 2          # one LDS add, one merge: unsigned
-    assert "s_setreg" not in kernel and "denorm" not in kernel and "hipMalloc" not in kernel and "hipMemset" not in kernel
-    # the units include nothing of the chains, of the fold, of the peak table or of the rank library
-    assert not re.search(r'#\s*include\s+"(?!sa_hist\.hpp|\.\./\.\./include/specan_hist\.h|specan\.h)', text), text[:200]
-
-
 def test_kernel_inventories(hist_lib):
     """libspecan_hist.so holds the six instantiations of the count, one per depth of the edge tree, and the kernel that zeroes
     the output of the sliced form, and nothing else; the other four libraries hold what they held."""
@@ -276,26 +246,6 @@ def test_kernel_inventories(hist_lib):
     assert inventory(abi.RANK_LIB_PATH) == {f"rank_f32_kernel<{f}>" for f in range(3)}
     design = open(os.path.join(os.path.dirname(INCLUDE), "DESIGN.md")).read()
     assert "hist_f32_kernel<STEPS>" in design and "hist_zero_kernel" in design
-
-
-def test_resource_remarks_show_no_scratch_and_no_spill():
-    """The compiler's figures for the seven kernels, as `make resource-hist-f32` prints them: no scratch, no SGPR or VGPR
-    spill; the count holds 66048 bytes of static LDS (64 levels of 257 counters and the 64 words of the edge tree) at 64 VGPRs
-    or fewer, occupancy 8: two workgroups of 16 waves on a compute unit."""
-    err = remarks("hist_f32.hip")
-    assert len(re.findall(r"Function Name: \S*hist_f32_kernel", err)) == 6 and len(re.findall(r"Function Name: \S*hist_zero_kernel", err)) == 1
-    for what, want in (("ScratchSize \\[bytes/lane\\]", [0] * 7), ("SGPRs Spill", [0] * 7), ("VGPRs Spill", [0] * 7),
-                       ("LDS Size \\[bytes/block\\]", [0] + [66048] * 6), ("Occupancy \\[waves/SIMD\\]", [8] * 7)):
-        got = sorted(int(v) for v in re.findall(what + r": (\d+)", err))
-        assert got == want, (what, got)
-    vgprs = [int(v) for v in re.findall(r" VGPRs: (\d+)", err)]
-    print("FIGURE VGPRs", vgprs)
-    assert max(vgprs) <= 64
-    assert "extern __shared__" not in unit_text("hist_f32.hip")
-    make = open(os.path.join(CSRC, "Makefile")).read()
-    assert "resource-hist-f32:" in make and re.search(r"^all:.*\$\(HIST_OUT\)", make, re.M)
-    assert re.search(r"^HIST_SRCS = hist_f32\.hip sa_hist_check\.cpp$", make, re.M) and re.search(r"^HIST_OBJS = ", make, re.M)
-    assert re.search(r"^UNITS = .*\$\(HIST_SRCS\)", make, re.M) and re.search(r"^clean:\n\trm .*\$\(HIST_OUT\)", make, re.M)
 
 
 # -------------------------------------------------------------------------------------------------------------- the check

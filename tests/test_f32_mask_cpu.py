@@ -4,7 +4,8 @@ header in fractions.Fraction, never the code under test; the rows on which a flo
 exact ratio, checked to be such rows; frames.limit_line, mask_from_trace and mask_margin_db; the header against the built
 library and the binding table abi.MASK_SIGNATURES; the kernels the library holds; the refusals through sa_mask_check with
 made-up addresses (every expected answer follows from the words of the header); the same arithmetic in a stand-alone program
-under the host sanitizers; and the compiler's resource remarks.  The rows and limits the GPU file reuses are made here."""
+under the host sanitizers (what it links and its resource remarks: tests/test_reduction_libraries_cpu.py).  The rows and
+limits the GPU file reuses are made here."""
 import ctypes
 import functools
 import itertools
@@ -17,36 +18,20 @@ import numpy as np
 import pytest
 
 from conftest import N
-from kernel_inventory import inventory, unit_text
-from native import CSRC, INCLUDE, compiles_as_c, declared, exported, needed, remarks, standalone_checks, undefined
+from kernel_inventory import inventory
+from native import INCLUDE, compiles_as_c, declared, exported, standalone_checks
+from reduction_libraries import BASE, FIELDS, SA_EINVAL, SA_ESHAPE, SA_OK, _shared, built, records_of
 
-SA_OK, SA_EINVAL, SA_ESHAPE = 0, -1, -2
-BASE = (1 << 47) - (1 << 36)
 HEADER = os.path.join(INCLUDE, "specan_mask.h")
 NAMES = ["sa_mask_check", "sa_mask_f32", "sa_mask_last_error", "sa_mask_version"]
 KERNELS = {f"mask_f32_kernel<{f}, {u}, {l}>" for f in range(3) for u, l in (("true", "true"), ("true", "false"), ("false", "true"))} \
     | {"mask_summary_kernel"}
-FIELDS = (None, "peak", "power")
 # every boundary the kernel has: a thread's four bins, a wave's 256, a round's 1024, the row
 EDGES = (0, 1, 3, 4, 5, 255, 256, 257, 1023, 1024, 1025, 16383, 16384)
 GAPS = (0.0, -1.0, np.inf, np.nan, -np.inf, -0.0)                  # every one of them means "no limit here"
 
 
 # ---------------------------------------------------------------------------------------------------------- the test data
-def _shared(a):
-    a.setflags(write=False)                                       # computed once, shared by the tests of both files
-    return a
-
-
-def records_of(pts, field):
-    """``pts`` float32 [R, N] in the layout of ``field``: itself, or records whose other float is a NaN"""
-    if field is None:
-        return pts
-    rec = np.full(pts.shape + (2,), np.nan, np.float32)
-    rec[..., 0 if field == "peak" else 1] = pts
-    return rec
-
-
 @functools.lru_cache(maxsize=None)
 def planted():
     """The bins b - 2 .. b + 1 of every boundary b of EDGES that lie in the row."""
@@ -392,11 +377,7 @@ def test_mask_from_trace_and_margin():
 # ------------------------------------------------------------------------------------------------------------ the surface
 @pytest.fixture(scope="module")
 def mask_lib():
-    """libspecan_mask.so, built on demand by the package's one build step (it cross-compiles without a GPU)."""
-    from fpga_real_time_fft_analyzer_amd import abi
-    if not os.path.exists(abi.MASK_LIB_PATH):
-        abi.build()
-    return abi.mask_lib()
+    return built("mask")
 
 
 FAR = {"in": BASE, "upper": BASE + (1 << 40), "lower": BASE + (2 << 40), "rows_out": BASE + (3 << 40), "summary": BASE + (4 << 40)}
@@ -455,51 +436,11 @@ def test_header_compiles_as_c99_pedantic(tmp_path):
                   " + (o[0].lo_val < o[0].lo_lim) + (int)sizeof(sa_mask_row); }\n")
 
 
-def test_library_links_hip_alone_and_reads_no_environment(mask_lib):
-    from fpga_real_time_fft_analyzer_amd import abi
-    libs = needed(abi.MASK_LIB_PATH)
-    for other in ("torch", "oracle", "specan_hip", "specan_fold", "specan_peaks", "specan_rank", "specan_hist", "specan_bands"):
-        assert other not in libs, libs
-    assert "amdhip64" in libs
-    assert "getenv" not in undefined(abi.MASK_LIB_PATH)
-    text = unit_text("mask_f32.hip") + unit_text("sa_mask_check.cpp")
-    assert "sa_mask_f32" in text and "sa_mask_check_call" in text
-    assert "getenv" not in text and "environ" not in text.replace("environment", "")
-    kernel = open(os.path.join(CSRC, "mask_f32.hip")).read()
-    code = re.sub(r"//.*", "", kernel)
-    assert "atomic" not in code and "s_setreg" not in code and "denorm" not in code and "hipMemset" not in code
-    # the row launch, written once for the nine instantiations, and the summary launch
-    assert len(re.findall(r"hipLaunchKernelGGL", code)) == 2 and "extern __shared__" not in code
-    # the units include nothing of the chains or of the other reductions
-    assert not re.search(r'#\s*include\s+"(?!sa_mask\.hpp|\.\./\.\./include/specan_mask\.h|specan\.h)', text), text[:200]
-
-
 def test_kernel_inventory(mask_lib):
     """libspecan_mask.so holds the nine instantiations -- one per input layout and set of limits present -- and the summary
     kernel, and nothing else."""
     from fpga_real_time_fft_analyzer_amd import abi
     assert inventory(abi.MASK_LIB_PATH) == KERNELS
-
-
-def test_resource_remarks_show_no_scratch_and_no_spill():
-    """The compiler's figures for the ten kernels, as `make resource-mask-f32` prints them: no scratch, no SGPR or VGPR spill,
-    static LDS only (a few hundred bytes).  VGPRs, occupancy and LDS are printed; DESIGN.md section 4.21 records them."""
-    err = remarks("mask_f32.hip")
-    assert len(re.findall(r"Function Name: \S*mask_f32_kernel", err)) == 9
-    assert len(re.findall(r"Function Name: \S*mask_summary_kernel", err)) == 1
-    for what in ("ScratchSize \\[bytes/lane\\]", "SGPRs Spill", "VGPRs Spill"):
-        got = [int(v) for v in re.findall(what + r": (\d+)", err)]
-        assert got == [0] * 10, (what, got)
-    lds = [int(v) for v in re.findall(r"LDS Size \[bytes/block\]: (\d+)", err)]
-    assert len(lds) == 10 and all(0 < v <= 1024 for v in lds), lds
-    print("FIGURE VGPRs", re.findall(r" VGPRs: (\d+)", err), "occupancy", re.findall(r"Occupancy \[waves/SIMD\]: (\d+)", err), "LDS", lds)
-    assert "extern __shared__" not in unit_text("mask_f32.hip")
-    make = open(os.path.join(CSRC, "Makefile")).read()
-    assert "resource-mask-f32:" in make and re.search(r"^all:.*\$\(MASK_OUT\)", make, re.M)
-    assert re.search(r"^MASK_SRCS = mask_f32\.hip sa_mask_check\.cpp$", make, re.M) and re.search(r"^MASK_OBJS = ", make, re.M)
-    assert re.search(r"^MASK_OUT = \.\./libspecan_mask\.so$", make, re.M)
-    assert re.search(r"^UNITS = .*\$\(MASK_SRCS\)", make, re.M) and re.search(r"^clean:\n\trm .*\$\(MASK_OUT\)", make, re.M)
-    assert re.search(r"^RESOURCE = .*resource-mask-f32", make, re.M)
 
 
 # -------------------------------------------------------------------------------------------------------------- the check

@@ -3,35 +3,24 @@ peak_table_f32) as far as no GPU is needed: the numpy mirror frames.peaks_of_row
 worked out by hand below, never from the code under test; the header against the built library and the binding table
 abi.PEAKS_SIGNATURES; the kernels the three libraries hold; the refusals through sa_peaks_check with made-up addresses
 (every expected answer follows from the words of the header); the same arithmetic in a stand-alone program under the host
-sanitizers; and the compiler's resource remarks."""
+sanitizers.  What it links and its resource remarks: tests/test_reduction_libraries_cpu.py."""
 import ctypes
 import itertools
 import os
-import re
 
 import numpy as np
 import pytest
 
 from conftest import N
-from kernel_inventory import TABLE, inventory, unit_text
-from native import CSRC, INCLUDE, compiles_as_c, declared, exported, needed, remarks, standalone_checks, undefined
+from kernel_inventory import TABLE, inventory
+from native import INCLUDE, compiles_as_c, declared, exported, standalone_checks
+from reduction_libraries import BASE, SA_EINVAL, SA_ESHAPE, SA_OK, bits, built, key
 
-SA_OK, SA_EINVAL, SA_ESHAPE = 0, -1, -2
-BASE = (1 << 47) - (1 << 36)
 FAR = BASE + (1 << 40)
 FAR2 = BASE + (1 << 41)
 HEADER = os.path.join(INCLUDE, "specan_peaks.h")
 NAMES = ["sa_peaks_check", "sa_peaks_f32", "sa_peaks_last_error", "sa_peaks_version"]
 NAN_KEY = 0x7FC00000
-
-
-def bits(x):
-    return np.ascontiguousarray(x, np.float32).view(np.uint32)
-
-
-def key(v):
-    """the key of one value: its float32 bits with the sign cleared"""
-    return int(bits(np.float32(v)).ravel()[0]) & 0x7FFFFFFF
 
 
 def row_of(pairs):
@@ -226,11 +215,7 @@ def test_rows_are_independent_and_arguments_are_checked():
 # ------------------------------------------------------------------------------------------------------------ the surface
 @pytest.fixture(scope="module")
 def peaks_lib():
-    """libspecan_peaks.so, built on demand by the package's one build step (it cross-compiles without a GPU)."""
-    from fpga_real_time_fft_analyzer_amd import abi
-    if not os.path.exists(abi.PEAKS_LIB_PATH):
-        abi.build()
-    return abi.peaks_lib()
+    return built("peaks")
 
 
 @pytest.fixture(scope="module")
@@ -271,22 +256,6 @@ def test_header_compiles_as_c99_pedantic(tmp_path):
                    " + SA_PEAKS_IN_POINT_PEAK - 1 + (o->bin < 0) + (o->mag > 0.0f); }\n")
 
 
-def test_library_links_hip_alone_and_reads_no_environment(peaks_lib):
-    from fpga_real_time_fft_analyzer_amd import abi
-    libs = needed(abi.PEAKS_LIB_PATH)
-    for other in ("torch", "oracle", "specan_hip", "specan_fold"):
-        assert other not in libs, libs
-    assert "amdhip64" in libs
-    assert "getenv" not in undefined(abi.PEAKS_LIB_PATH)
-    text = unit_text("peaks_f32.hip") + unit_text("sa_peaks_check.cpp")
-    assert "sa_peaks_f32" in text and "sa_peaks_check_call" in text
-    assert "getenv" not in text and "environ" not in text.replace("environment", "")
-    kernel = open(os.path.join(CSRC, "peaks_f32.hip")).read()
-    assert "atomic" not in kernel.replace("No atomics", "") and "s_setreg" not in kernel and "denorm" not in kernel
-    # the units include nothing of the chains or of the fold
-    assert not re.search(r'#\s*include\s+"(?!sa_peaks\.hpp|\.\./\.\./include/specan_peaks\.h|specan\.h)', text), text[:200]
-
-
 def test_kernel_inventories(peaks_lib):
     """libspecan_peaks.so holds the three instantiations, one per input layout, and nothing else; the other two libraries hold
     what they held."""
@@ -297,20 +266,6 @@ def test_kernel_inventories(peaks_lib):
             abi.build()
     assert inventory(abi.LIB_PATH) == set(TABLE)
     assert inventory(abi.FOLD_LIB_PATH) == {f"fold_mag_f32_kernel<{k}>" for k in range(7)}
-
-
-def test_resource_remarks_show_no_scratch_and_no_spill():
-    """The compiler's figures for the three kernels, as `make resource-peaks-f32` prints them: no scratch, no SGPR or VGPR
-    spill, the 80 bytes of LDS of the four wave slots (two buffers) and the four counts, static -- no dynamic LDS."""
-    err = remarks("peaks_f32.hip")
-    assert len(re.findall(r"Function Name: \S*peaks_f32_kernel", err)) == 3
-    for what, want in (("ScratchSize \\[bytes/lane\\]", 0), ("SGPRs Spill", 0), ("VGPRs Spill", 0), ("LDS Size \\[bytes/block\\]", 80)):
-        got = [int(v) for v in re.findall(what + r": (\d+)", err)]
-        assert got == [want] * 3, (what, got)
-    print("FIGURE VGPRs", re.findall(r" VGPRs: (\d+)", err), "occupancy", re.findall(r"Occupancy \[waves/SIMD\]: (\d+)", err))
-    assert "extern __shared__" not in unit_text("peaks_f32.hip")
-    make = open(os.path.join(CSRC, "Makefile")).read()
-    assert "resource-peaks-f32:" in make and re.search(r"^all:.*\$\(PEAKS_OUT\)", make, re.M)
 
 
 # -------------------------------------------------------------------------------------------------------------- the check

@@ -3,21 +3,19 @@ noise_floor_f32) as far as no GPU is needed: the numpy mirror frames.ranks_of_ro
 worked out by hand below, never from the code under test; frames.rank_of_quantile by hand; the header against the built
 library and the binding table abi.RANK_SIGNATURES; the kernels the four libraries hold; the refusals through sa_rank_check
 with made-up addresses (every expected answer follows from the words of the header); the same arithmetic in a stand-alone
-program under the host sanitizers; and the compiler's resource remarks."""
+program under the host sanitizers.  What it links and its resource remarks: tests/test_reduction_libraries_cpu.py."""
 import ctypes
 import itertools
 import os
-import re
 
 import numpy as np
 import pytest
 
 from conftest import N
-from kernel_inventory import TABLE, inventory, unit_text
-from native import CSRC, INCLUDE, compiles_as_c, declared, exported, needed, remarks, standalone_checks, undefined
+from kernel_inventory import TABLE, inventory
+from native import INCLUDE, compiles_as_c, declared, exported, standalone_checks
+from reduction_libraries import BASE, SA_EINVAL, SA_ESHAPE, SA_OK, bits, built, key, planted
 
-SA_OK, SA_EINVAL, SA_ESHAPE = 0, -1, -2
-BASE = (1 << 47) - (1 << 36)
 FAR = BASE + (1 << 40)
 HEADER = os.path.join(INCLUDE, "specan_rank.h")
 NAMES = ["sa_rank_check", "sa_rank_f32", "sa_rank_last_error", "sa_rank_version"]
@@ -26,23 +24,6 @@ ONE, ONE_UP = 0x3F800000, 0x3F800001                   # 1.0f and the next float
 # zeros (-0.0 is one of them), the denormal 2^-149 = 1e-45f (bits 1), 2.0, |-3.0|, +inf, the NaN
 SPECIALS = ((11, np.nan), (222, np.inf), (3333, -3.0), (4444, 2.0), (5555, 1e-45), (6666, -0.0))
 SPECIALS_TOP6 = [0x0, 0x1, 0x40000000, 0x40400000, 0x7F800000, 0x7FC00000]
-
-
-def bits(x):
-    return np.ascontiguousarray(x, np.float32).view(np.uint32)
-
-
-def key(v):
-    """the key of one value: its float32 bits with the sign cleared"""
-    return int(bits(np.float32(v)).ravel()[0]) & 0x7FFFFFFF
-
-
-def planted(pairs, fill=0.0, rows=1):
-    """rows equal rows of `fill` with the (bin, value) pairs planted"""
-    r = np.full((rows, N), fill, np.float32)
-    for b, v in pairs:
-        r[:, b] = v
-    return r
 
 
 def stats(points, ranks, **kw):
@@ -191,11 +172,7 @@ def test_rank_of_quantile_by_hand():
 # ------------------------------------------------------------------------------------------------------------ the surface
 @pytest.fixture(scope="module")
 def rank_lib():
-    """libspecan_rank.so, built on demand by the package's one build step (it cross-compiles without a GPU)."""
-    from fpga_real_time_fft_analyzer_amd import abi
-    if not os.path.exists(abi.RANK_LIB_PATH):
-        abi.build()
-    return abi.rank_lib()
+    return built("rank")
 
 
 def _ranks(values):
@@ -244,22 +221,6 @@ def test_header_compiles_as_c99_pedantic(tmp_path):
                    " + (sa_rank_last_error()[0] != 0) + SA_RANK_Q_MAX - 8 + SA_RANK_IN_POINT_PEAK - 1 + (o[0] > 0.0f); }\n")
 
 
-def test_library_links_hip_alone_and_reads_no_environment(rank_lib):
-    from fpga_real_time_fft_analyzer_amd import abi
-    libs = needed(abi.RANK_LIB_PATH)
-    for other in ("torch", "oracle", "specan_hip", "specan_fold", "specan_peaks"):
-        assert other not in libs, libs
-    assert "amdhip64" in libs
-    assert "getenv" not in undefined(abi.RANK_LIB_PATH)
-    text = unit_text("rank_f32.hip") + unit_text("sa_rank_check.cpp")
-    assert "sa_rank_f32" in text and "sa_rank_check_call" in text
-    assert "getenv" not in text and "environ" not in text.replace("environment", "")
-    kernel = open(os.path.join(CSRC, "rank_f32.hip")).read()
-    assert "atomic" not in kernel and "s_setreg" not in kernel and "denorm" not in kernel
-    # the units include nothing of the chains, of the fold or of the peak table
-    assert not re.search(r'#\s*include\s+"(?!sa_rank\.hpp|\.\./\.\./include/specan_rank\.h|specan\.h)', text), text[:200]
-
-
 def test_kernel_inventories(rank_lib):
     """libspecan_rank.so holds the three instantiations, one per input layout, and nothing else; the other three libraries
     hold what they held."""
@@ -271,21 +232,6 @@ def test_kernel_inventories(rank_lib):
     assert inventory(abi.LIB_PATH) == set(TABLE)
     assert inventory(abi.FOLD_LIB_PATH) == {f"fold_mag_f32_kernel<{k}>" for k in range(7)}
     assert inventory(abi.PEAKS_LIB_PATH) == {f"peaks_f32_kernel<{f}>" for f in range(3)}
-
-
-def test_resource_remarks_show_no_scratch_and_no_spill():
-    """The compiler's figures for the three kernels, as `make resource-rank-f32` prints them: no scratch, no SGPR or VGPR
-    spill, the 256 bytes of LDS of the count words (two buffers of eight ranks by four waves), static -- no dynamic LDS."""
-    err = remarks("rank_f32.hip")
-    assert len(re.findall(r"Function Name: \S*rank_f32_kernel", err)) == 3
-    for what, want in (("ScratchSize \\[bytes/lane\\]", 0), ("SGPRs Spill", 0), ("VGPRs Spill", 0), ("LDS Size \\[bytes/block\\]", 256)):
-        got = [int(v) for v in re.findall(what + r": (\d+)", err)]
-        assert got == [want] * 3, (what, got)
-    print("FIGURE VGPRs", re.findall(r" VGPRs: (\d+)", err), "occupancy", re.findall(r"Occupancy \[waves/SIMD\]: (\d+)", err))
-    assert "extern __shared__" not in unit_text("rank_f32.hip")
-    make = open(os.path.join(CSRC, "Makefile")).read()
-    assert "resource-rank-f32:" in make and re.search(r"^all:.*\$\(RANK_OUT\)", make, re.M)
-    assert re.search(r"^UNITS = .*\$\(RANK_SRCS\)", make, re.M) and re.search(r"^clean:\n\trm .*\$\(RANK_OUT\)", make, re.M)
 
 
 # -------------------------------------------------------------------------------------------------------------- the check

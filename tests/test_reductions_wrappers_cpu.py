@@ -1,6 +1,6 @@
 """CPU: the refusals of the reduction wrappers (reductions.py: fold_mag_f32, spectra_f32, find_peaks, peak_table_f32, order_stats,
 noise_floor_f32, level_hist, persistence_f32, band_power, channel_power_f32, mask_test, mask_trigger_f32, harmonics,
-harmonics_f32) as far as no device is needed, each pinned to its code and its full text, and the names the other tests and the
+harmonics_f32, find_signals, signals_f32, cfar, cfar_f32) as far as no device is needed, each pinned to its code and its full text, and the names the other tests and the
 tools reach the tables and the libraries by.
 
 Two objects stand in for a handle.  ``bare`` is ``object.__new__(SpectrumChain)``: nothing of it may be touched before the
@@ -9,7 +9,7 @@ host memory pass the input's check and the refusals behind it speak: the shapes,
 workspace.  Every case ends in a refusal, so no library is loaded and nothing is launched.
 
 The expected texts are those of the wrappers as they were before they shared one skeleton: the table was run against that
-version and its output committed.  A row is (call, code, message); ``LIM`` is an object no check may look at, ``X``, ``REC`` and
+version and its output committed; the rows of the last four methods came with their libraries.  A row is (call, code, message); ``LIM`` is an object no check may look at, ``X``, ``REC`` and
 ``V`` good inputs ([2,16384], [2,16384,2] and [16384] float32) and ``BAD`` a tensor that is right for nothing.
 """
 import numpy as np
@@ -235,11 +235,133 @@ CASES = [
     ('host.channel_power_f32(X, [(0, 5)], (0.5,), work=BAD)', -2, 'work must be a contiguous torch.float32 tensor of shape [2 or more, 16384]'),
     ('host.mask_trigger_f32(X, V, work=BAD)', -2, 'work must be a contiguous torch.float32 tensor of shape [2 or more, 16384]'),
     ('host.harmonics_f32(X, group=2, work=BAD)', -2, 'work must be a contiguous torch.float32 tensor of shape [2 or more, 16384]'),
+    ('bare.find_signals(None, k=True)', -1, 'k must be an int'),
+    ('bare.find_signals(None, lo=0.0)', -1, 'lo must be an int'),
+    ("bare.find_signals(None, hi='5')", -1, 'hi must be an int'),
+    ('bare.find_signals(None, gap=2.0)', -1, 'gap must be an int'),
+    ('bare.find_signals(None, min_width=False)', -1, 'min_width must be an int'),
+    ('bare.find_signals(None, k=0)', -1, 'k must be 1..32'),
+    ('bare.find_signals(None, k=33)', -1, 'k must be 1..32'),
+    ('bare.find_signals(None, lo=5, hi=5)', -1, 'the range must be 0 <= lo < hi <= 16384'),
+    ('bare.find_signals(None, hi=N + 1)', -1, 'the range must be 0 <= lo < hi <= 16384'),
+    ('bare.find_signals(None, gap=-1)', -1, 'gap must be 0..16383'),
+    ('bare.find_signals(None, gap=N)', -1, 'gap must be 0..16383'),
+    ('bare.find_signals(None, min_width=0)', -1, 'min_width must be 1..16384'),
+    ('bare.find_signals(None, min_width=N + 1)', -1, 'min_width must be 1..16384'),
+    ("bare.find_signals(None, field='mag')", -1, "field must be None, 'peak' or 'power'"),
+    ('bare.find_signals(None, field=0)', -1, "field must be None, 'peak' or 'power'"),
+    ("bare.find_signals(None, k=0, field='mag')", -1, 'k must be 1..32'),
+    ("bare.find_signals(None, threshold='1')", -1, 'threshold must be a number'),
+    ('bare.find_signals(None, threshold=True)', -1, 'threshold must be a number'),
+    ('bare.find_signals(None, threshold=None)', -1, 'threshold must be a number'),
+    ('bare.find_signals(None, threshold=-1.0)', -1, 'threshold must be +0.0 .. +inf: no NaN, no sign bit'),
+    ("bare.find_signals(None, threshold=float('nan'))", -1, 'threshold must be +0.0 .. +inf: no NaN, no sign bit'),
+    ('bare.find_signals(None, threshold=torch.zeros(2, dtype=torch.float64))', -1, 'a threshold per row must be a torch.float32 tensor'),
+    ('bare.find_signals(None, threshold=torch.zeros(2, dtype=torch.int32))', -1, 'a threshold per row must be a torch.float32 tensor'),
+    ('bare.find_signals(None)', -1, 'input must be a torch.float32 tensor'),
+    ("bare.find_signals(None, threshold=torch.zeros(2), field='peak')", -1, 'input must be a torch.float32 tensor'),
+    ("host.find_signals(X, field='power')", -2, 'input must be a contiguous [B, 16384, 2] tensor'),
+    ('host.find_signals(REC)', -2, 'input must be a contiguous [B, 16384] tensor'),
+    ('host.find_signals(X, threshold=torch.zeros(3))', -2, 'a threshold per row must be a contiguous torch.float32 tensor of shape (2,)'),
+    ('host.find_signals(X, threshold=torch.zeros((2, 1)))', -2, 'a threshold per row must be a contiguous torch.float32 tensor of shape (2,)'),
+    ('host.find_signals(X, threshold=torch.zeros(4)[::2])', -2, 'a threshold per row must be a contiguous torch.float32 tensor of shape (2,)'),
+    ('host.find_signals(X, threshold=torch.zeros(3), out=BAD)', -2, 'a threshold per row must be a contiguous torch.float32 tensor of shape (2,)'),
+    ('host.find_signals(X, k=4, out=BAD)', -2, 'out must be a contiguous torch.int32 tensor of shape (2, 4, 6)'),
+    ("host.find_signals(REC, field='peak', out=torch.zeros((2, 16, 6)))", -2, 'out must be a contiguous torch.int32 tensor of shape (2, 16, 6)'),
+    ('host.find_signals(X, k=4, out=BAD, stats=BAD)', -2, 'out must be a contiguous torch.int32 tensor of shape (2, 4, 6)'),
+    ('host.find_signals(X, k=4, stats=BAD)', -2, 'stats must be a contiguous torch.int32 tensor of shape (2, 3)'),
+    ('host.find_signals(X, k=4, out=torch.zeros((2, 4, 6), dtype=torch.int32), stats=torch.zeros((2, 3)))', -2, 'stats must be a contiguous torch.int32 tensor of shape (2, 3)'),
+    ('bare.signals_f32(None)', -1, 'exactly one of threshold and factor must be given'),
+    ('bare.signals_f32(None, threshold=1.0, factor=6.0)', -1, 'exactly one of threshold and factor must be given'),
+    ('bare.signals_f32(None, threshold=torch.zeros(2), factor=6)', -1, 'exactly one of threshold and factor must be given'),
+    ('bare.signals_f32(None, k=0)', -1, 'k must be 1..32'),
+    ('bare.signals_f32(None, k=0, threshold=1.0, factor=6.0, group=3)', -1, 'k must be 1..32'),
+    ('bare.signals_f32(None, factor=6.0, gap=N)', -1, 'gap must be 0..16383'),
+    ('bare.signals_f32(None, threshold=1.0, min_width=2.0)', -1, 'min_width must be an int'),
+    ('bare.signals_f32(None, threshold=1.0, lo=5, hi=5)', -1, 'the range must be 0 <= lo < hi <= 16384'),
+    ('bare.signals_f32(None, threshold=-1.0)', -1, 'threshold must be +0.0 .. +inf: no NaN, no sign bit'),
+    ("bare.signals_f32(None, threshold='1')", -1, 'threshold must be a number'),
+    ('bare.signals_f32(None, threshold=torch.zeros(2, dtype=torch.float64))', -1, 'a threshold per row must be a torch.float32 tensor'),
+    ('bare.signals_f32(None, factor=0.0)', -1, 'factor must be a finite number above 0 as a float32'),
+    ('bare.signals_f32(None, factor=-6.0)', -1, 'factor must be a finite number above 0 as a float32'),
+    ("bare.signals_f32(None, factor=float('inf'))", -1, 'factor must be a finite number above 0 as a float32'),
+    ("bare.signals_f32(None, factor=float('nan'))", -1, 'factor must be a finite number above 0 as a float32'),
+    ('bare.signals_f32(None, factor=1e-50)', -1, 'factor must be a finite number above 0 as a float32'),
+    ('bare.signals_f32(None, factor=1e39)', -1, 'factor must be a finite number above 0 as a float32'),
+    ('bare.signals_f32(None, factor=True)', -1, 'factor must be a finite number above 0 as a float32'),
+    ("bare.signals_f32(None, factor='6')", -1, 'factor must be a finite number above 0 as a float32'),
+    ('bare.signals_f32(None, factor=6.0, q=1.5)', -1, 'q must be a number in 0..1'),
+    ('bare.signals_f32(None, factor=6.0, q=[0.5])', -1, 'q must be a number in 0..1'),
+    ('bare.signals_f32(None, factor=6.0, q=True)', -1, 'q must be a number in 0..1'),
+    ('bare.signals_f32(None, factor=6.0, q=1.5, group=3)', -1, 'q must be a number in 0..1'),
+    ('bare.signals_f32(None, factor=6.0, group=3)', -1, 'group must be one of (1, 2, 4, 8, 16, 32, 64, 128)'),
+    ('bare.signals_f32(None, threshold=1.0, group=1)', -1, 'group = bucket = 1 folds nothing'),
+    ('bare.signals_f32(None, threshold=1.0, group=2.0)', -1, 'group must be one of (1, 2, 4, 8, 16, 32, 64, 128)'),
+    ('bare.signals_f32(None, factor=6.0, group=128)', -1, 'input must be a torch.float32 tensor'),
+    ('bare.signals_f32(None, threshold=1.0)', -1, 'input must be a torch.float32 tensor'),
+    ('host.signals_f32(X, factor=6.0, group=4)', -2, 'the batch (2 frames) must be a multiple of 4'),
+    ('host.signals_f32(X, threshold=torch.zeros(2), group=2)', -2, 'a threshold per row must be a contiguous torch.float32 tensor of shape (1,)'),
+    ('host.signals_f32(X, threshold=torch.zeros(3))', -2, 'a threshold per row must be a contiguous torch.float32 tensor of shape (2,)'),
+    ('host.signals_f32(X, factor=6.0, group=2, out=BAD)', -2, 'out must be a contiguous torch.int32 tensor of shape (1, 16, 6)'),
+    ('host.signals_f32(X, threshold=1.0, k=3, out=BAD)', -2, 'out must be a contiguous torch.int32 tensor of shape (2, 3, 6)'),
+    ('host.signals_f32(X, factor=6.0, stats=BAD)', -2, 'stats must be a contiguous torch.int32 tensor of shape (2, 3)'),
+    ('host.signals_f32(X, factor=6.0, work=BAD)', -2, 'work must be a contiguous torch.float32 tensor of shape [2 or more, 16384]'),
+    ('host.signals_f32(X, threshold=1.0, group=2, work=torch.zeros((1, N)))', -2, 'work must be a contiguous torch.float32 tensor of shape [2 or more, 16384]'),
+    ('bare.cfar(None, train=True)', -1, 'train must be an int'),
+    ('bare.cfar(None, train=16.0)', -1, 'train must be an int'),
+    ('bare.cfar(None, guard=2.0)', -1, 'guard must be an int'),
+    ('bare.cfar(None, guard=False)', -1, 'guard must be an int'),
+    ('bare.cfar(None, lo=0.0)', -1, 'lo must be an int'),
+    ("bare.cfar(None, hi='5')", -1, 'hi must be an int'),
+    ('bare.cfar(None, train=3)', -1, 'train must be one of (1, 2, 4, 8, 16, 32, 64)'),
+    ('bare.cfar(None, train=0)', -1, 'train must be one of (1, 2, 4, 8, 16, 32, 64)'),
+    ('bare.cfar(None, train=128)', -1, 'train must be one of (1, 2, 4, 8, 16, 32, 64)'),
+    ('bare.cfar(None, guard=-1)', -1, 'guard must be 0..64'),
+    ('bare.cfar(None, guard=65)', -1, 'guard must be 0..64'),
+    ("bare.cfar(None, mode='os')", -1, "mode must be 'ca', 'go' or 'so'"),
+    ('bare.cfar(None, mode=0)', -1, "mode must be 'ca', 'go' or 'so'"),
+    ("bare.cfar(None, what='db')", -1, "what must be 'ratio' or 'floor'"),
+    ('bare.cfar(None, what=1)', -1, "what must be 'ratio' or 'floor'"),
+    ('bare.cfar(None, lo=5, hi=5)', -1, 'the range must be 0 <= lo < hi <= 16384'),
+    ('bare.cfar(None, hi=N + 1)', -1, 'the range must be 0 <= lo < hi <= 16384'),
+    ('bare.cfar(None, lo=10, hi=15)', -1, 'the range must hold 2 * guard + 2 bins or more'),
+    ('bare.cfar(None, guard=64, lo=0, hi=129)', -1, 'the range must hold 2 * guard + 2 bins or more'),
+    ("bare.cfar(None, field='mag')", -1, "field must be None, 'peak' or 'power'"),
+    ('bare.cfar(None, field=0)', -1, "field must be None, 'peak' or 'power'"),
+    ("bare.cfar(None, train=True, field='mag')", -1, 'train must be an int'),
+    ('bare.cfar(None)', -1, 'input must be a torch.float32 tensor'),
+    ("bare.cfar(None, 64, 64, 'so', 'floor', 0, 130, 'power')", -1, 'input must be a torch.float32 tensor'),
+    ("host.cfar(X, field='power')", -2, 'input must be a contiguous [B, 16384, 2] tensor'),
+    ('host.cfar(REC)', -2, 'input must be a contiguous [B, 16384] tensor'),
+    ('host.cfar(X, out=BAD)', -2, 'out must be a contiguous torch.float32 tensor of shape (2, 16384)'),
+    ('host.cfar(X, out=torch.zeros((2, N), dtype=torch.float64))', -2, 'out must be a contiguous torch.float32 tensor of shape (2, 16384)'),
+    ("host.cfar(REC, field='peak', out=torch.zeros((2, N, 2)))", -2, 'out must be a contiguous torch.float32 tensor of shape (2, 16384)'),
+    ('bare.cfar_f32(None, train=5)', -1, 'train must be one of (1, 2, 4, 8, 16, 32, 64)'),
+    ('bare.cfar_f32(None, train=5, group=3)', -1, 'train must be one of (1, 2, 4, 8, 16, 32, 64)'),
+    ('bare.cfar_f32(None, guard=1.5)', -1, 'guard must be an int'),
+    ('bare.cfar_f32(None, guard=100)', -1, 'guard must be 0..64'),
+    ("bare.cfar_f32(None, mode='CA')", -1, "mode must be 'ca', 'go' or 'so'"),
+    ("bare.cfar_f32(None, what='snr')", -1, "what must be 'ratio' or 'floor'"),
+    ('bare.cfar_f32(None, lo=5, hi=5)', -1, 'the range must be 0 <= lo < hi <= 16384'),
+    ('bare.cfar_f32(None, lo=0, hi=5)', -1, 'the range must hold 2 * guard + 2 bins or more'),
+    ('bare.cfar_f32(None, group=3)', -1, 'group must be one of (1, 2, 4, 8, 16, 32, 64, 128)'),
+    ('bare.cfar_f32(None, group=1)', -1, 'group = bucket = 1 folds nothing'),
+    ('bare.cfar_f32(None, group=2.0)', -1, 'group must be one of (1, 2, 4, 8, 16, 32, 64, 128)'),
+    ('bare.cfar_f32(None, group=128)', -1, 'input must be a torch.float32 tensor'),
+    ('bare.cfar_f32(None)', -1, 'input must be a torch.float32 tensor'),
+    ('host.cfar_f32(X, group=4)', -2, 'the batch (2 frames) must be a multiple of 4'),
+    ('host.cfar_f32(X, group=2, out=torch.zeros((2, N)))', -2, 'out must be a contiguous torch.float32 tensor of shape (1, 16384)'),
+    ('host.cfar_f32(X, out=BAD)', -2, 'out must be a contiguous torch.float32 tensor of shape (2, 16384)'),
+    ('host.cfar_f32(X, work=BAD)', -2, 'work must be a contiguous torch.float32 tensor of shape [2 or more, 16384]'),
+    ('host.cfar_f32(X, group=2, work=torch.zeros((1, N)))', -2, 'work must be a contiguous torch.float32 tensor of shape [2 or more, 16384]'),
 ]
 METHODS = ("fold_mag_f32", "spectra_f32", "find_peaks", "peak_table_f32", "order_stats", "noise_floor_f32", "level_hist",
-           "persistence_f32", "band_power", "channel_power_f32", "mask_test", "mask_trigger_f32", "harmonics", "harmonics_f32")
-COMPOSED = ("peak_table_f32", "noise_floor_f32", "persistence_f32", "channel_power_f32", "mask_trigger_f32", "harmonics_f32")
-LIBRARIES = ("fold", "peaks", "rank", "hist", "bands", "mask", "harm")
+           "persistence_f32", "band_power", "channel_power_f32", "mask_test", "mask_trigger_f32", "harmonics", "harmonics_f32",
+           "find_signals", "signals_f32", "cfar", "cfar_f32")
+# the methods whose tables came with a floor of 8 distinct scalar refusals
+MANY_TEXTS = ("find_signals", "signals_f32", "cfar", "cfar_f32")
+COMPOSED = ("peak_table_f32", "noise_floor_f32", "persistence_f32", "channel_power_f32", "mask_trigger_f32", "harmonics_f32",
+            "signals_f32", "cfar_f32")
 
 
 def _namespace():
@@ -268,12 +390,12 @@ def _rows(method, obj=""):
 
 
 def test_the_table_covers_every_method():
-    """Each of the fourteen methods has a scalar refusal, and with good arguments the refusal of its input; a bad argument wins
+    """Each of the eighteen methods has a scalar refusal, and with good arguments the refusal of its input; a bad argument wins
     over a bad input (every ``bare`` row passes None as the input); the composed ones have their ``group`` refusals."""
     groups = "group must be one of (1, 2, 4, 8, 16, 32, 64, 128)"
     for method in METHODS:
         texts = list(_rows(method, "bare").values())
-        assert "input must be a torch.float32 tensor" in texts and len(set(texts)) >= 4, method
+        assert "input must be a torch.float32 tensor" in texts and len(set(texts)) >= (8 if method in MANY_TEXTS else 4), method
         assert any(" must be " in t and "tensor" not in t for t in texts), method
         assert any("shape" in message for message in _rows(method, "host").values()), method
     for method in COMPOSED:
@@ -300,6 +422,7 @@ def test_the_names_the_tests_and_tools_use():
     import os
 
     from fpga_real_time_fft_analyzer_amd import abi, chain
+    from reduction_libraries import LIBRARIES
     fields = [getattr(chain, f"_{x}_FIELDS") for x in ("PEAK", "RANK", "BANDS", "MASK", "HARM")]
     assert all(f == {None: 0, "peak": 1, "power": 2} for f in fields) and chain._HARM_WORDS == 42
     for x in LIBRARIES:
