@@ -25,6 +25,71 @@ def _iq(frame_bytes: bytes):
     return a[:, 0], a[:, 1]
 
 
+# ---------------------------------------------------------------------------- what the argument rules below share, each once
+def _is_int(v) -> bool:
+    """Whether ``v`` is an int: a bool or a float is none."""
+    return not isinstance(v, bool) and isinstance(v, (int, np.integer))
+
+
+def _is_number(v) -> bool:
+    """Whether ``v`` is an int or a float: a bool or a str is none."""
+    return not isinstance(v, bool) and isinstance(v, (int, float, np.integer, np.floating))
+
+
+def _ints(**named) -> tuple:
+    """The values as Python ints, in the order given, or ValueError "`name` must be an int" for the first that is none."""
+    for name, v in named.items():
+        if not _is_int(v):
+            raise ValueError(f"{name} must be an int")
+    return tuple(int(v) for v in named.values())
+
+
+def _is_bin_range(lo: int, hi: int) -> bool:
+    """Whether [lo, hi) is a range of bins that is not empty."""
+    return 0 <= lo < hi <= FFT_SIZE
+
+
+def _bin_range(lo: int, hi: int) -> None:
+    """ValueError unless the ints ``lo`` and ``hi`` are a range of bins."""
+    if not _is_bin_range(lo, hi):
+        raise ValueError(f"the range must be 0 <= lo < hi <= {FFT_SIZE}")
+
+
+RANK_FIELDS = {None: None, "peak": 0, "power": 1}      # field -> the float of a (peak, power) record that is the point
+
+
+def _field(field) -> None:
+    """ValueError unless ``field`` is None, 'peak' or 'power'; every rule function looks at it last."""
+    if not (field is None or isinstance(field, str)) or field not in RANK_FIELDS:
+        raise ValueError("field must be None, 'peak' or 'power'")
+
+
+def _points(points, field=None) -> np.ndarray:
+    """The input of a mirror as a C-contiguous float32 [R, 16384] array: ``points`` itself, or with ``field`` 'peak' or 'power'
+    that float of the records [R, 16384, 2]; ValueError on any other dtype or shape.  ``field`` has passed :func:`_field`."""
+    points = np.ascontiguousarray(points)
+    shape = (FFT_SIZE,) if field is None else (FFT_SIZE, 2)
+    if points.dtype != np.float32 or points.ndim != 1 + len(shape) or points.shape[1:] != shape:
+        raise ValueError(f"points must be float32 [R, {', '.join(map(str, shape))}]")
+    return points if field is None else np.ascontiguousarray(points[..., RANK_FIELDS[field]])
+
+
+def _key(a: np.ndarray) -> np.ndarray:
+    """The keys of float32 values, uint32: the bits with the sign cleared -- +inf above every finite value, a NaN above +inf,
+    -0.0 as +0.0, denormals kept."""
+    return a.view(np.uint32) & np.uint32(0x7FFFFFFF)
+
+
+def _threshold_key(threshold) -> int:
+    """The key of a threshold common to all rows, or ValueError: a number that is +0.0 .. +inf as a float32."""
+    if not _is_number(threshold):
+        raise ValueError("threshold must be a number")
+    key = int(np.array([threshold], np.float32).view(np.uint32)[0])
+    if key > 0x7F800000:
+        raise ValueError("threshold must be +0.0 .. +inf: no NaN, no sign bit")
+    return key
+
+
 def decode_mag_16iq_le(frame_bytes: bytes) -> np.ndarray:
     """Same result as gui.py:250-260: float32 sqrt(re^2 + im^2) over all 16384 bins."""
     re, im = _iq(frame_bytes)
@@ -35,7 +100,7 @@ def marker_of_frame(frame_bytes: bytes, lo: int = 0, hi: int = FFT_SIZE):
     """What the gui shows of a frame cut to the bins [lo, hi) (gui.py:294-305, 415-455): ``(peak_mag float32, peak_bin
     int, band_power int)`` -- np.max and lo + np.argmax of the decoded magnitudes, and the exact integer sum of
     re^2 + im^2.  The host mirror of one sa_marker_q15 record (include/specan.h)."""
-    if not 0 <= lo < hi <= FFT_SIZE:
+    if not _is_bin_range(lo, hi):
         raise ValueError("need 0 <= lo < hi <= 16384")
     mag = decode_mag_16iq_le(frame_bytes)[lo:hi]
     re, im = _iq(frame_bytes)
@@ -51,7 +116,7 @@ def trace_of_frame(frame_bytes: bytes, bucket: int):
     float32 [P], power float32 [P], exact int64 [P])`` -- the largest decoded magnitude of each bucket, the exact integer
     sum of re^2 + im^2 over it rounded once to float32 (numpy's int64 -> float32 conversion rounds to nearest even), and
     that sum itself.  The host mirror of one frame's sa_trace_point_q15 records (include/specan.h, SA_Q15_TRACE_KIND)."""
-    if isinstance(bucket, bool) or not isinstance(bucket, (int, np.integer)) or int(bucket) not in TRACE_BUCKETS:
+    if not _is_int(bucket) or int(bucket) not in TRACE_BUCKETS:
         raise ValueError(f"bucket must be one of {TRACE_BUCKETS}")
     bucket = int(bucket)
     peak = decode_mag_16iq_le(frame_bytes).reshape(-1, bucket).max(axis=1)
@@ -99,6 +164,17 @@ FOLD_GROUPS = (1, 2, 4, 8, 16, 32, 64, 128)
 FOLD_BUCKETS = (1, 2, 4, 8, 16, 32, 64)
 
 
+def _fold_args(group, bucket) -> tuple:
+    """``(group, bucket)`` of the fold as ints, or ValueError: ``group`` one of 1, 2, ..., 128 and ``bucket`` one of 1, 2, ...,
+    64 (no bool, no float), not both 1."""
+    for name, v, allowed in (("group", group, FOLD_GROUPS), ("bucket", bucket, FOLD_BUCKETS)):
+        if not _is_int(v) or int(v) not in allowed:
+            raise ValueError(f"{name} must be one of {allowed}")
+    if int(group) == 1 and int(bucket) == 1:
+        raise ValueError("group = bucket = 1 folds nothing")
+    return int(group), int(bucket)
+
+
 def fold_of_mags(mag, group: int, bucket: int):
     """Float32 magnitudes [B, n] (n = 16384 for the chain's 'mag_full' frames; any multiple of ``bucket`` here) reduced over
     groups of ``group`` = 1, 2, ..., 128 consecutive frames and buckets of ``bucket`` = 1, 2, ..., 64 adjacent bins, not both
@@ -111,19 +187,13 @@ def fold_of_mags(mag, group: int, bucket: int):
       the other, ascending, from +0.0 (the explicit loop), then across the bucket's bins by a balanced tree of adjacent
       pairs, ``t[i] = t[2i] + t[2i+1]`` (the explicit halving); power is s64 rounded once to float32 (numpy's cast rounds to
       nearest even, overflows to inf and keeps denormals).  It is the sum: the mean is ``power / (group * bucket)``, exactly."""
-    for name, v, allowed in (("group", group, FOLD_GROUPS), ("bucket", bucket, FOLD_BUCKETS)):
-        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or int(v) not in allowed:
-            raise ValueError(f"{name} must be one of {allowed}")
-    group, bucket = int(group), int(bucket)
-    if group == 1 and bucket == 1:
-        raise ValueError("group = bucket = 1 folds nothing")
+    group, bucket = _fold_args(group, bucket)
     mag = np.ascontiguousarray(mag)
     if mag.dtype != np.float32 or mag.ndim != 2 or mag.shape[0] % group or mag.shape[1] % bucket:
         raise ValueError("mag must be float32 [B, n] with B a multiple of group and n a multiple of bucket")
     B, n = mag.shape
     G, P = B // group, n // bucket
-    u = mag.view(np.uint32) & np.uint32(0x7FFFFFFF)
-    peak = np.ascontiguousarray(u.reshape(G, group, P, bucket).max(axis=(1, 3))).view(np.float32)
+    peak = np.ascontiguousarray(_key(mag).reshape(G, group, P, bucket).max(axis=(1, 3))).view(np.float32)
     m = mag.astype(np.float64).reshape(G, group, n)
     with np.errstate(over="ignore", invalid="ignore"):
         t = np.zeros((G, n), np.float64)
@@ -136,6 +206,21 @@ def fold_of_mags(mag, group: int, bucket: int):
 
 
 PEAKS_K_MAX = 32
+
+
+def _peaks_args(k, threshold, lo, hi, min_sep, field) -> tuple:
+    """``(k, the threshold's key, lo, hi, min_sep)`` of the peak table as ints, or ValueError: ``k``, ``lo``, ``hi`` and
+    ``min_sep`` ints (no bool, no float), ``k`` 1..32, ``threshold`` a number that is +0.0 .. +inf as a float32,
+    ``0 <= lo < hi <= 16384``, ``min_sep`` 1..16384; ``field`` None, 'peak' or 'power'."""
+    k, lo, hi, min_sep = _ints(k=k, lo=lo, hi=hi, min_sep=min_sep)
+    if not 1 <= k <= PEAKS_K_MAX:
+        raise ValueError(f"k must be 1..{PEAKS_K_MAX}")
+    tkey = _threshold_key(threshold)
+    _bin_range(lo, hi)
+    if not 1 <= min_sep <= FFT_SIZE:
+        raise ValueError(f"min_sep must be 1..{FFT_SIZE}")
+    _field(field)
+    return k, tkey, lo, hi, min_sep
 
 
 def peaks_of_rows(points, k: int = 8, threshold: float = 0.0, lo: int = 0, hi: int = FFT_SIZE, min_sep: int = 1):
@@ -152,20 +237,14 @@ def peaks_of_rows(points, k: int = 8, threshold: float = 0.0, lo: int = 0, hi: i
       was not accepted suppresses nothing;
     - the records in acceptance order, mag the point with its sign cleared; the unused slots are (+0.0, -1).
 
-    ``k`` is 1..32, ``threshold`` no NaN and not negative (-0.0 included), ``0 <= lo < hi <= 16384``, ``min_sep`` 1..16384, the
-    integers ints (no bool, no float): ValueError otherwise."""
-    for name, v in (("k", k), ("lo", lo), ("hi", hi), ("min_sep", min_sep)):
-        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
-            raise ValueError(f"{name} must be an int")
-    k, lo, hi, min_sep = int(k), int(lo), int(hi), int(min_sep)
-    tkey = int(np.array([threshold], np.float32).view(np.uint32)[0])
-    if not 1 <= k <= PEAKS_K_MAX or tkey > 0x7F800000 or not 0 <= lo < hi <= FFT_SIZE or not 1 <= min_sep <= FFT_SIZE:
-        raise ValueError("k must be 1..32, threshold +0.0..+inf, 0 <= lo < hi <= 16384 and min_sep 1..16384")
-    points = np.ascontiguousarray(points)
-    if points.dtype != np.float32 or points.ndim != 2 or points.shape[1] != FFT_SIZE:
-        raise ValueError("points must be float32 [R, 16384]")
+    The integers are ints (no bool, no float), ``k`` is 1..32, ``threshold`` a number (no bool, no str) that is no NaN and
+    not negative (-0.0 included), ``0 <= lo < hi <= 16384``, ``min_sep`` 1..16384: ValueError otherwise, one text per rule
+    and in that order (:func:`_peaks_args`, which ``find_peaks`` of the device refuses by too), and on a wrong dtype or
+    shape."""
+    k, tkey, lo, hi, min_sep = _peaks_args(k, threshold, lo, hi, min_sep, None)
+    points = _points(points)
     R = points.shape[0]
-    u = (points.view(np.uint32) & np.uint32(0x7FFFFFFF)).astype(np.int64)
+    u = _key(points).astype(np.int64)
     left = np.concatenate([np.full((R, 1), -1, np.int64), u[:, :-1]], axis=1)      # below every key: the missing neighbours
     right = np.concatenate([u[:, 1:], np.full((R, 1), -1, np.int64)], axis=1)
     i = np.arange(FFT_SIZE)
@@ -187,7 +266,21 @@ def peaks_of_rows(points, k: int = 8, threshold: float = 0.0, lo: int = 0, hi: i
 
 
 RANK_Q_MAX = 8
-RANK_FIELDS = {None: None, "peak": 0, "power": 1}      # field -> the float of a (peak, power) record that is the point
+
+
+def _rank_args(ranks, lo, hi, field) -> tuple:
+    """``(ranks as a tuple of ints, lo, hi)`` of the order statistics, or ValueError: ``lo`` and ``hi`` ints (no bool, no
+    float) with ``0 <= lo < hi <= 16384``, ``ranks`` a sequence of 1..8 ints, each ``0 <= rank < hi - lo``; ``field`` None,
+    'peak' or 'power'."""
+    lo, hi = _ints(lo=lo, hi=hi)
+    _bin_range(lo, hi)
+    if isinstance(ranks, (str, bytes)) or not hasattr(ranks, "__len__") or not 1 <= len(ranks) <= RANK_Q_MAX:
+        raise ValueError(f"ranks must be a sequence of 1..{RANK_Q_MAX} ints")
+    for v in ranks:
+        if not _is_int(v) or not 0 <= int(v) < hi - lo:
+            raise ValueError(f"a rank must be an int in 0..{hi - lo - 1}")
+    _field(field)
+    return tuple(int(v) for v in ranks), lo, hi
 
 
 def ranks_of_rows(points, ranks, lo: int = 0, hi: int = FFT_SIZE, field=None):
@@ -203,28 +296,9 @@ def ranks_of_rows(points, ranks, lo: int = 0, hi: int = FFT_SIZE, field=None):
     ``ranks`` is a sequence of 1..8 ints, each ``0 <= rank < hi - lo``, in any order, repeats allowed;
     ``0 <= lo < hi <= 16384``; the integers are ints (no bool, no float): ValueError otherwise, and on a wrong dtype or
     shape."""
-    for name, v in (("lo", lo), ("hi", hi)):
-        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
-            raise ValueError(f"{name} must be an int")
-    lo, hi = int(lo), int(hi)
-    if not 0 <= lo < hi <= FFT_SIZE:
-        raise ValueError("the range must be 0 <= lo < hi <= 16384")
-    if isinstance(ranks, (str, bytes)) or not hasattr(ranks, "__len__") or not 1 <= len(ranks) <= RANK_Q_MAX:
-        raise ValueError(f"ranks must be a sequence of 1..{RANK_Q_MAX} ints")
-    for v in ranks:
-        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) < hi - lo:
-            raise ValueError(f"a rank must be an int in 0..{hi - lo - 1}")
-    if not (field is None or isinstance(field, str)) or field not in RANK_FIELDS:
-        raise ValueError("field must be None, 'peak' or 'power'")
-    points = np.ascontiguousarray(points)
-    shape = (FFT_SIZE,) if field is None else (FFT_SIZE, 2)
-    if points.dtype != np.float32 or points.ndim != 1 + len(shape) or points.shape[1:] != shape:
-        raise ValueError(f"points must be float32 [R, {', '.join(map(str, shape))}]")
-    if field is not None:
-        points = np.ascontiguousarray(points[..., RANK_FIELDS[field]])
-    u = points.view(np.uint32)[:, lo:hi] & np.uint32(0x7FFFFFFF)
-    s = np.sort(u, axis=1)
-    return np.ascontiguousarray(s[:, [int(v) for v in ranks]]).view(np.float32)
+    ranks, lo, hi = _rank_args(ranks, lo, hi, field)
+    s = np.sort(_key(_points(points, field))[:, lo:hi], axis=1)
+    return np.ascontiguousarray(s[:, list(ranks)]).view(np.float32)
 
 
 def rank_of_quantile(q: float, m: int) -> int:
@@ -233,9 +307,9 @@ def rank_of_quantile(q: float, m: int) -> int:
     lower median.  The double product decides, not the decimal one: 0.29 * 100 is 28.999999999999996 in doubles, so
     ``rank_of_quantile(0.29, 101)`` is 28.  ValueError on a q that is no number in [0, 1] (a NaN included) or an m that is no
     int >= 1."""
-    if isinstance(m, bool) or not isinstance(m, (int, np.integer)) or int(m) < 1:
+    if not _is_int(m) or int(m) < 1:
         raise ValueError("m must be an int >= 1")
-    if isinstance(q, bool) or not isinstance(q, (int, float, np.integer, np.floating)) or not 0.0 <= float(q) <= 1.0:
+    if not _is_number(q) or not 0.0 <= float(q) <= 1.0:
         raise ValueError("q must be a number in 0..1")
     return math.floor(float(q) * (int(m) - 1))
 
@@ -250,9 +324,8 @@ def _hist_edge_keys(edges) -> np.ndarray:
     no NaN (bits <= 0x7F800000), the keys non-decreasing."""
     if isinstance(edges, (str, bytes)) or not hasattr(edges, "__len__") or not 1 <= len(edges) <= HIST_LEVELS_MAX - 1:
         raise ValueError(f"edges must be a sequence of 1..{HIST_LEVELS_MAX - 1} numbers")
-    for v in edges:
-        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
-            raise ValueError("an edge must be a number")
+    if not all(_is_number(v) for v in edges):
+        raise ValueError("an edge must be a number")
     with np.errstate(over="ignore"):
         keys = np.array([float(v) for v in edges], np.float64).astype(np.float32).view(np.uint32)
     if (keys > 0x7F800000).any():
@@ -260,6 +333,24 @@ def _hist_edge_keys(edges) -> np.ndarray:
     if (keys[1:] < keys[:-1]).any():
         raise ValueError("the edges must not decrease")
     return keys
+
+
+def _hist_args(edges, group, bucket, lo, hi) -> tuple:
+    """``(the edges' keys, group, bucket, lo, hi)`` of the level histogram, the last four as ints, or ValueError: ``bucket``,
+    ``lo``, ``hi`` and ``group`` ints (no bool, no float), ``group`` 1..2^24 -- or None, all rows, which stays None --
+    ``bucket`` one of 1, 2, ..., 64, the edges those of :func:`_hist_edge_keys`, ``0 <= lo < hi <= 16384``, both multiples of
+    the bucket."""
+    bucket, lo, hi = _ints(bucket=bucket, lo=lo, hi=hi)
+    if group is not None:
+        group, = _ints(group=group)
+        if not 1 <= group <= HIST_GROUP_MAX:
+            raise ValueError(f"group must be 1..{HIST_GROUP_MAX}")
+    if bucket not in HIST_BUCKETS:
+        raise ValueError(f"bucket must be one of {HIST_BUCKETS}")
+    edge_keys = _hist_edge_keys(edges)
+    if not _is_bin_range(lo, hi) or lo % bucket or hi % bucket:
+        raise ValueError(f"the range must be 0 <= lo < hi <= {FFT_SIZE}, both multiples of the bucket")
+    return edge_keys, group, bucket, lo, hi
 
 
 def hist_of_rows(points, edges, group: int = 1, bucket: int = 1, lo: int = 0, hi: int = FFT_SIZE):
@@ -273,27 +364,18 @@ def hist_of_rows(points, edges, group: int = 1, bucket: int = 1, lo: int = 0, hi
       value equal to an edge is in the level above it, a NaN in level L - 1, L = len(edges) + 1.
 
     ``edges`` is a sequence of 1..63 numbers, each +0.0 .. +inf as a float32 and none below the one before; ``group`` is
-    1..2^24 and divides R; ``bucket`` is 1, 2, ..., 64; ``0 <= lo < hi <= 16384``, both multiples of ``bucket``; the integers
-    are ints (no bool, no float): ValueError otherwise, and on a wrong dtype or shape."""
-    for name, v in (("group", group), ("bucket", bucket), ("lo", lo), ("hi", hi)):
-        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
-            raise ValueError(f"{name} must be an int")
-    group, bucket, lo, hi = int(group), int(bucket), int(lo), int(hi)
-    if not 1 <= group <= HIST_GROUP_MAX:
-        raise ValueError(f"group must be 1..{HIST_GROUP_MAX}")
-    if bucket not in HIST_BUCKETS:
-        raise ValueError(f"bucket must be one of {HIST_BUCKETS}")
-    edge_keys = _hist_edge_keys(edges)
-    if not 0 <= lo < hi <= FFT_SIZE or lo % bucket or hi % bucket:
-        raise ValueError("the range must be 0 <= lo < hi <= 16384, both multiples of the bucket")
-    points = np.ascontiguousarray(points)
-    if points.dtype != np.float32 or points.ndim != 2 or points.shape[1] != FFT_SIZE:
-        raise ValueError("points must be float32 [R, 16384]")
+    1..2^24 and divides R, or None, all rows (G = 1), as for ``level_hist``; ``bucket`` is 1, 2, ..., 64;
+    ``0 <= lo < hi <= 16384``, both multiples of ``bucket``; the integers are ints (no bool, no float), looked at in the order bucket, lo, hi, group, before the ranges: ValueError otherwise
+    (:func:`_hist_args`, which ``level_hist`` of the device refuses by too), and on a wrong dtype or shape."""
+    edge_keys, group, bucket, lo, hi = _hist_args(edges, group, bucket, lo, hi)
+    points = _points(points)
     R = points.shape[0]
+    if group is None:
+        group = max(R, 1)
     if R % group:
         raise ValueError(f"the rows ({R}) must be a multiple of group ({group})")
     G, cols, L = R // group, (hi - lo) // bucket, len(edge_keys) + 1
-    keys = points.view(np.uint32)[:, lo:hi] & np.uint32(0x7FFFFFFF)
+    keys = _key(points)[:, lo:hi]
     level = np.searchsorted(edge_keys, keys, side="right").reshape(G, group, cols, bucket)
     cell = (np.arange(G).reshape(G, 1, 1, 1) * cols + np.arange(cols).reshape(1, 1, cols, 1)) * L + level
     return np.bincount(cell.ravel(), minlength=G * cols * L).astype(np.uint32).reshape(G, cols, L)
@@ -305,10 +387,10 @@ def level_edges_db(top: float, span_db: float, levels: int) -> np.ndarray:
     2)))`` computed in float64 and rounded once.  With ``levels`` = 2 the single edge is ``top``.  A host convenience: the
     edges are an input of the histogram, not part of its definition.  ValueError unless ``top`` is a finite number above 0,
     ``span_db`` a finite number not below 0 and ``levels`` an int in 2..64."""
-    if isinstance(levels, bool) or not isinstance(levels, (int, np.integer)) or not 2 <= int(levels) <= HIST_LEVELS_MAX:
+    if not _is_int(levels) or not 2 <= int(levels) <= HIST_LEVELS_MAX:
         raise ValueError(f"levels must be an int in 2..{HIST_LEVELS_MAX}")
     for name, v in (("top", top), ("span_db", span_db)):
-        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not math.isfinite(float(v)):
+        if not _is_number(v) or not math.isfinite(float(v)):
             raise ValueError(f"{name} must be a finite number")
     if not float(top) > 0.0 or float(span_db) < 0.0:
         raise ValueError("top must be above 0 and span_db not below 0")
@@ -336,21 +418,18 @@ def _bands_args(bands, fracs, field) -> tuple:
     for b in bands:
         if isinstance(b, (str, bytes)) or not hasattr(b, "__len__") or len(b) != 2:
             raise ValueError("a band must be a (lo, hi) pair")
-        for v in b:
-            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
-                raise ValueError("lo and hi of a band must be ints")
+        if not all(_is_int(v) for v in b):
+            raise ValueError("lo and hi of a band must be ints")
         lo, hi = int(b[0]), int(b[1])
-        if not 0 <= lo < hi <= FFT_SIZE:
+        if not _is_bin_range(lo, hi):
             raise ValueError("a band must be 0 <= lo < hi <= 16384")
         pairs.append((lo, hi))
     if isinstance(fracs, (str, bytes)) or not hasattr(fracs, "__len__") or len(fracs) > BANDS_Q_MAX:
         raise ValueError(f"fracs must be a sequence of 0..{BANDS_Q_MAX} numbers")
     for v in fracs:
-        if (isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating))
-                or not 0.0 <= float(v) <= BANDS_FRAC_MAX):
+        if not _is_number(v) or not 0.0 <= float(v) <= BANDS_FRAC_MAX:
             raise ValueError("a fraction must be a number in 0 .. 1 - 2^-32")
-    if not (field is None or isinstance(field, str)) or field not in RANK_FIELDS:
-        raise ValueError("field must be None, 'peak' or 'power'")
+    _field(field)
     return tuple(pairs), tuple(float(v) for v in fracs)
 
 
@@ -373,14 +452,9 @@ def bands_of_rows(points, bands, fracs=(), field=None):
     ``fracs`` a sequence of 0..4 numbers in [0, 1 - 2^-32], in any order; the integers are ints (no bool, no float):
     ValueError otherwise, and on a wrong dtype or shape."""
     bands, fracs = _bands_args(bands, fracs, field)
-    points = np.ascontiguousarray(points)
-    shape = (FFT_SIZE,) if field is None else (FFT_SIZE, 2)
-    if points.dtype != np.float32 or points.ndim != 1 + len(shape) or points.shape[1:] != shape:
-        raise ValueError(f"points must be float32 [R, {', '.join(map(str, shape))}]")
-    if field is not None:
-        points = np.ascontiguousarray(points[..., RANK_FIELDS[field]])
+    points = _points(points, field)
     R = points.shape[0]
-    a = (points.view(np.uint32) & np.uint32(0x7FFFFFFF)).view(np.float32).astype(np.float64)
+    a = _key(points).view(np.float32).astype(np.float64)
     power = np.zeros((R, len(bands)), np.float64)
     cross = np.zeros((R, len(bands), len(fracs)), np.int32)
     rows = np.arange(R)
@@ -415,10 +489,7 @@ def channel_bands(center: int, width: int, spacing: int, adjacent: int = 1) -> l
     adjacent channel that lies wholly outside the spectrum is left out.  A host convenience: the bands are an input of the
     call, not part of its definition.  ValueError unless all four are ints (no bool, no float), ``width`` and ``spacing`` are
     1 or more, ``adjacent`` is 0 or more, at most 16 bands result and the main band, clipped, is not empty."""
-    for name, v in (("center", center), ("width", width), ("spacing", spacing), ("adjacent", adjacent)):
-        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
-            raise ValueError(f"{name} must be an int")
-    center, width, spacing, adjacent = int(center), int(width), int(spacing), int(adjacent)
+    center, width, spacing, adjacent = _ints(center=center, width=width, spacing=spacing, adjacent=adjacent)
     if width < 1 or spacing < 1 or adjacent < 0:
         raise ValueError("width and spacing must be 1 or more and adjacent 0 or more")
 
@@ -446,18 +517,18 @@ _MASK_UNITS = {"amplitude": 20.0, "power": 10.0}       # dB = 20 log10 of a rati
 
 
 def _mask_args(upper, lower, lo, hi, field) -> tuple:
-    """``(upper, lower, lo, hi)`` of the mask test, each limit None or a C-contiguous float32 [16384] array, or ValueError:
-    not both limits None, ``0 <= lo < hi <= 16384`` as ints (no bool, no float), ``field`` None, 'peak' or 'power'."""
-    for name, v in (("lo", lo), ("hi", hi)):
-        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
-            raise ValueError(f"{name} must be an int")
-    lo, hi = int(lo), int(hi)
-    if not 0 <= lo < hi <= FFT_SIZE:
-        raise ValueError("the range must be 0 <= lo < hi <= 16384")
-    if not (field is None or isinstance(field, str)) or field not in RANK_FIELDS:
-        raise ValueError("field must be None, 'peak' or 'power'")
+    """``(lo, hi)`` of the mask test as ints, or ValueError: ``0 <= lo < hi <= 16384`` as ints (no bool, no float), ``field``
+    None, 'peak' or 'power', not both limits None.  The limits are only counted here; :func:`_mask_limits` looks at them."""
+    lo, hi = _ints(lo=lo, hi=hi)
+    _bin_range(lo, hi)
+    _field(field)
     if upper is None and lower is None:
         raise ValueError("upper and lower are both None: no limit at all")
+    return lo, hi
+
+
+def _mask_limits(upper, lower) -> tuple:
+    """``(upper, lower)`` of the mirror of the mask test, each None or a C-contiguous float32 [16384] array, or ValueError."""
     limits = []
     for name, v in (("upper", upper), ("lower", lower)):
         if v is not None:
@@ -465,7 +536,7 @@ def _mask_args(upper, lower, lo, hi, field) -> tuple:
                 raise ValueError(f"{name} must be None or a float32 [16384] array")
             v = np.ascontiguousarray(v)
         limits.append(v)
-    return limits[0], limits[1], lo, hi
+    return tuple(limits)
 
 
 def _mask_worst(key, lim, has, up: bool) -> np.ndarray:
@@ -508,15 +579,11 @@ def mask_of_rows(points, upper, lower=None, lo: int = 0, hi: int = FFT_SIZE, fie
     - ``summary``: rows with over > 0, rows with under > 0, the first row with either or -1, the last or -1.
 
     ``0 <= lo < hi <= 16384`` as ints (no bool, no float): ValueError otherwise, and on a wrong dtype or shape."""
-    upper, lower, lo, hi = _mask_args(upper, lower, lo, hi, field)
-    points = np.ascontiguousarray(points)
-    shape = (FFT_SIZE,) if field is None else (FFT_SIZE, 2)
-    if points.dtype != np.float32 or points.ndim != 1 + len(shape) or points.shape[1:] != shape:
-        raise ValueError(f"points must be float32 [R, {', '.join(map(str, shape))}]")
-    if field is not None:
-        points = np.ascontiguousarray(points[..., RANK_FIELDS[field]])
+    lo, hi = _mask_args(upper, lower, lo, hi, field)
+    upper, lower = _mask_limits(upper, lower)
+    points = _points(points, field)
     R = points.shape[0]
-    a = points.view(np.uint32) & np.uint32(0x7FFFFFFF)
+    a = _key(points)
     nan = a > 0x7F800000
     i = np.arange(FFT_SIZE)
     inside = (i >= lo) & (i < hi)
@@ -565,9 +632,9 @@ def limit_line(points, unit: str = "amplitude") -> np.ndarray:
         if isinstance(p, (str, bytes)) or not hasattr(p, "__len__") or len(p) != 2:
             raise ValueError("a breakpoint must be a (bin, dB) pair")
         b, d = p
-        if isinstance(b, bool) or not isinstance(b, (int, np.integer)) or not 0 <= int(b) < FFT_SIZE:
+        if not _is_int(b) or not 0 <= int(b) < FFT_SIZE:
             raise ValueError("a breakpoint's bin must be an int in 0..16383")
-        if isinstance(d, bool) or not isinstance(d, (int, float, np.integer, np.floating)) or not math.isfinite(float(d)):
+        if not _is_number(d) or not math.isfinite(float(d)):
             raise ValueError("a breakpoint's level must be a finite number of dB")
         if pairs and int(b) <= pairs[-1][0]:
             raise ValueError("the breakpoints' bins must ascend strictly")
@@ -592,15 +659,14 @@ def mask_from_trace(trace, margin_db: float, widen: int, unit: str = "amplitude"
     ``margin_db`` a finite number and ``widen`` an int in 0..16384."""
     if not isinstance(unit, str) or unit not in _MASK_UNITS:
         raise ValueError("unit must be 'amplitude' or 'power'")
-    if isinstance(widen, bool) or not isinstance(widen, (int, np.integer)) or not 0 <= int(widen) <= FFT_SIZE:
+    if not _is_int(widen) or not 0 <= int(widen) <= FFT_SIZE:
         raise ValueError("widen must be an int in 0..16384")
-    if (isinstance(margin_db, bool) or not isinstance(margin_db, (int, float, np.integer, np.floating))
-            or not math.isfinite(float(margin_db))):
+    if not _is_number(margin_db) or not math.isfinite(float(margin_db)):
         raise ValueError("margin_db must be a finite number")
     if not isinstance(trace, np.ndarray) or trace.dtype != np.float32 or trace.shape != (FFT_SIZE,):
         raise ValueError("trace must be a float32 [16384] array")
     w = int(widen)
-    a = (np.ascontiguousarray(trace).view(np.uint32) & np.uint32(0x7FFFFFFF)).view(np.float32)
+    a = _key(np.ascontiguousarray(trace)).view(np.float32)
     L = 2 * w + 1
     m = np.concatenate([np.zeros(w, np.float32), a, np.zeros(w, np.float32)])
     span = 1
@@ -647,12 +713,8 @@ def _harm_args(order, span, lo, hi, fund, dc, top, field) -> tuple:
     ``lo = dc``, ``hi = top``, ``fund = -1`` for a search), or ValueError: every one an int (no bool, no float),
     ``0 <= dc < top <= 8193``, ``dc <= lo < hi <= top``, ``fund`` None, -1 or in [dc, top), ``span`` 0..64, ``order`` 1..10;
     ``field`` None, 'peak' or 'power'."""
-    for name, v, optional in (("order", order, False), ("span", span, False), ("lo", lo, True), ("hi", hi, True),
-                              ("fund", fund, True), ("dc", dc, True), ("top", top, False)):
-        if v is None and optional:
-            continue
-        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
-            raise ValueError(f"{name} must be an int")
+    given = dict(order=order, span=span, lo=lo, hi=hi, fund=fund, dc=dc, top=top)
+    _ints(**{name: v for name, v in given.items() if v is not None or name in ("order", "span", "top")})
     order, span, top = int(order), int(span), int(top)
     if not 0 <= span <= HARM_SPAN_MAX:
         raise ValueError(f"span must be 0..{HARM_SPAN_MAX}")
@@ -668,8 +730,7 @@ def _harm_args(order, span, lo, hi, fund, dc, top, field) -> tuple:
     fund = -1 if fund is None else int(fund)
     if fund != -1 and not dc <= fund < top:
         raise ValueError("fund must be None, -1 or a bin in [dc, top)")
-    if not (field is None or isinstance(field, str)) or field not in RANK_FIELDS:
-        raise ValueError("field must be None, 'peak' or 'power'")
+    _field(field)
     return dc, top, lo, hi, fund, span, order
 
 
@@ -707,14 +768,9 @@ def harm_of_rows(points, order: int = 5, span: int = 3, lo=None, hi=None, fund=N
     Defaults: ``dc = span + 1``, ``lo = dc``, ``hi = top``.  The integers are ints (no bool, no float), within the ranges of
     the header: ValueError otherwise, and on a wrong dtype or shape."""
     dc, top, lo, hi, fund, span, order = _harm_args(order, span, lo, hi, fund, dc, top, field)
-    points = np.ascontiguousarray(points)
-    shape = (FFT_SIZE,) if field is None else (FFT_SIZE, 2)
-    if points.dtype != np.float32 or points.ndim != 1 + len(shape) or points.shape[1:] != shape:
-        raise ValueError(f"points must be float32 [R, {', '.join(map(str, shape))}]")
-    if field is not None:
-        points = np.ascontiguousarray(points[..., RANK_FIELDS[field]])
+    points = _points(points, field)
     R = points.shape[0]
-    bits = points.view(np.uint32) & np.uint32(0x7FFFFFFF)
+    bits = _key(points)
     keys = bits.astype(np.int64)
     a = bits.view(np.float32).astype(np.float64)
     rec = np.zeros(R, HARM_ROW)
@@ -799,31 +855,16 @@ SIGNAL = np.dtype([("start", "<i4"), ("stop", "<i4"), ("peak", "<f4"), ("peak_bi
 def _signals_args(k, lo, hi, gap, min_width, field) -> tuple:
     """``(k, lo, hi, gap, min_width)`` of the signal list as ints, or ValueError: every one an int (no bool, no float), ``k``
     1..32, ``0 <= lo < hi <= 16384``, ``gap`` 0..16383, ``min_width`` 1..16384; ``field`` None, 'peak' or 'power'."""
-    for name, v in (("k", k), ("lo", lo), ("hi", hi), ("gap", gap), ("min_width", min_width)):
-        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
-            raise ValueError(f"{name} must be an int")
-    k, lo, hi, gap, min_width = int(k), int(lo), int(hi), int(gap), int(min_width)
+    k, lo, hi, gap, min_width = _ints(k=k, lo=lo, hi=hi, gap=gap, min_width=min_width)
     if not 1 <= k <= SIGNALS_K_MAX:
         raise ValueError(f"k must be 1..{SIGNALS_K_MAX}")
-    if not 0 <= lo < hi <= FFT_SIZE:
-        raise ValueError(f"the range must be 0 <= lo < hi <= {FFT_SIZE}")
+    _bin_range(lo, hi)
     if not 0 <= gap <= SIGNALS_GAP_MAX:
         raise ValueError(f"gap must be 0..{SIGNALS_GAP_MAX}")
     if not 1 <= min_width <= FFT_SIZE:
         raise ValueError(f"min_width must be 1..{FFT_SIZE}")
-    if not (field is None or isinstance(field, str)) or field not in RANK_FIELDS:
-        raise ValueError("field must be None, 'peak' or 'power'")
+    _field(field)
     return k, lo, hi, gap, min_width
-
-
-def _threshold_key(threshold) -> int:
-    """The key of a threshold common to all rows, or ValueError: a number that is +0.0 .. +inf as a float32."""
-    if isinstance(threshold, bool) or not isinstance(threshold, (int, float, np.integer, np.floating)):
-        raise ValueError("threshold must be a number")
-    key = int(np.array([threshold], np.float32).view(np.uint32)[0])
-    if key > 0x7F800000:
-        raise ValueError("threshold must be +0.0 .. +inf: no NaN, no sign bit")
-    return key
 
 
 def signals_of_rows(points, k: int = 16, threshold=0.0, lo: int = 0, hi: int = FFT_SIZE, gap: int = 0, min_width: int = 1,
@@ -847,20 +888,15 @@ def signals_of_rows(points, k: int = 16, threshold=0.0, lo: int = 0, hi: int = F
     ``k`` is 1..32, ``0 <= lo < hi <= 16384``, ``gap`` 0..16383, ``min_width`` 1..16384, the integers ints (no bool, no
     float): ValueError otherwise, and on a wrong dtype or shape."""
     k, lo, hi, gap, min_width = _signals_args(k, lo, hi, gap, min_width, field)
-    points = np.ascontiguousarray(points)
-    shape = (FFT_SIZE,) if field is None else (FFT_SIZE, 2)
-    if points.dtype != np.float32 or points.ndim != 1 + len(shape) or points.shape[1:] != shape:
-        raise ValueError(f"points must be float32 [R, {', '.join(map(str, shape))}]")
-    if field is not None:
-        points = np.ascontiguousarray(points[..., RANK_FIELDS[field]])
+    points = _points(points, field)
     R = points.shape[0]
     if isinstance(threshold, np.ndarray):
         if threshold.dtype != np.float32 or threshold.shape != (R,):
             raise ValueError(f"a threshold per row must be float32 [{R}]")
-        T = (np.ascontiguousarray(threshold).view(np.uint32) & np.uint32(0x7FFFFFFF)).astype(np.int64)
+        T = _key(np.ascontiguousarray(threshold)).astype(np.int64)
     else:
         T = np.full(R, _threshold_key(threshold), np.int64)
-    bits = points.view(np.uint32) & np.uint32(0x7FFFFFFF)
+    bits = _key(points)
     keys = bits.astype(np.int64)
     a = bits.view(np.float32).astype(np.float64)
     idx = np.arange(FFT_SIZE)
@@ -902,10 +938,7 @@ def _cfar_args(train, guard, mode, what, lo, hi, field) -> tuple:
     ``lo`` and ``hi`` ints (no bool, no float), ``train`` one of 1, 2, 4, ..., 64, ``guard`` 0..64, ``mode`` 'ca', 'go' or
     'so', ``what`` 'ratio' or 'floor', ``0 <= lo < hi <= 16384`` with ``hi - lo >= 2 * guard + 2``; ``field`` None, 'peak' or
     'power'."""
-    for name, v in (("train", train), ("guard", guard), ("lo", lo), ("hi", hi)):
-        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
-            raise ValueError(f"{name} must be an int")
-    train, guard, lo, hi = int(train), int(guard), int(lo), int(hi)
+    train, guard, lo, hi = _ints(train=train, guard=guard, lo=lo, hi=hi)
     if train not in CFAR_TRAINS:
         raise ValueError(f"train must be one of {CFAR_TRAINS}")
     if not 0 <= guard <= CFAR_GUARD_MAX:
@@ -914,12 +947,10 @@ def _cfar_args(train, guard, mode, what, lo, hi, field) -> tuple:
         raise ValueError("mode must be 'ca', 'go' or 'so'")
     if not isinstance(what, str) or what not in CFAR_OUTPUTS:
         raise ValueError("what must be 'ratio' or 'floor'")
-    if not 0 <= lo < hi <= FFT_SIZE:
-        raise ValueError(f"the range must be 0 <= lo < hi <= {FFT_SIZE}")
+    _bin_range(lo, hi)
     if hi - lo < 2 * guard + 2:
         raise ValueError("the range must hold 2 * guard + 2 bins or more")
-    if not (field is None or isinstance(field, str)) or field not in RANK_FIELDS:
-        raise ValueError("field must be None, 'peak' or 'power'")
+    _field(field)
     return train.bit_length() - 1, guard, CFAR_MODES[mode], CFAR_OUTPUTS[what], lo, hi
 
 
@@ -930,9 +961,9 @@ def cfar_alpha(pfa: float, n: int) -> float:
     ``cfar_of_rows(..., mode='ca', what='ratio')`` n is 2 * train.  It applies to single frames: the sum of a ``group`` of
     frames is gamma, not exponentially, distributed, and its threshold is lower.  ``0 < pfa < 1`` and ``n`` an int of 1 or
     more: ValueError otherwise."""
-    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 1:
+    if not _is_int(n) or n < 1:
         raise ValueError("n must be an int of 1 or more")
-    if isinstance(pfa, bool) or not isinstance(pfa, (int, float, np.integer, np.floating)) or not 0.0 < pfa < 1.0:
+    if not _is_number(pfa) or not 0.0 < pfa < 1.0:
         raise ValueError("pfa must be a number above 0 and below 1")
     return int(n) * (float(pfa) ** (-1.0 / int(n)) - 1.0)
 
@@ -961,14 +992,9 @@ def cfar_of_rows(points, train: int = 16, guard: int = 2, mode: str = "ca", what
     ints (no bool, no float): ValueError otherwise, and on a wrong dtype or shape."""
     t, G, mode, what, lo, hi = _cfar_args(train, guard, mode, what, lo, hi, field)
     T = 1 << t
-    points = np.ascontiguousarray(points)
-    shape = (FFT_SIZE,) if field is None else (FFT_SIZE, 2)
-    if points.dtype != np.float32 or points.ndim != 1 + len(shape) or points.shape[1:] != shape:
-        raise ValueError(f"points must be float32 [R, {', '.join(map(str, shape))}]")
-    if field is not None:
-        points = np.ascontiguousarray(points[..., RANK_FIELDS[field]])
+    points = _points(points, field)
     R = points.shape[0]
-    a = (points.view(np.uint32) & np.uint32(0x7FFFFFFF)).view(np.float32).astype(np.float64)
+    a = _key(points).view(np.float32).astype(np.float64)
     idx = np.arange(FFT_SIZE)
     pad = G + T                                                            # W is wanted for j = -pad .. 16383 + G + 1
     with np.errstate(over="ignore", invalid="ignore", divide="ignore"):

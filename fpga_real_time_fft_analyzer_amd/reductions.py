@@ -5,8 +5,10 @@ composed with the float chain, the spectra never leaving the device (``spectra_f
 
 ``Reductions`` is a mixin of ``SpectrumChain`` (chain.py, which this module does not import): it reaches the handle through
 ``self`` -- ``device``, ``_stream``, ``_check_in``, ``_float_frames``, ``process_f32``, ``flush`` -- and keeps one copy of
-what every reduction does: the int-only check (``_ints``), the field code (``_field_code``), allocate-or-refuse of the
-outputs (``_outs``), the C call (``_call``) and the body of the composed calls (``_of_spectra``).
+what every reduction does: allocate-or-refuse of the outputs (``_outs``), the C call (``_call``) and the body of the composed
+calls (``_of_spectra``).  The rules of the scalar arguments are those of the numpy mirrors, stated once in frames.py
+(``frames._x_args``): ``_rules`` runs one and turns its ValueError into SA_EINVAL with the same text, so that a wrapper and
+its mirror refuse the same calls in the same words.
 """
 from __future__ import annotations
 
@@ -19,7 +21,6 @@ import torch
 from . import abi, frames
 from .abi import SA_N, SpecanError
 
-FOLD_GROUPS, FOLD_BUCKETS = frames.FOLD_GROUPS, frames.FOLD_BUCKETS
 # field=... -> the `field` of include/specan_{peaks,rank,bands,mask,harm,signals,cfar}.h: plain magnitudes, or one float of
 # (peak, power) records; the seven headers number the three layouts alike (SA_X_IN_MAG, SA_X_IN_POINT_PEAK, SA_X_IN_POINT_POWER)
 FIELDS = {None: 0, "peak": 1, "power": 2}
@@ -27,18 +28,12 @@ HARM_WORDS = C.sizeof(abi.HarmRow) // 4                                       # 
 SIGNAL_WORDS = C.sizeof(abi.Signal) // 4                                      # an sa_signal as int32 words: 6
 
 
-def _ints(*pairs) -> None:
-    """SA_EINVAL where the value of a (name, value) pair is no int: a bool or a float is none."""
-    for name, v in pairs:
-        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
-            raise SpecanError(abi.SA_EINVAL, f"{name} must be an int")
-
-
-def _field_code(field) -> int:
-    """The code of ``field`` in every library's header (FIELDS), or SA_EINVAL."""
-    if not (field is None or isinstance(field, str)) or field not in FIELDS:
-        raise SpecanError(abi.SA_EINVAL, "field must be None, 'peak' or 'power'")
-    return FIELDS[field]
+def _rules(rule, *args):
+    """``rule(*args)``, a rule function of frames.py, its ValueError re-raised as SA_EINVAL with the same text."""
+    try:
+        return rule(*args)
+    except ValueError as e:
+        raise SpecanError(abi.SA_EINVAL, str(e)) from None
 
 
 class Reductions:
@@ -87,12 +82,8 @@ class Reductions:
     @staticmethod
     def _log2_fold(group, bucket) -> tuple:
         """The one validation of the ``group`` and ``bucket`` of the float fold: (a, k) of A = 2^a and W = 2^k, or SA_EINVAL."""
-        for name, v, allowed in (("group", group, FOLD_GROUPS), ("bucket", bucket, FOLD_BUCKETS)):
-            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or int(v) not in allowed:
-                raise SpecanError(abi.SA_EINVAL, f"{name} must be one of {allowed}")
-        if int(group) == 1 and int(bucket) == 1:
-            raise SpecanError(abi.SA_EINVAL, "group = bucket = 1 folds nothing")
-        return int(group).bit_length() - 1, int(bucket).bit_length() - 1
+        group, bucket = _rules(frames._fold_args, group, bucket)
+        return group.bit_length() - 1, bucket.bit_length() - 1
 
     def _fold_out(self, B: int, group: int, bucket: int, out: Optional[torch.Tensor]) -> torch.Tensor:
         """``out`` of the float fold of ``B`` frames, allocated when None: SA_ESHAPE where B is no multiple of the group or
@@ -167,18 +158,8 @@ class Reductions:
     @staticmethod
     def _peaks_args(k, threshold, lo, hi, min_sep, field) -> int:
         """The one validation of the arguments of the peak table: the ``field`` code of include/specan_peaks.h, or SA_EINVAL."""
-        _ints(("k", k), ("lo", lo), ("hi", hi), ("min_sep", min_sep))
-        if not 1 <= int(k) <= abi.SA_PEAKS_K_MAX:
-            raise SpecanError(abi.SA_EINVAL, f"k must be 1..{abi.SA_PEAKS_K_MAX}")
-        if isinstance(threshold, bool) or not isinstance(threshold, (int, float, np.integer, np.floating)):
-            raise SpecanError(abi.SA_EINVAL, "threshold must be a number")
-        if int(np.array([threshold], np.float32).view(np.uint32)[0]) > 0x7F800000:
-            raise SpecanError(abi.SA_EINVAL, "threshold must be +0.0 .. +inf: no NaN, no sign bit")
-        if not 0 <= int(lo) < int(hi) <= SA_N:
-            raise SpecanError(abi.SA_EINVAL, f"the range must be 0 <= lo < hi <= {SA_N}")
-        if not 1 <= int(min_sep) <= SA_N:
-            raise SpecanError(abi.SA_EINVAL, f"min_sep must be 1..{SA_N}")
-        return _field_code(field)
+        _rules(frames._peaks_args, k, threshold, lo, hi, min_sep, field)
+        return FIELDS[field]
 
     def _peaks_out(self, R: int, k: int, out: Optional[torch.Tensor]) -> torch.Tensor:
         """``out`` of the peak table of ``R`` rows, allocated when None: SA_ESHAPE where it is not the contiguous int32 [R, k, 2]
@@ -245,16 +226,8 @@ class Reductions:
     def _rank_args(ranks, lo, hi, field) -> tuple:
         """The one validation of the arguments of the order statistics: ``(field code of include/specan_rank.h, the ranks as a
         tuple of ints)``, or SA_EINVAL."""
-        _ints(("lo", lo), ("hi", hi))
-        if not 0 <= int(lo) < int(hi) <= SA_N:
-            raise SpecanError(abi.SA_EINVAL, f"the range must be 0 <= lo < hi <= {SA_N}")
-        if isinstance(ranks, (str, bytes)) or not hasattr(ranks, "__len__") or not 1 <= len(ranks) <= abi.SA_RANK_Q_MAX:
-            raise SpecanError(abi.SA_EINVAL, f"ranks must be a sequence of 1..{abi.SA_RANK_Q_MAX} ints")
-        m = int(hi) - int(lo)
-        for v in ranks:
-            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) < m:
-                raise SpecanError(abi.SA_EINVAL, f"a rank must be an int in 0..{m - 1}")
-        return _field_code(field), tuple(int(v) for v in ranks)
+        ranks, _, _ = _rules(frames._rank_args, ranks, lo, hi, field)
+        return FIELDS[field], ranks
 
     @staticmethod
     def _quantile_ranks(q, lo, hi) -> tuple:
@@ -263,10 +236,7 @@ class Reductions:
         qs = q if hasattr(q, "__len__") and not isinstance(q, (str, bytes)) else (q,)
         if not 1 <= len(qs) <= abi.SA_RANK_Q_MAX:
             raise SpecanError(abi.SA_EINVAL, f"q must be a number or a sequence of 1..{abi.SA_RANK_Q_MAX} numbers")
-        try:
-            return tuple(frames.rank_of_quantile(v, int(hi) - int(lo)) for v in qs)
-        except ValueError as e:
-            raise SpecanError(abi.SA_EINVAL, str(e)) from None
+        return tuple(_rules(frames.rank_of_quantile, v, int(hi) - int(lo)) for v in qs)
 
     def _rank_out(self, R: int, q: int, out: Optional[torch.Tensor]) -> torch.Tensor:
         """``out`` of the order statistics of ``R`` rows, allocated when None: SA_ESHAPE where it is not the contiguous float32
@@ -328,18 +298,8 @@ class Reductions:
     def _hist_args(edges, group, bucket, lo, hi) -> tuple:
         """The one validation of the arguments of the level histogram: ``(log2 of the bucket, the edges as a tuple of float32
         values)``, or SA_EINVAL.  ``group`` may be None (all rows)."""
-        _ints(("bucket", bucket), ("lo", lo), ("hi", hi), *([("group", group)] if group is not None else []))
-        if group is not None and not 1 <= int(group) <= frames.HIST_GROUP_MAX:
-            raise SpecanError(abi.SA_EINVAL, f"group must be 1..{frames.HIST_GROUP_MAX}")
-        if int(bucket) not in frames.HIST_BUCKETS:
-            raise SpecanError(abi.SA_EINVAL, f"bucket must be one of {frames.HIST_BUCKETS}")
-        try:
-            keys = frames._hist_edge_keys(edges)
-        except ValueError as e:
-            raise SpecanError(abi.SA_EINVAL, str(e)) from None
-        if not 0 <= int(lo) < int(hi) <= SA_N or int(lo) % int(bucket) or int(hi) % int(bucket):
-            raise SpecanError(abi.SA_EINVAL, f"the range must be 0 <= lo < hi <= {SA_N}, both multiples of the bucket")
-        return int(bucket).bit_length() - 1, tuple(float(v) for v in keys.view(np.float32))
+        keys, _, bucket, _, _ = _rules(frames._hist_args, edges, group, bucket, lo, hi)
+        return bucket.bit_length() - 1, tuple(float(v) for v in keys.view(np.float32))
 
     def _hist_out(self, R: int, group, bucket: int, lo: int, hi: int, L: int, out: Optional[torch.Tensor]) -> tuple:
         """``(group, out)`` of the level histogram of ``R`` rows, ``group`` None meaning all of them and ``out`` allocated when
@@ -404,10 +364,7 @@ class Reductions:
     def _bands_args(bands, fracs, field) -> tuple:
         """The one validation of the arguments of the band power: ``(field code of include/specan_bands.h, the bands as a
         tuple of (lo, hi) int pairs, the fractions as a tuple of floats)``, or SA_EINVAL."""
-        try:
-            bands, fracs = frames._bands_args(bands, fracs, field)
-        except ValueError as e:
-            raise SpecanError(abi.SA_EINVAL, str(e)) from None
+        bands, fracs = _rules(frames._bands_args, bands, fracs, field)
         return FIELDS[field], bands, fracs
 
     def _bands_out(self, R: int, nb: int, nq: int, power: Optional[torch.Tensor], cross: Optional[torch.Tensor]) -> tuple:
@@ -478,13 +435,8 @@ class Reductions:
     def _mask_args(upper, lower, lo, hi, field) -> int:
         """The one validation of the scalar arguments of the mask test: the ``field`` code of include/specan_mask.h, or
         SA_EINVAL.  The limits are only counted here; :meth:`_mask_limits` looks at them."""
-        _ints(("lo", lo), ("hi", hi))
-        if not 0 <= int(lo) < int(hi) <= SA_N:
-            raise SpecanError(abi.SA_EINVAL, f"the range must be 0 <= lo < hi <= {SA_N}")
-        code = _field_code(field)
-        if upper is None and lower is None:
-            raise SpecanError(abi.SA_EINVAL, "upper and lower are both None: no limit at all")
-        return code
+        _rules(frames._mask_args, upper, lower, lo, hi, field)
+        return FIELDS[field]
 
     def _mask_limits(self, upper, lower) -> None:
         """SA_ESHAPE where a limit is neither None nor a contiguous float32 [16384] tensor on the handle's device."""
@@ -574,10 +526,7 @@ class Reductions:
     def _harm_args(order, span, lo, hi, fund, dc, top, field) -> tuple:
         """The one validation of the arguments of the harmonic analysis: ``(field code of include/specan_harm.h, the
         sa_harm_cfg with the defaults filled in)``, or SA_EINVAL."""
-        try:
-            cfg = frames._harm_args(order, span, lo, hi, fund, dc, top, field)
-        except ValueError as e:
-            raise SpecanError(abi.SA_EINVAL, str(e)) from None
+        cfg = _rules(frames._harm_args, order, span, lo, hi, fund, dc, top, field)
         return FIELDS[field], abi.HarmCfg(*cfg)
 
     def _harm_out(self, R: int, out: Optional[torch.Tensor]) -> torch.Tensor:
@@ -648,13 +597,10 @@ class Reductions:
     def _signals_args(k, threshold, lo, hi, gap, min_width, field) -> int:
         """The one validation of the arguments of the signal list: the ``field`` code of include/specan_signals.h, or
         SA_EINVAL.  Of a threshold per row only the dtype is looked at here; :meth:`_signals_out` looks at the rest."""
-        try:
-            frames._signals_args(k, lo, hi, gap, min_width, field)
-            if not isinstance(threshold, torch.Tensor):
-                frames._threshold_key(threshold)
-        except ValueError as e:
-            raise SpecanError(abi.SA_EINVAL, str(e)) from None
-        if isinstance(threshold, torch.Tensor) and threshold.dtype != torch.float32:
+        _rules(frames._signals_args, k, lo, hi, gap, min_width, field)
+        if not isinstance(threshold, torch.Tensor):
+            _rules(frames._threshold_key, threshold)
+        elif threshold.dtype != torch.float32:
             raise SpecanError(abi.SA_EINVAL, "a threshold per row must be a torch.float32 tensor")
         return FIELDS[field]
 
@@ -739,13 +685,9 @@ class Reductions:
         if (threshold is None) == (factor is None):
             raise SpecanError(abi.SA_EINVAL, "exactly one of threshold and factor must be given")
         if factor is not None:
-            if isinstance(factor, bool) or not isinstance(factor, (int, float, np.integer, np.floating)) \
-                    or not 0.0 < self._as_float32(factor) < float("inf"):
+            if not frames._is_number(factor) or not 0.0 < self._as_float32(factor) < float("inf"):
                 raise SpecanError(abi.SA_EINVAL, "factor must be a finite number above 0 as a float32")
-            try:
-                rank = frames.rank_of_quantile(q, int(hi) - int(lo))
-            except ValueError as e:
-                raise SpecanError(abi.SA_EINVAL, str(e)) from None
+            rank = _rules(frames.rank_of_quantile, q, int(hi) - int(lo))
 
         def reduce(t, field, outs):
             thr = threshold
@@ -760,13 +702,8 @@ class Reductions:
     def _cfar_args(train, guard, mode, what, lo, hi, field) -> tuple:
         """The one validation of the arguments of the CFAR normalisation: ``(field code, log2_train, mode code, what code)``
         of include/specan_cfar.h, or SA_EINVAL."""
-        _ints(("train", train), ("guard", guard), ("lo", lo), ("hi", hi))
-        code = _field_code(field)
-        try:
-            t, _, m, w, _, _ = frames._cfar_args(train, guard, mode, what, lo, hi, field)
-        except ValueError as e:
-            raise SpecanError(abi.SA_EINVAL, str(e)) from None
-        return code, t, m, w
+        t, _, m, w, _, _ = _rules(frames._cfar_args, train, guard, mode, what, lo, hi, field)
+        return FIELDS[field], t, m, w
 
     def _cfar_out(self, R: int, out: Optional[torch.Tensor]) -> torch.Tensor:
         """``out`` of the CFAR normalisation of ``R`` rows, allocated when None: SA_ESHAPE where it is not the contiguous

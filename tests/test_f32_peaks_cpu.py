@@ -201,7 +201,7 @@ def test_rows_are_independent_and_arguments_are_checked():
         for w, o in zip(whole, one):
             assert np.array_equal(np.ascontiguousarray(w[r:r + 1]).view(np.uint32), o.view(np.uint32))
     bad = [dict(k=0), dict(k=33), dict(k=True), dict(k=2.0), dict(threshold=-1.0), dict(threshold=-0.0),
-           dict(threshold=float("nan")), dict(lo=-1), dict(lo=5, hi=5), dict(hi=N + 1), dict(lo=1.0), dict(hi=True),
+           dict(threshold=float("nan")), dict(threshold="1"), dict(threshold=True), dict(lo=-1), dict(lo=5, hi=5), dict(hi=N + 1), dict(lo=1.0), dict(hi=True),
            dict(min_sep=0), dict(min_sep=N + 1), dict(min_sep=2.0), dict(min_sep=False)]
     for kw in bad:
         with pytest.raises(ValueError):

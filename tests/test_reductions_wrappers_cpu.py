@@ -9,7 +9,8 @@ host memory pass the input's check and the refusals behind it speak: the shapes,
 workspace.  Every case ends in a refusal, so no library is loaded and nothing is launched.
 
 The expected texts are those of the wrappers as they were before they shared one skeleton: the table was run against that
-version and its output committed; the rows of the last four methods came with their libraries.  A row is (call, code, message); ``LIM`` is an object no check may look at, ``X``, ``REC`` and
+version and its output committed; the rows of the last four methods came with their libraries, and six rows of ``cfar``
+with a bad ``field`` beside another fault when its field moved to the end of its rules, where every other method has it.  A row is (call, code, message); ``LIM`` is an object no check may look at, ``X``, ``REC`` and
 ``V`` good inputs ([2,16384], [2,16384,2] and [16384] float32) and ``BAD`` a tensor that is right for nothing.
 """
 import numpy as np
@@ -329,6 +330,12 @@ CASES = [
     ("bare.cfar(None, field='mag')", -1, "field must be None, 'peak' or 'power'"),
     ('bare.cfar(None, field=0)', -1, "field must be None, 'peak' or 'power'"),
     ("bare.cfar(None, train=True, field='mag')", -1, 'train must be an int'),
+    ("bare.cfar(None, train=3, field='mag')", -1, 'train must be one of (1, 2, 4, 8, 16, 32, 64)'),
+    ('bare.cfar(None, guard=65, field=0)', -1, 'guard must be 0..64'),
+    ("bare.cfar(None, mode='os', field='mag')", -1, "mode must be 'ca', 'go' or 'so'"),
+    ("bare.cfar(None, what='db', field='mag')", -1, "what must be 'ratio' or 'floor'"),
+    ("bare.cfar(None, lo=5, hi=5, field='mag')", -1, 'the range must be 0 <= lo < hi <= 16384'),
+    ("bare.cfar(None, lo=10, hi=15, field='mag')", -1, 'the range must hold 2 * guard + 2 bins or more'),
     ('bare.cfar(None)', -1, 'input must be a torch.float32 tensor'),
     ("bare.cfar(None, 64, 64, 'so', 'floor', 0, 130, 'power')", -1, 'input must be a torch.float32 tensor'),
     ("host.cfar(X, field='power')", -2, 'input must be a contiguous [B, 16384, 2] tensor'),
