@@ -4,7 +4,8 @@
 // pass over HBM (read 64 KiB, write 64 KiB per frame).  One 256-thread workgroup per frame.
 //
 // Shape of the computation (DESIGN.md sections 3-5):
-//   * LDS holds HALF a frame at a time (35 KiB per workgroup) so that four workgroups share a CU
+//   * LDS holds HALF a frame at a time (34 KiB of image, 38.3 KiB per workgroup with the scan scratch, the per-lane scan
+//     matrices and the pass-B twiddles) so that four workgroups share a CU
 //     (16 waves): every exchange is done in two index-split rounds.  The kernel is latency bound
 //     at lower occupancy (profiles/r1_phase_stamps_iir.txt).
 //   * thread t owns samples [64t, 64t+64) for the IIR as two chunks of 32 held as float pairs
@@ -43,10 +44,14 @@ constexpr int kLdsComplex = 16 * 272;                 // half-frame exchange ima
 constexpr int kScrOff = kLdsComplex * 8;              // scan scratch: 6 sections x 16 rows x float2
 constexpr int kSideOff = kScrOff + 6 * 16 * 8;        // one complex side slot (Z[6144])
 constexpr int kLaneOff = kSideOff + 16;               // (two complex side slots) then the per-lane matrices P2^i: 6 x 16 x float4
-constexpr int kLdsBytes = kLaneOff + 6 * 16 * 16;
-constexpr int kLdsOneRound = 65536;                   // the bypassed chain at small batches: a whole float32 frame at once
+constexpr int kTwbOff = kLaneOff + 6 * 16 * 16;       // the pass-B twiddles (SaF32Tables::twB): 8 x 16 x float4, 2 KiB
+constexpr int kTwbBytes = 8 * 16 * 16;
+constexpr int kLdsBytes = kTwbOff + kTwbBytes;        // 39 184 bytes: four workgroups per CU take 156 736 of 163 840
+constexpr int kOneRoundImage = 65536;                 // the bypassed chain at small batches: a whole float32 frame at once,
+constexpr int kLdsOneRound = kOneRoundImage + kTwbBytes;   // with the pass-B twiddles behind the image
 constexpr int kOneRoundMax = 512;                     // ... up to this batch size (launch_spectrum)
-static_assert(kLdsBytes <= kLdsOneRound, "the exchange images and side slots live inside the one-round image");
+static_assert(kTwbOff <= kOneRoundImage, "the exchange images and side slots live inside the one-round image");
+static_assert(4 * kLdsBytes <= 160 * 1024, "four workgroups share a CU's LDS");
 
 // The two-component scan state travels as ONE register pair and every 2x2 matrix is stored column-major (a column is
 // an aligned register pair): a matrix-vector product is two packed FMAs, column x broadcast component -- for wave-uniform
@@ -139,8 +144,8 @@ __device__ __forceinline__ void stage_in_chunks(const InT *__restrict__ xin, con
         for (int u = 0; u < 2; ++u) {                          // four samples of either chunk at a time
             float4 wa = make_float4(0.f, 0.f, 0.f, 0.f), wb = wa;
             if constexpr (!WINGEN) {                           // table window: win_t[g'][t] = window at 64 t + 4 g' .. + 3
-                wa = wint[(2 * g + u) * 256 + t];
-                wb = wint[(8 + 2 * g + u) * 256 + t];
+                wa = *at_bytes(wint + (2 * g + u) * 256, 16u * (unsigned)t);
+                wb = *at_bytes(wint + (8 + 2 * g + u) * 256, 16u * (unsigned)t);
             }
             const float fa[4] = {wa.x, wa.y, wa.z, wa.w}, fb[4] = {wb.x, wb.y, wb.z, wb.w};
 #pragma unroll
@@ -222,7 +227,7 @@ __device__ __forceinline__ void stage_in_chunks(const float *__restrict__ xin, f
                     }
                 }
             } else {
-                const float4 w = wint[(8 * h + g) * 256 + t];
+                const float4 w = *at_bytes(wint + (8 * h + g) * 256, 16u * (unsigned)t);
                 // mul_to: one v_mul_f32 straight into its half of the (chunk A, chunk B) pair.  Left to the
                 // SLP vectoriser the two rounds become v_pk_mul_f32 on re-paired operands: ~100 v_mov per thread.
                 if (h == 0) {
@@ -246,18 +251,42 @@ __device__ __forceinline__ void stage_in_chunks(const float *__restrict__ xin, f
 // chunk B (from zero state) accumulate as (z1, z2) pairs: nA += tap * y.x, nB += tap * y.y.  Eight taps in one statement
 // (the compiler pads a wait state after every asm statement whose output the next one reads; 32 single-tap statements =
 // 32 pads per section).  Two accumulator sets alternate: a dependent FMA every fourth instruction.
+// FIRST_A / FIRST_B: the statement holds the first tap of the (nAa, nBa) / (nAb, nBb) chains, which is then a packed
+// multiply into a fresh register pair (tap_mul beside tap_fma): no accumulator is zeroed first.  fma(t, y, 0) and t * y
+// round alike, so the sums are the same bits but for the sign of an exact zero.
+template <bool FIRST_A, bool FIRST_B>
 __device__ __forceinline__ void tap_fma8(v2f &nAa, v2f &nBa, v2f &nAb, v2f &nBb, const v2f (&tp)[8], const v2f (&y)[8])
 {
 #define SA_TAP(ACCA, ACCB, T, Y)                                                               \
     "v_pk_fma_f32 %[" ACCA "], %[" T "], %[" Y "], %[" ACCA "] op_sel:[0,0,0] op_sel_hi:[1,0,1]\n\t" \
     "v_pk_fma_f32 %[" ACCB "], %[" T "], %[" Y "], %[" ACCB "] op_sel:[0,1,0] op_sel_hi:[1,1,1]\n\t"
-    asm(SA_TAP("a1", "a2", "t0", "y0") SA_TAP("b1", "b2", "t1", "y1") SA_TAP("a1", "a2", "t2", "y2")
-            SA_TAP("b1", "b2", "t3", "y3") SA_TAP("a1", "a2", "t4", "y4") SA_TAP("b1", "b2", "t5", "y5")
-                SA_TAP("a1", "a2", "t6", "y6") SA_TAP("b1", "b2", "t7", "y7") ""
-        : [a1] "+v"(nAa), [a2] "+v"(nBa), [b1] "+v"(nAb), [b2] "+v"(nBb)
-        : [t0] "s"(tp[0]), [t1] "s"(tp[1]), [t2] "s"(tp[2]), [t3] "s"(tp[3]), [t4] "s"(tp[4]), [t5] "s"(tp[5]), [t6] "s"(tp[6]),
-          [t7] "s"(tp[7]), [y0] "v"(y[0]), [y1] "v"(y[1]), [y2] "v"(y[2]), [y3] "v"(y[3]), [y4] "v"(y[4]), [y5] "v"(y[5]),
-          [y6] "v"(y[6]), [y7] "v"(y[7]));
+#define SA_TAP_MUL(ACCA, ACCB, T, Y)                                       \
+    "v_pk_mul_f32 %[" ACCA "], %[" T "], %[" Y "] op_sel:[0,0] op_sel_hi:[1,0]\n\t" \
+    "v_pk_mul_f32 %[" ACCB "], %[" T "], %[" Y "] op_sel:[0,1] op_sel_hi:[1,1]\n\t"
+#define SA_TAPS_2_7                                                                                        \
+    SA_TAP("a1", "a2", "t2", "y2") SA_TAP("b1", "b2", "t3", "y3") SA_TAP("a1", "a2", "t4", "y4")           \
+        SA_TAP("b1", "b2", "t5", "y5") SA_TAP("a1", "a2", "t6", "y6") SA_TAP("b1", "b2", "t7", "y7") ""
+#define SA_TAP_INS                                                                                                          \
+    [t0] "s"(tp[0]), [t1] "s"(tp[1]), [t2] "s"(tp[2]), [t3] "s"(tp[3]), [t4] "s"(tp[4]), [t5] "s"(tp[5]), [t6] "s"(tp[6]),  \
+        [t7] "s"(tp[7]), [y0] "v"(y[0]), [y1] "v"(y[1]), [y2] "v"(y[2]), [y3] "v"(y[3]), [y4] "v"(y[4]), [y5] "v"(y[5]),    \
+        [y6] "v"(y[6]), [y7] "v"(y[7])
+    if constexpr (FIRST_A && FIRST_B)
+        asm(SA_TAP_MUL("a1", "a2", "t0", "y0") SA_TAP_MUL("b1", "b2", "t1", "y1") SA_TAPS_2_7
+            : [a1] "=&v"(nAa), [a2] "=&v"(nBa), [b1] "=&v"(nAb), [b2] "=&v"(nBb)
+            : SA_TAP_INS);
+    else if constexpr (FIRST_B)
+        asm(SA_TAP("a1", "a2", "t0", "y0") SA_TAP_MUL("b1", "b2", "t1", "y1") SA_TAPS_2_7
+            : [a1] "+v"(nAa), [a2] "+v"(nBa), [b1] "=&v"(nAb), [b2] "=&v"(nBb)
+            : SA_TAP_INS);
+    else {
+        static_assert(!FIRST_A, "the (nAa, nBa) chains never start alone");
+        asm(SA_TAP("a1", "a2", "t0", "y0") SA_TAP("b1", "b2", "t1", "y1") SA_TAPS_2_7
+            : [a1] "+v"(nAa), [a2] "+v"(nBa), [b1] "+v"(nAb), [b2] "+v"(nBb)
+            : SA_TAP_INS);
+    }
+#undef SA_TAP_INS
+#undef SA_TAPS_2_7
+#undef SA_TAP_MUL
 #undef SA_TAP
 }
 
@@ -267,24 +296,26 @@ __device__ __forceinline__ void tap_fma8(v2f &nAa, v2f &nBa, v2f &nAb, v2f &nBb,
 __device__ __forceinline__ void predict_chunk_ends(const v2f (&tp)[16], const v2f q0, const v2f q1, const v2f (&d)[32],
                                                    v2f &zA, v2f &zB)
 {
-    // four accumulators: each chain sees a dependent FMA every fourth instruction
-    v2f nAa = {0.f, 0.f}, nBa = {0.f, 0.f}, nAb = {0.f, 0.f}, nBb = {0.f, 0.f};
+    // four accumulators: each chain sees a dependent FMA every fourth instruction.  None is zeroed: the first tap of a
+    // chain is a multiply (tap_fma8<FIRST_A, FIRST_B>)
+    v2f nAa, nBa, nAb, nBb;
+    const auto y8_at = [&](int o, v2f (&y8)[8]) {
 #pragma unroll
-    for (int hh = 0; hh < 2; ++hh) {
-#pragma unroll
-        for (int j = 0; j < 16; j += 8) {
-            const v2f t8[8] = {tp[j], tp[j + 1], tp[j + 2], tp[j + 3], tp[j + 4], tp[j + 5], tp[j + 6], tp[j + 7]};
-            const int o = 16 * hh + j;
-            const v2f y8[8] = {d[o], d[o + 1], d[o + 2], d[o + 3], d[o + 4], d[o + 5], d[o + 6], d[o + 7]};
-            tap_fma8(nAa, nBa, nAb, nBb, t8, y8);
-        }
-        if (hh == 0) {
-            nAa = mv0_s(q0, q1, nAa + nAb);
-            nBa = mv0_s(q0, q1, nBa + nBb);
-            nAb = v2f{0.f, 0.f};
-            nBb = v2f{0.f, 0.f};
-        }
-    }
+        for (int i = 0; i < 8; ++i) y8[i] = d[o + i];
+    };
+    const v2f tlo[8] = {tp[0], tp[1], tp[2], tp[3], tp[4], tp[5], tp[6], tp[7]};
+    const v2f thi[8] = {tp[8], tp[9], tp[10], tp[11], tp[12], tp[13], tp[14], tp[15]};
+    v2f y8[8];
+    y8_at(0, y8);
+    tap_fma8<true, true>(nAa, nBa, nAb, nBb, tlo, y8);
+    y8_at(8, y8);
+    tap_fma8<false, false>(nAa, nBa, nAb, nBb, thi, y8);
+    nAa = mv0_s(q0, q1, nAa + nAb);
+    nBa = mv0_s(q0, q1, nBa + nBb);
+    y8_at(16, y8);
+    tap_fma8<false, true>(nAa, nBa, nAb, nBb, tlo, y8);
+    y8_at(24, y8);
+    tap_fma8<false, false>(nAa, nBa, nAb, nBb, thi, y8);
     zA = nAa + nAb;
     zB = nBa + nBb;
 }
@@ -427,7 +458,7 @@ __device__ __forceinline__ void iir_cascade(v2f (&d)[32], const PlanT &ka, const
     // the per-lane matrices P2^i of all sections into LDS (96 x 16 bytes; read behind each section's scan barrier)
     if (t < 16 * NSEC)
         reinterpret_cast<float4 *>(reinterpret_cast<unsigned char *>(scr) + (kLaneOff - kScrOff))[t] =
-            *reinterpret_cast<const float4 *>(&lt->p[t >> 4][t & 15][0]);
+            *at_bytes(reinterpret_cast<const float4 *>(&lt->p[0][0][0]), 16u * (unsigned)t);
     // predictor for the first section (later ones run after the previous section's recursion)
     const SecConsts c0 = load_consts(ka.sec[0]);
     v2f tp[16];
@@ -527,10 +558,21 @@ __device__ __forceinline__ void chain_frame(const InT *__restrict__ in, const fl
     if (threadIdx.x == 0 && g_sa_stamps) g_sa_stamps[(size_t)f * 16 + 13] = __builtin_amdgcn_s_memrealtime();
 #endif
     SA_STAMP(0);
+    // The pass-B twiddles depend on lane & 15 alone: 2 KiB, which every thread used to read as eight 16-byte loads per frame
+    // (32 KiB through L1).  Threads 0..127 request one quad each in front of the frame and park it in LDS (park_twb) where
+    // the stage-in waits for the frame anyway; pass B reads them as 16-byte LDS reads, behind the barriers of the exchange
+    // into pass B.  Every word of the table is written before it is read.
+    float4 *twb_lds = reinterpret_cast<float4 *>(smem + (ONE_ROUND ? kOneRoundImage : kTwbOff));
+    float4 twb_mine = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (t < kTwbBytes / 16) twb_mine = twB[t];
+    const auto park_twb = [&] {
+        if (t < kTwbBytes / 16) twb_lds[t] = twb_mine;
+    };
 
     if constexpr (IIR) {
         v2f d[32];
         stage_in_chunks<WINGEN>(xin, in_scale, reinterpret_cast<const float4 *>(lanetab->win_t), lanetab, smem, t, d);
+        park_twb();
         SA_STAMP(1);
         iir_cascade<NSEC, UNIT>(d, ka, lanetab, scr, t);
         SA_STAMP(2);
@@ -571,11 +613,12 @@ __device__ __forceinline__ void chain_frame(const InT *__restrict__ in, const fl
 #pragma unroll
         for (int i = 0; i < kSlabs; ++i) {
             const int n = wave * kSlabs + i;
-            const InT *src = xin + n * (64 * kUnit) + lane * kUnit;
+            const InT *src = at_bytes(xin + (uniform_wave(wave) * kSlabs + i) * (64 * kUnit), 16u * (unsigned)lane);
             __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)src,
                                              (__attribute__((address_space(3))) void *)(smem + n * 1024), 16, 0, SA_DMA_AUX);
         }
         __builtin_amdgcn_s_setprio(0);
+        park_twb();               // requested ahead of the frame: arrives first, and the barrier orders the write too
         __syncthreads();
 #pragma unroll
         for (int pp = 0; pp < 16; ++pp) {
@@ -600,11 +643,12 @@ __device__ __forceinline__ void chain_frame(const InT *__restrict__ in, const fl
 #pragma unroll
             for (int i = 0; i < kSlabs; ++i) {
                 const int n = wave * kSlabs + i;
-                const float *src = xin + h * 8192 + n * 256 + lane * 4;
+                const float *src = at_bytes(xin + h * 8192 + (uniform_wave(wave) * kSlabs + i) * 256, 16u * (unsigned)lane);
                 __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)src,
                                                  (__attribute__((address_space(3))) void *)(smem + n * 1024), 16, 0, SA_DMA_AUX);
             }
             __builtin_amdgcn_s_setprio(0);
+            if (h == 0) park_twb();   // requested ahead of the frame: arrives first, and the barrier orders the write too
             __syncthreads();          // (the round's window values requested in front of this barrier: 2 % slower, round 4)
 #pragma unroll
             for (int pp = 0; pp < kPairs; ++pp) {
@@ -626,7 +670,7 @@ __device__ __forceinline__ void chain_frame(const InT *__restrict__ in, const fl
     // 24 KiB of anchors per frame, and the loads no longer sit between the butterflies and the exchange.
     float4 an[5];
 #pragma unroll
-    for (int i = 0; i < 5; ++i) an[i] = twT[i * 256 + t];
+    for (int i = 0; i < 5; ++i) an[i] = *at_bytes(twT + i * 256, 16u * (unsigned)t);
     // The split-step anchors W_16384^(4 t), W_16384^(4 (t + 1)) ride along for the full-spectrum output (round 4: requested
     // right before the split step their L2 round trip was exposed once per frame -- 103.8 -> 97.0 us on the bypassed chain
     // at B = 4096, 11.5 -> 10.8 us at B = 256, -1 % with the cascade, gpurun_out/ab_an5.txt).  The half-spectrum variants
@@ -634,7 +678,7 @@ __device__ __forceinline__ void chain_frame(const InT *__restrict__ in, const fl
     // holds no staging registers either, takes the early one.
     constexpr bool AN5_EARLY = OUT == SA_OUT_MAG_FULL || OUT == SA_OUT_MARKER;
     float4 an5_early = make_float4(0.f, 0.f, 0.f, 0.f);
-    if constexpr (AN5_EARLY) an5_early = twT[5 * 256 + t];
+    if constexpr (AN5_EARLY) an5_early = *at_bytes(twT + 5 * 256, 16u * (unsigned)t);
     safft::fft_dit<32>(a);
     {
         const cf wb[8] = {{1.f, 0.f}, {an[0].x, an[0].y}, {an[0].z, an[0].w}, {an[1].x, an[1].y},
@@ -666,7 +710,7 @@ __device__ __forceinline__ void chain_frame(const InT *__restrict__ in, const fl
     safft::fft_dit<16>(p[1]);
 #pragma unroll
     for (int pp = 0; pp < 8; ++pp) {                       // twB4[pp][b] = (W_256^(2pp * b), W_256^((2pp+1) * b))
-        const float4 w = twB[pp * 16 + lo];
+        const float4 w = twb_lds[pp * 16 + lo];
         if (pp > 0) {
             p[0][2 * pp] = safft::cmul(p[0][2 * pp], {w.x, w.y});
             p[1][2 * pp] = safft::cmul(p[1][2 * pp], {w.x, w.y});
@@ -705,7 +749,7 @@ __device__ __forceinline__ void chain_frame(const InT *__restrict__ in, const fl
     int ts = t;
     asm volatile("" : "+v"(ts));
     float4 an5 = an5_early;
-    if constexpr (!AN5_EARLY) an5 = twT[5 * 256 + ts];
+    if constexpr (!AN5_EARLY) an5 = *at_bytes(twT + 5 * 256, 16u * (unsigned)ts);
     const cf wP = {an5.x, an5.y}, wPn = {an5.z, an5.w};
     MarkerAcc mk = {-1.f, SA_NPTS, 0.f};                   // SA_OUT_MARKER: this thread's part of the record
     // ---- natural-order image + split step, two rounds: round 0 = d in {0..3,12..15} (bins k < 2048
@@ -769,7 +813,7 @@ __device__ __forceinline__ void chain_frame(const InT *__restrict__ in, const fl
             if constexpr (OUT == SA_OUT_MARKER) {
                 marker_group(R, I, k0, __builtin_amdgcn_readfirstlane(k0), mlo, mhi, mk);     // lane 0: the wave's first group
             } else if constexpr (!HALF) {
-                split_store<OUT>(R, I, out, f, k0);
+                split_store<OUT>(R, I, out, f, k0, t);
             } else if constexpr (OUT == SA_OUT_SPEC_HALF) {
 #pragma unroll
                 for (int e = 0; e < 5; ++e) {

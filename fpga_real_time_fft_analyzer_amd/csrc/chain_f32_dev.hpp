@@ -2,6 +2,7 @@
 // shifts, nontemporal stores, the row image that stages frames in and out of the IIR kernels, the split step of the
 // packed real FFT, its output layouts and the marker reduction.
 #pragma once
+#include <type_traits>
 #include "sa_common.hpp"
 #include "fft_regs.hpp"
 #include "p12_dev.hpp"
@@ -48,6 +49,29 @@ __device__ __forceinline__ void lds_barrier()
 }
 
 // ---------------------------------------------------------------------------------------------
+// Global addresses with a wave-uniform base (a frame, an output row, a table): the base stays in a scalar register pair
+// and a lane contributes one unsigned 32-bit byte offset, so that the access takes the scalar-base form of global_load /
+// global_store / LDS-DMA with the compile-time part as its immediate offset.  Formed as pointer + signed index the same
+// address costs a 64-bit vector add (v_lshl_add_u64 or a carry pair) per access and a register pair per address held.
+// `base` MUST be the same in every lane of the wave: the scalar constraint below takes one lane's value for all.
+template <typename T>
+__device__ __forceinline__ T *at_bytes(T *base, unsigned lane_bytes)
+{
+    using Byte = std::conditional_t<std::is_const_v<T>, const unsigned char, unsigned char>;
+    // the base as it stands, in a scalar pair: left transparent, the compiler adds the lane's offset to the common part of
+    // several bases first and every access is a 64-bit vector add again.  Two scalar adds per base instead.
+    // The offset likewise as the 32-bit register it is: widened where it is computed (the compiler knows 16 t fits) it
+    // reaches the access as a 64-bit pair, which the scalar-base form does not take.
+    // Behind the opaque copy the pointer is global memory by this cast alone (else: flat accesses).
+    asm("" : "+s"(base));
+    asm("" : "+v"(lane_bytes));
+    using GlobalByte = __attribute__((address_space(1))) Byte;
+    return reinterpret_cast<T *>((Byte *)((GlobalByte *)reinterpret_cast<Byte *>(base) + lane_bytes));
+}
+// the wave index as the scalar it is (the compiler takes threadIdx.x >> 6 for a per-lane value)
+__device__ __forceinline__ int uniform_wave(int wave) { return __builtin_amdgcn_readfirstlane(wave); }
+
+// ---------------------------------------------------------------------------------------------
 // DPP helpers: value of the lane `n` to the left inside the 16-lane row, 0 when there is none.
 template <int N>
 __device__ __forceinline__ float row_shr(float v)
@@ -90,14 +114,19 @@ __device__ __forceinline__ int row_swizzle(int r) { return (r >> 1) & 7; }
 template <typename T>
 __device__ __forceinline__ void dma_rows_impl(const T *x, int h, unsigned char *smem, int lane, int wave)
 {
-    const int rl = lane >> 3;                                  // row inside the slab
+    // Slab n = 8 wave + i holds rows r = 8n + rl, rl = lane >> 3, and row_swizzle(r) = 4 (i & 1) | (rl >> 1): the lane's
+    // source is  x + (512 wave + 64 i + 8 rl) row bytes + h * 32 elements + 16 ((lane & 7) ^ row_swizzle(r)), of which only
+    //   v0 = rl * row bytes + 16 ((lane & 7) ^ (rl >> 1))     (even i;  odd i: v0 ^ 64)
+    // differs from lane to lane (at_bytes): two registers instead of eight 64-bit addresses
+    constexpr int kRow = 64 * (int)sizeof(T);
+    const int rl = lane >> 3;
+    const unsigned v0 = (unsigned)(rl * kRow + (((lane & 7) ^ (rl >> 1)) << 4)), v1 = v0 ^ 64u;
+    const T *xw = x + uniform_wave(wave) * (64 * 64) + h * 32;
     __builtin_amdgcn_s_setprio(3);
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
         const int n = wave * 8 + i;                            // slab: rows 8n .. 8n+7
-        const int r = 8 * n + rl;
-        const int lc = (lane & 7) ^ row_swizzle(r);
-        const T *src = x + r * 64 + h * 32 + lc * (16 / (int)sizeof(T));
+        const T *src = at_bytes(xw + i * (8 * 64), (i & 1) ? v1 : v0);
         __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)src,
                                          (__attribute__((address_space(3))) void *)(smem + n * 1024), 16, 0, SA_DMA_AUX);
     }
@@ -133,13 +162,15 @@ __device__ __forceinline__ int p12_row_swizzle(int r) { return (r >> 3) & 1; }
 
 __device__ __forceinline__ void dma_rows(const SaP12 *x, unsigned char *smem, int lane, int wave)
 {
+    const int uw = uniform_wave(wave);
     __builtin_amdgcn_s_setprio(3);
 #pragma unroll
     for (int i = 0; i < 6; ++i) {
         const int n = wave * 6 + i;                            // slab: slots 64n .. 64n+63
         const int s = 64 * n + lane;                           // the slot this lane fills, of row s / 6
-        const int u = s ^ p12_row_swizzle(s / 6);
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(x + 16 * u),
+        // unit u = s ^ swizzle = 64 n + (lane ^ swizzle): the slab's KiB is wave-uniform, the lane's part 16 (lane ^ swizzle)
+        const unsigned v = (unsigned)((lane ^ p12_row_swizzle(s / 6)) << 4);
+        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)at_bytes(x + 1024 * (uw * 6 + i), v),
                                          (__attribute__((address_space(3))) void *)(smem + n * 1024), 16, 0, SA_DMA_AUX);
     }
     __builtin_amdgcn_s_setprio(0);
@@ -288,7 +319,7 @@ __device__ __forceinline__ void split_eval(const cf zk, const cf zm, const cf w,
 //   [8192+k0 ..] = |Q0..3|        [8192-k0-4 ..  ] = |Q4..1|
 // Every bin of the frame is written exactly once over the 1024 groups.
 template <int OUT>
-__device__ __forceinline__ void split_store(const cf (&R)[5], const cf (&I)[5], void *__restrict__ out, int f, int k0)
+__device__ __forceinline__ void split_store(const cf (&R)[5], const cf (&I)[5], void *__restrict__ out, int f, int k0, int t)
 {
     if constexpr (OUT == SA_OUT_MAG_FULL || OUT == SA_OUT_MAG_HALF) {
         float mp[5], mq[5];
@@ -299,11 +330,15 @@ __device__ __forceinline__ void split_store(const cf (&R)[5], const cf (&I)[5], 
             mq[e] = fast_sqrt(m2.y);
         }
         if constexpr (OUT == SA_OUT_MAG_FULL) {
+            // k0 = kc + 4 t with kc the same for every thread: the row and kc make four scalar bases, and the thread adds
+            // 16 t to the ascending streams and 16 (255 - t) to the descending ones (at_bytes)
             float *o = reinterpret_cast<float *>(out) + (size_t)f * SA_NPTS;
-            store_nt(o + k0, mp[0], mp[1], mp[2], mp[3]);
-            store_nt(o + SA_NPTS - k0 - 4, mp[4], mp[3], mp[2], mp[1]);
-            store_nt(o + SA_MC + k0, mq[0], mq[1], mq[2], mq[3]);
-            store_nt(o + SA_MC - k0 - 4, mq[4], mq[3], mq[2], mq[1]);
+            const unsigned up = 16u * (unsigned)t, dn = 16u * (unsigned)(SA_NTHREADS - 1 - t);
+            const int kc = k0 - 4 * t;
+            store_nt(at_bytes(o + kc, up), mp[0], mp[1], mp[2], mp[3]);
+            store_nt(at_bytes(o + (SA_NPTS - 4 * SA_NTHREADS - kc), dn), mp[4], mp[3], mp[2], mp[1]);
+            store_nt(at_bytes(o + (SA_MC + kc), up), mq[0], mq[1], mq[2], mq[3]);
+            store_nt(at_bytes(o + (SA_MC - 4 * SA_NTHREADS - kc), dn), mq[4], mq[3], mq[2], mq[1]);
         } else {
             float *o = reinterpret_cast<float *>(out) + (size_t)f * (SA_MC + 1);     // rows are not 16-byte aligned
 #pragma unroll

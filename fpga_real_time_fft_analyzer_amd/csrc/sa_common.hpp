@@ -123,7 +123,8 @@ struct SaF32Tables {               // the windows and twiddles are filled by sa_
     const float4 *twT;         // [6][256]   per-thread twiddle anchors, row i holds two complex values for thread t:
                                //   rows 0..3: W^(1t) W^(2t) | W^(3t) W^(4t) | W^(5t) W^(6t) | W^(7t) W^(8t)   (W = W_8192)
                                //   row 4:     W^(16t) W^(24t)          row 5: W_16384^(4t), W_16384^(4((t+1) & 255))
-    const float4 *twB;         // [8][16]    (W_256^(2p*b),   W_256^((2p+1)*b))
+    const float4 *twB;         // [8][16]    (W_256^(2p*b),   W_256^((2p+1)*b)): 2 KiB, which every workgroup copies into LDS
+                               //            once (chain_f32.hpp, park_twb) and pass B reads there by b = lane & 15
     const float2 *twC;         // [25]       W_16384^(1024 blk + e), index blk * 5 + e, blk = 2r + jj (+1): the wave-uniform
                                //            factor of the split-step twiddles
     const SaIirLaneTab *lanetab;   // device

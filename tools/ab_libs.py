@@ -2,7 +2,8 @@
 """A/B timing of alternative builds of the library in one process, interleaved rounds.
 usage: [SA_B=frames] ab_libs.py libA.so libB.so[@ovD] ...   (paths relative to the package dir; "@ov2" = overlap depth 2
 on that handle, sa_set_overlap: timed with a flush before the final synchronisation; SA_B = batch size, default 4096:
-the rotating buffers are slices of one 4096-frame pool, so small batches still stream from HBM)"""
+the rotating buffers are slices of one 4096-frame pool, so small batches still stream from HBM; SA_ROUNDS = timed blocks
+per build, default 12, the builds alternating block by block)"""
 import ctypes as C
 import os
 import sys
@@ -66,7 +67,7 @@ for name in sys.argv[1:]:
         name = f"{name}#{len(libs)}"            # the same build on a further handle
     libs.append((name, L, h))
 st = torch.cuda.current_stream().cuda_stream
-ROUNDS, REPS = 12, (40 if B >= 4096 else 200)
+ROUNDS, REPS = int(os.environ.get("SA_ROUNDS", "12")), (40 if B >= 4096 else 200)    # launches per side: ROUNDS * REPS
 for mode in (0xA1, 0xB1):
     res, ref = {}, None
     # sustained pre-warm so that every build is measured at the settled clock
