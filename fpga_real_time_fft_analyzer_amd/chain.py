@@ -131,8 +131,6 @@ Q15_FOLD_CHAIN = _Chain(_SPECTRA_OUT, {torch.int16: _form((SA_N, 2), _SPECTRA_OU
 # the fold of float magnitudes (include/specan_fold.h; fold_mag_f32, spectra_f32): a call of libspecan_fold.so, which takes
 # no handle and is no row of the tables above -- the float chain's own call writes the magnitudes it reads
 FOLD_GROUPS, FOLD_BUCKETS = frames.FOLD_GROUPS, frames.FOLD_BUCKETS         # 1 .. 128 and 1 .. 64: the mirror's, defined once
-# the `field` codes of find_peaks, order_stats, band_power, mask_test and harmonics: one table, by the name each had here
-_PEAK_FIELDS = _RANK_FIELDS = _BANDS_FIELDS = _MASK_FIELDS = _HARM_FIELDS = reductions.FIELDS
 _HARM_WORDS = reductions.HARM_WORDS
 
 

@@ -14,7 +14,7 @@ Rows.  Each row comes from a family that is itself drawn: (a) exp(U(-20, 20)); (
 the points +inf, -0.0, a float32 denormal or negative; (f) a constant 0, 1 or 3.5; (g) exp(U(-3, 3)) with one NaN.  Every header
 defines the result for a NaN (include/specan_x.h: a NaN's key lies above +inf's; the sums and quotients it enters are NaNs, a
 crossing -1), so (g) is drawn for all nine.  R is 1..8; for the histogram a multiple of the group, and in a few draws 64..130
-rows in one group over a narrow range, which takes the sliced form (offset_cases.hist_slices).
+rows in one group over a narrow range, which takes the sliced form (hist_slices).
 
 Integers.  20 % an end of the valid range, 30 % at or one off a multiple of an ownership size of that library's kernel (SIZES:
 the 4-bin quads, 2-bin record units, 64-bin mask words, 128- and 256-bin wave tiles and 512- and 1024-bin rounds of the
@@ -398,6 +398,10 @@ def outputs(name, R, kw):
     return [("out", (R, N), "float32")]
 
 
+# what a method allocates itself and only returns, one element per row: library -> (name, place in the returned tuple, dtype)
+RETURNED = {"peaks": (("count", 2, "int32"),)}
+
+
 def result(name, arrays, returned, kw):
     """What the device wrote, in the form of mirror(): ``arrays`` is argument -> the host copy of that output tensor, in the
     dtype and shape of outputs(); ``returned`` the host copies of what the method returned (peaks: its count is the third)."""
@@ -494,17 +498,29 @@ def plain_arrays(result_):
 
 
 # ----------------------------------------------------------------------------------------------- what a draw launches
+def hist_slices(rows, group, bucket, lo=0, hi=N):
+    """The row slices of a group, as sa_hist_f32 (csrc/hist_f32.hip) decides them from kHistOwnersFew = 256, kHistOwnersAim =
+    512 and kHistSliceRowsMin = 32 of csrc/sa_hist.hpp: G x tiles workgroups own their counters; below 256 of them a group
+    of 64 rows or more is cut so that about 512 workgroups run."""
+    tile = 256
+    tiles = (hi - 1) // tile - lo // tile + 1
+    owners = rows // group * tiles
+    if owners >= 256:
+        return 1
+    s = min(-(-512 // owners), group // 32)
+    return s if s >= 2 else 1
+
+
 def kernels(name, R, field, kw):
     """The kernel instantiations a draw launches, as kernel_inventory.key_of keys them."""
     code = FIELDS.index(field)
     if name == "fold":
         return (f"fold_mag_f32_kernel<{kw['bucket'].bit_length() - 1}>",)
     if name == "hist":
-        import offset_cases                                          # its rule of when the rows of a group are cut into slices
         levels, steps = len(kw["edges"]) + 1, 1
         while (1 << steps) < levels:
             steps += 1
-        sliced = offset_cases.hist_slices(R, kw["group"] or R, kw["bucket"], kw["lo"], kw["hi"]) > 1
+        sliced = hist_slices(R, kw["group"] or R, kw["bucket"], kw["lo"], kw["hi"]) > 1
         return (("hist_zero_kernel",) if sliced else ()) + (f"hist_f32_kernel<{steps}>",)
     if name == "bands":
         return (f"bands_f32_kernel<{code}, {'true' if len(kw['fracs']) > 0 else 'false'}>",)

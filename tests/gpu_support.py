@@ -1,8 +1,11 @@
 """Shared by the GPU test modules (a plain module, like structured_cases.py): the fixtures every one of them asks for,
 imported by name into the module that uses them, and the helpers that were the same in two or more of them."""
+import copy
+
 import numpy as np
 import pytest
 
+import drawn_cases as dc
 from conftest import N
 from native import Lds, gpu_helper
 
@@ -31,6 +34,44 @@ def ch(chain_cls):
 def to_device(torch_mod, a):
     a = np.ascontiguousarray(a)
     return torch_mod.from_numpy(a if a.flags.writeable else a.copy()).cuda()       # a shared read-only batch is copied
+
+
+COMPOSED = {"fold": "spectra_f32", "peaks": "peak_table_f32", "rank": "noise_floor_f32", "hist": "persistence_f32",
+            "bands": "channel_power_f32", "mask": "mask_trigger_f32", "harm": "harmonics_f32", "signals": "signals_f32",
+            "cfar": "cfar_f32"}
+
+
+class ReductionCall:
+    """One call of a reduction library's method (drawn_cases.METHODS), prepared so that making it is nothing but the method
+    call: the input resident, the arguments objects of its own (a limit line or a threshold per row on the device, the rest
+    copied) and an output of 0xFF bytes for every ``out=`` argument.  ``composed``: the arguments of the composed call that
+    stands for the plain call with ``kw``, ``x`` then being the frames."""
+
+    def __init__(self, torch, name, x, field, kw, composed=None):
+        self.name, self.x, self.kw = name, x, kw
+        self.method = dc.METHODS[name] if composed is None else COMPOSED[name]
+        self.args = {k: to_device(torch, v) if isinstance(v, np.ndarray) else copy.deepcopy(v)
+                     for k, v in (kw if composed is None else composed).items()}
+        if composed is None and name in dc.HAS_FIELD:
+            self.args["field"] = field
+        self.held = {}
+        for arg, shape, dtype in dc.outputs(name, x.shape[0], kw):
+            raw = torch.full((int(np.prod(shape)) * np.dtype(dtype).itemsize,), 0xFF, dtype=torch.uint8, device="cuda")
+            self.held[arg] = (raw, shape, dtype)
+            self.args[arg] = raw.view(getattr(torch, dtype)).view(shape)
+        self.returned = None
+
+    def launch(self, ch):
+        """The call, nothing waited for; the arguments are dropped with it: what they held is the kernel's or nobody's."""
+        self.returned = getattr(ch, self.method)(self.x, **self.args)
+        del self.args
+        return self
+
+    def result(self):
+        """The host copies of what the call wrote, in the form of drawn_cases.mirror()."""
+        arrays = {arg: raw.cpu().numpy().view(dtype).reshape(shape) for arg, (raw, shape, dtype) in self.held.items()}
+        back = self.returned if isinstance(self.returned, tuple) else ()
+        return dc.result(self.name, arrays, tuple(None if t is None else t.contiguous().cpu().numpy() for t in back), self.kw)
 
 
 def synth(B, seed):

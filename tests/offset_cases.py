@@ -13,7 +13,11 @@ chain.py name it (traces_q15: the bucket W, with a group the pair (W, A); spectr
 call has one output; `setup` the filter setup -- a name of q15_cases.SETUPS for the integer chain, of FLOAT_SETUPS for the
 float chain -- and `precision` that of the float chain; `A` the frames (rows) per output row; `hop` the stride of a stream
 in samples; `params` the further arguments of a handle-free call.  `P` is the period of the input in rows and `B` the batch,
-both made by the rules of period() and batch() and held to them, from the outside, by the guard.
+both made by the rules of period() and batch() and held to them, from the outside, by the guard; `recipe` names the rows of
+one period (RECIPES), "" for the draw of the input form.
+
+What a handle-free call is -- its method, its outputs, the kernels it launches, its mirror -- is said once, for all nine
+reduction libraries, by tests/drawn_cases.py; its entry point is the one data-plane name of the library's signature table.
 
 A tensor of a case is (bytes per row, rows): a row is what belongs to one output row, A frames where the call folds groups
 of A frames.  Every byte count is derived from abi.py and chain.py (output_spec, the input forms' row lengths,
@@ -23,6 +27,9 @@ import collections
 import math
 import re
 
+import numpy as np
+
+import drawn_cases as dc
 import kernel_inventory as ki
 import structured_cases
 from fpga_real_time_fft_analyzer_amd import abi, chain
@@ -54,22 +61,51 @@ _Q15_TABLES = {"process_q15": "Q15_CHAIN", "filter_q15": "Q15_WINDOW_CHAIN", "sp
                "fold_iq_q15": "Q15_FOLD_CHAIN"}
 CHAIN_TABLES = ("FLOAT_CHAIN", "Q15_CHAIN", "Q15_TRACE_CHAIN", "Q15_TRACE_AVG_CHAIN", "Q15_WINDOW_CHAIN", "Q15_SPECTRA_CHAIN",
                 "Q15_FOLD_CHAIN")
-HANDLE_FREE = {"fold_mag_f32": "sa_fold_mag_f32", "find_peaks": "sa_peaks_f32", "order_stats": "sa_rank_f32",
-               "level_hist": "sa_hist_f32"}
+LIBRARY = {method: name for name, method in dc.METHODS.items()}      # the method of a handle-free call -> its library
 HIST_EDGES = (0.2, 0.4, 0.6, 0.8)            # five levels; the data of the merged case stays below the top edge
 HIST_ABOVE = 1.0                             # ... except the rows that start at or beyond 2^32, which hold this
 
-Case = collections.namedtuple("Case", "id call form kind setup precision A hop params P B")
+# The rows of one period where the draw of the input form, 0.001 + 0.78 u, would leave a library's result without content:
+# name -> (noise, plants).  Noise "uniform" is that draw, "exp" is exp(8 u - 4).  A plant (bin, step, width, value) sets the
+# point `bin + step r` of row r -- a place of the row's own -- to `value`, with a width the point `1 + r % width` bins further.
+RECIPES = {"tone": ("uniform", ((100, 7, 0, 5.0),)),                # harm: a fundamental per row
+           # signals: three segments per row, each of the row's own place and width, above every threshold of the case
+           "segments": ("uniform", tuple(p for j in range(3) for p in ((100 + 3000 * j, 7, 0, 5.0), (100 + 3000 * j, 7, 3, 6.0)))),
+           "carrier": ("exp", ((100, 13, 0, 500.0),))}             # cfar: exponential noise, a carrier per row
+
+Case = collections.namedtuple("Case", "id call form kind setup precision A hop params P B recipe")
 
 
 # ------------------------------------------------------------------------------------------------------- bytes per row
+def _table(call, kind):
+    if call in ("process_f32", "markers"):
+        return "FLOAT_CHAIN"
+    if call == "traces_q15":
+        return "Q15_TRACE_AVG_CHAIN" if isinstance(kind, tuple) else "Q15_TRACE_CHAIN"
+    return _Q15_TABLES.get(call)
+
+
 def chain_table(case):
     """The name of the chain table of chain.py a case's call goes through; None for a handle-free call."""
-    if case.call in ("process_f32", "markers"):
-        return "FLOAT_CHAIN"
-    if case.call == "traces_q15":
-        return "Q15_TRACE_AVG_CHAIN" if isinstance(case.kind, tuple) else "Q15_TRACE_CHAIN"
-    return _Q15_TABLES.get(case.call)
+    return _table(case.call, case.kind)
+
+
+def arguments(case, R, only=None):
+    """(library, field, kw) of a handle-free case's call on R frames, as drawn_cases takes them: an argument of one entry per
+    row of the period -- a threshold per row -- is tiled to the R rows like the input.  `only`: of those rows these alone."""
+    return (LIBRARY[case.call],) + _arguments(case.params, case.P // case.A, R // case.A, only)
+
+
+def _arguments(params, period_rows, rows, only=None):
+    def tiled(v):
+        v = np.resize(v, (rows,) + v.shape[1:])
+        return v if only is None else v[list(only)]
+    return params.get("field"), {k: tiled(v) if _per_row(v, period_rows) else v for k, v in params.items() if k != "field"}
+
+
+def _per_row(v, period_rows):
+    """No argument has a fixed extent of a period's rows (a limit line has N points)."""
+    return isinstance(v, np.ndarray) and v.shape[0] == period_rows
 
 
 def _prod(shape):
@@ -95,37 +131,39 @@ def _torch_name(dtype):
     return str(dtype).replace("torch.", "")
 
 
-def out_row_bytes(call, kind, params):
-    """Bytes of one row of `out`: from chain.output_spec where the call has a chain table, else from the arguments."""
-    table = chain_table(Case(None, call, None, kind, None, None, None, None, None, None, None))
-    if table is not None:
-        ch = getattr(chain, table)
-        per_row = ch.output(kind)[3]
-        shape, dtype = chain.output_spec(ch, kind, per_row)
-        assert shape[0] == 1
-        return _prod(shape[1:]) * ITEMSIZE[_torch_name(dtype)]
-    if call == "fold_mag_f32":
-        return N // params["bucket"] * 2 * ITEMSIZE["float32"]
-    if call == "find_peaks":
-        return params["k"] * 2 * ITEMSIZE["int32"]
-    if call == "order_stats":
-        return len(params["ranks"]) * ITEMSIZE["float32"]
-    assert call == "level_hist", call
-    return N // params["bucket"] * (len(HIST_EDGES) + 1) * ITEMSIZE["uint32"]
+def out_row_bytes(table, kind):
+    """Bytes of one row of `out` of a call that has a chain table, from chain.output_spec."""
+    ch = getattr(chain, table)
+    per_row = ch.output(kind)[3]
+    shape, dtype = chain.output_spec(ch, kind, per_row)
+    assert shape[0] == 1
+    return _prod(shape[1:]) * ITEMSIZE[_torch_name(dtype)]
+
+
+def _handle_free_tensors(name, A, params):
+    """The tensors beside the input that grow with the batch of a handle-free call: of drawn_cases.outputs those with one
+    row per row -- no fixed extent (the 4 words of the mask summary, the 1 group of the merged histogram) equals the rows of
+    a period --, what the method only returns, and an argument per row."""
+    m = period(A) // A
+    _, kw = _arguments(params, m, m)
+    t = {arg: _prod(shape[1:]) * np.dtype(dtype).itemsize for arg, shape, dtype in dc.outputs(name, m * A, kw) if shape[0] == m}
+    t.update({arg: np.dtype(dtype).itemsize for arg, _, dtype in dc.RETURNED.get(name, ())})
+    t.update({k: v[0].nbytes for k, v in kw.items() if _per_row(v, m)})
+    return t
 
 
 def row_tensors(call, form, kind, setup, precision, A, hop, params):
-    """name -> bytes per row of every tensor of the call that grows with the batch, a row being A frames: "in", "out", and the
-    handle's workspaces -- "ws_q15" (the cascade's int16 frames in front of the FFT), "ws_f64" (the float64-state
-    cascade's float32 frames in front of the bypassed chain), "ws_trace" (the partial records of the grouped trace),
-    "ws_iq" (the IQ frames of spectra_q15).  The merged histogram (group None) is one output row of all B rows: its input
-    is counted row by row and its output does not grow."""
+    """name -> bytes per row of every tensor of the call that grows with the batch, a row being A frames: "in", the outputs by
+    the names of their arguments ("out"; bands: "power" and "cross"; signals: "out", "stats" and the "threshold" per row; the
+    "count" find_peaks returns), and the handle's workspaces -- "ws_q15" (the cascade's int16 frames in front of the FFT),
+    "ws_f64" (the float64-state cascade's float32 frames in front of the bypassed chain), "ws_trace" (the partial records of
+    the grouped trace), "ws_iq" (the IQ frames of spectra_q15).  The merged histogram (group None) is one output row of all
+    B rows: its input is counted row by row and its output does not grow."""
     t = {"in": A * frame_stride_bytes(form, hop)}
-    if call == "level_hist" and params["group"] is None:
+    if call in LIBRARY:
+        t.update(_handle_free_tensors(LIBRARY[call], A, params))
         return t
-    t["out"] = out_row_bytes(call, kind, params)
-    if call == "find_peaks":
-        t["count"] = ITEMSIZE["int32"]
+    t["out"] = out_row_bytes(_table(call, kind), kind)
     if call in ("process_f32", "markers") and precision == "f64" and kind != "time":
         t["ws_f64"] = A * N * ITEMSIZE["float32"]
     if call in ("process_q15", "traces_q15", "spectra_q15") and Q15_CASCADES[setup] is not None:
@@ -170,8 +208,8 @@ def batch(rows, A):
     return (-(-TWO32 // row_bytes) + 1 + EXTRA) * A
 
 
-def _case(call, form, kind=None, setup=None, precision=None, A=1, hop=None, **params):
-    if chain_table(Case(None, call, form, kind, setup, precision, A, hop, params, 0, 0)) == "FLOAT_CHAIN":
+def _case(call, form, kind=None, setup=None, precision=None, A=1, hop=None, recipe="", **params):
+    if _table(call, kind) == "FLOAT_CHAIN":
         precision = precision or "f32"
     rows = row_tensors(call, form, kind, setup, precision, A, hop, params)
     words = [call, form + (str(hop) if hop else "")]
@@ -179,7 +217,7 @@ def _case(call, form, kind=None, setup=None, precision=None, A=1, hop=None, **pa
     words += [setup] if setup else []
     words += ["f64"] if precision == "f64" else []
     words += [f"{k}={'all' if v is None else v}" for k, v in params.items() if k in ("field", "group")]
-    return Case("-".join(words), call, form, kind, setup, precision, A, hop, params, period(A), batch(rows, A))
+    return Case("-".join(words), call, form, kind, setup, precision, A, hop, params, period(A), batch(rows, A), recipe)
 
 
 def _cases():
@@ -218,14 +256,27 @@ def _cases():
     for form, hop in (("i16", None), ("p12", None), ("i16_hop", HOPS[0]), ("p12_hop", HOPS[0])):
         c.append(_case("process_q15", form, "marker", "wide6", hop=hop))
     c.append(_case("fold_iq_q15", "iq", 2, A=2))
-    # the handle-free calls: the float fold; peaks and ranks on magnitudes and on both fields of records; the histogram
-    # with many groups (one slice) and with one group of all rows (row slices that merge)
+    # the handle-free calls: the float fold; the histogram with many groups (one slice) and with one group of all rows (row
+    # slices that merge); the seven libraries that read records on magnitudes and on both fields of records.  bands with a
+    # fraction, so that `cross` is written; mask with both limit lines -- the top and the bottom 0.03 % of the points lie
+    # beyond them, so some rows fail and some pass -- and its summary; signals with a threshold per row; cfar's output is
+    # spectrum-sized, so it decides B where the input rows are records
     c.append(_case("fold_mag_f32", "mag", A=2, group=2, bucket=1))
+    c.append(_case("level_hist", "mag", A=2, edges=HIST_EDGES, group=2, bucket=64, lo=0, hi=N))
+    c.append(_case("level_hist", "mag", edges=HIST_EDGES, group=None, bucket=64, lo=0, hi=N))
+    rng = np.random.default_rng(2361)
+    upper, lower = rng.uniform(0.7808, 0.7812, N).astype(np.float32), rng.uniform(0.0005, 0.0012, N).astype(np.float32)
+    per_row = (2.0 + 0.25 * (np.arange(period(1)) % 5)).astype(np.float32)
+    for a in (upper, lower, per_row):
+        a.setflags(write=False)                                   # shared by three cases each
     for form, field in (("mag", None), ("rec", "peak"), ("rec", "power")):
         c.append(_case("find_peaks", form, field=field, k=8))
         c.append(_case("order_stats", form, field=field, ranks=(0, N // 2, N - 1)))
-    c.append(_case("level_hist", "mag", A=2, group=2, bucket=64))
-    c.append(_case("level_hist", "mag", group=None, bucket=64))
+        c.append(_case("band_power", form, field=field, bands=[(100, 16000), (8191, 8450)], fracs=(0.5,)))
+        c.append(_case("mask_test", form, field=field, upper=upper, lower=lower, lo=100, hi=16001))
+        c.append(_case("harmonics", form, recipe="tone", field=field, order=10, span=3))
+        c.append(_case("find_signals", form, recipe="segments", field=field, k=4, threshold=per_row, gap=3))
+        c.append(_case("cfar", form, recipe="carrier", field=field, train=32, guard=3, mode="go", what="ratio", lo=1, hi=N - 1))
     return tuple(c)
 
 
@@ -235,24 +286,17 @@ assert len(BY_ID) == len(CASES), sorted(c.id for c in CASES if [d.id for d in CA
 
 
 # ------------------------------------------------------------------------------------------------- what a case launches
-def hist_slices(rows, group, bucket, lo=0, hi=N):
-    """The row slices of a group, as sa_hist_f32 (csrc/hist_f32.hip) decides them from kHistOwnersFew = 256, kHistOwnersAim =
-    512 and kHistSliceRowsMin = 32 of csrc/sa_hist.hpp: G x tiles workgroups own their counters; below 256 of them a group
-    of 64 rows or more is cut so that about 512 workgroups run."""
-    tile = 256
-    tiles = (hi - 1) // tile - lo // tile + 1
-    owners = rows // group * tiles
-    if owners >= 256:
-        return 1
-    s = min(-(-512 // owners), group // 32)
-    return s if s >= 2 else 1
+def data_plane(signatures):
+    """The entry points of a signature table of abi.py that take data."""
+    return {n for n in signatures if not re.search(r"_(version|check|last_error)$", n)}
 
 
 def entry_point(case):
-    """The C entry point the call goes to."""
+    """The C entry point the call goes to: of a handle-free call the one data-plane name of its library."""
     table = chain_table(case)
     if table is None:
-        return HANDLE_FREE[case.call]
+        (name,) = data_plane(abi.LIBRARIES[LIBRARY[case.call]][1])
+        return name
     ch = getattr(chain, table)
     forms = ch.streams if FORMS[case.form][1] else ch.inputs
     return {_torch_name(k): v for k, v in forms.items()}[FORMS[case.form][0]][1][case.kind][0]
@@ -277,16 +321,8 @@ def kernels(case):
         what = {"process_q15": case.kind, "filter_q15": "filter", "spectra_q15": "spectra",
                 "traces_q15": "trace_avg" if isinstance(case.kind, tuple) else "trace"}[case.call]
         return ki.q15_kernels(Q15_CASCADES[case.setup], case.form, what)
-    p = case.params
-    if case.call == "fold_mag_f32":
-        return (f"fold_mag_f32_kernel<{p['bucket'].bit_length() - 1}>",)
-    if case.call in ("find_peaks", "order_stats"):
-        code = (chain._PEAK_FIELDS if case.call == "find_peaks" else chain._RANK_FIELDS)[p["field"]]
-        return (f"{'peaks' if case.call == 'find_peaks' else 'rank'}_f32_kernel<{code}>",)
-    steps = max(1, len(HIST_EDGES).bit_length())                       # 2^steps >= levels
-    assert 1 << steps >= len(HIST_EDGES) + 1 > 1 << (steps - 1)
-    sliced = hist_slices(case.B, case.B if p["group"] is None else p["group"], p["bucket"]) > 1
-    return (("hist_zero_kernel",) if sliced else ()) + (f"hist_f32_kernel<{steps}>",)
+    name, field, kw = arguments(case, case.B)
+    return dc.kernels(name, case.B, field, kw)
 
 
 # template arguments that do not enter an address, by kernel stem: their positions are dropped from a key
@@ -294,8 +330,14 @@ def kernels(case):
 #   NOB1: the short or the long step of the Q7 cascade, the same
 #   K of the float fold, STEPS of the histogram: the bucket's lane ladder and the depth of the edge tree; the row offsets
 #   of both kernels are those of the one instantiation a case launches
+#   UP, LOW of the mask test: whether fetch() of csrc/mask_f32.hip loads upper[q] and lower[q], q the 4-bin unit within a
+#   row -- an index below N / 4 that the row never enters
+#   CROSS of the band power: bands_f32_kernel<FIELD, true> makes every access of <FIELD, false> -- the reads of the row and
+#   the store to power[row nb + j] stand outside `if constexpr (CROSS)` -- plus the store to cross[(row nb + j) nq + q], so
+#   a case with a fraction covers both; the guard holds every bands case to nq >= 1
 _DROPPED = {"chain_f32_kernel": (1, 2, 4, 5), "chain_marker_kernel": (1, 2, 3, 4), "time_f32_kernel": (1, 2), "iir_f64_kernel": (0,),
-            "filter_q7_kernel": (1,), "fold_mag_f32_kernel": (0,), "hist_f32_kernel": (0,)}
+            "filter_q7_kernel": (1,), "fold_mag_f32_kernel": (0,), "hist_f32_kernel": (0,), "mask_f32_kernel": (1, 2),
+            "bands_f32_kernel": (1,)}
 _ONE_ROUND_AT = {"chain_f32_kernel": 5, "chain_marker_kernel": 4}
 EXEMPT = {"one round": "B <= 512 rows of <= 128 KiB: 64 MiB",
           "sa_spin_kernel": "waits on the clock, reads and writes no memory"}

@@ -513,4 +513,4 @@ def test_the_wrappers_surface():
     assert cls._bands_args([(np.int64(1), 5), (0, N)], (0, np.float32(0.5)), "power") == (2, ((1, 5), (0, N)), (0.0, 0.5))
     assert cls._bands_args(((3, 4),), (), None) == (0, ((3, 4),), ()) and cls._bands_args([[3, 4]], [FRAC_MAX], "peak")[0] == 1
     assert not [n for n in dir(chain) if n.endswith("_CHAIN") and "BAND" in n]
-    assert set(chain._PEAK_FIELDS) == set(chain._RANK_FIELDS) == {None, "peak", "power"}
+    assert set(chain.reductions.FIELDS) == {None, "peak", "power"}

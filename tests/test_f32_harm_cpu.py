@@ -503,4 +503,4 @@ def test_the_wrappers_surface():
     assert e.value.code == SA_EINVAL and "tensor" in str(e.value)
     code, cfg = cls._harm_args(np.int64(10), 64, None, None, 100, 0, 4000, "power")
     assert code == 2 and [getattr(cfg, n) for n in GOOD] == [0, 4000, 0, 4000, 100, 64, 10]
-    assert set(chain._HARM_FIELDS) == set(chain._BANDS_FIELDS) == {None, "peak", "power"} and chain._HARM_WORDS == 42
+    assert set(chain.reductions.FIELDS) == {None, "peak", "power"} and chain._HARM_WORDS == 42

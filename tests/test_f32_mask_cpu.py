@@ -568,4 +568,4 @@ def test_the_wrappers_surface():
         bare.mask_trigger_f32(None, lim, None, 5, 9, group=4)
     assert e.value.code == SA_EINVAL and "tensor" in str(e.value)
     assert cls._mask_args(lim, None, np.int64(1), 5, "power") == 2 and cls._mask_args(None, lim, 0, N, None) == 0
-    assert set(chain._MASK_FIELDS) == set(chain._BANDS_FIELDS) == {None, "peak", "power"}
+    assert set(chain.reductions.FIELDS) == {None, "peak", "power"}

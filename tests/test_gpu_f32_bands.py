@@ -15,7 +15,6 @@ import ctypes
 import numpy as np
 import pytest
 
-import offset_cases as oc
 from conftest import N, load_golden
 from gpu_support import ch, lds_fill, to_device, torch_mod  # noqa: F401 (fixtures)
 from test_f32_bands_cpu import AIMED_BAND, FRAC_MAX, ORDER_BANDS, aimed_fractions, noise_rows, same_bits, wide_rows
@@ -368,39 +367,3 @@ def test_channel_power_f32(ch, torch_mod, mode):
             ch.channel_power_f32(*args, **dict(dict(work=work), **kw))
         torch.cuda.synchronize()
         assert e.value.code == code and (work == 3.0).all().item(), kw
-
-
-@pytest.mark.parametrize("form,rows", [("mag", 65539), ("rec", 32771)])
-def test_every_row_past_4_gib(ch, torch_mod, form, rows):
-    """The input tiled from one period of 1027 rows until its last rows start beyond byte 2^32 (the batches the rules of
-    offset_cases give such rows), nb = 2, nq = 1, into outputs of 0xFF bytes: ALL rows equal the call on one period."""
-    from fpga_real_time_fft_analyzer_amd import frames
-    torch = torch_mod
-    P = oc.period(1)
-    row = (N,) if form == "mag" else (N, 2)
-    assert rows == oc.batch({"in": int(np.prod(row)) * 4}, 1) and (rows - 1) * int(np.prod(row)) * 4 >= 1 << 32
-    field = None if form == "mag" else "power"
-    gen = torch.Generator(device="cuda")
-    gen.manual_seed(2260)
-    per = 0.001 + 0.78 * torch.rand((P,) + row, device="cuda", generator=gen)
-    x = torch.empty((rows,) + row, dtype=torch.float32, device="cuda")
-    for s in range(0, rows, P):
-        n = min(P, rows - s)
-        x[s:s + n] = per[:n]
-    assert x[rows - 1:].data_ptr() - x.data_ptr() >= 1 << 32
-    bands, fracs = [(100, 16000), (8191, 8450)], (0.5,)
-    ref_p, ref_c = ch.band_power(x[:P], bands, fracs, field=field)
-    refs = [oc.as_rows(torch, ref_p, P).clone(), oc.as_rows(torch, ref_c, P).clone()]
-    assert oc.vacuous(torch, refs[0], ref_p) is None
-    assert bool((ref_c >= 0).all()) and torch.unique(ref_c[:, 0, 0]).numel() > 8
-    want_p, want_c = frames.bands_of_rows(per[:3].cpu().numpy(), bands, fracs, field=field)
-    assert same_bits(ref_p[:3].cpu().numpy(), want_p) and np.array_equal(ref_c[:3].cpu().numpy(), want_c)
-    power = torch.full((rows * 2 * 8,), 0xFF, dtype=torch.uint8, device="cuda").view(torch.float64).view(rows, 2)
-    cross = torch.full((rows * 2 * 4,), 0xFF, dtype=torch.uint8, device="cuda").view(torch.int32).view(rows, 2, 1)
-    got = ch.band_power(x, bands, fracs, field=field, power=power, cross=cross)
-    for t, want in zip(got, refs):
-        bad = oc.tiled_mismatch(torch, oc.as_rows(torch, t, rows), want)
-        assert bad is None, (form, tuple(t.shape), bad)
-    torch.cuda.synchronize()
-    del x, power, cross, got
-    torch.cuda.empty_cache()

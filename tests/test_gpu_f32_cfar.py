@@ -8,7 +8,6 @@ import itertools
 import numpy as np
 import pytest
 
-import offset_cases as oc
 from conftest import N, load_golden
 from gpu_support import ch, check_overlap_profiling_and_graph_capture, lds_fill, to_device, torch_mod  # noqa: F401 (fixtures)
 from test_f32_cfar_cpu import FIELDS, INF, MODES, QNAN, WHATS, bits, random_rows, records_of, shaped_rows, special_rows
@@ -252,38 +251,3 @@ def test_the_ratio_feeds_the_signal_list(ch, torch_mod):
     assert stats[:, 0].tolist() == [5] * 4 and bounds[:, :5, 0].tolist() == tones
     raw = ch.find_signals(x, 32, to_device(torch, (np.float32(6.0) * np.median(mag, axis=1)).astype(np.float32)))
     assert (raw[4][:, 0] >= 200).all().item() and not np.isin(raw[0][..., 0].cpu().numpy(), np.array(tones).ravel()).any()
-
-
-def test_the_last_row_past_4_gib(ch, torch_mod):
-    """Magnitudes tiled from one period of 1027 rows until the last rows of the input and of the output start beyond byte
-    2^32 (the batch the rules of offset_cases give such rows), into an output of 0xFF bytes: ALL rows equal the call on one
-    period, of which the first and the last rows equal the mirror."""
-    from fpga_real_time_fft_analyzer_amd import frames
-    torch = torch_mod
-    P, rows = oc.period(1), 65539
-    assert rows == oc.batch({"in": N * 4}, 1) and (rows - 1) * N * 4 >= 1 << 32
-    gen = torch.Generator(device="cuda")
-    gen.manual_seed(2660)
-    per = torch.exp(8.0 * torch.rand((P, N), device="cuda", generator=gen) - 4.0)
-    per[torch.arange(P, device="cuda"), 100 + 13 * torch.arange(P, device="cuda")] = 500.0     # a carrier of the row's own place
-    x = torch.empty((rows, N), dtype=torch.float32, device="cuda")
-    for s in range(0, rows, P):
-        n = min(P, rows - s)
-        x[s:s + n] = per[:n]
-    assert x[rows - 1:].data_ptr() - x.data_ptr() >= 1 << 32
-    kw = dict(train=32, guard=3, mode="go", what="ratio", lo=1, hi=N - 1)
-    ref = ch.cfar(x[:P], **kw).view(torch.int32)
-    assert oc.vacuous(torch, ref, ref.view(torch.float32)) is None
-    host = per[[0, 1, P - 1]].cpu().numpy()
-    assert np.array_equal(ref[[0, 1, P - 1]].cpu().numpy().view(np.uint32), bits(frames.cfar_of_rows(host, **kw)))
-    out = torch.full((rows * N * 4,), 0xFF, dtype=torch.uint8, device="cuda").view(torch.float32).view(rows, N)
-    assert out[rows - 1:].data_ptr() - out.data_ptr() >= 1 << 32
-    ch.cfar(x, out=out, **kw)
-    bad = oc.tiled_mismatch(torch, out.view(torch.int32), ref)
-    assert bad is None, bad
-    last = (rows - 1) % P
-    assert np.array_equal(out[[0, rows - 1]].view(torch.int32).cpu().numpy().view(np.uint32),
-                          bits(frames.cfar_of_rows(per[[0, last]].cpu().numpy(), **kw)))
-    torch.cuda.synchronize()
-    del x, out
-    torch.cuda.empty_cache()

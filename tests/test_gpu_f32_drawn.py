@@ -9,7 +9,6 @@ output given through ``out=`` starts as 0xFF bytes, so that a word the kernel do
 
 A failure names the library, the draw and its arguments in one line (drawn_cases.show): the draws are those of the seed, so
 that line repeats it."""
-import copy
 import gc
 
 import numpy as np
@@ -17,52 +16,15 @@ import pytest
 
 import drawn_cases as dc
 from conftest import N
-from gpu_support import ch, to_device, torch_mod  # noqa: F401 (fixtures)
+from gpu_support import ReductionCall, ch, to_device, torch_mod  # noqa: F401 (fixtures)
 from reduction_libraries import records_of
 from test_gpu_f32_peaks import _inputs, _tones
 
 pytestmark = pytest.mark.gpu
 
-COMPOSED = {"fold": "spectra_f32", "peaks": "peak_table_f32", "rank": "noise_floor_f32", "hist": "persistence_f32",
-            "bands": "channel_power_f32", "mask": "mask_trigger_f32", "harm": "harmonics_f32", "signals": "signals_f32",
-            "cfar": "cfar_f32"}
-
-
-class _Call:
-    """One call of a library's method, prepared so that making it is nothing but the method call: the input resident, the
-    arguments objects of its own (a limit line or a threshold per row on the device, the rest copied) and an output of 0xFF
-    bytes for every ``out=`` argument.  ``composed``: the arguments of the composed call that stands for the plain call with
-    ``kw``, ``x`` then being the frames."""
-
-    def __init__(self, torch, name, x, field, kw, composed=None):
-        self.name, self.x, self.kw = name, x, kw
-        self.method = dc.METHODS[name] if composed is None else COMPOSED[name]
-        self.args = {k: to_device(torch, v) if isinstance(v, np.ndarray) else copy.deepcopy(v)
-                     for k, v in (kw if composed is None else composed).items()}
-        if composed is None and name in dc.HAS_FIELD:
-            self.args["field"] = field
-        self.held = {}
-        for arg, shape, dtype in dc.outputs(name, x.shape[0], kw):
-            raw = torch.full((int(np.prod(shape)) * np.dtype(dtype).itemsize,), 0xFF, dtype=torch.uint8, device="cuda")
-            self.held[arg] = (raw, shape, dtype)
-            self.args[arg] = raw.view(getattr(torch, dtype)).view(shape)
-        self.returned = None
-
-    def launch(self, ch):
-        """The call, nothing waited for; the arguments are dropped with it: what they held is the kernel's or nobody's."""
-        self.returned = getattr(ch, self.method)(self.x, **self.args)
-        del self.args
-        return self
-
-    def result(self):
-        """The host copies of what the call wrote, in the form of drawn_cases.mirror()."""
-        arrays = {arg: raw.cpu().numpy().view(dtype).reshape(shape) for arg, (raw, shape, dtype) in self.held.items()}
-        back = self.returned if isinstance(self.returned, tuple) else ()
-        return dc.result(self.name, arrays, tuple(None if t is None else t.contiguous().cpu().numpy() for t in back), self.kw)
-
 
 def _call_of(torch, name, d, x=None):
-    return _Call(torch, name, to_device(torch, records_of(d.pts, d.field)) if x is None else x, d.field, d.kw)
+    return ReductionCall(torch, name, to_device(torch, records_of(d.pts, d.field)) if x is None else x, d.field, d.kw)
 
 
 def _bad(name, draw, got, want):
@@ -164,8 +126,8 @@ def test_composed_calls_on_drawn_arguments(ch, torch_mod):
             kw = dict(d.kw)
             if isinstance(kw.get("threshold"), np.ndarray):
                 kw["threshold"] = np.resize(kw["threshold"], B)
-            plain = _Call(torch, name, mag, None, kw).launch(ch)
-            composed = _Call(torch, name, x, None, kw, composed=_composed_arguments(name, kw)).launch(ch)
+            plain = ReductionCall(torch, name, mag, None, kw).launch(ch)
+            composed = ReductionCall(torch, name, x, None, kw, composed=_composed_arguments(name, kw)).launch(ch)
             for arg in plain.held:
                 assert torch.equal(composed.held[arg][0], plain.held[arg][0]), (arg, dc.show(name, d))
             if name == "peaks":

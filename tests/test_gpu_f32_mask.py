@@ -12,7 +12,6 @@ one of these boundaries."""
 import numpy as np
 import pytest
 
-import offset_cases as oc
 from conftest import N, load_golden
 from gpu_support import ch, check_overlap_profiling_and_graph_capture, lds_fill, to_device, torch_mod  # noqa: F401 (fixtures)
 from test_f32_mask_cpu import (FIELDS, GAPS, aimed_narrow, aimed_wide, edge_case, edge_ranges, planted, records_of,
@@ -374,50 +373,3 @@ def test_mask_trigger_f32(ch, torch_mod, mode):
             ch.mask_trigger_f32(*args, **dict(dict(work=work), **kw))
         torch.cuda.synchronize()
         assert e.value.code == code and (work == 3.0).all().item(), kw
-
-
-@pytest.mark.parametrize("form,rows", [("mag", 65539), ("rec", 32771)])
-def test_every_row_past_4_gib(ch, torch_mod, form, rows):
-    """The input tiled from one period of 1027 rows until its last rows start beyond byte 2^32 (the batches the rules of
-    offset_cases give such rows), both limits and the summary, into outputs of 0xFF bytes: ALL rows equal the call on one
-    period, and the summary counts every one of them."""
-    from fpga_real_time_fft_analyzer_amd import frames
-    torch = torch_mod
-    P = oc.period(1)
-    row = (N,) if form == "mag" else (N, 2)
-    assert rows == oc.batch({"in": int(np.prod(row)) * 4}, 1) and (rows - 1) * int(np.prod(row)) * 4 >= 1 << 32
-    field = None if form == "mag" else "power"
-    gen = torch.Generator(device="cuda")
-    gen.manual_seed(2360)
-    per = 0.001 + 0.78 * torch.rand((P,) + row, device="cuda", generator=gen)
-    x = torch.empty((rows,) + row, dtype=torch.float32, device="cuda")
-    for s in range(0, rows, P):
-        n = min(P, rows - s)
-        x[s:s + n] = per[:n]
-    assert x[rows - 1:].data_ptr() - x.data_ptr() >= 1 << 32
-    rng = np.random.default_rng(2361)
-    upper = rng.uniform(0.7808, 0.7812, N).astype(np.float32)       # the top 0.03 % of the points lie above it: some rows fail
-    lower = rng.uniform(0.0005, 0.0012, N).astype(np.float32)
-    du, dl = to_device(torch, upper), to_device(torch, lower)
-    lo, hi = 100, 16001
-    ref_i, ref_f, ref_s = ch.mask_test(x[:P], du, dl, lo, hi, field=field, summary=True)
-    ref = oc.as_rows(torch, torch.cat([ref_i, ref_f.view(torch.int32)], dim=1).contiguous(), P).clone()
-    assert oc.vacuous(torch, ref, ref_f) is None
-    failing = ((ref_i[:, 0] > 0) | (ref_i[:, 1] > 0))
-    assert 0 < int(failing.sum()) < P and torch.unique(ref_i[:, 4]).numel() > 8
-    h = per[:3].cpu().numpy()
-    want, _ = frames.mask_of_rows(h, upper, lower, lo, hi, field=field)
-    assert same_records(_host(ref_i[:3], ref_f[:3]), want)
-    out = torch.full((rows * 40,), 0xFF, dtype=torch.uint8, device="cuda").view(torch.int32).view(rows, 10)
-    summary = torch.full((4,), -9, dtype=torch.int32, device="cuda")
-    ch.mask_test(x, du, dl, lo, hi, field=field, out=out, summary=summary)
-    bad = oc.tiled_mismatch(torch, oc.as_rows(torch, out, rows), ref)
-    assert bad is None, (form, bad)
-    whole, tail = divmod(rows, P)
-    fails = torch.nonzero(failing).flatten()
-    n_over, n_under = (ref_i[:, 0] > 0), (ref_i[:, 1] > 0)
-    assert summary.tolist() == [whole * int(n_over.sum()) + int(n_over[:tail].sum()), whole * int(n_under.sum()) + int(n_under[:tail].sum()),
-                                int(fails[0]), max(int(f) + P * (whole if int(f) < tail else whole - 1) for f in fails.tolist())]
-    torch.cuda.synchronize()
-    del x, out
-    torch.cuda.empty_cache()

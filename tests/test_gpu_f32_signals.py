@@ -11,7 +11,6 @@ gaps on both sides of every one of these boundaries."""
 import numpy as np
 import pytest
 
-import offset_cases as oc
 from conftest import N, load_golden
 from gpu_support import ch, lds_fill, to_device, torch_mod  # noqa: F401 (fixtures)
 from test_f32_bands_cpu import noise_rows, same_bits, wide_rows
@@ -417,44 +416,3 @@ def test_signals_f32(ch, torch_mod, mode):
             ch.signals_f32(*args, **dict(dict(k=k, work=work), **kw))
         torch.cuda.synchronize()
         assert e.value.code == code and (work == 3.0).all().item(), kw
-
-
-def test_the_last_row_past_4_gib(ch, torch_mod):
-    """Magnitudes tiled from one period of 1027 rows until the last rows start beyond byte 2^32 (the batch the rules of
-    offset_cases give such rows), a threshold per row tiled alike, into records of 0xFF bytes: ALL rows equal the call on one
-    period."""
-    from fpga_real_time_fft_analyzer_amd import frames
-    torch = torch_mod
-    P, rows, k = oc.period(1), 65539, 4
-    assert rows == oc.batch({"in": N * 4}, 1) and (rows - 1) * N * 4 >= 1 << 32
-    gen = torch.Generator(device="cuda")
-    gen.manual_seed(2560)
-    per = 0.001 + 0.78 * torch.rand((P, N), device="cuda", generator=gen)
-    r = torch.arange(P, device="cuda")
-    for j in range(3):                                             # three segments of the row's own place and width
-        per[r, 100 + 7 * r + 3000 * j] = 5.0
-        per[r, 100 + 7 * r + 3000 * j + 1 + r % 3] = 6.0
-    tper = 2.0 + (r % 5).to(torch.float32) * 0.25
-    x = torch.empty((rows, N), dtype=torch.float32, device="cuda")
-    thr = torch.empty((rows,), dtype=torch.float32, device="cuda")
-    for s in range(0, rows, P):
-        n = min(P, rows - s)
-        x[s:s + n] = per[:n]
-        thr[s:s + n] = tper[:n]
-    assert x[rows - 1:].data_ptr() - x.data_ptr() >= 1 << 32
-    ref = torch.zeros((P, k * WORDS + 3), dtype=torch.int32, device="cuda")
-    o, s = torch.zeros((P, k, WORDS), dtype=torch.int32, device="cuda"), torch.zeros((P, 3), dtype=torch.int32, device="cuda")
-    ch.find_signals(x[:P], k, thr[:P], gap=3, out=o, stats=s)
-    ref[:, :k * WORDS], ref[:, k * WORDS:] = o.view(P, -1), s
-    assert oc.vacuous(torch, ref, None) is None
-    assert s[:, 0].tolist() == [3] * P and o[:, 0, 0].tolist() == [100 + 7 * i for i in range(P)]
-    want = frames.signals_of_rows(per[:3].cpu().numpy(), k=k, threshold=tper[:3].cpu().numpy(), gap=3)
-    assert same_result(_host(o[:3], s[:3]), want) is None
-    out = torch.full((rows * k * WORDS * 4,), 0xFF, dtype=torch.uint8, device="cuda").view(torch.int32).view(rows, k, WORDS)
-    stats = torch.full((rows * 12,), 0xFF, dtype=torch.uint8, device="cuda").view(torch.int32).view(rows, 3)
-    ch.find_signals(x, k, thr, gap=3, out=out, stats=stats)
-    bad = oc.tiled_mismatch(torch, out.view(rows, -1), o.view(P, -1)) or oc.tiled_mismatch(torch, stats, s)
-    assert bad is None, bad
-    torch.cuda.synchronize()
-    del x, out
-    torch.cuda.empty_cache()

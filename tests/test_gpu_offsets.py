@@ -8,13 +8,18 @@ first P rows alone -- small batches are held to the oracles and mirrors by the o
 forms of the large call -- and must itself be non-zero, finite and pairwise different row by row, or the test fails as
 vacuous.  The large call writes into an `out` filled with 0xFF bytes; then every whole period of `out` equals the reference
 by bits, and the tail its head: all B rows (B / A groups), not a sample, so a store that wrapped onto any row shows.  A
-wrong offset may also show as a memory fault: its cause is then in the address arithmetic of the kernels the case names."""
+wrong offset may also show as a memory fault: its cause is then in the address arithmetic of the kernels the case names.
+
+The calls of the nine reduction libraries go through one path, gpu_support.ReductionCall on the arguments of the table: every
+output of drawn_cases.outputs that has a row per row is compared so, a threshold per row is tiled like the input, and rows of
+the reference are held to the numpy mirror (drawn_cases.compare)."""
 import numpy as np
 import pytest
 
+import drawn_cases as dc
 import offset_cases as oc
 import structured_cases
-from gpu_support import ch, torch_mod  # noqa: F401 (fixtures)
+from gpu_support import ReductionCall, ch, torch_mod  # noqa: F401 (fixtures)
 from fpga_real_time_fft_analyzer_amd import chain
 from offset_cases import CASES, N, TWO32
 from q15_cases import configure as configure_q15
@@ -27,7 +32,7 @@ MERGED = "level_hist-mag-group=all"
 
 def _input_key(case):
     """Cases with one key read prefixes of one tiled input."""
-    return (case.form, case.hop or 0, case.P, case.id == MERGED)
+    return (case.form, case.hop or 0, case.P, case.id == MERGED, case.recipe)
 
 
 ORDERED = sorted(CASES, key=lambda c: (_input_key(c), c.B))
@@ -60,8 +65,15 @@ def _one_period(torch, case):
         return torch.randint(0, 256, (P,) + row, dtype=torch.uint8, device="cuda", generator=gen)
     if case.form == "iq":
         return torch.randint(-32768, 32768, (P, N, 2), dtype=torch.int16, device="cuda", generator=gen)
-    # magnitudes and records: non-negative, all below the top edge of the histogram
-    return 0.001 + 0.78 * torch.rand((P,) + row, device="cuda", generator=gen)
+    # magnitudes and records: non-negative and, without a recipe, all below the top edge of the histogram; a plant sets both
+    # floats of a record
+    noise, plants = oc.RECIPES[case.recipe] if case.recipe else ("uniform", ())
+    u = torch.rand((P,) + row, device="cuda", generator=gen)
+    per = 0.001 + 0.78 * u if noise == "uniform" else torch.exp(8.0 * u - 4.0)
+    r = torch.arange(P, device="cuda")
+    for first, step, width, value in plants:
+        per[r, first + step * r + (1 + r % width if width else 0)] = value
+    return per
 
 
 def _tiled_input(torch, case):
@@ -88,21 +100,6 @@ def _sentinel(torch, shape, dtype):
     return raw.view(dtype).view(tuple(shape))
 
 
-def _out_spec(case, B):
-    table = oc.chain_table(case)
-    if table is not None:
-        return chain.output_spec(getattr(chain, table), case.kind, B)
-    import torch
-    p, R = case.params, B // case.A
-    if case.call == "fold_mag_f32":
-        return (R, N // p["bucket"], 2), torch.float32
-    if case.call == "find_peaks":
-        return (R, p["k"], 2), torch.int32
-    if case.call == "order_stats":
-        return (R, len(p["ranks"])), torch.float32
-    return (1 if p["group"] is None else R, N // p["bucket"], len(oc.HIST_EDGES) + 1), torch.uint32
-
-
 def _configure(ch, case):
     table = oc.chain_table(case)
     if table == "FLOAT_CHAIN":
@@ -115,33 +112,76 @@ def _configure(ch, case):
         configure_q15(ch, case.setup)
 
 
-def _call(ch, case, x, out):
-    """The call of the case on x into out; the tensors it wrote."""
-    p = case.params
+def _chain_call(ch, case, x, out):
+    """The call of a case that has a chain table on x into out; the tensor it returned."""
     if case.call == "process_f32":
-        return (ch.process_f32(x, out=out, out_kind=case.kind, scale=I16_SCALE),)
+        return ch.process_f32(x, out=out, out_kind=case.kind, scale=I16_SCALE)
     if case.call == "markers":
         ch.markers(x, out=out, scale=I16_SCALE)
-        return (out,)
+        return out
     if case.call == "process_q15":
-        return (ch.process_q15(x, out=out, out_kind=case.kind, hop=case.hop),)
+        return ch.process_q15(x, out=out, out_kind=case.kind, hop=case.hop)
     if case.call == "traces_q15":
         w, a = case.kind if isinstance(case.kind, tuple) else (case.kind, None)
-        return (ch.traces_q15(x, bucket=w, out=out, hop=case.hop, group=a),)
+        return ch.traces_q15(x, bucket=w, out=out, hop=case.hop, group=a)
     if case.call == "spectra_q15":
-        return (ch.spectra_q15(x, case.kind, out=out, hop=case.hop),)
+        return ch.spectra_q15(x, case.kind, out=out, hop=case.hop)
     if case.call == "fold_iq_q15":
-        return (ch.fold_iq_q15(x, case.kind, out=out),)
-    if case.call == "filter_q15":
-        return (ch.filter_q15(x, out),)
-    if case.call == "fold_mag_f32":
-        return (ch.fold_mag_f32(x, p["group"], p["bucket"], out=out),)
-    if case.call == "find_peaks":
-        return (out, ch.find_peaks(x, k=p["k"], field=p["field"], out=out)[2])
-    if case.call == "order_stats":
-        return (ch.order_stats(x, p["ranks"], field=p["field"], out=out),)
-    assert case.call == "level_hist"
-    return (ch.level_hist(x, oc.HIST_EDGES, group=p["group"], bucket=p["bucket"], out=out),)
+        return ch.fold_iq_q15(x, case.kind, out=out)
+    assert case.call == "filter_q15", case.call
+    return ch.filter_q15(x, out)
+
+
+def _make(torch, ch, case, x, frames):
+    """The call of the case on x, `frames` frames, every output 0xFF bytes before it: (name of offset_cases.tensors -> each
+    tensor it wrote that has a row per row, the ReductionCall of a handle-free call or None)."""
+    if case.call in oc.LIBRARY:
+        name, field, kw = oc.arguments(case, frames)
+        call = ReductionCall(torch, name, x, field, kw).launch(ch)
+        wrote = {arg: raw.view(getattr(torch, dtype)).view(shape) for arg, (raw, shape, dtype) in call.held.items()}
+        wrote.update({arg: call.returned[i] for arg, i, _ in dc.RETURNED.get(name, ())})
+        return {k: wrote[k] for k in oc.tensors(case) if k in wrote}, call
+    shape, dtype = chain.output_spec(getattr(chain, oc.chain_table(case)), case.kind, frames)
+    out = _sentinel(torch, shape, dtype)
+    assert _chain_call(ch, case, x, out).data_ptr() == out.data_ptr()
+    return {"out": out}, None
+
+
+# what the reference of a library must hold beside non-zero, different rows, from the result in the form of
+# drawn_cases.mirror() and `at`, the place of the first plant of the recipe in every row: crossings reached at many bins;
+# rows that fail and rows that pass, the worst bin at many places; the fundamental found at the row's own place; three
+# segments, the first at the row's own place; the carrier the strongest ratio of its row
+NOT_VACUOUS = {
+    "bands": lambda got, at: bool((got[1] >= 0).all()) and np.unique(got[1][:, 0, 0]).size > 8,
+    "mask": lambda got, at: (0 < int(((got[0]["over"] > 0) | (got[0]["under"] > 0)).sum()) < len(got[0])
+                             and np.unique(got[0]["up_bin"]).size > 8),
+    "harm": lambda got, at: got[0]["bin"][:, 0].tolist() == at.tolist(),
+    "signals": lambda got, at: got[1][:, 0].tolist() == [3] * len(at) and got[0]["start"][:, 0].tolist() == at.tolist(),
+    "cfar": lambda got, at: got[0].argmax(axis=1).tolist() == at.tolist(),
+}
+
+
+def _reference_is_the_mirrors(case, x, call):
+    """The one-period reference of a handle-free case, on the host in the form of drawn_cases.mirror(): its floats finite, the
+    library's own predicate, and the rows (groups) 0, 1, the last and the one the last row of the large call repeats equal
+    to the numpy mirror by drawn_cases.compare.  An array the call has one of (the mask summary) is no row of anything: the
+    mirror's own stands in its place here and test_mask_summary_past_4_gib holds it."""
+    P, A = case.P, case.A
+    got = call.result()
+    for label, a in dc.plain_arrays(got):
+        assert a.dtype.kind != "f" or bool(np.isfinite(a).all()), (case.id, label, "a reference row is not finite")
+    name = oc.LIBRARY[case.call]
+    if name in NOT_VACUOUS:
+        first, step = oc.RECIPES[case.recipe][1][0][:2] if case.recipe else (0, 0)
+        assert NOT_VACUOUS[name](got, first + step * np.arange(P)), (case.id, "the reference says nothing")
+    groups = sorted({0, 1, P // A - 1, (case.B // A - 1) % (P // A)})
+    _, field, kw = oc.arguments(case, P, only=groups)
+    host = x[[g * A + i for g in groups for i in range(A)]].cpu().numpy()
+    want = dc.mirror(name, host if field is None else np.ascontiguousarray(host[..., dc.FIELDS.index(field) - 1]), field, kw)
+    some = tuple(g[groups] if g.shape[0] == P // A else w for g, w in zip(got, want))
+    bad = dc.compare(name, some, want)
+    assert bad is None, (case.id, groups, bad)
+    return got
 
 
 def _floating(torch, case, t):
@@ -149,8 +189,6 @@ def _floating(torch, case, t):
     if case.kind == "marker":
         f = t.view(torch.float32)
         return f[:, [0, 2]] if oc.chain_table(case) == "FLOAT_CHAIN" else f[:, 0]
-    if case.call == "find_peaks":
-        return t.view(torch.float32)[..., 0] if t.dim() == 3 else None
     if t.dtype == torch.complex64:
         return torch.view_as_real(t)
     return t if t.dtype == torch.float32 else None
@@ -161,48 +199,75 @@ def _last_row_offset(case, t, rows):
     return t[t.shape[0] - t.shape[0] // rows:].data_ptr() - t.data_ptr()
 
 
-@pytest.mark.parametrize("cid", [c.id for c in ORDERED if c.id != MERGED])
-def test_every_row_past_4_gib(ch, torch_mod, cid):
-    """One case of offset_cases.CASES: the reference on one period, the call on B rows into 0xFF bytes, every row compared."""
-    torch = torch_mod
+SUMMARY = [c.id for c in ORDERED if c.call == "mask_test"]        # one record per call beside the rows: a test of their own
+
+
+def _every_row(ch, torch, cid):
+    """One case of offset_cases.CASES: the reference on one period, the call on B rows into 0xFF bytes, every row of every
+    output compared.  Returns the reference of a handle-free case on the host, in the form of drawn_cases.mirror(), and the
+    host copy of every output of the large call that has no row per row."""
     case = oc.BY_ID[cid]
     P, B, A = case.P, case.B, case.A
     fig = oc.tensors(case)
     torch.cuda.reset_peak_memory_stats()
     x = _tiled_input(torch, case)
     _configure(ch, case)
-    # the table's figures are the tensors' own: the last row (group) of the input, and of the output where that decides B
+    # the table's figures are the tensors' own: the last row (group) of the input, and of every output that reaches 2^32
     stream = oc.FORMS[case.form][1]
     first_of_last = _elements(case, B - A + 1) - (oc.FORMS[case.form][2][0] if stream else 1)
     assert x[first_of_last:].data_ptr() - x.data_ptr() == oc.last_row_start(*fig["in"]) >= 1 << 32
     decides = oc.deciding_tensor(case)[0]
     # the reference: the same call on the first P rows alone
-    shape, dtype = _out_spec(case, P)
-    ref = _call(ch, case, x[:_elements(case, P)], _sentinel(torch, shape, dtype))
-    refs = []
-    for i, t in enumerate(ref):
-        rows = oc.as_rows(torch, t, P // A).clone()
-        if i == 0:
-            why = oc.vacuous(torch, rows, _floating(torch, case, t))
-            assert why is None, (cid, why)
-        else:                                                       # the candidate counts of the peak table: two rows may agree
-            assert bool((rows != 0).all()) and torch.unique(rows).numel() > 1, cid
-        refs.append(rows)
+    ref, ref_call = _make(torch, ch, case, x[:_elements(case, P)], P)
+    refs = {k: oc.as_rows(torch, t, P // A).clone() for k, t in ref.items()}
+    first = next(iter(refs))
+    why = oc.vacuous(torch, refs[first], None if ref_call else _floating(torch, case, ref[first]))
+    assert why is None, (cid, why)
+    for k, _, _ in dc.RETURNED.get(oc.LIBRARY.get(case.call), ()):     # the candidate counts of the peak table: two rows may agree
+        assert bool((refs[k] != 0).all()) and torch.unique(refs[k]).numel() > 1, (cid, k)
+    held = _reference_is_the_mirrors(case, x, ref_call) if ref_call else None
     # the call
-    shape, dtype = _out_spec(case, B)
-    out = _sentinel(torch, shape, dtype)
-    if decides == "out":
-        assert _last_row_offset(case, out, B // A) == oc.last_row_start(*fig["out"]) >= 1 << 32
-    got = _call(ch, case, x, out)
-    assert got[0].data_ptr() == out.data_ptr()
-    for t, want in zip(got, refs):
-        bad = oc.tiled_mismatch(torch, oc.as_rows(torch, t, B // A), want)
-        assert bad is None, (cid, tuple(t.shape), bad)
+    got, call = _make(torch, ch, case, x, B)
+    assert list(got) == list(refs) and (decides == "in" or decides in got)
+    for k, t in got.items():
+        if oc.last_row_start(*fig[k]) >= 1 << 32:
+            assert _last_row_offset(case, t, B // A) == oc.last_row_start(*fig[k]), (cid, k)
+        bad = oc.tiled_mismatch(torch, oc.as_rows(torch, t, B // A), refs[k])
+        assert bad is None, (cid, k, tuple(t.shape), bad)
     torch.cuda.synchronize()
+    once = {} if call is None else {k: raw.view(getattr(torch, dtype)).cpu().numpy() for k, (raw, _, dtype) in call.held.items()
+                                    if k not in got}
     print(f"FIGURE {cid}: B {B} P {P}, " + ", ".join(f"{k} {rb * n} B" for k, (rb, n) in fig.items())
           + f"; all {B // A} rows equal row mod {P // A}; peak torch memory {torch.cuda.max_memory_allocated() / 2 ** 30:.1f} GiB")
-    del out, got, ref, refs, x
+    del got, call, ref, ref_call, refs, x
     torch.cuda.empty_cache()
+    return held, once
+
+
+@pytest.mark.parametrize("cid", [c.id for c in ORDERED if c.id != MERGED and c.id not in SUMMARY])
+def test_every_row_past_4_gib(ch, torch_mod, cid):
+    """One case of offset_cases.CASES: the reference on one period, the call on B rows into 0xFF bytes, every row compared."""
+    _every_row(ch, torch_mod, cid)
+
+
+@pytest.mark.parametrize("cid", SUMMARY)
+def test_mask_summary_past_4_gib(ch, torch_mod, cid):
+    """A mask case: every row as in test_every_row_past_4_gib, and the summary, one record per call that tiling cannot check,
+    in closed form from the records of one period: the rows over and the rows under are (whole periods) x the count of one
+    period + the count of the tail, then the first and the last failing row -- of the call on one period and of the call on B."""
+    (rec, one_period), once = _every_row(ch, torch_mod, cid)
+    case = oc.BY_ID[cid]
+    P = case.P
+    over, under = rec["over"] > 0, rec["under"] > 0
+    fails = np.nonzero(over | under)[0].tolist()
+
+    def summary(rows):
+        whole, tail = divmod(rows, P)
+        return [whole * int(over.sum()) + int(over[:tail].sum()), whole * int(under.sum()) + int(under[:tail].sum()), fails[0],
+                max(f + P * (whole if f < tail else whole - 1) for f in fails)]
+
+    assert one_period.tolist() == summary(P), cid
+    assert once["summary"].tolist() == summary(case.B), cid
 
 
 def test_merged_histogram_past_4_gib(ch, torch_mod):
@@ -221,6 +286,9 @@ def test_merged_histogram_past_4_gib(ch, torch_mod):
     x[B - past:] = oc.HIST_ABOVE
     period = ch.level_hist(x[:P], oc.HIST_EDGES, group=None, bucket=W).to(torch.int64)
     tail = ch.level_hist(x[B // P * P:].clone(), oc.HIST_EDGES, group=None, bucket=W).to(torch.int64)
+    name, field, kw = oc.arguments(case, P)                             # the period as one group equals the numpy mirror
+    bad = dc.compare(name, (period.to(torch.uint32).cpu().numpy(),), dc.mirror(name, x[:P].cpu().numpy(), field, kw))
+    assert bad is None, bad
     assert tuple(period.shape) == (1, N // W, L) and bool((period[..., :L - 1] > 0).all()) and not bool(period[..., L - 1].any())
     assert bool((period.sum(dim=2) == P * W).all()) and bool((tail[..., L - 1] == past * W).all())
     out = _sentinel(torch, (1, N // W, L), torch.uint32)

@@ -430,8 +430,7 @@ def test_the_names_the_tests_and_tools_use():
 
     from fpga_real_time_fft_analyzer_amd import abi, chain
     from reduction_libraries import LIBRARIES
-    fields = [getattr(chain, f"_{x}_FIELDS") for x in ("PEAK", "RANK", "BANDS", "MASK", "HARM")]
-    assert all(f == {None: 0, "peak": 1, "power": 2} for f in fields) and chain._HARM_WORDS == 42
+    assert chain.reductions.FIELDS == {None: 0, "peak": 1, "power": 2} and chain._HARM_WORDS == 42
     for x in LIBRARIES:
         if x not in ("fold", "hist"):                 # these two take magnitudes only
             assert [getattr(abi, f"SA_{x.upper()}_IN_{k}") for k in ("MAG", "POINT_PEAK", "POINT_POWER")] == [0, 1, 2], x
