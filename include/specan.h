@@ -344,7 +344,18 @@ int sa_load_sos_f64(sa_handle *h, const double *sos, int n_sections);
 int sa_load_sos_q14(sa_handle *h, const int16_t *sos, int n_sections);
 
 /* Window tables (host pointers, copied).  NULL restores the default generated with the formula of
- * scripts/hann_coeff.py:3-5 (the Q15 table includes the int16 wrap of entries 8178..8205). */
+ * scripts/hann_coeff.py:3-5 (the Q15 table includes the int16 wrap of entries 8178..8205).
+ *
+ * A float table that is a two-term cosine window, w[n] = a0 - a1 cos(2 pi n / 16383) to within 1.5e-7 of its peak
+ * (a0, a1 fitted by least squares in double: Hann, Hamming, ...; the default is one, with a0 = a1 = 0.5 exactly), is
+ * replaced by that formula in the kernels that compute a spectrum behind an IIR cascade (filter modes DEFAULT and CUSTOM)
+ * in the float32 precision: they evaluate it in place in float32 by the angle-addition formula, two fused multiply-adds
+ * per sample, and do not read the table.  The window they apply differs from the loaded table by at most
+ *     A(w) = 1.5e-7 + 5 * 2^-24 * (|a0| + |a1|) / peak      (4.5e-7 for Hann)
+ * of the table's peak: the fit's threshold plus five float32 roundings.  The bound is absolute, not relative: near a
+ * zero of the window (Hann at n = 1 is 3.7e-8) the generated value is off by more than the table entry itself.  Any
+ * other table is applied as loaded.  Bypass mode (NONE), SA_OUT_TIME and SA_PRECISION_F64_STATE always apply the table
+ * itself (float32 x * w rounded once; in the float64-state precision the table widened exactly, in double). */
 int sa_set_window_q15(sa_handle *h, const int16_t *w /* [16384] or NULL */);
 int sa_set_window_f32(sa_handle *h, const float *w /* [16384] or NULL */);
 int sa_set_window_mode_q15(sa_handle *h, int mode /* SA_WIN_* */);

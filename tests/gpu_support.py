@@ -84,7 +84,8 @@ def synth(B, seed):
 
 def table_window():
     """ones with a 1e-5 ripple at 3 cycles per frame: not a0 - a1 cos(2 pi n / (N-1)) (fit bound 1.5e-7), so the float
-    kernels read the window table (WINGEN off)."""
+    kernels read the window table (WINGEN off).  Smooth by design: a sample read from the wrong place moves it by less
+    than the gates notice; position errors are the business of window_cases.coded (tests/test_gpu_f32_window.py)."""
     n = np.arange(N)
     return (1.0 + 1e-5 * np.cos(2 * np.pi * 3 * n / N)).astype(np.float32)
 

@@ -67,9 +67,9 @@ def standalone(tmp_path, name, units=(), sanitize=True, args=()):
     return r.stdout
 
 
-def standalone_checks(tmp_path, name, units=()):
+def standalone_checks(tmp_path, name, units=(), args=()):
     """standalone() under the sanitizers for a program that ends with "ok <number of checks>": that number."""
-    out = standalone(tmp_path, name, units)
+    out = standalone(tmp_path, name, units, args=args)
     assert out.startswith("ok "), out
     return int(out.split()[1])
 
