@@ -371,4 +371,26 @@ def _loader(x: str):
 
 fold_lib, peaks_lib, rank_lib, hist_lib, bands_lib, mask_lib, harm_lib, cfar_lib, signals_lib = map(_loader, LIBRARIES)
 
+# the entry points of include/specan_hold.h: libspecan_hold.so, the eleventh product library, again without a handle (per bin
+# the keys at given ranks of the sorted frames of every group of A rows: float32 [G, q, 16384]), bound by hold_lib() and held
+# name for name against that header (tests/test_f32_hold_cpu.py); no name is in the tables above.  The library stands outside
+# LIBRARIES: the tests of the nine rows hold that table, the data-plane entry points and the offset cases to the counts they
+# have, and a row there belongs to a change of those tests alone.
+SA_HOLD_VERSION = 1
+SA_HOLD_Q_MAX = 8
+SA_HOLD_GROUP_MAX = 128
+SA_HOLD_IN_MAG, SA_HOLD_IN_POINT_PEAK, SA_HOLD_IN_POINT_POWER = 0, 1, 2
+HOLD_SIGNATURES = {
+    "sa_hold_version": (_INT, []),
+    "sa_hold_f32": (_INT, [C.c_void_p, _INT, C.c_void_p, _INT, _INT, _INT, _P(C.c_int32), C.c_void_p]),
+    "sa_hold_check": (_INT, [_INT, C.c_uint64, C.c_uint64, _INT, _INT, _INT, _P(C.c_int32)]),
+    "sa_hold_last_error": (C.c_char_p, []),
+}
+HOLD_LIB_PATH = os.path.join(_PKG, "libspecan_hold.so")
+
+
+def hold_lib() -> C.CDLL:
+    """Load libspecan_hold.so (include/specan_hold.h), after torch as lib() does; raise loudly when it has not been built."""
+    return _loaded_once(HOLD_LIB_PATH, (HOLD_SIGNATURES,))
+
 

@@ -16,7 +16,7 @@ from typing import NamedTuple, Optional, Sequence
 import numpy as np
 import torch
 
-from . import abi, frames, reductions
+from . import abi, frames, holds, reductions
 from .abi import (SA_FILTER_CUSTOM, SA_FILTER_DEFAULT, SA_FILTER_NONE, SA_FILTER_WIDE, SA_N, SA_P12_FRAME_BYTES,
                   SA_OUT_MAG_FULL, SA_OUT_MAG_HALF, SA_OUT_MARKER, SA_OUT_SPEC_HALF, SA_OUT_TIME, SA_PRECISION_F32,
                   SA_PRECISION_F64_STATE, SA_Q15_OUT_IQ, SA_Q15_OUT_MAG, SA_Q15_OUT_MARKER, SpecanError)
@@ -155,7 +155,7 @@ def _command_buffer(data: bytes):
     return (C.c_uint8 * len(data)).from_buffer_copy(bytes(data)) if len(data) else (C.c_uint8 * 1)()
 
 
-class SpectrumChain(reductions.Reductions):
+class SpectrumChain(reductions.Reductions, holds.Holds):
     """One handle = one (GPU, stream) instance of window -> IIR -> 16K FFT.
 
     Not thread-safe (same rule as the C ABI).  All process calls are asynchronous on the current

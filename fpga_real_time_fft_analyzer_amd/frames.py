@@ -314,6 +314,47 @@ def rank_of_quantile(q: float, m: int) -> int:
     return math.floor(float(q) * (int(m) - 1))
 
 
+HOLD_Q_MAX = 8
+HOLD_GROUP_MAX = 128
+
+
+def _hold_args(ranks, group, field) -> tuple:
+    """``(ranks as a tuple of ints, group)`` of the percentile traces, or ValueError: ``group`` an int (no bool, no float) in
+    2..128, ``ranks`` a sequence of 1..8 ints, each ``0 <= rank < group``; ``field`` None, 'peak' or 'power'."""
+    (group,) = _ints(group=group)
+    if not 2 <= group <= HOLD_GROUP_MAX:
+        raise ValueError(f"group must be 2..{HOLD_GROUP_MAX}")
+    if isinstance(ranks, (str, bytes)) or not hasattr(ranks, "__len__") or not 1 <= len(ranks) <= HOLD_Q_MAX:
+        raise ValueError(f"ranks must be a sequence of 1..{HOLD_Q_MAX} ints")
+    for v in ranks:
+        if not _is_int(v) or not 0 <= int(v) < group:
+            raise ValueError(f"a rank must be an int in 0..{group - 1}")
+    _field(field)
+    return tuple(int(v) for v in ranks), group
+
+
+def holds_of_rows(points, ranks, group: int, field=None):
+    """The percentile traces of float32 ``points`` [R,16384] -- or, with ``field`` 'peak' or 'power', of that float of the
+    records [R,16384,2] -- over groups of ``group`` consecutive rows: float32 [R // group, q, 16384], one row per group and
+    entry of ``ranks``.  The numpy mirror of sa_hold_f32 (include/specan_hold.h):
+
+    - key: the float's bits with the sign cleared, as a uint32 -- +inf above every finite value, a NaN above +inf, -0.0 as
+      +0.0, denormals kept;
+    - ``s = np.sort`` of the ``group`` keys of a bin in a group, ascending along the frames; the result is ``s[ranks[j]]`` as
+      float bits: rank 0 is the min hold, rank ``group - 1`` the max hold, rank ``(group - 1) // 2`` the lower median
+      (:func:`rank_of_quantile` gives the rank of a quantile).
+
+    ``group`` is an int in 2..128; ``ranks`` a sequence of 1..8 ints, each ``0 <= rank < group``, in any order, repeats
+    allowed; the integers are ints (no bool, no float): ValueError otherwise, on rows that are no multiple of ``group`` and
+    on a wrong dtype or shape."""
+    ranks, group = _hold_args(ranks, group, field)
+    keys = _key(_points(points, field))
+    if keys.shape[0] % group:
+        raise ValueError(f"the rows ({keys.shape[0]}) must be a multiple of {group}")
+    s = np.sort(keys.reshape(keys.shape[0] // group, group, FFT_SIZE), axis=1)
+    return np.ascontiguousarray(s[:, list(ranks)]).view(np.float32)
+
+
 HIST_LEVELS_MAX = 64
 HIST_BUCKETS = (1, 2, 4, 8, 16, 32, 64)
 HIST_GROUP_MAX = 1 << 24
