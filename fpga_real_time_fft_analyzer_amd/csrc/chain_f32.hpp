@@ -352,10 +352,18 @@ __device__ __forceinline__ void pin_consts(const SecConsts &c)
 #define SA_STAMP_SEC(i) do {} while (0)
 #define SA_STAMP_FFT(i) SA_STAMP(i)
 #endif
+// ScanLane: what a lane's scan reads need and every section would compute again, formed once in iir_cascade --
+struct ScanLane {
+    unsigned own;         // LDS address of this lane's row total in section 0's scratch (section S: + 128 S, the offset field)
+    unsigned prev;        // ... of row (row - 1) & 15's total
+    unsigned mine;        // ... of row (lane & 15)'s total
+    unsigned lanep;       // ... of the lane's matrix P2^(lane & 15) of section 0 (section S: + 256 S)
+    unsigned src;         // ds_bpermute byte index of lane (lane & 48) | ((row - 1) & 15)
+    int t;                // the thread index, for the two lane predicates
+};
 template <bool PREDICT_NEXT, bool UNIT, int SIDX, typename SecT>
 __device__ __forceinline__ void iir_section(v2f (&d)[32], const SecT &k, const SecT &knext, const SecConsts c,
-                                            SecConsts &cn, const float4 *lanep_lds, float2 *scr_s, int lane, int wave,
-                                            v2f &zA, v2f &zB)
+                                            SecConsts &cn, const ScanLane sl, v2f &zA, v2f &zB)
 {
     SA_STAMP_SEC(3);
     // state after both chunks of this thread, from zero state: T = Pc zA + zB
@@ -367,8 +375,7 @@ __device__ __forceinline__ void iir_section(v2f (&d)[32], const SecT &k, const S
     if (!(flags & 2)) scan_level<2>(T, k.plev[1]);
     if (!(flags & 4)) scan_level<4>(T, k.plev[2]);
     if (!(flags & 8)) scan_level<8>(T, k.plev[3]);
-    const int row = 4 * wave + (lane >> 4);
-    if ((lane & 15) == 15) scr_s[row] = make_float2(T.x, T.y);
+    if ((sl.t & 15) == 15) *(__attribute__((address_space(3))) v2f *)(size_t)(sl.own + 128u * SIDX) = T;
     const v2f e = {row_shr<1>(T.x), row_shr<1>(T.y)};            // exclusive: state before this thread, row-local
     SA_STAMP_SEC(4);
     lds_barrier();
@@ -376,23 +383,20 @@ __device__ __forceinline__ void iir_section(v2f (&d)[32], const SecT &k, const S
     v2f cst;
     if (flags & SA_IIR_SKIP_ROWSCAN) {
         // a row (1024 samples) outlasts the section's memory: the row starts from the previous row's total
-        const float2 tt = scr_s[(row - 1) & 15];
-        cst = v2f{tt.x, tt.y};
+        cst = lds_at<v2f>(sl.prev + 128u * SIDX);
     } else {
         // scan over the 16 row totals (every row of every wave repeats it: 16 lanes, 4 DPP levels)
-        const float2 tt = scr_s[lane & 15];
-        v2f r = {tt.x, tt.y};
+        v2f r = lds_at<v2f>(sl.mine + 128u * SIDX);
         scan_level<1>(r, k.prow[0]);
         scan_level<2>(r, k.prow[1]);
         scan_level<4>(r, k.prow[2]);
         scan_level<8>(r, k.prow[3]);
         // state at the start of this lane's row = inclusive result of the previous row
-        const int src = (lane & 48) | ((row - 1) & 15);
-        cst = v2f{lane_get(r.x, src), lane_get(r.y, src)};
+        cst = v2f{lane_get_at(r.x, sl.src), lane_get_at(r.y, sl.src)};
     }
-    if (row == 0) cst = v2f{0.f, 0.f};
+    if (sl.t < 16) cst = v2f{0.f, 0.f};                   // row 0
     // start state of chunk A: row-local part + P2^i * (row start state); chunk B: Pc sA + zA
-    const float4 lanep = *lanep_lds;                     // read behind this section's barrier (the copy of section 0 is then visible)
+    const f4v lanep = lds_at<f4v>(sl.lanep + 256u * SIDX);   // read behind this section's barrier (the copy of section 0 is then visible)
     const v2f aS = mv_v(v2f{lanep.x, lanep.y}, v2f{lanep.z, lanep.w}, cst, e);
     const v2f bS = mv_s(c.pc0, c.pc1, aS, zA);
     // pole coordinates -> DF2T states of the recursion (sa_common.hpp), re-paired as (chunk A, chunk B)
@@ -437,17 +441,14 @@ __device__ __forceinline__ void iir_section(v2f (&d)[32], const SecT &k, const S
 // through control-flow merges and cost ~190 register copies.
 template <int S, int NSEC, bool UNIT, typename PlanT>
 __device__ __forceinline__ void iir_sections(v2f (&d)[32], const PlanT &ka, const SaIirLaneTab *__restrict__ lt,
-                                             float2 *scr, int lane, int wave, v2f &zA, v2f &zB, const SecConsts c)
+                                             const ScanLane sl, v2f &zA, v2f &zB, const SecConsts c)
 {
     if constexpr (S < NSEC) {
         // the per-lane matrices sit in LDS (iir_cascade copies them once): a 64-bit global address per thread held through
         // the whole cascade was among the values the tightest variants spilled
-        const float4 *lanep = reinterpret_cast<const float4 *>(reinterpret_cast<const unsigned char *>(scr) + (kLaneOff - kScrOff)) +
-                              16 * S + (lane & 15);
         SecConsts cn = c;
-        iir_section<(S + 1 < NSEC), UNIT, S>(d, ka.sec[S], ka.sec[S + 1 < NSEC ? S + 1 : S], c, cn, lanep, scr + 16 * S, lane,
-                                          wave, zA, zB);
-        iir_sections<S + 1, NSEC, UNIT>(d, ka, lt, scr, lane, wave, zA, zB, cn);
+        iir_section<(S + 1 < NSEC), UNIT, S>(d, ka.sec[S], ka.sec[S + 1 < NSEC ? S + 1 : S], c, cn, sl, zA, zB);
+        iir_sections<S + 1, NSEC, UNIT>(d, ka, lt, sl, zA, zB, cn);
     }
 }
 
@@ -467,7 +468,16 @@ __device__ __forceinline__ void iir_cascade(v2f (&d)[32], const PlanT &ka, const
     v2f zA, zB;
     predict_chunk_ends(tp, v2f{ka.p16_0[0], ka.p16_0[1]}, v2f{ka.p16_0[2], ka.p16_0[3]}, d, zA, zB);
     pin_consts(c0);
-    iir_sections<0, NSEC, UNIT>(d, ka, lt, scr, t & 63, t >> 6, zA, zB, c0);
+    // the scan's lane addresses, once for all sections and opaque: left visible, every section forms them again (about
+    // ten integer instructions each) where it cannot spare the three registers
+    // (and from an opaque copy of the thread index, or the frame's other uses of lane & 15 and t >> 4 keep theirs beside these)
+    unsigned tc = (unsigned)t;
+    asm volatile("" : "+v"(tc));
+    const unsigned prow = ((tc >> 4) - 1u) & 15u, lo = tc & 15u, sb = lds_addr(scr);
+    ScanLane sl = {sb + 8u * (tc >> 4), sb + 8u * prow, sb + 8u * lo, sb + (unsigned)(kLaneOff - kScrOff) + 16u * lo,
+                   4u * ((tc & 48u) | prow), (int)tc};
+    asm volatile("" : "+v"(sl.own), "+v"(sl.prev), "+v"(sl.mine), "+v"(sl.lanep), "+v"(sl.src));
+    iir_sections<0, NSEC, UNIT>(d, ka, lt, sl, zA, zB, c0);
 }
 
 // Half-spectrum outputs (SA_OUT_MAG_HALF, SA_OUT_SPEC_HALF: the numpy.fft.rfft layout, rows of 8193 elements).  A row is
@@ -526,6 +536,40 @@ __device__ __forceinline__ int zrow_pos(int within, int row)
 }
 __device__ __forceinline__ int zpos_low(int q) { return zrow_pos(q, q >> 9); }
 __device__ __forceinline__ int zpos_partner(int w) { return zrow_pos(w, (4 + (w >> 9)) & 7); }
+
+// The ten reads of one split-step group and their wait, written out as single 8-byte reads with 16-bit offsets: left to the
+// compiler they pair up (ds_read2_b64), whose offsets reach 2040 bytes only, and every pair two rows away from its position
+// gets a base of its own.  Low members zk[e] at za + UP + 8 e (e < 4) and zb + ZB_OFF; partners zm[0] at zm0 + ZM0_OFF and
+// zm[e] at zm4 + DN + 8 (4 - e).
+// (!WRITTEN_OUT: the same reads left to the compiler.)
+template <bool WRITTEN_OUT, int UP, int ZB_OFF, int ZM0_OFF, int DN>
+__device__ __forceinline__ void split_reads(unsigned za, unsigned zb, unsigned zm0, unsigned zm4, cf (&zk)[5], cf (&zm)[5])
+{
+    if constexpr (!WRITTEN_OUT) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) zk[e] = lds_at<cf>(za + UP + 8 * e);
+        zk[4] = lds_at<cf>(zb + ZB_OFF);
+        zm[0] = lds_at<cf>(zm0 + ZM0_OFF);
+#pragma unroll
+        for (int e = 1; e < 5; ++e) zm[e] = lds_at<cf>(zm4 + DN + 8 * (4 - e));
+        return;
+    }
+    asm volatile("ds_read_b64 %0, %10 offset:%14\n\t"
+                 "ds_read_b64 %5, %12 offset:%16\n\t"
+                 "ds_read_b64 %1, %10 offset:%14+8\n\t"
+                 "ds_read_b64 %6, %13 offset:%17+24\n\t"
+                 "ds_read_b64 %2, %10 offset:%14+16\n\t"
+                 "ds_read_b64 %7, %13 offset:%17+16\n\t"
+                 "ds_read_b64 %3, %10 offset:%14+24\n\t"
+                 "ds_read_b64 %8, %13 offset:%17+8\n\t"
+                 "ds_read_b64 %4, %11 offset:%15\n\t"
+                 "ds_read_b64 %9, %13 offset:%17\n\t"
+                 "s_waitcnt lgkmcnt(0)"
+                 : "=&v"(zk[0]), "=&v"(zk[1]), "=&v"(zk[2]), "=&v"(zk[3]), "=&v"(zk[4]), "=&v"(zm[0]), "=&v"(zm[1]), "=&v"(zm[2]),
+                   "=&v"(zm[3]), "=&v"(zm[4])
+                 : "v"(za), "v"(zb), "v"(zm0), "v"(zm4), "n"(UP), "n"(ZB_OFF), "n"(ZM0_OFF), "n"(DN)
+                 : "memory");
+}
 
 // ---------------------------------------------------------------------------------------------
 // One frame: window -> IIR -> FFT -> split -> store.
@@ -752,19 +796,47 @@ __device__ __forceinline__ void chain_frame(const InT *__restrict__ in, const fl
     if constexpr (!AN5_EARLY) an5 = *at_bytes(twT + 5 * 256, 16u * (unsigned)ts);
     const cf wP = {an5.x, an5.y}, wPn = {an5.z, an5.w};
     MarkerAcc mk = {-1.f, SA_NPTS, 0.f};                   // SA_OUT_MARKER: this thread's part of the record
+    // The split step's read positions, as LDS byte addresses, the same in both rounds.  A group of four bins never straddles
+    // a padding or row boundary, so four positions serve the ten reads of a group: low members q0 + e at za + 8 e (e < 4)
+    // and zb; partners at zm0, zm4 + 24, zm4 + 16, zm4 + 8, zm4.  Group jj = 1 (q0 = 4 t + 1024) lies two image rows
+    // (kTwoRows bytes) above group jj = 0 for the low members and two rows below it for the partners, so each position is
+    // evaluated for the lower of the two groups and the other group's is its reads' offset field.
+    // Three reads leave that pattern, and each takes its address by a select here instead of its value by two selects in
+    // every round (and the side slots are read by the lanes that need them only):
+    //   t = 0, jj = 0: the partner of bin 2048 r is Z[8192] = Z[0], the image's first entry, in round 0 and Z[6144], not
+    //                  in round 1's image, in round 1 (side slot 0); the pattern's address is one row past the image
+    //   t = 255, jj = 1, round 0: bin 2048 is not in round 0's image (side slot 1).  Its partner Z[6144] is: the image
+    //                  holds the value that side slot 0 holds, at the pattern's address
+    constexpr int kTwoRows = 8 * 2 * 528;
+    // The 8-byte accesses of the natural-order image are written out one by one (below, split_reads) except in the one-round
+    // kernels: those sit at 127-128 registers, and with all ten reads of a group behind one wait the marker form spills one.
+    constexpr bool kWrittenOut = !ONE_ROUND;
+    const unsigned img = lds_addr(smem);
+    const unsigned za = img + 8u * (unsigned)zpos_low(4 * t), zb = img + 8u * (unsigned)zpos_low(4 * t + 4);
+    const unsigned zm0 = img + 8u * (unsigned)zpos_partner(1024 - 4 * t), zm4 = img + 8u * (unsigned)zpos_partner(1020 - 4 * t);
+    const unsigned zm0_r0 = t == 0 ? img : zm0 + kTwoRows, zm0_r1 = t == 0 ? img + (unsigned)kSideOff : zm0 + kTwoRows;
+    const unsigned zb_r0 = t == 255 ? img + (unsigned)kSideOff + 8u : zb + kTwoRows;
     // ---- natural-order image + split step, two rounds: round 0 = d in {0..3,12..15} (bins k < 2048
     //      and their partners), round 1 = d in {4..11}.  Z[2048] and Z[6144] sit on the seam and
     //      travel through two side slots.
 #pragma unroll
     for (int r = 0; r < 2; ++r) {
         lds_barrier();
+        // Z[k1 + 32 c + 512 d] at k1 + 33 c + 528 d', k1 = 16 q + 4 wave + kq: one address per thread, q and the row in the
+        // offset field.  Written out: the compiler pairs the 8-byte stores (ds_write2_b64), whose offsets reach 2040 bytes,
+        // and adds a base per row.  (kWrittenOut: not in the one-round kernels, see there)
+        {
+            const unsigned zw = img + 8u * (unsigned)(4 * wave + kq + 33 * lo);
 #pragma unroll
-        for (int q = 0; q < 2; ++q) {
-            const int k1 = 16 * q + 4 * wave + kq;
+            for (int q = 0; q < 2; ++q) {
 #pragma unroll
-            for (int dd = 0; dd < 8; ++dd) {
-                const int dsel = (r == 0) ? (dd < 4 ? dd : dd + 8) : dd + 4;
-                ldc[k1 + 33 * lo + 528 * dd] = p[q][dsel];
+                for (int dd = 0; dd < 8; ++dd) {
+                    const int dsel = (r == 0) ? (dd < 4 ? dd : dd + 8) : dd + 4;
+                    if constexpr (kWrittenOut)
+                        asm volatile("ds_write_b64 %0, %1 offset:%2" ::"v"(zw), "v"(p[q][dsel]), "n"(8 * (16 * q + 528 * dd)) : "memory");
+                    else
+                        ldc[16 * q + 4 * wave + kq + 33 * lo + 528 * dd] = p[q][dsel];
+                }
             }
         }
         if (r == 0 && t == 0) {                               // k1 = 0, c = 0: d = 12 and d = 4
@@ -795,18 +867,14 @@ __device__ __forceinline__ void chain_frame(const InT *__restrict__ in, const fl
                 const cf csel = (t == 255) ? cf{c1.x, c1.y} : cf{c0.x, c0.y};
                 w[4] = safft::cmul(wPn, csel);
             }
-            // a group of four bins never straddles a padding or row boundary, so four positions serve
-            // the ten reads: low members q0+e at pa+e (e<4) and pb; partners at pm0, pm4+3, pm4+2, pm4+1, pm4
-            const int pa = zpos_low(q0), pb = zpos_low(q0 + 4);
-            const int pm0 = zpos_partner(2048 - q0), pm4 = zpos_partner(2044 - q0);
-            cf zk[5] = {ldc[pa], ldc[pa + 1], ldc[pa + 2], ldc[pa + 3], ldc[pb]};
-            cf zm[5] = {ldc[pm0], ldc[pm4 + 3], ldc[pm4 + 2], ldc[pm4 + 1], ldc[pm4]};
-            // the seam pair (2048, 6144): Z[2048] is not in round 0's image, Z[6144] not in round 1's
-            if (r == 0 && q0 == 2044) {
-                zk[4] = side[1];
-                zm[4] = side[0];
-            }
-            if (r == 1 && q0 == 0) zm[0] = side[0];
+            // the ten reads (positions and the seam pair (2048, 6144): above the rounds)
+            cf zk[5], zm[5];
+            if (jj == 1 && r == 0)
+                split_reads<kWrittenOut, kTwoRows, 0, 0, 0>(za, zb_r0, zm0, zm4, zk, zm);
+            else if (jj == 1)
+                split_reads<kWrittenOut, kTwoRows, kTwoRows, 0, 0>(za, zb, zm0, zm4, zk, zm);
+            else
+                split_reads<kWrittenOut, 0, 0, 0, kTwoRows>(za, zb, r == 0 ? zm0_r0 : zm0_r1, zm4, zk, zm);
             cf R[5], I[5];
 #pragma unroll
             for (int e = 0; e < 5; ++e) split_eval(zk[e], zm[e], w[e], R[e], I[e]);

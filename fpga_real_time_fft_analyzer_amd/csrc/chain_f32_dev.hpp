@@ -71,6 +71,20 @@ __device__ __forceinline__ T *at_bytes(T *base, unsigned lane_bytes)
 // the wave index as the scalar it is (the compiler takes threadIdx.x >> 6 for a per-lane value)
 __device__ __forceinline__ int uniform_wave(int wave) { return __builtin_amdgcn_readfirstlane(wave); }
 
+// LDS positions as the 32-bit byte addresses they are.  An address computed once (lds_addr + the lane's part) and kept
+// serves every access that differs from it by a compile-time constant through the access's 16-bit offset field; formed as
+// pointer + index each access adds the image's base to a fresh index again.
+__device__ __forceinline__ unsigned lds_addr(const void *p)
+{
+    return (unsigned)(size_t)(const __attribute__((address_space(3))) unsigned char *)(p);
+}
+template <typename T>                                          // T: float or a vector of floats (cf, v2f, f4v)
+__device__ __forceinline__ T lds_at(unsigned addr)
+{
+    return *(const __attribute__((address_space(3))) T *)(size_t)(addr);
+}
+typedef float f4v __attribute__((ext_vector_type(4)));
+
 // ---------------------------------------------------------------------------------------------
 // DPP helpers: value of the lane `n` to the left inside the 16-lane row, 0 when there is none.
 template <int N>
@@ -79,9 +93,10 @@ __device__ __forceinline__ float row_shr(float v)
     return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x110 + N, 0xF, 0xF, true));
 }
 
-__device__ __forceinline__ float lane_get(float v, int src_lane)
+// the value of another lane of the wave; src_bytes = 4 * that lane, as ds_bpermute takes it
+__device__ __forceinline__ float lane_get_at(float v, unsigned src_bytes)
 {
-    return __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(src_lane << 2, __builtin_bit_cast(int, v)));
+    return __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute((int)src_bytes, __builtin_bit_cast(int, v)));
 }
 
 // Output stores are streaming: every byte is written once and not read by this launch.  Marked
@@ -121,11 +136,12 @@ __device__ __forceinline__ void dma_rows_impl(const T *x, int h, unsigned char *
     constexpr int kRow = 64 * (int)sizeof(T);
     const int rl = lane >> 3;
     const unsigned v0 = (unsigned)(rl * kRow + (((lane & 7) ^ (rl >> 1)) << 4)), v1 = v0 ^ 64u;
-    const T *xw = x + uniform_wave(wave) * (64 * 64) + h * 32;
+    const int uw = uniform_wave(wave);                         // the slabs' LDS bases are scalar adds on it, as the sources are
+    const T *xw = x + uw * (64 * 64) + h * 32;
     __builtin_amdgcn_s_setprio(3);
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
-        const int n = wave * 8 + i;                            // slab: rows 8n .. 8n+7
+        const int n = uw * 8 + i;                              // slab: rows 8n .. 8n+7
         const T *src = at_bytes(xw + i * (8 * 64), (i & 1) ? v1 : v0);
         __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)src,
                                          (__attribute__((address_space(3))) void *)(smem + n * 1024), 16, 0, SA_DMA_AUX);
@@ -166,7 +182,7 @@ __device__ __forceinline__ void dma_rows(const SaP12 *x, unsigned char *smem, in
     __builtin_amdgcn_s_setprio(3);
 #pragma unroll
     for (int i = 0; i < 6; ++i) {
-        const int n = wave * 6 + i;                            // slab: slots 64n .. 64n+63
+        const int n = uw * 6 + i;                              // slab: slots 64n .. 64n+63
         const int s = 64 * n + lane;                           // the slot this lane fills, of row s / 6
         // unit u = s ^ swizzle = 64 n + (lane ^ swizzle): the slab's KiB is wave-uniform, the lane's part 16 (lane ^ swizzle)
         const unsigned v = (unsigned)((lane ^ p12_row_swizzle(s / 6)) << 4);
